@@ -7,6 +7,7 @@ stretch-move step = 2 half-ensemble updates = 1024 log-posterior evaluations.  M
 ensemble are resident in HBM before the timed region; the chain is kept on the device.
 
     python bench.py [--gpus N --steps K --warmup W]        (N > 1: starts its N ranks itself, as child processes)
+    python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR      (also writes the last timed step's outputs)
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...   (N > 1, launcher environment)
 
 With N > 1 the SAME 1024 walkers are sharded over the ranks (strong scaling): each rank evaluates
@@ -20,6 +21,12 @@ launch) / its mean launch duration measured with HIP events in a second pass of 
 (`achieved` / `frac`); `step_achieved` / `step_frac` is SURVEY 8(d)'s own definition for the whole step:
 evaluations per second x FLOP_eval (1.02e7 at C3) / peak -- the kernels around the GEMM count against it.
 `cpu_baseline` times the CPU oracle (reference-form per-walker log_posterior) on this host.
+
+--dump-outputs DIR (one GPU): after the K timed steps, what the timed path computed in its last step -- the chain row a
+caller of DeviceSampler.run / get_chain receives -- is written as DIR/chain_last.npy (walkers x d) and
+DIR/log_prob_last.npy (walkers), float64.  The timed chain starts from the seeded ensemble and random stream whatever
+the time-based pre-warm did (the sampler's state is snapshot before it and restored after it), so with the same
+arguments the outputs of two builds can be compared element for element.
 """
 from __future__ import annotations
 
@@ -501,7 +508,12 @@ def main():
     ap.add_argument("--emulate-world", type=int, default=0,
                     help="diagnostic: time ONE rank's share of an N-GPU step on this GPU (world-1 RCCL gather); "
                          "the printed value is NOT a throughput claim")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's chain row and log-probabilities as DIR/<name>.npy (float64); "
+                         "one GPU only")
     args = ap.parse_args()
+    if args.dump_outputs and args.gpus > 1:
+        ap.error("--dump-outputs needs --gpus 1: a sharded pre-warm cannot be undone, so its outputs would not repeat")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and not args.emulate_world:
         sys.exit(self_launch(args))
@@ -527,7 +539,8 @@ def main():
             dist.init_process_group(backend, rank=rank, world_size=world)
     coll_dev = "cuda" if (not dist.is_initialized() or dist.get_backend() == "nccl") else "cpu"
 
-    from gpemu import synthetic
+    from gpemu import _lib, synthetic
+    from gpemu._lib import check
     from gpemu.model import DeviceModel
     from gpemu.sampler import DeviceSampler
 
@@ -553,7 +566,12 @@ def main():
         return bool(int(t.item()))
 
     def timed_pass(ds, n_walkers, transport):
-        """Pre-warm, W warm-up steps, then EXACTLY K timed steps between barrier + synchronize; max over ranks."""
+        """Pre-warm, W warm-up steps, then EXACTLY K timed steps between barrier + synchronize; max over ranks.
+        One GPU: the pre-warm runs for a time, not a number of steps, so the sampler is put back to its state before it
+        (ensemble, counters, random stream) and the W + K steps are the same steps in every run."""
+        rewind = world == 1
+        if rewind:
+            check(_lib.lib().gpemu_sampler_snapshot(ds._h))
         def run(steps, store=True):
             if args.emulate_world:
                 ds.run_sharded(steps, store=store, force=True, emulate_world=args.emulate_world)
@@ -575,6 +593,8 @@ def main():
                 go = bool(int(flag.item()))
             if not go:
                 break
+        if rewind:
+            check(_lib.lib().gpemu_sampler_restore(ds._h))
         run(args.warmup)
         barrier()
         t0 = time.perf_counter()
@@ -585,8 +605,13 @@ def main():
             tt = torch.tensor([dt], dtype=torch.float64, device=coll_dev)
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
             dt = float(tt.item())
+        outputs = None
+        if args.dump_outputs:
+            _, _, chain_len = ds.counts()
+            chain, lp = ds.get_chain(first=chain_len - 1, n=1)
+            outputs = {"chain_last": chain[0], "log_prob_last": lp[0]}
         return {"ms_per_step": dt / args.steps * 1e3, "value": n_walkers * args.steps / dt, "seconds": dt,
-                "transport_taken": ds.last_transport or "single", "run": run}
+                "transport_taken": ds.last_transport or "single", "run": run, "outputs": outputs}
 
     def measure(n_walkers, seed):
         """One ensemble of `n_walkers`, every requested transport timed on it.  Returns (sampler, results, best)."""
@@ -623,6 +648,10 @@ def main():
         raise SystemExit(1)
     headline = results[best]
     run = headline["run"]
+    if args.dump_outputs and rank == 0:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, arr in headline["outputs"].items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), np.ascontiguousarray(arr, dtype=np.float64))
 
     # second pass of the same K steps with HIP events around every launch of the hot kernels
     dm.profile(True)
@@ -662,7 +691,7 @@ def main():
                     "n_walkers": N_WALKERS * world, "transport": wbest,
                     "value": wres[wbest]["value"] if wbest else None,
                     "ms_per_step": wres[wbest]["ms_per_step"] if wbest else None,
-                    "transports": {t: {k: v for k, v in r.items() if k != "run"} for t, r in wres.items()}}
+                    "transports": {t: {k: v for k, v in r.items() if k not in ("run", "outputs")} for t, r in wres.items()}}
             dsw.close()
         except Exception as e:
             weak = {"error": repr(e)}
@@ -731,7 +760,7 @@ def main():
                           "n_walkers": N_WALKERS, "evals_per_step": N_WALKERS,
                           "parallelism": f"walkers sharded over {world} GPU(s)"},
                "transport": headline["transport_taken"],
-               "transports": {t: {k: v for k, v in r.items() if k != "run"} for t, r in results.items()},
+               "transports": {t: {k: v for k, v in r.items() if k not in ("run", "outputs")} for t, r in results.items()},
                "ranks_seen": ranks_seen,
                "peer_selftest_per_rank": tinfo.get("peer_selftest_per_rank"),
                "fallback_vote": {"peer_to_collective": bool(tinfo.get("fallback_from_peer", False)),
