@@ -5,6 +5,7 @@
 
 #include "internal.h"
 #include "kstar_host.h"
+#include "matern_dev.h"
 #include "gemm.h"
 #include "linalg_dev.h"
 
@@ -165,7 +166,7 @@ int logpost_groups(gpemu_model *const *ms, int ng, int64_t B, double *dXq, doubl
     const gpemu_model *m = ms[g];
     if (!m->lik_ready) { set_error("gpemu_likelihood_setup has not been called"); return GPEMU_ERR_STATE; }
     const int64_t Bv = m->variant_B > 0 ? m->variant_B : B;
-    if (Bv > 128 || m->k > 32 || m->d != ms[0]->d || kstar_kind(m) != kstar_kind(ms[0]) || m->ksteps != ms[0]->ksteps ||
+    if (Bv > 128 || m->k > 32 || m->d != ms[0]->d || !kstar_same_kernel(m, ms[0]) || m->ksteps != ms[0]->ksteps ||
         m->device != ms[0]->device || m->profiling)
       return GPEMU_ERR_UNSUPPORTED;
   }
@@ -258,8 +259,7 @@ int gpemu_model_create(gpemu_model **out, int device, int64_t N, int64_t d, int6
   GP_ARG(d <= DPAD, "d > 8 parameters is not supported by this build");
   GP_ARG(k <= 64, "k > 64 principal components is not supported by this build");
   GP_ARG(kernel_kind == GPEMU_KERNEL_RBF || kernel_kind == GPEMU_KERNEL_MATERN, "kernel_kind");
-  if (kernel_kind == GPEMU_KERNEL_MATERN)
-    GP_ARG(nu == 0.5 || nu == 1.5 || nu == 2.5, "Matern nu must be 0.5, 1.5 or 2.5");
+  if (kernel_kind == GPEMU_KERNEL_MATERN) GP_ARG(nu > 0.0, "Matern nu must be > 0 (finite or +inf; not NaN)");
   GP_ARG(X_train && ls && alpha && L && components && scaler_mean && scaler_scale, "null array");
   GP_ARG(!has_const || constv, "constv");
   GP_ARG(!has_noise || noise, "noise");
@@ -292,9 +292,11 @@ int gpemu_model_create(gpemu_model **out, int device, int64_t N, int64_t d, int6
   }
   hipStream_t st = m->stream;
 
-  // host staging of the small padded arrays
-  const bool matern05 = kernel_kind == GPEMU_KERNEL_MATERN && nu == 0.5;
-  std::vector<double> hXs(matern05 ? (size_t)(k * Np * DPAD) : 0, 0.0), hls((size_t)(k * DPAD), 1.0),
+  // host staging of the small padded arrays; `direct`: the kernels whose value is not flat at r = 0 (Matern 0.5, general
+  // nu < 1) recompute the distance of near-coincident pairs from the coordinates (predict_dev.h: KstarDirect)
+  const int kkind = kstar_kind(m);
+  const bool direct = kkind == 1 || (kkind == 4 && nu < 1.0);
+  std::vector<double> hXs(direct ? (size_t)(k * Np * DPAD) : 0, 0.0), hls((size_t)(k * DPAD), 1.0),
       hc((size_t)k, 0.0), hkd((size_t)k, 1.0), hal((size_t)(k * Np), 0.0);
   for (int64_t p = 0; p < k; ++p) {
     for (int64_t dd = 0; dd < d; ++dd) {
@@ -302,7 +304,7 @@ int gpemu_model_create(gpemu_model **out, int device, int64_t N, int64_t d, int6
       if (!(l > 0.0)) { set_error("length scale must be positive"); return fail(GPEMU_ERR_ARG); }
       hls[p * DPAD + dd] = l;
     }
-    if (matern05)
+    if (direct)
       for (int64_t j = 0; j < N; ++j)
         for (int64_t dd = 0; dd < d; ++dd)
           hXs[(p * Np + j) * DPAD + dd] = X_train[j * d + dd] / ls[p * d + dd];  // skl: X / length_scale
@@ -325,7 +327,13 @@ int gpemu_model_create(gpemu_model **out, int device, int64_t N, int64_t d, int6
   {
     // the cross-kernel's operands for the matrix cores (kstar_host.h)
     KstarHost kh;
-    build_kstar_operands(N, Np, d, k, kstar_kind(m), X_train, ls, alpha, kh);
+    build_kstar_operands(N, Np, d, k, kkind, X_train, ls, alpha, kh);
+    if (kkind == 4) {   // the constants of nu behind the exponential's table (predict_dev.h: kstar_matern_nu)
+      const MaternNu mn = matern_nu_constants(nu);
+      const size_t n0 = kh.tab.size(), nw = (sizeof(MaternNu) + sizeof(double) - 1) / sizeof(double);
+      kh.tab.resize(n0 + nw, 0.0);
+      std::memcpy(kh.tab.data() + n0, &mn, sizeof(MaternNu));
+    }
     m->ksteps = kh.ksteps;
     GP_STEP(dev_alloc(&m->Xa, (int64_t)kh.Xa.size()));
     GP_STEP(dev_alloc(&m->alf, (int64_t)kh.alf.size()));
@@ -338,7 +346,7 @@ int gpemu_model_create(gpemu_model **out, int device, int64_t N, int64_t d, int6
     GP_STEP(upload(m->qof, kh.qof.data(), (int64_t)kh.qof.size(), st));
     GP_STEP(upload(m->etab, kh.tab.data(), (int64_t)kh.tab.size(), st));
     std::vector<double> hinv(hls.size());
-    if (matern05) {
+    if (direct) {
       for (size_t i = 0; i < hls.size(); ++i) hinv[i] = 1.0 / hls[i];
       GP_STEP(dev_alloc(&m->Xs, k * Np * DPAD));
       GP_STEP(dev_alloc(&m->inv_ls, k * DPAD));

@@ -1,6 +1,7 @@
 // Internal declarations shared by the translation units of libgpemu.so (gfx950 only).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -96,8 +97,8 @@ struct gpemu_model {
   double *alf = nullptr;       // [k][Npad/16][16]          alpha in accumulator-row order
   double *qsc = nullptr;       // [k][4 ksteps]             query side: q' = q qsc + qof
   double *qof = nullptr;
-  double *etab = nullptr;      // [2^KSTAR_TB]              2^(j / 2^KSTAR_TB)
-  // Matern-0.5 only (the direct distance of near-coincident pairs): row-major scaled rows, else null
+  double *etab = nullptr;      // [2^KSTAR_TB]              2^(j / 2^KSTAR_TB)  (kind 4: + the MaternNu of nu)
+  // Matern-0.5 and general nu < 1 only (the direct distance of near-coincident pairs): row-major scaled rows, else null
   double *Xs = nullptr;        // [k][Npad][DPAD]  X_train / ls_p  (padded rows/dims = 0)
   double *inv_ls = nullptr;    // [k][DPAD]        1 / ls (the query side multiplies; the training side X / ls is exact)
   double *ls = nullptr;        // [k][DPAD]        length scales (padded dims = 1)
@@ -181,10 +182,19 @@ struct ProposeArgs {
 };
 
 int ensure_workspace(gpemu_model *m, int64_t B);
-// base kernel of the cross-kernel templates: 0 RBF, 1 / 2 / 3 Matern 0.5 / 1.5 / 2.5
+// base kernel of the cross-kernel templates: 0 RBF (and Matern nu = inf, skl kernels.py:1722-1723), 1 / 2 / 3 Matern
+// 0.5 / 1.5 / 2.5 (closed forms), 4 Matern of any other nu (matern_dev.h; its constants behind etab's table)
 static inline int kstar_kind(const gpemu_model *m) {
-  if (m->kernel_kind != GPEMU_KERNEL_MATERN) return 0;
-  return (m->nu == 0.5) ? 1 : (m->nu == 1.5 ? 2 : 3);
+  if (m->kernel_kind == GPEMU_KERNEL_RBF) return 0;
+  if (m->nu == 0.5) return 1;
+  if (m->nu == 1.5) return 2;
+  if (m->nu == 2.5) return 3;
+  if (m->nu == INFINITY) return 0;
+  return 4;
+}
+// two models whose cross-kernels can share one launch: the same base kernel (and, for kind 4, the same nu)
+static inline bool kstar_same_kernel(const gpemu_model *a, const gpemu_model *b) {
+  return kstar_kind(a) == kstar_kind(b) && (kstar_kind(a) != 4 || a->nu == b->nu);
 }
 
 // kernels (launchers; all asynchronous on `st`)

@@ -22,6 +22,7 @@
 
 #include "gemm.h"
 #include "internal.h"
+#include "matern_dev.h"
 
 namespace gpemu {
 
@@ -78,6 +79,47 @@ __global__ __launch_bounds__(256) void kmat_kernel(const double *__restrict__ X,
         r2 = fma(df, df, r2);
       }
       v = base_from_r2(kind, r2) + cst;
+    }
+    K[(int64_t)i * Np + j] = v;
+  }
+}
+
+// kind 4 (Matern, general nu: matern_dev.h): kmat_kernel with the general value -- a kernel of its own, so that the
+// instance that serves kinds 0-3 keeps its code
+__global__ __launch_bounds__(256) void kmat_nu_kernel(const double *__restrict__ X, const double *__restrict__ hp,
+                                                      double *__restrict__ K, int N, int Np, MaternNu mn, double jitter) {
+  __shared__ double s_xi[KMAT_ROWS][DPAD];
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  const int i0 = blockIdx.y * KMAT_ROWS;
+  hp += (int64_t)blockIdx.z * (DPAD + 2);
+  K += (int64_t)blockIdx.z * Np * Np;
+  // skl: X / length_scale, then the difference -- the quotients are the same numbers whoever forms them
+  if (threadIdx.x < KMAT_ROWS * DPAD) {
+    const int r = threadIdx.x / DPAD, dd = threadIdx.x % DPAD;
+    s_xi[r][dd] = (i0 + r < N) ? X[(i0 + r) * DPAD + dd] / hp[dd] : 0.0;
+  }
+  double xj[DPAD];
+#pragma unroll
+  for (int dd = 0; dd < DPAD; ++dd) xj[dd] = (j < N) ? X[j * DPAD + dd] / hp[dd] : 0.0;
+  const double cst = hp[DPAD], diag = 1.0 + hp[DPAD] + hp[DPAD + 1] + jitter;   // np.fill_diagonal(K, 1) + const + noise + alpha
+  __syncthreads();
+  if (j >= Np) return;
+  for (int r = 0; r < KMAT_ROWS; ++r) {
+    const int i = i0 + r;
+    if (i >= Np) break;
+    double v;
+    if (i >= N || j >= N) {
+      v = (i == j) ? 1.0 : 0.0;
+    } else if (i == j) {
+      v = diag;
+    } else {
+      double r2 = 0.0;
+#pragma unroll
+      for (int dd = 0; dd < DPAD; ++dd) {
+        const double df = s_xi[r][dd] - xj[dd];
+        r2 = fma(df, df, r2);
+      }
+      v = matern_nu_value(mn, sqrt(r2)) + cst;
     }
     K[(int64_t)i * Np + j] = v;
   }
@@ -1115,6 +1157,69 @@ __global__ __launch_bounds__(256) void lml_grad_kernel(const double *__restrict_
   }
 }
 
+// kind 4: lml_grad_kernel with the general-nu derivative (matern_dev.h: matern_nu_value_grad), a kernel of its own
+__global__ __launch_bounds__(256) void lml_grad_nu_kernel(const double *__restrict__ X, const double *__restrict__ hp,
+                                                          const double *__restrict__ alpha,
+                                                          const double *__restrict__ Kinv, int64_t ld,
+                                                          double *__restrict__ gpart, int N, int d, MaternNu mn,
+                                                          int has_const, int has_noise) {
+  __shared__ double red[NTH_MAX][4];
+  // 1-D grid over the (row group, 256-column block) pairs that reach under the diagonal only (half of the full grid's
+  // workgroups would start to find nothing to do): row groups 16 b .. 16 b + 15 have b + 1 blocks, so position
+  // t = (b + 1)(8 b + r) + x  <->  row group 16 b + r, block x
+  int b = (int)((sqrt(1.0 + 0.5 * (double)blockIdx.x) - 1.0) * 0.5);
+  while (8 * b * (b + 1) > (int)blockIdx.x) --b;
+  while (8 * (b + 1) * (b + 2) <= (int)blockIdx.x) ++b;
+  const int rem = (int)blockIdx.x - 8 * b * (b + 1);
+  const int by = 16 * b + rem / (b + 1), bx = rem % (b + 1);
+  const int l = bx * blockDim.x + threadIdx.x;
+  const int j0 = by * GRAD_ROWS;                       // this workgroup's rows j0 .. j0 + GRAD_ROWS - 1 (one reduction for all)
+  hp += (int64_t)blockIdx.z * (DPAD + 2);              // blockIdx.z: problem of a batch
+  alpha += (int64_t)blockIdx.z * ld;
+  Kinv += (int64_t)blockIdx.z * ld * ld;
+  gpart += (int64_t)blockIdx.z * gridDim.x * NTH_MAX;
+  double acc[NTH_MAX];
+#pragma unroll
+  for (int t = 0; t < NTH_MAX; ++t) acc[t] = 0.0;
+  double xl[DPAD], il2[DPAD];
+#pragma unroll
+  for (int dd = 0; dd < DPAD; ++dd) {
+    xl[dd] = (l < N) ? X[l * DPAD + dd] : 0.0;
+    il2[dd] = 1.0 / (hp[dd] * hp[dd]);      // once per thread; a division per pair and dimension was 4/5 of this kernel
+  }
+  const double al = (l < N) ? alpha[l] : 0.0;
+  // the summand is symmetric in (j, l): the lower triangle counts twice, Kinv is only read (and only valid) there
+  for (int j = j0; j < j0 + GRAD_ROWS && j < N; ++j) {
+    if (l > j) continue;
+    const double wgt = (l < j ? 2.0 : 1.0) * (alpha[j] * al - Kinv[(int64_t)j * ld + l]);
+    double D[DPAD], r2 = 0.0;
+#pragma unroll
+    for (int dd = 0; dd < DPAD; ++dd) {
+      double df = X[j * DPAD + dd] - xl[dd];
+      D[dd] = (df * df) * il2[dd];             // (x - x')^2 / l^2   (skl kernels.py:1574, 1748)
+      r2 += D[dd];
+    }
+    double f;  // dK_base/dlog l_dd = f * D[dd]: analytic (skl: forward difference, kernels.py:1767-1774)
+    (void)matern_nu_value_grad(mn, sqrt(r2), f);
+#pragma unroll
+    for (int dd = 0; dd < DPAD; ++dd) acc[dd] += 0.5 * wgt * f * D[dd];
+    if (has_const) acc[d] += 0.5 * wgt * hp[DPAD];
+    if (has_noise && j == l) acc[d + has_const] += 0.5 * wgt * hp[DPAD + 1];
+  }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int t = 0; t < NTH_MAX; ++t) {
+    double s = acc[t];
+    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
+    if (lane == 0) red[t][wave] = s;
+  }
+  __syncthreads();
+  if (threadIdx.x < NTH_MAX) {
+    const int t = threadIdx.x;
+    gpart[(int64_t)blockIdx.x * NTH_MAX + t] = (red[t][0] + red[t][1]) + (red[t][2] + red[t][3]);
+  }
+}
+
 // two-stage deterministic sum of the partial gradients: GR_BLOCKS workgroups each sum a contiguous slice ...
 constexpr int GR_BLOCKS = 128;
 __global__ __launch_bounds__(256) void grad_reduce_stage1_kernel(const double *__restrict__ gpart, int nparts,
@@ -1200,7 +1305,8 @@ int device_invert_factor_to_Wt(const double *dL, int64_t N, double *Wt, int64_t 
 struct gpemu_fit {
   int device = 0;
   int64_t N = 0, d = 0, Np = 0;
-  int kind = 0, has_const = 0, has_noise = 0;
+  int kind = 0, has_const = 0, has_noise = 0;   // kind: fit_kind_of
+  gpemu::MaternNu mnu{};           // kind 4: the constants of nu (matern_dev.h)
   double jitter = 0.0;
   hipStream_t stream = nullptr;
   gpemu::CholOverlap overlap;      // side stream + events of the Cholesky look-ahead
@@ -1220,9 +1326,23 @@ using namespace gpemu;
     if (rc__ != GPEMU_OK) return rc__; \
   } while (0)
 
-static int kind_of(int kernel_kind, double nu) {
+// 0 RBF (and Matern nu = inf: skl kernels.py:1722-1723, exp(-d^2 / 2)), 1 / 2 / 3 Matern 0.5 / 1.5 / 2.5 (closed forms),
+// 4 Matern of any other nu (matern_dev.h)
+static int fit_kind_of(int kernel_kind, double nu) {
   if (kernel_kind == GPEMU_KERNEL_RBF) return 0;
-  return nu == 0.5 ? 1 : (nu == 1.5 ? 2 : 3);
+  if (nu == 0.5) return 1;
+  if (nu == 1.5) return 2;
+  if (nu == 2.5) return 3;
+  if (nu == INFINITY) return 0;
+  return 4;
+}
+
+static void launch_kmat(const gpemu_fit *f, int64_t N, int nb, double jitter, hipStream_t st) {
+  const dim3 grid((unsigned)((f->Np + 255) / 256), (unsigned)((f->Np + KMAT_ROWS - 1) / KMAT_ROWS), (unsigned)nb);
+  if (f->kind == 4)
+    hipLaunchKernelGGL(kmat_nu_kernel, grid, dim3(256), 0, st, f->X, f->hp, f->K, (int)N, (int)f->Np, f->mnu, jitter);
+  else
+    hipLaunchKernelGGL(kmat_kernel, grid, dim3(256), 0, st, f->X, f->hp, f->K, (int)N, (int)f->Np, f->kind, jitter);
 }
 
 // workspace for `nb` problems evaluated together (one set of matrices each)
@@ -1274,8 +1394,7 @@ static int fit_eval_batch(gpemu_fit *f, int nb, const double *ys, const double *
   GP_HIP(hipMemcpyAsync(f->hp, hp.data(), sizeof(double) * hp.size(), hipMemcpyHostToDevice, st));
   GP_HIP(hipMemcpyAsync(f->y, hy.data(), sizeof(double) * hy.size(), hipMemcpyHostToDevice, st));
   GP_HIP(hipMemsetAsync(f->info, 0, sizeof(int) * nb, st));
-  hipLaunchKernelGGL(kmat_kernel, dim3((unsigned)((Np + 255) / 256), (unsigned)((Np + KMAT_ROWS - 1) / KMAT_ROWS), (unsigned)nb), dim3(256), 0, st, f->X,
-                     f->hp, f->K, (int)N, (int)Np, f->kind, f->jitter);
+  launch_kmat(f, N, nb, f->jitter, st);
   GP_HIP(hipGetLastError());
   // look-ahead (with the one-launch panels only; it gained nothing over the three-launch steps, whose narrow kernels
   // slowed down by what the overlap won: profiles/r03_chol_lookahead.txt); GPEMU_CHOL_LOOKAHEAD=0 switches it off
@@ -1310,8 +1429,12 @@ static int fit_eval_batch(gpemu_fit *f, int nb, const double *ys, const double *
     int npairs = 0;
     for (int y = 0; y < ngroups; ++y) npairs += y / 16 + 1;
     dim3 grid((unsigned)npairs, 1, (unsigned)nb);
-    hipLaunchKernelGGL(lml_grad_kernel, grid, dim3(256), 0, st, f->X, f->hp, f->alpha, f->Kinv, Np, f->gpart, (int)N,
-                       (int)d, f->kind, f->has_const, f->has_noise);
+    if (f->kind == 4)
+      hipLaunchKernelGGL(lml_grad_nu_kernel, grid, dim3(256), 0, st, f->X, f->hp, f->alpha, f->Kinv, Np, f->gpart, (int)N,
+                         (int)d, f->mnu, f->has_const, f->has_noise);
+    else
+      hipLaunchKernelGGL(lml_grad_kernel, grid, dim3(256), 0, st, f->X, f->hp, f->alpha, f->Kinv, Np, f->gpart, (int)N,
+                         (int)d, f->kind, f->has_const, f->has_noise);
     hipLaunchKernelGGL(grad_reduce_stage1_kernel, dim3(GR_BLOCKS, (unsigned)nb), dim3(256), 0, st, f->gpart,
                        npairs, f->gstage, nth);
     hipLaunchKernelGGL(grad_reduce_kernel, dim3((unsigned)nb), dim3(64), 0, st, f->gstage, f->grad, nth);
@@ -1356,7 +1479,7 @@ int gpemu_fit_create(gpemu_fit **out, int device, int64_t N, int64_t d, const do
   *out = nullptr;
   GP_ARG(N > 0 && d > 0 && d <= DPAD, "N > 0 and 0 < d <= 8 required");
   GP_ARG(kernel_kind == GPEMU_KERNEL_RBF || kernel_kind == GPEMU_KERNEL_MATERN, "kernel_kind");
-  if (kernel_kind == GPEMU_KERNEL_MATERN) GP_ARG(nu == 0.5 || nu == 1.5 || nu == 2.5, "Matern nu must be 0.5, 1.5 or 2.5");
+  if (kernel_kind == GPEMU_KERNEL_MATERN) GP_ARG(nu > 0.0, "Matern nu must be > 0 (finite or +inf; not NaN)");
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
     set_error("no HIP device available: libgpemu has no CPU implementation");
@@ -1366,7 +1489,9 @@ int gpemu_fit_create(gpemu_fit **out, int device, int64_t N, int64_t d, const do
   GP_HIP(hipSetDevice(device));
   gpemu_fit *f = new gpemu_fit();
   f->device = device; f->N = N; f->d = d; f->Np = round_up(N, NB);
-  f->kind = kind_of(kernel_kind, nu); f->has_const = has_const ? 1 : 0; f->has_noise = has_noise ? 1 : 0;
+  f->kind = fit_kind_of(kernel_kind, nu);
+  if (f->kind == 4) f->mnu = matern_nu_constants(nu);
+  f->has_const = has_const ? 1 : 0; f->has_noise = has_noise ? 1 : 0;
   f->jitter = jitter;
   const int64_t Np = f->Np;
   f->n_gparts = (int)(((N + 255) / 256) * N);
@@ -1474,8 +1599,7 @@ int gpemu_kernel_matrix(int device, int64_t N, int64_t d, const double *X, const
     hp[DPAD] = f->has_const ? std::exp(theta[d]) : 0.0;
     hp[DPAD + 1] = f->has_noise ? std::exp(theta[d + f->has_const]) : 0.0;
     hipError_t e = hipMemcpy(f->hp, hp, sizeof(hp), hipMemcpyHostToDevice);
-    hipLaunchKernelGGL(kmat_kernel, dim3((unsigned)((f->Np + 255) / 256), (unsigned)((f->Np + KMAT_ROWS - 1) / KMAT_ROWS)), dim3(256), 0, f->stream,
-                       f->X, f->hp, f->K, (int)N, (int)f->Np, f->kind, jitter);
+    launch_kmat(f, N, 1, jitter, f->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(f->stream);
     if (e == hipSuccess)
       e = hipMemcpy2D(K_out, sizeof(double) * N, f->K, sizeof(double) * f->Np, sizeof(double) * N, (size_t)N, hipMemcpyDeviceToHost);

@@ -32,7 +32,8 @@ typedef double d2 __attribute__((ext_vector_type(2)));
 constexpr int FRONT_MAX_GROUPS = 8;
 
 struct FrontGroup {
-  // cross-kernel of the half being opened (matrix-core operands, kstar_host.h; Xs / inv_ls: Matern-0.5 only)
+  // cross-kernel of the half being opened (matrix-core operands, kstar_host.h; Xs / inv_ls: Matern-0.5 / general nu < 1
+  // only; kind 4: the nu constants behind etab's table)
   const double *Xa, *alf, *qsc, *qof, *etab, *constv, *Xs, *inv_ls;
   double *KS, *mean_part_next;
   // likelihood of the half before
@@ -199,8 +200,9 @@ __device__ __forceinline__ double front_loglik_lds(const FrontGroup &gr, bool in
   return walker_loglik_lowrank_lds(inside, mu, sd, gr.G, gr.g0, gr.scal, gr.k, gr.nblk, lane, M, gr.k + 1);
 }
 
-// the cross-kernel rows of one workgroup (kstar_kernel's arithmetic: predict_dev.h), base kernel chosen at run time
-template <int JTW>
+// the cross-kernel rows of one workgroup (kstar_kernel's arithmetic: predict_dev.h), base kernel chosen at run time;
+// kind 4 (general nu) only in the NU instances (front_kernel<JTW + FRONT_NU, ..>), which the host launches when a group has it
+template <int JTW, bool NU>
 __device__ __forceinline__ double front_kstar_block(const FrontGroup &gk, const KstarFrags<2, JTW> &fr, const double *s_q,
                                                     const double *s_tab, double *s_red, int p, int chunk, int64_t b0, int d,
                                                     int lane, int wave) {
@@ -209,12 +211,19 @@ __device__ __forceinline__ double front_kstar_block(const FrontGroup &gk, const 
   const double *qsc = gk.qsc + p * 8, *qof = gk.qof + p * 8;
   double *ks = gk.KS + (int64_t)p * gk.Npad * gk.Bcap + b0;
   const KstarDirect none{nullptr, nullptr};
+  if (NU && gk.kind == 4)
+    return kstar_mfma_block<4, 2, JTW, 2, KSTAR_TB>(s_q, s_tab, s_red, fr, qsc, qof, c, d, (int64_t)chunk * JT, gk.N, ks, gk.Bcap,
+                                                   KstarDirect{gk.Xs + (int64_t)p * gk.Npad * DPAD, gk.inv_ls + p * DPAD}, lane,
+                                                   wave, kstar_matern_nu(gk.etab + (1 << KSTAR_TB)));
   switch (gk.kind) {
     case 0: return kstar_mfma_block<0, 2, JTW, 2, KSTAR_TB>(s_q, s_tab, s_red, fr, qsc, qof, c, d, (int64_t)chunk * JT, gk.N, ks, gk.Bcap, none, lane, wave);
     case 1: return kstar_mfma_block<1, 2, JTW, 2, KSTAR_TB>(s_q, s_tab, s_red, fr, qsc, qof, c, d, (int64_t)chunk * JT, gk.N, ks, gk.Bcap,
                                                            KstarDirect{gk.Xs + (int64_t)p * gk.Npad * DPAD, gk.inv_ls + p * DPAD}, lane, wave);
     case 2: return kstar_mfma_block<2, 2, JTW, 2, KSTAR_TB>(s_q, s_tab, s_red, fr, qsc, qof, c, d, (int64_t)chunk * JT, gk.N, ks, gk.Bcap, none, lane, wave);
-    default: return kstar_mfma_block<3, 2, JTW, 2, KSTAR_TB>(s_q, s_tab, s_red, fr, qsc, qof, c, d, (int64_t)chunk * JT, gk.N, ks, gk.Bcap, none, lane, wave);
+    case 3:
+    default:   // launch_front hands these instances kinds 0 - 3 only (kind 4: the NU instances, above); the arm stays the
+               // default one so that the instances keep the code they had
+      return kstar_mfma_block<3, 2, JTW, 2, KSTAR_TB>(s_q, s_tab, s_red, fr, qsc, qof, c, d, (int64_t)chunk * JT, gk.N, ks, gk.Bcap, none, lane, wave);
   }
 }
 
@@ -229,8 +238,13 @@ __device__ __forceinline__ double front_kstar_block(const FrontGroup &gk, const 
 #ifndef GPEMU_FRONT_KBIG_WPE
 #define GPEMU_FRONT_KBIG_WPE 3
 #endif
-template <int JTW, bool KBIG>
+// JTWN = JTW + FRONT_NU: the instances with kind 4, launched when a group has the general-nu Matern;
+// the other instances keep the code they had before kind 4 existed
+constexpr int FRONT_NU = 16;
+template <int JTWN, bool KBIG>
 __global__ __launch_bounds__(256, KBIG ? GPEMU_FRONT_KBIG_WPE : 3) void front_kernel(FrontArgs fa) {
+  constexpr int JTW = JTWN % FRONT_NU;
+  constexpr bool NU = JTWN >= FRONT_NU;
   __shared__ double s_tab[1 << KSTAR_TB];
   __shared__ __attribute__((aligned(16))) double s_q[64 * DPAD];
   __shared__ double s_eff[2][64][DPAD];
@@ -359,7 +373,7 @@ __global__ __launch_bounds__(256, KBIG ? GPEMU_FRONT_KBIG_WPE : 3) void front_ke
     s_q[lane * DPAD + c1] = q1;
   }
   __syncthreads();
-  const double sum = front_kstar_block<JTW>(gk, fr, s_q, s_tab, red, p, chunk, (int64_t)cb * 64, fa.d, lane, wave);
+  const double sum = front_kstar_block<JTW, NU>(gk, fr, s_q, s_tab, red, p, chunk, (int64_t)cb * 64, fa.d, lane, wave);
   if (wave == 0) gk.mean_part_next[(b * gk.k + p) * gk.nchunk + chunk] = sum;
 }
 
@@ -447,15 +461,25 @@ static bool front_kbig(const gpemu_sampler *s) {
     if (m->k > 16 && m->k <= 32) return true;
   return false;
 }
-static const void *front_kernel_ptr(bool small, bool kbig) {
+// a group with the general-nu Matern: the front_kernel<JTW + FRONT_NU, ..> instances
+static bool front_nu(const gpemu_sampler *s) {
+  for (const gpemu_model *m : s->groups)
+    if (kstar_kind(m) == 4) return true;
+  return false;
+}
+static const void *front_kernel_ptr(bool small, bool kbig, bool nu) {
+  if (nu) {
+    if (small) return kbig ? (const void *)front_kernel<1 + FRONT_NU, true> : (const void *)front_kernel<1 + FRONT_NU, false>;
+    return kbig ? (const void *)front_kernel<2 + FRONT_NU, true> : (const void *)front_kernel<2 + FRONT_NU, false>;
+  }
   if (small) return kbig ? (const void *)front_kernel<1, true> : (const void *)front_kernel<1, false>;
   return kbig ? (const void *)front_kernel<2, true> : (const void *)front_kernel<2, false>;
 }
 static int front_set_lds_limit() {
   static bool attr_set = false;
   if (!attr_set) {
-    for (int v = 0; v < 4; ++v)
-      GP_HIP(hipFuncSetAttribute(front_kernel_ptr(v & 1, v & 2), hipFuncAttributeMaxDynamicSharedMemorySize, 136 * 1024));
+    for (int v = 0; v < 8; ++v)
+      GP_HIP(hipFuncSetAttribute(front_kernel_ptr(v & 1, v & 2, v & 4), hipFuncAttributeMaxDynamicSharedMemorySize, 136 * 1024));
     attr_set = true;
   }
   return GPEMU_OK;
@@ -467,10 +491,18 @@ static int64_t front_capacity(const gpemu_sampler *s, bool small) {
   int per_cu = 0;
   const bool kbig = front_kbig(s);
   hipError_t e;
-  if (small) e = kbig ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, front_kernel<1, true>, 256, dyn)
-                      : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, front_kernel<1, false>, 256, dyn);
-  else e = kbig ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, front_kernel<2, true>, 256, dyn)
-                : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, front_kernel<2, false>, 256, dyn);
+  if (front_nu(s)) {
+    if (small) e = kbig ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, front_kernel<1 + FRONT_NU, true>, 256, dyn)
+                        : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, front_kernel<1 + FRONT_NU, false>, 256, dyn);
+    else e = kbig ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, front_kernel<2 + FRONT_NU, true>, 256, dyn)
+                  : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, front_kernel<2 + FRONT_NU, false>, 256, dyn);
+  } else if (small) {
+    e = kbig ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, front_kernel<1, true>, 256, dyn)
+             : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, front_kernel<1, false>, 256, dyn);
+  } else {
+    e = kbig ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, front_kernel<2, true>, 256, dyn)
+             : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, front_kernel<2, false>, 256, dyn);
+  }
   if (e != hipSuccess) { (void)hipGetLastError(); return 0; }
   return (int64_t)per_cu * s->groups[0]->num_cu;
 }
@@ -663,10 +695,20 @@ static int launch_front(gpemu_sampler *s, const Pending &pv, bool have_next, int
   if (dyn > 40 * 1024 && front_set_lds_limit() != GPEMU_OK) return GPEMU_ERR_HIP;
   const int pe0 = prof_mark(m0, st);
   const bool kbig = front_kbig(s);
-  if (small && kbig) hipLaunchKernelGGL((front_kernel<1, true>), grid, block, dyn, st, fa);
-  else if (small) hipLaunchKernelGGL((front_kernel<1, false>), grid, block, dyn, st, fa);
-  else if (kbig) hipLaunchKernelGGL((front_kernel<2, true>), grid, block, dyn, st, fa);
-  else hipLaunchKernelGGL((front_kernel<2, false>), grid, block, dyn, st, fa);
+  if (front_nu(s)) {
+    if (small && kbig) hipLaunchKernelGGL((front_kernel<1 + FRONT_NU, true>), grid, block, dyn, st, fa);
+    else if (small) hipLaunchKernelGGL((front_kernel<1 + FRONT_NU, false>), grid, block, dyn, st, fa);
+    else if (kbig) hipLaunchKernelGGL((front_kernel<2 + FRONT_NU, true>), grid, block, dyn, st, fa);
+    else hipLaunchKernelGGL((front_kernel<2 + FRONT_NU, false>), grid, block, dyn, st, fa);
+  } else if (small && kbig) {
+    hipLaunchKernelGGL((front_kernel<1, true>), grid, block, dyn, st, fa);
+  } else if (small) {
+    hipLaunchKernelGGL((front_kernel<1, false>), grid, block, dyn, st, fa);
+  } else if (kbig) {
+    hipLaunchKernelGGL((front_kernel<2, true>), grid, block, dyn, st, fa);
+  } else {
+    hipLaunchKernelGGL((front_kernel<2, false>), grid, block, dyn, st, fa);
+  }
   GP_HIP(hipGetLastError());
   prof_pair(m0, 1, pe0, prof_mark(m0, st));
   // bookkeeping

@@ -193,7 +193,8 @@ __global__ __launch_bounds__(512) void halfstep_small_kernel(HsArgs ha, ProposeA
     part += __shfl_xor(part, 32);
     const double hq = (KIND == 0) ? -0.5 * part : part;
     KstarDirect dir{nullptr, nullptr};
-    if (KIND == 1) dir = KstarDirect{gr.Xs + (int64_t)p * Npad * DPAD, gr.inv_ls + p * DPAD};
+    if (KIND == 1 || KIND == 4) dir = KstarDirect{gr.Xs + (int64_t)p * Npad * DPAD, gr.inv_ls + p * DPAD};
+    const MaternNu mn = (KIND == 4) ? kstar_matern_nu(ha.etab + (1 << TB)) : MaternNu();   // (one nu per launch)
     // the products of all of the wave's tiles first: their matrix-core latency hides behind the first tile's ~100 vector
     // instructions (padding tiles multiply zeros and are dropped below)
     kd4 accs[4];
@@ -204,7 +205,7 @@ __global__ __launch_bounds__(512) void halfstep_small_kernel(HsArgs ha, ProposeA
       const int jt = jt0 + 4 * u;
       if (jt < njt) {                                       // (wave-uniform)
         const int64_t row0 = (int64_t)jt * 16 + lk;
-        kd4 v = kstar_value4<KIND, TB>(accs[u], hq, s_tab, dir, s_q, row0, col);
+        kd4 v = kstar_value4<KIND, TB>(accs[u], hq, s_tab, dir, s_q, row0, col, mn);
 #pragma unroll
         for (int r = 0; r < 4; ++r) v[r] += cst;
         if ((jt + 1) * 16 > N) {
@@ -355,7 +356,7 @@ int launch_halfstep_small(gpemu_model *const *ms, int ng, int64_t B, double *dXq
   for (int g = 0; g < ng; ++g) {
     const gpemu_model *m = ms[g];
     const int64_t Bv = m->variant_B > 0 ? m->variant_B : B;
-    if (m->Npad > HS_NMAX || m->k > 32 || m->ksteps != 2 || Bv > 128 || m->d != m0->d || kstar_kind(m) != kstar_kind(m0) ||
+    if (m->Npad > HS_NMAX || m->k > 32 || m->ksteps != 2 || Bv > 128 || m->d != m0->d || !kstar_same_kernel(m, m0) ||
         m->device != m0->device || m->profiling)
       return GPEMU_ERR_UNSUPPORTED;
     nt32max = std::max(nt32max, (int)((m->N + 31) / 32));
@@ -406,7 +407,9 @@ int launch_halfstep_small(gpemu_model *const *ms, int ng, int64_t B, double *dXq
     case 0: GP_LAUNCH_HS(0); break;
     case 1: GP_LAUNCH_HS(1); break;
     case 2: GP_LAUNCH_HS(2); break;
-    default: GP_LAUNCH_HS(3); break;
+    case 3: GP_LAUNCH_HS(3); break;
+    case 4: GP_LAUNCH_HS(4); break;
+    default: return GPEMU_ERR_UNSUPPORTED;
   }
 #undef GP_LAUNCH_HS
   GP_HIP(hipGetLastError());

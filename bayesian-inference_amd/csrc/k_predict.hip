@@ -32,7 +32,7 @@ struct KstarArgs {
   double *Xq;                          // [Bcap][DPAD] padded query rows (read, or written once per column block)
   const double *Xa, *alf, *qsc, *qof;  // matrix-core operands (kstar_host.h)
   const double *etab, *constv;
-  const double *Xs, *inv_ls;           // Matern-0.5 only: row-major scaled training rows for the direct distance
+  const double *Xs, *inv_ls;           // Matern-0.5 / general nu < 1 only: row-major scaled training rows for the direct distance
   double *KS, *mean_part;
   int64_t N, Npad, Bcap;
   int has_const, d;
@@ -119,10 +119,11 @@ __device__ __forceinline__ void kstar_body(const KstarArgs &ka, const ProposeArg
                                  lane, wave);
   const double c = ka.has_const ? ka.constv[p] : 0.0;
   KstarDirect dir{nullptr, nullptr};
-  if (KIND == 1) dir = KstarDirect{ka.Xs + (int64_t)p * ka.Npad * DPAD, ka.inv_ls + p * DPAD};
+  if (KIND == 1 || KIND == 4) dir = KstarDirect{ka.Xs + (int64_t)p * ka.Npad * DPAD, ka.inv_ls + p * DPAD};
+  const MaternNu mn = (KIND == 4) ? kstar_matern_nu(ka.etab + (1 << KSTAR_TB)) : MaternNu();
   const double sum = kstar_mfma_block<KIND, KS, JTW, NBW, KSTAR_TB>(
       s_q, s_tab, s_red, fr, ka.qsc + p * 4 * KS, ka.qof + p * 4 * KS, c, ka.d, (int64_t)chunk * JT, ka.N, ka.KS + (int64_t)p * ka.Npad * ka.Bcap + b0, ka.Bcap, dir,
-      lane, wave);
+      lane, wave, mn);
   if (wave == 0) ka.mean_part[(b * ka.k + p) * nchunk + chunk] = sum;
 }
 
@@ -201,14 +202,18 @@ static KstarArgs kstar_setup(gpemu_model *m, int64_t B, double *dXq, int &nwg, b
         case 0: if (small) LAUNCH(0, 2, 1); else LAUNCH(0, 2, 2); break; \
         case 1: if (small) LAUNCH(1, 2, 1); else LAUNCH(1, 2, 2); break; \
         case 2: if (small) LAUNCH(2, 2, 1); else LAUNCH(2, 2, 2); break; \
-        default: if (small) LAUNCH(3, 2, 1); else LAUNCH(3, 2, 2); break; \
+        case 3: if (small) LAUNCH(3, 2, 1); else LAUNCH(3, 2, 2); break; \
+        case 4: if (small) LAUNCH(4, 2, 1); else LAUNCH(4, 2, 2); break; \
+        default: set_error("cross-kernel: unknown base kernel %d", (int)(kind)); return GPEMU_ERR_STATE; \
       }                                                                  \
     } else {                                                             \
       switch (kind) {                                                    \
         case 0: if (small) LAUNCH(0, 3, 1); else LAUNCH(0, 3, 2); break; \
         case 1: if (small) LAUNCH(1, 3, 1); else LAUNCH(1, 3, 2); break; \
         case 2: if (small) LAUNCH(2, 3, 1); else LAUNCH(2, 3, 2); break; \
-        default: if (small) LAUNCH(3, 3, 1); else LAUNCH(3, 3, 2); break; \
+        case 3: if (small) LAUNCH(3, 3, 1); else LAUNCH(3, 3, 2); break; \
+        case 4: if (small) LAUNCH(4, 3, 1); else LAUNCH(4, 3, 2); break; \
+        default: set_error("cross-kernel: unknown base kernel %d", (int)(kind)); return GPEMU_ERR_STATE; \
       }                                                                  \
     }                                                                    \
   } while (0)

@@ -3,6 +3,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "matern_dev.h"
+
 namespace gpemu {
 
 // exp(x) for x <= 0 (the only arguments the kernels produce): x = (32 e + j) ln2/32 + r, |r| <= ln2/64,
@@ -116,7 +118,7 @@ __device__ __forceinline__ kd4 exp2_scaled4(kd4 y, const double *tab) {
   return v;
 }
 
-// Matern-0.5 only: exp(-r) is not flat at r = 0, so a pair closer than ~1e-3.5 of the data's extent (a query ON a
+// Matern-0.5 (and general nu < 1: 1 - k ~ r^(2 nu)): exp(-r) is not flat at r = 0, so a pair closer than ~1e-3.5 of the data's extent (a query ON a
 // training point) needs r^2 to better than the product form's ~d eps |x|^2: those few pairs are recomputed from the
 // coordinate differences, round 3's arithmetic (row-major scaled rows xs[j][8], query q inv_ls).
 struct KstarDirect {
@@ -133,12 +135,29 @@ __device__ __forceinline__ double kstar_direct_r2(const KstarDirect &dir, const 
   return r2;
 }
 
+// The constants of a general-nu model (KIND 4) sit behind the exponential's table in the model's etab buffer (built at
+// model creation, gpemu_api.hip): the kernels' argument structs keep the layout of kinds 0-3.
+__device__ __forceinline__ MaternNu kstar_matern_nu(const double *etab_end) {
+  return *reinterpret_cast<const MaternNu *>(etab_end);
+}
+
 // kernel values of the four accumulator registers of a lane (one query column, four training rows)
 //   KIND 0 (RBF): operands scaled, acc + hq = -1/2 r^2 2^TB / ln2;  hq = -1/2 |q'|^2
 //   KIND 1, 2, 3 (Matern 0.5 / 1.5 / 2.5): operands unscaled, r^2 = max(-2 acc + |q'|^2, 0);  hq = |q'|^2
+//   KIND 4 (Matern, general nu: matern_dev.h): as 1 - 3; for nu < 1 near-coincident pairs by the direct distance
 template <int KIND, int TB>
 __device__ __forceinline__ kd4 kstar_value4(kd4 acc, double hq, const double *tab, const KstarDirect &dir,
-                                            const double *s_q, int64_t row0, int col) {
+                                            const double *s_q, int64_t row0, int col, const MaternNu &mn = MaternNu()) {
+  if (KIND == 4) {
+    kd4 v;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      double r2 = fmax(fma(acc[r], -2.0, hq), 0.0);
+      if (mn.nu < 1.0 && r2 < 1e-7 * (hq + 1.0)) r2 = kstar_direct_r2(dir, s_q, row0 + 4 * r, col);
+      v[r] = matern_nu_value_call(mn, sqrt(r2));
+    }
+    return v;
+  }
   if (KIND == 0) {
 #pragma unroll
     for (int r = 0; r < 4; ++r) acc[r] += hq;
@@ -177,8 +196,9 @@ __device__ __forceinline__ kd4 kstar_tile_product(const double (&a)[KS], const d
 template <int KIND, int TB, int ABL = 0>   // ABL: probe ablations (1: no stores, 2: no exponential, 3: nontemporal stores)
 __device__ __forceinline__ void kstar_tile_finish(kd4 acc, double hq, kd4 al, double c, const double *s_tab, bool ragged,
                                                   int64_t row0, int64_t N, double *__restrict__ kout, int64_t Bcap, double &macc,
-                                                  const KstarDirect &dir, const double *s_q, int col) {
-  kd4 v = (ABL == 2) ? acc : kstar_value4<KIND, TB>(acc, hq, s_tab, dir, s_q, row0, col);
+                                                  const KstarDirect &dir, const double *s_q, int col,
+                                                  const MaternNu &mn = MaternNu()) {
+  kd4 v = (ABL == 2) ? acc : kstar_value4<KIND, TB>(acc, hq, s_tab, dir, s_q, row0, col, mn);
 #pragma unroll
   for (int r = 0; r < 4; ++r) v[r] += c;
   if (ragged) {                                           // wave-uniform: only the tiles that hold padded training rows
@@ -225,7 +245,8 @@ __device__ __forceinline__ double kstar_mfma_block(const double *s_q, const doub
                                                    const KstarFrags<KS, JTW> &fr,
                                                    const double *__restrict__ qsc, const double *__restrict__ qof,
                                                    double c, int d, int64_t jt0, int64_t N, double *__restrict__ ks,
-                                                   int64_t Bcap, const KstarDirect &dir, int lane, int wave) {
+                                                   int64_t Bcap, const KstarDirect &dir, int lane, int wave,
+                                                   const MaternNu &mn = MaternNu()) {
   constexpr int WC = 4 / NBW, WR = 4 / WC;
   const int wr = wave % WR, wc = wave / WR;
   const int ln = lane & 15, lq = lane >> 4;
@@ -266,7 +287,7 @@ __device__ __forceinline__ double kstar_mfma_block(const double *s_q, const doub
     if (i + 1 < NT) nxt = kstar_tile_product<KS>(fr.a[(i + 1) / NBW], bq[(i + 1) % NBW]);
     const int64_t jt = jt0 + wr * JTW + jj;
     kstar_tile_finish<KIND, TB, ABL>(acc, hq[bt], fr.al[jj], c, s_tab, (jt + 1) * 16 > N, jt * 16 + lq, N,
-                                     kcol + jt * 16 * Bcap + bt * 16, Bcap, macc[bt], dir, s_q, wc * NBW * 16 + ln + bt * 16);
+                                     kcol + jt * 16 * Bcap + bt * 16, Bcap, macc[bt], dir, s_q, wc * NBW * 16 + ln + bt * 16, mn);
     acc = nxt;
   }
   // column sums: over the four lane groups, then over the wave rows in a fixed order

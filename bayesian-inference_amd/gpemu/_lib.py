@@ -8,6 +8,7 @@ fallback.
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 
 import numpy as np
@@ -102,6 +103,20 @@ _SIGNATURES = {
     "gpemu_halfstep_small_launches": (C.c_int64, []),
     "gpemu_philox4x32": (C.c_int, [C.c_uint32] * 6 + [C.POINTER(C.c_uint32)]),
 }
+
+
+def kernel_args(kernel_kind, nu):
+    """``(kernel_kind, nu)`` as the library's create calls take them.  Matern with nu = inf is the RBF kernel
+    (skl kernels.py:1722-1723): it goes to the device as the RBF kind.  A Matern nu that is not > 0 (NaN included)
+    raises ValueError before any library call; an RBF's nu is not read (passed as before: 0 if not finite)."""
+    kind, nu = int(kernel_kind), float(nu)
+    if kind == 1:
+        if not nu > 0.0:
+            raise ValueError(f"Matern nu must be > 0 (or inf), got {nu}")
+        if math.isinf(nu):
+            return 0, 0.0
+        return kind, nu
+    return kind, (nu if math.isfinite(nu) else 0.0)
 
 
 def exported_symbols():

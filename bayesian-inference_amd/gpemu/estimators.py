@@ -93,6 +93,8 @@ class ARDKernel:
                  constant_value_bounds=None, noise_level=None, noise_level_bounds=None):
         self.kind = int(kind)
         self.nu = float(nu)
+        if self.kind == MATERN_KIND and not self.nu > 0.0:   # sklearn accepts any nu > 0 and inf
+            raise ValueError(f"Matern nu must be > 0 (or inf), got {nu}")
         self.length_scale = np.atleast_1d(np.asarray(length_scale, dtype=np.float64)).copy()
         self.length_scale_bounds = np.atleast_2d(np.asarray(length_scale_bounds, dtype=np.float64)).copy()
         self.constant_value = None if constant_value is None else float(constant_value)

@@ -27,10 +27,10 @@ class DeviceFit:
         X = as_f64(X)
         self.N, self.d = X.shape
         self.n_theta = self.d + int(has_const) + int(has_noise)
+        kind_arg, nu_arg = _lib.kernel_args(kernel_kind, nu)
         h = C.c_void_p()
-        check(_lib.lib().gpemu_fit_create(C.byref(h), int(device), self.N, self.d, ptr(X), int(kernel_kind),
-                                          float(nu) if np.isfinite(nu) else 0.0, int(has_const), int(has_noise),
-                                          float(jitter)))
+        check(_lib.lib().gpemu_fit_create(C.byref(h), int(device), self.N, self.d, ptr(X), kind_arg, nu_arg,
+                                          int(has_const), int(has_noise), float(jitter)))
         self._h = h
         self.n_evaluations = 0          # log-marginal-likelihood evaluations run through this handle
         self.seconds_in_library = 0.0   # wall time inside the (synchronous) C calls: upload, launch chain, download
@@ -100,9 +100,9 @@ def kernel_matrix(X, theta, kernel_kind=0, nu=np.inf, has_const=False, has_noise
     N, d = X.shape
     theta = as_f64(theta)
     K = np.empty((N, N))
-    check(_lib.lib().gpemu_kernel_matrix(int(device), N, d, ptr(X), ptr(theta), theta.size, int(kernel_kind),
-                                         float(nu) if np.isfinite(nu) else 0.0, int(has_const), int(has_noise),
-                                         float(jitter), ptr(K)))
+    kind_arg, nu_arg = _lib.kernel_args(kernel_kind, nu)
+    check(_lib.lib().gpemu_kernel_matrix(int(device), N, d, ptr(X), ptr(theta), theta.size, kind_arg, nu_arg,
+                                         int(has_const), int(has_noise), float(jitter), ptr(K)))
     return K
 
 

@@ -40,10 +40,11 @@ class DeviceModel:
         const_a = None if const is None else as_f64(const, (k,))
         noise_a = None if noise is None else as_f64(noise, (k,))
         cu = None if cov_unexplained is None else as_f64(cov_unexplained, (F, F))
+        kind_arg, nu_arg = _lib.kernel_args(kernel_kind, nu)
         h = C.c_void_p()
         check(_lib.lib().gpemu_model_create(
-            C.byref(h), int(device), N, d, F, k, int(kernel_kind),
-            float(nu) if np.isfinite(nu) else 0.0, int(const is not None), int(noise is not None),
+            C.byref(h), int(device), N, d, F, k, kind_arg,
+            nu_arg, int(const is not None), int(noise is not None),
             ptr(X_train), ptr(ls), ptr(const_a), ptr(noise_a), ptr(alpha), ptr(L), ptr(components),
             ptr(scaler_mean), ptr(scaler_scale), ptr(cu)))
         self._h = h

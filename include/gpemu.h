@@ -39,7 +39,7 @@ extern "C" {
 
 /* kernel_kind (ref: emulation.py:133-149) */
 #define GPEMU_KERNEL_RBF 0    /* skl gaussian_process/kernels.py:1553-1582 */
-#define GPEMU_KERNEL_MATERN 1 /* skl gaussian_process/kernels.py:1708-1781, nu in {0.5,1.5,2.5} */
+#define GPEMU_KERNEL_MATERN 1 /* skl gaussian_process/kernels.py:1708-1781: any nu > 0 (0.5 / 1.5 / 2.5 closed forms, +inf = RBF, else K_nu) */
 
 /* gpemu_logpost mode */
 #define GPEMU_LOGPOST_LOWRANK 0 /* k x k Woodbury form, the throughput path          */
