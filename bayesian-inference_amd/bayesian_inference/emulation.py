@@ -121,7 +121,7 @@ def fit_emulator_group(config: "EmulationGroupConfig") -> dict[str, Any]:
     for index, gp in enumerate(emulators):
         logger.info(f'  PC {index}: {gp.kernel_}')
 
-    return {
+    results = {
         'PCA': {
             'Y': observables,
             'Y_pca': scores,
@@ -133,6 +133,119 @@ def fit_emulator_group(config: "EmulationGroupConfig") -> dict[str, Any]:
         },
         'emulators': emulators,
     }
+    if config.cross_validation:
+        cv = cross_validate_emulator_group(config, results)
+        logger.info(f'{cv["n_folds"]}-fold cross-validation at the fitted hyper-parameters:')
+        for index, mz2 in enumerate(cv['mean_z2_pc']):
+            logger.info(f'  PC {index}: mean(z^2) = {mz2:.4g}')
+        logger.info(f'  observables: RMSE {np.sqrt(np.mean(cv["residual"] ** 2)):.4g}, '
+                    f'mean(z^2) {np.nanmean(cv["z"] ** 2):.4g}, '
+                    f'coverage {cv["coverage"]:.3f} at confidence {cv["confidence"]}')
+        results['cross_validation'] = cv
+    return results
+
+
+####################################################################################################
+# Cross-validation of the emulators at their fitted hyper-parameters.  The analysis YAML's
+# `cross_validation` / `cross_validation_k` keys (ref: config/jet_substructure.yaml, emulator_parameters), which the
+# reference declares but never reads.
+def kfold_labels(N: int, k: int) -> np.ndarray:
+    """Fold label of each of N design points as sklearn.model_selection.KFold(n_splits=k) without shuffling deals
+    them: contiguous folds in design order, the first N % k folds one point larger.  k = N: leave-one-out."""
+    N, k = int(N), int(k)
+    if k < 2:
+        raise ValueError(f"cross_validation_k must be at least 2, got {k}")
+    if k > N:
+        raise ValueError(f"cross_validation_k = {k} exceeds the number of design points ({N})")
+    sizes = np.full(k, N // k, dtype=np.int64)
+    sizes[:N % k] += 1
+    return np.repeat(np.arange(k, dtype=np.int32), sizes)
+
+
+def _closure_confidence(config) -> float:
+    """The analysis' closure `confidence` (ref: config/jet_substructure.yaml, closure parameters); 0.9 if absent."""
+    try:
+        conf = config.analysis_config['parameters']['closure']['confidence']
+    except (KeyError, TypeError):
+        return 0.9
+    if isinstance(conf, (list, tuple)):
+        conf = conf[0]
+    return float(conf)
+
+
+def _cv_summary(out: dict, Y: np.ndarray, confidence: float) -> dict:
+    """Residuals and their summary (host numpy) of merged or per-group cross-validation results."""
+    from statistics import NormalDist
+    residual = Y - out['central_value']
+    with np.errstate(divide='ignore', invalid='ignore'):
+        z = residual / np.sqrt(out['variance'])
+    bound = NormalDist().inv_cdf(0.5 + 0.5 * confidence)
+    out.update(residual=residual, z=z,
+               rmse=np.sqrt(np.mean(residual ** 2, axis=0)),
+               mean_z2=np.mean(z ** 2, axis=0),
+               coverage=float(np.mean(np.abs(z) <= bound)),
+               confidence=float(confidence))
+    return out
+
+
+def cross_validate_emulator_group(config: "EmulationGroupConfig", results: dict[str, Any],
+                                  n_folds: int | None = None) -> dict[str, Any]:
+    """k-fold cross-validation of one group's emulators on the device (``DeviceModel.cross_validate``).
+
+    Each design point is predicted by its PCs' GPs refitted to the other folds with the hyper-parameters held at the
+    fitted ``kernel_`` and the scaler and PCA held at the full-data fit (no re-optimisation per fold):
+    ``GaussianProcessRegressor(kernel=gp.kernel_, alpha=alpha, optimizer=None).fit(X[R], y[R])
+    .predict(X[I], return_std=True)``, back-projected as ``predict_emulation_group`` does for one sample.
+    ``n_folds`` defaults to the group's ``cross_validation_k``; the folds are ``kfold_labels``.
+
+    Returns ``fold`` (N,), ``n_folds``, ``mean_pc`` / ``var_pc`` (N, n_pc), ``central_value`` / ``variance`` (N, F),
+    ``residual`` = Y - central_value, ``z`` = residual / sqrt(variance), per feature ``rmse`` and ``mean_z2``, per PC
+    ``mean_z2_pc``, per point ``chi2_pc`` = sum_p (y_pc - mean_pc)^2 / var_pc, and ``coverage``, the fraction of |z|
+    inside the two-sided normal interval of the closure ``confidence``."""
+    k = config.cross_validation_k if n_folds is None else n_folds
+    y_pc = np.asarray(results['PCA']['Y_pca_truncated'], dtype=np.float64)[:, :config.n_pc]
+    fold = kfold_labels(y_pc.shape[0], k)
+    dm = device_model_for(results, config.n_pc)
+    mean_pc, var_pc, cv, variance = dm.cross_validate(y_pc, fold)
+    with np.errstate(divide='ignore', invalid='ignore'):
+        z2_pc = (y_pc - mean_pc) ** 2 / var_pc
+    out = dict(fold=fold, n_folds=int(k), mean_pc=mean_pc, var_pc=var_pc, central_value=cv, variance=variance,
+               mean_z2_pc=np.mean(z2_pc, axis=0), chi2_pc=np.sum(z2_pc, axis=1))
+    return _cv_summary(out, np.asarray(results['PCA']['Y'], dtype=np.float64), _closure_confidence(config))
+
+
+def cross_validate(emulation_config: "EmulationConfig", emulation_results: dict[str, dict[str, Any]] | None = None,
+                   n_folds: int | None = None) -> dict[str, Any]:
+    """Cross-validation of every emulation group (``cross_validate_emulator_group``), merged into the full observable
+    order by the conversion ``predict`` uses.  The groups share the design, so they share the folds.
+
+    Returns ``fold``, ``n_folds``, per group ``mean_pc`` / ``var_pc`` / ``chi2_pc`` ({group: array}), the merged
+    ``central_value`` / ``variance`` / ``residual`` / ``z`` (N, F_total), per feature ``rmse`` / ``mean_z2``, the
+    per-point ``chi2_pc`` summed over groups (``chi2_pc_total``) and ``coverage``."""
+    emulation_config._need_groups("cross-validation")
+    emulation_results = emulation_results or {}
+    per_group = {}
+    for name, group_config in emulation_config.emulation_groups_config.items():
+        results = emulation_results.get(name)
+        if results is None:
+            results = read_emulators(group_config)
+        res = cross_validate_emulator_group(group_config, results, n_folds)
+        res['Y'] = np.asarray(results['PCA']['Y'], dtype=np.float64)
+        per_group[name] = res
+    sorter = emulation_config.sort_observables_in_matrix
+    # a sorter of its own: convert() fixes the value types it merges on first use
+    merged = SortEmulationGroupObservables(sorter.emulation_group_to_observable_matrix, sorter.shape).convert(
+        {name: {'central_value': r['central_value'], 'variance': r['variance'], 'Y': r['Y']}
+         for name, r in per_group.items()})
+    first = next(iter(per_group.values()))
+    confidence = _closure_confidence(next(iter(emulation_config.emulation_groups_config.values())))
+    out = dict(fold=first['fold'], n_folds=first['n_folds'],
+               mean_pc={n: r['mean_pc'] for n, r in per_group.items()},
+               var_pc={n: r['var_pc'] for n, r in per_group.items()},
+               chi2_pc={n: r['chi2_pc'] for n, r in per_group.items()},
+               chi2_pc_total=np.sum([r['chi2_pc'] for r in per_group.values()], axis=0),
+               central_value=merged['central_value'], variance=merged['variance'])
+    return _cv_summary(out, merged['Y'], confidence)
 
 
 ####################################################################################################
@@ -380,6 +493,13 @@ class EmulationGroupConfig(_Base):
         self.force_retrain, self.n_pc = block['force_retrain'], block['n_pc']
         self.max_n_components_to_calculate = block.get('max_n_components_to_calculate')
         self.n_restarts, self.alpha = block['GPR']['n_restarts'], block['GPR']['alpha']
+        # k-fold cross-validation at the fitted hyper-parameters after the fit; absent = off
+        self.cross_validation = bool(block.get('cross_validation', False))
+        self.cross_validation_k = block.get('cross_validation_k', 5)
+        if self.cross_validation and (isinstance(self.cross_validation_k, bool) or
+                                      not isinstance(self.cross_validation_k, (int, np.integer)) or
+                                      self.cross_validation_k < 2):
+            raise ValueError(f"cross_validation_k must be an integer >= 2, got {self.cross_validation_k!r}")
 
         kernels = block['kernels']
         self.active_kernels = {name: kernels[name] for name in kernels['active']}     # order of `active` is kept

@@ -297,7 +297,7 @@ int gpemu_model_create(gpemu_model **out, int device, int64_t N, int64_t d, int6
   const int kkind = kstar_kind(m);
   const bool direct = kkind == 1 || (kkind == 4 && nu < 1.0);
   std::vector<double> hXs(direct ? (size_t)(k * Np * DPAD) : 0, 0.0), hls((size_t)(k * DPAD), 1.0),
-      hc((size_t)k, 0.0), hkd((size_t)k, 1.0), hal((size_t)(k * Np), 0.0);
+      hc((size_t)k, 0.0), hkd((size_t)k, 1.0), hal((size_t)(k * Np), 0.0), hjit((size_t)k, 0.0);
   for (int64_t p = 0; p < k; ++p) {
     for (int64_t dd = 0; dd < d; ++dd) {
       double l = ls[p * d + dd];
@@ -311,12 +311,15 @@ int gpemu_model_create(gpemu_model **out, int device, int64_t N, int64_t d, int6
     if (has_const) { hc[p] = constv[p]; hkd[p] += constv[p]; }
     if (has_noise) hkd[p] += noise[p];
     for (int64_t j = 0; j < N; ++j) hal[p * Np + j] = alpha[p * N + j];
+    // the fit's alpha jitter (skl _gpr.py:346-348: K + alpha I = L L^T): K_00 - kernel_.diag, K_00 = L_00^2
+    hjit[p] = std::fma(L[p * N * N], L[p * N * N], -hkd[p]);
   }
 #define GP_STEP(expr) if ((rc = (expr)) != GPEMU_OK) return fail(rc)
   GP_STEP(dev_alloc(&m->ls, k * DPAD));
   GP_STEP(dev_alloc(&m->constv, k));
   GP_STEP(dev_alloc(&m->kdiag, k));
   GP_STEP(dev_alloc(&m->alpha, k * Np));
+  GP_STEP(dev_alloc(&m->cv_jit, k));
   GP_STEP(dev_alloc(&m->Wt, k * Np * Np));
   GP_STEP(dev_alloc(&m->comp, k * F));
   GP_STEP(dev_alloc(&m->smean, F));
@@ -361,6 +364,7 @@ int gpemu_model_create(gpemu_model **out, int device, int64_t N, int64_t d, int6
   GP_STEP(upload(m->constv, hc.data(), k, st));
   GP_STEP(upload(m->kdiag, hkd.data(), k, st));
   GP_STEP(upload(m->alpha, hal.data(), k * Np, st));
+  GP_STEP(upload(m->cv_jit, hjit.data(), k, st));
   GP_STEP(upload(m->comp, components, k * F, st));
   GP_STEP(upload(m->smean, scaler_mean, F, st));
   GP_STEP(upload(m->sscale, scaler_scale, F, st));
@@ -408,7 +412,7 @@ int gpemu_model_destroy(gpemu_model *m) {
   if (m->stream) hipStreamSynchronize(m->stream);
   hipFree(m->Xs); hipFree(m->inv_ls); hipFree(m->ls); hipFree(m->Xa); hipFree(m->alf); hipFree(m->qsc); hipFree(m->qof);
   hipFree(m->etab); hipFree(m->constv); hipFree(m->kdiag);
-  hipFree(m->alpha); hipFree(m->Wt); hipFree(m->comp); hipFree(m->smean); hipFree(m->sscale);
+  hipFree(m->alpha); hipFree(m->cv_jit); hipFree(m->Wt); hipFree(m->comp); hipFree(m->smean); hipFree(m->sscale);
   hipFree(m->cunexpl); hipFree(m->yexp); hipFree(m->yerr); hipFree(m->lo); hipFree(m->hi);
   for (const gpemu_model::LikEntry &en : m->lik_cache) { hipFree(en.G); hipFree(en.g0); hipFree(en.scal); }
   hipFree(m->exact_scratch);
@@ -514,6 +518,64 @@ int gpemu_gp_predict(gpemu_model *m, int64_t B, const double *X, double *mean_ou
     if (e != hipSuccess) { set_error("gp_predict: %s", hipGetErrorString(e)); rc = GPEMU_ERR_HIP; }
   }
   hipFree(dX); hipFree(dm); hipFree(dv);
+  return rc;
+}
+
+// ---- cross-validation (k_cv.hip) -----------------------------------------------------------------------
+int gpemu_model_cross_validate(gpemu_model *m, int64_t n_folds, const int32_t *fold, const double *y_train,
+                               double *mean_pc, double *var_pc, double *central_value, double *variance) {
+  GP_ARG(m && fold && y_train && mean_pc && var_pc, "null pointer");
+  const int64_t N = m->N, k = m->k;
+  GP_ARG(n_folds >= 2 && n_folds <= N, "n_folds must be in [2, N]");
+  std::vector<int> cnt((size_t)n_folds + 1, 0);
+  for (int64_t i = 0; i < N; ++i) {
+    GP_ARG(fold[i] >= 0 && fold[i] < n_folds, "fold label out of [0, n_folds)");
+    ++cnt[(size_t)fold[i] + 1];
+  }
+  for (int64_t f = 0; f < n_folds; ++f) GP_ARG(cnt[(size_t)f + 1] > 0, "empty fold");
+  // the points of every fold, ascending, fold after fold; hfoff = fold offsets, hr0 = first point of each fold
+  std::vector<int> hfoff((size_t)n_folds + 1, 0), hr0((size_t)n_folds), hidx((size_t)N);
+  for (int64_t f = 0; f < n_folds; ++f) hfoff[(size_t)f + 1] = hfoff[(size_t)f] + cnt[(size_t)f + 1];
+  {
+    std::vector<int> pos(hfoff.begin(), hfoff.end() - 1);
+    for (int64_t i = 0; i < N; ++i) hidx[(size_t)pos[(size_t)fold[i]]++] = (int)i;
+  }
+  for (int64_t f = 0; f < n_folds; ++f) hr0[(size_t)f] = hidx[(size_t)hfoff[(size_t)f]];
+  // tests: the largest number of (PC, fold) problems per chunk; read once per call
+  const char *cap_env = getenv("GPEMU_CV_CHUNK");
+  const int64_t max_chunk = cap_env ? atoll(cap_env) : 0;
+  GP_HIP(hipSetDevice(m->device));
+  hipStream_t st = m->stream;
+  int *didx = nullptr, *dfoff = nullptr;
+  double *dy = nullptr, *dm = nullptr, *dv = nullptr, *dcv = nullptr, *dvo = nullptr;
+  int rc = dev_alloc(&didx, N);
+  if (rc == GPEMU_OK) rc = dev_alloc(&dfoff, n_folds + 1);
+  if (rc == GPEMU_OK) rc = dev_alloc(&dy, N * k);
+  if (rc == GPEMU_OK) rc = dev_alloc(&dm, N * k);
+  if (rc == GPEMU_OK) rc = dev_alloc(&dv, N * k);
+  if (rc == GPEMU_OK && central_value) rc = dev_alloc(&dcv, N * m->F);
+  if (rc == GPEMU_OK && variance) rc = dev_alloc(&dvo, N * m->F);
+  hipError_t e = hipSuccess;
+  if (rc == GPEMU_OK) {
+    e = hipMemcpyAsync(didx, hidx.data(), sizeof(int) * (size_t)N, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(dfoff, hfoff.data(), sizeof(int) * (size_t)(n_folds + 1), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(dy, y_train, sizeof(double) * (size_t)(N * k), hipMemcpyHostToDevice, st);
+    if (e != hipSuccess) { set_error("cross_validate: %s", hipGetErrorString(e)); rc = GPEMU_ERR_HIP; }
+  }
+  if (rc == GPEMU_OK) rc = cross_validate(m, (int)n_folds, didx, dfoff, hfoff, hr0, dy, dm, dv, max_chunk);
+  if (rc == GPEMU_OK) rc = launch_cv_backproject(m, dm, dv, dcv, dvo);
+  if (rc == GPEMU_OK) {
+    e = hipMemcpyAsync(mean_pc, dm, sizeof(double) * (size_t)(N * k), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(var_pc, dv, sizeof(double) * (size_t)(N * k), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && dcv)
+      e = hipMemcpyAsync(central_value, dcv, sizeof(double) * (size_t)(N * m->F), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && dvo)
+      e = hipMemcpyAsync(variance, dvo, sizeof(double) * (size_t)(N * m->F), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) { set_error("cross_validate: %s", hipGetErrorString(e)); rc = GPEMU_ERR_HIP; }
+  }
+  (void)hipStreamSynchronize(st);
+  hipFree(didx); hipFree(dfoff); hipFree(dy); hipFree(dm); hipFree(dv); hipFree(dcv); hipFree(dvo);
   return rc;
 }
 

@@ -105,6 +105,7 @@ struct gpemu_model {
   double *constv = nullptr;    // [k]
   double *kdiag = nullptr;     // [k]  kernel_.diag = 1 (+const) (+noise)
   double *alpha = nullptr;     // [k][Npad] (padded = 0)
+  double *cv_jit = nullptr;    // [k]  the fit's alpha jitter: L_00^2 - kdiag (cross-validation variances, k_cv.hip)
   double *Wt = nullptr;        // [k][Npad][Npad]  Wt[p][j][i] = (L_p^-1)[i][j]  (upper triangular)
 
   // PCA / scaler
@@ -239,6 +240,11 @@ int device_trtri_blocked(const double *L, int64_t Np, const double *Dinv, double
                          bool zero_upper = true);
 int device_invert_factor_to_Wt(const double *dL, int64_t N, double *Wt, int64_t Npad, double *A, double *Dinv,
                                double *W, double *T, hipStream_t st);
+// cross-validation at the fitted theta (k_cv.hip): per-(PC, fold) means / variances into dmean / dvar [N][k], then the
+// observable-space back-projection (either output may be null)
+int cross_validate(gpemu_model *m, int n_folds, const int *didx, const int *dfoff, const std::vector<int> &hfoff,
+                   const std::vector<int> &hr0, const double *dy, double *dmean, double *dvar, int64_t max_chunk);
+int launch_cv_backproject(gpemu_model *m, const double *dmean, const double *dvar, double *dcv, double *dvo);
 // profiling helpers: record an event on `st` and return its pool index (-1 when profiling is off)
 int prof_mark(gpemu_model *m, hipStream_t st);
 void prof_pair(gpemu_model *m, int which, int e0, int e1);

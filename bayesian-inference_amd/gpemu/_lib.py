@@ -50,6 +50,7 @@ _SIGNATURES = {
     "gpemu_predict_full": (C.c_int, [C.c_void_p, c_i64, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]),
     "gpemu_predict_full_dev": (C.c_int, [C.c_void_p, c_i64, C.c_void_p, C.c_double, C.c_void_p,
                                          C.c_void_p, C.c_void_p]),
+    "gpemu_model_cross_validate": (C.c_int, [C.c_void_p, c_i64] + [C.c_void_p] * 6),
     "gpemu_likelihood_setup": (C.c_int, [C.c_void_p] + [C.c_void_p] * 4 + [C.c_double, c_i64, C.c_void_p]),
     "gpemu_likelihood_setup_chains": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_double, c_i64, C.c_void_p]),
     "gpemu_logpost": (C.c_int, [C.c_void_p, c_i64, C.c_void_p, C.c_void_p, C.c_int]),

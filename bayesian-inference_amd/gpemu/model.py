@@ -119,6 +119,49 @@ class DeviceModel:
                                             ptr(cv), ptr(cov)))
         return cv, cov
 
+    @staticmethod
+    def check_folds(fold, N):
+        """The fold labels as an int32 vector [N] and their number; ValueError unless every label is in
+        [0, n_folds), every fold is non-empty and 2 <= n_folds <= N (n_folds = max label + 1)."""
+        fold = np.asarray(fold)
+        if fold.shape != (N,):
+            raise ValueError(f"fold must hold one label per design point ({N}), got shape {fold.shape}")
+        if fold.size and not np.issubdtype(fold.dtype, np.integer):
+            if not np.all(np.isfinite(fold)) or not np.all(fold == np.round(fold)):
+                raise ValueError("fold labels must be integers")
+        fold = fold.astype(np.int64)
+        if fold.min() < 0:
+            raise ValueError("fold labels must be >= 0")
+        n_folds = int(fold.max()) + 1
+        if n_folds < 2:
+            raise ValueError("cross-validation needs at least 2 folds")
+        if n_folds > N:
+            raise ValueError(f"more folds ({n_folds}) than design points ({N})")
+        empty = np.flatnonzero(np.bincount(fold, minlength=n_folds) == 0)
+        if empty.size:
+            raise ValueError(f"fold {int(empty[0])} is empty")
+        return np.ascontiguousarray(fold, dtype=np.int32), n_folds
+
+    def cross_validate(self, y_train, fold):
+        """Cross-validation at the fitted hyper-parameters.
+
+        ``y_train`` (N, k) = the group's ``Y_pca_truncated``; ``fold`` (N,) = fold label of every design point
+        (0 .. n_folds - 1, every fold non-empty).  Each point is predicted by the GP of its PC refitted to the points
+        of the other folds with theta (``kernel_``), the scaler and the PCA held at the full-data fit -- what
+        ``GaussianProcessRegressor(kernel=gp.kernel_, alpha=alpha, optimizer=None).fit(X[R], y[R])
+        .predict(X[I], return_std=True)`` gives.  Returns ``mean_pc`` (N, k), ``var_pc`` (N, k) (std squared),
+        ``central_value`` (N, F) and ``variance`` (N, F), the diagonal of the reference's ``cov`` of one sample
+        (ref: emulation.py:466-548)."""
+        fold, n_folds = self.check_folds(fold, self.N)
+        y = as_f64(y_train, (self.N, self.k))
+        mean = np.empty((self.N, self.k))
+        var = np.empty((self.N, self.k))
+        cv = np.empty((self.N, self.F))
+        vo = np.empty((self.N, self.F))
+        check(_lib.lib().gpemu_model_cross_validate(self._h, n_folds, fold.ctypes.data_as(C.c_void_p), ptr(y),
+                                                    ptr(mean), ptr(var), ptr(cv), ptr(vo)))
+        return mean, var, cv, vo
+
     def likelihood_setup(self, y_exp, y_err, lo, hi, n_div=1.0, block_start=None):
         """Data, box prior and the observable block boundaries of this group (``block_start`` =
         first feature of each observable plus F at the end; None = a single block).  ``y_exp`` of shape (C, F):

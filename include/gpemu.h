@@ -103,6 +103,18 @@ int gpemu_predict_full(gpemu_model *m, int64_t B, const double *X, double n_div,
 int gpemu_predict_full_dev(gpemu_model *m, int64_t B, const double *dX, double n_div, double *dcv,
                            double *dcov, void *stream);
 
+/* Cross-validation of the group's emulators at their fitted theta: every point i is predicted by the GP
+ * fitted, at the same kernel_ hyper-parameters, to the points of the other folds -- what
+ * GaussianProcessRegressor(kernel=gp.kernel_, alpha, optimizer=None).fit(X[R], y[R]).predict(X[I], return_std=True)
+ * gives (skl _gpr.py:346-364, 441-494), from the closed form mu_I = y_I - (A_II)^-1 (A y)_I, var = diag((A_II)^-1) -
+ * alpha (clipped at 0), A = K^-1.  The scaler and the PCA stay at the full-data fit.
+ * fold[N]: labels in [0, n_folds), no fold empty, 2 <= n_folds <= N (else GPEMU_ERR_ARG).  y_train[N*k] = the group's
+ * Y_pca_truncated.  -> mean_pc[N*k], var_pc[N*k] (std squared, ref: emulation.py:497-499); central_value[N*F] and the
+ * diagonal of the reference's cov, variance[N*F], of predict_emulation_group for one sample (ref: emulation.py:466-548,
+ * n_div = 1); either may be NULL. */
+int gpemu_model_cross_validate(gpemu_model *m, int64_t n_folds, const int32_t *fold, const double *y_train,
+                               double *mean_pc, double *var_pc, double *central_value, double *variance);
+
 /* ref: log_posterior.py:63-64, 73-74, 92-94: box prior + experimental data for this group's
  * features (already gathered into the group's column order).  n_div as above (1 for MCMC).
  * block_start[n_blocks+1]: first feature of every observable of the group (ascending, 0 .. F).
