@@ -1,5 +1,6 @@
 // C ABI of libgpemu.so (see include/gpemu.h).  Host-side glue only: argument checks, device
 // memory ownership, launch sequencing.  All arithmetic is in the k_*.hip kernels.
+#include <atomic>
 #include <cmath>
 #include <cstdarg>
 
@@ -12,6 +13,12 @@
 namespace gpemu {
 
 static thread_local char g_err[512] = "";
+
+static std::atomic<int64_t> g_path_counts[GPEMU_PATH_COUNT];
+
+void path_count(int path) {
+  if (path >= 0 && path < GPEMU_PATH_COUNT) g_path_counts[path].fetch_add(1, std::memory_order_relaxed);
+}
 
 void set_error(const char *fmt, ...) {
   va_list ap;
@@ -144,6 +151,7 @@ int logpost_padded(gpemu_model *m, int64_t B, double *dXq, double *dout, int acc
     rc = launch_halfstep_small(one, 1, B, dXq, st, pa);
   }
   if (rc == GPEMU_ERR_UNSUPPORTED) {
+    path_count(GPEMU_PATH_HALFSTEP_GENERAL);
     rc = launch_kstar(m, B, dXq, st, pa);
     if (rc == GPEMU_OK) rc = launch_trmm_vsq(m, B, st);
   }
@@ -213,6 +221,12 @@ extern "C" {
 
 const char *gpemu_version(void) { return "gpemu 0.1 (gfx950)"; }
 const char *gpemu_last_error(void) { return g_err; }
+
+int gpemu_path_counts(int64_t *out, int64_t n) {
+  GP_ARG(out && n >= 0, "out, n");
+  for (int64_t i = 0; i < n && i < GPEMU_PATH_COUNT; ++i) out[i] = g_path_counts[i].load(std::memory_order_relaxed);
+  return GPEMU_PATH_COUNT;
+}
 
 int gpemu_device_count(void) {
   int n = 0;
@@ -480,6 +494,7 @@ static int gp_predict_core(gpemu_model *m, int64_t B, const double *dX, hipStrea
     const int rc = launch_halfstep_small(one, 1, B, m->ws.Xq, st, &raw);
     if (rc != GPEMU_ERR_UNSUPPORTED) return rc;
   }
+  if (small_ok) path_count(GPEMU_PATH_HALFSTEP_GENERAL);
   GP_TRY(launch_kstar(m, B, m->ws.Xq, st, &raw));
   GP_TRY(launch_trmm_vsq(m, B, st));
   return GPEMU_OK;
@@ -494,6 +509,7 @@ int gpemu_gp_predict_dev(gpemu_model *m, int64_t B, const double *dX, double *dm
   hipStream_t st = stream ? (hipStream_t)stream : m->stream;
   for (int64_t off = 0; off < B; off += MAX_CHUNK) {   // large batches go through in chunks
     const int64_t nb = (B - off < MAX_CHUNK) ? (B - off) : MAX_CHUNK;
+    path_count(GPEMU_PATH_PREDICT_PASS);
     GP_TRY(gp_predict_core(m, nb, dX + off * m->d, st));
     GP_TRY(launch_reduce_mean_var(m, nb, dmean + off * m->k, dvar + off * m->k, st));
   }
@@ -706,6 +722,7 @@ int gpemu_logpost_dev(gpemu_model *m, int64_t B, const double *dX, double *dout,
   hipStream_t st = stream ? (hipStream_t)stream : m->stream;
   for (int64_t off = 0; off < B; off += MAX_CHUNK) {
     const int64_t nb = (B - off < MAX_CHUNK) ? (B - off) : MAX_CHUNK;
+    path_count(GPEMU_PATH_PREDICT_PASS);
     GP_TRY(gp_predict_core(m, nb, dX + off * m->d, st, mode == GPEMU_LOGPOST_LOWRANK));
     if (mode == GPEMU_LOGPOST_LOWRANK) GP_TRY(launch_loglik_lowrank(m, nb, m->ws.Xq, dout + off, 0, st));
     else GP_TRY(launch_loglik_exact(m, nb, m->ws.Xq, dout + off, st));
@@ -807,6 +824,7 @@ int gpemu_predict_full_dev(gpemu_model *m, int64_t B, const double *dX, double n
   const int64_t F = m->F;
   for (int64_t off = 0; off < B; off += MAX_CHUNK) {
     const int64_t nb = (B - off < MAX_CHUNK) ? (B - off) : MAX_CHUNK;
+    path_count(GPEMU_PATH_PREDICT_PASS);
     GP_TRY(gp_predict_core(m, nb, dX + off * m->d, st));
     // no mean / variance arrays: the writer sums the GP stage's partials itself (one launch less)
     GP_TRY(launch_predict_full(m, nb, n_div, dcv + off * F, dcov + off * F * F, st, nullptr, nullptr));

@@ -35,6 +35,9 @@ void set_error(const char *fmt, ...);
 
 static inline int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
 
+// one relaxed host-side increment per launch decision (gpemu_path_counts; enum gpemu_path in gpemu.h)
+void path_count(int path);
+
 constexpr int DPAD = 8;        // parameter dimensions padded to 8 (reference uses d = 6 or 7)
 constexpr int TILE = 128;      // row / column tile of the triangular GEMM
 constexpr int KSTAR_ROWS_BIG = 64;    // training rows per workgroup of the cross-kernel: batches of more than 256 columns

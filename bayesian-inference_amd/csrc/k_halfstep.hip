@@ -414,6 +414,7 @@ int launch_halfstep_small(gpemu_model *const *ms, int ng, int64_t B, double *dXq
 #undef GP_LAUNCH_HS
   GP_HIP(hipGetLastError());
   g_halfstep_launches.fetch_add(1, std::memory_order_relaxed);
+  path_count(GPEMU_PATH_HALFSTEP_SMALL);
   return GPEMU_OK;
 }
 

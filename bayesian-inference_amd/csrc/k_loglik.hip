@@ -530,6 +530,7 @@ int launch_loglik_tasks(gpemu_model *const *ms, int ng, int64_t B, const double 
   hipLaunchKernelGGL(loglik_tasks_kernel, dim3((unsigned)(B * lt.nwg)), dim3(64 * LL_TASK_WAVES), 0, st, dXq, lt, dout, B,
                      (int)ms[0]->d, accumulate, a);
   GP_HIP(hipGetLastError());
+  path_count(lt.nwg == 1 ? GPEMU_PATH_LOGLIK_TASKS_ONE : B > 256 ? GPEMU_PATH_LOGLIK_TASKS_MULTI_BIG : GPEMU_PATH_LOGLIK_TASKS_MULTI);
   return GPEMU_OK;
 }
 
@@ -554,6 +555,7 @@ int launch_loglik_groups(gpemu_model *const *ms, int ng, int64_t B, const double
   hipLaunchKernelGGL(loglik_groups_kernel, dim3((unsigned)((B + wpw - 1) / wpw)), dim3(256), 0, st, dXq, lg, dout, B,
                      (int)ms[0]->d, accumulate, a);
   GP_HIP(hipGetLastError());
+  path_count(GPEMU_PATH_LOGLIK_GROUPS);
   return GPEMU_OK;
 }
 
@@ -599,6 +601,7 @@ int launch_loglik_lowrank(gpemu_model *m, int64_t B, const double *dXq, double *
   }
 #undef GP_LAUNCH_LL
   GP_HIP(hipGetLastError());
+  path_count(GPEMU_PATH_LOGLIK_LOWRANK);
   return GPEMU_OK;
 }
 

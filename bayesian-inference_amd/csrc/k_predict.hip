@@ -171,6 +171,13 @@ int trmm_xcd_of(const gpemu_model *m, int64_t B, int p, int64_t col) {
   return (p * ncbp + (int)(col / TILE) % ncbp) / (ngroups / 8);
 }
 
+// which cross-kernel instance a launch takes (gpemu_path_counts)
+static void kstar_count(const gpemu_model *m, bool small) {
+  path_count(small ? GPEMU_PATH_KSTAR_SMALL : GPEMU_PATH_KSTAR_BIG);
+  path_count(m->ksteps == 2 ? GPEMU_PATH_KSTAR_KSTEPS2 : GPEMU_PATH_KSTAR_KSTEPS3);
+  if (kstar_kind(m) == 1 || (kstar_kind(m) == 4 && m->nu < 1.0)) path_count(GPEMU_PATH_KSTAR_DIRECT);
+}
+
 // arguments and grid of one group's cross-kernel for a batch of B columns (sets the workspace's chunk count)
 static KstarArgs kstar_setup(gpemu_model *m, int64_t B, double *dXq, int &nwg, bool &small) {
   // only the column tiles that hold real queries; without a proposal / raw rows, the rows of dXq up to
@@ -229,6 +236,7 @@ int launch_kstar(gpemu_model *m, int64_t B, double *dXq, hipStream_t st, const P
   GP_KSTAR_DISPATCH(kstar_kind(m), m->ksteps, small, GP_LAUNCH_ONE);
 #undef GP_LAUNCH_ONE
   GP_HIP(hipGetLastError());
+  kstar_count(m, small);
   prof_pair(m, 1, pe0, prof_mark(m, st));
   return GPEMU_OK;
 }
@@ -251,6 +259,7 @@ int launch_kstar_groups(gpemu_model *const *ms, int ng, int64_t B, double *dXq, 
   GP_KSTAR_DISPATCH(kstar_kind(ms[0]), ms[0]->ksteps, small, GP_LAUNCH_GROUPS);
 #undef GP_LAUNCH_GROUPS
   GP_HIP(hipGetLastError());
+  kstar_count(ms[0], small);
   return GPEMU_OK;
 }
 
@@ -558,23 +567,32 @@ static void build_trmm_schedule(gpemu_model *m, int ncb, std::vector<TrmmItem> &
   }
 }
 
+static int launch_trmm_vsq_one(gpemu_model *m, int64_t B, hipStream_t st, bool piece);
+
 int launch_trmm_vsq(gpemu_model *m, int64_t B, hipStream_t st) {
   Workspace &w = m->ws;
-  constexpr int64_t smallb_max = 128;
-  const int64_t Bv = m->variant_B > 0 ? m->variant_B : B;   // a chain stacked with others is evaluated as it would be alone
   const int64_t per = trmm_piece_cols(m, B);
   if (per < round_up(B, TILE)) {     // one launch per piece; the column partials of a piece land where a single launch would put them
+    path_count(GPEMU_PATH_TRMM_DMA_PIECES);
     double *const KS0 = w.KS, *const V0 = w.vsq_part;
     int rc = GPEMU_OK;
     for (int64_t c0 = 0; c0 < B && rc == GPEMU_OK; c0 += per) {
       w.KS = KS0 + c0;
       w.vsq_part = V0 + c0 * m->k * m->vsq_nrb;
-      rc = launch_trmm_vsq(m, std::min(per, B - c0), st);
+      rc = launch_trmm_vsq_one(m, std::min(per, B - c0), st, true);
     }
     w.KS = KS0;
     w.vsq_part = V0;
     return rc;
   }
+  return launch_trmm_vsq_one(m, B, st, false);
+}
+
+// one launch of the triangular GEMM for B columns (a whole batch, or one piece of it)
+static int launch_trmm_vsq_one(gpemu_model *m, int64_t B, hipStream_t st, bool piece) {
+  Workspace &w = m->ws;
+  constexpr int64_t smallb_max = 128;
+  const int64_t Bv = m->variant_B > 0 ? m->variant_B : B;   // a chain stacked with others is evaluated as it would be alone
   if (Bv <= smallb_max) {  // small batch: persistent 32 x 32 items, operands straight into registers
     const int rc = launch_trmm_vsq_small(m, B, st);
     if (rc != GPEMU_ERR_UNSUPPORTED) return rc;
@@ -583,6 +601,7 @@ int launch_trmm_vsq(gpemu_model *m, int64_t B, hipStream_t st) {
       return rc;
     }
     // a shape with more items per worker than the small-batch kernel holds: the large-batch kernel with every item halved
+    path_count(GPEMU_PATH_TRMM_SMALL_FALLBACK);
   }
   w.cur_nrb = (int)m->vsq_nrb;
   const int nrb = (int)m->vsq_nrb;
@@ -614,6 +633,10 @@ int launch_trmm_vsq(gpemu_model *m, int64_t B, hipStream_t st) {
     m->sched_items = hit->items; m->sched_cnt = hit->cnt;
     m->sched_ncb = ncb; m->sched_cap = cap; m->sched_max_items = hit->max_items; m->sched_workers = hit->workers;
   }
+  if (!piece) path_count(GPEMU_PATH_TRMM_DMA_WHOLE);
+  // build_trmm_schedule's XCD-aware placement: every CU a worker, whole groups per XCD
+  const bool xcd = m->sched_workers == cap && cap % 8 == 0 && ((int)m->k * ncb) % 8 == 0;
+  path_count(xcd ? GPEMU_PATH_TRMM_DMA_XCD : GPEMU_PATH_TRMM_DMA_LPT);
   const int pe0 = prof_mark(m, st);
 #ifdef GPEMU_TRMM_STAMPS
   // diagnostic build only (make STAMPS=1; tools/trmm_balance.py): per-worker time stamps of launch 600, dumped to the

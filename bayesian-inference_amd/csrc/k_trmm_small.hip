@@ -320,6 +320,15 @@ int launch_trmm_vsq_small(gpemu_model *m, int64_t B, hipStream_t st) {
   const int rc = small_schedule_ready(m, B, st);
   if (rc != GPEMU_OK) return rc;
   w.cur_nrb = nrb;
+  {
+    // build_small_schedule's placement, from the shape (the schedule itself is cached)
+    const int ncb = (int)(round_up(B, ST_N) / ST_N);
+    const int ncu = m->num_cu * small_workers_per_cu((int64_t)nrb * m->k * ncb, m->num_cu);
+    if (m->sm_workers < ncu) path_count(GPEMU_PATH_TRMM_SMALL_FEW_ITEMS);
+    else if (ncu % 8 == 0 && (int)m->k * ncb >= 8) path_count(GPEMU_PATH_TRMM_SMALL_XCD);
+    else path_count(GPEMU_PATH_TRMM_SMALL_LEFTOVER);
+    path_count(m->sm_workers > 2 * m->num_cu ? GPEMU_PATH_TRMM_SMALL_36 : GPEMU_PATH_TRMM_SMALL_44);
+  }
   const int pe0 = prof_mark(m, st);
   if (m->sm_workers > 2 * m->num_cu)
     hipLaunchKernelGGL((trmm_vsq_small_kernel<3, 6>), dim3((unsigned)m->sm_workers), dim3(512), 0, st, m->Wt, w.KS, w.vsq_part,
@@ -373,6 +382,7 @@ int launch_trmm_vsq_small_groups(gpemu_model *const *ms, int ng, int64_t B, hipS
   }
   hipLaunchKernelGGL(trmm_vsq_small_groups_kernel, dim3((unsigned)sg.start[ng]), dim3(512), 0, st, sg);
   GP_HIP(hipGetLastError());
+  path_count(GPEMU_PATH_TRMM_SMALL_44);
   return GPEMU_OK;
 }
 

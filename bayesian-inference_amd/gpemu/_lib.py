@@ -102,6 +102,7 @@ _SIGNATURES = {
     "gpemu_sampler_snapshot": (C.c_int, [C.c_void_p]),
     "gpemu_sampler_restore": (C.c_int, [C.c_void_p]),
     "gpemu_halfstep_small_launches": (C.c_int64, []),
+    "gpemu_path_counts": (C.c_int, [C.POINTER(c_i64), c_i64]),
     "gpemu_philox4x32": (C.c_int, [C.c_uint32] * 6 + [C.POINTER(C.c_uint32)]),
 }
 

@@ -312,6 +312,37 @@ int gpemu_sampler_restore(gpemu_sampler *s);
  * batched log-posterior take there).  For tests: which path ran.  GPEMU_NO_HALFSTEP=1 switches that path off. */
 int64_t gpemu_halfstep_small_launches(void);
 
+/* Launch decisions so far, in this process, per path of the predict / likelihood pipeline (host-side counters, one
+ * relaxed increment per decision; nothing on the device).  For tests: which tiling, schedule and epilogue ran. */
+enum gpemu_path {
+  GPEMU_PATH_KSTAR_SMALL = 0,        /* cross-kernel, B <= KSTAR_SMALL_MAX columns (32-row workgroups)              */
+  GPEMU_PATH_KSTAR_BIG,              /* cross-kernel, more columns (64-row workgroups)                               */
+  GPEMU_PATH_KSTAR_KSTEPS2,          /* cross-kernel with 2 MFMA k-steps (d <= 7)                                    */
+  GPEMU_PATH_KSTAR_KSTEPS3,          /* ... 3 k-steps (d = 8)                                                        */
+  GPEMU_PATH_KSTAR_DIRECT,           /* the instance with the direct distance of near pairs (Matern 0.5, nu < 1)     */
+  GPEMU_PATH_TRMM_SMALL_44,          /* small-batch triangular GEMM, trmm_vsq_small_kernel<4,4>                      */
+  GPEMU_PATH_TRMM_SMALL_36,          /* ... <3,6> (at least 5 num_cu items)                                          */
+  GPEMU_PATH_TRMM_SMALL_XCD,         /* ... XCD-aware placement of whole (PC, column block) groups                  */
+  GPEMU_PATH_TRMM_SMALL_LEFTOVER,    /* ... every group left over (fewer than 8 groups): plain LPT                  */
+  GPEMU_PATH_TRMM_SMALL_FEW_ITEMS,   /* ... fewer items than workers                                                 */
+  GPEMU_PATH_TRMM_SMALL_FALLBACK,    /* ... more than ST_MAX_ITEMS items per worker: the large-batch kernel instead */
+  GPEMU_PATH_TRMM_DMA_LPT,           /* large-batch trmm_vsq_dma_kernel, plain LPT schedule                          */
+  GPEMU_PATH_TRMM_DMA_XCD,           /* ... XCD-aware schedule                                                       */
+  GPEMU_PATH_TRMM_DMA_WHOLE,         /* ... the batch in one launch                                                  */
+  GPEMU_PATH_TRMM_DMA_PIECES,        /* ... the batch split into pieces of trmm_piece_cols (counted once per batch)  */
+  GPEMU_PATH_HALFSTEP_SMALL,         /* one-launch cross-kernel + GEMM for small emulators (k_halfstep.hip)          */
+  GPEMU_PATH_HALFSTEP_GENERAL,       /* the same request on the general cross-kernel + GEMM launches                 */
+  GPEMU_PATH_LOGLIK_LOWRANK,         /* loglik_lowrank_kernel / _lds_kernel                                          */
+  GPEMU_PATH_LOGLIK_GROUPS,          /* loglik_groups_kernel                                                         */
+  GPEMU_PATH_LOGLIK_TASKS_ONE,       /* loglik_tasks_kernel, one workgroup per proposal                              */
+  GPEMU_PATH_LOGLIK_TASKS_MULTI,     /* ... several workgroups per proposal (tickets), at most 256 rows               */
+  GPEMU_PATH_LOGLIK_TASKS_MULTI_BIG, /* ... several workgroups per proposal, more than 256 rows                       */
+  GPEMU_PATH_PREDICT_PASS,           /* one pass of at most MAX_CHUNK (2048) rows of the predict pipeline            */
+  GPEMU_PATH_COUNT
+};
+/* out[0 .. min(n, GPEMU_PATH_COUNT)) = the counters; returns GPEMU_PATH_COUNT (or GPEMU_ERR_ARG for out == NULL, n < 0). */
+int gpemu_path_counts(int64_t *out, int64_t n);
+
 /* Philox4x32-10 block function (host copy of the device generator; for tests) */
 int gpemu_philox4x32(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
                      uint32_t *out4);
