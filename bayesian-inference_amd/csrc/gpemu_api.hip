@@ -15,9 +15,14 @@ namespace gpemu {
 static thread_local char g_err[512] = "";
 
 static std::atomic<int64_t> g_path_counts[GPEMU_PATH_COUNT];
+static std::atomic<int64_t> g_fit_path_counts[GPEMU_FIT_PATH_COUNT];
 
 void path_count(int path) {
   if (path >= 0 && path < GPEMU_PATH_COUNT) g_path_counts[path].fetch_add(1, std::memory_order_relaxed);
+}
+
+void fit_path_count(int path) {
+  if (path >= 0 && path < GPEMU_FIT_PATH_COUNT) g_fit_path_counts[path].fetch_add(1, std::memory_order_relaxed);
 }
 
 void set_error(const char *fmt, ...) {
@@ -226,6 +231,12 @@ int gpemu_path_counts(int64_t *out, int64_t n) {
   GP_ARG(out && n >= 0, "out, n");
   for (int64_t i = 0; i < n && i < GPEMU_PATH_COUNT; ++i) out[i] = g_path_counts[i].load(std::memory_order_relaxed);
   return GPEMU_PATH_COUNT;
+}
+
+int gpemu_fit_path_counts(int64_t *out, int64_t n) {
+  GP_ARG(out && n >= 0, "out, n");
+  for (int64_t i = 0; i < n && i < GPEMU_FIT_PATH_COUNT; ++i) out[i] = g_fit_path_counts[i].load(std::memory_order_relaxed);
+  return GPEMU_FIT_PATH_COUNT;
 }
 
 int gpemu_device_count(void) {

@@ -37,6 +37,7 @@ static inline int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * 
 
 // one relaxed host-side increment per launch decision (gpemu_path_counts; enum gpemu_path in gpemu.h)
 void path_count(int path);
+void fit_path_count(int path);   // the same for enum gpemu_fit_path (gpemu_fit_path_counts)
 
 constexpr int DPAD = 8;        // parameter dimensions padded to 8 (reference uses d = 6 or 7)
 constexpr int TILE = 128;      // row / column tile of the triangular GEMM

@@ -880,9 +880,13 @@ int device_cholesky_blocked(double *A, int64_t Np, double *Dinv, int *dinfo, hip
   for (int jb0 = 0; jb0 < nblk; jb0 += chol_q) {
     const int jb1 = std::min(nblk, jb0 + chol_q);             // the panel: blocks [jb0, jb1)
     if (fused) {
+      fit_path_count(GPEMU_FIT_PATH_CHOL_PANEL);
+      if (heads_one_xcd && nblk - jb0 >= 32) fit_path_count(GPEMU_FIT_PATH_CHOL_HEADS_ONE_XCD);   // (the kernel's own condition)
       hipLaunchKernelGGL(chol_panel_kernel, dim3((unsigned)(nblk - jb0), (unsigned)nb), dim3(256), 0, st, A, Np, Dinv, jb0,
                          jb1 - jb0, dinfo, ov->flags, jb0 / chol_q + 1, Np * Np, Np * NB, fault, heads_one_xcd);
       GP_HIP(hipGetLastError());
+    } else {
+      fit_path_count(GPEMU_FIT_PATH_CHOL_STEPS);
     }
     for (int jb = jb0; jb < jb1 && !fused; ++jb) {
       const int64_t j0 = (int64_t)jb * NB;
@@ -931,6 +935,7 @@ int device_cholesky_blocked(double *A, int64_t Np, double *Dinv, int *dinfo, hip
     if (rc != GPEMU_OK) return rc;
     if (t1 < Np) {
       GP_HIP(hipStreamWaitEvent(ov->side, ov->panel_done, 0));
+      fit_path_count(GPEMU_FIT_PATH_CHOL_LOOKAHEAD);
       rc = update(t1, t1, Np, k0, t0, ov->side);
       if (rc != GPEMU_OK) return rc;
       GP_HIP(hipEventRecord(ov->rest_done, ov->side));
@@ -985,6 +990,7 @@ int device_trtri_blocked(const double *L, int64_t Np, const double *Dinv, double
       if (rc != GPEMU_OK) return rc;
     }
     if (rem > b) {                                           // a ragged pair: (b, rem - b)
+      fit_path_count(GPEMU_FIT_PATH_TRTRI_RAGGED);
       int rc = merge(nfull * 2 * b, rem - b, 1);
       if (rc != GPEMU_OK) return rc;
     }
@@ -1316,6 +1322,8 @@ struct gpemu_fit {
   int *info = nullptr;
   int n_gparts = 0;
   int cap = 0;              // problems the workspace holds (fit_reserve)
+  int last_nb = 0;          // problems of the last completed evaluation, and whether it formed K^-1 (gpemu_fit_workspace)
+  bool last_grad = false;
   bool counted = false;     // in g_live_fit_handles (the panel kernel's head placement rule)
 };
 
@@ -1339,29 +1347,36 @@ static int fit_kind_of(int kernel_kind, double nu) {
 
 static void launch_kmat(const gpemu_fit *f, int64_t N, int nb, double jitter, hipStream_t st) {
   const dim3 grid((unsigned)((f->Np + 255) / 256), (unsigned)((f->Np + KMAT_ROWS - 1) / KMAT_ROWS), (unsigned)nb);
+  fit_path_count(f->kind == 4 ? GPEMU_FIT_PATH_KMAT_NU : GPEMU_FIT_PATH_KMAT);
   if (f->kind == 4)
     hipLaunchKernelGGL(kmat_nu_kernel, grid, dim3(256), 0, st, f->X, f->hp, f->K, (int)N, (int)f->Np, f->mnu, jitter);
   else
     hipLaunchKernelGGL(kmat_kernel, grid, dim3(256), 0, st, f->X, f->hp, f->K, (int)N, (int)f->Np, f->kind, jitter);
 }
 
+// the workspace's buffers of doubles and their lengths per problem: fn(pointer, doubles per problem)
+template <class Fn>
+static void fit_buffers(gpemu_fit *f, Fn fn) {
+  const int64_t Np = f->Np;
+  fn(&f->hp, DPAD + 2); fn(&f->K, Np * Np); fn(&f->Dinv, Np * NB); fn(&f->W, Np * Np); fn(&f->T, Np * Np);
+  fn(&f->Kinv, Np * Np); fn(&f->y, Np); fn(&f->v, Np); fn(&f->alpha, Np);
+  fn(&f->gpart, (int64_t)f->n_gparts * NTH_MAX); fn(&f->scal, 4); fn(&f->grad, NTH_MAX);
+  fn(&f->gstage, (int64_t)GR_BLOCKS * NTH_MAX);
+}
+
 // workspace for `nb` problems evaluated together (one set of matrices each)
 static int fit_reserve(gpemu_fit *f, int nb) {
   if (nb <= f->cap) return GPEMU_OK;
   GP_HIP(hipStreamSynchronize(f->stream));
-  double **ptrs[] = {&f->hp, &f->K, &f->Dinv, &f->W, &f->T, &f->Kinv, &f->y, &f->v, &f->alpha, &f->gpart, &f->scal,
-                     &f->grad, &f->gstage};
-  for (double **p : ptrs) { (void)hipFree(*p); *p = nullptr; }
+  fit_buffers(f, [](double **p, int64_t) { (void)hipFree(*p); *p = nullptr; });
   (void)hipFree(f->info);
   f->info = nullptr;
   f->cap = 0;
-  const int64_t Np = f->Np;
+  f->last_nb = 0;
   hipError_t e = hipSuccess;
-  auto A = [&](double **p, int64_t n) { if (e == hipSuccess) e = hipMalloc((void **)p, sizeof(double) * (size_t)(n > 0 ? n : 1) * nb); };
-  A(&f->hp, DPAD + 2); A(&f->K, Np * Np); A(&f->Dinv, Np * NB); A(&f->W, Np * Np); A(&f->T, Np * Np);
-  A(&f->Kinv, Np * Np); A(&f->y, Np); A(&f->v, Np); A(&f->alpha, Np);
-  A(&f->gpart, (int64_t)f->n_gparts * NTH_MAX); A(&f->scal, 4); A(&f->grad, NTH_MAX);
-  A(&f->gstage, (int64_t)GR_BLOCKS * NTH_MAX);
+  fit_buffers(f, [&](double **p, int64_t n) {
+    if (e == hipSuccess) e = hipMalloc((void **)p, sizeof(double) * (size_t)(n > 0 ? n : 1) * nb);
+  });
   if (e == hipSuccess) e = hipMalloc((void **)&f->info, sizeof(int) * nb);
   (void)hipFree(f->overlap.flags);
   f->overlap.flags = nullptr;
@@ -1381,6 +1396,8 @@ static int fit_eval_batch(gpemu_fit *f, int nb, const double *ys, const double *
   GP_ARG(n_theta == nth, "n_theta must be d (+1 constant) (+1 noise)");
   GP_ARG(nb >= 1, "empty batch");
   GP_TRY(fit_reserve(f, nb));
+  if (nb > 1) fit_path_count(GPEMU_FIT_PATH_BATCH);
+  f->last_nb = 0;                  // (gpemu_fit_workspace: nothing valid until this evaluation has run through)
   hipStream_t st = f->stream;
   std::vector<double> hp((size_t)nb * (DPAD + 2)), hy((size_t)nb * Np, 0.0);
   for (int z = 0; z < nb; ++z) {
@@ -1429,6 +1446,7 @@ static int fit_eval_batch(gpemu_fit *f, int nb, const double *ys, const double *
     int npairs = 0;
     for (int y = 0; y < ngroups; ++y) npairs += y / 16 + 1;
     dim3 grid((unsigned)npairs, 1, (unsigned)nb);
+    fit_path_count(f->kind == 4 ? GPEMU_FIT_PATH_GRAD_NU : GPEMU_FIT_PATH_GRAD);
     if (f->kind == 4)
       hipLaunchKernelGGL(lml_grad_nu_kernel, grid, dim3(256), 0, st, f->X, f->hp, f->alpha, f->Kinv, Np, f->gpart, (int)N,
                          (int)d, f->mnu, f->has_const, f->has_noise);
@@ -1446,6 +1464,8 @@ static int fit_eval_batch(gpemu_fit *f, int nb, const double *ys, const double *
   GP_HIP(hipMemcpyAsync(info.data(), f->info, sizeof(int) * nb, hipMemcpyDeviceToHost, st));
   if (want_grad) GP_HIP(hipMemcpyAsync(hg.data(), f->grad, sizeof(double) * hg.size(), hipMemcpyDeviceToHost, st));
   GP_HIP(hipStreamSynchronize(st));
+  f->last_nb = nb;
+  f->last_grad = want_grad;
   int first_bad = 0;
   for (int z = 0; z < nb; ++z) {
     if (info_out) info_out[z] = info[z];
@@ -1582,6 +1602,37 @@ int gpemu_fit_factor(gpemu_fit *f, const double *y, const double *theta, int64_t
     for (int64_t i = 0; i < N; ++i)
       for (int64_t j = i + 1; j < N; ++j) L_out[i * N + j] = 0.0;   // only the lower triangle is the factor
   }
+  return GPEMU_OK;
+}
+
+int gpemu_fit_workspace(gpemu_fit *f, int which, int64_t z, double *out) {
+  GP_ARG(f && out, "null pointer");
+  GP_ARG(which == GPEMU_FIT_WS_L || which == GPEMU_FIT_WS_W || which == GPEMU_FIT_WS_KINV, "which");
+  if (f->last_nb == 0 || (which == GPEMU_FIT_WS_KINV && !f->last_grad)) {
+    set_error("fit_workspace: no %s from the last evaluation", which == GPEMU_FIT_WS_KINV ? "K^-1" : "factor");
+    return GPEMU_ERR_STATE;
+  }
+  GP_ARG(z >= 0 && z < f->last_nb, "z: problem of the last evaluation");
+  GP_HIP(hipSetDevice(f->device));
+  const int64_t N = f->N, Np = f->Np;
+  const double *src = (which == GPEMU_FIT_WS_L ? f->K : which == GPEMU_FIT_WS_W ? f->W : f->Kinv) + z * Np * Np;
+  GP_HIP(hipStreamSynchronize(f->stream));
+  GP_HIP(hipMemcpy2D(out, sizeof(double) * N, src, sizeof(double) * Np, sizeof(double) * N, (size_t)N, hipMemcpyDeviceToHost));
+  for (int64_t i = 0; i < N; ++i)
+    for (int64_t j = i + 1; j < N; ++j) out[i * N + j] = 0.0;   // what lies above is not part of the result
+  return GPEMU_OK;
+}
+
+int gpemu_fit_poison(gpemu_fit *f) {
+  GP_ARG(f, "null pointer");
+  GP_HIP(hipSetDevice(f->device));
+  hipError_t e = hipSuccess;
+  fit_buffers(f, [&](double **p, int64_t n) {
+    if (e == hipSuccess && *p) e = hipMemsetAsync(*p, 0xff, sizeof(double) * (size_t)(n > 0 ? n : 1) * f->cap, f->stream);
+  });
+  if (e == hipSuccess) e = hipStreamSynchronize(f->stream);
+  if (e != hipSuccess) { set_error("fit_poison: %s", hipGetErrorString(e)); return GPEMU_ERR_HIP; }
+  f->last_nb = 0;
   return GPEMU_OK;
 }
 

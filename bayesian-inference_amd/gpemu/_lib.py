@@ -62,6 +62,8 @@ _SIGNATURES = {
     "gpemu_fit_lml_batch": (C.c_int, [C.c_void_p, c_i64, C.c_void_p, C.c_void_p, c_i64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gpemu_fit_factor": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, c_i64, C.c_void_p, C.c_void_p,
                                    C.POINTER(C.c_double)]),
+    "gpemu_fit_workspace": (C.c_int, [C.c_void_p, C.c_int, c_i64, C.c_void_p]),
+    "gpemu_fit_poison": (C.c_int, [C.c_void_p]),
     "gpemu_kernel_matrix": (C.c_int, [C.c_int, c_i64, c_i64, C.c_void_p, C.c_void_p, c_i64, C.c_int, C.c_double,
                                       C.c_int, C.c_int, C.c_double, C.c_void_p]),
     "gpemu_cholesky": (C.c_int, [C.c_int, c_i64, C.c_void_p]),
@@ -103,6 +105,7 @@ _SIGNATURES = {
     "gpemu_sampler_restore": (C.c_int, [C.c_void_p]),
     "gpemu_halfstep_small_launches": (C.c_int64, []),
     "gpemu_path_counts": (C.c_int, [C.POINTER(c_i64), c_i64]),
+    "gpemu_fit_path_counts": (C.c_int, [C.POINTER(c_i64), c_i64]),
     "gpemu_philox4x32": (C.c_int, [C.c_uint32] * 6 + [C.POINTER(C.c_uint32)]),
 }
 

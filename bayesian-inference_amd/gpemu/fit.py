@@ -93,6 +93,20 @@ class DeviceFit:
                                                 C.byref(val)))
         return L, alpha, val.value
 
+    # ---- for the tests only (include/gpemu.h: gpemu_fit_workspace, gpemu_fit_poison) ----
+    WORKSPACE = {"L": 0, "W": 1, "Kinv": 2}
+
+    def workspace(self, which, z=0):
+        """problem ``z`` of the last evaluation as the handle holds it: ``which`` = "L" (the factor), "W" (L^-1) or
+        "Kinv" (after an evaluation with gradient); (N, N), lower triangle."""
+        out = np.empty((self.N, self.N))
+        check(_lib.lib().gpemu_fit_workspace(self._h, self.WORKSPACE[which], int(z), ptr(out)))
+        return out
+
+    def poison(self):
+        """fill the whole device workspace with NaN bytes (0xff)"""
+        check(_lib.lib().gpemu_fit_poison(self._h))
+
 
 def kernel_matrix(X, theta, kernel_kind=0, nu=np.inf, has_const=False, has_noise=False, jitter=0.0, device=None):
     device = _lib.resolve_device(device)

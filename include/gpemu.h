@@ -343,6 +343,40 @@ enum gpemu_path {
 /* out[0 .. min(n, GPEMU_PATH_COUNT)) = the counters; returns GPEMU_PATH_COUNT (or GPEMU_ERR_ARG for out == NULL, n < 0). */
 int gpemu_path_counts(int64_t *out, int64_t n);
 
+/* The same for the fit side (csrc/k_fit.hip: gpemu_fit_*, gpemu_kernel_matrix, gpemu_cholesky and the factorisations
+ * of the model, likelihood and cross-validation setup that share its Cholesky and inverse).  A set of its own, so that
+ * the predict / likelihood set above keeps its size and indices. */
+enum gpemu_fit_path {
+  GPEMU_FIT_PATH_KMAT = 0,           /* kernel matrix, kmat_kernel (RBF, Matern 0.5 / 1.5 / 2.5)                      */
+  GPEMU_FIT_PATH_KMAT_NU,            /* ... kmat_nu_kernel (Matern of general nu)                                     */
+  GPEMU_FIT_PATH_CHOL_PANEL,         /* blocked Cholesky: one fused chol_panel_kernel launch per 256-wide panel       */
+  GPEMU_FIT_PATH_CHOL_STEPS,         /* ... one panel of the three-launch steps (diagonal factor, solve, update)      */
+  GPEMU_FIT_PATH_CHOL_LOOKAHEAD,     /* ... one look-ahead update of the columns beyond the next panel, side stream   */
+  GPEMU_FIT_PATH_CHOL_HEADS_ONE_XCD, /* ... one fused panel launch with its four heads placed on one XCD              */
+  GPEMU_FIT_PATH_TRTRI_RAGGED,       /* triangular inverse: one merge of a ragged pair (second block shorter)        */
+  GPEMU_FIT_PATH_GRAD,               /* LML gradient, lml_grad_kernel                                                 */
+  GPEMU_FIT_PATH_GRAD_NU,            /* ... lml_grad_nu_kernel                                                        */
+  GPEMU_FIT_PATH_BATCH,              /* one fit evaluation of more than one problem at once                           */
+  GPEMU_FIT_PATH_COUNT
+};
+/* out[0 .. min(n, GPEMU_FIT_PATH_COUNT)) = the counters; returns GPEMU_FIT_PATH_COUNT (or GPEMU_ERR_ARG). */
+int gpemu_fit_path_counts(int64_t *out, int64_t n);
+
+/* ---- fit handle: test-only entry points ---------------------------------------------------------------------------
+ * For the tests of the fit side only; nothing in the library's own flow calls them.
+ * gpemu_fit_workspace: out[N*N] = problem z of the last evaluation (gpemu_fit_lml / _lml_batch / _factor) as the
+ * handle holds it, the lower triangle (zeros above the diagonal): which = GPEMU_FIT_WS_L (the Cholesky factor),
+ * GPEMU_FIT_WS_W (its inverse W = L^-1) or GPEMU_FIT_WS_KINV (K^-1 = W^T W: only after an evaluation with gradient,
+ * else GPEMU_ERR_STATE).  z >= the last evaluation's number of problems: GPEMU_ERR_ARG.
+ * gpemu_fit_poison: every byte of the handle's workspace (K, Dinv, W, T, K^-1, y, v, alpha, gpart, gstage, scal, grad,
+ * hyper-parameters) set to 0xff -- a NaN in every double -- on the handle's stream: an evaluation that reads anything
+ * it has not written first shows it. */
+#define GPEMU_FIT_WS_L 0
+#define GPEMU_FIT_WS_W 1
+#define GPEMU_FIT_WS_KINV 2
+int gpemu_fit_workspace(gpemu_fit *f, int which, int64_t z, double *out);
+int gpemu_fit_poison(gpemu_fit *f);
+
 /* Philox4x32-10 block function (host copy of the device generator; for tests) */
 int gpemu_philox4x32(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
                      uint32_t *out4);
