@@ -16,6 +16,7 @@ static thread_local char g_err[512] = "";
 
 static std::atomic<int64_t> g_path_counts[GPEMU_PATH_COUNT];
 static std::atomic<int64_t> g_fit_path_counts[GPEMU_FIT_PATH_COUNT];
+static std::atomic<int64_t> g_wide_path_counts[GPEMU_WIDE_PATH_COUNT];
 
 void path_count(int path) {
   if (path >= 0 && path < GPEMU_PATH_COUNT) g_path_counts[path].fetch_add(1, std::memory_order_relaxed);
@@ -23,6 +24,10 @@ void path_count(int path) {
 
 void fit_path_count(int path) {
   if (path >= 0 && path < GPEMU_FIT_PATH_COUNT) g_fit_path_counts[path].fetch_add(1, std::memory_order_relaxed);
+}
+
+void wide_path_count(int path) {
+  if (path >= 0 && path < GPEMU_WIDE_PATH_COUNT) g_wide_path_counts[path].fetch_add(1, std::memory_order_relaxed);
 }
 
 void set_error(const char *fmt, ...) {
@@ -69,7 +74,7 @@ int ensure_workspace(gpemu_model *m, int64_t B) {
   GP_HIP(hipStreamSynchronize(m->stream));
   free_workspace(w);
   const int64_t k = m->k;
-  GP_TRY(dev_alloc(&w.Xq, need * DPAD));
+  GP_TRY(dev_alloc(&w.Xq, need * m->dp));
   GP_TRY(dev_alloc(&w.KS, k * m->Npad * need));
   GP_TRY(dev_alloc(&w.mean_part, k * (m->Npad / 32) * need));   // sized for the 32-row small-batch form
   GP_TRY(dev_alloc(&w.mean_part2, k * (m->Npad / 32) * need));
@@ -78,7 +83,7 @@ int ensure_workspace(gpemu_model *m, int64_t B) {
   GP_TRY(dev_alloc(&w.var, need * k));
   GP_TRY(dev_alloc(&w.logp, need));
   GP_HIP(hipMemsetAsync(w.KS, 0, sizeof(double) * (size_t)(k * m->Npad * need), m->stream));
-  GP_HIP(hipMemsetAsync(w.Xq, 0, sizeof(double) * (size_t)(need * DPAD), m->stream));
+  GP_HIP(hipMemsetAsync(w.Xq, 0, sizeof(double) * (size_t)(need * m->dp), m->stream));
   GP_HIP(hipMemsetAsync(w.vsq_part, 0, sizeof(double) * (size_t)(k * (m->Npad / 32) * need), m->stream));
   // the caller's launches may go to ANOTHER stream (a sampler over several groups runs every group on the first
   // group's stream): the zero fill must have landed before anything writes the new buffers (found by the shipped
@@ -142,7 +147,7 @@ static int check_device(int device) {
 }  // namespace gpemu
 
 namespace gpemu {
-// Log-posterior of B query rows already in the padded [rows >= round_up(B,128)][DPAD] layout
+// Log-posterior of B query rows already in the padded [rows >= round_up(B,128)][m->dp] layout
 // (the sampler writes its proposals in that layout).  accumulate != 0 adds to dout (multi-group).
 int logpost_padded(gpemu_model *m, int64_t B, double *dXq, double *dout, int accumulate,
                    hipStream_t st, const AcceptArgs *aa, const ProposeArgs *pa) {
@@ -239,6 +244,12 @@ int gpemu_fit_path_counts(int64_t *out, int64_t n) {
   return GPEMU_FIT_PATH_COUNT;
 }
 
+int gpemu_wide_path_counts(int64_t *out, int64_t n) {
+  GP_ARG(out && n >= 0, "out, n");
+  for (int64_t i = 0; i < n && i < GPEMU_WIDE_PATH_COUNT; ++i) out[i] = g_wide_path_counts[i].load(std::memory_order_relaxed);
+  return GPEMU_WIDE_PATH_COUNT;
+}
+
 int gpemu_device_count(void) {
   int n = 0;
   if (hipGetDeviceCount(&n) != hipSuccess) return 0;
@@ -281,7 +292,7 @@ int gpemu_model_create(gpemu_model **out, int device, int64_t N, int64_t d, int6
   GP_ARG(out, "out");
   *out = nullptr;
   GP_ARG(N > 0 && d > 0 && F > 0 && k > 0, "N, d, F, k must be positive");
-  GP_ARG(d <= DPAD, "d > 8 parameters is not supported by this build");
+  GP_ARG(d <= DPAD_WIDE, "d > 16 parameters is not supported by this build");
   GP_ARG(k <= 64, "k > 64 principal components is not supported by this build");
   GP_ARG(kernel_kind == GPEMU_KERNEL_RBF || kernel_kind == GPEMU_KERNEL_MATERN, "kernel_kind");
   if (kernel_kind == GPEMU_KERNEL_MATERN) GP_ARG(nu > 0.0, "Matern nu must be > 0 (finite or +inf; not NaN)");
@@ -294,6 +305,7 @@ int gpemu_model_create(gpemu_model **out, int device, int64_t N, int64_t d, int6
   gpemu_model *m = new gpemu_model();
   m->device = device;
   m->N = N; m->d = d; m->F = F; m->k = k;
+  m->dp = dpad_of(d);
   m->Npad = round_up(N, TILE);
   m->vsq_nrb = m->Npad / 64;
   {
@@ -321,18 +333,19 @@ int gpemu_model_create(gpemu_model **out, int device, int64_t N, int64_t d, int6
   // nu < 1) recompute the distance of near-coincident pairs from the coordinates (predict_dev.h: KstarDirect)
   const int kkind = kstar_kind(m);
   const bool direct = kkind == 1 || (kkind == 4 && nu < 1.0);
-  std::vector<double> hXs(direct ? (size_t)(k * Np * DPAD) : 0, 0.0), hls((size_t)(k * DPAD), 1.0),
+  const int dp = m->dp;
+  std::vector<double> hXs(direct ? (size_t)(k * Np * dp) : 0, 0.0), hls((size_t)(k * dp), 1.0),
       hc((size_t)k, 0.0), hkd((size_t)k, 1.0), hal((size_t)(k * Np), 0.0), hjit((size_t)k, 0.0);
   for (int64_t p = 0; p < k; ++p) {
     for (int64_t dd = 0; dd < d; ++dd) {
       double l = ls[p * d + dd];
       if (!(l > 0.0)) { set_error("length scale must be positive"); return fail(GPEMU_ERR_ARG); }
-      hls[p * DPAD + dd] = l;
+      hls[p * dp + dd] = l;
     }
     if (direct)
       for (int64_t j = 0; j < N; ++j)
         for (int64_t dd = 0; dd < d; ++dd)
-          hXs[(p * Np + j) * DPAD + dd] = X_train[j * d + dd] / ls[p * d + dd];  // skl: X / length_scale
+          hXs[(p * Np + j) * dp + dd] = X_train[j * d + dd] / ls[p * d + dd];  // skl: X / length_scale
     if (has_const) { hc[p] = constv[p]; hkd[p] += constv[p]; }
     if (has_noise) hkd[p] += noise[p];
     for (int64_t j = 0; j < N; ++j) hal[p * Np + j] = alpha[p * N + j];
@@ -340,7 +353,7 @@ int gpemu_model_create(gpemu_model **out, int device, int64_t N, int64_t d, int6
     hjit[p] = std::fma(L[p * N * N], L[p * N * N], -hkd[p]);
   }
 #define GP_STEP(expr) if ((rc = (expr)) != GPEMU_OK) return fail(rc)
-  GP_STEP(dev_alloc(&m->ls, k * DPAD));
+  GP_STEP(dev_alloc(&m->ls, k * dp));
   GP_STEP(dev_alloc(&m->constv, k));
   GP_STEP(dev_alloc(&m->kdiag, k));
   GP_STEP(dev_alloc(&m->alpha, k * Np));
@@ -351,7 +364,7 @@ int gpemu_model_create(gpemu_model **out, int device, int64_t N, int64_t d, int6
   GP_STEP(dev_alloc(&m->sscale, F));
   GP_STEP(dev_alloc(&m->cunexpl, F * F));
   GP_STEP(dev_alloc(&dL, k * N * N));
-  GP_STEP(upload(m->ls, hls.data(), k * DPAD, st));
+  GP_STEP(upload(m->ls, hls.data(), k * dp, st));
   {
     // the cross-kernel's operands for the matrix cores (kstar_host.h)
     KstarHost kh;
@@ -376,10 +389,10 @@ int gpemu_model_create(gpemu_model **out, int device, int64_t N, int64_t d, int6
     std::vector<double> hinv(hls.size());
     if (direct) {
       for (size_t i = 0; i < hls.size(); ++i) hinv[i] = 1.0 / hls[i];
-      GP_STEP(dev_alloc(&m->Xs, k * Np * DPAD));
-      GP_STEP(dev_alloc(&m->inv_ls, k * DPAD));
-      GP_STEP(upload(m->Xs, hXs.data(), k * Np * DPAD, st));
-      GP_STEP(upload(m->inv_ls, hinv.data(), k * DPAD, st));
+      GP_STEP(dev_alloc(&m->Xs, k * Np * dp));
+      GP_STEP(dev_alloc(&m->inv_ls, k * dp));
+      GP_STEP(upload(m->Xs, hXs.data(), k * Np * dp, st));
+      GP_STEP(upload(m->inv_ls, hinv.data(), k * dp, st));
     }
     if (hipStreamSynchronize(st) != hipSuccess) {   // the staging vectors go out of scope
       set_error("model_create: upload failed");
@@ -669,7 +682,7 @@ int gpemu_likelihood_setup_chains(gpemu_model *m, int n_chains, const double *y_
   GP_HIP(hipStreamSynchronize(st));
   if (!m->yerr) {
     GP_TRY(dev_alloc(&m->yerr, F));
-    GP_TRY(dev_alloc(&m->lo, DPAD)); GP_TRY(dev_alloc(&m->hi, DPAD));
+    GP_TRY(dev_alloc(&m->lo, m->dp)); GP_TRY(dev_alloc(&m->hi, m->dp));
     GP_TRY(dev_alloc(&m->blk_of, F));
   }
   (void)hipFree(m->yexp);
@@ -689,10 +702,10 @@ int gpemu_likelihood_setup_chains(gpemu_model *m, int n_chains, const double *y_
   m->lik_ready = false;
   m->lik_host.clear();
   m->n_div = n_div;
-  double hlo[DPAD], hhi[DPAD];
-  for (int i = 0; i < DPAD; ++i) { hlo[i] = i < m->d ? lo[i] : -INFINITY; hhi[i] = i < m->d ? hi[i] : INFINITY; }
+  double hlo[DPAD_WIDE], hhi[DPAD_WIDE];
+  for (int i = 0; i < m->dp; ++i) { hlo[i] = i < m->d ? lo[i] : -INFINITY; hhi[i] = i < m->d ? hi[i] : INFINITY; }
   GP_TRY(upload(m->yexp, y_exp, NC * F, st)); GP_TRY(upload(m->yerr, y_err, F, st));
-  GP_TRY(upload(m->lo, hlo, DPAD, st)); GP_TRY(upload(m->hi, hhi, DPAD, st));
+  GP_TRY(upload(m->lo, hlo, m->dp, st)); GP_TRY(upload(m->hi, hhi, m->dp, st));
   GP_HIP(hipStreamSynchronize(st));  // hlo/hhi are stack buffers
   double *dA = nullptr, *dPT = nullptr, *dZ = nullptr;
   int *dinfo = nullptr;

@@ -38,8 +38,12 @@ static inline int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * 
 // one relaxed host-side increment per launch decision (gpemu_path_counts; enum gpemu_path in gpemu.h)
 void path_count(int path);
 void fit_path_count(int path);   // the same for enum gpemu_fit_path (gpemu_fit_path_counts)
+void wide_path_count(int path);  // ... and for enum gpemu_wide_path (gpemu_wide_path_counts): d > 8 only
 
-constexpr int DPAD = 8;        // parameter dimensions padded to 8 (reference uses d = 6 or 7)
+constexpr int DPAD = 8;        // parameter dimensions padded to 8 (reference uses d = 6 or 7) ...
+constexpr int DPAD_WIDE = 16;  // ... or, for 9 <= d <= 16, to 16 (separate instantiations: d <= 8 keeps the code of DPAD)
+// padded width of a d-parameter model, fit handle or sampler: the row stride of every padded layout
+__host__ __device__ inline int dpad_of(int64_t d) { return d <= DPAD ? DPAD : DPAD_WIDE; }
 constexpr int TILE = 128;      // row / column tile of the triangular GEMM
 constexpr int KSTAR_ROWS_BIG = 64;    // training rows per workgroup of the cross-kernel: batches of more than 256 columns
 constexpr int KSTAR_ROWS_SMALL = 32;  // ... and of at most KSTAR_SMALL_MAX
@@ -48,7 +52,7 @@ constexpr int KSTAR_SMALL_MAX = 128;  // (256 until round 4: at 129 .. 256 colum
 // ---- device model -----------------------------------------------------------------------------
 struct Workspace {
   int64_t Bcap = 0;            // padded batch capacity (multiple of TILE)
-  double *Xq = nullptr;        // [Bcap][DPAD]   query points (padded with 0)
+  double *Xq = nullptr;        // [Bcap][dp]     query points (padded with 0; dp: the model's padded width)
   double *KS = nullptr;        // [k][Npad][Bcap] cross-kernel K_*^T per PC
   double *mean_part = nullptr; // [Bcap][k][nchunk] partial K_* . alpha per 64- (or 32-) row chunk
   double *mean_part2 = nullptr; // second copy: the fused sampler run reads one half-step's while the next is written
@@ -65,6 +69,7 @@ struct Workspace {
 struct gpemu_model {
   int device = 0;
   int64_t N = 0, d = 0, F = 0, k = 0;
+  int dp = gpemu::DPAD;        // padded width of every [..][dp] layout below: dpad_of(d), 8 or 16
   int64_t Npad = 0;            // N rounded up to TILE
   int num_cu = 256;
   // LPT schedule of the persistent triangular GEMM for the current number of column tiles
@@ -96,16 +101,16 @@ struct gpemu_model {
 
   // per-PC GP state on the device
   // cross-kernel operands for the matrix cores (kstar_host.h; predict_dev.h: kstar_mfma_block)
-  int ksteps = 2;              // MFMA k-steps of the augmented product: 4 ksteps >= d + 1
+  int ksteps = 2;              // MFMA k-steps of the augmented product: 4 ksteps >= d + 1 (2, 3 at dp 8; 3 .. 5 at dp 16)
   double *Xa = nullptr;        // [k][Npad/16][ksteps][64]  augmented, centred training rows in A-fragment order
   double *alf = nullptr;       // [k][Npad/16][16]          alpha in accumulator-row order
   double *qsc = nullptr;       // [k][4 ksteps]             query side: q' = q qsc + qof
   double *qof = nullptr;
   double *etab = nullptr;      // [2^KSTAR_TB]              2^(j / 2^KSTAR_TB)  (kind 4: + the MaternNu of nu)
   // Matern-0.5 and general nu < 1 only (the direct distance of near-coincident pairs): row-major scaled rows, else null
-  double *Xs = nullptr;        // [k][Npad][DPAD]  X_train / ls_p  (padded rows/dims = 0)
-  double *inv_ls = nullptr;    // [k][DPAD]        1 / ls (the query side multiplies; the training side X / ls is exact)
-  double *ls = nullptr;        // [k][DPAD]        length scales (padded dims = 1)
+  double *Xs = nullptr;        // [k][Npad][dp]  X_train / ls_p  (padded rows/dims = 0)
+  double *inv_ls = nullptr;    // [k][dp]        1 / ls (the query side multiplies; the training side X / ls is exact)
+  double *ls = nullptr;        // [k][dp]        length scales (padded dims = 1)
   double *constv = nullptr;    // [k]
   double *kdiag = nullptr;     // [k]  kernel_.diag = 1 (+const) (+noise)
   double *alpha = nullptr;     // [k][Npad] (padded = 0)
@@ -129,7 +134,7 @@ struct gpemu_model {
   struct LikEntry { double n_div; double *G, *g0, *scal; };
   std::vector<LikEntry> lik_cache;
   std::vector<double> lik_host;        // y_exp | y_err | lo | hi | block starts the cache belongs to
-  double *yexp = nullptr, *yerr = nullptr, *lo = nullptr, *hi = nullptr;  // [F],[F],[DPAD],[DPAD]
+  double *yexp = nullptr, *yerr = nullptr, *lo = nullptr, *hi = nullptr;  // [F],[F],[dp],[dp]
   int64_t nblk = 1;            // observable blocks of the (block-diagonal) covariance
   int *blk_start = nullptr;    // [nblk+1] first feature of each block
   int *blk_of = nullptr;       // [F]      block index of each feature
@@ -156,7 +161,7 @@ namespace gpemu {
 // optional fused stretch-move finish (accept / reject + chain record) for the walker of each proposal
 struct AcceptArgs {
   int enabled = 0;
-  double *X = nullptr;            // [W][DPAD] ensemble positions (updated in place)
+  double *X = nullptr;            // [W][dp] ensemble positions (updated in place)
   double *logp = nullptr;         // [W]
   const int *idx_s = nullptr;     // [ns] walker of proposal i
   const double *factors = nullptr;  // [ns] (d-1) log zz
@@ -169,20 +174,21 @@ struct AcceptArgs {
   // chain_per rows per chain; 0 = one chain.  Selects the chain's data constants (g0, q0) in the likelihood.
   int chain_per = 0;
   int64_t first = 0;
+  int dp = DPAD;                  // padded width of X and of the query rows (the models' dp)
 };
 
 // optional fused stretch-move proposal: kstar_kernel builds its query rows from the ensemble
 // (q_i = c[rint_i] - (c[rint_i] - s_i) zz_i, emcee moves/stretch.py) instead of reading them
 struct ProposeArgs {
   int enabled = 0;
-  const double *X = nullptr;      // [W][DPAD]
+  const double *X = nullptr;      // [W][dpad_of(d)]
   const int *idx_s = nullptr;     // [n] walker of proposal i (already offset to the evaluated slice)
   const double *zz = nullptr;     // [n]
   const int *partner = nullptr;   // [n] walker index of the complementary-set member drawn for proposal i
   double *factors = nullptr;      // [n] out: (d - 1) log zz
   int n = 0, d = 0;
   // enabled == 0 and raw != nullptr: the queries come as caller rows [n][d] (gpemu_gp_predict / predict_full); the
-  // kernel pads them to [..][DPAD] on the fly and stores the padded rows once (what pad_queries_kernel used to do)
+  // kernel pads them to [..][dpad_of(d)] on the fly and stores the padded rows once (what pad_queries_kernel used to do)
   const double *raw = nullptr;
 };
 

@@ -534,7 +534,7 @@ __global__ __launch_bounds__(CHOL_THREADS) void loglik_exact_kernel(
     __syncthreads();
     if (tid == 0) {
       int in = 1;
-      for (int dd = 0; dd < d; ++dd) in &= (Xq[b * DPAD + dd] > lo[dd]) && (Xq[b * DPAD + dd] < hi[dd]);
+      for (int dd = 0; dd < d; ++dd) in &= (Xq[b * dpad_of(d) + dd] > lo[dd]) && (Xq[b * dpad_of(d) + dd] < hi[dd]);
       s_inside = in;
     }
     if (tid < k) {

@@ -42,25 +42,26 @@ __device__ __forceinline__ double base_from_r2(int kind, double r2) {
   return (1.0 + t + t * t / 3.0) * exp(-t);
 }
 
-// X [Np][DPAD] raw inputs; hp = {ls[DPAD], const, noise}; K[i][j] for i,j < N, identity tail
+// X [Np][DP] raw inputs; hp = {ls[DP], const, noise}; K[i][j] for i,j < N, identity tail (DP: the handle's padded width)
 // blockIdx.z: problem of a batch (own hyper-parameters and matrix, shared inputs)
 constexpr int KMAT_ROWS = 16;     // rows of K per workgroup: the scaled coordinates of column j are formed once for all of them
+template <int DP>
 __global__ __launch_bounds__(256) void kmat_kernel(const double *__restrict__ X, const double *__restrict__ hp,
                                                    double *__restrict__ K, int N, int Np, int kind, double jitter) {
-  __shared__ double s_xi[KMAT_ROWS][DPAD];
+  __shared__ double s_xi[KMAT_ROWS][DP];
   const int j = blockIdx.x * blockDim.x + threadIdx.x;
   const int i0 = blockIdx.y * KMAT_ROWS;
-  hp += (int64_t)blockIdx.z * (DPAD + 2);
+  hp += (int64_t)blockIdx.z * (DP + 2);
   K += (int64_t)blockIdx.z * Np * Np;
   // skl: X / length_scale, then the difference -- the quotients are the same numbers whoever forms them
-  if (threadIdx.x < KMAT_ROWS * DPAD) {
-    const int r = threadIdx.x / DPAD, dd = threadIdx.x % DPAD;
-    s_xi[r][dd] = (i0 + r < N) ? X[(i0 + r) * DPAD + dd] / hp[dd] : 0.0;
+  if (threadIdx.x < KMAT_ROWS * DP) {
+    const int r = threadIdx.x / DP, dd = threadIdx.x % DP;
+    s_xi[r][dd] = (i0 + r < N) ? X[(i0 + r) * DP + dd] / hp[dd] : 0.0;
   }
-  double xj[DPAD];
+  double xj[DP];
 #pragma unroll
-  for (int dd = 0; dd < DPAD; ++dd) xj[dd] = (j < N) ? X[j * DPAD + dd] / hp[dd] : 0.0;
-  const double cst = hp[DPAD], diag = 1.0 + hp[DPAD] + hp[DPAD + 1] + jitter;   // np.fill_diagonal(K, 1) + const + noise + alpha
+  for (int dd = 0; dd < DP; ++dd) xj[dd] = (j < N) ? X[j * DP + dd] / hp[dd] : 0.0;
+  const double cst = hp[DP], diag = 1.0 + hp[DP] + hp[DP + 1] + jitter;   // np.fill_diagonal(K, 1) + const + noise + alpha
   __syncthreads();
   if (j >= Np) return;
   for (int r = 0; r < KMAT_ROWS; ++r) {
@@ -74,7 +75,7 @@ __global__ __launch_bounds__(256) void kmat_kernel(const double *__restrict__ X,
     } else {
       double r2 = 0.0;
 #pragma unroll
-      for (int dd = 0; dd < DPAD; ++dd) {
+      for (int dd = 0; dd < DP; ++dd) {
         const double df = s_xi[r][dd] - xj[dd];
         r2 = fma(df, df, r2);
       }
@@ -86,22 +87,23 @@ __global__ __launch_bounds__(256) void kmat_kernel(const double *__restrict__ X,
 
 // kind 4 (Matern, general nu: matern_dev.h): kmat_kernel with the general value -- a kernel of its own, so that the
 // instance that serves kinds 0-3 keeps its code
+template <int DP>
 __global__ __launch_bounds__(256) void kmat_nu_kernel(const double *__restrict__ X, const double *__restrict__ hp,
                                                       double *__restrict__ K, int N, int Np, MaternNu mn, double jitter) {
-  __shared__ double s_xi[KMAT_ROWS][DPAD];
+  __shared__ double s_xi[KMAT_ROWS][DP];
   const int j = blockIdx.x * blockDim.x + threadIdx.x;
   const int i0 = blockIdx.y * KMAT_ROWS;
-  hp += (int64_t)blockIdx.z * (DPAD + 2);
+  hp += (int64_t)blockIdx.z * (DP + 2);
   K += (int64_t)blockIdx.z * Np * Np;
   // skl: X / length_scale, then the difference -- the quotients are the same numbers whoever forms them
-  if (threadIdx.x < KMAT_ROWS * DPAD) {
-    const int r = threadIdx.x / DPAD, dd = threadIdx.x % DPAD;
-    s_xi[r][dd] = (i0 + r < N) ? X[(i0 + r) * DPAD + dd] / hp[dd] : 0.0;
+  if (threadIdx.x < KMAT_ROWS * DP) {
+    const int r = threadIdx.x / DP, dd = threadIdx.x % DP;
+    s_xi[r][dd] = (i0 + r < N) ? X[(i0 + r) * DP + dd] / hp[dd] : 0.0;
   }
-  double xj[DPAD];
+  double xj[DP];
 #pragma unroll
-  for (int dd = 0; dd < DPAD; ++dd) xj[dd] = (j < N) ? X[j * DPAD + dd] / hp[dd] : 0.0;
-  const double cst = hp[DPAD], diag = 1.0 + hp[DPAD] + hp[DPAD + 1] + jitter;   // np.fill_diagonal(K, 1) + const + noise + alpha
+  for (int dd = 0; dd < DP; ++dd) xj[dd] = (j < N) ? X[j * DP + dd] / hp[dd] : 0.0;
+  const double cst = hp[DP], diag = 1.0 + hp[DP] + hp[DP + 1] + jitter;   // np.fill_diagonal(K, 1) + const + noise + alpha
   __syncthreads();
   if (j >= Np) return;
   for (int r = 0; r < KMAT_ROWS; ++r) {
@@ -115,7 +117,7 @@ __global__ __launch_bounds__(256) void kmat_nu_kernel(const double *__restrict__
     } else {
       double r2 = 0.0;
 #pragma unroll
-      for (int dd = 0; dd < DPAD; ++dd) {
+      for (int dd = 0; dd < DP; ++dd) {
         const double df = s_xi[r][dd] - xj[dd];
         r2 = fma(df, df, r2);
       }
@@ -1089,14 +1091,17 @@ __global__ __launch_bounds__(1024) void lml_terms_kernel(const double *__restric
 // ---- gradient contraction --------------------------------------------------------------------------
 // gpart[block][t] = 1/2 sum over this block's (j, l) of (alpha_j alpha_l - Kinv_jl) dK_jl/dtheta_t
 // theta order: log l_1..l_d, (log const), (log noise)   (skl kernels.py:733-760, Sum :861-866)
-constexpr int NTH_MAX = DPAD + 2;
+// NTH = DP + 2 slots per partial sum (the padded width's length scales, const, noise), whatever d is
+static inline int64_t nth_max(int dp) { return dp + 2; }
 constexpr int GRAD_ROWS = 16;
+template <int DP>
 __global__ __launch_bounds__(256) void lml_grad_kernel(const double *__restrict__ X, const double *__restrict__ hp,
                                                        const double *__restrict__ alpha,
                                                        const double *__restrict__ Kinv, int64_t ld,
                                                        double *__restrict__ gpart, int N, int d, int kind,
                                                        int has_const, int has_noise) {
-  __shared__ double red[NTH_MAX][4];
+  constexpr int NTH = DP + 2;
+  __shared__ double red[NTH][4];
   // 1-D grid over the (row group, 256-column block) pairs that reach under the diagonal only (half of the full grid's
   // workgroups would start to find nothing to do): row groups 16 b .. 16 b + 15 have b + 1 blocks, so position
   // t = (b + 1)(8 b + r) + x  <->  row group 16 b + r, block x
@@ -1107,17 +1112,17 @@ __global__ __launch_bounds__(256) void lml_grad_kernel(const double *__restrict_
   const int by = 16 * b + rem / (b + 1), bx = rem % (b + 1);
   const int l = bx * blockDim.x + threadIdx.x;
   const int j0 = by * GRAD_ROWS;                       // this workgroup's rows j0 .. j0 + GRAD_ROWS - 1 (one reduction for all)
-  hp += (int64_t)blockIdx.z * (DPAD + 2);              // blockIdx.z: problem of a batch
+  hp += (int64_t)blockIdx.z * (DP + 2);              // blockIdx.z: problem of a batch
   alpha += (int64_t)blockIdx.z * ld;
   Kinv += (int64_t)blockIdx.z * ld * ld;
-  gpart += (int64_t)blockIdx.z * gridDim.x * NTH_MAX;
-  double acc[NTH_MAX];
+  gpart += (int64_t)blockIdx.z * gridDim.x * NTH;
+  double acc[NTH];
 #pragma unroll
-  for (int t = 0; t < NTH_MAX; ++t) acc[t] = 0.0;
-  double xl[DPAD], il2[DPAD];
+  for (int t = 0; t < NTH; ++t) acc[t] = 0.0;
+  double xl[DP], il2[DP];
 #pragma unroll
-  for (int dd = 0; dd < DPAD; ++dd) {
-    xl[dd] = (l < N) ? X[l * DPAD + dd] : 0.0;
+  for (int dd = 0; dd < DP; ++dd) {
+    xl[dd] = (l < N) ? X[l * DP + dd] : 0.0;
     il2[dd] = 1.0 / (hp[dd] * hp[dd]);      // once per thread; a division per pair and dimension was 4/5 of this kernel
   }
   const double al = (l < N) ? alpha[l] : 0.0;
@@ -1125,10 +1130,10 @@ __global__ __launch_bounds__(256) void lml_grad_kernel(const double *__restrict_
   for (int j = j0; j < j0 + GRAD_ROWS && j < N; ++j) {
     if (l > j) continue;
     const double wgt = (l < j ? 2.0 : 1.0) * (alpha[j] * al - Kinv[(int64_t)j * ld + l]);
-    double D[DPAD], r2 = 0.0;
+    double D[DP], r2 = 0.0;
 #pragma unroll
-    for (int dd = 0; dd < DPAD; ++dd) {
-      double df = X[j * DPAD + dd] - xl[dd];
+    for (int dd = 0; dd < DP; ++dd) {
+      double df = X[j * DP + dd] - xl[dd];
       D[dd] = (df * df) * il2[dd];             // (x - x')^2 / l^2   (skl kernels.py:1574, 1748)
       r2 += D[dd];
     }
@@ -1145,31 +1150,42 @@ __global__ __launch_bounds__(256) void lml_grad_kernel(const double *__restrict_
       f = 5.0 / 3.0 * (tmp + 1.0) * exp(-tmp);                    // 5/3 D (tmp + 1) exp(-tmp)
     }
 #pragma unroll
-    for (int dd = 0; dd < DPAD; ++dd) acc[dd] += 0.5 * wgt * f * D[dd];
-    if (has_const) acc[d] += 0.5 * wgt * hp[DPAD];
-    if (has_noise && j == l) acc[d + has_const] += 0.5 * wgt * hp[DPAD + 1];
+    for (int dd = 0; dd < DP; ++dd) acc[dd] += 0.5 * wgt * f * D[dd];
+    if constexpr (DP == DPAD) {
+      if (has_const) acc[d] += 0.5 * wgt * hp[DP];
+      if (has_noise && j == l) acc[d + has_const] += 0.5 * wgt * hp[DP + 1];
+    } else {
+      // the same two additions with compile-time slots: a runtime index into 18 registers puts acc in scratch
+#pragma unroll
+      for (int t = 0; t < NTH; ++t) {
+        if (has_const && t == d) acc[t] += 0.5 * wgt * hp[DP];
+        if (has_noise && j == l && t == d + has_const) acc[t] += 0.5 * wgt * hp[DP + 1];
+      }
+    }
   }
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
-  for (int t = 0; t < NTH_MAX; ++t) {
+  for (int t = 0; t < NTH; ++t) {
     double s = acc[t];
     for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
     if (lane == 0) red[t][wave] = s;
   }
   __syncthreads();
-  if (threadIdx.x < NTH_MAX) {
+  if (threadIdx.x < NTH) {
     const int t = threadIdx.x;
-    gpart[(int64_t)blockIdx.x * NTH_MAX + t] = (red[t][0] + red[t][1]) + (red[t][2] + red[t][3]);
+    gpart[(int64_t)blockIdx.x * NTH + t] = (red[t][0] + red[t][1]) + (red[t][2] + red[t][3]);
   }
 }
 
 // kind 4: lml_grad_kernel with the general-nu derivative (matern_dev.h: matern_nu_value_grad), a kernel of its own
+template <int DP>
 __global__ __launch_bounds__(256) void lml_grad_nu_kernel(const double *__restrict__ X, const double *__restrict__ hp,
                                                           const double *__restrict__ alpha,
                                                           const double *__restrict__ Kinv, int64_t ld,
                                                           double *__restrict__ gpart, int N, int d, MaternNu mn,
                                                           int has_const, int has_noise) {
-  __shared__ double red[NTH_MAX][4];
+  constexpr int NTH = DP + 2;
+  __shared__ double red[NTH][4];
   // 1-D grid over the (row group, 256-column block) pairs that reach under the diagonal only (half of the full grid's
   // workgroups would start to find nothing to do): row groups 16 b .. 16 b + 15 have b + 1 blocks, so position
   // t = (b + 1)(8 b + r) + x  <->  row group 16 b + r, block x
@@ -1180,17 +1196,17 @@ __global__ __launch_bounds__(256) void lml_grad_nu_kernel(const double *__restri
   const int by = 16 * b + rem / (b + 1), bx = rem % (b + 1);
   const int l = bx * blockDim.x + threadIdx.x;
   const int j0 = by * GRAD_ROWS;                       // this workgroup's rows j0 .. j0 + GRAD_ROWS - 1 (one reduction for all)
-  hp += (int64_t)blockIdx.z * (DPAD + 2);              // blockIdx.z: problem of a batch
+  hp += (int64_t)blockIdx.z * (DP + 2);              // blockIdx.z: problem of a batch
   alpha += (int64_t)blockIdx.z * ld;
   Kinv += (int64_t)blockIdx.z * ld * ld;
-  gpart += (int64_t)blockIdx.z * gridDim.x * NTH_MAX;
-  double acc[NTH_MAX];
+  gpart += (int64_t)blockIdx.z * gridDim.x * NTH;
+  double acc[NTH];
 #pragma unroll
-  for (int t = 0; t < NTH_MAX; ++t) acc[t] = 0.0;
-  double xl[DPAD], il2[DPAD];
+  for (int t = 0; t < NTH; ++t) acc[t] = 0.0;
+  double xl[DP], il2[DP];
 #pragma unroll
-  for (int dd = 0; dd < DPAD; ++dd) {
-    xl[dd] = (l < N) ? X[l * DPAD + dd] : 0.0;
+  for (int dd = 0; dd < DP; ++dd) {
+    xl[dd] = (l < N) ? X[l * DP + dd] : 0.0;
     il2[dd] = 1.0 / (hp[dd] * hp[dd]);      // once per thread; a division per pair and dimension was 4/5 of this kernel
   }
   const double al = (l < N) ? alpha[l] : 0.0;
@@ -1198,61 +1214,74 @@ __global__ __launch_bounds__(256) void lml_grad_nu_kernel(const double *__restri
   for (int j = j0; j < j0 + GRAD_ROWS && j < N; ++j) {
     if (l > j) continue;
     const double wgt = (l < j ? 2.0 : 1.0) * (alpha[j] * al - Kinv[(int64_t)j * ld + l]);
-    double D[DPAD], r2 = 0.0;
+    double D[DP], r2 = 0.0;
 #pragma unroll
-    for (int dd = 0; dd < DPAD; ++dd) {
-      double df = X[j * DPAD + dd] - xl[dd];
+    for (int dd = 0; dd < DP; ++dd) {
+      double df = X[j * DP + dd] - xl[dd];
       D[dd] = (df * df) * il2[dd];             // (x - x')^2 / l^2   (skl kernels.py:1574, 1748)
       r2 += D[dd];
     }
     double f;  // dK_base/dlog l_dd = f * D[dd]: analytic (skl: forward difference, kernels.py:1767-1774)
     (void)matern_nu_value_grad(mn, sqrt(r2), f);
 #pragma unroll
-    for (int dd = 0; dd < DPAD; ++dd) acc[dd] += 0.5 * wgt * f * D[dd];
-    if (has_const) acc[d] += 0.5 * wgt * hp[DPAD];
-    if (has_noise && j == l) acc[d + has_const] += 0.5 * wgt * hp[DPAD + 1];
+    for (int dd = 0; dd < DP; ++dd) acc[dd] += 0.5 * wgt * f * D[dd];
+    if constexpr (DP == DPAD) {
+      if (has_const) acc[d] += 0.5 * wgt * hp[DP];
+      if (has_noise && j == l) acc[d + has_const] += 0.5 * wgt * hp[DP + 1];
+    } else {
+      // the same two additions with compile-time slots: a runtime index into 18 registers puts acc in scratch
+#pragma unroll
+      for (int t = 0; t < NTH; ++t) {
+        if (has_const && t == d) acc[t] += 0.5 * wgt * hp[DP];
+        if (has_noise && j == l && t == d + has_const) acc[t] += 0.5 * wgt * hp[DP + 1];
+      }
+    }
   }
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
-  for (int t = 0; t < NTH_MAX; ++t) {
+  for (int t = 0; t < NTH; ++t) {
     double s = acc[t];
     for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
     if (lane == 0) red[t][wave] = s;
   }
   __syncthreads();
-  if (threadIdx.x < NTH_MAX) {
+  if (threadIdx.x < NTH) {
     const int t = threadIdx.x;
-    gpart[(int64_t)blockIdx.x * NTH_MAX + t] = (red[t][0] + red[t][1]) + (red[t][2] + red[t][3]);
+    gpart[(int64_t)blockIdx.x * NTH + t] = (red[t][0] + red[t][1]) + (red[t][2] + red[t][3]);
   }
 }
 
 // two-stage deterministic sum of the partial gradients: GR_BLOCKS workgroups each sum a contiguous slice ...
 constexpr int GR_BLOCKS = 128;
+template <int DP>
 __global__ __launch_bounds__(256) void grad_reduce_stage1_kernel(const double *__restrict__ gpart, int nparts,
                                                                  double *__restrict__ stage, int nth) {
+  constexpr int NTH = DP + 2;
   __shared__ double part[4];
-  gpart += (int64_t)blockIdx.y * nparts * NTH_MAX;     // blockIdx.y: problem of a batch
-  stage += (int64_t)blockIdx.y * GR_BLOCKS * NTH_MAX;
+  gpart += (int64_t)blockIdx.y * nparts * NTH;     // blockIdx.y: problem of a batch
+  stage += (int64_t)blockIdx.y * GR_BLOCKS * NTH;
   const int per = (nparts + GR_BLOCKS - 1) / GR_BLOCKS;
   const int i0 = blockIdx.x * per, i1 = (i0 + per < nparts) ? i0 + per : nparts;
   for (int t = 0; t < nth; ++t) {
     double s = 0.0;
-    for (int i = i0 + threadIdx.x; i < i1; i += 256) s += gpart[(int64_t)i * NTH_MAX + t];
+    for (int i = i0 + threadIdx.x; i < i1; i += 256) s += gpart[(int64_t)i * NTH + t];
     for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
     __syncthreads();
     if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s;
     __syncthreads();
-    if (threadIdx.x == 0) stage[blockIdx.x * NTH_MAX + t] = (part[0] + part[1]) + (part[2] + part[3]);
+    if (threadIdx.x == 0) stage[blockIdx.x * NTH + t] = (part[0] + part[1]) + (part[2] + part[3]);
   }
 }
 
 // ... and one workgroup sums the GR_BLOCKS slices
+template <int DP>
 __global__ __launch_bounds__(64) void grad_reduce_kernel(const double *__restrict__ stage, double *__restrict__ grad, int nth) {
-  stage += (int64_t)blockIdx.x * GR_BLOCKS * NTH_MAX;  // blockIdx.x: problem of a batch
-  grad += blockIdx.x * NTH_MAX;
+  constexpr int NTH = DP + 2;
+  stage += (int64_t)blockIdx.x * GR_BLOCKS * NTH;  // blockIdx.x: problem of a batch
+  grad += blockIdx.x * NTH;
   for (int t = 0; t < nth; ++t) {
     double s = 0.0;
-    for (int i = threadIdx.x; i < GR_BLOCKS; i += 64) s += stage[i * NTH_MAX + t];
+    for (int i = threadIdx.x; i < GR_BLOCKS; i += 64) s += stage[i * NTH + t];
     for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
     if (threadIdx.x == 0) grad[t] = s;
   }
@@ -1311,6 +1340,7 @@ int device_invert_factor_to_Wt(const double *dL, int64_t N, double *Wt, int64_t 
 struct gpemu_fit {
   int device = 0;
   int64_t N = 0, d = 0, Np = 0;
+  int dp = gpemu::DPAD;                  // padded parameter width of X and hp: DPAD (d <= 8) or DPAD_WIDE
   int kind = 0, has_const = 0, has_noise = 0;   // kind: fit_kind_of
   gpemu::MaternNu mnu{};           // kind 4: the constants of nu (matern_dev.h)
   double jitter = 0.0;
@@ -1347,21 +1377,30 @@ static int fit_kind_of(int kernel_kind, double nu) {
 
 static void launch_kmat(const gpemu_fit *f, int64_t N, int nb, double jitter, hipStream_t st) {
   const dim3 grid((unsigned)((f->Np + 255) / 256), (unsigned)((f->Np + KMAT_ROWS - 1) / KMAT_ROWS), (unsigned)nb);
-  fit_path_count(f->kind == 4 ? GPEMU_FIT_PATH_KMAT_NU : GPEMU_FIT_PATH_KMAT);
-  if (f->kind == 4)
-    hipLaunchKernelGGL(kmat_nu_kernel, grid, dim3(256), 0, st, f->X, f->hp, f->K, (int)N, (int)f->Np, f->mnu, jitter);
-  else
-    hipLaunchKernelGGL(kmat_kernel, grid, dim3(256), 0, st, f->X, f->hp, f->K, (int)N, (int)f->Np, f->kind, jitter);
+  if (f->dp == DPAD) fit_path_count(f->kind == 4 ? GPEMU_FIT_PATH_KMAT_NU : GPEMU_FIT_PATH_KMAT);
+  else wide_path_count(GPEMU_WIDE_PATH_FIT_KMAT);
+  if (f->kind == 4) {
+    if (f->dp == DPAD)
+      hipLaunchKernelGGL(kmat_nu_kernel<DPAD>, grid, dim3(256), 0, st, f->X, f->hp, f->K, (int)N, (int)f->Np, f->mnu, jitter);
+    else
+      hipLaunchKernelGGL(kmat_nu_kernel<DPAD_WIDE>, grid, dim3(256), 0, st, f->X, f->hp, f->K, (int)N, (int)f->Np, f->mnu, jitter);
+  } else {
+    if (f->dp == DPAD)
+      hipLaunchKernelGGL(kmat_kernel<DPAD>, grid, dim3(256), 0, st, f->X, f->hp, f->K, (int)N, (int)f->Np, f->kind, jitter);
+    else
+      hipLaunchKernelGGL(kmat_kernel<DPAD_WIDE>, grid, dim3(256), 0, st, f->X, f->hp, f->K, (int)N, (int)f->Np, f->kind, jitter);
+  }
 }
 
 // the workspace's buffers of doubles and their lengths per problem: fn(pointer, doubles per problem)
 template <class Fn>
 static void fit_buffers(gpemu_fit *f, Fn fn) {
   const int64_t Np = f->Np;
-  fn(&f->hp, DPAD + 2); fn(&f->K, Np * Np); fn(&f->Dinv, Np * NB); fn(&f->W, Np * Np); fn(&f->T, Np * Np);
+  const int64_t nthm = nth_max(f->dp);
+  fn(&f->hp, f->dp + 2); fn(&f->K, Np * Np); fn(&f->Dinv, Np * NB); fn(&f->W, Np * Np); fn(&f->T, Np * Np);
   fn(&f->Kinv, Np * Np); fn(&f->y, Np); fn(&f->v, Np); fn(&f->alpha, Np);
-  fn(&f->gpart, (int64_t)f->n_gparts * NTH_MAX); fn(&f->scal, 4); fn(&f->grad, NTH_MAX);
-  fn(&f->gstage, (int64_t)GR_BLOCKS * NTH_MAX);
+  fn(&f->gpart, (int64_t)f->n_gparts * nthm); fn(&f->scal, 4); fn(&f->grad, nthm);
+  fn(&f->gstage, (int64_t)GR_BLOCKS * nthm);
 }
 
 // workspace for `nb` problems evaluated together (one set of matrices each)
@@ -1399,13 +1438,14 @@ static int fit_eval_batch(gpemu_fit *f, int nb, const double *ys, const double *
   if (nb > 1) fit_path_count(GPEMU_FIT_PATH_BATCH);
   f->last_nb = 0;                  // (gpemu_fit_workspace: nothing valid until this evaluation has run through)
   hipStream_t st = f->stream;
-  std::vector<double> hp((size_t)nb * (DPAD + 2)), hy((size_t)nb * Np, 0.0);
+  const int dp = f->dp;
+  std::vector<double> hp((size_t)nb * (dp + 2)), hy((size_t)nb * Np, 0.0);
   for (int z = 0; z < nb; ++z) {
     const double *theta = thetas + (size_t)z * nth;
-    double *h = hp.data() + (size_t)z * (DPAD + 2);
-    for (int i = 0; i < DPAD; ++i) h[i] = i < d ? std::exp(theta[i]) : 1.0;
-    h[DPAD] = f->has_const ? std::exp(theta[d]) : 0.0;
-    h[DPAD + 1] = f->has_noise ? std::exp(theta[d + f->has_const]) : 0.0;
+    double *h = hp.data() + (size_t)z * (dp + 2);
+    for (int i = 0; i < dp; ++i) h[i] = i < d ? std::exp(theta[i]) : 1.0;
+    h[dp] = f->has_const ? std::exp(theta[d]) : 0.0;
+    h[dp + 1] = f->has_noise ? std::exp(theta[d + f->has_const]) : 0.0;
     for (int64_t i = 0; i < N; ++i) hy[(size_t)z * Np + i] = ys[(size_t)z * N + i];
   }
   GP_HIP(hipMemcpyAsync(f->hp, hp.data(), sizeof(double) * hp.size(), hipMemcpyHostToDevice, st));
@@ -1446,19 +1486,26 @@ static int fit_eval_batch(gpemu_fit *f, int nb, const double *ys, const double *
     int npairs = 0;
     for (int y = 0; y < ngroups; ++y) npairs += y / 16 + 1;
     dim3 grid((unsigned)npairs, 1, (unsigned)nb);
-    fit_path_count(f->kind == 4 ? GPEMU_FIT_PATH_GRAD_NU : GPEMU_FIT_PATH_GRAD);
-    if (f->kind == 4)
-      hipLaunchKernelGGL(lml_grad_nu_kernel, grid, dim3(256), 0, st, f->X, f->hp, f->alpha, f->Kinv, Np, f->gpart, (int)N,
-                         (int)d, f->mnu, f->has_const, f->has_noise);
-    else
-      hipLaunchKernelGGL(lml_grad_kernel, grid, dim3(256), 0, st, f->X, f->hp, f->alpha, f->Kinv, Np, f->gpart, (int)N,
-                         (int)d, f->kind, f->has_const, f->has_noise);
-    hipLaunchKernelGGL(grad_reduce_stage1_kernel, dim3(GR_BLOCKS, (unsigned)nb), dim3(256), 0, st, f->gpart,
-                       npairs, f->gstage, nth);
-    hipLaunchKernelGGL(grad_reduce_kernel, dim3((unsigned)nb), dim3(64), 0, st, f->gstage, f->grad, nth);
+    if (dp == DPAD) fit_path_count(f->kind == 4 ? GPEMU_FIT_PATH_GRAD_NU : GPEMU_FIT_PATH_GRAD);
+    else wide_path_count(GPEMU_WIDE_PATH_FIT_GRAD);
+#define GP_LAUNCH_GRAD(DPV)                                                                                                   \
+  do {                                                                                                                      \
+    if (f->kind == 4)                                                                                                       \
+      hipLaunchKernelGGL(lml_grad_nu_kernel<DPV>, grid, dim3(256), 0, st, f->X, f->hp, f->alpha, f->Kinv, Np, f->gpart,     \
+                         (int)N, (int)d, f->mnu, f->has_const, f->has_noise);                                               \
+    else                                                                                                                    \
+      hipLaunchKernelGGL(lml_grad_kernel<DPV>, grid, dim3(256), 0, st, f->X, f->hp, f->alpha, f->Kinv, Np, f->gpart,        \
+                         (int)N, (int)d, f->kind, f->has_const, f->has_noise);                                              \
+    hipLaunchKernelGGL(grad_reduce_stage1_kernel<DPV>, dim3(GR_BLOCKS, (unsigned)nb), dim3(256), 0, st, f->gpart,          \
+                       npairs, f->gstage, nth);                                                                             \
+    hipLaunchKernelGGL(grad_reduce_kernel<DPV>, dim3((unsigned)nb), dim3(64), 0, st, f->gstage, f->grad, nth);             \
+  } while (0)
+    if (dp == DPAD) GP_LAUNCH_GRAD(DPAD);
+    else GP_LAUNCH_GRAD(DPAD_WIDE);
+#undef GP_LAUNCH_GRAD
     GP_HIP(hipGetLastError());
   }
-  std::vector<double> hs((size_t)nb * 4), hg((size_t)nb * NTH_MAX);
+  std::vector<double> hs((size_t)nb * 4), hg((size_t)nb * nth_max(dp));
   std::vector<int> info((size_t)nb, 0);
   GP_HIP(hipMemcpyAsync(hs.data(), f->scal, sizeof(double) * hs.size(), hipMemcpyDeviceToHost, st));
   GP_HIP(hipMemcpyAsync(info.data(), f->info, sizeof(int) * nb, hipMemcpyDeviceToHost, st));
@@ -1476,7 +1523,7 @@ static int fit_eval_batch(gpemu_fit *f, int nb, const double *ys, const double *
     if (info[z] != 0 && first_bad == 0) first_bad = info[z];
     if (lml) lml[z] = -0.5 * hs[(size_t)z * 4] - hs[(size_t)z * 4 + 1] - 0.5 * (double)N * std::log(2.0 * M_PI);
     if (want_grad && grad)
-      for (int t = 0; t < nth; ++t) grad[(size_t)z * nth + t] = hg[(size_t)z * NTH_MAX + t];
+      for (int t = 0; t < nth; ++t) grad[(size_t)z * nth + t] = hg[(size_t)z * nth_max(dp) + t];
   }
   if (first_bad != 0 && !info_out) {
     set_error("kernel matrix is not positive definite (pivot %d): the kernel is not returning a positive "
@@ -1497,7 +1544,7 @@ int gpemu_fit_create(gpemu_fit **out, int device, int64_t N, int64_t d, const do
                      double nu, int has_const, int has_noise, double jitter) {
   GP_ARG(out && X, "null pointer");
   *out = nullptr;
-  GP_ARG(N > 0 && d > 0 && d <= DPAD, "N > 0 and 0 < d <= 8 required");
+  GP_ARG(N > 0 && d > 0 && d <= DPAD_WIDE, "N > 0 and 0 < d <= 16 required");
   GP_ARG(kernel_kind == GPEMU_KERNEL_RBF || kernel_kind == GPEMU_KERNEL_MATERN, "kernel_kind");
   if (kernel_kind == GPEMU_KERNEL_MATERN) GP_ARG(nu > 0.0, "Matern nu must be > 0 (finite or +inf; not NaN)");
   int ndev = 0;
@@ -1509,6 +1556,7 @@ int gpemu_fit_create(gpemu_fit **out, int device, int64_t N, int64_t d, const do
   GP_HIP(hipSetDevice(device));
   gpemu_fit *f = new gpemu_fit();
   f->device = device; f->N = N; f->d = d; f->Np = round_up(N, NB);
+  f->dp = dpad_of(d);
   f->kind = fit_kind_of(kernel_kind, nu);
   if (f->kind == 4) f->mnu = matern_nu_constants(nu);
   f->has_const = has_const ? 1 : 0; f->has_noise = has_noise ? 1 : 0;
@@ -1539,11 +1587,12 @@ int gpemu_fit_create(gpemu_fit **out, int device, int64_t N, int64_t d, const do
   }
   if (e == hipSuccess) e = hipEventCreateWithFlags(&f->overlap.panel_done, hipEventDisableTiming);
   if (e == hipSuccess) e = hipEventCreateWithFlags(&f->overlap.rest_done, hipEventDisableTiming);
-  if (e == hipSuccess) e = hipMalloc((void **)&f->X, sizeof(double) * (size_t)(Np * DPAD));
+  const int dp = f->dp;
+  if (e == hipSuccess) e = hipMalloc((void **)&f->X, sizeof(double) * (size_t)(Np * dp));
   if (e == hipSuccess && fit_reserve(f, 1) != GPEMU_OK) e = hipErrorOutOfMemory;
-  std::vector<double> hX((size_t)(Np * DPAD), 0.0);
+  std::vector<double> hX((size_t)(Np * dp), 0.0);
   for (int64_t i = 0; i < N; ++i)
-    for (int64_t dd = 0; dd < d; ++dd) hX[i * DPAD + dd] = X[i * d + dd];
+    for (int64_t dd = 0; dd < d; ++dd) hX[i * dp + dd] = X[i * d + dd];
   if (e == hipSuccess) e = hipMemcpy(f->X, hX.data(), sizeof(double) * hX.size(), hipMemcpyHostToDevice);
   if (e != hipSuccess) {
     set_error("fit_create: %s", hipGetErrorString(e));
@@ -1645,11 +1694,12 @@ int gpemu_kernel_matrix(int device, int64_t N, int64_t d, const double *X, const
   const int nth = (int)(d + f->has_const + f->has_noise);
   if (n_theta != nth) { set_error("bad argument: n_theta"); rc = GPEMU_ERR_ARG; }
   if (rc == GPEMU_OK) {
-    double hp[DPAD + 2];
-    for (int i = 0; i < DPAD; ++i) hp[i] = i < d ? std::exp(theta[i]) : 1.0;
-    hp[DPAD] = f->has_const ? std::exp(theta[d]) : 0.0;
-    hp[DPAD + 1] = f->has_noise ? std::exp(theta[d + f->has_const]) : 0.0;
-    hipError_t e = hipMemcpy(f->hp, hp, sizeof(hp), hipMemcpyHostToDevice);
+    const int dp = f->dp;
+    double hp[DPAD_WIDE + 2];
+    for (int i = 0; i < dp; ++i) hp[i] = i < d ? std::exp(theta[i]) : 1.0;
+    hp[dp] = f->has_const ? std::exp(theta[d]) : 0.0;
+    hp[dp + 1] = f->has_noise ? std::exp(theta[d + f->has_const]) : 0.0;
+    hipError_t e = hipMemcpy(f->hp, hp, sizeof(double) * (dp + 2), hipMemcpyHostToDevice);
     launch_kmat(f, N, 1, jitter, f->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(f->stream);
     if (e == hipSuccess)

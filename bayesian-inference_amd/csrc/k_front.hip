@@ -563,7 +563,8 @@ bool front_eligible(const gpemu_sampler *s) {
   static const bool off = getenv("GPEMU_NO_FUSED") != nullptr;
   if (off || s->groups.empty() || (int)s->groups.size() > FRONT_MAX_GROUPS || s->nchains != 1) return false;
   for (const gpemu_model *m : s->groups)
-    if (m->k > 64 || m->ksteps != 2 || m->device != s->groups[0]->device) return false;   // ksteps 3: d = 8 parameters
+    // ksteps 3: d = 8 parameters; and the wide padding (d > 8) has no instance here: those runs take the general path
+    if (m->k > 64 || m->ksteps != 2 || m->dp != DPAD || m->device != s->groups[0]->device) return false;
   return true;
 }
 

@@ -209,7 +209,7 @@ __global__ __launch_bounds__(256) void loglik_lowrank_kernel(
   const double sc0_pre = scal[0], sc1_pre = scal[1];
 
   bool in = true;
-  if (lane < d) in = (Xq[b * DPAD + lane] > lo[lane]) && (Xq[b * DPAD + lane] < hi[lane]);
+  if (lane < d) in = (Xq[b * dpad_of(d) + lane] > lo[lane]) && (Xq[b * dpad_of(d) + lane] < hi[lane]);
   const bool inside = __all(in);
 
   double mu, sd;
@@ -239,7 +239,7 @@ __global__ __launch_bounds__(256) void loglik_lowrank_lds_kernel(
   double *M = smem + (size_t)wave * k * (k + 1);
   const int ldm = k + 1;
   bool in = true;
-  if (lane < d) in = (Xq[b * DPAD + lane] > lo[lane]) && (Xq[b * DPAD + lane] < hi[lane]);
+  if (lane < d) in = (Xq[b * dpad_of(d) + lane] > lo[lane]) && (Xq[b * dpad_of(d) + lane] < hi[lane]);
   const bool inside = __all(in);
   double mu, sd;
   if (k <= 32) walker_mean_sd<32>(mean_part, vsq_part, kdiag, mean_out, var_out, b, Bcap, k, nchunk, nrb, lane, mu, sd);
@@ -299,7 +299,7 @@ __global__ __launch_bounds__(256) void loglik_groups_kernel(const double *__rest
     for (int g = gw; g < lg.ng; g += wv) {
       const LoglikGroup &gr = lg.g[g];
       bool in = true;
-      if (lane < d) in = (Xq[b * DPAD + lane] > gr.lo[lane]) && (Xq[b * DPAD + lane] < gr.hi[lane]);
+      if (lane < d) in = (Xq[b * dpad_of(d) + lane] > gr.lo[lane]) && (Xq[b * dpad_of(d) + lane] < gr.hi[lane]);
       const bool inside = __all(in);
       double lp;
       // (the value does not depend on KMAX: loglik_dev.h)
@@ -383,7 +383,7 @@ __global__ __launch_bounds__(64 * LL_TASK_WAVES) void loglik_tasks_kernel(const 
     const int g = lt.tg[t], o = lt.to[t];
     const LoglikGroup &gr = lt.g[g];
     bool in = true;
-    if (lane < d) in = (Xq[b * DPAD + lane] > gr.lo[lane]) && (Xq[b * DPAD + lane] < gr.hi[lane]);
+    if (lane < d) in = (Xq[b * dpad_of(d) + lane] > gr.lo[lane]) && (Xq[b * dpad_of(d) + lane] < gr.hi[lane]);
     double term = 0.0;
     if (__all(in)) {                                         // (outside the box the group's term is -inf whatever the blocks say)
       if (gr.k <= 4) term = task_term<4>(gr, o, b, lane);
@@ -421,7 +421,7 @@ __global__ __launch_bounds__(64 * LL_TASK_WAVES) void loglik_tasks_kernel(const 
     for (int g = 0; g < lt.ng; ++g) {
       const LoglikGroup &gr = lt.g[g];
       bool in = true;
-      if (lane < d) in = (Xq[b * DPAD + lane] > gr.lo[lane]) && (Xq[b * DPAD + lane] < gr.hi[lane]);
+      if (lane < d) in = (Xq[b * dpad_of(d) + lane] > gr.lo[lane]) && (Xq[b * dpad_of(d) + lane] < gr.hi[lane]);
       double lp = -INFINITY;
       if (__all(in)) {
         lp = 0.0;

@@ -27,9 +27,9 @@ typedef double d2 __attribute__((ext_vector_type(2)));
 // Cross-kernel.  grid (Bcap / 64, Npad / rows per workgroup, k), block 256 = 4 waves on a tile of
 // WR JTW x 16 training rows x 64 queries (predict_dev.h: kstar_mfma_block).  The workgroup first puts its 64 raw query
 // rows into LDS -- read from the padded buffer, padded on the fly from the caller's rows, or formed as the stretch
-// proposal of the sampler -- two components per thread.
+// proposal of the sampler -- two components per thread (four at the wide padding, DP = 16: d > 8).
 struct KstarArgs {
-  double *Xq;                          // [Bcap][DPAD] padded query rows (read, or written once per column block)
+  double *Xq;                          // [Bcap][DP] padded query rows (read, or written once per column block)
   const double *Xa, *alf, *qsc, *qof;  // matrix-core operands (kstar_host.h)
   const double *etab, *constv;
   const double *Xs, *inv_ls;           // Matern-0.5 / general nu < 1 only: row-major scaled training rows for the direct distance
@@ -43,10 +43,12 @@ struct KstarArgs {
 
 // bidx: the workgroup's index within its group's grid; store_rows: this group's first workgroups keep the padded query
 // rows / stretch factors (the first group of a launch that serves several: the others form the same rows and store nothing)
-template <int KIND, int KS, int JTW, int NBW>
+template <int KIND, int KS, int JTW, int NBW, int DP>
 __device__ __forceinline__ void kstar_body(const KstarArgs &ka, const ProposeArgs &pa, const int bidx, const bool store_rows) {
+  static_assert(DP == DPAD || DP == DPAD_WIDE, "padded width");
+  constexpr int NC = DP / 4;                         // components of a query per thread
   __shared__ double s_tab[1 << KSTAR_TB];
-  __shared__ __attribute__((aligned(16))) double s_q[64 * DPAD];
+  __shared__ __attribute__((aligned(16))) double s_q[64 * DP];
   __shared__ double s_red[4 * 64];
   constexpr int WC = 4 / NBW, WR = 4 / WC, JT = WR * JTW;
   const int lane = threadIdx.x & 63;
@@ -76,60 +78,63 @@ __device__ __forceinline__ void kstar_body(const KstarArgs &ka, const ProposeArg
   }
   const int64_t b0 = (int64_t)cb * 64;
   const int64_t b = b0 + lane;
-  const int c0 = wave, c1 = wave + 4;                // this thread's two components of query b
+  // this thread's NC components of query b: wave, wave + 4, ...
   const int64_t njt = ka.Npad / 16;
   KstarFrags<KS, JTW> fr;
   if (threadIdx.x < (1 << KSTAR_TB)) s_tab[threadIdx.x] = ka.etab[threadIdx.x];
   const bool keeper = store_rows && chunk == 0 && p == 0;   // the workgroup that stores the padded rows of its columns
-  double q0 = 0.0, q1 = 0.0;
+  double q[NC];
+#pragma unroll
+  for (int u = 0; u < NC; ++u) q[u] = 0.0;
   if (pa.enabled) {
     // stretch-move proposal for column b (every workgroup recomputes it; one of them stores it)
     if (b < pa.n) {
       const int w = pa.idx_s[b], j = pa.partner[b];
       const double z = pa.zz[b];
-      if (c0 < pa.d) {
-        const double cj = pa.X[(int64_t)j * DPAD + c0], sw = pa.X[(int64_t)w * DPAD + c0];
-        q0 = cj - (cj - sw) * z;                     // emcee moves/stretch.py get_proposal
-      }
-      if (c1 < pa.d) {
-        const double cj = pa.X[(int64_t)j * DPAD + c1], sw = pa.X[(int64_t)w * DPAD + c1];
-        q1 = cj - (cj - sw) * z;
+#pragma unroll
+      for (int u = 0; u < NC; ++u) {
+        const int c = wave + 4 * u;
+        if (c < pa.d) {
+          const double cj = pa.X[(int64_t)j * DP + c], sw = pa.X[(int64_t)w * DP + c];
+          q[u] = cj - (cj - sw) * z;                 // emcee moves/stretch.py get_proposal
+        }
       }
       if (keeper && wave == 0) pa.factors[b] = (pa.d - 1.0) * log(z);
     }
   } else if (pa.raw) {
     // caller rows [n][d]: padded on the fly
     if (b < pa.n) {
-      if (c0 < pa.d) q0 = pa.raw[b * pa.d + c0];
-      if (c1 < pa.d) q1 = pa.raw[b * pa.d + c1];
+#pragma unroll
+      for (int u = 0; u < NC; ++u)
+        if (wave + 4 * u < pa.d) q[u] = pa.raw[b * pa.d + wave + 4 * u];
     }
   } else {
-    q0 = ka.Xq[b * DPAD + c0];
-    q1 = ka.Xq[b * DPAD + c1];
+#pragma unroll
+    for (int u = 0; u < NC; ++u) q[u] = ka.Xq[b * DP + wave + 4 * u];
   }
   if (keeper && (pa.enabled || pa.raw)) {
-    ka.Xq[b * DPAD + c0] = q0;
-    ka.Xq[b * DPAD + c1] = q1;
+#pragma unroll
+    for (int u = 0; u < NC; ++u) ka.Xq[b * DP + wave + 4 * u] = q[u];
   }
-  s_q[lane * DPAD + c0] = q0;
-  s_q[lane * DPAD + c1] = q1;
+#pragma unroll
+  for (int u = 0; u < NC; ++u) s_q[lane * DP + wave + 4 * u] = q[u];
   __syncthreads();
   // (requesting the fragments ahead of the proposal's loads was measured: 16.45 vs 16.1 us, slower)
   kstar_load_frags<KS, JTW, NBW>(fr, ka.Xa + (int64_t)p * njt * KS * 64, ka.alf + (int64_t)p * njt * 16, (int64_t)chunk * JT,
                                  lane, wave);
   const double c = ka.has_const ? ka.constv[p] : 0.0;
   KstarDirect dir{nullptr, nullptr};
-  if (KIND == 1 || KIND == 4) dir = KstarDirect{ka.Xs + (int64_t)p * ka.Npad * DPAD, ka.inv_ls + p * DPAD};
+  if (KIND == 1 || KIND == 4) dir = KstarDirect{ka.Xs + (int64_t)p * ka.Npad * DP, ka.inv_ls + p * DP};
   const MaternNu mn = (KIND == 4) ? kstar_matern_nu(ka.etab + (1 << KSTAR_TB)) : MaternNu();
-  const double sum = kstar_mfma_block<KIND, KS, JTW, NBW, KSTAR_TB>(
+  const double sum = kstar_mfma_block<KIND, KS, JTW, NBW, KSTAR_TB, 0, DP>(
       s_q, s_tab, s_red, fr, ka.qsc + p * 4 * KS, ka.qof + p * 4 * KS, c, ka.d, (int64_t)chunk * JT, ka.N, ka.KS + (int64_t)p * ka.Npad * ka.Bcap + b0, ka.Bcap, dir,
       lane, wave, mn);
   if (wave == 0) ka.mean_part[(b * ka.k + p) * nchunk + chunk] = sum;
 }
 
-template <int KIND, int KS, int JTW, int NBW>
+template <int KIND, int KS, int JTW, int NBW, int DP>
 __global__ __launch_bounds__(256, 2) void kstar_kernel(KstarArgs ka, ProposeArgs pa) {
-  kstar_body<KIND, KS, JTW, NBW>(ka, pa, (int)blockIdx.x, true);
+  kstar_body<KIND, KS, JTW, NBW, DP>(ka, pa, (int)blockIdx.x, true);
 }
 
 // The cross-kernels of several emulation groups in ONE launch (a sampler over the shipped three groups spends its
@@ -141,11 +146,11 @@ struct KstarGroups {
   int start[GROUPS_MAX + 1];
   int ng;
 };
-template <int KIND, int KS, int JTW, int NBW>
+template <int KIND, int KS, int JTW, int NBW, int DP>
 __global__ __launch_bounds__(256, 2) void kstar_groups_kernel(KstarGroups kg, ProposeArgs pa) {
   int gi = 0;
   while (gi + 1 < kg.ng && (int)blockIdx.x >= kg.start[gi + 1]) ++gi;
-  kstar_body<KIND, KS, JTW, NBW>(kg.g[gi], pa, (int)blockIdx.x - kg.start[gi], gi == 0);
+  kstar_body<KIND, KS, JTW, NBW, DP>(kg.g[gi], pa, (int)blockIdx.x - kg.start[gi], gi == 0);
 }
 
 // Columns per launch of the large-batch triangular GEMM.  More than 512 columns (emulation.predict on a large batch) go
@@ -174,7 +179,9 @@ int trmm_xcd_of(const gpemu_model *m, int64_t B, int p, int64_t col) {
 // which cross-kernel instance a launch takes (gpemu_path_counts)
 static void kstar_count(const gpemu_model *m, bool small) {
   path_count(small ? GPEMU_PATH_KSTAR_SMALL : GPEMU_PATH_KSTAR_BIG);
-  path_count(m->ksteps == 2 ? GPEMU_PATH_KSTAR_KSTEPS2 : GPEMU_PATH_KSTAR_KSTEPS3);
+  if (m->dp == DPAD) path_count(m->ksteps == 2 ? GPEMU_PATH_KSTAR_KSTEPS2 : GPEMU_PATH_KSTAR_KSTEPS3);
+  else wide_path_count(m->ksteps == 3 ? GPEMU_WIDE_PATH_KSTAR_KSTEPS3 : m->ksteps == 4 ? GPEMU_WIDE_PATH_KSTAR_KSTEPS4
+                                                                                        : GPEMU_WIDE_PATH_KSTAR_KSTEPS5);
   if (kstar_kind(m) == 1 || (kstar_kind(m) == 4 && m->nu < 1.0)) path_count(GPEMU_PATH_KSTAR_DIRECT);
 }
 
@@ -202,27 +209,26 @@ static KstarArgs kstar_setup(gpemu_model *m, int64_t B, double *dXq, int &nwg, b
                    m->N, m->Npad, w.Bcap, m->has_const, (int)m->d, (int)m->k, w.cur_nchunk, ncb64, gper, ncbp};
 }
 
-#define GP_KSTAR_DISPATCH(kind, ksteps, small, LAUNCH)                  \
-  do {                                                                   \
-    if ((ksteps) == 2) {                                                 \
-      switch (kind) {                                                    \
-        case 0: if (small) LAUNCH(0, 2, 1); else LAUNCH(0, 2, 2); break; \
-        case 1: if (small) LAUNCH(1, 2, 1); else LAUNCH(1, 2, 2); break; \
-        case 2: if (small) LAUNCH(2, 2, 1); else LAUNCH(2, 2, 2); break; \
-        case 3: if (small) LAUNCH(3, 2, 1); else LAUNCH(3, 2, 2); break; \
-        case 4: if (small) LAUNCH(4, 2, 1); else LAUNCH(4, 2, 2); break; \
-        default: set_error("cross-kernel: unknown base kernel %d", (int)(kind)); return GPEMU_ERR_STATE; \
-      }                                                                  \
-    } else {                                                             \
-      switch (kind) {                                                    \
-        case 0: if (small) LAUNCH(0, 3, 1); else LAUNCH(0, 3, 2); break; \
-        case 1: if (small) LAUNCH(1, 3, 1); else LAUNCH(1, 3, 2); break; \
-        case 2: if (small) LAUNCH(2, 3, 1); else LAUNCH(2, 3, 2); break; \
-        case 3: if (small) LAUNCH(3, 3, 1); else LAUNCH(3, 3, 2); break; \
-        case 4: if (small) LAUNCH(4, 3, 1); else LAUNCH(4, 3, 2); break; \
-        default: set_error("cross-kernel: unknown base kernel %d", (int)(kind)); return GPEMU_ERR_STATE; \
-      }                                                                  \
-    }                                                                    \
+// instances: (ksteps, padded width) = (2, 8) d <= 7, (3, 8) d = 8; (3, 16) d = 9 .. 11, (4, 16) d = 12 .. 15, (5, 16) d = 16
+#define GP_KSTAR_KINDS(kind, KSV, DPV, small, LAUNCH)                                 \
+  switch (kind) {                                                                     \
+    case 0: if (small) LAUNCH(0, KSV, 1, DPV); else LAUNCH(0, KSV, 2, DPV); break;    \
+    case 1: if (small) LAUNCH(1, KSV, 1, DPV); else LAUNCH(1, KSV, 2, DPV); break;    \
+    case 2: if (small) LAUNCH(2, KSV, 1, DPV); else LAUNCH(2, KSV, 2, DPV); break;    \
+    case 3: if (small) LAUNCH(3, KSV, 1, DPV); else LAUNCH(3, KSV, 2, DPV); break;    \
+    case 4: if (small) LAUNCH(4, KSV, 1, DPV); else LAUNCH(4, KSV, 2, DPV); break;    \
+    default: set_error("cross-kernel: unknown base kernel %d", (int)(kind)); return GPEMU_ERR_STATE; \
+  }
+#define GP_KSTAR_DISPATCH(kind, ksteps, dp, small, LAUNCH)                            \
+  do {                                                                                \
+    if ((dp) == DPAD) {                                                               \
+      if ((ksteps) == 2) { GP_KSTAR_KINDS(kind, 2, DPAD, small, LAUNCH) }             \
+      else { GP_KSTAR_KINDS(kind, 3, DPAD, small, LAUNCH) }                           \
+    } else {                                                                          \
+      if ((ksteps) == 3) { GP_KSTAR_KINDS(kind, 3, DPAD_WIDE, small, LAUNCH) }        \
+      else if ((ksteps) == 4) { GP_KSTAR_KINDS(kind, 4, DPAD_WIDE, small, LAUNCH) }   \
+      else { GP_KSTAR_KINDS(kind, 5, DPAD_WIDE, small, LAUNCH) }                      \
+    }                                                                                 \
   } while (0)
 
 int launch_kstar(gpemu_model *m, int64_t B, double *dXq, hipStream_t st, const ProposeArgs *pa) {
@@ -232,8 +238,8 @@ int launch_kstar(gpemu_model *m, int64_t B, double *dXq, hipStream_t st, const P
   const KstarArgs ka = kstar_setup(m, B, dXq, nwg, small);
   const dim3 grid((unsigned)nwg), block(256);
   const int pe0 = prof_mark(m, st);
-#define GP_LAUNCH_ONE(KD, KSV, JT) hipLaunchKernelGGL((kstar_kernel<KD, KSV, JT, 2>), grid, block, 0, st, ka, pargs)
-  GP_KSTAR_DISPATCH(kstar_kind(m), m->ksteps, small, GP_LAUNCH_ONE);
+#define GP_LAUNCH_ONE(KD, KSV, JT, DPV) hipLaunchKernelGGL((kstar_kernel<KD, KSV, JT, 2, DPV>), grid, block, 0, st, ka, pargs)
+  GP_KSTAR_DISPATCH(kstar_kind(m), m->ksteps, m->dp, small, GP_LAUNCH_ONE);
 #undef GP_LAUNCH_ONE
   GP_HIP(hipGetLastError());
   kstar_count(m, small);
@@ -255,8 +261,8 @@ int launch_kstar_groups(gpemu_model *const *ms, int ng, int64_t B, double *dXq, 
     kg.start[g + 1] = kg.start[g] + nwg;
   }
   const dim3 grid((unsigned)kg.start[ng]), block(256);
-#define GP_LAUNCH_GROUPS(KD, KSV, JT) hipLaunchKernelGGL((kstar_groups_kernel<KD, KSV, JT, 2>), grid, block, 0, st, kg, pargs)
-  GP_KSTAR_DISPATCH(kstar_kind(ms[0]), ms[0]->ksteps, small, GP_LAUNCH_GROUPS);
+#define GP_LAUNCH_GROUPS(KD, KSV, JT, DPV) hipLaunchKernelGGL((kstar_groups_kernel<KD, KSV, JT, 2, DPV>), grid, block, 0, st, kg, pargs)
+  GP_KSTAR_DISPATCH(kstar_kind(ms[0]), ms[0]->ksteps, ms[0]->dp, small, GP_LAUNCH_GROUPS);
 #undef GP_LAUNCH_GROUPS
   GP_HIP(hipGetLastError());
   kstar_count(ms[0], small);

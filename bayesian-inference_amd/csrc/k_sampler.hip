@@ -190,6 +190,7 @@ __global__ void build_sets_kernel(const int *inds, int *idx, int W) {
 // accept / reject of one half with log-probabilities gathered from all ranks.  The proposal is
 // recomputed from the ensemble (the complementary set is unchanged during this half), so no rank
 // needs the other ranks' proposal rows; optionally records the chain row of its walkers.
+template <int DP>
 __global__ void accept_kernel(double *__restrict__ X, double *__restrict__ logp,
                               const int *__restrict__ idx_s,
                               const double *__restrict__ zz, const int *__restrict__ partner,
@@ -206,13 +207,13 @@ __global__ void accept_kernel(double *__restrict__ X, double *__restrict__ logp,
   const double lnpdiff = (d - 1.0) * log(z) + nlp - oldlp;
   const bool acc = lnpdiff > logu[i];
 #pragma unroll
-  for (int dd = 0; dd < DPAD; ++dd) {
-    const double sw = X[w * DPAD + dd];
+  for (int dd = 0; dd < DP; ++dd) {
+    const double sw = X[w * DP + dd];
     double v = sw;
     if (acc && dd < d) {
-      const double cj = X[j * DPAD + dd];
+      const double cj = X[j * DP + dd];
       v = cj - (cj - sw) * z;              // emcee moves/stretch.py get_proposal
-      X[w * DPAD + dd] = v;
+      X[w * DP + dd] = v;
     }
     if (chain && dd < d) chain[(int64_t)w * d + dd] = v;
   }
@@ -223,17 +224,19 @@ __global__ void accept_kernel(double *__restrict__ X, double *__restrict__ logp,
   if (lpchain) lpchain[w] = acc ? nlp : oldlp;
 }
 
+template <int DP>
 __global__ void pad_rows_kernel(const double *__restrict__ src, double *__restrict__ dst, int n, int d) {
   int idx = blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= n * DPAD) return;
-  int r = idx / DPAD, dd = idx % DPAD;
+  if (idx >= n * DP) return;
+  int r = idx / DP, dd = idx % DP;
   dst[idx] = dd < d ? src[r * d + dd] : 0.0;
 }
 
+template <int DP>
 __global__ void unpad_rows_kernel(const double *__restrict__ src, double *__restrict__ dst, int n, int d) {
   int idx = blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= n * d) return;
-  dst[idx] = src[(idx / d) * DPAD + idx % d];
+  dst[idx] = src[(idx / d) * DP + idx % d];
 }
 
 // ---- host helpers ---------------------------------------------------------------------------------
@@ -322,8 +325,8 @@ static int launch_accept(gpemu_sampler *s, int h, const double *dnewlp, int stor
     chain = s->chain + s->chain_len * s->W * s->d;
     lpchain = s->lpchain + s->chain_len * s->W;
   }
-  hipLaunchKernelGGL(accept_kernel, dim3((ns + 255) / 256), dim3(256), 0, st, s->X, s->logp,
-                     s->idx + o2 + h * s->W, s->zz + o2 + h * s->W,
+  hipLaunchKernelGGL(s->dp == DPAD ? accept_kernel<DPAD> : accept_kernel<DPAD_WIDE>, dim3((ns + 255) / 256), dim3(256), 0,
+                     st, s->X, s->logp, s->idx + o2 + h * s->W, s->zz + o2 + h * s->W,
                      s->rint + o2 + h * s->W, dnewlp, s->logu + o2 + h * s->W, s->naccept, s->flags, ns,
                      (int)s->d, chain, lpchain);
   GP_HIP(hipGetLastError());
@@ -365,6 +368,7 @@ static int half_step_fused(gpemu_sampler *s, int h, int store_chain, hipStream_t
     aa.naccept = s->naccept; aa.flags = s->flags;
     aa.chain_per = s->nchains > 1 ? (int)per_chain : 0;
     aa.first = lo;
+    aa.dp = s->dp;
     if (store_chain) {
       aa.chain = s->chain + s->chain_len * s->W * s->d;
       aa.lpchain = s->lpchain + s->chain_len * s->W;
@@ -435,13 +439,15 @@ int gpemu_sampler_create_chains(gpemu_sampler **out, gpemu_model *const *groups,
   s->device = groups[0]->device;
   s->groups.assign(groups, groups + n_groups);
   s->W = W; s->d = d; s->a = a; s->seed = seed;
+  s->dp = dpad_of(d);
+  const int64_t dp = s->dp;
   s->nchains = n_chains;
   s->ns[0] = (Wc + 1) / 2 * n_chains; s->ns[1] = Wc / 2 * n_chains;     // proposals of a half, chain after chain
   s->qcap = round_up(s->ns[0], TILE) + TILE;
   s->stream = groups[0]->stream;
   hipError_t e = hipSuccess;
   auto A = [&](void **p, size_t bytes) { if (e == hipSuccess) e = hipMalloc(p, bytes ? bytes : 8); };
-  A((void **)&s->Xbuf, sizeof(double) * 2 * W * DPAD);
+  A((void **)&s->Xbuf, sizeof(double) * 2 * W * dp);
   A((void **)&s->lpbuf, sizeof(double) * 2 * W);
   A((void **)&s->inds, sizeof(int) * W * RNG_RING);
   A((void **)&s->idx, sizeof(int) * 2 * W * RNG_RING);
@@ -450,8 +456,8 @@ int gpemu_sampler_create_chains(gpemu_sampler **out, gpemu_model *const *groups,
   A((void **)&s->rint, sizeof(int) * 2 * W * RNG_RING);
   A((void **)&s->fac, sizeof(double) * 2 * W * RNG_RING);
   A((void **)&s->pos, sizeof(int) * W * RNG_RING);
-  A((void **)&s->q2, sizeof(double) * 2 * s->qcap * DPAD);
-  A((void **)&s->q, sizeof(double) * s->qcap * DPAD);
+  A((void **)&s->q2, sizeof(double) * 2 * s->qcap * dp);
+  A((void **)&s->q, sizeof(double) * s->qcap * dp);
   A((void **)&s->factors, sizeof(double) * W);
   A((void **)&s->newlp, sizeof(double) * s->qcap);
   A((void **)&s->naccept, sizeof(long long) * W);
@@ -460,12 +466,12 @@ int gpemu_sampler_create_chains(gpemu_sampler **out, gpemu_model *const *groups,
   if (e == hipSuccess) e = hipMemcpy(s->seeds, seeds, sizeof(unsigned long long) * n_chains, hipMemcpyHostToDevice);
   if (e == hipSuccess) { s->X = s->Xbuf; s->logp = s->lpbuf; s->cur = 0; }
 
-  if (e == hipSuccess) e = hipMemsetAsync(s->q, 0, sizeof(double) * s->qcap * DPAD, s->stream);
-  if (e == hipSuccess) e = hipMemsetAsync(s->q2, 0, sizeof(double) * 2 * s->qcap * DPAD, s->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(s->q, 0, sizeof(double) * s->qcap * dp, s->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(s->q2, 0, sizeof(double) * 2 * s->qcap * dp, s->stream);
   if (e == hipSuccess) e = hipMemsetAsync(s->lpbuf, 0, sizeof(double) * 2 * W, s->stream);
   if (e == hipSuccess) e = hipMemsetAsync(s->naccept, 0, sizeof(long long) * W, s->stream);
   if (e == hipSuccess) e = hipMemsetAsync(s->flags, 0, sizeof(int) * 2, s->stream);
-  if (e == hipSuccess) e = hipMemsetAsync(s->Xbuf, 0, sizeof(double) * 2 * W * DPAD, s->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(s->Xbuf, 0, sizeof(double) * 2 * W * dp, s->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
   if (e != hipSuccess) {
     set_error("sampler_create: %s", hipGetErrorString(e));
@@ -504,8 +510,8 @@ int gpemu_sampler_set_state(gpemu_sampler *s, const double *X0, const double *lo
   int rc = GPEMU_OK;
   if (e != hipSuccess) { set_error("set_state: %s", hipGetErrorString(e)); rc = GPEMU_ERR_HIP; }
   if (rc == GPEMU_OK) {
-    hipLaunchKernelGGL(pad_rows_kernel, dim3((unsigned)((W * DPAD + 255) / 256)), dim3(256), 0, st, tmp,
-                       s->X, (int)W, (int)d);
+    hipLaunchKernelGGL(s->dp == DPAD ? pad_rows_kernel<DPAD> : pad_rows_kernel<DPAD_WIDE>,
+                       dim3((unsigned)((W * s->dp + 255) / 256)), dim3(256), 0, st, tmp, s->X, (int)W, (int)d);
     if (logp0) {
       e = hipMemcpyAsync(s->logp, logp0, sizeof(double) * W, hipMemcpyHostToDevice, st);
       if (e != hipSuccess) { set_error("set_state: %s", hipGetErrorString(e)); rc = GPEMU_ERR_HIP; }
@@ -518,11 +524,12 @@ int gpemu_sampler_set_state(gpemu_sampler *s, const double *X0, const double *lo
       for (int64_t off = 0; off < W && rc == GPEMU_OK;) {
         int64_t nb = std::min<int64_t>(step, W - off);
         if (Wc > cap) nb = std::min<int64_t>(nb, Wc - off % Wc);
-        e = hipMemcpyAsync(s->q, s->X + off * DPAD, sizeof(double) * nb * DPAD, hipMemcpyDeviceToDevice, st);
+        e = hipMemcpyAsync(s->q, s->X + off * s->dp, sizeof(double) * nb * s->dp, hipMemcpyDeviceToDevice, st);
         if (e != hipSuccess) { set_error("set_state: %s", hipGetErrorString(e)); rc = GPEMU_ERR_HIP; break; }
         AcceptArgs ca;                       // not an accept: only tells the likelihood which chain a row belongs to
         ca.chain_per = s->nchains > 1 ? (int)Wc : 0;
         ca.first = off;
+        ca.dp = s->dp;
         for (gpemu_model *m : s->groups) m->variant_B = (Wc + 1) / 2;
         rc = eval_logpost(s, s->q, nb, s->newlp, st, &ca);
         for (gpemu_model *m : s->groups) m->variant_B = 0;
@@ -548,8 +555,8 @@ int gpemu_sampler_get_state(gpemu_sampler *s, double *X, double *logp) {
   if (X) {
     double *tmp = nullptr;
     GP_HIP(hipMalloc((void **)&tmp, sizeof(double) * W * d));
-    hipLaunchKernelGGL(unpad_rows_kernel, dim3((unsigned)((W * d + 255) / 256)), dim3(256), 0, st, s->X,
-                       tmp, (int)W, (int)d);
+    hipLaunchKernelGGL(s->dp == DPAD ? unpad_rows_kernel<DPAD> : unpad_rows_kernel<DPAD_WIDE>,
+                       dim3((unsigned)((W * d + 255) / 256)), dim3(256), 0, st, s->X, tmp, (int)W, (int)d);
     hipError_t e = hipMemcpyAsync(X, tmp, sizeof(double) * W * d, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     (void)hipFree(tmp);
@@ -580,11 +587,11 @@ int gpemu_sampler_snapshot(gpemu_sampler *s) {
   GP_HIP(hipSetDevice(s->device));
   const int64_t W = s->W;
   if (!s->snapX) {
-    GP_HIP(hipMalloc((void **)&s->snapX, sizeof(double) * W * DPAD));
+    GP_HIP(hipMalloc((void **)&s->snapX, sizeof(double) * W * s->dp));
     GP_HIP(hipMalloc((void **)&s->snaplp, sizeof(double) * W));
     GP_HIP(hipMalloc((void **)&s->snapacc, sizeof(long long) * W));
   }
-  GP_HIP(hipMemcpyAsync(s->snapX, s->X, sizeof(double) * W * DPAD, hipMemcpyDeviceToDevice, s->stream));
+  GP_HIP(hipMemcpyAsync(s->snapX, s->X, sizeof(double) * W * s->dp, hipMemcpyDeviceToDevice, s->stream));
   GP_HIP(hipMemcpyAsync(s->snaplp, s->logp, sizeof(double) * W, hipMemcpyDeviceToDevice, s->stream));
   GP_HIP(hipMemcpyAsync(s->snapacc, s->naccept, sizeof(long long) * W, hipMemcpyDeviceToDevice, s->stream));
   s->snap_step_counter = s->step_counter;
@@ -600,7 +607,7 @@ int gpemu_sampler_restore(gpemu_sampler *s) {
   GP_HIP(hipSetDevice(s->device));
   const int64_t W = s->W;
   GP_HIP(hipStreamSynchronize(s->stream));
-  GP_HIP(hipMemcpyAsync(s->X, s->snapX, sizeof(double) * W * DPAD, hipMemcpyDeviceToDevice, s->stream));
+  GP_HIP(hipMemcpyAsync(s->X, s->snapX, sizeof(double) * W * s->dp, hipMemcpyDeviceToDevice, s->stream));
   GP_HIP(hipMemcpyAsync(s->logp, s->snaplp, sizeof(double) * W, hipMemcpyDeviceToDevice, s->stream));
   GP_HIP(hipMemcpyAsync(s->naccept, s->snapacc, sizeof(long long) * W, hipMemcpyDeviceToDevice, s->stream));
   GP_HIP(hipMemsetAsync(s->flags, 0, sizeof(int) * 2, s->stream));

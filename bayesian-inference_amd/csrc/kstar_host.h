@@ -9,19 +9,23 @@
 namespace gpemu {
 
 constexpr int KSTAR_TB = 6;            // log2 of the exponential's table size (exp2_scaled)
+constexpr int KSTAR_DMAX = 16;         // parameters the operands are built for (the padded width DPAD_WIDE)
+
+// MFMA k-steps of a d-parameter model: the smallest KS with 4 KS >= d + 1 (at least 2: d <= 7 keeps its 2-step product)
+inline int kstar_ksteps(int64_t d) { return (d + 1 <= 8) ? 2 : (int)((d + 4) / 4); }
 
 struct KstarHost {
-  int ksteps = 2;                      // MFMA k-steps: 4 ksteps >= d + 1
+  int ksteps = 2;                      // MFMA k-steps: 4 ksteps >= d + 1 (kstar_ksteps: 2 .. 5)
   std::vector<double> Xa;              // [k][Npad/16][ksteps][64]
   std::vector<double> alf;             // [k][Npad/16][16]
   std::vector<double> qsc, qof;        // [k][4 ksteps]: q' = q qsc + qof  (slot d: 0, 1)
   std::vector<double> tab;             // [2^TB]: 2^(j / 2^TB)
 };
 
-// X_train [N][d], ls [k][d], alpha [k][N];  kind 0: RBF (operands scaled by sqrt(2^TB / ln 2)), else Matern (unscaled)
+// X_train [N][d] (d <= KSTAR_DMAX), ls [k][d], alpha [k][N];  kind 0: RBF (operands scaled by sqrt(2^TB / ln 2)), else Matern (unscaled)
 inline void build_kstar_operands(int64_t N, int64_t Npad, int64_t d, int64_t k, int kind, const double *X_train,
                                  const double *ls, const double *alpha, KstarHost &out, int tb = KSTAR_TB) {
-  const int KS = (d + 1 <= 8) ? 2 : 3;
+  const int KS = kstar_ksteps(d);
   const int64_t njt = Npad / 16;
   out.ksteps = KS;
   out.Xa.assign((size_t)(k * njt * KS * 64), 0.0);
@@ -34,7 +38,7 @@ inline void build_kstar_operands(int64_t N, int64_t Npad, int64_t d, int64_t k, 
   std::vector<double> aug((size_t)(4 * KS));
   for (int64_t p = 0; p < k; ++p) {
     // centre: mid-range of the scaled training coordinates u = X / ls (skl: X / length_scale)
-    double cen[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    double cen[KSTAR_DMAX] = {};
     for (int64_t dd = 0; dd < d; ++dd) {
       double lo = INFINITY, hi = -INFINITY;
       for (int64_t j = 0; j < N; ++j) {

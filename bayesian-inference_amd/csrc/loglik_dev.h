@@ -68,9 +68,9 @@ __device__ __forceinline__ AcceptOperands load_accept_operands(const double *__r
   ao.oldlp = aa.logp[ao.w];
   ao.factor = aa.factors[b];
   ao.logu = aa.logu[b];
-  if (lane < DPAD) {
-    ao.xold = aa.X[(int64_t)ao.w * DPAD + lane];
-    ao.xnew = Xq[b * DPAD + lane];
+  if (lane < aa.dp) {
+    ao.xold = aa.X[(int64_t)ao.w * aa.dp + lane];
+    ao.xnew = Xq[b * aa.dp + lane];
   }
   return ao;
 }
@@ -87,7 +87,7 @@ __device__ __forceinline__ void finish_walker(double total, double *__restrict__
   if (total != total && lane == 0) atomicAdd(aa.flags, 1);  // emcee raises on NaN
   const bool acc = (ao.factor + total - oldlp) > ao.logu;
   const double xold = ao.xold;
-  if (lane < DPAD && acc) aa.X[(int64_t)w * DPAD + lane] = ao.xnew;
+  if (lane < aa.dp && acc) aa.X[(int64_t)w * aa.dp + lane] = ao.xnew;
   if (lane == 0) {
     out[b] = total;
     if (acc) {

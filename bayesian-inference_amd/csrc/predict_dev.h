@@ -64,7 +64,8 @@ __device__ __forceinline__ double base_kernel_fast(double r2, const double *tab)
 // the exponential then needs no range-reduction multiply (exp2_scaled).  Layouts (built on the host at model creation,
 // gpemu_api.hip: build_kstar_operands): Xa[p][jt][ks][lane] = aug[16 jt + (lane & 15)][4 ks + (lane >> 4)] -- the A
 // fragment of a j-tile is one coalesced 512-byte load -- and alf[p][jt][4 q + r] = alpha[16 jt + q + 4 r], the order in
-// which the accumulator rows of lane group q = lane >> 4 come.
+// which the accumulator rows of lane group q = lane >> 4 come.  d = 8 takes three k-steps, and 9 .. 16 parameters (query
+// rows padded to DP = 16) ceil((d + 1) / 4) = 3 .. 5 (kstar_host.h: kstar_ksteps).
 // ref: emulation.py:497 -> skl kernels.py:1553-1582 (RBF), 1708-1781 (Matern).
 typedef double kd4 __attribute__((ext_vector_type(4)));
 
@@ -120,16 +121,17 @@ __device__ __forceinline__ kd4 exp2_scaled4(kd4 y, const double *tab) {
 
 // Matern-0.5 (and general nu < 1: 1 - k ~ r^(2 nu)): exp(-r) is not flat at r = 0, so a pair closer than ~1e-3.5 of the data's extent (a query ON a
 // training point) needs r^2 to better than the product form's ~d eps |x|^2: those few pairs are recomputed from the
-// coordinate differences, round 3's arithmetic (row-major scaled rows xs[j][8], query q inv_ls).
+// coordinate differences, round 3's arithmetic (row-major scaled rows xs[j][DP], query q inv_ls; DP: padded width).
 struct KstarDirect {
-  const double *xs;    // [Npad][8] of this PC
-  const double *inv;   // [8]
+  const double *xs;    // [Npad][DP] of this PC
+  const double *inv;   // [DP]
 };
+template <int DP = 8>
 __device__ __forceinline__ double kstar_direct_r2(const KstarDirect &dir, const double *s_q, int64_t row, int col) {
   double r2 = 0.0;
 #pragma unroll
-  for (int dd = 0; dd < 8; ++dd) {
-    const double df = s_q[col * 8 + dd] * dir.inv[dd] - dir.xs[row * 8 + dd];
+  for (int dd = 0; dd < DP; ++dd) {
+    const double df = s_q[col * DP + dd] * dir.inv[dd] - dir.xs[row * DP + dd];
     r2 = fma(df, df, r2);
   }
   return r2;
@@ -145,7 +147,7 @@ __device__ __forceinline__ MaternNu kstar_matern_nu(const double *etab_end) {
 //   KIND 0 (RBF): operands scaled, acc + hq = -1/2 r^2 2^TB / ln2;  hq = -1/2 |q'|^2
 //   KIND 1, 2, 3 (Matern 0.5 / 1.5 / 2.5): operands unscaled, r^2 = max(-2 acc + |q'|^2, 0);  hq = |q'|^2
 //   KIND 4 (Matern, general nu: matern_dev.h): as 1 - 3; for nu < 1 near-coincident pairs by the direct distance
-template <int KIND, int TB>
+template <int KIND, int TB, int DP = 8>
 __device__ __forceinline__ kd4 kstar_value4(kd4 acc, double hq, const double *tab, const KstarDirect &dir,
                                             const double *s_q, int64_t row0, int col, const MaternNu &mn = MaternNu()) {
   if (KIND == 4) {
@@ -153,7 +155,7 @@ __device__ __forceinline__ kd4 kstar_value4(kd4 acc, double hq, const double *ta
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       double r2 = fmax(fma(acc[r], -2.0, hq), 0.0);
-      if (mn.nu < 1.0 && r2 < 1e-7 * (hq + 1.0)) r2 = kstar_direct_r2(dir, s_q, row0 + 4 * r, col);
+      if (mn.nu < 1.0 && r2 < 1e-7 * (hq + 1.0)) r2 = kstar_direct_r2<DP>(dir, s_q, row0 + 4 * r, col);
       v[r] = matern_nu_value_call(mn, sqrt(r2));
     }
     return v;
@@ -168,7 +170,7 @@ __device__ __forceinline__ kd4 kstar_value4(kd4 acc, double hq, const double *ta
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     double r2 = fmax(fma(acc[r], -2.0, hq), 0.0);
-    if (KIND == 1 && r2 < 1e-7 * (hq + 1.0)) r2 = kstar_direct_r2(dir, s_q, row0 + 4 * r, col);
+    if (KIND == 1 && r2 < 1e-7 * (hq + 1.0)) r2 = kstar_direct_r2<DP>(dir, s_q, row0 + 4 * r, col);
     const double rr = sqrt(r2);
     t[r] = (KIND == 1) ? rr : rr * ((KIND == 2) ? 1.7320508075688772 : 2.23606797749979);
     y[r] = -C * t[r];
@@ -193,12 +195,12 @@ __device__ __forceinline__ kd4 kstar_tile_product(const double (&a)[KS], const d
 }
 
 // kernel values, stores and the mean's FMAs of one tile from its accumulator
-template <int KIND, int TB, int ABL = 0>   // ABL: probe ablations (1: no stores, 2: no exponential, 3: nontemporal stores)
+template <int KIND, int TB, int ABL = 0, int DP = 8>   // ABL: probe ablations (1: no stores, 2: no exponential, 3: nontemporal stores)
 __device__ __forceinline__ void kstar_tile_finish(kd4 acc, double hq, kd4 al, double c, const double *s_tab, bool ragged,
                                                   int64_t row0, int64_t N, double *__restrict__ kout, int64_t Bcap, double &macc,
                                                   const KstarDirect &dir, const double *s_q, int col,
                                                   const MaternNu &mn = MaternNu()) {
-  kd4 v = (ABL == 2) ? acc : kstar_value4<KIND, TB>(acc, hq, s_tab, dir, s_q, row0, col, mn);
+  kd4 v = (ABL == 2) ? acc : kstar_value4<KIND, TB, DP>(acc, hq, s_tab, dir, s_q, row0, col, mn);
 #pragma unroll
   for (int r = 0; r < 4; ++r) v[r] += c;
   if (ragged) {                                           // wave-uniform: only the tiles that hold padded training rows
@@ -238,9 +240,10 @@ __device__ __forceinline__ void kstar_load_frags(KstarFrags<KS, JTW> &f, const d
 //   wave w: wave row wr = w % WR, wave column wc = w / WR (WC = 4 / NBW, WR = 4 / WC);
 //           j-tiles jt0 + wr JTW .. + JTW - 1, b-tiles wc NBW .. + NBW - 1
 //   NBW = 2, JTW = 2: 64 rows per workgroup (large batches);  NBW = 2, JTW = 1: 32 rows (small batches)
-// s_q: LDS [64][8] raw (unscaled, zero-padded) query rows of the workgroup's columns; s_red: LDS [4][64].
+// s_q: LDS [64][DP] raw (unscaled, zero-padded) query rows of the workgroup's columns (DP = 8, or 16 for d > 8: KS 3 .. 5);
+// s_red: LDS [4][64].
 // Returns, in wave 0, the workgroup's partial mean  sum_j alpha_j K[j][b]  of column b = lane (NaN if the query has one).
-template <int KIND, int KS, int JTW, int NBW, int TB, int ABL = 0>
+template <int KIND, int KS, int JTW, int NBW, int TB, int ABL = 0, int DP = 8>
 __device__ __forceinline__ double kstar_mfma_block(const double *s_q, const double *s_tab, double *s_red,
                                                    const KstarFrags<KS, JTW> &fr,
                                                    const double *__restrict__ qsc, const double *__restrict__ qof,
@@ -262,7 +265,7 @@ __device__ __forceinline__ double kstar_mfma_block(const double *s_q, const doub
 #pragma unroll
     for (int s = 0; s < KS; ++s) {
       const int comp = 4 * s + lq;
-      const double qv = (comp < 8) ? s_q[col * 8 + comp] : 0.0;
+      const double qv = (comp < DP) ? s_q[col * DP + comp] : 0.0;
       const double v = fma(qv, sc[s], of[s]);
       bq[bt][s] = v;
       part = (comp < d) ? fma(v, v, part) : part;
@@ -286,7 +289,7 @@ __device__ __forceinline__ double kstar_mfma_block(const double *s_q, const doub
     kd4 nxt = acc;
     if (i + 1 < NT) nxt = kstar_tile_product<KS>(fr.a[(i + 1) / NBW], bq[(i + 1) % NBW]);
     const int64_t jt = jt0 + wr * JTW + jj;
-    kstar_tile_finish<KIND, TB, ABL>(acc, hq[bt], fr.al[jj], c, s_tab, (jt + 1) * 16 > N, jt * 16 + lq, N,
+    kstar_tile_finish<KIND, TB, ABL, DP>(acc, hq[bt], fr.al[jj], c, s_tab, (jt + 1) * 16 > N, jt * 16 + lq, N,
                                      kcol + jt * 16 * Bcap + bt * 16, Bcap, macc[bt], dir, s_q, wc * NBW * 16 + ln + bt * 16, mn);
     acc = nxt;
   }

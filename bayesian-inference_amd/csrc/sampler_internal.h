@@ -17,6 +17,7 @@ struct gpemu_sampler {
   int device = 0;
   std::vector<gpemu_model *> groups;
   int64_t W = 0, d = 0;
+  int dp = gpemu::DPAD;        // padded width of X, Xbuf, q, q2, snapX: dpad_of(d) (the groups' dp)
   int64_t ns[2] = {0, 0};      // set sizes: ceil(W/2), floor(W/2)
   int64_t qcap = 0;            // rows of q (>= ns[0] rounded up to 128, + 128)
   double a = 2.0;
@@ -26,9 +27,9 @@ struct gpemu_sampler {
   uint64_t step_counter = 0;   // RNG counter, never reset
   int64_t iterations = 0;      // steps since the last reset
   hipStream_t stream = nullptr;
-  double *X = nullptr;         // [W][DPAD]  current positions: one of the two halves of Xbuf
+  double *X = nullptr;         // [W][dp]  current positions: one of the two halves of Xbuf
   double *logp = nullptr;      // [W]        current log-probabilities: one of the two halves of lpbuf
-  double *Xbuf = nullptr;      // [2][W][DPAD]  the fused run writes the accepted state into the other half
+  double *Xbuf = nullptr;      // [2][W][dp]  the fused run writes the accepted state into the other half
   double *lpbuf = nullptr;     // [2][W]
   int cur = 0;                 // which half X / logp point at
   // per-step randomness, ring of RNG_RING steps (slot = step_counter % RNG_RING)
@@ -40,7 +41,7 @@ struct gpemu_sampler {
   double *fac = nullptr;       // [RING][2][W]  (d - 1) log zz
   int *pos = nullptr;          // [RING][W]     position of each walker in its set's list
   uint64_t rng_ready_until = 0; // steps [.., rng_ready_until) of the device stream are in the ring
-  double *q = nullptr;         // [qcap][DPAD]
+  double *q = nullptr;         // [qcap][dp]
   double *factors = nullptr;   // [W]
   double *newlp = nullptr;     // [qcap]
   long long *naccept = nullptr;  // [W]
@@ -54,7 +55,7 @@ struct gpemu_sampler {
   int64_t gper[2] = {0, 0};
   int gworld = 0;
   // fused run (k_front.hip): proposals of the half in flight and of the one before, log-probability exchange
-  double *q2 = nullptr;        // [2][qcap][DPAD]
+  double *q2 = nullptr;        // [2][qcap][dp]
   double *gather = nullptr;    // [GATHER_SLOTS][ns[0]]  this rank's copy of every proposal's new log-probability
   bool gather_uncached = false;
   double **peers = nullptr;    // device array [peer_world]: every rank's gather buffer (own one included)
@@ -67,7 +68,7 @@ struct gpemu_sampler {
   std::vector<FrontPerm> front_perms;
   // snapshot of the chain state (gpemu_sampler_snapshot / _restore): a block of steps that failed -- a lost peer
   // exchange -- is rerun from here over another transport and gives the chain of an unbroken run
-  double *snapX = nullptr, *snaplp = nullptr;        // [W][DPAD], [W]
+  double *snapX = nullptr, *snaplp = nullptr;        // [W][dp], [W]
   long long *snapacc = nullptr;                      // [W]
   bool snap_valid = false;
   uint64_t snap_step_counter = 0;

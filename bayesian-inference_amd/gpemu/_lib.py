@@ -106,6 +106,7 @@ _SIGNATURES = {
     "gpemu_halfstep_small_launches": (C.c_int64, []),
     "gpemu_path_counts": (C.c_int, [C.POINTER(c_i64), c_i64]),
     "gpemu_fit_path_counts": (C.c_int, [C.POINTER(c_i64), c_i64]),
+    "gpemu_wide_path_counts": (C.c_int, [C.POINTER(c_i64), c_i64]),
     "gpemu_philox4x32": (C.c_int, [C.c_uint32] * 6 + [C.POINTER(C.c_uint32)]),
 }
 

@@ -73,6 +73,8 @@ int gpemu_device_memory(int device, int64_t *free_bytes, int64_t *total_bytes);
  *   scaler_mean[F], scaler_scale[F]   StandardScaler
  *   cov_unexplained[F*F]  ref: emulation.py:246-249, or NULL (then 0)
  * The factor is inverted on the device once (W = L^-1) so that prediction is a triangular GEMM.
+ * 1 <= d <= 16 (GPEMU_ERR_ARG beyond): d <= 8 runs on 8-wide padded rows, 9 .. 16 on 16-wide ones, whose samplers
+ * take the general path (no fused sharded half-step, no small-emulator launch: the sharded run falls back).
  */
 int gpemu_model_create(gpemu_model **out, int device, int64_t N, int64_t d, int64_t F, int64_t k,
                        int kernel_kind, double nu, int has_const, int has_noise,
@@ -147,6 +149,7 @@ int gpemu_logpost_dev(gpemu_model *m, int64_t B, const double *dX, double *dout,
  * (L-BFGS-B + restarts, skl _gpr.py:299-337) stays on the host and calls gpemu_fit_lml.
  * A non-positive-definite kernel matrix returns > 0 (index + 1 of the failing pivot); sklearn
  * raises LinAlgError there (skl _gpr.py:350-358).
+ * 1 <= d <= 16 (GPEMU_ERR_ARG beyond); d > 8 takes the 16-wide kernel-matrix and gradient instances.
  */
 int gpemu_fit_create(gpemu_fit **out, int device, int64_t N, int64_t d, const double *X,
                      int kernel_kind, double nu, int has_const, int has_noise, double jitter);
@@ -361,6 +364,21 @@ enum gpemu_fit_path {
 };
 /* out[0 .. min(n, GPEMU_FIT_PATH_COUNT)) = the counters; returns GPEMU_FIT_PATH_COUNT (or GPEMU_ERR_ARG). */
 int gpemu_fit_path_counts(int64_t *out, int64_t n);
+
+/* Which instances of padded width 16 (models and fit handles of 9 to 16 parameters) ran.  Their launches still count in
+ * the sets above where those do not name a width (KSTAR_SMALL / _BIG, KSTAR_DIRECT, HALFSTEP_GENERAL, the LOGLIK_* and
+ * TRMM_* entries, the fit's CHOL_* / TRTRI_* / BATCH); KSTAR_KSTEPS2 / _KSTEPS3, FIT_PATH_KMAT* and FIT_PATH_GRAD* count
+ * the 8-wide instances only, and their 16-wide counterparts count here. */
+enum gpemu_wide_path {
+  GPEMU_WIDE_PATH_KSTAR_KSTEPS3 = 0, /* cross-kernel, 16-wide rows, 3 MFMA k-steps (d = 9 .. 11)                      */
+  GPEMU_WIDE_PATH_KSTAR_KSTEPS4,     /* ... 4 k-steps (d = 12 .. 15)                                                  */
+  GPEMU_WIDE_PATH_KSTAR_KSTEPS5,     /* ... 5 k-steps (d = 16)                                                        */
+  GPEMU_WIDE_PATH_FIT_KMAT,          /* kernel matrix, kmat_kernel / kmat_nu_kernel of width 16                        */
+  GPEMU_WIDE_PATH_FIT_GRAD,          /* LML gradient, lml_grad_kernel / lml_grad_nu_kernel of width 16                 */
+  GPEMU_WIDE_PATH_COUNT
+};
+/* out[0 .. min(n, GPEMU_WIDE_PATH_COUNT)) = the counters; returns GPEMU_WIDE_PATH_COUNT (or GPEMU_ERR_ARG). */
+int gpemu_wide_path_counts(int64_t *out, int64_t n);
 
 /* ---- fit handle: test-only entry points ---------------------------------------------------------------------------
  * For the tests of the fit side only; nothing in the library's own flow calls them.
