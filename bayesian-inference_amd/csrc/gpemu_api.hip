@@ -147,81 +147,79 @@ static int check_device(int device) {
 }  // namespace gpemu
 
 namespace gpemu {
-// Log-posterior of B query rows already in the padded [rows >= round_up(B,128)][m->dp] layout
-// (the sampler writes its proposals in that layout).  accumulate != 0 adds to dout (multi-group).
-int logpost_padded(gpemu_model *m, int64_t B, double *dXq, double *dout, int accumulate,
-                   hipStream_t st, const AcceptArgs *aa, const ProposeArgs *pa) {
-  if (!m->lik_ready) { set_error("gpemu_likelihood_setup has not been called"); return GPEMU_ERR_STATE; }
-  int rc = ensure_workspace(m, B);
-  if (rc != GPEMU_OK) return rc;
-  // small emulators: cross-kernel and GEMM in one launch (k_halfstep.hip; the same bits), else the two general launches
-  rc = GPEMU_ERR_UNSUPPORTED;
-  if (getenv("GPEMU_NO_HALFSTEP") == nullptr && getenv("GPEMU_NO_GROUP_MERGE") == nullptr && !(aa && aa->chain_per != 0)) {
-    gpemu_model *one[1] = {m};
-    rc = launch_halfstep_small(one, 1, B, dXq, st, pa);
-  }
-  if (rc == GPEMU_ERR_UNSUPPORTED) {
-    path_count(GPEMU_PATH_HALFSTEP_GENERAL);
-    rc = launch_kstar(m, B, dXq, st, pa);
-    if (rc == GPEMU_OK) rc = launch_trmm_vsq(m, B, st);
-  }
-  if (rc != GPEMU_OK) return rc;
-  return launch_loglik_lowrank(m, B, dXq, dout, accumulate, st, aa);
+LaunchSwitches read_launch_switches() {
+  LaunchSwitches sw;
+  sw.group_merge = getenv("GPEMU_NO_GROUP_MERGE") == nullptr;
+  sw.halfstep = sw.group_merge && getenv("GPEMU_NO_HALFSTEP") == nullptr;   // "stage by stage, group by group" includes it
+  sw.loglik_tasks = getenv("GPEMU_NO_LOGLIK_TASKS") == nullptr;
+  const char *e = getenv("GPEMU_HALFSTEP_MIN_PAIRS");
+  sw.halfstep_min_pairs = e ? atoi(e) : 64;
+  e = getenv("GPEMU_LOGLIK_TASKS_MAX_ROWS");
+  sw.loglik_tasks_max_rows = e ? atoll(e) : 256;
+  return sw;
 }
 
-// Log-posterior of B padded query rows summed over ng >= 2 emulation groups with ONE launch per stage (cross-kernels,
-// triangular GEMMs, likelihoods + accept).  A sampler over the reference's shipped three groups (5 / 11 / 25 PCs, ~150
-// design points, 200 walkers) spends its half-step in nine ~6 us launches otherwise; the kernels' work per group is the
-// per-group launches' (same device functions, the groups' terms added in the same order): the same bits.
-// Eligible: at most 128 columns (the small-batch GEMM) evaluated as one chain, at most 32 PCs per group, one base kernel
-// and parameter count.  GPEMU_ERR_UNSUPPORTED otherwise (nothing launched): the caller goes group by group.
-int logpost_groups(gpemu_model *const *ms, int ng, int64_t B, double *dXq, double *dout, hipStream_t st,
-                   const AcceptArgs *aa, const ProposeArgs *pa) {
-  const bool off = getenv("GPEMU_NO_GROUP_MERGE") != nullptr;     // (tests: the per-group launches; read per call)
-  if (off || ng < 2 || ng > 8 || B < 1 || B > 128) return GPEMU_ERR_UNSUPPORTED;
-  if (aa && aa->chain_per != 0) return GPEMU_ERR_UNSUPPORTED;
+// Eligible for one launch per stage for all groups: at most 128 columns (the small-batch GEMM), at most 32 PCs per
+// group, one base kernel, parameter count and device.  A sampler over the reference's shipped three groups (5 / 11 / 25
+// PCs, ~150 design points, 200 walkers) spends its half-step in nine ~6 us launches otherwise; the kernels' work per
+// group is the per-group launches' (same device functions, the groups' terms added in the same order): the same bits.
+static bool groups_fit(gpemu_model *const *ms, int ng, int64_t B) {
+  if (ng < 2 || ng > 8 || B < 1 || B > 128) return false;
   for (int g = 0; g < ng; ++g) {
     const gpemu_model *m = ms[g];
-    if (!m->lik_ready) { set_error("gpemu_likelihood_setup has not been called"); return GPEMU_ERR_STATE; }
     const int64_t Bv = m->variant_B > 0 ? m->variant_B : B;
     if (Bv > 128 || m->k > 32 || m->d != ms[0]->d || !kstar_same_kernel(m, ms[0]) || m->ksteps != ms[0]->ksteps ||
         m->device != ms[0]->device || m->profiling)
-      return GPEMU_ERR_UNSUPPORTED;
+      return false;
   }
-  for (int g = 0; g < ng; ++g) {
-    const int rc = ensure_workspace(ms[g], B);
-    if (rc != GPEMU_OK) return rc;
-  }
-  // (the GEMM's schedules first: the one step that can still say "unsupported", before anything is launched)
-  int rc = prepare_trmm_vsq_small_groups(ms, ng, B, st);
-  if (rc != GPEMU_OK) return rc;
-  rc = launch_kstar_groups(ms, ng, B, dXq, st, pa);
-  if (rc == GPEMU_OK) rc = launch_trmm_vsq_small_groups(ms, ng, B, st);
-  if (rc != GPEMU_OK) return rc;
-  return launch_loglik_groups(ms, ng, B, dXq, dout, 0, st, aa);
+  return true;
 }
 
-// Log-posterior of B <= 128 padded query rows over ng >= 1 groups of small emulators (at most 256 design points, 32 PCs
-// each): cross-kernel and triangular GEMM of every group in ONE launch (k_halfstep.hip), then the likelihood launch of
-// the general path on single partial sums.  The same bits as the general path.  GPEMU_NO_HALFSTEP (or
-// GPEMU_NO_GROUP_MERGE: "stage by stage, group by group") switches it off (tests; read per call).
-int logpost_small(gpemu_model *const *ms, int ng, int64_t B, double *dXq, double *dout, hipStream_t st,
-                  const AcceptArgs *aa, const ProposeArgs *pa) {
-  if (getenv("GPEMU_NO_HALFSTEP") != nullptr || getenv("GPEMU_NO_GROUP_MERGE") != nullptr) return GPEMU_ERR_UNSUPPORTED;
-  if (ng < 1 || ng > 8 || B < 1 || B > 128 || (aa && aa->chain_per != 0)) return GPEMU_ERR_UNSUPPORTED;
-  for (int g = 0; g < ng; ++g) {
-    const gpemu_model *m = ms[g];
-    if (!m->lik_ready) { set_error("gpemu_likelihood_setup has not been called"); return GPEMU_ERR_STATE; }
-    if (m->Npad > 256 || m->k > 32) return GPEMU_ERR_UNSUPPORTED;
+// The query rows are in the padded [rows >= round_up(B,128)][dp] layout (the sampler writes its proposals in it), or
+// `pa` builds them there.  In order of preference: (1) cross-kernel and GEMM of every group in one launch (small
+// emulators, k_halfstep.hip); (2) for several groups, one launch per stage; (3) group by group, the groups after the
+// first adding to dout.  Stacked chains take neither (1) nor (2).  Every form gives the same bits.
+int logpost_eval(gpemu_model *const *ms, int ng, int64_t B, double *dXq, double *dout, hipStream_t st,
+                 const LaunchSwitches &sw, const AcceptArgs *aa, const ProposeArgs *pa) {
+  for (int g = 0; g < ng; ++g)
+    if (!ms[g]->lik_ready) { set_error("gpemu_likelihood_setup has not been called"); return GPEMU_ERR_STATE; }
+  for (int g = 0; g < ng; ++g) GP_TRY(ensure_workspace(ms[g], B));
+  // the likelihood stage: observable blocks on different waves where that applies, else one launch for the groups
+  auto loglik = [&](gpemu_model *const *gs, int n, int accumulate, const AcceptArgs *a) {
+    if (loglik_tasks_fit(gs, n, B, a, sw)) return launch_loglik_tasks(gs, n, B, dXq, dout, accumulate, st, a);
+    if (n == 1) return launch_loglik_lowrank(gs[0], B, dXq, dout, accumulate, st, a);
+    return launch_loglik_groups(gs, n, B, dXq, dout, accumulate, st, a);
+  };
+  const bool one_chain = !(aa && aa->chain_per != 0);
+  if (one_chain && halfstep_fits(ms, ng, B, sw)) {
+    GP_TRY(launch_halfstep_small(ms, ng, B, dXq, st, pa));
+    return loglik(ms, ng, 0, aa);
   }
-  for (int g = 0; g < ng; ++g) {
-    const int rc = ensure_workspace(ms[g], B);
-    if (rc != GPEMU_OK) return rc;
+  if (one_chain && sw.group_merge && groups_fit(ms, ng, B)) {
+    // (the GEMM's schedules first: the one step that can still decline, before anything is launched)
+    const int rc = prepare_trmm_vsq_small_groups(ms, ng, B, st);
+    if (rc != GPEMU_ERR_UNSUPPORTED) {
+      GP_TRY(rc);
+      GP_TRY(launch_kstar_groups(ms, ng, B, dXq, st, pa));
+      GP_TRY(launch_trmm_vsq_small_groups(ms, ng, B, st));
+      return loglik(ms, ng, 0, aa);
+    }
   }
-  const int rc = launch_halfstep_small(ms, ng, B, dXq, st, pa);
-  if (rc != GPEMU_OK) return rc;
-  if (ng == 1) return launch_loglik_lowrank(ms[0], B, dXq, dout, 0, st, aa);
-  return launch_loglik_groups(ms, ng, B, dXq, dout, 0, st, aa);
+  AcceptArgs chain_only;                 // groups before the last: no accept, but the rows' chains (data constants)
+  if (aa) { chain_only.chain_per = aa->chain_per; chain_only.first = aa->first; }
+  for (int g = 0; g < ng; ++g) {
+    gpemu_model *const *one = ms + g;
+    const ProposeArgs *pg = g == 0 ? pa : nullptr;
+    if (one_chain && halfstep_fits(one, 1, B, sw)) {
+      GP_TRY(launch_halfstep_small(one, 1, B, dXq, st, pg));
+    } else {
+      path_count(GPEMU_PATH_HALFSTEP_GENERAL);
+      GP_TRY(launch_kstar(ms[g], B, dXq, st, pg));
+      GP_TRY(launch_trmm_vsq(ms[g], B, st));
+    }
+    GP_TRY(loglik(one, 1, g > 0 ? 1 : 0, g + 1 == ng ? aa : (aa ? &chain_only : nullptr)));
+  }
+  return GPEMU_OK;
 }
 }  // namespace gpemu
 
@@ -507,18 +505,16 @@ int gpemu_model_sync(gpemu_model *m) {
 // ---- GP predict --------------------------------------------------------------------------------
 constexpr int64_t MAX_CHUNK = 2048;   // rows per pass of the predict pipeline (bounds the K_* workspace)
 
-// small_ok: the caller sums the partials in the likelihood's order (walker_mean_sd), which is the order in which the
-// one-launch form for small emulators (k_halfstep.hip) has summed them already
-static int gp_predict_core(gpemu_model *m, int64_t B, const double *dX, hipStream_t st, bool small_ok = false) {
-  GP_TRY(ensure_workspace(m, B));
-  ProposeArgs raw;                 // the cross-kernel kernel pads the caller's rows itself
+// caller rows [B][d]: the cross-kernel kernel pads them into the workspace itself
+static ProposeArgs raw_rows(const gpemu_model *m, int64_t B, const double *dX) {
+  ProposeArgs raw;
   raw.raw = dX; raw.n = (int)B; raw.d = (int)m->d;
-  if (small_ok && getenv("GPEMU_NO_HALFSTEP") == nullptr && getenv("GPEMU_NO_GROUP_MERGE") == nullptr) {
-    gpemu_model *one[1] = {m};
-    const int rc = launch_halfstep_small(one, 1, B, m->ws.Xq, st, &raw);
-    if (rc != GPEMU_ERR_UNSUPPORTED) return rc;
-  }
-  if (small_ok) path_count(GPEMU_PATH_HALFSTEP_GENERAL);
+  return raw;
+}
+
+static int gp_predict_core(gpemu_model *m, int64_t B, const double *dX, hipStream_t st) {
+  GP_TRY(ensure_workspace(m, B));
+  const ProposeArgs raw = raw_rows(m, B, dX);
   GP_TRY(launch_kstar(m, B, m->ws.Xq, st, &raw));
   GP_TRY(launch_trmm_vsq(m, B, st));
   return GPEMU_OK;
@@ -744,12 +740,18 @@ int gpemu_logpost_dev(gpemu_model *m, int64_t B, const double *dX, double *dout,
   if (!m->lik_ready) { set_error("gpemu_likelihood_setup has not been called"); return GPEMU_ERR_STATE; }
   GP_HIP(hipSetDevice(m->device));
   hipStream_t st = stream ? (hipStream_t)stream : m->stream;
+  const LaunchSwitches sw = read_launch_switches();
   for (int64_t off = 0; off < B; off += MAX_CHUNK) {
     const int64_t nb = (B - off < MAX_CHUNK) ? (B - off) : MAX_CHUNK;
     path_count(GPEMU_PATH_PREDICT_PASS);
-    GP_TRY(gp_predict_core(m, nb, dX + off * m->d, st, mode == GPEMU_LOGPOST_LOWRANK));
-    if (mode == GPEMU_LOGPOST_LOWRANK) GP_TRY(launch_loglik_lowrank(m, nb, m->ws.Xq, dout + off, 0, st));
-    else GP_TRY(launch_loglik_exact(m, nb, m->ws.Xq, dout + off, st));
+    if (mode == GPEMU_LOGPOST_LOWRANK) {
+      GP_TRY(ensure_workspace(m, nb));   // (before ws.Xq is read: it may move)
+      const ProposeArgs raw = raw_rows(m, nb, dX + off * m->d);
+      GP_TRY(logpost_eval(&m, 1, nb, m->ws.Xq, dout + off, st, sw, nullptr, &raw));
+    } else {
+      GP_TRY(gp_predict_core(m, nb, dX + off * m->d, st));
+      GP_TRY(launch_loglik_exact(m, nb, m->ws.Xq, dout + off, st));
+    }
   }
   return GPEMU_OK;
 }

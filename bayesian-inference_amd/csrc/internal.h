@@ -216,25 +216,36 @@ int small_trmm_xcd_of(const gpemu_model *m, int64_t B, int p, int64_t col);
 int trmm_xcd_of(const gpemu_model *m, int64_t B, int p, int64_t col);   // XCD that reads K_*^T rows (p, col) in launch_trmm_vsq(m, B); -1: any
 int launch_trmm_vsq_small(gpemu_model *m, int64_t B, hipStream_t st);   // B <= 128; GPEMU_ERR_UNSUPPORTED if the shape does not fit
 int launch_reduce_mean_var(gpemu_model *m, int64_t B, double *dmean, double *dvar, hipStream_t st);
+// The switches that choose among the log-posterior's launch forms (the same bits; tests compare them).  Their only
+// reader, read_launch_switches, runs once per public call: never cached, tests change them between calls.
+struct LaunchSwitches {
+  bool halfstep;                  // not GPEMU_NO_HALFSTEP and not GPEMU_NO_GROUP_MERGE: small emulators' one-launch form
+  bool group_merge;               // not GPEMU_NO_GROUP_MERGE: one launch per stage for all groups
+  bool loglik_tasks;              // not GPEMU_NO_LOGLIK_TASKS: observable blocks on different waves
+  int halfstep_min_pairs;         // GPEMU_HALFSTEP_MIN_PAIRS, default 64
+  int64_t loglik_tasks_max_rows;  // GPEMU_LOGLIK_TASKS_MAX_ROWS, default 256
+};
+LaunchSwitches read_launch_switches();
+// log-posterior of B padded query rows summed over ng groups: the one place that chooses the launches (gpemu_api.hip)
+int logpost_eval(gpemu_model *const *ms, int ng, int64_t B, double *dXq, double *dout, hipStream_t st,
+                 const LaunchSwitches &sw, const AcceptArgs *aa, const ProposeArgs *pa);
 int launch_loglik_lowrank(gpemu_model *m, int64_t B, const double *dXq_padded, double *dout,
-                          int accumulate, hipStream_t st, const AcceptArgs *aa = nullptr);
-int logpost_padded(gpemu_model *m, int64_t B, double *dXq, double *dout, int accumulate,
-                   hipStream_t st, const AcceptArgs *aa = nullptr, const ProposeArgs *pa = nullptr);
+                          int accumulate, hipStream_t st, const AcceptArgs *aa);
 // several emulation groups, one launch per stage instead of one per group and stage (k_predict.hip, k_trmm_small.hip,
-// k_loglik.hip): the same arithmetic as the per-group launches.  logpost_groups returns GPEMU_ERR_UNSUPPORTED -- nothing
-// launched, no error set -- where the per-group launches must be used.
+// k_loglik.hip): the same arithmetic as the per-group launches
 int launch_kstar_groups(gpemu_model *const *ms, int ng, int64_t B, double *dXq_padded, hipStream_t st, const ProposeArgs *pa);
 int prepare_trmm_vsq_small_groups(gpemu_model *const *ms, int ng, int64_t B, hipStream_t st);   // the schedules only
 int launch_trmm_vsq_small_groups(gpemu_model *const *ms, int ng, int64_t B, hipStream_t st);
 int launch_loglik_groups(gpemu_model *const *ms, int ng, int64_t B, const double *dXq_padded, double *dout, int accumulate,
                          hipStream_t st, const AcceptArgs *aa);
-int logpost_groups(gpemu_model *const *ms, int ng, int64_t B, double *dXq, double *dout, hipStream_t st,
-                   const AcceptArgs *aa, const ProposeArgs *pa);
+// the likelihood with the observable blocks on different waves (k_loglik.hip), where loglik_tasks_fit
+bool loglik_tasks_fit(gpemu_model *const *ms, int ng, int64_t B, const AcceptArgs *aa, const LaunchSwitches &sw);
+int launch_loglik_tasks(gpemu_model *const *ms, int ng, int64_t B, const double *dXq_padded, double *dout, int accumulate,
+                        hipStream_t st, const AcceptArgs *aa);
 // small emulators (N <= 256 design points, k_halfstep.hip): cross-kernel + triangular GEMM of all groups in one launch,
-// then the likelihood launch; the bits of the general path.  GPEMU_ERR_UNSUPPORTED (nothing launched) where it does not apply
+// then the likelihood launch; the bits of the general path.  Launch only where halfstep_fits
+bool halfstep_fits(gpemu_model *const *ms, int ng, int64_t B, const LaunchSwitches &sw);
 int launch_halfstep_small(gpemu_model *const *ms, int ng, int64_t B, double *dXq_padded, hipStream_t st, const ProposeArgs *pa);
-int logpost_small(gpemu_model *const *ms, int ng, int64_t B, double *dXq, double *dout, hipStream_t st,
-                  const AcceptArgs *aa, const ProposeArgs *pa);
 // fit-side building blocks (k_fit.hip): in-place blocked Cholesky of an Np x Np matrix (Np multiple of 64) with the
 // inverted diagonal blocks in Dinv [Np/64][64][64], and W = L^-1 from it (T: Np x Np scratch)
 // Optional look-ahead of the blocked Cholesky: a second (lower-priority) stream that applies a panel's update to the

@@ -346,30 +346,30 @@ __global__ __launch_bounds__(512) void halfstep_small_kernel(HsArgs ha, ProposeA
   HS_WALL(2);
 }
 
-// cross-kernel + triangular GEMM of B <= 128 query rows for ng groups of at most 256 design points in one launch; the
-// groups' workspaces then hold ONE partial per (row, PC) (cur_nchunk = cur_nrb = 1) for the likelihood launch.
-// GPEMU_ERR_UNSUPPORTED (nothing launched, no error set) where the shape does not fit: the caller takes the general path.
-int launch_halfstep_small(gpemu_model *const *ms, int ng, int64_t B, double *dXq, hipStream_t st, const ProposeArgs *pa) {
-  if (ng < 1 || ng > HS_GROUPS_MAX || B < 1 || B > 128) return GPEMU_ERR_UNSUPPORTED;
+// whether the one-launch form takes B <= 128 query rows of ng groups of at most 256 design points and 32 PCs each
+bool halfstep_fits(gpemu_model *const *ms, int ng, int64_t B, const LaunchSwitches &sw) {
+  if (!sw.halfstep || ng < 1 || ng > HS_GROUPS_MAX || B < 1 || B > 128) return false;
   const gpemu_model *m0 = ms[0];
-  int nt32max = 0;
+  int ktot = 0;
   for (int g = 0; g < ng; ++g) {
     const gpemu_model *m = ms[g];
     const int64_t Bv = m->variant_B > 0 ? m->variant_B : B;
     if (m->Npad > HS_NMAX || m->k > 32 || m->ksteps != 2 || Bv > 128 || m->d != m0->d || !kstar_same_kernel(m, m0) ||
         m->device != m0->device || m->profiling)
-      return GPEMU_ERR_UNSUPPORTED;
-    nt32max = std::max(nt32max, (int)((m->N + 31) / 32));
+      return false;
+    ktot += (int)m->k;
   }
   // few (PC, block) pairs: the general path spreads the same work over more, shorter workgroups (one group of 11 PCs, 200
   // walkers: 44 pairs, 41.1 us per step here against 38.6; 25 PCs: 100 pairs, 53.3 against 63.5)
-  {
-    int ktot = 0;
-    for (int g = 0; g < ng; ++g) ktot += (int)ms[g]->k;
-    const char *e = getenv("GPEMU_HALFSTEP_MIN_PAIRS");
-    const int min_pairs = e ? atoi(e) : 64;
-    if (ktot * (int)((B + HS_COLS - 1) / HS_COLS) < min_pairs) return GPEMU_ERR_UNSUPPORTED;
-  }
+  return ktot * (int)((B + HS_COLS - 1) / HS_COLS) >= sw.halfstep_min_pairs;
+}
+
+// cross-kernel + triangular GEMM in one launch (where halfstep_fits); the groups' workspaces then hold ONE partial per
+// (row, PC) (cur_nchunk = cur_nrb = 1) for the likelihood launch
+int launch_halfstep_small(gpemu_model *const *ms, int ng, int64_t B, double *dXq, hipStream_t st, const ProposeArgs *pa) {
+  const gpemu_model *m0 = ms[0];
+  int nt32max = 0;
+  for (int g = 0; g < ng; ++g) nt32max = std::max(nt32max, (int)((ms[g]->N + 31) / 32));
   HsArgs ha;
   memset(&ha, 0, sizeof(ha));
   ha.ng = ng;

@@ -433,31 +433,32 @@ __global__ __launch_bounds__(64 * LL_TASK_WAVES) void loglik_tasks_kernel(const 
   }
 }
 
-// GPEMU_ERR_UNSUPPORTED (nothing launched, no error set) where it does not apply: no group with more than one observable
-// block, more than 64 blocks in all, more than 32 PCs in a group, stacked chains; GPEMU_NO_LOGLIK_TASKS (tests; read per call)
-int launch_loglik_tasks(gpemu_model *const *ms, int ng, int64_t B, const double *dXq, double *dout, int accumulate,
-                        hipStream_t st, const AcceptArgs *aa) {
-  if (getenv("GPEMU_NO_LOGLIK_TASKS") != nullptr || ng < 1 || ng > LL_GROUPS_MAX || B < 1) return GPEMU_ERR_UNSUPPORTED;
-  if (aa && aa->chain_per != 0) return GPEMU_ERR_UNSUPPORTED;
+// whether launch_loglik_tasks applies: some group with more than one observable block, at most 64 blocks in all, at most
+// 32 PCs per group, no stacked chains
+bool loglik_tasks_fit(gpemu_model *const *ms, int ng, int64_t B, const AcceptArgs *aa, const LaunchSwitches &sw) {
+  if (!sw.loglik_tasks || ng < 1 || ng > LL_GROUPS_MAX || B < 1 || (aa && aa->chain_per != 0)) return false;
   int ntask = 0;
   for (int g = 0; g < ng; ++g) {
-    if (ms[g]->k > 32 || ms[g]->nblk < 1) return GPEMU_ERR_UNSUPPORTED;
+    if (ms[g]->k > 32 || ms[g]->nblk < 1) return false;
     ntask += (int)ms[g]->nblk;
   }
-  if (ntask <= ng || ntask > LL_TASKS_MAX) return GPEMU_ERR_UNSUPPORTED;
+  if (ntask <= ng || ntask > LL_TASKS_MAX) return false;
+  // A wave per task pays where the proposals alone leave most of the chip idle (the shipped ensembles: 50 - 100 per half-step:
+  // 78 -> 19 us per launch) or a proposal has many blocks; measured at C3 size, 512 proposals per half-step
+  // (tools/time_c3_blocks.py): 10 blocks 0.2714 -> 0.2634 ms per step, 5 blocks 0.2476 -> 0.2499, 2 blocks 0.2344 -> 0.2364
+  return B <= sw.loglik_tasks_max_rows || ntask >= 8;
+}
+
+int launch_loglik_tasks(gpemu_model *const *ms, int ng, int64_t B, const double *dXq, double *dout, int accumulate,
+                        hipStream_t st, const AcceptArgs *aa) {
+  int ntask = 0;
+  for (int g = 0; g < ng; ++g) ntask += (int)ms[g]->nblk;
   gpemu_model *m0 = ms[0];
   LoglikTasks lt;
   memset(&lt, 0, sizeof(lt));
   lt.ng = ng;
   lt.ntask = ntask;
   lt.nwg = (ntask + LL_TASK_WAVES - 1) / LL_TASK_WAVES;
-  // A wave per task pays where the proposals alone leave most of the chip idle (the shipped ensembles: 50 - 100 per half-step:
-  // 78 -> 19 us per launch) or a proposal has many blocks; measured at C3 size, 512 proposals per half-step
-  // (tools/time_c3_blocks.py): 10 blocks 0.2714 -> 0.2634 ms per step, 5 blocks 0.2476 -> 0.2499, 2 blocks 0.2344 -> 0.2364
-  {
-    const char *e = getenv("GPEMU_LOGLIK_TASKS_MAX_ROWS");
-    if (B > (e ? atoll(e) : 256) && ntask < 8) return GPEMU_ERR_UNSUPPORTED;
-  }
   if (lt.nwg > 1) {
     // the terms' way to the last workgroup: per model (the first group's), grown with the batch
     if (m0->lik_terms_cap < B) {
@@ -538,10 +539,6 @@ int launch_loglik_tasks(gpemu_model *const *ms, int ng, int64_t B, const double 
 // triangular GEMM launches have just written; `aa` finishes the stretch move
 int launch_loglik_groups(gpemu_model *const *ms, int ng, int64_t B, const double *dXq, double *dout, int accumulate,
                          hipStream_t st, const AcceptArgs *aa) {
-  {
-    const int rc = launch_loglik_tasks(ms, ng, B, dXq, dout, accumulate, st, aa);      // observable blocks on different waves
-    if (rc != GPEMU_ERR_UNSUPPORTED) return rc;
-  }
   LoglikGroups lg;
   lg.ng = ng;
   for (int g = 0; g < ng; ++g) {
@@ -561,11 +558,6 @@ int launch_loglik_groups(gpemu_model *const *ms, int ng, int64_t B, const double
 
 int launch_loglik_lowrank(gpemu_model *m, int64_t B, const double *dXq, double *dout, int accumulate,
                           hipStream_t st, const AcceptArgs *aa) {
-  if (m->nblk > 1) {
-    gpemu_model *one[1] = {m};
-    const int rc = launch_loglik_tasks(one, 1, B, dXq, dout, accumulate, st, aa);      // observable blocks on different waves
-    if (rc != GPEMU_ERR_UNSUPPORTED) return rc;
-  }
   const Workspace &w = m->ws;
   const int k = (int)m->k;
   AcceptArgs a = aa ? *aa : AcceptArgs();

@@ -240,29 +240,6 @@ __global__ void unpad_rows_kernel(const double *__restrict__ src, double *__rest
 }
 
 // ---- host helpers ---------------------------------------------------------------------------------
-// log-posterior of B padded query rows summed over the groups; `pa` lets the first group's kernel
-// build the rows from the ensemble (fused proposal), `aa` lets the last group's kernel finish the move
-static int eval_logpost(gpemu_sampler *s, double *dq, int64_t B, double *dout, hipStream_t st,
-                        const AcceptArgs *aa = nullptr, const ProposeArgs *pa = nullptr) {
-  const size_t ng = s->groups.size();
-  {                  // small emulators: cross-kernel and GEMM of all groups in one launch (k_halfstep.hip)
-    const int rc = logpost_small(s->groups.data(), (int)ng, B, dq, dout, st, aa, pa);
-    if (rc != GPEMU_ERR_UNSUPPORTED) return rc;
-  }
-  if (ng >= 2) {     // one launch per stage for all groups where that applies (gpemu_api.hip: logpost_groups)
-    const int rc = logpost_groups(s->groups.data(), (int)ng, B, dq, dout, st, aa, pa);
-    if (rc != GPEMU_ERR_UNSUPPORTED) return rc;
-  }
-  AcceptArgs chain_only;                 // groups before the last: no accept, but the rows' chains (data constants)
-  if (aa) { chain_only.chain_per = aa->chain_per; chain_only.first = aa->first; }
-  for (size_t g = 0; g < ng; ++g) {
-    int rc = logpost_padded(s->groups[g], B, dq, dout, g > 0 ? 1 : 0, st, g + 1 == ng ? aa : (aa ? &chain_only : nullptr),
-                            g == 0 ? pa : nullptr);
-    if (rc != GPEMU_OK) return rc;
-  }
-  return GPEMU_OK;
-}
-
 static int ensure_chain(gpemu_sampler *s, int64_t need) {
   if (need <= s->chain_cap) return GPEMU_OK;
   int64_t cap = s->chain_cap ? s->chain_cap : 256;
@@ -352,7 +329,7 @@ static ProposeArgs propose_args(gpemu_sampler *s, int h, int64_t lo, int64_t n) 
 // stacked, or more than 4096 walkers) go through in chunks of proposals: a proposal only reads walkers of the
 // complementary set, which no chunk of this half modifies.  The kernel variants (row-chunk sizes of the partial sums)
 // are chosen by the PER-CHAIN half size, so that a chain stacked with others is evaluated exactly as it would be alone.
-static int half_step_fused(gpemu_sampler *s, int h, int store_chain, hipStream_t st) {
+static int half_step_fused(gpemu_sampler *s, int h, int store_chain, hipStream_t st, const LaunchSwitches &sw) {
   const size_t o2 = rslot(s) * 2 * s->W;
   const int64_t n = s->ns[h], per_chain = n / s->nchains;
   const int64_t chunk_max = (per_chain <= 128) ? 1024 : 2048;
@@ -374,7 +351,7 @@ static int half_step_fused(gpemu_sampler *s, int h, int store_chain, hipStream_t
       aa.lpchain = s->lpchain + s->chain_len * s->W;
     }
     for (gpemu_model *m : s->groups) m->variant_B = per_chain;
-    const int rc = eval_logpost(s, s->q, nb, s->newlp + lo, st, &aa, &pa);
+    const int rc = logpost_eval(s->groups.data(), (int)s->groups.size(), nb, s->q, s->newlp + lo, st, sw, &aa, &pa);
     for (gpemu_model *m : s->groups) m->variant_B = 0;
     if (rc != GPEMU_OK) return rc;
   }
@@ -503,6 +480,7 @@ int gpemu_sampler_set_state(gpemu_sampler *s, const double *X0, const double *lo
   GP_ARG(s && X0, "null pointer");
   GP_HIP(hipSetDevice(s->device));
   hipStream_t st = s->stream;
+  const LaunchSwitches sw = read_launch_switches();
   const int64_t W = s->W, d = s->d;
   double *tmp = nullptr;
   GP_HIP(hipMalloc((void **)&tmp, sizeof(double) * W * d));
@@ -531,7 +509,7 @@ int gpemu_sampler_set_state(gpemu_sampler *s, const double *X0, const double *lo
         ca.first = off;
         ca.dp = s->dp;
         for (gpemu_model *m : s->groups) m->variant_B = (Wc + 1) / 2;
-        rc = eval_logpost(s, s->q, nb, s->newlp, st, &ca);
+        rc = logpost_eval(s->groups.data(), (int)s->groups.size(), nb, s->q, s->newlp, st, sw, &ca, nullptr);
         for (gpemu_model *m : s->groups) m->variant_B = 0;
         if (rc == GPEMU_OK) {
           e = hipMemcpyAsync(s->logp + off, s->newlp, sizeof(double) * nb, hipMemcpyDeviceToDevice, st);
@@ -635,13 +613,14 @@ int gpemu_sampler_run(gpemu_sampler *s, int64_t steps, int store_chain) {
   GP_ARG(s && steps >= 0, "sampler / steps");
   GP_HIP(hipSetDevice(s->device));
   hipStream_t st = s->stream;
+  const LaunchSwitches sw = read_launch_switches();
   // On one GPU the three-launch half-step below is the faster form (0.2275 vs 0.2516 ms per step at C3,
   // tools/time_fused_single.py: the fused front kernel runs its likelihood and cross-kernel phases back to back); the two-launch form at one rank is
   // reachable through gpemu_sampler_run_peer with a one-rank import (test_fused_run_world1_equals_three_launch_run).
   if (store_chain) GP_TRY(ensure_chain(s, s->chain_len + steps));
   for (int64_t it = 0; it < steps; ++it) {
     GP_TRY(launch_rng(s, st, steps - it));
-    for (int h = 0; h < 2; ++h) GP_TRY(half_step_fused(s, h, store_chain, st));
+    for (int h = 0; h < 2; ++h) GP_TRY(half_step_fused(s, h, store_chain, st, sw));
     GP_TRY(end_step(s, store_chain, st, true));
   }
   return check_nan(s);
@@ -652,6 +631,7 @@ int gpemu_sampler_step_host_rng(gpemu_sampler *s, const int32_t *inds, const dou
   GP_ARG(s && inds && zz && rint && logu, "null pointer");
   GP_HIP(hipSetDevice(s->device));
   hipStream_t st = s->stream;
+  const LaunchSwitches sw = read_launch_switches();
   const int64_t W = s->W;
   int64_t n0 = 0;
   for (int64_t w = 0; w < W; ++w) {
@@ -680,7 +660,7 @@ int gpemu_sampler_step_host_rng(gpemu_sampler *s, const int32_t *inds, const dou
   GP_HIP(hipMemcpyAsync(s->logu + sl * 2 * W, hu.data(), sizeof(double) * 2 * W, hipMemcpyHostToDevice, st));
   hipLaunchKernelGGL(build_sets_kernel, dim3(1), dim3(64), 0, st, s->inds + sl * W, s->idx + sl * 2 * W, (int)W);
   GP_TRY(ensure_chain(s, s->chain_len + 1));
-  for (int h = 0; h < 2; ++h) GP_TRY(half_step_fused(s, h, store_chain, st));
+  for (int h = 0; h < 2; ++h) GP_TRY(half_step_fused(s, h, store_chain, st, sw));
   GP_TRY(end_step(s, store_chain, st, true));
   return check_nan(s);  // also synchronises, so the host staging vectors may go out of scope
 }
@@ -731,11 +711,12 @@ int gpemu_sampler_half_propose_eval(gpemu_sampler *s, int half, int64_t lo, int6
   GP_ARG(s && (half == 0 || half == 1), "half");
   GP_ARG(lo >= 0 && lo <= hi && hi <= s->ns[half] && dnewlp_slice, "slice");
   GP_HIP(hipSetDevice(s->device));
+  const LaunchSwitches sw = read_launch_switches();
   if (hi > lo) {
     // the cross-kernel kernel builds this rank's proposal rows itself; the likelihood kernel writes the
     // log-probabilities straight into the caller's all-gather buffer
     const ProposeArgs pa = propose_args(s, half, lo, hi - lo);
-    GP_TRY(eval_logpost(s, s->q, hi - lo, dnewlp_slice, s->stream, nullptr, &pa));
+    GP_TRY(logpost_eval(s->groups.data(), (int)s->groups.size(), hi - lo, s->q, dnewlp_slice, s->stream, sw, nullptr, &pa));
   }
   return GPEMU_OK;
 }
@@ -886,6 +867,7 @@ int gpemu_sampler_run_sharded(gpemu_sampler *s, gpemu_comm *c, int64_t steps, in
                               int emulate_world) {
   GP_ARG(s && steps >= 0 && emulate_world >= 0, "sampler / steps / emulate_world");
   GP_HIP(hipSetDevice(s->device));
+  const LaunchSwitches sw = read_launch_switches();
   // the timing aid needs no communicator where the fused two-launch half-step applies (bench.py's scaling_model leg)
   if (emulate_world > 0 && front_eligible_for(s, emulate_world)) return front_run(s, steps, store_chain, emulate_world, 0, true);
   if (emulate_world > 0 && !c) {
@@ -926,7 +908,7 @@ int gpemu_sampler_run_sharded(gpemu_sampler *s, gpemu_comm *c, int64_t steps, in
     for (int h = 0; h < 2; ++h) {
       if (err == GPEMU_OK && hi[h] > lo[h]) {
         const ProposeArgs pa = propose_args(s, h, lo[h], hi[h] - lo[h]);
-        keep(eval_logpost(s, s->q, hi[h] - lo[h], s->gmine[h], st, nullptr, &pa));
+        keep(logpost_eval(s->groups.data(), (int)s->groups.size(), hi[h] - lo[h], s->q, s->gmine[h], st, sw, nullptr, &pa));
       }
       const ncclResult_t r = g_rccl.AllGather(s->gmine[h], s->gfull[h], (size_t)s->gper[h], ncclDouble, c->comm, st);
       if (r != ncclSuccess) {                   // the communicator itself failed: nothing more can be exchanged

@@ -273,7 +273,7 @@ def test_phase_api_slices_of_eight_ranks_equal_single(world):
 def test_groups_in_one_launch_per_stage_equal_the_per_group_launches(monkeypatch):
     """A sampler over several emulation groups at the shipped size (~150 design points, 200 walkers, 5 / 11 / 25 PCs)
     runs ONE cross-kernel, ONE triangular-GEMM and ONE likelihood launch per half-step for all groups
-    (gpemu_api.hip: logpost_groups); with GPEMU_NO_GROUP_MERGE the nine per-group launches: the same chain, bit for bit
+    (gpemu_api.hip: logpost_eval); with GPEMU_NO_GROUP_MERGE the nine per-group launches: the same chain, bit for bit
     -- also for two groups (two walkers per likelihood workgroup), through the per-phase API, and against the oracle."""
     import ctypes as C
     import torch
