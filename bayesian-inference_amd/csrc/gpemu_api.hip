@@ -357,12 +357,23 @@ int gpemu_model_create(gpemu_model **out, int device, int64_t N, int64_t d, int6
   GP_STEP(dev_alloc(&m->alpha, k * Np));
   GP_STEP(dev_alloc(&m->cv_jit, k));
   GP_STEP(dev_alloc(&m->Wt, k * Np * Np));
+  GP_STEP(dev_alloc(&m->Xtr, Np * dp));
   GP_STEP(dev_alloc(&m->comp, k * F));
   GP_STEP(dev_alloc(&m->smean, F));
   GP_STEP(dev_alloc(&m->sscale, F));
   GP_STEP(dev_alloc(&m->cunexpl, F * F));
   GP_STEP(dev_alloc(&dL, k * N * N));
   GP_STEP(upload(m->ls, hls.data(), k * dp, st));
+  {
+    std::vector<double> hX((size_t)(Np * dp), 0.0);
+    for (int64_t j = 0; j < N; ++j)
+      for (int64_t dd = 0; dd < d; ++dd) hX[(size_t)(j * dp + dd)] = X_train[j * d + dd];
+    GP_STEP(upload(m->Xtr, hX.data(), Np * dp, st));
+    if (hipStreamSynchronize(st) != hipSuccess) {   // hX goes out of scope
+      set_error("model_create: upload failed");
+      return fail(GPEMU_ERR_HIP);
+    }
+  }
   {
     // the cross-kernel's operands for the matrix cores (kstar_host.h)
     KstarHost kh;
@@ -448,7 +459,7 @@ int gpemu_model_destroy(gpemu_model *m) {
   if (m->stream) hipStreamSynchronize(m->stream);
   hipFree(m->Xs); hipFree(m->inv_ls); hipFree(m->ls); hipFree(m->Xa); hipFree(m->alf); hipFree(m->qsc); hipFree(m->qof);
   hipFree(m->etab); hipFree(m->constv); hipFree(m->kdiag);
-  hipFree(m->alpha); hipFree(m->cv_jit); hipFree(m->Wt); hipFree(m->comp); hipFree(m->smean); hipFree(m->sscale);
+  hipFree(m->alpha); hipFree(m->cv_jit); hipFree(m->Wt); hipFree(m->Xtr); hipFree(m->comp); hipFree(m->smean); hipFree(m->sscale);
   hipFree(m->cunexpl); hipFree(m->yexp); hipFree(m->yerr); hipFree(m->lo); hipFree(m->hi);
   for (const gpemu_model::LikEntry &en : m->lik_cache) { hipFree(en.G); hipFree(en.g0); hipFree(en.scal); }
   hipFree(m->exact_scratch);
@@ -554,6 +565,95 @@ int gpemu_gp_predict(gpemu_model *m, int64_t B, const double *X, double *mean_ou
     if (e != hipSuccess) { set_error("gp_predict: %s", hipGetErrorString(e)); rc = GPEMU_ERR_HIP; }
   }
   hipFree(dX); hipFree(dm); hipFree(dv);
+  return rc;
+}
+
+// ---- joint predictive covariance and draws (k_pcov.hip) --------------------------------------------------
+static bool all_finite(const double *x, int64_t n) {
+  for (int64_t i = 0; i < n; ++i)
+    if (!std::isfinite(x[i])) return false;
+  return true;
+}
+
+int gpemu_gp_predict_cov_dev(gpemu_model *m, int64_t M1, const double *dX1, int64_t M2, const double *dX2,
+                             int64_t workspace_bytes, double *dmean, double *dcov, void *stream) {
+  GP_ARG(m && dX1 && dcov, "null pointer");
+  GP_ARG(M1 > 0, "M1 must be positive");
+  GP_ARG(!dX2 || M2 > 0, "M2 must be positive");
+  GP_ARG(workspace_bytes >= 0, "workspace_bytes must be >= 0");
+  GP_HIP(hipSetDevice(m->device));
+  hipStream_t st = stream ? (hipStream_t)stream : m->stream;
+  if (dmean) {
+    // the mean through gp_predict's own launches: the same bits
+    double *dvar = nullptr;
+    GP_TRY(dev_alloc(&dvar, M1 * m->k));
+    int rc = gpemu_gp_predict_dev(m, M1, dX1, dmean, dvar, st);
+    if (rc == GPEMU_OK && hipStreamSynchronize(st) != hipSuccess) {
+      set_error("gp_predict_cov: %s", hipGetErrorString(hipGetLastError()));
+      rc = GPEMU_ERR_HIP;
+    }
+    hipFree(dvar);
+    if (rc != GPEMU_OK) return rc;
+  }
+  return predict_cov(m, M1, dX1, dX2 ? M2 : M1, dX2, workspace_bytes, dcov, st);
+}
+
+int gpemu_gp_predict_cov(gpemu_model *m, int64_t M1, const double *X1, int64_t M2, const double *X2,
+                         int64_t workspace_bytes, double *mean_out, double *cov_out) {
+  GP_ARG(m && X1 && cov_out, "null pointer");
+  GP_ARG(M1 > 0, "M1 must be positive");
+  GP_ARG(!X2 || M2 > 0, "M2 must be positive");
+  GP_ARG(workspace_bytes >= 0, "workspace_bytes must be >= 0");
+  GP_ARG(all_finite(X1, M1 * m->d) && (!X2 || all_finite(X2, M2 * m->d)), "X contains NaN or infinity");
+  if (!X2) M2 = M1;
+  GP_HIP(hipSetDevice(m->device));
+  hipStream_t st = m->stream;
+  double *dX1 = nullptr, *dX2 = nullptr, *dm = nullptr, *dc = nullptr;
+  int rc = dev_alloc(&dX1, M1 * m->d);
+  if (rc == GPEMU_OK && X2) rc = dev_alloc(&dX2, M2 * m->d);
+  if (rc == GPEMU_OK && mean_out) rc = dev_alloc(&dm, M1 * m->k);
+  if (rc == GPEMU_OK) rc = dev_alloc(&dc, m->k * M1 * M2);
+  if (rc == GPEMU_OK) rc = upload(dX1, X1, M1 * m->d, st);
+  if (rc == GPEMU_OK && X2) rc = upload(dX2, X2, M2 * m->d, st);
+  if (rc == GPEMU_OK) rc = gpemu_gp_predict_cov_dev(m, M1, dX1, M2, dX2, workspace_bytes, dm, dc, st);
+  if (rc == GPEMU_OK) {
+    hipError_t e = hipMemcpyAsync(cov_out, dc, sizeof(double) * (size_t)(m->k * M1 * M2), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && mean_out)
+      e = hipMemcpyAsync(mean_out, dm, sizeof(double) * (size_t)(M1 * m->k), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) { set_error("gp_predict_cov: %s", hipGetErrorString(e)); rc = GPEMU_ERR_HIP; }
+  }
+  (void)hipStreamSynchronize(st);
+  hipFree(dX1); hipFree(dX2); hipFree(dm); hipFree(dc);
+  return rc;
+}
+
+int gpemu_gp_sample(gpemu_model *m, int64_t M, const double *X, int64_t n_draws, const double *z,
+                    double *draws_out, double *tau_out) {
+  GP_ARG(m && X && z && draws_out && tau_out, "null pointer");
+  GP_ARG(M > 0, "M must be positive");
+  GP_ARG(n_draws > 0, "n_draws must be positive");
+  GP_ARG(all_finite(X, M * m->d), "X contains NaN or infinity");
+  GP_HIP(hipSetDevice(m->device));
+  hipStream_t st = m->stream;
+  const int64_t k = m->k;
+  double *dX = nullptr, *dm = nullptr, *dc = nullptr, *dz = nullptr, *dout = nullptr;
+  int rc = dev_alloc(&dX, M * m->d);
+  if (rc == GPEMU_OK) rc = dev_alloc(&dm, M * k);
+  if (rc == GPEMU_OK) rc = dev_alloc(&dc, k * M * M);
+  if (rc == GPEMU_OK) rc = dev_alloc(&dz, k * M * n_draws);
+  if (rc == GPEMU_OK) rc = dev_alloc(&dout, k * M * n_draws);
+  if (rc == GPEMU_OK) rc = upload(dX, X, M * m->d, st);
+  if (rc == GPEMU_OK) rc = upload(dz, z, k * M * n_draws, st);
+  if (rc == GPEMU_OK) rc = gpemu_gp_predict_cov_dev(m, M, dX, 0, nullptr, 0, dm, dc, st);
+  if (rc == GPEMU_OK) rc = sample_from_cov(m, M, n_draws, dc, dm, dz, dout, tau_out, st);
+  if (rc >= GPEMU_OK) {   // a PC whose ladder ran out (rc > 0): the others' draws are still returned
+    hipError_t e = hipMemcpyAsync(draws_out, dout, sizeof(double) * (size_t)(k * M * n_draws), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) { set_error("gp_sample: %s", hipGetErrorString(e)); rc = GPEMU_ERR_HIP; }
+  }
+  (void)hipStreamSynchronize(st);
+  hipFree(dX); hipFree(dm); hipFree(dc); hipFree(dz); hipFree(dout);
   return rc;
 }
 

@@ -116,6 +116,7 @@ struct gpemu_model {
   double *alpha = nullptr;     // [k][Npad] (padded = 0)
   double *cv_jit = nullptr;    // [k]  the fit's alpha jitter: L_00^2 - kdiag (cross-validation variances, k_cv.hip)
   double *Wt = nullptr;        // [k][Npad][Npad]  Wt[p][j][i] = (L_p^-1)[i][j]  (upper triangular)
+  double *Xtr = nullptr;       // [Npad][dp]  raw training rows (padded rows / dims = 0): the joint covariance (k_pcov.hip)
 
   // PCA / scaler
   double *comp = nullptr;      // [k][F]
@@ -266,6 +267,14 @@ int device_invert_factor_to_Wt(const double *dL, int64_t N, double *Wt, int64_t 
 int cross_validate(gpemu_model *m, int n_folds, const int *didx, const int *dfoff, const std::vector<int> &hfoff,
                    const std::vector<int> &hr0, const double *dy, double *dmean, double *dvar, int64_t max_chunk);
 int launch_cv_backproject(gpemu_model *m, const double *dmean, const double *dvar, double *dcv, double *dvo);
+// joint predictive covariance (k_pcov.hip): dcov [k][M1][M2] of the query rows dX1 [M1][d] and dX2 [M2][d] (null: the
+// symmetric form on dX1, noise on the diagonal); workspace_bytes <= 0: sized from free device memory.  Synchronises st.
+int predict_cov(gpemu_model *m, int64_t M1, const double *dX1, int64_t M2, const double *dX2, int64_t workspace_bytes,
+                double *dcov, hipStream_t st);
+// draws dout [k][M][n] = mean + chol(C_p + tau_p I) z_p from the symmetric dcov [k][M][M], dmean [M][k], dz [k][M][n];
+// tau_out[k] on the host.  Returns p + 1 for the first PC whose jitter ladder is exhausted.
+int sample_from_cov(gpemu_model *m, int64_t M, int64_t n, const double *dcov, const double *dmean, const double *dz,
+                    double *dout, double *tau_out, hipStream_t st);
 // profiling helpers: record an event on `st` and return its pool index (-1 when profiling is off)
 int prof_mark(gpemu_model *m, hipStream_t st);
 void prof_pair(gpemu_model *m, int which, int e0, int e1);

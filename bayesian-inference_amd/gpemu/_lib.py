@@ -47,6 +47,11 @@ _SIGNATURES = {
     "gpemu_model_profile_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "gpemu_gp_predict": (C.c_int, [C.c_void_p, c_i64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gpemu_gp_predict_dev": (C.c_int, [C.c_void_p, c_i64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gpemu_gp_predict_cov": (C.c_int, [C.c_void_p, c_i64, C.c_void_p, c_i64, C.c_void_p, c_i64, C.c_void_p,
+                                       C.c_void_p]),
+    "gpemu_gp_predict_cov_dev": (C.c_int, [C.c_void_p, c_i64, C.c_void_p, c_i64, C.c_void_p, c_i64, C.c_void_p,
+                                           C.c_void_p, C.c_void_p]),
+    "gpemu_gp_sample": (C.c_int, [C.c_void_p, c_i64, C.c_void_p, c_i64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gpemu_predict_full": (C.c_int, [C.c_void_p, c_i64, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]),
     "gpemu_predict_full_dev": (C.c_int, [C.c_void_p, c_i64, C.c_void_p, C.c_double, C.c_void_p,
                                          C.c_void_p, C.c_void_p]),

@@ -191,6 +191,7 @@ class GaussianProcessRegressor:
     def __getstate__(self):
         st = dict(self.__dict__)
         st["_dev"] = None
+        st.pop("sample_y_jitter_", None)   # a result of the last sample_y call, not state of the emulator
         return st
 
     def _optimise(self, dfit, y, theta0, bounds):
@@ -282,13 +283,50 @@ class GaussianProcessRegressor:
         return self._dev
 
     def predict(self, X, return_std=False, return_cov=False):
-        if return_cov:
-            raise NotImplementedError("return_cov is not on the reference's path")
+        """skl _gpr.py:367-469 with normalize_y=False: the mean, and with ``return_std`` the standard deviation
+        (negative variances clipped to 0) or with ``return_cov`` the joint covariance kernel_(X) - V^T V (not clipped;
+        the White noise on its diagonal), both on the device."""
+        if return_std and return_cov:
+            raise RuntimeError("At most one of return_std or return_cov can be requested.")
         X = np.array(X, ndmin=2, dtype=np.float64)
+        if return_cov:
+            mean, cov = self._device().gp_predict_cov(X)
+            return mean[:, 0], cov[0]
         mean, var = self._device().gp_predict(X)
         if return_std:
             return mean[:, 0], np.sqrt(var[:, 0])
         return mean[:, 0]
+
+    def sample_y(self, X, n_samples=1, random_state=0):
+        """Draws of the GP at X, shape (M, n_samples) (skl _gpr.py:498-531).
+
+        ``Z`` (M, n_samples) comes from ``random_state`` (int, None or ``np.random.RandomState``, as sklearn's
+        ``check_random_state``) by ``standard_normal``; a draw is ``mean + chol(C + tau I) Z`` with C the joint
+        covariance of ``predict(X, return_cov=True)``, factored on the device.  The draws follow the same
+        distribution as scikit-learn's, but they are not the same numbers: scikit-learn draws through the SVD of
+        ``RandomState.multivariate_normal``.  ``tau`` is 0 unless C is not numerically positive definite; then it
+        climbs ``1e-12 mean(diag C) 10^i``, i = 0 .. 6, and the value used is left in ``sample_y_jitter_``.  If the
+        last rung fails, ``gpemu.fit.LinAlgError`` is raised."""
+        n_samples = int(n_samples)
+        if n_samples < 1:
+            raise ValueError(f"n_samples must be >= 1, got {n_samples}")
+        rng = _check_random_state(random_state)
+        X = np.array(X, ndmin=2, dtype=np.float64)
+        z = rng.standard_normal((X.shape[0], n_samples))
+        draws, tau = self._device().gp_sample(X, z[None])
+        self.sample_y_jitter_ = float(tau[0])
+        return draws[0]
+
+
+def _check_random_state(seed):
+    """sklearn.utils.check_random_state: None -> numpy's global RandomState, int -> a new one, an instance as is."""
+    if seed is None or seed is np.random:
+        return np.random.mtrand._rand
+    if isinstance(seed, (int, np.integer)):
+        return np.random.RandomState(seed)
+    if isinstance(seed, np.random.RandomState):
+        return seed
+    raise ValueError(f"{seed!r} cannot be used to seed a numpy.random.RandomState instance")
 
 
 class _LockStepEvaluator:

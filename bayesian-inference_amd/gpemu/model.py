@@ -109,6 +109,41 @@ class DeviceModel:
         check(_lib.lib().gpemu_gp_predict(self._h, B, ptr(X), ptr(mean), ptr(var)))
         return mean, var
 
+    def gp_predict_cov(self, X, X2=None, workspace_bytes=0):
+        """Joint predictive covariance of every PC (skl _gpr.py:367-469, predict(X, return_cov=True)): ``mean``
+        (M1, k) and ``cov`` (k, M1, M2) = kernel_(X, X2) - V1^T V2.  ``X2=None``: the symmetric form on X (the White
+        noise on the diagonal, the output symmetric bit for bit).  ``workspace_bytes`` caps the device workspace
+        (0: sized from free memory); the result does not depend on it."""
+        X = self._finite(self._X(X))
+        M1 = X.shape[0]
+        X2a = None if X2 is None else self._finite(self._X(X2))
+        M2 = M1 if X2a is None else X2a.shape[0]
+        mean = np.empty((M1, self.k))
+        cov = np.empty((self.k, M1, M2))
+        check(_lib.lib().gpemu_gp_predict_cov(self._h, M1, ptr(X), M2, ptr(X2a), int(workspace_bytes), ptr(mean),
+                                              ptr(cov)))
+        return mean, cov
+
+    def gp_sample(self, X, z):
+        """Draws of every PC's GP at X (skl _gpr.py:498-531, sample_y): ``draws`` (k, M, n) = mean_p +
+        chol(C_p + tau_p I) z_p for the standard normals ``z`` (k, M, n), and ``tau`` (k,), the jitter each PC's
+        factor needed (0 first, then 1e-12 mean(diag C_p) 10^i, i = 0 .. 6).  Raises ``fit.LinAlgError`` if a PC's
+        covariance is not positive definite at the last rung."""
+        from .fit import LinAlgError
+        X = self._finite(self._X(X))
+        M = X.shape[0]
+        z = np.ascontiguousarray(z, dtype=np.float64)
+        if z.ndim != 3 or z.shape[0] != self.k or z.shape[1] != M or z.shape[2] < 1:
+            raise ValueError(f"z must have shape ({self.k}, {M}, n_draws >= 1), got {z.shape}")
+        n = z.shape[2]
+        draws = np.empty((self.k, M, n))
+        tau = np.empty(self.k)
+        rc = _lib.lib().gpemu_gp_sample(self._h, M, ptr(X), n, ptr(z), ptr(draws), ptr(tau))
+        if rc > 0:
+            raise LinAlgError(_lib.last_error())
+        check(rc)
+        return draws, tau
+
     def predict_full(self, X, n_div=None):
         """central_value (B,F), cov (B,F,F) as ref: emulation.py:466-548 (n_div defaults to B)."""
         X = self._finite(self._X(X))
@@ -211,6 +246,12 @@ class DeviceModel:
     def gp_predict_dev(self, dX_ptr, B, dmean_ptr, dvar_ptr, stream=0):
         check(_lib.lib().gpemu_gp_predict_dev(self._h, int(B), C.c_void_p(dX_ptr), C.c_void_p(dmean_ptr),
                                               C.c_void_p(dvar_ptr), C.c_void_p(stream)))
+
+    def gp_predict_cov_dev(self, dX1_ptr, M1, dX2_ptr, M2, dmean_ptr, dcov_ptr, workspace_bytes=0, stream=0):
+        check(_lib.lib().gpemu_gp_predict_cov_dev(self._h, int(M1), C.c_void_p(dX1_ptr), int(M2),
+                                                  C.c_void_p(dX2_ptr) if dX2_ptr else None, int(workspace_bytes),
+                                                  C.c_void_p(dmean_ptr) if dmean_ptr else None, C.c_void_p(dcov_ptr),
+                                                  C.c_void_p(stream)))
 
     def predict_full_dev(self, dX_ptr, B, n_div, dcv_ptr, dcov_ptr, stream=0):
         check(_lib.lib().gpemu_predict_full_dev(self._h, int(B), C.c_void_p(dX_ptr), float(n_div),

@@ -98,6 +98,18 @@ int gpemu_gp_predict(gpemu_model *m, int64_t B, const double *X, double *mean_ou
 int gpemu_gp_predict_dev(gpemu_model *m, int64_t B, const double *dX, double *dmean, double *dvar,
                          void *stream);
 
+/* skl _gpr.py:367-469 predict(X, return_cov=True), per PC: cov_out[p*M1*M2 + a*M2 + b] = kernel_(x1_a, x2_b)
+ * - V1_a . V2_b.  X2 == NULL: the symmetric form on X1 (noise on the diagonal, exactly symmetric output).
+ * mean_out[M1*k] may be NULL.  workspace_bytes = 0: sized from free device memory. */
+int gpemu_gp_predict_cov(gpemu_model *m, int64_t M1, const double *X1, int64_t M2, const double *X2,
+                         int64_t workspace_bytes, double *mean_out, double *cov_out);
+int gpemu_gp_predict_cov_dev(gpemu_model *m, int64_t M1, const double *dX1, int64_t M2, const double *dX2,
+                             int64_t workspace_bytes, double *dmean, double *dcov, void *stream);
+/* skl _gpr.py:498-531 sample_y: draws_out[p*M*n + a*n + s] = mean_p(x_a) + (chol(C_p + tau_p I) z_p)[a, s],
+ * z[k*M*n] standard normals, tau_out[k] the jitter each PC needed; returns p+1 if PC p's ladder is exhausted. */
+int gpemu_gp_sample(gpemu_model *m, int64_t M, const double *X, int64_t n_draws, const double *z,
+                    double *draws_out, double *tau_out);
+
 /* ref: emulation.py:466-548 (predict_emulation_group): central_value[B*F], cov[B*F*F];
  * n_div = the reference's n_samples divisor of the truncation covariance (emulation.py:531-532). */
 int gpemu_predict_full(gpemu_model *m, int64_t B, const double *X, double n_div, double *cv_out,
