@@ -3,6 +3,8 @@
 #include <atomic>
 #include <cmath>
 #include <cstdarg>
+#include <mutex>
+#include <set>
 
 #include "internal.h"
 #include "kstar_host.h"
@@ -37,6 +39,18 @@ void set_error(const char *fmt, ...) {
   va_end(ap);
 }
 
+int allow_dynamic_lds(const void *fn, int bytes) {
+  static std::mutex mu;
+  static std::set<std::pair<const void *, int>> allowed;   // (function, device) pairs whose attribute is set
+  int dev = 0;
+  GP_HIP(hipGetDevice(&dev));
+  std::lock_guard<std::mutex> lock(mu);
+  if (allowed.count({fn, dev})) return GPEMU_OK;
+  GP_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+  allowed.insert({fn, dev});
+  return GPEMU_OK;
+}
+
 int launch_lik_setup(gpemu_model *m, const std::vector<int> &hstart, double *dA, double *dPT, double *dZ, int *dinfo,
                      hipStream_t st);
 int launch_predict_full(gpemu_model *m, int64_t B, double n_div, double *dcv, double *dcov, hipStream_t st,
@@ -50,12 +64,6 @@ static int dev_alloc(T **p, int64_t n) {
   GP_HIP(hipMalloc((void **)p, sizeof(T) * (size_t)n));
   return GPEMU_OK;
 }
-#define GP_TRY(expr)            \
-  do {                          \
-    int rc__ = (expr);          \
-    if (rc__ != GPEMU_OK) return rc__; \
-  } while (0)
-
 static int upload(double *dst, const double *src, int64_t n, hipStream_t st) {
   GP_HIP(hipMemcpyAsync(dst, src, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, st));
   return GPEMU_OK;

@@ -7,6 +7,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -32,6 +33,16 @@ void set_error(const char *fmt, ...);
       return GPEMU_ERR_ARG;              \
     }                                    \
   } while (0)
+// propagate a non-OK status code of a library call
+#define GP_TRY(expr)                     \
+  do {                                   \
+    const int rc__ = (expr);             \
+    if (rc__ != GPEMU_OK) return rc__;   \
+  } while (0)
+
+// lets `fn` (a kernel, by its host stub) use `bytes` of dynamic LDS beyond the default 64 KiB: the attribute is set once
+// per (function, current device), under a lock, so that later calls -- from any host thread -- make no call to set it
+int allow_dynamic_lds(const void *fn, int bytes);
 
 static inline int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
 
@@ -194,15 +205,29 @@ struct ProposeArgs {
 };
 
 int ensure_workspace(gpemu_model *m, int64_t B);
-// base kernel of the cross-kernel templates: 0 RBF (and Matern nu = inf, skl kernels.py:1722-1723), 1 / 2 / 3 Matern
-// 0.5 / 1.5 / 2.5 (closed forms), 4 Matern of any other nu (matern_dev.h; its constants behind etab's table)
-static inline int kstar_kind(const gpemu_model *m) {
-  if (m->kernel_kind == GPEMU_KERNEL_RBF) return 0;
-  if (m->nu == 0.5) return 1;
-  if (m->nu == 1.5) return 2;
-  if (m->nu == 2.5) return 3;
-  if (m->nu == INFINITY) return 0;
+// base kernel of the kernel templates (fit, cross-kernel, covariance): 0 RBF (and Matern nu = inf, skl
+// kernels.py:1722-1723), 1 / 2 / 3 Matern 0.5 / 1.5 / 2.5 (closed forms: matern_dev.h, base_from_r2), 4 Matern of any
+// other nu (matern_dev.h; in the cross-kernel its constants behind etab's table)
+static inline int base_kind(int kernel_kind, double nu) {
+  if (kernel_kind == GPEMU_KERNEL_RBF) return 0;
+  if (nu == 0.5) return 1;
+  if (nu == 1.5) return 2;
+  if (nu == 2.5) return 3;
+  if (nu == INFINITY) return 0;
   return 4;
+}
+static inline int kstar_kind(const gpemu_model *m) { return base_kind(m->kernel_kind, m->nu); }
+// the runtime base kind as a template argument: returns fn(std::integral_constant<int, K>{}) for K = kind in 0 .. 4
+template <class Fn>
+static inline int with_base_kind(int kind, Fn &&fn) {
+  switch (kind) {
+    case 0: return fn(std::integral_constant<int, 0>{});
+    case 1: return fn(std::integral_constant<int, 1>{});
+    case 2: return fn(std::integral_constant<int, 2>{});
+    case 3: return fn(std::integral_constant<int, 3>{});
+    case 4: return fn(std::integral_constant<int, 4>{});
+    default: set_error("unknown base kernel %d", kind); return GPEMU_ERR_STATE;
+  }
 }
 // two models whose cross-kernels can share one launch: the same base kernel (and, for kind 4, the same nu)
 static inline bool kstar_same_kernel(const gpemu_model *a, const gpemu_model *b) {

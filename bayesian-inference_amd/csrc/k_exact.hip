@@ -461,12 +461,7 @@ int launch_predict_full(gpemu_model *m, int64_t B, double n_div, double *dcv, do
     // 16 waves x 32 columns (CBW = 2, 8 waves x 64 columns, measured within 1 % on the whole chip: not instantiated)
 #define GP_LAUNCH_PM2(KSV, CB, DB)                                                                                 \
   do {                                                                                                             \
-    static bool attr_set = false;                                                                                  \
-    if (!attr_set) {                                                                                               \
-      GP_HIP(hipFuncSetAttribute((const void *)predict_cov_mfma_kernel<KSV, CB, DB>,                               \
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, 140 * 1024));                        \
-      attr_set = true;                                                                                             \
-    }                                                                                                              \
+    GP_TRY(allow_dynamic_lds((const void *)predict_cov_mfma_kernel<KSV, CB, DB>, 140 * 1024));                     \
     hipLaunchKernelGGL((predict_cov_mfma_kernel<KSV, CB, DB>), dim3((unsigned)workers), dim3(1024 / CB), shm_pm,   \
                        st, parts, m->comp, m->sscale, m->cunexpl, dcov, B, F, k, 1.0 / n_div, ngroups, total);     \
   } while (0)

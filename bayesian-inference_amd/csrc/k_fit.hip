@@ -30,24 +30,17 @@ constexpr int NB = 64;
 typedef double d4t __attribute__((ext_vector_type(4)));
 
 // ---- kernel matrix ---------------------------------------------------------------------------
-__device__ __forceinline__ double base_from_r2(int kind, double r2) {
-  if (kind == 0) return exp(-0.5 * r2);
-  double r = sqrt(r2);
-  if (kind == 1) return exp(-r);
-  if (kind == 2) {
-    double t = r * 1.7320508075688772;
-    return (1.0 + t) * exp(-t);
-  }
-  double t = r * 2.23606797749979;
-  return (1.0 + t + t * t / 3.0) * exp(-t);
-}
+// the base kernel of a fit kernel's instance: its kind 0-3 (matern_dev.h: base_from_r2), or with NU the constants of
+// the general-nu Matern (kind 4) -- an instance of its own, so that the one that serves kinds 0-3 keeps its code
+template <bool NU>
+using FitBase = std::conditional_t<NU, MaternNu, int>;
 
 // X [Np][DP] raw inputs; hp = {ls[DP], const, noise}; K[i][j] for i,j < N, identity tail (DP: the handle's padded width)
 // blockIdx.z: problem of a batch (own hyper-parameters and matrix, shared inputs)
 constexpr int KMAT_ROWS = 16;     // rows of K per workgroup: the scaled coordinates of column j are formed once for all of them
-template <int DP>
+template <int DP, bool NU>
 __global__ __launch_bounds__(256) void kmat_kernel(const double *__restrict__ X, const double *__restrict__ hp,
-                                                   double *__restrict__ K, int N, int Np, int kind, double jitter) {
+                                                   double *__restrict__ K, int N, int Np, FitBase<NU> base, double jitter) {
   __shared__ double s_xi[KMAT_ROWS][DP];
   const int j = blockIdx.x * blockDim.x + threadIdx.x;
   const int i0 = blockIdx.y * KMAT_ROWS;
@@ -79,49 +72,8 @@ __global__ __launch_bounds__(256) void kmat_kernel(const double *__restrict__ X,
         const double df = s_xi[r][dd] - xj[dd];
         r2 = fma(df, df, r2);
       }
-      v = base_from_r2(kind, r2) + cst;
-    }
-    K[(int64_t)i * Np + j] = v;
-  }
-}
-
-// kind 4 (Matern, general nu: matern_dev.h): kmat_kernel with the general value -- a kernel of its own, so that the
-// instance that serves kinds 0-3 keeps its code
-template <int DP>
-__global__ __launch_bounds__(256) void kmat_nu_kernel(const double *__restrict__ X, const double *__restrict__ hp,
-                                                      double *__restrict__ K, int N, int Np, MaternNu mn, double jitter) {
-  __shared__ double s_xi[KMAT_ROWS][DP];
-  const int j = blockIdx.x * blockDim.x + threadIdx.x;
-  const int i0 = blockIdx.y * KMAT_ROWS;
-  hp += (int64_t)blockIdx.z * (DP + 2);
-  K += (int64_t)blockIdx.z * Np * Np;
-  // skl: X / length_scale, then the difference -- the quotients are the same numbers whoever forms them
-  if (threadIdx.x < KMAT_ROWS * DP) {
-    const int r = threadIdx.x / DP, dd = threadIdx.x % DP;
-    s_xi[r][dd] = (i0 + r < N) ? X[(i0 + r) * DP + dd] / hp[dd] : 0.0;
-  }
-  double xj[DP];
-#pragma unroll
-  for (int dd = 0; dd < DP; ++dd) xj[dd] = (j < N) ? X[j * DP + dd] / hp[dd] : 0.0;
-  const double cst = hp[DP], diag = 1.0 + hp[DP] + hp[DP + 1] + jitter;   // np.fill_diagonal(K, 1) + const + noise + alpha
-  __syncthreads();
-  if (j >= Np) return;
-  for (int r = 0; r < KMAT_ROWS; ++r) {
-    const int i = i0 + r;
-    if (i >= Np) break;
-    double v;
-    if (i >= N || j >= N) {
-      v = (i == j) ? 1.0 : 0.0;
-    } else if (i == j) {
-      v = diag;
-    } else {
-      double r2 = 0.0;
-#pragma unroll
-      for (int dd = 0; dd < DP; ++dd) {
-        const double df = s_xi[r][dd] - xj[dd];
-        r2 = fma(df, df, r2);
-      }
-      v = matern_nu_value(mn, sqrt(r2)) + cst;
+      if constexpr (NU) v = matern_nu_value(base, sqrt(r2)) + cst;
+      else v = base_from_r2(base, r2) + cst;
     }
     K[(int64_t)i * Np + j] = v;
   }
@@ -1094,11 +1046,11 @@ __global__ __launch_bounds__(1024) void lml_terms_kernel(const double *__restric
 // NTH = DP + 2 slots per partial sum (the padded width's length scales, const, noise), whatever d is
 static inline int64_t nth_max(int dp) { return dp + 2; }
 constexpr int GRAD_ROWS = 16;
-template <int DP>
+template <int DP, bool NU>
 __global__ __launch_bounds__(256) void lml_grad_kernel(const double *__restrict__ X, const double *__restrict__ hp,
                                                        const double *__restrict__ alpha,
                                                        const double *__restrict__ Kinv, int64_t ld,
-                                                       double *__restrict__ gpart, int N, int d, int kind,
+                                                       double *__restrict__ gpart, int N, int d, FitBase<NU> base,
                                                        int has_const, int has_noise) {
   constexpr int NTH = DP + 2;
   __shared__ double red[NTH][4];
@@ -1138,91 +1090,19 @@ __global__ __launch_bounds__(256) void lml_grad_kernel(const double *__restrict_
       r2 += D[dd];
     }
     double f;  // dK_base/dlog l_dd = f * D[dd]
-    if (kind == 0) {
+    if constexpr (NU) {
+      (void)matern_nu_value_grad(base, sqrt(r2), f);              // analytic (skl: forward difference, kernels.py:1767-1774)
+    } else if (base == 0) {
       f = (j == l) ? 1.0 : exp(-0.5 * r2);                       // K_gradient = D * K
-    } else if (kind == 1) {
+    } else if (base == 1) {
       double r = sqrt(r2);
       f = (r > 0.0) ? exp(-r) / r : 0.0;                          // K * D / sqrt(sum D), 0 where r == 0
-    } else if (kind == 2) {
+    } else if (base == 2) {
       f = 3.0 * exp(-sqrt(3.0 * r2));                             // 3 D exp(-sqrt(3 sum D))
     } else {
       double tmp = sqrt(5.0 * r2);
       f = 5.0 / 3.0 * (tmp + 1.0) * exp(-tmp);                    // 5/3 D (tmp + 1) exp(-tmp)
     }
-#pragma unroll
-    for (int dd = 0; dd < DP; ++dd) acc[dd] += 0.5 * wgt * f * D[dd];
-    if constexpr (DP == DPAD) {
-      if (has_const) acc[d] += 0.5 * wgt * hp[DP];
-      if (has_noise && j == l) acc[d + has_const] += 0.5 * wgt * hp[DP + 1];
-    } else {
-      // the same two additions with compile-time slots: a runtime index into 18 registers puts acc in scratch
-#pragma unroll
-      for (int t = 0; t < NTH; ++t) {
-        if (has_const && t == d) acc[t] += 0.5 * wgt * hp[DP];
-        if (has_noise && j == l && t == d + has_const) acc[t] += 0.5 * wgt * hp[DP + 1];
-      }
-    }
-  }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int t = 0; t < NTH; ++t) {
-    double s = acc[t];
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
-    if (lane == 0) red[t][wave] = s;
-  }
-  __syncthreads();
-  if (threadIdx.x < NTH) {
-    const int t = threadIdx.x;
-    gpart[(int64_t)blockIdx.x * NTH + t] = (red[t][0] + red[t][1]) + (red[t][2] + red[t][3]);
-  }
-}
-
-// kind 4: lml_grad_kernel with the general-nu derivative (matern_dev.h: matern_nu_value_grad), a kernel of its own
-template <int DP>
-__global__ __launch_bounds__(256) void lml_grad_nu_kernel(const double *__restrict__ X, const double *__restrict__ hp,
-                                                          const double *__restrict__ alpha,
-                                                          const double *__restrict__ Kinv, int64_t ld,
-                                                          double *__restrict__ gpart, int N, int d, MaternNu mn,
-                                                          int has_const, int has_noise) {
-  constexpr int NTH = DP + 2;
-  __shared__ double red[NTH][4];
-  // 1-D grid over the (row group, 256-column block) pairs that reach under the diagonal only (half of the full grid's
-  // workgroups would start to find nothing to do): row groups 16 b .. 16 b + 15 have b + 1 blocks, so position
-  // t = (b + 1)(8 b + r) + x  <->  row group 16 b + r, block x
-  int b = (int)((sqrt(1.0 + 0.5 * (double)blockIdx.x) - 1.0) * 0.5);
-  while (8 * b * (b + 1) > (int)blockIdx.x) --b;
-  while (8 * (b + 1) * (b + 2) <= (int)blockIdx.x) ++b;
-  const int rem = (int)blockIdx.x - 8 * b * (b + 1);
-  const int by = 16 * b + rem / (b + 1), bx = rem % (b + 1);
-  const int l = bx * blockDim.x + threadIdx.x;
-  const int j0 = by * GRAD_ROWS;                       // this workgroup's rows j0 .. j0 + GRAD_ROWS - 1 (one reduction for all)
-  hp += (int64_t)blockIdx.z * (DP + 2);              // blockIdx.z: problem of a batch
-  alpha += (int64_t)blockIdx.z * ld;
-  Kinv += (int64_t)blockIdx.z * ld * ld;
-  gpart += (int64_t)blockIdx.z * gridDim.x * NTH;
-  double acc[NTH];
-#pragma unroll
-  for (int t = 0; t < NTH; ++t) acc[t] = 0.0;
-  double xl[DP], il2[DP];
-#pragma unroll
-  for (int dd = 0; dd < DP; ++dd) {
-    xl[dd] = (l < N) ? X[l * DP + dd] : 0.0;
-    il2[dd] = 1.0 / (hp[dd] * hp[dd]);      // once per thread; a division per pair and dimension was 4/5 of this kernel
-  }
-  const double al = (l < N) ? alpha[l] : 0.0;
-  // the summand is symmetric in (j, l): the lower triangle counts twice, Kinv is only read (and only valid) there
-  for (int j = j0; j < j0 + GRAD_ROWS && j < N; ++j) {
-    if (l > j) continue;
-    const double wgt = (l < j ? 2.0 : 1.0) * (alpha[j] * al - Kinv[(int64_t)j * ld + l]);
-    double D[DP], r2 = 0.0;
-#pragma unroll
-    for (int dd = 0; dd < DP; ++dd) {
-      double df = X[j * DP + dd] - xl[dd];
-      D[dd] = (df * df) * il2[dd];             // (x - x')^2 / l^2   (skl kernels.py:1574, 1748)
-      r2 += D[dd];
-    }
-    double f;  // dK_base/dlog l_dd = f * D[dd]: analytic (skl: forward difference, kernels.py:1767-1774)
-    (void)matern_nu_value_grad(mn, sqrt(r2), f);
 #pragma unroll
     for (int dd = 0; dd < DP; ++dd) acc[dd] += 0.5 * wgt * f * D[dd];
     if constexpr (DP == DPAD) {
@@ -1341,7 +1221,7 @@ struct gpemu_fit {
   int device = 0;
   int64_t N = 0, d = 0, Np = 0;
   int dp = gpemu::DPAD;                  // padded parameter width of X and hp: DPAD (d <= 8) or DPAD_WIDE
-  int kind = 0, has_const = 0, has_noise = 0;   // kind: fit_kind_of
+  int kind = 0, has_const = 0, has_noise = 0;   // kind: base_kind
   gpemu::MaternNu mnu{};           // kind 4: the constants of nu (matern_dev.h)
   double jitter = 0.0;
   hipStream_t stream = nullptr;
@@ -1358,22 +1238,6 @@ struct gpemu_fit {
 };
 
 using namespace gpemu;
-#define GP_TRY(expr)            \
-  do {                          \
-    int rc__ = (expr);          \
-    if (rc__ != GPEMU_OK) return rc__; \
-  } while (0)
-
-// 0 RBF (and Matern nu = inf: skl kernels.py:1722-1723, exp(-d^2 / 2)), 1 / 2 / 3 Matern 0.5 / 1.5 / 2.5 (closed forms),
-// 4 Matern of any other nu (matern_dev.h)
-static int fit_kind_of(int kernel_kind, double nu) {
-  if (kernel_kind == GPEMU_KERNEL_RBF) return 0;
-  if (nu == 0.5) return 1;
-  if (nu == 1.5) return 2;
-  if (nu == 2.5) return 3;
-  if (nu == INFINITY) return 0;
-  return 4;
-}
 
 static void launch_kmat(const gpemu_fit *f, int64_t N, int nb, double jitter, hipStream_t st) {
   const dim3 grid((unsigned)((f->Np + 255) / 256), (unsigned)((f->Np + KMAT_ROWS - 1) / KMAT_ROWS), (unsigned)nb);
@@ -1381,14 +1245,14 @@ static void launch_kmat(const gpemu_fit *f, int64_t N, int nb, double jitter, hi
   else wide_path_count(GPEMU_WIDE_PATH_FIT_KMAT);
   if (f->kind == 4) {
     if (f->dp == DPAD)
-      hipLaunchKernelGGL(kmat_nu_kernel<DPAD>, grid, dim3(256), 0, st, f->X, f->hp, f->K, (int)N, (int)f->Np, f->mnu, jitter);
+      hipLaunchKernelGGL((kmat_kernel<DPAD, true>), grid, dim3(256), 0, st, f->X, f->hp, f->K, (int)N, (int)f->Np, f->mnu, jitter);
     else
-      hipLaunchKernelGGL(kmat_nu_kernel<DPAD_WIDE>, grid, dim3(256), 0, st, f->X, f->hp, f->K, (int)N, (int)f->Np, f->mnu, jitter);
+      hipLaunchKernelGGL((kmat_kernel<DPAD_WIDE, true>), grid, dim3(256), 0, st, f->X, f->hp, f->K, (int)N, (int)f->Np, f->mnu, jitter);
   } else {
     if (f->dp == DPAD)
-      hipLaunchKernelGGL(kmat_kernel<DPAD>, grid, dim3(256), 0, st, f->X, f->hp, f->K, (int)N, (int)f->Np, f->kind, jitter);
+      hipLaunchKernelGGL((kmat_kernel<DPAD, false>), grid, dim3(256), 0, st, f->X, f->hp, f->K, (int)N, (int)f->Np, f->kind, jitter);
     else
-      hipLaunchKernelGGL(kmat_kernel<DPAD_WIDE>, grid, dim3(256), 0, st, f->X, f->hp, f->K, (int)N, (int)f->Np, f->kind, jitter);
+      hipLaunchKernelGGL((kmat_kernel<DPAD_WIDE, false>), grid, dim3(256), 0, st, f->X, f->hp, f->K, (int)N, (int)f->Np, f->kind, jitter);
   }
 }
 
@@ -1491,11 +1355,11 @@ static int fit_eval_batch(gpemu_fit *f, int nb, const double *ys, const double *
 #define GP_LAUNCH_GRAD(DPV)                                                                                                   \
   do {                                                                                                                      \
     if (f->kind == 4)                                                                                                       \
-      hipLaunchKernelGGL(lml_grad_nu_kernel<DPV>, grid, dim3(256), 0, st, f->X, f->hp, f->alpha, f->Kinv, Np, f->gpart,     \
-                         (int)N, (int)d, f->mnu, f->has_const, f->has_noise);                                               \
+      hipLaunchKernelGGL((lml_grad_kernel<DPV, true>), grid, dim3(256), 0, st, f->X, f->hp, f->alpha, f->Kinv, Np,          \
+                         f->gpart, (int)N, (int)d, f->mnu, f->has_const, f->has_noise);                                     \
     else                                                                                                                    \
-      hipLaunchKernelGGL(lml_grad_kernel<DPV>, grid, dim3(256), 0, st, f->X, f->hp, f->alpha, f->Kinv, Np, f->gpart,        \
-                         (int)N, (int)d, f->kind, f->has_const, f->has_noise);                                              \
+      hipLaunchKernelGGL((lml_grad_kernel<DPV, false>), grid, dim3(256), 0, st, f->X, f->hp, f->alpha, f->Kinv, Np,         \
+                         f->gpart, (int)N, (int)d, f->kind, f->has_const, f->has_noise);                                    \
     hipLaunchKernelGGL(grad_reduce_stage1_kernel<DPV>, dim3(GR_BLOCKS, (unsigned)nb), dim3(256), 0, st, f->gpart,          \
                        npairs, f->gstage, nth);                                                                             \
     hipLaunchKernelGGL(grad_reduce_kernel<DPV>, dim3((unsigned)nb), dim3(64), 0, st, f->gstage, f->grad, nth);             \
@@ -1557,7 +1421,7 @@ int gpemu_fit_create(gpemu_fit **out, int device, int64_t N, int64_t d, const do
   gpemu_fit *f = new gpemu_fit();
   f->device = device; f->N = N; f->d = d; f->Np = round_up(N, NB);
   f->dp = dpad_of(d);
-  f->kind = fit_kind_of(kernel_kind, nu);
+  f->kind = base_kind(kernel_kind, nu);
   if (f->kind == 4) f->mnu = matern_nu_constants(nu);
   f->has_const = has_const ? 1 : 0; f->has_noise = has_noise ? 1 : 0;
   f->jitter = jitter;

@@ -475,19 +475,14 @@ static const void *front_kernel_ptr(bool small, bool kbig, bool nu) {
   if (small) return kbig ? (const void *)front_kernel<1, true> : (const void *)front_kernel<1, false>;
   return kbig ? (const void *)front_kernel<2, true> : (const void *)front_kernel<2, false>;
 }
-static int front_set_lds_limit() {
-  static bool attr_set = false;
-  if (!attr_set) {
-    for (int v = 0; v < 8; ++v)
-      GP_HIP(hipFuncSetAttribute(front_kernel_ptr(v & 1, v & 2, v & 4), hipFuncAttributeMaxDynamicSharedMemorySize, 136 * 1024));
-    attr_set = true;
-  }
-  return GPEMU_OK;
+// lets the instance that serves (small, the sampler's groups) use more than 64 KiB of dynamic LDS
+static int front_allow_lds(const gpemu_sampler *s, bool small) {
+  return allow_dynamic_lds(front_kernel_ptr(small, front_kbig(s), front_nu(s)), 136 * 1024);
 }
 // workgroups of front_kernel resident at once on the device (runtime occupancy x CUs); 0 if the runtime cannot say
 static int64_t front_capacity(const gpemu_sampler *s, bool small) {
   const size_t dyn = front_dyn_lds(s);
-  if (dyn > 40 * 1024 && front_set_lds_limit() != GPEMU_OK) return 0;
+  if (dyn > 40 * 1024 && front_allow_lds(s, small) != GPEMU_OK) return 0;
   int per_cu = 0;
   const bool kbig = front_kbig(s);
   hipError_t e;
@@ -693,7 +688,7 @@ static int launch_front(gpemu_sampler *s, const Pending &pv, bool have_next, int
   const int nstate = (int)((std::max<int64_t>(W, fa.reset_cnt) + 255) / 256);
   const dim3 grid((unsigned)(fa.nks + nstate)), block(256);
   const size_t dyn = front_dyn_lds(s);
-  if (dyn > 40 * 1024 && front_set_lds_limit() != GPEMU_OK) return GPEMU_ERR_HIP;
+  if (dyn > 40 * 1024 && front_allow_lds(s, small) != GPEMU_OK) return GPEMU_ERR_HIP;
   const int pe0 = prof_mark(m0, st);
   const bool kbig = front_kbig(s);
   if (front_nu(s)) {

@@ -393,25 +393,13 @@ int launch_halfstep_small(gpemu_model *const *ms, int ng, int64_t B, double *dXq
   const ProposeArgs pargs = pa ? *pa : ProposeArgs();
   const size_t shm = sizeof(double) * (size_t)nt32max * 32 * HS_LDK;
   const dim3 grid((unsigned)nprod), block(512);
-#define GP_LAUNCH_HS(KD)                                                                                                  \
-  do {                                                                                                                    \
-    static bool allowed[64] = {false};       /* per device: the kernel's LDS goes beyond the default 64 KiB */             \
-    if (!allowed[m0->device & 63]) {                                                                                      \
-      GP_HIP(hipFuncSetAttribute((const void *)halfstep_small_kernel<KD>, hipFuncAttributeMaxDynamicSharedMemorySize,     \
-                                 (int)(sizeof(double) * HS_NMAX * HS_LDK)));                                              \
-      allowed[m0->device & 63] = true;                                                                                    \
-    }                                                                                                                     \
-    hipLaunchKernelGGL(halfstep_small_kernel<KD>, grid, block, shm, st, ha, pargs);                                      \
-  } while (0)
-  switch (kstar_kind(m0)) {
-    case 0: GP_LAUNCH_HS(0); break;
-    case 1: GP_LAUNCH_HS(1); break;
-    case 2: GP_LAUNCH_HS(2); break;
-    case 3: GP_LAUNCH_HS(3); break;
-    case 4: GP_LAUNCH_HS(4); break;
-    default: return GPEMU_ERR_UNSUPPORTED;
-  }
-#undef GP_LAUNCH_HS
+  GP_TRY(with_base_kind(kstar_kind(m0), [&](auto kd) {
+    constexpr int KD = decltype(kd)::value;
+    // the kernel's LDS goes beyond the default 64 KiB
+    GP_TRY(allow_dynamic_lds((const void *)halfstep_small_kernel<KD>, (int)(sizeof(double) * HS_NMAX * HS_LDK)));
+    hipLaunchKernelGGL(halfstep_small_kernel<KD>, grid, block, shm, st, ha, pargs);
+    return GPEMU_OK;
+  }));
   GP_HIP(hipGetLastError());
   g_halfstep_launches.fetch_add(1, std::memory_order_relaxed);
   path_count(GPEMU_PATH_HALFSTEP_SMALL);

@@ -584,9 +584,8 @@ int launch_loglik_lowrank(gpemu_model *m, int64_t B, const double *dXq, double *
     GP_LAUNCH_LL(32);
   } else {
     size_t shm = sizeof(double) * 4 * (size_t)k * (k + 1);
-    if (shm > 64 * 1024)
-      GP_HIP(hipFuncSetAttribute((const void *)loglik_lowrank_lds_kernel,
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
+    if (shm > 64 * 1024)   // allowed once, up to what k <= 64 (gpemu_model_create) can ask for
+      GP_TRY(allow_dynamic_lds((const void *)loglik_lowrank_lds_kernel, (int)(sizeof(double) * 4 * 64 * 65)));
     hipLaunchKernelGGL(loglik_lowrank_lds_kernel, grid, block, shm, st, dXq, m->lo, m->hi, w.mean_part,
                        w.vsq_part, m->kdiag, m->G, m->g0, m->scal, dout, w.mean, w.var, B, w.Bcap,
                        (int)m->d, k, w.cur_nchunk, w.cur_nrb, (int)m->nblk, accumulate, a);

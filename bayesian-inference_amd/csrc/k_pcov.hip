@@ -20,12 +20,6 @@ namespace gpemu {
 
 constexpr int PC_NB = 64;   // padding unit of every operand (launch_gemm, the blocked Cholesky)
 
-#define GP_TRY_PCOV(expr)             \
-  do {                                \
-    const int rc__ = (expr);          \
-    if (rc__ != GPEMU_OK) return rc__; \
-  } while (0)
-
 // one block of kernel values per PC: out[z][r][c] = k(A[a0 + r], B[b0 + c]) + const for a0 + r < na, b0 + c < nb;
 // zero in the padding.  sym: element (i, i) is kernel_.diag exactly (r = 0: 1 + const + noise).
 struct KmatArgs {
@@ -40,22 +34,6 @@ struct KmatArgs {
   int dp = DPAD, d = 1, p0 = 0, sym = 0;
   MaternNu mn;
 };
-
-template <int KIND>
-__device__ __forceinline__ double pcov_base(double r2, const MaternNu &mn) {
-  if (KIND == 0) return exp(-0.5 * r2);
-  const double r = sqrt(r2);
-  if (KIND == 1) return exp(-r);
-  if (KIND == 2) {
-    const double t = r * 1.7320508075688772;
-    return (1.0 + t) * exp(-t);
-  }
-  if (KIND == 3) {
-    const double t = r * 2.23606797749979;
-    return (1.0 + t + t * t / 3.0) * exp(-t);
-  }
-  return matern_nu_value_call(mn, r);
-}
 
 // blockDim (64, 4): x = column (coalesced stores), 4 rows per thread (y, y + 4, ..); grid (cols / 64, rows / 16, PCs)
 template <int KIND, int DP>
@@ -88,7 +66,8 @@ __global__ __launch_bounds__(256) void pcov_kmat_kernel(KmatArgs g) {
             r2 = fma(df, df, r2);
           }
         }
-        v = pcov_base<KIND>(r2, g.mn) + cst;
+        const double r = sqrt(r2);   // before the call copies g.mn (the other order changes the instruction schedule)
+        v = (KIND == 4 ? matern_nu_value_call(g.mn, r) : base_from_r2(KIND, r2)) + cst;
       }
     }
     o[r * g.ldo + c] = v;
@@ -99,19 +78,12 @@ static int launch_kmat(const gpemu_model *m, KmatArgs g, int npc, hipStream_t st
   g.ls = m->ls; g.constv = m->constv; g.kdiag = m->kdiag; g.dp = m->dp; g.d = (int)m->d;
   if (kstar_kind(m) == 4) g.mn = matern_nu_constants(m->nu);
   dim3 grid((unsigned)(g.cols / 64), (unsigned)(g.rows / 16), (unsigned)npc), block(64, 4);
-#define GP_KMAT(K)                                                                                   \
-  do {                                                                                               \
-    if (m->dp == DPAD) hipLaunchKernelGGL((pcov_kmat_kernel<K, DPAD>), grid, block, 0, st, g);       \
-    else hipLaunchKernelGGL((pcov_kmat_kernel<K, DPAD_WIDE>), grid, block, 0, st, g);                \
-  } while (0)
-  switch (kstar_kind(m)) {
-    case 0: GP_KMAT(0); break;
-    case 1: GP_KMAT(1); break;
-    case 2: GP_KMAT(2); break;
-    case 3: GP_KMAT(3); break;
-    default: GP_KMAT(4); break;
-  }
-#undef GP_KMAT
+  GP_TRY(with_base_kind(kstar_kind(m), [&](auto kd) {
+    constexpr int K = decltype(kd)::value;
+    if (m->dp == DPAD) hipLaunchKernelGGL((pcov_kmat_kernel<K, DPAD>), grid, block, 0, st, g);
+    else hipLaunchKernelGGL((pcov_kmat_kernel<K, DPAD_WIDE>), grid, block, 0, st, g);
+    return GPEMU_OK;
+  }));
   GP_HIP(hipGetLastError());
   return GPEMU_OK;
 }
@@ -195,7 +167,7 @@ int predict_cov(gpemu_model *m, int64_t M1, const double *dX1, int64_t M2, const
   const int64_t M1p = round_up(M1, PC_NB), M2p = round_up(M2, PC_NB);
   int64_t budget = 0;
   bool automatic = false;
-  GP_TRY_PCOV(pcov_budget(workspace_bytes, budget, automatic));
+  GP_TRY(pcov_budget(workspace_bytes, budget, automatic));
   int pc = 0;
   int64_t mc = 0;
   if (!pcov_plan(k, N64, M1p, M2p, sym, budget, pc, mc)) {
@@ -229,8 +201,8 @@ int predict_cov(gpemu_model *m, int64_t M1, const double *dX1, int64_t M2, const
     KmatArgs g;
     g.A = m->Xtr; g.sa = m->dp; g.na = N; g.B = dX1; g.sb = d; g.nb = M1; g.p0 = p0;
     g.out = KT1; g.ldo = M1p; g.strideo = N64 * M1p; g.rows = N64; g.cols = M1p;
-    GP_TRY_PCOV(launch_kmat(m, g, np, st));
-    GP_TRY_PCOV(launch_v(m, p0, np, KT1, V1, N64, M1p, st));
+    GP_TRY(launch_kmat(m, g, np, st));
+    GP_TRY(launch_v(m, p0, np, KT1, V1, N64, M1p, st));
     for (int64_t c0 = 0; c0 < M2p; c0 += mc) {
       const int64_t nc = std::min(mc, M2p - c0);
       const int64_t r0 = sym ? c0 : 0;               // symmetric form: rows from the chunk's first column down
@@ -240,15 +212,15 @@ int predict_cov(gpemu_model *m, int64_t M1, const double *dX1, int64_t M2, const
       h.A = dX1; h.sa = d; h.na = M1; h.a0 = r0;
       h.B = sym ? dX1 : dX2; h.sb = d; h.nb = M2; h.b0 = c0;
       h.out = Cc; h.ldo = nc; h.strideo = M1p * nc; h.rows = nr; h.cols = nc; h.p0 = p0; h.sym = sym ? 1 : 0;
-      GP_TRY_PCOV(launch_kmat(m, h, np, st));
+      GP_TRY(launch_kmat(m, h, np, st));
       const double *B = V1 + c0;
       int64_t ldb = M1p, strideB = N64 * M1p;
       if (!sym) {
         KmatArgs t;
         t.A = m->Xtr; t.sa = m->dp; t.na = N; t.B = dX2; t.sb = d; t.nb = M2; t.b0 = c0; t.p0 = p0;
         t.out = KT2; t.ldo = nc; t.strideo = N64 * nc; t.rows = N64; t.cols = nc;
-        GP_TRY_PCOV(launch_kmat(m, t, np, st));
-        GP_TRY_PCOV(launch_v(m, p0, np, KT2, V2, N64, nc, st));
+        GP_TRY(launch_kmat(m, t, np, st));
+        GP_TRY(launch_v(m, p0, np, KT2, V2, N64, nc, st));
         B = V2; ldb = nc; strideB = N64 * nc;
       }
       // Cc = K12 - V1[:, r0 ..]^T V2
@@ -259,7 +231,7 @@ int predict_cov(gpemu_model *m, int64_t M1, const double *dX1, int64_t M2, const
       c.M = (int)nr; c.N = (int)nc; c.K = (int)Kc;
       c.alpha = -1.0; c.beta = 1.0;
       c.lower_only = sym ? 1 : 0;
-      GP_TRY_PCOV(launch_gemm(c, true, true, np, st));
+      GP_TRY(launch_gemm(c, true, true, np, st));
       StoreArgs s;
       s.Cc = Cc; s.ldc = nc; s.stridec = M1p * nc; s.rows = nr; s.cols = nc; s.r0 = r0; s.c0 = c0;
       s.M1 = M1; s.M2 = M2; s.out = dcov; s.p0 = p0; s.sym = sym ? 1 : 0;
@@ -348,7 +320,7 @@ int sample_from_cov(gpemu_model *m, int64_t M, int64_t n, const double *dcov, co
   }
   int64_t budget = 0;
   bool automatic = false;
-  GP_TRY_PCOV(pcov_budget(0, budget, automatic));
+  GP_TRY(pcov_budget(0, budget, automatic));
   const int64_t per = (Mp * Mp + Mp * PC_NB + 2 * Mp * np) * 8;
   if (budget < per) {
     set_error("bad argument: sample: the device is too full for the factor of one PC (%lld bytes needed, %lld available)",
@@ -360,14 +332,14 @@ int sample_from_cov(gpemu_model *m, int64_t M, int64_t n, const double *dcov, co
   DrawArgs a;
   double *A = nullptr, *Dinv = nullptr, *Z = nullptr, *Y = nullptr, *tau = nullptr;
   int *pc_of = nullptr, *ok = nullptr, *dinfo = nullptr;
-  GP_TRY_PCOV(fr.alloc(&A, (int64_t)slots * Mp * Mp));
-  GP_TRY_PCOV(fr.alloc(&Dinv, (int64_t)slots * Mp * PC_NB));
-  GP_TRY_PCOV(fr.alloc(&Z, (int64_t)slots * Mp * np));
-  GP_TRY_PCOV(fr.alloc(&Y, (int64_t)slots * Mp * np));
-  GP_TRY_PCOV(fr.alloc(&tau, slots));
-  GP_TRY_PCOV(fr.alloc(&pc_of, slots));
-  GP_TRY_PCOV(fr.alloc(&ok, slots));
-  GP_TRY_PCOV(fr.alloc(&dinfo, slots));
+  GP_TRY(fr.alloc(&A, (int64_t)slots * Mp * Mp));
+  GP_TRY(fr.alloc(&Dinv, (int64_t)slots * Mp * PC_NB));
+  GP_TRY(fr.alloc(&Z, (int64_t)slots * Mp * np));
+  GP_TRY(fr.alloc(&Y, (int64_t)slots * Mp * np));
+  GP_TRY(fr.alloc(&tau, slots));
+  GP_TRY(fr.alloc(&pc_of, slots));
+  GP_TRY(fr.alloc(&ok, slots));
+  GP_TRY(fr.alloc(&dinfo, slots));
   a.cov = dcov; a.z = dz; a.mean = dmean; a.pc_of = pc_of; a.tau = tau; a.ok = ok;
   a.A = A; a.Z = Z; a.Y = Y; a.out = dout; a.M = M; a.n = n; a.Mp = Mp; a.np = np; a.k = k;
   std::vector<int> todo;   // PCs without a factor yet
@@ -388,7 +360,7 @@ int sample_from_cov(gpemu_model *m, int64_t M, int64_t n, const double *dcov, co
     GP_HIP(hipMemsetAsync(dinfo, 0, sizeof(int) * (size_t)ns, st));
     hipLaunchKernelGGL(pcov_chol_setup_kernel, dim3((unsigned)Mp, (unsigned)ns), dim3(256), 0, st, a);
     GP_HIP(hipGetLastError());
-    GP_TRY_PCOV(device_cholesky_blocked(A, Mp, Dinv, dinfo, st, ns));
+    GP_TRY(device_cholesky_blocked(A, Mp, Dinv, dinfo, st, ns));
     GP_HIP(hipMemcpyAsync(hinfo.data(), dinfo, sizeof(int) * (size_t)ns, hipMemcpyDeviceToHost, st));
     GP_HIP(hipStreamSynchronize(st));
     std::vector<int> next;
@@ -414,7 +386,7 @@ int sample_from_cov(gpemu_model *m, int64_t M, int64_t n, const double *dcov, co
     g.C = Y; g.ldc = np; g.strideC = Mp * np;
     g.M = (int)Mp; g.N = (int)np; g.K = (int)Mp;
     g.k_to_m = 1;
-    GP_TRY_PCOV(launch_gemm(g, false, true, ns, st));
+    GP_TRY(launch_gemm(g, false, true, ns, st));
     hipLaunchKernelGGL(pcov_draw_store_kernel, dim3((unsigned)M, (unsigned)ns), dim3(256), 0, st, a);
     GP_HIP(hipGetLastError());
     GP_HIP(hipStreamSynchronize(st));   // hok / htau / the slots are reused by the next round

@@ -209,26 +209,18 @@ static KstarArgs kstar_setup(gpemu_model *m, int64_t B, double *dXq, int &nwg, b
                    m->N, m->Npad, w.Bcap, m->has_const, (int)m->d, (int)m->k, w.cur_nchunk, ncb64, gper, ncbp};
 }
 
-// instances: (ksteps, padded width) = (2, 8) d <= 7, (3, 8) d = 8; (3, 16) d = 9 .. 11, (4, 16) d = 12 .. 15, (5, 16) d = 16
-#define GP_KSTAR_KINDS(kind, KSV, DPV, small, LAUNCH)                                 \
-  switch (kind) {                                                                     \
-    case 0: if (small) LAUNCH(0, KSV, 1, DPV); else LAUNCH(0, KSV, 2, DPV); break;    \
-    case 1: if (small) LAUNCH(1, KSV, 1, DPV); else LAUNCH(1, KSV, 2, DPV); break;    \
-    case 2: if (small) LAUNCH(2, KSV, 1, DPV); else LAUNCH(2, KSV, 2, DPV); break;    \
-    case 3: if (small) LAUNCH(3, KSV, 1, DPV); else LAUNCH(3, KSV, 2, DPV); break;    \
-    case 4: if (small) LAUNCH(4, KSV, 1, DPV); else LAUNCH(4, KSV, 2, DPV); break;    \
-    default: set_error("cross-kernel: unknown base kernel %d", (int)(kind)); return GPEMU_ERR_STATE; \
-  }
-#define GP_KSTAR_DISPATCH(kind, ksteps, dp, small, LAUNCH)                            \
-  do {                                                                                \
-    if ((dp) == DPAD) {                                                               \
-      if ((ksteps) == 2) { GP_KSTAR_KINDS(kind, 2, DPAD, small, LAUNCH) }             \
-      else { GP_KSTAR_KINDS(kind, 3, DPAD, small, LAUNCH) }                           \
-    } else {                                                                          \
-      if ((ksteps) == 3) { GP_KSTAR_KINDS(kind, 3, DPAD_WIDE, small, LAUNCH) }        \
-      else if ((ksteps) == 4) { GP_KSTAR_KINDS(kind, 4, DPAD_WIDE, small, LAUNCH) }   \
-      else { GP_KSTAR_KINDS(kind, 5, DPAD_WIDE, small, LAUNCH) }                      \
-    }                                                                                 \
+// instances: (ksteps, padded width) = (2, 8) d <= 7, (3, 8) d = 8; (3, 16) d = 9 .. 11, (4, 16) d = 12 .. 15, (5, 16) d = 16;
+// JT = 1 for a small batch, else 2
+#define GP_KSTAR_DISPATCH(KD, ksteps, dp, small, LAUNCH)                                                  \
+  do {                                                                                                    \
+    if ((dp) == DPAD) {                                                                                   \
+      if ((ksteps) == 2) { if (small) LAUNCH(KD, 2, 1, DPAD); else LAUNCH(KD, 2, 2, DPAD); }              \
+      else { if (small) LAUNCH(KD, 3, 1, DPAD); else LAUNCH(KD, 3, 2, DPAD); }                            \
+    } else {                                                                                              \
+      if ((ksteps) == 3) { if (small) LAUNCH(KD, 3, 1, DPAD_WIDE); else LAUNCH(KD, 3, 2, DPAD_WIDE); }    \
+      else if ((ksteps) == 4) { if (small) LAUNCH(KD, 4, 1, DPAD_WIDE); else LAUNCH(KD, 4, 2, DPAD_WIDE); } \
+      else { if (small) LAUNCH(KD, 5, 1, DPAD_WIDE); else LAUNCH(KD, 5, 2, DPAD_WIDE); }                  \
+    }                                                                                                     \
   } while (0)
 
 int launch_kstar(gpemu_model *m, int64_t B, double *dXq, hipStream_t st, const ProposeArgs *pa) {
@@ -239,7 +231,10 @@ int launch_kstar(gpemu_model *m, int64_t B, double *dXq, hipStream_t st, const P
   const dim3 grid((unsigned)nwg), block(256);
   const int pe0 = prof_mark(m, st);
 #define GP_LAUNCH_ONE(KD, KSV, JT, DPV) hipLaunchKernelGGL((kstar_kernel<KD, KSV, JT, 2, DPV>), grid, block, 0, st, ka, pargs)
-  GP_KSTAR_DISPATCH(kstar_kind(m), m->ksteps, m->dp, small, GP_LAUNCH_ONE);
+  GP_TRY(with_base_kind(kstar_kind(m), [&](auto kd) {
+    GP_KSTAR_DISPATCH(decltype(kd)::value, m->ksteps, m->dp, small, GP_LAUNCH_ONE);
+    return GPEMU_OK;
+  }));
 #undef GP_LAUNCH_ONE
   GP_HIP(hipGetLastError());
   kstar_count(m, small);
@@ -262,7 +257,10 @@ int launch_kstar_groups(gpemu_model *const *ms, int ng, int64_t B, double *dXq, 
   }
   const dim3 grid((unsigned)kg.start[ng]), block(256);
 #define GP_LAUNCH_GROUPS(KD, KSV, JT, DPV) hipLaunchKernelGGL((kstar_groups_kernel<KD, KSV, JT, 2, DPV>), grid, block, 0, st, kg, pargs)
-  GP_KSTAR_DISPATCH(kstar_kind(ms[0]), ms[0]->ksteps, ms[0]->dp, small, GP_LAUNCH_GROUPS);
+  GP_TRY(with_base_kind(kstar_kind(ms[0]), [&](auto kd) {
+    GP_KSTAR_DISPATCH(decltype(kd)::value, ms[0]->ksteps, ms[0]->dp, small, GP_LAUNCH_GROUPS);
+    return GPEMU_OK;
+  }));
 #undef GP_LAUNCH_GROUPS
   GP_HIP(hipGetLastError());
   kstar_count(ms[0], small);

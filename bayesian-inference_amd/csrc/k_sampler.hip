@@ -54,16 +54,6 @@ __host__ __device__ static inline double u01_from(uint32_t hi, uint32_t lo) {
   return (double)(v >> 11) * (1.0 / 9007199254740992.0);  // [0,1), 53 bits
 }
 
-}  // namespace gpemu
-
-#define GP_TRY0(expr)           \
-  do {                          \
-    int rc0__ = (expr);         \
-    if (rc0__ != GPEMU_OK) return rc0__; \
-  } while (0)
-
-namespace gpemu {
-
 // ---- kernels ------------------------------------------------------------------------------------
 // One workgroup per (step, chain) (grid = steps generated ahead x chains): random balanced split (rank of W random
 // keys by counting), set member lists (ballot prefix sums), and the step's zz / rint / log u draws
@@ -282,7 +272,7 @@ static int launch_rng(gpemu_sampler *s, hipStream_t st, int64_t ahead = 1) {
   if (step < s->rng_ready_until) return GPEMU_OK;
   const int64_t to_edge = RNG_BATCH - (int64_t)(step % RNG_BATCH);
   const int64_t n = ahead < 1 ? 1 : (ahead > to_edge ? to_edge : ahead);
-  GP_TRY0(launch_rng_batch(s, st, step, n));
+  GP_TRY(launch_rng_batch(s, st, step, n));
   s->rng_ready_until = step + (uint64_t)n;
   return GPEMU_OK;
 }
@@ -370,12 +360,6 @@ static int end_step(gpemu_sampler *s, int store_chain, hipStream_t st, bool reco
 }  // namespace gpemu
 
 using namespace gpemu;
-#define GP_TRY(expr)            \
-  do {                          \
-    int rc__ = (expr);          \
-    if (rc__ != GPEMU_OK) return rc__; \
-  } while (0)
-
 extern "C" {
 
 int gpemu_philox4x32(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,

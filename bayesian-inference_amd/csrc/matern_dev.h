@@ -179,6 +179,20 @@ GPEMU_HD inline double matern_nu_value_grad(const MaternNu &c, double r, double 
 }
 
 #if defined(__HIPCC__)
+// the closed forms from the squared scaled distance r2: kind 0 RBF, 1 / 2 / 3 Matern 0.5 / 1.5 / 2.5 (internal.h:
+// base_kind; kind 4 is matern_nu_value above).  Each caller forms r2 in its own way (the bits differ between the forms).
+__device__ __forceinline__ double base_from_r2(int kind, double r2) {
+  if (kind == 0) return exp(-0.5 * r2);
+  double r = sqrt(r2);
+  if (kind == 1) return exp(-r);
+  if (kind == 2) {
+    double t = r * 1.7320508075688772;
+    return (1.0 + t) * exp(-t);
+  }
+  double t = r * 2.23606797749979;
+  return (1.0 + t + t * t / 3.0) * exp(-t);
+}
+
 // The cross-kernel's call (predict_dev.h: kstar_value4, four values per lane and tile): one out-of-line copy of the
 // Bessel loops instead of one inlined per accumulator register (kstar_kernel<4, 2, 2, 2>: ~20 000 instructions inlined,
 // beyond the instruction cache).  -DGPEMU_MATERN_NU_INLINE inlines it again (A/B: tools/time_matern_nu.py).

@@ -362,15 +362,15 @@ int gpemu_path_counts(int64_t *out, int64_t n);
  * of the model, likelihood and cross-validation setup that share its Cholesky and inverse).  A set of its own, so that
  * the predict / likelihood set above keeps its size and indices. */
 enum gpemu_fit_path {
-  GPEMU_FIT_PATH_KMAT = 0,           /* kernel matrix, kmat_kernel (RBF, Matern 0.5 / 1.5 / 2.5)                      */
-  GPEMU_FIT_PATH_KMAT_NU,            /* ... kmat_nu_kernel (Matern of general nu)                                     */
+  GPEMU_FIT_PATH_KMAT = 0,           /* kernel matrix, kmat_kernel<8, false> (RBF, Matern 0.5 / 1.5 / 2.5)            */
+  GPEMU_FIT_PATH_KMAT_NU,            /* ... kmat_kernel<8, true> (Matern of general nu)                               */
   GPEMU_FIT_PATH_CHOL_PANEL,         /* blocked Cholesky: one fused chol_panel_kernel launch per 256-wide panel       */
   GPEMU_FIT_PATH_CHOL_STEPS,         /* ... one panel of the three-launch steps (diagonal factor, solve, update)      */
   GPEMU_FIT_PATH_CHOL_LOOKAHEAD,     /* ... one look-ahead update of the columns beyond the next panel, side stream   */
   GPEMU_FIT_PATH_CHOL_HEADS_ONE_XCD, /* ... one fused panel launch with its four heads placed on one XCD              */
   GPEMU_FIT_PATH_TRTRI_RAGGED,       /* triangular inverse: one merge of a ragged pair (second block shorter)        */
-  GPEMU_FIT_PATH_GRAD,               /* LML gradient, lml_grad_kernel                                                 */
-  GPEMU_FIT_PATH_GRAD_NU,            /* ... lml_grad_nu_kernel                                                        */
+  GPEMU_FIT_PATH_GRAD,               /* LML gradient, lml_grad_kernel<8, false>                                       */
+  GPEMU_FIT_PATH_GRAD_NU,            /* ... lml_grad_kernel<8, true>                                                  */
   GPEMU_FIT_PATH_BATCH,              /* one fit evaluation of more than one problem at once                           */
   GPEMU_FIT_PATH_COUNT
 };
@@ -385,8 +385,8 @@ enum gpemu_wide_path {
   GPEMU_WIDE_PATH_KSTAR_KSTEPS3 = 0, /* cross-kernel, 16-wide rows, 3 MFMA k-steps (d = 9 .. 11)                      */
   GPEMU_WIDE_PATH_KSTAR_KSTEPS4,     /* ... 4 k-steps (d = 12 .. 15)                                                  */
   GPEMU_WIDE_PATH_KSTAR_KSTEPS5,     /* ... 5 k-steps (d = 16)                                                        */
-  GPEMU_WIDE_PATH_FIT_KMAT,          /* kernel matrix, kmat_kernel / kmat_nu_kernel of width 16                        */
-  GPEMU_WIDE_PATH_FIT_GRAD,          /* LML gradient, lml_grad_kernel / lml_grad_nu_kernel of width 16                 */
+  GPEMU_WIDE_PATH_FIT_KMAT,          /* kernel matrix, kmat_kernel<16, ..>                                            */
+  GPEMU_WIDE_PATH_FIT_GRAD,          /* LML gradient, lml_grad_kernel<16, ..>                                         */
   GPEMU_WIDE_PATH_COUNT
 };
 /* out[0 .. min(n, GPEMU_WIDE_PATH_COUNT)) = the counters; returns GPEMU_WIDE_PATH_COUNT (or GPEMU_ERR_ARG). */

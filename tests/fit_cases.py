@@ -5,13 +5,13 @@ fit_eval_batch).  Shared by the CPU tests of the extended-precision reference (t
 predict / likelihood set of tests/path_cases.py.
 
 Rules restated here:
-- the kernel matrix: kmat_nu_kernel for a Matern of general nu, kmat_kernel otherwise;
+- the kernel matrix: kmat_kernel<DP, true> for a Matern of general nu, kmat_kernel<DP, false> otherwise;
 - the Cholesky runs as one fused launch per panel of 4 blocks of 64 when nblk * nb <= 320 (and GPEMU_CHOL_PANEL is not
   0), else as three-launch steps; the stand-alone gpemu_cholesky always takes the steps;
 - a fused panel updates the columns beyond the next panel on the side stream when at least 40 tile rows lie beyond it;
 - the heads of a fused panel sit on one XCD (GPEMU_CHOL_HEADS_ONE_XCD=1) when the panel has at least 32 tile rows;
 - the triangular inverse merges a ragged pair at every level b where Np - 2 b floor(Np / 2b) > b;
-- the gradient: lml_grad_nu_kernel for a general nu, lml_grad_kernel otherwise.
+- the gradient: lml_grad_kernel<DP, true> for a general nu, lml_grad_kernel<DP, false> otherwise.
 """
 from __future__ import annotations
 
