@@ -213,6 +213,13 @@ def run_mcmc(config, closure_index=-1):
         logger.info(f'closure test {closure_index}: runs on rank {owner}')
         return
     alone = owner is not None          # this rank runs the whole chain by itself
+    if getattr(config, 'n_temperatures', 1) > 1:
+        # parallel tempering runs on one GPU: rank 0 (or the closure chain's owner) runs it, the other ranks return;
+        # a tempered closure chain runs by itself (not stacked with the other closure points)
+        if world > 1 and not alone and rank != 0:
+            logger.info('tempered run: runs on rank 0')
+            return
+        return _run_tempered(config, closure_index)
     if closure_index >= 0 and (alone or world == 1) and _closure_batch_enabled() \
             and 'validation_indices' in config.analysis_config:
         key = _closure_key(config)
@@ -289,6 +296,11 @@ def run_mcmc(config, closure_index=-1):
         validation_design = io.design_array_from_h5(config.output_dir, filename='observables.h5', validation_set=True)
         results['design_point'] = validation_design[closure_index]
         results['experimental_pseudodata'] = data
+    _write_outputs(config, results, sampler, io)
+
+
+def _write_outputs(config, results, sampler, io):
+    """mcmc.h5 and the pickled sampler of one run."""
     # the two big outputs -- mcmc.h5 (ref: mcmc.py:125) and the pickled sampler (ref: mcmc.py:131-132), ~0.5 GB each at
     # the shipped length -- are written side by side: the file writes release the interpreter lock
     logger.info(f'Writing {config.mcmc_outputfile}')
@@ -316,6 +328,97 @@ def run_mcmc(config, closure_index=-1):
     if failure:
         raise failure[0]
     logger.info('MCMC finished.')
+
+
+####################################################################################################
+# Parallel tempering: optional keys under parameters.mcmc -- n_temperatures (absent or 1: the path
+# above), t_max, swap_every, prior_rung.  Rung 0 samples the posterior and is what mcmc.h5 and the pickle hold, with the
+# same keys and shapes as an untempered run; the ladder adds the log-evidence (thermodynamic integration).
+def _run_tempered(config, closure_index):
+    from gpemu.sampler import TemperedSampler
+    from gpemu.tempering import geometric_ladder
+    box = config.analysis_config['parameterization'][config.parameterization]
+    lower, upper = box['min'], box['max']
+    n_par, n_walk, n_temp = len(box['names']), config.n_walkers, config.n_temperatures
+    emu_cfg = emulation.EmulationConfig.from_config_file(
+        analysis_name=config.analysis_name, parameterization=config.parameterization,
+        analysis_config=config.analysis_config, config_file=config.config_file)
+    emu_results = emu_cfg.read_all_emulator_groups()
+    truncation_cov = emulation.compute_emulator_cov_unexplained(emu_cfg, emu_results)
+    io = _data_IO()
+    data = io.data_array_from_h5(config.output_dir, 'observables.h5', pseudodata_index=closure_index,
+                                 observable_filter=emu_cfg.observable_filter)
+    log_posterior.initialize_pool_variables(lower, upper, emu_cfg, emu_results, data, truncation_cov)
+    betas = geometric_ladder(n_temp, config.t_max, prior_rung=config.prior_rung)
+    seed = int(np.random.randint(0, 2 ** 31 - 1))          # drawn where the untempered path's sampler draws its seed
+    sampler = TemperedSampler(log_posterior.log_posterior._gpemu_device_models(), n_walk, betas, seed=seed,
+                              swap_every=config.swap_every)
+    logger.info(f'Tempered sampler ready: {n_temp} temperatures x {n_walk} walkers, {n_par} parameters, '
+                f'betas {np.array2string(betas, precision=4)}, swaps every {config.swap_every} step(s)')
+    start = np.random.uniform(lower, upper, (n_temp * n_walk, n_par))       # ref: mcmc.py:88, for every rung
+
+    def advance(X0, steps):
+        if X0 is not None:
+            if not walkers_independent(np.asarray(X0).reshape(n_temp, n_walk, n_par)[0]):
+                raise ValueError("Initial state has a large condition number. Make sure that your walkers are "
+                                 "linearly independent for the best performance")
+            sampler.set_state(X0)
+            if np.any(np.isnan(sampler.get_state()[1])):
+                raise ValueError("The initial log_prob was NaN")
+        done = 0
+        while done < steps:
+            block = min(config.n_logging_steps - done % config.n_logging_steps, steps - done)
+            sampler.run(block)
+            done += block
+            if done % config.n_logging_steps == 0 or done == steps:
+                frac = sampler.acceptance_fraction[0]
+                logger.info(f'  step {done}: acceptance fraction (beta = 1): mean {frac.mean()}, std {frac.std()}, '
+                            f'min {frac.min()}, max {frac.max()}; swap acceptance '
+                            f'{np.array2string(sampler.tswap_acceptance_fraction, precision=3)}')
+
+    first_stage = config.n_burn_steps // 2
+    logger.info(f'Burn-in, stage 1 ({first_stage} steps)...')
+    advance(start, first_stage)
+    # only rung 0 restarts from its best distinct points (ref: mcmc.py:99); the hotter rungs continue
+    X = sampler.get_state()[0]
+    if first_stage > 0:
+        chain0, lp0 = sampler.get_chain(temp=0)
+        _, first_seen = np.unique(lp0.reshape(-1), return_index=True)
+        X[0] = chain0.reshape(-1, n_par)[first_seen[-n_walk:]]
+    sampler.reset()
+    logger.info(f'Burn-in, stage 2 ({config.n_burn_steps - first_stage} steps) from the best {n_walk} points...')
+    advance(X, config.n_burn_steps - first_stage)
+    sampler.reset()
+    logger.info(f'Production ({config.n_sampling_steps} steps)...')
+    advance(None, config.n_sampling_steps)
+
+    chain, lps = sampler.get_chain(temp=0)
+    nacc, iters, _ = sampler.counts()
+    try:
+        tau = sampler.integrated_time(temp=0)
+    except Exception as err:        # chain too short for a reliable estimate (emcee's AutocorrError upstream)
+        logger.info(f'No autocorrelation time: {err}')
+        tau = None
+    mean_ll = sampler.mean_log_likelihood()
+    log_z, dlog_z = sampler.log_evidence_estimate()
+    swap_frac = sampler.tswap_acceptance_fraction
+    sampler.close()
+    logger.info(f'log-evidence {log_z} +- {dlog_z}; swap acceptance {np.array2string(swap_frac, precision=3)}')
+
+    one = LoggingEnsembleSampler(n_walk, n_par, log_posterior.log_posterior, seed=seed, sharded=False)
+    one._cache = (chain, lps, nacc[:n_walk].copy(), iters)
+    one._frozen = True
+    one.betas, one.log_evidence, one.log_evidence_error = betas, float(log_z), float(dlog_z)
+    one.mean_log_likelihood, one.temperature_swap_acceptance_fraction = mean_ll, swap_frac
+    results = {'chain': one.get_chain(), 'acceptance_fraction': one.acceptance_fraction,
+               'log_prob': one.get_log_prob(), 'autocorrelation_time': tau,
+               'betas': betas, 'log_evidence': np.float64(log_z), 'log_evidence_error': np.float64(dlog_z),
+               'mean_log_likelihood': mean_ll, 'temperature_swap_acceptance_fraction': swap_frac}
+    if closure_index >= 0:
+        validation_design = io.design_array_from_h5(config.output_dir, filename='observables.h5', validation_set=True)
+        results['design_point'] = validation_design[closure_index]
+        results['experimental_pseudodata'] = data
+    _write_outputs(config, results, one, io)
 
 
 ####################################################################################################
@@ -389,6 +492,12 @@ class MCMCConfig:
             setattr(self, key, top[key])
         for key in _MCMC_KEYS:
             setattr(self, key, analysis_config['parameters']['mcmc'][key])
+        # parallel tempering (optional keys; absent or n_temperatures = 1: the untempered sampler)
+        mc = analysis_config['parameters']['mcmc']
+        self.n_temperatures = int(mc.get('n_temperatures', 1) or 1)
+        self.t_max = float(mc.get('t_max', 1e5))
+        self.swap_every = int(mc.get('swap_every', 1))
+        self.prior_rung = bool(mc.get('prior_rung', True))
 
         # <output_dir>/<analysis>_<parameterization>[/closure/results/<index>]/{mcmc.h5, mcmc_sampler.pkl}
         self.output_dir = os.path.join(top['output_dir'], f'{analysis_name}_{parameterization}')

@@ -214,7 +214,7 @@ int logpost_eval(gpemu_model *const *ms, int ng, int64_t B, double *dXq, double 
     }
   }
   AcceptArgs chain_only;                 // groups before the last: no accept, but the rows' chains (data constants)
-  if (aa) { chain_only.chain_per = aa->chain_per; chain_only.first = aa->first; }
+  if (aa) { chain_only.chain_per = aa->chain_per; chain_only.first = aa->first; chain_only.chain_data = aa->chain_data; }
   for (int g = 0; g < ng; ++g) {
     gpemu_model *const *one = ms + g;
     const ProposeArgs *pg = g == 0 ? pa : nullptr;

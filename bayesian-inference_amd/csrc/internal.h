@@ -187,7 +187,23 @@ struct AcceptArgs {
   int chain_per = 0;
   int64_t first = 0;
   int dp = DPAD;                  // padded width of X and of the query rows (the models' dp)
+  // parallel tempering (k_temper.hip): the rungs are chain_per-row chains that share data vector 0 (chain_data = 0)
+  // and scale the accept test by their inverse temperature beta[(first + b) / chain_per]; null: untempered
+  const double *beta = nullptr;
+  int chain_data = 1;             // with chain_per != 0: the row's chain selects the data constants (g0, q0)
 };
+
+// stretch-move accept of a proposal (log-probability nlp) for a walker at oldlp, at inverse temperature beta.
+// beta = 1 is the untempered test, bit for bit.  Otherwise the infinite cases are decided explicitly -- at beta = 0,
+// 0 * (nlp - oldlp) would be NaN for either -- as every beta > 0 decides them: a proposal of non-finite
+// log-probability is rejected, a walker at -inf (a start outside the open box) takes any finite proposal; else the
+// log-likelihood difference is scaled by beta.
+__host__ __device__ inline bool tempered_accept(double factor, double nlp, double oldlp, double logu, double beta) {
+  if (beta == 1.0) return (factor + nlp - oldlp) > logu;
+  if (!__builtin_isfinite(nlp)) return false;
+  if (oldlp == -INFINITY) return true;
+  return factor + beta * (nlp - oldlp) > logu;
+}
 
 // optional fused stretch-move proposal: kstar_kernel builds its query rows from the ensemble
 // (q_i = c[rint_i] - (c[rint_i] - s_i) zz_i, emcee moves/stretch.py) instead of reading them

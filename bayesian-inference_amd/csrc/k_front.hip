@@ -556,7 +556,7 @@ static int64_t front_grid(const gpemu_sampler *s, int64_t cnt) {
 
 bool front_eligible(const gpemu_sampler *s) {
   static const bool off = getenv("GPEMU_NO_FUSED") != nullptr;
-  if (off || s->groups.empty() || (int)s->groups.size() > FRONT_MAX_GROUPS || s->nchains != 1) return false;
+  if (off || s->groups.empty() || (int)s->groups.size() > FRONT_MAX_GROUPS || s->nchains != 1 || s->tempered) return false;
   for (const gpemu_model *m : s->groups)
     // ksteps 3: d = 8 parameters; and the wide padding (d > 8) has no instance here: those runs take the general path
     if (m->k > 64 || m->ksteps != 2 || m->dp != DPAD || m->device != s->groups[0]->device) return false;
@@ -823,6 +823,10 @@ extern "C" {
 
 int gpemu_sampler_peer_export(gpemu_sampler *s, char *handle_out64) {
   GP_ARG(s && handle_out64, "null pointer");
+  if (s->tempered) {
+    set_error("gpemu_sampler_peer_export: tempered samplers run on one GPU (gpemu_sampler_run)");
+    return GPEMU_ERR_UNSUPPORTED;
+  }
   GP_HIP(hipSetDevice(s->device));
   if (!front_eligible(s)) {     // the caller (every rank alike) then stays on the collective transports
     set_error("the fused run needs at most %d emulation groups of at most 64 PCs and 7 parameters, one chain", FRONT_MAX_GROUPS);
@@ -839,6 +843,10 @@ int gpemu_sampler_peer_export(gpemu_sampler *s, char *handle_out64) {
 
 int gpemu_sampler_peer_import(gpemu_sampler *s, int world, int rank, const char *handles) {
   GP_ARG(s && handles && world >= 1 && world <= 64 && rank >= 0 && rank < world, "world / rank / handles");
+  if (s->tempered) {
+    set_error("gpemu_sampler_peer_import: tempered samplers run on one GPU (gpemu_sampler_run)");
+    return GPEMU_ERR_UNSUPPORTED;
+  }
   GP_HIP(hipSetDevice(s->device));
   if (!front_eligible_for(s, world)) {
     set_error("the fused run cannot take this sampler at %d rank(s): at most %d groups of at most 64 PCs and 7 parameters, "
@@ -906,6 +914,10 @@ int gpemu_sampler_peer_selftest(gpemu_sampler *s) {
 
 int gpemu_sampler_run_peer(gpemu_sampler *s, int64_t steps, int store_chain) {
   GP_ARG(s && steps >= 0, "sampler / steps");
+  if (s->tempered) {
+    set_error("gpemu_sampler_run_peer: tempered samplers run on one GPU (gpemu_sampler_run)");
+    return GPEMU_ERR_UNSUPPORTED;
+  }
   GP_HIP(hipSetDevice(s->device));
   if (!front_eligible(s)) {
     set_error("the fused run needs at most %d emulation groups of at most 64 PCs, one chain", FRONT_MAX_GROUPS);

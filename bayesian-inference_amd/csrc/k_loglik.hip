@@ -190,7 +190,7 @@ __global__ __launch_bounds__(256) void loglik_lowrank_kernel(
   const int wave = threadIdx.x >> 6;
   const int64_t b = (int64_t)blockIdx.x * 4 + wave;
   if (b >= B) return;  // whole wave exits together; no workgroup barriers below
-  if (aa.chain_per) {  // several chains stacked: this row's chain selects the data constants
+  if (aa.chain_per && aa.chain_data) {  // several chains stacked: this row's chain selects the data constants
     const int64_t ch = (aa.first + b) / aa.chain_per;
     g0 += ch * nblk * k;
     scal += ch * 2 * nblk;
@@ -231,7 +231,7 @@ __global__ __launch_bounds__(256) void loglik_lowrank_lds_kernel(
   const int wave = threadIdx.x >> 6;
   const int64_t b = (int64_t)blockIdx.x * 4 + wave;
   if (b >= B) return;
-  if (aa.chain_per) {
+  if (aa.chain_per && aa.chain_data) {
     const int64_t ch = (aa.first + b) / aa.chain_per;
     g0 += ch * nblk * k;
     scal += ch * 2 * nblk;

@@ -24,23 +24,7 @@
 
 namespace gpemu {
 
-// ---- Philox4x32-10 (Salmon et al., SC'11) ----------------------------------------------------
-struct u32x4 { uint32_t x, y, z, w; };
-__host__ __device__ static inline u32x4 philox4x32_10(u32x4 c, uint32_t k0, uint32_t k1) {
-  const uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u, W0 = 0x9E3779B9u, W1 = 0xBB67AE85u;
-  for (int r = 0; r < 10; ++r) {
-    uint64_t p0 = (uint64_t)M0 * c.x, p1 = (uint64_t)M1 * c.z;
-    u32x4 n;
-    n.x = (uint32_t)(p1 >> 32) ^ c.y ^ k0;
-    n.y = (uint32_t)p1;
-    n.z = (uint32_t)(p0 >> 32) ^ c.w ^ k1;
-    n.w = (uint32_t)p0;
-    c = n;
-    k0 += W0;
-    k1 += W1;
-  }
-  return c;
-}
+// Philox4x32-10 and u01_from: sampler_internal.h (the swap pass of k_temper.hip draws from the same generator)
 // LDS bitonic sort of the split keys (rng_step_kernel): power-of-two size for W walkers, 0 if it would not fit
 constexpr int RNG_SORT_MAX = 2048;
 __host__ __device__ static inline int rng_sort_size(int W) {
@@ -49,11 +33,6 @@ __host__ __device__ static inline int rng_sort_size(int W) {
   while (P < W) P <<= 1;
   return P;
 }
-__host__ __device__ static inline double u01_from(uint32_t hi, uint32_t lo) {
-  uint64_t v = ((uint64_t)hi << 32) | lo;
-  return (double)(v >> 11) * (1.0 / 9007199254740992.0);  // [0,1), 53 bits
-}
-
 // ---- kernels ------------------------------------------------------------------------------------
 // One workgroup per (step, chain) (grid = steps generated ahead x chains): random balanced split (rank of W random
 // keys by counting), set member lists (ballot prefix sums), and the step's zz / rint / log u draws
@@ -186,7 +165,8 @@ __global__ void accept_kernel(double *__restrict__ X, double *__restrict__ logp,
                               const double *__restrict__ zz, const int *__restrict__ partner,
                               const double *__restrict__ newlp, const double *__restrict__ logu,
                               long long *__restrict__ naccept, int *__restrict__ flags, int ns, int d,
-                              double *__restrict__ chain, double *__restrict__ lpchain) {
+                              double *__restrict__ chain, double *__restrict__ lpchain,
+                              const double *__restrict__ beta, int per_chain) {
   int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= ns) return;
   const int w = idx_s[i], j = partner[i];
@@ -194,8 +174,13 @@ __global__ void accept_kernel(double *__restrict__ X, double *__restrict__ logp,
   const double nlp = newlp[i];
   if (nlp != nlp) atomicAdd(flags, 1);  // emcee raises on NaN log-probability
   const double oldlp = logp[w];
-  const double lnpdiff = (d - 1.0) * log(z) + nlp - oldlp;
-  const bool acc = lnpdiff > logu[i];
+  bool acc;
+  if (!beta) {
+    const double lnpdiff = (d - 1.0) * log(z) + nlp - oldlp;
+    acc = lnpdiff > logu[i];
+  } else {              // tempered: proposal i belongs to rung i / per_chain
+    acc = tempered_accept((d - 1.0) * log(z), nlp, oldlp, logu[i], beta[i / per_chain]);
+  }
 #pragma unroll
   for (int dd = 0; dd < DP; ++dd) {
     const double sw = X[w * DP + dd];
@@ -295,7 +280,7 @@ static int launch_accept(gpemu_sampler *s, int h, const double *dnewlp, int stor
   hipLaunchKernelGGL(s->dp == DPAD ? accept_kernel<DPAD> : accept_kernel<DPAD_WIDE>, dim3((ns + 255) / 256), dim3(256), 0,
                      st, s->X, s->logp, s->idx + o2 + h * s->W, s->zz + o2 + h * s->W,
                      s->rint + o2 + h * s->W, dnewlp, s->logu + o2 + h * s->W, s->naccept, s->flags, ns,
-                     (int)s->d, chain, lpchain);
+                     (int)s->d, chain, lpchain, s->tempered ? s->betas : nullptr, (int)(ns / s->nchains));
   GP_HIP(hipGetLastError());
   return GPEMU_OK;
 }
@@ -336,6 +321,7 @@ static int half_step_fused(gpemu_sampler *s, int h, int store_chain, hipStream_t
     aa.chain_per = s->nchains > 1 ? (int)per_chain : 0;
     aa.first = lo;
     aa.dp = s->dp;
+    if (s->tempered) { aa.beta = s->betas; aa.chain_data = 0; }
     if (store_chain) {
       aa.chain = s->chain + s->chain_len * s->W * s->d;
       aa.lpchain = s->lpchain + s->chain_len * s->W;
@@ -350,7 +336,8 @@ static int half_step_fused(gpemu_sampler *s, int h, int store_chain, hipStream_t
 
 // bookkeeping after both halves (the chain row was written by the fused / accept kernels)
 static int end_step(gpemu_sampler *s, int store_chain, hipStream_t st, bool recorded = true) {
-  (void)st; (void)recorded;
+  (void)recorded;
+  if (s->tempered) GP_TRY(temper_swap(s, store_chain, st));   // rewrites this step's chain row for the walkers it exchanges
   if (store_chain) s->chain_len += 1;
   s->iterations += 1;
   s->step_counter += 1;
@@ -453,8 +440,9 @@ int gpemu_sampler_destroy(gpemu_sampler *s) {
   (void)hipFree(s->zz); (void)hipFree(s->logu); (void)hipFree(s->rint); (void)hipFree(s->q);
   (void)hipFree(s->factors); (void)hipFree(s->newlp); (void)hipFree(s->naccept); (void)hipFree(s->flags);
   (void)hipFree(s->chain); (void)hipFree(s->lpchain);
-  (void)hipFree(s->snapX); (void)hipFree(s->snaplp); (void)hipFree(s->snapacc);
+  (void)hipFree(s->snapX); (void)hipFree(s->snaplp); (void)hipFree(s->snapacc); (void)hipFree(s->snapswap);
   (void)hipFree(s->acf_part); (void)hipFree(s->acf_acf); (void)hipFree(s->acf_mean); (void)hipFree(s->acf_acf0);
+  (void)hipFree(s->betas); (void)hipFree(s->nswap_acc); (void)hipFree(s->nswap_try); (void)hipFree(s->mean_ll);
   for (int h = 0; h < 2; ++h) { (void)hipFree(s->gmine[h]); (void)hipFree(s->gfull[h]); }
   delete s;
   return GPEMU_OK;
@@ -490,6 +478,7 @@ int gpemu_sampler_set_state(gpemu_sampler *s, const double *X0, const double *lo
         if (e != hipSuccess) { set_error("set_state: %s", hipGetErrorString(e)); rc = GPEMU_ERR_HIP; break; }
         AcceptArgs ca;                       // not an accept: only tells the likelihood which chain a row belongs to
         ca.chain_per = s->nchains > 1 ? (int)Wc : 0;
+        ca.chain_data = s->tempered ? 0 : 1;     // the rungs of a tempered sampler share data vector 0
         ca.first = off;
         ca.dp = s->dp;
         for (gpemu_model *m : s->groups) m->variant_B = (Wc + 1) / 2;
@@ -535,6 +524,11 @@ int gpemu_sampler_reset(gpemu_sampler *s) {
   GP_ARG(s, "sampler");
   GP_HIP(hipSetDevice(s->device));
   GP_HIP(hipMemsetAsync(s->naccept, 0, sizeof(long long) * s->W, s->stream));
+  if (s->tempered) {
+    const size_t npair = (size_t)(s->nchains - 1) * (size_t)(s->W / s->nchains);
+    GP_HIP(hipMemsetAsync(s->nswap_acc, 0, sizeof(long long) * npair, s->stream));
+    GP_HIP(hipMemsetAsync(s->nswap_try, 0, sizeof(long long) * npair, s->stream));
+  }
   GP_HIP(hipStreamSynchronize(s->stream));
   s->chain_len = 0;
   s->iterations = 0;
@@ -556,6 +550,13 @@ int gpemu_sampler_snapshot(gpemu_sampler *s) {
   GP_HIP(hipMemcpyAsync(s->snapX, s->X, sizeof(double) * W * s->dp, hipMemcpyDeviceToDevice, s->stream));
   GP_HIP(hipMemcpyAsync(s->snaplp, s->logp, sizeof(double) * W, hipMemcpyDeviceToDevice, s->stream));
   GP_HIP(hipMemcpyAsync(s->snapacc, s->naccept, sizeof(long long) * W, hipMemcpyDeviceToDevice, s->stream));
+  if (s->tempered) {          // the swap counters belong to the state as well
+    const size_t npair = (size_t)(s->nchains - 1) * (size_t)(W / s->nchains);
+    if (!s->snapswap) GP_HIP(hipMalloc((void **)&s->snapswap, sizeof(long long) * 2 * npair));
+    GP_HIP(hipMemcpyAsync(s->snapswap, s->nswap_acc, sizeof(long long) * npair, hipMemcpyDeviceToDevice, s->stream));
+    GP_HIP(hipMemcpyAsync(s->snapswap + npair, s->nswap_try, sizeof(long long) * npair, hipMemcpyDeviceToDevice,
+                          s->stream));
+  }
   s->snap_step_counter = s->step_counter;
   s->snap_iterations = s->iterations;
   s->snap_chain_len = s->chain_len;
@@ -572,6 +573,12 @@ int gpemu_sampler_restore(gpemu_sampler *s) {
   GP_HIP(hipMemcpyAsync(s->X, s->snapX, sizeof(double) * W * s->dp, hipMemcpyDeviceToDevice, s->stream));
   GP_HIP(hipMemcpyAsync(s->logp, s->snaplp, sizeof(double) * W, hipMemcpyDeviceToDevice, s->stream));
   GP_HIP(hipMemcpyAsync(s->naccept, s->snapacc, sizeof(long long) * W, hipMemcpyDeviceToDevice, s->stream));
+  if (s->tempered) {
+    const size_t npair = (size_t)(s->nchains - 1) * (size_t)(W / s->nchains);
+    GP_HIP(hipMemcpyAsync(s->nswap_acc, s->snapswap, sizeof(long long) * npair, hipMemcpyDeviceToDevice, s->stream));
+    GP_HIP(hipMemcpyAsync(s->nswap_try, s->snapswap + npair, sizeof(long long) * npair, hipMemcpyDeviceToDevice,
+                          s->stream));
+  }
   GP_HIP(hipMemsetAsync(s->flags, 0, sizeof(int) * 2, s->stream));
   GP_HIP(hipStreamSynchronize(s->stream));
   s->step_counter = s->snap_step_counter;
@@ -613,6 +620,10 @@ int gpemu_sampler_run(gpemu_sampler *s, int64_t steps, int store_chain) {
 int gpemu_sampler_step_host_rng(gpemu_sampler *s, const int32_t *inds, const double *zz,
                                 const int64_t *rint, const double *logu, int store_chain) {
   GP_ARG(s && inds && zz && rint && logu, "null pointer");
+  if (s->tempered) {
+    set_error("gpemu_sampler_step_host_rng: a tempered sampler draws its randomness on the device (gpemu_sampler_run)");
+    return GPEMU_ERR_UNSUPPORTED;
+  }
   GP_HIP(hipSetDevice(s->device));
   hipStream_t st = s->stream;
   const LaunchSwitches sw = read_launch_switches();
@@ -660,6 +671,24 @@ int gpemu_sampler_get_chain(gpemu_sampler *s, int64_t first, int64_t n, double *
   if (logp_out)
     GP_HIP(hipMemcpyAsync(logp_out, s->lpchain + first * s->W, sizeof(double) * n * s->W,
                           hipMemcpyDeviceToHost, s->stream));
+  GP_HIP(hipStreamSynchronize(s->stream));
+  return GPEMU_OK;
+}
+
+int gpemu_sampler_get_chain_walkers(gpemu_sampler *s, int64_t first, int64_t n, int64_t w0, int64_t nw,
+                                    double *chain_out, double *logp_out) {
+  GP_ARG(s && first >= 0 && n >= 0 && first + n <= s->chain_len, "chain range");
+  GP_ARG(w0 >= 0 && nw >= 1 && w0 + nw <= s->W, "walker range");
+  GP_HIP(hipSetDevice(s->device));
+  if (n == 0) return GPEMU_OK;
+  // rows of W walkers on the device, rows of nw on the host: one strided copy each
+  const size_t d = (size_t)s->d, W = (size_t)s->W;
+  if (chain_out)
+    GP_HIP(hipMemcpy2DAsync(chain_out, sizeof(double) * nw * d, s->chain + (first * W + w0) * d, sizeof(double) * W * d,
+                            sizeof(double) * nw * d, (size_t)n, hipMemcpyDeviceToHost, s->stream));
+  if (logp_out)
+    GP_HIP(hipMemcpy2DAsync(logp_out, sizeof(double) * nw, s->lpchain + first * W + w0, sizeof(double) * W,
+                            sizeof(double) * nw, (size_t)n, hipMemcpyDeviceToHost, s->stream));
   GP_HIP(hipStreamSynchronize(s->stream));
   return GPEMU_OK;
 }
@@ -850,6 +879,10 @@ __global__ void fill_kernel(double *p, int64_t n, double v) {
 int gpemu_sampler_run_sharded(gpemu_sampler *s, gpemu_comm *c, int64_t steps, int store_chain,
                               int emulate_world) {
   GP_ARG(s && steps >= 0 && emulate_world >= 0, "sampler / steps / emulate_world");
+  if (s->tempered) {
+    set_error("gpemu_sampler_run_sharded: tempered samplers run on one GPU (gpemu_sampler_run)");
+    return GPEMU_ERR_UNSUPPORTED;
+  }
   GP_HIP(hipSetDevice(s->device));
   const LaunchSwitches sw = read_launch_switches();
   // the timing aid needs no communicator where the fused two-launch half-step applies (bench.py's scaling_model leg)

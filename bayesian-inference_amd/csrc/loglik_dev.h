@@ -85,7 +85,8 @@ __device__ __forceinline__ void finish_walker(double total, double *__restrict__
   const int w = ao.w;
   const double oldlp = ao.oldlp;
   if (total != total && lane == 0) atomicAdd(aa.flags, 1);  // emcee raises on NaN
-  const bool acc = (ao.factor + total - oldlp) > ao.logu;
+  const bool acc = aa.beta ? tempered_accept(ao.factor, total, oldlp, ao.logu, aa.beta[(aa.first + b) / aa.chain_per])
+                           : (ao.factor + total - oldlp) > ao.logu;
   const double xold = ao.xold;
   if (lane < aa.dp && acc) aa.X[(int64_t)w * aa.dp + lane] = ao.xnew;
   if (lane == 0) {

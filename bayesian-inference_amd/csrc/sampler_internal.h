@@ -1,4 +1,5 @@
-// Sampler state shared by k_sampler.hip (stretch move, phase API, RCCL run) and k_front.hip (fused run).
+// Sampler state shared by k_sampler.hip (stretch move, phase API, RCCL run), k_front.hip (fused run) and k_temper.hip
+// (parallel tempering).
 #pragma once
 #include <vector>
 
@@ -11,6 +12,28 @@ constexpr int RNG_BATCH = 16;       // steps generated per launch (half the ring
 constexpr int GATHER_SLOTS = 3;
 // a log-probability that has not arrived yet: a quiet NaN with a payload no computation produces
 constexpr unsigned long long GATHER_EMPTY = 0x7FF8DEADBEEF0001ull;
+
+// ---- Philox4x32-10 (Salmon et al., SC'11) ----------------------------------------------------
+struct u32x4 { uint32_t x, y, z, w; };
+__host__ __device__ static inline u32x4 philox4x32_10(u32x4 c, uint32_t k0, uint32_t k1) {
+  const uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u, W0 = 0x9E3779B9u, W1 = 0xBB67AE85u;
+  for (int r = 0; r < 10; ++r) {
+    uint64_t p0 = (uint64_t)M0 * c.x, p1 = (uint64_t)M1 * c.z;
+    u32x4 n;
+    n.x = (uint32_t)(p1 >> 32) ^ c.y ^ k0;
+    n.y = (uint32_t)p1;
+    n.z = (uint32_t)(p0 >> 32) ^ c.w ^ k1;
+    n.w = (uint32_t)p0;
+    c = n;
+    k0 += W0;
+    k1 += W1;
+  }
+  return c;
+}
+__host__ __device__ static inline double u01_from(uint32_t hi, uint32_t lo) {
+  uint64_t v = ((uint64_t)hi << 32) | lo;
+  return (double)(v >> 11) * (1.0 / 9007199254740992.0);  // [0,1), 53 bits
+}
 }  // namespace gpemu
 
 struct gpemu_sampler {
@@ -70,6 +93,7 @@ struct gpemu_sampler {
   // exchange -- is rerun from here over another transport and gives the chain of an unbroken run
   double *snapX = nullptr, *snaplp = nullptr;        // [W][dp], [W]
   long long *snapacc = nullptr;                      // [W]
+  long long *snapswap = nullptr;                     // tempered: [2][nchains - 1][W / nchains] swap counters
   bool snap_valid = false;
   uint64_t snap_step_counter = 0;
   int64_t snap_iterations = 0, snap_chain_len = 0;
@@ -77,6 +101,15 @@ struct gpemu_sampler {
   double *acf_part = nullptr, *acf_acf = nullptr, *acf_mean = nullptr, *acf_acf0 = nullptr;
   size_t acf_part_bytes = 0, acf_acf_bytes = 0, acf_mean_bytes = 0;   // capacity of acf_part / acf_acf / acf_mean + acf_acf0
   int64_t acf_first = -1, acf_n = -1, acf_w0 = -1, acf_nw = -1;       // the estimate the scratch belongs to
+  // parallel tempering (gpemu_sampler_create_tempered, k_temper.hip): the nchains stacked chains are the rungs of a
+  // temperature ladder on ONE data vector; rung t accepts with beta[t] and swaps states with rung t - 1 every
+  // swap_every steps
+  bool tempered = false;
+  int swap_every = 0;                // 0: no swaps
+  double *betas = nullptr;           // [nchains] inverse temperatures, betas[0] = 1 >= betas[1] >= ... >= 0
+  long long *nswap_acc = nullptr;    // [nchains - 1][W / nchains] accepted swaps of rung pair (t, t + 1), column w
+  long long *nswap_try = nullptr;    // [nchains - 1][W / nchains] attempted swaps
+  double *mean_ll = nullptr;         // [nchains] scratch of gpemu_sampler_mean_loglik
 };
 
 namespace gpemu {
@@ -84,6 +117,9 @@ namespace gpemu {
 int sampler_launch_rng(gpemu_sampler *s, hipStream_t st, int64_t ahead);
 int sampler_ensure_chain(gpemu_sampler *s, int64_t need);
 int sampler_check_nan(gpemu_sampler *s);
+// k_temper.hip
+int temper_swap(gpemu_sampler *s, int store_chain, hipStream_t st);   // the swap pass of step s->step_counter, if due
+int temper_validate_ladder(const double *betas, int n_temps);
 // k_front.hip
 void front_release(gpemu_sampler *s);                         // frees the gather buffer and the peer mappings
 bool front_eligible(const gpemu_sampler *s);

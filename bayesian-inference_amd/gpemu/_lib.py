@@ -78,6 +78,11 @@ _SIGNATURES = {
                                        C.c_double, C.c_uint64]),
     "gpemu_sampler_create_chains": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int, c_i64,
                                               C.c_double, C.c_void_p, C.c_int]),
+    "gpemu_sampler_create_tempered": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int, c_i64,
+                                                C.c_double, C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
+    "gpemu_sampler_set_betas": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "gpemu_sampler_get_swap_counts": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gpemu_sampler_mean_loglik": (C.c_int, [C.c_void_p, c_i64, c_i64, C.c_void_p]),
     "gpemu_sampler_destroy": (C.c_int, [C.c_void_p]),
     "gpemu_sampler_set_stream": (C.c_int, [C.c_void_p, C.c_void_p]),
     "gpemu_sampler_set_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -87,6 +92,7 @@ _SIGNATURES = {
     "gpemu_sampler_step_host_rng": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                               C.c_void_p, C.c_int]),
     "gpemu_sampler_get_chain": (C.c_int, [C.c_void_p, c_i64, c_i64, C.c_void_p, C.c_void_p]),
+    "gpemu_sampler_get_chain_walkers": (C.c_int, [C.c_void_p, c_i64, c_i64, c_i64, c_i64, C.c_void_p, C.c_void_p]),
     "gpemu_sampler_get_counts": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(c_i64), C.POINTER(c_i64)]),
     "gpemu_sampler_acf": (C.c_int, [C.c_void_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, C.c_void_p]),
     "gpemu_sampler_reserve_chain": (C.c_int, [C.c_void_p, c_i64]),

@@ -126,23 +126,26 @@ class DeviceSampler:
         _lib.require_device()
         self.models = list(models)
         arr = (C.c_void_p * len(self.models))(*[m.handle for m in self.models])
-        h = C.c_void_p()
-        if seeds is None:
-            check(_lib.lib().gpemu_sampler_create(C.byref(h), arr, len(self.models), int(n_walkers), float(a),
-                                                  C.c_uint64(int(seed) & (2 ** 64 - 1))))
-            self.n_chains = 1
-        else:
-            sd = np.array([int(v) & (2 ** 64 - 1) for v in seeds], dtype=np.uint64)
-            check(_lib.lib().gpemu_sampler_create_chains(C.byref(h), arr, len(self.models), int(n_walkers), float(a),
-                                                         ptr(sd), int(sd.size)))
-            self.n_chains = int(sd.size)
-        self._h = h
+        self._h, self.n_chains = self._create(arr, int(n_walkers), float(a), seed, seeds)
         self.walkers_per_chain = int(n_walkers)
         self.W, self.d = int(n_walkers) * self.n_chains, self.models[0].d
-        self.ns = ((self.W + 1) // 2, self.W // 2)
+        # proposals of each half, chain after chain (the library's set sizes: ceil / floor of n_walkers / 2 per chain)
+        self.ns = ((int(n_walkers) + 1) // 2 * self.n_chains, int(n_walkers) // 2 * self.n_chains)
         self.device = self.models[0].device
         self.last_transport = None       # what the last run_sharded call really took: "peer" / "rccl" / "torch" / "single" / "replicated"
         self.transport_info = {}         # self-test results, communicator sizes, fall-back reasons
+
+    def _create(self, arr, n_walkers, a, seed, seeds):
+        """The library handle and the number of stacked chains."""
+        h = C.c_void_p()
+        if seeds is None:
+            check(_lib.lib().gpemu_sampler_create(C.byref(h), arr, len(self.models), n_walkers, a,
+                                                  C.c_uint64(int(seed) & (2 ** 64 - 1))))
+            return h, 1
+        sd = np.array([int(v) & (2 ** 64 - 1) for v in seeds], dtype=np.uint64)
+        check(_lib.lib().gpemu_sampler_create_chains(C.byref(h), arr, len(self.models), n_walkers, a,
+                                                     ptr(sd), int(sd.size)))
+        return h, int(sd.size)
 
     def close(self):
         for h in self.__dict__.pop("_comms", {}).values():
@@ -557,6 +560,118 @@ class DeviceSampler:
         finally:
             stream.synchronize()
             L.gpemu_sampler_set_stream(self._h, None)
+
+
+# ------------------------------------------------------------------------------------------------
+# Philox keys of the rungs of a TemperedSampler without explicit seeds: rung t uses seed + t * RUNG_KEY_STRIDE (mod 2^64),
+# so rung 0 draws what DeviceSampler(models, n_walkers, seed=seed) draws
+RUNG_KEY_STRIDE = 0x9E3779B97F4A7C15
+
+
+class TemperedSampler(DeviceSampler):
+    """Parallel-tempered stretch-move ensemble on one GPU (emcee 2's ``PTSampler`` with a stretch move
+    per rung): ``len(betas)`` rungs of ``n_walkers`` walkers, stacked in one sampler on the models' single data vector.
+    Rung t accepts with its log-likelihood difference scaled by ``betas[t]`` and, every ``swap_every`` steps (0: never),
+    exchanges states with rung t - 1 column by column.  ``betas[0]`` must be 1 (rung 0 samples the posterior).
+    Without ``seeds``, rung t's Philox key is ``seed + t * RUNG_KEY_STRIDE`` (mod 2^64).  State and chain arrays are
+    shaped ``(T, n_walkers, ...)``; the stored log-probabilities are the untempered log-likelihoods."""
+
+    def __init__(self, models, n_walkers, betas, a=2.0, seed=0, seeds=None, swap_every=1):
+        betas = np.ascontiguousarray(betas, dtype=np.float64).reshape(-1)
+        if seeds is None:
+            seeds = [(int(seed) + t * RUNG_KEY_STRIDE) & (2 ** 64 - 1) for t in range(betas.size)]
+        if len(seeds) != betas.size:
+            raise ValueError(f"{len(seeds)} seeds for {betas.size} temperatures")
+        self._betas_init, self.swap_every = betas, int(swap_every)
+        super().__init__(models, n_walkers, a=a, seeds=seeds)
+        self.n_temps, self.betas = self.n_chains, betas.copy()
+
+    def _create(self, arr, n_walkers, a, seed, seeds):
+        h = C.c_void_p()
+        sd = np.array([int(v) & (2 ** 64 - 1) for v in seeds], dtype=np.uint64)
+        b = self._betas_init
+        check(_lib.lib().gpemu_sampler_create_tempered(C.byref(h), arr, len(self.models), n_walkers, a, ptr(sd), ptr(b),
+                                                       int(b.size), self.swap_every))
+        return h, int(b.size)
+
+    def set_betas(self, betas):
+        """A new ladder (same length; e.g. after a burn-in)."""
+        b = as_f64(np.asarray(betas, dtype=np.float64).reshape(-1), (self.n_temps,))
+        check(_lib.lib().gpemu_sampler_set_betas(self._h, ptr(b)))
+        self.betas = b.copy()
+
+    def set_state(self, X0, logp0=None):
+        """``X0`` of shape ``(T * n_walkers, d)`` or ``(T, n_walkers, d)``."""
+        X0 = np.asarray(X0, dtype=np.float64).reshape(self.W, self.d)
+        super().set_state(X0, None if logp0 is None else np.asarray(logp0, dtype=np.float64).reshape(self.W))
+
+    def get_state(self):
+        """``(X (T, n_walkers, d), ll (T, n_walkers))``."""
+        X, lp = super().get_state()
+        return X.reshape(self.n_temps, -1, self.d), lp.reshape(self.n_temps, -1)
+
+    def get_chain(self, temp=None, discard=0):
+        """``(chain (steps, T, n_walkers, d), ll (steps, T, n_walkers))`` of the stored steps from ``discard`` on, or
+        those of rung ``temp`` alone (``(steps, n_walkers, d)``, ``(steps, n_walkers)``)."""
+        if temp is None:
+            chain, lp = DeviceSampler.get_chain(self, first=int(discard))
+            n, Wc = chain.shape[0], self.walkers_per_chain
+            return chain.reshape(n, self.n_temps, Wc, self.d), lp.reshape(n, self.n_temps, Wc)
+        t = int(temp)
+        if not 0 <= t < self.n_temps:
+            raise IndexError(f"temperature index {temp} outside [0, {self.n_temps})")
+        # only this rung's walkers leave the device (a strided copy), not the whole ladder
+        _, _, cl = self.counts()
+        n, Wc = cl - int(discard), self.walkers_per_chain
+        chain, lp = np.empty((n, Wc, self.d)), np.empty((n, Wc))
+        check(_lib.lib().gpemu_sampler_get_chain_walkers(self._h, int(discard), int(n), t * Wc, Wc, ptr(chain), ptr(lp)))
+        return chain, lp
+
+    def run_sharded(self, steps, store=True, group=None, force=False, emulate_world=None, transport=None):
+        """Tempered runs are single-GPU (``run``); the library declines its sharded and peer runs, and the per-phase
+        transport is declined here."""
+        raise _lib.GpemuError(-5, "tempered samplers run on one GPU (TemperedSampler.run); sharded runs are not supported")
+
+    @property
+    def acceptance_fraction(self):
+        """Stretch-move acceptance per rung and walker, ``(T, n_walkers)``."""
+        nacc, it, _ = self.counts()
+        return (nacc / float(max(it, 1))).reshape(self.n_temps, -1)
+
+    def swap_counts(self):
+        """(accepted, attempted) swaps since the last reset, ``(T - 1, n_walkers)`` each: row t is the pair (t, t+1)."""
+        shape = (self.n_temps - 1, self.walkers_per_chain)
+        acc, tried = np.zeros(shape, dtype=np.int64), np.zeros(shape, dtype=np.int64)
+        check(_lib.lib().gpemu_sampler_get_swap_counts(self._h, ptr(acc), ptr(tried)))
+        return acc, tried
+
+    @property
+    def tswap_acceptance_fraction(self):
+        """Swap acceptance of each neighbouring rung pair, ``(T - 1,)`` (0 before any attempt)."""
+        acc, tried = self.swap_counts()
+        return acc.sum(axis=1) / np.maximum(tried.sum(axis=1), 1).astype(np.float64)
+
+    def mean_log_likelihood(self, discard=0):
+        """Mean stored log-likelihood of every rung over the steps from ``discard`` on, ``(T,)`` (on the device)."""
+        _, _, cl = self.counts()
+        n = cl - int(discard)
+        if n < 1:
+            raise ValueError(f"no stored steps after discarding {discard} of {cl}")
+        out = np.empty(self.n_temps)
+        check(_lib.lib().gpemu_sampler_mean_loglik(self._h, int(discard), int(n), ptr(out)))
+        return out
+
+    def log_evidence_estimate(self, discard=0):
+        """``(logZ, dlogZ)`` by thermodynamic integration over the ladder (gpemu.tempering); Z is the evidence under
+        the normalised uniform prior on the box."""
+        from .tempering import thermodynamic_integration_log_evidence
+        return thermodynamic_integration_log_evidence(self.betas, self.mean_log_likelihood(discard))
+
+    def integrated_time(self, temp=0, first=0, n=None, c=5, tol=50, quiet=False, block=256):
+        """emcee's integrated autocorrelation time of rung ``temp``, estimated on the device."""
+        Wc = self.walkers_per_chain
+        return DeviceSampler.integrated_time(self, first=first, n=n, w0=int(temp) * Wc, nw=Wc, c=c, tol=tol,
+                                             quiet=quiet, block=block)
 
 
 # ------------------------------------------------------------------------------------------------

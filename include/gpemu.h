@@ -227,12 +227,31 @@ int gpemu_sampler_create(gpemu_sampler **out, gpemu_model *const *groups, int n_
  * vector c.  State, chain and counters are laid out chain after chain: walker c W + w. */
 int gpemu_sampler_create_chains(gpemu_sampler **out, gpemu_model *const *groups, int n_groups, int64_t W,
                                 double a, const uint64_t *seeds, int n_chains);
+/* Parallel tempering: n_temps rungs of Wc walkers each, stacked as the chains above (rung t owns
+ * walkers t Wc .. t Wc + Wc - 1 and draws its stretch moves from seeds[t]), all on the groups' ONE data vector
+ * (GPEMU_ERR_STATE for a group set up with several).  Rung t accepts a proposal iff
+ *     betas[t] == 1:  factor + ll' - ll > log u           (the untempered test, bit for bit)
+ *     otherwise:      ll' finite and factor + betas[t] (ll' - ll) > log u,
+ * and after step s, when swap_every > 0 and (s + 1) % swap_every == 0, walker column w of rungs t and t - 1
+ * (t = n_temps-1 .. 1) exchange states iff both ll are finite and
+ *     log u < (betas[t-1] - betas[t]) (ll[t][w] - ll[t-1][w]),  u from Philox(c = (w, 5, s_lo, s_hi), key = seeds[t]).
+ * The stored chain row of a step is the state after the swaps; the stored log-probabilities are the untempered ll.
+ * Ladder: 2 <= n_temps <= 64, betas[0] = 1 >= betas[1] >= ... >= betas[n_temps-1] >= 0 (else GPEMU_ERR_ARG).
+ * gpemu_sampler_run_sharded, the peer transport and gpemu_sampler_step_host_rng return GPEMU_ERR_UNSUPPORTED. */
+int gpemu_sampler_create_tempered(gpemu_sampler **out, gpemu_model *const *groups, int n_groups, int64_t Wc, double a,
+                                  const uint64_t *seeds, const double *betas, int n_temps, int swap_every);
+int gpemu_sampler_set_betas(gpemu_sampler *s, const double *betas /*[n_temps], validated as above*/);
+/* swap counters since the last reset, per rung pair (t, t + 1) and column: accepted / attempted [(n_temps-1)*Wc] */
+int gpemu_sampler_get_swap_counts(gpemu_sampler *s, int64_t *accepted, int64_t *attempted);
+/* out[t] = mean of the stored log-likelihoods of rung t over chain rows [first, first + n) and its Wc walkers
+ * (a fixed-order device reduction: the same bits on every call) -- the thermodynamic-integration input */
+int gpemu_sampler_mean_loglik(gpemu_sampler *s, int64_t first, int64_t n, double *out /*[n_temps]*/);
 int gpemu_sampler_destroy(gpemu_sampler *s);
 int gpemu_sampler_set_stream(gpemu_sampler *s, void *stream); /* NULL = the first group's stream */
 /* X0[W*d]; logp0[W] or NULL to evaluate it (ref: mcmc.py:88, emcee State(initial_state)) */
 int gpemu_sampler_set_state(gpemu_sampler *s, const double *X0, const double *logp0);
 int gpemu_sampler_get_state(gpemu_sampler *s, double *X, double *logp);
-int gpemu_sampler_reset(gpemu_sampler *s); /* emcee sampler.reset(): drop chain + acceptance counts */
+int gpemu_sampler_reset(gpemu_sampler *s); /* emcee sampler.reset(): drop chain + acceptance (and swap) counts */
 /* `steps` full stretch-move steps with device-side Philox randomness; returns 1 if any proposal's
  * log-probability was NaN (emcee raises ValueError). */
 int gpemu_sampler_run(gpemu_sampler *s, int64_t steps, int store_chain);
@@ -244,6 +263,10 @@ int gpemu_sampler_step_host_rng(gpemu_sampler *s, const int32_t *inds, const dou
 /* chain_out[n*W*d] (emcee get_chain()[first:first+n]), logp_out[n*W] (get_log_prob()) */
 int gpemu_sampler_get_chain(gpemu_sampler *s, int64_t first, int64_t n, double *chain_out,
                             double *logp_out);
+/* the same for walkers [w0, w0 + nw) only (a chain of a stacked sampler, a rung of a tempered one):
+ * chain_out[n*nw*d], logp_out[n*nw] */
+int gpemu_sampler_get_chain_walkers(gpemu_sampler *s, int64_t first, int64_t n, int64_t w0, int64_t nw,
+                                    double *chain_out, double *logp_out);
 int gpemu_sampler_get_counts(gpemu_sampler *s, int64_t *naccepted /*[W]*/, int64_t *iterations,
                              int64_t *chain_len);
 /* Walker-averaged normalised autocorrelation function of the stored chain rows [first, first + n_steps), walkers
