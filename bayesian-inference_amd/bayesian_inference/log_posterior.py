@@ -10,6 +10,11 @@ does upstream; emcee calls it with one walker at a time.  The ensemble sampler's
 
 A covariance that is not positive definite yields NaN (the reference's dpotrf error branch is dead
 code, ref: log_posterior.py:125-135, and it would also compute with an invalid factor).
+
+Correlated experimental uncertainties (the reference's TODO at log_posterior.py:90-94 resolved):
+``experimental_results['cov']`` (F, F), in the merged observable order, replaces ``diag(y_err**2)`` inside each
+observable and must be zero across observables; ``experimental_results['sys_sources']`` (S, F), S <= 16, adds
+``sum_s b_s b_s^T``, spanning any observables and groups.  Without either key nothing changes.
 """
 from __future__ import annotations
 
@@ -28,7 +33,7 @@ emulation_results = None
 experimental_results = None
 emulator_cov_unexplained = None
 
-_state = {"models": None, "n_div": None}
+_state = {"models": None, "n_div": None, "data_cov": None}
 
 
 def initialize_pool_variables(local_min, local_max, local_emulation_config, local_emulation_results,
@@ -43,6 +48,7 @@ def initialize_pool_variables(local_min, local_max, local_emulation_config, loca
     emulator_cov_unexplained = local_emulator_cov_unexplained
     _state["models"] = None
     _state["n_div"] = None
+    _state["data_cov"] = None
     # the previous run's device models (k N^2 doubles each) are not needed any more
     emulation.release_device_models()
 
@@ -65,6 +71,71 @@ def _group_layouts():
     return out
 
 
+def _observable_of_columns(F):
+    """(observable index of every merged column, observable names): one observable without a sorter."""
+    sorter = getattr(emulation_config, "sort_observables_in_matrix", None)
+    mapping = getattr(sorter, "emulation_group_to_observable_matrix", None)
+    if not mapping:
+        return np.zeros(F, dtype=np.int64), ["all observables"]
+    obs = np.full(F, -1, dtype=np.int64)
+    names = []
+    for i, (name, (_, slice_out, _)) in enumerate(sorted(mapping.items(), key=lambda e: e[1][1].start)):
+        obs[slice_out] = i
+        names.append(str(name))
+    return obs, names
+
+
+def data_covariance():
+    """(cov or None, sys_sources or None) of ``experimental_results``, in the merged observable order, checked
+    (once per ``initialize_pool_variables``)."""
+    if _state["data_cov"] is None:
+        _state["data_cov"] = _read_data_covariance()
+    return _state["data_cov"]
+
+
+def _read_data_covariance():
+    er = experimental_results
+    get = er.get if hasattr(er, "get") else (lambda key: er[key] if key in er else None)
+    cov, src = get('cov'), get('sys_sources')
+    F = np.asarray(er['y']).shape[0]
+    if cov is not None:
+        cov = np.ascontiguousarray(cov, dtype=np.float64)
+        if cov.shape != (F, F):
+            raise ValueError(f"experimental_results['cov'] must have shape ({F}, {F}), got {cov.shape}")
+        if not np.all(np.isfinite(cov)) or not np.array_equal(cov, cov.T):
+            raise ValueError("experimental_results['cov'] must be finite and symmetric")
+        obs, names = _observable_of_columns(F)
+        cross = (obs[:, None] != obs[None, :]) & (cov != 0.0)
+        if np.any(cross):
+            i, j = (int(v) for v in np.argwhere(cross)[0])
+            raise ValueError(
+                f"experimental_results['cov'][{i}, {j}] = {cov[i, j]:g} couples observables {names[obs[i]]!r} and "
+                f"{names[obs[j]]!r}: only the covariance inside an observable may be dense; give correlations across "
+                "observables as fully correlated sources, experimental_results['sys_sources'] (S, F)")
+    if src is not None:
+        src = np.ascontiguousarray(src, dtype=np.float64)
+        if src.ndim != 2 or src.shape[1] != F:
+            raise ValueError(f"experimental_results['sys_sources'] must have shape (S, {F}), got {src.shape}")
+        if src.shape[0] > 16:
+            raise ValueError(f"experimental_results['sys_sources'] holds {src.shape[0]} sources: at most 16 are supported")
+        if not np.all(np.isfinite(src)):
+            raise ValueError("experimental_results['sys_sources'] must be finite")
+        if src.shape[0] == 0:
+            src = None
+    return cov, src
+
+
+def _setup_group(dm, y, cols, starts, lo, hi, n_div, cov, src):
+    """One group's likelihood setup: today's call without correlated uncertainties, else with its slices."""
+    y_err = experimental_results['y_err']
+    if cov is None and src is None:
+        dm.likelihood_setup(y, y_err[cols], lo, hi, n_div=n_div, block_start=starts)
+    else:
+        dm.likelihood_setup(y, y_err[cols], lo, hi, n_div=n_div, block_start=starts,
+                            cov=None if cov is None else cov[np.ix_(cols, cols)],
+                            sys_sources=None if src is None else src[:, cols])
+
+
 def device_models(n_div: float = 1.0):
     """Device models of all groups with the likelihood set up for ``n_div`` (cached)."""
     if _state["models"] is None:
@@ -78,9 +149,10 @@ def device_models(n_div: float = 1.0):
     if _state["n_div"] != float(n_div):
         lo = np.asarray(min, dtype=np.float64)
         hi = np.asarray(max, dtype=np.float64)
-        y, y_err = experimental_results['y'], experimental_results['y_err']
+        y = experimental_results['y']
+        cov, src = data_covariance()
         for dm, cols, starts in _state["models"]:
-            dm.likelihood_setup(y[cols], y_err[cols], lo, hi, n_div=float(n_div), block_start=starts)
+            _setup_group(dm, y[cols], cols, starts, lo, hi, float(n_div), cov, src)
         _state["n_div"] = float(n_div)
     return [m for m, _, _ in _state["models"]]
 
@@ -104,9 +176,9 @@ def device_models_for_chains(y_chains):
     models = device_models(n_div=1.0)               # builds / caches the models
     lo = np.asarray(min, dtype=np.float64)
     hi = np.asarray(max, dtype=np.float64)
-    y_err = experimental_results['y_err']
+    cov, src = data_covariance()
     for dm, cols, starts in _state["models"]:
-        dm.likelihood_setup(y_chains[:, cols], y_err[cols], lo, hi, n_div=1.0, block_start=starts)
+        _setup_group(dm, y_chains[:, cols], cols, starts, lo, hi, 1.0, cov, src)
     _state["n_div"] = None                          # the single-vector constants are gone
     return models
 
@@ -120,9 +192,14 @@ def log_posterior(X):
     n_samples = int(np.count_nonzero(inside))
     if n_samples > 0:
         models = device_models(n_div=n_samples)
-        total = np.zeros(X.shape[0])
-        for dm in models:
-            total += dm.logpost(X)          # rows outside the box come back as -inf
+        if data_covariance()[1] is not None:
+            # sources span the groups: their term needs every group at once
+            from gpemu.model import logpost_groups
+            total = logpost_groups(models, X)
+        else:
+            total = np.zeros(X.shape[0])
+            for dm in models:
+                total += dm.logpost(X)          # rows outside the box come back as -inf
         log_post[inside] = total[inside]
     return log_post
 

@@ -109,6 +109,22 @@ def _closure_indices(config, first, rank, world):
     return [j for j in range(first, hi - lo) if closure_owner(j, world) in (None, rank)]
 
 
+def _with_data_covariance(config, data):
+    """``data`` with the arrays of ``parameters.mcmc.data_covariance`` (an ``.npz`` holding ``cov`` (F, F) and / or
+    ``sys_sources`` (S, F) in the merged, filtered observable order) added; without the key, ``data``
+    itself."""
+    path = getattr(config, 'data_covariance', None)
+    if not path:
+        return data
+    with np.load(path) as npz:
+        extra = {key: np.array(npz[key], dtype=np.float64) for key in ('cov', 'sys_sources') if key in npz.files}
+    if not extra:
+        raise ValueError(f"{path}: parameters.mcmc.data_covariance holds neither 'cov' nor 'sys_sources'")
+    data = dict(data)
+    data.update(extra)
+    return data
+
+
 def _run_closure_batch(config, indices):
     """The chains of ``indices`` (ref: mcmc.py:34-134 each) as one stacked run: per chain the reference's pseudo-data
     draw and start positions (numpy's global state, in the reference's order), its two-stage burn-in with the
@@ -132,7 +148,8 @@ def _run_closure_batch(config, indices):
     for dat in datas[1:]:
         if not np.array_equal(np.asarray(dat['y_err'], dtype=np.float64), y_err):
             raise ValueError("closure chains must share the experimental uncertainties to be stacked")
-    log_posterior.initialize_pool_variables(lower, upper, emu_cfg, emu_results, datas[0], truncation_cov)
+    log_posterior.initialize_pool_variables(lower, upper, emu_cfg, emu_results, _with_data_covariance(config, datas[0]),
+                                            truncation_cov)
     models = log_posterior.device_models_for_chains(np.stack([np.asarray(dat['y'], dtype=np.float64) for dat in datas]))
     seeds = [int(np.random.randint(0, 2 ** 31 - 1)) for _ in indices]
     sampler = DeviceSampler(models, n_walk, seeds=seeds)
@@ -262,6 +279,7 @@ def run_mcmc(config, closure_index=-1):
             data[key] = _same_on_all_ranks(np.asarray(data[key], dtype=np.float64))
 
     # upstream copies this state into every pool worker (ref: mcmc.py:77-78); here it goes to the device once
+    data = _with_data_covariance(config, data)
     log_posterior.initialize_pool_variables(lower, upper, emu_cfg, emu_results, data, truncation_cov)
     sampler = LoggingEnsembleSampler(n_walk, n_par, log_posterior.log_posterior, sharded=False if alone else None)
     logger.info(f'Sampler ready: {n_walk} walkers, {n_par} parameters, {sampler.world_size} GPU process(es)')
@@ -348,6 +366,7 @@ def _run_tempered(config, closure_index):
     io = _data_IO()
     data = io.data_array_from_h5(config.output_dir, 'observables.h5', pseudodata_index=closure_index,
                                  observable_filter=emu_cfg.observable_filter)
+    data = _with_data_covariance(config, data)
     log_posterior.initialize_pool_variables(lower, upper, emu_cfg, emu_results, data, truncation_cov)
     betas = geometric_ladder(n_temp, config.t_max, prior_rung=config.prior_rung)
     seed = int(np.random.randint(0, 2 ** 31 - 1))          # drawn where the untempered path's sampler draws its seed
@@ -498,6 +517,12 @@ class MCMCConfig:
         self.t_max = float(mc.get('t_max', 1e5))
         self.swap_every = int(mc.get('swap_every', 1))
         self.prior_rung = bool(mc.get('prior_rung', True))
+        # correlated experimental uncertainties (optional): an .npz of 'cov' and / or 'sys_sources', a relative path
+        # taken from the directory of the configuration file
+        dc = mc.get('data_covariance')
+        if dc and not os.path.isabs(str(dc)):
+            dc = os.path.join(os.path.dirname(os.path.abspath(config_file)), str(dc))
+        self.data_covariance = str(dc) if dc else None
 
         # <output_dir>/<analysis>_<parameterization>[/closure/results/<index>]/{mcmc.h5, mcmc_sampler.pkl}
         self.output_dir = os.path.join(top['output_dir'], f'{analysis_name}_{parameterization}')

@@ -19,6 +19,7 @@ static thread_local char g_err[512] = "";
 static std::atomic<int64_t> g_path_counts[GPEMU_PATH_COUNT];
 static std::atomic<int64_t> g_fit_path_counts[GPEMU_FIT_PATH_COUNT];
 static std::atomic<int64_t> g_wide_path_counts[GPEMU_WIDE_PATH_COUNT];
+static std::atomic<int64_t> g_src_path_counts[GPEMU_SRC_PATH_COUNT];
 
 void path_count(int path) {
   if (path >= 0 && path < GPEMU_PATH_COUNT) g_path_counts[path].fetch_add(1, std::memory_order_relaxed);
@@ -30,6 +31,10 @@ void fit_path_count(int path) {
 
 void wide_path_count(int path) {
   if (path >= 0 && path < GPEMU_WIDE_PATH_COUNT) g_wide_path_counts[path].fetch_add(1, std::memory_order_relaxed);
+}
+
+void src_path_count(int path) {
+  if (path >= 0 && path < GPEMU_SRC_PATH_COUNT) g_src_path_counts[path].fetch_add(1, std::memory_order_relaxed);
 }
 
 void set_error(const char *fmt, ...) {
@@ -67,6 +72,11 @@ static int dev_alloc(T **p, int64_t n) {
 static int upload(double *dst, const double *src, int64_t n, hipStream_t st) {
   GP_HIP(hipMemcpyAsync(dst, src, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, st));
   return GPEMU_OK;
+}
+
+static void free_lik_entry(const gpemu_model::LikEntry &en) {
+  (void)hipFree(en.G); (void)hipFree(en.g0); (void)hipFree(en.scal);
+  (void)hipFree(en.W); (void)hipFree(en.Q); (void)hipFree(en.w0);
 }
 
 static void free_workspace(Workspace &w) {
@@ -191,6 +201,13 @@ int logpost_eval(gpemu_model *const *ms, int ng, int64_t B, double *dXq, double 
                  const LaunchSwitches &sw, const AcceptArgs *aa, const ProposeArgs *pa) {
   for (int g = 0; g < ng; ++g)
     if (!ms[g]->lik_ready) { set_error("gpemu_likelihood_setup has not been called"); return GPEMU_ERR_STATE; }
+  // correlated sources (k_srccorr.hip): one set of sources for all groups, whose term follows the likelihood stage
+  const int S = ms[0]->n_src;
+  for (int g = 1; g < ng; ++g)
+    if (ms[g]->n_src != S) {
+      set_error("groups set up with different numbers of correlated sources (%d and %d)", S, ms[g]->n_src);
+      return GPEMU_ERR_STATE;
+    }
   for (int g = 0; g < ng; ++g) GP_TRY(ensure_workspace(ms[g], B));
   // the likelihood stage: observable blocks on different waves where that applies, else one launch for the groups
   auto loglik = [&](gpemu_model *const *gs, int n, int accumulate, const AcceptArgs *a) {
@@ -198,10 +215,16 @@ int logpost_eval(gpemu_model *const *ms, int ng, int64_t B, double *dXq, double 
     if (n == 1) return launch_loglik_lowrank(gs[0], B, dXq, dout, accumulate, st, a);
     return launch_loglik_groups(gs, n, B, dXq, dout, accumulate, st, a);
   };
+  AcceptArgs chain_only;                 // groups before the last: no accept, but the rows' chains (data constants)
+  if (aa) { chain_only.chain_per = aa->chain_per; chain_only.first = aa->first; chain_only.chain_data = aa->chain_data; }
+  // with sources the likelihood stage leaves the accept to the sources' launch
+  const AcceptArgs *aa_lik = (S > 0 && aa) ? &chain_only : aa;
+  auto finish = [&]() { return S > 0 ? launch_source_correction(ms, ng, B, dXq, dout, st, aa) : GPEMU_OK; };
   const bool one_chain = !(aa && aa->chain_per != 0);
   if (one_chain && halfstep_fits(ms, ng, B, sw)) {
     GP_TRY(launch_halfstep_small(ms, ng, B, dXq, st, pa));
-    return loglik(ms, ng, 0, aa);
+    GP_TRY(loglik(ms, ng, 0, aa_lik));
+    return finish();
   }
   if (one_chain && sw.group_merge && groups_fit(ms, ng, B)) {
     // (the GEMM's schedules first: the one step that can still decline, before anything is launched)
@@ -210,11 +233,10 @@ int logpost_eval(gpemu_model *const *ms, int ng, int64_t B, double *dXq, double 
       GP_TRY(rc);
       GP_TRY(launch_kstar_groups(ms, ng, B, dXq, st, pa));
       GP_TRY(launch_trmm_vsq_small_groups(ms, ng, B, st));
-      return loglik(ms, ng, 0, aa);
+      GP_TRY(loglik(ms, ng, 0, aa_lik));
+      return finish();
     }
   }
-  AcceptArgs chain_only;                 // groups before the last: no accept, but the rows' chains (data constants)
-  if (aa) { chain_only.chain_per = aa->chain_per; chain_only.first = aa->first; chain_only.chain_data = aa->chain_data; }
   for (int g = 0; g < ng; ++g) {
     gpemu_model *const *one = ms + g;
     const ProposeArgs *pg = g == 0 ? pa : nullptr;
@@ -225,9 +247,9 @@ int logpost_eval(gpemu_model *const *ms, int ng, int64_t B, double *dXq, double 
       GP_TRY(launch_kstar(ms[g], B, dXq, st, pg));
       GP_TRY(launch_trmm_vsq(ms[g], B, st));
     }
-    GP_TRY(loglik(one, 1, g > 0 ? 1 : 0, g + 1 == ng ? aa : (aa ? &chain_only : nullptr)));
+    GP_TRY(loglik(one, 1, g > 0 ? 1 : 0, g + 1 == ng ? aa_lik : (aa ? &chain_only : nullptr)));
   }
-  return GPEMU_OK;
+  return finish();
 }
 }  // namespace gpemu
 
@@ -254,6 +276,12 @@ int gpemu_wide_path_counts(int64_t *out, int64_t n) {
   GP_ARG(out && n >= 0, "out, n");
   for (int64_t i = 0; i < n && i < GPEMU_WIDE_PATH_COUNT; ++i) out[i] = g_wide_path_counts[i].load(std::memory_order_relaxed);
   return GPEMU_WIDE_PATH_COUNT;
+}
+
+int gpemu_src_path_counts(int64_t *out, int64_t n) {
+  GP_ARG(out && n >= 0, "out, n");
+  for (int64_t i = 0; i < n && i < GPEMU_SRC_PATH_COUNT; ++i) out[i] = g_src_path_counts[i].load(std::memory_order_relaxed);
+  return GPEMU_SRC_PATH_COUNT;
 }
 
 int gpemu_device_count(void) {
@@ -469,7 +497,8 @@ int gpemu_model_destroy(gpemu_model *m) {
   hipFree(m->etab); hipFree(m->constv); hipFree(m->kdiag);
   hipFree(m->alpha); hipFree(m->cv_jit); hipFree(m->Wt); hipFree(m->Xtr); hipFree(m->comp); hipFree(m->smean); hipFree(m->sscale);
   hipFree(m->cunexpl); hipFree(m->yexp); hipFree(m->yerr); hipFree(m->lo); hipFree(m->hi);
-  for (const gpemu_model::LikEntry &en : m->lik_cache) { hipFree(en.G); hipFree(en.g0); hipFree(en.scal); }
+  for (const gpemu_model::LikEntry &en : m->lik_cache) free_lik_entry(en);
+  hipFree(m->ycov); hipFree(m->srcs);
   hipFree(m->exact_scratch);
   hipFree(m->blk_start); hipFree(m->blk_of);
   for (const gpemu_model::SchedEntry &en : m->sched_cache) { hipFree(en.items); hipFree(en.cnt); }
@@ -733,10 +762,18 @@ int gpemu_likelihood_setup(gpemu_model *m, const double *y_exp, const double *y_
 int gpemu_likelihood_setup_chains(gpemu_model *m, int n_chains, const double *y_exp, const double *y_err,
                                   const double *lo, const double *hi, double n_div, int64_t n_blocks,
                                   const int64_t *block_start) {
+  return gpemu_likelihood_setup_cov(m, n_chains, y_exp, y_err, nullptr, 0, nullptr, lo, hi, n_div, n_blocks, block_start);
+}
+
+int gpemu_likelihood_setup_cov(gpemu_model *m, int n_chains, const double *y_exp, const double *y_err,
+                               const double *cov, int64_t n_src, const double *sources, const double *lo,
+                               const double *hi, double n_div, int64_t n_blocks, const int64_t *block_start) {
   GP_ARG(m && y_exp && y_err && lo && hi, "null pointer");
   GP_ARG(n_div >= 1.0, "n_div must be >= 1");
   GP_ARG(n_chains >= 1 && n_chains <= 4096, "n_chains must be in [1, 4096]");
-  const int64_t NC = n_chains;
+  GP_ARG(n_src >= 0 && n_src <= GPEMU_MAX_SOURCES, "n_src must be in [0, 16]");
+  GP_ARG(n_src == 0 || sources, "sources");
+  const int64_t NC = n_chains, S = n_src;
   GP_HIP(hipSetDevice(m->device));
   hipStream_t st = m->stream;
   const int64_t F = m->F, k = m->k;
@@ -754,6 +791,24 @@ int gpemu_likelihood_setup_chains(gpemu_model *m, int n_chains, const double *y_
   const int64_t nblk = (int64_t)hstart.size() - 1;
   for (int64_t o = 0; o < nblk; ++o)
     for (int f = hstart[o]; f < hstart[o + 1]; ++f) hof[f] = (int)o;
+  if (cov) {
+    // C_d's dense part lives inside the observables: the likelihood factorises over the blocks (the sources carry what
+    // is correlated across them)
+    for (int64_t f = 0; f < F; ++f)
+      for (int64_t g = 0; g < F; ++g) {
+        const double v = cov[f * F + g];
+        if (v != cov[g * F + f] || !std::isfinite(v)) {
+          set_error("bad argument: cov must be finite and symmetric (entry %lld, %lld)", (long long)f, (long long)g);
+          return GPEMU_ERR_ARG;
+        }
+        if (hof[f] != hof[g] && v != 0.0) {
+          set_error("bad argument: cov[%lld][%lld] = %g couples observable blocks %d and %d: give correlations across "
+                    "observables as sources", (long long)f, (long long)g, v, hof[f], hof[g]);
+          return GPEMU_ERR_ARG;
+        }
+      }
+  }
+  GP_ARG(S == 0 || all_finite(sources, S * F), "sources must be finite");
   // same data as the cached constants belong to?  then an n_div seen before is a pointer swap
   std::vector<double> key;
   key.push_back((double)NC);
@@ -762,25 +817,29 @@ int gpemu_likelihood_setup_chains(gpemu_model *m, int n_chains, const double *y_
   key.insert(key.end(), lo, lo + m->d);
   key.insert(key.end(), hi, hi + m->d);
   for (int v : hstart) key.push_back((double)v);
+  key.push_back(cov ? 1.0 : 0.0);
+  if (cov) key.insert(key.end(), cov, cov + F * F);
+  key.push_back((double)S);
+  key.insert(key.end(), sources, sources + S * F);
   const bool same_data = m->lik_ready && key.size() == m->lik_host.size() &&
                          memcmp(key.data(), m->lik_host.data(), sizeof(double) * key.size()) == 0;
   if (same_data) {
     for (const gpemu_model::LikEntry &en : m->lik_cache)
       if (en.n_div == n_div) {
         GP_HIP(hipStreamSynchronize(st));
-        m->G = en.G; m->g0 = en.g0; m->scal = en.scal; m->n_div = n_div;
+        m->G = en.G; m->g0 = en.g0; m->scal = en.scal; m->W = en.W; m->Q = en.Q; m->w0 = en.w0; m->n_div = n_div;
         return GPEMU_OK;
       }
   } else {
     GP_HIP(hipStreamSynchronize(st));
-    for (const gpemu_model::LikEntry &en : m->lik_cache) { (void)hipFree(en.G); (void)hipFree(en.g0); (void)hipFree(en.scal); }
+    for (const gpemu_model::LikEntry &en : m->lik_cache) free_lik_entry(en);
     m->lik_cache.clear();
-    m->G = m->g0 = m->scal = nullptr;
+    m->G = m->g0 = m->scal = m->W = m->Q = m->w0 = nullptr;
   }
   if (m->lik_cache.size() >= 64) {           // bounded: drop the oldest entry
     GP_HIP(hipStreamSynchronize(st));
     const gpemu_model::LikEntry en = m->lik_cache.front();
-    (void)hipFree(en.G); (void)hipFree(en.g0); (void)hipFree(en.scal);
+    free_lik_entry(en);
     m->lik_cache.erase(m->lik_cache.begin());
   }
   GP_HIP(hipStreamSynchronize(st));
@@ -795,10 +854,20 @@ int gpemu_likelihood_setup_chains(gpemu_model *m, int n_chains, const double *y_
   m->lik_chains = n_chains;
   (void)hipFree(m->blk_start);
   m->blk_start = nullptr;
-  gpemu_model::LikEntry en{n_div, nullptr, nullptr, nullptr};
+  (void)hipFree(m->ycov);
+  (void)hipFree(m->srcs);
+  m->ycov = m->srcs = nullptr;
+  m->n_src = 0;
+  if (cov) GP_TRY(dev_alloc(&m->ycov, F * F));
+  if (S > 0) GP_TRY(dev_alloc(&m->srcs, S * F));
+  m->n_src = (int)S;
+  gpemu_model::LikEntry en{n_div, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   GP_TRY(dev_alloc(&en.G, nblk * k * k)); GP_TRY(dev_alloc(&en.g0, NC * nblk * k));
   GP_TRY(dev_alloc(&en.scal, NC * 2 * nblk)); GP_TRY(dev_alloc(&m->blk_start, nblk + 1));
-  m->G = en.G; m->g0 = en.g0; m->scal = en.scal;
+  if (S > 0) {
+    GP_TRY(dev_alloc(&en.W, nblk * k * S)); GP_TRY(dev_alloc(&en.Q, nblk * S * S)); GP_TRY(dev_alloc(&en.w0, NC * nblk * S));
+  }
+  m->G = en.G; m->g0 = en.g0; m->scal = en.scal; m->W = en.W; m->Q = en.Q; m->w0 = en.w0;
   m->lik_cache.push_back(en);
   m->nblk = nblk;
   GP_HIP(hipMemcpyAsync(m->blk_start, hstart.data(), sizeof(int) * (nblk + 1), hipMemcpyHostToDevice, st));
@@ -810,12 +879,14 @@ int gpemu_likelihood_setup_chains(gpemu_model *m, int n_chains, const double *y_
   for (int i = 0; i < m->dp; ++i) { hlo[i] = i < m->d ? lo[i] : -INFINITY; hhi[i] = i < m->d ? hi[i] : INFINITY; }
   GP_TRY(upload(m->yexp, y_exp, NC * F, st)); GP_TRY(upload(m->yerr, y_err, F, st));
   GP_TRY(upload(m->lo, hlo, m->dp, st)); GP_TRY(upload(m->hi, hhi, m->dp, st));
+  if (cov) GP_TRY(upload(m->ycov, cov, F * F, st));
+  if (S > 0) GP_TRY(upload(m->srcs, sources, S * F, st));
   GP_HIP(hipStreamSynchronize(st));  // hlo/hhi are stack buffers
   double *dA = nullptr, *dPT = nullptr, *dZ = nullptr;
   int *dinfo = nullptr;
   int rc = dev_alloc(&dA, F * F);
   if (rc == GPEMU_OK) rc = dev_alloc(&dPT, nblk * chol_scratch_size(F));
-  if (rc == GPEMU_OK) rc = dev_alloc(&dZ, F * (k + NC));
+  if (rc == GPEMU_OK) rc = dev_alloc(&dZ, F * (k + NC + S));
   if (rc == GPEMU_OK) rc = dev_alloc(&dinfo, nblk);
   std::vector<int> info((size_t)nblk, 0);
   if (rc == GPEMU_OK && hipMemsetAsync(dinfo, 0, sizeof(int) * nblk, st) != hipSuccess) rc = GPEMU_ERR_HIP;
@@ -829,13 +900,15 @@ int gpemu_likelihood_setup_chains(gpemu_model *m, int n_chains, const double *y_
   if (rc != GPEMU_OK) return rc;
   for (int64_t o = 0; o < nblk; ++o) {
     if (info[o] != 0) {
-      set_error("likelihood_setup: A = C_unexpl/n o ss^T + diag(y_err^2) is not positive definite "
-                "(observable block %lld, pivot %d)", (long long)o, info[o]);
+      set_error("likelihood_setup: A = C_unexpl/n o ss^T + %s is not positive definite "
+                "(observable block %lld, pivot %d)", cov ? "cov" : "diag(y_err^2)", (long long)o, info[o]);
       return hstart[o] + info[o];
     }
   }
   m->lik_ready = true;
   m->lik_host = key;
+  if (cov) src_path_count(GPEMU_SRC_PATH_SETUP_COV);
+  if (S > 0) src_path_count(GPEMU_SRC_PATH_SETUP_SOURCES);
   return GPEMU_OK;
 }
 
@@ -846,6 +919,10 @@ int gpemu_logpost_dev(gpemu_model *m, int64_t B, const double *dX, double *dout,
   GP_ARG(dX && dout, "null pointer");
   GP_ARG(mode == GPEMU_LOGPOST_LOWRANK || mode == GPEMU_LOGPOST_EXACT, "mode");
   if (!m->lik_ready) { set_error("gpemu_likelihood_setup has not been called"); return GPEMU_ERR_STATE; }
+  if (mode == GPEMU_LOGPOST_EXACT && m->n_src > 0) {
+    set_error("GPEMU_LOGPOST_EXACT does not support correlated sources (n_src = %d): use GPEMU_LOGPOST_LOWRANK", m->n_src);
+    return GPEMU_ERR_UNSUPPORTED;
+  }
   GP_HIP(hipSetDevice(m->device));
   hipStream_t st = stream ? (hipStream_t)stream : m->stream;
   const LaunchSwitches sw = read_launch_switches();
@@ -881,6 +958,55 @@ int gpemu_logpost(gpemu_model *m, int64_t B, const double *X, double *out, int m
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e != hipSuccess) { set_error("logpost: %s", hipGetErrorString(e)); rc = GPEMU_ERR_HIP; }
   }
+  hipFree(dX); hipFree(dout);
+  return rc;
+}
+
+int gpemu_logpost_groups(gpemu_model *const *models, int n_groups, int64_t B, const double *X, double *out, int mode) {
+  GP_ARG(models && n_groups > 0, "models");
+  GP_ARG(B >= 0, "B must not be negative");
+  GP_ARG(mode == GPEMU_LOGPOST_LOWRANK || mode == GPEMU_LOGPOST_EXACT, "mode");
+  for (int g = 0; g < n_groups; ++g) {
+    GP_ARG(models[g], "null model");
+    GP_ARG(models[g]->d == models[0]->d && models[g]->device == models[0]->device,
+           "models must share the parameter dimension and the device");
+  }
+  if (B == 0) return GPEMU_OK;
+  GP_ARG(X && out, "null pointer");
+  gpemu_model *m0 = models[0];
+  if (mode == GPEMU_LOGPOST_EXACT) {
+    // validation form: the groups one after the other, their terms added in group order on the host
+    std::vector<double> part((size_t)B);
+    for (int g = 0; g < n_groups; ++g) {
+      GP_TRY(gpemu_logpost(models[g], B, X, g == 0 ? out : part.data(), mode));
+      if (g > 0)
+        for (int64_t i = 0; i < B; ++i) out[i] = part[(size_t)i] + out[i];
+    }
+    return GPEMU_OK;
+  }
+  for (int g = 0; g < n_groups; ++g)
+    if (!models[g]->lik_ready) { set_error("gpemu_likelihood_setup has not been called"); return GPEMU_ERR_STATE; }
+  GP_HIP(hipSetDevice(m0->device));
+  hipStream_t st = m0->stream;
+  const LaunchSwitches sw = read_launch_switches();
+  double *dX = nullptr, *dout = nullptr;
+  int rc = dev_alloc(&dX, B * m0->d);
+  if (rc == GPEMU_OK) rc = dev_alloc(&dout, B);
+  if (rc == GPEMU_OK) rc = upload(dX, X, B * m0->d, st);
+  for (int64_t off = 0; off < B && rc == GPEMU_OK; off += MAX_CHUNK) {
+    const int64_t nb = (B - off < MAX_CHUNK) ? (B - off) : MAX_CHUNK;
+    path_count(GPEMU_PATH_PREDICT_PASS);
+    rc = ensure_workspace(m0, nb);   // (before ws.Xq is read: it may move)
+    if (rc != GPEMU_OK) break;
+    const ProposeArgs raw = raw_rows(m0, nb, dX + off * m0->d);
+    rc = logpost_eval(models, n_groups, nb, m0->ws.Xq, dout + off, st, sw, nullptr, &raw);
+  }
+  if (rc == GPEMU_OK) {
+    hipError_t e = hipMemcpyAsync(out, dout, sizeof(double) * B, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) { set_error("logpost_groups: %s", hipGetErrorString(e)); rc = GPEMU_ERR_HIP; }
+  }
+  (void)hipStreamSynchronize(st);
   hipFree(dX); hipFree(dout);
   return rc;
 }

@@ -143,9 +143,9 @@ struct gpemu_model {
   // the constants (G, g0, scal) depend on the data AND on n_div (the reference divides the truncation covariance by
   // the number of in-bounds rows of each call): one entry per n_div seen with the current data, so that a batch
   // size that comes back costs nothing.  G / g0 / scal below point into the current entry.
-  struct LikEntry { double n_div; double *G, *g0, *scal; };
+  struct LikEntry { double n_div; double *G, *g0, *scal, *W, *Q, *w0; };
   std::vector<LikEntry> lik_cache;
-  std::vector<double> lik_host;        // y_exp | y_err | lo | hi | block starts the cache belongs to
+  std::vector<double> lik_host;        // y_exp | y_err | lo | hi | block starts | cov | sources the cache belongs to
   double *yexp = nullptr, *yerr = nullptr, *lo = nullptr, *hi = nullptr;  // [F],[F],[dp],[dp]
   int64_t nblk = 1;            // observable blocks of the (block-diagonal) covariance
   int *blk_start = nullptr;    // [nblk+1] first feature of each block
@@ -153,6 +153,13 @@ struct gpemu_model {
   double *G = nullptr;         // [nblk][k][k]   U_o^T A_o^-1 U_o
   double *g0 = nullptr;        // [nblk][k]      U_o^T A_o^-1 r0_o
   double *scal = nullptr;      // [nblk][2]      q0_o, logdet A_o
+  // correlated data uncertainties (k_srccorr.hip): C_d = blockdiag_o(C_o) + sum_s b_s b_s^T
+  double *ycov = nullptr;      // [F][F] within-observable data covariance C_o, or null: diag(y_err^2)
+  double *srcs = nullptr;      // [n_src][F] fully correlated systematic sources b_s (this group's columns)
+  int n_src = 0;               // S, 0 .. GPEMU_MAX_SOURCES
+  double *W = nullptr;         // [nblk][k][S]   U_o^T A_o^-1 B_o
+  double *Q = nullptr;         // [nblk][S][S]   B_o^T A_o^-1 B_o
+  double *w0 = nullptr;        // [chains][nblk][S]  B_o^T A_o^-1 r0_o
 
   // exact-form (validation) scratch: per-workgroup Sigma, panel and residual
   double *exact_scratch = nullptr;
@@ -170,6 +177,14 @@ struct gpemu_model {
 };
 
 namespace gpemu {
+// A[f][g] + the data covariance's entry (likelihood setup, exact form): C_o where given (ycov, k_srccorr.hip), else
+// diag(y_err^2).  A diagonal entry of C_o equal to y_err_f^2 is added as the default adds it, fma(y_err_f, y_err_f, v):
+// cov = diag(y_err^2) gives the bits of the setup without cov.
+__device__ inline double add_data_cov(double v, int f, int g, int64_t idx, const double *yerr, const double *ycov) {
+  if (ycov && (f != g || ycov[idx] != yerr[f] * yerr[f])) return v + ycov[idx];
+  return (f == g) ? fma(yerr[f], yerr[f], v) : v;
+}
+
 // optional fused stretch-move finish (accept / reject + chain record) for the walker of each proposal
 struct AcceptArgs {
   int enabled = 0;
@@ -284,6 +299,11 @@ int launch_loglik_groups(gpemu_model *const *ms, int ng, int64_t B, const double
 bool loglik_tasks_fit(gpemu_model *const *ms, int ng, int64_t B, const AcceptArgs *aa, const LaunchSwitches &sw);
 int launch_loglik_tasks(gpemu_model *const *ms, int ng, int64_t B, const double *dXq_padded, double *dout, int accumulate,
                         hipStream_t st, const AcceptArgs *aa);
+// the fully correlated sources' term (k_srccorr.hip), after the likelihood stage of all ng groups (which wrote their
+// block-diagonal sum to dout and left the accept to this launch): adds the Woodbury correction, finishes the stretch move
+int launch_source_correction(gpemu_model *const *ms, int ng, int64_t B, const double *dXq_padded, double *dout,
+                             hipStream_t st, const AcceptArgs *aa);
+void src_path_count(int path);   // enum gpemu_src_path (gpemu_src_path_counts)
 // small emulators (N <= 256 design points, k_halfstep.hip): cross-kernel + triangular GEMM of all groups in one launch,
 // then the likelihood launch; the bits of the general path.  Launch only where halfstep_fits
 bool halfstep_fits(gpemu_model *const *ms, int ng, int64_t B, const LaunchSwitches &sw);

@@ -507,7 +507,7 @@ int launch_predict_full(gpemu_model *m, int64_t B, double n_div, double *dcv, do
 }
 
 // ------------------------------------------------------------------------------------------
-// Exact form: Sigma_b = cov_b + diag(y_err^2) (lower triangle), Cholesky, forward solve, log-det.
+// Exact form: Sigma_b = cov_b + diag(y_err^2) (or + C_o, the dense within-observable data covariance; lower triangle), Cholesky, forward solve, log-det.
 // One workgroup per walker slot; walkers are processed grid-stride so the scratch stays bounded.
 __global__ __launch_bounds__(CHOL_THREADS) void loglik_exact_kernel(
     const double *__restrict__ Xq, const double *__restrict__ lo, const double *__restrict__ hi,
@@ -515,7 +515,7 @@ __global__ __launch_bounds__(CHOL_THREADS) void loglik_exact_kernel(
     const double *__restrict__ kdiag, const double *__restrict__ comp,
     const double *__restrict__ smean, const double *__restrict__ sscale,
     const double *__restrict__ cun, const double *__restrict__ yexp, const double *__restrict__ yerr,
-    const int *__restrict__ blk_of, double *__restrict__ scratch, double *__restrict__ out, int64_t B,
+    const double *__restrict__ ycov, const int *__restrict__ blk_of, double *__restrict__ scratch, double *__restrict__ out, int64_t B,
     int64_t Bcap, int d, int F,
     int k, int nchunk, int nrb, double inv_ndiv) {
   __shared__ double s_mu[64], s_var[64];
@@ -557,8 +557,7 @@ __global__ __launch_bounds__(CHOL_THREADS) void loglik_exact_kernel(
       double acc = 0.0;
       for (int p = 0; p < k; ++p) acc = fma(comp[(int64_t)p * F + f] * s_var[p], comp[(int64_t)p * F + g], acc);
       double v = (acc + cun[idx] * inv_ndiv) * (sscale[f] * sscale[g]);
-      if (f == g) v += yerr[f] * yerr[f];
-      S[idx] = v;
+      S[idx] = add_data_cov(v, f, g, idx, yerr, ycov);   // + C_o or diag(y_err^2)
     }
     for (int f = tid; f < F; f += nthr) {
       double s = 0.0;
@@ -593,9 +592,10 @@ int launch_loglik_exact(gpemu_model *m, int64_t B, const double *dXq, double *do
   const Workspace &w = m->ws;
   hipLaunchKernelGGL(loglik_exact_kernel, dim3((unsigned)nwg), dim3(CHOL_THREADS), 0, st, dXq, m->lo,
                      m->hi, w.mean_part, w.vsq_part, m->kdiag, m->comp, m->smean, m->sscale,
-                     m->cunexpl, m->yexp, m->yerr, m->blk_of, m->exact_scratch, dout, B, w.Bcap, (int)m->d,
+                     m->cunexpl, m->yexp, m->yerr, m->ycov, m->blk_of, m->exact_scratch, dout, B, w.Bcap, (int)m->d,
                      F, (int)m->k, w.cur_nchunk, w.cur_nrb, 1.0 / m->n_div);
   GP_HIP(hipGetLastError());
+  if (m->ycov) src_path_count(GPEMU_SRC_PATH_EXACT_COV);
   return GPEMU_OK;
 }
 

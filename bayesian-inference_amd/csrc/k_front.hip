@@ -559,7 +559,8 @@ bool front_eligible(const gpemu_sampler *s) {
   if (off || s->groups.empty() || (int)s->groups.size() > FRONT_MAX_GROUPS || s->nchains != 1 || s->tempered) return false;
   for (const gpemu_model *m : s->groups)
     // ksteps 3: d = 8 parameters; and the wide padding (d > 8) has no instance here: those runs take the general path
-    if (m->k > 64 || m->ksteps != 2 || m->dp != DPAD || m->device != s->groups[0]->device) return false;
+    // ... nor does the sources' term (k_srccorr.hip): groups with correlated sources take the collective transport
+    if (m->k > 64 || m->ksteps != 2 || m->dp != DPAD || m->device != s->groups[0]->device || m->n_src > 0) return false;
   return true;
 }
 
@@ -829,7 +830,8 @@ int gpemu_sampler_peer_export(gpemu_sampler *s, char *handle_out64) {
   }
   GP_HIP(hipSetDevice(s->device));
   if (!front_eligible(s)) {     // the caller (every rank alike) then stays on the collective transports
-    set_error("the fused run needs at most %d emulation groups of at most 64 PCs and 7 parameters, one chain", FRONT_MAX_GROUPS);
+    set_error("the fused run needs at most %d emulation groups of at most 64 PCs and 7 parameters, one chain, no correlated "
+              "sources (gpemu_likelihood_setup_cov with n_src > 0)", FRONT_MAX_GROUPS);
     return GPEMU_ERR_UNSUPPORTED;
   }
   int rc = ensure_gather(s);
@@ -850,7 +852,7 @@ int gpemu_sampler_peer_import(gpemu_sampler *s, int world, int rank, const char 
   GP_HIP(hipSetDevice(s->device));
   if (!front_eligible_for(s, world)) {
     set_error("the fused run cannot take this sampler at %d rank(s): at most %d groups of at most 64 PCs and 7 parameters, "
-              "one chain, and -- with %d ranks on this device -- all their launches resident together", world,
+              "one chain, no correlated sources, and -- with %d ranks on this device -- all their launches resident together", world,
               FRONT_MAX_GROUPS, s->device_share);
     return GPEMU_ERR_UNSUPPORTED;
   }
@@ -920,7 +922,8 @@ int gpemu_sampler_run_peer(gpemu_sampler *s, int64_t steps, int store_chain) {
   }
   GP_HIP(hipSetDevice(s->device));
   if (!front_eligible(s)) {
-    set_error("the fused run needs at most %d emulation groups of at most 64 PCs, one chain", FRONT_MAX_GROUPS);
+    set_error("the fused run needs at most %d emulation groups of at most 64 PCs and 7 parameters, one chain, no correlated "
+              "sources (gpemu_likelihood_setup_cov with n_src > 0)", FRONT_MAX_GROUPS);
     return GPEMU_ERR_UNSUPPORTED;
   }
   if (s->peer_world < 1) { set_error("gpemu_sampler_peer_import has not been called"); return GPEMU_ERR_STATE; }

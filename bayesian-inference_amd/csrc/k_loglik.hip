@@ -23,53 +23,84 @@
 namespace gpemu {
 
 // ---- setup ----------------------------------------------------------------------------------
+// ycov (optional): the dense within-observable data covariance C_o in place of diag(y_err^2) (k_srccorr.hip)
 __global__ void build_A_kernel(const double *__restrict__ cun, const double *__restrict__ s,
-                               const double *__restrict__ yerr, double *__restrict__ A, int F,
-                               double inv_ndiv) {
+                               const double *__restrict__ yerr, const double *__restrict__ ycov, double *__restrict__ A,
+                               int F, double inv_ndiv) {
   int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= (int64_t)F * F) return;
   int f = (int)(idx / F), g = (int)(idx - (int64_t)f * F);
-  double v = cun[idx] * inv_ndiv * (s[f] * s[g]);
-  if (f == g) v += yerr[f] * yerr[f];
-  A[idx] = v;
+  A[idx] = add_data_cov(cun[idx] * inv_ndiv * (s[f] * s[g]), f, g, idx, yerr, ycov);
 }
 
-// one workgroup per observable block o (features f0..f1): chol(A_o); Z = C^-1 [U_o | r0_o];
-// G_o = Zu^T Zu; g0_o = Zu^T zr; q0_o = zr^T zr; logdet A_o
+// the right-hand sides of the setup's triangular solve, column p of feature f: [U | r0 per chain | sources]
+__device__ __forceinline__ double setup_rhs(int p, int f, int F, int k, int nch, const double *__restrict__ comp,
+                                            const double *__restrict__ s, const double *__restrict__ smean,
+                                            const double *__restrict__ yexp, const double *__restrict__ src) {
+  if (p < k) return s[f] * comp[(int64_t)p * F + f];
+  if (p < k + nch) return smean[f] - yexp[(int64_t)(p - k) * F + f];
+  return src[(int64_t)(p - k - nch) * F + f];
+}
+
+// the Gram products Z^T Z the likelihood keeps, Z = C^-1 [U | r0 (nch chains) | B (S sources)] of block o: G = Zu^T Zu,
+// g0 = Zu^T zr, q0 = zr^T zr and, for the sources, W = Zu^T Zb, Q = Zb^T Zb, w0 = Zb^T zr (k_srccorr.hip)
+struct GramOut {
+  double *G, *g0, *scal, *W, *Q, *w0;
+  int k, nch, S, nblk;
+};
+__device__ __forceinline__ bool gram_wanted(int p, int q, const GramOut &go) {
+  const int k = go.k, kc = go.k + go.nch;
+  if (p < k) return true;                          // G, g0, W
+  if (p < kc) return p == q;                       // q0
+  return q >= k;                                   // w0 (chain column q), Q (source column q)
+}
+__device__ __forceinline__ void gram_store(int p, int q, int o, double acc, const GramOut &go) {
+  const int k = go.k, kc = go.k + go.nch, S = go.S;
+  if (p < k) {
+    if (q < k) go.G[((int64_t)o * k + p) * k + q] = acc;
+    else if (q < kc) go.g0[((int64_t)(q - k) * go.nblk + o) * k + p] = acc;
+    else go.W[((int64_t)o * k + p) * S + (q - kc)] = acc;
+  } else if (p < kc) {
+    go.scal[((int64_t)(p - k) * go.nblk + o) * 2] = acc;
+  } else if (q < kc) {
+    go.w0[((int64_t)(q - k) * go.nblk + o) * S + (p - kc)] = acc;
+  } else {
+    go.Q[((int64_t)o * S + (p - kc)) * S + (q - kc)] = acc;
+  }
+}
+
+// one workgroup per observable block o (features f0..f1): chol(A_o); Z = C^-1 [U_o | r0_o | B_o];
+// the Gram products of GramOut; logdet A_o
 __global__ __launch_bounds__(CHOL_THREADS) void lik_setup_kernel(
-    double *A, double *PT, double *Z /*[F][k+1]*/, const double *__restrict__ comp,
+    double *A, double *PT, double *Z /*[F][k+nch+S]*/, const double *__restrict__ comp,
     const double *__restrict__ s, const double *__restrict__ smean, const double *__restrict__ yexp,
-    const int *__restrict__ blk_start, double *G, double *g0, double *scal, int F, int k, int *info, int max_nf,
-    int nch) {
+    const double *__restrict__ src, const int *__restrict__ blk_start, GramOut go, int F, int *info, int max_nf) {
   const int tid = threadIdx.x, nthr = blockDim.x;
-  const int o = blockIdx.x, nblk = gridDim.x;
+  const int o = blockIdx.x, k = go.k, nch = go.nch;
   const int f0 = blk_start[o], nf = blk_start[o + 1] - f0;
   if (nf > max_nf) return;       // large blocks go through the blocked path (launch_lik_setup)
-  const int k1 = k + nch;
+  const int k1 = k + nch + go.S;
   double *Ao = A + (int64_t)f0 * F + f0;
   double *Zo = Z + (int64_t)f0 * k1;
   double *PTo = PT + (int64_t)o * chol_scratch_size(F);
   for (int idx = tid; idx < nf * k1; idx += nthr) {
     int f = f0 + idx / k1, p = idx % k1;
-    Zo[idx] = (p < k) ? s[f] * comp[(int64_t)p * F + f] : (smean[f] - yexp[(int64_t)(p - k) * F + f]);
+    Zo[idx] = setup_rhs(p, f, F, k, nch, comp, s, smean, yexp, src);
   }
   wg_cholesky_lower(Ao, nf, F, PTo, info + o);
   for (int c0 = 0; c0 < k1; c0 += nthr)        // one thread per right-hand side
     wg_forward_solve_multi(Ao, nf, F, Zo + c0, k1, (k1 - c0 < nthr) ? (k1 - c0) : nthr);
   for (int idx = tid; idx < k1 * k1; idx += nthr) {
     int p = idx / k1, q = idx - p * k1;
-    const bool wanted = (p < k && q < k) || (p < k && q >= k) || (p == q);
-    if (!wanted) continue;
+    if (!gram_wanted(p, q, go)) continue;
     double acc = 0.0;
     for (int f = 0; f < nf; ++f) acc = fma(Zo[(int64_t)f * k1 + p], Zo[(int64_t)f * k1 + q], acc);
-    if (p < k && q < k) G[((int64_t)o * k + p) * k + q] = acc;
-    else if (p < k) g0[((int64_t)(q - k) * nblk + o) * k + p] = acc;
-    else scal[((int64_t)(p - k) * nblk + o) * 2] = acc;
+    gram_store(p, q, o, acc, go);
   }
   double ld = 0.0;
   for (int f = tid; f < nf; f += nthr) ld += log(Ao[(int64_t)f * F + f]);
   ld = wg_sum(ld);
-  if (tid < nch) scal[((int64_t)tid * nblk + o) * 2 + 1] = 2.0 * ld;
+  if (tid < nch) go.scal[((int64_t)tid * go.nblk + o) * 2 + 1] = 2.0 * ld;
 }
 
 // ---- large observable blocks: blocked MFMA Cholesky + triangular inverse instead of one workgroup ------------
@@ -85,20 +116,20 @@ __global__ void lik_pad_block_kernel(const double *__restrict__ A, int ld, int n
   Ab[(int64_t)r * Np + c] = v;
 }
 
-// Z[i][c] = sum_{j <= i} W[i][j] R[j][c],  R = [U_o | r0_o]  (nf x (k+1)); one wave per row i, lanes over j
+// Z[i][c] = sum_{j <= i} W[i][j] R[j][c],  R = [U_o | r0_o | B_o]  (nf x (k+nch+S)); one wave per row i, lanes over j
 __global__ __launch_bounds__(256) void lik_z_kernel(const double *__restrict__ W, int Np, int nf, int f0, int F, int k,
                                                     const double *__restrict__ comp, const double *__restrict__ s,
                                                     const double *__restrict__ smean, const double *__restrict__ yexp,
-                                                    double *__restrict__ Z, int nch) {
+                                                    const double *__restrict__ src, double *__restrict__ Z, int nch, int S) {
   const int lane = threadIdx.x & 63;
   const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (i >= nf) return;
-  const int k1 = k + nch;
+  const int k1 = k + nch + S;
   for (int c = 0; c < k1; ++c) {
     double acc = 0.0;
     for (int j = lane; j <= i; j += 64) {
       const int f = f0 + j;
-      const double r = (c < k) ? s[f] * comp[(int64_t)c * F + f] : (smean[f] - yexp[(int64_t)(c - k) * F + f]);
+      const double r = setup_rhs(c, f, F, k, nch, comp, s, smean, yexp, src);
       acc = fma(W[(int64_t)i * Np + j], r, acc);
     }
     for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
@@ -106,26 +137,22 @@ __global__ __launch_bounds__(256) void lik_z_kernel(const double *__restrict__ W
   }
 }
 
-// G_o = Zu^T Zu, g0_o = Zu^T zr, q0_o = zr^T zr, logdet A_o = 2 sum log diag C: one workgroup
+// the Gram products of GramOut for block o, logdet A_o = 2 sum log diag C: one workgroup
 __global__ __launch_bounds__(1024) void lik_gram_kernel(const double *__restrict__ Z, const double *__restrict__ Lb, int Np,
-                                                        int nf, int f0, int k, int o, double *G, double *g0, double *scal,
-                                                        int nch, int nblk) {
-  const int tid = threadIdx.x, k1 = k + nch;
+                                                        int nf, int f0, int o, GramOut go) {
+  const int tid = threadIdx.x, k1 = go.k + go.nch + go.S;
   const double *Zo = Z + (int64_t)f0 * k1;
   for (int idx = tid; idx < k1 * k1; idx += 1024) {
     const int p = idx / k1, q = idx - p * k1;
-    const bool wanted = (p < k && q < k) || (p < k && q >= k) || (p == q);
-    if (!wanted) continue;
+    if (!gram_wanted(p, q, go)) continue;
     double acc = 0.0;
     for (int f = 0; f < nf; ++f) acc = fma(Zo[(int64_t)f * k1 + p], Zo[(int64_t)f * k1 + q], acc);
-    if (p < k && q < k) G[((int64_t)o * k + p) * k + q] = acc;
-    else if (p < k) g0[((int64_t)(q - k) * nblk + o) * k + p] = acc;
-    else scal[((int64_t)(p - k) * nblk + o) * 2] = acc;
+    gram_store(p, q, o, acc, go);
   }
   double ld = 0.0;
   for (int f = tid; f < nf; f += 1024) ld += log(Lb[(int64_t)f * Np + f]);
   ld = wg_sum(ld);
-  if (tid < nch) scal[((int64_t)tid * nblk + o) * 2 + 1] = 2.0 * ld;
+  if (tid < go.nch) go.scal[((int64_t)tid * go.nblk + o) * 2 + 1] = 2.0 * ld;
 }
 
 // hstart: the observable block boundaries (host copy).  Small blocks: one workgroup each (lik_setup_kernel, all of
@@ -135,11 +162,11 @@ int launch_lik_setup(gpemu_model *m, const std::vector<int> &hstart, double *dA,
                      hipStream_t st) {
   const int F = (int)m->F, k = (int)m->k;
   int64_t n = (int64_t)F * F;
+  const GramOut go{m->G, m->g0, m->scal, m->W, m->Q, m->w0, k, m->lik_chains, m->n_src, (int)m->nblk};
   hipLaunchKernelGGL(build_A_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, m->cunexpl,
-                     m->sscale, m->yerr, dA, F, 1.0 / m->n_div);
+                     m->sscale, m->yerr, m->ycov, dA, F, 1.0 / m->n_div);
   hipLaunchKernelGGL(lik_setup_kernel, dim3((unsigned)m->nblk), dim3(CHOL_THREADS), 0, st, dA, dPT, dZ,
-                     m->comp, m->sscale, m->smean, m->yexp, m->blk_start, m->G, m->g0, m->scal, F,
-                     k, dinfo, LIK_BLOCKED_MIN, m->lik_chains);
+                     m->comp, m->sscale, m->smean, m->yexp, m->srcs, m->blk_start, go, F, dinfo, LIK_BLOCKED_MIN);
   GP_HIP(hipGetLastError());
   int64_t maxnp = 0;
   for (size_t o = 0; o + 1 < hstart.size(); ++o) {
@@ -164,9 +191,9 @@ int launch_lik_setup(gpemu_model *m, const std::vector<int> &hstart, double *dA,
     if (rc == GPEMU_OK) rc = device_trtri_blocked(Ab, Np, Dinv, W, T, st);
     if (rc != GPEMU_OK) break;
     hipLaunchKernelGGL(lik_z_kernel, dim3((unsigned)((nf + 3) / 4)), dim3(256), 0, st, W, Np, nf, f0, F, k, m->comp,
-                       m->sscale, m->smean, m->yexp, dZ, m->lik_chains);
-    hipLaunchKernelGGL(lik_gram_kernel, dim3(1), dim3(1024), 0, st, dZ, Ab, Np, nf, f0, k, (int)o, m->G, m->g0, m->scal,
-                       m->lik_chains, (int)m->nblk);
+                       m->sscale, m->smean, m->yexp, m->srcs, dZ, m->lik_chains, m->n_src);
+    hipLaunchKernelGGL(lik_gram_kernel, dim3(1), dim3(1024), 0, st, dZ, Ab, Np, nf, f0, (int)o, go);
+    if (m->ycov || m->n_src > 0) src_path_count(GPEMU_SRC_PATH_SETUP_BLOCKED);
     if (hipGetLastError() != hipSuccess) { set_error("likelihood_setup: launch failed"); rc = GPEMU_ERR_HIP; }
   }
   if (rc == GPEMU_OK && hipStreamSynchronize(st) != hipSuccess) { set_error("likelihood_setup: sync failed"); rc = GPEMU_ERR_HIP; }

@@ -373,6 +373,11 @@ int gpemu_sampler_create_chains(gpemu_sampler **out, gpemu_model *const *groups,
     GP_ARG(groups[g]->d == groups[0]->d && groups[g]->device == groups[0]->device,
            "groups must share the parameter dimension and the device");
     if (!groups[g]->lik_ready) { set_error("gpemu_likelihood_setup must be called on every group first"); return GPEMU_ERR_STATE; }
+    if (groups[g]->n_src != groups[0]->n_src) {
+      set_error("bad argument: group %d has %d correlated sources, group 0 has %d: set every group up with its columns "
+                "of the same sources", g, groups[g]->n_src, groups[0]->n_src);
+      return GPEMU_ERR_ARG;
+    }
     if (groups[g]->lik_chains != 1 && groups[g]->lik_chains != n_chains) {
       set_error("group %d carries data for %d chains, the sampler has %d", g, groups[g]->lik_chains, n_chains);
       return GPEMU_ERR_STATE;

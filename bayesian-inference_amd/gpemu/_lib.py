@@ -58,7 +58,10 @@ _SIGNATURES = {
     "gpemu_model_cross_validate": (C.c_int, [C.c_void_p, c_i64] + [C.c_void_p] * 6),
     "gpemu_likelihood_setup": (C.c_int, [C.c_void_p] + [C.c_void_p] * 4 + [C.c_double, c_i64, C.c_void_p]),
     "gpemu_likelihood_setup_chains": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_double, c_i64, C.c_void_p]),
+    "gpemu_likelihood_setup_cov": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, c_i64, C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.c_double, c_i64, C.c_void_p]),
     "gpemu_logpost": (C.c_int, [C.c_void_p, c_i64, C.c_void_p, C.c_void_p, C.c_int]),
+    "gpemu_logpost_groups": (C.c_int, [C.c_void_p, C.c_int, c_i64, C.c_void_p, C.c_void_p, C.c_int]),
     "gpemu_logpost_dev": (C.c_int, [C.c_void_p, c_i64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "gpemu_fit_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, c_i64, c_i64, C.c_void_p, C.c_int, C.c_double,
                                    C.c_int, C.c_int, C.c_double]),
@@ -118,6 +121,7 @@ _SIGNATURES = {
     "gpemu_path_counts": (C.c_int, [C.POINTER(c_i64), c_i64]),
     "gpemu_fit_path_counts": (C.c_int, [C.POINTER(c_i64), c_i64]),
     "gpemu_wide_path_counts": (C.c_int, [C.POINTER(c_i64), c_i64]),
+    "gpemu_src_path_counts": (C.c_int, [C.POINTER(c_i64), c_i64]),
     "gpemu_philox4x32": (C.c_int, [C.c_uint32] * 6 + [C.POINTER(C.c_uint32)]),
 }
 

@@ -197,24 +197,51 @@ class DeviceModel:
                                                     ptr(mean), ptr(var), ptr(cv), ptr(vo)))
         return mean, var, cv, vo
 
-    def likelihood_setup(self, y_exp, y_err, lo, hi, n_div=1.0, block_start=None):
+    def likelihood_setup(self, y_exp, y_err, lo, hi, n_div=1.0, block_start=None, cov=None, sys_sources=None):
         """Data, box prior and the observable block boundaries of this group (``block_start`` =
         first feature of each observable plus F at the end; None = a single block).  ``y_exp`` of shape (C, F):
-        one data vector per chain of a multi-chain sampler (closure tests), all against the same ``y_err``."""
+        one data vector per chain of a multi-chain sampler (closure tests), all against the same ``y_err``.
+
+        Correlated uncertainties: ``cov`` (F, F) is the data covariance inside the observable blocks
+        in place of ``diag(y_err**2)`` (zero across blocks); ``sys_sources`` (S, F), S <= 16, are this group's columns
+        of fully correlated systematic sources.  With sources, evaluate all groups together (``logpost_groups``)."""
         y_exp = np.ascontiguousarray(y_exp, dtype=np.float64)
-        if y_exp.ndim == 2:
-            return self._likelihood_setup_chains(y_exp, y_err, lo, hi, n_div, block_start)
-        y_exp = as_f64(y_exp, (self.F,))
+        if cov is None and sys_sources is None:
+            if y_exp.ndim == 2:
+                return self._likelihood_setup_chains(y_exp, y_err, lo, hi, n_div, block_start)
+            y_exp = as_f64(y_exp, (self.F,))
+            y_err = as_f64(y_err, (self.F,))
+            lo = as_f64(lo, (self.d,))
+            hi = as_f64(hi, (self.d,))
+            bs = None
+            nb = 0
+            if block_start is not None:
+                bs = np.ascontiguousarray(block_start, dtype=np.int64)
+                nb = bs.size - 1
+            check(_lib.lib().gpemu_likelihood_setup(self._h, ptr(y_exp), ptr(y_err), ptr(lo), ptr(hi),
+                                                    float(n_div), nb, ptr(bs)))
+            self._lik_key = (float(n_div), None if bs is None else tuple(bs.tolist()))
+            return
+        n_chains = y_exp.shape[0] if y_exp.ndim == 2 else 1
+        y_exp = as_f64(y_exp.reshape(n_chains, -1), (n_chains, self.F))
         y_err = as_f64(y_err, (self.F,))
         lo = as_f64(lo, (self.d,))
         hi = as_f64(hi, (self.d,))
-        bs = None
-        nb = 0
+        covd = None if cov is None else as_f64(cov, (self.F, self.F))
+        S = 0
+        src = None
+        if sys_sources is not None:
+            src = np.ascontiguousarray(sys_sources, dtype=np.float64)
+            if src.ndim != 2 or src.shape[1] != self.F:
+                raise ValueError(f"sys_sources must have shape (S, {self.F}), got {src.shape}")
+            S = src.shape[0]
+        bs, nb = None, 0
         if block_start is not None:
             bs = np.ascontiguousarray(block_start, dtype=np.int64)
             nb = bs.size - 1
-        check(_lib.lib().gpemu_likelihood_setup(self._h, ptr(y_exp), ptr(y_err), ptr(lo), ptr(hi),
-                                                float(n_div), nb, ptr(bs)))
+        check(_lib.lib().gpemu_likelihood_setup_cov(self._h, int(n_chains), ptr(y_exp), ptr(y_err), ptr(covd), int(S),
+                                                    ptr(src) if S > 0 else None, ptr(lo), ptr(hi), float(n_div), nb,
+                                                    ptr(bs)))
         self._lik_key = (float(n_div), None if bs is None else tuple(bs.tolist()))
 
     def _likelihood_setup_chains(self, y_exp, y_err, lo, hi, n_div, block_start):
@@ -256,3 +283,25 @@ class DeviceModel:
     def predict_full_dev(self, dX_ptr, B, n_div, dcv_ptr, dcov_ptr, stream=0):
         check(_lib.lib().gpemu_predict_full_dev(self._h, int(B), C.c_void_p(dX_ptr), float(n_div),
                                                 C.c_void_p(dcv_ptr), C.c_void_p(dcov_ptr), C.c_void_p(stream)))
+
+
+def logpost_groups(models, X, mode=LOWRANK):
+    """log-posterior of the rows of X summed over the emulation groups ``models`` (DeviceModel, one device, one
+    parameter box), evaluated together: the term of correlated sources (``likelihood_setup(sys_sources=...)``) spans
+    the groups, so with sources this is not the sum of the groups' ``logpost``."""
+    models = list(models)
+    if not models:
+        raise ValueError("logpost_groups needs at least one model")
+    X = models[0]._X(X)
+    B = X.shape[0]
+    out = np.empty(B)
+    hs = (C.c_void_p * len(models))(*[m.handle for m in models])
+    check(_lib.lib().gpemu_logpost_groups(hs, len(models), B, ptr(X), ptr(out), int(mode)))
+    return out
+
+
+def src_path_counts():
+    """Counters of enum gpemu_src_path (the correlated-source launches), as an int64 array."""
+    out = np.zeros(8, dtype=np.int64)
+    n = _lib.lib().gpemu_src_path_counts(out.ctypes.data_as(C.POINTER(C.c_int64)), out.size)
+    return out[:n].copy()

@@ -146,6 +146,27 @@ int gpemu_likelihood_setup_chains(gpemu_model *m, int n_chains, const double *y_
                                   const double *lo, const double *hi, double n_div, int64_t n_blocks,
                                   const int64_t *block_start);
 
+/* Correlated experimental uncertainties: the data covariance of the group is
+ *     C_d = blockdiag_o(C_o) + sum_{s < n_src} b_s b_s^T
+ * instead of diag(y_err^2).  cov[F*F] (row-major, this group's column order) holds C_o on the observable blocks and
+ * zeros across them (GPEMU_ERR_ARG otherwise); NULL = diag(y_err^2), as gpemu_likelihood_setup_chains.  sources[n_src*F]
+ * are the group's columns of n_src fully correlated systematic sources, 0 <= n_src <= GPEMU_MAX_SOURCES (else
+ * GPEMU_ERR_ARG); a source may span several observables and several groups, so with n_src > 0 the log-posterior of a
+ * set of groups is NOT the sum of the groups' log-posteriors: evaluate them together (gpemu_logpost_groups, or one
+ * sampler over all groups), each group set up with its own columns of the same sources.  With cov = NULL and
+ * n_src = 0 this is gpemu_likelihood_setup_chains, bit for bit.  GPEMU_LOGPOST_EXACT reads cov; with n_src > 0 it
+ * returns GPEMU_ERR_UNSUPPORTED.  The fused sharded run and the peer transport decline sampler groups with n_src > 0
+ * (gpemu_sampler_run_sharded takes the collective transport). */
+#define GPEMU_MAX_SOURCES 16
+int gpemu_likelihood_setup_cov(gpemu_model *m, int n_chains, const double *y_exp, const double *y_err,
+                               const double *cov, int64_t n_src, const double *sources, const double *lo,
+                               const double *hi, double n_div, int64_t n_blocks, const int64_t *block_start);
+
+/* The log-posterior of X[B*d] summed over n_groups models set up on the same device with the same parameter box:
+ * out[B].  Where any group has sources, all must have the same n_src (GPEMU_ERR_STATE otherwise) and their term is
+ * added once for the set.  n_div: each model's current setup. */
+int gpemu_logpost_groups(gpemu_model *const *models, int n_groups, int64_t B, const double *X, double *out, int mode);
+
 /* ref: log_posterior.py:42-101 + 104-146: X[B*d] -> out[B]; rows outside the open box -> -inf.
  * A non-positive-definite covariance yields NaN (the reference does not detect it either,
  * log_posterior.py:125-135). */
@@ -414,6 +435,21 @@ enum gpemu_wide_path {
 };
 /* out[0 .. min(n, GPEMU_WIDE_PATH_COUNT)) = the counters; returns GPEMU_WIDE_PATH_COUNT (or GPEMU_ERR_ARG). */
 int gpemu_wide_path_counts(int64_t *out, int64_t n);
+
+/* The launches of the correlated-source likelihood (gpemu_likelihood_setup_cov).  A set of its own: the sets above keep
+ * their sizes and indices. */
+enum gpemu_src_path {
+  GPEMU_SRC_PATH_CORRECTION = 0,     /* source_correction_kernel: the per-proposal Woodbury term of the sources       */
+  GPEMU_SRC_PATH_SETUP_COV,          /* a likelihood setup that read a dense within-observable covariance            */
+  GPEMU_SRC_PATH_SETUP_SOURCES,      /* a likelihood setup with n_src > 0                                             */
+  GPEMU_SRC_PATH_EXACT_COV,          /* loglik_exact_kernel with a dense within-observable covariance                */
+  GPEMU_SRC_PATH_SETUP_BLOCKED,      /* an observable block of > 256 features, with cov or sources, through the blocked
+                                        setup (lik_z_kernel / lik_gram_kernel)                                        */
+  GPEMU_SRC_PATH_CORRECTION_K64,     /* source_correction_kernel with a group of 33 .. 64 PCs (over 64 KB of LDS)     */
+  GPEMU_SRC_PATH_COUNT
+};
+/* out[0 .. min(n, GPEMU_SRC_PATH_COUNT)) = the counters; returns GPEMU_SRC_PATH_COUNT (or GPEMU_ERR_ARG). */
+int gpemu_src_path_counts(int64_t *out, int64_t n);
 
 /* ---- fit handle: test-only entry points ---------------------------------------------------------------------------
  * For the tests of the fit side only; nothing in the library's own flow calls them.
