@@ -22,11 +22,13 @@ import numpy as np
 
 import fit_ref as FR
 from oracle import gp_oracle as O
+from path_cases import DPAD
 
 # enum gpemu_fit_path (include/gpemu.h), read through gpemu_fit_path_counts
 FIT_PATHS = ["FIT_KMAT", "FIT_KMAT_NU", "CHOL_PANEL", "CHOL_STEPS", "CHOL_LOOKAHEAD", "CHOL_HEADS_ONE_XCD", "TRTRI_RAGGED",
              "FIT_GRAD", "FIT_GRAD_NU", "FIT_BATCH"]
 FIT_PATH = {n: i for i, n in enumerate(FIT_PATHS)}
+# the 16-wide instances of d = 9 .. 16 count in gpemu_wide_path_counts (tests/path_cases.WIDE_PATHS), not above
 
 NB, CHOL_Q, PANEL_MAX_WG, LA_MIN = 64, 4, 320, 40
 R, M = O.RBF, O.MATERN
@@ -87,6 +89,15 @@ def cases():
                 full=False),
         FitCase("n3300_rbf_lookahead", 3300, 6, R, np.inf, True, True, env={"GPEMU_CHOL_HEADS_ONE_XCD": "0"},
                 full=False),
+        # 9 .. 16 parameters: kmat_kernel<16, ..> and lml_grad_kernel<16, ..>
+        FitCase("w9_n130_m15_dup", 130, 9, M, 1.5, True, True, design="dup"),
+        FitCase("w12_n320_nu07_ragged", 320, 12, M, 0.7, False, True),
+        FitCase("w12_n129_m25_lsb", 129, 12, M, 2.5, True, True, design="ls_bounds"),
+        FitCase("w16_n200_rbf_lsb_steps", 200, 16, R, np.inf, True, True, design="ls_bounds",
+                env={"GPEMU_CHOL_PANEL": "0"}),
+        # (noise 1e-5 beside near-duplicates: the gradient's bound is wide here, so that even all eight wide gradient
+        # components dropped stay inside it -- this case covers the wide kernel matrix, not the wide gradient)
+        FitCase("w16_n257_m05_dup", 257, 16, M, 0.5, True, True, design="dup"),
     ]
 
 
@@ -155,12 +166,23 @@ def ragged_merges(N):
 
 
 def fit_paths(c: FitCase, nb=1, grad=True, env=None):
-    """exact counter increments of one fit evaluation (gpemu_fit_lml / _lml_batch / _factor) of nb problems"""
+    """exact counter increments of one fit evaluation (gpemu_fit_lml / _lml_batch / _factor) of nb problems; the keys
+    WIDE_FIT_KMAT / WIDE_FIT_GRAD are gpemu_wide_path_counts' FIT_KMAT / FIT_GRAD"""
     env = c.env if env is None else env
-    out = {"FIT_KMAT_NU" if c.general_nu else "FIT_KMAT": 1, "FIT_KMAT" if c.general_nu else "FIT_KMAT_NU": 0}
+    out = kmat_paths(c)
     out.update(chol_paths(c.N, nb, env))
     out["TRTRI_RAGGED"] = ragged_merges(c.N)
-    out["FIT_GRAD_NU" if c.general_nu else "FIT_GRAD"] = 1 if grad else 0
+    wide = c.d > DPAD
+    out["FIT_GRAD_NU" if c.general_nu else "FIT_GRAD"] = 1 if grad and not wide else 0
     out["FIT_GRAD" if c.general_nu else "FIT_GRAD_NU"] = 0
+    out["WIDE_FIT_GRAD"] = 1 if grad and wide else 0
     out["FIT_BATCH"] = 1 if nb > 1 else 0
+    return out
+
+
+def kmat_paths(c: FitCase):
+    """exact counter increments of one kernel-matrix launch: 8-wide by kind, or the 16-wide instance"""
+    wide = c.d > DPAD
+    out = {"FIT_KMAT_NU" if c.general_nu else "FIT_KMAT": 0 if wide else 1, "FIT_KMAT" if c.general_nu else "FIT_KMAT_NU": 0}
+    out["WIDE_FIT_KMAT"] = 1 if wide else 0
     return out

@@ -38,8 +38,15 @@ order, componentwise, computed in float64 on absolute values; only the reference
   ``delta = (d + 8) u r^2`` (the device's ``(x - x')^2 / l^2`` per dimension, ``G_t = f(r^2) D_t``), and ``u`` of
   ``G_t`` for the constant and the noise.
 
-Constants, fixed once from the algorithm: ``C_X = 8``, ``EPS_K = 8 u`` (closed forms: at most seven roundings of
-positive terms and a correctly rounded-to-1-ulp exponential), ``EPS_BESSEL = 2e-14`` (hp_ref.py).
+Constants, fixed once from the algorithm: ``EPS_K = 8 u`` (closed forms: at most seven roundings of positive terms and
+a correctly rounded-to-1-ulp exponential), ``EPS_BESSEL = 2e-14`` (hp_ref.py), and ``C_X = c_x(d)``:
+
+``kmat_kernel<DP, ..>`` (k_fit.hip) sums ``fma(df, df, r2)`` serially over the DP = 8 or 16 padded coordinates.  A
+padded coordinate has ``df = 0`` and its fma is exact, so d terms are rounded, each once.  ``C_X8 = 8`` was set for the
+8-wide instance, whose sums have at most 8 terms; the first-order worst-case error of a sum grows linearly in its
+length (``gamma_n ~ n u``, Higham ch. 3), so ``c_x(d) = C_X8 max(d, 8) / 8 = max(d, 8)``: exactly 8 for d <= 8, 16
+for the 16 squared differences at d = 16 (the rule of ``hp_ref.c_x_direct``).  The gradient's ``delta`` above already
+counts its d terms.
 """
 from __future__ import annotations
 
@@ -56,13 +63,18 @@ LD = np.longdouble
 assert np.finfo(LD).eps < 1e-18, "tests/fit_ref.py needs an extended np.longdouble (x87 80-bit or better)"
 
 U = 2.0 ** -53
-C_X = 8.0
+C_X8 = 8.0
 EPS_K = 8 * U
 EPS_BESSEL = H.EPS_BESSEL
 
 
 def g(n):
     return (n + 64) * U
+
+
+def c_x(d):
+    """the kernel matrix's distance factor of d parameters (module docstring)"""
+    return C_X8 * max(d, 8) / 8
 
 
 def general_nu(spec):
@@ -103,7 +115,7 @@ def kernel_rows(p, rows):
     a = np.abs(X / ls)
     df = np.abs(np.asarray(diff, dtype=np.float64))
     r2f = np.asarray(r2, dtype=np.float64)
-    delta = C_X * U * (np.einsum("rjd,rjd->rj", a[rows][:, None, :] + a[None, :, :], df) + r2f)
+    delta = c_x(X.shape[1]) * U * (np.einsum("rjd,rjd->rj", a[rows][:, None, :] + a[None, :, :], df) + r2f)
     k64 = np.asarray(K, dtype=np.float64)
     dK = np.maximum(np.abs(H._base64(r2f - delta, p.spec) - k64), np.abs(H._base64(r2f + delta, p.spec) - k64))
     dK += p.eps_k * np.abs(k64)

@@ -18,11 +18,13 @@ is still extended).  Its relative error is budgeted in ``EPS_BESSEL`` below, wit
 Error bound.  ``u = 2^-53``.  A running error analysis of the device's algorithm, as the same sums in absolute values:
 
 - cross-kernel entry ``k_j``:  the device forms r^2 by the expanded, centred form ``|q~|^2 + |x~_j|^2 - 2 q~.x~_j``
-  (``kstar_host.h``, ``predict_dev.h``), whose absolute error is ``C_X u (|q~|^2 + |x~_j|^2)``.  It moves the kernel by
+  (``kstar_host.h``, ``predict_dev.h``), whose absolute error is ``C_X u (|q~|^2 + |x~_j|^2)`` (plus the rounding of
+  the inputs, see "Limit" below).  It moves the kernel by
   at most ``|k(r^2 +- delta) - k(r^2)|`` (the kernel is monotone in r).  Pairs the device measures by the direct
-  distance (Matern 0.5, nu < 1, ``r^2 < 1e-7 (|q~|^2 + 1)``) have ``delta_r = C_X u sum_i (|q_i| + |x_ji|) / ls_i``
+  distance (Matern 0.5, nu < 1, ``r^2 < 1e-7 (|q~|^2 + 1)``) have ``delta_r = C_Xd u sum_i (|q_i| + |x_ji|) / ls_i``
   instead.  On top: the evaluation of the kernel, ``EPS_EXP |k|`` (table exponential, closed forms) or
-  ``EPS_BESSEL |k|`` (general nu), and the constant term's addition ``u (|k| + const)``.  Call this ``dk_j``.
+  ``EPS_BESSEL |k|`` (general nu), the exponential's clamp at -700 (closed forms: ``prefactor(t) e^-700`` where the
+  argument is below it, ~1e-304), and the constant's addition ``u (|k| + const)``.  Call this ``dk_j``.
 - mean:  ``C_M u sum_j |k_j||alpha_j| + sum_j dk_j |alpha_j|``.
 - variance:  with ``W = L^-1`` (device: inverted once), ``a = |W||k|`` and ``b = |W||L||W||k|`` (the componentwise error
   of a triangular inverse, Higham, Accuracy and Stability, ch. 8), ``V`` the exact product:
@@ -34,7 +36,38 @@ Error bound.  ``u = 2^-53``.  A running error analysis of the device's algorithm
   setup and of the walker's k x k matrix).  An absolute bound, not a fraction of ``|lp|``.
 
 Constants, chosen once for every shape (the depth of the device's summation trees is at most a few dozen levels):
-``C_X = 8``, ``C_M = 64``, ``C_V = 64``, ``C_L = 64``, ``EPS_EXP = 4 u``, ``EPS_BESSEL = 2e-14``.
+``C_M = 64``, ``C_V = 64``, ``C_L = 64``, ``EPS_EXP = 4 u``, ``EPS_BESSEL = 2e-14``; ``C_X = c_x(d)`` and
+``C_Xd = c_x_direct(d)`` depend on the number of parameters, as follows.
+
+The distance factors.  ``C_X8 = 8`` was set for the 8-wide instances (d <= 8) and covers their longest sums: the
+d + 1 = 9 rounded product-adds of the d = 8 product and the 8 squared differences of the direct distance.  The
+first-order worst-case error of a sum of n rounded terms is ``gamma_n ~ n u`` times the sum of the absolute terms
+(Higham, Accuracy and Stability, ch. 3), linear in n, so a longer sum scales the factor by the ratio of the counts:
+
+- expanded form: ``r^2 = fma(acc, -2, |q'|^2)``.  ``acc`` is a chain of KS = ``kstar_ksteps(d)`` MFMA k-steps
+  (``kstar_tile_product``) of 4 product-adds each; ``|q'|^2`` is, per lane, a chain of at most KS fmas over the
+  components 4 s + (lane >> 4) and then two cross-lane adds (``kstar_mfma_block``), at most KS + 2 <= 7 roundings.
+  Rounding assumption for the f64 MFMA: one rounding per product-add, in an order that is not documented.  A padded
+  slot adds an exact zero, which a rounding leaves exact, so of the 4 KS slots the d + 1 that hold a coordinate or
+  the training row's -1/2 |x'|^2 are rounded, whatever KS is; the |q'|^2 chain is never longer.  Then
+  ``c_x(d) = C_X8 max(d + 1, 9) / 9``: 8 for d <= 8, 80/9 at d = 9, 128/9 at d = 15 and 136/9 at d = 16.
+- direct distance: ``kstar_direct_r2<DP>`` sums ``fma(df, df, r2)`` serially over the DP = 8 or 16 padded
+  coordinates; a padded coordinate has ``df = 0``, whose fma is exact, so d terms are rounded:
+  ``c_x_direct(d) = C_X8 max(d, 8) / 8 = max(d, 8)``.
+
+Both are exactly 8 for d <= 8, so every bound of the 8-wide instances is the one it was.  A caller that wants the
+8-wide factor at d > 8 passes ``cx=C_X8``.
+
+Limit: the rounding of the inputs.  ``C_X u (|q~|^2 + |x~_j|^2)`` counts the roundings of the product and of the sums,
+measured in the centred coordinates.  The centred operands are themselves rounded from the uncentred scaled ones:
+the query's ``fma(q, s / ls, -s c)`` with both constants rounded on the host, the training row's ``(X / ls - c) s``.
+That moves ``q~ - x~_j`` by up to ``u (|q / ls| + |X_j / ls| + |c| + |q~| + 2 |x~_j|)`` per coordinate, and r^2 by
+twice its product with ``|q~ - x~_j|``.  Where a length scale is small against the coordinates' distance from the
+origin (sklearn's lower bound 1e-5: ``|q / ls| ~ 1e5`` while ``|q~ - x~_j|`` stays O(1) for near pairs) this term
+dominates: without it the float64 oracle leaves the bound (err/bound up to 11 on the 8-wide shapes), and the
+device rounds the same inputs.  ``input_rounding=True``
+adds it.  It is off by default so that the bounds the sweep was calibrated with stay as they were; a case with
+``path_cases.Case.ls_bounds`` must turn it on.
 """
 from __future__ import annotations
 
@@ -50,9 +83,24 @@ LD = np.longdouble
 assert np.finfo(LD).eps < 1e-18, "tests/hp_ref.py needs an extended np.longdouble (x87 80-bit or better)"
 
 U = 2.0 ** -53
-C_X, C_M, C_V, C_L = 8.0, 64.0, 64.0, 64.0
+C_X8, C_M, C_V, C_L = 8.0, 64.0, 64.0, 64.0
 EPS_EXP = 4 * U
 EPS_BESSEL = 2e-14
+
+
+def kstar_ksteps(d):
+    """MFMA k-steps of the cross-kernel for d parameters (kstar_host.h: kstar_ksteps)"""
+    return 2 if d + 1 <= 8 else (d + 4) // 4
+
+
+def c_x(d):
+    """the expanded-form distance factor of d parameters (module docstring): C_X8 max(d + 1, 9) / 9"""
+    return C_X8 * max(d + 1, 9) / 9
+
+
+def c_x_direct(d):
+    """the direct-distance factor of d parameters (module docstring): C_X8 max(d, 8) / 8"""
+    return C_X8 * max(d, 8) / 8
 
 
 def _is_direct(spec):
@@ -86,9 +134,26 @@ def _base64(r2, spec):
     return np.asarray(_base_ld(np.asarray(np.maximum(r2, 0.0), dtype=LD), spec), dtype=np.float64)
 
 
-def kstar(Xq, X_train, gp, spec):
-    """longdouble K_* [B, N] and its error bound dk [B, N] (module docstring)"""
+def _clamp_floor(r2, spec):
+    """what the closed forms' exponential returns where it clamps: exp2_scaled4 (predict_dev.h) takes arguments below
+    -700 (natural units) as -700, so there the device gives prefactor(t) e^-700 (~1e-304 times the prefactor) where
+    the kernel is ~0.  An absolute term of dk (0 for general nu, whose Bessel routine does not clamp)"""
+    if spec.kind == O.MATERN and spec.nu not in (0.5, 1.5, 2.5) and not np.isinf(spec.nu):
+        return np.zeros_like(r2)
+    if spec.kind == O.RBF or np.isinf(spec.nu):
+        a, pref = r2 / 2, np.ones_like(r2)
+    else:
+        a = np.sqrt(r2) * {0.5: 1.0, 1.5: math.sqrt(3.0), 2.5: math.sqrt(5.0)}[spec.nu]
+        pref = 1 + a if spec.nu == 1.5 else 1 + a + a * a / 3 if spec.nu == 2.5 else np.ones_like(r2)
+    return np.where(a > 700.0, pref * math.exp(-700.0) * (1 + 16 * U), 0.0)
+
+
+def kstar(Xq, X_train, gp, spec, cx=None, input_rounding=False):
+    """longdouble K_* [B, N] and its error bound dk [B, N] (module docstring); cx: one distance factor for both forms
+    instead of c_x(d) and c_x_direct(d); input_rounding: add the rounding of the centred inputs (module docstring)"""
     ls = np.asarray(gp.ls, dtype=np.float64)
+    d = X_train.shape[1]
+    cx, cxd = (c_x(d), c_x_direct(d)) if cx is None else (cx, cx)
     q = Xq.astype(LD) / ls.astype(LD)
     x = X_train.astype(LD) / ls.astype(LD)
     diff = q[:, None, :] - x[None, :, :]
@@ -103,19 +168,23 @@ def kstar(Xq, X_train, gp, spec):
     nx = np.sum(xt * xt, axis=1)
     r2f = np.asarray(r2, dtype=np.float64)
     k64 = np.asarray(K, dtype=np.float64)
-    d2 = C_X * U * (nq[:, None] + nx[None, :])
+    d2 = cx * U * (nq[:, None] + nx[None, :])
+    if input_rounding:
+        aq = np.abs(Xq / ls) + np.abs(cen) + np.abs(qt)
+        ax = np.abs(u) + 2 * np.abs(xt)
+        d2 = d2 + 2 * U * np.einsum("bnd,bnd->bn", np.abs(qt[:, None, :] - xt[None, :, :]), aq[:, None, :] + ax[None, :, :])
     dk = np.maximum(np.abs(_base64(r2f - d2, spec) - k64), np.abs(_base64(r2f + d2, spec) - k64))
     if _is_direct(spec):
         near = r2f < 2e-7 * (nq[:, None] + 1.0)
         if np.any(near):
             rr = np.sqrt(r2f)
-            dr = C_X * U * (np.abs(Xq / ls).sum(axis=1)[:, None] + np.abs(u).sum(axis=1)[None, :])
+            dr = cxd * U * (np.abs(Xq / ls).sum(axis=1)[:, None] + np.abs(u).sum(axis=1)[None, :])
             ddir = np.maximum(np.abs(_base64((rr + dr) ** 2, spec) - k64),
                               np.abs(_base64(np.maximum(rr - dr, 0.0) ** 2, spec) - k64))
             strictly = r2f < 0.5e-7 * (nq[:, None] + 1.0)
             dk = np.where(strictly, ddir, np.where(near, np.maximum(dk, ddir), dk))
     eps = EPS_BESSEL if (spec.kind == O.MATERN and spec.nu not in (0.5, 1.5, 2.5) and not np.isinf(spec.nu)) else EPS_EXP
-    dk = dk + eps * np.abs(k64)
+    dk = dk + eps * np.abs(k64) + _clamp_floor(r2f + d2, spec)
     if spec.has_const:
         K = K + LD(gp.const)
         dk = dk + U * (np.abs(k64) + gp.const)
@@ -134,8 +203,8 @@ def forward_subst(L, B):
 class PCRef:
     """the reference of one PC for B queries: mean, var (longdouble) and their bounds (float64); V kept for tests"""
 
-    def __init__(self, Xq, X_train, gp, spec):
-        K, dk = kstar(Xq, X_train, gp, spec)
+    def __init__(self, Xq, X_train, gp, spec, cx=None, input_rounding=False):
+        K, dk = kstar(Xq, X_train, gp, spec, cx, input_rounding)
         self.K, self.dk = K, dk
         self.mean = K @ np.asarray(gp.alpha, dtype=LD)
         V = forward_subst(gp.L, K.T.astype(LD))
@@ -157,9 +226,9 @@ class PCRef:
                           + 2 * np.sum(Vf * (aW @ dk.T), axis=0))
 
 
-def gp_predict(Xq, model):
+def gp_predict(Xq, model, cx=None, input_rounding=False):
     """(mean, var) [B, k] longdouble and (mean_bound, var_bound) [B, k] float64; the PCRef objects"""
-    pcs = [PCRef(Xq, model.X_train, gp, model.spec) for gp in model.gps]
+    pcs = [PCRef(Xq, model.X_train, gp, model.spec, cx, input_rounding) for gp in model.gps]
     mean = np.stack([p.mean for p in pcs], axis=1)
     var = np.stack([p.var for p in pcs], axis=1)
     mb = np.stack([p.mean_bound for p in pcs], axis=1)
@@ -265,9 +334,10 @@ def loglik_bound(m, var, mb, vb, setups):
     return bound
 
 
-def log_posterior(Xq, model, lo, hi, y_exp, y_err, block_start, n_div=1.0, cov_unexpl=None, pred=None):
+def log_posterior(Xq, model, lo, hi, y_exp, y_err, block_start, n_div=1.0, cov_unexpl=None, pred=None,
+                  input_rounding=False):
     """(lp [B] longdouble with -inf outside the open box, bound [B] float64); pred: gp_predict(Xq, model) if at hand"""
-    mean, var, mb, vb, _ = pred if pred is not None else gp_predict(Xq, model)
+    mean, var, mb, vb, _ = pred if pred is not None else gp_predict(Xq, model, input_rounding=input_rounding)
     setups = lowrank_setup_blocks(model, y_exp, y_err, block_start, n_div, cov_unexpl)
     lp, _, _, _ = loglik_blocks(mean, var, setups)
     bound = loglik_bound(mean, var, mb, vb, setups)

@@ -1,7 +1,8 @@
 """The launch-path sweep (tests only): a table of cases, each there for a path of the predict / likelihood pipeline, the
 models and adversarial queries they run on, and the paths the host dispatch must take for them (mirrored from
 csrc/gpemu_api.hip, k_predict.hip, k_trmm_small.hip, k_halfstep.hip and k_loglik.hip).  Shared by the CPU tests of the
-extended-precision reference (test_hp_ref_host.py) and the GPU sweep (test_gpu_paths.py)."""
+extended-precision reference (test_hp_ref_host.py) and the GPU sweep (test_gpu_paths.py).  The cases of 9 to 16
+parameters run the 16-wide instances; wide_paths gives the exact increments of their counters (gpemu_wide_path_counts)."""
 from __future__ import annotations
 
 import math
@@ -19,6 +20,10 @@ PATHS = ["KSTAR_SMALL", "KSTAR_BIG", "KSTAR_KSTEPS2", "KSTAR_KSTEPS3", "KSTAR_DI
          "HALFSTEP_SMALL", "HALFSTEP_GENERAL", "LOGLIK_LOWRANK", "LOGLIK_GROUPS", "LOGLIK_TASKS_ONE",
          "LOGLIK_TASKS_MULTI", "LOGLIK_TASKS_MULTI_BIG", "PREDICT_PASS"]
 PATH = {n: i for i, n in enumerate(PATHS)}
+# enum gpemu_wide_path (include/gpemu.h): the 16-wide instances (d = 9 .. 16), read through gpemu_wide_path_counts
+WIDE_PATHS = ["KSTAR_KSTEPS3", "KSTAR_KSTEPS4", "KSTAR_KSTEPS5", "FIT_KMAT", "FIT_GRAD"]
+WIDE_PATH = {n: i for i, n in enumerate(WIDE_PATHS)}
+DPAD = 8
 
 EDGE_ROWS = (0, 15, 16, 31, 32, 63, 64, 127, 128, 255, 256)
 EDGE_COLS = (0, 31, 32, 63, 64, 127, 128)
@@ -41,6 +46,10 @@ class Case:
     const: bool
     nblk: int = 1
     F: int = 0           # 0: k + 3 (at least nblk)
+    # length scale 1e-5 on coordinate 0 and 1e5 on coordinate d - 1 (problem()).  The reference of such a case needs
+    # hp_ref's input_rounding=True: without it the bound leaves out the rounding of the uncentred scaled coordinates,
+    # which dominates at ls = 1e-5 (hp_ref docstring, "Limit")
+    ls_bounds: bool = False
 
     @property
     def spec(self):
@@ -80,6 +89,16 @@ def cases(num_cu=256):
         Case("small_36", n36, 6, 10, 128, R, np.inf, False, nblk=2),
         Case("small_leftover", nleft, 3, 1, 128, M, 1.5, False),
         Case("n100_blocks65_fallback", 100, 2, 4, 64, R, np.inf, False, nblk=65, F=70),
+        # 9 .. 16 parameters: rows padded to 16, 3 .. 5 MFMA k-steps; shapes fixed (no CU count), every special fits
+        Case("w9_ks3_m05_small_lowrank", 40, 9, 3, 100, M, 0.5, False),
+        Case("w11_ks3_rbf_const_big_tasks_one", 130, 11, 4, 200, R, np.inf, True, nblk=3),
+        Case("w12_ks4_nu075_direct_tasks_multi", 64, 12, 5, 128, M, 0.75, False, nblk=6),
+        Case("w15_ks4_m25_big_dma", 100, 15, 3, 160, M, 2.5, False),
+        Case("w16_ks5_m15_pieces_tasks_big", 200, 16, 4, 768, M, 1.5, False, nblk=8),
+        Case("w16_ks5_m05_direct_small", 50, 16, 2, 96, M, 0.5, False),
+        Case("w16_ks5_rbf_const_two_passes", 60, 16, 2, 2100, R, np.inf, True, nblk=2),
+        Case("w13_ks4_m15_lsb_big", 90, 13, 3, 150, M, 1.5, False, ls_bounds=True),
+        Case("w10_ks3_m05_lsb_direct_small", 48, 10, 2, 80, M, 0.5, False, ls_bounds=True),
     ]
 
 
@@ -114,7 +133,8 @@ def predict_paths(c, num_cu):
     for off in range(0, c.B, MAX_CHUNK):
         nb = min(MAX_CHUNK, c.B - off)
         out.add("KSTAR_SMALL" if nb <= KSTAR_SMALL_MAX else "KSTAR_BIG")
-        out.add("KSTAR_KSTEPS2" if c.d + 1 <= 8 else "KSTAR_KSTEPS3")
+        if c.d <= DPAD:                                     # 16-wide instances: wide_paths
+            out.add("KSTAR_KSTEPS2" if c.d + 1 <= 8 else "KSTAR_KSTEPS3")
         if c.kind == O.MATERN and c.nu < 1.0:
             out.add("KSTAR_DIRECT")
         n = math.ceil(nb / 512)
@@ -128,6 +148,26 @@ def predict_paths(c, num_cu):
         else:
             out.add("TRMM_DMA_WHOLE")
             _trmm_dma(c, nb, num_cu, out)
+    return out
+
+
+def kstar_ksteps(d):
+    """MFMA k-steps of the cross-kernel (kstar_host.h: kstar_ksteps)"""
+    return 2 if d + 1 <= 8 else (d + 4) // 4
+
+
+def wide_paths(c):
+    """exact increments of gpemu_wide_path_counts and of the 8-wide KSTAR_KSTEPS2 / 3 counters in one gp_predict, or
+    one logpost (mode 0), of B rows: one cross-kernel launch per pass of MAX_CHUNK rows, counted by its width and
+    k-steps (k_predict.hip: kstar_count)"""
+    passes = math.ceil(c.B / MAX_CHUNK)
+    out = {"WIDE_" + p: 0 for p in WIDE_PATHS}
+    out["KSTAR_KSTEPS2"] = out["KSTAR_KSTEPS3"] = 0
+    ks = kstar_ksteps(c.d)
+    if c.d > DPAD:
+        out[f"WIDE_KSTAR_KSTEPS{ks}"] = passes
+    else:
+        out[f"KSTAR_KSTEPS{ks}"] = passes
     return out
 
 
@@ -149,8 +189,10 @@ def logpost_paths(c, num_cu):
 
 
 # ---- models and queries --------------------------------------------------------------------------------------------------
-def problem(c, seed=0):
-    """(model, lo, hi, y_exp, y_err, block_start, rng): noise >= 1e-2 in every PC"""
+def problem(c, seed=0, ls_bounds=None):
+    """(model, lo, hi, y_exp, y_err, block_start, rng): noise >= 1e-2 in every PC.  ls_bounds (default: the case's):
+    every PC's length scale of coordinate 0 at 1e-5 and of coordinate d - 1 at 1e5, sklearn's default bounds"""
+    ls_bounds = c.ls_bounds if ls_bounds is None else ls_bounds
     rng = np.random.default_rng(seed + 7919 * c.N + 104729 * c.k + c.B)
     d = c.d
     lo = rng.uniform(-2.0, 0.0, d)
@@ -168,6 +210,8 @@ def problem(c, seed=0):
     gps = []
     for i in range(k):
         th = [np.log((hi - lo) * rng.uniform(0.3, 1.5, d))]
+        if ls_bounds:
+            th[0][0], th[0][d - 1] = np.log(1e-5), np.log(1e5)
         if c.const:
             th.append(np.log(rng.uniform(0.1, 2.0, 1)))
         th.append(np.log(rng.uniform(1e-2, 5e-2, 1)))
@@ -182,6 +226,21 @@ def problem(c, seed=0):
     return model, lo, hi, y_exp, y_err, block_start, rng
 
 
+def edge_rows(c):
+    return sorted({r for r in EDGE_ROWS if r < c.N} | {c.N - 1})
+
+
+def repeat_cols(c):
+    return sorted({cc for cc in EDGE_COLS if cc < c.B} | {c.B - 1})
+
+
+def special_count(c):
+    """(specials queries() places, free columns it has for them): specials beyond the free columns are dropped, the
+    box-edge walkers of the last coordinates first"""
+    n = 2 * len(edge_rows(c)) + (5 if c.general_nu else 0) + 1 + c.d
+    return n, c.B - len(repeat_cols(c))
+
+
 def queries(c, model, lo, hi, rng):
     """(Xq [B, d], repeat_cols, ref_cols): adversarial queries (training rows at the tile edges, 1e-7 ls beside them,
     the t = 2 switch of the general-nu Bessel routine, far outside the design, one query repeated at the edge columns,
@@ -190,8 +249,7 @@ def queries(c, model, lo, hi, rng):
     ls = model.gps[0].ls
     Xq = rng.uniform(lo, hi, (B, d))
     special = []
-    rows = sorted({r for r in EDGE_ROWS if r < c.N} | {c.N - 1})
-    for r in rows:
+    for r in edge_rows(c):
         special.append(X[r].copy())
         special.append(X[r] + 1e-7 * ls * rng.choice([-1.0, 1.0], d))
     if c.general_nu:
@@ -205,7 +263,7 @@ def queries(c, model, lo, hi, rng):
         q = 0.5 * (lo + hi)
         q[j] = lo[j] if j % 2 == 0 else hi[j]
         special.append(q)
-    rep_cols = sorted({cc for cc in EDGE_COLS if cc < B} | {B - 1})
+    rep_cols = repeat_cols(c)
     q_rep = X[min(c.N - 1, 16)] + 1e-7 * ls
     for cc in rep_cols:
         Xq[cc] = q_rep

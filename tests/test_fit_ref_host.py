@@ -23,7 +23,8 @@ from oracle import gp_oracle as O
 
 LD = np.longdouble
 HOST_SHAPES = ["n17_nu07_noise", "n65_m15_dup", "n129_m25_lsb", "n271_nu07_all", "n273_rbf_dup", "n320_m05_ragged",
-               "n448_nu2_ragged_steps", "n513_rbf_all"]
+               "n448_nu2_ragged_steps", "n513_rbf_all",
+               "w9_n130_m15_dup", "w12_n320_nu07_ragged", "w12_n129_m25_lsb", "w16_n200_rbf_lsb_steps", "w16_n257_m05_dup"]
 
 
 def _case(name):
@@ -154,7 +155,11 @@ def device_sim(p, bug=None):
     Np = FC.rup(N, NB)
     nblk = Np // NB
     xs = X / ls
+    if bug == "kmat_ls_stride8":
+        xs[:, 8:] = X[:, 8:] / ls[:d - 8]
     df = xs[:, None, :] - xs[None, :, :]
+    if bug == "kmat_r2_first8":
+        df = df[:, :, :8]
     k = H._base64(np.sum(df * df, axis=2), p.spec) + (const if p.spec.has_const else 0.0)
     if bug == "jitter_offdiag":
         k = k + p.jitter
@@ -233,6 +238,12 @@ def device_sim(p, bug=None):
                 grad[d] += 0.5 * np.sum(w) * const
             if p.spec.has_noise:
                 grad[-1] += 0.5 * np.sum(w[jj == ll]) * noise
+    if bug == "grad_wide_dropped":
+        grad[8:d] = 0.0
+    if bug == "grad_last_dropped":
+        grad[d - 1] = 0.0
+    if bug == "grad_wide_swapped":
+        grad[[7, 8]] = grad[[8, 7]]
     return out, grad
 
 
@@ -248,6 +259,12 @@ BUGS = {   # injected bug -> the shapes it applies to
     "grad_last_group": lambda c: c.N % 16 != 0,                     # the last partial 16-row group dropped
     "grad_const_group": lambda c: c.const,                          # the constant's term of row group 0 dropped
     "jitter_offdiag": lambda c: True,                               # the jitter added off the diagonal too
+    # 16-wide instances (d > 8)
+    "kmat_r2_first8": lambda c: c.d > 8,                            # r^2 of the kernel matrix over coordinates 0..7
+    "kmat_ls_stride8": lambda c: c.d > 8,                           # coordinate j >= 8 scaled by ls[j - 8]
+    "grad_wide_dropped": lambda c: c.d > 8,                         # the gradient of coordinates 8..d-1 dropped
+    "grad_last_dropped": lambda c: c.d > 8,                         # ... of coordinate d - 1 (ls_bounds: at 1e5)
+    "grad_wide_swapped": lambda c: c.d > 8,                         # coordinates 7 and 8 in each other's slots
 }
 
 
@@ -259,6 +276,23 @@ def _old_catches(ref, out, grad):
     return (rel(out["L"], ref.L) >= 1e-9 or rel(out["alpha"], ref.alpha) >= 1e-7
             or abs(out["lml"] - float(ref.lml)) > 1e-8 * abs(float(ref.lml))
             or np.max(np.abs(grad - g)) > 1e-6 * max(1.0, np.max(np.abs(g))))
+
+
+def _old_wide_catches(p, ref, out, grad):
+    """test_gpu_wide_d.py's tolerances: K 1e-12 of max|K|, LML 1e-9 |lml|, gradient 1e-7 max(1, max|g|) (1e-6 for a
+    general nu)"""
+    g = ref.grad.astype(np.float64)
+    K = np.asarray(ref.K, dtype=np.float64)
+    gtol = 1e-6 if FR.general_nu(p.spec) else 1e-7
+    return (np.max(np.abs(out["K"] - K)) >= 1e-12 * np.max(np.abs(K))
+            or abs(out["lml"] - float(ref.lml)) >= 1e-9 * abs(float(ref.lml))
+            or np.max(np.abs(grad - g)) >= gtol * max(1.0, np.max(np.abs(g))))
+
+
+def test_distance_factor():
+    """kmat_kernel's distance factor: the 8-wide constant for d <= 8, the number of squared differences beyond"""
+    assert all(FR.c_x(d) == FR.C_X8 == 8.0 for d in range(1, 9))
+    assert [FR.c_x(d) for d in (9, 12, 16)] == [9.0, 12.0, 16.0]
 
 
 def test_device_restatement_inside_the_bound_and_every_bug_leaves_it(sweep):
@@ -287,7 +321,9 @@ def test_device_restatement_inside_the_bound_and_every_bug_leaves_it(sweep):
                 continue
             if not max(r.values()) <= 1.0:
                 flagged.append(c.name)
-            if _old_catches(ref, out, grad):
+            if (_old_wide_catches(p, ref, out, grad) if c.d > 8 else _old_catches(ref, out, grad)):
                 old.append(c.name)
-        print(f"{bug}: flagged on {len(flagged)}/{len(shapes)} {flagged}; old tolerances catch {len(old)}/{len(shapes)}")
+        print(f"{bug}: flagged on {len(flagged)}/{len(shapes)} {flagged}; old tolerances catch {len(old)}/{len(shapes)}"
+              + (f"; let through by test_gpu_wide_d.py's: {sorted(set(flagged) - set(old))}"
+                 if all(_case(n).d > 8 for n in shapes) else ""))
         assert shapes and flagged, f"{bug} is not flagged on any shape where it applies ({shapes})"

@@ -13,6 +13,7 @@ import pytest
 
 import fit_cases as FC
 import fit_ref as FR
+import path_cases as PC
 from gpemu import _lib
 from gpemu.fit import DeviceFit, LinAlgError, cholesky, kernel_matrix
 
@@ -22,15 +23,23 @@ LD = np.longdouble
 ENV_KEYS = ("GPEMU_CHOL_PANEL", "GPEMU_CHOL_HEADS_ONE_XCD", "GPEMU_CHOL_LOOKAHEAD")
 
 
+WIDE = ("FIT_KMAT", "FIT_GRAD")    # of enum gpemu_wide_path (path_cases.WIDE_PATHS)
+ALL_PATH = dict(FC.FIT_PATH, **{"WIDE_" + p: len(FC.FIT_PATHS) + i for i, p in enumerate(WIDE)})
+
+
 def counts():
+    """gpemu_fit_path_counts, then gpemu_wide_path_counts' FIT_KMAT and FIT_GRAD (the keys of ALL_PATH)"""
     out = np.zeros(len(FC.FIT_PATHS), dtype=np.int64)
     n = _lib.lib().gpemu_fit_path_counts(out.ctypes.data_as(C.POINTER(C.c_int64)), out.size)
     assert n == len(FC.FIT_PATHS), "enum gpemu_fit_path and tests/fit_cases.FIT_PATHS disagree"
-    return out
+    wide = np.zeros(len(PC.WIDE_PATHS), dtype=np.int64)
+    n = _lib.lib().gpemu_wide_path_counts(wide.ctypes.data_as(C.POINTER(C.c_int64)), wide.size)
+    assert n == len(PC.WIDE_PATHS), "enum gpemu_wide_path and tests/path_cases.WIDE_PATHS disagree"
+    return np.concatenate([out, wide[[PC.WIDE_PATH[p] for p in WIDE]]])
 
 
 def assert_deltas(delta, expected, what):
-    got = {p: int(delta[FC.FIT_PATH[p]]) for p in expected}
+    got = {p: int(delta[ALL_PATH[p]]) for p in expected}
     assert got == expected, f"{what}: path counts {got}, expected {expected}"
 
 
@@ -86,7 +95,7 @@ def test_fit_path_against_extended_reference(c, monkeypatch):
     c0 = counts()
     K = kernel_matrix(p.X, p.theta, c.kind, c.nu, c.const, c.noise, c.jitter)
     d = counts() - c0
-    assert_deltas(d, {"FIT_KMAT_NU" if c.general_nu else "FIT_KMAT": 1}, c.name + " kernel_matrix")
+    assert_deltas(d, FC.kmat_paths(c), c.name + " kernel_matrix")
 
     f = device_fit(c, p)
     c0 = counts()
@@ -130,14 +139,15 @@ def batch_problems(c, n_distinct):
     return ps, bad_theta
 
 
-@pytest.mark.parametrize("nb,N,kind,nu,env", [
-    (3, 129, FC.M, 1.5, {}),
-    (8, 273, FC.R, np.inf, {}),
-    (8, 320, FC.M, 2.0, {"GPEMU_CHOL_PANEL": "0"}),
-    (41, 449, FC.M, 2.5, {}),                      # 41 x 8 blocks > 320: the three-launch steps inside the fit
-], ids=["nb3_n129", "nb8_n273", "nb8_n320_nu2_steps", "nb41_n449_steps"])
-def test_fit_batch_members_against_extended_reference(nb, N, kind, nu, env, monkeypatch):
-    c = FC.FitCase(f"batch{nb}", N, 3, kind, nu, True, True, jitter=0.0)
+@pytest.mark.parametrize("nb,N,kind,nu,env,d", [
+    (3, 129, FC.M, 1.5, {}, 3),
+    (8, 273, FC.R, np.inf, {}, 3),
+    (8, 320, FC.M, 2.0, {"GPEMU_CHOL_PANEL": "0"}, 3),
+    (41, 449, FC.M, 2.5, {}, 3),                   # 41 x 8 blocks > 320: the three-launch steps inside the fit
+    (5, 200, FC.M, 2.5, {}, 16),                   # 16-wide members
+], ids=["nb3_n129", "nb8_n273", "nb8_n320_nu2_steps", "nb41_n449_steps", "nb5_n200_d16"])
+def test_fit_batch_members_against_extended_reference(nb, N, kind, nu, env, d, monkeypatch):
+    c = FC.FitCase(f"batch{nb}", N, d, kind, nu, True, True, jitter=0.0)
     ps, bad_theta = batch_problems(c, 3)
     refs = [FR.FitRef(p) for p in ps]
     bad = nb // 2
@@ -170,7 +180,7 @@ def test_fit_batch_members_against_extended_reference(nb, N, kind, nu, env, monk
         r = check_member(f"batch {nb} member {z}", refs[s], ps[s], Ld, Wd, Kid, lml[z], grad[z])
         for k, v in r.items():
             worst[k] = max(worst.get(k, 0.0), v)
-    print(f"\nRATIOS batch{nb}_n{N} " + " ".join(f"{k}={v:.3g}" for k, v in worst.items()))
+    print(f"\nRATIOS batch{nb}_n{N}_d{d} " + " ".join(f"{k}={v:.3g}" for k, v in worst.items()))
 
 
 @pytest.mark.parametrize("N,kind,nu,env", [

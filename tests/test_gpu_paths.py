@@ -32,6 +32,22 @@ def counts():
     return out
 
 
+def wide_counts():
+    """gpemu_wide_path_counts beside the 8-wide KSTAR_KSTEPS2 / 3 counters: the keys of path_cases.wide_paths"""
+    out = np.zeros(len(PC.WIDE_PATHS), dtype=np.int64)
+    n = _lib.lib().gpemu_wide_path_counts(out.ctypes.data_as(C.POINTER(C.c_int64)), out.size)
+    assert n == len(PC.WIDE_PATHS), "enum gpemu_wide_path and tests/path_cases.WIDE_PATHS disagree"
+    c = counts()
+    got = {"WIDE_" + p: int(v) for p, v in zip(PC.WIDE_PATHS, out)}
+    got.update(KSTAR_KSTEPS2=int(c[PC.PATH["KSTAR_KSTEPS2"]]), KSTAR_KSTEPS3=int(c[PC.PATH["KSTAR_KSTEPS3"]]))
+    return got
+
+
+def assert_wide(w0, expected, what):
+    got = {p: v - w0[p] for p, v in wide_counts().items()}
+    assert got == expected, f"{what}: k-step / wide counts {got}, expected {expected}"
+
+
 def num_cu():
     import torch
     return torch.cuda.get_device_properties(0).multi_processor_count
@@ -64,12 +80,13 @@ def test_path_against_extended_reference(idx):
     dm = GU.device_model(model)
     dm.likelihood_setup(y_exp, y_err, lo, hi, 1.0, block_start=bs)
     X = Xq[cols]
-    mean, var, mb, vb, _ = pred = H.gp_predict(X, model)
+    mean, var, mb, vb, _ = pred = H.gp_predict(X, model, input_rounding=c.ls_bounds)
     lp, lb, _ = H.log_posterior(X, model, lo, hi, y_exp, y_err, bs, pred=pred)
 
-    c0 = counts()
+    c0, w0 = counts(), wide_counts()
     m, v = dm.gp_predict(Xq)
     d_pred = counts() - c0
+    assert_wide(w0, PC.wide_paths(c), c.name + " gp_predict")
     assert_paths(d_pred, PC.predict_paths(c, ncu), c.name + " gp_predict")
     assert d_pred[PC.PATH["PREDICT_PASS"]] == math.ceil(c.B / PC.MAX_CHUNK)
     ratios = {"mean": within("mean", m[cols], mean, mb), "var": within("var", v[cols], var, vb)}
@@ -80,9 +97,11 @@ def test_path_against_extended_reference(idx):
     for a in (m, v):
         assert np.array_equal(a[same], np.broadcast_to(a[same[0]], a[same].shape)), "repeated query differs across columns"
 
-    c0 = counts()
+    c0, w0 = counts(), wide_counts()
     out0 = dm.logpost(Xq, mode=0)
     d_lp = counts() - c0
+    if c.d > PC.DPAD:                      # (8-wide: the small half-step forms K_* without the cross-kernel launch)
+        assert_wide(w0, PC.wide_paths(c), c.name + " logpost")
     assert_paths(d_lp, PC.logpost_paths(c, ncu), c.name + " logpost")
     out1 = dm.logpost(Xq, mode=1)
     lp64 = np.asarray(lp, dtype=np.float64)
@@ -108,26 +127,26 @@ def test_path_against_extended_reference(idx):
     dg_b = vbr @ ac2 + 16 * H.U * (np.asarray(vr, float) @ ac2 + np.abs(np.asarray(cu, float)) * model.scaler_scale ** 2)
     ratios["cv"] = within("predict_full central value", cv, cv_ref, cv_b)
     ratios["cov"] = within("predict_full cov diagonal", np.diagonal(cov, axis1=1, axis2=2), dg_ref, dg_b)
-    print(f"{c.name}: err/bound " + " ".join(f"{n} {r:.3g}" for n, r in ratios.items()))
+    print(f"\nRATIOS {c.name} " + " ".join(f"{n}={r:.3g}" for n, r in ratios.items()))
     dm.close()
 
 
-def _sampler_models(ng, seed):
-    """ng single-block groups over the same parameters (one kernel), set up for the sampler"""
+def _sampler_models(ng, seed, d=3):
+    """ng single-block groups over the same d parameters (one kernel), set up for the sampler"""
     out = []
     for g in range(ng):
-        c = PC.Case(f"g{g}", 40 + 7 * g, 3, 3 + g % 3, 64, O.MATERN, 1.5, g % 2 == 1)
+        c = PC.Case(f"g{g}", 40 + 7 * g, d, 3 + g % 3, 64, O.MATERN, 1.5, g % 2 == 1)
         model, lo, hi, y_exp, y_err, bs, _ = PC.problem(c, seed=seed)
         out.append((model, y_exp, y_err, bs))
-    lo, hi = np.full(3, -2.0), np.full(3, 3.5)
+    lo, hi = np.full(d, -2.0), np.full(d, 3.5)
     return out, lo, hi
 
 
-@pytest.mark.parametrize("ng", [3, 8])
-def test_groups_kernel_in_the_sampler(ng):
-    """several groups (up to LL_GROUPS_MAX = 8) in one likelihood launch: loglik_groups_kernel; the state's
-    log-probabilities against the sum of the groups' references"""
-    groups, lo, hi = _sampler_models(ng, seed=ng)
+def _groups_in_the_sampler(ng, d):
+    """the state after 3 steps within the summed bounds; at d > 8 a quarter of the walkers start beside the upper box
+    edge on the coordinates >= 8 only, so that stretch proposals leave the box there and nowhere else, and the whole
+    chain must stay inside the box (with finite log-probabilities)"""
+    groups, lo, hi = _sampler_models(ng, seed=ng, d=d)
     dms = []
     for model, y_exp, y_err, bs in groups:
         dm = GU.device_model(model)
@@ -135,26 +154,45 @@ def test_groups_kernel_in_the_sampler(ng):
         dms.append(dm)
     W = 64
     rng = np.random.default_rng(5)
-    X0 = rng.uniform(-1.0, 1.0, (W, 3))
+    X0 = rng.uniform(-1.0, 1.0, (W, d))
+    if d > PC.DPAD:
+        X0[: W // 4, PC.DPAD:] = hi[PC.DPAD:] - rng.uniform(0.01, 0.1, (W // 4, d - PC.DPAD))
     ds = DeviceSampler(dms, W, seed=11)
     c0 = counts()
     ds.set_state(X0)
     ds.run(3)
     assert counts()[PC.PATH["LOGLIK_GROUPS"]] > c0[PC.PATH["LOGLIK_GROUPS"]]
+    chain, lps = ds.get_chain()
+    assert np.all((chain > lo) & (chain < hi)) and np.all(np.isfinite(lps)), "a walker left the box"
     X, lpd = ds.get_state()
     tot, bnd = np.zeros(W, dtype=LD), np.zeros(W)
     for model, y_exp, y_err, bs in groups:
         lp, lb, _ = H.log_posterior(X, model, lo, hi, y_exp, y_err, bs)
         tot += lp
         bnd += lb
-    within(f"{ng}-group sampler state", lpd, tot, bnd)
+    r = within(f"{ng}-group sampler state (d = {d})", lpd, tot, bnd)
     ds.close()
     for dm in dms:
         dm.close()
+    return r
 
 
-def _blocks10():
-    c = PC.Case("blocks10", 300, 3, 5, 512, O.RBF, np.inf, False, nblk=10)
+@pytest.mark.parametrize("ng", [3, 8])
+def test_groups_kernel_in_the_sampler(ng):
+    """several groups (up to LL_GROUPS_MAX = 8) in one likelihood launch: loglik_groups_kernel; the state's
+    log-probabilities against the sum of the groups' references"""
+    _groups_in_the_sampler(ng, 3)
+
+
+def test_wide_groups_kernel_in_the_sampler():
+    """three groups of 13 parameters (16-wide rows) in one loglik_groups_kernel launch, within the sum of the groups'
+    bounds; walkers beside the box edge on lanes 8 .. 12 (_groups_in_the_sampler)"""
+    r = _groups_in_the_sampler(3, 13)
+    print(f"\nRATIOS wide_groups_d13 lp={r:.3g}")
+
+
+def _blocks10(d=3):
+    c = PC.Case("blocks10", 300, d, 5, 512, O.RBF, np.inf, False, nblk=10)
     return c, PC.problem(c)
 
 
@@ -185,7 +223,16 @@ def test_likelihood_state_across_calls():
 def test_sampler_10_blocks_with_and_without_tasks_kernel(monkeypatch):
     """a 10-block sampler with 1024 walkers (512 proposals per half-step: the tasks kernel above 256 rows) gives the
     chain of the serial likelihood kernel bit for bit, and a second run on the same model equals a fresh one"""
-    c, (model, lo, hi, y_exp, y_err, bs, rng) = _blocks10()
+    _ten_blocks_with_and_without_tasks(monkeypatch, 3)
+
+
+def test_wide_sampler_10_blocks_with_and_without_tasks_kernel(monkeypatch):
+    """the same at 16 parameters: 16-wide proposals through the tasks kernel and through the serial one"""
+    _ten_blocks_with_and_without_tasks(monkeypatch, 16)
+
+
+def _ten_blocks_with_and_without_tasks(monkeypatch, d):
+    c, (model, lo, hi, y_exp, y_err, bs, rng) = _blocks10(d)
     W = 1024
     X0 = rng.uniform(lo + 0.1 * (hi - lo), hi - 0.1 * (hi - lo), (W, c.d))
     chains = []
@@ -199,11 +246,11 @@ def test_sampler_10_blocks_with_and_without_tasks_kernel(monkeypatch):
         c0 = counts()
         ds.set_state(X0)
         ds.run(5)
-        d = counts() - c0
+        delta = counts() - c0
         chain, lps = ds.get_chain()
         chains.append((chain, lps))
         if env is None:
-            assert d[PC.PATH["LOGLIK_TASKS_MULTI_BIG"]] > 0
+            assert delta[PC.PATH["LOGLIK_TASKS_MULTI_BIG"]] > 0
             ds.run(5)                      # the same model and sampler again: tickets and terms as left behind
             ds.close()
             ds = DeviceSampler([dm], W, seed=2024)

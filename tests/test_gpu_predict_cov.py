@@ -127,7 +127,7 @@ def test_symmetric_form(kernel, cn, d):
         m, v = dm.gp_predict(X)
         assert np.array_equal(mean, m), "mean differs from gp_predict's"
         _, two = dm.gp_predict_cov(X, X.copy())
-        _, _, _, vb, _ = H.gp_predict(X, model)
+        _, _, _, vb, _ = H.gp_predict(X, model, cx=H.C_X8)       # the factor this check was set with
         for p, ref in enumerate(CR.predict_cov(X, None, model)):
             lo = np.tril_indices(len(X))
             within(f"sym pc {p}", cov[p][lo], ref.C[lo], ref.bound[lo])
@@ -217,7 +217,7 @@ def test_gpr_predict_cov_and_sample_y(name):
         assert mean.shape == (20,) and cov.shape == (20, 20)
         ref = CR.PCCov(X, None, model.X_train, gp, model.spec)
         within(f"{name} predict cov", cov, ref.C, ref.bound)
-        pr = H.PCRef(X, model.X_train, gp, model.spec)
+        pr = H.PCRef(X, model.X_train, gp, model.spec, cx=H.C_X8)
         within(f"{name} predict mean", mean, pr.mean, pr.mean_bound)
         Y = r.sample_y(X, n_samples=5, random_state=7)
         assert Y.shape == (20, 5)

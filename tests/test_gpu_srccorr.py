@@ -60,8 +60,8 @@ def test_diag_cov_without_sources_same_bits(name):
     _close(dms)
 
 
-def _reference(c, X, Cd, src, n_div=1.0):
-    preds = [H.gp_predict(X, model) for model, _, _ in c["groups"]]
+def _reference(c, X, Cd, src, n_div=1.0, input_rounding=False):
+    preds = [H.gp_predict(X, model, input_rounding=input_rounding) for model, _, _ in c["groups"]]
     means = [p[0] for p in preds]
     vars_ = [p[1] for p in preds]
     ref, *_ = R.dense_logpost(c, X, means, vars_, Cd, n_div)
@@ -254,7 +254,7 @@ def test_path_cases_with_cov_and_sources(idx, S):
     # the reference on the special columns (a few rows where the blocks are large: longdouble is slow there)
     X = Xq[cols[:6] if c.F > 256 else cols]
     got = out[cols[:6] if c.F > 256 else cols]
-    ref, bnd = _reference(cc, X, Cd, src)
+    ref, bnd = _reference(cc, X, Cd, src, input_rounding=c.ls_bounds)
     _within(got, ref, bnd)
     dm.close()
 

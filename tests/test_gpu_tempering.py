@@ -129,6 +129,49 @@ def test_tempered_chain_equals_host_reference(W, swap_every):
     dm.close()
 
 
+def _wide(d=16):
+    """a d-parameter model of the path sweep's family, its box and the oracle's log-posterior"""
+    import path_cases as PC
+    c = PC.Case("wide", 60, d, 3, 64, O.MATERN, 2.5, True)
+    model, lo, hi, y_exp, y_err, _, _ = PC.problem(c)
+    dm = GU.device_model(model)
+    dm.likelihood_setup(y_exp, y_err, lo, hi, 1.0)
+
+    def oracle_lp(X):
+        X = np.atleast_2d(X)
+        return np.array([O.log_posterior(x, {"g": model}, lo, hi, y_exp, y_err)[0] for x in X])
+    return dict(lo=lo, hi=hi), model, dm, oracle_lp
+
+
+@pytest.mark.parametrize("swap_every", [1, 3])
+def test_tempered_chain_equals_host_reference_d16(swap_every):
+    """16 parameters, odd W: temper_swap_kernel<16> swaps 16-wide rows of the state and of the stored chain; chain,
+    acceptance and swap counts and stored log-probabilities against tests/pt_ref.py"""
+    from gpemu.sampler import TemperedSampler
+    g, _, dm, oracle_lp = _wide(16)
+    betas = np.array([1.0, 0.4, 0.1, 0.0])
+    T, W, steps = betas.size, 33, 10
+    seeds = [0xBEEF + 7 * t for t in range(T)]
+    rng = np.random.default_rng(9)
+    lo, hi = g["lo"], g["hi"]
+    X0 = rng.uniform(lo + 0.2 * (hi - lo), hi - 0.2 * (hi - lo), (T, W, 16))
+    ts = TemperedSampler([dm], W, betas, seeds=seeds, swap_every=swap_every)
+    ts.set_state(X0)
+    ts.run(steps)
+    chain, lps = ts.get_chain()
+    nacc = ts.counts()[0].reshape(T, W)
+    sacc, stry = ts.swap_counts()
+    ochain, olps, onacc, osacc, ostry = pt_ref.run(X0, oracle_lp, betas, seeds, steps, swap_every=swap_every)
+    _compare_chains(chain, lps, ochain, olps)
+    np.testing.assert_array_equal(nacc, onacc)
+    np.testing.assert_array_equal(sacc, osacc)
+    np.testing.assert_array_equal(stry, ostry)
+    assert stry.sum() == (steps // swap_every) * (T - 1) * W and sacc.sum() > 0
+    assert np.all(chain > lo) and np.all(chain < hi) and np.all(np.isfinite(lps))
+    ts.close()
+    dm.close()
+
+
 def _model_2d(y_err_scale):
     """A d = 2 emulator from the oracle's pieces (as oracle.workloads.fixed_theta_model, on a 2-D design)."""
     rng = np.random.default_rng(23)

@@ -1,7 +1,8 @@
 """-m gpu tests of models, fit handles and samplers with 9 to 16 parameters (the padded width 16 of csrc/internal.h:
 DPAD_WIDE): fit-side kernel matrix / LML / gradient, predictions, full predictions and the log-posterior against the CPU
 oracle, the d = 8 path against the wide path on the same problem (padding cross-check), sampler chains against the
-stretch-move restatement, and the rejection of d > 16."""
+stretch-move restatement (d = 9, 12, 16; the state's log-probabilities also within the bound of tests/hp_ref.py),
+snapshot and restore at d = 16, and the rejection of d > 16."""
 import contextlib
 
 import numpy as np
@@ -278,6 +279,74 @@ def test_stacked_chains_equal_separate_chains_d12():
         one.close()
         np.testing.assert_array_equal(chain_s[:, c * W:(c + 1) * W], ch)
         np.testing.assert_array_equal(lps_s[:, c * W:(c + 1) * W], lp)
+    dm.close()
+
+
+def _path_model(d, kind, nu):
+    import path_cases as PC
+    c = PC.Case(f"sampler_d{d}", 70, d, 3, 64, kind, nu, False)
+    model, lo, hi, y_exp, y_err, bs, _ = PC.problem(c)
+    dm = _device(model)
+    dm.likelihood_setup(y_exp, y_err, lo, hi, 1.0)
+
+    def oracle_lp(X):
+        return np.array([O.log_posterior(x, {"g": model}, lo, hi, y_exp, y_err)[0] for x in np.atleast_2d(X)])
+    return model, lo, hi, y_exp, y_err, bs, dm, oracle_lp
+
+
+@pytest.mark.parametrize("d", [9, 16])
+def test_philox_chain_equals_oracle_and_state_within_bound(d):
+    """d = 9 (7 padded lanes) and d = 16 (none): accept_kernel<16> and the 16-wide pad / unpad of the rows against the
+    stretch-move restatement on the Philox stream; the state's log-probabilities within the hp_ref bound"""
+    import hp_ref as H
+    from gpemu.sampler import DeviceSampler
+    model, lo, hi, y_exp, y_err, bs, dm, oracle_lp = _path_model(d, O.MATERN, 1.5)
+    W, steps = 48, 6
+    X0 = np.random.default_rng(d).uniform(lo + 0.2 * (hi - lo), hi - 0.2 * (hi - lo), (W, d))
+    ds = DeviceSampler([dm], W, a=2.0, seed=0x5EED + d)
+    ds.set_state(X0)
+    ds.run(steps)
+    chain, lps = ds.get_chain()
+    ochain, olps, onacc = SO.run(X0, oracle_lp, SO.PhiloxStream(0x5EED + d), steps)
+    np.testing.assert_allclose(chain, ochain, rtol=1e-12, atol=1e-12)
+    np.testing.assert_array_equal(ds.counts()[0], onacc)
+    assert onacc.sum() > 0
+    X, lpd = ds.get_state()
+    np.testing.assert_array_equal(X, chain[-1])
+    lp, lb, _ = H.log_posterior(X, model, lo, hi, y_exp, y_err, bs)
+    err = np.abs(lpd.astype(np.longdouble) - lp).astype(np.float64)
+    r = np.where(err == 0, 0.0, err / np.maximum(lb, 1e-300))
+    assert r.max() <= 1.0, f"state log-probability: err/bound {r.max():.3g}"
+    print(f"\nRATIOS sampler_state_d{d} lp={r.max():.3g}")
+    ds.close()
+    dm.close()
+
+
+def test_snapshot_restore_d16():
+    """gpemu_sampler_snapshot / _restore at d = 16 (the snapshot's rows are 16 wide): the rerun block equals an
+    unbroken run in state, chain and counts"""
+    from gpemu import _lib
+    from gpemu.sampler import DeviceSampler
+    _, lo, hi, _, _, _, dm, _ = _path_model(16, O.RBF, np.inf)
+    W = 40
+    X0 = np.random.default_rng(4).uniform(lo + 0.2 * (hi - lo), hi - 0.2 * (hi - lo), (W, 16))
+    a = DeviceSampler([dm], W, seed=31)
+    b = DeviceSampler([dm], W, seed=31)
+    a.set_state(X0)
+    b.set_state(X0)
+    a.run(9)
+    b.run(4)
+    _lib.check(_lib.lib().gpemu_sampler_snapshot(b._h))
+    b.run(5)
+    _lib.check(_lib.lib().gpemu_sampler_restore(b._h))
+    b.run(5)
+    np.testing.assert_array_equal(a.counts()[0], b.counts()[0])
+    np.testing.assert_array_equal(a.get_chain()[0], b.get_chain()[0])
+    np.testing.assert_array_equal(a.get_chain()[1], b.get_chain()[1])
+    np.testing.assert_array_equal(a.get_state()[0], b.get_state()[0])
+    np.testing.assert_array_equal(a.get_state()[1], b.get_state()[1])
+    a.close()
+    b.close()
     dm.close()
 
 
