@@ -409,11 +409,17 @@ def device_model_for(results: dict[str, Any], n_pc: int, cov_unexplained: np.nda
 
 def predict(parameters, emulation_config: "EmulationConfig", merge_predictions_over_groups: bool = True,
             emulation_group_results: dict[str, dict[str, Any]] | None = None,
-            emulator_cov_unexplained: dict | None = None) -> dict[str, np.ndarray]:
-    """{'central_value': (B,F), 'cov': (B,F,F)} over all groups (ref: emulation.py:410-462)."""
+            emulator_cov_unexplained: dict | None = None, return_jacobian: bool = False) -> dict[str, np.ndarray]:
+    """{'central_value': (B,F), 'cov': (B,F,F)} over all groups (ref: emulation.py:410-462).
+
+    ``return_jacobian=True`` adds ``'jacobian'`` (B, F, d), ``J[b, f, i] = d central_value[b, f] / d x_i =
+    scale_f sum_p components[p, f] d m_p / d x_i`` from the analytic GP Jacobian on the device,
+    merged over the groups like ``central_value``.  ``central_value`` and ``cov`` come from the same calls either
+    way: the flag does not change their bits.  RBF and Matern nu = 1.5 / 2.5 / inf kernels only."""
     emulation_group_results = emulation_group_results or {}
     emulator_cov_unexplained = emulator_cov_unexplained or {}
     predict_output = {}
+    jacobians = {}
     for group_name, group_config in emulation_config.emulation_groups_config.items():
         group_result = emulation_group_results.get(group_name)
         if group_result is None:
@@ -421,9 +427,59 @@ def predict(parameters, emulation_config: "EmulationConfig", merge_predictions_o
         cov_un = emulator_cov_unexplained[group_name] if emulator_cov_unexplained else None
         predict_output[group_name] = predict_emulation_group(parameters, group_result, group_config,
                                                              emulator_group_cov_unexplained=cov_un)
+        if return_jacobian:
+            jacobians[group_name] = group_jacobian(parameters, group_result, group_config, cov_un)
     if not merge_predictions_over_groups:
+        for group_name, jac in jacobians.items():
+            predict_output[group_name]['jacobian'] = jac
         return predict_output
-    return emulation_config.sort_observables_in_matrix.convert(group_matrices=predict_output)
+    sorter = emulation_config.sort_observables_in_matrix
+    output = sorter.convert(group_matrices=predict_output)
+    if return_jacobian:
+        output['jacobian'] = merge_jacobians(sorter, jacobians)
+    return output
+
+
+def group_jacobian(parameters, results, emulation_group_config, emulator_group_cov_unexplained=None) -> np.ndarray:
+    """(B, F, d) Jacobian of one group's central values: the device's d m_p / d x back-projected through the PCA and
+    the scaler, as ``central_value = (m @ components) * scale + mean`` is."""
+    parameters = np.array(parameters, ndmin=2, dtype=np.float64)
+    n_pc = emulation_group_config.n_pc
+    dm = device_model_for(results, n_pc, emulator_group_cov_unexplained)
+    dmean = dm.gp_predict_grad(parameters)[2]
+    return backproject_jacobian(dmean, results['PCA']['pca'].components_[:n_pc], results['PCA']['scaler'].scale_)
+
+
+def backproject_jacobian(dmean, components, scale) -> np.ndarray:
+    """dmean (B, k, d), components (k, F), scale (F,) -> (B, F, d)"""
+    return np.einsum('bpi,pf->bfi', np.asarray(dmean), np.asarray(components)) * np.asarray(scale)[None, :, None]
+
+
+def merge_jacobians(sorter, jacobians) -> np.ndarray:
+    """The groups' (B, F_g, d) Jacobians in the merged observable order, (B, F, d): ``convert``'s rule for
+    ``central_value`` with one more axis."""
+    out = None
+    for _, (group_name, slice_out, slice_group) in sorter.emulation_group_to_observable_matrix.items():
+        jac = jacobians[group_name]
+        if out is None:
+            out = np.zeros((jac.shape[0], *sorter.shape[1:], jac.shape[2]))
+        out[:, slice_out, :] = jac[:, slice_group, :]
+    return out
+
+
+def sensitivity(parameters, emulation_config: "EmulationConfig",
+                emulation_group_results: dict[str, dict[str, Any]] | None = None) -> np.ndarray:
+    """Normalised sensitivities (B, F, d): ``d O_f / d x_i * x_i / O_f`` at each row of ``parameters``, from the
+    analytic Jacobian -- the quantity the reference's sensitivity plot approximates with a 10 % forward difference
+    (ref: plot_qhat.py:172-183, 204-258)."""
+    parameters = np.array(parameters, ndmin=2, dtype=np.float64)
+    out = predict(parameters, emulation_config, emulation_group_results=emulation_group_results, return_jacobian=True)
+    return normalised_sensitivity(out['jacobian'], parameters, out['central_value'])
+
+
+def normalised_sensitivity(jacobian, parameters, central_value) -> np.ndarray:
+    """J[b, f, i] x[b, i] / O[b, f]"""
+    return np.asarray(jacobian) * np.asarray(parameters)[:, None, :] / np.asarray(central_value)[:, :, None]
 
 
 def predict_emulation_group(parameters, results, emulation_group_config, emulator_group_cov_unexplained=None):

@@ -204,5 +204,19 @@ def log_posterior(X):
     return log_post
 
 
+def log_posterior_and_gradient(X):
+    """``(lp (B,), grad (B, d))``: the log-posterior of each row of X and its gradient with respect to the parameters
+    (DESIGN.md §4.24), on the state ``initialize_pool_variables`` set.  Every row is evaluated on its own, as emcee
+    evaluates a walker (the truncation covariance is not divided by the batch size: n_div = 1), so a row's value and
+    gradient do not depend on the rest of the batch.  Rows outside the open box: ``-inf`` and a zero gradient.
+    Fully correlated sources (``experimental_results['sys_sources']``) have no gradient path: ValueError."""
+    X = np.array(X, ndmin=2, dtype=np.float64)
+    if data_covariance()[1] is not None:
+        raise ValueError("log_posterior_and_gradient does not support experimental_results['sys_sources'] "
+                         "(fully correlated sources have no gradient path)")
+    from gpemu.model import logpost_groups_grad
+    return logpost_groups_grad(device_models(n_div=1.0), X)
+
+
 # the ensemble sampler recognises this function and takes the fused device path (n_div = 1)
 log_posterior._gpemu_device_models = lambda: device_models(n_div=1.0)

@@ -236,6 +236,7 @@ def run_mcmc(config, closure_index=-1):
         if world > 1 and not alone and rank != 0:
             logger.info('tempered run: runs on rank 0')
             return
+        _warn_find_map_not_read(config, 'the tempered run')
         return _run_tempered(config, closure_index)
     if closure_index >= 0 and (alone or world == 1) and _closure_batch_enabled() \
             and 'validation_indices' in config.analysis_config:
@@ -246,6 +247,7 @@ def run_mcmc(config, closure_index=-1):
             for stale in [k for k in _closure_done if k[:3] == key[:3] and k != key]:
                 del _closure_done[stale]
             done.clear()                      # a new pass: everything reruns, like the reference
+            _warn_find_map_not_read(config, 'the stacked closure chains')
             n_par = len(config.analysis_config['parameterization'][config.parameterization]['names'])
             for batch in _closure_sub_batches(config, owned, n_par):
                 _run_closure_batch(config, batch)
@@ -281,6 +283,12 @@ def run_mcmc(config, closure_index=-1):
     # upstream copies this state into every pool worker (ref: mcmc.py:77-78); here it goes to the device once
     data = _with_data_covariance(config, data)
     log_posterior.initialize_pool_variables(lower, upper, emu_cfg, emu_results, data, truncation_cov)
+    if getattr(config, 'find_map', False):
+        # what the gradient path declines is known now: say so before a step is taken, not after production
+        reason = find_map_unsupported(emu_cfg, emu_results)
+        if reason:
+            raise ValueError(f"parameters.mcmc.find_map: {reason}; remove the key (or the unsupported setting) -- "
+                             "no step has been taken")
     sampler = LoggingEnsembleSampler(n_walk, n_par, log_posterior.log_posterior, sharded=False if alone else None)
     logger.info(f'Sampler ready: {n_walk} walkers, {n_par} parameters, {sampler.world_size} GPU process(es)')
 
@@ -314,6 +322,20 @@ def run_mcmc(config, closure_index=-1):
         validation_design = io.design_array_from_h5(config.output_dir, filename='observables.h5', validation_set=True)
         results['design_point'] = validation_design[closure_index]
         results['experimental_pseudodata'] = data
+    if getattr(config, 'find_map', False):
+        # parameters.mcmc.find_map: the maximum from the production chain's best distinct points (the pool still holds
+        # this run's data); three more entries in mcmc.h5, none without the key
+        logger.info('Maximising the log-posterior from the best points of the chain...')
+        try:
+            found = find_map_on_pool(lower, upper, n_starts=min(32, n_walk), chain=results['chain'],
+                                     log_prob=results['log_prob'])
+        except Exception as err:     # the chain is worth more than the maximum: it is written either way
+            logger.warning(f'parameters.mcmc.find_map: the maximisation failed ({err!r}); mcmc.h5 is written without '
+                           'map_parameters, map_log_prob and map_hessian')
+        else:
+            results['map_parameters'] = found['map_parameters']
+            results['map_log_prob'] = np.float64(found['map_log_prob'])
+            results['map_hessian'] = found['hessian']
     _write_outputs(config, results, sampler, io)
 
 
@@ -473,6 +495,78 @@ def map_parameters(posterior, method='quantile'):
     return estimate
 
 
+def find_map_unsupported(emulation_config, emulation_results):
+    """Why ``log_posterior_and_gradient`` would decline the state ``initialize_pool_variables`` has just set, or None:
+    fully correlated sources in the data, or a group whose kernel has no derivative path (Matern nu other than 1.5,
+    2.5, inf).  Decided on the host, from the data and the emulators' kernels."""
+    if log_posterior.data_covariance()[1] is not None:
+        return "the data carry fully correlated sources (sys_sources), which have no gradient path"
+    for name, cfg in emulation_config.emulation_groups_config.items():
+        kernel = emulation_results[name]['emulators'][0].kernel_
+        nu = float(getattr(kernel, 'nu', np.inf))
+        if int(kernel.kind) == 1 and not (np.isinf(nu) or nu in (1.5, 2.5)):
+            return f"emulation group {name!r} has a Matern kernel of nu = {nu:g}; gradients need nu = 1.5, 2.5 or inf (RBF)"
+    return None
+
+
+def _warn_find_map_not_read(config, what):
+    """``parameters.mcmc.find_map`` is read by the untempered, unstacked ``run_mcmc`` only: say so where it is set and
+    another path runs (``find_map(config, closure_index)`` afterwards gives the same from the written mcmc.h5)."""
+    if getattr(config, 'find_map', False):
+        logger.warning(f'parameters.mcmc.find_map is not read by {what}: mcmc.h5 will hold no map_* entries; call '
+                       'mcmc.find_map(config, closure_index) on the written chain instead')
+
+
+def find_map_on_pool(lower, upper, n_starts=32, starts=None, chain=None, log_prob=None, hessian=True):
+    """The maximum of the log-posterior on the state ``log_posterior.initialize_pool_variables`` set.
+    Starts: ``starts`` (n, d) if given; else the positions of the ``n_starts`` highest distinct log-probabilities of a
+    stored ``chain`` (steps, walkers, d) / ``log_prob`` (steps, walkers); else uniform draws in the box (numpy's global
+    state).  All starts advance in lock step (``gpemu.mapfit``), one batched device evaluation of value and analytic
+    gradient per round.  Returns ``gpemu.mapfit.find_map``'s dict."""
+    from gpemu import mapfit
+    lower = np.asarray(lower, dtype=np.float64)
+    upper = np.asarray(upper, dtype=np.float64)
+    if starts is None:
+        if chain is not None and log_prob is not None:
+            starts = mapfit.best_distinct(chain, log_prob, n_starts)
+        else:
+            starts = np.random.uniform(lower, upper, (int(n_starts), lower.size))
+    return mapfit.find_map(log_posterior.log_posterior_and_gradient, starts, lower, upper, hessian=hessian)
+
+
+def find_map(config, closure_index=-1, n_starts=32, starts=None):
+    """The MAP point of the analysis of ``config`` (or of the closure test ``closure_index``): a maximum of the
+    log-posterior by L-BFGS-B on the device's analytic gradient, where ``map_parameters`` gives a per-coordinate
+    marginal median.  The starts come from ``mcmc.h5`` of the run if it exists (the ``n_starts`` best distinct points of
+    its chain), else they are uniform in the box.  Returns a dict with ``map_parameters`` (d,), ``map_log_prob``,
+    ``all_parameters`` (n_starts, d), ``all_log_prob``, ``status``, ``nfev`` (per start) and ``hessian`` (d, d), the
+    second derivatives of the log-posterior from central differences of the gradient with the step
+    ``h_i = 1e-4 (max_i - min_i)``: at the maximum, except that a coordinate closer than ``2 h_i`` to a face of the box
+    has its pair of points centred ``2 h_i`` inside that face, so that column is the derivative at that shifted point
+    (``gpemu.mapfit.central_hessian``).  A maximum ON a face has no two-sided second derivative there."""
+    box = config.analysis_config['parameterization'][config.parameterization]
+    lower, upper = box['min'], box['max']
+    emu_cfg = emulation.EmulationConfig.from_config_file(
+        analysis_name=config.analysis_name, parameterization=config.parameterization,
+        analysis_config=config.analysis_config, config_file=config.config_file)
+    emu_results = emu_cfg.read_all_emulator_groups()
+    truncation_cov = emulation.compute_emulator_cov_unexplained(emu_cfg, emu_results)
+    io = _data_IO()
+    chain = log_prob = None
+    stored = None
+    if os.path.exists(config.mcmc_outputfile):
+        stored = io.read_dict_from_h5(config.mcmc_output_dir, 'mcmc.h5')
+        chain, log_prob = stored.get('chain'), stored.get('log_prob')
+    if closure_index >= 0 and stored is not None and 'experimental_pseudodata' in stored:
+        data = stored['experimental_pseudodata']           # the draw the chain was conditioned on
+    else:
+        data = io.data_array_from_h5(config.output_dir, 'observables.h5', pseudodata_index=closure_index,
+                                     observable_filter=emu_cfg.observable_filter)
+    data = _with_data_covariance(config, data)
+    log_posterior.initialize_pool_variables(lower, upper, emu_cfg, emu_results, data, truncation_cov)
+    return find_map_on_pool(lower, upper, n_starts=n_starts, starts=starts, chain=chain, log_prob=log_prob)
+
+
 ####################################################################################################
 class LoggingEnsembleSampler(EnsembleSampler):
     """Ensemble sampler that reports the acceptance fraction every ``n_logging_steps`` steps
@@ -523,6 +617,8 @@ class MCMCConfig:
         if dc and not os.path.isabs(str(dc)):
             dc = os.path.join(os.path.dirname(os.path.abspath(config_file)), str(dc))
         self.data_covariance = str(dc) if dc else None
+        # the MAP point after production (optional, default off): map_parameters, map_log_prob, map_hessian in mcmc.h5
+        self.find_map = bool(mc.get('find_map', False))
 
         # <output_dir>/<analysis>_<parameterization>[/closure/results/<index>]/{mcmc.h5, mcmc_sampler.pkl}
         self.output_dir = os.path.join(top['output_dir'], f'{analysis_name}_{parameterization}')

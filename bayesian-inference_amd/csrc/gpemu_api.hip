@@ -500,6 +500,8 @@ int gpemu_model_destroy(gpemu_model *m) {
   for (const gpemu_model::LikEntry &en : m->lik_cache) free_lik_entry(en);
   hipFree(m->ycov); hipFree(m->srcs);
   hipFree(m->exact_scratch);
+  (void)hipFree(m->grad_ws);
+  (void)hipFree(m->grad_lik_ws);
   hipFree(m->blk_start); hipFree(m->blk_of);
   for (const gpemu_model::SchedEntry &en : m->sched_cache) { hipFree(en.items); hipFree(en.cnt); }
   for (const gpemu_model::SchedEntry &en : m->sm_cache) { hipFree(en.items); hipFree(en.cnt); }

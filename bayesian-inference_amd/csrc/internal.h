@@ -161,6 +161,11 @@ struct gpemu_model {
   double *Q = nullptr;         // [nblk][S][S]   B_o^T A_o^-1 B_o
   double *w0 = nullptr;        // [chains][nblk][S]  B_o^T A_o^-1 r0_o
 
+  // workspace of the derivative calls (k_grad.hip): allocated by the first of them, null until then
+  double *grad_ws = nullptr;
+  double *grad_lik_ws = nullptr;   // the likelihood's per-(row, observable block) terms, grown with the number of blocks
+  int64_t grad_lik_cap = 0;
+
   // exact-form (validation) scratch: per-workgroup Sigma, panel and residual
   double *exact_scratch = nullptr;
   int64_t exact_scratch_size = 0;

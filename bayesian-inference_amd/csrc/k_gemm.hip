@@ -226,6 +226,8 @@ int launch_gemm(const GemmArgs &g, bool a_kmajor, bool b_kmajor, int batch, hipS
   if (!big && !g.lower_only && tiles >= 400) {
     if (g.k_from_n && !g.k_from_m && !g.k_to_m && g.N >= 128) gs.pair = 1;
     else if (g.k_to_m && !g.k_from_n && !g.k_from_m && g.M >= 128) gs.pair = 2;
+    // (the mirror image of k_to_m: row tile t has the k-tiles from its first row on, T - 1 - t the rest; U = W^T V of k_grad.hip)
+    else if (g.k_from_m && !g.k_from_n && !g.k_to_m && g.M >= 128) gs.pair = 2;
   }
   const int T = big ? 128 : 64;
   {

@@ -63,6 +63,12 @@ _SIGNATURES = {
     "gpemu_logpost": (C.c_int, [C.c_void_p, c_i64, C.c_void_p, C.c_void_p, C.c_int]),
     "gpemu_logpost_groups": (C.c_int, [C.c_void_p, C.c_int, c_i64, C.c_void_p, C.c_void_p, C.c_int]),
     "gpemu_logpost_dev": (C.c_int, [C.c_void_p, c_i64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "gpemu_gp_predict_grad": (C.c_int, [C.c_void_p, c_i64] + [C.c_void_p] * 5),
+    "gpemu_gp_predict_grad_dev": (C.c_int, [C.c_void_p, c_i64] + [C.c_void_p] * 6),
+    "gpemu_logpost_grad": (C.c_int, [C.c_void_p, c_i64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+    "gpemu_logpost_grad_dev": (C.c_int, [C.c_void_p, c_i64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "gpemu_logpost_groups_grad": (C.c_int, [C.c_void_p, C.c_int, c_i64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+    "gpemu_grad_path_counts": (C.c_int, [C.POINTER(c_i64), c_i64]),
     "gpemu_fit_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, c_i64, c_i64, C.c_void_p, C.c_int, C.c_double,
                                    C.c_int, C.c_int, C.c_double]),
     "gpemu_fit_destroy": (C.c_int, [C.c_void_p]),

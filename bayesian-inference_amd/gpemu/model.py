@@ -265,6 +265,34 @@ class DeviceModel:
         check(_lib.lib().gpemu_logpost(self._h, B, ptr(X), ptr(out), int(mode)))
         return out
 
+    # -- derivatives with respect to the parameters -------------------------------------
+    def gp_predict_grad(self, X):
+        """``mean`` (B, k), ``var`` (B, k) and their Jacobians ``dmean`` (B, k, d), ``dvar`` (B, k, d) with respect to
+        the query.  ``dvar`` is 0 where the variance was clipped at 0.  RBF and Matern nu = 1.5 / 2.5 / inf; other nu
+        raise ``GpemuError`` (code -5).  Non-finite queries are refused as in ``gp_predict``."""
+        X = self._finite(self._X(X))
+        B = X.shape[0]
+        mean = np.empty((B, self.k))
+        var = np.empty((B, self.k))
+        dmean = np.empty((B, self.k, self.d))
+        dvar = np.empty((B, self.k, self.d))
+        check(_lib.lib().gpemu_gp_predict_grad(self._h, B, ptr(X), ptr(mean), ptr(var), ptr(dmean), ptr(dvar)))
+        return mean, var, dmean, dvar
+
+    def logpost_grad(self, X, mode=LOWRANK):
+        """``lp`` (B,) and ``grad`` (B, d) of the log-posterior after ``likelihood_setup``; rows outside the open box
+        (a NaN parameter included) give ``lp = -inf`` and ``grad = 0``."""
+        X = self._X(X)
+        B = X.shape[0]
+        lp = np.empty(B)
+        grad = np.empty((B, self.d))
+        check(_lib.lib().gpemu_logpost_grad(self._h, B, ptr(X), ptr(lp), ptr(grad), int(mode)))
+        return lp, grad
+
+    def logpost_grad_dev(self, dX_ptr, B, dlp_ptr, dgrad_ptr, mode=LOWRANK, stream=0):
+        check(_lib.lib().gpemu_logpost_grad_dev(self._h, int(B), C.c_void_p(dX_ptr), C.c_void_p(dlp_ptr),
+                                                C.c_void_p(dgrad_ptr), int(mode), C.c_void_p(stream)))
+
     # -- device-pointer API (torch tensors on this device; stream = torch's current stream) ----
     def logpost_dev(self, dX_ptr, B, dout_ptr, mode=LOWRANK, stream=0):
         check(_lib.lib().gpemu_logpost_dev(self._h, int(B), C.c_void_p(dX_ptr), C.c_void_p(dout_ptr),
@@ -298,6 +326,28 @@ def logpost_groups(models, X, mode=LOWRANK):
     hs = (C.c_void_p * len(models))(*[m.handle for m in models])
     check(_lib.lib().gpemu_logpost_groups(hs, len(models), B, ptr(X), ptr(out), int(mode)))
     return out
+
+
+def logpost_groups_grad(models, X, mode=LOWRANK):
+    """``lp`` (B,) and ``grad`` (B, d) of the log-posterior summed over the emulation groups ``models`` (one device, one
+    parameter box).  Groups with correlated sources are declined (``GpemuError``, code -5)."""
+    models = list(models)
+    if not models:
+        raise ValueError("logpost_groups_grad needs at least one model")
+    X = models[0]._X(X)
+    B = X.shape[0]
+    lp = np.empty(B)
+    grad = np.empty((B, models[0].d))
+    hs = (C.c_void_p * len(models))(*[m.handle for m in models])
+    check(_lib.lib().gpemu_logpost_groups_grad(hs, len(models), B, ptr(X), ptr(lp), ptr(grad), int(mode)))
+    return lp, grad
+
+
+def grad_path_counts():
+    """Counters of enum gpemu_grad_path (the derivative launches), as an int64 array."""
+    out = np.zeros(8, dtype=np.int64)
+    n = _lib.lib().gpemu_grad_path_counts(out.ctypes.data_as(C.POINTER(C.c_int64)), out.size)
+    return out[:n].copy()
 
 
 def src_path_counts():

@@ -174,6 +174,46 @@ int gpemu_logpost(gpemu_model *m, int64_t B, const double *X, double *out, int m
 int gpemu_logpost_dev(gpemu_model *m, int64_t B, const double *dX, double *dout, int mode,
                       void *stream);
 
+/* ---- derivatives with respect to the parameters ------------------------------------------------
+ * Supported: RBF and Matern nu = 1.5, 2.5, inf; with or without constant and noise; 1 <= d <= 16; k <= 64; any number of
+ * observable blocks; a dense within-observable data covariance.  Declined before any launch with
+ * GPEMU_ERR_UNSUPPORTED: Matern 0.5 and any other nu (the derivative needs K_{nu-1} and is singular or discontinuous at
+ * r = 0 for nu < 1), groups with correlated sources (n_src > 0), a likelihood set up for several data vectors, and
+ * mode = GPEMU_LOGPOST_EXACT.  A row's results have the same bits whatever else is in the batch.
+ * One stream per model: the derivative calls share a workspace that belongs to the model (allocated by the first of
+ * them, regrown when a likelihood setup changes the number of observable blocks), as the value calls share theirs.  The
+ * _dev forms do not synchronise: calls on one model must be ordered on ONE stream -- two streams at a time, or
+ * alternating streams without a synchronisation between the calls, race on that workspace.
+ *
+ * Jacobians of the PCs' GPs: mean[B*k], var[B*k] (clipped at 0, NULL in the _dev form: not wanted), dmean_dx[B*k*d],
+ * dvar_dx[B*k*d] (0 where the variance was clipped: the derivative of the function as it is computed). */
+int gpemu_gp_predict_grad(gpemu_model *m, int64_t B, const double *X, double *mean, double *var, double *dmean_dx,
+                          double *dvar_dx);
+int gpemu_gp_predict_grad_dev(gpemu_model *m, int64_t B, const double *dX, double *dmean, double *dvar,
+                              double *ddmean_dx, double *ddvar_dx, void *stream);
+/* Log-posterior and its gradient after a likelihood setup: lp[B], grad[B*d].  Rows outside the open box (a NaN
+ * parameter included): lp = -inf, grad = 0.  A row whose lp is NaN (a covariance that is not positive definite, as in the
+ * value call) has a NaN gradient.  lp is held to the same reference as the value-only call; it need not have
+ * the same bits (the distances are taken directly from the coordinates, the sums run in another order). */
+int gpemu_logpost_grad(gpemu_model *m, int64_t B, const double *X, double *lp, double *grad, int mode);
+int gpemu_logpost_grad_dev(gpemu_model *m, int64_t B, const double *dX, double *dlp, double *dgrad, int mode,
+                           void *stream);
+/* ... summed over n_groups models on one device with one parameter box */
+int gpemu_logpost_groups_grad(gpemu_model *const *models, int n_groups, int64_t B, const double *X, double *lp,
+                              double *grad, int mode);
+/* Which instances of the derivative path ran.  A set of its own: the other sets keep their sizes and indices. */
+enum gpemu_grad_path {
+  GPEMU_GRAD_PATH_CHUNK = 0,         /* one pass of up to 1024 rows of one group: K_*^T, V = W K_*^T, U = W^T V      */
+  GPEMU_GRAD_PATH_LOGLIK,            /* grad_loglik_kernel: the likelihood with the adjoints a_p, b_p (per pass)     */
+  GPEMU_GRAD_PATH_CONTRACT_8,        /* grad_contract_kernel, 8-wide rows (d <= 8), the log-posterior's gradient     */
+  GPEMU_GRAD_PATH_CONTRACT_16,       /* ... 16-wide rows (d = 9 .. 16)                                               */
+  GPEMU_GRAD_PATH_JACOBIAN_8,        /* grad_contract_kernel, 8-wide rows, the GP Jacobians                          */
+  GPEMU_GRAD_PATH_JACOBIAN_16,       /* ... 16-wide rows                                                             */
+  GPEMU_GRAD_PATH_COUNT
+};
+/* out[0 .. min(n, GPEMU_GRAD_PATH_COUNT)) = the counters; returns GPEMU_GRAD_PATH_COUNT (or GPEMU_ERR_ARG). */
+int gpemu_grad_path_counts(int64_t *out, int64_t n);
+
 /* ---- GP fit: kernel matrix, Cholesky, log-marginal likelihood + gradient -------------------------
  * Replaces the arithmetic inside ref: emulation.py:169-172 (GaussianProcessRegressor(...).fit):
  * skl _gpr.py:537-652 log_marginal_likelihood(theta, eval_gradient=True) and :346-364 (final L_,
