@@ -1,5 +1,6 @@
-// C ABI of libgpemu.so (see include/gpemu.h).  Host-side glue only: argument checks, device
-// memory ownership, launch sequencing.  All arithmetic is in the k_*.hip kernels.
+// C ABI of libgpemu.so (see include/gpemu.h).  Host-side glue: argument checks, device memory
+// ownership (devmem.h), launch sequencing.  The arithmetic is in the k_*.hip kernels, with one
+// exception: trunc_pack_kernel, the operand packing of gpemu_truncation_cov, sits next to its caller.
 #include <atomic>
 #include <cmath>
 #include <cstdarg>
@@ -16,25 +17,23 @@ namespace gpemu {
 
 static thread_local char g_err[512] = "";
 
-static std::atomic<int64_t> g_path_counts[GPEMU_PATH_COUNT];
-static std::atomic<int64_t> g_fit_path_counts[GPEMU_FIT_PATH_COUNT];
-static std::atomic<int64_t> g_wide_path_counts[GPEMU_WIDE_PATH_COUNT];
-static std::atomic<int64_t> g_src_path_counts[GPEMU_SRC_PATH_COUNT];
+// the path counters of every family (internal.h: PathFamily), a row each
+constexpr int PATH_FAMILY_SIZE[PATH_FAMILIES] = {GPEMU_PATH_COUNT, GPEMU_FIT_PATH_COUNT, GPEMU_WIDE_PATH_COUNT,
+                                                 GPEMU_SRC_PATH_COUNT, GPEMU_GRAD_PATH_COUNT};
+constexpr int PATH_ROW = 32;
+static_assert(GPEMU_PATH_COUNT <= PATH_ROW && GPEMU_FIT_PATH_COUNT <= PATH_ROW && GPEMU_WIDE_PATH_COUNT <= PATH_ROW &&
+              GPEMU_SRC_PATH_COUNT <= PATH_ROW && GPEMU_GRAD_PATH_COUNT <= PATH_ROW, "a family outgrew its row");
+static std::atomic<int64_t> g_path_counts[PATH_FAMILIES][PATH_ROW];
 
-void path_count(int path) {
-  if (path >= 0 && path < GPEMU_PATH_COUNT) g_path_counts[path].fetch_add(1, std::memory_order_relaxed);
+void count_path(PathFamily family, int path) {
+  if (path >= 0 && path < PATH_FAMILY_SIZE[family]) g_path_counts[family][path].fetch_add(1, std::memory_order_relaxed);
 }
 
-void fit_path_count(int path) {
-  if (path >= 0 && path < GPEMU_FIT_PATH_COUNT) g_fit_path_counts[path].fetch_add(1, std::memory_order_relaxed);
-}
-
-void wide_path_count(int path) {
-  if (path >= 0 && path < GPEMU_WIDE_PATH_COUNT) g_wide_path_counts[path].fetch_add(1, std::memory_order_relaxed);
-}
-
-void src_path_count(int path) {
-  if (path >= 0 && path < GPEMU_SRC_PATH_COUNT) g_src_path_counts[path].fetch_add(1, std::memory_order_relaxed);
+int read_path_counts(PathFamily family, int64_t *out, int64_t n) {
+  GP_ARG(out && n >= 0, "out, n");
+  const int size = PATH_FAMILY_SIZE[family];
+  for (int64_t i = 0; i < n && i < size; ++i) out[i] = g_path_counts[family][i].load(std::memory_order_relaxed);
+  return size;
 }
 
 void set_error(const char *fmt, ...) {
@@ -62,26 +61,15 @@ int launch_predict_full(gpemu_model *m, int64_t B, double n_div, double *dcv, do
                         const double *dmean, const double *dvar);
 int launch_loglik_exact(gpemu_model *m, int64_t B, const double *dXq, double *dout, hipStream_t st);
 
-template <typename T>
-static int dev_alloc(T **p, int64_t n) {
-  *p = nullptr;
-  if (n <= 0) n = 1;
-  GP_HIP(hipMalloc((void **)p, sizeof(T) * (size_t)n));
-  return GPEMU_OK;
-}
-static int upload(double *dst, const double *src, int64_t n, hipStream_t st) {
-  GP_HIP(hipMemcpyAsync(dst, src, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, st));
-  return GPEMU_OK;
-}
 
-static void free_lik_entry(const gpemu_model::LikEntry &en) {
-  (void)hipFree(en.G); (void)hipFree(en.g0); (void)hipFree(en.scal);
-  (void)hipFree(en.W); (void)hipFree(en.Q); (void)hipFree(en.w0);
+static void free_lik_entry(gpemu_model::LikEntry &en) {
+  dev_free(en.G); dev_free(en.g0); dev_free(en.scal);
+  dev_free(en.W); dev_free(en.Q); dev_free(en.w0);
 }
 
 static void free_workspace(Workspace &w) {
-  hipFree(w.Xq); hipFree(w.KS); hipFree(w.mean_part); hipFree(w.mean_part2); hipFree(w.vsq_part);
-  hipFree(w.mean); hipFree(w.var); hipFree(w.logp);
+  dev_free(w.Xq); dev_free(w.KS); dev_free(w.mean_part); dev_free(w.mean_part2); dev_free(w.vsq_part);
+  dev_free(w.mean); dev_free(w.var); dev_free(w.logp);
   w = Workspace();
 }
 
@@ -162,9 +150,6 @@ static int check_device(int device) {
   return GPEMU_OK;
 }
 
-}  // namespace gpemu
-
-namespace gpemu {
 LaunchSwitches read_launch_switches() {
   LaunchSwitches sw;
   sw.group_merge = getenv("GPEMU_NO_GROUP_MERGE") == nullptr;
@@ -260,29 +245,11 @@ extern "C" {
 const char *gpemu_version(void) { return "gpemu 0.1 (gfx950)"; }
 const char *gpemu_last_error(void) { return g_err; }
 
-int gpemu_path_counts(int64_t *out, int64_t n) {
-  GP_ARG(out && n >= 0, "out, n");
-  for (int64_t i = 0; i < n && i < GPEMU_PATH_COUNT; ++i) out[i] = g_path_counts[i].load(std::memory_order_relaxed);
-  return GPEMU_PATH_COUNT;
-}
-
-int gpemu_fit_path_counts(int64_t *out, int64_t n) {
-  GP_ARG(out && n >= 0, "out, n");
-  for (int64_t i = 0; i < n && i < GPEMU_FIT_PATH_COUNT; ++i) out[i] = g_fit_path_counts[i].load(std::memory_order_relaxed);
-  return GPEMU_FIT_PATH_COUNT;
-}
-
-int gpemu_wide_path_counts(int64_t *out, int64_t n) {
-  GP_ARG(out && n >= 0, "out, n");
-  for (int64_t i = 0; i < n && i < GPEMU_WIDE_PATH_COUNT; ++i) out[i] = g_wide_path_counts[i].load(std::memory_order_relaxed);
-  return GPEMU_WIDE_PATH_COUNT;
-}
-
-int gpemu_src_path_counts(int64_t *out, int64_t n) {
-  GP_ARG(out && n >= 0, "out, n");
-  for (int64_t i = 0; i < n && i < GPEMU_SRC_PATH_COUNT; ++i) out[i] = g_src_path_counts[i].load(std::memory_order_relaxed);
-  return GPEMU_SRC_PATH_COUNT;
-}
+int gpemu_path_counts(int64_t *out, int64_t n) { return read_path_counts(PATHS_LOGPOST, out, n); }
+int gpemu_fit_path_counts(int64_t *out, int64_t n) { return read_path_counts(PATHS_FIT, out, n); }
+int gpemu_wide_path_counts(int64_t *out, int64_t n) { return read_path_counts(PATHS_WIDE, out, n); }
+int gpemu_src_path_counts(int64_t *out, int64_t n) { return read_path_counts(PATHS_SRC, out, n); }
+int gpemu_grad_path_counts(int64_t *out, int64_t n) { return read_path_counts(PATHS_GRAD, out, n); }
 
 int gpemu_device_count(void) {
   int n = 0;
@@ -314,6 +281,142 @@ int gpemu_device_memory(int device, int64_t *free_bytes, int64_t *total_bytes) {
   GP_HIP(hipMemGetInfo(&f, &t));
   *free_bytes = (int64_t)f;
   *total_bytes = (int64_t)t;
+  return GPEMU_OK;
+}
+
+// the device state of a new model, whose dimensions are set: gpemu_model_create destroys `m` if this fails
+static int model_fill(gpemu_model *m, const double *X_train, const double *ls, const double *constv, const double *noise,
+                      const double *alpha, const double *L, const double *components, const double *scaler_mean,
+                      const double *scaler_scale, const double *cov_unexplained) {
+  const int64_t N = m->N, d = m->d, F = m->F, k = m->k, Np = m->Npad;
+  const int has_const = m->has_const, has_noise = m->has_noise;
+  const double nu = m->nu;
+  if (hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking) != hipSuccess) {
+    set_error("hipStreamCreate failed");
+    return GPEMU_ERR_HIP;
+  }
+  hipStream_t st = m->stream;
+  DevScope sc(st);
+
+  // host staging of the small padded arrays; `direct`: the kernels whose value is not flat at r = 0 (Matern 0.5, general
+  // nu < 1) recompute the distance of near-coincident pairs from the coordinates (predict_dev.h: KstarDirect)
+  const int kkind = kstar_kind(m);
+  const bool direct = kkind == 1 || (kkind == 4 && nu < 1.0);
+  const int dp = m->dp;
+  std::vector<double> hXs(direct ? (size_t)(k * Np * dp) : 0, 0.0), hls((size_t)(k * dp), 1.0),
+      hc((size_t)k, 0.0), hkd((size_t)k, 1.0), hal((size_t)(k * Np), 0.0), hjit((size_t)k, 0.0);
+  for (int64_t p = 0; p < k; ++p) {
+    for (int64_t dd = 0; dd < d; ++dd) {
+      double l = ls[p * d + dd];
+      if (!(l > 0.0)) { set_error("length scale must be positive"); return GPEMU_ERR_ARG; }
+      hls[p * dp + dd] = l;
+    }
+    if (direct)
+      for (int64_t j = 0; j < N; ++j)
+        for (int64_t dd = 0; dd < d; ++dd)
+          hXs[(p * Np + j) * dp + dd] = X_train[j * d + dd] / ls[p * d + dd];  // skl: X / length_scale
+    if (has_const) { hc[p] = constv[p]; hkd[p] += constv[p]; }
+    if (has_noise) hkd[p] += noise[p];
+    for (int64_t j = 0; j < N; ++j) hal[p * Np + j] = alpha[p * N + j];
+    // the fit's alpha jitter (skl _gpr.py:346-348: K + alpha I = L L^T): K_00 - kernel_.diag, K_00 = L_00^2
+    hjit[p] = std::fma(L[p * N * N], L[p * N * N], -hkd[p]);
+  }
+  double *dL = nullptr;
+  GP_TRY(dev_alloc(&m->ls, k * dp));
+  GP_TRY(dev_alloc(&m->constv, k));
+  GP_TRY(dev_alloc(&m->kdiag, k));
+  GP_TRY(dev_alloc(&m->alpha, k * Np));
+  GP_TRY(dev_alloc(&m->cv_jit, k));
+  GP_TRY(dev_alloc(&m->Wt, k * Np * Np));
+  GP_TRY(dev_alloc(&m->Xtr, Np * dp));
+  GP_TRY(dev_alloc(&m->comp, k * F));
+  GP_TRY(dev_alloc(&m->smean, F));
+  GP_TRY(dev_alloc(&m->sscale, F));
+  GP_TRY(dev_alloc(&m->cunexpl, F * F));
+  GP_TRY(sc.alloc(&dL, k * N * N));
+  GP_TRY(upload(m->ls, hls.data(), k * dp, st));
+  {
+    std::vector<double> hX((size_t)(Np * dp), 0.0);
+    for (int64_t j = 0; j < N; ++j)
+      for (int64_t dd = 0; dd < d; ++dd) hX[(size_t)(j * dp + dd)] = X_train[j * d + dd];
+    GP_TRY(upload(m->Xtr, hX.data(), Np * dp, st));
+    if (hipStreamSynchronize(st) != hipSuccess) {   // hX goes out of scope
+      set_error("model_create: upload failed");
+      return GPEMU_ERR_HIP;
+    }
+  }
+  {
+    // the cross-kernel's operands for the matrix cores (kstar_host.h)
+    KstarHost kh;
+    build_kstar_operands(N, Np, d, k, kkind, X_train, ls, alpha, kh);
+    if (kkind == 4) {   // the constants of nu behind the exponential's table (predict_dev.h: kstar_matern_nu)
+      const MaternNu mn = matern_nu_constants(nu);
+      const size_t n0 = kh.tab.size(), nw = (sizeof(MaternNu) + sizeof(double) - 1) / sizeof(double);
+      kh.tab.resize(n0 + nw, 0.0);
+      std::memcpy(kh.tab.data() + n0, &mn, sizeof(MaternNu));
+    }
+    m->ksteps = kh.ksteps;
+    GP_TRY(dev_alloc(&m->Xa, (int64_t)kh.Xa.size()));
+    GP_TRY(dev_alloc(&m->alf, (int64_t)kh.alf.size()));
+    GP_TRY(dev_alloc(&m->qsc, (int64_t)kh.qsc.size()));
+    GP_TRY(dev_alloc(&m->qof, (int64_t)kh.qof.size()));
+    GP_TRY(dev_alloc(&m->etab, (int64_t)kh.tab.size()));
+    GP_TRY(upload(m->Xa, kh.Xa.data(), (int64_t)kh.Xa.size(), st));
+    GP_TRY(upload(m->alf, kh.alf.data(), (int64_t)kh.alf.size(), st));
+    GP_TRY(upload(m->qsc, kh.qsc.data(), (int64_t)kh.qsc.size(), st));
+    GP_TRY(upload(m->qof, kh.qof.data(), (int64_t)kh.qof.size(), st));
+    GP_TRY(upload(m->etab, kh.tab.data(), (int64_t)kh.tab.size(), st));
+    std::vector<double> hinv(hls.size());
+    if (direct) {
+      for (size_t i = 0; i < hls.size(); ++i) hinv[i] = 1.0 / hls[i];
+      GP_TRY(dev_alloc(&m->Xs, k * Np * dp));
+      GP_TRY(dev_alloc(&m->inv_ls, k * dp));
+      GP_TRY(upload(m->Xs, hXs.data(), k * Np * dp, st));
+      GP_TRY(upload(m->inv_ls, hinv.data(), k * dp, st));
+    }
+    if (hipStreamSynchronize(st) != hipSuccess) {   // the staging vectors go out of scope
+      set_error("model_create: upload failed");
+      return GPEMU_ERR_HIP;
+    }
+  }
+  GP_TRY(upload(m->constv, hc.data(), k, st));
+  GP_TRY(upload(m->kdiag, hkd.data(), k, st));
+  GP_TRY(upload(m->alpha, hal.data(), k * Np, st));
+  GP_TRY(upload(m->cv_jit, hjit.data(), k, st));
+  GP_TRY(upload(m->comp, components, k * F, st));
+  GP_TRY(upload(m->smean, scaler_mean, F, st));
+  GP_TRY(upload(m->sscale, scaler_scale, F, st));
+  if (cov_unexplained) {
+    GP_TRY(upload(m->cunexpl, cov_unexplained, F * F, st));
+  } else if (hipMemsetAsync(m->cunexpl, 0, sizeof(double) * (size_t)(F * F), st) != hipSuccess) {
+    set_error("hipMemsetAsync failed");
+    return GPEMU_ERR_HIP;
+  }
+  GP_TRY(upload(dL, L, k * N * N, st));
+  {
+    // W_p = L_p^-1 by the blocked MFMA triangular inverse, written transposed into Wt[p]
+    const int64_t N64 = round_up(N, 64);
+    DevScope inv(st);
+    double *sA = nullptr, *sD = nullptr, *sW = nullptr, *sT = nullptr;
+    GP_TRY(inv.alloc(&sA, N64 * N64));
+    GP_TRY(inv.alloc(&sD, N64 * 64));
+    GP_TRY(inv.alloc(&sW, N64 * N64));
+    GP_TRY(inv.alloc(&sT, N64 * N64));
+    if (hipMemsetAsync(m->Wt, 0, sizeof(double) * (size_t)(k * Np * Np), st) != hipSuccess) {
+      set_error("hipMemsetAsync failed");
+      return GPEMU_ERR_HIP;
+    }
+    for (int64_t p = 0; p < k; ++p)
+      GP_TRY(device_invert_factor_to_Wt(dL + p * N * N, N, m->Wt + p * Np * Np, Np, sA, sD, sW, sT, st));
+    if (hipStreamSynchronize(st) != hipSuccess) {
+      set_error("model_create: triangular inverse failed: %s", hipGetErrorString(hipGetLastError()));
+      return GPEMU_ERR_HIP;
+    }
+  }
+  if (hipStreamSynchronize(st) != hipSuccess) {
+    set_error("model_create: device synchronisation failed: %s", hipGetErrorString(hipGetLastError()));
+    return GPEMU_ERR_HIP;
+  }
   return GPEMU_OK;
 }
 
@@ -349,142 +452,11 @@ int gpemu_model_create(gpemu_model **out, int device, int64_t N, int64_t d, int6
   }
   m->kernel_kind = kernel_kind; m->nu = nu;
   m->has_const = has_const ? 1 : 0; m->has_noise = has_noise ? 1 : 0;
-  const int64_t Np = m->Npad;
-  int rc = GPEMU_OK;
-  double *dL = nullptr;
-  auto fail = [&](int code) {
-    hipFree(dL);
+  const int rc = model_fill(m, X_train, ls, constv, noise, alpha, L, components, scaler_mean, scaler_scale, cov_unexplained);
+  if (rc != GPEMU_OK) {
     gpemu_model_destroy(m);
-    return code;
-  };
-  if (hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking) != hipSuccess) {
-    set_error("hipStreamCreate failed");
-    return fail(GPEMU_ERR_HIP);
+    return rc;
   }
-  hipStream_t st = m->stream;
-
-  // host staging of the small padded arrays; `direct`: the kernels whose value is not flat at r = 0 (Matern 0.5, general
-  // nu < 1) recompute the distance of near-coincident pairs from the coordinates (predict_dev.h: KstarDirect)
-  const int kkind = kstar_kind(m);
-  const bool direct = kkind == 1 || (kkind == 4 && nu < 1.0);
-  const int dp = m->dp;
-  std::vector<double> hXs(direct ? (size_t)(k * Np * dp) : 0, 0.0), hls((size_t)(k * dp), 1.0),
-      hc((size_t)k, 0.0), hkd((size_t)k, 1.0), hal((size_t)(k * Np), 0.0), hjit((size_t)k, 0.0);
-  for (int64_t p = 0; p < k; ++p) {
-    for (int64_t dd = 0; dd < d; ++dd) {
-      double l = ls[p * d + dd];
-      if (!(l > 0.0)) { set_error("length scale must be positive"); return fail(GPEMU_ERR_ARG); }
-      hls[p * dp + dd] = l;
-    }
-    if (direct)
-      for (int64_t j = 0; j < N; ++j)
-        for (int64_t dd = 0; dd < d; ++dd)
-          hXs[(p * Np + j) * dp + dd] = X_train[j * d + dd] / ls[p * d + dd];  // skl: X / length_scale
-    if (has_const) { hc[p] = constv[p]; hkd[p] += constv[p]; }
-    if (has_noise) hkd[p] += noise[p];
-    for (int64_t j = 0; j < N; ++j) hal[p * Np + j] = alpha[p * N + j];
-    // the fit's alpha jitter (skl _gpr.py:346-348: K + alpha I = L L^T): K_00 - kernel_.diag, K_00 = L_00^2
-    hjit[p] = std::fma(L[p * N * N], L[p * N * N], -hkd[p]);
-  }
-#define GP_STEP(expr) if ((rc = (expr)) != GPEMU_OK) return fail(rc)
-  GP_STEP(dev_alloc(&m->ls, k * dp));
-  GP_STEP(dev_alloc(&m->constv, k));
-  GP_STEP(dev_alloc(&m->kdiag, k));
-  GP_STEP(dev_alloc(&m->alpha, k * Np));
-  GP_STEP(dev_alloc(&m->cv_jit, k));
-  GP_STEP(dev_alloc(&m->Wt, k * Np * Np));
-  GP_STEP(dev_alloc(&m->Xtr, Np * dp));
-  GP_STEP(dev_alloc(&m->comp, k * F));
-  GP_STEP(dev_alloc(&m->smean, F));
-  GP_STEP(dev_alloc(&m->sscale, F));
-  GP_STEP(dev_alloc(&m->cunexpl, F * F));
-  GP_STEP(dev_alloc(&dL, k * N * N));
-  GP_STEP(upload(m->ls, hls.data(), k * dp, st));
-  {
-    std::vector<double> hX((size_t)(Np * dp), 0.0);
-    for (int64_t j = 0; j < N; ++j)
-      for (int64_t dd = 0; dd < d; ++dd) hX[(size_t)(j * dp + dd)] = X_train[j * d + dd];
-    GP_STEP(upload(m->Xtr, hX.data(), Np * dp, st));
-    if (hipStreamSynchronize(st) != hipSuccess) {   // hX goes out of scope
-      set_error("model_create: upload failed");
-      return fail(GPEMU_ERR_HIP);
-    }
-  }
-  {
-    // the cross-kernel's operands for the matrix cores (kstar_host.h)
-    KstarHost kh;
-    build_kstar_operands(N, Np, d, k, kkind, X_train, ls, alpha, kh);
-    if (kkind == 4) {   // the constants of nu behind the exponential's table (predict_dev.h: kstar_matern_nu)
-      const MaternNu mn = matern_nu_constants(nu);
-      const size_t n0 = kh.tab.size(), nw = (sizeof(MaternNu) + sizeof(double) - 1) / sizeof(double);
-      kh.tab.resize(n0 + nw, 0.0);
-      std::memcpy(kh.tab.data() + n0, &mn, sizeof(MaternNu));
-    }
-    m->ksteps = kh.ksteps;
-    GP_STEP(dev_alloc(&m->Xa, (int64_t)kh.Xa.size()));
-    GP_STEP(dev_alloc(&m->alf, (int64_t)kh.alf.size()));
-    GP_STEP(dev_alloc(&m->qsc, (int64_t)kh.qsc.size()));
-    GP_STEP(dev_alloc(&m->qof, (int64_t)kh.qof.size()));
-    GP_STEP(dev_alloc(&m->etab, (int64_t)kh.tab.size()));
-    GP_STEP(upload(m->Xa, kh.Xa.data(), (int64_t)kh.Xa.size(), st));
-    GP_STEP(upload(m->alf, kh.alf.data(), (int64_t)kh.alf.size(), st));
-    GP_STEP(upload(m->qsc, kh.qsc.data(), (int64_t)kh.qsc.size(), st));
-    GP_STEP(upload(m->qof, kh.qof.data(), (int64_t)kh.qof.size(), st));
-    GP_STEP(upload(m->etab, kh.tab.data(), (int64_t)kh.tab.size(), st));
-    std::vector<double> hinv(hls.size());
-    if (direct) {
-      for (size_t i = 0; i < hls.size(); ++i) hinv[i] = 1.0 / hls[i];
-      GP_STEP(dev_alloc(&m->Xs, k * Np * dp));
-      GP_STEP(dev_alloc(&m->inv_ls, k * dp));
-      GP_STEP(upload(m->Xs, hXs.data(), k * Np * dp, st));
-      GP_STEP(upload(m->inv_ls, hinv.data(), k * dp, st));
-    }
-    if (hipStreamSynchronize(st) != hipSuccess) {   // the staging vectors go out of scope
-      set_error("model_create: upload failed");
-      return fail(GPEMU_ERR_HIP);
-    }
-  }
-  GP_STEP(upload(m->constv, hc.data(), k, st));
-  GP_STEP(upload(m->kdiag, hkd.data(), k, st));
-  GP_STEP(upload(m->alpha, hal.data(), k * Np, st));
-  GP_STEP(upload(m->cv_jit, hjit.data(), k, st));
-  GP_STEP(upload(m->comp, components, k * F, st));
-  GP_STEP(upload(m->smean, scaler_mean, F, st));
-  GP_STEP(upload(m->sscale, scaler_scale, F, st));
-  if (cov_unexplained) {
-    GP_STEP(upload(m->cunexpl, cov_unexplained, F * F, st));
-  } else if (hipMemsetAsync(m->cunexpl, 0, sizeof(double) * (size_t)(F * F), st) != hipSuccess) {
-    set_error("hipMemsetAsync failed");
-    return fail(GPEMU_ERR_HIP);
-  }
-  GP_STEP(upload(dL, L, k * N * N, st));
-  {
-    // W_p = L_p^-1 by the blocked MFMA triangular inverse, written transposed into Wt[p]
-    const int64_t N64 = round_up(N, 64);
-    double *sA = nullptr, *sD = nullptr, *sW = nullptr, *sT = nullptr;
-    rc = dev_alloc(&sA, N64 * N64);
-    if (rc == GPEMU_OK) rc = dev_alloc(&sD, N64 * 64);
-    if (rc == GPEMU_OK) rc = dev_alloc(&sW, N64 * N64);
-    if (rc == GPEMU_OK) rc = dev_alloc(&sT, N64 * N64);
-    if (rc == GPEMU_OK && hipMemsetAsync(m->Wt, 0, sizeof(double) * (size_t)(k * Np * Np), st) != hipSuccess) {
-      set_error("hipMemsetAsync failed");
-      rc = GPEMU_ERR_HIP;
-    }
-    for (int64_t p = 0; p < k && rc == GPEMU_OK; ++p)
-      rc = device_invert_factor_to_Wt(dL + p * N * N, N, m->Wt + p * Np * Np, Np, sA, sD, sW, sT, st);
-    if (rc == GPEMU_OK && hipStreamSynchronize(st) != hipSuccess) {
-      set_error("model_create: triangular inverse failed: %s", hipGetErrorString(hipGetLastError()));
-      rc = GPEMU_ERR_HIP;
-    }
-    hipFree(sA); hipFree(sD); hipFree(sW); hipFree(sT);
-    if (rc != GPEMU_OK) return fail(rc);
-  }
-#undef GP_STEP
-  if (hipStreamSynchronize(st) != hipSuccess) {
-    set_error("model_create: device synchronisation failed: %s", hipGetErrorString(hipGetLastError()));
-    return fail(GPEMU_ERR_HIP);
-  }
-  hipFree(dL);
   *out = m;
   return GPEMU_OK;
 }
@@ -493,20 +465,20 @@ int gpemu_model_destroy(gpemu_model *m) {
   if (!m) return GPEMU_OK;
   hipSetDevice(m->device);
   if (m->stream) hipStreamSynchronize(m->stream);
-  hipFree(m->Xs); hipFree(m->inv_ls); hipFree(m->ls); hipFree(m->Xa); hipFree(m->alf); hipFree(m->qsc); hipFree(m->qof);
-  hipFree(m->etab); hipFree(m->constv); hipFree(m->kdiag);
-  hipFree(m->alpha); hipFree(m->cv_jit); hipFree(m->Wt); hipFree(m->Xtr); hipFree(m->comp); hipFree(m->smean); hipFree(m->sscale);
-  hipFree(m->cunexpl); hipFree(m->yexp); hipFree(m->yerr); hipFree(m->lo); hipFree(m->hi);
-  for (const gpemu_model::LikEntry &en : m->lik_cache) free_lik_entry(en);
-  hipFree(m->ycov); hipFree(m->srcs);
-  hipFree(m->exact_scratch);
-  (void)hipFree(m->grad_ws);
-  (void)hipFree(m->grad_lik_ws);
-  hipFree(m->blk_start); hipFree(m->blk_of);
-  for (const gpemu_model::SchedEntry &en : m->sched_cache) { hipFree(en.items); hipFree(en.cnt); }
-  for (const gpemu_model::SchedEntry &en : m->sm_cache) { hipFree(en.items); hipFree(en.cnt); }
-  (void)hipFree(m->lik_terms);
-  (void)hipFree(m->lik_tickets);
+  dev_free(m->Xs); dev_free(m->inv_ls); dev_free(m->ls); dev_free(m->Xa); dev_free(m->alf); dev_free(m->qsc); dev_free(m->qof);
+  dev_free(m->etab); dev_free(m->constv); dev_free(m->kdiag);
+  dev_free(m->alpha); dev_free(m->cv_jit); dev_free(m->Wt); dev_free(m->Xtr); dev_free(m->comp); dev_free(m->smean); dev_free(m->sscale);
+  dev_free(m->cunexpl); dev_free(m->yexp); dev_free(m->yerr); dev_free(m->lo); dev_free(m->hi);
+  for (gpemu_model::LikEntry &en : m->lik_cache) free_lik_entry(en);
+  dev_free(m->ycov); dev_free(m->srcs);
+  dev_free(m->exact_scratch);
+  dev_free(m->grad_ws);
+  dev_free(m->grad_lik_ws);
+  dev_free(m->blk_start); dev_free(m->blk_of);
+  for (gpemu_model::SchedEntry &en : m->sched_cache) { dev_free(en.items); dev_free(en.cnt); }
+  for (gpemu_model::SchedEntry &en : m->sm_cache) { dev_free(en.items); dev_free(en.cnt); }
+  dev_free(m->lik_terms);
+  dev_free(m->lik_tickets);
   free_workspace(m->ws);
   for (hipEvent_t e : m->ev_pool) (void)hipEventDestroy(e);
   if (m->stream) hipStreamDestroy(m->stream);
@@ -591,20 +563,17 @@ int gpemu_gp_predict(gpemu_model *m, int64_t B, const double *X, double *mean_ou
   GP_ARG(B > 0, "B must be positive");
   GP_HIP(hipSetDevice(m->device));
   hipStream_t st = m->stream;
+  DevScope sc(st);
   double *dX = nullptr, *dm = nullptr, *dv = nullptr;
-  int rc = dev_alloc(&dX, B * m->d);
-  if (rc == GPEMU_OK) rc = dev_alloc(&dm, B * m->k);
-  if (rc == GPEMU_OK) rc = dev_alloc(&dv, B * m->k);
-  if (rc == GPEMU_OK) rc = upload(dX, X, B * m->d, st);
-  if (rc == GPEMU_OK) rc = gpemu_gp_predict_dev(m, B, dX, dm, dv, st);
-  if (rc == GPEMU_OK) {
-    hipError_t e = hipMemcpyAsync(mean_out, dm, sizeof(double) * B * m->k, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(var_out, dv, sizeof(double) * B * m->k, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) { set_error("gp_predict: %s", hipGetErrorString(e)); rc = GPEMU_ERR_HIP; }
-  }
-  hipFree(dX); hipFree(dm); hipFree(dv);
-  return rc;
+  GP_TRY(sc.alloc(&dX, B * m->d));
+  GP_TRY(sc.alloc(&dm, B * m->k));
+  GP_TRY(sc.alloc(&dv, B * m->k));
+  GP_TRY(upload(dX, X, B * m->d, st));
+  GP_TRY(gpemu_gp_predict_dev(m, B, dX, dm, dv, st));
+  GP_TRY(sc.download(mean_out, dm, B * m->k));
+  GP_TRY(sc.download(var_out, dv, B * m->k));
+  GP_HIP(hipStreamSynchronize(st));
+  return GPEMU_OK;
 }
 
 // ---- joint predictive covariance and draws (k_pcov.hip) --------------------------------------------------
@@ -624,15 +593,14 @@ int gpemu_gp_predict_cov_dev(gpemu_model *m, int64_t M1, const double *dX1, int6
   hipStream_t st = stream ? (hipStream_t)stream : m->stream;
   if (dmean) {
     // the mean through gp_predict's own launches: the same bits
+    DevScope sc(st);
     double *dvar = nullptr;
-    GP_TRY(dev_alloc(&dvar, M1 * m->k));
-    int rc = gpemu_gp_predict_dev(m, M1, dX1, dmean, dvar, st);
-    if (rc == GPEMU_OK && hipStreamSynchronize(st) != hipSuccess) {
+    GP_TRY(sc.alloc(&dvar, M1 * m->k));
+    GP_TRY(gpemu_gp_predict_dev(m, M1, dX1, dmean, dvar, st));
+    if (hipStreamSynchronize(st) != hipSuccess) {
       set_error("gp_predict_cov: %s", hipGetErrorString(hipGetLastError()));
-      rc = GPEMU_ERR_HIP;
+      return GPEMU_ERR_HIP;
     }
-    hipFree(dvar);
-    if (rc != GPEMU_OK) return rc;
   }
   return predict_cov(m, M1, dX1, dX2 ? M2 : M1, dX2, workspace_bytes, dcov, st);
 }
@@ -647,24 +615,19 @@ int gpemu_gp_predict_cov(gpemu_model *m, int64_t M1, const double *X1, int64_t M
   if (!X2) M2 = M1;
   GP_HIP(hipSetDevice(m->device));
   hipStream_t st = m->stream;
+  DevScope sc(st);
   double *dX1 = nullptr, *dX2 = nullptr, *dm = nullptr, *dc = nullptr;
-  int rc = dev_alloc(&dX1, M1 * m->d);
-  if (rc == GPEMU_OK && X2) rc = dev_alloc(&dX2, M2 * m->d);
-  if (rc == GPEMU_OK && mean_out) rc = dev_alloc(&dm, M1 * m->k);
-  if (rc == GPEMU_OK) rc = dev_alloc(&dc, m->k * M1 * M2);
-  if (rc == GPEMU_OK) rc = upload(dX1, X1, M1 * m->d, st);
-  if (rc == GPEMU_OK && X2) rc = upload(dX2, X2, M2 * m->d, st);
-  if (rc == GPEMU_OK) rc = gpemu_gp_predict_cov_dev(m, M1, dX1, M2, dX2, workspace_bytes, dm, dc, st);
-  if (rc == GPEMU_OK) {
-    hipError_t e = hipMemcpyAsync(cov_out, dc, sizeof(double) * (size_t)(m->k * M1 * M2), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && mean_out)
-      e = hipMemcpyAsync(mean_out, dm, sizeof(double) * (size_t)(M1 * m->k), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) { set_error("gp_predict_cov: %s", hipGetErrorString(e)); rc = GPEMU_ERR_HIP; }
-  }
-  (void)hipStreamSynchronize(st);
-  hipFree(dX1); hipFree(dX2); hipFree(dm); hipFree(dc);
-  return rc;
+  GP_TRY(sc.alloc(&dX1, M1 * m->d));
+  if (X2) GP_TRY(sc.alloc(&dX2, M2 * m->d));
+  if (mean_out) GP_TRY(sc.alloc(&dm, M1 * m->k));
+  GP_TRY(sc.alloc(&dc, m->k * M1 * M2));
+  GP_TRY(upload(dX1, X1, M1 * m->d, st));
+  if (X2) GP_TRY(upload(dX2, X2, M2 * m->d, st));
+  GP_TRY(gpemu_gp_predict_cov_dev(m, M1, dX1, M2, dX2, workspace_bytes, dm, dc, st));
+  GP_TRY(sc.download(cov_out, dc, m->k * M1 * M2));
+  if (mean_out) GP_TRY(sc.download(mean_out, dm, M1 * m->k));
+  GP_HIP(hipStreamSynchronize(st));
+  return GPEMU_OK;
 }
 
 int gpemu_gp_sample(gpemu_model *m, int64_t M, const double *X, int64_t n_draws, const double *z,
@@ -676,23 +639,21 @@ int gpemu_gp_sample(gpemu_model *m, int64_t M, const double *X, int64_t n_draws,
   GP_HIP(hipSetDevice(m->device));
   hipStream_t st = m->stream;
   const int64_t k = m->k;
+  DevScope sc(st);
   double *dX = nullptr, *dm = nullptr, *dc = nullptr, *dz = nullptr, *dout = nullptr;
-  int rc = dev_alloc(&dX, M * m->d);
-  if (rc == GPEMU_OK) rc = dev_alloc(&dm, M * k);
-  if (rc == GPEMU_OK) rc = dev_alloc(&dc, k * M * M);
-  if (rc == GPEMU_OK) rc = dev_alloc(&dz, k * M * n_draws);
-  if (rc == GPEMU_OK) rc = dev_alloc(&dout, k * M * n_draws);
-  if (rc == GPEMU_OK) rc = upload(dX, X, M * m->d, st);
-  if (rc == GPEMU_OK) rc = upload(dz, z, k * M * n_draws, st);
-  if (rc == GPEMU_OK) rc = gpemu_gp_predict_cov_dev(m, M, dX, 0, nullptr, 0, dm, dc, st);
-  if (rc == GPEMU_OK) rc = sample_from_cov(m, M, n_draws, dc, dm, dz, dout, tau_out, st);
-  if (rc >= GPEMU_OK) {   // a PC whose ladder ran out (rc > 0): the others' draws are still returned
-    hipError_t e = hipMemcpyAsync(draws_out, dout, sizeof(double) * (size_t)(k * M * n_draws), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) { set_error("gp_sample: %s", hipGetErrorString(e)); rc = GPEMU_ERR_HIP; }
-  }
-  (void)hipStreamSynchronize(st);
-  hipFree(dX); hipFree(dm); hipFree(dc); hipFree(dz); hipFree(dout);
+  GP_TRY(sc.alloc(&dX, M * m->d));
+  GP_TRY(sc.alloc(&dm, M * k));
+  GP_TRY(sc.alloc(&dc, k * M * M));
+  GP_TRY(sc.alloc(&dz, k * M * n_draws));
+  GP_TRY(sc.alloc(&dout, k * M * n_draws));
+  GP_TRY(upload(dX, X, M * m->d, st));
+  GP_TRY(upload(dz, z, k * M * n_draws, st));
+  GP_TRY(gpemu_gp_predict_cov_dev(m, M, dX, 0, nullptr, 0, dm, dc, st));
+  const int rc = sample_from_cov(m, M, n_draws, dc, dm, dz, dout, tau_out, st);
+  if (rc < GPEMU_OK) return rc;
+  // a PC whose ladder ran out (rc > 0): the others' draws are still returned
+  GP_TRY(sc.download(draws_out, dout, k * M * n_draws));
+  GP_HIP(hipStreamSynchronize(st));
   return rc;
 }
 
@@ -721,37 +682,27 @@ int gpemu_model_cross_validate(gpemu_model *m, int64_t n_folds, const int32_t *f
   const int64_t max_chunk = cap_env ? atoll(cap_env) : 0;
   GP_HIP(hipSetDevice(m->device));
   hipStream_t st = m->stream;
+  DevScope sc(st);
   int *didx = nullptr, *dfoff = nullptr;
   double *dy = nullptr, *dm = nullptr, *dv = nullptr, *dcv = nullptr, *dvo = nullptr;
-  int rc = dev_alloc(&didx, N);
-  if (rc == GPEMU_OK) rc = dev_alloc(&dfoff, n_folds + 1);
-  if (rc == GPEMU_OK) rc = dev_alloc(&dy, N * k);
-  if (rc == GPEMU_OK) rc = dev_alloc(&dm, N * k);
-  if (rc == GPEMU_OK) rc = dev_alloc(&dv, N * k);
-  if (rc == GPEMU_OK && central_value) rc = dev_alloc(&dcv, N * m->F);
-  if (rc == GPEMU_OK && variance) rc = dev_alloc(&dvo, N * m->F);
-  hipError_t e = hipSuccess;
-  if (rc == GPEMU_OK) {
-    e = hipMemcpyAsync(didx, hidx.data(), sizeof(int) * (size_t)N, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(dfoff, hfoff.data(), sizeof(int) * (size_t)(n_folds + 1), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(dy, y_train, sizeof(double) * (size_t)(N * k), hipMemcpyHostToDevice, st);
-    if (e != hipSuccess) { set_error("cross_validate: %s", hipGetErrorString(e)); rc = GPEMU_ERR_HIP; }
-  }
-  if (rc == GPEMU_OK) rc = cross_validate(m, (int)n_folds, didx, dfoff, hfoff, hr0, dy, dm, dv, max_chunk);
-  if (rc == GPEMU_OK) rc = launch_cv_backproject(m, dm, dv, dcv, dvo);
-  if (rc == GPEMU_OK) {
-    e = hipMemcpyAsync(mean_pc, dm, sizeof(double) * (size_t)(N * k), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(var_pc, dv, sizeof(double) * (size_t)(N * k), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && dcv)
-      e = hipMemcpyAsync(central_value, dcv, sizeof(double) * (size_t)(N * m->F), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && dvo)
-      e = hipMemcpyAsync(variance, dvo, sizeof(double) * (size_t)(N * m->F), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) { set_error("cross_validate: %s", hipGetErrorString(e)); rc = GPEMU_ERR_HIP; }
-  }
-  (void)hipStreamSynchronize(st);
-  hipFree(didx); hipFree(dfoff); hipFree(dy); hipFree(dm); hipFree(dv); hipFree(dcv); hipFree(dvo);
-  return rc;
+  GP_TRY(sc.alloc(&didx, N));
+  GP_TRY(sc.alloc(&dfoff, n_folds + 1));
+  GP_TRY(sc.alloc(&dy, N * k));
+  GP_TRY(sc.alloc(&dm, N * k));
+  GP_TRY(sc.alloc(&dv, N * k));
+  if (central_value) GP_TRY(sc.alloc(&dcv, N * m->F));
+  if (variance) GP_TRY(sc.alloc(&dvo, N * m->F));
+  GP_TRY(upload(didx, hidx.data(), N, st));
+  GP_TRY(upload(dfoff, hfoff.data(), n_folds + 1, st));
+  GP_TRY(upload(dy, y_train, N * k, st));
+  GP_TRY(cross_validate(m, (int)n_folds, didx, dfoff, hfoff, hr0, dy, dm, dv, max_chunk));
+  GP_TRY(launch_cv_backproject(m, dm, dv, dcv, dvo));
+  GP_TRY(sc.download(mean_pc, dm, N * k));
+  GP_TRY(sc.download(var_pc, dv, N * k));
+  if (dcv) GP_TRY(sc.download(central_value, dcv, N * m->F));
+  if (dvo) GP_TRY(sc.download(variance, dvo, N * m->F));
+  GP_HIP(hipStreamSynchronize(st));
+  return GPEMU_OK;
 }
 
 // ---- likelihood ----------------------------------------------------------------------------------
@@ -834,14 +785,13 @@ int gpemu_likelihood_setup_cov(gpemu_model *m, int n_chains, const double *y_exp
       }
   } else {
     GP_HIP(hipStreamSynchronize(st));
-    for (const gpemu_model::LikEntry &en : m->lik_cache) free_lik_entry(en);
+    for (gpemu_model::LikEntry &en : m->lik_cache) free_lik_entry(en);
     m->lik_cache.clear();
     m->G = m->g0 = m->scal = m->W = m->Q = m->w0 = nullptr;
   }
   if (m->lik_cache.size() >= 64) {           // bounded: drop the oldest entry
     GP_HIP(hipStreamSynchronize(st));
-    const gpemu_model::LikEntry en = m->lik_cache.front();
-    free_lik_entry(en);
+    free_lik_entry(m->lik_cache.front());
     m->lik_cache.erase(m->lik_cache.begin());
   }
   GP_HIP(hipStreamSynchronize(st));
@@ -850,24 +800,26 @@ int gpemu_likelihood_setup_cov(gpemu_model *m, int n_chains, const double *y_exp
     GP_TRY(dev_alloc(&m->lo, m->dp)); GP_TRY(dev_alloc(&m->hi, m->dp));
     GP_TRY(dev_alloc(&m->blk_of, F));
   }
-  (void)hipFree(m->yexp);
-  m->yexp = nullptr;
+  dev_free(m->yexp);
   GP_TRY(dev_alloc(&m->yexp, NC * F));
   m->lik_chains = n_chains;
-  (void)hipFree(m->blk_start);
-  m->blk_start = nullptr;
-  (void)hipFree(m->ycov);
-  (void)hipFree(m->srcs);
-  m->ycov = m->srcs = nullptr;
+  dev_free(m->blk_start);
+  dev_free(m->ycov);
+  dev_free(m->srcs);
   m->n_src = 0;
   if (cov) GP_TRY(dev_alloc(&m->ycov, F * F));
   if (S > 0) GP_TRY(dev_alloc(&m->srcs, S * F));
   m->n_src = (int)S;
+  // the new cache entry belongs to a scope until it is complete: a failure half way leaves nothing behind
   gpemu_model::LikEntry en{n_div, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  GP_TRY(dev_alloc(&en.G, nblk * k * k)); GP_TRY(dev_alloc(&en.g0, NC * nblk * k));
-  GP_TRY(dev_alloc(&en.scal, NC * 2 * nblk)); GP_TRY(dev_alloc(&m->blk_start, nblk + 1));
-  if (S > 0) {
-    GP_TRY(dev_alloc(&en.W, nblk * k * S)); GP_TRY(dev_alloc(&en.Q, nblk * S * S)); GP_TRY(dev_alloc(&en.w0, NC * nblk * S));
+  {
+    DevScope entry(st);
+    GP_TRY(entry.alloc(&en.G, nblk * k * k)); GP_TRY(entry.alloc(&en.g0, NC * nblk * k));
+    GP_TRY(entry.alloc(&en.scal, NC * 2 * nblk)); GP_TRY(dev_alloc(&m->blk_start, nblk + 1));
+    if (S > 0) {
+      GP_TRY(entry.alloc(&en.W, nblk * k * S)); GP_TRY(entry.alloc(&en.Q, nblk * S * S)); GP_TRY(entry.alloc(&en.w0, NC * nblk * S));
+    }
+    for (double *p : {en.G, en.g0, en.scal, en.W, en.Q, en.w0}) entry.release(p);
   }
   m->G = en.G; m->g0 = en.g0; m->scal = en.scal; m->W = en.W; m->Q = en.Q; m->w0 = en.w0;
   m->lik_cache.push_back(en);
@@ -884,22 +836,20 @@ int gpemu_likelihood_setup_cov(gpemu_model *m, int n_chains, const double *y_exp
   if (cov) GP_TRY(upload(m->ycov, cov, F * F, st));
   if (S > 0) GP_TRY(upload(m->srcs, sources, S * F, st));
   GP_HIP(hipStreamSynchronize(st));  // hlo/hhi are stack buffers
-  double *dA = nullptr, *dPT = nullptr, *dZ = nullptr;
-  int *dinfo = nullptr;
-  int rc = dev_alloc(&dA, F * F);
-  if (rc == GPEMU_OK) rc = dev_alloc(&dPT, nblk * chol_scratch_size(F));
-  if (rc == GPEMU_OK) rc = dev_alloc(&dZ, F * (k + NC + S));
-  if (rc == GPEMU_OK) rc = dev_alloc(&dinfo, nblk);
   std::vector<int> info((size_t)nblk, 0);
-  if (rc == GPEMU_OK && hipMemsetAsync(dinfo, 0, sizeof(int) * nblk, st) != hipSuccess) rc = GPEMU_ERR_HIP;
-  if (rc == GPEMU_OK) rc = launch_lik_setup(m, hstart, dA, dPT, dZ, dinfo, st);
-  if (rc == GPEMU_OK) {
-    hipError_t e = hipMemcpyAsync(info.data(), dinfo, sizeof(int) * nblk, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) { set_error("likelihood_setup: %s", hipGetErrorString(e)); rc = GPEMU_ERR_HIP; }
+  {
+    DevScope sc(st);
+    double *dA = nullptr, *dPT = nullptr, *dZ = nullptr;
+    int *dinfo = nullptr;
+    GP_TRY(sc.alloc(&dA, F * F));
+    GP_TRY(sc.alloc(&dPT, nblk * chol_scratch_size(F)));
+    GP_TRY(sc.alloc(&dZ, F * (k + NC + S)));
+    GP_TRY(sc.alloc(&dinfo, nblk));
+    GP_HIP(hipMemsetAsync(dinfo, 0, sizeof(int) * nblk, st));
+    GP_TRY(launch_lik_setup(m, hstart, dA, dPT, dZ, dinfo, st));
+    GP_TRY(sc.download(info.data(), dinfo, nblk));
+    GP_HIP(hipStreamSynchronize(st));
   }
-  hipFree(dA); hipFree(dPT); hipFree(dZ); hipFree(dinfo);
-  if (rc != GPEMU_OK) return rc;
   for (int64_t o = 0; o < nblk; ++o) {
     if (info[o] != 0) {
       set_error("likelihood_setup: A = C_unexpl/n o ss^T + %s is not positive definite "
@@ -950,18 +900,15 @@ int gpemu_logpost(gpemu_model *m, int64_t B, const double *X, double *out, int m
   GP_ARG(X && out, "null pointer");
   GP_HIP(hipSetDevice(m->device));
   hipStream_t st = m->stream;
+  DevScope sc(st);
   double *dX = nullptr, *dout = nullptr;
-  int rc = dev_alloc(&dX, B * m->d);
-  if (rc == GPEMU_OK) rc = dev_alloc(&dout, B);
-  if (rc == GPEMU_OK) rc = upload(dX, X, B * m->d, st);
-  if (rc == GPEMU_OK) rc = gpemu_logpost_dev(m, B, dX, dout, mode, st);
-  if (rc == GPEMU_OK) {
-    hipError_t e = hipMemcpyAsync(out, dout, sizeof(double) * B, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) { set_error("logpost: %s", hipGetErrorString(e)); rc = GPEMU_ERR_HIP; }
-  }
-  hipFree(dX); hipFree(dout);
-  return rc;
+  GP_TRY(sc.alloc(&dX, B * m->d));
+  GP_TRY(sc.alloc(&dout, B));
+  GP_TRY(upload(dX, X, B * m->d, st));
+  GP_TRY(gpemu_logpost_dev(m, B, dX, dout, mode, st));
+  GP_TRY(sc.download(out, dout, B));
+  GP_HIP(hipStreamSynchronize(st));
+  return GPEMU_OK;
 }
 
 int gpemu_logpost_groups(gpemu_model *const *models, int n_groups, int64_t B, const double *X, double *out, int mode) {
@@ -991,26 +938,21 @@ int gpemu_logpost_groups(gpemu_model *const *models, int n_groups, int64_t B, co
   GP_HIP(hipSetDevice(m0->device));
   hipStream_t st = m0->stream;
   const LaunchSwitches sw = read_launch_switches();
+  DevScope sc(st);
   double *dX = nullptr, *dout = nullptr;
-  int rc = dev_alloc(&dX, B * m0->d);
-  if (rc == GPEMU_OK) rc = dev_alloc(&dout, B);
-  if (rc == GPEMU_OK) rc = upload(dX, X, B * m0->d, st);
-  for (int64_t off = 0; off < B && rc == GPEMU_OK; off += MAX_CHUNK) {
+  GP_TRY(sc.alloc(&dX, B * m0->d));
+  GP_TRY(sc.alloc(&dout, B));
+  GP_TRY(upload(dX, X, B * m0->d, st));
+  for (int64_t off = 0; off < B; off += MAX_CHUNK) {
     const int64_t nb = (B - off < MAX_CHUNK) ? (B - off) : MAX_CHUNK;
     path_count(GPEMU_PATH_PREDICT_PASS);
-    rc = ensure_workspace(m0, nb);   // (before ws.Xq is read: it may move)
-    if (rc != GPEMU_OK) break;
+    GP_TRY(ensure_workspace(m0, nb));   // (before ws.Xq is read: it may move)
     const ProposeArgs raw = raw_rows(m0, nb, dX + off * m0->d);
-    rc = logpost_eval(models, n_groups, nb, m0->ws.Xq, dout + off, st, sw, nullptr, &raw);
+    GP_TRY(logpost_eval(models, n_groups, nb, m0->ws.Xq, dout + off, st, sw, nullptr, &raw));
   }
-  if (rc == GPEMU_OK) {
-    hipError_t e = hipMemcpyAsync(out, dout, sizeof(double) * B, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) { set_error("logpost_groups: %s", hipGetErrorString(e)); rc = GPEMU_ERR_HIP; }
-  }
-  (void)hipStreamSynchronize(st);
-  hipFree(dX); hipFree(dout);
-  return rc;
+  GP_TRY(sc.download(out, dout, B));
+  GP_HIP(hipStreamSynchronize(st));
+  return GPEMU_OK;
 }
 
 // ---- truncation covariance -----------------------------------------------------------------------
@@ -1044,39 +986,29 @@ int gpemu_truncation_cov(int device, int64_t n_comp, int64_t F, int64_t n_pc, co
   const int64_t Fp = round_up(F, 64), Kp = round_up(K, 32);
   double *dcomp = nullptr, *dev_ = nullptr, *dA = nullptr, *dB = nullptr, *dC = nullptr;
   hipStream_t st = nullptr;   // a one-off setup product: the null stream
-  int rc = dev_alloc(&dcomp, n_comp * F);
-  if (rc == GPEMU_OK) rc = dev_alloc(&dev_, n_comp);
-  if (rc == GPEMU_OK) rc = dev_alloc(&dA, Kp * Fp);
-  if (rc == GPEMU_OK) rc = dev_alloc(&dB, Kp * Fp);
-  if (rc == GPEMU_OK) rc = dev_alloc(&dC, Fp * Fp);
-  if (rc == GPEMU_OK) rc = upload(dcomp, components, n_comp * F, st);
-  if (rc == GPEMU_OK) rc = upload(dev_, explained_variance, n_comp, st);
-  if (rc == GPEMU_OK) {
-    const int64_t n = Kp * Fp;
-    hipLaunchKernelGGL(trunc_pack_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, dcomp, dev_, dA, dB,
-                       (int)F, (int)Fp, (int)K, (int)Kp, (int)n_pc);
-    GemmArgs g;                       // C[f][g] = sum_r A[r][f] * (lambda_r A[r][g]): both operands k-major
-    g.A = dA; g.B = dB; g.C = dC;
-    g.lda = Fp; g.ldb = Fp; g.ldc = Fp;
-    g.M = (int)Fp; g.N = (int)Fp; g.K = (int)Kp;
-    rc = launch_gemm(g, true, true, 1, st);
-  }
-  if (rc == GPEMU_OK) {
-    hipError_t e = hipMemcpy2DAsync(cov_out, sizeof(double) * F, dC, sizeof(double) * Fp, sizeof(double) * F, (size_t)F,
-                                    hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) { set_error("truncation_cov: %s", hipGetErrorString(e)); rc = GPEMU_ERR_HIP; }
-  }
-  hipFree(dcomp); hipFree(dev_); hipFree(dA); hipFree(dB); hipFree(dC);
-  return rc;
+  DevScope sc(st);
+  GP_TRY(sc.alloc(&dcomp, n_comp * F));
+  GP_TRY(sc.alloc(&dev_, n_comp));
+  GP_TRY(sc.alloc(&dA, Kp * Fp));
+  GP_TRY(sc.alloc(&dB, Kp * Fp));
+  GP_TRY(sc.alloc(&dC, Fp * Fp));
+  GP_TRY(upload(dcomp, components, n_comp * F, st));
+  GP_TRY(upload(dev_, explained_variance, n_comp, st));
+  const int64_t n = Kp * Fp;
+  hipLaunchKernelGGL(trunc_pack_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, dcomp, dev_, dA, dB,
+                     (int)F, (int)Fp, (int)K, (int)Kp, (int)n_pc);
+  GemmArgs g;                       // C[f][g] = sum_r A[r][f] * (lambda_r A[r][g]): both operands k-major
+  g.A = dA; g.B = dB; g.C = dC;
+  g.lda = Fp; g.ldb = Fp; g.ldc = Fp;
+  g.M = (int)Fp; g.N = (int)Fp; g.K = (int)Kp;
+  GP_TRY(launch_gemm(g, true, true, 1, st));
+  GP_HIP(hipMemcpy2DAsync(cov_out, sizeof(double) * F, dC, sizeof(double) * Fp, sizeof(double) * F, (size_t)F,
+                          hipMemcpyDeviceToHost, st));
+  GP_HIP(hipStreamSynchronize(st));
+  return GPEMU_OK;
 }
 
 // ---- full predict ----------------------------------------------------------------------------------
-}  // extern "C"
-namespace gpemu {
-}  // namespace gpemu
-extern "C" {
-
 int gpemu_predict_full_dev(gpemu_model *m, int64_t B, const double *dX, double n_div, double *dcv,
                            double *dcov, void *stream) {
   GP_ARG(m && dX && dcv && dcov, "null pointer");
@@ -1101,21 +1033,17 @@ int gpemu_predict_full(gpemu_model *m, int64_t B, const double *X, double n_div,
   GP_HIP(hipSetDevice(m->device));
   hipStream_t st = m->stream;
   const int64_t F = m->F;
+  DevScope sc(st);
   double *dX = nullptr, *dcv = nullptr, *dcov = nullptr;
-  int rc = dev_alloc(&dX, B * m->d);
-  if (rc == GPEMU_OK) rc = dev_alloc(&dcv, B * F);
-  if (rc == GPEMU_OK) rc = dev_alloc(&dcov, B * F * F);
-  if (rc == GPEMU_OK) rc = upload(dX, X, B * m->d, st);
-  if (rc == GPEMU_OK) rc = gpemu_predict_full_dev(m, B, dX, n_div, dcv, dcov, st);
-  if (rc == GPEMU_OK) {
-    hipError_t e = hipMemcpyAsync(cv_out, dcv, sizeof(double) * B * F, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess)
-      e = hipMemcpyAsync(cov_out, dcov, sizeof(double) * B * F * F, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) { set_error("predict_full: %s", hipGetErrorString(e)); rc = GPEMU_ERR_HIP; }
-  }
-  hipFree(dX); hipFree(dcv); hipFree(dcov);
-  return rc;
+  GP_TRY(sc.alloc(&dX, B * m->d));
+  GP_TRY(sc.alloc(&dcv, B * F));
+  GP_TRY(sc.alloc(&dcov, B * F * F));
+  GP_TRY(upload(dX, X, B * m->d, st));
+  GP_TRY(gpemu_predict_full_dev(m, B, dX, n_div, dcv, dcov, st));
+  GP_TRY(sc.download(cv_out, dcv, B * F));
+  GP_TRY(sc.download(cov_out, dcov, B * F * F));
+  GP_HIP(hipStreamSynchronize(st));
+  return GPEMU_OK;
 }
 
 }  // extern "C"

@@ -46,10 +46,16 @@ int allow_dynamic_lds(const void *fn, int bytes);
 
 static inline int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
 
-// one relaxed host-side increment per launch decision (gpemu_path_counts; enum gpemu_path in gpemu.h)
-void path_count(int path);
-void fit_path_count(int path);   // the same for enum gpemu_fit_path (gpemu_fit_path_counts)
-void wide_path_count(int path);  // ... and for enum gpemu_wide_path (gpemu_wide_path_counts): d > 8 only
+// one relaxed host-side increment per launch decision, in one table (gpemu_api.hip) with a row per family of gpemu.h;
+// a path outside its family's enum is not counted
+enum PathFamily { PATHS_LOGPOST, PATHS_FIT, PATHS_WIDE, PATHS_SRC, PATHS_GRAD, PATH_FAMILIES };
+void count_path(PathFamily family, int path);
+int read_path_counts(PathFamily family, int64_t *out, int64_t n);     // what the five public gpemu_*_path_counts return
+static inline void path_count(int path) { count_path(PATHS_LOGPOST, path); }    // enum gpemu_path
+static inline void fit_path_count(int path) { count_path(PATHS_FIT, path); }    // enum gpemu_fit_path
+static inline void wide_path_count(int path) { count_path(PATHS_WIDE, path); }  // enum gpemu_wide_path: d > 8 only
+static inline void src_path_count(int path) { count_path(PATHS_SRC, path); }    // enum gpemu_src_path
+static inline void grad_path_count(int path) { count_path(PATHS_GRAD, path); }  // enum gpemu_grad_path
 
 constexpr int DPAD = 8;        // parameter dimensions padded to 8 (reference uses d = 6 or 7) ...
 constexpr int DPAD_WIDE = 16;  // ... or, for 9 <= d <= 16, to 16 (separate instantiations: d <= 8 keeps the code of DPAD)
@@ -308,7 +314,6 @@ int launch_loglik_tasks(gpemu_model *const *ms, int ng, int64_t B, const double 
 // block-diagonal sum to dout and left the accept to this launch): adds the Woodbury correction, finishes the stretch move
 int launch_source_correction(gpemu_model *const *ms, int ng, int64_t B, const double *dXq_padded, double *dout,
                              hipStream_t st, const AcceptArgs *aa);
-void src_path_count(int path);   // enum gpemu_src_path (gpemu_src_path_counts)
 // small emulators (N <= 256 design points, k_halfstep.hip): cross-kernel + triangular GEMM of all groups in one launch,
 // then the likelihood launch; the bits of the general path.  Launch only where halfstep_fits
 bool halfstep_fits(gpemu_model *const *ms, int ng, int64_t B, const LaunchSwitches &sw);
@@ -345,3 +350,5 @@ int sample_from_cov(gpemu_model *m, int64_t M, int64_t n, const double *dcov, co
 int prof_mark(gpemu_model *m, hipStream_t st);
 void prof_pair(gpemu_model *m, int which, int e0, int e1);
 }  // namespace gpemu
+
+#include "devmem.h"   // who owns device memory: DevScope, dev_reserve, dev_alloc / dev_free

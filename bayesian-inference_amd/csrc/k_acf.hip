@@ -141,29 +141,11 @@ int gpemu_sampler_acf(gpemu_sampler *s, int64_t first, int64_t n_steps, int64_t 
   const bool fresh = lag0 == 0 || s->acf_first != first || s->acf_n != n_steps || s->acf_w0 != w0 || s->acf_nw != nw;
   const size_t need_part = sizeof(double) * (size_t)nchunk * (size_t)n_lags * (size_t)S;
   const size_t need_acf = sizeof(double) * (size_t)n_lags * (size_t)S, need_mean = sizeof(double) * (size_t)S;
-  if (s->acf_part_bytes < need_part) {
-    GP_HIP(hipStreamSynchronize(st));
-    (void)hipFree(s->acf_part);
-    s->acf_part = nullptr; s->acf_part_bytes = 0;
-    GP_HIP(hipMalloc((void **)&s->acf_part, need_part));
-    s->acf_part_bytes = need_part;
-  }
-  if (s->acf_acf_bytes < need_acf) {
-    GP_HIP(hipStreamSynchronize(st));
-    (void)hipFree(s->acf_acf);
-    s->acf_acf = nullptr; s->acf_acf_bytes = 0;
-    GP_HIP(hipMalloc((void **)&s->acf_acf, need_acf));
-    s->acf_acf_bytes = need_acf;
-  }
-  if (s->acf_mean_bytes < need_mean) {
-    GP_ARG(lag0 == 0, "the first block of an estimate must start at lag 0");
-    GP_HIP(hipStreamSynchronize(st));
-    (void)hipFree(s->acf_mean); (void)hipFree(s->acf_acf0);
-    s->acf_mean = s->acf_acf0 = nullptr; s->acf_mean_bytes = 0;
-    GP_HIP(hipMalloc((void **)&s->acf_mean, need_mean));
-    GP_HIP(hipMalloc((void **)&s->acf_acf0, need_mean));
-    s->acf_mean_bytes = need_mean;
-  }
+  GP_TRY(dev_reserve(&s->acf_part_bytes, need_part, {st}, {dev_field_bytes(&s->acf_part, need_part)}));
+  GP_TRY(dev_reserve(&s->acf_acf_bytes, need_acf, {st}, {dev_field_bytes(&s->acf_acf, need_acf)}));
+  if (s->acf_mean_bytes < need_mean) GP_ARG(lag0 == 0, "the first block of an estimate must start at lag 0");
+  GP_TRY(dev_reserve(&s->acf_mean_bytes, need_mean, {st},
+                     {dev_field_bytes(&s->acf_mean, need_mean), dev_field_bytes(&s->acf_acf0, need_mean)}));
   if (fresh) {
     GP_ARG(lag0 == 0, "the first block of an estimate must start at lag 0");
     hipLaunchKernelGGL(acf_sum_kernel, dim3(gs, 1, (unsigned)nchunk), block, 0, st, chain, n_t, S, ld, tchunk, s->acf_part);
@@ -174,15 +156,14 @@ int gpemu_sampler_acf(gpemu_sampler *s, int64_t first, int64_t n_steps, int64_t 
                      tchunk, lag0, (int)n_lags, s->acf_part);
   hipLaunchKernelGGL(acf_reduce_kernel, dim3(gs, (unsigned)n_lags), block, 0, st, s->acf_part, S, (int)n_lags, nchunk,
                      s->acf_acf, s->acf_acf0, lag0 == 0 ? 1 : 0);
+  DevScope sc(st);
   double *df = nullptr;
-  GP_HIP(hipMalloc((void **)&df, sizeof(double) * (size_t)n_lags * s->d));
+  GP_TRY(sc.alloc(&df, n_lags * s->d));
   hipLaunchKernelGGL(acf_walker_mean_kernel, dim3((unsigned)n_lags, (unsigned)s->d), block, 0, st, s->acf_acf, s->acf_acf0, S,
                      (int)s->d, (int)nw, df);
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess) e = hipMemcpyAsync(f_out, df, sizeof(double) * (size_t)n_lags * s->d, hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  (void)hipFree(df);
-  if (e != hipSuccess) { set_error("sampler_acf: %s", hipGetErrorString(e)); return GPEMU_ERR_HIP; }
+  GP_HIP(hipGetLastError());
+  GP_TRY(sc.download(f_out, df, n_lags * s->d));
+  GP_HIP(hipStreamSynchronize(st));
   return GPEMU_OK;
 }
 

@@ -172,24 +172,14 @@ int cross_validate(gpemu_model *m, int n_folds, const int *didx, const int *dfof
 
   double *G = nullptr, *A = nullptr, *W = nullptr, *T = nullptr, *Dinv = nullptr, *u = nullptr;
   int *dinfo = nullptr;
-  struct Free {
-    std::vector<void *> p;
-    ~Free() { for (void *q : p) (void)hipFree(q); }
-  } fr;
-  auto alloc = [&](double **q, int64_t n) -> int {
-    GP_HIP(hipMalloc((void **)q, sizeof(double) * (size_t)n));
-    fr.p.push_back(*q);
-    return GPEMU_OK;
-  };
-  int rc = GPEMU_OK;
-  if ((rc = alloc(&G, chunk * mp * Kcap)) != GPEMU_OK) return rc;
-  if ((rc = alloc(&A, chunk * mp * mp)) != GPEMU_OK) return rc;
-  if ((rc = alloc(&W, chunk * mp * mp)) != GPEMU_OK) return rc;
-  if ((rc = alloc(&T, chunk * mp * mp)) != GPEMU_OK) return rc;
-  if ((rc = alloc(&Dinv, chunk * mp * CV_NB)) != GPEMU_OK) return rc;
-  if ((rc = alloc(&u, chunk * mp)) != GPEMU_OK) return rc;
-  GP_HIP(hipMalloc((void **)&dinfo, sizeof(int) * (size_t)nprob));
-  fr.p.push_back(dinfo);
+  DevScope sc(st);
+  GP_TRY(sc.alloc(&G, chunk * mp * Kcap));
+  GP_TRY(sc.alloc(&A, chunk * mp * mp));
+  GP_TRY(sc.alloc(&W, chunk * mp * mp));
+  GP_TRY(sc.alloc(&T, chunk * mp * mp));
+  GP_TRY(sc.alloc(&Dinv, chunk * mp * CV_NB));
+  GP_TRY(sc.alloc(&u, chunk * mp));
+  GP_TRY(sc.alloc(&dinfo, nprob));
   GP_HIP(hipMemsetAsync(dinfo, 0, sizeof(int) * (size_t)nprob, st));
 
   CvChunk c;
@@ -213,20 +203,20 @@ int cross_validate(gpemu_model *m, int n_folds, const int *didx, const int *dfof
       g.C = A + (int64_t)z0 * mp * mp; g.ldc = mp; g.strideC = mp * mp;
       g.M = (int)mp; g.N = (int)mp; g.K = (int)round_up(N - hr0[f], 16);
       g.lower_only = 1;
-      if ((rc = launch_gemm(g, false, false, z1 - z0, st)) != GPEMU_OK) return rc;
+      GP_TRY(launch_gemm(g, false, false, z1 - z0, st));
       z0 = z1;
     }
     hipLaunchKernelGGL(cv_pad_diag_kernel, dim3((unsigned)nb), dim3(64), 0, st, c);
     GP_HIP(hipGetLastError());
-    if ((rc = device_cholesky_blocked(A, mp, Dinv, dinfo + q0, st, nb)) != GPEMU_OK) return rc;
-    if ((rc = device_trtri_blocked(A, mp, Dinv, W, T, st, nb, true)) != GPEMU_OK) return rc;
+    GP_TRY(device_cholesky_blocked(A, mp, Dinv, dinfo + q0, st, nb));
+    GP_TRY(device_trtri_blocked(A, mp, Dinv, W, T, st, nb, true));
     hipLaunchKernelGGL(cv_u_kernel, dim3((unsigned)(mp / 4), (unsigned)nb), dim3(256), 0, st, c);
     GP_HIP(hipGetLastError());
     hipLaunchKernelGGL(cv_out_kernel, dim3((unsigned)((mp + 255) / 256), (unsigned)nb), dim3(256), 0, st, c);
     GP_HIP(hipGetLastError());
   }
   std::vector<int> info((size_t)nprob);
-  GP_HIP(hipMemcpyAsync(info.data(), dinfo, sizeof(int) * (size_t)nprob, hipMemcpyDeviceToHost, st));
+  GP_TRY(sc.download(info.data(), dinfo, nprob));
   GP_HIP(hipStreamSynchronize(st));
   for (int64_t q = 0; q < nprob; ++q)
     if (info[q] != 0) {

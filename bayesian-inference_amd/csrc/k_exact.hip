@@ -582,13 +582,7 @@ int launch_loglik_exact(gpemu_model *m, int64_t B, const double *dXq, double *do
   const int F = (int)m->F;
   const int64_t per = (int64_t)F * F + chol_scratch_size(F) + F;
   int nwg = (int)(B < 256 ? B : 256);
-  if (m->exact_scratch_size < per * nwg) {
-    GP_HIP(hipStreamSynchronize(st));
-    hipFree(m->exact_scratch);
-    m->exact_scratch = nullptr; m->exact_scratch_size = 0;
-    GP_HIP(hipMalloc((void **)&m->exact_scratch, sizeof(double) * (size_t)(per * nwg)));
-    m->exact_scratch_size = per * nwg;
-  }
+  GP_TRY(dev_reserve(&m->exact_scratch_size, per * nwg, {st}, {dev_field(&m->exact_scratch, per * nwg)}));
   const Workspace &w = m->ws;
   hipLaunchKernelGGL(loglik_exact_kernel, dim3((unsigned)nwg), dim3(CHOL_THREADS), 0, st, dXq, m->lo,
                      m->hi, w.mean_part, w.vsq_part, m->kdiag, m->comp, m->smean, m->sscale,

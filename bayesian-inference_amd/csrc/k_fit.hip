@@ -1270,21 +1270,14 @@ static void fit_buffers(gpemu_fit *f, Fn fn) {
 // workspace for `nb` problems evaluated together (one set of matrices each)
 static int fit_reserve(gpemu_fit *f, int nb) {
   if (nb <= f->cap) return GPEMU_OK;
-  GP_HIP(hipStreamSynchronize(f->stream));
-  fit_buffers(f, [](double **p, int64_t) { (void)hipFree(*p); *p = nullptr; });
-  (void)hipFree(f->info);
-  f->info = nullptr;
-  f->cap = 0;
   f->last_nb = 0;
-  hipError_t e = hipSuccess;
-  fit_buffers(f, [&](double **p, int64_t n) {
-    if (e == hipSuccess) e = hipMalloc((void **)p, sizeof(double) * (size_t)(n > 0 ? n : 1) * nb);
-  });
-  if (e == hipSuccess) e = hipMalloc((void **)&f->info, sizeof(int) * nb);
-  (void)hipFree(f->overlap.flags);
-  f->overlap.flags = nullptr;
-  if (e == hipSuccess) e = hipMalloc((void **)&f->overlap.flags, sizeof(int) * (size_t)CHOL_FLAGS * nb);
-  if (e != hipSuccess) { set_error("fit workspace for %d problems: %s", nb, hipGetErrorString(e)); return GPEMU_ERR_HIP; }
+  std::vector<DevField> fields;
+  fit_buffers(f, [&](double **p, int64_t n) { fields.push_back(dev_field(p, (n > 0 ? n : 1) * nb)); });
+  fields.push_back(dev_field(&f->info, nb));
+  GP_TRY(dev_reserve(&f->cap, nb, {f->stream}, fields.data(), fields.size()));
+  f->cap = 0;   // ... and the look-ahead's flags, which go with the same capacity
+  dev_free(f->overlap.flags);
+  GP_TRY(dev_alloc(&f->overlap.flags, (int64_t)CHOL_FLAGS * nb));
   f->cap = nb;
   return GPEMU_OK;
 }
@@ -1404,6 +1397,42 @@ static int fit_eval(gpemu_fit *f, const double *y, const double *theta, int64_t 
 
 extern "C" {
 
+// the streams, events and device buffers of a new fit handle, whose sizes are set: gpemu_fit_create destroys `f` if
+// this fails
+static int fit_fill(gpemu_fit *f, const double *X) {
+  const int64_t N = f->N, d = f->d, Np = f->Np;
+  // the serial chain of the factorisation runs on `stream`; the look-ahead updates fill the rest of the chip from a
+  // stream of lower priority, so that a waiting step of the chain is dispatched first
+  int prio_least = 0, prio_greatest = 0;
+  (void)hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest);
+  GP_HIP(hipStreamCreateWithPriority(&f->stream, hipStreamNonBlocking, prio_greatest));
+  // The side stream may not use the first GPEMU_CHOL_RESERVE (default 4) CUs of every XCD: its GEMM workgroups take a
+  // quarter of a CU's LDS each and are replaced one by one as they finish, so without a reserve the 75 KiB diagonal-block
+  // kernel of the serial chain finds no CU with room until the whole side grid has drained (measured: 18 -> 100 us).
+  // hipExtStreamCreateWithCUMask: bit i = CU i / 8 of XCD i % 8 (profiles/r03_cu_mask_probe.txt).
+  hipDeviceProp_t prop;
+  GP_HIP(hipGetDeviceProperties(&prop, f->device));
+  const int ncu = prop.multiProcessorCount;
+  constexpr int reserve = 4;
+  if (reserve > 0 && ncu % 8 == 0 && 8 * reserve < ncu) {
+    std::vector<uint32_t> mask((size_t)(ncu + 31) / 32, 0u);
+    for (int i = 8 * reserve; i < ncu; ++i) mask[i / 32] |= 1u << (i % 32);
+    GP_HIP(hipExtStreamCreateWithCUMask(&f->overlap.side, (uint32_t)mask.size(), mask.data()));
+  } else {
+    GP_HIP(hipStreamCreateWithPriority(&f->overlap.side, hipStreamNonBlocking, prio_least));
+  }
+  GP_HIP(hipEventCreateWithFlags(&f->overlap.panel_done, hipEventDisableTiming));
+  GP_HIP(hipEventCreateWithFlags(&f->overlap.rest_done, hipEventDisableTiming));
+  const int dp = f->dp;
+  GP_TRY(dev_alloc(&f->X, Np * dp));
+  GP_TRY(fit_reserve(f, 1));
+  std::vector<double> hX((size_t)(Np * dp), 0.0);
+  for (int64_t i = 0; i < N; ++i)
+    for (int64_t dd = 0; dd < d; ++dd) hX[i * dp + dd] = X[i * d + dd];
+  GP_HIP(hipMemcpy(f->X, hX.data(), sizeof(double) * hX.size(), hipMemcpyHostToDevice));
+  return GPEMU_OK;
+}
+
 int gpemu_fit_create(gpemu_fit **out, int device, int64_t N, int64_t d, const double *X, int kernel_kind,
                      double nu, int has_const, int has_noise, double jitter) {
   GP_ARG(out && X, "null pointer");
@@ -1425,43 +1454,11 @@ int gpemu_fit_create(gpemu_fit **out, int device, int64_t N, int64_t d, const do
   if (f->kind == 4) f->mnu = matern_nu_constants(nu);
   f->has_const = has_const ? 1 : 0; f->has_noise = has_noise ? 1 : 0;
   f->jitter = jitter;
-  const int64_t Np = f->Np;
   f->n_gparts = (int)(((N + 255) / 256) * N);
-  // the serial chain of the factorisation runs on `stream`; the look-ahead updates fill the rest of the chip from a
-  // stream of lower priority, so that a waiting step of the chain is dispatched first
-  int prio_least = 0, prio_greatest = 0;
-  (void)hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest);
-  hipError_t e = hipStreamCreateWithPriority(&f->stream, hipStreamNonBlocking, prio_greatest);
-  if (e == hipSuccess) {
-    // The side stream may not use the first GPEMU_CHOL_RESERVE (default 4) CUs of every XCD: its GEMM workgroups take a
-    // quarter of a CU's LDS each and are replaced one by one as they finish, so without a reserve the 75 KiB diagonal-block
-    // kernel of the serial chain finds no CU with room until the whole side grid has drained (measured: 18 -> 100 us).
-    // hipExtStreamCreateWithCUMask: bit i = CU i / 8 of XCD i % 8 (profiles/r03_cu_mask_probe.txt).
-    hipDeviceProp_t prop;
-    e = hipGetDeviceProperties(&prop, device);
-    const int ncu = prop.multiProcessorCount;
-    constexpr int reserve = 4;
-    if (e == hipSuccess && reserve > 0 && ncu % 8 == 0 && 8 * reserve < ncu) {
-      std::vector<uint32_t> mask((size_t)(ncu + 31) / 32, 0u);
-      for (int i = 8 * reserve; i < ncu; ++i) mask[i / 32] |= 1u << (i % 32);
-      e = hipExtStreamCreateWithCUMask(&f->overlap.side, (uint32_t)mask.size(), mask.data());
-    } else if (e == hipSuccess) {
-      e = hipStreamCreateWithPriority(&f->overlap.side, hipStreamNonBlocking, prio_least);
-    }
-  }
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&f->overlap.panel_done, hipEventDisableTiming);
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&f->overlap.rest_done, hipEventDisableTiming);
-  const int dp = f->dp;
-  if (e == hipSuccess) e = hipMalloc((void **)&f->X, sizeof(double) * (size_t)(Np * dp));
-  if (e == hipSuccess && fit_reserve(f, 1) != GPEMU_OK) e = hipErrorOutOfMemory;
-  std::vector<double> hX((size_t)(Np * dp), 0.0);
-  for (int64_t i = 0; i < N; ++i)
-    for (int64_t dd = 0; dd < d; ++dd) hX[i * dp + dd] = X[i * d + dd];
-  if (e == hipSuccess) e = hipMemcpy(f->X, hX.data(), sizeof(double) * hX.size(), hipMemcpyHostToDevice);
-  if (e != hipSuccess) {
-    set_error("fit_create: %s", hipGetErrorString(e));
+  const int rc = fit_fill(f, X);
+  if (rc != GPEMU_OK) {
     gpemu_fit_destroy(f);
-    return GPEMU_ERR_HIP;
+    return rc;
   }
   f->counted = true;
   g_live_fit_handles.fetch_add(1);
@@ -1477,11 +1474,10 @@ int gpemu_fit_destroy(gpemu_fit *f) {
   if (f->overlap.side) { (void)hipStreamSynchronize(f->overlap.side); (void)hipStreamDestroy(f->overlap.side); }
   if (f->overlap.panel_done) (void)hipEventDestroy(f->overlap.panel_done);
   if (f->overlap.rest_done) (void)hipEventDestroy(f->overlap.rest_done);
-  double *ptrs[] = {f->X, f->hp, f->K, f->Dinv, f->W, f->T, f->Kinv, f->y, f->v, f->alpha, f->gpart, f->scal, f->grad,
-                    f->gstage};
-  for (double *p : ptrs) (void)hipFree(p);
-  (void)hipFree(f->info);
-  (void)hipFree(f->overlap.flags);
+  dev_free(f->X);
+  fit_buffers(f, [](double **p, int64_t) { dev_free(*p); });
+  dev_free(f->info);
+  dev_free(f->overlap.flags);
   if (f->stream) (void)hipStreamDestroy(f->stream);
   delete f;
   return GPEMU_OK;
@@ -1584,24 +1580,24 @@ int gpemu_cholesky(int device, int64_t N, double *A_inout) {
   GP_ARG(device >= 0 && device < ndev, "device");
   GP_HIP(hipSetDevice(device));
   const int64_t Np = round_up(N, NB);
-  double *A = nullptr, *Dinv = nullptr;
-  int *dinfo = nullptr;
-  hipError_t e = hipMalloc((void **)&A, sizeof(double) * Np * Np);
-  if (e == hipSuccess) e = hipMalloc((void **)&Dinv, sizeof(double) * Np * NB);
-  if (e == hipSuccess) e = hipMalloc((void **)&dinfo, sizeof(int));
   std::vector<double> h((size_t)(Np * Np), 0.0);
   for (int64_t i = 0; i < Np; ++i)
     for (int64_t j = 0; j <= i; ++j) h[i * Np + j] = (i < N && j < N) ? A_inout[i * N + j] : (i == j ? 1.0 : 0.0);
-  int rc = GPEMU_OK, info = 0;
-  if (e == hipSuccess) e = hipMemcpy(A, h.data(), sizeof(double) * h.size(), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemset(dinfo, 0, sizeof(int));
-  if (e == hipSuccess) rc = device_cholesky_blocked(A, Np, Dinv, dinfo, nullptr);
-  if (e == hipSuccess && rc == GPEMU_OK) e = hipDeviceSynchronize();
-  if (e == hipSuccess && rc == GPEMU_OK) e = hipMemcpy(&info, dinfo, sizeof(int), hipMemcpyDeviceToHost);
-  if (e == hipSuccess && rc == GPEMU_OK) e = hipMemcpy(h.data(), A, sizeof(double) * h.size(), hipMemcpyDeviceToHost);
-  (void)hipFree(A); (void)hipFree(Dinv); (void)hipFree(dinfo);
-  if (e != hipSuccess) { set_error("cholesky: %s", hipGetErrorString(e)); return GPEMU_ERR_HIP; }
-  if (rc != GPEMU_OK) return rc;
+  int info = 0;
+  {
+    DevScope sc(nullptr);   // a one-off factorisation: the null stream
+    double *A = nullptr, *Dinv = nullptr;
+    int *dinfo = nullptr;
+    GP_TRY(sc.alloc(&A, Np * Np));
+    GP_TRY(sc.alloc(&Dinv, Np * NB));
+    GP_TRY(sc.alloc(&dinfo, 1));
+    GP_HIP(hipMemcpy(A, h.data(), sizeof(double) * h.size(), hipMemcpyHostToDevice));
+    GP_HIP(hipMemset(dinfo, 0, sizeof(int)));
+    GP_TRY(device_cholesky_blocked(A, Np, Dinv, dinfo, nullptr));
+    GP_HIP(hipDeviceSynchronize());
+    GP_HIP(hipMemcpy(&info, dinfo, sizeof(int), hipMemcpyDeviceToHost));
+    GP_HIP(hipMemcpy(h.data(), A, sizeof(double) * h.size(), hipMemcpyDeviceToHost));
+  }
   if (info < 0) { set_error("cholesky: a wait inside the factorisation kernels expired"); return GPEMU_ERR_STATE; }
   if (info != 0) { set_error("matrix is not positive definite (pivot %d)", info); return info; }
   for (int64_t i = 0; i < N; ++i)

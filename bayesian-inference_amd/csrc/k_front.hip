@@ -385,15 +385,9 @@ __global__ void gather_fill_kernel(double *p, int64_t n, unsigned long long bits
 // ---- host side --------------------------------------------------------------------------------------------
 static int ensure_gather(gpemu_sampler *s) {
   if (s->gather) return GPEMU_OK;
-  const size_t bytes = sizeof(double) * GATHER_SLOTS * (size_t)s->ns[0];
-  // uncached device memory: the values are written by other workgroups / other GPUs and polled here
-  hipError_t e = hipExtMallocWithFlags((void **)&s->gather, bytes, hipDeviceMallocUncached);
-  s->gather_uncached = (e == hipSuccess);
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
-    GP_HIP(hipMalloc((void **)&s->gather, bytes));
-  }
   const int64_t n = GATHER_SLOTS * s->ns[0];
+  // uncached device memory: the values are written by other workgroups / other GPUs and polled here
+  GP_TRY(dev_alloc_uncached(&s->gather, n, &s->gather_uncached));
   hipLaunchKernelGGL(gather_fill_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s->stream, s->gather, n,
                      GATHER_EMPTY);
   GP_HIP(hipStreamSynchronize(s->stream));
@@ -405,9 +399,8 @@ static int set_local_peer(gpemu_sampler *s) {
   GP_HIP(hipStreamSynchronize(s->stream));
   for (void *q : s->peer_opened) (void)hipIpcCloseMemHandle(q);
   s->peer_opened.clear();
-  (void)hipFree(s->peers);
-  s->peers = nullptr;
-  GP_HIP(hipMalloc((void **)&s->peers, sizeof(double *)));
+  dev_free(s->peers);
+  GP_TRY(dev_alloc(&s->peers, 1));
   GP_HIP(hipMemcpy(s->peers, &s->gather, sizeof(double *), hipMemcpyHostToDevice));
   s->peer_world = 1;
   s->peer_rank = 0;
@@ -415,14 +408,12 @@ static int set_local_peer(gpemu_sampler *s) {
 }
 
 void front_release(gpemu_sampler *s) {
-  for (const gpemu_sampler::FrontPerm &e : s->front_perms) (void)hipFree(e.dperm);
+  for (gpemu_sampler::FrontPerm &e : s->front_perms) dev_free(e.dperm);
   s->front_perms.clear();
   for (void *q : s->peer_opened) (void)hipIpcCloseMemHandle(q);
   s->peer_opened.clear();
-  (void)hipFree(s->peers);
-  (void)hipFree(s->gather);
-  s->peers = nullptr;
-  s->gather = nullptr;
+  dev_free(s->peers);
+  dev_free(s->gather);
   s->peer_world = 0;
 }
 
@@ -533,10 +524,12 @@ static const int *front_perm_for(gpemu_sampler *s, int g, int64_t cnt, int wg0, 
   }
   int *d = nullptr;
   if (any_pref) {
-    if (hipMalloc((void **)&d, sizeof(int) * perm.size()) != hipSuccess ||
-        hipMemcpy(d, perm.data(), sizeof(int) * perm.size(), hipMemcpyHostToDevice) != hipSuccess) {
+    DevScope sc(s->stream);
+    if (sc.alloc(&d, (int64_t)perm.size()) == GPEMU_OK &&
+        hipMemcpy(d, perm.data(), sizeof(int) * perm.size(), hipMemcpyHostToDevice) == hipSuccess) {
+      sc.release(d);                                        // kept in front_perms
+    } else {
       (void)hipGetLastError();
-      (void)hipFree(d);
       d = nullptr;                                          // no table: index order (correct, only slower)
     }
   }
@@ -861,8 +854,7 @@ int gpemu_sampler_peer_import(gpemu_sampler *s, int world, int rank, const char 
   GP_HIP(hipStreamSynchronize(s->stream));
   for (void *q : s->peer_opened) (void)hipIpcCloseMemHandle(q);
   s->peer_opened.clear();
-  (void)hipFree(s->peers);
-  s->peers = nullptr;
+  dev_free(s->peers);
   s->peer_world = 0;
   std::vector<double *> ptrs((size_t)world, nullptr);
   for (int r = 0; r < world; ++r) {
@@ -880,7 +872,7 @@ int gpemu_sampler_peer_import(gpemu_sampler *s, int world, int rank, const char 
     s->peer_opened.push_back(q);
     ptrs[r] = (double *)q;
   }
-  GP_HIP(hipMalloc((void **)&s->peers, sizeof(double *) * world));
+  GP_TRY(dev_alloc(&s->peers, world));
   GP_HIP(hipMemcpy(s->peers, ptrs.data(), sizeof(double *) * world, hipMemcpyHostToDevice));
   s->peer_world = world;
   s->peer_rank = rank;
@@ -898,15 +890,16 @@ int gpemu_sampler_peer_selftest(gpemu_sampler *s) {
   GP_HIP(hipSetDevice(s->device));
   if (s->peer_world < 1 || !s->peers) { set_error("gpemu_sampler_peer_import has not been called"); return GPEMU_ERR_STATE; }
   if ((int64_t)s->peer_world > GATHER_SLOTS * s->ns[0]) { set_error("peer self-test: more ranks than buffer entries"); return GPEMU_ERR_ARG; }
-  int *dres = nullptr;
-  GP_HIP(hipMalloc((void **)&dres, sizeof(int)));
-  GP_HIP(hipMemsetAsync(dres, 0, sizeof(int), s->stream));
-  hipLaunchKernelGGL(peer_selftest_kernel, dim3(1), dim3(64), 0, s->stream, s->peers, s->gather, s->peer_world, s->peer_rank, dres);
   int res = -1;
-  hipError_t e = hipMemcpyAsync(&res, dres, sizeof(int), hipMemcpyDeviceToHost, s->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
-  (void)hipFree(dres);
-  if (e != hipSuccess) { set_error("peer self-test: %s", hipGetErrorString(e)); return GPEMU_ERR_HIP; }
+  {
+    DevScope sc(s->stream);
+    int *dres = nullptr;
+    GP_TRY(sc.alloc(&dres, 1));
+    GP_HIP(hipMemsetAsync(dres, 0, sizeof(int), s->stream));
+    hipLaunchKernelGGL(peer_selftest_kernel, dim3(1), dim3(64), 0, s->stream, s->peers, s->gather, s->peer_world, s->peer_rank, dres);
+    GP_TRY(sc.download(&res, dres, 1));
+    GP_HIP(hipStreamSynchronize(s->stream));
+  }
   if (res != 0) {
     set_error("peer self-test: the tokens of %d rank(s) did not arrive through the mapped buffers", res);
     return GPEMU_ERR_STATE;

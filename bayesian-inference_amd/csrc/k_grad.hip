@@ -32,8 +32,6 @@ namespace gpemu {
 constexpr int GRAD_CHUNK = 1024;  // rows per pass (bounds the three [k][Npad][chunk] operands: together 3072 / Npad of Wt's size)
 constexpr int GRAD_RB = 256;      // training rows per partial sum of the contraction
 
-static std::atomic<int64_t> g_grad_counts[GPEMU_GRAD_PATH_COUNT];
-static void grad_path_count(int path) { g_grad_counts[path].fetch_add(1, std::memory_order_relaxed); }
 
 // ---- K_*^T from the raw coordinates ---------------------------------------------------------------------------------
 struct GradKmatArgs {
@@ -151,96 +149,92 @@ __global__ __launch_bounds__(64) void grad_loglik_kernel(GradLikArgs g) {
     sd = sqrt(g.var[c * k + lane]);
   }
   double total = 0.0, av = 0.0, bv = 0.0;
-  {
-    {
-      const double *Go = g.G + (int64_t)o * k * k;
-      double h = 0.0;
-      const double gl = (lane < k) ? g.g0[(int64_t)o * k + lane] : 0.0;
-      for (int q = 0; q < k; ++q) {
-        const double gq = (lane < k) ? Go[q * k + lane] : 0.0;       // G symmetric: column-wise, coalesced
-        h = fma(gq, __shfl(mu, q), h);
-        const double sq = __shfl(sd, q);
-        if (lane < k) {
-          M[lane * ldm + q] = ((lane == q) ? 1.0 : 0.0) + sd * gq * sq;
-          Y[q * k + lane] = sq * gq;                                  // (S G)[q][lane]
-        }
-      }
-      h += gl;
-      double t = (lane < k) ? mu * (h + gl) : 0.0;
-      for (int off = 32; off > 0; off >>= 1) t += __shfl_xor(t, off);
-      const double quadA = t + g.scal[2 * o];
-      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      double logdiag = 0.0;
-      for (int j = 0; j < k; ++j) {
-        const double piv = sqrt(M[j * ldm + j]);
-        __builtin_amdgcn_wave_barrier();
-        if (lane == j) {
-          M[j * ldm + j] = piv;
-          logdiag = log(piv);
-        }
-        if (lane > j && lane < k) M[lane * ldm + j] = M[lane * ldm + j] / piv;
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        if (lane > j && lane < k) {
-          const double lij = M[lane * ldm + j];
-          for (int cc = j + 1; cc <= lane; ++cc) M[lane * ldm + cc] -= lij * M[cc * ldm + j];
-        }
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-      }
-      // y = L^-1 (S h)
-      double y = (lane < k) ? sd * h : 0.0;
-      for (int j = 0; j < k; ++j) {
-        const double zj = __shfl(y, j) / M[j * ldm + j];
-        if (lane == j) y = zj;
-        if (lane > j && lane < k) y = fma(-M[lane * ldm + j], zj, y);
-      }
-      double ww = (lane < k) ? y * y : 0.0;
-      double ldsum = logdiag;
-      for (int off = 32; off > 0; off >>= 1) {
-        ww += __shfl_xor(ww, off);
-        ldsum += __shfl_xor(ldsum, off);
-      }
-      total += -0.5 * (quadA - ww) - 0.5 * (g.scal[2 * o + 1] + 2.0 * ldsum);
-      // Y_:lane = L^-1 (S G)_:lane, lane = right-hand side: L's entries are broadcast reads, Y's are conflict free
-      double ynorm = 0.0;
-      if (lane < k) {
-        for (int i = 0; i < k; ++i) {
-          double s = Y[i * k + lane];
-          for (int j = 0; j < i; ++j) s = fma(-M[i * ldm + j], Y[j * k + lane], s);
-          s /= M[i * ldm + i];
-          Y[i * k + lane] = s;
-          ynorm = fma(s, s, ynorm);
-        }
-      }
-      // t = L^-T y, rows from the last up: row j of L is read along the lanes
-      double tt = y;
-      for (int j = k - 1; j >= 0; --j) {
-        const double tj = __shfl(tt, j) / M[j * ldm + j];
-        if (lane == j) tt = tj;
-        if (lane < j) tt = fma(-M[j * ldm + lane], tj, tt);
-      }
-      // z = h - G S t
-      const double st = sd * tt;
-      double z = h;
-      for (int q = 0; q < k; ++q) {
-        const double gq = (lane < k) ? Go[q * k + lane] : 0.0;
-        z = fma(-gq, __shfl(st, q), z);
-      }
-      if (lane < k) {
-        const double pdiag = Go[lane * k + lane] - ynorm;
-        av -= z;
-        bv += 0.5 * (z * z - pdiag);
-      }
+  const double *Go = g.G + (int64_t)o * k * k;
+  double h = 0.0;
+  const double gl = (lane < k) ? g.g0[(int64_t)o * k + lane] : 0.0;
+  for (int q = 0; q < k; ++q) {
+    const double gq = (lane < k) ? Go[q * k + lane] : 0.0;       // G symmetric: column-wise, coalesced
+    h = fma(gq, __shfl(mu, q), h);
+    const double sq = __shfl(sd, q);
+    if (lane < k) {
+      M[lane * ldm + q] = ((lane == q) ? 1.0 : 0.0) + sd * gq * sq;
+      Y[q * k + lane] = sq * gq;                                  // (S G)[q][lane]
     }
   }
-  const int64_t t = c * g.nblk + o;
-  if (lane < k) {
-    g.ta[t * k + lane] = av;
-    g.tb[t * k + lane] = bv;
+  h += gl;
+  double t = (lane < k) ? mu * (h + gl) : 0.0;
+  for (int off = 32; off > 0; off >>= 1) t += __shfl_xor(t, off);
+  const double quadA = t + g.scal[2 * o];
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  double logdiag = 0.0;
+  for (int j = 0; j < k; ++j) {
+    const double piv = sqrt(M[j * ldm + j]);
+    __builtin_amdgcn_wave_barrier();
+    if (lane == j) {
+      M[j * ldm + j] = piv;
+      logdiag = log(piv);
+    }
+    if (lane > j && lane < k) M[lane * ldm + j] = M[lane * ldm + j] / piv;
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    if (lane > j && lane < k) {
+      const double lij = M[lane * ldm + j];
+      for (int cc = j + 1; cc <= lane; ++cc) M[lane * ldm + cc] -= lij * M[cc * ldm + j];
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
   }
-  if (lane == 0) g.tlp[t] = total;
+  // y = L^-1 (S h)
+  double y = (lane < k) ? sd * h : 0.0;
+  for (int j = 0; j < k; ++j) {
+    const double zj = __shfl(y, j) / M[j * ldm + j];
+    if (lane == j) y = zj;
+    if (lane > j && lane < k) y = fma(-M[lane * ldm + j], zj, y);
+  }
+  double ww = (lane < k) ? y * y : 0.0;
+  double ldsum = logdiag;
+  for (int off = 32; off > 0; off >>= 1) {
+    ww += __shfl_xor(ww, off);
+    ldsum += __shfl_xor(ldsum, off);
+  }
+  total += -0.5 * (quadA - ww) - 0.5 * (g.scal[2 * o + 1] + 2.0 * ldsum);
+  // Y_:lane = L^-1 (S G)_:lane, lane = right-hand side: L's entries are broadcast reads, Y's are conflict free
+  double ynorm = 0.0;
+  if (lane < k) {
+    for (int i = 0; i < k; ++i) {
+      double s = Y[i * k + lane];
+      for (int j = 0; j < i; ++j) s = fma(-M[i * ldm + j], Y[j * k + lane], s);
+      s /= M[i * ldm + i];
+      Y[i * k + lane] = s;
+      ynorm = fma(s, s, ynorm);
+    }
+  }
+  // t = L^-T y, rows from the last up: row j of L is read along the lanes
+  double tt = y;
+  for (int j = k - 1; j >= 0; --j) {
+    const double tj = __shfl(tt, j) / M[j * ldm + j];
+    if (lane == j) tt = tj;
+    if (lane < j) tt = fma(-M[j * ldm + lane], tj, tt);
+  }
+  // z = h - G S t
+  const double st = sd * tt;
+  double z = h;
+  for (int q = 0; q < k; ++q) {
+    const double gq = (lane < k) ? Go[q * k + lane] : 0.0;
+    z = fma(-gq, __shfl(st, q), z);
+  }
+  if (lane < k) {
+    const double pdiag = Go[lane * k + lane] - ynorm;
+    av -= z;
+    bv += 0.5 * (z * z - pdiag);
+  }
+  const int64_t term = c * g.nblk + o;
+  if (lane < k) {
+    g.ta[term * k + lane] = av;
+    g.tb[term * k + lane] = bv;
+  }
+  if (lane == 0) g.tlp[term] = total;
 }
 
 // the blocks' terms added in block order, per (row, PC): a_p, b_p (0 where the variance was clipped), and the row's lp
@@ -424,7 +418,7 @@ static int64_t grad_ws_doubles(const gpemu_model *m) {
 
 // the workspace of the gradient calls, allocated by the first of them (a model that never asks allocates nothing)
 static int grad_workspace(gpemu_model *m, GradWs &w) {
-  if (!m->grad_ws) GP_HIP(hipMalloc((void **)&m->grad_ws, sizeof(double) * (size_t)grad_ws_doubles(m)));
+  if (!m->grad_ws) GP_TRY(dev_alloc(&m->grad_ws, grad_ws_doubles(m)));
   const int64_t big = m->k * m->Npad * GRAD_CHUNK, sm = GRAD_CHUNK * m->k;
   w.nrb = (int)((m->N + GRAD_RB - 1) / GRAD_RB);
   double *q = m->grad_ws;
@@ -445,13 +439,7 @@ static int grad_workspace(gpemu_model *m, GradWs &w) {
 // may change
 static int grad_lik_workspace(gpemu_model *m, GradWs &w, hipStream_t st) {
   const int64_t need = (int64_t)GRAD_CHUNK * m->nblk * (2 * m->k + 1);
-  if (m->grad_lik_cap < need) {
-    GP_HIP(hipStreamSynchronize(st));
-    (void)hipFree(m->grad_lik_ws);
-    m->grad_lik_ws = nullptr; m->grad_lik_cap = 0;
-    GP_HIP(hipMalloc((void **)&m->grad_lik_ws, sizeof(double) * (size_t)need));
-    m->grad_lik_cap = need;
-  }
+  GP_TRY(dev_reserve(&m->grad_lik_cap, need, {st}, {dev_field(&m->grad_lik_ws, need)}));
   w.tlp = m->grad_lik_ws;
   w.ta = w.tlp + (int64_t)GRAD_CHUNK * m->nblk;
   w.tb = w.ta + (int64_t)GRAD_CHUNK * m->nblk * m->k;
@@ -576,28 +564,11 @@ static int logpost_grad_eval(gpemu_model *const *ms, int ng, int64_t B, const do
   return GPEMU_OK;
 }
 
-struct GradDevFree {
-  std::vector<void *> p;
-  ~GradDevFree() { for (void *q : p) (void)hipFree(q); }
-  int alloc(double **q, int64_t n) {
-    *q = nullptr;
-    GP_HIP(hipMalloc((void **)q, sizeof(double) * (size_t)(n < 1 ? 1 : n)));
-    p.push_back(*q);
-    return GPEMU_OK;
-  }
-};
-
 }  // namespace gpemu
 
 using namespace gpemu;
 
 extern "C" {
-
-int gpemu_grad_path_counts(int64_t *out, int64_t n) {
-  GP_ARG(out && n >= 0, "out");
-  for (int64_t i = 0; i < n && i < GPEMU_GRAD_PATH_COUNT; ++i) out[i] = g_grad_counts[i].load(std::memory_order_relaxed);
-  return GPEMU_GRAD_PATH_COUNT;
-}
 
 int gpemu_gp_predict_grad_dev(gpemu_model *m, int64_t B, const double *dX, double *dmean, double *dvar, double *ddmean,
                               double *ddvar, void *stream) {
@@ -632,23 +603,21 @@ int gpemu_gp_predict_grad(gpemu_model *m, int64_t B, const double *X, double *me
   GP_HIP(hipSetDevice(m->device));
   hipStream_t st = m->stream;
   const int64_t d = m->d, k = m->k;
-  GradDevFree fr;
+  DevScope sc(st);
   double *dX, *dm, *dv, *ddm, *ddv;
-  GP_TRY(fr.alloc(&dX, B * d));
-  GP_TRY(fr.alloc(&dm, B * k));
-  GP_TRY(fr.alloc(&dv, B * k));
-  GP_TRY(fr.alloc(&ddm, B * k * d));
-  GP_TRY(fr.alloc(&ddv, B * k * d));
-  GP_HIP(hipMemcpyAsync(dX, X, sizeof(double) * (size_t)(B * d), hipMemcpyHostToDevice, st));
-  int rc = gpemu_gp_predict_grad_dev(m, B, dX, dm, dv, ddm, ddv, st);
-  if (rc == GPEMU_OK) {
-    GP_HIP(hipMemcpyAsync(mean, dm, sizeof(double) * (size_t)(B * k), hipMemcpyDeviceToHost, st));
-    GP_HIP(hipMemcpyAsync(var, dv, sizeof(double) * (size_t)(B * k), hipMemcpyDeviceToHost, st));
-    GP_HIP(hipMemcpyAsync(dmean_dx, ddm, sizeof(double) * (size_t)(B * k * d), hipMemcpyDeviceToHost, st));
-    GP_HIP(hipMemcpyAsync(dvar_dx, ddv, sizeof(double) * (size_t)(B * k * d), hipMemcpyDeviceToHost, st));
-  }
+  GP_TRY(sc.alloc(&dX, B * d));
+  GP_TRY(sc.alloc(&dm, B * k));
+  GP_TRY(sc.alloc(&dv, B * k));
+  GP_TRY(sc.alloc(&ddm, B * k * d));
+  GP_TRY(sc.alloc(&ddv, B * k * d));
+  GP_TRY(upload(dX, X, B * d, st));
+  GP_TRY(gpemu_gp_predict_grad_dev(m, B, dX, dm, dv, ddm, ddv, st));
+  GP_TRY(sc.download(mean, dm, B * k));
+  GP_TRY(sc.download(var, dv, B * k));
+  GP_TRY(sc.download(dmean_dx, ddm, B * k * d));
+  GP_TRY(sc.download(dvar_dx, ddv, B * k * d));
   GP_HIP(hipStreamSynchronize(st));
-  return rc;
+  return GPEMU_OK;
 }
 
 int gpemu_logpost_grad_dev(gpemu_model *m, int64_t B, const double *dX, double *dlp, double *dgrad, int mode, void *stream) {
@@ -690,19 +659,17 @@ int gpemu_logpost_groups_grad(gpemu_model *const *models, int n_groups, int64_t 
   const int64_t d = m0->d;
   // the other groups' streams may still hold work on their models (a likelihood setup): the evaluation runs on the first's
   for (int g = 1; g < n_groups; ++g) GP_HIP(hipStreamSynchronize(models[g]->stream));
-  GradDevFree fr;
+  DevScope sc(st);
   double *dX, *dlp, *dgrad;
-  GP_TRY(fr.alloc(&dX, B * d));
-  GP_TRY(fr.alloc(&dlp, B));
-  GP_TRY(fr.alloc(&dgrad, B * d));
-  GP_HIP(hipMemcpyAsync(dX, X, sizeof(double) * (size_t)(B * d), hipMemcpyHostToDevice, st));
-  int rc = logpost_grad_eval(models, n_groups, B, dX, dlp, dgrad, st);
-  if (rc == GPEMU_OK) {
-    GP_HIP(hipMemcpyAsync(lp, dlp, sizeof(double) * (size_t)B, hipMemcpyDeviceToHost, st));
-    GP_HIP(hipMemcpyAsync(grad, dgrad, sizeof(double) * (size_t)(B * d), hipMemcpyDeviceToHost, st));
-  }
+  GP_TRY(sc.alloc(&dX, B * d));
+  GP_TRY(sc.alloc(&dlp, B));
+  GP_TRY(sc.alloc(&dgrad, B * d));
+  GP_TRY(upload(dX, X, B * d, st));
+  GP_TRY(logpost_grad_eval(models, n_groups, B, dX, dlp, dgrad, st));
+  GP_TRY(sc.download(lp, dlp, B));
+  GP_TRY(sc.download(grad, dgrad, B * d));
   GP_HIP(hipStreamSynchronize(st));
-  return rc;
+  return GPEMU_OK;
 }
 
 int gpemu_logpost_grad(gpemu_model *m, int64_t B, const double *X, double *lp, double *grad, int mode) {

@@ -174,31 +174,28 @@ int launch_lik_setup(gpemu_model *m, const std::vector<int> &hstart, double *dA,
     if (nf > LIK_BLOCKED_MIN) maxnp = std::max<int64_t>(maxnp, round_up(nf, 64));
   }
   if (maxnp == 0) return GPEMU_OK;
+  DevScope sc(st);
   double *Ab = nullptr, *Dinv = nullptr, *W = nullptr, *T = nullptr;
-  hipError_t e = hipMalloc((void **)&Ab, sizeof(double) * maxnp * maxnp);
-  if (e == hipSuccess) e = hipMalloc((void **)&Dinv, sizeof(double) * maxnp * 64);
-  if (e == hipSuccess) e = hipMalloc((void **)&W, sizeof(double) * maxnp * maxnp);
-  if (e == hipSuccess) e = hipMalloc((void **)&T, sizeof(double) * maxnp * maxnp);
-  int rc = GPEMU_OK;
-  if (e != hipSuccess) { set_error("likelihood_setup: %s", hipGetErrorString(e)); rc = GPEMU_ERR_HIP; }
-  for (size_t o = 0; o + 1 < hstart.size() && rc == GPEMU_OK; ++o) {
+  GP_TRY(sc.alloc(&Ab, maxnp * maxnp));
+  GP_TRY(sc.alloc(&Dinv, maxnp * 64));
+  GP_TRY(sc.alloc(&W, maxnp * maxnp));
+  GP_TRY(sc.alloc(&T, maxnp * maxnp));
+  for (size_t o = 0; o + 1 < hstart.size(); ++o) {
     const int f0 = hstart[o], nf = hstart[o + 1] - f0;
     if (nf <= LIK_BLOCKED_MIN) continue;
     const int Np = (int)round_up(nf, 64);
     hipLaunchKernelGGL(lik_pad_block_kernel, dim3((unsigned)((Np + 255) / 256), (unsigned)Np), dim3(256), 0, st,
                        dA + (int64_t)f0 * F + f0, F, nf, Ab, Np);
-    rc = device_cholesky_blocked(Ab, Np, Dinv, dinfo + o, st);
-    if (rc == GPEMU_OK) rc = device_trtri_blocked(Ab, Np, Dinv, W, T, st);
-    if (rc != GPEMU_OK) break;
+    GP_TRY(device_cholesky_blocked(Ab, Np, Dinv, dinfo + o, st));
+    GP_TRY(device_trtri_blocked(Ab, Np, Dinv, W, T, st));
     hipLaunchKernelGGL(lik_z_kernel, dim3((unsigned)((nf + 3) / 4)), dim3(256), 0, st, W, Np, nf, f0, F, k, m->comp,
                        m->sscale, m->smean, m->yexp, m->srcs, dZ, m->lik_chains, m->n_src);
     hipLaunchKernelGGL(lik_gram_kernel, dim3(1), dim3(1024), 0, st, dZ, Ab, Np, nf, f0, (int)o, go);
     if (m->ycov || m->n_src > 0) src_path_count(GPEMU_SRC_PATH_SETUP_BLOCKED);
-    if (hipGetLastError() != hipSuccess) { set_error("likelihood_setup: launch failed"); rc = GPEMU_ERR_HIP; }
+    if (hipGetLastError() != hipSuccess) { set_error("likelihood_setup: launch failed"); return GPEMU_ERR_HIP; }
   }
-  if (rc == GPEMU_OK && hipStreamSynchronize(st) != hipSuccess) { set_error("likelihood_setup: sync failed"); rc = GPEMU_ERR_HIP; }
-  (void)hipFree(Ab); (void)hipFree(Dinv); (void)hipFree(W); (void)hipFree(T);
-  return rc;
+  if (hipStreamSynchronize(st) != hipSuccess) { set_error("likelihood_setup: sync failed"); return GPEMU_ERR_HIP; }
+  return GPEMU_OK;
 }
 
 // k <= KMAX <= 32.  The k x k matrix M = I + D^1/2 G D^1/2 is padded to KMAX x KMAX with the identity, so
@@ -488,14 +485,12 @@ int launch_loglik_tasks(gpemu_model *const *ms, int ng, int64_t B, const double 
   lt.nwg = (ntask + LL_TASK_WAVES - 1) / LL_TASK_WAVES;
   if (lt.nwg > 1) {
     // the terms' way to the last workgroup: per model (the first group's), grown with the batch
+    // (a launch on the model's own stream may still read the old pair, as one on `st` may)
     if (m0->lik_terms_cap < B) {
-      GP_HIP(hipStreamSynchronize(st));
-      (void)hipFree(m0->lik_terms);
-      (void)hipFree(m0->lik_tickets);
-      m0->lik_terms = nullptr; m0->lik_tickets = nullptr; m0->lik_terms_cap = 0;
       const int64_t cap = round_up(B, 128);
-      GP_HIP(hipMalloc((void **)&m0->lik_terms, sizeof(double) * (size_t)cap * LL_TASKS_MAX));
-      GP_HIP(hipMalloc((void **)&m0->lik_tickets, sizeof(unsigned) * (size_t)cap));
+      GP_TRY(dev_reserve(&m0->lik_terms_cap, cap, {st, m0->stream},
+                         {dev_field(&m0->lik_terms, cap * LL_TASKS_MAX), dev_field(&m0->lik_tickets, cap)}));
+      m0->lik_terms_cap = 0;   // not usable before the tickets are zero
       GP_HIP(hipMemsetAsync(m0->lik_tickets, 0, sizeof(unsigned) * (size_t)cap, st));
       m0->lik_terms_cap = cap;
     }

@@ -610,25 +610,26 @@ extern "C" int gpemu_pca_fit(int device, int64_t N, int64_t F, const double *Y, 
          *dW = nullptr, *dpart = nullptr, *dJ = nullptr, *dss = nullptr;
   int *dflags = nullptr, *dtickets = nullptr;
   unsigned long long *doff = nullptr;
-  hipError_t e = hipMalloc((void **)&dY, sizeof(double) * N * F);
-  auto A = [&](double **p, int64_t cnt) { if (e == hipSuccess) e = hipMalloc((void **)p, sizeof(double) * (size_t)cnt); };
-  A(&dYs, N * F); A(&dmean, F); A(&dvar, F); A(&dscale, F); A(&dpm, F); A(&dW, (int64_t)ncols * ldw);
-  if (e == hipSuccess) e = hipExtMallocWithFlags((void **)&dpart, sizeof(double) * (size_t)npairs * nsplit * PP * PP, hipDeviceMallocUncached);
-  A(&dJ, (int64_t)npairs * PP * PP); A(&dss, F);
-  if (e == hipSuccess) e = hipMalloc((void **)&dflags, sizeof(int) * npairs);
-  if (e == hipSuccess) e = hipMalloc((void **)&dtickets, sizeof(int) * npairs);
-  if (e == hipSuccess) e = hipMemset(dtickets, 0, sizeof(int) * npairs);
-  if (e == hipSuccess) e = hipMalloc((void **)&doff, 8 * sizeof(unsigned long long));
-  if (e == hipSuccess) e = hipMemset(doff, 0, 8 * sizeof(unsigned long long));
   std::vector<double> hW;
   int sweeps = 0;
-  if (e == hipSuccess) e = hipMemcpy(dY, Y, sizeof(double) * N * F, hipMemcpyHostToDevice);
-  if (e == hipSuccess) {
+  {
+    DevScope sc(nullptr);   // a one-off decomposition: the null stream
+    GP_TRY(sc.alloc(&dY, N * F)); GP_TRY(sc.alloc(&dYs, N * F)); GP_TRY(sc.alloc(&dmean, F)); GP_TRY(sc.alloc(&dvar, F));
+    GP_TRY(sc.alloc(&dscale, F)); GP_TRY(sc.alloc(&dpm, F)); GP_TRY(sc.alloc(&dW, (int64_t)ncols * ldw));
+    GP_HIP(hipExtMallocWithFlags((void **)&dpart, sizeof(double) * (size_t)npairs * nsplit * PP * PP, hipDeviceMallocUncached));
+    sc.adopt(dpart);
+    GP_TRY(sc.alloc(&dJ, (int64_t)npairs * PP * PP)); GP_TRY(sc.alloc(&dss, F));
+    GP_TRY(sc.alloc(&dflags, npairs));
+    GP_TRY(sc.alloc(&dtickets, npairs));
+    GP_HIP(hipMemset(dtickets, 0, sizeof(int) * npairs));
+    GP_TRY(sc.alloc(&doff, 8));
+    GP_HIP(hipMemset(doff, 0, 8 * sizeof(unsigned long long)));
+    GP_HIP(hipMemcpy(dY, Y, sizeof(double) * N * F, hipMemcpyHostToDevice));
     hipLaunchKernelGGL(column_stats_kernel, dim3((unsigned)((F + 63) / 64)), dim3(64), 0, nullptr, dY, (int)N, (int)F,
                        dmean, dvar, dscale);
     hipLaunchKernelGGL(standardise_kernel, dim3((unsigned)((N * F + 255) / 256)), dim3(256), 0, nullptr, dY, (int)N,
                        (int)F, dmean, dscale, dYs);
-    e = hipMemsetAsync(dW, 0, sizeof(double) * (size_t)ncols * ldw, nullptr);
+    GP_HIP(hipMemsetAsync(dW, 0, sizeof(double) * (size_t)ncols * ldw, nullptr));
     hipLaunchKernelGGL(pca_centre_kernel, dim3((unsigned)((F + 63) / 64)), dim3(64), 0, nullptr, dYs, (int)N, (int)F,
                        dpm, dW, ldw, tw ? 1 : 0, dss);
     hipLaunchKernelGGL(pca_identity_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, dW, ldw, mpad, n);
@@ -641,21 +642,21 @@ extern "C" int gpemu_pca_fit(int device, int64_t N, int64_t F, const double *Y, 
     double noise2 = 0.0;
     {
       std::vector<double> hss((size_t)F);
-      if (e == hipSuccess) e = hipMemcpy(hss.data(), dss, sizeof(double) * F, hipMemcpyDeviceToHost);
+      GP_HIP(hipMemcpy(hss.data(), dss, sizeof(double) * F, hipMemcpyDeviceToHost));
       double fro2 = 0.0;
       for (double v : hss) fro2 += v;
       const double noise_c = 4.0;
       const double lim = noise_c * std::sqrt((double)m) * 2.220446049250313e-16;
       noise2 = lim * lim * fro2;
     }
-    for (sweeps = 0; sweeps < 60 && e == hipSuccess; ++sweeps) {
-      e = hipMemsetAsync(doff, 0, sizeof(unsigned long long), nullptr);
+    for (sweeps = 0; sweeps < 60; ++sweeps) {
+      GP_HIP(hipMemsetAsync(doff, 0, sizeof(unsigned long long), nullptr));
       for (int r = 0; r < nb - 1; ++r) {
         if (PB == 16) jacobi_round<16>(dW, ldw, mpad, nstrips, nb, r, nsplit, inner, tol, noise2, dpart, dtickets, dJ, dflags, doff, apply_y);
         else jacobi_round<32>(dW, ldw, mpad, nstrips, nb, r, nsplit, inner, tol, noise2, dpart, dtickets, dJ, dflags, doff, apply_y);
       }
       unsigned long long bits = 0, dbg[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-      if (e == hipSuccess) e = hipMemcpy(dbg, doff, sizeof(dbg), hipMemcpyDeviceToHost);
+      GP_HIP(hipMemcpy(dbg, doff, sizeof(dbg), hipMemcpyDeviceToHost));
       bits = dbg[0];
       if (trace && dbg[3])
         fprintf(stderr, "pca_fit:   pair 0 so far: %llu solves, %.0f shader clocks, %.2f us each (%.2f GHz)\n", dbg[3],
@@ -668,19 +669,14 @@ extern "C" int gpemu_pca_fit(int device, int64_t N, int64_t F, const double *Y, 
       if (trace) fprintf(stderr, "pca_fit: sweep %d  largest cosine %.3e  (tol %.3e)\n", sweeps, off, tol);
       if (off <= tol) { ++sweeps; break; }
     }
-    if (e == hipSuccess) e = hipGetLastError();
-  }
-  if (e == hipSuccess) {
+    GP_HIP(hipGetLastError());
     hW.resize((size_t)ncols * ldw);
-    e = hipMemcpy(hW.data(), dW, sizeof(double) * hW.size(), hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(scaler_mean, dmean, sizeof(double) * F, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(scaler_var, dvar, sizeof(double) * F, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(scaler_scale, dscale, sizeof(double) * F, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(pca_mean, dpm, sizeof(double) * F, hipMemcpyDeviceToHost);
+    GP_HIP(hipMemcpy(hW.data(), dW, sizeof(double) * hW.size(), hipMemcpyDeviceToHost));
+    GP_HIP(hipMemcpy(scaler_mean, dmean, sizeof(double) * F, hipMemcpyDeviceToHost));
+    GP_HIP(hipMemcpy(scaler_var, dvar, sizeof(double) * F, hipMemcpyDeviceToHost));
+    GP_HIP(hipMemcpy(scaler_scale, dscale, sizeof(double) * F, hipMemcpyDeviceToHost));
+    GP_HIP(hipMemcpy(pca_mean, dpm, sizeof(double) * F, hipMemcpyDeviceToHost));
   }
-  (void)hipFree(dY); (void)hipFree(dYs); (void)hipFree(dmean); (void)hipFree(dvar); (void)hipFree(dscale);
-  (void)hipFree(dpm); (void)hipFree(dW); (void)hipFree(dpart); (void)hipFree(dJ); (void)hipFree(dflags); (void)hipFree(dtickets); (void)hipFree(doff); (void)hipFree(dss);
-  if (e != hipSuccess) { set_error("pca_fit: %s", hipGetErrorString(e)); return GPEMU_ERR_HIP; }
   if (n_sweeps) *n_sweeps = sweeps;
 
   // ---- host assembly: order by singular value, normalise, sign convention -----------------------------

@@ -147,17 +147,6 @@ static int pcov_budget(int64_t workspace_bytes, int64_t &budget, bool &automatic
   return GPEMU_OK;
 }
 
-struct DevFree {
-  std::vector<void *> p;
-  ~DevFree() { for (void *q : p) (void)hipFree(q); }
-  template <typename T> int alloc(T **q, int64_t n) {
-    *q = nullptr;
-    GP_HIP(hipMalloc((void **)q, sizeof(T) * (size_t)(n < 1 ? 1 : n)));
-    p.push_back(*q);
-    return GPEMU_OK;
-  }
-};
-
 // dX1 [M1][d], dX2 [M2][d] or null (symmetric form) -> dcov [k][M1][M2]; everything on st (asynchronous)
 int predict_cov(gpemu_model *m, int64_t M1, const double *dX1, int64_t M2, const double *dX2, int64_t workspace_bytes,
                 double *dcov, hipStream_t st) {
@@ -180,13 +169,15 @@ int predict_cov(gpemu_model *m, int64_t M1, const double *dX1, int64_t M2, const
                 "(%lld bytes needed)", (long long)workspace_bytes, (long long)need);
     return GPEMU_ERR_ARG;
   }
-  DevFree fr;
+  DevScope sc(st);
   double *KT1 = nullptr, *V1 = nullptr, *KT2 = nullptr, *V2 = nullptr, *Cc = nullptr;
-  int rc = fr.alloc(&KT1, (int64_t)pc * N64 * M1p);
-  if (rc == GPEMU_OK) rc = fr.alloc(&V1, (int64_t)pc * N64 * M1p);
-  if (rc == GPEMU_OK && !sym) rc = fr.alloc(&KT2, (int64_t)pc * N64 * mc);
-  if (rc == GPEMU_OK && !sym) rc = fr.alloc(&V2, (int64_t)pc * N64 * mc);
-  if (rc == GPEMU_OK) rc = fr.alloc(&Cc, (int64_t)pc * M1p * mc);
+  const int rc = [&]() -> int {
+    GP_TRY(sc.alloc(&KT1, (int64_t)pc * N64 * M1p));
+    GP_TRY(sc.alloc(&V1, (int64_t)pc * N64 * M1p));
+    if (!sym) GP_TRY(sc.alloc(&KT2, (int64_t)pc * N64 * mc));
+    if (!sym) GP_TRY(sc.alloc(&V2, (int64_t)pc * N64 * mc));
+    return sc.alloc(&Cc, (int64_t)pc * M1p * mc);
+  }();
   if (rc != GPEMU_OK) {
     if (automatic) {   // the free memory went elsewhere between the query and the allocation
       const std::string why = gpemu_last_error();
@@ -328,18 +319,18 @@ int sample_from_cov(gpemu_model *m, int64_t M, int64_t n, const double *dcov, co
     return GPEMU_ERR_ARG;
   }
   const int slots = (int)std::min<int64_t>(k, std::max<int64_t>(1, std::min<int64_t>(budget / per, 16384 * 64 / Mp)));
-  DevFree fr;
+  DevScope sc(st);
   DrawArgs a;
   double *A = nullptr, *Dinv = nullptr, *Z = nullptr, *Y = nullptr, *tau = nullptr;
   int *pc_of = nullptr, *ok = nullptr, *dinfo = nullptr;
-  GP_TRY(fr.alloc(&A, (int64_t)slots * Mp * Mp));
-  GP_TRY(fr.alloc(&Dinv, (int64_t)slots * Mp * PC_NB));
-  GP_TRY(fr.alloc(&Z, (int64_t)slots * Mp * np));
-  GP_TRY(fr.alloc(&Y, (int64_t)slots * Mp * np));
-  GP_TRY(fr.alloc(&tau, slots));
-  GP_TRY(fr.alloc(&pc_of, slots));
-  GP_TRY(fr.alloc(&ok, slots));
-  GP_TRY(fr.alloc(&dinfo, slots));
+  GP_TRY(sc.alloc(&A, (int64_t)slots * Mp * Mp));
+  GP_TRY(sc.alloc(&Dinv, (int64_t)slots * Mp * PC_NB));
+  GP_TRY(sc.alloc(&Z, (int64_t)slots * Mp * np));
+  GP_TRY(sc.alloc(&Y, (int64_t)slots * Mp * np));
+  GP_TRY(sc.alloc(&tau, slots));
+  GP_TRY(sc.alloc(&pc_of, slots));
+  GP_TRY(sc.alloc(&ok, slots));
+  GP_TRY(sc.alloc(&dinfo, slots));
   a.cov = dcov; a.z = dz; a.mean = dmean; a.pc_of = pc_of; a.tau = tau; a.ok = ok;
   a.A = A; a.Z = Z; a.Y = Y; a.out = dout; a.M = M; a.n = n; a.Mp = Mp; a.np = np; a.k = k;
   std::vector<int> todo;   // PCs without a factor yet

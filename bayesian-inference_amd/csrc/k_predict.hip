@@ -626,12 +626,14 @@ static int launch_trmm_vsq_one(gpemu_model *m, int64_t B, hipStream_t st, bool p
         return GPEMU_ERR_UNSUPPORTED;
       }
       // schedules are kept (a few KB each): launches in flight keep reading the one they were given
-      gpemu_model::SchedEntry e{ncb, cap, nullptr, nullptr, max_items, nworkers};
-      GP_HIP(hipMalloc(&e.items, sizeof(TrmmItem) * flat.size()));
-      GP_HIP(hipMalloc((void **)&e.cnt, sizeof(int) * cnt.size()));
-      GP_HIP(hipMemcpy(e.items, flat.data(), sizeof(TrmmItem) * flat.size(), hipMemcpyHostToDevice));
-      GP_HIP(hipMemcpy(e.cnt, cnt.data(), sizeof(int) * cnt.size(), hipMemcpyHostToDevice));
-      m->sched_cache.push_back(e);
+      DevScope sc(st);   // owns the new entry until it is complete
+      TrmmItem *ditems = nullptr;
+      int *dcnt = nullptr;
+      GP_TRY(sc.alloc(&ditems, (int64_t)flat.size()));
+      GP_TRY(sc.alloc(&dcnt, (int64_t)cnt.size()));
+      GP_HIP(hipMemcpy(ditems, flat.data(), sizeof(TrmmItem) * flat.size(), hipMemcpyHostToDevice));
+      GP_HIP(hipMemcpy(dcnt, cnt.data(), sizeof(int) * cnt.size(), hipMemcpyHostToDevice));
+      m->sched_cache.push_back({ncb, cap, sc.release(ditems), sc.release(dcnt), max_items, nworkers});
       hit = &m->sched_cache.back();
     }
     m->sched_items = hit->items; m->sched_cnt = hit->cnt;
@@ -649,7 +651,7 @@ static int launch_trmm_vsq_one(gpemu_model *m, int64_t B, hipStream_t st, bool p
   static unsigned long long *dstamps = nullptr;
   static int stamp_calls = 0;
   if (stamp_path && !dstamps) {
-    GP_HIP(hipMalloc((void **)&dstamps, sizeof(unsigned long long) * 16 * 1024));
+    GP_TRY(dev_alloc(&dstamps, 16 * 1024));
     GP_HIP(hipMemset(dstamps, 0, sizeof(unsigned long long) * 16 * 1024));
   }
   hipLaunchKernelGGL(trmm_vsq_dma_kernel, dim3((unsigned)m->sched_workers), dim3(512), 0, st, m->Wt,

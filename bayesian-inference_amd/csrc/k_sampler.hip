@@ -219,9 +219,12 @@ static int ensure_chain(gpemu_sampler *s, int64_t need) {
   if (need <= s->chain_cap) return GPEMU_OK;
   int64_t cap = s->chain_cap ? s->chain_cap : 256;
   while (cap < need) cap *= 2;
+  // the new pair belongs to the scope until the old contents are in it: a failure on the way leaks nothing and leaves
+  // the sampler's chain as it was
+  DevScope sc(s->stream);
   double *nc = nullptr, *nl = nullptr;
-  GP_HIP(hipMalloc((void **)&nc, sizeof(double) * (size_t)(cap * s->W * s->d)));
-  GP_HIP(hipMalloc((void **)&nl, sizeof(double) * (size_t)(cap * s->W)));
+  GP_TRY(sc.alloc(&nc, cap * s->W * s->d));
+  GP_TRY(sc.alloc(&nl, cap * s->W));
   if (s->chain_len > 0) {
     GP_HIP(hipMemcpyAsync(nc, s->chain, sizeof(double) * (size_t)(s->chain_len * s->W * s->d),
                           hipMemcpyDeviceToDevice, s->stream));
@@ -229,9 +232,9 @@ static int ensure_chain(gpemu_sampler *s, int64_t need) {
                           hipMemcpyDeviceToDevice, s->stream));
   }
   GP_HIP(hipStreamSynchronize(s->stream));
-  (void)hipFree(s->chain);
-  (void)hipFree(s->lpchain);
-  s->chain = nc; s->lpchain = nl; s->chain_cap = cap;
+  dev_free(s->chain);
+  dev_free(s->lpchain);
+  s->chain = sc.release(nc); s->lpchain = sc.release(nl); s->chain_cap = cap;
   return GPEMU_OK;
 }
 
@@ -362,6 +365,38 @@ int gpemu_sampler_create(gpemu_sampler **out, gpemu_model *const *groups, int n_
   return gpemu_sampler_create_chains(out, groups, n_groups, W, a, &seed, 1);
 }
 
+// the device buffers of a new sampler, whose sizes are set: gpemu_sampler_create_chains destroys `s` if this fails
+static int sampler_fill(gpemu_sampler *s, const uint64_t *seeds) {
+  const int64_t W = s->W, dp = s->dp, n_chains = s->nchains;
+  GP_TRY(dev_alloc(&s->Xbuf, 2 * W * dp));
+  GP_TRY(dev_alloc(&s->lpbuf, 2 * W));
+  GP_TRY(dev_alloc(&s->inds, W * RNG_RING));
+  GP_TRY(dev_alloc(&s->idx, 2 * W * RNG_RING));
+  GP_TRY(dev_alloc(&s->zz, 2 * W * RNG_RING));
+  GP_TRY(dev_alloc(&s->logu, 2 * W * RNG_RING));
+  GP_TRY(dev_alloc(&s->rint, 2 * W * RNG_RING));
+  GP_TRY(dev_alloc(&s->fac, 2 * W * RNG_RING));
+  GP_TRY(dev_alloc(&s->pos, W * RNG_RING));
+  GP_TRY(dev_alloc(&s->q2, 2 * s->qcap * dp));
+  GP_TRY(dev_alloc(&s->q, s->qcap * dp));
+  GP_TRY(dev_alloc(&s->factors, W));
+  GP_TRY(dev_alloc(&s->newlp, s->qcap));
+  GP_TRY(dev_alloc(&s->naccept, W));
+  GP_TRY(dev_alloc(&s->flags, 2));
+  GP_TRY(dev_alloc(&s->seeds, n_chains));
+  GP_HIP(hipMemcpy(s->seeds, seeds, sizeof(unsigned long long) * n_chains, hipMemcpyHostToDevice));
+  s->X = s->Xbuf; s->logp = s->lpbuf; s->cur = 0;
+
+  GP_HIP(hipMemsetAsync(s->q, 0, sizeof(double) * s->qcap * dp, s->stream));
+  GP_HIP(hipMemsetAsync(s->q2, 0, sizeof(double) * 2 * s->qcap * dp, s->stream));
+  GP_HIP(hipMemsetAsync(s->lpbuf, 0, sizeof(double) * 2 * W, s->stream));
+  GP_HIP(hipMemsetAsync(s->naccept, 0, sizeof(long long) * W, s->stream));
+  GP_HIP(hipMemsetAsync(s->flags, 0, sizeof(int) * 2, s->stream));
+  GP_HIP(hipMemsetAsync(s->Xbuf, 0, sizeof(double) * 2 * W * dp, s->stream));
+  GP_HIP(hipStreamSynchronize(s->stream));
+  return GPEMU_OK;
+}
+
 int gpemu_sampler_create_chains(gpemu_sampler **out, gpemu_model *const *groups, int n_groups, int64_t Wc,
                                 double a, const uint64_t *seeds, int n_chains) {
   GP_ARG(out && groups && n_groups > 0 && seeds, "groups / seeds");
@@ -393,43 +428,14 @@ int gpemu_sampler_create_chains(gpemu_sampler **out, gpemu_model *const *groups,
   s->groups.assign(groups, groups + n_groups);
   s->W = W; s->d = d; s->a = a; s->seed = seed;
   s->dp = dpad_of(d);
-  const int64_t dp = s->dp;
   s->nchains = n_chains;
   s->ns[0] = (Wc + 1) / 2 * n_chains; s->ns[1] = Wc / 2 * n_chains;     // proposals of a half, chain after chain
   s->qcap = round_up(s->ns[0], TILE) + TILE;
   s->stream = groups[0]->stream;
-  hipError_t e = hipSuccess;
-  auto A = [&](void **p, size_t bytes) { if (e == hipSuccess) e = hipMalloc(p, bytes ? bytes : 8); };
-  A((void **)&s->Xbuf, sizeof(double) * 2 * W * dp);
-  A((void **)&s->lpbuf, sizeof(double) * 2 * W);
-  A((void **)&s->inds, sizeof(int) * W * RNG_RING);
-  A((void **)&s->idx, sizeof(int) * 2 * W * RNG_RING);
-  A((void **)&s->zz, sizeof(double) * 2 * W * RNG_RING);
-  A((void **)&s->logu, sizeof(double) * 2 * W * RNG_RING);
-  A((void **)&s->rint, sizeof(int) * 2 * W * RNG_RING);
-  A((void **)&s->fac, sizeof(double) * 2 * W * RNG_RING);
-  A((void **)&s->pos, sizeof(int) * W * RNG_RING);
-  A((void **)&s->q2, sizeof(double) * 2 * s->qcap * dp);
-  A((void **)&s->q, sizeof(double) * s->qcap * dp);
-  A((void **)&s->factors, sizeof(double) * W);
-  A((void **)&s->newlp, sizeof(double) * s->qcap);
-  A((void **)&s->naccept, sizeof(long long) * W);
-  A((void **)&s->flags, sizeof(int) * 2);
-  A((void **)&s->seeds, sizeof(unsigned long long) * n_chains);
-  if (e == hipSuccess) e = hipMemcpy(s->seeds, seeds, sizeof(unsigned long long) * n_chains, hipMemcpyHostToDevice);
-  if (e == hipSuccess) { s->X = s->Xbuf; s->logp = s->lpbuf; s->cur = 0; }
-
-  if (e == hipSuccess) e = hipMemsetAsync(s->q, 0, sizeof(double) * s->qcap * dp, s->stream);
-  if (e == hipSuccess) e = hipMemsetAsync(s->q2, 0, sizeof(double) * 2 * s->qcap * dp, s->stream);
-  if (e == hipSuccess) e = hipMemsetAsync(s->lpbuf, 0, sizeof(double) * 2 * W, s->stream);
-  if (e == hipSuccess) e = hipMemsetAsync(s->naccept, 0, sizeof(long long) * W, s->stream);
-  if (e == hipSuccess) e = hipMemsetAsync(s->flags, 0, sizeof(int) * 2, s->stream);
-  if (e == hipSuccess) e = hipMemsetAsync(s->Xbuf, 0, sizeof(double) * 2 * W * dp, s->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
-  if (e != hipSuccess) {
-    set_error("sampler_create: %s", hipGetErrorString(e));
+  const int rc = sampler_fill(s, seeds);
+  if (rc != GPEMU_OK) {
     gpemu_sampler_destroy(s);
-    return GPEMU_ERR_HIP;
+    return rc;
   }
   *out = s;
   return GPEMU_OK;
@@ -440,15 +446,15 @@ int gpemu_sampler_destroy(gpemu_sampler *s) {
   (void)hipSetDevice(s->device);
   if (s->stream) (void)hipStreamSynchronize(s->stream);
   front_release(s);
-  (void)hipFree(s->Xbuf); (void)hipFree(s->lpbuf); (void)hipFree(s->inds); (void)hipFree(s->idx);
-  (void)hipFree(s->fac); (void)hipFree(s->pos); (void)hipFree(s->q2); (void)hipFree(s->seeds);
-  (void)hipFree(s->zz); (void)hipFree(s->logu); (void)hipFree(s->rint); (void)hipFree(s->q);
-  (void)hipFree(s->factors); (void)hipFree(s->newlp); (void)hipFree(s->naccept); (void)hipFree(s->flags);
-  (void)hipFree(s->chain); (void)hipFree(s->lpchain);
-  (void)hipFree(s->snapX); (void)hipFree(s->snaplp); (void)hipFree(s->snapacc); (void)hipFree(s->snapswap);
-  (void)hipFree(s->acf_part); (void)hipFree(s->acf_acf); (void)hipFree(s->acf_mean); (void)hipFree(s->acf_acf0);
-  (void)hipFree(s->betas); (void)hipFree(s->nswap_acc); (void)hipFree(s->nswap_try); (void)hipFree(s->mean_ll);
-  for (int h = 0; h < 2; ++h) { (void)hipFree(s->gmine[h]); (void)hipFree(s->gfull[h]); }
+  dev_free(s->Xbuf); dev_free(s->lpbuf); dev_free(s->inds); dev_free(s->idx);
+  dev_free(s->fac); dev_free(s->pos); dev_free(s->q2); dev_free(s->seeds);
+  dev_free(s->zz); dev_free(s->logu); dev_free(s->rint); dev_free(s->q);
+  dev_free(s->factors); dev_free(s->newlp); dev_free(s->naccept); dev_free(s->flags);
+  dev_free(s->chain); dev_free(s->lpchain);
+  dev_free(s->snapX); dev_free(s->snaplp); dev_free(s->snapacc); dev_free(s->snapswap);
+  dev_free(s->acf_part); dev_free(s->acf_acf); dev_free(s->acf_mean); dev_free(s->acf_acf0);
+  dev_free(s->betas); dev_free(s->nswap_acc); dev_free(s->nswap_try); dev_free(s->mean_ll);
+  for (int h = 0; h < 2; ++h) { dev_free(s->gmine[h]); dev_free(s->gfull[h]); }
   delete s;
   return GPEMU_OK;
 }
@@ -459,48 +465,39 @@ int gpemu_sampler_set_state(gpemu_sampler *s, const double *X0, const double *lo
   hipStream_t st = s->stream;
   const LaunchSwitches sw = read_launch_switches();
   const int64_t W = s->W, d = s->d;
+  DevScope sc(st);
   double *tmp = nullptr;
-  GP_HIP(hipMalloc((void **)&tmp, sizeof(double) * W * d));
-  hipError_t e = hipMemcpyAsync(tmp, X0, sizeof(double) * W * d, hipMemcpyHostToDevice, st);
-  int rc = GPEMU_OK;
-  if (e != hipSuccess) { set_error("set_state: %s", hipGetErrorString(e)); rc = GPEMU_ERR_HIP; }
-  if (rc == GPEMU_OK) {
-    hipLaunchKernelGGL(s->dp == DPAD ? pad_rows_kernel<DPAD> : pad_rows_kernel<DPAD_WIDE>,
-                       dim3((unsigned)((W * s->dp + 255) / 256)), dim3(256), 0, st, tmp, s->X, (int)W, (int)d);
-    if (logp0) {
-      e = hipMemcpyAsync(s->logp, logp0, sizeof(double) * W, hipMemcpyHostToDevice, st);
-      if (e != hipSuccess) { set_error("set_state: %s", hipGetErrorString(e)); rc = GPEMU_ERR_HIP; }
-    } else {
-      // evaluate all walkers; X has exactly W rows, so go through a padded scratch copy in chunks
-      // chunks never straddle a chain: every chunk is a whole number of chains or a piece of one
-      const int64_t Wc = W / s->nchains;
-      const int64_t cap = std::min<int64_t>(s->ns[0], 1024);
-      const int64_t step = (Wc <= cap) ? (cap / Wc) * Wc : cap;
-      for (int64_t off = 0; off < W && rc == GPEMU_OK;) {
-        int64_t nb = std::min<int64_t>(step, W - off);
-        if (Wc > cap) nb = std::min<int64_t>(nb, Wc - off % Wc);
-        e = hipMemcpyAsync(s->q, s->X + off * s->dp, sizeof(double) * nb * s->dp, hipMemcpyDeviceToDevice, st);
-        if (e != hipSuccess) { set_error("set_state: %s", hipGetErrorString(e)); rc = GPEMU_ERR_HIP; break; }
-        AcceptArgs ca;                       // not an accept: only tells the likelihood which chain a row belongs to
-        ca.chain_per = s->nchains > 1 ? (int)Wc : 0;
-        ca.chain_data = s->tempered ? 0 : 1;     // the rungs of a tempered sampler share data vector 0
-        ca.first = off;
-        ca.dp = s->dp;
-        for (gpemu_model *m : s->groups) m->variant_B = (Wc + 1) / 2;
-        rc = logpost_eval(s->groups.data(), (int)s->groups.size(), nb, s->q, s->newlp, st, sw, &ca, nullptr);
-        for (gpemu_model *m : s->groups) m->variant_B = 0;
-        if (rc == GPEMU_OK) {
-          e = hipMemcpyAsync(s->logp + off, s->newlp, sizeof(double) * nb, hipMemcpyDeviceToDevice, st);
-          if (e != hipSuccess) { set_error("set_state: %s", hipGetErrorString(e)); rc = GPEMU_ERR_HIP; }
-        }
-        off += nb;
-      }
+  GP_TRY(sc.alloc(&tmp, W * d));
+  GP_TRY(upload(tmp, X0, W * d, st));
+  hipLaunchKernelGGL(s->dp == DPAD ? pad_rows_kernel<DPAD> : pad_rows_kernel<DPAD_WIDE>,
+                     dim3((unsigned)((W * s->dp + 255) / 256)), dim3(256), 0, st, tmp, s->X, (int)W, (int)d);
+  if (logp0) {
+    GP_TRY(upload(s->logp, logp0, W, st));
+  } else {
+    // evaluate all walkers; X has exactly W rows, so go through a padded scratch copy in chunks
+    // chunks never straddle a chain: every chunk is a whole number of chains or a piece of one
+    const int64_t Wc = W / s->nchains;
+    const int64_t cap = std::min<int64_t>(s->ns[0], 1024);
+    const int64_t step = (Wc <= cap) ? (cap / Wc) * Wc : cap;
+    for (int64_t off = 0; off < W;) {
+      int64_t nb = std::min<int64_t>(step, W - off);
+      if (Wc > cap) nb = std::min<int64_t>(nb, Wc - off % Wc);
+      GP_HIP(hipMemcpyAsync(s->q, s->X + off * s->dp, sizeof(double) * nb * s->dp, hipMemcpyDeviceToDevice, st));
+      AcceptArgs ca;                       // not an accept: only tells the likelihood which chain a row belongs to
+      ca.chain_per = s->nchains > 1 ? (int)Wc : 0;
+      ca.chain_data = s->tempered ? 0 : 1;     // the rungs of a tempered sampler share data vector 0
+      ca.first = off;
+      ca.dp = s->dp;
+      for (gpemu_model *m : s->groups) m->variant_B = (Wc + 1) / 2;
+      const int rc = logpost_eval(s->groups.data(), (int)s->groups.size(), nb, s->q, s->newlp, st, sw, &ca, nullptr);
+      for (gpemu_model *m : s->groups) m->variant_B = 0;
+      GP_TRY(rc);
+      GP_HIP(hipMemcpyAsync(s->logp + off, s->newlp, sizeof(double) * nb, hipMemcpyDeviceToDevice, st));
+      off += nb;
     }
   }
-  e = hipStreamSynchronize(st);
-  if (rc == GPEMU_OK && e != hipSuccess) { set_error("set_state: %s", hipGetErrorString(e)); rc = GPEMU_ERR_HIP; }
-  (void)hipFree(tmp);
-  return rc;
+  GP_HIP(hipStreamSynchronize(st));
+  return GPEMU_OK;
 }
 
 int gpemu_sampler_get_state(gpemu_sampler *s, double *X, double *logp) {
@@ -509,14 +506,13 @@ int gpemu_sampler_get_state(gpemu_sampler *s, double *X, double *logp) {
   hipStream_t st = s->stream;
   const int64_t W = s->W, d = s->d;
   if (X) {
+    DevScope sc(st);
     double *tmp = nullptr;
-    GP_HIP(hipMalloc((void **)&tmp, sizeof(double) * W * d));
+    GP_TRY(sc.alloc(&tmp, W * d));
     hipLaunchKernelGGL(s->dp == DPAD ? unpad_rows_kernel<DPAD> : unpad_rows_kernel<DPAD_WIDE>,
                        dim3((unsigned)((W * d + 255) / 256)), dim3(256), 0, st, s->X, tmp, (int)W, (int)d);
-    hipError_t e = hipMemcpyAsync(X, tmp, sizeof(double) * W * d, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    (void)hipFree(tmp);
-    if (e != hipSuccess) { set_error("get_state: %s", hipGetErrorString(e)); return GPEMU_ERR_HIP; }
+    GP_TRY(sc.download(X, tmp, W * d));
+    GP_HIP(hipStreamSynchronize(st));
   }
   if (logp) {
     GP_HIP(hipMemcpyAsync(logp, s->logp, sizeof(double) * W, hipMemcpyDeviceToHost, st));
@@ -548,16 +544,16 @@ int gpemu_sampler_snapshot(gpemu_sampler *s) {
   GP_HIP(hipSetDevice(s->device));
   const int64_t W = s->W;
   if (!s->snapX) {
-    GP_HIP(hipMalloc((void **)&s->snapX, sizeof(double) * W * s->dp));
-    GP_HIP(hipMalloc((void **)&s->snaplp, sizeof(double) * W));
-    GP_HIP(hipMalloc((void **)&s->snapacc, sizeof(long long) * W));
+    GP_TRY(dev_alloc(&s->snapX, W * s->dp));
+    GP_TRY(dev_alloc(&s->snaplp, W));
+    GP_TRY(dev_alloc(&s->snapacc, W));
   }
   GP_HIP(hipMemcpyAsync(s->snapX, s->X, sizeof(double) * W * s->dp, hipMemcpyDeviceToDevice, s->stream));
   GP_HIP(hipMemcpyAsync(s->snaplp, s->logp, sizeof(double) * W, hipMemcpyDeviceToDevice, s->stream));
   GP_HIP(hipMemcpyAsync(s->snapacc, s->naccept, sizeof(long long) * W, hipMemcpyDeviceToDevice, s->stream));
   if (s->tempered) {          // the swap counters belong to the state as well
     const size_t npair = (size_t)(s->nchains - 1) * (size_t)(W / s->nchains);
-    if (!s->snapswap) GP_HIP(hipMalloc((void **)&s->snapswap, sizeof(long long) * 2 * npair));
+    if (!s->snapswap) GP_TRY(dev_alloc(&s->snapswap, (int64_t)(2 * npair)));
     GP_HIP(hipMemcpyAsync(s->snapswap, s->nswap_acc, sizeof(long long) * npair, hipMemcpyDeviceToDevice, s->stream));
     GP_HIP(hipMemcpyAsync(s->snapswap + npair, s->nswap_try, sizeof(long long) * npair, hipMemcpyDeviceToDevice,
                           s->stream));
@@ -909,13 +905,8 @@ int gpemu_sampler_run_sharded(gpemu_sampler *s, gpemu_comm *c, int64_t steps, in
     const int r = emulate_world > 0 ? 0 : c->rank;
     lo[h] = std::min<int64_t>((int64_t)r * share, s->ns[h]);
     hi[h] = std::min<int64_t>(lo[h] + share, s->ns[h]);
-    if (s->gworld != world || s->gper[h] != per) {
-      (void)hipFree(s->gmine[h]); (void)hipFree(s->gfull[h]);
-      s->gmine[h] = s->gfull[h] = nullptr;
-      GP_HIP(hipMalloc((void **)&s->gmine[h], sizeof(double) * per));
-      GP_HIP(hipMalloc((void **)&s->gfull[h], sizeof(double) * per * world));
-      s->gper[h] = per;
-    }
+    if (s->gworld != world || s->gper[h] != per) s->gper[h] = 0;   // sized exactly: any other split allocates anew
+    GP_TRY(dev_reserve(&s->gper[h], per, {st}, {dev_field(&s->gmine[h], per), dev_field(&s->gfull[h], per * world)}));
     hipLaunchKernelGGL(fill_kernel, dim3((unsigned)((per + 255) / 256)), dim3(256), 0, st, s->gmine[h], per,
                        emulate_world > 0 ? -INFINITY : 0.0);
   }

@@ -131,18 +131,20 @@ int gpemu_sampler_create_tempered(gpemu_sampler **out, gpemu_model *const *group
   gpemu_sampler *s = nullptr;
   GP_TRY(gpemu_sampler_create_chains(&s, groups, n_groups, Wc, a, seeds, n_temps));
   const size_t npair = (size_t)(n_temps - 1) * (size_t)Wc;
-  hipError_t e = hipMalloc((void **)&s->betas, sizeof(double) * n_temps);
-  if (e == hipSuccess) e = hipMalloc((void **)&s->nswap_acc, sizeof(long long) * npair);
-  if (e == hipSuccess) e = hipMalloc((void **)&s->nswap_try, sizeof(long long) * npair);
-  if (e == hipSuccess) e = hipMalloc((void **)&s->mean_ll, sizeof(double) * n_temps);
-  if (e == hipSuccess) e = hipMemcpy(s->betas, betas, sizeof(double) * n_temps, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemsetAsync(s->nswap_acc, 0, sizeof(long long) * npair, s->stream);
-  if (e == hipSuccess) e = hipMemsetAsync(s->nswap_try, 0, sizeof(long long) * npair, s->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
-  if (e != hipSuccess) {
-    set_error("sampler_create_tempered: %s", hipGetErrorString(e));
+  const int rc = [&]() -> int {     // the ladder's fields: the sampler is destroyed if one of them fails
+    GP_TRY(dev_alloc(&s->betas, n_temps));
+    GP_TRY(dev_alloc(&s->nswap_acc, (int64_t)npair));
+    GP_TRY(dev_alloc(&s->nswap_try, (int64_t)npair));
+    GP_TRY(dev_alloc(&s->mean_ll, n_temps));
+    GP_HIP(hipMemcpy(s->betas, betas, sizeof(double) * n_temps, hipMemcpyHostToDevice));
+    GP_HIP(hipMemsetAsync(s->nswap_acc, 0, sizeof(long long) * npair, s->stream));
+    GP_HIP(hipMemsetAsync(s->nswap_try, 0, sizeof(long long) * npair, s->stream));
+    GP_HIP(hipStreamSynchronize(s->stream));
+    return GPEMU_OK;
+  }();
+  if (rc != GPEMU_OK) {
     gpemu_sampler_destroy(s);
-    return GPEMU_ERR_HIP;
+    return rc;
   }
   s->tempered = true;
   s->swap_every = swap_every;

@@ -296,16 +296,18 @@ static int small_schedule_ready(gpemu_model *m, int64_t B, hipStream_t st, int w
       if (m->sm_cache.size() >= 16) {                                  // bounded: drop the oldest once nothing reads it
         GP_HIP(hipStreamSynchronize(st));
         GP_HIP(hipStreamSynchronize(m->stream));
-        (void)hipFree(m->sm_cache.front().items);
-        (void)hipFree(m->sm_cache.front().cnt);
+        dev_free(m->sm_cache.front().items);
+        dev_free(m->sm_cache.front().cnt);
         m->sm_cache.erase(m->sm_cache.begin());
       }
-      gpemu_model::SchedEntry e{ncb, cap, nullptr, nullptr, max_items, nworkers};
-      GP_HIP(hipMalloc(&e.items, sizeof(SmallItem) * flat.size()));
-      GP_HIP(hipMalloc((void **)&e.cnt, sizeof(int) * cnt.size()));
-      GP_HIP(hipMemcpy(e.items, flat.data(), sizeof(SmallItem) * flat.size(), hipMemcpyHostToDevice));
-      GP_HIP(hipMemcpy(e.cnt, cnt.data(), sizeof(int) * cnt.size(), hipMemcpyHostToDevice));
-      m->sm_cache.push_back(e);
+      DevScope sc(st);   // owns the new entry until it is complete
+      SmallItem *ditems = nullptr;
+      int *dcnt = nullptr;
+      GP_TRY(sc.alloc(&ditems, (int64_t)flat.size()));
+      GP_TRY(sc.alloc(&dcnt, (int64_t)cnt.size()));
+      GP_HIP(hipMemcpy(ditems, flat.data(), sizeof(SmallItem) * flat.size(), hipMemcpyHostToDevice));
+      GP_HIP(hipMemcpy(dcnt, cnt.data(), sizeof(int) * cnt.size(), hipMemcpyHostToDevice));
+      m->sm_cache.push_back({ncb, cap, sc.release(ditems), sc.release(dcnt), max_items, nworkers});
       hit = &m->sm_cache.back();
     }
     m->sm_items = hit->items; m->sm_cnt = hit->cnt;

@@ -18,6 +18,7 @@ void set_error(const char *fmt, ...) {
   va_end(ap);
   fputc('\n', stderr);
 }
+void count_path(PathFamily, int) {}   // the probe keeps no path counters
 }  // namespace gpemu
 
 int main() {

@@ -28,6 +28,7 @@ void set_error(const char *fmt, ...) {
   va_end(ap);
   fputc('\n', stderr);
 }
+void count_path(PathFamily, int) {}   // the probe keeps no path counters
 int prof_mark(gpemu_model *, hipStream_t) { return -1; }
 void prof_pair(gpemu_model *, int, int, int) {}
 }  // namespace gpemu
