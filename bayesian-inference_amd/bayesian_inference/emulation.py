@@ -482,6 +482,57 @@ def normalised_sensitivity(jacobian, parameters, central_value) -> np.ndarray:
     return np.asarray(jacobian) * np.asarray(parameters)[:, None, :] / np.asarray(central_value)[:, :, None]
 
 
+POSTERIOR_PREDICTIVE_PROBABILITIES = (0.05, 0.5, 0.95)
+_PP_VECTORS = ('mean', 'variance_parameters', 'variance_emulator', 'variance')
+
+
+def merge_posterior_predictive(sorter, group_results) -> dict[str, np.ndarray]:
+    """The groups' posterior-predictive summaries in the merged observable order of ``predict``: every entry is per
+    feature, so the merge is a scatter -- ``convert``'s rule for ``central_value``, applied to the (F,) vectors and the
+    (nq, F) quantiles stacked as the rows of one matrix.  A sorter that has no mapping of its own (a stand-in that only
+    implements ``convert``) converts that matrix as a ``central_value``."""
+    first = next(iter(group_results.values()))
+    rows = {name: np.vstack([g[key] for key in _PP_VECTORS] + [g['quantiles']]) for name, g in group_results.items()}
+    mapping = getattr(sorter, 'emulation_group_to_observable_matrix', None)
+    if mapping is None:
+        merged = np.asarray(sorter.convert({name: {'central_value': m} for name, m in rows.items()})['central_value'])
+    else:
+        merged = np.zeros((len(_PP_VECTORS) + first['quantiles'].shape[0], sorter.shape[1]))
+        for _, (group_name, slice_out, slice_group) in mapping.items():
+            merged[:, slice_out] = rows[group_name][:, slice_group]
+    out = {key: merged[i].copy() for i, key in enumerate(_PP_VECTORS)}
+    out['quantiles'] = merged[len(_PP_VECTORS):].copy()
+    out['probabilities'] = np.array(first['probabilities'], dtype=np.float64)
+    return out
+
+
+def posterior_predictive(parameters, emulation_config: "EmulationConfig",
+                         emulation_group_results: dict[str, dict[str, Any]] | None = None,
+                         emulator_cov_unexplained: dict | None = None,
+                         probabilities=POSTERIOR_PREDICTIVE_PROBABILITIES,
+                         merge_predictions_over_groups: bool = True) -> dict[str, Any]:
+    """What the calibrated model predicts for every observable bin, from ALL rows of ``parameters`` (S, d) --
+    typically the flattened chain -- instead of the few hundred draws the reference's plots push through ``predict``
+    (ref: plot_mcmc.py:343-371): ``mean``, ``variance_parameters`` (spread of the central value over the rows),
+    ``variance_emulator`` (mean emulator variance of one sample, the diagonal of ``predict``'s ``cov`` with one row per
+    call), ``variance`` (their sum), ``quantiles`` (nq, F) and ``probabilities``, in the observable order of
+    ``predict``.  Reduced on the device per group (``DeviceModel.posterior_predictive``)."""
+    parameters = np.array(parameters, ndmin=2, dtype=np.float64)
+    emulation_group_results = emulation_group_results or {}
+    emulator_cov_unexplained = emulator_cov_unexplained or {}
+    per_group = {}
+    for group_name, group_config in emulation_config.emulation_groups_config.items():
+        group_result = emulation_group_results.get(group_name)
+        if group_result is None:
+            group_result = read_emulators(group_config)
+        cov_un = emulator_cov_unexplained[group_name] if emulator_cov_unexplained else None
+        dm = device_model_for(group_result, group_config.n_pc, cov_un)
+        per_group[group_name] = dm.posterior_predictive(parameters, probabilities=probabilities)
+    if not merge_predictions_over_groups:
+        return per_group
+    return merge_posterior_predictive(emulation_config.sort_observables_in_matrix, per_group)
+
+
 def predict_emulation_group(parameters, results, emulation_group_config, emulator_group_cov_unexplained=None):
     """Central values (B,F) and covariances (B,F,F) of one group (ref: emulation.py:466-548).
     The truncation covariance is divided by the number of rows passed, like the reference

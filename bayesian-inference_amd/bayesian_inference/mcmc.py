@@ -214,6 +214,7 @@ def _run_closure_batch(config, indices):
         results = {'chain': one.get_chain(), 'acceptance_fraction': one.acceptance_fraction,
                    'log_prob': one.get_log_prob(), 'autocorrelation_time': tau,
                    'design_point': validation_design[j], 'experimental_pseudodata': datas[c]}
+        _add_posterior_predictive(config, results, emu_cfg, emu_results, truncation_cov)
         logger.info(f'Writing {cfg_j.mcmc_outputfile}')
         io.write_dict_to_h5(results, cfg_j.mcmc_output_dir, 'mcmc.h5', verbose=True)
         pickle_path = Path(cfg_j.sampler_outputfile)
@@ -336,6 +337,7 @@ def run_mcmc(config, closure_index=-1):
             results['map_parameters'] = found['map_parameters']
             results['map_log_prob'] = np.float64(found['map_log_prob'])
             results['map_hessian'] = found['hessian']
+    _add_posterior_predictive(config, results, emu_cfg, emu_results, truncation_cov)
     _write_outputs(config, results, sampler, io)
 
 
@@ -459,10 +461,65 @@ def _run_tempered(config, closure_index):
         validation_design = io.design_array_from_h5(config.output_dir, filename='observables.h5', validation_set=True)
         results['design_point'] = validation_design[closure_index]
         results['experimental_pseudodata'] = data
+    _add_posterior_predictive(config, results, emu_cfg, emu_results, truncation_cov)
     _write_outputs(config, results, one, io)
 
 
 ####################################################################################################
+def posterior_predictive_settings(mc):
+    """(on, probabilities) from the ``parameters.mcmc`` mapping: ``posterior_predictive`` (default off) and the
+    optional ``posterior_predictive_probabilities`` (default 0.05, 0.5, 0.95; each in [0, 1])."""
+    on = bool(mc.get('posterior_predictive', False))
+    probs = mc.get('posterior_predictive_probabilities')
+    if probs is None:
+        probs = emulation.POSTERIOR_PREDICTIVE_PROBABILITIES
+    probs = tuple(float(p) for p in np.atleast_1d(np.asarray(probs, dtype=np.float64)))
+    if not probs or not all(0.0 <= p <= 1.0 for p in probs):
+        raise ValueError("parameters.mcmc.posterior_predictive_probabilities must be probabilities in [0, 1], got "
+                         f"{probs}")
+    return on, probs
+
+
+POSTERIOR_PREDICTIVE_KEYS = ('mean', 'variance_parameters', 'variance_emulator', 'quantiles', 'probabilities')
+
+
+def _add_posterior_predictive(config, results, emu_cfg, emu_results, truncation_cov):
+    """With ``parameters.mcmc.posterior_predictive``: ``posterior_predictive_<key>`` of the production chain into the
+    results that go to mcmc.h5 (``variance`` is the sum of the two parts and is not stored)."""
+    if not getattr(config, 'posterior_predictive', False):
+        return
+    chain = np.asarray(results['chain'], dtype=np.float64)
+    logger.info(f'Posterior-predictive bands from {chain.shape[0] * chain.shape[1]} samples...')
+    out = emulation.posterior_predictive(chain.reshape(-1, chain.shape[-1]), emu_cfg, emulation_group_results=emu_results,
+                                         emulator_cov_unexplained=truncation_cov,
+                                         probabilities=config.posterior_predictive_probabilities)
+    for key in POSTERIOR_PREDICTIVE_KEYS:
+        results[f'posterior_predictive_{key}'] = out[key]
+
+
+def posterior_predictive(config, closure_index=-1, discard=0, thin=1,
+                         probabilities=emulation.POSTERIOR_PREDICTIVE_PROBABILITIES):
+    """``emulation.posterior_predictive`` of the chain stored in mcmc.h5 (of closure chain ``closure_index``, if >= 0),
+    steps ``[discard::thin]``, all walkers."""
+    if closure_index >= 0:
+        config = MCMCConfig(analysis_name=config.analysis_name, parameterization=config.parameterization,
+                            analysis_config=config.analysis_config, config_file=config.config_file,
+                            closure_index=closure_index)
+    if int(discard) < 0 or int(thin) < 1:
+        raise ValueError("discard must be >= 0 and thin >= 1")
+    stored = _data_IO().read_dict_from_h5(config.mcmc_output_dir, 'mcmc.h5')
+    chain = np.asarray(stored['chain'], dtype=np.float64)[int(discard)::int(thin)]
+    if chain.shape[0] == 0:
+        raise ValueError("no stored steps after discard")
+    emu_cfg = emulation.EmulationConfig.from_config_file(
+        analysis_name=config.analysis_name, parameterization=config.parameterization,
+        analysis_config=config.analysis_config, config_file=config.config_file)
+    emu_results = emu_cfg.read_all_emulator_groups()
+    truncation_cov = emulation.compute_emulator_cov_unexplained(emu_cfg, emu_results)
+    return emulation.posterior_predictive(chain.reshape(-1, chain.shape[-1]), emu_cfg, emulation_group_results=emu_results,
+                                          emulator_cov_unexplained=truncation_cov, probabilities=probabilities)
+
+
 def credible_interval(samples, confidence=0.9, interval_type='quantile'):
     """(low, high) of a 1-D sample array (ref: mcmc.py:137-164).
 
@@ -619,6 +676,9 @@ class MCMCConfig:
         self.data_covariance = str(dc) if dc else None
         # the MAP point after production (optional, default off): map_parameters, map_log_prob, map_hessian in mcmc.h5
         self.find_map = bool(mc.get('find_map', False))
+        # per-bin posterior-predictive bands from the whole production chain (optional, default off): five more
+        # entries in mcmc.h5, none without the key
+        self.posterior_predictive, self.posterior_predictive_probabilities = posterior_predictive_settings(mc)
 
         # <output_dir>/<analysis>_<parameterization>[/closure/results/<index>]/{mcmc.h5, mcmc_sampler.pkl}
         self.output_dir = os.path.join(top['output_dir'], f'{analysis_name}_{parameterization}')

@@ -48,14 +48,15 @@ static inline int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * 
 
 // one relaxed host-side increment per launch decision, in one table (gpemu_api.hip) with a row per family of gpemu.h;
 // a path outside its family's enum is not counted
-enum PathFamily { PATHS_LOGPOST, PATHS_FIT, PATHS_WIDE, PATHS_SRC, PATHS_GRAD, PATH_FAMILIES };
+enum PathFamily { PATHS_LOGPOST, PATHS_FIT, PATHS_WIDE, PATHS_SRC, PATHS_GRAD, PATHS_POSTPRED, PATH_FAMILIES };
 void count_path(PathFamily family, int path);
-int read_path_counts(PathFamily family, int64_t *out, int64_t n);     // what the five public gpemu_*_path_counts return
+int read_path_counts(PathFamily family, int64_t *out, int64_t n);     // what the six public gpemu_*_path_counts return
 static inline void path_count(int path) { count_path(PATHS_LOGPOST, path); }    // enum gpemu_path
 static inline void fit_path_count(int path) { count_path(PATHS_FIT, path); }    // enum gpemu_fit_path
 static inline void wide_path_count(int path) { count_path(PATHS_WIDE, path); }  // enum gpemu_wide_path: d > 8 only
 static inline void src_path_count(int path) { count_path(PATHS_SRC, path); }    // enum gpemu_src_path
 static inline void grad_path_count(int path) { count_path(PATHS_GRAD, path); }  // enum gpemu_grad_path
+static inline void postpred_path_count(int path) { count_path(PATHS_POSTPRED, path); }  // enum gpemu_postpred_path
 
 constexpr int DPAD = 8;        // parameter dimensions padded to 8 (reference uses d = 6 or 7) ...
 constexpr int DPAD_WIDE = 16;  // ... or, for 9 <= d <= 16, to 16 (separate instantiations: d <= 8 keeps the code of DPAD)

@@ -1,0 +1,525 @@
+// Exact order statistics of many rows at once (gpemu_select*) and the posterior-predictive reduction built on them
+// (gpemu_posterior_predictive*).
+//
+// Selection: radix select on the order-preserving 64-bit key of a double (negative: all bits flipped, else the sign bit
+// set), most significant byte first, SEL_PASSES = 8 passes of 8 bits.  Per pass
+//   sel_hist_kernel   every workgroup counts a fixed slice of one row into LDS histograms (LDS atomics, the lanes of a
+//                     wave that agree with its first lane added as one count) and adds its non-zero bins to the row's
+//                     global histogram (64-bit integer atomics: counters, no floating-point sum anywhere);
+//   sel_scan_kernel   per row, every rank walks its histogram to the digit that holds it, extends its prefix by that
+//                     digit and keeps the rank within the bin.
+// All ranks of a row share the passes: ranks are sorted on the host, so ranks with one prefix are neighbours and share a
+// "slot" (one histogram); an element is counted in the slot whose prefix it matches, if any.  After the last pass the
+// prefix IS the key of the wanted element -- an element of the input, not an approximation.  The pass count is fixed:
+// a row of equal values, or of values that differ in the last bits only, takes the same eight passes.  The counts are
+// integers, so the result does not depend on the grid, on the slices or on the order in which workgroups arrive.
+// A row with a NaN returns NaN for every rank (np.quantile); -0 and +0 are distinct keys next to each other, so either
+// may be returned for a zero.  More than SEL_MAXR ranks go in groups of SEL_MAXR, rows in batches of SEL_ROWS.
+//
+// Posterior predictive: PC means / variances of all S rows through gpemu_gp_predict_dev in fixed chunks of PP_CHUNK
+// logical rows (a chunk that is not contiguous in the caller's block layout is gathered into a staging buffer first, so
+// the launches -- and the bits -- are those of the contiguous rows), then per block of features
+//   pp_project_kernel  mu[f][s] = (sum_p mean[s][p] comp[p][f]) scale_f + mean_f, feature-major (cv_backproject's sum);
+//   pp_rowsum_kernel   sums of fixed 4096-sample chunks (lane-strided partial sums in index order, fixed butterfly),
+//   pp_finish_kernel   added in chunk order: the mean, then the centred second moment (two passes);
+//   selection on the rows of the workspace.
+// var_emu_f = mean_s sigma^2_f(theta_s) = (sum_p comp[p][f] vbar_p comp[p][f] + cov_unexplained[f][f]) scale_f^2 with
+// vbar_p = mean_s var_p(theta_s): the mean is linear and every term is non-negative, so the F x S variances never exist.
+// Every sum over samples runs over chunks fixed by the logical sample index: the bits do not depend on the workspace,
+// on the feature blocks or on the run.
+#include <algorithm>
+#include <numeric>
+
+#include "internal.h"
+#include "sampler_internal.h"
+
+namespace gpemu {
+
+constexpr int SEL_PASSES = 8;        // 8 bits each
+constexpr int SEL_BINS = 256;
+constexpr int SEL_MAXR = 16;         // ranks (and slots) per group
+constexpr int SEL_ROWS = 512;        // rows per batch: 16 MiB of global histograms
+constexpr int64_t SEL_SLICE = 4096;  // least elements per workgroup
+constexpr int64_t SEL_MAX_WG = 8192; // workgroups per launch, about
+constexpr int64_t PP_CHUNK = 2048;   // logical rows per predict pass (one pass of gpemu_gp_predict_dev)
+constexpr int64_t PP_SUM = 4096;     // samples per partial sum
+constexpr int PP_FT = 32;            // features per projection workgroup
+constexpr int64_t PP_FIXED = GPEMU_POSTPRED_FIXED_BYTES;
+
+typedef unsigned long long u64;
+
+static __device__ __forceinline__ u64 sel_key(double v) {
+  const u64 u = (u64)__double_as_longlong(v);
+  return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
+}
+static __device__ __forceinline__ double sel_value(u64 key) {
+  const u64 u = (key >> 63) ? (key ^ 0x8000000000000000ull) : ~key;
+  return __longlong_as_double((long long)u);
+}
+
+struct SelState {
+  u64 *prefix = nullptr;    // [SEL_ROWS][SEL_MAXR] key bits found so far, per rank
+  u64 *krem = nullptr;      // [SEL_ROWS][SEL_MAXR] rank within the elements that match the prefix
+  u64 *slotpre = nullptr;   // [SEL_ROWS][SEL_MAXR] prefix of each slot
+  int *slot = nullptr;      // [SEL_ROWS][SEL_MAXR] slot of each rank
+  int *nslot = nullptr;     // [SEL_ROWS]
+  int *nan = nullptr;       // [SEL_ROWS] the row holds a NaN
+  u64 *hist = nullptr;      // [SEL_ROWS][SEL_MAXR][SEL_BINS], zero between passes
+};
+
+__global__ __launch_bounds__(256) void sel_init_kernel(SelState s, int rows, int nr, const u64 *__restrict__ ranks) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= rows * SEL_MAXR) return;
+  const int r = i % SEL_MAXR;
+  s.prefix[i] = 0;
+  s.slotpre[i] = 0;
+  s.krem[i] = r < nr ? ranks[r] : 0;
+  s.slot[i] = 0;
+  if (r == 0) {
+    s.nslot[i / SEL_MAXR] = 1;
+    s.nan[i / SEL_MAXR] = 0;
+  }
+}
+
+// workgroup (row rl, slice c) of the batch: elements [c slice, (c + 1) slice) of the row
+__global__ __launch_bounds__(256) void sel_hist_kernel(SelState s, const double *__restrict__ V, int64_t row_stride,
+                                                       int64_t elem_stride, int64_t S, int64_t row0, int nblk,
+                                                       int64_t slice, int pass) {
+  __shared__ unsigned h[SEL_MAXR * SEL_BINS];
+  __shared__ u64 spre[SEL_MAXR];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int64_t rl = blockIdx.x / nblk, c = blockIdx.x % nblk;
+  const int ns = s.nslot[rl];
+  for (int t = tid; t < ns * SEL_BINS; t += 256) h[t] = 0;
+  if (tid < SEL_MAXR) spre[tid] = s.slotpre[rl * SEL_MAXR + tid];
+  __syncthreads();
+  const int shift = 56 - 8 * pass;
+  const double *row = V + (row0 + rl) * row_stride;
+  const int64_t base = c * slice, end = (base + slice < S) ? base + slice : S;
+  bool seen_nan = false;
+  for (int64_t off = base; off < end; off += 256) {   // the trip count is the same for every lane
+    const int64_t i = off + tid;
+    int bin = -1;
+    if (i < end) {
+      const double v = row[i * elem_stride];
+      const u64 key = sel_key(v);
+      if (pass == 0) {
+        bin = (int)(key >> 56);
+        seen_nan |= (v != v);
+      } else {
+        const u64 hi = key >> (shift + 8);
+        for (int j = 0; j < ns; ++j)
+          if ((spre[j] >> (shift + 8)) == hi) bin = j * SEL_BINS + (int)((key >> shift) & 255);
+      }
+    }
+    // the lanes that agree with the wave's first lane count once: the leading bytes of real data are nearly constant
+    const int lead = __builtin_amdgcn_readfirstlane(bin);
+    const u64 same = __ballot(bin == lead);
+    if (lead >= 0 && lane == 0) atomicAdd(&h[lead], (unsigned)__popcll(same));
+    if (bin >= 0 && bin != lead) atomicAdd(&h[bin], 1u);
+  }
+  __syncthreads();
+  u64 *g = s.hist + rl * (SEL_MAXR * SEL_BINS);
+  for (int t = tid; t < ns * SEL_BINS; t += 256)
+    if (h[t]) atomicAdd(&g[t], (u64)h[t]);
+  if (seen_nan) s.nan[rl] = 1;
+}
+
+// one workgroup per row: extend every rank's prefix by the digit of this pass, regroup the slots, clear the histograms
+__global__ __launch_bounds__(256) void sel_scan_kernel(SelState s, int nr, int pass) {
+  __shared__ u64 sh[SEL_MAXR * SEL_BINS];
+  __shared__ u64 pre[SEL_MAXR];
+  const int tid = threadIdx.x;
+  const int64_t rl = blockIdx.x;
+  const int ns = s.nslot[rl];
+  u64 *g = s.hist + rl * (SEL_MAXR * SEL_BINS);
+  for (int t = tid; t < ns * SEL_BINS; t += 256) {
+    sh[t] = g[t];
+    g[t] = 0;
+  }
+  __syncthreads();
+  const int shift = 56 - 8 * pass;
+  if (tid < nr) {
+    const int64_t i = rl * SEL_MAXR + tid;
+    const u64 *hs = sh + s.slot[i] * SEL_BINS;
+    const u64 k = s.krem[i];
+    u64 below = 0;
+    int digit = SEL_BINS - 1;
+    for (int b = 0; b < SEL_BINS; ++b) {
+      const u64 cnt = hs[b];
+      if (k < below + cnt) { digit = b; break; }
+      below += cnt;
+    }
+    const u64 p = s.prefix[i] | ((u64)digit << shift);
+    s.prefix[i] = p;
+    s.krem[i] = k - below;
+    pre[tid] = p;
+  }
+  __syncthreads();
+  if (tid == 0) {   // sorted ranks: prefixes ascend, equal ones are neighbours
+    int n = 0;
+    for (int r = 0; r < nr; ++r) {
+      if (r == 0 || pre[r] != pre[r - 1]) s.slotpre[rl * SEL_MAXR + n++] = pre[r];
+      s.slot[rl * SEL_MAXR + r] = n - 1;
+    }
+    s.nslot[rl] = n;
+  }
+}
+
+__global__ __launch_bounds__(256) void sel_out_kernel(SelState s, int rows, int nr, const int *__restrict__ perm,
+                                                      int64_t row0, int64_t out_stride, double *__restrict__ out) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= rows * nr) return;
+  const int rl = i / nr, r = i % nr;
+  const double v = s.nan[rl] ? __longlong_as_double(0x7ff8000000000000ll) : sel_value(s.prefix[rl * SEL_MAXR + r]);
+  out[(row0 + rl) * out_stride + perm[r]] = v;
+}
+
+// out[r * out_stride + i] = order statistic ranks[i] of row r (elements dV[r row_stride + j elem_stride], j < S), all
+// on st; synchronises st before it returns (the scratch goes with the call).  The caller has validated the ranks.
+static int select_rows(const double *dV, int64_t R, int64_t S, int64_t row_stride, int64_t elem_stride, int64_t n_ranks,
+                       const int64_t *ranks, double *dout, int64_t out_stride, hipStream_t st) {
+  std::vector<int> order((size_t)n_ranks);
+  std::iota(order.begin(), order.end(), 0);
+  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return ranks[a] < ranks[b]; });
+  std::vector<u64> sorted((size_t)n_ranks);
+  for (int64_t i = 0; i < n_ranks; ++i) sorted[(size_t)i] = (u64)ranks[order[(size_t)i]];
+
+  const int rows_cap = (int)std::min<int64_t>(R, SEL_ROWS);
+  DevScope sc(st);
+  SelState s;
+  u64 *dranks = nullptr;
+  int *dperm = nullptr;
+  GP_TRY(sc.alloc(&s.prefix, (int64_t)rows_cap * SEL_MAXR));
+  GP_TRY(sc.alloc(&s.krem, (int64_t)rows_cap * SEL_MAXR));
+  GP_TRY(sc.alloc(&s.slotpre, (int64_t)rows_cap * SEL_MAXR));
+  GP_TRY(sc.alloc(&s.slot, (int64_t)rows_cap * SEL_MAXR));
+  GP_TRY(sc.alloc(&s.nslot, rows_cap));
+  GP_TRY(sc.alloc(&s.nan, rows_cap));
+  GP_TRY(sc.alloc(&s.hist, (int64_t)rows_cap * SEL_MAXR * SEL_BINS));
+  GP_TRY(sc.alloc(&dranks, n_ranks));
+  GP_TRY(sc.alloc(&dperm, n_ranks));
+  GP_TRY(upload(dranks, sorted.data(), n_ranks, st));
+  GP_TRY(upload(dperm, order.data(), n_ranks, st));
+  GP_HIP(hipMemsetAsync(s.hist, 0, sizeof(u64) * (size_t)rows_cap * SEL_MAXR * SEL_BINS, st));
+
+  for (int64_t row0 = 0; row0 < R; row0 += SEL_ROWS) {
+    const int rows = (int)std::min<int64_t>(SEL_ROWS, R - row0);
+    // slices: at least SEL_SLICE elements, about SEL_MAX_WG workgroups per launch; whole multiples of the workgroup
+    int64_t nblk = std::max<int64_t>(1, std::min((S + SEL_SLICE - 1) / SEL_SLICE, SEL_MAX_WG / rows));
+    const int64_t slice = round_up((S + nblk - 1) / nblk, 256);
+    nblk = (S + slice - 1) / slice;
+    for (int64_t g0 = 0; g0 < n_ranks; g0 += SEL_MAXR) {
+      const int nr = (int)std::min<int64_t>(SEL_MAXR, n_ranks - g0);
+      hipLaunchKernelGGL(sel_init_kernel, dim3((unsigned)((rows * SEL_MAXR + 255) / 256)), dim3(256), 0, st, s, rows, nr,
+                         dranks + g0);
+      GP_HIP(hipGetLastError());
+      for (int pass = 0; pass < SEL_PASSES; ++pass) {
+        postpred_path_count(GPEMU_POSTPRED_PATH_SELECT_PASS);
+        hipLaunchKernelGGL(sel_hist_kernel, dim3((unsigned)(rows * nblk)), dim3(256), 0, st, s, dV, row_stride,
+                           elem_stride, S, row0, (int)nblk, slice, pass);
+        GP_HIP(hipGetLastError());
+        hipLaunchKernelGGL(sel_scan_kernel, dim3((unsigned)rows), dim3(256), 0, st, s, nr, pass);
+        GP_HIP(hipGetLastError());
+      }
+      hipLaunchKernelGGL(sel_out_kernel, dim3((unsigned)((rows * nr + 255) / 256)), dim3(256), 0, st, s, rows, nr,
+                         dperm + g0, row0, out_stride, dout);
+      GP_HIP(hipGetLastError());
+    }
+  }
+  GP_HIP(hipStreamSynchronize(st));   // `sorted` and `order` are read by the copies above
+  return GPEMU_OK;
+}
+
+static int select_check(int64_t R, int64_t S, int64_t n_ranks, const int64_t *ranks) {
+  GP_ARG(R > 0, "R must be positive");
+  GP_ARG(S > 0, "S must be positive");
+  GP_ARG(n_ranks > 0 && ranks, "n_ranks must be positive");
+  for (int64_t i = 0; i < n_ranks; ++i) GP_ARG(ranks[i] >= 0 && ranks[i] < S, "every rank must be in [0, S)");
+  return GPEMU_OK;
+}
+
+static int device_ready(int device) {
+  int n = 0;
+  if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) {
+    set_error("no HIP device available: libgpemu has no CPU implementation");
+    return GPEMU_ERR_NO_DEVICE;
+  }
+  GP_ARG(device >= 0 && device < n, "device out of range");
+  GP_HIP(hipSetDevice(device));
+  return GPEMU_OK;
+}
+
+// ---- posterior predictive ------------------------------------------------------------------------------------------
+static __device__ __forceinline__ double pp_wave_sum(double s) {
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off, 64);
+  return s;
+}
+
+// logical rows [r0, r0 + n) of the block layout -> dst[n][d]
+__global__ __launch_bounds__(256) void pp_gather_kernel(const double *__restrict__ X, int64_t block_rows,
+                                                        int64_t block_stride_rows, int d, int64_t r0, int64_t n,
+                                                        double *__restrict__ dst) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n * d) return;
+  const int64_t r = r0 + i / d;
+  dst[i] = X[((r / block_rows) * block_stride_rows + r % block_rows) * d + i % d];
+}
+
+// workgroup (256 samples, PP_FT features): W[(f - f0) ldw + s] = central value of feature f for sample s
+__global__ __launch_bounds__(256) void pp_project_kernel(const double *__restrict__ M, int64_t S, int k,
+                                                         const double *__restrict__ comp,
+                                                         const double *__restrict__ smean,
+                                                         const double *__restrict__ sscale, int64_t F, int64_t f0,
+                                                         int64_t fb, double *__restrict__ W, int64_t ldw) {
+  const int64_t s = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int64_t ft0 = f0 + (int64_t)blockIdx.y * PP_FT;
+  const int nf = (int)((f0 + fb - ft0 < PP_FT) ? f0 + fb - ft0 : PP_FT);
+  if (s >= S) return;
+  double a[PP_FT];
+#pragma unroll
+  for (int j = 0; j < PP_FT; ++j) a[j] = 0.0;
+  const double *mrow = M + s * k;
+  for (int p = 0; p < k; ++p) {
+    const double mp = mrow[p];
+    const double *c = comp + (int64_t)p * F + ft0;   // the same for the whole workgroup
+#pragma unroll
+    for (int j = 0; j < PP_FT; ++j)
+      if (j < nf) a[j] = fma(mp, c[j], a[j]);
+  }
+#pragma unroll
+  for (int j = 0; j < PP_FT; ++j)
+    if (j < nf) W[(ft0 - f0 + j) * ldw + s] = a[j] * sscale[ft0 + j] + smean[ft0 + j];
+}
+
+// part[row nchunk + c] = sum over samples [c PP_SUM, (c + 1) PP_SUM) of x (centre null) or (x - centre[row])^2,
+// x = X[row rs + i es]: every lane adds its 16 elements in index order, then a fixed butterfly and the waves in order
+__global__ __launch_bounds__(256) void pp_rowsum_kernel(const double *__restrict__ X, int64_t rs, int64_t es, int64_t S,
+                                                        const double *__restrict__ centre, double *__restrict__ part,
+                                                        int64_t nchunk) {
+  __shared__ double ws[4];
+  const int tid = threadIdx.x;
+  const int64_t c = blockIdx.x, row = blockIdx.y;
+  const double *x = X + row * rs;
+  const double mu = centre ? centre[row] : 0.0;
+  double acc = 0.0;
+  for (int j = 0; j < PP_SUM / 256; ++j) {
+    const int64_t i = c * PP_SUM + (int64_t)j * 256 + tid;
+    if (i < S) {
+      const double v = x[i * es];
+      acc += centre ? (v - mu) * (v - mu) : v;
+    }
+  }
+  acc = pp_wave_sum(acc);
+  if ((tid & 63) == 0) ws[tid >> 6] = acc;
+  __syncthreads();
+  if (tid == 0) part[row * nchunk + c] = ((ws[0] + ws[1]) + ws[2]) + ws[3];
+}
+
+// out[row] = (sum of the row's partial sums, in chunk order) * scale
+__global__ __launch_bounds__(256) void pp_finish_kernel(const double *__restrict__ part, int64_t R, int64_t nchunk,
+                                                        double scale, double *__restrict__ out) {
+  const int64_t row = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (row >= R) return;
+  double acc = 0.0;
+  for (int64_t c = 0; c < nchunk; ++c) acc += part[row * nchunk + c];
+  out[row] = acc * scale;
+}
+
+// var_emu[f] = (sum_p comp[p][f] vbar_p comp[p][f] + cov_unexplained[f][f]) scale_f^2  (cv_backproject's variance sum)
+__global__ __launch_bounds__(256) void pp_varemu_kernel(const double *__restrict__ vbar, const double *__restrict__ comp,
+                                                        const double *__restrict__ sscale,
+                                                        const double *__restrict__ cunexpl, int k, int64_t F,
+                                                        double *__restrict__ out) {
+  const int64_t f = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (f >= F) return;
+  double b = 0.0;
+  for (int p = 0; p < k; ++p) {
+    const double c = comp[(int64_t)p * F + f];
+    b = fma(c * vbar[p], c, b);
+  }
+  const double sc = sscale[f];
+  out[f] = (b + cunexpl[f * F + f]) * (sc * sc);
+}
+
+static int launch_rowmean(const double *X, int64_t rs, int64_t es, int64_t R, int64_t S, const double *centre,
+                          double *part, double *out, hipStream_t st) {
+  const int64_t nchunk = (S + PP_SUM - 1) / PP_SUM;
+  for (int64_t r0 = 0; r0 < R; r0 += 32768) {   // grid.y
+    const int64_t nr = std::min<int64_t>(32768, R - r0);
+    hipLaunchKernelGGL(pp_rowsum_kernel, dim3((unsigned)nchunk, (unsigned)nr), dim3(256), 0, st, X + r0 * rs, rs, es, S,
+                       centre ? centre + r0 : nullptr, part + r0 * nchunk, nchunk);
+    GP_HIP(hipGetLastError());
+  }
+  hipLaunchKernelGGL(pp_finish_kernel, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, st, part, R, nchunk,
+                     1.0 / (double)S, out);
+  GP_HIP(hipGetLastError());
+  return GPEMU_OK;
+}
+
+}  // namespace gpemu
+
+using namespace gpemu;
+
+extern "C" {
+
+int gpemu_postpred_path_counts(int64_t *out, int64_t n) { return read_path_counts(PATHS_POSTPRED, out, n); }
+
+int gpemu_select_dev(int device, int64_t R, int64_t S, const double *dV, int64_t row_stride, int64_t elem_stride,
+                     int64_t n_ranks, const int64_t *ranks, double *dout, void *stream) {
+  GP_ARG(dV && dout, "null pointer");
+  GP_TRY(select_check(R, S, n_ranks, ranks));
+  GP_ARG(row_stride > 0 && elem_stride > 0, "strides must be positive");
+  GP_TRY(device_ready(device));
+  return select_rows(dV, R, S, row_stride, elem_stride, n_ranks, ranks, dout, n_ranks, (hipStream_t)stream);
+}
+
+int gpemu_select(int device, int64_t R, int64_t S, const double *V, int64_t n_ranks, const int64_t *ranks, double *out) {
+  GP_ARG(V && out, "null pointer");
+  GP_TRY(select_check(R, S, n_ranks, ranks));
+  GP_TRY(device_ready(device));
+  hipStream_t st = nullptr;
+  DevScope sc(st);
+  double *dV = nullptr, *dout = nullptr;
+  GP_TRY(sc.alloc(&dV, R * S));
+  GP_TRY(sc.alloc(&dout, R * n_ranks));
+  GP_TRY(upload(dV, V, R * S, st));
+  GP_TRY(select_rows(dV, R, S, S, 1, n_ranks, ranks, dout, n_ranks, st));
+  GP_TRY(sc.download(out, dout, R * n_ranks));
+  GP_HIP(hipStreamSynchronize(st));
+  return GPEMU_OK;
+}
+
+int gpemu_posterior_predictive_dev(gpemu_model *m, const double *dX, int64_t n_blocks, int64_t block_rows,
+                                   int64_t block_stride_rows, int64_t n_ranks, const int64_t *ranks,
+                                   int64_t workspace_bytes, double *dmean, double *dvar_param, double *dvar_emu,
+                                   double *dorder, void *stream) {
+  GP_ARG(m && dX, "null pointer");
+  GP_ARG(n_blocks > 0 && block_rows > 0, "n_blocks and block_rows must be positive");
+  GP_ARG(n_blocks == 1 || block_stride_rows >= block_rows, "block_stride_rows must be >= block_rows");
+  GP_ARG(n_blocks <= INT64_MAX / block_rows, "n_blocks * block_rows overflows");
+  GP_ARG(workspace_bytes >= 0, "workspace_bytes must be >= 0");
+  GP_ARG(n_ranks >= 0, "n_ranks must be >= 0");
+  const int64_t S = n_blocks * block_rows, F = m->F, k = m->k, d = m->d;
+  if (n_ranks > 0) {
+    GP_ARG(dorder, "order_stats is null with n_ranks > 0");
+    GP_TRY(select_check(F, S, n_ranks, ranks));
+  }
+  GP_HIP(hipSetDevice(m->device));
+  hipStream_t st = stream ? (hipStream_t)stream : m->stream;
+
+  // the plan: the PC arrays stay resident, the features go through the workspace in blocks
+  int64_t budget = workspace_bytes;
+  if (budget == 0) {
+    size_t fb = 0, tb = 0;
+    GP_HIP(hipMemGetInfo(&fb, &tb));
+    budget = (int64_t)(fb / 2);
+  }
+  const int64_t pc_bytes = 2 * S * k * 8;
+  const bool want_ws = dmean || dvar_param || n_ranks > 0;
+  int64_t Fb = F;
+  if (want_ws) {
+    const int64_t room = budget - pc_bytes - PP_FIXED;
+    Fb = room > 0 ? std::min<int64_t>(F, room / (8 * S)) : 0;
+    if (Fb < F) Fb = Fb / 16 * 16;
+    if (Fb < std::min<int64_t>(F, 16)) {
+      set_error("posterior_predictive: out of memory: %lld rows need %lld bytes of PC arrays, %lld bytes of scratch and "
+                "%lld bytes for one block of 16 features; %lld bytes %s", (long long)S, (long long)pc_bytes,
+                (long long)PP_FIXED, (long long)(std::min<int64_t>(F, 16) * 8 * S), (long long)budget,
+                workspace_bytes ? "allowed by workspace_bytes" : "available (half of the free device memory)");
+      return GPEMU_ERR_HIP;
+    }
+  }
+  const int64_t nchunk = (S + PP_SUM - 1) / PP_SUM;
+
+  DevScope sc(st);
+  double *Mpc = nullptr, *Vpc = nullptr, *stage = nullptr, *W = nullptr, *part = nullptr, *vbar = nullptr, *mu = nullptr;
+  GP_TRY(sc.alloc(&Mpc, S * k));
+  GP_TRY(sc.alloc(&Vpc, S * k));
+  const bool contiguous = n_blocks == 1 || block_stride_rows == block_rows;
+  if (!contiguous) GP_TRY(sc.alloc(&stage, PP_CHUNK * d));
+  GP_TRY(sc.alloc(&part, std::max(Fb, k) * nchunk));
+  GP_TRY(sc.alloc(&vbar, k));
+  GP_TRY(sc.alloc(&mu, F));
+  if (want_ws) GP_TRY(sc.alloc(&W, Fb * S));
+
+  for (int64_t r0 = 0; r0 < S; r0 += PP_CHUNK) {
+    const int64_t nb = std::min(PP_CHUNK, S - r0);
+    const double *src = nullptr;
+    if (contiguous) {
+      src = dX + r0 * d;
+    } else if (r0 / block_rows == (r0 + nb - 1) / block_rows) {   // the chunk lies within one block
+      src = dX + ((r0 / block_rows) * block_stride_rows + r0 % block_rows) * d;
+    } else {
+      hipLaunchKernelGGL(pp_gather_kernel, dim3((unsigned)((nb * d + 255) / 256)), dim3(256), 0, st, dX, block_rows,
+                         block_stride_rows, (int)d, r0, nb, stage);
+      GP_HIP(hipGetLastError());
+      src = stage;
+    }
+    GP_TRY(gpemu_gp_predict_dev(m, nb, src, Mpc + r0 * k, Vpc + r0 * k, st));
+  }
+
+  if (dvar_emu) {
+    GP_TRY(launch_rowmean(Vpc, 1, k, k, S, nullptr, part, vbar, st));
+    hipLaunchKernelGGL(pp_varemu_kernel, dim3((unsigned)((F + 255) / 256)), dim3(256), 0, st, vbar, m->comp, m->sscale,
+                       m->cunexpl, (int)k, F, dvar_emu);
+    GP_HIP(hipGetLastError());
+  }
+  if (want_ws) {
+    postpred_path_count(Fb >= F ? GPEMU_POSTPRED_PATH_WHOLE : GPEMU_POSTPRED_PATH_FEATURE_BLOCKED);
+    for (int64_t f0 = 0; f0 < F; f0 += Fb) {
+      const int64_t fb = std::min(Fb, F - f0);
+      postpred_path_count(GPEMU_POSTPRED_PATH_FEATURE_BLOCK);
+      hipLaunchKernelGGL(pp_project_kernel, dim3((unsigned)((S + 255) / 256), (unsigned)((fb + PP_FT - 1) / PP_FT)),
+                         dim3(256), 0, st, Mpc, S, (int)k, m->comp, m->smean, m->sscale, F, f0, fb, W, S);
+      GP_HIP(hipGetLastError());
+      if (dmean || dvar_param) GP_TRY(launch_rowmean(W, S, 1, fb, S, nullptr, part, mu + f0, st));
+      if (dvar_param) GP_TRY(launch_rowmean(W, S, 1, fb, S, mu + f0, part, dvar_param + f0, st));
+      if (n_ranks > 0) GP_TRY(select_rows(W, fb, S, S, 1, n_ranks, ranks, dorder + f0 * n_ranks, n_ranks, st));
+    }
+    if (dmean) GP_HIP(hipMemcpyAsync(dmean, mu, sizeof(double) * (size_t)F, hipMemcpyDeviceToDevice, st));
+  }
+  GP_HIP(hipStreamSynchronize(st));
+  return GPEMU_OK;
+}
+
+int gpemu_posterior_predictive(gpemu_model *m, int64_t S, const double *X, int64_t n_ranks, const int64_t *ranks,
+                               int64_t workspace_bytes, double *mean, double *var_param, double *var_emu,
+                               double *order_stats) {
+  GP_ARG(m && X, "null pointer");
+  GP_ARG(S > 0, "S must be positive");
+  GP_ARG(n_ranks >= 0, "n_ranks must be >= 0");
+  GP_ARG(n_ranks == 0 || order_stats, "order_stats is null with n_ranks > 0");
+  for (int64_t i = 0; i < S * m->d; ++i) GP_ARG(std::isfinite(X[i]), "X contains NaN or infinity");
+  GP_HIP(hipSetDevice(m->device));
+  hipStream_t st = m->stream;
+  const int64_t F = m->F;
+  DevScope sc(st);
+  double *dX = nullptr, *dm = nullptr, *dvp = nullptr, *dve = nullptr, *dq = nullptr;
+  GP_TRY(sc.alloc(&dX, S * m->d));
+  if (mean) GP_TRY(sc.alloc(&dm, F));
+  if (var_param) GP_TRY(sc.alloc(&dvp, F));
+  if (var_emu) GP_TRY(sc.alloc(&dve, F));
+  if (n_ranks > 0) GP_TRY(sc.alloc(&dq, F * n_ranks));
+  GP_TRY(upload(dX, X, S * m->d, st));
+  GP_TRY(gpemu_posterior_predictive_dev(m, dX, 1, S, S, n_ranks, ranks, workspace_bytes, dm, dvp, dve, dq, st));
+  if (mean) GP_TRY(sc.download(mean, dm, F));
+  if (var_param) GP_TRY(sc.download(var_param, dvp, F));
+  if (var_emu) GP_TRY(sc.download(var_emu, dve, F));
+  if (n_ranks > 0) GP_TRY(sc.download(order_stats, dq, F * n_ranks));
+  GP_HIP(hipStreamSynchronize(st));
+  return GPEMU_OK;
+}
+
+int gpemu_sampler_chain_ptr(gpemu_sampler *s, int64_t first, const double **dchain, int64_t *n_steps) {
+  GP_ARG(s && dchain && n_steps, "null pointer");
+  GP_ARG(first >= 0 && first <= s->chain_len, "first must be in [0, chain_len]");
+  GP_HIP(hipSetDevice(s->device));
+  GP_HIP(hipStreamSynchronize(s->stream));   // the steps stored so far are in the buffer
+  *dchain = s->chain + first * s->W * s->d;
+  *n_steps = s->chain_len - first;
+  return GPEMU_OK;
+}
+
+}  // extern "C"

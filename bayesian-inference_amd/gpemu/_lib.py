@@ -129,6 +129,14 @@ _SIGNATURES = {
     "gpemu_wide_path_counts": (C.c_int, [C.POINTER(c_i64), c_i64]),
     "gpemu_src_path_counts": (C.c_int, [C.POINTER(c_i64), c_i64]),
     "gpemu_philox4x32": (C.c_int, [C.c_uint32] * 6 + [C.POINTER(C.c_uint32)]),
+    "gpemu_select": (C.c_int, [C.c_int, c_i64, c_i64, C.c_void_p, c_i64, C.c_void_p, C.c_void_p]),
+    "gpemu_select_dev": (C.c_int, [C.c_int, c_i64, c_i64, C.c_void_p, c_i64, c_i64, c_i64, C.c_void_p, C.c_void_p,
+                                   C.c_void_p]),
+    "gpemu_posterior_predictive": (C.c_int, [C.c_void_p, c_i64, C.c_void_p, c_i64, C.c_void_p, c_i64] + [C.c_void_p] * 4),
+    "gpemu_posterior_predictive_dev": (C.c_int, [C.c_void_p, C.c_void_p, c_i64, c_i64, c_i64, c_i64, C.c_void_p, c_i64]
+                                       + [C.c_void_p] * 5),
+    "gpemu_sampler_chain_ptr": (C.c_int, [C.c_void_p, c_i64, C.POINTER(C.c_void_p), C.POINTER(c_i64)]),
+    "gpemu_postpred_path_counts": (C.c_int, [C.POINTER(c_i64), c_i64]),
 }
 
 

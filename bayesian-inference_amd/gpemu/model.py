@@ -197,6 +197,36 @@ class DeviceModel:
                                                     ptr(mean), ptr(var), ptr(cv), ptr(vo)))
         return mean, var, cv, vo
 
+    # -- posterior-predictive summaries ---------------------------------------------------
+    def posterior_predictive(self, X, probabilities=(0.05, 0.5, 0.95), workspace_bytes=0):
+        """Per-feature summaries of the group's prediction over the rows of ``X`` (S, d) -- typically the flattened
+        chain: a dict with ``mean`` (F,), ``variance_parameters`` (F,) (population variance of the central value over
+        the rows), ``variance_emulator`` (F,) (mean over the rows of the emulator variance of one sample, the diagonal
+        of the reference's ``cov``, ref: emulation.py:466-548), ``variance`` (their sum: the law of total variance),
+        ``quantiles`` (nq, F) of the central value (``np.quantile(..., method='linear')`` of exact device order
+        statistics) and ``probabilities``.  ``probabilities=None`` or empty skips the quantiles.  Rows are not checked
+        against a prior box; non-finite rows are refused as in ``gp_predict``.  ``workspace_bytes`` caps the device
+        workspace (0: sized from free memory); the result, bit for bit, does not depend on it."""
+        X = self._finite(self._X(X))
+        plan = QuantilePlan(X.shape[0], probabilities)
+        mean, vp, ve = np.empty(self.F), np.empty(self.F), np.empty(self.F)
+        order = np.empty((self.F, max(plan.ranks.size, 1)))
+        check(_lib.lib().gpemu_posterior_predictive(self._h, X.shape[0], ptr(X), int(plan.ranks.size), ptr(plan.ranks),
+                                                    int(workspace_bytes), ptr(mean), ptr(vp), ptr(ve), ptr(order)))
+        return plan.result(mean, vp, ve, order)
+
+    def posterior_predictive_dev(self, dX_ptr, n_blocks, block_rows, block_stride_rows, ranks, dmean_ptr, dvar_param_ptr,
+                                 dvar_emu_ptr, dorder_ptr, workspace_bytes=0, stream=0):
+        """The device-pointer entry: row r of the S = n_blocks * block_rows rows is read at ``dX + ((r // block_rows) *
+        block_stride_rows + r % block_rows) * d``; ``ranks`` is a host int64 array (may be empty), the outputs device
+        pointers (0: not wanted).  Waits for the stream before it returns."""
+        ranks = np.ascontiguousarray(ranks, dtype=np.int64).reshape(-1)
+        vp = lambda a: C.c_void_p(a) if a else None
+        check(_lib.lib().gpemu_posterior_predictive_dev(
+            self._h, C.c_void_p(dX_ptr), int(n_blocks), int(block_rows), int(block_stride_rows), int(ranks.size),
+            ptr(ranks) if ranks.size else None, int(workspace_bytes), vp(dmean_ptr), vp(dvar_param_ptr), vp(dvar_emu_ptr),
+            vp(dorder_ptr), C.c_void_p(stream)))
+
     def likelihood_setup(self, y_exp, y_err, lo, hi, n_div=1.0, block_start=None, cov=None, sys_sources=None):
         """Data, box prior and the observable block boundaries of this group (``block_start`` =
         first feature of each observable plus F at the end; None = a single block).  ``y_exp`` of shape (C, F):
@@ -341,6 +371,51 @@ def logpost_groups_grad(models, X, mode=LOWRANK):
     hs = (C.c_void_p * len(models))(*[m.handle for m in models])
     check(_lib.lib().gpemu_logpost_groups_grad(hs, len(models), B, ptr(X), ptr(lp), ptr(grad), int(mode)))
     return lp, grad
+
+
+class QuantilePlan:
+    """The order statistics a set of probabilities needs from S samples, and the assembly of a posterior-predictive
+    result from the library's outputs (``gpemu.select``: numpy's ``linear`` virtual index and ``_lerp``)."""
+
+    def __init__(self, S, probabilities):
+        from . import select
+        self.probabilities = (np.zeros(0) if probabilities is None
+                              else np.asarray(probabilities, dtype=np.float64).reshape(-1).copy())
+        if self.probabilities.size:
+            self.ranks, self.ilo, self.ihi, self.t = select._bracket(int(S), self.probabilities)
+        else:
+            self.ranks = np.zeros(0, dtype=np.int64)
+
+    def quantiles(self, order):
+        """``order`` (F, n_ranks) -> (nq, F)."""
+        from . import select
+        if not self.probabilities.size:
+            return np.zeros((0, order.shape[0]))
+        return select.lerp(order[:, self.ilo].T, order[:, self.ihi].T, self.t[:, None])
+
+    def result(self, mean, var_param, var_emu, order):
+        return {"mean": mean, "variance_parameters": var_param, "variance_emulator": var_emu,
+                "variance": var_param + var_emu, "quantiles": self.quantiles(order),
+                "probabilities": self.probabilities}
+
+
+POSTPRED_FIXED_BYTES = 32 << 20    # GPEMU_POSTPRED_FIXED_BYTES
+
+
+def postpred_workspace_bytes(S, k, n_features):
+    """``workspace_bytes`` with which ``posterior_predictive`` of S rows holds ``n_features`` features at a time (a
+    multiple of 16 below F): the resident PC arrays, the fixed scratch, 8 S bytes per feature (include/gpemu.h)."""
+    return 16 * int(S) * int(k) + POSTPRED_FIXED_BYTES + 8 * int(S) * int(n_features)
+
+
+POSTPRED_PATHS = ("whole", "feature_blocked", "feature_block", "select_pass")    # enum gpemu_postpred_path
+
+
+def postpred_path_counts():
+    """Counters of enum gpemu_postpred_path (selection and posterior-predictive reduction), as an int64 array."""
+    out = np.zeros(8, dtype=np.int64)
+    n = _lib.lib().gpemu_postpred_path_counts(out.ctypes.data_as(C.POINTER(C.c_int64)), out.size)
+    return out[:n].copy()
 
 
 def grad_path_counts():

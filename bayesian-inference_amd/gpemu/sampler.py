@@ -210,6 +210,84 @@ class DeviceSampler:
         check(_lib.lib().gpemu_sampler_get_chain(self._h, int(first), int(n), ptr(chain), ptr(lp)))
         return chain, lp
 
+    # -- summaries of the stored chain, read where it lies ------------------------------------
+    def _chain_walkers(self, chain):
+        """(first walker, walkers) of the chain the summaries are taken over."""
+        if self.n_chains == 1:
+            if chain not in (None, 0):
+                raise IndexError(f"chain index {chain} outside [0, 1)")
+            return 0, self.W
+        if chain is None:
+            raise ValueError(f"this sampler stacks {self.n_chains} chains: pass chain=<index>")
+        c = int(chain)
+        if not 0 <= c < self.n_chains:
+            raise IndexError(f"chain index {chain} outside [0, {self.n_chains})")
+        return c * self.walkers_per_chain, self.walkers_per_chain
+
+    def chain_ptr(self, first=0):
+        """``(device address of step first of the chain [steps][W][d], steps from there on)``; valid until the next
+        run, reserve, reset or restore."""
+        p, n = C.c_void_p(), C.c_int64()
+        check(_lib.lib().gpemu_sampler_chain_ptr(self._h, int(first), C.byref(p), C.byref(n)))
+        return int(p.value or 0), int(n.value)
+
+    def posterior_predictive(self, models=None, discard=0, thin=1, probabilities=(0.05, 0.5, 0.95), chain=None,
+                             workspace_bytes=0):
+        """``DeviceModel.posterior_predictive`` of the stored chain ``get_chain()[discard::thin]`` (all walkers of the
+        chain, flattened step by step), read in place on the device: a list with one result dict per model of
+        ``models`` (default: the sampler's groups).  Stacked samplers take ``chain=<index>``.  A sharded run stores
+        the whole chain on every rank (every rank accepts identically), so each rank may call this on its own."""
+        import torch
+        from .model import QuantilePlan
+        models = self.models if models is None else list(models)
+        if int(thin) < 1 or int(discard) < 0:
+            raise ValueError("discard must be >= 0 and thin >= 1")
+        w0, nw = self._chain_walkers(chain)
+        base, n = self.chain_ptr(int(discard))
+        if n < 1:
+            raise ValueError("no stored steps after discard")
+        n_blocks = (n + int(thin) - 1) // int(thin)
+        plan = QuantilePlan(n_blocks * nw, probabilities)
+        dev = torch.device("cuda", self.device)
+        out = []
+        for m in models:
+            if m.d != self.d or m.device != self.device:
+                raise ValueError("model and sampler differ in parameters or device")
+            bufs = torch.empty((3 + max(plan.ranks.size, 1), m.F), dtype=torch.float64, device=dev)
+            order = bufs[3:].reshape(-1)          # [F][n_ranks] as the library writes it
+            m.posterior_predictive_dev(base + 8 * w0 * self.d, n_blocks, nw, int(thin) * self.W, plan.ranks,
+                                       bufs[0].data_ptr(), bufs[1].data_ptr(), bufs[2].data_ptr(),
+                                       order.data_ptr() if plan.ranks.size else 0, workspace_bytes=workspace_bytes)
+            h = bufs.cpu().numpy()
+            out.append(plan.result(h[0].copy(), h[1].copy(), h[2].copy(),
+                                   h[3:].reshape(-1)[:m.F * max(plan.ranks.size, 1)].reshape(m.F, -1).copy()))
+        return out
+
+    def parameter_quantiles(self, probabilities, discard=0, chain=None):
+        """``np.quantile(get_chain()[discard:].reshape(-1, d), probabilities, axis=0)``: (nq, d), from exact order
+        statistics selected on the device.  The whole ensemble is read in place (parameter j = the elements of stride
+        d of the device chain); one chain of a stacked sampler is not a single stride, so its walkers are copied out
+        first and selected from that copy."""
+        from . import select
+        w0, nw = self._chain_walkers(chain)
+        base, n = self.chain_ptr(int(discard))
+        if n < 1:
+            raise ValueError("no stored steps after discard")
+        if nw != self.W:
+            x = np.empty((n, nw, self.d))
+            lp = np.empty((n, nw))
+            check(_lib.lib().gpemu_sampler_get_chain_walkers(self._h, int(discard), n, w0, nw, ptr(x), ptr(lp)))
+            return select.quantile(x.reshape(-1, self.d), probabilities, axis=0, device=self.device)
+        import torch
+        S = n * self.W
+        ranks, ilo, ihi, t = select._bracket(S, probabilities)
+        dout = torch.empty((self.d, ranks.size), dtype=torch.float64, device=torch.device("cuda", self.device))
+        check(_lib.lib().gpemu_select_dev(self.device, self.d, S, C.c_void_p(base), 1, self.d, int(ranks.size), ptr(ranks),
+                                          C.c_void_p(dout.data_ptr()), None))
+        sel = dout.cpu().numpy()
+        q = select.lerp(sel[:, ilo].T, sel[:, ihi].T, t[:, None])
+        return q[0] if np.ndim(probabilities) == 0 else q
+
     def acf_block(self, lag0, n_lags, first=0, n=None, w0=0, nw=None):
         """Walker-averaged normalised autocorrelation function, lags [lag0, lag0 + n_lags), of the chain stored on
         the device: (n_lags, d).  ``lag0`` a multiple of 16, the first block of an estimate at 0."""
@@ -626,6 +704,13 @@ class TemperedSampler(DeviceSampler):
         chain, lp = np.empty((n, Wc, self.d)), np.empty((n, Wc))
         check(_lib.lib().gpemu_sampler_get_chain_walkers(self._h, int(discard), int(n), t * Wc, Wc, ptr(chain), ptr(lp)))
         return chain, lp
+
+    def _chain_walkers(self, chain):
+        """The summaries of a tempered sampler are those of rung 0, the posterior (``chain`` = another rung)."""
+        t = 0 if chain is None else int(chain)
+        if not 0 <= t < self.n_temps:
+            raise IndexError(f"temperature index {chain} outside [0, {self.n_temps})")
+        return t * self.walkers_per_chain, self.walkers_per_chain
 
     def run_sharded(self, steps, store=True, group=None, force=False, emulate_world=None, transport=None):
         """Tempered runs are single-GPU (``run``); the library declines its sharded and peer runs, and the per-phase

@@ -491,6 +491,63 @@ enum gpemu_src_path {
 /* out[0 .. min(n, GPEMU_SRC_PATH_COUNT)) = the counters; returns GPEMU_SRC_PATH_COUNT (or GPEMU_ERR_ARG). */
 int gpemu_src_path_counts(int64_t *out, int64_t n);
 
+/* ---- exact order statistics and posterior-predictive summaries ------------------------------------
+ * Replaces ref: mcmc.py credible_interval (np.quantile over the chain; call sites ref: plot_qhat.py:102-109) and the
+ * per-bin bands of ref: plot_mcmc.py:343-371 (_plot_posterior_observables: predict on draws of the chain, then
+ * quantiles per feature), for the WHOLE chain instead of a few hundred draws of it.
+ *
+ * Selection: out[r*n_ranks + i] = the ranks[i]-th smallest element (0-based) of row r of V[R*S] -- an element of the
+ * input, equal as a double to np.sort(V[r])[ranks[i]].  +0 and -0 compare equal, so the sign of a returned zero is not
+ * specified; a row that holds a NaN returns NaN for every rank (np.quantile); +-inf order as usual.  Radix select on the
+ * order-preserving 64-bit key of a double, eight 8-bit passes shared by all ranks of a row, whatever the data (a row of
+ * equal values takes the same passes).  Selection is exact and its counters are integers: the result bits do not depend
+ * on the grid, on the scratch or on the run.  R, S, n_ranks >= 1 and every rank in [0, S), else GPEMU_ERR_ARG.
+ * The _dev form reads element j of row r at dV[r*row_stride + j*elem_stride] (strides in doubles, > 0: a parameter of
+ * the device chain [steps][W][d] is the "row" j with row_stride 1, elem_stride d); ranks[] is a HOST array, dout
+ * [R*n_ranks] a device array; stream NULL = the null stream.  It waits for the stream before it returns (its scratch
+ * goes with the call). */
+int gpemu_select(int device, int64_t R, int64_t S, const double *V, int64_t n_ranks, const int64_t *ranks, double *out);
+int gpemu_select_dev(int device, int64_t R, int64_t S, const double *dV, int64_t row_stride, int64_t elem_stride,
+                     int64_t n_ranks, const int64_t *ranks, double *dout, void *stream);
+
+/* Summaries over the S rows of X[S*d] of the group's prediction for one sample (ref: emulation.py:466-548, n_div = 1):
+ * with mu_f(theta) = central_value and sigma2_f(theta) = the diagonal of cov (gpemu_model_cross_validate's `variance`),
+ *   mean[F]                 mean over the rows of mu_f
+ *   var_param[F]            population variance (ddof 0) of mu_f, two passes
+ *   var_emu[F]              mean over the rows of sigma2_f  (var_param + var_emu = the predictive variance)
+ *   order_stats[F*n_ranks]  order statistic ranks[i] of mu_f, as gpemu_select
+ * Each output may be NULL; n_ranks = 0 skips the selection.  Rows are not checked against a prior box; the host form
+ * refuses non-finite rows (GPEMU_ERR_ARG).  The F x F covariances and the S x F variances are never formed.
+ * workspace_bytes = 0: half of the free device memory.  Resident: the PC means and variances, 16*S*k bytes, and
+ * GPEMU_POSTPRED_FIXED_BYTES of scratch; what is left holds the feature-major central values, 8*S bytes per feature, for
+ * all features or for blocks of a multiple of 16 of them.  If not even 16 features fit: GPEMU_ERR_HIP, sizes in
+ * the error text.  Every sum over rows runs over chunks fixed by the row index: the results, bit for bit, do not depend
+ * on workspace_bytes, on the feature blocks or on the run.
+ * _dev: row r is read at dX + ((r / block_rows)*block_stride_rows + r % block_rows)*d, S = n_blocks*block_rows -- the
+ * sampler's chain in place: thinned by steps, one rung of a tempered chain, one chain of a stacked sampler.  Outputs
+ * are device arrays, ranks[] a HOST array; works on `stream` (NULL = the model's) and waits for it before returning. */
+#define GPEMU_POSTPRED_FIXED_BYTES (32ll << 20)
+int gpemu_posterior_predictive(gpemu_model *m, int64_t S, const double *X, int64_t n_ranks, const int64_t *ranks,
+                               int64_t workspace_bytes, double *mean, double *var_param, double *var_emu,
+                               double *order_stats);
+int gpemu_posterior_predictive_dev(gpemu_model *m, const double *dX, int64_t n_blocks, int64_t block_rows,
+                                   int64_t block_stride_rows, int64_t n_ranks, const int64_t *ranks,
+                                   int64_t workspace_bytes, double *dmean, double *dvar_param, double *dvar_emu,
+                                   double *dorder_stats, void *stream);
+/* Device address of step `first` of the stored chain [steps][W][d] and the number of steps from there on; valid until
+ * the next run, reserve, reset or restore of the sampler.  Waits for the sampler's stream. */
+int gpemu_sampler_chain_ptr(gpemu_sampler *s, int64_t first, const double **dchain, int64_t *n_steps);
+/* Which forms of the two ran.  A set of its own: the other sets keep their sizes and indices. */
+enum gpemu_postpred_path {
+  GPEMU_POSTPRED_PATH_WHOLE = 0,        /* a reduction whose features all fit the workspace at once                 */
+  GPEMU_POSTPRED_PATH_FEATURE_BLOCKED,  /* ... that went through the workspace in blocks of features                */
+  GPEMU_POSTPRED_PATH_FEATURE_BLOCK,    /* one block of features: projection, moments, selection                    */
+  GPEMU_POSTPRED_PATH_SELECT_PASS,      /* one histogram + scan pass of the radix select                            */
+  GPEMU_POSTPRED_PATH_COUNT
+};
+/* out[0 .. min(n, GPEMU_POSTPRED_PATH_COUNT)) = the counters; returns GPEMU_POSTPRED_PATH_COUNT (or GPEMU_ERR_ARG). */
+int gpemu_postpred_path_counts(int64_t *out, int64_t n);
+
 /* ---- fit handle: test-only entry points ---------------------------------------------------------------------------
  * For the tests of the fit side only; nothing in the library's own flow calls them.
  * gpemu_fit_workspace: out[N*N] = problem z of the last evaluation (gpemu_fit_lml / _lml_batch / _factor) as the
