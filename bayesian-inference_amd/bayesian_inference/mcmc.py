@@ -231,6 +231,11 @@ def run_mcmc(config, closure_index=-1):
         logger.info(f'closure test {closure_index}: runs on rank {owner}')
         return
     alone = owner is not None          # this rank runs the whole chain by itself
+    if getattr(config, 'sampler', 'stretch') == 'hmc':
+        reason = hmc_unsupported(config, closure_index, world)
+        if reason:
+            raise ValueError(f"parameters.mcmc.sampler: hmc: {reason} -- no step has been taken")
+        return _run_hmc(config, closure_index)
     if getattr(config, 'n_temperatures', 1) > 1:
         # parallel tempering runs on one GPU: rank 0 (or the closure chain's owner) runs it, the other ranks return;
         # a tempered closure chain runs by itself (not stacked with the other closure points)
@@ -466,6 +471,118 @@ def _run_tempered(config, closure_index):
 
 
 ####################################################################################################
+# Hamiltonian Monte Carlo: optional parameters.mcmc.sampler: hmc (absent or "stretch": the paths
+# above), with hmc_n_leapfrog, hmc_target_accept, hmc_step_size.  n_walkers independent chains; n_burn_steps of warm-up
+# (step size and diagonal metric adapt), n_sampling_steps of production.  mcmc.h5 keeps the keys and shapes of a
+# stretch-move run and adds hmc_step_size, hmc_inverse_metric, hmc_divergences.
+def hmc_unsupported(config, closure_index, world):
+    """Why ``sampler: hmc`` cannot run this configuration, or None.  Decided before anything is loaded."""
+    if getattr(config, 'n_temperatures', 1) > 1:
+        return "it cannot be combined with parallel tempering (n_temperatures > 1)"
+    if world > 1:
+        return f"it runs on one GPU, this job has {world} ranks"
+    if closure_index >= 0 and _closure_batch_enabled() and 'validation_indices' in config.analysis_config:
+        return ("closure chains are stacked in one stretch-move sampler; run them one by one with GPEMU_CLOSURE_BATCH=0 "
+                "or use the stretch sampler")
+    return None
+
+
+def _run_hmc(config, closure_index):
+    from gpemu.sampler import HMCSampler
+    box = config.analysis_config['parameterization'][config.parameterization]
+    lower, upper = box['min'], box['max']
+    n_par, n_walk = len(box['names']), config.n_walkers
+    emu_cfg = emulation.EmulationConfig.from_config_file(
+        analysis_name=config.analysis_name, parameterization=config.parameterization,
+        analysis_config=config.analysis_config, config_file=config.config_file)
+    emu_results = emu_cfg.read_all_emulator_groups()
+    truncation_cov = emulation.compute_emulator_cov_unexplained(emu_cfg, emu_results)
+    io = _data_IO()
+    data = io.data_array_from_h5(config.output_dir, 'observables.h5', pseudodata_index=closure_index,
+                                 observable_filter=emu_cfg.observable_filter)
+    data = _with_data_covariance(config, data)
+    log_posterior.initialize_pool_variables(lower, upper, emu_cfg, emu_results, data, truncation_cov)
+    # what the gradient path declines is known now: say so before a step is taken
+    reason = find_map_unsupported(emu_cfg, emu_results)
+    if reason:
+        raise ValueError(f"parameters.mcmc.sampler: hmc: {reason}; use the stretch sampler -- no step has been taken")
+    seed = int(np.random.randint(0, 2 ** 31 - 1))          # drawn where the stretch path's sampler draws its seed
+    sampler = HMCSampler(log_posterior.log_posterior._gpemu_device_models(), n_walk, n_leapfrog=config.hmc_n_leapfrog,
+                         step_size=config.hmc_step_size, seed=seed)
+    logger.info(f'HMC sampler ready: {n_walk} chains, {n_par} parameters, {config.hmc_n_leapfrog} leapfrog steps')
+    start = np.random.uniform(lower, upper, (n_walk, n_par))       # ref: mcmc.py:88
+    sampler.set_state(start)
+    if np.any(np.isnan(sampler.get_state()[1])):
+        raise ValueError("The initial log_prob was NaN")
+    # The burn-in keeps the reference's two stages (ref: mcmc.py:88-101).  Uniform starts lie far out in the tails of a
+    # narrow posterior, where the one step size the chains share -- adapted to their MEAN accept probability -- is too
+    # large for the curvature: such a chain would reject every proposal, also after the warm-up.  So the first half
+    # adapts the step size only, from the uniform starts, and the second half, the three-stage warm-up proper, restarts
+    # every chain from the best distinct points seen so far, as the stretch path's second stage does.
+    first_stage = config.n_burn_steps // 2
+    if first_stage > 0:
+        logger.info(f'Burn-in, stage 1 ({first_stage} iterations, step size only)...')
+        sampler.adapt(True, config.hmc_target_accept)
+        sampler.run(first_stage)
+        chain1, lp1 = sampler.get_chain()
+        _, first_seen = np.unique(lp1.reshape(-1), return_index=True)      # ascending in log-probability
+        best = chain1.reshape(-1, n_par)[first_seen[-n_walk:]]
+        if best.shape[0] == n_walk:          # (fewer distinct points than chains: the chains go on from where they are)
+            sampler.set_state(best)
+        sampler.reset()
+    logger.info(f'Warm-up ({config.n_burn_steps - first_stage} iterations, target accept probability '
+                f'{config.hmc_target_accept})...')
+    warm = sampler.warmup(config.n_burn_steps - first_stage, target_accept=config.hmc_target_accept)
+    logger.info(f"  step size {warm['step_size']}, mean accept probability {warm['mean_accept_prob']}, "
+                f"{warm['divergences']} divergences")
+    logger.info(f'Production ({config.n_sampling_steps} iterations)...')
+    done = 0
+    while done < config.n_sampling_steps:
+        block = min(config.n_logging_steps - done % config.n_logging_steps, config.n_sampling_steps - done)
+        sampler.run(block)
+        done += block
+        if done % config.n_logging_steps == 0 or done == config.n_sampling_steps:
+            frac = sampler.acceptance_fraction
+            logger.info(f'  step {done}: acceptance fraction: mean {frac.mean()}, std {frac.std()}, min {frac.min()}, '
+                        f'max {frac.max()}; divergences {int(sampler.divergences.sum())}')
+    chain, lps = sampler.get_chain()
+    nacc, iters, _ = sampler.counts()
+    try:
+        tau = sampler.integrated_time()
+    except Exception as err:        # chain too short for a reliable estimate (emcee's AutocorrError upstream)
+        logger.info(f'No autocorrelation time: {err}')
+        tau = None
+    step_size, inverse_metric, divergences = sampler.step_size, sampler.inverse_metric, sampler.divergences
+    sampler.close()
+
+    one = LoggingEnsembleSampler(n_walk, n_par, log_posterior.log_posterior, seed=seed, sharded=False)
+    one._cache = (chain, lps, nacc.copy(), iters)
+    one._frozen = True
+    one.hmc_step_size, one.hmc_inverse_metric, one.hmc_divergences = step_size, inverse_metric, divergences
+    results = {'chain': one.get_chain(), 'acceptance_fraction': one.acceptance_fraction,
+               'log_prob': one.get_log_prob(), 'autocorrelation_time': tau,
+               'hmc_step_size': np.float64(step_size), 'hmc_inverse_metric': inverse_metric, 'hmc_divergences': divergences}
+    if closure_index >= 0:
+        validation_design = io.design_array_from_h5(config.output_dir, filename='observables.h5', validation_set=True)
+        results['design_point'] = validation_design[closure_index]
+        results['experimental_pseudodata'] = data
+    if getattr(config, 'find_map', False):
+        logger.info('Maximising the log-posterior from the best points of the chain...')
+        try:
+            found = find_map_on_pool(lower, upper, n_starts=min(32, n_walk), chain=results['chain'],
+                                     log_prob=results['log_prob'])
+        except Exception as err:     # the chain is worth more than the maximum: it is written either way
+            logger.warning(f'parameters.mcmc.find_map: the maximisation failed ({err!r}); mcmc.h5 is written without '
+                           'map_parameters, map_log_prob and map_hessian')
+        else:
+            results['map_parameters'] = found['map_parameters']
+            results['map_log_prob'] = np.float64(found['map_log_prob'])
+            results['map_hessian'] = found['hessian']
+    _add_posterior_predictive(config, results, emu_cfg, emu_results, truncation_cov)
+    _write_outputs(config, results, one, io)
+
+
+####################################################################################################
 def posterior_predictive_settings(mc):
     """(on, probabilities) from the ``parameters.mcmc`` mapping: ``posterior_predictive`` (default off) and the
     optional ``posterior_predictive_probabilities`` (default 0.05, 0.5, 0.95; each in [0, 1])."""
@@ -668,6 +785,16 @@ class MCMCConfig:
         self.t_max = float(mc.get('t_max', 1e5))
         self.swap_every = int(mc.get('swap_every', 1))
         self.prior_rung = bool(mc.get('prior_rung', True))
+        # the sampler (optional): "stretch" (default, the reference's) or "hmc" with its three optional settings
+        self.sampler = str(mc.get('sampler', 'stretch') or 'stretch').lower()
+        if self.sampler not in ('stretch', 'hmc'):
+            raise ValueError(f"parameters.mcmc.sampler must be 'stretch' or 'hmc', got {mc.get('sampler')!r}")
+        self.hmc_n_leapfrog = int(mc.get('hmc_n_leapfrog', 8))
+        self.hmc_target_accept = float(mc.get('hmc_target_accept', 0.8))
+        self.hmc_step_size = float(mc.get('hmc_step_size', 0.1))
+        if self.sampler == 'hmc' and not (self.hmc_n_leapfrog >= 1 and 0.0 < self.hmc_target_accept < 1.0
+                                          and self.hmc_step_size > 0.0):
+            raise ValueError("parameters.mcmc: hmc_n_leapfrog must be >= 1, hmc_target_accept in (0, 1) and hmc_step_size > 0")
         # correlated experimental uncertainties (optional): an .npz of 'cov' and / or 'sys_sources', a relative path
         # taken from the directory of the configuration file
         dc = mc.get('data_covariance')

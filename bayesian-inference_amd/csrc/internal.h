@@ -48,9 +48,9 @@ static inline int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * 
 
 // one relaxed host-side increment per launch decision, in one table (gpemu_api.hip) with a row per family of gpemu.h;
 // a path outside its family's enum is not counted
-enum PathFamily { PATHS_LOGPOST, PATHS_FIT, PATHS_WIDE, PATHS_SRC, PATHS_GRAD, PATHS_POSTPRED, PATH_FAMILIES };
+enum PathFamily { PATHS_LOGPOST, PATHS_FIT, PATHS_WIDE, PATHS_SRC, PATHS_GRAD, PATHS_POSTPRED, PATHS_HMC, PATH_FAMILIES };
 void count_path(PathFamily family, int path);
-int read_path_counts(PathFamily family, int64_t *out, int64_t n);     // what the six public gpemu_*_path_counts return
+int read_path_counts(PathFamily family, int64_t *out, int64_t n);     // what the seven public gpemu_*_path_counts return
 static inline void path_count(int path) { count_path(PATHS_LOGPOST, path); }    // enum gpemu_path
 static inline void fit_path_count(int path) { count_path(PATHS_FIT, path); }    // enum gpemu_fit_path
 static inline void wide_path_count(int path) { count_path(PATHS_WIDE, path); }  // enum gpemu_wide_path: d > 8 only
@@ -347,6 +347,12 @@ int predict_cov(gpemu_model *m, int64_t M1, const double *dX1, int64_t M2, const
 // tau_out[k] on the host.  Returns p + 1 for the first PC whose jitter ladder is exhausted.
 int sample_from_cov(gpemu_model *m, int64_t M, int64_t n, const double *dcov, const double *dmean, const double *dz,
                     double *dout, double *tau_out, hipStream_t st);
+// the derivative path (k_grad.hip) for the HMC sampler (k_hmc.hip): what it declines (GPEMU_ERR_UNSUPPORTED: Matern 0.5
+// and general nu, n_src > 0, several data vectors), and lp [B], grad [B][d] of the unpadded rows dX [B][d] summed over
+// ng groups the caller has checked, asynchronous on st
+int grad_lik_supported(const gpemu_model *m, const char *what);
+int logpost_grad_eval(gpemu_model *const *ms, int ng, int64_t B, const double *dX, double *dlp, double *dgrad,
+                      hipStream_t st);
 // profiling helpers: record an event on `st` and return its pool index (-1 when profiling is off)
 int prof_mark(gpemu_model *m, hipStream_t st);
 void prof_pair(gpemu_model *m, int which, int e0, int e1);

@@ -817,6 +817,7 @@ extern "C" {
 
 int gpemu_sampler_peer_export(gpemu_sampler *s, char *handle_out64) {
   GP_ARG(s && handle_out64, "null pointer");
+  GP_NOT_HMC(s, "gpemu_sampler_peer_export");
   if (s->tempered) {
     set_error("gpemu_sampler_peer_export: tempered samplers run on one GPU (gpemu_sampler_run)");
     return GPEMU_ERR_UNSUPPORTED;
@@ -838,6 +839,7 @@ int gpemu_sampler_peer_export(gpemu_sampler *s, char *handle_out64) {
 
 int gpemu_sampler_peer_import(gpemu_sampler *s, int world, int rank, const char *handles) {
   GP_ARG(s && handles && world >= 1 && world <= 64 && rank >= 0 && rank < world, "world / rank / handles");
+  GP_NOT_HMC(s, "gpemu_sampler_peer_import");
   if (s->tempered) {
     set_error("gpemu_sampler_peer_import: tempered samplers run on one GPU (gpemu_sampler_run)");
     return GPEMU_ERR_UNSUPPORTED;
@@ -909,6 +911,7 @@ int gpemu_sampler_peer_selftest(gpemu_sampler *s) {
 
 int gpemu_sampler_run_peer(gpemu_sampler *s, int64_t steps, int store_chain) {
   GP_ARG(s && steps >= 0, "sampler / steps");
+  GP_NOT_HMC(s, "gpemu_sampler_run_peer");
   if (s->tempered) {
     set_error("gpemu_sampler_run_peer: tempered samplers run on one GPU (gpemu_sampler_run)");
     return GPEMU_ERR_UNSUPPORTED;

@@ -457,7 +457,7 @@ static int grad_supported(const gpemu_model *m, const char *what) {
   return GPEMU_OK;
 }
 
-static int grad_lik_supported(const gpemu_model *m, const char *what) {
+int grad_lik_supported(const gpemu_model *m, const char *what) {
   GP_TRY(grad_supported(m, what));
   if (!m->lik_ready) { set_error("gpemu_likelihood_setup has not been called"); return GPEMU_ERR_STATE; }
   if (m->n_src > 0) {
@@ -545,7 +545,7 @@ static int grad_chunk_contract(gpemu_model *m, const GradWs &w, int64_t off, int
 }
 
 // lp [B] and grad [B][d] of dX [B][d] summed over ng groups (all checked by the caller); asynchronous on st
-static int logpost_grad_eval(gpemu_model *const *ms, int ng, int64_t B, const double *dX, double *dlp, double *dgrad,
+int logpost_grad_eval(gpemu_model *const *ms, int ng, int64_t B, const double *dX, double *dlp, double *dgrad,
                              hipStream_t st) {
   for (int64_t off = 0; off < B; off += GRAD_CHUNK) {
     const int64_t Bc = (B - off < GRAD_CHUNK) ? (B - off) : GRAD_CHUNK, Bp = round_up(Bc, 64);

@@ -446,6 +446,7 @@ int gpemu_sampler_destroy(gpemu_sampler *s) {
   (void)hipSetDevice(s->device);
   if (s->stream) (void)hipStreamSynchronize(s->stream);
   front_release(s);
+  hmc_release(s);
   dev_free(s->Xbuf); dev_free(s->lpbuf); dev_free(s->inds); dev_free(s->idx);
   dev_free(s->fac); dev_free(s->pos); dev_free(s->q2); dev_free(s->seeds);
   dev_free(s->zz); dev_free(s->logu); dev_free(s->rint); dev_free(s->q);
@@ -471,7 +472,9 @@ int gpemu_sampler_set_state(gpemu_sampler *s, const double *X0, const double *lo
   GP_TRY(upload(tmp, X0, W * d, st));
   hipLaunchKernelGGL(s->dp == DPAD ? pad_rows_kernel<DPAD> : pad_rows_kernel<DPAD_WIDE>,
                      dim3((unsigned)((W * s->dp + 255) / 256)), dim3(256), 0, st, tmp, s->X, (int)W, (int)d);
-  if (logp0) {
+  if (s->hmc) {
+    GP_TRY(hmc_refresh_state(s, st));      // logp0 is not read: lp and the gradient come from the gradient path
+  } else if (logp0) {
     GP_TRY(upload(s->logp, logp0, W, st));
   } else {
     // evaluate all walkers; X has exactly W rows, so go through a padded scratch copy in chunks
@@ -530,6 +533,7 @@ int gpemu_sampler_reset(gpemu_sampler *s) {
     GP_HIP(hipMemsetAsync(s->nswap_acc, 0, sizeof(long long) * npair, s->stream));
     GP_HIP(hipMemsetAsync(s->nswap_try, 0, sizeof(long long) * npair, s->stream));
   }
+  if (s->hmc) GP_TRY(hmc_reset(s));
   GP_HIP(hipStreamSynchronize(s->stream));
   s->chain_len = 0;
   s->iterations = 0;
@@ -558,6 +562,7 @@ int gpemu_sampler_snapshot(gpemu_sampler *s) {
     GP_HIP(hipMemcpyAsync(s->snapswap + npair, s->nswap_try, sizeof(long long) * npair, hipMemcpyDeviceToDevice,
                           s->stream));
   }
+  if (s->hmc) GP_TRY(hmc_snapshot(s));
   s->snap_step_counter = s->step_counter;
   s->snap_iterations = s->iterations;
   s->snap_chain_len = s->chain_len;
@@ -580,6 +585,7 @@ int gpemu_sampler_restore(gpemu_sampler *s) {
     GP_HIP(hipMemcpyAsync(s->nswap_try, s->snapswap + npair, sizeof(long long) * npair, hipMemcpyDeviceToDevice,
                           s->stream));
   }
+  if (s->hmc) GP_TRY(hmc_restore(s));
   GP_HIP(hipMemsetAsync(s->flags, 0, sizeof(int) * 2, s->stream));
   GP_HIP(hipStreamSynchronize(s->stream));
   s->step_counter = s->snap_step_counter;
@@ -604,6 +610,7 @@ static int check_nan(gpemu_sampler *s) {
 int gpemu_sampler_run(gpemu_sampler *s, int64_t steps, int store_chain) {
   GP_ARG(s && steps >= 0, "sampler / steps");
   GP_HIP(hipSetDevice(s->device));
+  if (s->hmc) return hmc_run(s, steps, store_chain);
   hipStream_t st = s->stream;
   const LaunchSwitches sw = read_launch_switches();
   // On one GPU the three-launch half-step below is the faster form (0.2275 vs 0.2516 ms per step at C3,
@@ -621,6 +628,7 @@ int gpemu_sampler_run(gpemu_sampler *s, int64_t steps, int store_chain) {
 int gpemu_sampler_step_host_rng(gpemu_sampler *s, const int32_t *inds, const double *zz,
                                 const int64_t *rint, const double *logu, int store_chain) {
   GP_ARG(s && inds && zz && rint && logu, "null pointer");
+  GP_NOT_HMC(s, "gpemu_sampler_step_host_rng");
   if (s->tempered) {
     set_error("gpemu_sampler_step_host_rng: a tempered sampler draws its randomness on the device (gpemu_sampler_run)");
     return GPEMU_ERR_UNSUPPORTED;
@@ -716,6 +724,7 @@ int gpemu_sampler_reserve_chain(gpemu_sampler *s, int64_t additional_steps) {
 
 int gpemu_sampler_begin_step(gpemu_sampler *s) {
   GP_ARG(s, "sampler");
+  GP_NOT_HMC(s, "gpemu_sampler_begin_step");
   GP_HIP(hipSetDevice(s->device));
   return launch_rng(s, s->stream, RNG_BATCH);
 }
@@ -723,6 +732,7 @@ int gpemu_sampler_begin_step(gpemu_sampler *s) {
 int gpemu_sampler_half_propose_eval(gpemu_sampler *s, int half, int64_t lo, int64_t hi,
                                     double *dnewlp_slice) {
   GP_ARG(s && (half == 0 || half == 1), "half");
+  GP_NOT_HMC(s, "gpemu_sampler_half_propose_eval");
   GP_ARG(lo >= 0 && lo <= hi && hi <= s->ns[half] && dnewlp_slice, "slice");
   GP_HIP(hipSetDevice(s->device));
   const LaunchSwitches sw = read_launch_switches();
@@ -737,12 +747,14 @@ int gpemu_sampler_half_propose_eval(gpemu_sampler *s, int half, int64_t lo, int6
 
 int gpemu_sampler_half_accept(gpemu_sampler *s, int half, const double *dnewlp_all, int store_chain) {
   GP_ARG(s && (half == 0 || half == 1) && dnewlp_all, "half / newlp");
+  GP_NOT_HMC(s, "gpemu_sampler_half_accept");
   GP_HIP(hipSetDevice(s->device));
   return launch_accept(s, half, dnewlp_all, store_chain, s->stream);
 }
 
 int gpemu_sampler_end_step(gpemu_sampler *s, int store_chain) {
   GP_ARG(s, "sampler");
+  GP_NOT_HMC(s, "gpemu_sampler_end_step");
   GP_HIP(hipSetDevice(s->device));
   return end_step(s, store_chain, s->stream, true);   // the accept kernels recorded the chain row
 }
@@ -880,6 +892,7 @@ __global__ void fill_kernel(double *p, int64_t n, double v) {
 int gpemu_sampler_run_sharded(gpemu_sampler *s, gpemu_comm *c, int64_t steps, int store_chain,
                               int emulate_world) {
   GP_ARG(s && steps >= 0 && emulate_world >= 0, "sampler / steps / emulate_world");
+  GP_NOT_HMC(s, "gpemu_sampler_run_sharded");
   if (s->tempered) {
     set_error("gpemu_sampler_run_sharded: tempered samplers run on one GPU (gpemu_sampler_run)");
     return GPEMU_ERR_UNSUPPORTED;

@@ -154,6 +154,7 @@ int gpemu_sampler_create_tempered(gpemu_sampler **out, gpemu_model *const *group
 
 int gpemu_sampler_set_betas(gpemu_sampler *s, const double *betas) {
   GP_ARG(s, "sampler");
+  GP_NOT_HMC(s, "gpemu_sampler_set_betas");
   if (!s->tempered) { set_error("gpemu_sampler_set_betas: the sampler is not tempered"); return GPEMU_ERR_STATE; }
   GP_TRY(temper_validate_ladder(betas, s->nchains));
   GP_HIP(hipSetDevice(s->device));
@@ -164,6 +165,7 @@ int gpemu_sampler_set_betas(gpemu_sampler *s, const double *betas) {
 
 int gpemu_sampler_get_swap_counts(gpemu_sampler *s, int64_t *accepted, int64_t *attempted) {
   GP_ARG(s, "sampler");
+  GP_NOT_HMC(s, "gpemu_sampler_get_swap_counts");
   if (!s->tempered) { set_error("gpemu_sampler_get_swap_counts: the sampler is not tempered"); return GPEMU_ERR_STATE; }
   GP_HIP(hipSetDevice(s->device));
   const size_t npair = (size_t)(s->nchains - 1) * (size_t)(s->W / s->nchains);
@@ -175,6 +177,7 @@ int gpemu_sampler_get_swap_counts(gpemu_sampler *s, int64_t *accepted, int64_t *
 
 int gpemu_sampler_mean_loglik(gpemu_sampler *s, int64_t first, int64_t n, double *out) {
   GP_ARG(s && out, "sampler / out");
+  GP_NOT_HMC(s, "gpemu_sampler_mean_loglik");
   if (!s->tempered) { set_error("gpemu_sampler_mean_loglik: the sampler is not tempered"); return GPEMU_ERR_STATE; }
   GP_ARG(first >= 0 && n >= 1 && first + n <= s->chain_len, "chain range");
   GP_HIP(hipSetDevice(s->device));

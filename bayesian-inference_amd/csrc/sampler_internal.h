@@ -36,7 +36,35 @@ __host__ __device__ static inline double u01_from(uint32_t hi, uint32_t lo) {
 }
 }  // namespace gpemu
 
+// what an HMC sampler (gpemu_sampler_create_hmc, k_hmc.hip) holds beside the chain layout of gpemu_sampler
+struct HmcState {
+  int L = 1;                   // leapfrog steps per iteration
+  double jitter = 0.0;         // eps_w = eps (1 + jitter (2 u - 1))
+  int adapt_on = 0;            // dual averaging of the step size after every iteration
+  double target = 0.8;         // its target mean accept probability
+  double *g = nullptr;         // [W][d]  gradient of the current state, carried between the iterations
+  double *xq = nullptr;        // [W][d]  trajectory position (unpadded rows: the gradient path's input)
+  double *p = nullptr;         // [W][d]  trajectory momentum
+  double *gnew = nullptr;      // [W][d]  gradient at xq
+  double *lpnew = nullptr;     // [W]     log-posterior at xq
+  double *kin0 = nullptr;      // [W]     kinetic energy of the drawn momentum
+  double *epsw = nullptr;      // [W]     the chains' step sizes of this iteration
+  double *logu = nullptr;      // [W]     log of the accept uniform
+  double *accp = nullptr;      // [W]     min(1, exp(H_old - H_new)), 0 for a divergence
+  double *minv = nullptr;      // [16]    diagonal inverse metric (1 beyond d)
+  double *ad = nullptr;        // step size and dual-averaging state (k_hmc.hip: AD_*)
+  long long *ndiv = nullptr;   // [W]     divergences
+  std::vector<double> minv_host;
+  // gpemu_sampler_snapshot / _restore
+  double *snapg = nullptr, *snapad = nullptr;
+  long long *snapdiv = nullptr;
+  int snap_adapt_on = 0;
+  double snap_target = 0.8;
+  std::vector<double> snap_minv;
+};
+
 struct gpemu_sampler {
+  HmcState *hmc = nullptr;     // an HMC sampler: the stretch move's fields below are allocated but idle
   int device = 0;
   std::vector<gpemu_model *> groups;
   int64_t W = 0, d = 0;
@@ -120,6 +148,21 @@ int sampler_check_nan(gpemu_sampler *s);
 // k_temper.hip
 int temper_swap(gpemu_sampler *s, int store_chain, hipStream_t st);   // the swap pass of step s->step_counter, if due
 int temper_validate_ladder(const double *betas, int n_temps);
+// k_hmc.hip: the parts of the sampler calls that an HMC sampler (s->hmc) takes
+int hmc_run(gpemu_sampler *s, int64_t steps, int store_chain);
+int hmc_refresh_state(gpemu_sampler *s, hipStream_t st);      // lp and gradient of the positions just set
+int hmc_reset(gpemu_sampler *s);
+int hmc_snapshot(gpemu_sampler *s);
+int hmc_restore(gpemu_sampler *s);
+void hmc_release(gpemu_sampler *s);
+// the calls an HMC sampler declines
+#define GP_NOT_HMC(s, name)                                                                              \
+  do {                                                                                                   \
+    if ((s) && (s)->hmc) {                                                                               \
+      gpemu::set_error(name ": not supported on an HMC sampler (one GPU, gpemu_sampler_run)");           \
+      return GPEMU_ERR_UNSUPPORTED;                                                                      \
+    }                                                                                                    \
+  } while (0)
 // k_front.hip
 void front_release(gpemu_sampler *s);                         // frees the gather buffer and the peer mappings
 bool front_eligible(const gpemu_sampler *s);

@@ -137,6 +137,19 @@ _SIGNATURES = {
                                        + [C.c_void_p] * 5),
     "gpemu_sampler_chain_ptr": (C.c_int, [C.c_void_p, c_i64, C.POINTER(C.c_void_p), C.POINTER(c_i64)]),
     "gpemu_postpred_path_counts": (C.c_int, [C.POINTER(c_i64), c_i64]),
+    "gpemu_sampler_create_hmc": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int, c_i64, C.c_int,
+                                           C.c_double, C.c_double, C.c_uint64]),
+    "gpemu_sampler_hmc_set_metric": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "gpemu_sampler_hmc_get_metric": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "gpemu_sampler_hmc_set_step_size": (C.c_int, [C.c_void_p, C.c_double]),
+    "gpemu_sampler_hmc_get_step_size": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
+    "gpemu_sampler_hmc_adapt": (C.c_int, [C.c_void_p, C.c_int, C.c_double]),
+    "gpemu_sampler_hmc_step_host_rng": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+    "gpemu_sampler_hmc_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double),
+                                          C.POINTER(C.c_double)]),
+    "gpemu_sampler_hmc_draws": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gpemu_sampler_chain_moments": (C.c_int, [C.c_void_p, c_i64, c_i64, C.c_void_p, C.c_void_p]),
+    "gpemu_hmc_path_counts": (C.c_int, [C.POINTER(c_i64), c_i64]),
 }
 
 

@@ -418,6 +418,13 @@ def postpred_path_counts():
     return out[:n].copy()
 
 
+def hmc_path_counts():
+    """Counters of enum gpemu_hmc_path (the HMC sampler's launches and the chain moments), as an int64 array."""
+    out = np.zeros(8, dtype=np.int64)
+    n = _lib.lib().gpemu_hmc_path_counts(out.ctypes.data_as(C.POINTER(C.c_int64)), out.size)
+    return out[:n].copy()
+
+
 def grad_path_counts():
     """Counters of enum gpemu_grad_path (the derivative launches), as an int64 array."""
     out = np.zeros(8, dtype=np.int64)

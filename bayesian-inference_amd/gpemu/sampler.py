@@ -288,6 +288,16 @@ class DeviceSampler:
         q = select.lerp(sel[:, ilo].T, sel[:, ihi].T, t[:, None])
         return q[0] if np.ndim(probabilities) == 0 else q
 
+    def chain_moments(self, discard=0, n=None):
+        """``(mean (d,), var (d,))`` of the stored steps ``[discard, discard + n)`` pooled over all walkers --
+        ``x = get_chain()[discard:discard + n].reshape(-1, d)``, ``x.mean(0)``, ``x.var(0)`` -- computed on the device
+        in two passes with sums in a fixed order; the chain stays where it is."""
+        _, _, cl = self.counts()
+        n = cl - int(discard) if n is None else int(n)
+        mean, var = np.empty(self.d), np.empty(self.d)
+        check(_lib.lib().gpemu_sampler_chain_moments(self._h, int(discard), n, ptr(mean), ptr(var)))
+        return mean, var
+
     def acf_block(self, lag0, n_lags, first=0, n=None, w0=0, nw=None):
         """Walker-averaged normalised autocorrelation function, lags [lag0, lag0 + n_lags), of the chain stored on
         the device: (n_lags, d).  ``lag0`` a multiple of 16, the first block of an estimate at 0."""
@@ -757,6 +767,118 @@ class TemperedSampler(DeviceSampler):
         Wc = self.walkers_per_chain
         return DeviceSampler.integrated_time(self, first=first, n=n, w0=int(temp) * Wc, nw=Wc, c=c, tol=tol,
                                              quiet=quiet, block=block)
+
+
+# ------------------------------------------------------------------------------------------------
+class HMCSampler(DeviceSampler):
+    """``n_chains`` independent Hamiltonian Monte Carlo chains in lock step on one GPU, on the
+    analytic gradient of the log-posterior (``DeviceModel.logpost_grad``'s path).  Chain w is walker w of the stored
+    chain, so ``get_chain``, ``chain_ptr``, ``integrated_time``, ``posterior_predictive``, ``parameter_quantiles``,
+    ``chain_moments`` and snapshot / restore work as on a ``DeviceSampler``.  Trajectories reflect at the faces of the
+    prior box.  ``warmup`` adapts the step size (dual averaging, on the device) and the diagonal metric; ``run``
+    then samples with both fixed.  Kernels the gradient declines (Matern 0.5, general nu), correlated systematic
+    sources and several data vectors are declined at construction; sharded runs are not supported."""
+
+    def __init__(self, models, n_chains, n_leapfrog=8, step_size=0.1, jitter=None, seed=0):
+        from . import hmc as _hmc
+        self.n_leapfrog = int(n_leapfrog)
+        self._eps0 = float(step_size)
+        self.jitter = _hmc.DEFAULT_JITTER if jitter is None else float(jitter)
+        super().__init__(models, n_chains, seed=seed)
+        self._prior_var = self.inverse_metric
+
+    def _create(self, arr, n_walkers, a, seed, seeds):
+        if seeds is not None:
+            raise ValueError("an HMC sampler takes one seed: its chains are independent already")
+        h = C.c_void_p()
+        check(_lib.lib().gpemu_sampler_create_hmc(C.byref(h), arr, len(self.models), n_walkers, self.n_leapfrog, self._eps0,
+                                                  self.jitter, C.c_uint64(int(seed) & (2 ** 64 - 1))))
+        return h, 1
+
+    @property
+    def step_size(self):
+        e = C.c_double()
+        check(_lib.lib().gpemu_sampler_hmc_get_step_size(self._h, C.byref(e)))
+        return float(e.value)
+
+    @step_size.setter
+    def step_size(self, eps):
+        check(_lib.lib().gpemu_sampler_hmc_set_step_size(self._h, float(eps)))
+
+    @property
+    def inverse_metric(self):
+        m = np.empty(self.d)
+        check(_lib.lib().gpemu_sampler_hmc_get_metric(self._h, ptr(m)))
+        return m
+
+    @inverse_metric.setter
+    def inverse_metric(self, minv):
+        check(_lib.lib().gpemu_sampler_hmc_set_metric(self._h, ptr(as_f64(minv, (self.d,)))))
+
+    def adapt(self, on, target_accept=None):
+        """Switch the device's dual averaging of the step size on (restarting it at the current step size) or off
+        (freezing the step size at the averaged one)."""
+        from . import hmc as _hmc
+        t = _hmc.DEFAULT_TARGET_ACCEPT if target_accept is None else float(target_accept)
+        check(_lib.lib().gpemu_sampler_hmc_adapt(self._h, int(bool(on)), t))
+
+    def stats(self):
+        """dict: ``accepted``, ``divergences`` (per chain, since the last reset), ``mean_accept_prob`` (over the
+        iterations since then) and ``last_accept_prob`` (of the last iteration)."""
+        acc, div = np.zeros(self.W, dtype=np.int64), np.zeros(self.W, dtype=np.int64)
+        mean, last = C.c_double(), C.c_double()
+        check(_lib.lib().gpemu_sampler_hmc_stats(self._h, ptr(acc), ptr(div), C.byref(mean), C.byref(last)))
+        return dict(accepted=acc, divergences=div, mean_accept_prob=float(mean.value), last_accept_prob=float(last.value))
+
+    @property
+    def divergences(self):
+        return self.stats()["divergences"]
+
+    @property
+    def acceptance_fraction(self):
+        nacc, it, _ = self.counts()
+        return nacc / float(max(it, 1))
+
+    def draws(self, step):
+        """What iteration ``step`` of the device's random stream draws: ``(z (W, d), u_accept (W,), u_jitter (W,))``."""
+        z, ua, uj = np.empty((self.W, self.d)), np.empty(self.W), np.empty(self.W)
+        check(_lib.lib().gpemu_sampler_hmc_draws(self._h, C.c_uint64(int(step)), ptr(z), ptr(ua), ptr(uj)))
+        return z, ua, uj
+
+    def step_host_rng(self, p0, logu, eps_w, store=True):
+        """One iteration with the caller's momenta ``p0 (W, d)``, log-uniforms and per-chain step sizes."""
+        p0, logu, eps_w = as_f64(p0, (self.W, self.d)), as_f64(logu, (self.W,)), as_f64(eps_w, (self.W,))
+        rc = _lib.lib().gpemu_sampler_hmc_step_host_rng(self._h, ptr(p0), ptr(logu), ptr(eps_w), int(bool(store)))
+        if rc == 1:
+            raise ValueError("Probability function returned NaN")
+        check(rc)
+
+    def warmup(self, n_warmup, target_accept=None, adapt_metric=True):
+        """``n_warmup`` iterations of the three-stage warm-up (``gpemu.hmc.warmup_schedule``) from the current state.
+        The step size adapts on the device after every iteration; the host is heard only at the ends of the metric
+        windows.  Afterwards step size and metric are fixed, and the warm-up's chain and counters are dropped
+        (``reset``); returns dict ``step_size``, ``inverse_metric``, ``mean_accept_prob``, ``divergences`` (of the
+        warm-up)."""
+        from . import hmc as _hmc
+        self.reset()
+        self.adapt(True, target_accept)
+        for n, set_metric in _hmc.warmup_schedule(n_warmup):
+            set_metric = set_metric and adapt_metric
+            _, _, before = self.counts()
+            self.run(n, store=set_metric)
+            if set_metric:
+                _, var = self.chain_moments(discard=before, n=n)
+                self.inverse_metric = _hmc.regularised_metric(var, n, self._prior_var)
+                self.adapt(True, target_accept)          # the averaging restarts at the step size reached
+        self.adapt(False)
+        st = self.stats()
+        out = dict(step_size=self.step_size, inverse_metric=self.inverse_metric, mean_accept_prob=st["mean_accept_prob"],
+                   divergences=int(st["divergences"].sum()))
+        self.reset()
+        return out
+
+    def run_sharded(self, steps, store=True, group=None, force=False, emulate_world=None, transport=None):
+        raise _lib.GpemuError(-5, "HMC samplers run on one GPU (HMCSampler.run); sharded runs are not supported")
 
 
 # ------------------------------------------------------------------------------------------------

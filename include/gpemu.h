@@ -548,6 +548,54 @@ enum gpemu_postpred_path {
 /* out[0 .. min(n, GPEMU_POSTPRED_PATH_COUNT)) = the counters; returns GPEMU_POSTPRED_PATH_COUNT (or GPEMU_ERR_ARG). */
 int gpemu_postpred_path_counts(int64_t *out, int64_t n);
 
+/* ---- Hamiltonian Monte Carlo -----------------------------------------------------------------------
+ * W independent chains in lock step on the gradient of gpemu_logpost_groups_grad; chain w is "walker" w of the
+ * sampler's chain layout, so gpemu_sampler_run, _set_state (logp0 is not read: lp and the gradient of the start come
+ * from the gradient path), _get_state, _reset, _get_chain*, _get_counts, _acf, _chain_ptr, _snapshot and _restore work
+ * on the handle.  One iteration: eps_w = eps (1 + jitter (2 u - 1)); p = z / sqrt(minv); n_leapfrog leapfrog steps with
+ * reflection at the faces of the prior box; accept iff log u' < H_old - H_new, H = -lp + 1/2 sum minv p^2.  A
+ * non-finite H_new or H_new - H_old > 1000 (away from a face, where lp = -inf is the ordinary reject) is a rejected
+ * divergence.  Inverse metric: diagonal, default (hi - lo)^2 / 12.  Random stream: Philox4x32-10 keyed by seed, a
+ * chain's draws depend on its index and the step only: chains 0 .. n-1 of a larger sampler are those of a smaller one.
+ * Declines (GPEMU_ERR_UNSUPPORTED) at create, before any launch, whatever gpemu_logpost_grad declines; on the handle:
+ * gpemu_sampler_run_sharded, the peer transport, the phase calls, gpemu_sampler_step_host_rng, the tempered setters. */
+int gpemu_sampler_create_hmc(gpemu_sampler **out, gpemu_model *const *groups, int n_groups, int64_t W, int n_leapfrog,
+                             double eps0, double jitter, uint64_t seed);
+int gpemu_sampler_hmc_set_metric(gpemu_sampler *s, const double *minv /*[d], > 0*/);
+int gpemu_sampler_hmc_get_metric(gpemu_sampler *s, double *minv /*[d]*/);
+/* the step size; with the adaptation on, setting it restarts the averaging there */
+int gpemu_sampler_hmc_set_step_size(gpemu_sampler *s, double eps);
+int gpemu_sampler_hmc_get_step_size(gpemu_sampler *s, double *eps); /* waits for the sampler's stream */
+/* Dual averaging of the step size (Hoffman & Gelman 2014: gamma 0.05, t0 10, kappa 0.75, mu = log(10 eps)), updated on
+ * the device after every iteration from the chains' mean accept probability.  on: (re)start the averaging at the
+ * current step size; off: freeze the step size at the averaged one. */
+int gpemu_sampler_hmc_adapt(gpemu_sampler *s, int on, double target_accept);
+/* one iteration with the caller's momenta p0[W*d], log-uniforms logu[W] and step sizes eps_w[W] */
+int gpemu_sampler_hmc_step_host_rng(gpemu_sampler *s, const double *p0, const double *logu, const double *eps_w,
+                                    int store_chain);
+/* per-chain accepts and divergences [W] since the last reset (either may be NULL), the mean over iterations and
+ * chains of min(1, exp(H_old - H_new)) since then, and that of the last iteration alone */
+int gpemu_sampler_hmc_stats(gpemu_sampler *s, int64_t *naccepted, int64_t *divergences, double *mean_accept_prob,
+                            double *last_accept_prob);
+/* what iteration `step` of the device stream draws (for tests): the normals z[W*d] and the two uniforms [W] */
+int gpemu_sampler_hmc_draws(gpemu_sampler *s, uint64_t step, double *z, double *u_accept, double *u_jitter);
+/* Pooled mean[d] and variance[d] (divisor: the number of points) of steps [first, first + n) of ANY sampler's stored
+ * chain, all walkers, computed where the chain lies: two passes, sums in a fixed order. */
+int gpemu_sampler_chain_moments(gpemu_sampler *s, int64_t first, int64_t n, double *mean, double *var);
+/* Which launches of the HMC sampler ran.  A set of its own: the other sets keep their sizes and indices. */
+enum gpemu_hmc_path {
+  GPEMU_HMC_PATH_BEGIN = 0,         /* momentum draw (Philox), first kick, drift, reflection                         */
+  GPEMU_HMC_PATH_BEGIN_HOST_RNG,    /* ... with the caller's momenta                                                 */
+  GPEMU_HMC_PATH_LEAPFROG,          /* the fused kick-kick-drift-reflect between two gradient evaluations            */
+  GPEMU_HMC_PATH_FINISH,            /* last kick, energies, accept, counters, state and chain row                    */
+  GPEMU_HMC_PATH_ADAPT,             /* mean accept probability + dual-averaging update                               */
+  GPEMU_HMC_PATH_ACCEPT_MEAN,       /* mean accept probability alone (adaptation off)                                */
+  GPEMU_HMC_PATH_MOMENTS,           /* gpemu_sampler_chain_moments                                                   */
+  GPEMU_HMC_PATH_COUNT
+};
+/* out[0 .. min(n, GPEMU_HMC_PATH_COUNT)) = the counters; returns GPEMU_HMC_PATH_COUNT (or GPEMU_ERR_ARG). */
+int gpemu_hmc_path_counts(int64_t *out, int64_t n);
+
 /* ---- fit handle: test-only entry points ---------------------------------------------------------------------------
  * For the tests of the fit side only; nothing in the library's own flow calls them.
  * gpemu_fit_workspace: out[N*N] = problem z of the last evaluation (gpemu_fit_lml / _lml_batch / _factor) as the
