@@ -200,6 +200,11 @@ def _run_closure_batch(config, indices):
         except Exception as err:
             logger.info(f'No autocorrelation time (closure {indices[c]}): {err}')
             taus.append(None)
+    diags = []
+    for c in range(n_ch):           # where the chain lies: before the sampler goes
+        part = {}
+        _add_diagnostics(config, part, lambda c=c: sampler.diagnostics(chain=c), label=f'closure chain {indices[c]}')
+        diags.append(part)
     sampler.close()
 
     validation_design = io.design_array_from_h5(config.output_dir, filename='observables.h5', validation_set=True)
@@ -214,6 +219,7 @@ def _run_closure_batch(config, indices):
         results = {'chain': one.get_chain(), 'acceptance_fraction': one.acceptance_fraction,
                    'log_prob': one.get_log_prob(), 'autocorrelation_time': tau,
                    'design_point': validation_design[j], 'experimental_pseudodata': datas[c]}
+        results.update(diags[c])
         _add_posterior_predictive(config, results, emu_cfg, emu_results, truncation_cov)
         logger.info(f'Writing {cfg_j.mcmc_outputfile}')
         io.write_dict_to_h5(results, cfg_j.mcmc_output_dir, 'mcmc.h5', verbose=True)
@@ -324,6 +330,7 @@ def run_mcmc(config, closure_index=-1):
         tau = None
     results = {'chain': sampler.get_chain(), 'acceptance_fraction': sampler.acceptance_fraction,
                'log_prob': sampler.get_log_prob(), 'autocorrelation_time': tau}
+    _add_diagnostics(config, results, sampler.get_diagnostics)
     if closure_index >= 0:
         validation_design = io.design_array_from_h5(config.output_dir, filename='observables.h5', validation_set=True)
         results['design_point'] = validation_design[closure_index]
@@ -447,6 +454,8 @@ def _run_tempered(config, closure_index):
     except Exception as err:        # chain too short for a reliable estimate (emcee's AutocorrError upstream)
         logger.info(f'No autocorrelation time: {err}')
         tau = None
+    diag = {}
+    _add_diagnostics(config, diag, lambda: sampler.diagnostics(temp=0), label='production chain (beta = 1)')
     mean_ll = sampler.mean_log_likelihood()
     log_z, dlog_z = sampler.log_evidence_estimate()
     swap_frac = sampler.tswap_acceptance_fraction
@@ -462,6 +471,7 @@ def _run_tempered(config, closure_index):
                'log_prob': one.get_log_prob(), 'autocorrelation_time': tau,
                'betas': betas, 'log_evidence': np.float64(log_z), 'log_evidence_error': np.float64(dlog_z),
                'mean_log_likelihood': mean_ll, 'temperature_swap_acceptance_fraction': swap_frac}
+    results.update(diag)
     if closure_index >= 0:
         validation_design = io.design_array_from_h5(config.output_dir, filename='observables.h5', validation_set=True)
         results['design_point'] = validation_design[closure_index]
@@ -552,6 +562,8 @@ def _run_hmc(config, closure_index):
     except Exception as err:        # chain too short for a reliable estimate (emcee's AutocorrError upstream)
         logger.info(f'No autocorrelation time: {err}')
         tau = None
+    diag = {}
+    _add_diagnostics(config, diag, sampler.diagnostics)
     step_size, inverse_metric, divergences = sampler.step_size, sampler.inverse_metric, sampler.divergences
     sampler.close()
 
@@ -562,6 +574,7 @@ def _run_hmc(config, closure_index):
     results = {'chain': one.get_chain(), 'acceptance_fraction': one.acceptance_fraction,
                'log_prob': one.get_log_prob(), 'autocorrelation_time': tau,
                'hmc_step_size': np.float64(step_size), 'hmc_inverse_metric': inverse_metric, 'hmc_divergences': divergences}
+    results.update(diag)
     if closure_index >= 0:
         validation_design = io.design_array_from_h5(config.output_dir, filename='observables.h5', validation_set=True)
         results['design_point'] = validation_design[closure_index]
@@ -595,6 +608,58 @@ def posterior_predictive_settings(mc):
         raise ValueError("parameters.mcmc.posterior_predictive_probabilities must be probabilities in [0, 1], got "
                          f"{probs}")
     return on, probs
+
+
+def diagnostics_settings(mc):
+    """``parameters.mcmc.diagnostics`` (default off) from the ``parameters.mcmc`` mapping: rank-normalised split-R-hat,
+    bulk / tail ESS, the ESS of the mean and its Monte Carlo standard error of the production chain into mcmc.h5."""
+    on = mc.get('diagnostics', False)
+    if not isinstance(on, (bool, np.bool_)):
+        raise ValueError(f"parameters.mcmc.diagnostics must be true or false, got {on!r}")
+    return bool(on)
+
+
+DIAGNOSTICS_KEYS = ('rhat', 'ess_bulk', 'ess_tail', 'ess_mean', 'mcse_mean')
+RHAT_THRESHOLD = 1.01      # Vehtari et al. (2021)
+
+
+def _add_diagnostics(config, results, compute, label='production chain'):
+    """With ``parameters.mcmc.diagnostics``: the five ``(d,)`` arrays of ``compute()`` (a sampler's ``diagnostics`` on
+    the chain where it lies) into the results that go to mcmc.h5, one log line, and a warning where max R-hat exceeds
+    1.01.  The walkers of a stretch ensemble are not independent chains: R-hat compares walkers there."""
+    if not getattr(config, 'diagnostics', False):
+        return
+    try:
+        diag = compute()
+    except Exception as err:         # e.g. fewer than 8 stored steps: the chain is written either way
+        logger.warning(f'parameters.mcmc.diagnostics: not computed ({err!r}); mcmc.h5 is written without '
+                       + ', '.join(DIAGNOSTICS_KEYS))
+        return
+    for key in DIAGNOSTICS_KEYS:
+        results[key] = np.asarray(diag[key], dtype=np.float64)
+    from gpemu.diagnostics import log_line
+    line, warn = log_line(diag, label=f"Diagnostics of the {label} ({diag['n_chains']} split chains x "
+                                      f"{diag['n_draws']} draws)")
+    logger.info(line)
+    if warn:
+        logger.warning(f"max R-hat {np.nanmax(results['rhat']):.4f} > {RHAT_THRESHOLD}: the chains have not mixed")
+
+
+def diagnostics(config, closure_index=-1, discard=0, thin=1):
+    """The five diagnostics (``gpemu.diagnostics.summary``) of the chain stored in mcmc.h5 (of closure chain
+    ``closure_index``, if >= 0), steps ``[discard::thin]``, every walker as a chain."""
+    if closure_index >= 0:
+        config = MCMCConfig(analysis_name=config.analysis_name, parameterization=config.parameterization,
+                            analysis_config=config.analysis_config, config_file=config.config_file,
+                            closure_index=closure_index)
+    if int(discard) < 0 or int(thin) < 1:
+        raise ValueError("discard must be >= 0 and thin >= 1")
+    stored = _data_IO().read_dict_from_h5(config.mcmc_output_dir, 'mcmc.h5')
+    chain = np.ascontiguousarray(np.asarray(stored['chain'], dtype=np.float64)[int(discard)::int(thin)])
+    if chain.shape[0] == 0:
+        raise ValueError("no stored steps after discard")
+    from gpemu import diagnostics as _diag
+    return _diag.summary(chain)
 
 
 POSTERIOR_PREDICTIVE_KEYS = ('mean', 'variance_parameters', 'variance_emulator', 'quantiles', 'probabilities')
@@ -806,6 +871,9 @@ class MCMCConfig:
         # per-bin posterior-predictive bands from the whole production chain (optional, default off): five more
         # entries in mcmc.h5, none without the key
         self.posterior_predictive, self.posterior_predictive_probabilities = posterior_predictive_settings(mc)
+        # convergence diagnostics of the production chain (optional, default off): rhat, ess_bulk, ess_tail, ess_mean and
+        # mcse_mean in mcmc.h5, none without the key
+        self.diagnostics = diagnostics_settings(mc)
 
         # <output_dir>/<analysis>_<parameterization>[/closure/results/<index>]/{mcmc.h5, mcmc_sampler.pkl}
         self.output_dir = os.path.join(top['output_dir'], f'{analysis_name}_{parameterization}')

@@ -19,9 +19,6 @@
 
 namespace gpemu {
 
-constexpr int ACF_LPT = 16;      // lags per thread
-constexpr int ACF_TCHUNKS = 8;   // chunks of steps (partial sums)
-
 // part[c][s] = sum of the series over chunk c
 // (chain: first series of the block asked for; ld: doubles per chain row; S: series in the block)
 __global__ __launch_bounds__(256) void acf_sum_kernel(const double *__restrict__ chain, int64_t n_t, int64_t S, int64_t ld,

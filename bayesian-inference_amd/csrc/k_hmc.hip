@@ -225,7 +225,7 @@ __global__ __launch_bounds__(256) void hmc_draws_kernel(double *z, double *ua, d
 }
 
 // ---- chain moments: pooled mean and variance per parameter, two passes, fixed order ---------------------------------
-constexpr int MOM_ROWS = 1024;   // rows of the flattened chain [R][d] per workgroup
+// (MOM_ROWS rows of the flattened chain [R][d] per workgroup: sampler_internal.h)
 
 // part[b][dd] = sum over the rows of block b of x (mean == null) or of (x - mean[dd])^2
 __global__ __launch_bounds__(256) void moments_partial_kernel(const double *__restrict__ x, int64_t R, int d,

@@ -46,16 +46,7 @@ constexpr int64_t PP_SUM = 4096;     // samples per partial sum
 constexpr int PP_FT = 32;            // features per projection workgroup
 constexpr int64_t PP_FIXED = GPEMU_POSTPRED_FIXED_BYTES;
 
-typedef unsigned long long u64;
-
-static __device__ __forceinline__ u64 sel_key(double v) {
-  const u64 u = (u64)__double_as_longlong(v);
-  return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
-}
-static __device__ __forceinline__ double sel_value(u64 key) {
-  const u64 u = (key >> 63) ? (key ^ 0x8000000000000000ull) : ~key;
-  return __longlong_as_double((long long)u);
-}
+// (sel_key / sel_value: sampler_internal.h)
 
 struct SelState {
   u64 *prefix = nullptr;    // [SEL_ROWS][SEL_MAXR] key bits found so far, per rank

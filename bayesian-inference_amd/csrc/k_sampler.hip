@@ -216,6 +216,7 @@ __global__ void unpad_rows_kernel(const double *__restrict__ src, double *__rest
 
 // ---- host helpers ---------------------------------------------------------------------------------
 static int ensure_chain(gpemu_sampler *s, int64_t need) {
+  ++s->chain_epoch;   // every caller is about to store steps, or may move the buffer
   if (need <= s->chain_cap) return GPEMU_OK;
   int64_t cap = s->chain_cap ? s->chain_cap : 256;
   while (cap < need) cap *= 2;
@@ -536,6 +537,7 @@ int gpemu_sampler_reset(gpemu_sampler *s) {
   if (s->hmc) GP_TRY(hmc_reset(s));
   GP_HIP(hipStreamSynchronize(s->stream));
   s->chain_len = 0;
+  ++s->chain_epoch;
   s->iterations = 0;
   return GPEMU_OK;
 }
@@ -592,6 +594,7 @@ int gpemu_sampler_restore(gpemu_sampler *s) {
   s->rng_ready_until = 0;              // the ring may hold later steps' draws in these slots: generate again
   s->iterations = s->snap_iterations;
   s->chain_len = s->snap_chain_len;    // rows written by the failed attempt are overwritten
+  ++s->chain_epoch;
   return GPEMU_OK;
 }
 

@@ -100,6 +100,8 @@ struct gpemu_sampler {
   double *chain = nullptr;     // [chain_cap][W][d]
   double *lpchain = nullptr;   // [chain_cap][W]
   int64_t chain_cap = 0, chain_len = 0;
+  uint64_t chain_epoch = 0;    // bumped by whatever may move or rewrite the stored chain (a storing run, reserve, reset,
+                               // restore): a gpemu_diag that borrowed the chain before is stale (k_diag.hip)
   // multi-GPU: this rank's slice / the gathered log-probabilities of each half ([per] / [per*world])
   double *gmine[2] = {nullptr, nullptr};
   double *gfull[2] = {nullptr, nullptr};
@@ -141,6 +143,35 @@ struct gpemu_sampler {
 };
 
 namespace gpemu {
+// order-preserving 64-bit key of a double (negative: all bits flipped, else the sign bit set) and its inverse: the
+// radix select (k_postpred.hip) and the radix sort (k_diag.hip)
+typedef unsigned long long u64;
+static __device__ __forceinline__ u64 sel_key(double v) {
+  const u64 u = (u64)__double_as_longlong(v);
+  return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
+}
+static __device__ __forceinline__ double sel_value(u64 key) {
+  const u64 u = (key >> 63) ? (key ^ 0x8000000000000000ull) : ~key;
+  return __longlong_as_double((long long)u);
+}
+// k_acf.hip: per-series sums, means and lag products of a block of series (the kernels' own comments), which
+// k_diag.hip runs on the transformed split chains
+__global__ __launch_bounds__(256) void acf_sum_kernel(const double *__restrict__ chain, int64_t n_t, int64_t S, int64_t ld, int64_t tchunk,
+                               double *__restrict__ part);
+__global__ __launch_bounds__(256) void acf_mean_kernel(const double *__restrict__ part, int64_t n_t, int64_t S, int nchunk,
+                                double *__restrict__ mean);
+__global__ __launch_bounds__(256) void acf_lag_kernel(const double *__restrict__ chain, const double *__restrict__ mean, int64_t n_t, int64_t S,
+                               int64_t ld, int64_t tchunk, int64_t lag0, int n_lags, double *__restrict__ part);
+__global__ __launch_bounds__(256) void acf_reduce_kernel(const double *__restrict__ part, int64_t S, int n_lags, int nchunk,
+                                  double *__restrict__ acf, double *__restrict__ acf0, int is_first);
+constexpr int ACF_LPT = 16;      // lags per thread
+constexpr int ACF_TCHUNKS = 8;   // chunks of steps (partial sums)
+// k_hmc.hip: pooled sums of a flattened chain [R][d] (moments_partial_kernel: MOM_ROWS rows per workgroup)
+constexpr int MOM_ROWS = 1024;
+__global__ __launch_bounds__(256) void moments_partial_kernel(const double *__restrict__ x, int64_t R, int d, const double *__restrict__ mean,
+                                       double *__restrict__ part);
+__global__ __launch_bounds__(256) void moments_final_kernel(const double *__restrict__ part, int64_t nb, int d, int64_t R,
+                                     double *__restrict__ out);
 // k_sampler.hip
 int sampler_launch_rng(gpemu_sampler *s, hipStream_t st, int64_t ahead);
 int sampler_ensure_chain(gpemu_sampler *s, int64_t need);

@@ -150,6 +150,19 @@ _SIGNATURES = {
     "gpemu_sampler_hmc_draws": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gpemu_sampler_chain_moments": (C.c_int, [C.c_void_p, c_i64, c_i64, C.c_void_p, C.c_void_p]),
     "gpemu_hmc_path_counts": (C.c_int, [C.POINTER(c_i64), c_i64]),
+    "gpemu_rank": (C.c_int, [C.c_int, c_i64, c_i64, C.c_void_p, C.c_void_p]),
+    "gpemu_rank_dev": (C.c_int, [C.c_int, c_i64, c_i64, C.c_void_p, c_i64, c_i64, C.c_void_p, c_i64, C.c_void_p]),
+    "gpemu_diag_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_void_p, c_i64, c_i64, C.c_int]),
+    "gpemu_diag_create_dev": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_void_p, c_i64, c_i64, c_i64, c_i64, C.c_int,
+                                        c_i64, C.c_void_p]),
+    "gpemu_sampler_diag_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p, c_i64, c_i64, c_i64, c_i64, c_i64]),
+    "gpemu_diag_transform": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gpemu_diag_range": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gpemu_diag_series": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "gpemu_diag_acov": (C.c_int, [C.c_void_p, c_i64, c_i64, C.c_void_p]),
+    "gpemu_diag_pooled": (C.c_int, [C.c_void_p] + [C.c_void_p] * 5),
+    "gpemu_diag_destroy": (None, [C.c_void_p]),
+    "gpemu_diag_path_counts": (C.c_int, [C.POINTER(c_i64), c_i64]),
 }
 
 

@@ -298,6 +298,26 @@ class DeviceSampler:
         check(_lib.lib().gpemu_sampler_chain_moments(self._h, int(discard), n, ptr(mean), ptr(var)))
         return mean, var
 
+    def diagnostics(self, discard=0, thin=1, chain=None):
+        """Rank-normalised split-R-hat, bulk / tail ESS, the ESS of the mean and its Monte Carlo standard error
+        (``gpemu.diagnostics.summary``; DESIGN.md §4.27) of the stored chain ``get_chain()[discard::thin]``, read in
+        place on the device: a dict of ``(d,)`` arrays plus ``n_chains`` and ``n_draws``.  Every walker counts as a
+        chain.  The walkers of a stretch ensemble are NOT independent chains -- each move uses the other half of the
+        ensemble -- so R-hat here compares walkers with each other, and ``ess_*`` does not replace emcee's integrated
+        autocorrelation time (``integrated_time``) for an ensemble; the chains of an ``HMCSampler`` are independent and
+        the statistics mean what they mean in Stan.  Stacked samplers take ``chain=<index>``."""
+        from .diagnostics import Diag
+        discard, thin = int(discard), int(thin)
+        if thin < 1 or discard < 0:
+            raise ValueError("discard must be >= 0 and thin >= 1")
+        w0, nw = self._chain_walkers(chain)
+        _, _, cl = self.counts()
+        n = (cl - discard + thin - 1) // thin
+        if n < 1:
+            raise ValueError("no stored steps after discard")
+        with Diag.from_sampler(self._h, discard, n, thin, w0, nw, self.d) as h:
+            return h.summary()
+
     def acf_block(self, lag0, n_lags, first=0, n=None, w0=0, nw=None):
         """Walker-averaged normalised autocorrelation function, lags [lag0, lag0 + n_lags), of the chain stored on
         the device: (n_lags, d).  ``lag0`` a multiple of 16, the first block of an estimate at 0."""
@@ -762,6 +782,11 @@ class TemperedSampler(DeviceSampler):
         from .tempering import thermodynamic_integration_log_evidence
         return thermodynamic_integration_log_evidence(self.betas, self.mean_log_likelihood(discard))
 
+    def diagnostics(self, temp=0, discard=0, thin=1):
+        """``DeviceSampler.diagnostics`` of one rung (default: rung 0, the posterior), its walkers as the chains.  They
+        are the walkers of a stretch ensemble that also swaps states with its neighbours: not independent chains."""
+        return DeviceSampler.diagnostics(self, discard=discard, thin=thin, chain=int(temp))
+
     def integrated_time(self, temp=0, first=0, n=None, c=5, tol=50, quiet=False, block=256):
         """emcee's integrated autocorrelation time of rung ``temp``, estimated on the device."""
         Wc = self.walkers_per_chain
@@ -1171,6 +1196,17 @@ class EnsembleSampler:
             if set(kwargs) <= {"c", "tol", "quiet"}:
                 return self._impl.integrated_time(first=int(discard), **kw)
         return thin * integrated_time(self.get_chain(discard=discard, thin=thin), **kwargs)
+
+    def get_diagnostics(self, discard=0, thin=1):
+        """``gpemu.diagnostics.summary`` of ``get_chain(discard=discard, thin=thin)``, every walker as a chain, computed
+        on the device -- in place while the chain still lives there, from the host copy otherwise.  The walkers of the
+        stretch ensemble are not independent chains: R-hat compares walkers, and ``ess_*`` does not replace
+        ``get_autocorr_time`` (emcee's tau)."""
+        discard, thin = int(discard), int(thin)
+        if self._impl is not None and getattr(self, "_device", False) and not self.__dict__.get("_frozen"):
+            return self._impl.diagnostics(discard=discard + thin - 1, thin=thin)
+        from . import diagnostics
+        return diagnostics.summary(np.ascontiguousarray(self.get_chain(discard=discard, thin=thin)))
 
     # -- pickling (ref: mcmc.py:131-132 pickles the sampler) --------------------------------------
     def __getstate__(self):

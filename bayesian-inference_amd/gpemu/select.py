@@ -138,3 +138,45 @@ def quantile(values, probabilities, axis=-1, device=None):
         return out[0] if scalar else out
     out = lerp(sel[ilo], sel[ihi], t.reshape((-1,) + (1,) * (sel.ndim - 1)))
     return out[0] if scalar else out
+
+
+def rankdata(values, axis=-1, device=None, workspace_bytes=0):
+    """``scipy.stats.rankdata(values, method='average', axis=axis)``: the average 1-based rank of every element among
+    those of its slice along ``axis``, exact (gpemu_rank: a key-only radix sort on the device, then the lower and upper
+    bound of every element).  -0 and +0 are tied; a slice that holds a NaN is NaN throughout.  Host arrays give an
+    array, float64 device tensors are read in place and give a tensor on the same device.  ``workspace_bytes`` bounds
+    the sort's buffers for a batch of slices (0: half of the free device memory); the ranks do not depend on it."""
+    if _is_device_tensor(values):
+        import torch
+        if values.dtype != torch.float64:
+            raise TypeError("device ranking needs float64 tensors")
+        v = values.movedim(axis, -1)
+        S = v.shape[-1]
+        lead = v.shape[:-1]
+        R = int(np.prod(lead)) if lead else 1
+        if R == 0 or S == 0:
+            raise ValueError("no elements to rank")
+        flat = v.reshape(R, S)
+        rs = flat.stride(0) if R > 1 else 1
+        es = flat.stride(1) if S > 1 else 1
+        if rs <= 0 or es <= 0:      # expanded (stride 0) tensors
+            flat = flat.contiguous()
+            rs, es = S, 1
+        out = torch.empty((R, S), dtype=torch.float64, device=values.device)
+        stream = torch.cuda.current_stream(values.device).cuda_stream
+        check(_lib.lib().gpemu_rank_dev(int(values.device.index or 0), R, S, C.c_void_p(flat.data_ptr()), int(rs), int(es),
+                                        C.c_void_p(out.data_ptr()), int(workspace_bytes), C.c_void_p(stream)))
+        return out.reshape(*lead, S).movedim(-1, axis)
+    _lib.require_device()
+    v = np.asarray(values, dtype=np.float64)
+    if v.ndim == 0:
+        raise ValueError("values must have at least one axis")
+    v = np.moveaxis(v, axis, -1)
+    S = v.shape[-1]
+    lead = v.shape[:-1]
+    v = np.ascontiguousarray(v).reshape(-1, S)
+    if v.size == 0:
+        raise ValueError("no elements to rank")
+    out = np.empty_like(v)
+    check(_lib.lib().gpemu_rank(int(_lib.resolve_device(device)), v.shape[0], S, ptr(v), ptr(out)))
+    return np.moveaxis(out.reshape(*lead, S), -1, axis)

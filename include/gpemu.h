@@ -596,6 +596,78 @@ enum gpemu_hmc_path {
 /* out[0 .. min(n, GPEMU_HMC_PATH_COUNT)) = the counters; returns GPEMU_HMC_PATH_COUNT (or GPEMU_ERR_ARG). */
 int gpemu_hmc_path_counts(int64_t *out, int64_t n);
 
+/* ---- chain diagnostics: exact ranks, rank-normalised split-Rhat, bulk / tail ESS -----------------------
+ * The convergence statistics of Vehtari, Gelman, Simpson, Carpenter, Buerkner (2021), computed where the chain lies.
+ * The reference's only convergence statistic is emcee's integrated autocorrelation time (ref: mcmc.py:111-119), which
+ * gpemu_sampler_acf covers; these compare chains with each other.
+ *
+ * Ranks: ranks_out[r*S + j] = the average 1-based rank of element j among the S elements of row r, as a double equal
+ * to scipy.stats.rankdata(V[r], 'average')[j].  -0 and +0 are tied; a row that holds a NaN returns NaN everywhere;
+ * +-inf order as usual.  Key-only LSD radix sort of the order-preserving 64-bit keys (eight stable 8-bit passes: per-tile
+ * digit histograms, a scan over (digit, tile), a stable scatter), then the lower and upper bound of every element in
+ * the sorted keys: rank = (lo + hi + 1) / 2.  All counters are integers and the sorted key array is unique: the bits
+ * do not depend on the grid, on the batches or on the run.  R, S >= 1 and S < 2^31, else GPEMU_ERR_ARG.
+ * _dev addresses as gpemu_select_dev does (element j of row r at dV[r*row_stride + j*elem_stride]); dranks is a dense
+ * device array [R][S].  Rows go through the workspace in batches, 16*S + 1024*ceil(S/2048) + 4 bytes per row;
+ * workspace_bytes = 0: half of the free device memory.  If not one row fits: GPEMU_ERR_HIP, sizes in the error text.
+ * stream NULL = the null stream; waits for it before returning. */
+int gpemu_rank(int device, int64_t R, int64_t S, const double *V, double *ranks_out);
+int gpemu_rank_dev(int device, int64_t R, int64_t S, const double *dV, int64_t row_stride, int64_t elem_stride,
+                   double *dranks, int64_t workspace_bytes, void *stream);
+
+/* A segment x[n][M][d] of a chain (n stored steps, M chains or walkers) and its split, transformed series.
+ * N = floor(n / 2) >= 4 (else GPEMU_ERR_ARG); split chain (h, m) is half h of chain m: rows [0, N) and [n - N, n).
+ * _create copies a host chain [n][W][d]; _create_dev borrows walkers [w0, w0 + nw) of a device chain whose steps are
+ * step_stride doubles apart and whose rows are [..][d] (the pointer is to walker 0 of the first step);
+ * gpemu_sampler_diag_create borrows steps first, first + thin, ... (n of them) of the stored chain in place: valid until
+ * the next run that stores, reserve, reset or restore of the sampler, GPEMU_ERR_STATE from every call after that.
+ * Memory: one buffer of n*nw*d doubles (the transformed series Y, or the dense segment while a median or quantile is
+ * selected), the select's and the sort's scratch for a batch of parameters (gpemu_rank_dev's bound with S = 2*N*nw,
+ * within workspace_bytes; 0 = half of the free memory) and the lag-block scratch of gpemu_sampler_acf.
+ *
+ * gpemu_diag_transform writes Y[N][2*nw*d], series (h*nw + w)*d + dd, for one of the kinds below and returns the split
+ * chains' moments, sums in a fixed order (two passes, then a tree): grand_mean[d] = the mean of the 2*nw chain means,
+ * mean_var[d] = W, the mean of the ddof-1 chain variances, var_of_means[d] = b, the ddof-1 variance of the chain means.
+ *   IDENTITY        x
+ *   RANK_Z          normcdfinv((r - 3/8) / (S + 1/4)), r the pooled average rank among the S = 2*N*nw split values
+ *   FOLDED_RANK_Z   the same of |x - median|, the np.median of the pooled unsplit segment (gpemu_select)
+ *   INDICATOR_LE    1[x <= q], q = np.quantile(pooled unsplit segment, prob) as gpemu.select.quantile computes it
+ * gpemu_diag_range: min[d] and max[d] over the current Y (exact); gpemu_diag_series: Y itself, Y_out[N*2*nw*d] on the
+ * host.  gpemu_diag_acov: g_out[l*d + dd] = the mean over the
+ * 2*nw split chains of the biased autocovariance 1/N sum_t c[t] c[t + l], c = y - chain mean, of the current Y, for
+ * lags [lag0, lag0 + n_lags): gpemu_sampler_acf's protocol (lag0 a multiple of 16, n_lags <= min(4096, N), the first
+ * block after a transform at lag 0).  gpemu_diag_pooled: mean, ddof-1 standard deviation, np.median, min and max of the
+ * pooled unsplit segment, [d] each (any may be NULL); a parameter with a NaN gives NaN.  Arguments are checked before
+ * any launch.  The bits depend on (n, nw, d) and the values alone. */
+typedef struct gpemu_diag gpemu_diag;
+#define GPEMU_DIAG_IDENTITY 0
+#define GPEMU_DIAG_RANK_Z 1
+#define GPEMU_DIAG_FOLDED_RANK_Z 2
+#define GPEMU_DIAG_INDICATOR_LE 3
+int gpemu_diag_create(gpemu_diag **out, int device, const double *chain, int64_t n, int64_t W, int d);
+int gpemu_diag_create_dev(gpemu_diag **out, int device, const double *dchain, int64_t n, int64_t step_stride, int64_t w0,
+                          int64_t nw, int d, int64_t workspace_bytes, void *stream);
+int gpemu_sampler_diag_create(gpemu_diag **out, gpemu_sampler *s, int64_t first, int64_t n, int64_t thin, int64_t w0,
+                              int64_t nw);
+int gpemu_diag_transform(gpemu_diag *h, int kind, double prob, double *grand_mean, double *mean_var,
+                         double *var_of_means);
+int gpemu_diag_range(gpemu_diag *h, double *min, double *max);
+int gpemu_diag_series(gpemu_diag *h, double *Y_out);
+int gpemu_diag_acov(gpemu_diag *h, int64_t lag0, int64_t n_lags, double *g_out);
+int gpemu_diag_pooled(gpemu_diag *h, double *mean, double *sd_ddof1, double *median, double *min, double *max);
+void gpemu_diag_destroy(gpemu_diag *h);
+/* Which launches of the diagnostics ran.  A set of its own: the other sets keep their sizes and indices. */
+enum gpemu_diag_path {
+  GPEMU_DIAG_PATH_SORT_PASS = 0,    /* one histogram + scan + scatter pass of the radix sort, for one batch of rows    */
+  GPEMU_DIAG_PATH_RANK_LOOKUP,      /* the lower / upper bound lookup of one batch of rows                            */
+  GPEMU_DIAG_PATH_TRANSFORM,        /* one gpemu_diag_transform                                                       */
+  GPEMU_DIAG_PATH_ACOV_BLOCK,       /* one lag block of gpemu_diag_acov                                               */
+  GPEMU_DIAG_PATH_ROW_BATCH,        /* one batch of rows through the sort's workspace                                 */
+  GPEMU_DIAG_PATH_COUNT
+};
+/* out[0 .. min(n, GPEMU_DIAG_PATH_COUNT)) = the counters; returns GPEMU_DIAG_PATH_COUNT (or GPEMU_ERR_ARG). */
+int gpemu_diag_path_counts(int64_t *out, int64_t n);
+
 /* ---- fit handle: test-only entry points ---------------------------------------------------------------------------
  * For the tests of the fit side only; nothing in the library's own flow calls them.
  * gpemu_fit_workspace: out[N*N] = problem z of the last evaluation (gpemu_fit_lml / _lml_batch / _factor) as the
