@@ -486,6 +486,19 @@ POSTERIOR_PREDICTIVE_PROBABILITIES = (0.05, 0.5, 0.95)
 _PP_VECTORS = ('mean', 'variance_parameters', 'variance_emulator', 'variance')
 
 
+def scatter_feature_rows(sorter, rows) -> np.ndarray:
+    """The groups' per-feature rows ``{group: (R, F_g)}`` in the merged observable order of ``predict``, (R, F):
+    ``convert``'s rule for ``central_value``.  A sorter that has no mapping of its own (a stand-in that only implements
+    ``convert``) converts every matrix as a ``central_value``."""
+    mapping = getattr(sorter, 'emulation_group_to_observable_matrix', None)
+    if mapping is None:
+        return np.asarray(sorter.convert({name: {'central_value': m} for name, m in rows.items()})['central_value'])
+    merged = np.zeros((next(iter(rows.values())).shape[0], sorter.shape[1]))
+    for _, (group_name, slice_out, slice_group) in mapping.items():
+        merged[:, slice_out] = rows[group_name][:, slice_group]
+    return merged
+
+
 def merge_posterior_predictive(sorter, group_results) -> dict[str, np.ndarray]:
     """The groups' posterior-predictive summaries in the merged observable order of ``predict``: every entry is per
     feature, so the merge is a scatter -- ``convert``'s rule for ``central_value``, applied to the (F,) vectors and the
@@ -493,13 +506,7 @@ def merge_posterior_predictive(sorter, group_results) -> dict[str, np.ndarray]:
     implements ``convert``) converts that matrix as a ``central_value``."""
     first = next(iter(group_results.values()))
     rows = {name: np.vstack([g[key] for key in _PP_VECTORS] + [g['quantiles']]) for name, g in group_results.items()}
-    mapping = getattr(sorter, 'emulation_group_to_observable_matrix', None)
-    if mapping is None:
-        merged = np.asarray(sorter.convert({name: {'central_value': m} for name, m in rows.items()})['central_value'])
-    else:
-        merged = np.zeros((len(_PP_VECTORS) + first['quantiles'].shape[0], sorter.shape[1]))
-        for _, (group_name, slice_out, slice_group) in mapping.items():
-            merged[:, slice_out] = rows[group_name][:, slice_group]
+    merged = scatter_feature_rows(sorter, rows)
     out = {key: merged[i].copy() for i, key in enumerate(_PP_VECTORS)}
     out['quantiles'] = merged[len(_PP_VECTORS):].copy()
     out['probabilities'] = np.array(first['probabilities'], dtype=np.float64)
@@ -531,6 +538,54 @@ def posterior_predictive(parameters, emulation_config: "EmulationConfig",
     if not merge_predictions_over_groups:
         return per_group
     return merge_posterior_predictive(emulation_config.sort_observables_in_matrix, per_group)
+
+
+_GS_MATRICES = ('first_order', 'total', 'first_order_se', 'total_se')
+_GS_VECTORS = ('variance', 'mean')
+
+
+def merge_global_sensitivity(sorter, group_results) -> dict[str, Any]:
+    """The groups' Sobol' results in the merged observable order of ``predict``: the (d, F_g) index matrices and the
+    (F_g,) vectors stacked as the rows of one matrix and scattered as ``merge_posterior_predictive`` scatters."""
+    first = next(iter(group_results.values()))
+    d = first['first_order'].shape[0]
+    rows = {name: np.vstack([g[key] for key in _GS_MATRICES] + [g[key][None, :] for key in _GS_VECTORS])
+            for name, g in group_results.items()}
+    merged = scatter_feature_rows(sorter, rows)
+    out = {key: merged[i * d:(i + 1) * d].copy() for i, key in enumerate(_GS_MATRICES)}
+    for i, key in enumerate(_GS_VECTORS):
+        out[key] = merged[len(_GS_MATRICES) * d + i].copy()
+    out['n'], out['n_batches'] = first['n'], first['n_batches']
+    return out
+
+
+def global_sensitivity(emulation_config: "EmulationConfig", n: int = 4096, seed: int = 0, method: str = 'sobol',
+                       box=None, n_batches: int = 16,
+                       emulation_group_results: dict[str, dict[str, Any]] | None = None) -> dict[str, Any]:
+    """Global, variance-based sensitivities of every observable bin over a parameter box: ``first_order`` (d, F), the
+    share of the emulated observable's variance that parameter i explains alone, ``total`` (d, F), its share with all
+    interactions, their batch-means standard errors ``first_order_se`` / ``total_se``, ``variance`` and ``mean`` (F,)
+    of the emulated central value over the box, ``n``, ``n_batches`` and ``parameter_names``, in the observable order
+    of ``predict`` -- the global counterpart of ``sensitivity`` (the reference's only sensitivity is a 10 % forward
+    difference at one point, ref: plot_qhat.py:172-258).  ``box`` = (lo, hi) defaults to the prior box of the
+    parameterisation, the one ``mcmc.run_mcmc`` samples in; a sub-box restricts the analysis.  One pair of base
+    matrices (``gpemu.sensitivity.base_samples``) is shared by all groups; reduced on the device per group
+    (``DeviceModel.sobol_indices``)."""
+    from gpemu import sensitivity as gs
+    par = emulation_config.analysis_config['parameterization'][emulation_config.parameterization]
+    lo, hi = (par['min'], par['max']) if box is None else box
+    A, B = gs.base_samples(n, lo, hi, seed=seed, method=method)
+    emulation_group_results = emulation_group_results or {}
+    per_group = {}
+    for group_name, group_config in emulation_config.emulation_groups_config.items():
+        group_result = emulation_group_results.get(group_name)
+        if group_result is None:
+            group_result = read_emulators(group_config)
+        dm = device_model_for(group_result, group_config.n_pc)
+        per_group[group_name] = dm.sobol_indices(A, B, n_batches=n_batches)
+    out = merge_global_sensitivity(emulation_config.sort_observables_in_matrix, per_group)
+    out['parameter_names'] = [str(name) for name in par['names']]
+    return out
 
 
 def predict_emulation_group(parameters, results, emulation_group_config, emulator_group_cov_unexplained=None):

@@ -163,6 +163,10 @@ _SIGNATURES = {
     "gpemu_diag_pooled": (C.c_int, [C.c_void_p] + [C.c_void_p] * 5),
     "gpemu_diag_destroy": (None, [C.c_void_p]),
     "gpemu_diag_path_counts": (C.c_int, [C.POINTER(c_i64), c_i64]),
+    "gpemu_gp_mean_pick_freeze": (C.c_int, [C.c_void_p, c_i64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gpemu_sobol_moments": (C.c_int, [C.c_void_p, c_i64, C.c_void_p, C.c_void_p, c_i64, c_i64] + [C.c_void_p] * 8),
+    "gpemu_sobol_moments_dev": (C.c_int, [C.c_void_p, c_i64, C.c_void_p, C.c_void_p, c_i64, c_i64] + [C.c_void_p] * 9),
+    "gpemu_sobol_path_counts": (C.c_int, [C.POINTER(c_i64), c_i64]),
 }
 
 

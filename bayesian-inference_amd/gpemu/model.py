@@ -50,6 +50,8 @@ class DeviceModel:
         self._h = h
         self.N, self.d, self.F, self.k, self.device = N, d, F, k, int(device)
         self._lik_key = None
+        # host copies of the back-projection (k F + 2 F doubles): sobol_indices forms its quadratic forms with them
+        self._projection = (components.copy(), scaler_scale.copy(), scaler_mean.copy())
 
     # -- lifetime --------------------------------------------------------------------------
     def close(self):
@@ -226,6 +228,56 @@ class DeviceModel:
             self._h, C.c_void_p(dX_ptr), int(n_blocks), int(block_rows), int(block_stride_rows), int(ranks.size),
             ptr(ranks) if ranks.size else None, int(workspace_bytes), vp(dmean_ptr), vp(dvar_param_ptr), vp(dvar_emu_ptr),
             vp(dorder_ptr), C.c_void_p(stream)))
+
+    # -- global sensitivity ----------------------------------------------------------------
+    def _base_pair(self, A, B):
+        A, B = self._finite(self._X(A)), self._finite(self._X(B))
+        if A.shape != B.shape:
+            raise ValueError(f"A and B must have the same shape, got {A.shape} and {B.shape}")
+        return A, B
+
+    def mean_pick_freeze(self, A, B):
+        """PC means (d + 2, n, k) of the rows of ``A`` (slot 0), of ``B`` (slot 1) and of the pick-freeze rows
+        ``AB_i`` = A with column i from B (slot 2 + i), without K_* or the variance GEMM."""
+        A, B = self._base_pair(A, B)
+        n = A.shape[0]
+        Z = np.empty((self.d + 2, n, self.k))
+        check(_lib.lib().gpemu_gp_mean_pick_freeze(self._h, n, ptr(A), ptr(B), ptr(Z)))
+        return Z
+
+    def sobol_moments(self, A, B, n_batches=16, workspace_bytes=0):
+        """The moments of the pick-freeze PC means per batch of rows (row r in batch ``r * n_batches // n``), about
+        the returned ``pivot`` (k,): a dict with ``count`` (T,), ``sumA``, ``sumB`` (T, k), ``C2`` (T, k, k),
+        ``sumD`` (T, d, k), ``M`` and ``D`` (T, d, k, k) as include/gpemu.h defines them, and ``n``, ``n_batches``.
+        ``workspace_bytes`` caps the chunk of PC means (0: sized from free memory); the result, bit for bit, does not
+        depend on it."""
+        A, B = self._base_pair(A, B)
+        return self._sobol_moments(_lib.lib().gpemu_sobol_moments, A.shape[0], ptr(A), ptr(B), n_batches, workspace_bytes)
+
+    def sobol_moments_dev(self, dA_ptr, dB_ptr, n, n_batches=16, workspace_bytes=0, stream=0):
+        """``sobol_moments`` of base matrices resident on the device (``dA``, ``dB``: n x d doubles); the moments come
+        back to the host.  Works on ``stream`` (0: the model's) and waits for it.  Rows are not checked."""
+        return self._sobol_moments(_lib.lib().gpemu_sobol_moments_dev, int(n), C.c_void_p(dA_ptr), C.c_void_p(dB_ptr),
+                                   n_batches, workspace_bytes, C.c_void_p(stream))
+
+    def _sobol_moments(self, fn, n, A, B, n_batches, workspace_bytes, *tail):
+        T, d, k = int(n_batches), self.d, self.k
+        if not 1 <= T <= n:
+            raise ValueError(f"n_batches must be in 1 .. n = {n}, got {n_batches}")
+        out = {"pivot": np.empty(k), "count": np.empty(T, dtype=np.int64), "sumA": np.empty((T, k)),
+               "sumB": np.empty((T, k)), "C2": np.empty((T, k, k)), "sumD": np.empty((T, d, k)),
+               "M": np.empty((T, d, k, k)), "D": np.empty((T, d, k, k))}
+        check(fn(self._h, n, A, B, T, int(workspace_bytes), ptr(out["pivot"]), ptr(out["count"]), ptr(out["sumA"]),
+                 ptr(out["sumB"]), ptr(out["C2"]), ptr(out["sumD"]), ptr(out["M"]), ptr(out["D"]), *tail))
+        out["n"], out["n_batches"] = n, T
+        return out
+
+    def sobol_indices(self, A, B, n_batches=16, workspace_bytes=0):
+        """First-order and total-effect Sobol' indices of every feature over the rows of ``A`` and ``B``, with
+        batch-means standard errors: ``gpemu.sensitivity.indices_from_moments`` of ``sobol_moments`` with the
+        components and the scaler the model was created with."""
+        from . import sensitivity
+        return sensitivity.indices_from_moments(self.sobol_moments(A, B, n_batches, workspace_bytes), *self._projection)
 
     def likelihood_setup(self, y_exp, y_err, lo, hi, n_div=1.0, block_start=None, cov=None, sys_sources=None):
         """Data, box prior and the observable block boundaries of this group (``block_start`` =

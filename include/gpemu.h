@@ -668,6 +668,56 @@ enum gpemu_diag_path {
 /* out[0 .. min(n, GPEMU_DIAG_PATH_COUNT)) = the counters; returns GPEMU_DIAG_PATH_COUNT (or GPEMU_ERR_ARG). */
 int gpemu_diag_path_counts(int64_t *out, int64_t n);
 
+/* ---- global (Sobol') sensitivity of the emulators ----------------------------------------------------
+ * The variance-based counterpart of the local sensitivities the reference takes by a 10 % forward difference at one
+ * point (ref: plot_qhat.py:172-258; the analytic Jacobian: gpemu_gp_predict_grad): over base matrices A, B [n*d]
+ * (rows in the prior box) the pick-freeze rows AB_i = A with column i from B.
+ *
+ * gpemu_gp_mean_pick_freeze: Z_out[(d+2)*n*k] = the PC means (ref: emulation.py:494-499, the mean of
+ * GaussianProcessRegressor.predict) of the rows of A (slot 0), of B (slot 1) and of AB_0 .. AB_(d-1) (slots 2 ..),
+ * Z_out[(slot*n + r)*k + p].  K_* is never stored and the variance GEMM is not run.
+ *
+ * gpemu_sobol_moments: row r belongs to batch floor(r*n_batches / n).  Per batch t, about the pivot c (returned: the
+ * mean of z over the first min(n, 1024) rows of A and of B), with zA, zB the means of the batch's rows and
+ * D_i = z(AB_i) - z(A):
+ *   count[T]        rows of the batch
+ *   sumA, sumB[T*k] sum (zA - c), sum (zB - c)
+ *   C2[T*k*k]       sum (zA - c)(zA - c)^T + sum (zB - c)(zB - c)^T
+ *   sumD[T*d*k]     per i: sum D_i
+ *   M[T*d*k*k]      per i: sum (zB - c) D_i^T       (Saltelli et al. 2010: the first-order index)
+ *   D[T*d*k*k]      per i: sum D_i D_i^T            (Jansen 1999: the total-effect index)
+ * from which gpemu.sensitivity.indices_from_moments forms the indices of every feature as k x k quadratic forms (the
+ * back-projection is linear, ref: emulation.py:516-548: no n x F array exists).  Every sum runs over slices of the
+ * rows fixed by n and n_batches and is added in a fixed order, no floating-point atomics: the results, bit for bit, do
+ * not depend on workspace_bytes or on the run.  workspace_bytes bounds the chunk of PC means, 8*(d+2)*k bytes per row
+ * (0: half of the free device memory; at least one slice of min(n, 256) rows, else GPEMU_ERR_HIP); the per-slice
+ * partial sums are allocated beside it.  n >= 1, 1 <= n_batches <= n, a model with d <= 16 and k <= 64, else
+ * GPEMU_ERR_ARG; the host forms refuse non-finite rows (GPEMU_ERR_ARG) before any launch.
+ * _dev: dA, dB are device arrays, the outputs HOST arrays; works on `stream` (NULL = the model's) and waits for it. */
+int gpemu_gp_mean_pick_freeze(gpemu_model *m, int64_t n, const double *A, const double *B, double *Z_out);
+int gpemu_sobol_moments(gpemu_model *m, int64_t n, const double *A, const double *B, int64_t n_batches,
+                        int64_t workspace_bytes, double *pivot, int64_t *count, double *sumA, double *sumB, double *C2,
+                        double *sumD, double *M, double *D);
+int gpemu_sobol_moments_dev(gpemu_model *m, int64_t n, const double *dA, const double *dB, int64_t n_batches,
+                            int64_t workspace_bytes, double *pivot, int64_t *count, double *sumA, double *sumB,
+                            double *C2, double *sumD, double *M, double *D, void *stream);
+/* Which launches of the two ran.  A set of its own: the other sets keep their sizes and indices. */
+enum gpemu_sobol_path {
+  GPEMU_SOBOL_PATH_CALL = 0,   /* one gpemu_sobol_moments[_dev]                                                       */
+  GPEMU_SOBOL_PATH_CHUNK,      /* one chunk of rows through the workspace                                             */
+  GPEMU_SOBOL_PATH_WHOLE,      /* a call whose rows all fitted one chunk                                              */
+  GPEMU_SOBOL_PATH_DP8,        /* a launch of the mean kernel, 8-wide instance (d <= 8)                               */
+  GPEMU_SOBOL_PATH_DP16,       /* ... 16-wide instance (9 <= d <= 16)                                                 */
+  GPEMU_SOBOL_PATH_KIND0,      /* ... by base kernel: RBF / nu = inf, then Matern 0.5, 1.5, 2.5, general nu           */
+  GPEMU_SOBOL_PATH_KIND1,
+  GPEMU_SOBOL_PATH_KIND2,
+  GPEMU_SOBOL_PATH_KIND3,
+  GPEMU_SOBOL_PATH_KIND4,
+  GPEMU_SOBOL_PATH_COUNT
+};
+/* out[0 .. min(n, GPEMU_SOBOL_PATH_COUNT)) = the counters; returns GPEMU_SOBOL_PATH_COUNT (or GPEMU_ERR_ARG). */
+int gpemu_sobol_path_counts(int64_t *out, int64_t n);
+
 /* ---- fit handle: test-only entry points ---------------------------------------------------------------------------
  * For the tests of the fit side only; nothing in the library's own flow calls them.
  * gpemu_fit_workspace: out[N*N] = problem z of the last evaluation (gpemu_fit_lml / _lml_batch / _factor) as the
