@@ -204,6 +204,8 @@ def _run_closure_batch(config, indices):
     for c in range(n_ch):           # where the chain lies: before the sampler goes
         part = {}
         _add_diagnostics(config, part, lambda c=c: sampler.diagnostics(chain=c), label=f'closure chain {indices[c]}')
+        _add_marginals(config, part, lambda c=c, **kw: sampler.marginals(chain=c, **kw),
+                       label=f'closure chain {indices[c]}')
         diags.append(part)
     sampler.close()
 
@@ -331,6 +333,7 @@ def run_mcmc(config, closure_index=-1):
     results = {'chain': sampler.get_chain(), 'acceptance_fraction': sampler.acceptance_fraction,
                'log_prob': sampler.get_log_prob(), 'autocorrelation_time': tau}
     _add_diagnostics(config, results, sampler.get_diagnostics)
+    _add_marginals(config, results, sampler.get_marginals)
     if closure_index >= 0:
         validation_design = io.design_array_from_h5(config.output_dir, filename='observables.h5', validation_set=True)
         results['design_point'] = validation_design[closure_index]
@@ -456,6 +459,7 @@ def _run_tempered(config, closure_index):
         tau = None
     diag = {}
     _add_diagnostics(config, diag, lambda: sampler.diagnostics(temp=0), label='production chain (beta = 1)')
+    _add_marginals(config, diag, lambda **kw: sampler.marginals(temp=0, **kw), label='production chain (beta = 1)')
     mean_ll = sampler.mean_log_likelihood()
     log_z, dlog_z = sampler.log_evidence_estimate()
     swap_frac = sampler.tswap_acceptance_fraction
@@ -564,6 +568,7 @@ def _run_hmc(config, closure_index):
         tau = None
     diag = {}
     _add_diagnostics(config, diag, sampler.diagnostics)
+    _add_marginals(config, diag, sampler.marginals)
     step_size, inverse_metric, divergences = sampler.step_size, sampler.inverse_metric, sampler.divergences
     sampler.close()
 
@@ -660,6 +665,88 @@ def diagnostics(config, closure_index=-1, discard=0, thin=1):
         raise ValueError("no stored steps after discard")
     from gpemu import diagnostics as _diag
     return _diag.summary(chain)
+
+
+def marginals_settings(mc, default_confidence=None):
+    """``(on, (bins_1d, bins_2d), confidence, kde)`` from the ``parameters.mcmc`` mapping: ``marginals`` (true or false,
+    default off) and the optional ``marginals_bins`` (``[bins_1d, bins_2d]``, default 100 and 50),
+    ``marginals_confidence`` (a list of levels in (0, 1); default ``[default_confidence]`` -- the configuration's
+    ``confidence``, if it has one -- else 0.9) and ``marginals_kde`` (true or false, default on).  DESIGN.md §4.29."""
+    on = mc.get('marginals', False)
+    if not isinstance(on, (bool, np.bool_)):
+        raise ValueError(f"parameters.mcmc.marginals must be true or false, got {on!r}")
+    kde = mc.get('marginals_kde', True)
+    if not isinstance(kde, (bool, np.bool_)):
+        raise ValueError(f"parameters.mcmc.marginals_kde must be true or false, got {kde!r}")
+    bins = mc.get('marginals_bins', (100, 50))
+    ok = isinstance(bins, (list, tuple)) and len(bins) == 2 and all(
+        isinstance(b, (int, np.integer)) and not isinstance(b, (bool, np.bool_)) for b in bins)
+    if not ok or not (1 <= bins[0] <= 4096 and 1 <= bins[1] <= 256):
+        raise ValueError("parameters.mcmc.marginals_bins must be [bins_1d, bins_2d], integers in [1, 4096] and [1, 256], "
+                         f"got {bins!r}")
+    conf = mc.get('marginals_confidence')
+    if conf is None:
+        conf = [0.9 if default_confidence is None else default_confidence]
+    try:
+        ok = isinstance(conf, (list, tuple)) and len(conf) > 0 and all(
+            not isinstance(c, (bool, np.bool_)) and 0.0 < float(c) < 1.0 for c in conf)
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError(f"parameters.mcmc.marginals_confidence must be a list of levels in (0, 1), got {conf!r}")
+    return bool(on), (int(bins[0]), int(bins[1])), tuple(float(c) for c in conf), bool(kde)
+
+
+MARGINALS_KEYS = ('edges_1d', 'edges_2d', 'hist_1d', 'pairs', 'hist_2d', 'n_inside', 'confidence', 'hpd')
+MARGINALS_KDE_KEYS = ('kde_grid', 'kde_density', 'kde_bandwidth')
+
+
+def _marginals_kwargs(config):
+    """The arguments of ``DeviceSampler.marginals`` / ``gpemu.marginals.summary`` from the configuration: the prior box
+    of the parameterization and the ``marginals_*`` settings."""
+    box = config.analysis_config['parameterization'][config.parameterization]
+    return dict(lower=np.asarray(box['min'], dtype=np.float64), upper=np.asarray(box['max'], dtype=np.float64),
+                bins_1d=config.marginals_bins[0], bins_2d=config.marginals_bins[1],
+                confidence=config.marginals_confidence, kde=config.marginals_kde)
+
+
+def _add_marginals(config, results, compute, label='production chain'):
+    """With ``parameters.mcmc.marginals``: ``marginal_<key>`` for the keys of ``compute(**kwargs)`` (a sampler's
+    ``marginals`` on the chain where it lies) into the results that go to mcmc.h5 -- histogram counts as int64, the
+    rest float64 -- and one log line."""
+    if not getattr(config, 'marginals', False):
+        return
+    keys = MARGINALS_KEYS + (MARGINALS_KDE_KEYS if config.marginals_kde else ())
+    try:
+        out = compute(**_marginals_kwargs(config))
+    except ValueError as err:        # e.g. too few stored samples for a level: the chain is written either way (a
+        # device failure is not caught: it ends the run)
+        logger.warning(f'parameters.mcmc.marginals: not computed ({err!r}); mcmc.h5 is written without '
+                       + ', '.join(f'marginal_{k}' for k in keys))
+        return
+    for key in keys:
+        results[f'marginal_{key}'] = np.asarray(out[key])
+    n = int(np.asarray(results['marginal_n_inside']).max(initial=0))
+    logger.info(f"Marginals of the {label}: {out['hist_1d'].shape[1]} / {out['hist_2d'].shape[-1]}^2 bins, "
+                f"{out['pairs'].shape[0]} pairs, HPD at {list(config.marginals_confidence)}, up to {n} samples in "
+                "the box")
+
+
+def marginals(config, closure_index=-1, discard=0, thin=1):
+    """The marginals (``gpemu.marginals.summary``) of the chain stored in mcmc.h5 (of closure chain ``closure_index``,
+    if >= 0), steps ``[discard::thin]``, all walkers, with the configuration's box and ``marginals_*`` settings."""
+    if closure_index >= 0:
+        config = MCMCConfig(analysis_name=config.analysis_name, parameterization=config.parameterization,
+                            analysis_config=config.analysis_config, config_file=config.config_file,
+                            closure_index=closure_index)
+    if int(discard) < 0 or int(thin) < 1:
+        raise ValueError("discard must be >= 0 and thin >= 1")
+    stored = _data_IO().read_dict_from_h5(config.mcmc_output_dir, 'mcmc.h5')
+    chain = np.asarray(stored['chain'], dtype=np.float64)[int(discard)::int(thin)]
+    if chain.shape[0] == 0:
+        raise ValueError("no stored steps after discard")
+    from gpemu import marginals as _marg
+    return _marg.summary(np.ascontiguousarray(chain.reshape(-1, chain.shape[-1])), **_marginals_kwargs(config))
 
 
 POSTERIOR_PREDICTIVE_KEYS = ('mean', 'variance_parameters', 'variance_emulator', 'quantiles', 'probabilities')
@@ -874,6 +961,10 @@ class MCMCConfig:
         # convergence diagnostics of the production chain (optional, default off): rhat, ess_bulk, ess_tail, ess_mean and
         # mcse_mean in mcmc.h5, none without the key
         self.diagnostics = diagnostics_settings(mc)
+        # the data of a corner plot from the whole production chain (optional, default off): marginal_* in mcmc.h5,
+        # none without the key
+        self.marginals, self.marginals_bins, self.marginals_confidence, self.marginals_kde = marginals_settings(
+            mc, getattr(self, 'confidence', None))
 
         # <output_dir>/<analysis>_<parameterization>[/closure/results/<index>]/{mcmc.h5, mcmc_sampler.pkl}
         self.output_dir = os.path.join(top['output_dir'], f'{analysis_name}_{parameterization}')

@@ -1,0 +1,658 @@
+// Marginal posteriors of a stored chain (gpemu_marginal_hist*, gpemu_hpd*, gpemu_kde1d*): the data of a
+// corner plot from every sample, where the chain lies.
+//
+// Histograms (mh_*): one sweep of mh_hist_kernel over the rows fills, per workgroup, private 16-bit counters in LDS --
+// two to a 32-bit word, advanced by LDS integer atomics of 1 or 1 << 16; a workgroup takes at most MH_MAX_ROWS < 2^16
+// rows, so a counter cannot carry into its neighbour -- for the 1-D histograms of parameters [a0, a1) and the 2-D
+// histograms of pairs [p0, p1).  A thread owns a row: its d doubles are loaded once, every bin index is found once
+// (guessed from the affine map of the box, then walked to the bin whose edges hold the value: numpy's rule, on the
+// edges themselves) and shared by all pairs of the sweep.  Non-zero counters go to the 64-bit outputs with global
+// integer atomics.  The host plans the sweeps: floor(cap / nb2^2) pairs each, the 1-D counters beside the last group
+// where they fit, else in sweeps of their own.  Every counter is an integer: nothing depends on the grid, on the plan
+// or on the run.
+//
+// Highest-density intervals (hpd_*): the rows are sorted by sort_dev.h's radix sort in batches; hpd_window_kernel takes,
+// for every (row, level, chunk of HW_PER windows), the lexicographic minimum of (s[S - n + i] - s[i], i), and
+// hpd_finish_kernel that of a (row, level)'s chunks: the narrowest window, the smallest i among ties (np.argmin).
+//
+// Kernel density (kde_*): workgroup (chunk of KD_CHUNK samples, tile of 256 GPT grid points, row).  A thread keeps GPT
+// grid points in registers; the samples go through LDS in stages of KD_STAGE and sample j of the chunk is added to sum
+// j mod 4 of every grid point, so the order of every sum is fixed by the sample index.  kde_sum_kernel adds a grid
+// point's chunk sums: lane-strided in chunk order, then a butterfly and the waves in order.  A term whose exponent is
+// below -746 is exactly 0 in fp64 and is not evaluated.
+#include <algorithm>
+#include <cmath>
+#include <vector>
+
+#include "internal.h"
+#include "sampler_internal.h"
+#include "sort_dev.h"
+
+namespace gpemu {
+
+constexpr int MH_THREADS = 1024;
+constexpr int64_t MH_CAP = 73728;        // 16-bit counters of a sweep: 144 KiB of LDS
+constexpr int64_t MH_MAX_ROWS = 65280;   // rows per workgroup, < 2^16: a 16-bit counter cannot overflow
+constexpr int MH_MAX_D = 16;
+constexpr int HW_PER = 4096;             // windows per workgroup of the window search
+constexpr int KD_CHUNK = 8192;           // samples per partial sum
+constexpr int KD_STAGE = 1024;           // samples staged in LDS at a time
+constexpr int KD_MAX_GPT = 4;            // grid points per thread: tiles of up to 1024 grid points
+constexpr int64_t KD_PART_BYTES = 256ll << 20;   // chunk sums of a batch of rows, about
+
+static inline void marginal_path_count(int path) { count_path(PATHS_MARGINAL, path); }   // enum gpemu_marginal_path
+
+// ---- histograms ----------------------------------------------------------------------------------------------------
+struct HistArgs {
+  const double *X;
+  int64_t S, block_rows, block_stride_rows, rows_per_wg;
+  const double *e1, *e2;           // [d][nb1 + 1], [d][nb2 + 1]
+  int d, nb1, nb2;
+  int a0, a1, p0, p1;              // this sweep: 1-D histograms of parameters [a0, a1), pairs [p0, p1)
+  int i0, j0;                      // pair p0 = (i0, j0)
+  unsigned long long *hist1, *hist2;
+};
+
+// the bin b with e[b] <= x < e[b + 1], the last one closed on the right; -1 outside [e[0], e[nb]] and for NaN.
+// tab = {e[0], e[nb], nb / (e[nb] - e[0])}
+static __device__ __forceinline__ int mh_bin(double x, const double *__restrict__ e, int nb, const double *tab) {
+  const double e0 = tab[0], eN = tab[1];
+  if (!(x >= e0 && x <= eN)) return -1;
+  double t = (x - e0) * tab[2];
+  t = fmin(fmax(t, 0.0), (double)(nb - 1));   // a NaN guess (an infinite span) starts at 0
+  int b = (int)t;
+  while (b > 0 && x < e[b]) --b;
+  while (b < nb - 1 && x >= e[b + 1]) ++b;
+  return b;
+}
+
+static __device__ __forceinline__ void mh_count(unsigned *lds, int c) { atomicAdd(&lds[c >> 1], 1u << ((c & 1) << 4)); }
+
+template <int DP>
+__global__ __launch_bounds__(MH_THREADS) void mh_hist_kernel(HistArgs a) {
+  extern __shared__ unsigned mh_lds[];           // the 16-bit counters, two per word: 1-D section, then the pairs
+  __shared__ double tab[2][MH_MAX_D][3];
+  const int tid = threadIdx.x;
+  const int d = a.d, nb1 = a.nb1, nb2 = a.nb2, nb2sq = nb2 * nb2;
+  const int n1 = (a.a1 - a.a0) * nb1, ncnt = n1 + (a.p1 - a.p0) * nb2sq, nwords = (ncnt + 1) >> 1;
+  for (int w = tid; w < nwords; w += MH_THREADS) mh_lds[w] = 0;
+  if (tid < 2 * d) {
+    const int which = tid / d, k = tid % d, nb = which ? nb2 : nb1;
+    const double *e = (which ? a.e2 : a.e1) + (int64_t)k * (nb + 1);
+    tab[which][k][0] = e[0];
+    tab[which][k][1] = e[nb];
+    tab[which][k][2] = (double)nb / (e[nb] - e[0]);
+  }
+  __syncthreads();
+  const int64_t r0 = (int64_t)blockIdx.x * a.rows_per_wg, r1 = (r0 + a.rows_per_wg < a.S) ? r0 + a.rows_per_wg : a.S;
+  for (int64_t r = r0 + tid; r < r1; r += MH_THREADS) {
+    const double *row = a.X + ((r / a.block_rows) * a.block_stride_rows + r % a.block_rows) * d;
+    int b2[DP];
+#pragma unroll 1
+    for (int k = 0; k < d; ++k) {   // (k is the same for every lane: b2 stays in registers)
+      const double xv = row[k];
+      if (k >= a.a0 && k < a.a1) {
+        const int b = mh_bin(xv, a.e1 + (int64_t)k * (nb1 + 1), nb1, tab[0][k]);
+        if (b >= 0) mh_count(mh_lds, (k - a.a0) * nb1 + b);
+      }
+      if (a.p1 > a.p0) b2[k] = mh_bin(xv, a.e2 + (int64_t)k * (nb2 + 1), nb2, tab[1][k]);
+    }
+    if (a.p1 > a.p0) {
+      int i = a.i0, j = a.j0, off = n1;   // pair p0 = (i0, j0), then row-major: the index is the same for every lane
+#pragma unroll 1
+      for (int p = a.p0; p < a.p1; ++p) {
+        const int bi = b2[i], bj = b2[j];
+        if (bi >= 0 && bj >= 0) mh_count(mh_lds, off + bi * nb2 + bj);
+        off += nb2sq;
+        if (++j == d) {
+          ++i;
+          j = i + 1;
+        }
+      }
+    }
+  }
+  __syncthreads();
+  unsigned long long *g1 = a.hist1 + (int64_t)a.a0 * nb1, *g2 = a.hist2 + (int64_t)a.p0 * nb2sq;
+  for (int w = tid; w < nwords; w += MH_THREADS) {
+    const unsigned v = mh_lds[w];
+    if (!v) continue;
+#pragma unroll
+    for (int half = 0; half < 2; ++half) {
+      const int c = 2 * w + half;
+      const unsigned cnt = (v >> (16 * half)) & 0xffffu;
+      if (cnt && c < ncnt) atomicAdd(c < n1 ? &g1[c] : &g2[c - n1], (unsigned long long)cnt);
+    }
+  }
+}
+
+// n_inside[j] = the sum of hist1[j][.]; workgroup j
+__global__ __launch_bounds__(256) void mh_inside_kernel(const unsigned long long *__restrict__ hist1, int nb1,
+                                                        unsigned long long *__restrict__ n_inside) {
+  __shared__ unsigned long long red[256];
+  const int tid = threadIdx.x;
+  unsigned long long s = 0;
+  for (int b = tid; b < nb1; b += 256) s += hist1[(int64_t)blockIdx.x * nb1 + b];
+  red[tid] = s;
+  __syncthreads();
+  for (int off = 128; off > 0; off >>= 1) {
+    if (tid < off) red[tid] += red[tid + off];
+    __syncthreads();
+  }
+  if (tid == 0) n_inside[blockIdx.x] = red[0];
+}
+
+// logical rows of the block layout -> dst[S][d]
+__global__ __launch_bounds__(256) void mh_dense_kernel(const double *__restrict__ X, int64_t block_rows,
+                                                       int64_t block_stride_rows, int d, int64_t S,
+                                                       double *__restrict__ dst) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= S * d) return;
+  const int64_t r = i / d;
+  dst[i] = X[((r / block_rows) * block_stride_rows + r % block_rows) * d + i % d];
+}
+
+struct HistSweep { int a0, a1, p0, p1; };
+
+// the sweeps of one call (the file's header); cap: 16-bit counters per sweep
+static std::vector<HistSweep> hist_plan(int d, int nb1, int nb2, int64_t cap) {
+  std::vector<HistSweep> plan;
+  const int np = d * (d - 1) / 2;
+  const int64_t sq = (int64_t)nb2 * nb2, ppg = cap / sq, dpg = cap / nb1;
+  for (int p0 = 0; p0 < np; p0 += (int)ppg) plan.push_back({0, 0, p0, (int)std::min<int64_t>(np, p0 + ppg)});
+  int a = 0;
+  if (!plan.empty()) {   // beside the last group of pairs, as many parameters as fit
+    HistSweep &last = plan.back();
+    a = (int)std::min<int64_t>(d, (cap - (last.p1 - last.p0) * sq) / nb1);
+    last.a1 = a;
+  }
+  for (; a < d; a += (int)dpg) plan.push_back({a, (int)std::min<int64_t>(d, a + dpg), 0, 0});
+  return plan;
+}
+
+static int marginal_device_ready(int device) {
+  int n = 0;
+  if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) {
+    set_error("no HIP device available: libgpemu has no CPU implementation");
+    return GPEMU_ERR_NO_DEVICE;
+  }
+  GP_ARG(device >= 0 && device < n, "device out of range");
+  GP_HIP(hipSetDevice(device));
+  return GPEMU_OK;
+}
+
+static int edges_check(const double *e, int d, int nb) {
+  for (int k = 0; k < d; ++k)
+    for (int b = 0; b <= nb; ++b) {
+      const double v = e[(int64_t)k * (nb + 1) + b];
+      GP_ARG(std::isfinite(v), "bin edges must be finite");
+      GP_ARG(b == 0 || v > e[(int64_t)k * (nb + 1) + b - 1], "bin edges must be strictly increasing");
+    }
+  return GPEMU_OK;
+}
+
+static int block_check(int64_t n_blocks, int64_t block_rows, int64_t block_stride_rows) {
+  GP_ARG(n_blocks > 0 && block_rows > 0, "n_blocks and block_rows must be positive");
+  GP_ARG(n_blocks == 1 || block_stride_rows >= block_rows, "block_stride_rows must be >= block_rows");
+  GP_ARG(n_blocks <= ((1ll << 31) - 1) / block_rows, "S = n_blocks * block_rows must be below 2^31");
+  return GPEMU_OK;
+}
+
+static int hist_check(int d, int nb1, const double *edges1, int nb2, const double *edges2, int64_t group_counters,
+                      const void *hist1, const void *hist2, const void *n_inside1) {
+  GP_ARG(d >= 1 && d <= MH_MAX_D, "d must be in [1, 16]");
+  GP_ARG(nb1 >= 1 && nb1 <= 4096, "nb1 must be in [1, 4096]");
+  GP_ARG(nb2 >= 1 && nb2 <= 256, "nb2 must be in [1, 256]");
+  GP_ARG(edges1 && edges2 && hist1 && n_inside1 && (hist2 || d == 1), "null pointer");
+  GP_ARG(group_counters == 0 || (group_counters >= std::max<int64_t>(nb1, (int64_t)nb2 * nb2) && group_counters <= MH_CAP),
+         "group_counters must be 0 or in [max(nb1, nb2^2), 73728]");
+  GP_TRY(edges_check(edges1, d, nb1));
+  GP_TRY(edges_check(edges2, d, nb2));
+  return GPEMU_OK;
+}
+
+// the sweeps over device rows; asynchronous on st but for the edges' upload, which the scope outlives: waits for st
+static int hist_rows(const double *dX, int64_t n_blocks, int64_t block_rows, int64_t block_stride_rows, int d, int nb1,
+                     const double *edges1, int nb2, const double *edges2, int64_t group_counters, int64_t *dhist1,
+                     int64_t *dhist2, int64_t *dn_inside1, hipStream_t st) {
+  const int64_t S = n_blocks * block_rows, np = d * (d - 1) / 2;
+  const std::vector<HistSweep> plan = hist_plan(d, nb1, nb2, group_counters ? group_counters : MH_CAP);
+  DevScope sc(st);
+  double *de1 = nullptr, *de2 = nullptr;
+  GP_TRY(sc.alloc(&de1, (int64_t)d * (nb1 + 1)));
+  GP_TRY(sc.alloc(&de2, (int64_t)d * (nb2 + 1)));
+  GP_TRY(upload(de1, edges1, (int64_t)d * (nb1 + 1), st));
+  GP_TRY(upload(de2, edges2, (int64_t)d * (nb2 + 1), st));
+  GP_HIP(hipMemsetAsync(dhist1, 0, sizeof(int64_t) * (size_t)d * nb1, st));
+  if (np > 0) GP_HIP(hipMemsetAsync(dhist2, 0, sizeof(int64_t) * (size_t)np * nb2 * nb2, st));
+  HistArgs a;
+  a.X = dX; a.S = S; a.block_rows = block_rows; a.block_stride_rows = block_stride_rows;
+  a.rows_per_wg = std::min<int64_t>(MH_MAX_ROWS, std::max<int64_t>(4096, round_up((S + 1023) / 1024, 256)));
+  a.e1 = de1; a.e2 = de2; a.d = d; a.nb1 = nb1; a.nb2 = nb2;
+  a.hist1 = (unsigned long long *)dhist1; a.hist2 = (unsigned long long *)dhist2;
+  const unsigned nwg = (unsigned)((S + a.rows_per_wg - 1) / a.rows_per_wg);
+  const void *fn = d <= 8 ? (const void *)mh_hist_kernel<8> : (const void *)mh_hist_kernel<16>;
+  GP_TRY(allow_dynamic_lds(fn, (int)(2 * MH_CAP + 16)));
+  for (const HistSweep &sw : plan) {
+    a.a0 = sw.a0; a.a1 = sw.a1; a.p0 = sw.p0; a.p1 = sw.p1;
+    int i0 = 0, rem = sw.p0;   // row i of the pair list holds d - 1 - i pairs
+    while (i0 < d - 1 && rem >= d - 1 - i0) rem -= d - 1 - i0++;
+    a.i0 = i0; a.j0 = i0 + 1 + rem;
+    const int64_t ncnt = (int64_t)(sw.a1 - sw.a0) * nb1 + (int64_t)(sw.p1 - sw.p0) * nb2 * nb2;
+    const size_t lds = (size_t)round_up(2 * ncnt + 2, 16);
+    marginal_path_count(GPEMU_MARGINAL_PATH_HIST_SWEEP);
+    if (sw.p1 > sw.p0) marginal_path_count(GPEMU_MARGINAL_PATH_PAIR_GROUP);
+    if (d <= 8)
+      hipLaunchKernelGGL(mh_hist_kernel<8>, dim3(nwg), dim3(MH_THREADS), lds, st, a);
+    else
+      hipLaunchKernelGGL(mh_hist_kernel<16>, dim3(nwg), dim3(MH_THREADS), lds, st, a);
+    GP_HIP(hipGetLastError());
+  }
+  hipLaunchKernelGGL(mh_inside_kernel, dim3((unsigned)d), dim3(256), 0, st, (const unsigned long long *)dhist1, nb1,
+                     (unsigned long long *)dn_inside1);
+  GP_HIP(hipGetLastError());
+  GP_HIP(hipStreamSynchronize(st));
+  return GPEMU_OK;
+}
+
+// ---- highest-density intervals ---------------------------------------------------------------------------------------
+// is (w, i) before (bw, bi) in the lexicographic order?
+static __device__ __forceinline__ bool hpd_before(double w, long long i, double bw, long long bi) {
+  return w < bw || (w == bw && i < bi);
+}
+
+// the lexicographic minimum over the workgroup, valid in thread 0
+static __device__ __forceinline__ void hpd_wg_min(double &w, long long &i, double *sw, long long *si) {
+  const int tid = threadIdx.x;
+  sw[tid] = w;
+  si[tid] = i;
+  __syncthreads();
+  for (int off = 128; off > 0; off >>= 1) {
+    if (tid < off && hpd_before(sw[tid + off], si[tid + off], sw[tid], si[tid])) {
+      sw[tid] = sw[tid + off];
+      si[tid] = si[tid + off];
+    }
+    __syncthreads();
+  }
+  w = sw[0];
+  i = si[0];
+}
+
+// pw / pi[(rl L + l) nchunk + c] = the minimum of (s[S - n + i] - s[i], i) over the windows i of chunk c, i < n = n_out[l]
+__global__ __launch_bounds__(256) void hpd_window_kernel(const u64 *__restrict__ sorted, int64_t S, int n_levels,
+                                                         const int64_t *__restrict__ n_out, int64_t nchunk,
+                                                         double *__restrict__ pw, long long *__restrict__ pi) {
+  __shared__ double sw[256];
+  __shared__ long long si[256];
+  const int64_t c = blockIdx.x % nchunk, rl_l = blockIdx.x / nchunk, rl = rl_l / n_levels;
+  const int64_t n = n_out[rl_l % n_levels];
+  const u64 *k = sorted + rl * S;
+  double bw = INFINITY;
+  long long bi = 0x7fffffffffffffffll;
+#pragma unroll 4
+  for (int j = 0; j < HW_PER / 256; ++j) {
+    const int64_t i = c * HW_PER + (int64_t)j * 256 + threadIdx.x;
+    if (i < n) {
+      const double w = sel_value(k[S - n + i]) - sel_value(k[i]);
+      if (hpd_before(w, i, bw, bi)) { bw = w; bi = i; }
+    }
+  }
+  hpd_wg_min(bw, bi, sw, si);
+  if (threadIdx.x == 0) {
+    pw[blockIdx.x] = bw;
+    pi[blockIdx.x] = bi;
+  }
+}
+
+// out[((row0 + rl) L + l) 2 + {0, 1}] = the ends of the narrowest window; workgroup (rl, l)
+__global__ __launch_bounds__(256) void hpd_finish_kernel(const u64 *__restrict__ sorted, int64_t S, int n_levels,
+                                                         const int64_t *__restrict__ n_out, int64_t nchunk,
+                                                         const double *__restrict__ pw, const long long *__restrict__ pi,
+                                                         const int *__restrict__ nan, int64_t row0,
+                                                         double *__restrict__ out) {
+  __shared__ double sw[256];
+  __shared__ long long si[256];
+  const int64_t rl = blockIdx.x / n_levels;
+  const int64_t n = n_out[blockIdx.x % n_levels];
+  double bw = INFINITY;
+  long long bi = 0x7fffffffffffffffll;
+  for (int64_t c = threadIdx.x; c < nchunk; c += 256) {
+    const double w = pw[(int64_t)blockIdx.x * nchunk + c];
+    const long long i = pi[(int64_t)blockIdx.x * nchunk + c];
+    if (hpd_before(w, i, bw, bi)) { bw = w; bi = i; }
+  }
+  hpd_wg_min(bw, bi, sw, si);
+  if (threadIdx.x == 0) {
+    const u64 *k = sorted + rl * S;
+    const double smin = sel_value(k[0]), smax = sel_value(k[S - 1]);
+    double lo = __longlong_as_double(0x7ff8000000000000ll), hi = lo;
+    // (a chunk's sentinel index survives only where every width is a NaN: a row with an infinite end)
+    if (!nan[rl] && !isinf(smin) && !isinf(smax) && bi >= 0 && bi < n) {
+      lo = sel_value(k[bi]);
+      hi = sel_value(k[S - n + bi]);
+    }
+    double *o = out + ((row0 + rl) * n_levels + blockIdx.x % n_levels) * 2;
+    o[0] = lo;
+    o[1] = hi;
+  }
+}
+
+static int hpd_check(int64_t R, int64_t S, int64_t n_levels, const int64_t *n_out) {
+  GP_ARG(R > 0, "R must be positive");
+  GP_ARG(S > 0 && S < (1ll << 31), "S must be in [1, 2^31)");
+  GP_ARG(n_levels > 0 && n_levels <= 4096 && n_out, "n_levels must be in [1, 4096]");
+  for (int64_t l = 0; l < n_levels; ++l) GP_ARG(n_out[l] >= 1 && n_out[l] <= S, "every n_out must be in [1, S]");
+  return GPEMU_OK;
+}
+
+// the intervals of R rows, in batches of rows that fit workspace_bytes (0: half of the free memory); waits for st
+static int hpd_rows(const double *dV, int64_t R, int64_t S, int64_t row_stride, int64_t elem_stride, int64_t n_levels,
+                    const int64_t *n_out, double *dout, int64_t workspace_bytes, hipStream_t st) {
+  int64_t budget = workspace_bytes;
+  if (budget == 0) {
+    size_t fb = 0, tb = 0;
+    GP_HIP(hipMemGetInfo(&fb, &tb));
+    budget = (int64_t)(fb / 2);
+  }
+  const int64_t n_max = *std::max_element(n_out, n_out + n_levels), nchunk = (n_max + HW_PER - 1) / HW_PER;
+  const int64_t ntiles = (S + RK_TILE - 1) / RK_TILE, nblk = (S + 255) / 256;
+  const int64_t per_row = rank_row_bytes(S) + 16 * n_levels * nchunk;
+  int64_t rows_cap = std::min<int64_t>(R, budget / per_row);
+  rows_cap = std::min<int64_t>(rows_cap, (int64_t)0x7fffffff / nblk);   // the grids are (rows, blocks) flattened
+  rows_cap = std::min<int64_t>(rows_cap, (int64_t)0x7fffffff / (n_levels * nchunk));
+  if (rows_cap < 1) {
+    set_error("hpd: out of memory: one row of %lld elements and %lld levels needs %lld bytes of sort and window buffers; "
+              "%lld bytes %s", (long long)S, (long long)n_levels, (long long)per_row, (long long)budget,
+              workspace_bytes ? "allowed by workspace_bytes" : "available (half of the free device memory)");
+    return GPEMU_ERR_HIP;
+  }
+  DevScope sc(st);
+  u64 *ka = nullptr, *kb = nullptr;
+  unsigned *hist = nullptr;
+  int *nan = nullptr;
+  int64_t *dn = nullptr;
+  double *pw = nullptr;
+  long long *pi = nullptr;
+  GP_TRY(sc.alloc(&ka, rows_cap * S));
+  GP_TRY(sc.alloc(&kb, rows_cap * S));
+  GP_TRY(sc.alloc(&hist, rows_cap * RK_BINS * ntiles));
+  GP_TRY(sc.alloc(&nan, rows_cap));
+  GP_TRY(sc.alloc(&dn, n_levels));
+  GP_TRY(sc.alloc(&pw, rows_cap * n_levels * nchunk));
+  GP_TRY(sc.alloc(&pi, rows_cap * n_levels * nchunk));
+  GP_TRY(upload(dn, n_out, n_levels, st));
+  for (int64_t row0 = 0; row0 < R; row0 += rows_cap) {
+    const int64_t rows = std::min(rows_cap, R - row0);
+    marginal_path_count(GPEMU_MARGINAL_PATH_SORT_BATCH);
+    GP_TRY(sort_rows(dV, row_stride, elem_stride, S, row0, rows, ka, kb, hist, nan, [] {}, st));
+    marginal_path_count(GPEMU_MARGINAL_PATH_WINDOW_SEARCH);
+    hipLaunchKernelGGL(hpd_window_kernel, dim3((unsigned)(rows * n_levels * nchunk)), dim3(256), 0, st, ka, S, (int)n_levels,
+                       dn, nchunk, pw, pi);
+    GP_HIP(hipGetLastError());
+    hipLaunchKernelGGL(hpd_finish_kernel, dim3((unsigned)(rows * n_levels)), dim3(256), 0, st, ka, S, (int)n_levels, dn,
+                       nchunk, pw, pi, nan, row0, dout);
+    GP_HIP(hipGetLastError());
+  }
+  GP_HIP(hipStreamSynchronize(st));   // n_out is read by the copy above
+  return GPEMU_OK;
+}
+
+// ---- kernel density ------------------------------------------------------------------------------------------------
+// part[((rl G) + g) nchunk + c] = sum over the samples j of chunk c of exp(-((grid[r][g] - x_rj) inv_h[r])^2 / 2);
+// workgroup (c, tile, rl)
+template <int GPT>
+__global__ __launch_bounds__(256) void kde_partial_kernel(const double *__restrict__ V, int64_t row_stride,
+                                                          int64_t elem_stride, int64_t S, int64_t row0,
+                                                          const double *__restrict__ grid,
+                                                          const double *__restrict__ inv_h, int64_t G, int64_t nchunk,
+                                                          double *__restrict__ part) {
+  __shared__ double xs[KD_STAGE];
+  const int tid = threadIdx.x;
+  const int64_t c = blockIdx.x, rl = blockIdx.z, r = row0 + rl;
+  const double ih = inv_h[r];
+  const double *x = V + r * row_stride;
+  double g[GPT], acc[GPT][4];
+#pragma unroll
+  for (int k = 0; k < GPT; ++k) {
+    const int64_t gi = ((int64_t)blockIdx.y * GPT + k) * 256 + tid;
+    g[k] = gi < G ? grid[r * G + gi] : 0.0;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) acc[k][q] = 0.0;
+  }
+  const int64_t j0 = c * KD_CHUNK, j1 = (j0 + KD_CHUNK < S) ? j0 + KD_CHUNK : S;
+  for (int64_t s0 = j0; s0 < j1; s0 += KD_STAGE) {
+    const int n = (int)((j1 - s0 < KD_STAGE) ? j1 - s0 : KD_STAGE);
+    __syncthreads();
+    for (int t = tid; t < n; t += 256) xs[t] = x[(s0 + t) * elem_stride];
+    __syncthreads();
+    for (int t = 0; t < n; t += 4) {
+#pragma unroll
+      for (int q = 0; q < 4; ++q)
+        if (t + q < n) {
+          const double xv = xs[t + q];
+#pragma unroll
+          for (int k = 0; k < GPT; ++k) {
+            const double u = (g[k] - xv) * ih;
+            const double e = -0.5 * (u * u);
+            if (e > -746.0) acc[k][q] += exp(e);   // below: exactly 0 in fp64
+          }
+        }
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < GPT; ++k) {
+    const int64_t gi = ((int64_t)blockIdx.y * GPT + k) * 256 + tid;
+    if (gi < G) part[(rl * G + gi) * nchunk + c] = (acc[k][0] + acc[k][1]) + (acc[k][2] + acc[k][3]);
+  }
+}
+
+// dens[(row0 + rl) G + g] = norm[row0 + rl] * the sum of the grid point's chunk sums; workgroup (rl, g)
+__global__ __launch_bounds__(256) void kde_sum_kernel(const double *__restrict__ part, int64_t nchunk, int64_t G,
+                                                      int64_t row0, const double *__restrict__ norm,
+                                                      double *__restrict__ dens) {
+  __shared__ double ws[4];
+  const int tid = threadIdx.x;
+  const double *p = part + (int64_t)blockIdx.x * nchunk;
+  double a = 0.0;
+  for (int64_t c = tid; c < nchunk; c += 256) a += p[c];
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) a += __shfl_xor(a, off, 64);
+  if ((tid & 63) == 0) ws[tid >> 6] = a;
+  __syncthreads();
+  if (tid == 0) {
+    const int64_t rl = blockIdx.x / G, g = blockIdx.x % G;
+    dens[(row0 + rl) * G + g] = (((ws[0] + ws[1]) + ws[2]) + ws[3]) * norm[row0 + rl];
+  }
+}
+
+static int kde_check(int64_t R, int64_t S, int64_t G, const double *grid, const double *h) {
+  GP_ARG(R > 0 && S > 0 && G > 0, "R, S and G must be positive");
+  GP_ARG(grid && h, "null pointer");
+  GP_ARG(R <= ((1ll << 31) - 1) / G, "R * G must be below 2^31");
+  for (int64_t r = 0; r < R; ++r) GP_ARG(std::isfinite(h[r]) && h[r] > 0.0, "every bandwidth must be finite and > 0");
+  for (int64_t i = 0; i < R * G; ++i) GP_ARG(std::isfinite(grid[i]), "grid points must be finite");
+  return GPEMU_OK;
+}
+
+static int kde_rows(const double *dV, int64_t R, int64_t S, int64_t row_stride, int64_t elem_stride, int64_t G,
+                    const double *grid, const double *h, double *ddens, hipStream_t st) {
+  const int64_t nchunk = (S + KD_CHUNK - 1) / KD_CHUNK;
+  const int gpt = G <= 256 ? 1 : (G <= 512 ? 2 : KD_MAX_GPT);
+  const int64_t ntile = (G + 256 * gpt - 1) / (256 * gpt);
+  GP_ARG(ntile <= 65535, "G must be at most 65535 * 1024");
+  int64_t rows_cap = std::max<int64_t>(1, KD_PART_BYTES / (8 * G * nchunk));
+  rows_cap = std::min<int64_t>(std::min<int64_t>(rows_cap, R), 65535);
+  rows_cap = std::min<int64_t>(rows_cap, std::max<int64_t>(1, (int64_t)0x7fffffff / G));
+  std::vector<double> ih((size_t)R), norm((size_t)R);
+  for (int64_t r = 0; r < R; ++r) {
+    ih[(size_t)r] = 1.0 / h[r];
+    norm[(size_t)r] = 1.0 / ((double)S * h[r] * std::sqrt(2.0 * M_PI));
+  }
+  DevScope sc(st);
+  double *dgrid = nullptr, *dih = nullptr, *dnorm = nullptr, *part = nullptr;
+  GP_TRY(sc.alloc(&dgrid, R * G));
+  GP_TRY(sc.alloc(&dih, R));
+  GP_TRY(sc.alloc(&dnorm, R));
+  GP_TRY(sc.alloc(&part, rows_cap * G * nchunk));
+  GP_TRY(upload(dgrid, grid, R * G, st));
+  GP_TRY(upload(dih, ih.data(), R, st));
+  GP_TRY(upload(dnorm, norm.data(), R, st));
+  for (int64_t row0 = 0; row0 < R; row0 += rows_cap) {
+    const int64_t rows = std::min(rows_cap, R - row0);
+    marginal_path_count(GPEMU_MARGINAL_PATH_KDE);
+    const dim3 gr((unsigned)nchunk, (unsigned)ntile, (unsigned)rows);
+    if (gpt == 1)
+      hipLaunchKernelGGL(kde_partial_kernel<1>, gr, dim3(256), 0, st, dV, row_stride, elem_stride, S, row0, dgrid, dih, G,
+                         nchunk, part);
+    else if (gpt == 2)
+      hipLaunchKernelGGL(kde_partial_kernel<2>, gr, dim3(256), 0, st, dV, row_stride, elem_stride, S, row0, dgrid, dih, G,
+                         nchunk, part);
+    else
+      hipLaunchKernelGGL(kde_partial_kernel<KD_MAX_GPT>, gr, dim3(256), 0, st, dV, row_stride, elem_stride, S, row0, dgrid,
+                         dih, G, nchunk, part);
+    hipLaunchKernelGGL(kde_sum_kernel, dim3((unsigned)(rows * G)), dim3(256), 0, st, part, nchunk, G, row0, dnorm, ddens);
+    GP_HIP(hipGetLastError());
+  }
+  GP_HIP(hipStreamSynchronize(st));   // ih and norm are read by the copies above
+  return GPEMU_OK;
+}
+
+}  // namespace gpemu
+
+using namespace gpemu;
+
+extern "C" {
+
+int gpemu_marginal_path_counts(int64_t *out, int64_t n) { return read_path_counts(PATHS_MARGINAL, out, n); }
+
+int gpemu_marginal_hist_dev(int device, const double *dX, int64_t n_blocks, int64_t block_rows,
+                            int64_t block_stride_rows, int d, int nb1, const double *edges1, int nb2,
+                            const double *edges2, int64_t group_counters, int64_t *dhist1, int64_t *dhist2,
+                            int64_t *dn_inside1, void *stream) {
+  GP_ARG(dX, "null pointer");
+  GP_TRY(block_check(n_blocks, block_rows, block_stride_rows));
+  GP_TRY(hist_check(d, nb1, edges1, nb2, edges2, group_counters, dhist1, dhist2, dn_inside1));
+  GP_TRY(marginal_device_ready(device));
+  return hist_rows(dX, n_blocks, block_rows, block_stride_rows, d, nb1, edges1, nb2, edges2, group_counters, dhist1, dhist2,
+                   dn_inside1, (hipStream_t)stream);
+}
+
+int gpemu_marginal_hist(int device, int64_t S, int d, const double *X, int nb1, const double *edges1, int nb2,
+                        const double *edges2, int64_t group_counters, int64_t *hist1, int64_t *hist2,
+                        int64_t *n_inside1) {
+  GP_ARG(X, "null pointer");
+  GP_ARG(S > 0 && S < (1ll << 31), "S must be in [1, 2^31)");
+  GP_TRY(hist_check(d, nb1, edges1, nb2, edges2, group_counters, hist1, hist2, n_inside1));
+  GP_TRY(marginal_device_ready(device));
+  hipStream_t st = nullptr;
+  const int64_t np = d * (d - 1) / 2, n2 = np * nb2 * nb2;
+  DevScope sc(st);
+  double *dX = nullptr;
+  int64_t *dh1 = nullptr, *dh2 = nullptr, *dni = nullptr;
+  GP_TRY(sc.alloc(&dX, S * d));
+  GP_TRY(sc.alloc(&dh1, (int64_t)d * nb1));
+  GP_TRY(sc.alloc(&dh2, n2));
+  GP_TRY(sc.alloc(&dni, d));
+  GP_TRY(upload(dX, X, S * d, st));
+  GP_TRY(hist_rows(dX, 1, S, S, d, nb1, edges1, nb2, edges2, group_counters, dh1, dh2, dni, st));
+  GP_TRY(sc.download(hist1, dh1, (int64_t)d * nb1));
+  if (n2 > 0) GP_TRY(sc.download(hist2, dh2, n2));
+  GP_TRY(sc.download(n_inside1, dni, d));
+  GP_HIP(hipStreamSynchronize(st));
+  return GPEMU_OK;
+}
+
+int gpemu_hpd_dev(int device, int64_t R, int64_t S, const double *dV, int64_t row_stride, int64_t elem_stride,
+                  int64_t n_levels, const int64_t *n_out, double *dout, int64_t workspace_bytes, void *stream) {
+  GP_ARG(dV && dout, "null pointer");
+  GP_TRY(hpd_check(R, S, n_levels, n_out));
+  GP_ARG(row_stride > 0 && elem_stride > 0, "strides must be positive");
+  GP_ARG(workspace_bytes >= 0, "workspace_bytes must be >= 0");
+  GP_TRY(marginal_device_ready(device));
+  return hpd_rows(dV, R, S, row_stride, elem_stride, n_levels, n_out, dout, workspace_bytes, (hipStream_t)stream);
+}
+
+int gpemu_hpd(int device, int64_t R, int64_t S, const double *V, int64_t n_levels, const int64_t *n_out, double *out) {
+  GP_ARG(V && out, "null pointer");
+  GP_TRY(hpd_check(R, S, n_levels, n_out));
+  GP_ARG(R <= INT64_MAX / 8 / S, "R * S overflows");
+  GP_TRY(marginal_device_ready(device));
+  hipStream_t st = nullptr;
+  DevScope sc(st);
+  double *dV = nullptr, *dout = nullptr;
+  GP_TRY(sc.alloc(&dV, R * S));
+  GP_TRY(sc.alloc(&dout, R * n_levels * 2));
+  GP_TRY(upload(dV, V, R * S, st));
+  GP_TRY(hpd_rows(dV, R, S, S, 1, n_levels, n_out, dout, 0, st));
+  GP_TRY(sc.download(out, dout, R * n_levels * 2));
+  GP_HIP(hipStreamSynchronize(st));
+  return GPEMU_OK;
+}
+
+int gpemu_kde1d_dev(int device, int64_t R, int64_t S, const double *dV, int64_t row_stride, int64_t elem_stride,
+                    int64_t G, const double *grid, const double *h, double *ddens, void *stream) {
+  GP_ARG(dV && ddens, "null pointer");
+  GP_TRY(kde_check(R, S, G, grid, h));
+  GP_ARG(row_stride > 0 && elem_stride > 0, "strides must be positive");
+  GP_TRY(marginal_device_ready(device));
+  return kde_rows(dV, R, S, row_stride, elem_stride, G, grid, h, ddens, (hipStream_t)stream);
+}
+
+int gpemu_kde1d(int device, int64_t R, int64_t S, const double *V, int64_t G, const double *grid, const double *h,
+                double *dens) {
+  GP_ARG(V && dens, "null pointer");
+  GP_TRY(kde_check(R, S, G, grid, h));
+  GP_ARG(R <= INT64_MAX / 8 / S, "R * S overflows");
+  GP_TRY(marginal_device_ready(device));
+  hipStream_t st = nullptr;
+  DevScope sc(st);
+  double *dV = nullptr, *dd = nullptr;
+  GP_TRY(sc.alloc(&dV, R * S));
+  GP_TRY(sc.alloc(&dd, R * G));
+  GP_TRY(upload(dV, V, R * S, st));
+  GP_TRY(kde_rows(dV, R, S, S, 1, G, grid, h, dd, st));
+  GP_TRY(sc.download(dens, dd, R * G));
+  GP_HIP(hipStreamSynchronize(st));
+  return GPEMU_OK;
+}
+
+int gpemu_marginal_dense_dev(int device, const double *dX, int64_t n_blocks, int64_t block_rows,
+                             int64_t block_stride_rows, int d, double *ddense, void *stream) {
+  GP_ARG(dX && ddense, "null pointer");
+  GP_TRY(block_check(n_blocks, block_rows, block_stride_rows));
+  GP_ARG(d >= 1 && d <= MH_MAX_D, "d must be in [1, 16]");
+  GP_TRY(marginal_device_ready(device));
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t S = n_blocks * block_rows;
+  hipLaunchKernelGGL(mh_dense_kernel, dim3((unsigned)((S * d + 255) / 256)), dim3(256), 0, st, dX, block_rows,
+                     block_stride_rows, d, S, ddense);
+  GP_HIP(hipGetLastError());
+  GP_HIP(hipStreamSynchronize(st));
+  return GPEMU_OK;
+}
+
+int gpemu_marginal_moments_dev(int device, const double *dX, int64_t S, int d, double *mean, double *var, void *stream) {
+  GP_ARG(dX && mean && var, "null pointer");
+  GP_ARG(S > 0 && S < (1ll << 31), "S must be in [1, 2^31)");
+  GP_ARG(d >= 1 && d <= MH_MAX_D, "d must be in [1, 16]");
+  GP_TRY(marginal_device_ready(device));
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t nb = (S + MOM_ROWS - 1) / MOM_ROWS;
+  DevScope sc(st);
+  double *dpart = nullptr, *dmom = nullptr;
+  GP_TRY(sc.alloc(&dpart, nb * d));
+  GP_TRY(sc.alloc(&dmom, 2 * d));
+  hipLaunchKernelGGL(moments_partial_kernel, dim3((unsigned)nb), dim3(256), 0, st, dX, S, d, (const double *)nullptr, dpart);
+  GP_HIP(hipGetLastError());
+  hipLaunchKernelGGL(moments_final_kernel, dim3((unsigned)d), dim3(256), 0, st, dpart, nb, d, S, dmom);
+  GP_HIP(hipGetLastError());
+  hipLaunchKernelGGL(moments_partial_kernel, dim3((unsigned)nb), dim3(256), 0, st, dX, S, d, (const double *)dmom, dpart);
+  GP_HIP(hipGetLastError());
+  hipLaunchKernelGGL(moments_final_kernel, dim3((unsigned)d), dim3(256), 0, st, dpart, nb, d, S, dmom + d);
+  GP_HIP(hipGetLastError());
+  GP_TRY(sc.download(mean, dmom, d));
+  GP_TRY(sc.download(var, dmom + d, d));
+  GP_HIP(hipStreamSynchronize(st));
+  return GPEMU_OK;
+}
+
+}  // extern "C"

@@ -167,6 +167,19 @@ _SIGNATURES = {
     "gpemu_sobol_moments": (C.c_int, [C.c_void_p, c_i64, C.c_void_p, C.c_void_p, c_i64, c_i64] + [C.c_void_p] * 8),
     "gpemu_sobol_moments_dev": (C.c_int, [C.c_void_p, c_i64, C.c_void_p, C.c_void_p, c_i64, c_i64] + [C.c_void_p] * 9),
     "gpemu_sobol_path_counts": (C.c_int, [C.POINTER(c_i64), c_i64]),
+    "gpemu_marginal_hist": (C.c_int, [C.c_int, c_i64, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, c_i64,
+                                      C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gpemu_marginal_hist_dev": (C.c_int, [C.c_int, C.c_void_p, c_i64, c_i64, c_i64, C.c_int, C.c_int, C.c_void_p, C.c_int,
+                                          C.c_void_p, c_i64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gpemu_hpd": (C.c_int, [C.c_int, c_i64, c_i64, C.c_void_p, c_i64, C.c_void_p, C.c_void_p]),
+    "gpemu_hpd_dev": (C.c_int, [C.c_int, c_i64, c_i64, C.c_void_p, c_i64, c_i64, c_i64, C.c_void_p, C.c_void_p, c_i64,
+                                C.c_void_p]),
+    "gpemu_kde1d": (C.c_int, [C.c_int, c_i64, c_i64, C.c_void_p, c_i64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gpemu_kde1d_dev": (C.c_int, [C.c_int, c_i64, c_i64, C.c_void_p, c_i64, c_i64, c_i64, C.c_void_p, C.c_void_p,
+                                  C.c_void_p, C.c_void_p]),
+    "gpemu_marginal_dense_dev": (C.c_int, [C.c_int, C.c_void_p, c_i64, c_i64, c_i64, C.c_int, C.c_void_p, C.c_void_p]),
+    "gpemu_marginal_moments_dev": (C.c_int, [C.c_int, C.c_void_p, c_i64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gpemu_marginal_path_counts": (C.c_int, [C.POINTER(c_i64), c_i64]),
 }
 
 

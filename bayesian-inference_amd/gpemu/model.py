@@ -50,6 +50,7 @@ class DeviceModel:
         self._h = h
         self.N, self.d, self.F, self.k, self.device = N, d, F, k, int(device)
         self._lik_key = None
+        self.prior_box = None            # (lo, hi) of the last likelihood_setup
         # host copies of the back-projection (k F + 2 F doubles): sobol_indices forms its quadratic forms with them
         self._projection = (components.copy(), scaler_scale.copy(), scaler_mean.copy())
 
@@ -303,6 +304,7 @@ class DeviceModel:
             check(_lib.lib().gpemu_likelihood_setup(self._h, ptr(y_exp), ptr(y_err), ptr(lo), ptr(hi),
                                                     float(n_div), nb, ptr(bs)))
             self._lik_key = (float(n_div), None if bs is None else tuple(bs.tolist()))
+            self.prior_box = (lo.copy(), hi.copy())
             return
         n_chains = y_exp.shape[0] if y_exp.ndim == 2 else 1
         y_exp = as_f64(y_exp.reshape(n_chains, -1), (n_chains, self.F))
@@ -325,6 +327,7 @@ class DeviceModel:
                                                     ptr(src) if S > 0 else None, ptr(lo), ptr(hi), float(n_div), nb,
                                                     ptr(bs)))
         self._lik_key = (float(n_div), None if bs is None else tuple(bs.tolist()))
+        self.prior_box = (lo.copy(), hi.copy())
 
     def _likelihood_setup_chains(self, y_exp, y_err, lo, hi, n_div, block_start):
         n_chains = y_exp.shape[0]
@@ -339,6 +342,7 @@ class DeviceModel:
         check(_lib.lib().gpemu_likelihood_setup_chains(self._h, int(n_chains), ptr(y_exp), ptr(y_err), ptr(lo), ptr(hi),
                                                        float(n_div), nb, ptr(bs)))
         self._lik_key = (float(n_div), None if bs is None else tuple(bs.tolist()))
+        self.prior_box = (lo.copy(), hi.copy())
 
     def logpost(self, X, mode=LOWRANK):
         X = self._X(X)

@@ -318,6 +318,59 @@ class DeviceSampler:
         with Diag.from_sampler(self._h, discard, n, thin, w0, nw, self.d) as h:
             return h.summary()
 
+    def marginals(self, lower=None, upper=None, bins_1d=100, bins_2d=50, confidence=(0.9,), kde=True, n_grid=200,
+                  discard=0, thin=1, chain=None):
+        """Marginal histograms, highest-density intervals and kernel densities (``gpemu.marginals.summary``; DESIGN.md
+        §4.29) of the stored chain ``get_chain()[discard::thin].reshape(-1, d)``, taken where it lies: one dict with
+        ``edges_1d``, ``edges_2d``, ``hist_1d``, ``pairs``, ``hist_2d``, ``n_inside``, ``confidence``, ``hpd (n_levels,
+        d, 2)`` and, with ``kde``, ``kde_grid``, ``kde_density``, ``kde_bandwidth``.  The box defaults to the prior box
+        of the sampler's models.  The histograms read the chain in place, thinned or stacked; the sort and the density
+        read one parameter as one stride, so a thinned chain or one chain of a stacked sampler is first copied to a
+        dense device buffer.  Stacked samplers take ``chain=<index>``."""
+        import torch
+        from . import marginals as M
+        discard, thin = int(discard), int(thin)
+        if thin < 1 or discard < 0:
+            raise ValueError("discard must be >= 0 and thin >= 1")
+        if lower is None or upper is None:
+            box = getattr(self.models[0], "prior_box", None)
+            if box is None:
+                raise ValueError("no prior box is known (likelihood_setup has not been called): pass lower and upper")
+            lower, upper = (box[0] if lower is None else lower), (box[1] if upper is None else upper)
+        if not (1 <= int(bins_1d) <= M.MAX_BINS_1D and 1 <= int(bins_2d) <= M.MAX_BINS_2D):
+            raise ValueError(f"bins_1d must be in [1, {M.MAX_BINS_1D}] and bins_2d in [1, {M.MAX_BINS_2D}]")
+        e1, e2 = M.bin_edges(lower, upper, bins_1d), M.bin_edges(lower, upper, bins_2d)
+        if e1.shape[0] != self.d:
+            raise ValueError(f"the box has {e1.shape[0]} parameters, the sampler {self.d}")
+        w0, nw = self._chain_walkers(chain)
+        base, n = self.chain_ptr(discard)
+        if n < 1:
+            raise ValueError("no stored steps after discard")
+        n_blocks = (n + thin - 1) // thin
+        S, d = n_blocks * nw, self.d
+        conf = np.atleast_1d(np.asarray(confidence, dtype=np.float64))
+        n_out = M.n_outside(conf, S)
+        src = base + 8 * w0 * d
+        h1, h2, ni = M._hist_dev(self.device, src, n_blocks, nw, thin * self.W, d, e1, e2)
+        hist = {"edges_1d": e1, "edges_2d": e2, "hist_1d": h1, "pairs": M.pair_indices(d), "hist_2d": h2, "n_inside": ni}
+        dense = None
+        if thin > 1 or nw != self.W:
+            dense = torch.empty((S, d), dtype=torch.float64, device=torch.device("cuda", self.device))
+            check(_lib.lib().gpemu_marginal_dense_dev(self.device, C.c_void_p(src), n_blocks, nw, thin * self.W, d,
+                                                      C.c_void_p(dense.data_ptr()), M._stream(self.device)))
+            src = dense.data_ptr()
+        # one sort serves the intervals and, as the level n_out = 1 (window 0: smallest, largest), the density's support
+        ends = M._hpd_dev(self.device, src, S, d, np.append(n_out, 1) if kde else n_out)
+        dens = None
+        if kde:
+            def spread():
+                _, var = M._moments_dev(self.device, src, S, d)
+                return np.sqrt(var * (S / max(S - 1.0, 1.0))), ends[-1, :, 0], ends[-1, :, 1]
+            h, g = M._kde_plan(S, d, None, None, n_grid, 3.0, spread)
+            dens = {"grid": g, "density": M._kde_dev(self.device, src, S, d, g, h), "bandwidth": h}
+        del dense
+        return M.assemble(hist, conf, ends[:n_out.size], dens)
+
     def acf_block(self, lag0, n_lags, first=0, n=None, w0=0, nw=None):
         """Walker-averaged normalised autocorrelation function, lags [lag0, lag0 + n_lags), of the chain stored on
         the device: (n_lags, d).  ``lag0`` a multiple of 16, the first block of an estimate at 0."""
@@ -787,6 +840,10 @@ class TemperedSampler(DeviceSampler):
         are the walkers of a stretch ensemble that also swaps states with its neighbours: not independent chains."""
         return DeviceSampler.diagnostics(self, discard=discard, thin=thin, chain=int(temp))
 
+    def marginals(self, temp=0, **kw):
+        """``DeviceSampler.marginals`` of one rung (default: rung 0, the posterior)."""
+        return DeviceSampler.marginals(self, chain=int(temp), **kw)
+
     def integrated_time(self, temp=0, first=0, n=None, c=5, tol=50, quiet=False, block=256):
         """emcee's integrated autocorrelation time of rung ``temp``, estimated on the device."""
         Wc = self.walkers_per_chain
@@ -1207,6 +1264,19 @@ class EnsembleSampler:
             return self._impl.diagnostics(discard=discard + thin - 1, thin=thin)
         from . import diagnostics
         return diagnostics.summary(np.ascontiguousarray(self.get_chain(discard=discard, thin=thin)))
+
+    def get_marginals(self, discard=0, thin=1, **kw):
+        """``gpemu.marginals.summary`` of ``get_chain(discard=discard, thin=thin, flat=True)`` (``lower``, ``upper``,
+        ``bins_1d``, ``bins_2d``, ``confidence``, ``kde``, ``n_grid``), computed on the device -- in place while the chain
+        still lives there (the box defaults to the prior box), from the host copy otherwise (``lower`` and ``upper``
+        are then required)."""
+        discard, thin = int(discard), int(thin)
+        if self._impl is not None and getattr(self, "_device", False) and not self.__dict__.get("_frozen"):
+            return self._impl.marginals(discard=discard + thin - 1, thin=thin, **kw)
+        from . import marginals
+        if kw.get("lower") is None or kw.get("upper") is None:
+            raise ValueError("the chain is on the host: pass lower and upper")
+        return marginals.summary(np.ascontiguousarray(self.get_chain(discard=discard, thin=thin, flat=True)), **kw)
 
     # -- pickling (ref: mcmc.py:131-132 pickles the sampler) --------------------------------------
     def __getstate__(self):

@@ -718,6 +718,84 @@ enum gpemu_sobol_path {
 /* out[0 .. min(n, GPEMU_SOBOL_PATH_COUNT)) = the counters; returns GPEMU_SOBOL_PATH_COUNT (or GPEMU_ERR_ARG). */
 int gpemu_sobol_path_counts(int64_t *out, int64_t n);
 
+/* ---- marginal posteriors: histograms, highest-density intervals, kernel density ----------------------
+ * The data of a corner plot from the WHOLE chain, where it lies: what ref: plot_mcmc.py _plot_posterior_pairplot draws
+ * from a subsample (a Gaussian KDE of every parameter, every pair of parameters, the shaded highest-density interval)
+ * and the narrowest-window rule of ref: mcmc.py:150-158 (credible_interval, interval_type 'hpd').
+ *
+ * Histograms: over the S rows of X[S*d], 1 <= d <= 16,
+ *   hist1[d*nb1]           hist1[j*nb1 + b] = the rows with edges1[j][b] <= x_j < edges1[j][b+1], the last bin closed on
+ *                          the right: np.histogram(x[:, j], bins=edges1[j])
+ *   hist2[n_pairs*nb2*nb2] for the pairs (i, j), i < j, in row-major order, [pair][bin of x_i][bin of x_j]:
+ *                          np.histogram2d(x[:, i], x[:, j], bins=[edges2[i], edges2[j]]); NULL allowed for d = 1
+ *   n_inside1[d]           the rows counted in hist1[j]
+ * edges1[d*(nb1+1)] and edges2[d*(nb2+1)] are HOST arrays in both forms, every row finite and strictly increasing (else
+ * GPEMU_ERR_ARG).  The bin is guessed from (x - e0) / (eN - e0) * nb and corrected against the edges themselves, so a
+ * value on an edge is counted as numpy counts it; rows outside [e0, eN] and NaN are not counted; -0 = +0.  One sweep
+ * over the rows fills, per workgroup, private 16-bit counters in LDS (two to a word, LDS integer atomics; a workgroup
+ * takes at most 65280 rows, so no counter overflows) for a group of pairs and, where they fit beside the last group,
+ * the 1-D histograms; a row's d doubles are loaded once per sweep and every bin index is found once.  Non-zero counters
+ * are added to the 64-bit outputs with global integer atomics.  Sweeps: ceil(n_pairs / floor(group_counters / nb2^2)),
+ * plus one where the d*nb1 1-D counters do not fit beside the last group (and d = 1: one).  group_counters = 0: 73728
+ * (144 KiB); otherwise max(nb1, nb2^2) <= group_counters <= 73728.  Counters are integers: the result does not depend
+ * on the grid, on group_counters or on the run.  1 <= nb1 <= 4096, 1 <= nb2 <= 256, 1 <= S < 2^31, else GPEMU_ERR_ARG,
+ * before any launch.
+ * _dev: row r is read at dX + ((r / block_rows)*block_stride_rows + r % block_rows)*d, S = n_blocks*block_rows, as
+ * gpemu_posterior_predictive_dev; the outputs are device arrays.
+ *
+ * Highest-density intervals: with s the sorted row r of V[R*S] and, per level l, n_out[l] in [1, S] points left outside,
+ *   i* = the smallest i in [0, n_out) that minimises s[S - n_out + i] - s[i] (the difference rounded as a double),
+ *   out[(r*n_levels + l)*2 + {0, 1}] = s[i*], s[S - n_out + i*]
+ * -- elements of the input (a zero may come back as +0).  A row that holds a NaN, or whose smallest or largest element
+ * is infinite, returns NaN for both ends at every level.  The rows are sorted by gpemu_rank_dev's radix sort, in batches
+ * that fit workspace_bytes (16*S + 1024*ceil(S/2048) + 4 bytes per row, and 16 bytes per 4096 windows and level beside
+ * it; 0 = half of the free device memory; if not one row fits: GPEMU_ERR_HIP, sizes in the error text); the window is a
+ * reduction over the sorted keys on the key (width, i), one launch for all levels of a batch and one that combines its
+ * chunks.  R >= 1, 1 <= n_levels <= 4096, 1 <= S < 2^31, else GPEMU_ERR_ARG before any launch.  n_out[] is a HOST array.
+ * _dev addresses as gpemu_select_dev does (element j of row r at dV[r*row_stride + j*elem_stride]); dout is a device
+ * array.
+ *
+ * Kernel density: dens[r*G + g] = 1 / (S h_r sqrt(2 pi)) sum_j exp(-(grid[r*G + g] - x_rj)^2 / (2 h_r^2)), the direct sum
+ * over all S elements of row r: no binning, no truncation.  grid[R*G] and h[R] (finite, > 0) are HOST arrays.  Workgroup
+ * (row, tile of up to 1024 grid points, chunk of 8192 samples): the grid points sit in registers, the samples are staged
+ * through LDS once and added in index order into four interleaved sums; the chunk sums of a grid point are then added
+ * by a lane-strided sum in chunk order and a fixed tree.  The order is fixed by S alone: the bits do not depend on the
+ * grid or on the run.  The row is read once per tile of 1024 grid points.  R, G, S >= 1, else GPEMU_ERR_ARG.
+ * _dev addresses as gpemu_select_dev does; ddens[R*G] is a device array.
+ *
+ * gpemu_marginal_dense_dev copies the rows of the block layout above into ddense[S*d]; gpemu_marginal_moments_dev
+ * returns mean[d] and var[d] (divisor S; HOST arrays) of a dense device matrix dX[S*d], two passes, sums in a fixed
+ * order (gpemu_sampler_chain_moments' kernels).
+ * Every _dev form works on `stream` (NULL = the null stream) and waits for it before it returns. */
+int gpemu_marginal_hist(int device, int64_t S, int d, const double *X, int nb1, const double *edges1, int nb2,
+                        const double *edges2, int64_t group_counters, int64_t *hist1, int64_t *hist2,
+                        int64_t *n_inside1);
+int gpemu_marginal_hist_dev(int device, const double *dX, int64_t n_blocks, int64_t block_rows,
+                            int64_t block_stride_rows, int d, int nb1, const double *edges1, int nb2,
+                            const double *edges2, int64_t group_counters, int64_t *dhist1, int64_t *dhist2,
+                            int64_t *dn_inside1, void *stream);
+int gpemu_hpd(int device, int64_t R, int64_t S, const double *V, int64_t n_levels, const int64_t *n_out, double *out);
+int gpemu_hpd_dev(int device, int64_t R, int64_t S, const double *dV, int64_t row_stride, int64_t elem_stride,
+                  int64_t n_levels, const int64_t *n_out, double *dout, int64_t workspace_bytes, void *stream);
+int gpemu_kde1d(int device, int64_t R, int64_t S, const double *V, int64_t G, const double *grid, const double *h,
+                double *dens);
+int gpemu_kde1d_dev(int device, int64_t R, int64_t S, const double *dV, int64_t row_stride, int64_t elem_stride,
+                    int64_t G, const double *grid, const double *h, double *ddens, void *stream);
+int gpemu_marginal_dense_dev(int device, const double *dX, int64_t n_blocks, int64_t block_rows,
+                             int64_t block_stride_rows, int d, double *ddense, void *stream);
+int gpemu_marginal_moments_dev(int device, const double *dX, int64_t S, int d, double *mean, double *var, void *stream);
+/* Which launches of the three ran.  A set of its own: the other sets keep their sizes and indices. */
+enum gpemu_marginal_path {
+  GPEMU_MARGINAL_PATH_HIST_SWEEP = 0,  /* one sweep of the histogram kernel over the rows                             */
+  GPEMU_MARGINAL_PATH_PAIR_GROUP,      /* ... that carried a group of pairs                                           */
+  GPEMU_MARGINAL_PATH_SORT_BATCH,      /* one batch of rows through the sort's workspace (eight passes)               */
+  GPEMU_MARGINAL_PATH_WINDOW_SEARCH,   /* the narrowest-window reduction of one batch, all levels                     */
+  GPEMU_MARGINAL_PATH_KDE,             /* one launch of the density kernel (a batch of rows) and of its chunk sum      */
+  GPEMU_MARGINAL_PATH_COUNT
+};
+/* out[0 .. min(n, GPEMU_MARGINAL_PATH_COUNT)) = the counters; returns GPEMU_MARGINAL_PATH_COUNT (or GPEMU_ERR_ARG). */
+int gpemu_marginal_path_counts(int64_t *out, int64_t n);
+
 /* ---- fit handle: test-only entry points ---------------------------------------------------------------------------
  * For the tests of the fit side only; nothing in the library's own flow calls them.
  * gpemu_fit_workspace: out[N*N] = problem z of the last evaluation (gpemu_fit_lml / _lml_batch / _factor) as the
