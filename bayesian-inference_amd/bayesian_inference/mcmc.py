@@ -650,9 +650,9 @@ def _add_diagnostics(config, results, compute, label='production chain'):
         logger.warning(f"max R-hat {np.nanmax(results['rhat']):.4f} > {RHAT_THRESHOLD}: the chains have not mixed")
 
 
-def diagnostics(config, closure_index=-1, discard=0, thin=1):
-    """The five diagnostics (``gpemu.diagnostics.summary``) of the chain stored in mcmc.h5 (of closure chain
-    ``closure_index``, if >= 0), steps ``[discard::thin]``, every walker as a chain."""
+def _stored_chain(config, closure_index, discard, thin):
+    """``(config, chain)``: steps ``[discard::thin]`` of the chain stored in mcmc.h5, ``(steps, walkers, d)`` -- with
+    ``closure_index >= 0`` that of closure chain ``closure_index``, under the configuration rebuilt for it."""
     if closure_index >= 0:
         config = MCMCConfig(analysis_name=config.analysis_name, parameterization=config.parameterization,
                             analysis_config=config.analysis_config, config_file=config.config_file,
@@ -660,11 +660,18 @@ def diagnostics(config, closure_index=-1, discard=0, thin=1):
     if int(discard) < 0 or int(thin) < 1:
         raise ValueError("discard must be >= 0 and thin >= 1")
     stored = _data_IO().read_dict_from_h5(config.mcmc_output_dir, 'mcmc.h5')
-    chain = np.ascontiguousarray(np.asarray(stored['chain'], dtype=np.float64)[int(discard)::int(thin)])
+    chain = np.asarray(stored['chain'], dtype=np.float64)[int(discard)::int(thin)]
     if chain.shape[0] == 0:
         raise ValueError("no stored steps after discard")
+    return config, chain
+
+
+def diagnostics(config, closure_index=-1, discard=0, thin=1):
+    """The five diagnostics (``gpemu.diagnostics.summary``) of the chain stored in mcmc.h5 (of closure chain
+    ``closure_index``, if >= 0), steps ``[discard::thin]``, every walker as a chain."""
+    _, chain = _stored_chain(config, closure_index, discard, thin)
     from gpemu import diagnostics as _diag
-    return _diag.summary(chain)
+    return _diag.summary(np.ascontiguousarray(chain))
 
 
 def marginals_settings(mc, default_confidence=None):
@@ -735,16 +742,7 @@ def _add_marginals(config, results, compute, label='production chain'):
 def marginals(config, closure_index=-1, discard=0, thin=1):
     """The marginals (``gpemu.marginals.summary``) of the chain stored in mcmc.h5 (of closure chain ``closure_index``,
     if >= 0), steps ``[discard::thin]``, all walkers, with the configuration's box and ``marginals_*`` settings."""
-    if closure_index >= 0:
-        config = MCMCConfig(analysis_name=config.analysis_name, parameterization=config.parameterization,
-                            analysis_config=config.analysis_config, config_file=config.config_file,
-                            closure_index=closure_index)
-    if int(discard) < 0 or int(thin) < 1:
-        raise ValueError("discard must be >= 0 and thin >= 1")
-    stored = _data_IO().read_dict_from_h5(config.mcmc_output_dir, 'mcmc.h5')
-    chain = np.asarray(stored['chain'], dtype=np.float64)[int(discard)::int(thin)]
-    if chain.shape[0] == 0:
-        raise ValueError("no stored steps after discard")
+    config, chain = _stored_chain(config, closure_index, discard, thin)
     from gpemu import marginals as _marg
     return _marg.summary(np.ascontiguousarray(chain.reshape(-1, chain.shape[-1])), **_marginals_kwargs(config))
 
@@ -770,16 +768,7 @@ def posterior_predictive(config, closure_index=-1, discard=0, thin=1,
                          probabilities=emulation.POSTERIOR_PREDICTIVE_PROBABILITIES):
     """``emulation.posterior_predictive`` of the chain stored in mcmc.h5 (of closure chain ``closure_index``, if >= 0),
     steps ``[discard::thin]``, all walkers."""
-    if closure_index >= 0:
-        config = MCMCConfig(analysis_name=config.analysis_name, parameterization=config.parameterization,
-                            analysis_config=config.analysis_config, config_file=config.config_file,
-                            closure_index=closure_index)
-    if int(discard) < 0 or int(thin) < 1:
-        raise ValueError("discard must be >= 0 and thin >= 1")
-    stored = _data_IO().read_dict_from_h5(config.mcmc_output_dir, 'mcmc.h5')
-    chain = np.asarray(stored['chain'], dtype=np.float64)[int(discard)::int(thin)]
-    if chain.shape[0] == 0:
-        raise ValueError("no stored steps after discard")
+    config, chain = _stored_chain(config, closure_index, discard, thin)
     emu_cfg = emulation.EmulationConfig.from_config_file(
         analysis_name=config.analysis_name, parameterization=config.parameterization,
         analysis_config=config.analysis_config, config_file=config.config_file)

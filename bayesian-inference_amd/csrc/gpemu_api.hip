@@ -142,7 +142,7 @@ void prof_pair(gpemu_model *m, int which, int e0, int e1) {
   (which == 0 ? m->ev_trmm : m->ev_kstar).emplace_back(e0, e1);
 }
 
-static int check_device(int device) {
+int device_ready(int device) {
   int n = 0;
   if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) {
     set_error("no HIP device available: libgpemu has no CPU implementation");
@@ -152,6 +152,7 @@ static int check_device(int device) {
     set_error("device %d out of range (have %d)", device, n);
     return GPEMU_ERR_ARG;
   }
+  GP_HIP(hipSetDevice(device));
   return GPEMU_OK;
 }
 
@@ -263,7 +264,7 @@ int gpemu_device_count(void) {
 }
 
 int gpemu_device_name(int device, char *buf, int64_t buflen) {
-  GP_TRY(check_device(device));
+  GP_TRY(device_ready(device));
   GP_ARG(buf && buflen > 0, "buf");
   hipDeviceProp_t prop;
   GP_HIP(hipGetDeviceProperties(&prop, device));
@@ -272,16 +273,15 @@ int gpemu_device_name(int device, char *buf, int64_t buflen) {
 }
 
 int gpemu_device_bus_id(int device, char *buf, int64_t buflen) {
-  GP_TRY(check_device(device));
+  GP_TRY(device_ready(device));
   GP_ARG(buf && buflen >= 16, "buf");
   GP_HIP(hipDeviceGetPCIBusId(buf, (int)buflen, device));
   return GPEMU_OK;
 }
 
 int gpemu_device_memory(int device, int64_t *free_bytes, int64_t *total_bytes) {
-  GP_TRY(check_device(device));
+  GP_TRY(device_ready(device));
   GP_ARG(free_bytes && total_bytes, "null pointer");
-  GP_HIP(hipSetDevice(device));
   size_t f = 0, t = 0;
   GP_HIP(hipMemGetInfo(&f, &t));
   *free_bytes = (int64_t)f;
@@ -441,8 +441,7 @@ int gpemu_model_create(gpemu_model **out, int device, int64_t N, int64_t d, int6
   GP_ARG(X_train && ls && alpha && L && components && scaler_mean && scaler_scale, "null array");
   GP_ARG(!has_const || constv, "constv");
   GP_ARG(!has_noise || noise, "noise");
-  GP_TRY(check_device(device));
-  GP_HIP(hipSetDevice(device));
+  GP_TRY(device_ready(device));
 
   gpemu_model *m = new gpemu_model();
   m->device = device;
@@ -981,8 +980,7 @@ int gpemu_truncation_cov(int device, int64_t n_comp, int64_t F, int64_t n_pc, co
                          const double *explained_variance, double *cov_out) {
   GP_ARG(components && explained_variance && cov_out, "null pointer");
   GP_ARG(n_comp > 0 && F > 0 && n_pc >= 0 && n_pc <= n_comp, "n_comp, F, n_pc");
-  GP_TRY(check_device(device));
-  GP_HIP(hipSetDevice(device));
+  GP_TRY(device_ready(device));
   const int64_t K = n_comp - n_pc;
   if (K == 0) {
     memset(cov_out, 0, sizeof(double) * (size_t)(F * F));

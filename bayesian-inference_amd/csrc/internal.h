@@ -44,6 +44,9 @@ void set_error(const char *fmt, ...);
 // per (function, current device), under a lock, so that later calls -- from any host thread -- make no call to set it
 int allow_dynamic_lds(const void *fn, int bytes);
 
+// GPEMU_ERR_NO_DEVICE without a HIP device, GPEMU_ERR_ARG for a `device` that is none of them; else makes it current
+int device_ready(int device);
+
 static inline int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
 
 // one relaxed host-side increment per launch decision, in one table (gpemu_api.hip) with a row per family of gpemu.h;

@@ -1,7 +1,7 @@
 // Exact average ranks of many rows at once (gpemu_rank*) and the transformed split chains behind rank-normalised
 // split-Rhat and bulk / tail ESS (gpemu_diag_*; Vehtari, Gelman, Simpson, Carpenter, Buerkner 2021).
 //
-// Ranks: the key-only LSD radix sort of sort_dev.h (order-preserving 64-bit keys, eight stable 8-bit passes), then two
+// Ranks: the key-only LSD radix sort of k_rows.hip (order-preserving 64-bit keys, eight stable 8-bit passes), then two
 // binary searches per element.
 // rk_lookup_kernel finds, for every element, the number of sorted keys below it (lo) and not above it (hi): the ranks
 // lo + 1 .. hi are tied, their average is (lo + hi + 1) / 2, exact in a double.  The sorted key array of a row is unique
@@ -18,8 +18,8 @@
 
 #include "internal.h"
 #include "linalg_dev.h"
+#include "rows_dev.h"
 #include "sampler_internal.h"
-#include "sort_dev.h"
 
 namespace gpemu {
 
@@ -59,42 +59,29 @@ __global__ __launch_bounds__(256) void rk_lookup_kernel(const double *V, int64_t
 // works on st and waits for it.  The caller has checked the arguments.
 static int rank_rows(const double *dV, int64_t R, int64_t S, int64_t row_stride, int64_t elem_stride, double *dout,
                      int64_t out_rs, int64_t out_es, bool z, int64_t workspace_bytes, hipStream_t st) {
-  int64_t budget = workspace_bytes;
-  if (budget == 0) {
-    size_t fb = 0, tb = 0;
-    GP_HIP(hipMemGetInfo(&fb, &tb));
-    budget = (int64_t)(fb / 2);
-  }
-  const int64_t ntiles = (S + RK_TILE - 1) / RK_TILE, nblk = (S + 255) / 256, per_row = rank_row_bytes(S);
-  int64_t rows_cap = std::min<int64_t>(R, budget / per_row);
-  rows_cap = std::min<int64_t>(rows_cap, (int64_t)0x7fffffff / nblk);   // the grids are (rows, blocks) flattened
+  int64_t budget = 0;
+  GP_TRY(workspace_budget(workspace_bytes, &budget));
+  const int64_t nblk = (S + 255) / 256, per_row = rank_row_bytes(S), rows_cap = sort_rows_cap(R, S, budget, per_row);
   if (rows_cap < 1) {
     set_error("rank: out of memory: one row of %lld elements needs %lld bytes of sort buffers; %lld bytes %s", (long long)S,
-              (long long)per_row, (long long)budget,
-              workspace_bytes ? "allowed by workspace_bytes" : "available (half of the free device memory)");
+              (long long)per_row, (long long)budget, workspace_budget_name(workspace_bytes));
     return GPEMU_ERR_HIP;
   }
   DevScope sc(st);
-  u64 *ka = nullptr, *kb = nullptr;
-  unsigned *hist = nullptr;
-  int *nan = nullptr;
-  GP_TRY(sc.alloc(&ka, rows_cap * S));
-  GP_TRY(sc.alloc(&kb, rows_cap * S));
-  GP_TRY(sc.alloc(&hist, rows_cap * RK_BINS * ntiles));
-  GP_TRY(sc.alloc(&nan, rows_cap));
+  SortScratch sort;
+  GP_TRY(sort.alloc(sc, rows_cap, S));
   for (int64_t row0 = 0; row0 < R; row0 += rows_cap) {
     const int64_t rows = std::min(rows_cap, R - row0);
     diag_path_count(GPEMU_DIAG_PATH_ROW_BATCH);
-    GP_TRY(sort_rows(dV, row_stride, elem_stride, S, row0, rows, ka, kb, hist, nan,
-                     [] { diag_path_count(GPEMU_DIAG_PATH_SORT_PASS); }, st));
-    const u64 *src = ka;
+    GP_TRY(sort_rows(dV, row_stride, elem_stride, S, row0, rows, sort, [] { diag_path_count(GPEMU_DIAG_PATH_SORT_PASS); },
+                     st));
     diag_path_count(GPEMU_DIAG_PATH_RANK_LOOKUP);
     if (z)
       hipLaunchKernelGGL(rk_lookup_kernel<true>, dim3((unsigned)(rows * nblk)), dim3(256), 0, st, dV, row_stride,
-                         elem_stride, S, row0, nblk, src, nan, dout, out_rs, out_es);
+                         elem_stride, S, row0, nblk, (const u64 *)sort.ka, (const int *)sort.nan, dout, out_rs, out_es);
     else
       hipLaunchKernelGGL(rk_lookup_kernel<false>, dim3((unsigned)(rows * nblk)), dim3(256), 0, st, dV, row_stride,
-                         elem_stride, S, row0, nblk, src, nan, dout, out_rs, out_es);
+                         elem_stride, S, row0, nblk, (const u64 *)sort.ka, (const int *)sort.nan, dout, out_rs, out_es);
     GP_HIP(hipGetLastError());
   }
   GP_HIP(hipStreamSynchronize(st));
@@ -107,27 +94,7 @@ static int rank_check(int64_t R, int64_t S) {
   return GPEMU_OK;
 }
 
-static int diag_device_ready(int device) {
-  int n = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) {
-    set_error("no HIP device available: libgpemu has no CPU implementation");
-    return GPEMU_ERR_NO_DEVICE;
-  }
-  GP_ARG(device >= 0 && device < n, "device out of range");
-  GP_HIP(hipSetDevice(device));
-  return GPEMU_OK;
-}
-
 // ---- the transformed split chains ----------------------------------------------------------------------------------
-// dense[(t nw + w) d + dd] = x[t][w][dd] of the segment (src: walker w0 of its first step)
-__global__ __launch_bounds__(256) void diag_dense_kernel(const double *__restrict__ src, int64_t step_stride, int64_t n,
-                                                         int64_t nw, int d, double *__restrict__ dense) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n * nw * d) return;
-  const int64_t wd = nw * d;
-  dense[i] = src[(i / wd) * step_stride + i % wd];
-}
-
 // Y[t][(h nw + w) d + dd] = op(x[h ? n - N + t : t][w][dd]): identity, |x - par[dd]| or 1[x <= par[dd]]
 __global__ __launch_bounds__(256) void diag_split_kernel(const double *__restrict__ src, int64_t step_stride, int64_t n,
                                                          int64_t N, int64_t nw, int d, int op,
@@ -267,10 +234,11 @@ static int diag_new(gpemu_diag **out, int device, hipStream_t st, const double *
   return GPEMU_OK;
 }
 
-static int diag_shape_check(int64_t n, int64_t nw, int d) {
+// the segment as rows in blocks (a step is a block) within the handle's own limits
+static int diag_view_check(int64_t n, int64_t step_stride, int64_t nw, int d) {
+  GP_TRY(rows_check(RowsView{nullptr, n, nw, step_stride, d}));
   GP_ARG(n >= 8, "n must be at least 8 (N = n / 2 >= 4)");
-  GP_ARG(nw >= 1, "nw must be positive");
-  GP_ARG(d >= 1 && d <= 65535, "d must be in [1, 65535]");
+  GP_ARG(d <= 65535, "d must be in [1, 65535]");
   GP_ARG(n <= ((1ll << 31) - 1) / nw, "n * nw must be below 2^31");
   return GPEMU_OK;
 }
@@ -278,11 +246,7 @@ static int diag_shape_check(int64_t n, int64_t nw, int d) {
 // the dense unsplit segment into Y's buffer (Y is no transform after this)
 static int diag_dense(gpemu_diag *h) {
   h->kind = -1;
-  const int64_t tot = h->n * h->nw * h->d;
-  hipLaunchKernelGGL(diag_dense_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, h->stream, h->src, h->step_stride,
-                     h->n, h->nw, h->d, h->Y);
-  GP_HIP(hipGetLastError());
-  return GPEMU_OK;
+  return gather_rows(RowsView{h->src, h->n, h->nw, h->step_stride, h->d}, 0, h->n * h->nw, h->Y, h->stream);
 }
 
 // order statistics ranks[0 .. nr) of every parameter of the pooled unsplit segment -> host out[dd nr + i]
@@ -310,21 +274,8 @@ static int diag_ensure_pooled(gpemu_diag *h) {
   }
   std::vector<double> q((size_t)d * 4);
   GP_TRY(diag_select(h, nr, ranks, q.data()));   // leaves the dense segment in Y
-  const int64_t nb = (T + MOM_ROWS - 1) / MOM_ROWS;
-  DevScope sc(h->stream);
-  double *dpart = nullptr;
-  GP_TRY(sc.alloc(&dpart, nb * d));
-  double *dmom = h->small;
-  hipLaunchKernelGGL(moments_partial_kernel, dim3((unsigned)nb), dim3(256), 0, h->stream, h->Y, T, d, (const double *)nullptr,
-                     dpart);
-  hipLaunchKernelGGL(moments_final_kernel, dim3((unsigned)d), dim3(256), 0, h->stream, dpart, nb, d, T, dmom);
-  hipLaunchKernelGGL(moments_partial_kernel, dim3((unsigned)nb), dim3(256), 0, h->stream, h->Y, T, d, (const double *)dmom,
-                     dpart);
-  hipLaunchKernelGGL(moments_final_kernel, dim3((unsigned)d), dim3(256), 0, h->stream, dpart, nb, d, T, dmom + d);
-  GP_HIP(hipGetLastError());
   std::vector<double> mom((size_t)2 * d);
-  GP_TRY(sc.download(mom.data(), dmom, 2 * d));
-  GP_HIP(hipStreamSynchronize(h->stream));
+  GP_TRY(moments_to_host(h->Y, T, d, mom.data(), mom.data() + d, h->stream));
   h->pooled.assign((size_t)5 * d, 0.0);
   for (int dd = 0; dd < d; ++dd) {
     const double *qd = q.data() + (size_t)dd * nr;
@@ -378,7 +329,7 @@ int gpemu_rank_dev(int device, int64_t R, int64_t S, const double *dV, int64_t r
   GP_TRY(rank_check(R, S));
   GP_ARG(row_stride > 0 && elem_stride > 0, "strides must be positive");
   GP_ARG(workspace_bytes >= 0, "workspace_bytes must be >= 0");
-  GP_TRY(diag_device_ready(device));
+  GP_TRY(device_ready(device));
   return rank_rows(dV, R, S, row_stride, elem_stride, dranks, S, 1, false, workspace_bytes, (hipStream_t)stream);
 }
 
@@ -386,23 +337,16 @@ int gpemu_rank(int device, int64_t R, int64_t S, const double *V, double *ranks_
   GP_ARG(V && ranks_out, "null pointer");
   GP_TRY(rank_check(R, S));
   GP_ARG(R <= INT64_MAX / 8 / S, "R * S overflows");
-  GP_TRY(diag_device_ready(device));
-  hipStream_t st = nullptr;
-  DevScope sc(st);
-  double *dV = nullptr, *dr = nullptr;
-  GP_TRY(sc.alloc(&dV, R * S));
-  GP_TRY(sc.alloc(&dr, R * S));
-  GP_TRY(upload(dV, V, R * S, st));
-  GP_TRY(rank_rows(dV, R, S, S, 1, dr, S, 1, false, 0, st));
-  GP_TRY(sc.download(ranks_out, dr, R * S));
-  GP_HIP(hipStreamSynchronize(st));
-  return GPEMU_OK;
+  return with_host_rows(device, R, S, V, S, ranks_out, [&](const double *dV, double *dr, hipStream_t st) {
+    return rank_rows(dV, R, S, S, 1, dr, S, 1, false, 0, st);
+  });
 }
 
 int gpemu_diag_create(gpemu_diag **out, int device, const double *chain, int64_t n, int64_t W, int d) {
   GP_ARG(out && chain, "null pointer");
-  GP_TRY(diag_shape_check(n, W, d));
-  GP_TRY(diag_device_ready(device));
+  GP_ARG(W <= INT64_MAX / 8 / std::max(d, 1), "W * d overflows");
+  GP_TRY(diag_view_check(n, W * d, W, d));
+  GP_TRY(device_ready(device));
   hipStream_t st = nullptr;
   double *dchain = nullptr;
   {
@@ -418,11 +362,11 @@ int gpemu_diag_create(gpemu_diag **out, int device, const double *chain, int64_t
 int gpemu_diag_create_dev(gpemu_diag **out, int device, const double *dchain, int64_t n, int64_t step_stride, int64_t w0,
                           int64_t nw, int d, int64_t workspace_bytes, void *stream) {
   GP_ARG(out && dchain, "null pointer");
-  GP_TRY(diag_shape_check(n, nw, d));
+  GP_TRY(diag_view_check(n, step_stride, nw, d));
   GP_ARG(w0 >= 0, "w0 must be >= 0");
   GP_ARG(step_stride >= (w0 + nw) * d, "step_stride must hold walkers [0, w0 + nw)");
   GP_ARG(workspace_bytes >= 0, "workspace_bytes must be >= 0");
-  GP_TRY(diag_device_ready(device));
+  GP_TRY(device_ready(device));
   return diag_new(out, device, (hipStream_t)stream, dchain + w0 * d, nullptr, n, step_stride, nw, d, workspace_bytes);
 }
 
@@ -431,7 +375,7 @@ int gpemu_sampler_diag_create(gpemu_diag **out, gpemu_sampler *s, int64_t first,
   GP_ARG(out && s, "null pointer");
   GP_ARG(thin >= 1, "thin must be positive");
   GP_ARG(w0 >= 0 && nw >= 1 && w0 + nw <= s->W, "walker range");
-  GP_TRY(diag_shape_check(n, nw, (int)s->d));
+  GP_TRY(diag_view_check(n, thin * s->W * s->d, nw, (int)s->d));
   GP_ARG(first >= 0 && first < s->chain_len && (n - 1) <= (s->chain_len - 1 - first) / thin, "chain range");
   GP_HIP(hipSetDevice(s->device));
   GP_TRY(diag_new(out, s->device, s->stream, s->chain + first * s->W * s->d + w0 * s->d, nullptr, n, thin * s->W * s->d, nw,

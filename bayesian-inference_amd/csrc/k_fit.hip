@@ -1440,13 +1440,7 @@ int gpemu_fit_create(gpemu_fit **out, int device, int64_t N, int64_t d, const do
   GP_ARG(N > 0 && d > 0 && d <= DPAD_WIDE, "N > 0 and 0 < d <= 16 required");
   GP_ARG(kernel_kind == GPEMU_KERNEL_RBF || kernel_kind == GPEMU_KERNEL_MATERN, "kernel_kind");
   if (kernel_kind == GPEMU_KERNEL_MATERN) GP_ARG(nu > 0.0, "Matern nu must be > 0 (finite or +inf; not NaN)");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-    set_error("no HIP device available: libgpemu has no CPU implementation");
-    return GPEMU_ERR_NO_DEVICE;
-  }
-  GP_ARG(device >= 0 && device < ndev, "device");
-  GP_HIP(hipSetDevice(device));
+  GP_TRY(device_ready(device));
   gpemu_fit *f = new gpemu_fit();
   f->device = device; f->N = N; f->d = d; f->Np = round_up(N, NB);
   f->dp = dpad_of(d);
@@ -1572,13 +1566,7 @@ int gpemu_kernel_matrix(int device, int64_t N, int64_t d, const double *X, const
 
 int gpemu_cholesky(int device, int64_t N, double *A_inout) {
   GP_ARG(A_inout && N > 0, "A / N");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-    set_error("no HIP device available: libgpemu has no CPU implementation");
-    return GPEMU_ERR_NO_DEVICE;
-  }
-  GP_ARG(device >= 0 && device < ndev, "device");
-  GP_HIP(hipSetDevice(device));
+  GP_TRY(device_ready(device));
   const int64_t Np = round_up(N, NB);
   std::vector<double> h((size_t)(Np * Np), 0.0);
   for (int64_t i = 0; i < Np; ++i)

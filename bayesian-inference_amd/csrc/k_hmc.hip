@@ -17,6 +17,7 @@
 // is ordered by the sampler's stream: the step size is read and written on the device, the host reads nothing in a run.
 // No float atomics.
 #include "internal.h"
+#include "rows_dev.h"
 #include "sampler_internal.h"
 
 #include <algorithm>
@@ -222,61 +223,6 @@ __global__ __launch_bounds__(256) void hmc_draws_kernel(double *z, double *ua, d
     z[(int64_t)w * d + 2 * j] = z0;
     if (2 * j + 1 < d) z[(int64_t)w * d + 2 * j + 1] = z1;
   }
-}
-
-// ---- chain moments: pooled mean and variance per parameter, two passes, fixed order ---------------------------------
-// (MOM_ROWS rows of the flattened chain [R][d] per workgroup: sampler_internal.h)
-
-// part[b][dd] = sum over the rows of block b of x (mean == null) or of (x - mean[dd])^2
-__global__ __launch_bounds__(256) void moments_partial_kernel(const double *__restrict__ x, int64_t R, int d,
-                                                              const double *__restrict__ mean, double *__restrict__ part) {
-  __shared__ double red[256];
-  const int t = threadIdx.x;
-  const int64_t r0 = (int64_t)blockIdx.x * MOM_ROWS, r1 = (r0 + MOM_ROWS < R) ? r0 + MOM_ROWS : R;
-  for (int dd = 0; dd < d; ++dd) {
-    const double mu = mean ? mean[dd] : 0.0;
-    double s = 0.0;
-    for (int64_t r = r0 + t; r < r1; r += 256) {
-      const double v = x[r * d + dd] - mu;
-      s += mean ? v * v : v;
-    }
-    red[t] = s;
-    __syncthreads();
-    for (int off = 128; off > 0; off >>= 1) {
-      if (t < off) red[t] += red[t + off];
-      __syncthreads();
-    }
-    if (t == 0) part[(int64_t)blockIdx.x * d + dd] = red[0];
-    __syncthreads();
-  }
-}
-
-// out[dd] = (sum over the blocks of part[b][dd]) / R; grid = d workgroups
-__global__ __launch_bounds__(256) void moments_final_kernel(const double *__restrict__ part, int64_t nb, int d, int64_t R,
-                                                            double *__restrict__ out) {
-  __shared__ double red[256];
-  const int t = threadIdx.x, dd = blockIdx.x;
-  double s = 0.0;
-  for (int64_t b = t; b < nb; b += 256) s += part[b * d + dd];
-  red[t] = s;
-  __syncthreads();
-  for (int off = 128; off > 0; off >>= 1) {
-    if (t < off) red[t] += red[t + off];
-    __syncthreads();
-  }
-  if (t == 0) out[dd] = red[0] / (double)R;
-}
-
-// dmom[0 .. d) = mean, dmom[d .. 2d) = variance (divisor R) of the R rows of dx [R][d]; asynchronous on st
-static int launch_moments(const double *dx, int64_t R, int d, double *dpart, double *dmom, hipStream_t st) {
-  const int64_t nb = (R + MOM_ROWS - 1) / MOM_ROWS;
-  hipLaunchKernelGGL(moments_partial_kernel, dim3((unsigned)nb), dim3(256), 0, st, dx, R, d, (const double *)nullptr, dpart);
-  hipLaunchKernelGGL(moments_final_kernel, dim3((unsigned)d), dim3(256), 0, st, dpart, nb, d, R, dmom);
-  hipLaunchKernelGGL(moments_partial_kernel, dim3((unsigned)nb), dim3(256), 0, st, dx, R, d, (const double *)dmom, dpart);
-  hipLaunchKernelGGL(moments_final_kernel, dim3((unsigned)d), dim3(256), 0, st, dpart, nb, d, R, dmom + d);
-  GP_HIP(hipGetLastError());
-  hmc_path_count(GPEMU_HMC_PATH_MOMENTS);
-  return GPEMU_OK;
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------
@@ -568,17 +514,8 @@ int gpemu_sampler_chain_moments(gpemu_sampler *s, int64_t first, int64_t n, doub
   GP_ARG(s && mean && var, "null pointer");
   GP_ARG(first >= 0 && n >= 1 && first + n <= s->chain_len, "chain range");
   GP_HIP(hipSetDevice(s->device));
-  hipStream_t st = s->stream;
-  const int64_t R = n * s->W, nb = (R + MOM_ROWS - 1) / MOM_ROWS;
-  const int d = (int)s->d;
-  DevScope sc(st);
-  double *dpart, *dmom;
-  GP_TRY(sc.alloc(&dpart, nb * d));
-  GP_TRY(sc.alloc(&dmom, 2 * d));
-  GP_TRY(launch_moments(s->chain + first * s->W * s->d, R, d, dpart, dmom, st));
-  GP_TRY(sc.download(mean, dmom, d));
-  GP_TRY(sc.download(var, dmom + d, d));
-  GP_HIP(hipStreamSynchronize(st));
+  GP_TRY(moments_to_host(s->chain + first * s->W * s->d, n * s->W, (int)s->d, mean, var, s->stream));
+  hmc_path_count(GPEMU_HMC_PATH_MOMENTS);
   return GPEMU_OK;
 }
 

@@ -11,7 +11,7 @@
 // where they fit, else in sweeps of their own.  Every counter is an integer: nothing depends on the grid, on the plan
 // or on the run.
 //
-// Highest-density intervals (hpd_*): the rows are sorted by sort_dev.h's radix sort in batches; hpd_window_kernel takes,
+// Highest-density intervals (hpd_*): the rows are sorted by k_rows.hip's radix sort in batches; hpd_window_kernel takes,
 // for every (row, level, chunk of HW_PER windows), the lexicographic minimum of (s[S - n + i] - s[i], i), and
 // hpd_finish_kernel that of a (row, level)'s chunks: the narrowest window, the smallest i among ties (np.argmin).
 //
@@ -25,8 +25,8 @@
 #include <vector>
 
 #include "internal.h"
+#include "rows_dev.h"
 #include "sampler_internal.h"
-#include "sort_dev.h"
 
 namespace gpemu {
 
@@ -141,16 +141,6 @@ __global__ __launch_bounds__(256) void mh_inside_kernel(const unsigned long long
   if (tid == 0) n_inside[blockIdx.x] = red[0];
 }
 
-// logical rows of the block layout -> dst[S][d]
-__global__ __launch_bounds__(256) void mh_dense_kernel(const double *__restrict__ X, int64_t block_rows,
-                                                       int64_t block_stride_rows, int d, int64_t S,
-                                                       double *__restrict__ dst) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= S * d) return;
-  const int64_t r = i / d;
-  dst[i] = X[((r / block_rows) * block_stride_rows + r % block_rows) * d + i % d];
-}
-
 struct HistSweep { int a0, a1, p0, p1; };
 
 // the sweeps of one call (the file's header); cap: 16-bit counters per sweep
@@ -169,17 +159,6 @@ static std::vector<HistSweep> hist_plan(int d, int nb1, int nb2, int64_t cap) {
   return plan;
 }
 
-static int marginal_device_ready(int device) {
-  int n = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) {
-    set_error("no HIP device available: libgpemu has no CPU implementation");
-    return GPEMU_ERR_NO_DEVICE;
-  }
-  GP_ARG(device >= 0 && device < n, "device out of range");
-  GP_HIP(hipSetDevice(device));
-  return GPEMU_OK;
-}
-
 static int edges_check(const double *e, int d, int nb) {
   for (int k = 0; k < d; ++k)
     for (int b = 0; b <= nb; ++b) {
@@ -190,9 +169,12 @@ static int edges_check(const double *e, int d, int nb) {
   return GPEMU_OK;
 }
 
-static int block_check(int64_t n_blocks, int64_t block_rows, int64_t block_stride_rows) {
-  GP_ARG(n_blocks > 0 && block_rows > 0, "n_blocks and block_rows must be positive");
-  GP_ARG(n_blocks == 1 || block_stride_rows >= block_rows, "block_stride_rows must be >= block_rows");
+// the rows of the _dev calls as a view, within the marginals' own limits
+static int marginal_view(const double *dX, int64_t n_blocks, int64_t block_rows, int64_t block_stride_rows, int d,
+                         RowsView *v) {
+  GP_ARG(d >= 1 && d <= MH_MAX_D, "d must be in [1, 16]");
+  *v = RowsView{dX, n_blocks, block_rows, block_stride_rows * d, d};
+  GP_TRY(rows_check(*v));
   GP_ARG(n_blocks <= ((1ll << 31) - 1) / block_rows, "S = n_blocks * block_rows must be below 2^31");
   return GPEMU_OK;
 }
@@ -347,35 +329,23 @@ static int hpd_check(int64_t R, int64_t S, int64_t n_levels, const int64_t *n_ou
 // the intervals of R rows, in batches of rows that fit workspace_bytes (0: half of the free memory); waits for st
 static int hpd_rows(const double *dV, int64_t R, int64_t S, int64_t row_stride, int64_t elem_stride, int64_t n_levels,
                     const int64_t *n_out, double *dout, int64_t workspace_bytes, hipStream_t st) {
-  int64_t budget = workspace_bytes;
-  if (budget == 0) {
-    size_t fb = 0, tb = 0;
-    GP_HIP(hipMemGetInfo(&fb, &tb));
-    budget = (int64_t)(fb / 2);
-  }
+  int64_t budget = 0;
+  GP_TRY(workspace_budget(workspace_bytes, &budget));
   const int64_t n_max = *std::max_element(n_out, n_out + n_levels), nchunk = (n_max + HW_PER - 1) / HW_PER;
-  const int64_t ntiles = (S + RK_TILE - 1) / RK_TILE, nblk = (S + 255) / 256;
-  const int64_t per_row = rank_row_bytes(S) + 16 * n_levels * nchunk;
-  int64_t rows_cap = std::min<int64_t>(R, budget / per_row);
-  rows_cap = std::min<int64_t>(rows_cap, (int64_t)0x7fffffff / nblk);   // the grids are (rows, blocks) flattened
-  rows_cap = std::min<int64_t>(rows_cap, (int64_t)0x7fffffff / (n_levels * nchunk));
+  const int64_t per_row = rank_row_bytes(S) + 16 * n_levels * nchunk;   // the sort's and the windows' (pw, pi)
+  const int64_t rows_cap = sort_rows_cap(R, S, budget, per_row, n_levels * nchunk);
   if (rows_cap < 1) {
     set_error("hpd: out of memory: one row of %lld elements and %lld levels needs %lld bytes of sort and window buffers; "
               "%lld bytes %s", (long long)S, (long long)n_levels, (long long)per_row, (long long)budget,
-              workspace_bytes ? "allowed by workspace_bytes" : "available (half of the free device memory)");
+              workspace_budget_name(workspace_bytes));
     return GPEMU_ERR_HIP;
   }
   DevScope sc(st);
-  u64 *ka = nullptr, *kb = nullptr;
-  unsigned *hist = nullptr;
-  int *nan = nullptr;
+  SortScratch sort;
   int64_t *dn = nullptr;
   double *pw = nullptr;
   long long *pi = nullptr;
-  GP_TRY(sc.alloc(&ka, rows_cap * S));
-  GP_TRY(sc.alloc(&kb, rows_cap * S));
-  GP_TRY(sc.alloc(&hist, rows_cap * RK_BINS * ntiles));
-  GP_TRY(sc.alloc(&nan, rows_cap));
+  GP_TRY(sort.alloc(sc, rows_cap, S));
   GP_TRY(sc.alloc(&dn, n_levels));
   GP_TRY(sc.alloc(&pw, rows_cap * n_levels * nchunk));
   GP_TRY(sc.alloc(&pi, rows_cap * n_levels * nchunk));
@@ -383,13 +353,13 @@ static int hpd_rows(const double *dV, int64_t R, int64_t S, int64_t row_stride, 
   for (int64_t row0 = 0; row0 < R; row0 += rows_cap) {
     const int64_t rows = std::min(rows_cap, R - row0);
     marginal_path_count(GPEMU_MARGINAL_PATH_SORT_BATCH);
-    GP_TRY(sort_rows(dV, row_stride, elem_stride, S, row0, rows, ka, kb, hist, nan, [] {}, st));
+    GP_TRY(sort_rows(dV, row_stride, elem_stride, S, row0, rows, sort, [] {}, st));
     marginal_path_count(GPEMU_MARGINAL_PATH_WINDOW_SEARCH);
-    hipLaunchKernelGGL(hpd_window_kernel, dim3((unsigned)(rows * n_levels * nchunk)), dim3(256), 0, st, ka, S, (int)n_levels,
-                       dn, nchunk, pw, pi);
+    hipLaunchKernelGGL(hpd_window_kernel, dim3((unsigned)(rows * n_levels * nchunk)), dim3(256), 0, st, sort.ka, S,
+                       (int)n_levels, dn, nchunk, pw, pi);
     GP_HIP(hipGetLastError());
-    hipLaunchKernelGGL(hpd_finish_kernel, dim3((unsigned)(rows * n_levels)), dim3(256), 0, st, ka, S, (int)n_levels, dn,
-                       nchunk, pw, pi, nan, row0, dout);
+    hipLaunchKernelGGL(hpd_finish_kernel, dim3((unsigned)(rows * n_levels)), dim3(256), 0, st, sort.ka, S, (int)n_levels, dn,
+                       nchunk, pw, pi, sort.nan, row0, dout);
     GP_HIP(hipGetLastError());
   }
   GP_HIP(hipStreamSynchronize(st));   // n_out is read by the copy above
@@ -529,9 +499,10 @@ int gpemu_marginal_hist_dev(int device, const double *dX, int64_t n_blocks, int6
                             const double *edges2, int64_t group_counters, int64_t *dhist1, int64_t *dhist2,
                             int64_t *dn_inside1, void *stream) {
   GP_ARG(dX, "null pointer");
-  GP_TRY(block_check(n_blocks, block_rows, block_stride_rows));
+  RowsView X;
+  GP_TRY(marginal_view(dX, n_blocks, block_rows, block_stride_rows, d, &X));
   GP_TRY(hist_check(d, nb1, edges1, nb2, edges2, group_counters, dhist1, dhist2, dn_inside1));
-  GP_TRY(marginal_device_ready(device));
+  GP_TRY(device_ready(device));
   return hist_rows(dX, n_blocks, block_rows, block_stride_rows, d, nb1, edges1, nb2, edges2, group_counters, dhist1, dhist2,
                    dn_inside1, (hipStream_t)stream);
 }
@@ -542,7 +513,7 @@ int gpemu_marginal_hist(int device, int64_t S, int d, const double *X, int nb1, 
   GP_ARG(X, "null pointer");
   GP_ARG(S > 0 && S < (1ll << 31), "S must be in [1, 2^31)");
   GP_TRY(hist_check(d, nb1, edges1, nb2, edges2, group_counters, hist1, hist2, n_inside1));
-  GP_TRY(marginal_device_ready(device));
+  GP_TRY(device_ready(device));
   hipStream_t st = nullptr;
   const int64_t np = d * (d - 1) / 2, n2 = np * nb2 * nb2;
   DevScope sc(st);
@@ -567,7 +538,7 @@ int gpemu_hpd_dev(int device, int64_t R, int64_t S, const double *dV, int64_t ro
   GP_TRY(hpd_check(R, S, n_levels, n_out));
   GP_ARG(row_stride > 0 && elem_stride > 0, "strides must be positive");
   GP_ARG(workspace_bytes >= 0, "workspace_bytes must be >= 0");
-  GP_TRY(marginal_device_ready(device));
+  GP_TRY(device_ready(device));
   return hpd_rows(dV, R, S, row_stride, elem_stride, n_levels, n_out, dout, workspace_bytes, (hipStream_t)stream);
 }
 
@@ -575,17 +546,9 @@ int gpemu_hpd(int device, int64_t R, int64_t S, const double *V, int64_t n_level
   GP_ARG(V && out, "null pointer");
   GP_TRY(hpd_check(R, S, n_levels, n_out));
   GP_ARG(R <= INT64_MAX / 8 / S, "R * S overflows");
-  GP_TRY(marginal_device_ready(device));
-  hipStream_t st = nullptr;
-  DevScope sc(st);
-  double *dV = nullptr, *dout = nullptr;
-  GP_TRY(sc.alloc(&dV, R * S));
-  GP_TRY(sc.alloc(&dout, R * n_levels * 2));
-  GP_TRY(upload(dV, V, R * S, st));
-  GP_TRY(hpd_rows(dV, R, S, S, 1, n_levels, n_out, dout, 0, st));
-  GP_TRY(sc.download(out, dout, R * n_levels * 2));
-  GP_HIP(hipStreamSynchronize(st));
-  return GPEMU_OK;
+  return with_host_rows(device, R, S, V, n_levels * 2, out, [&](const double *dV, double *dout, hipStream_t st) {
+    return hpd_rows(dV, R, S, S, 1, n_levels, n_out, dout, 0, st);
+  });
 }
 
 int gpemu_kde1d_dev(int device, int64_t R, int64_t S, const double *dV, int64_t row_stride, int64_t elem_stride,
@@ -593,7 +556,7 @@ int gpemu_kde1d_dev(int device, int64_t R, int64_t S, const double *dV, int64_t 
   GP_ARG(dV && ddens, "null pointer");
   GP_TRY(kde_check(R, S, G, grid, h));
   GP_ARG(row_stride > 0 && elem_stride > 0, "strides must be positive");
-  GP_TRY(marginal_device_ready(device));
+  GP_TRY(device_ready(device));
   return kde_rows(dV, R, S, row_stride, elem_stride, G, grid, h, ddens, (hipStream_t)stream);
 }
 
@@ -602,30 +565,19 @@ int gpemu_kde1d(int device, int64_t R, int64_t S, const double *V, int64_t G, co
   GP_ARG(V && dens, "null pointer");
   GP_TRY(kde_check(R, S, G, grid, h));
   GP_ARG(R <= INT64_MAX / 8 / S, "R * S overflows");
-  GP_TRY(marginal_device_ready(device));
-  hipStream_t st = nullptr;
-  DevScope sc(st);
-  double *dV = nullptr, *dd = nullptr;
-  GP_TRY(sc.alloc(&dV, R * S));
-  GP_TRY(sc.alloc(&dd, R * G));
-  GP_TRY(upload(dV, V, R * S, st));
-  GP_TRY(kde_rows(dV, R, S, S, 1, G, grid, h, dd, st));
-  GP_TRY(sc.download(dens, dd, R * G));
-  GP_HIP(hipStreamSynchronize(st));
-  return GPEMU_OK;
+  return with_host_rows(device, R, S, V, G, dens, [&](const double *dV, double *dd, hipStream_t st) {
+    return kde_rows(dV, R, S, S, 1, G, grid, h, dd, st);
+  });
 }
 
 int gpemu_marginal_dense_dev(int device, const double *dX, int64_t n_blocks, int64_t block_rows,
                              int64_t block_stride_rows, int d, double *ddense, void *stream) {
   GP_ARG(dX && ddense, "null pointer");
-  GP_TRY(block_check(n_blocks, block_rows, block_stride_rows));
-  GP_ARG(d >= 1 && d <= MH_MAX_D, "d must be in [1, 16]");
-  GP_TRY(marginal_device_ready(device));
+  RowsView X;
+  GP_TRY(marginal_view(dX, n_blocks, block_rows, block_stride_rows, d, &X));
+  GP_TRY(device_ready(device));
   hipStream_t st = (hipStream_t)stream;
-  const int64_t S = n_blocks * block_rows;
-  hipLaunchKernelGGL(mh_dense_kernel, dim3((unsigned)((S * d + 255) / 256)), dim3(256), 0, st, dX, block_rows,
-                     block_stride_rows, d, S, ddense);
-  GP_HIP(hipGetLastError());
+  GP_TRY(gather_rows(X, 0, X.rows(), ddense, st));
   GP_HIP(hipStreamSynchronize(st));
   return GPEMU_OK;
 }
@@ -634,25 +586,8 @@ int gpemu_marginal_moments_dev(int device, const double *dX, int64_t S, int d, d
   GP_ARG(dX && mean && var, "null pointer");
   GP_ARG(S > 0 && S < (1ll << 31), "S must be in [1, 2^31)");
   GP_ARG(d >= 1 && d <= MH_MAX_D, "d must be in [1, 16]");
-  GP_TRY(marginal_device_ready(device));
-  hipStream_t st = (hipStream_t)stream;
-  const int64_t nb = (S + MOM_ROWS - 1) / MOM_ROWS;
-  DevScope sc(st);
-  double *dpart = nullptr, *dmom = nullptr;
-  GP_TRY(sc.alloc(&dpart, nb * d));
-  GP_TRY(sc.alloc(&dmom, 2 * d));
-  hipLaunchKernelGGL(moments_partial_kernel, dim3((unsigned)nb), dim3(256), 0, st, dX, S, d, (const double *)nullptr, dpart);
-  GP_HIP(hipGetLastError());
-  hipLaunchKernelGGL(moments_final_kernel, dim3((unsigned)d), dim3(256), 0, st, dpart, nb, d, S, dmom);
-  GP_HIP(hipGetLastError());
-  hipLaunchKernelGGL(moments_partial_kernel, dim3((unsigned)nb), dim3(256), 0, st, dX, S, d, (const double *)dmom, dpart);
-  GP_HIP(hipGetLastError());
-  hipLaunchKernelGGL(moments_final_kernel, dim3((unsigned)d), dim3(256), 0, st, dpart, nb, d, S, dmom + d);
-  GP_HIP(hipGetLastError());
-  GP_TRY(sc.download(mean, dmom, d));
-  GP_TRY(sc.download(var, dmom + d, d));
-  GP_HIP(hipStreamSynchronize(st));
-  return GPEMU_OK;
+  GP_TRY(device_ready(device));
+  return moments_to_host(dX, S, d, mean, var, (hipStream_t)stream);
 }
 
 }  // extern "C"

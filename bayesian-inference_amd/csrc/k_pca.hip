@@ -586,13 +586,7 @@ extern "C" int gpemu_pca_fit(int device, int64_t N, int64_t F, const double *Y, 
   const int64_t nmin = std::min(N, F);
   const int64_t nc = (n_components <= 0) ? nmin : n_components;
   GP_ARG(nc <= nmin, "n_components must be <= min(N, F)");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-    set_error("no HIP device available: libgpemu has no CPU implementation");
-    return GPEMU_ERR_NO_DEVICE;
-  }
-  GP_ARG(device >= 0 && device < ndev, "device");
-  GP_HIP(hipSetDevice(device));
+  GP_TRY(device_ready(device));
   const bool tw = N < F;                          // work on the transpose when there are fewer rows
   const int m = (int)(tw ? F : N), n = (int)(tw ? N : F);
   const int PB = n <= 1024 ? 16 : 32;                                     // columns per block (more, smaller pairs keep a small matrix's rounds short)

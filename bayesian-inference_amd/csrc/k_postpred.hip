@@ -31,6 +31,7 @@
 #include <numeric>
 
 #include "internal.h"
+#include "rows_dev.h"
 #include "sampler_internal.h"
 
 namespace gpemu {
@@ -230,32 +231,11 @@ static int select_check(int64_t R, int64_t S, int64_t n_ranks, const int64_t *ra
   return GPEMU_OK;
 }
 
-static int device_ready(int device) {
-  int n = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) {
-    set_error("no HIP device available: libgpemu has no CPU implementation");
-    return GPEMU_ERR_NO_DEVICE;
-  }
-  GP_ARG(device >= 0 && device < n, "device out of range");
-  GP_HIP(hipSetDevice(device));
-  return GPEMU_OK;
-}
-
 // ---- posterior predictive ------------------------------------------------------------------------------------------
 static __device__ __forceinline__ double pp_wave_sum(double s) {
 #pragma unroll
   for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off, 64);
   return s;
-}
-
-// logical rows [r0, r0 + n) of the block layout -> dst[n][d]
-__global__ __launch_bounds__(256) void pp_gather_kernel(const double *__restrict__ X, int64_t block_rows,
-                                                        int64_t block_stride_rows, int d, int64_t r0, int64_t n,
-                                                        double *__restrict__ dst) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n * d) return;
-  const int64_t r = r0 + i / d;
-  dst[i] = X[((r / block_rows) * block_stride_rows + r % block_rows) * d + i % d];
 }
 
 // workgroup (256 samples, PP_FT features): W[(f - f0) ldw + s] = central value of feature f for sample s
@@ -369,17 +349,9 @@ int gpemu_select_dev(int device, int64_t R, int64_t S, const double *dV, int64_t
 int gpemu_select(int device, int64_t R, int64_t S, const double *V, int64_t n_ranks, const int64_t *ranks, double *out) {
   GP_ARG(V && out, "null pointer");
   GP_TRY(select_check(R, S, n_ranks, ranks));
-  GP_TRY(device_ready(device));
-  hipStream_t st = nullptr;
-  DevScope sc(st);
-  double *dV = nullptr, *dout = nullptr;
-  GP_TRY(sc.alloc(&dV, R * S));
-  GP_TRY(sc.alloc(&dout, R * n_ranks));
-  GP_TRY(upload(dV, V, R * S, st));
-  GP_TRY(select_rows(dV, R, S, S, 1, n_ranks, ranks, dout, n_ranks, st));
-  GP_TRY(sc.download(out, dout, R * n_ranks));
-  GP_HIP(hipStreamSynchronize(st));
-  return GPEMU_OK;
+  return with_host_rows(device, R, S, V, n_ranks, out, [&](const double *dV, double *dout, hipStream_t st) {
+    return select_rows(dV, R, S, S, 1, n_ranks, ranks, dout, n_ranks, st);
+  });
 }
 
 int gpemu_posterior_predictive_dev(gpemu_model *m, const double *dX, int64_t n_blocks, int64_t block_rows,
@@ -387,8 +359,8 @@ int gpemu_posterior_predictive_dev(gpemu_model *m, const double *dX, int64_t n_b
                                    int64_t workspace_bytes, double *dmean, double *dvar_param, double *dvar_emu,
                                    double *dorder, void *stream) {
   GP_ARG(m && dX, "null pointer");
-  GP_ARG(n_blocks > 0 && block_rows > 0, "n_blocks and block_rows must be positive");
-  GP_ARG(n_blocks == 1 || block_stride_rows >= block_rows, "block_stride_rows must be >= block_rows");
+  const RowsView X{dX, n_blocks, block_rows, block_stride_rows * m->d, (int)m->d};
+  GP_TRY(rows_check(X));
   GP_ARG(n_blocks <= INT64_MAX / block_rows, "n_blocks * block_rows overflows");
   GP_ARG(workspace_bytes >= 0, "workspace_bytes must be >= 0");
   GP_ARG(n_ranks >= 0, "n_ranks must be >= 0");
@@ -401,12 +373,8 @@ int gpemu_posterior_predictive_dev(gpemu_model *m, const double *dX, int64_t n_b
   hipStream_t st = stream ? (hipStream_t)stream : m->stream;
 
   // the plan: the PC arrays stay resident, the features go through the workspace in blocks
-  int64_t budget = workspace_bytes;
-  if (budget == 0) {
-    size_t fb = 0, tb = 0;
-    GP_HIP(hipMemGetInfo(&fb, &tb));
-    budget = (int64_t)(fb / 2);
-  }
+  int64_t budget = 0;
+  GP_TRY(workspace_budget(workspace_bytes, &budget));
   const int64_t pc_bytes = 2 * S * k * 8;
   const bool want_ws = dmean || dvar_param || n_ranks > 0;
   int64_t Fb = F;
@@ -418,7 +386,7 @@ int gpemu_posterior_predictive_dev(gpemu_model *m, const double *dX, int64_t n_b
       set_error("posterior_predictive: out of memory: %lld rows need %lld bytes of PC arrays, %lld bytes of scratch and "
                 "%lld bytes for one block of 16 features; %lld bytes %s", (long long)S, (long long)pc_bytes,
                 (long long)PP_FIXED, (long long)(std::min<int64_t>(F, 16) * 8 * S), (long long)budget,
-                workspace_bytes ? "allowed by workspace_bytes" : "available (half of the free device memory)");
+                workspace_budget_name(workspace_bytes));
       return GPEMU_ERR_HIP;
     }
   }
@@ -428,8 +396,7 @@ int gpemu_posterior_predictive_dev(gpemu_model *m, const double *dX, int64_t n_b
   double *Mpc = nullptr, *Vpc = nullptr, *stage = nullptr, *W = nullptr, *part = nullptr, *vbar = nullptr, *mu = nullptr;
   GP_TRY(sc.alloc(&Mpc, S * k));
   GP_TRY(sc.alloc(&Vpc, S * k));
-  const bool contiguous = n_blocks == 1 || block_stride_rows == block_rows;
-  if (!contiguous) GP_TRY(sc.alloc(&stage, PP_CHUNK * d));
+  if (!X.dense()) GP_TRY(sc.alloc(&stage, PP_CHUNK * d));
   GP_TRY(sc.alloc(&part, std::max(Fb, k) * nchunk));
   GP_TRY(sc.alloc(&vbar, k));
   GP_TRY(sc.alloc(&mu, F));
@@ -437,17 +404,13 @@ int gpemu_posterior_predictive_dev(gpemu_model *m, const double *dX, int64_t n_b
 
   for (int64_t r0 = 0; r0 < S; r0 += PP_CHUNK) {
     const int64_t nb = std::min(PP_CHUNK, S - r0);
-    const double *src = nullptr;
-    if (contiguous) {
+    const double *src = stage;
+    if (X.dense())
       src = dX + r0 * d;
-    } else if (r0 / block_rows == (r0 + nb - 1) / block_rows) {   // the chunk lies within one block
-      src = dX + ((r0 / block_rows) * block_stride_rows + r0 % block_rows) * d;
-    } else {
-      hipLaunchKernelGGL(pp_gather_kernel, dim3((unsigned)((nb * d + 255) / 256)), dim3(256), 0, st, dX, block_rows,
-                         block_stride_rows, (int)d, r0, nb, stage);
-      GP_HIP(hipGetLastError());
-      src = stage;
-    }
+    else if (r0 / block_rows == (r0 + nb - 1) / block_rows)   // the chunk lies within one block
+      src = X.row(r0);
+    else
+      GP_TRY(gather_rows(X, r0, nb, stage, st));
     GP_TRY(gpemu_gp_predict_dev(m, nb, src, Mpc + r0 * k, Vpc + r0 * k, st));
   }
 

@@ -33,6 +33,7 @@
 
 #include "internal.h"
 #include "predict_dev.h"
+#include "rows_dev.h"
 
 namespace gpemu {
 
@@ -354,18 +355,14 @@ int gpemu_sobol_moments_dev(gpemu_model *m, int64_t n, const double *dA, const d
   const int64_t nslices = (int64_t)start.size() - 1;
   for (int64_t t = 0; t < T; ++t) count[t] = start[(size_t)first[(size_t)t + 1]] - start[(size_t)first[(size_t)t]];
 
-  int64_t budget = workspace_bytes;
-  if (budget == 0) {
-    size_t fb = 0, tb = 0;
-    GP_HIP(hipMemGetInfo(&fb, &tb));
-    budget = (int64_t)(fb / 2);
-  }
+  int64_t budget = 0;
+  GP_TRY(workspace_budget(workspace_bytes, &budget));
   const int64_t npiv = std::min(n, SB_PIVOT);
   int64_t cap = std::min(budget / row_bytes, n);          // rows of means the workspace holds
   if (cap < std::min<int64_t>(n, SB_SLICE)) {
     set_error("sobol_moments: out of memory: one slice of %lld rows needs %lld bytes of PC means; %lld bytes %s",
               (long long)std::min<int64_t>(n, SB_SLICE), (long long)(std::min<int64_t>(n, SB_SLICE) * row_bytes),
-              (long long)budget, workspace_bytes ? "allowed by workspace_bytes" : "available (half of the free device memory)");
+              (long long)budget, workspace_budget_name(workspace_bytes));
     return GPEMU_ERR_HIP;
   }
 

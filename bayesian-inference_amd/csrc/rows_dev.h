@@ -1,0 +1,90 @@
+// What the summaries of a stored chain share (k_rows.hip): the view of a chain as blocks of rows with its
+// check and its gather, the pooled moments, the workspace budget, the key-only radix sort of rows with its scratch, and
+// the host form of a function of device rows.  The summaries' own kernels -- selection, histograms, window search,
+// density, split, rank lookup -- stay in their files.
+#pragma once
+#include <algorithm>
+
+#include "internal.h"
+#include "sampler_internal.h"
+
+namespace gpemu {
+
+// ---- rows in blocks ------------------------------------------------------------------------------------------------
+// n_blocks blocks of block_rows rows of d doubles; block b starts block_stride ELEMENTS after block b - 1 (a stride in
+// elements: a step of a chain may be padded to a length that is no multiple of d).  Logical row r is row r % block_rows
+// of block r / block_rows: the sampler's chain in place, thinned by steps, one chain of a stacked sampler.
+struct RowsView {
+  const double *base;
+  int64_t n_blocks, block_rows, block_stride;
+  int d;
+  __host__ __device__ int64_t rows() const { return n_blocks * block_rows; }
+  __host__ __device__ const double *row(int64_t r) const {
+    return base + (r / block_rows) * block_stride + (r % block_rows) * d;
+  }
+  bool dense() const { return n_blocks == 1 || block_stride == block_rows * d; }
+};
+// GPEMU_ERR_ARG unless the blocks are non-empty and do not overlap; the callers add their own limits
+int rows_check(const RowsView &v);
+// dst[n][d] = logical rows [r0, r0 + n) of v; asynchronous on st
+int gather_rows(const RowsView &v, int64_t r0, int64_t n, double *dst, hipStream_t st);
+
+// ---- pooled moments ------------------------------------------------------------------------------------------------
+// dmom[0 .. d) = mean, dmom[d .. 2d) = variance (divisor R) of the R rows of dx [R][d], two passes with sums in a fixed
+// order; dpart: (R + MOM_ROWS - 1) / MOM_ROWS * d doubles of scratch; asynchronous on st
+constexpr int MOM_ROWS = 1024;
+int launch_moments(const double *dx, int64_t R, int d, double *dpart, double *dmom, hipStream_t st);
+// ... with its scratch, into host mean [d] and var [d]; waits for st
+int moments_to_host(const double *dx, int64_t R, int d, double *mean, double *var, hipStream_t st);
+
+// ---- workspace budget ----------------------------------------------------------------------------------------------
+// *budget = workspace_bytes, or half of the free memory of the current device where that is 0
+int workspace_budget(int64_t workspace_bytes, int64_t *budget);
+// how an out-of-memory message names that budget, after "%lld bytes "
+const char *workspace_budget_name(int64_t workspace_bytes);
+
+// ---- key-only LSD radix sort of rows of doubles (the kernels' comments: k_rows.hip) ----------------------------------
+constexpr int RK_PASSES = 8;       // 8 bits each
+constexpr int RK_BINS = 256;
+constexpr int RK_TILE = 2048;      // keys per workgroup: 4 waves x 8 rounds x 64 lanes
+
+static __device__ __forceinline__ u64 rk_key(double v) {
+  if (v == 0.0) v = 0.0;   // -0 and +0 are tied
+  return sel_key(v);
+}
+
+// bytes of the sort's buffers for one row of S elements: two key arrays, the (digit, tile) histogram, the NaN flag
+static inline int64_t rank_row_bytes(int64_t S) { return 16 * S + 4 * RK_BINS * ((S + RK_TILE - 1) / RK_TILE) + 4; }
+// rows of S elements per batch: what budget holds at per_row bytes each, at most R, and no more than a flattened grid
+// of (rows, 256-element blocks) -- or of (rows, grid_per_row workgroups) -- can address.  Below 1: out of memory
+int64_t sort_rows_cap(int64_t R, int64_t S, int64_t budget, int64_t per_row, int64_t grid_per_row = 1);
+
+struct SortScratch {
+  u64 *ka = nullptr, *kb = nullptr;   // [rows_cap][S] keys; the sorted keys end in ka
+  unsigned *hist = nullptr;           // [rows_cap][RK_BINS][tiles]
+  int *nan = nullptr;                 // [rows_cap] the row holds a NaN
+  int alloc(DevScope &sc, int64_t rows_cap, int64_t S);
+};
+// sorts the keys of `rows` rows from row0 on (elements dV[row row_stride + i elem_stride], i < S) into s.ka; s.nan[rl] = 1
+// for a row that holds a NaN.  on_pass() is called once per pass (path counters).  Asynchronous on st
+int sort_rows(const double *dV, int64_t row_stride, int64_t elem_stride, int64_t S, int64_t row0, int64_t rows,
+              const SortScratch &s, void (*on_pass)(), hipStream_t st);
+
+// ---- the host form of a function of device rows --------------------------------------------------------------------
+// device_ready, V [R][S] to the device, fn(dV, dout, stream) on rows of strides (S, 1), dout [R][out_per_row] back, wait
+template <class Fn>
+static int with_host_rows(int device, int64_t R, int64_t S, const double *V, int64_t out_per_row, double *out, Fn &&fn) {
+  GP_TRY(device_ready(device));
+  hipStream_t st = nullptr;
+  DevScope sc(st);
+  double *dV = nullptr, *dout = nullptr;
+  GP_TRY(sc.alloc(&dV, R * S));
+  GP_TRY(sc.alloc(&dout, R * out_per_row));
+  GP_TRY(upload(dV, V, R * S, st));
+  GP_TRY(fn(dV, dout, st));
+  GP_TRY(sc.download(out, dout, R * out_per_row));
+  GP_HIP(hipStreamSynchronize(st));
+  return GPEMU_OK;
+}
+
+}  // namespace gpemu

@@ -1,5 +1,6 @@
-// Sampler state shared by k_sampler.hip (stretch move, phase API, RCCL run), k_front.hip (fused run) and k_temper.hip
-// (parallel tempering).
+// Sampler state shared by k_sampler.hip (stretch move, phase API, RCCL run), k_front.hip (fused run), k_temper.hip
+// (parallel tempering), k_hmc.hip (Hamiltonian Monte Carlo), k_acf.hip (autocorrelation) and the summaries of the stored
+// chain: k_postpred.hip, k_diag.hip, k_marginal.hip and what they share, k_rows.hip (rows_dev.h).
 #pragma once
 #include <vector>
 
@@ -144,7 +145,7 @@ struct gpemu_sampler {
 
 namespace gpemu {
 // order-preserving 64-bit key of a double (negative: all bits flipped, else the sign bit set) and its inverse: the
-// radix select (k_postpred.hip) and the radix sort (k_diag.hip)
+// radix select (k_postpred.hip) and the radix sort (k_rows.hip)
 typedef unsigned long long u64;
 static __device__ __forceinline__ u64 sel_key(double v) {
   const u64 u = (u64)__double_as_longlong(v);
@@ -166,12 +167,6 @@ __global__ __launch_bounds__(256) void acf_reduce_kernel(const double *__restric
                                   double *__restrict__ acf, double *__restrict__ acf0, int is_first);
 constexpr int ACF_LPT = 16;      // lags per thread
 constexpr int ACF_TCHUNKS = 8;   // chunks of steps (partial sums)
-// k_hmc.hip: pooled sums of a flattened chain [R][d] (moments_partial_kernel: MOM_ROWS rows per workgroup)
-constexpr int MOM_ROWS = 1024;
-__global__ __launch_bounds__(256) void moments_partial_kernel(const double *__restrict__ x, int64_t R, int d, const double *__restrict__ mean,
-                                       double *__restrict__ part);
-__global__ __launch_bounds__(256) void moments_final_kernel(const double *__restrict__ part, int64_t nb, int d, int64_t R,
-                                     double *__restrict__ out);
 // k_sampler.hip
 int sampler_launch_rng(gpemu_sampler *s, hipStream_t st, int64_t ahead);
 int sampler_ensure_chain(gpemu_sampler *s, int64_t need);

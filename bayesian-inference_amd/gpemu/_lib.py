@@ -296,3 +296,16 @@ def as_f64(a, shape=None):
 
 def ptr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def is_device_tensor(x):
+    """Is ``x`` a torch tensor in device memory?  (Asked without importing torch.)"""
+    return type(x).__module__.startswith("torch") and hasattr(x, "data_ptr") and x.is_cuda
+
+
+def current_stream(device):
+    """torch's current stream on ``device`` (an index or a ``torch.device``), as the ``void *stream`` of the ``_dev``
+    calls: their launches are ordered with the caller's torch work."""
+    import torch
+    dev = device if isinstance(device, torch.device) else torch.device("cuda", int(device))
+    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)

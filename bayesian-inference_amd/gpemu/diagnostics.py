@@ -100,17 +100,16 @@ class Diag:
         if _handle is not None:
             self._h, (self.n, self.M, self.d) = _handle, _shape
             return
-        if type(chain).__module__.startswith("torch") and hasattr(chain, "data_ptr") and chain.is_cuda:
+        if _lib.is_device_tensor(chain):
             import torch
             if chain.dtype != torch.float64 or chain.dim() != 3:
                 raise TypeError("a device chain must be a float64 tensor [n][M][d]")
             chain = chain.contiguous()
             self._keep = chain
             n, M, d = (int(v) for v in chain.shape)
-            stream = torch.cuda.current_stream(chain.device).cuda_stream
             check(_lib.lib().gpemu_diag_create_dev(C.byref(self._h), int(chain.device.index or 0),
                                                    C.c_void_p(chain.data_ptr()), n, M * d, 0, M, d, int(workspace_bytes),
-                                                   C.c_void_p(stream)))
+                                                   _lib.current_stream(chain.device)))
         else:
             x = np.asarray(chain, dtype=np.float64)
             if x.ndim == 2:

@@ -108,13 +108,9 @@ def credible_levels(hist_2d, probabilities):
 
 
 # -- device plumbing ------------------------------------------------------------------------------------------------
-def _is_device_tensor(values):
-    return type(values).__module__.startswith("torch") and hasattr(values, "data_ptr") and values.is_cuda
-
-
 def _samples(samples):
     """``(array or tensor (S, d), on_device)``; a vector is one parameter."""
-    if _is_device_tensor(samples):
+    if _lib.is_device_tensor(samples):
         import torch
         if samples.dtype != torch.float64 or samples.dim() not in (1, 2):
             raise TypeError("device samples must be a float64 tensor (S, d)")
@@ -135,11 +131,6 @@ def _check_shape(S, d):
         raise ValueError(f"d must be in [1, {MAX_D}], got {d}")
 
 
-def _stream(device):
-    import torch
-    return C.c_void_p(torch.cuda.current_stream(torch.device("cuda", int(device))).cuda_stream)
-
-
 def _hist_dev(device, base, n_blocks, block_rows, block_stride_rows, d, e1, e2, group_counters=0):
     """The histograms of device rows in the block layout: ``(hist_1d, hist_2d, n_inside)`` as numpy int64."""
     import torch
@@ -151,7 +142,7 @@ def _hist_dev(device, base, n_blocks, block_rows, block_stride_rows, d, e1, e2, 
     check(_lib.lib().gpemu_marginal_hist_dev(int(device), C.c_void_p(base), int(n_blocks), int(block_rows),
                                              int(block_stride_rows), int(d), int(nb1), ptr(e1), int(nb2), ptr(e2),
                                              int(group_counters), C.c_void_p(h1.data_ptr()), C.c_void_p(h2.data_ptr()),
-                                             C.c_void_p(ni.data_ptr()), _stream(device)))
+                                             C.c_void_p(ni.data_ptr()), _lib.current_stream(device)))
     return h1.cpu().numpy(), h2[:npairs].cpu().numpy(), ni.cpu().numpy()
 
 
@@ -161,7 +152,7 @@ def _hpd_dev(device, base, S, d, n_out, workspace_bytes=0):
     n_out = np.ascontiguousarray(n_out, dtype=np.int64)
     out = torch.empty((d, n_out.size, 2), dtype=torch.float64, device=torch.device("cuda", int(device)))
     check(_lib.lib().gpemu_hpd_dev(int(device), int(d), int(S), C.c_void_p(base), 1, int(d), int(n_out.size), ptr(n_out),
-                                   C.c_void_p(out.data_ptr()), int(workspace_bytes), _stream(device)))
+                                   C.c_void_p(out.data_ptr()), int(workspace_bytes), _lib.current_stream(device)))
     return np.ascontiguousarray(out.cpu().numpy().transpose(1, 0, 2))
 
 
@@ -170,7 +161,7 @@ def _kde_dev(device, base, S, d, grid, h):
     import torch
     out = torch.empty(grid.shape, dtype=torch.float64, device=torch.device("cuda", int(device)))
     check(_lib.lib().gpemu_kde1d_dev(int(device), int(d), int(S), C.c_void_p(base), 1, int(d), int(grid.shape[1]),
-                                     ptr(grid), ptr(h), C.c_void_p(out.data_ptr()), _stream(device)))
+                                     ptr(grid), ptr(h), C.c_void_p(out.data_ptr()), _lib.current_stream(device)))
     return out.cpu().numpy()
 
 
@@ -178,7 +169,7 @@ def _moments_dev(device, base, S, d):
     """``(mean, var with divisor S)`` of a dense device matrix ``[S][d]``."""
     mean, var = np.empty(d), np.empty(d)
     check(_lib.lib().gpemu_marginal_moments_dev(int(device), C.c_void_p(base), int(S), int(d), ptr(mean), ptr(var),
-                                                _stream(device)))
+                                                _lib.current_stream(device)))
     return mean, var
 
 
@@ -241,7 +232,7 @@ def hpd_intervals(samples, confidence=0.9, axis=0, device=None, workspace_bytes=
     """Highest-posterior-density intervals by the reference's rule (``credible_interval(x, confidence, 'hpd')`` per
     parameter): ``(n_levels, d, 2)``, or ``(d, 2)`` for a scalar confidence, ``[..., 0]`` the lower end.  Both ends
     are elements of the input.  A parameter with a NaN or an infinite extreme gives NaN."""
-    if _is_device_tensor(samples):
+    if _lib.is_device_tensor(samples):
         x, _ = _samples(samples if axis in (0, -samples.dim()) else samples.movedim(axis, 0))
         S, d = int(x.shape[0]), int(x.shape[1])
         _check_shape(S, 1)

@@ -72,6 +72,28 @@ def function_1d(x):
     return acf
 
 
+def _check_tolerance(tau_est, n_t, tol, quiet):
+    """``tau_est``, unless the chain of ``n_t`` steps is shorter than ``tol`` times one of them: then emcee's
+    AutocorrError, or with ``quiet`` its message as a warning (emcee.autocorr.integrated_time)."""
+    flag = tol * tau_est > n_t
+    if np.any(flag):
+        msg = ("The chain is shorter than {0} times the integrated autocorrelation time for {1} "
+               "parameter(s). Use this estimate with caution and run a longer chain!\n"
+               ).format(tol, np.sum(flag))
+        msg += "N/{0} = {1:.0f};\ntau: {2}".format(tol, n_t / tol, tau_est)
+        if not quiet:
+            raise AutocorrError(tau_est, msg)
+        logging.getLogger(__name__).warning(msg)            # emcee logs the message when quiet (autocorr.py)
+    return tau_est
+
+
+def _check_run(rc):
+    """The status of a call that ran the chain: 1 is a NaN log-probability, raised as emcee raises it."""
+    if rc == 1:
+        raise ValueError("Probability function returned NaN")
+    check(rc)
+
+
 def integrated_time(x, c=5, tol=50, quiet=False):
     """Integrated autocorrelation time per dimension with Sokal's window
     (emcee.autocorr.integrated_time; x has shape (steps, walkers, ndim))."""
@@ -101,16 +123,7 @@ def integrated_time(x, c=5, tol=50, quiet=False):
         m = np.arange(len(taus)) < c * taus
         windows[d] = np.argmin(m) if np.any(m) else len(taus) - 1
         tau_est[d] = taus[windows[d]]
-    flag = tol * tau_est > n_t
-    if np.any(flag):
-        msg = ("The chain is shorter than {0} times the integrated autocorrelation time for {1} "
-               "parameter(s). Use this estimate with caution and run a longer chain!\n"
-               ).format(tol, np.sum(flag))
-        msg += "N/{0} = {1:.0f};\ntau: {2}".format(tol, n_t / tol, tau_est)
-        if not quiet:
-            raise AutocorrError(tau_est, msg)
-        logging.getLogger(__name__).warning(msg)            # emcee logs the message when quiet (autocorr.py)
-    return tau_est
+    return _check_tolerance(tau_est, n_t, tol, quiet)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -180,21 +193,15 @@ class DeviceSampler:
         check(_lib.lib().gpemu_sampler_reserve_chain(self._h, int(steps)))
 
     def run(self, steps, store=True):
-        rc = _lib.lib().gpemu_sampler_run(self._h, int(steps), int(bool(store)))
-        if rc == 1:
-            raise ValueError("Probability function returned NaN")
-        check(rc)
+        _check_run(_lib.lib().gpemu_sampler_run(self._h, int(steps), int(bool(store))))
 
     def step_host_rng(self, inds, zz, rint, logu, store=True):
         inds = np.ascontiguousarray(inds, dtype=np.int32)
         zz = as_f64(np.concatenate(zz), (self.W,))
         logu = as_f64(np.concatenate(logu), (self.W,))
         rint = np.ascontiguousarray(np.concatenate(rint), dtype=np.int64)
-        rc = _lib.lib().gpemu_sampler_step_host_rng(self._h, ptr(inds), ptr(zz), ptr(rint), ptr(logu),
-                                                    int(bool(store)))
-        if rc == 1:
-            raise ValueError("Probability function returned NaN")
-        check(rc)
+        _check_run(_lib.lib().gpemu_sampler_step_host_rng(self._h, ptr(inds), ptr(zz), ptr(rint), ptr(logu),
+                                                          int(bool(store))))
 
     def counts(self):
         nacc = np.zeros(self.W, dtype=np.int64)
@@ -231,6 +238,20 @@ class DeviceSampler:
         check(_lib.lib().gpemu_sampler_chain_ptr(self._h, int(first), C.byref(p), C.byref(n)))
         return int(p.value or 0), int(n.value)
 
+    def _stored_view(self, discard, thin, chain):
+        """The stored chain ``get_chain()[discard::thin]`` of ``chain`` as rows in blocks on the device: ``(address of
+        walker w0 of step discard, n_blocks, nw, block stride in rows, S = n_blocks * nw)`` -- a block is the chain's
+        walkers of one kept step."""
+        discard, thin = int(discard), int(thin)
+        if thin < 1 or discard < 0:
+            raise ValueError("discard must be >= 0 and thin >= 1")
+        w0, nw = self._chain_walkers(chain)
+        if discard >= self.counts()[2]:
+            raise ValueError("no stored steps after discard")
+        base, n = self.chain_ptr(discard)
+        n_blocks = (n + thin - 1) // thin
+        return base + 8 * w0 * self.d, n_blocks, nw, thin * self.W, n_blocks * nw
+
     def posterior_predictive(self, models=None, discard=0, thin=1, probabilities=(0.05, 0.5, 0.95), chain=None,
                              workspace_bytes=0):
         """``DeviceModel.posterior_predictive`` of the stored chain ``get_chain()[discard::thin]`` (all walkers of the
@@ -240,14 +261,8 @@ class DeviceSampler:
         import torch
         from .model import QuantilePlan
         models = self.models if models is None else list(models)
-        if int(thin) < 1 or int(discard) < 0:
-            raise ValueError("discard must be >= 0 and thin >= 1")
-        w0, nw = self._chain_walkers(chain)
-        base, n = self.chain_ptr(int(discard))
-        if n < 1:
-            raise ValueError("no stored steps after discard")
-        n_blocks = (n + int(thin) - 1) // int(thin)
-        plan = QuantilePlan(n_blocks * nw, probabilities)
+        src, n_blocks, nw, stride, S = self._stored_view(discard, thin, chain)
+        plan = QuantilePlan(S, probabilities)
         dev = torch.device("cuda", self.device)
         out = []
         for m in models:
@@ -255,7 +270,7 @@ class DeviceSampler:
                 raise ValueError("model and sampler differ in parameters or device")
             bufs = torch.empty((3 + max(plan.ranks.size, 1), m.F), dtype=torch.float64, device=dev)
             order = bufs[3:].reshape(-1)          # [F][n_ranks] as the library writes it
-            m.posterior_predictive_dev(base + 8 * w0 * self.d, n_blocks, nw, int(thin) * self.W, plan.ranks,
+            m.posterior_predictive_dev(src, n_blocks, nw, stride, plan.ranks,
                                        bufs[0].data_ptr(), bufs[1].data_ptr(), bufs[2].data_ptr(),
                                        order.data_ptr() if plan.ranks.size else 0, workspace_bytes=workspace_bytes)
             h = bufs.cpu().numpy()
@@ -269,20 +284,17 @@ class DeviceSampler:
         d of the device chain); one chain of a stacked sampler is not a single stride, so its walkers are copied out
         first and selected from that copy."""
         from . import select
-        w0, nw = self._chain_walkers(chain)
-        base, n = self.chain_ptr(int(discard))
-        if n < 1:
-            raise ValueError("no stored steps after discard")
+        src, n, nw, _, S = self._stored_view(discard, 1, chain)
         if nw != self.W:
             x = np.empty((n, nw, self.d))
             lp = np.empty((n, nw))
+            w0 = self._chain_walkers(chain)[0]
             check(_lib.lib().gpemu_sampler_get_chain_walkers(self._h, int(discard), n, w0, nw, ptr(x), ptr(lp)))
             return select.quantile(x.reshape(-1, self.d), probabilities, axis=0, device=self.device)
         import torch
-        S = n * self.W
         ranks, ilo, ihi, t = select._bracket(S, probabilities)
         dout = torch.empty((self.d, ranks.size), dtype=torch.float64, device=torch.device("cuda", self.device))
-        check(_lib.lib().gpemu_select_dev(self.device, self.d, S, C.c_void_p(base), 1, self.d, int(ranks.size), ptr(ranks),
+        check(_lib.lib().gpemu_select_dev(self.device, self.d, S, C.c_void_p(src), 1, self.d, int(ranks.size), ptr(ranks),
                                           C.c_void_p(dout.data_ptr()), None))
         sel = dout.cpu().numpy()
         q = select.lerp(sel[:, ilo].T, sel[:, ihi].T, t[:, None])
@@ -307,15 +319,8 @@ class DeviceSampler:
         autocorrelation time (``integrated_time``) for an ensemble; the chains of an ``HMCSampler`` are independent and
         the statistics mean what they mean in Stan.  Stacked samplers take ``chain=<index>``."""
         from .diagnostics import Diag
-        discard, thin = int(discard), int(thin)
-        if thin < 1 or discard < 0:
-            raise ValueError("discard must be >= 0 and thin >= 1")
-        w0, nw = self._chain_walkers(chain)
-        _, _, cl = self.counts()
-        n = (cl - discard + thin - 1) // thin
-        if n < 1:
-            raise ValueError("no stored steps after discard")
-        with Diag.from_sampler(self._h, discard, n, thin, w0, nw, self.d) as h:
+        _, n, nw, _, _ = self._stored_view(discard, thin, chain)
+        with Diag.from_sampler(self._h, int(discard), n, int(thin), self._chain_walkers(chain)[0], nw, self.d) as h:
             return h.summary()
 
     def marginals(self, lower=None, upper=None, bins_1d=100, bins_2d=50, confidence=(0.9,), kde=True, n_grid=200,
@@ -329,9 +334,7 @@ class DeviceSampler:
         dense device buffer.  Stacked samplers take ``chain=<index>``."""
         import torch
         from . import marginals as M
-        discard, thin = int(discard), int(thin)
-        if thin < 1 or discard < 0:
-            raise ValueError("discard must be >= 0 and thin >= 1")
+        src, n_blocks, nw, stride, S = self._stored_view(discard, thin, chain)
         if lower is None or upper is None:
             box = getattr(self.models[0], "prior_box", None)
             if box is None:
@@ -342,22 +345,16 @@ class DeviceSampler:
         e1, e2 = M.bin_edges(lower, upper, bins_1d), M.bin_edges(lower, upper, bins_2d)
         if e1.shape[0] != self.d:
             raise ValueError(f"the box has {e1.shape[0]} parameters, the sampler {self.d}")
-        w0, nw = self._chain_walkers(chain)
-        base, n = self.chain_ptr(discard)
-        if n < 1:
-            raise ValueError("no stored steps after discard")
-        n_blocks = (n + thin - 1) // thin
-        S, d = n_blocks * nw, self.d
+        d = self.d
         conf = np.atleast_1d(np.asarray(confidence, dtype=np.float64))
         n_out = M.n_outside(conf, S)
-        src = base + 8 * w0 * d
-        h1, h2, ni = M._hist_dev(self.device, src, n_blocks, nw, thin * self.W, d, e1, e2)
+        h1, h2, ni = M._hist_dev(self.device, src, n_blocks, nw, stride, d, e1, e2)
         hist = {"edges_1d": e1, "edges_2d": e2, "hist_1d": h1, "pairs": M.pair_indices(d), "hist_2d": h2, "n_inside": ni}
         dense = None
-        if thin > 1 or nw != self.W:
+        if stride != nw:
             dense = torch.empty((S, d), dtype=torch.float64, device=torch.device("cuda", self.device))
-            check(_lib.lib().gpemu_marginal_dense_dev(self.device, C.c_void_p(src), n_blocks, nw, thin * self.W, d,
-                                                      C.c_void_p(dense.data_ptr()), M._stream(self.device)))
+            check(_lib.lib().gpemu_marginal_dense_dev(self.device, C.c_void_p(src), n_blocks, nw, stride, d,
+                                                      C.c_void_p(dense.data_ptr()), _lib.current_stream(self.device)))
             src = dense.data_ptr()
         # one sort serves the intervals and, as the level n_out = 1 (window 0: smallest, largest), the density's support
         ends = M._hpd_dev(self.device, src, S, d, np.append(n_out, 1) if kde else n_out)
@@ -419,16 +416,7 @@ class DeviceSampler:
             run = cs[-1]
             lag0 += nl
             block = min(block * 2, 4096)
-        flag = tol * tau_est > n_t
-        if np.any(flag):
-            msg = ("The chain is shorter than {0} times the integrated autocorrelation time for {1} "
-                   "parameter(s). Use this estimate with caution and run a longer chain!\n"
-                   ).format(tol, np.sum(flag))
-            msg += "N/{0} = {1:.0f};\ntau: {2}".format(tol, n_t / tol, tau_est)
-            if not quiet:
-                raise AutocorrError(tau_est, msg)
-            logging.getLogger(__name__).warning(msg)        # emcee logs the message when quiet (autocorr.py)
-        return tau_est
+        return _check_tolerance(tau_est, n_t, tol, quiet)
 
     # -- multi-GPU: one process per GPU, the ensemble replicated, proposals sharded -------------
     def _rccl_comm_agreed(self, group):
@@ -595,8 +583,7 @@ class DeviceSampler:
             vote(False)                                                  # (the peers must not wait for this rank's vote)
             check(rc)
         if vote(rc in (0, 1)):
-            if rc == 1:
-                raise ValueError("Probability function returned NaN")
+            _check_run(rc)
             return True
         check(L.gpemu_sampler_restore(self._h))
         return False
@@ -672,10 +659,7 @@ class DeviceSampler:
                 transport = "torch"
         if on_device and transport == "rccl":
             self.last_transport = "rccl"
-            rc = L.gpemu_sampler_run_sharded(self._h, comm, int(steps), int(bool(store)), int(emulate_world or 0))
-            if rc == 1:
-                raise ValueError("Probability function returned NaN")
-            check(rc)
+            _check_run(L.gpemu_sampler_run_sharded(self._h, comm, int(steps), int(bool(store)), int(emulate_world or 0)))
             return None
         self.last_transport = "torch"
         # a dedicated (non-null) torch stream carries the library's launches AND the collectives, so
@@ -714,10 +698,7 @@ class DeviceSampler:
                         full[h].copy_(host_full)
                     check(L.gpemu_sampler_half_accept(self._h, h, C.c_void_p(full[h].data_ptr()), int(bool(store))))
                 check(L.gpemu_sampler_end_step(self._h, int(bool(store))))
-            rc = L.gpemu_sampler_check(self._h)
-            if rc == 1:
-                raise ValueError("Probability function returned NaN")
-            check(rc)
+            _check_run(L.gpemu_sampler_check(self._h))
         finally:
             stream.synchronize()
             L.gpemu_sampler_set_stream(self._h, None)
@@ -930,10 +911,7 @@ class HMCSampler(DeviceSampler):
     def step_host_rng(self, p0, logu, eps_w, store=True):
         """One iteration with the caller's momenta ``p0 (W, d)``, log-uniforms and per-chain step sizes."""
         p0, logu, eps_w = as_f64(p0, (self.W, self.d)), as_f64(logu, (self.W,)), as_f64(eps_w, (self.W,))
-        rc = _lib.lib().gpemu_sampler_hmc_step_host_rng(self._h, ptr(p0), ptr(logu), ptr(eps_w), int(bool(store)))
-        if rc == 1:
-            raise ValueError("Probability function returned NaN")
-        check(rc)
+        _check_run(_lib.lib().gpemu_sampler_hmc_step_host_rng(self._h, ptr(p0), ptr(logu), ptr(eps_w), int(bool(store))))
 
     def warmup(self, n_warmup, target_accept=None, adapt_metric=True):
         """``n_warmup`` iterations of the three-stage warm-up (``gpemu.hmc.warmup_schedule``) from the current state.

@@ -68,8 +68,23 @@ def _bracket(S, probabilities):
     return ranks, inv[:lo.size], inv[lo.size:], t
 
 
-def _is_device_tensor(values):
-    return type(values).__module__.startswith("torch") and hasattr(values, "data_ptr") and values.is_cuda
+def _flat_rows(values, axis):
+    """A float64 device tensor with ``axis`` last and the other axes flattened to rows, for the strided ``_dev`` calls:
+    ``(flat (R, S), row stride, element stride, the other axes' shape)`` -- a view where torch can express the rows
+    by one stride, else a copy on the device."""
+    v = values.movedim(axis, -1)
+    S = v.shape[-1]
+    lead = v.shape[:-1]
+    R = int(np.prod(lead)) if lead else 1
+    if R == 0 or S == 0:
+        return None, 0, 0, lead
+    flat = v.reshape(R, S)
+    rs = flat.stride(0) if R > 1 else 1
+    es = flat.stride(1) if S > 1 else 1
+    if rs <= 0 or es <= 0:      # expanded (stride 0) tensors
+        flat = flat.contiguous()
+        rs, es = S, 1
+    return flat, int(rs), int(es), lead
 
 
 def _select_tensor(values, ranks, axis):
@@ -77,24 +92,15 @@ def _select_tensor(values, ranks, axis):
     import torch
     if values.dtype != torch.float64:
         raise TypeError("device selection needs float64 tensors")
-    v = values.movedim(axis, -1)
-    S = v.shape[-1]
-    ranks = check_ranks(ranks, S)
-    lead = v.shape[:-1]
-    R = int(np.prod(lead)) if lead else 1
-    if R == 0:
+    ranks = check_ranks(ranks, values.shape[axis])
+    flat, rs, es, lead = _flat_rows(values, axis)
+    if flat is None:
         raise ValueError("no rows to select from")
-    # rows = the flattened leading axes: a view where torch can express them by one stride, else a copy on the device
-    flat = v.reshape(R, S)
-    rs = flat.stride(0) if R > 1 else 1
-    es = flat.stride(1) if S > 1 else 1
-    if rs <= 0 or es <= 0:      # expanded (stride 0) tensors
-        flat = flat.contiguous()
-        rs, es = S, 1
+    R, S = flat.shape
     out = torch.empty((R, ranks.size), dtype=torch.float64, device=values.device)
-    stream = torch.cuda.current_stream(values.device).cuda_stream
-    check(_lib.lib().gpemu_select_dev(int(values.device.index or 0), R, S, C.c_void_p(flat.data_ptr()), int(rs), int(es),
-                                      int(ranks.size), ptr(ranks), C.c_void_p(out.data_ptr()), C.c_void_p(stream)))
+    check(_lib.lib().gpemu_select_dev(int(values.device.index or 0), R, S, C.c_void_p(flat.data_ptr()), rs, es,
+                                      int(ranks.size), ptr(ranks), C.c_void_p(out.data_ptr()),
+                                      _lib.current_stream(values.device)))
     return out.reshape(*lead, ranks.size).movedim(-1, 0)
 
 
@@ -102,7 +108,7 @@ def order_statistics(values, ranks, axis=-1, device=None):
     """The ``ranks``-th smallest elements (0-based) along ``axis``: shape ``(len(ranks), *values.shape without axis)``,
     equal as doubles to ``np.take(np.sort(values, axis), ranks, axis)`` moved to the front.  A slice that holds a NaN
     gives NaN for every rank."""
-    if _is_device_tensor(values):
+    if _lib.is_device_tensor(values):
         return _select_tensor(values, ranks, axis)
     _lib.require_device()
     v = np.moveaxis(np.asarray(values, dtype=np.float64), axis, -1)
@@ -128,7 +134,7 @@ def quantile(values, probabilities, axis=-1, device=None):
     S = values.shape[axis]
     ranks, ilo, ihi, t = _bracket(S, probabilities)
     sel = order_statistics(values, ranks, axis=axis, device=device)
-    if _is_device_tensor(values):
+    if _lib.is_device_tensor(values):
         import torch
         a, b = sel[torch.as_tensor(ilo, device=sel.device)], sel[torch.as_tensor(ihi, device=sel.device)]
         tt = torch.as_tensor(t, device=sel.device).reshape((-1,) + (1,) * (sel.dim() - 1))
@@ -146,26 +152,18 @@ def rankdata(values, axis=-1, device=None, workspace_bytes=0):
     bound of every element).  -0 and +0 are tied; a slice that holds a NaN is NaN throughout.  Host arrays give an
     array, float64 device tensors are read in place and give a tensor on the same device.  ``workspace_bytes`` bounds
     the sort's buffers for a batch of slices (0: half of the free device memory); the ranks do not depend on it."""
-    if _is_device_tensor(values):
+    if _lib.is_device_tensor(values):
         import torch
         if values.dtype != torch.float64:
             raise TypeError("device ranking needs float64 tensors")
-        v = values.movedim(axis, -1)
-        S = v.shape[-1]
-        lead = v.shape[:-1]
-        R = int(np.prod(lead)) if lead else 1
-        if R == 0 or S == 0:
+        flat, rs, es, lead = _flat_rows(values, axis)
+        if flat is None:
             raise ValueError("no elements to rank")
-        flat = v.reshape(R, S)
-        rs = flat.stride(0) if R > 1 else 1
-        es = flat.stride(1) if S > 1 else 1
-        if rs <= 0 or es <= 0:      # expanded (stride 0) tensors
-            flat = flat.contiguous()
-            rs, es = S, 1
+        R, S = flat.shape
         out = torch.empty((R, S), dtype=torch.float64, device=values.device)
-        stream = torch.cuda.current_stream(values.device).cuda_stream
-        check(_lib.lib().gpemu_rank_dev(int(values.device.index or 0), R, S, C.c_void_p(flat.data_ptr()), int(rs), int(es),
-                                        C.c_void_p(out.data_ptr()), int(workspace_bytes), C.c_void_p(stream)))
+        check(_lib.lib().gpemu_rank_dev(int(values.device.index or 0), R, S, C.c_void_p(flat.data_ptr()), rs, es,
+                                        C.c_void_p(out.data_ptr()), int(workspace_bytes),
+                                        _lib.current_stream(values.device)))
         return out.reshape(*lead, S).movedim(-1, axis)
     _lib.require_device()
     v = np.asarray(values, dtype=np.float64)
