@@ -204,6 +204,33 @@ def log_posterior(X):
     return log_post
 
 
+def observable_labels():
+    """The observable of every block of every group, in the order of ``log_likelihood_pointwise``'s rows (the groups'
+    order, each group's blocks in turn): the sorter's observable names, ``<group>`` for a group of one block without
+    a sorter."""
+    F = np.asarray(experimental_results['y']).shape[0]
+    obs, names = _observable_of_columns(F)
+    labels = []
+    for name, _, cols, starts in _group_layouts():
+        for o in range(len(starts) - 1):
+            i = obs[np.asarray(cols)[int(starts[o])]]
+            labels.append(str(names[i]) if len(names) > 1 or i < 0 else str(name))
+    return labels
+
+
+def log_likelihood_pointwise(X):
+    """``(labels, T)``: ``T (n_obs, n_samples)``, the log-likelihood term of every observable for each row of X -- the
+    terms whose sum over the observables is ``log_posterior`` of a single row inside the box (n_div =
+    1: every row on its own, as the sampler evaluates a walker).  A likelihood: no prior box.  Fully correlated sources
+    (``experimental_results['sys_sources']``) span the observables, so the likelihood is no sum of terms: ValueError."""
+    X = np.array(X, ndmin=2, dtype=np.float64)
+    if data_covariance()[1] is not None:
+        raise ValueError("log_likelihood_pointwise does not support experimental_results['sys_sources'] "
+                         "(fully correlated sources span the observables)")
+    from gpemu import loo
+    return observable_labels(), loo.pointwise(device_models(n_div=1.0), X)
+
+
 def log_posterior_and_gradient(X):
     """``(lp (B,), grad (B, d))``: the log-posterior of each row of X and its gradient with respect to the parameters
     (DESIGN.md §4.24), on the state ``initialize_pool_variables`` set.  Every row is evaluated on its own, as emcee

@@ -206,6 +206,7 @@ def _run_closure_batch(config, indices):
         _add_diagnostics(config, part, lambda c=c: sampler.diagnostics(chain=c), label=f'closure chain {indices[c]}')
         _add_marginals(config, part, lambda c=c, **kw: sampler.marginals(chain=c, **kw),
                        label=f'closure chain {indices[c]}')
+        _add_loo(config, part, lambda c=c, **kw: sampler.loo(chain=c, **kw), label=f'closure chain {indices[c]}')
         diags.append(part)
     sampler.close()
 
@@ -334,6 +335,7 @@ def run_mcmc(config, closure_index=-1):
                'log_prob': sampler.get_log_prob(), 'autocorrelation_time': tau}
     _add_diagnostics(config, results, sampler.get_diagnostics)
     _add_marginals(config, results, sampler.get_marginals)
+    _add_loo(config, results, lambda **kw: sampler.get_loo(models=log_posterior.device_models(n_div=1.0), **kw))
     if closure_index >= 0:
         validation_design = io.design_array_from_h5(config.output_dir, filename='observables.h5', validation_set=True)
         results['design_point'] = validation_design[closure_index]
@@ -460,6 +462,7 @@ def _run_tempered(config, closure_index):
     diag = {}
     _add_diagnostics(config, diag, lambda: sampler.diagnostics(temp=0), label='production chain (beta = 1)')
     _add_marginals(config, diag, lambda **kw: sampler.marginals(temp=0, **kw), label='production chain (beta = 1)')
+    _add_loo(config, diag, lambda **kw: sampler.loo(temp=0, **kw), label='production chain (beta = 1)')
     mean_ll = sampler.mean_log_likelihood()
     log_z, dlog_z = sampler.log_evidence_estimate()
     swap_frac = sampler.tswap_acceptance_fraction
@@ -569,6 +572,7 @@ def _run_hmc(config, closure_index):
     diag = {}
     _add_diagnostics(config, diag, sampler.diagnostics)
     _add_marginals(config, diag, sampler.marginals)
+    _add_loo(config, diag, sampler.loo)
     step_size, inverse_metric, divergences = sampler.step_size, sampler.inverse_metric, sampler.divergences
     sampler.close()
 
@@ -745,6 +749,104 @@ def marginals(config, closure_index=-1, discard=0, thin=1):
     config, chain = _stored_chain(config, closure_index, discard, thin)
     from gpemu import marginals as _marg
     return _marg.summary(np.ascontiguousarray(chain.reshape(-1, chain.shape[-1])), **_marginals_kwargs(config))
+
+
+def loo_settings(mc):
+    """``(on, leave_out)`` from the ``parameters.mcmc`` mapping: ``loo`` (true or false, default off) and the optional
+    ``loo_leave_out``, a non-empty list of non-empty lists of observable labels -- the classes of observables left out
+    together (default: every observable on its own).  DESIGN.md §4.31."""
+    on = mc.get('loo', False)
+    if not isinstance(on, (bool, np.bool_)):
+        raise ValueError(f"parameters.mcmc.loo must be true or false, got {on!r}")
+    groups = mc.get('loo_leave_out')
+    if groups is not None:
+        ok = isinstance(groups, (list, tuple)) and len(groups) > 0 and all(
+            isinstance(g, (list, tuple)) and len(g) > 0 and all(isinstance(v, str) and v for v in g) for g in groups)
+        if not ok:
+            raise ValueError("parameters.mcmc.loo_leave_out must be a non-empty list of non-empty lists of observable "
+                             f"labels, got {groups!r}")
+        groups = [[str(v) for v in g] for g in groups]
+    return bool(on), groups
+
+
+LOO_KEYS = ('labels', 'elpd_loo', 'p_loo', 'pareto_k', 'k_threshold', 'ess_w', 'elpd_waic', 'p_waic', 'lppd', 'se')
+LOO_SHIFT_KEYS = ('loo_mean', 'loo_sd', 'shift')
+
+
+def _loo_kwargs(config):
+    """``leave_out`` (rows of the terms, from the labels of ``parameters.mcmc.loo_leave_out``) and the observable
+    labels for ``DeviceSampler.loo`` / ``gpemu.loo.chain_loo``, on the pool's state."""
+    labels = log_posterior.observable_labels()
+    rows = None
+    if getattr(config, 'loo_leave_out', None):
+        rows = []
+        for group in config.loo_leave_out:
+            for name in group:
+                if labels.count(name) != 1:
+                    raise ValueError(f"parameters.mcmc.loo_leave_out names {name!r}; the observables are {labels}")
+            rows.append([labels.index(name) for name in group])
+    return labels, rows
+
+
+def _loo_entries(out, labels, rows):
+    """the ``loo_*`` entries of mcmc.h5 from a loo table: the observables by name"""
+    names = labels if rows is None else ['+'.join(labels[o] for o in g) for g in rows]
+    entries = {'loo_labels': np.array(names)}
+    for key in LOO_KEYS[1:-1]:
+        entries[f'loo_{key}'] = np.asarray(out[key], dtype=np.float64)
+    entries['loo_se'] = np.float64(out['se'])
+    for key in LOO_SHIFT_KEYS:
+        if key in out:
+            entries['loo_' + key.replace('loo_', 'weighted_')] = np.asarray(out[key], dtype=np.float64)
+    return entries
+
+
+def _add_loo(config, results, compute, label='production chain'):
+    """With ``parameters.mcmc.loo``: the ``loo_*`` entries of ``compute(leave_out=...)`` (a sampler's ``loo`` on the
+    chain where it lies) into the results that go to mcmc.h5, one log line, and a warning where a Pareto k-hat
+    exceeds its threshold."""
+    if not getattr(config, 'loo', False):
+        return
+    try:
+        labels, rows = _loo_kwargs(config)
+        out = compute(leave_out=rows)
+        entries = _loo_entries(out, labels, rows)
+    except Exception as err:         # the chain is worth more than the table: it is written either way
+        logger.warning(f'parameters.mcmc.loo: not computed ({err!r}); mcmc.h5 is written without the loo_* entries')
+        return
+    results.update(entries)
+    logger.info(f"PSIS-LOO of the {label}: elpd_loo {out['elpd_loo_total']:.3f} +- {out['se']:.3f}, p_loo "
+                f"{out['p_loo_total']:.3f} over {out['n_obs']} observables, {out['n_samples']} samples; largest Pareto "
+                f"k-hat {np.max(out['pareto_k']):.3f}")
+    if np.any(out['warning']):
+        bad = [str(n) for n, w in zip(entries['loo_labels'], out['warning']) if w]
+        logger.warning(f"Pareto k-hat above {out['k_threshold'][0]:.2f} for {bad}: their leave-one-out estimates are "
+                       "not reliable")
+
+
+def loo(config, closure_index=-1, discard=0, thin=1):
+    """The ``loo_*`` entries (``gpemu.loo.chain_loo``) of the chain stored in mcmc.h5 (of closure chain
+    ``closure_index``, if >= 0, against its stored pseudo-data), steps ``[discard::thin]``, all walkers."""
+    cfg, chain = _stored_chain(config, closure_index, discard, thin)
+    box = cfg.analysis_config['parameterization'][cfg.parameterization]
+    emu_cfg = emulation.EmulationConfig.from_config_file(
+        analysis_name=cfg.analysis_name, parameterization=cfg.parameterization,
+        analysis_config=cfg.analysis_config, config_file=cfg.config_file)
+    emu_results = emu_cfg.read_all_emulator_groups()
+    truncation_cov = emulation.compute_emulator_cov_unexplained(emu_cfg, emu_results)
+    io = _data_IO()
+    if closure_index >= 0:
+        data = io.read_dict_from_h5(cfg.mcmc_output_dir, 'mcmc.h5')['experimental_pseudodata']
+    else:
+        data = io.data_array_from_h5(cfg.output_dir, 'observables.h5', pseudodata_index=-1,
+                                     observable_filter=emu_cfg.observable_filter)
+    log_posterior.initialize_pool_variables(box['min'], box['max'], emu_cfg, emu_results,
+                                            _with_data_covariance(cfg, data), truncation_cov)
+    from gpemu import loo as _loo
+    labels, rows = _loo_kwargs(cfg)
+    out = _loo.chain_loo(log_posterior.device_models(n_div=1.0), np.ascontiguousarray(chain.reshape(-1, chain.shape[-1])),
+                         leave_out=rows)
+    return _loo_entries(out, labels, rows)
 
 
 POSTERIOR_PREDICTIVE_KEYS = ('mean', 'variance_parameters', 'variance_emulator', 'quantiles', 'probabilities')
@@ -954,6 +1056,9 @@ class MCMCConfig:
         # none without the key
         self.marginals, self.marginals_bins, self.marginals_confidence, self.marginals_kde = marginals_settings(
             mc, getattr(self, 'confidence', None))
+        # per-observable PSIS-LOO / WAIC and the observable-influence table of the production chain (optional, default
+        # off): loo_* in mcmc.h5, none without the key
+        self.loo, self.loo_leave_out = loo_settings(mc)
 
         # <output_dir>/<analysis>_<parameterization>[/closure/results/<index>]/{mcmc.h5, mcmc_sampler.pkl}
         self.output_dir = os.path.join(top['output_dir'], f'{analysis_name}_{parameterization}')

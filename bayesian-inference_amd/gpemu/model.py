@@ -2,6 +2,7 @@
 from __future__ import annotations
 
 import ctypes as C
+import math
 
 import numpy as np
 
@@ -350,6 +351,39 @@ class DeviceModel:
         out = np.empty(B)
         check(_lib.lib().gpemu_logpost(self._h, B, ptr(X), ptr(out), int(mode)))
         return out
+
+    # -- per-observable log-likelihood terms -------------------------------------------
+    @property
+    def n_observable_blocks(self):
+        """Observable blocks of the last ``likelihood_setup`` (``GpemuError`` -4 before it)."""
+        n = C.c_int64()
+        check(_lib.lib().gpemu_model_observable_blocks(self._h, C.byref(n)))
+        return int(n.value)
+
+    def _block_features(self):
+        """Features of every observable block of the last ``likelihood_setup``: ``(n_obs,)``."""
+        bs = getattr(self, "_lik_key", (None, None))[1]
+        return np.array([self.F], dtype=np.int64) if bs is None else np.diff(np.asarray(bs, dtype=np.int64))
+
+    def loglik_pointwise(self, X, normalised=False, chain=0):
+        """``T (n_obs, B)``: the log-likelihood term of every observable block for the rows of ``X (B, d)`` -- the terms
+        whose sum, for a row inside the prior box, is ``logpost`` (the same normalisation: no 2 pi constant;
+        ``normalised`` adds ``-(F_o / 2) log 2 pi`` per block).  A likelihood: the box is not applied; a row with a
+        non-finite coordinate gives NaN.  ``chain``: the data vector of a setup with several.  A setup with
+        ``sys_sources`` raises ``GpemuError`` (code -5): the sources span the blocks."""
+        X = self._X(X)
+        T = np.empty((self.n_observable_blocks, X.shape[0]))
+        check(_lib.lib().gpemu_loglik_pointwise(self._h, int(chain), X.shape[0], ptr(X), ptr(T)))
+        if normalised:
+            T -= 0.5 * math.log(2.0 * math.pi) * self._block_features()[:, None]
+        return T
+
+    def loglik_pointwise_dev(self, dX_ptr, n_blocks, block_rows, block_stride_rows, dT_ptr, ldt, chain=0, stream=0):
+        """The device-pointer entry: rows in the block layout of ``posterior_predictive_dev``, ``T`` block-major with
+        ``ldt >= n_blocks * block_rows`` doubles per observable.  Waits for the stream before it returns."""
+        check(_lib.lib().gpemu_loglik_pointwise_dev(self._h, int(chain), C.c_void_p(dX_ptr), int(n_blocks), int(block_rows),
+                                                    int(block_stride_rows), C.c_void_p(dT_ptr), int(ldt),
+                                                    C.c_void_p(stream)))
 
     # -- derivatives with respect to the parameters (DESIGN.md §4.24) -------------------------------------
     def gp_predict_grad(self, X):

@@ -368,6 +368,39 @@ class DeviceSampler:
         del dense
         return M.assemble(hist, conf, ends[:n_out.size], dens)
 
+    def _data_chain(self, chain):
+        """The data vector of the models' likelihood setup that ``chain`` of this sampler was run on."""
+        return 0 if self.n_chains == 1 else int(chain)
+
+    def loo(self, models=None, discard=0, thin=1, chain=None, leave_out=None, shifts=True, r_eff=None,
+            workspace_bytes=0):
+        """PSIS-LOO, WAIC and the observable-influence table (``gpemu.loo``) of the stored chain
+        ``get_chain()[discard::thin]``, read in place on the device: ``gpemu.loo.summary`` of the per-observable
+        log-likelihood terms of ``models`` (default: the sampler's groups), their rows concatenated in ``predict``'s
+        observable order, plus ``labels`` ``"g<group>o<block>"``.  ``leave_out`` sums rows first (a class of observables
+        left out together).  With ``shifts``: ``mean``, ``sd`` ``(d,)`` of the chain, ``loo_mean``, ``loo_sd`` ``(n_obs,
+        d)`` under each row's leave-one-out weights and ``shift = (loo_mean - mean) / sd`` -- how far leaving an observable
+        out moves each parameter, in posterior standard deviations.  Stacked samplers take ``chain=<index>`` (scored
+        against that chain's own data vector)."""
+        import torch
+        from . import loo as LO
+        models = self.models if models is None else list(models)
+        src, n_blocks, nw, stride, S = self._stored_view(discard, thin, chain)
+        dev = torch.device("cuda", self.device)
+        nobs = [m.n_observable_blocks for m in models]
+        T = torch.empty((sum(nobs), S), dtype=torch.float64, device=dev)
+        labels, o0 = [], 0
+        for g, (m, nb) in enumerate(zip(models, nobs)):
+            if m.d != self.d or m.device != self.device:
+                raise ValueError("model and sampler differ in parameters or device")
+            m.loglik_pointwise_dev(src, n_blocks, nw, stride, T[o0].data_ptr(), S, chain=self._data_chain(chain),
+                                   stream=_lib.current_stream(self.device).value or 0)
+            labels += [f"g{g}o{o}" for o in range(nb)]
+            o0 += nb
+        whole = thin == 1 and nw == self.W      # else a thinned or stacked view: the same reduction, uniform weights
+        return LO.from_terms(self.device, T, labels, (src, n_blocks, nw, stride), self.d, leave_out, shifts, r_eff,
+                             workspace_bytes, baseline=(lambda: self.chain_moments(discard)) if whole else None)
+
     def acf_block(self, lag0, n_lags, first=0, n=None, w0=0, nw=None):
         """Walker-averaged normalised autocorrelation function, lags [lag0, lag0 + n_lags), of the chain stored on
         the device: (n_lags, d).  ``lag0`` a multiple of 16, the first block of an estimate at 0."""
@@ -825,6 +858,13 @@ class TemperedSampler(DeviceSampler):
         """``DeviceSampler.marginals`` of one rung (default: rung 0, the posterior)."""
         return DeviceSampler.marginals(self, chain=int(temp), **kw)
 
+    def _data_chain(self, chain):
+        return 0   # the rungs share the models' single data vector
+
+    def loo(self, temp=0, **kw):
+        """``DeviceSampler.loo`` of one rung (default: rung 0, the posterior)."""
+        return DeviceSampler.loo(self, chain=int(temp), **kw)
+
     def integrated_time(self, temp=0, first=0, n=None, c=5, tol=50, quiet=False, block=256):
         """emcee's integrated autocorrelation time of rung ``temp``, estimated on the device."""
         Wc = self.walkers_per_chain
@@ -1255,6 +1295,18 @@ class EnsembleSampler:
         if kw.get("lower") is None or kw.get("upper") is None:
             raise ValueError("the chain is on the host: pass lower and upper")
         return marginals.summary(np.ascontiguousarray(self.get_chain(discard=discard, thin=thin, flat=True)), **kw)
+
+    def get_loo(self, discard=0, thin=1, models=None, **kw):
+        """``DeviceSampler.loo`` of ``get_chain(discard=discard, thin=thin)`` (``leave_out``, ``shifts``, ``r_eff``): in
+        place while the chain still lives on the device, from the host copy otherwise (``models`` are then required:
+        the device models with the likelihood set up)."""
+        discard, thin = int(discard), int(thin)
+        if self._impl is not None and getattr(self, "_device", False) and not self.__dict__.get("_frozen"):
+            return self._impl.loo(models=models, discard=discard + thin - 1, thin=thin, **kw)
+        from . import loo
+        if models is None:
+            raise ValueError("the chain is on the host: pass the device models")
+        return loo.chain_loo(models, self.get_chain(discard=discard, thin=thin, flat=True), **kw)
 
     # -- pickling (ref: mcmc.py:131-132 pickles the sampler) --------------------------------------
     def __getstate__(self):

@@ -796,6 +796,80 @@ enum gpemu_marginal_path {
 /* out[0 .. min(n, GPEMU_MARGINAL_PATH_COUNT)) = the counters; returns GPEMU_MARGINAL_PATH_COUNT (or GPEMU_ERR_ARG). */
 int gpemu_marginal_path_counts(int64_t *out, int64_t n);
 
+/* ---- per-observable log-likelihoods, PSIS-LOO and WAIC ------------------------------------------------
+ * Which observable does what to the posterior, and how well is each predicted by all the others -- what the reference
+ * answers by a second analysis on a subset of the observables and otherwise leaves open (ref: plot_analyses.py:144,
+ * plot_qhat.py:116, "one could also plot some type of information gain metric").
+ *
+ * Terms: the merged covariance keeps only the within-observable blocks (ref: emulation.py:370-388), so the
+ * log-likelihood of a group (ref: log_posterior.py:87-99) is a sum of per-observable terms.  T[o*ldt + s] = the term of
+ * observable block o for row s, in gpemu_logpost's normalisation (no 2 pi constant): block-major, ldt >= S, one
+ * contiguous row per observable.  A likelihood: the prior box is not applied; a row with a non-finite coordinate gives
+ * NaN terms.  chain selects the data vector of gpemu_likelihood_setup_chains (0 otherwise).  No likelihood setup:
+ * GPEMU_ERR_STATE; a setup with n_src > 0 (the sources span the blocks: no sum of terms): GPEMU_ERR_UNSUPPORTED, before
+ * any launch.  A dense within-observable covariance only changes the setup's constants.  PC means / variances through
+ * gpemu_gp_predict_dev in chunks of 2048 logical rows, then one wave per (row, block) with the likelihood's own
+ * per-block function.  _dev reads row r at dX + ((r / block_rows)*block_stride_rows + r % block_rows)*d, S =
+ * n_blocks*block_rows, as gpemu_posterior_predictive_dev; works on `stream` (NULL = the model's) and waits for it.
+ * The host form writes T[n_blocks_of_the_model][B].  gpemu_model_observable_blocks: the blocks of the last setup.
+ *
+ * gpemu_psis: per row r of V[R*S] (log-likelihoods of one observable, or sums of several) with r_eff[r] (NULL: 1; HOST):
+ *   x_s = -V_s - max(-V); tail size M = ceil(min(S/5, 3 sqrt(S / r_eff))); cutoff x_c = max(x_(max(S-M-1, 0)),
+ *   log DBL_MIN) (ascending, 0-based); the tail = the n elements strictly above x_c (ties at the cutoff shorten it);
+ *   n <= 4: pareto_k = +inf, raw weights.  Else the generalised Pareto fit of Zhang & Stephens (2009) to t_i =
+ *   exp(x_(i)) - exp(x_c) (m = 30 + floor(sqrt(n)) grid points, weights below 10*2^-52 dropped, pareto_k = (n*k + 5) /
+ *   (n + 10)); tail element i gets log(exp(x_c) + sigma*expm1(-pareto_k*log1p(-(i + 1/2)/n))/pareto_k), at most 0; tied
+ *   raw values share the mean of their positions' values, so nothing depends on an order among equals; log-sum-exp
+ *   normalisation.  out[r*GPEMU_PSIS_NOUT + .]: the indices below; p_waic is the sample variance of V with divisor S - 1
+ *   (Vehtari, Gelman, Gabry 2017; NaN for S = 1).  logw (NULL: not wanted): the normalised log-weights [R*S], dense, in
+ *   the input's order.  A row that holds a NaN or an infinity: NaN everywhere.  The row is sorted by gpemu_rank_dev's radix sort; every
+ *   sum over samples runs over chunks of 4096 fixed by the index, in a fixed tree: the bits do not depend on
+ *   workspace_bytes, on the grid or on the run.  Rows go through the workspace in batches (the sort's 16*S +
+ *   1024*ceil(S/2048) + 4 bytes per row, 16 bytes per tail element and 40 per chunk beside it; 0 = half of the free
+ *   device memory; if not one row fits: GPEMU_ERR_HIP, sizes in the error text).  R >= 1, 1 <= S < 2^31, r_eff finite
+ *   and > 0, else GPEMU_ERR_ARG before any launch.  _dev addresses as gpemu_select_dev does; dout and dlogw are device
+ *   arrays; stream NULL = the null stream; waits for it.
+ *
+ * gpemu_weighted_moments_dev: for the rows x_s of the block layout above (d <= 16) and R rows of log-weights
+ * dlogw[r*ldw + s]: dmean[r*d + j] = sum_s w x_sj / sum_s w, dvar[r*d + j] = sum_s w (x_sj - mean)^2 / sum_s w, w =
+ * exp(logw): the leave-one-observable-out posterior moments.  Two passes, the same fixed tree.
+ * gpemu_loo_group_rows_dev: dout[g*ldo + s] = the sum of rows rows[group_start[g] .. group_start[g+1]) of dT[R][ldt] at s,
+ * added in the given order (group_start, rows: HOST): a class of observables left out together. */
+#define GPEMU_PSIS_ELPD_LOO 0
+#define GPEMU_PSIS_LPPD 1
+#define GPEMU_PSIS_P_LOO 2
+#define GPEMU_PSIS_PARETO_K 3
+#define GPEMU_PSIS_N_TAIL 4
+#define GPEMU_PSIS_ESS_W 5
+#define GPEMU_PSIS_P_WAIC 6
+#define GPEMU_PSIS_ELPD_WAIC 7
+#define GPEMU_PSIS_CUTOFF 8
+#define GPEMU_PSIS_NOUT 9
+int gpemu_model_observable_blocks(const gpemu_model *m, int64_t *n_blocks);
+int gpemu_loglik_pointwise(gpemu_model *m, int chain, int64_t B, const double *X, double *T);
+int gpemu_loglik_pointwise_dev(gpemu_model *m, int chain, const double *dX, int64_t n_blocks, int64_t block_rows,
+                               int64_t block_stride_rows, double *dT, int64_t ldt, void *stream);
+int gpemu_psis(int device, int64_t R, int64_t S, const double *V, const double *r_eff, int64_t workspace_bytes, double *out,
+               double *logw);
+int gpemu_psis_dev(int device, int64_t R, int64_t S, const double *dV, int64_t row_stride, int64_t elem_stride,
+                   const double *r_eff, double *dout, double *dlogw, int64_t workspace_bytes, void *stream);
+int gpemu_weighted_moments_dev(int device, const double *dX, int64_t n_blocks, int64_t block_rows,
+                               int64_t block_stride_rows, int d, int64_t R, const double *dlogw, int64_t ldw,
+                               double *dmean, double *dvar, void *stream);
+int gpemu_loo_group_rows_dev(int device, int64_t R, int64_t S, const double *dT, int64_t ldt, int64_t n_groups,
+                             const int64_t *group_start, const int64_t *rows, double *dout, int64_t ldo, void *stream);
+/* Which launches of these ran.  A set of its own: the other sets keep their sizes and indices. */
+enum gpemu_loo_path {
+  GPEMU_LOO_PATH_SORT_PASS = 0,   /* one pass of the radix sort, for one batch of rows                                */
+  GPEMU_LOO_PATH_ROW_SMOOTHED,    /* a row whose tail (n > 4) was fitted and smoothed                                 */
+  GPEMU_LOO_PATH_ROW_RAW,         /* a row left with its raw weights (n <= 4, or a NaN)                               */
+  GPEMU_LOO_PATH_CHUNK,           /* one chunk of 2048 rows through gpemu_gp_predict_dev and the terms kernel         */
+  GPEMU_LOO_PATH_ROW_BATCH,       /* one batch of rows through the sort's workspace                                   */
+  GPEMU_LOO_PATH_COUNT
+};
+/* out[0 .. min(n, GPEMU_LOO_PATH_COUNT)) = the counters; returns GPEMU_LOO_PATH_COUNT (or GPEMU_ERR_ARG). */
+int gpemu_loo_path_counts(int64_t *out, int64_t n);
+
 /* ---- fit handle: test-only entry points ---------------------------------------------------------------------------
  * For the tests of the fit side only; nothing in the library's own flow calls them.
  * gpemu_fit_workspace: out[N*N] = problem z of the last evaluation (gpemu_fit_lml / _lml_batch / _factor) as the
