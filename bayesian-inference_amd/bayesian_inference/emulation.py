@@ -588,6 +588,80 @@ def global_sensitivity(emulation_config: "EmulationConfig", n: int = 4096, seed:
     return out
 
 
+def gather_feature_rows(sorter, merged, group_names) -> dict[str, np.ndarray]:
+    """The inverse of ``scatter_feature_rows`` for one vector: ``merged`` (F,) in the observable order of ``predict``
+    -> ``{group: (F_g,)}`` in each group's own order.  A sorter that has no mapping of its own (a stand-in that only
+    implements ``convert``) serves one group, which takes the whole vector."""
+    merged = np.asarray(merged, dtype=np.float64).reshape(-1)
+    mapping = getattr(sorter, 'emulation_group_to_observable_matrix', None)
+    group_names = list(group_names)
+    if mapping is None:
+        if len(group_names) != 1:
+            raise ValueError("a sorter without a mapping serves one group")
+        return {group_names[0]: merged.copy()}
+    if merged.size != sorter.shape[1]:
+        raise ValueError(f"expected {sorter.shape[1]} merged feature weights, got {merged.size}")
+    width = {name: 0 for name in group_names}
+    for _, (group_name, _, slice_group) in mapping.items():
+        width[group_name] = max(width[group_name], slice_group.stop)
+    out = {name: np.zeros(width[name]) for name in group_names}
+    for _, (group_name, slice_out, slice_group) in mapping.items():
+        out[group_name][slice_group] = merged[slice_out]
+    return out
+
+
+def design_sets(lo, hi, reference=None, candidates=None, n_reference=4096, n_candidates=2048, seed=0):
+    """``(reference (S, d), candidates (M, d))`` of a design proposal.  ``reference=None``: ``n_reference`` points
+    filling the prior box (the B matrix of ``gpemu.sensitivity.base_samples(n_reference, lo, hi, seed)``) -- plain
+    integrated-variance design.  ``candidates=None``: ``gpemu.design.default_candidates`` -- box points (the A matrix of
+    a sequence of its own, so no candidate coincides with a reference point by construction) and, when a reference set
+    was given, a seeded subsample of its rows."""
+    from gpemu import design as _design, sensitivity as gs
+    given = reference is not None
+    if not given:
+        reference = gs.base_samples(n_reference, lo, hi, seed=seed)[1]
+    reference = np.ascontiguousarray(np.array(reference, ndmin=2, dtype=np.float64))
+    if candidates is None:
+        candidates = _design.default_candidates(lo, hi, reference if given else None, n_candidates, seed=seed)
+    return reference, np.ascontiguousarray(np.array(candidates, ndmin=2, dtype=np.float64))
+
+
+def propose_design_points(emulation_config: "EmulationConfig", n_points: int, reference=None, candidates=None,
+                          n_reference: int = 4096, n_candidates: int = 2048, seed: int = 0, feature_weights=None,
+                          emulation_group_results: dict[str, dict[str, Any]] | None = None, **design_kwargs) -> dict[str, Any]:
+    """Where should the model be run next?  ``n_points`` design points chosen greedily from ``candidates`` so that each
+    lowers the emulators' integrated predictive variance over ``reference`` the most, at the fitted hyper-parameters
+    (``gpemu.design.Design.select``) -- what the reference leaves to the user once cross-validation says
+    the emulator limits the analysis.  ``reference``: (S, d) rows the variance is integrated over (posterior samples
+    put the points where the posterior lives); None: ``n_reference`` points filling the prior box.  ``candidates``:
+    (M, d); None: ``design_sets``' default.  ``feature_weights`` (F,) in the observable order of ``predict`` (default
+    1; ``1 / y_err^2`` counts variance in units of the data's) is split over the groups the way ``predict`` merges
+    them.  Returns ``points`` (q, d), ``indices``, ``gain``, ``integrated_variance`` (q + 1,), ``first_scores`` (M,),
+    ``candidates`` and ``parameter_names``."""
+    from gpemu import design as _design
+    par = emulation_config.analysis_config['parameterization'][emulation_config.parameterization]
+    reference, candidates = design_sets(par['min'], par['max'], reference, candidates, n_reference, n_candidates, seed)
+    emulation_group_results = emulation_group_results or {}
+    names = list(emulation_config.emulation_groups_config)
+    models = []
+    for group_name in names:
+        group_config = emulation_config.emulation_groups_config[group_name]
+        group_result = emulation_group_results.get(group_name)
+        if group_result is None:
+            group_result = read_emulators(group_config)
+        models.append(device_model_for(group_result, group_config.n_pc))
+    fws = None
+    if feature_weights is not None:
+        split = gather_feature_rows(emulation_config.sort_observables_in_matrix, feature_weights, names)
+        fws = [split[name] for name in names]
+    design_kwargs.setdefault('max_picks', max(int(n_points), 1))
+    with _design.Design(models, reference, candidates, feature_weights=fws, **design_kwargs) as ds:
+        out = ds.select(n_points)
+    out['candidates'] = candidates
+    out['parameter_names'] = [str(name) for name in par['names']]
+    return out
+
+
 def predict_emulation_group(parameters, results, emulation_group_config, emulator_group_cov_unexplained=None):
     """Central values (B,F) and covariances (B,F,F) of one group (ref: emulation.py:466-548).
     The truncation covariance is divided by the number of rows passed, like the reference

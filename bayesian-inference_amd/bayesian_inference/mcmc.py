@@ -849,6 +849,41 @@ def loo(config, closure_index=-1, discard=0, thin=1):
     return _loo_entries(out, labels, rows)
 
 
+def propose_design_points(config, closure_index=-1, discard=0, thin=None, n_points=8, n_reference=4096,
+                          n_candidates=2048, candidates=None, seed=0, feature_weights=None, **design_kwargs):
+    """``emulation.propose_design_points`` with the chain stored in mcmc.h5 (of closure chain ``closure_index``, if
+    >= 0) as the reference set: steps ``[discard::thin]``, all walkers; ``thin=None``: the smallest thinning that keeps
+    at most ``n_reference`` rows.  ``feature_weights`` defaults to ``1 / y_err^2`` of the run's data (the closure
+    chain's stored pseudo-data), so that emulator variance counts in units of the data's."""
+    thin_read = 1 if thin is None else int(thin)
+    cfg, chain = _stored_chain(config, closure_index, discard, thin_read)
+    if thin is None:
+        rows = chain.shape[0] * chain.shape[1]
+        chain = chain[::max(1, -(-rows // max(1, int(n_reference))))]
+    emu_cfg = emulation.EmulationConfig.from_config_file(
+        analysis_name=cfg.analysis_name, parameterization=cfg.parameterization,
+        analysis_config=cfg.analysis_config, config_file=cfg.config_file)
+    if feature_weights is None:
+        io = _data_IO()
+        if closure_index >= 0:
+            data = io.read_dict_from_h5(cfg.mcmc_output_dir, 'mcmc.h5')['experimental_pseudodata']
+        else:
+            data = io.data_array_from_h5(cfg.output_dir, 'observables.h5', pseudodata_index=-1,
+                                         observable_filter=emu_cfg.observable_filter)
+        feature_weights = design_feature_weights(data['y_err'])
+    return emulation.propose_design_points(
+        emu_cfg, n_points, reference=np.ascontiguousarray(chain.reshape(-1, chain.shape[-1])), candidates=candidates,
+        n_candidates=n_candidates, seed=seed, feature_weights=feature_weights,
+        emulation_group_results=emu_cfg.read_all_emulator_groups(), **design_kwargs)
+
+
+def design_feature_weights(y_err):
+    """``1 / y_err^2`` per feature; a feature without a positive, finite uncertainty gets weight 0."""
+    y_err = np.asarray(y_err, dtype=np.float64).reshape(-1)
+    ok = np.isfinite(y_err) & (y_err > 0)
+    return np.where(ok, 1.0 / np.where(ok, y_err, 1.0) ** 2, 0.0)
+
+
 POSTERIOR_PREDICTIVE_KEYS = ('mean', 'variance_parameters', 'variance_emulator', 'quantiles', 'probabilities')
 
 

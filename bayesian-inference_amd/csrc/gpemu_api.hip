@@ -21,12 +21,12 @@ static thread_local char g_err[512] = "";
 constexpr int PATH_FAMILY_SIZE[PATH_FAMILIES] = {GPEMU_PATH_COUNT, GPEMU_FIT_PATH_COUNT, GPEMU_WIDE_PATH_COUNT,
                                                  GPEMU_SRC_PATH_COUNT, GPEMU_GRAD_PATH_COUNT, GPEMU_POSTPRED_PATH_COUNT,
                                                  GPEMU_HMC_PATH_COUNT, GPEMU_DIAG_PATH_COUNT, GPEMU_SOBOL_PATH_COUNT,
-                                                 GPEMU_MARGINAL_PATH_COUNT};
+                                                 GPEMU_MARGINAL_PATH_COUNT, GPEMU_DESIGN_PATH_COUNT};
 constexpr int PATH_ROW = 32;
 static_assert(GPEMU_PATH_COUNT <= PATH_ROW && GPEMU_FIT_PATH_COUNT <= PATH_ROW && GPEMU_WIDE_PATH_COUNT <= PATH_ROW &&
               GPEMU_SRC_PATH_COUNT <= PATH_ROW && GPEMU_GRAD_PATH_COUNT <= PATH_ROW && GPEMU_POSTPRED_PATH_COUNT <= PATH_ROW &&
               GPEMU_HMC_PATH_COUNT <= PATH_ROW && GPEMU_DIAG_PATH_COUNT <= PATH_ROW && GPEMU_SOBOL_PATH_COUNT <= PATH_ROW &&
-              GPEMU_MARGINAL_PATH_COUNT <= PATH_ROW,
+              GPEMU_MARGINAL_PATH_COUNT <= PATH_ROW && GPEMU_DESIGN_PATH_COUNT <= PATH_ROW,
               "a family outgrew its row");
 static std::atomic<int64_t> g_path_counts[PATH_FAMILIES][PATH_ROW];
 
@@ -326,6 +326,9 @@ static int model_fill(gpemu_model *m, const double *X_train, const double *ls, c
     // the fit's alpha jitter (skl _gpr.py:346-348: K + alpha I = L L^T): K_00 - kernel_.diag, K_00 = L_00^2
     hjit[p] = std::fma(L[p * N * N], L[p * N * N], -hkd[p]);
   }
+  m->h_kdiag = hkd;
+  m->h_noise.assign((size_t)k, 0.0);
+  if (has_noise) m->h_noise.assign(noise, noise + k);
   double *dL = nullptr;
   GP_TRY(dev_alloc(&m->ls, k * dp));
   GP_TRY(dev_alloc(&m->constv, k));

@@ -52,9 +52,9 @@ static inline int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * 
 // one relaxed host-side increment per launch decision, in one table (gpemu_api.hip) with a row per family of gpemu.h;
 // a path outside its family's enum is not counted
 enum PathFamily { PATHS_LOGPOST, PATHS_FIT, PATHS_WIDE, PATHS_SRC, PATHS_GRAD, PATHS_POSTPRED, PATHS_HMC, PATHS_DIAG,
-                  PATHS_SOBOL, PATHS_MARGINAL, PATH_FAMILIES };
+                  PATHS_SOBOL, PATHS_MARGINAL, PATHS_DESIGN, PATH_FAMILIES };
 void count_path(PathFamily family, int path);
-int read_path_counts(PathFamily family, int64_t *out, int64_t n);     // what the ten public gpemu_*_path_counts return
+int read_path_counts(PathFamily family, int64_t *out, int64_t n);     // what the eleven public gpemu_*_path_counts return
 static inline void path_count(int path) { count_path(PATHS_LOGPOST, path); }    // enum gpemu_path
 static inline void fit_path_count(int path) { count_path(PATHS_FIT, path); }    // enum gpemu_fit_path
 static inline void wide_path_count(int path) { count_path(PATHS_WIDE, path); }  // enum gpemu_wide_path: d > 8 only
@@ -139,6 +139,7 @@ struct gpemu_model {
   double *cv_jit = nullptr;    // [k]  the fit's alpha jitter: L_00^2 - kdiag (cross-validation variances, k_cv.hip)
   double *Wt = nullptr;        // [k][Npad][Npad]  Wt[p][j][i] = (L_p^-1)[i][j]  (upper triangular)
   double *Xtr = nullptr;       // [Npad][dp]  raw training rows (padded rows / dims = 0): the joint covariance (k_pcov.hip)
+  std::vector<double> h_kdiag, h_noise;   // host copies [k] of kernel_.diag and of the White level (0 without one): k_design.hip
 
   // PCA / scaler
   double *comp = nullptr;      // [k][F]

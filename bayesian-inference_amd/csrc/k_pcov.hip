@@ -14,26 +14,9 @@
 // Every element's sums run in one fixed order whatever the chunking: the results do not depend on the workspace.
 #include "internal.h"
 #include "gemm.h"
-#include "matern_dev.h"
+#include "pcov_dev.h"
 
 namespace gpemu {
-
-constexpr int PC_NB = 64;   // padding unit of every operand (launch_gemm, the blocked Cholesky)
-
-// one block of kernel values per PC: out[z][r][c] = k(A[a0 + r], B[b0 + c]) + const for a0 + r < na, b0 + c < nb;
-// zero in the padding.  sym: element (i, i) is kernel_.diag exactly (r = 0: 1 + const + noise).
-struct KmatArgs {
-  const double *A = nullptr;   // rows [na][sa] (raw coordinates, first d columns read)
-  const double *B = nullptr;   // rows [nb][sb]
-  int64_t sa = 0, sb = 0, na = 0, nb = 0, a0 = 0, b0 = 0;
-  double *out = nullptr;
-  int64_t ldo = 0, strideo = 0, rows = 0, cols = 0;   // rows, cols: multiples of 16 and 64
-  const double *ls = nullptr;      // [k][dp]
-  const double *constv = nullptr;  // [k]
-  const double *kdiag = nullptr;   // [k]
-  int dp = DPAD, d = 1, p0 = 0, sym = 0;
-  MaternNu mn;
-};
 
 // blockDim (64, 4): x = column (coalesced stores), 4 rows per thread (y, y + 4, ..); grid (cols / 64, rows / 16, PCs)
 template <int KIND, int DP>
@@ -58,23 +41,14 @@ __global__ __launch_bounds__(256) void pcov_kmat_kernel(KmatArgs g) {
       if (g.sym && ai == bi) {
         v = g.kdiag[p];
       } else {
-        double r2 = 0.0;
-#pragma unroll
-        for (int dd = 0; dd < DP; ++dd) {
-          if (dd < g.d) {
-            const double df = (g.A[ai * g.sa + dd] - xb[dd]) * inv[dd];
-            r2 = fma(df, df, r2);
-          }
-        }
-        const double r = sqrt(r2);   // before the call copies g.mn (the other order changes the instruction schedule)
-        v = (KIND == 4 ? matern_nu_value_call(g.mn, r) : base_from_r2(KIND, r2)) + cst;
+        v = kmat_value<KIND, DP>(g.A + ai * g.sa, xb, inv, g.d, g.mn, cst);
       }
     }
     o[r * g.ldo + c] = v;
   }
 }
 
-static int launch_kmat(const gpemu_model *m, KmatArgs g, int npc, hipStream_t st) {
+int launch_kmat(const gpemu_model *m, KmatArgs g, int npc, hipStream_t st) {
   g.ls = m->ls; g.constv = m->constv; g.kdiag = m->kdiag; g.dp = m->dp; g.d = (int)m->d;
   if (kstar_kind(m) == 4) g.mn = matern_nu_constants(m->nu);
   dim3 grid((unsigned)(g.cols / 64), (unsigned)(g.rows / 16), (unsigned)npc), block(64, 4);
@@ -88,13 +62,13 @@ static int launch_kmat(const gpemu_model *m, KmatArgs g, int npc, hipStream_t st
   return GPEMU_OK;
 }
 
-// V[z] = W_p KT[z]  (W = Wt^T lower triangular: k_to_m skips the tiles above the diagonal), rows [0, N64)
-static int launch_v(const gpemu_model *m, int p0, int npc, const double *KT, double *V, int64_t N64, int64_t ncols,
-                    hipStream_t st) {
+// V[z] = W_p KT[z]  (pcov_dev.h)
+int launch_v(const gpemu_model *m, int p0, int npc, const double *KT, double *V, int64_t N64, int64_t ncols,
+             hipStream_t st, int64_t strideV) {
   GemmArgs g;
   g.A = m->Wt + (int64_t)p0 * m->Npad * m->Npad; g.lda = m->Npad; g.strideA = m->Npad * m->Npad;   // [k][m]: W^T
   g.B = KT; g.ldb = ncols; g.strideB = N64 * ncols;
-  g.C = V; g.ldc = ncols; g.strideC = N64 * ncols;
+  g.C = V; g.ldc = ncols; g.strideC = strideV ? strideV : N64 * ncols;
   g.M = (int)N64; g.N = (int)ncols; g.K = (int)N64;
   g.k_to_m = 1;
   return launch_gemm(g, true, true, npc, st);

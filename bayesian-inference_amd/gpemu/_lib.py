@@ -192,6 +192,16 @@ _SIGNATURES = {
     "gpemu_loo_group_rows_dev": (C.c_int, [C.c_int, c_i64, c_i64, C.c_void_p, c_i64, c_i64, C.c_void_p, C.c_void_p,
                                            C.c_void_p, c_i64, C.c_void_p]),
     "gpemu_loo_path_counts": (C.c_int, [C.POINTER(c_i64), c_i64]),
+    "gpemu_design_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p, c_i64, C.c_void_p, C.c_void_p, c_i64, C.c_void_p,
+                                      C.c_void_p, C.c_void_p, C.c_double, c_i64, c_i64]),
+    "gpemu_design_create_dev": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, c_i64, c_i64, c_i64, C.c_void_p,
+                                          c_i64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, c_i64, c_i64,
+                                          C.c_void_p]),
+    "gpemu_design_scores": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gpemu_design_condition": (C.c_int, [C.c_void_p, c_i64]),
+    "gpemu_design_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(c_i64)]),
+    "gpemu_design_destroy": (C.c_int, [C.c_void_p]),
+    "gpemu_design_path_counts": (C.c_int, [C.POINTER(c_i64), c_i64]),
 }
 
 

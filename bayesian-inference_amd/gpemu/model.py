@@ -232,6 +232,12 @@ class DeviceModel:
             vp(dorder_ptr), C.c_void_p(stream)))
 
     # -- global sensitivity ----------------------------------------------------------------
+    def design(self, reference, candidates, **kw):
+        """``gpemu.design.Design`` of this one group: the sequential-design criterion (integrated variance reduction;
+        DESIGN.md §4.32) over ``reference`` (S, d) and ``candidates`` (M, d); keywords as ``Design``'s."""
+        from .design import Design
+        return Design([self], reference, candidates, **kw)
+
     def _base_pair(self, A, B):
         A, B = self._finite(self._X(A)), self._finite(self._X(B))
         if A.shape != B.shape:

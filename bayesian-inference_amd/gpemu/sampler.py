@@ -401,6 +401,36 @@ class DeviceSampler:
         return LO.from_terms(self.device, T, labels, (src, n_blocks, nw, stride), self.d, leave_out, shifts, r_eff,
                              workspace_bytes, baseline=(lambda: self.chain_moments(discard)) if whole else None)
 
+    def propose_design(self, n_points, candidates=None, n_candidates=2048, n_reference=4096, discard=0, thin=None,
+                       chain=None, seed=0, models=None, **kw):
+        """Where to run the model next, given this posterior: ``gpemu.design.Design.select(n_points)`` (DESIGN.md
+        §4.32) with the stored chain ``get_chain()[discard::thin]`` as the reference set, read in place on the device.
+        ``thin=None``: the smallest thinning that keeps at most ``n_reference`` rows.  ``candidates=None``:
+        ``gpemu.design.default_candidates`` -- ``n_candidates - n_candidates // 2`` Sobol' points of the models' prior
+        box, then ``n_candidates // 2`` of the reference rows drawn with ``seed``.  Further keywords go to ``Design``
+        (``feature_weights``, ``tau``, ``min_variance``, ``workspace_bytes``, ...).  The result of ``select`` plus
+        ``candidates``, ``thin`` and ``n_reference_rows``.  Stacked samplers take ``chain=<index>``."""
+        from . import design as DS
+        models = self.models if models is None else list(models)
+        w0, nw = self._chain_walkers(chain)
+        if thin is None:
+            steps = self.counts()[2] - int(discard)
+            thin = max(1, -(-steps * nw // max(1, int(n_reference))))
+        src, n_blocks, nw, stride, S = self._stored_view(discard, thin, chain)
+        if candidates is None:
+            box = getattr(models[0], "prior_box", None)
+            if box is None:
+                raise ValueError("no prior box is known (likelihood_setup has not been called): pass candidates")
+            rows = self.get_chain(int(discard))[0][::int(thin), w0:w0 + nw].reshape(-1, self.d)
+            candidates = DS.default_candidates(box[0], box[1], rows, n_candidates, seed=seed)
+        ref = DS.DeviceRows(src, n_blocks, nw, stride, stream=_lib.current_stream(self.device))
+        kw.setdefault("max_picks", max(int(n_points), 1))
+        with DS.Design(models, ref, candidates, **kw) as ds:
+            out = ds.select(n_points)
+            out["candidates"] = ds.candidates
+        out["thin"], out["n_reference_rows"] = int(thin), S
+        return out
+
     def acf_block(self, lag0, n_lags, first=0, n=None, w0=0, nw=None):
         """Walker-averaged normalised autocorrelation function, lags [lag0, lag0 + n_lags), of the chain stored on
         the device: (n_lags, d).  ``lag0`` a multiple of 16, the first block of an estimate at 0."""
@@ -864,6 +894,10 @@ class TemperedSampler(DeviceSampler):
     def loo(self, temp=0, **kw):
         """``DeviceSampler.loo`` of one rung (default: rung 0, the posterior)."""
         return DeviceSampler.loo(self, chain=int(temp), **kw)
+
+    def propose_design(self, n_points, temp=0, **kw):
+        """``DeviceSampler.propose_design`` of one rung (default: rung 0, the posterior)."""
+        return DeviceSampler.propose_design(self, n_points, chain=int(temp), **kw)
 
     def integrated_time(self, temp=0, first=0, n=None, c=5, tol=50, quiet=False, block=256):
         """emcee's integrated autocorrelation time of rung ``temp``, estimated on the device."""

@@ -870,6 +870,65 @@ enum gpemu_loo_path {
 /* out[0 .. min(n, GPEMU_LOO_PATH_COUNT)) = the counters; returns GPEMU_LOO_PATH_COUNT (or GPEMU_ERR_ARG). */
 int gpemu_loo_path_counts(int64_t *out, int64_t n);
 
+/* ---- sequential design: where to run the model next -------------------------------------------------
+ * Active learning in Cohn's sense (integrated variance reduction) at the fitted hyper-parameters.  With c_p(x, x') the
+ * two-set predictive covariance of PC p (gpemu_gp_predict_cov with X2: it carries no noise), a reference set x_s (s < S, weights
+ * omega_s >= 0 that the call normalises to sum 1) and candidates x_c (c < M):
+ *     IV_p = sum_s omega_s c_p(x_s, x_s),       den_p(c) = c_p(x_c, x_c) + tau_p
+ *     score(c) = sum_p pc_weight[p] * [sum_s omega_s c_p(x_s, x_c)^2] / den_p(c)
+ * -- the amount by which a model run at x_c, carrying noise variance tau_p, lowers sum_p pc_weight[p] IV_p.  A PC whose
+ * den_p(c) <= min_variance * kernel_.diag_p contributes exactly 0 (the emulator is exact there already).  Conditioning
+ * on a pick c* replaces every covariance by c(a, b) - u(a) u(b), u(.) = c(., c*) / sqrt(den(c*)) (u = 0 for a PC under
+ * the floor at c*): u is appended to the two GEMM operands, den_p(c) -= u(c)^2 and IV_p -= sum_s omega_s u(s)^2 in place.
+ *
+ * The handle keeps V = W K(X_train, .)^T of the reference rows and of the candidates per PC, k-major, with max_picks
+ * (rounded up to 16) spare rows, and a copy of both sets of rows; the S x M covariance is never stored: the score kernel
+ * (MFMA f64) forms 64 x 64 tiles of it in registers, squares, weights and sums the 64 rows of a tile in a fixed order and
+ * writes one partial per (PC, row tile, candidate); the partials of a candidate are added in index order.  No
+ * floating-point atomics: the bits depend neither on workspace_bytes nor on the run.  workspace_bytes (0: half of the
+ * free device memory) bounds the operands, the work array of the create call (N64 * max(S64, M64) doubles) and the
+ * partials, which are chunked over candidate tiles; if the operands and one tile of partials do not fit: GPEMU_ERR_ARG
+ * with the bytes needed in the error text.
+ *
+ * Checked before any launch (GPEMU_ERR_ARG): 1 <= S, M <= 4194240, k <= 64, 0 <= max_picks <= 256, min_variance finite
+ * and >= 0, pc_weight and tau (NULL: the White level of each PC, 0 without one) finite and >= 0, w_ref (NULL: 1 / S;
+ * always a HOST array) finite and >= 0 with a positive sum, finite rows in the host form.  The _dev form reads its rows
+ * from device memory unchecked: reference row r at dXref + ((r / block_rows)*block_stride_rows + r % block_rows)*d, S =
+ * n_blocks*block_rows, as gpemu_posterior_predictive_dev (a stored chain in place); dXcand[M*d] dense; `stream` (NULL:
+ * none) is waited for before the rows are read.  All work runs on the model's stream; every call waits for it.
+ * The model must outlive the handle.
+ * gpemu_design_scores: score[M] and, if not NULL, score_pc[k*M] (the PCs' weighted terms), HOST arrays.
+ * gpemu_design_condition: GPEMU_ERR_ARG for a candidate outside [0, M) or beyond max_picks picks.
+ * gpemu_design_state: iv[k] (unweighted IV_p), den[k*M] or NULL, n_picks or NULL. */
+typedef struct gpemu_design gpemu_design;
+int gpemu_design_create(gpemu_design **out, gpemu_model *m, int64_t S, const double *Xref, const double *w_ref,
+                        int64_t M, const double *Xcand, const double *pc_weight, const double *tau,
+                        double min_variance, int64_t max_picks, int64_t workspace_bytes);
+int gpemu_design_create_dev(gpemu_design **out, gpemu_model *m, const double *dXref, int64_t n_blocks,
+                            int64_t block_rows, int64_t block_stride_rows, const double *w_ref, int64_t M,
+                            const double *dXcand, const double *pc_weight, const double *tau, double min_variance,
+                            int64_t max_picks, int64_t workspace_bytes, void *stream);
+int gpemu_design_scores(gpemu_design *h, double *score, double *score_pc);
+int gpemu_design_condition(gpemu_design *h, int64_t candidate);
+int gpemu_design_state(gpemu_design *h, double *iv, double *den, int64_t *n_picks);
+int gpemu_design_destroy(gpemu_design *h);
+/* Which launches ran.  A set of its own: the other sets keep their sizes and indices. */
+enum gpemu_design_path {
+  GPEMU_DESIGN_PATH_SCORES = 0,   /* one gpemu_design_scores call                                                      */
+  GPEMU_DESIGN_PATH_CHUNK,        /* one chunk of candidate tiles through the score and finish kernels                 */
+  GPEMU_DESIGN_PATH_DP8,          /* ... on 8-wide rows (d <= 8)                                                       */
+  GPEMU_DESIGN_PATH_DP16,         /* ... on 16-wide rows (9 <= d <= 16)                                                */
+  GPEMU_DESIGN_PATH_KIND_RBF,     /* ... with the RBF kernel (and Matern nu = inf)                                     */
+  GPEMU_DESIGN_PATH_KIND_M05,     /* ... Matern 0.5                                                                    */
+  GPEMU_DESIGN_PATH_KIND_M15,     /* ... Matern 1.5                                                                    */
+  GPEMU_DESIGN_PATH_KIND_M25,     /* ... Matern 2.5                                                                    */
+  GPEMU_DESIGN_PATH_KIND_NU,      /* ... Matern of any other nu (the out-of-line Bessel call)                          */
+  GPEMU_DESIGN_PATH_COLUMN,       /* one conditioning step (the column kernel and the in-place updates)                */
+  GPEMU_DESIGN_PATH_COUNT
+};
+/* out[0 .. min(n, GPEMU_DESIGN_PATH_COUNT)) = the counters; returns GPEMU_DESIGN_PATH_COUNT (or GPEMU_ERR_ARG). */
+int gpemu_design_path_counts(int64_t *out, int64_t n);
+
 /* ---- fit handle: test-only entry points ---------------------------------------------------------------------------
  * For the tests of the fit side only; nothing in the library's own flow calls them.
  * gpemu_fit_workspace: out[N*N] = problem z of the last evaluation (gpemu_fit_lml / _lml_batch / _factor) as the
