@@ -708,17 +708,38 @@ def marginals_settings(mc, default_confidence=None):
     return bool(on), (int(bins[0]), int(bins[1])), tuple(float(c) for c in conf), bool(kde)
 
 
+def marginals_kde2d_settings(mc):
+    """``(on, n_grid, covariance)`` from the ``parameters.mcmc`` mapping: ``marginals_kde2d`` (true or false, default
+    off: the 2-D kernel densities of all parameter pairs beside the other marginals), ``marginals_kde2d_grid`` (points
+    per axis, an integer in [1, 512], default 100) and ``marginals_kde2d_covariance`` (``full`` -- scipy's
+    ``gaussian_kde`` on a sheared grid -- or ``diagonal``, default ``full``).  DESIGN.md §4.33."""
+    on = mc.get('marginals_kde2d', False)
+    if not isinstance(on, (bool, np.bool_)):
+        raise ValueError(f"parameters.mcmc.marginals_kde2d must be true or false, got {on!r}")
+    grid = mc.get('marginals_kde2d_grid', 100)
+    if not isinstance(grid, (int, np.integer)) or isinstance(grid, (bool, np.bool_)) or not 1 <= grid <= 512:
+        raise ValueError(f"parameters.mcmc.marginals_kde2d_grid must be an integer in [1, 512], got {grid!r}")
+    cov = mc.get('marginals_kde2d_covariance', 'full')
+    if cov not in ('full', 'diagonal'):
+        raise ValueError(f"parameters.mcmc.marginals_kde2d_covariance must be 'full' or 'diagonal', got {cov!r}")
+    return bool(on), int(grid), str(cov)
+
+
 MARGINALS_KEYS = ('edges_1d', 'edges_2d', 'hist_1d', 'pairs', 'hist_2d', 'n_inside', 'confidence', 'hpd')
 MARGINALS_KDE_KEYS = ('kde_grid', 'kde_density', 'kde_bandwidth')
+MARGINALS_KDE2D_KEYS = ('kde2d_pairs', 'kde2d_shear', 'kde2d_bandwidth', 'kde2d_grid_a', 'kde2d_grid_b', 'kde2d_density')
 
 
 def _marginals_kwargs(config):
     """The arguments of ``DeviceSampler.marginals`` / ``gpemu.marginals.summary`` from the configuration: the prior box
-    of the parameterization and the ``marginals_*`` settings."""
+    of the parameterization and the ``marginals_*`` settings (the 2-D density's only where it is on)."""
     box = config.analysis_config['parameterization'][config.parameterization]
-    return dict(lower=np.asarray(box['min'], dtype=np.float64), upper=np.asarray(box['max'], dtype=np.float64),
-                bins_1d=config.marginals_bins[0], bins_2d=config.marginals_bins[1],
-                confidence=config.marginals_confidence, kde=config.marginals_kde)
+    kw = dict(lower=np.asarray(box['min'], dtype=np.float64), upper=np.asarray(box['max'], dtype=np.float64),
+              bins_1d=config.marginals_bins[0], bins_2d=config.marginals_bins[1],
+              confidence=config.marginals_confidence, kde=config.marginals_kde)
+    if getattr(config, 'marginals_kde2d', False):
+        kw.update(kde2d=True, n_grid_2d=config.marginals_kde2d_grid, covariance_2d=config.marginals_kde2d_covariance)
+    return kw
 
 
 def _add_marginals(config, results, compute, label='production chain'):
@@ -728,8 +749,19 @@ def _add_marginals(config, results, compute, label='production chain'):
     if not getattr(config, 'marginals', False):
         return
     keys = MARGINALS_KEYS + (MARGINALS_KDE_KEYS if config.marginals_kde else ())
+    kwargs = _marginals_kwargs(config)
+    out = None
+    if kwargs.get('kde2d'):          # the 2-D densities fail on their own (e.g. two linearly dependent parameters)
+        try:
+            out = compute(**kwargs)
+            keys = keys + MARGINALS_KDE2D_KEYS
+        except ValueError as err:
+            logger.warning(f'parameters.mcmc.marginals_kde2d: not computed ({err!r}); mcmc.h5 is written without '
+                           + ', '.join(f'marginal_{k}' for k in MARGINALS_KDE2D_KEYS))
+            kwargs = {k: v for k, v in kwargs.items() if k not in ('kde2d', 'n_grid_2d', 'covariance_2d')}
     try:
-        out = compute(**_marginals_kwargs(config))
+        if out is None:
+            out = compute(**kwargs)
     except ValueError as err:        # e.g. too few stored samples for a level: the chain is written either way (a
         # device failure is not caught: it ends the run)
         logger.warning(f'parameters.mcmc.marginals: not computed ({err!r}); mcmc.h5 is written without '
@@ -1091,6 +1123,8 @@ class MCMCConfig:
         # none without the key
         self.marginals, self.marginals_bins, self.marginals_confidence, self.marginals_kde = marginals_settings(
             mc, getattr(self, 'confidence', None))
+        # ... and the 2-D kernel densities of all parameter pairs beside them (optional, default off): marginal_kde2d_*
+        self.marginals_kde2d, self.marginals_kde2d_grid, self.marginals_kde2d_covariance = marginals_kde2d_settings(mc)
         # per-observable PSIS-LOO / WAIC and the observable-influence table of the production chain (optional, default
         # off): loo_* in mcmc.h5, none without the key
         self.loo, self.loo_leave_out = loo_settings(mc)

@@ -180,6 +180,13 @@ _SIGNATURES = {
     "gpemu_marginal_dense_dev": (C.c_int, [C.c_int, C.c_void_p, c_i64, c_i64, c_i64, C.c_int, C.c_void_p, C.c_void_p]),
     "gpemu_marginal_moments_dev": (C.c_int, [C.c_int, C.c_void_p, c_i64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gpemu_marginal_path_counts": (C.c_int, [C.POINTER(c_i64), c_i64]),
+    "gpemu_kde2d": (C.c_int, [C.c_int, c_i64, C.c_int, C.c_void_p, c_i64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                              C.c_void_p, C.c_void_p, C.c_void_p, c_i64]),
+    "gpemu_kde2d_dev": (C.c_int, [C.c_int, C.c_void_p, c_i64, c_i64, c_i64, C.c_int, c_i64, C.c_void_p, C.c_void_p,
+                                  C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, c_i64, C.c_void_p]),
+    "gpemu_pair_moments_dev": (C.c_int, [C.c_int, C.c_void_p, c_i64, c_i64, c_i64, C.c_int, C.c_void_p, C.c_void_p, c_i64,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gpemu_kde2d_path_counts": (C.c_int, [C.POINTER(c_i64), c_i64]),
     "gpemu_model_observable_blocks": (C.c_int, [C.c_void_p, C.POINTER(c_i64)]),
     "gpemu_loglik_pointwise": (C.c_int, [C.c_void_p, C.c_int, c_i64, C.c_void_p, C.c_void_p]),
     "gpemu_loglik_pointwise_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, c_i64, c_i64, c_i64, C.c_void_p, c_i64,

@@ -9,7 +9,10 @@ highest-density interval) and the narrowest-window rule of its ``credible_interv
   elements of the input, ties to the lowest window (``np.argmin``);
 * ``kde_1d``: the direct-sum Gaussian kernel density of each parameter (no binning, no truncation), bandwidth and grid by
   scipy's Scott factor and seaborn's ``cut`` rule unless given;
-* ``credible_levels``: the contour levels of a 2-D histogram (host numpy).
+* ``credible_levels``: the contour levels of a 2-D histogram (host numpy);
+* ``kde_2d``: the direct-sum Gaussian kernel density of each PAIR of parameters on a product grid, a matrix product on
+  the fp64 matrix cores -- scipy's full-covariance ``gaussian_kde`` on a sheared grid, or the
+  axis-aligned product kernel -- with ``kde_2d_mesh`` and ``density_levels`` (host numpy) for the contours.
 
 Samples are ``(S, d)`` (or ``(S,)``): numpy arrays go through the host entries, contiguous float64 device tensors are read
 in place.  ``summary`` takes all three at once; ``DeviceSampler.marginals`` is the same over the stored chain where it
@@ -24,7 +27,8 @@ from . import _lib
 from ._lib import check, ptr
 
 PATHS = ("HIST_SWEEP", "PAIR_GROUP", "SORT_BATCH", "WINDOW_SEARCH", "KDE")
-MAX_D, MAX_BINS_1D, MAX_BINS_2D = 16, 4096, 256
+PATHS_KDE2D = ("DENSITY", "PAIR_BATCH", "PARTIAL_SUM", "MOMENTS", "EXTENTS")
+MAX_D, MAX_BINS_1D, MAX_BINS_2D, MAX_GRID_2D = 16, 4096, 256, 512
 
 
 def path_counts():
@@ -34,6 +38,16 @@ def path_counts():
     if n < 0:
         check(n)
     return {k: int(out[i]) for i, k in enumerate(PATHS)}
+
+
+def kde2d_path_counts():
+    """The library's counters of the 2-D densities' launches since the process started, by name (a family of its own:
+    ``path_counts`` does not move)."""
+    out = (C.c_int64 * len(PATHS_KDE2D))()
+    n = _lib.lib().gpemu_kde2d_path_counts(out, len(PATHS_KDE2D))
+    if n < 0:
+        check(n)
+    return {k: int(out[i]) for i, k in enumerate(PATHS_KDE2D)}
 
 
 # -- host-side rules ------------------------------------------------------------------------------------------------
@@ -107,6 +121,139 @@ def credible_levels(hist_2d, probabilities):
     return out[..., 0] if np.ndim(probabilities) == 0 else out
 
 
+def density_levels(density, probabilities):
+    """The float twin of ``credible_levels``: for each panel ``(..., G, G)`` of density values on cells of equal area
+    and each probability p, the largest density value t such that the cells with value >= t hold at least p of the
+    panel's summed mass -- the contour levels of the 68 % / 95 % regions.  ``(..., len(probabilities))`` float64 (a
+    scalar p drops the last axis); an all-zero panel gives 0."""
+    z = np.asarray(density, dtype=np.float64)
+    if z.ndim < 2:
+        raise ValueError("density must have at least two axes")
+    p = np.atleast_1d(np.asarray(probabilities, dtype=np.float64))
+    if not np.all((p >= 0.0) & (p <= 1.0)):
+        raise ValueError("probabilities must be in [0, 1]")
+    lead = z.shape[:-2]
+    flat = z.reshape((-1, z.shape[-2] * z.shape[-1]))
+    out = np.zeros((flat.shape[0], p.size))
+    for r, row in enumerate(flat):
+        vals = np.sort(row)[::-1]
+        mass = np.cumsum(vals)
+        total = mass[-1]                 # the running sum's own end: p = 1 is reached where the sum stops growing
+        if not total > 0.0:
+            out[r] = total               # 0 for an all-zero panel, NaN for a NaN one
+            continue
+        for q, prob in enumerate(p):
+            k = int(np.searchsorted(mass, prob * total, side="left"))
+            out[r, q] = vals[min(k, vals.size - 1)]
+    out = out.reshape(lead + (p.size,))
+    return out[..., 0] if np.ndim(probabilities) == 0 else out
+
+
+def scott_factor_2d(S, bw_adjust=1.0):
+    """scipy.stats.gaussian_kde's Scott factor for two dimensions, ``S ** (-1 / 6)``, times ``bw_adjust``."""
+    return float(bw_adjust) * np.power(float(S), -1.0 / 6.0)
+
+
+def _pair_list(pairs, d):
+    if pairs is None:
+        return pair_indices(d)
+    pr = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+    if pr.shape[0] < 1:
+        raise ValueError("pairs must hold at least one pair")
+    if np.any(pr < 0) or np.any(pr >= d) or np.any(pr[:, 0] == pr[:, 1]):
+        raise ValueError(f"every pair must be two different parameters in [0, {d})")
+    return np.ascontiguousarray(pr)
+
+
+def kde2d_plan(S, d, pairs=None, covariance="full", bandwidth=None, shear=None, grid_a=None, grid_b=None, n_grid=100,
+               cut=3.0, bw_adjust=1.0, cov=None, extents=None):
+    """The plan of ``kde_2d`` -- ``pairs (P, 2)``, ``shear (P,)``, ``bandwidth (P, 2)``, ``grid_a``, ``grid_b (P, G)``
+    -- from what is given and, for the rest, from ``cov() -> (d, d)`` (the ``ddof=1`` covariance of the samples) and
+    ``extents(pairs (n, 2), shear (n,)) -> (n, 2)`` (the minimum and maximum of ``x_j - shear x_i``), which are only
+    called where something is missing.  A pure host function.
+
+    For pair (i, j) and the factor ``f = bw_adjust S ** (-1 / 6)``: with ``"full"`` the shear is ``C_ij / C_ii``, with
+    ``"diagonal"`` 0; ``h_a = f sqrt(C_ii)`` and ``h_b = f sqrt(var(v))``, ``var(v) = C_jj - shear (2 C_ij - shear C_ii)``
+    the variance of the sheared coordinate ``v = x_j - shear x_i`` -- the conditional variance ``C_jj - C_ij^2 / C_ii``
+    under ``"full"`` (x and v are then uncorrelated and ``f^2 C`` is diagonal in them: scipy's bandwidth matrix), ``C_jj``
+    under ``"diagonal"``.  The grids are ``linspace(min - cut h, max + cut h, n_grid)`` of x_i and of v."""
+    if covariance not in ("full", "diagonal"):
+        raise ValueError(f"covariance must be 'full' or 'diagonal', got {covariance!r}")
+    pr = _pair_list(pairs, d)
+    P = pr.shape[0]
+    beta = None if shear is None else np.broadcast_to(np.asarray(shear, dtype=np.float64), (P,)).copy()
+    h = None if bandwidth is None else np.broadcast_to(np.asarray(bandwidth, dtype=np.float64), (P, 2)).copy()
+    if h is None or (beta is None and covariance == "full"):
+        if S < 3:
+            raise ValueError(f"pair ({pr[0, 0]}, {pr[0, 1]}): the default bandwidth needs at least 3 samples, got {S}")
+        c = np.asarray(cov(), dtype=np.float64).reshape(d, d)
+        cii, cjj, cij = c[pr[:, 0], pr[:, 0]], c[pr[:, 1], pr[:, 1]], c[pr[:, 0], pr[:, 1]]
+        for (i, j), a, b in zip(pr, cii, cjj):
+            if not (a > 0.0 and b > 0.0 and np.isfinite(a) and np.isfinite(b)):
+                raise ValueError(f"pair ({i}, {j}): the variances {a}, {b} must be finite and > 0")
+        if beta is None:
+            beta = cij / cii if covariance == "full" else np.zeros(P)
+        if h is None:
+            var_v = cjj - beta * (2.0 * cij - beta * cii)
+            for (i, j), v, b in zip(pr, var_v, cjj):
+                # (a variance of v within the rounding of C_jj is no variance: scipy raises for a singular covariance)
+                if not v > 64.0 * np.finfo(np.float64).eps * b:
+                    raise ValueError(f"pair ({i}, {j}): the conditional variance {v} is not > 0 (the two parameters "
+                                     "are linearly dependent); use covariance='diagonal' or give the bandwidth")
+            h = scott_factor_2d(S, bw_adjust) * np.sqrt(np.stack([cii, var_v], axis=1))
+    if beta is None:
+        beta = np.zeros(P)
+    if not np.all(np.isfinite(beta)):
+        raise ValueError(f"every shear must be finite, got {beta}")
+    if not np.all(np.isfinite(h) & (h > 0.0)):
+        raise ValueError(f"every bandwidth must be finite and > 0, got {h}")
+
+    def given(g, name):
+        g = np.asarray(g, dtype=np.float64)
+        g = np.broadcast_to(g, (P, g.shape[-1])).copy() if g.ndim == 1 else np.ascontiguousarray(g)
+        if g.ndim != 2 or g.shape[0] != P or g.shape[1] < 1:
+            raise ValueError(f"{name} must be (G,) or ({P}, G)")
+        return g
+    ga = None if grid_a is None else given(grid_a, "grid_a")
+    gb = None if grid_b is None else given(grid_b, "grid_b")
+    G = ga.shape[1] if ga is not None else (gb.shape[1] if gb is not None else int(n_grid))
+    if ga is not None and gb is not None and ga.shape[1] != gb.shape[1]:
+        raise ValueError("grid_a and grid_b must have one length")
+    if not 1 <= G <= MAX_GRID_2D:
+        raise ValueError(f"the grid must have 1 to {MAX_GRID_2D} points per axis, got {G}")
+    if ga is None or gb is None:
+        # one pass for both: the extents of x_i are those of the pair (j, i) without shear
+        ends = np.asarray(extents(np.concatenate([pr[:, ::-1], pr]), np.concatenate([np.zeros(P), beta])))
+        if not np.all(np.isfinite(ends)):
+            raise ValueError("the default grid needs finite samples")
+        if ga is None:
+            ga = default_grid(ends[:P, 0], ends[:P, 1], h[:, 0], G, cut)
+        if gb is None:
+            gb = default_grid(ends[P:, 0], ends[P:, 1], h[:, 1], G, cut)
+    return {"pairs": pr, "shear": np.ascontiguousarray(beta), "bandwidth": np.ascontiguousarray(h),
+            "grid_a": np.ascontiguousarray(ga), "grid_b": np.ascontiguousarray(gb)}
+
+
+def kde2d_plan_host(x, **kw):
+    """``kde2d_plan`` of host samples ``x (S, d)``, moments and extents by numpy."""
+    x = np.asarray(x, dtype=np.float64)
+    S, d = x.shape
+
+    def extents(pr, beta):
+        v = x[:, pr[:, 1]] - beta[None, :] * x[:, pr[:, 0]]
+        return np.stack([v.min(axis=0), v.max(axis=0)], axis=1)
+    return kde2d_plan(S, d, cov=lambda: np.atleast_2d(np.cov(x, rowvar=False, ddof=1)), extents=extents, **kw)
+
+
+def kde_2d_mesh(result, p):
+    """``(X, Y)``, the ``(G, G)`` meshes of panel ``p`` of a ``kde_2d`` result in parameter coordinates -- what contour
+    routines take beside ``density[p]``: ``X = grid_a[p][:, None]``, ``Y = grid_b[p][None, :] + shear[p] X`` (a
+    parallelogram where the shear is not 0)."""
+    ga, gb = np.asarray(result["grid_a"])[p], np.asarray(result["grid_b"])[p]
+    X = np.broadcast_to(ga[:, None], (ga.size, gb.size)).copy()
+    return X, gb[None, :] + float(np.asarray(result["shear"])[p]) * X
+
+
 # -- device plumbing ------------------------------------------------------------------------------------------------
 def _samples(samples):
     """``(array or tensor (S, d), on_device)``; a vector is one parameter."""
@@ -171,6 +318,44 @@ def _moments_dev(device, base, S, d):
     check(_lib.lib().gpemu_marginal_moments_dev(int(device), C.c_void_p(base), int(S), int(d), ptr(mean), ptr(var),
                                                 _lib.current_stream(device)))
     return mean, var
+
+
+def _pair_moments_dev(device, base, n_blocks, block_rows, block_stride_rows, d, pairs=None, shear=None, moments=True):
+    """``(mean, cov with divisor S, extents (n, 2))`` of device rows in the block layout (what is not asked: None)."""
+    mean, cov = (np.empty(d), np.empty((d, d))) if moments else (None, None)
+    n = 0 if pairs is None else int(np.asarray(pairs).shape[0])
+    pr = None if n == 0 else np.ascontiguousarray(pairs, dtype=np.int64)
+    sh = None if n == 0 else np.ascontiguousarray(shear, dtype=np.float64)
+    ext = None if n == 0 else np.empty((n, 2))
+    check(_lib.lib().gpemu_pair_moments_dev(int(device), C.c_void_p(base), int(n_blocks), int(block_rows),
+                                            int(block_stride_rows), int(d), ptr(mean), ptr(cov), n, ptr(pr), ptr(sh),
+                                            ptr(ext), _lib.current_stream(device)))
+    return mean, cov, ext
+
+
+def _kde2d_dev(device, base, n_blocks, block_rows, block_stride_rows, d, plan, workspace_bytes=0):
+    """The panels of ``plan`` from device rows in the block layout, read in place: ``(P, G, G)``."""
+    import torch
+    P, G = plan["grid_a"].shape
+    out = torch.empty((P, G, G), dtype=torch.float64, device=torch.device("cuda", int(device)))
+    check(_lib.lib().gpemu_kde2d_dev(int(device), C.c_void_p(base), int(n_blocks), int(block_rows),
+                                     int(block_stride_rows), int(d), P, ptr(plan["pairs"]), ptr(plan["shear"]),
+                                     ptr(plan["bandwidth"]), G, ptr(plan["grid_a"]), ptr(plan["grid_b"]),
+                                     C.c_void_p(out.data_ptr()), int(workspace_bytes), _lib.current_stream(device)))
+    return out.cpu().numpy()
+
+
+def _kde2d_view(device, base, n_blocks, block_rows, block_stride_rows, d, workspace_bytes=0, **plan_kw):
+    """``kde_2d`` of device rows in the block layout: the plan from the device moments and extents, then the panels."""
+    S = int(n_blocks) * int(block_rows)
+    view = (device, base, n_blocks, block_rows, block_stride_rows, d)
+
+    def cov():
+        return _pair_moments_dev(*view)[1] * (S / (S - 1.0))
+    plan = kde2d_plan(S, d, cov=cov, extents=lambda pr, beta: _pair_moments_dev(*view, pr, beta, moments=False)[2],
+                      **plan_kw)
+    plan["density"] = _kde2d_dev(*view, plan, workspace_bytes)
+    return plan
 
 
 def _kde_plan(S, d, grid, bandwidth, n_grid, cut, spread):
@@ -285,25 +470,69 @@ def kde_1d(samples, grid=None, bandwidth=None, n_grid=200, cut=3.0, device=None)
     return {"grid": g, "density": dens, "bandwidth": h}
 
 
+def kde_2d(samples, pairs=None, covariance="full", bandwidth=None, shear=None, grid_a=None, grid_b=None, n_grid=100,
+           cut=3.0, bw_adjust=1.0, device=None, workspace_bytes=0):
+    """Gaussian kernel density of pairs of parameters of ``samples (S, d)``, the direct sum over all samples computed
+    as a matrix product on the fp64 matrix cores: a dict of ``pairs (P, 2)``, ``shear (P,)``,
+    ``bandwidth (P, 2)``, ``grid_a (P, G)``, ``grid_b (P, G)`` and ``density (P, G, G)`` (first axis: the pair's first
+    parameter, as ``hist_2d``).  ``density[p][a][b]`` is the density at ``x_i = grid_a[p][a]``, ``x_j = grid_b[p][b] +
+    shear[p] grid_a[p][a]`` (``kde_2d_mesh``).
+
+    Defaults (``kde2d_plan``): all pairs ``i < j`` in ``pair_indices`` order; ``covariance="full"`` is
+    ``scipy.stats.gaussian_kde`` of the pair (Scott's factor ``S ** (-1 / 6)`` times ``bw_adjust``, the full sample
+    covariance) evaluated on the sheared grid; ``"diagonal"`` the axis-aligned product kernel with ``h = f std(ddof=1)``;
+    the grids are ``linspace(min - cut h, max + cut h, n_grid)`` of x_i and of ``v = x_j - shear x_i``.  What is given
+    is used as given: ``bandwidth`` ``(2,)`` or ``(P, 2)``, ``shear`` a number or ``(P,)``, the grids ``(G,)`` or ``(P,
+    G)``, at most 512 points.  ``workspace_bytes`` bounds the partial tiles of a batch of pairs (0: half of the free
+    device memory); the bits of the result do not depend on it.  A NaN sample makes the panels of its pairs NaN."""
+    x, on_device = _samples(samples)
+    S, d = int(x.shape[0]), int(x.shape[1])
+    _check_shape(S, d)
+    if d < 2:
+        raise ValueError("a pair needs at least two parameters")
+    kw = dict(pairs=pairs, covariance=covariance, bandwidth=bandwidth, shear=shear, grid_a=grid_a, grid_b=grid_b,
+              n_grid=n_grid, cut=cut, bw_adjust=bw_adjust)
+    if on_device:
+        return _kde2d_view(x.device.index or 0, x.data_ptr(), 1, S, S, d, workspace_bytes, **kw)
+    plan = kde2d_plan_host(x, **kw)
+    _lib.require_device()
+    P, G = plan["grid_a"].shape
+    dens = np.empty((P, G, G))
+    check(_lib.lib().gpemu_kde2d(int(_lib.resolve_device(device)), S, d, ptr(x), P, ptr(plan["pairs"]),
+                                 ptr(plan["shear"]), ptr(plan["bandwidth"]), G, ptr(plan["grid_a"]),
+                                 ptr(plan["grid_b"]), ptr(dens), int(workspace_bytes)))
+    plan["density"] = dens
+    return plan
+
+
 KEYS = ("edges_1d", "edges_2d", "hist_1d", "pairs", "hist_2d", "n_inside", "confidence", "hpd", "kde_grid", "kde_density",
         "kde_bandwidth")
+KEYS_KDE2D = ("kde2d_pairs", "kde2d_shear", "kde2d_bandwidth", "kde2d_grid_a", "kde2d_grid_b", "kde2d_density")
 
 
-def assemble(hist, confidence, hpd, kde):
-    """The one dict of ``summary`` / ``DeviceSampler.marginals`` from its parts (``kde`` None: no ``kde_*`` keys)."""
+def assemble(hist, confidence, hpd, kde, kde2d=None):
+    """The one dict of ``summary`` / ``DeviceSampler.marginals`` from its parts (``kde`` None: no ``kde_*`` keys;
+    ``kde2d`` None: no ``kde2d_*`` keys)."""
     out = dict(hist)
     out["confidence"] = np.atleast_1d(np.asarray(confidence, dtype=np.float64))
     out["hpd"] = hpd
     if kde is not None:
         out["kde_grid"], out["kde_density"], out["kde_bandwidth"] = kde["grid"], kde["density"], kde["bandwidth"]
+    if kde2d is not None:
+        for key in KEYS_KDE2D:
+            out[key] = kde2d[key[len("kde2d_"):]]
     return out
 
 
-def summary(samples, lower, upper, bins_1d=100, bins_2d=50, confidence=(0.9,), kde=True, n_grid=200, device=None):
-    """``histograms``, ``hpd_intervals`` (``hpd (n_levels, d, 2)`` for ``confidence (n_levels,)``) and, with ``kde``,
-    ``kde_1d`` (``kde_grid``, ``kde_density``, ``kde_bandwidth``) of ``samples (S, d)`` in one dict."""
+def summary(samples, lower, upper, bins_1d=100, bins_2d=50, confidence=(0.9,), kde=True, n_grid=200, device=None,
+            kde2d=False, n_grid_2d=100, covariance_2d="full"):
+    """``histograms``, ``hpd_intervals`` (``hpd (n_levels, d, 2)`` for ``confidence (n_levels,)``), with ``kde``
+    ``kde_1d`` (``kde_grid``, ``kde_density``, ``kde_bandwidth``) and, with ``kde2d``, ``kde_2d`` of all pairs on
+    ``n_grid_2d`` points per axis (``KEYS_KDE2D``: ``kde2d_pairs``, ``kde2d_shear``, ``kde2d_bandwidth``,
+    ``kde2d_grid_a``, ``kde2d_grid_b``, ``kde2d_density``) of ``samples (S, d)`` in one dict."""
     conf = np.atleast_1d(np.asarray(confidence, dtype=np.float64))
     hist = histograms(samples, lower, upper, bins_1d, bins_2d, device=device)
     hpd = hpd_intervals(samples, conf, device=device)
     dens = kde_1d(samples, n_grid=n_grid, device=device) if kde else None
-    return assemble(hist, conf, hpd, dens)
+    dens2 = kde_2d(samples, covariance=covariance_2d, n_grid=n_grid_2d, device=device) if kde2d else None
+    return assemble(hist, conf, hpd, dens, dens2)

@@ -324,17 +324,21 @@ class DeviceSampler:
             return h.summary()
 
     def marginals(self, lower=None, upper=None, bins_1d=100, bins_2d=50, confidence=(0.9,), kde=True, n_grid=200,
-                  discard=0, thin=1, chain=None):
+                  discard=0, thin=1, chain=None, kde2d=False, n_grid_2d=100, covariance_2d="full"):
         """Marginal histograms, highest-density intervals and kernel densities (``gpemu.marginals.summary``; DESIGN.md
         §4.29) of the stored chain ``get_chain()[discard::thin].reshape(-1, d)``, taken where it lies: one dict with
         ``edges_1d``, ``edges_2d``, ``hist_1d``, ``pairs``, ``hist_2d``, ``n_inside``, ``confidence``, ``hpd (n_levels,
         d, 2)`` and, with ``kde``, ``kde_grid``, ``kde_density``, ``kde_bandwidth``.  The box defaults to the prior box
         of the sampler's models.  The histograms read the chain in place, thinned or stacked; the sort and the density
         read one parameter as one stride, so a thinned chain or one chain of a stacked sampler is first copied to a
-        dense device buffer.  Stacked samplers take ``chain=<index>``."""
+        dense device buffer.  With ``kde2d``: the 2-D kernel densities of all pairs (``gpemu.marginals.kde_2d``; DESIGN.md
+        §4.33) on ``n_grid_2d`` points per axis, ``covariance_2d`` ``"full"`` or ``"diagonal"``, as ``kde2d_pairs``,
+        ``kde2d_shear``, ``kde2d_bandwidth``, ``kde2d_grid_a``, ``kde2d_grid_b`` and ``kde2d_density``; they read the same
+        view in place, thinned or stacked.  Stacked samplers take ``chain=<index>``."""
         import torch
         from . import marginals as M
         src, n_blocks, nw, stride, S = self._stored_view(discard, thin, chain)
+        view = (self.device, src, n_blocks, nw, stride, self.d)
         if lower is None or upper is None:
             box = getattr(self.models[0], "prior_box", None)
             if box is None:
@@ -366,7 +370,12 @@ class DeviceSampler:
             h, g = M._kde_plan(S, d, None, None, n_grid, 3.0, spread)
             dens = {"grid": g, "density": M._kde_dev(self.device, src, S, d, g, h), "bandwidth": h}
         del dense
-        return M.assemble(hist, conf, ends[:n_out.size], dens)
+        dens2 = None
+        if kde2d:
+            if d < 2:
+                raise ValueError("kde2d needs at least two parameters")
+            dens2 = M._kde2d_view(*view, covariance=covariance_2d, n_grid=n_grid_2d)
+        return M.assemble(hist, conf, ends[:n_out.size], dens, dens2)
 
     def _data_chain(self, chain):
         """The data vector of the models' likelihood setup that ``chain`` of this sampler was run on."""
@@ -1319,9 +1328,9 @@ class EnsembleSampler:
 
     def get_marginals(self, discard=0, thin=1, **kw):
         """``gpemu.marginals.summary`` of ``get_chain(discard=discard, thin=thin, flat=True)`` (``lower``, ``upper``,
-        ``bins_1d``, ``bins_2d``, ``confidence``, ``kde``, ``n_grid``), computed on the device -- in place while the chain
-        still lives there (the box defaults to the prior box), from the host copy otherwise (``lower`` and ``upper``
-        are then required)."""
+        ``bins_1d``, ``bins_2d``, ``confidence``, ``kde``, ``n_grid``, ``kde2d``, ``n_grid_2d``, ``covariance_2d``), computed
+        on the device -- in place while the chain still lives there (the box defaults to the prior box), from the host
+        copy otherwise (``lower`` and ``upper`` are then required)."""
         discard, thin = int(discard), int(thin)
         if self._impl is not None and getattr(self, "_device", False) and not self.__dict__.get("_frozen"):
             return self._impl.marginals(discard=discard + thin - 1, thin=thin, **kw)

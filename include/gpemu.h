@@ -796,6 +796,56 @@ enum gpemu_marginal_path {
 /* out[0 .. min(n, GPEMU_MARGINAL_PATH_COUNT)) = the counters; returns GPEMU_MARGINAL_PATH_COUNT (or GPEMU_ERR_ARG). */
 int gpemu_marginal_path_counts(int64_t *out, int64_t n);
 
+/* ---- 2-D kernel densities of parameter pairs ----------------------------------------------------------
+ * The smooth off-diagonal panels of a corner plot from the WHOLE chain.  For pair p = (i, j), i != j, with shear beta,
+ * bandwidths (h_a, h_b) = bandwidth[2p], bandwidth[2p+1], grids g_a = grid_a[p*G ..], g_b = grid_b[p*G ..] and
+ * v_s = fma(-beta, x_si, x_sj),
+ *   out[(p*G + a)*G + b] = 1 / (S 2 pi h_a h_b) sum_s exp(-((g_a[a] - x_si) / h_a)^2 / 2) exp(-((g_b[b] - v_s) / h_b)^2 / 2),
+ * the direct sum over all S rows: no binning, no truncation.  With beta = C_ij / C_ii, h_a^2 = f^2 C_ii and
+ * h_b^2 = f^2 (C_jj - C_ij^2 / C_ii) this is scipy.stats.gaussian_kde's full-covariance density at the points
+ * (g_a[a], g_b[b] + beta g_a[a]); with beta = 0 the axis-aligned product-kernel density.
+ * The sum is a G x S by S x G matrix product whose operands are generated in the kernel (never stored) and multiplied
+ * on the fp64 matrix cores: workgroup (chunk of 8192 samples, 128 x 128 tile of the panel -- 64 x 64 where G <= 64 --,
+ * pair) writes a partial tile; a second kernel adds a panel element's partial tiles in chunk order and scales once by
+ * 1 / (S 2 pi h_a h_b).  No
+ * floating-point atomics: the order of every sum depends on S and G alone, so two calls give the same bytes, whatever
+ * the number of pairs, the batches or the device's free memory.  The rounding error of v_s is carried beside it, so the
+ * argument of the second factor is as accurate as that of the first.  A factor whose exponent is below -746 is exactly 0.
+ * A NaN in column i or j makes every element of the pair's panel NaN.
+ * Pairs are processed in batches whose partial tiles (8 G^2 ceil(S / 8192) bytes per pair) fit workspace_bytes (0 = half
+ * of the free device memory; if not one pair fits: GPEMU_ERR_HIP, sizes in the error text).
+ * pairs[2P] (int64), shear[P], bandwidth[2P], grid_a[P*G], grid_b[P*G] are HOST arrays in both forms.  GPEMU_ERR_ARG,
+ * before any launch: P < 1; G outside [1, 512]; d outside [1, 16]; S < 1 or S >= 2^31; a pair index outside [0, d) or
+ * i = j; a bandwidth that is not finite and > 0; a grid value or shear that is not finite; workspace_bytes < 0.
+ * gpemu_kde2d takes host samples X[S*d] and host out[P*G*G]; _dev reads the rows in the block layout of
+ * gpemu_marginal_hist_dev in place, writes the device array dout[P*G*G], works on `stream` and waits for it.
+ *
+ * gpemu_pair_moments_dev: what the default plan needs of device rows in the same layout.  mean[d] and cov[d*d] (the
+ * full covariance, divisor S; both NULL: skipped) by two passes with sums in a fixed order; for n_pairs > 0 pairs with
+ * their shear, ext[2p], ext[2p+1] = the minimum and maximum over the rows of fma(-shear[p], x_i, x_j), the expression
+ * the density kernel evaluates (NaN rows are passed over).  mean, cov, ext, pairs and shear are HOST arrays. */
+#define GPEMU_MAX_GRID_2D 512
+int gpemu_kde2d(int device, int64_t S, int d, const double *X, int64_t n_pairs, const int64_t *pairs, const double *shear,
+                const double *bandwidth, int G, const double *grid_a, const double *grid_b, double *out,
+                int64_t workspace_bytes);
+int gpemu_kde2d_dev(int device, const double *dX, int64_t n_blocks, int64_t block_rows, int64_t block_stride_rows, int d,
+                    int64_t n_pairs, const int64_t *pairs, const double *shear, const double *bandwidth, int G,
+                    const double *grid_a, const double *grid_b, double *dout, int64_t workspace_bytes, void *stream);
+int gpemu_pair_moments_dev(int device, const double *dX, int64_t n_blocks, int64_t block_rows, int64_t block_stride_rows,
+                           int d, double *mean, double *cov, int64_t n_pairs, const int64_t *pairs, const double *shear,
+                           double *ext, void *stream);
+/* Which launches ran.  A set of its own: gpemu_marginal_path keeps its five. */
+enum gpemu_kde2d_path {
+  GPEMU_KDE2D_PATH_DENSITY = 0,   /* one launch of the density kernel (the partial tiles of a batch of pairs)          */
+  GPEMU_KDE2D_PATH_PAIR_BATCH,    /* one batch of pairs through the partial-tile workspace                             */
+  GPEMU_KDE2D_PATH_PARTIAL_SUM,   /* one launch of the kernel that adds a batch's partial tiles in chunk order          */
+  GPEMU_KDE2D_PATH_MOMENTS,       /* one mean-and-covariance computation of gpemu_pair_moments_dev                      */
+  GPEMU_KDE2D_PATH_EXTENTS,       /* one extents computation of gpemu_pair_moments_dev                                  */
+  GPEMU_KDE2D_PATH_COUNT
+};
+/* out[0 .. min(n, GPEMU_KDE2D_PATH_COUNT)) = the counters; returns GPEMU_KDE2D_PATH_COUNT (or GPEMU_ERR_ARG). */
+int gpemu_kde2d_path_counts(int64_t *out, int64_t n);
+
 /* ---- per-observable log-likelihoods, PSIS-LOO and WAIC ------------------------------------------------
  * Which observable does what to the posterior, and how well is each predicted by all the others -- what the reference
  * answers by a second analysis on a subset of the observables and otherwise leaves open (ref: plot_analyses.py:144,
