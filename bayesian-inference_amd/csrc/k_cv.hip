@@ -16,16 +16,11 @@
 // for bit, and independent of how the problems are dealt into chunks.
 #include "internal.h"
 #include "gemm.h"
+#include "wave_dev.h"
 
 namespace gpemu {
 
 constexpr int CV_NB = 64;   // padding unit of the fold operands (launch_gemm, the blocked Cholesky)
-
-static __device__ __forceinline__ double wave_sum(double s) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off, 64);
-  return s;
-}
 
 // LOO: one wave per (point i, PC p).  Row i of Wt[p] is non-zero in columns [i, N) only.
 __global__ __launch_bounds__(256) void cv_loo_kernel(const double *__restrict__ Wt, int64_t Npad, int N, int k,

@@ -173,19 +173,11 @@ __device__ __forceinline__ void state_after_prev(const FrontArgs &fa, int x, dou
 // loglik_lowrank_kernel<KMAX> (whose value does not depend on KMAX: one instantiation serves 17 <= k <= 32 here)
 template <int KMAX>
 __device__ __forceinline__ double front_loglik(const FrontGroup &gr, bool inside, int64_t b, int lane) {
-  constexpr bool PRE = KMAX <= 16;
-  double gpre[PRE ? KMAX : 1];
-  if (PRE) {
-#pragma unroll
-    for (int q = 0; q < KMAX; ++q) gpre[q] = (q < gr.k && lane < gr.k) ? gr.G[q * gr.k + lane] : 0.0;
-  }
-  const double gl_pre = (lane < gr.k) ? gr.g0[lane] : 0.0;
-  const double sc0_pre = gr.scal[0], sc1_pre = gr.scal[1];
+  const BlockPre<KMAX> pre = prefetch_block<KMAX>(gr.G, gr.g0, gr.scal, gr.k, lane);
   double mu, sd;
   walker_mean_sd<(KMAX <= 16 ? 16 : 32)>(gr.mean_part_prev, gr.vsq_part, gr.kdiag, nullptr, nullptr, b, gr.Bcap, gr.k,
                                          gr.nchunk_prev, gr.nrb_prev, lane, mu, sd);
-  return walker_loglik_lowrank<KMAX, PRE>(inside, mu, sd, gpre, gl_pre, sc0_pre, sc1_pre, gr.G, gr.g0, gr.scal, gr.k,
-                                          gr.nblk, lane);
+  return walker_loglik_lowrank<KMAX>(inside, mu, sd, pre, gr.G, gr.g0, gr.scal, gr.k, gr.nblk, lane);
 }
 
 // 32 < k <= 64: the arithmetic of loglik_lowrank_lds_kernel, the wave's k x (k + 1) matrix in `M`
@@ -299,14 +291,14 @@ __global__ __launch_bounds__(256, KBIG ? GPEMU_FRONT_KBIG_WPE : 3) void front_ke
   if (does_ll) {
     const int i = g * 4 + wave;
     if (i < fa.prev_cnt) {
-      bool in = true;
-      if (lane < fa.d) in = (fa.Xq_prev[(int64_t)i * DPAD + lane] > fa.lo[lane]) && (fa.Xq_prev[(int64_t)i * DPAD + lane] < fa.hi[lane]);
-      const bool inside = __all(in);
+      const bool inside = inside_box(fa.Xq_prev, i, DPAD, fa.d, fa.lo, fa.hi, lane);
       // the groups' log-likelihoods, added in the order the single-GPU run accumulates them (lp_g + sum so far)
       double total = 0.0;
       for (int t = 0; t < fa.ngroups; ++t) {
         const FrontGroup &gr = fa.grp[t];
         double lp;
+        // (this kernel's own set of instances, not with_kmax's: 17 ... 32 PCs share one, and only where the launch has
+        // such a group, KBIG)
         if (gr.k <= 4) lp = front_loglik<4>(gr, inside, i, lane);
         else if (gr.k <= 8) lp = front_loglik<8>(gr, inside, i, lane);
         else if (gr.k <= 12) lp = front_loglik<12>(gr, inside, i, lane);

@@ -25,6 +25,7 @@
 
 #include "internal.h"
 #include "gemm.h"
+#include "loglik_dev.h"
 #include "matern_dev.h"
 
 namespace gpemu {
@@ -128,77 +129,26 @@ struct GradLikArgs {
 
 // One wave per (row, observable block) (one wave per workgroup: k (2 k + 1) doubles of LDS), lane = PC: the blocks'
 // factorisations are the serial part, so they run side by side (as loglik_tasks_kernel's do) and grad_lik_reduce_kernel
-// adds their terms in block order.  The term is walker_loglik_lowrank_lds's (loglik_dev.h); the factor L stays in M's
-// lower triangle for the three further solves.  Rows outside the box write nothing.
+// adds their terms in block order.  The term is the likelihood's own lowrank_block_term_lds (loglik_dev.h), which also
+// fills Y = S G and hands back h and y; the factor L stays in M's lower triangle for the three further solves.  Rows
+// outside the box write nothing.
 __global__ __launch_bounds__(64) void grad_loglik_kernel(GradLikArgs g) {
   extern __shared__ __attribute__((aligned(16))) double smem[];
   const int lane = threadIdx.x, k = g.k, ldm = k + 1;
   const int64_t c = blockIdx.x, b = g.off + c;
   const int o = blockIdx.y;
   double *M = smem, *Y = smem + (size_t)k * ldm;
-  bool in = true;
-  if (lane < g.d) {
-    const double x = g.X[b * g.d + lane];
-    in = (x > g.lo[lane]) && (x < g.hi[lane]);      // a NaN fails both: outside
-  }
-  const bool inside = __all(in);
-  if (!inside) return;
+  if (!inside_box(g.X, b, g.d, g.d, g.lo, g.hi, lane)) return;
   double mu = 0.0, sd = 0.0;
   if (lane < k) {
     mu = g.mean[c * k + lane];
     sd = sqrt(g.var[c * k + lane]);
   }
-  double total = 0.0, av = 0.0, bv = 0.0;
+  double av = 0.0, bv = 0.0;
   const double *Go = g.G + (int64_t)o * k * k;
-  double h = 0.0;
-  const double gl = (lane < k) ? g.g0[(int64_t)o * k + lane] : 0.0;
-  for (int q = 0; q < k; ++q) {
-    const double gq = (lane < k) ? Go[q * k + lane] : 0.0;       // G symmetric: column-wise, coalesced
-    h = fma(gq, __shfl(mu, q), h);
-    const double sq = __shfl(sd, q);
-    if (lane < k) {
-      M[lane * ldm + q] = ((lane == q) ? 1.0 : 0.0) + sd * gq * sq;
-      Y[q * k + lane] = sq * gq;                                  // (S G)[q][lane]
-    }
-  }
-  h += gl;
-  double t = (lane < k) ? mu * (h + gl) : 0.0;
-  for (int off = 32; off > 0; off >>= 1) t += __shfl_xor(t, off);
-  const double quadA = t + g.scal[2 * o];
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  double logdiag = 0.0;
-  for (int j = 0; j < k; ++j) {
-    const double piv = sqrt(M[j * ldm + j]);
-    __builtin_amdgcn_wave_barrier();
-    if (lane == j) {
-      M[j * ldm + j] = piv;
-      logdiag = log(piv);
-    }
-    if (lane > j && lane < k) M[lane * ldm + j] = M[lane * ldm + j] / piv;
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    if (lane > j && lane < k) {
-      const double lij = M[lane * ldm + j];
-      for (int cc = j + 1; cc <= lane; ++cc) M[lane * ldm + cc] -= lij * M[cc * ldm + j];
-    }
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-  }
-  // y = L^-1 (S h)
-  double y = (lane < k) ? sd * h : 0.0;
-  for (int j = 0; j < k; ++j) {
-    const double zj = __shfl(y, j) / M[j * ldm + j];
-    if (lane == j) y = zj;
-    if (lane > j && lane < k) y = fma(-M[lane * ldm + j], zj, y);
-  }
-  double ww = (lane < k) ? y * y : 0.0;
-  double ldsum = logdiag;
-  for (int off = 32; off > 0; off >>= 1) {
-    ww += __shfl_xor(ww, off);
-    ldsum += __shfl_xor(ldsum, off);
-  }
-  total += -0.5 * (quadA - ww) - 0.5 * (g.scal[2 * o + 1] + 2.0 * ldsum);
+  double h, y;   // h = G_o m + g0_o, y = L^-1 (S h)
+  const double total =
+      lowrank_block_term_lds<true>(Go, g.g0 + (int64_t)o * k, g.scal + 2 * o, k, mu, sd, lane, M, ldm, h, y, Y);
   // Y_:lane = L^-1 (S G)_:lane, lane = right-hand side: L's entries are broadcast reads, Y's are conflict free
   double ynorm = 0.0;
   if (lane < k) {

@@ -132,7 +132,7 @@ __global__ __launch_bounds__(256) void lik_z_kernel(const double *__restrict__ W
       const double r = setup_rhs(c, f, F, k, nch, comp, s, smean, yexp, src);
       acc = fma(W[(int64_t)i * Np + j], r, acc);
     }
-    for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
+    acc = wave_sum(acc);
     if (lane == 0) Z[(int64_t)(f0 + i) * k1 + c] = acc;
   }
 }
@@ -223,22 +223,12 @@ __global__ __launch_bounds__(256) void loglik_lowrank_kernel(
   // everything that does not depend on the GP stage is requested first: the accept operands (a dependent
   // index -> state chain) and the first observable block's constants
   const AcceptOperands ao = load_accept_operands(Xq, b, lane, aa);
-  constexpr bool PRE = KMAX <= 16;
-  double gpre[PRE ? KMAX : 1];
-  if (PRE) {
-#pragma unroll
-    for (int q = 0; q < KMAX; ++q) gpre[q] = (q < k && lane < k) ? G[q * k + lane] : 0.0;
-  }
-  const double gl_pre = (lane < k) ? g0[lane] : 0.0;
-  const double sc0_pre = scal[0], sc1_pre = scal[1];
-
-  bool in = true;
-  if (lane < d) in = (Xq[b * dpad_of(d) + lane] > lo[lane]) && (Xq[b * dpad_of(d) + lane] < hi[lane]);
-  const bool inside = __all(in);
+  const BlockPre<KMAX> pre = prefetch_block<KMAX>(G, g0, scal, k, lane);
+  const bool inside = inside_box(Xq, b, dpad_of(d), d, lo, hi, lane);
 
   double mu, sd;
   walker_mean_sd<(KMAX <= 16 ? 16 : 32)>(mean_part, vsq_part, kdiag, mean_out, var_out, b, Bcap, k, nchunk, nrb, lane, mu, sd);
-  const double total = walker_loglik_lowrank<KMAX, PRE>(inside, mu, sd, gpre, gl_pre, sc0_pre, sc1_pre, G, g0, scal, k, nblk, lane);
+  const double total = walker_loglik_lowrank<KMAX>(inside, mu, sd, pre, G, g0, scal, k, nblk, lane);
   finish_walker(total, out, b, d, lane, accumulate, aa, ao);
 }
 
@@ -262,9 +252,7 @@ __global__ __launch_bounds__(256) void loglik_lowrank_lds_kernel(
   }
   double *M = smem + (size_t)wave * k * (k + 1);
   const int ldm = k + 1;
-  bool in = true;
-  if (lane < d) in = (Xq[b * dpad_of(d) + lane] > lo[lane]) && (Xq[b * dpad_of(d) + lane] < hi[lane]);
-  const bool inside = __all(in);
+  const bool inside = inside_box(Xq, b, dpad_of(d), d, lo, hi, lane);
   double mu, sd;
   if (k <= 32) walker_mean_sd<32>(mean_part, vsq_part, kdiag, mean_out, var_out, b, Bcap, k, nchunk, nrb, lane, mu, sd);
   else walker_mean_sd<64>(mean_part, vsq_part, kdiag, mean_out, var_out, b, Bcap, k, nchunk, nrb, lane, mu, sd);
@@ -292,19 +280,12 @@ struct LoglikGroups {
 
 template <int KMAX>
 __device__ __forceinline__ double group_loglik(const LoglikGroup &gr, bool inside, int64_t b, int lane) {
-  constexpr bool PRE = KMAX <= 16;
   const int k = gr.k;
-  double gpre[PRE ? KMAX : 1];
-  if (PRE) {
-#pragma unroll
-    for (int q = 0; q < KMAX; ++q) gpre[q] = (q < k && lane < k) ? gr.G[q * k + lane] : 0.0;
-  }
-  const double gl_pre = (lane < k) ? gr.g0[lane] : 0.0;
-  const double sc0_pre = gr.scal[0], sc1_pre = gr.scal[1];
+  const BlockPre<KMAX> pre = prefetch_block<KMAX>(gr.G, gr.g0, gr.scal, k, lane);
   double mu, sd;
   walker_mean_sd<(KMAX <= 16 ? 16 : 32)>(gr.mean_part, gr.vsq_part, gr.kdiag, gr.mean_out, gr.var_out, b, gr.Bcap, k,
                                          gr.nchunk, gr.nrb, lane, mu, sd);
-  return walker_loglik_lowrank<KMAX, PRE>(inside, mu, sd, gpre, gl_pre, sc0_pre, sc1_pre, gr.G, gr.g0, gr.scal, k, gr.nblk, lane);
+  return walker_loglik_lowrank<KMAX>(inside, mu, sd, pre, gr.G, gr.g0, gr.scal, k, gr.nblk, lane);
 }
 
 __global__ __launch_bounds__(256) void loglik_groups_kernel(const double *__restrict__ Xq, LoglikGroups lg,
@@ -322,19 +303,8 @@ __global__ __launch_bounds__(256) void loglik_groups_kernel(const double *__rest
     if (gw == 0) ao = load_accept_operands(Xq, b, lane, aa);
     for (int g = gw; g < lg.ng; g += wv) {
       const LoglikGroup &gr = lg.g[g];
-      bool in = true;
-      if (lane < d) in = (Xq[b * dpad_of(d) + lane] > gr.lo[lane]) && (Xq[b * dpad_of(d) + lane] < gr.hi[lane]);
-      const bool inside = __all(in);
-      double lp;
-      // (the value does not depend on KMAX: loglik_dev.h)
-      if (gr.k <= 4) lp = group_loglik<4>(gr, inside, b, lane);
-      else if (gr.k <= 8) lp = group_loglik<8>(gr, inside, b, lane);
-      else if (gr.k <= 12) lp = group_loglik<12>(gr, inside, b, lane);
-      else if (gr.k <= 16) lp = group_loglik<16>(gr, inside, b, lane);
-      else if (gr.k <= 20) lp = group_loglik<20>(gr, inside, b, lane);
-      else if (gr.k <= 24) lp = group_loglik<24>(gr, inside, b, lane);
-      else if (gr.k <= 28) lp = group_loglik<28>(gr, inside, b, lane);
-      else lp = group_loglik<32>(gr, inside, b, lane);
+      const bool inside = inside_box(Xq, b, dpad_of(d), d, gr.lo, gr.hi, lane);
+      const double lp = with_kmax(gr.k, [&](auto km) { return group_loglik<decltype(km)::value>(gr, inside, b, lane); });
       if (lane == 0) s_lp[slot][g] = lp;
     }
   }
@@ -370,22 +340,15 @@ struct LoglikTasks {
 
 template <int KMAX>
 __device__ __forceinline__ double task_term(const LoglikGroup &gr, int o, int64_t b, int lane) {
-  constexpr bool PRE = KMAX <= 16;
   const int k = gr.k;
   // the block's own constants as "block 0" of lowrank_block_term: requested ahead of the partial sums where the registers
-  // allow (PRE), the same values either way
+  // allow (BlockPre), the same values either way
   const double *G = gr.G + (int64_t)o * k * k, *g0 = gr.g0 + (int64_t)o * k, *scal = gr.scal + 2 * o;
-  double gpre[PRE ? KMAX : 1];
-  if (PRE) {
-#pragma unroll
-    for (int q = 0; q < KMAX; ++q) gpre[q] = (q < k && lane < k) ? G[q * k + lane] : 0.0;
-  }
-  const double gl_pre = (lane < k) ? g0[lane] : 0.0;
-  const double sc0_pre = scal[0], sc1_pre = scal[1];
+  const BlockPre<KMAX> pre = prefetch_block<KMAX>(G, g0, scal, k, lane);
   double mu, sd;
   walker_mean_sd<(KMAX <= 16 ? 16 : 32)>(gr.mean_part, gr.vsq_part, gr.kdiag, o == 0 ? gr.mean_out : nullptr,
                                          o == 0 ? gr.var_out : nullptr, b, gr.Bcap, k, gr.nchunk, gr.nrb, lane, mu, sd);
-  return lowrank_block_term<KMAX, PRE>(0, mu, sd, gpre, gl_pre, sc0_pre, sc1_pre, G, g0, scal, k, lane);
+  return lowrank_block_term<KMAX>(0, mu, sd, pre, G, g0, scal, k, lane);
 }
 
 // grid: workgroup j of proposal b at index j B + b (the workgroups with the longest tasks first)
@@ -406,19 +369,10 @@ __global__ __launch_bounds__(64 * LL_TASK_WAVES) void loglik_tasks_kernel(const 
   for (int t = lt.wstart[slot]; t < lt.wstart[slot + 1]; ++t) {
     const int g = lt.tg[t], o = lt.to[t];
     const LoglikGroup &gr = lt.g[g];
-    bool in = true;
-    if (lane < d) in = (Xq[b * dpad_of(d) + lane] > gr.lo[lane]) && (Xq[b * dpad_of(d) + lane] < gr.hi[lane]);
     double term = 0.0;
-    if (__all(in)) {                                         // (outside the box the group's term is -inf whatever the blocks say)
-      if (gr.k <= 4) term = task_term<4>(gr, o, b, lane);
-      else if (gr.k <= 8) term = task_term<8>(gr, o, b, lane);
-      else if (gr.k <= 12) term = task_term<12>(gr, o, b, lane);
-      else if (gr.k <= 16) term = task_term<16>(gr, o, b, lane);
-      else if (gr.k <= 20) term = task_term<20>(gr, o, b, lane);
-      else if (gr.k <= 24) term = task_term<24>(gr, o, b, lane);
-      else if (gr.k <= 28) term = task_term<28>(gr, o, b, lane);
-      else term = task_term<32>(gr, o, b, lane);
-    }
+    // (outside the box the group's term is -inf whatever the blocks say)
+    if (inside_box(Xq, b, dpad_of(d), d, gr.lo, gr.hi, lane))
+      term = with_kmax(gr.k, [&](auto km) { return task_term<decltype(km)::value>(gr, o, b, lane); });
     if (lane == 0) {
       s_term[lt.first[g] + o] = term;
       // straight to the device's coherence point: the workgroup that reads it may run on another XCD, whose L2 may still
@@ -444,10 +398,8 @@ __global__ __launch_bounds__(64 * LL_TASK_WAVES) void loglik_tasks_kernel(const 
     double total = 0.0;
     for (int g = 0; g < lt.ng; ++g) {
       const LoglikGroup &gr = lt.g[g];
-      bool in = true;
-      if (lane < d) in = (Xq[b * dpad_of(d) + lane] > gr.lo[lane]) && (Xq[b * dpad_of(d) + lane] < gr.hi[lane]);
       double lp = -INFINITY;
-      if (__all(in)) {
+      if (inside_box(Xq, b, dpad_of(d), d, gr.lo, gr.hi, lane)) {
         lp = 0.0;
         for (int o = lt.first[g]; o < lt.first[g + 1]; ++o) lp += s_term[o];      // walker_loglik_lowrank's loop
       }
@@ -584,26 +536,12 @@ int launch_loglik_lowrank(gpemu_model *m, int64_t B, const double *dXq, double *
   const int k = (int)m->k;
   AcceptArgs a = aa ? *aa : AcceptArgs();
   const dim3 grid((unsigned)((B + 3) / 4)), block(256);
-#define GP_LAUNCH_LL(KM)                                                                            \
-  hipLaunchKernelGGL(loglik_lowrank_kernel<KM>, grid, block, 0, st, dXq, m->lo, m->hi, w.mean_part,  \
-                     w.vsq_part, m->kdiag, m->G, m->g0, m->scal, dout, w.mean, w.var, B, w.Bcap,     \
-                     (int)m->d, k, w.cur_nchunk, w.cur_nrb, (int)m->nblk, accumulate, a)
-  if (k <= 4) {
-    GP_LAUNCH_LL(4);
-  } else if (k <= 8) {
-    GP_LAUNCH_LL(8);
-  } else if (k <= 12) {
-    GP_LAUNCH_LL(12);
-  } else if (k <= 16) {
-    GP_LAUNCH_LL(16);
-  } else if (k <= 20) {
-    GP_LAUNCH_LL(20);
-  } else if (k <= 24) {
-    GP_LAUNCH_LL(24);
-  } else if (k <= 28) {
-    GP_LAUNCH_LL(28);
-  } else if (k <= 32) {
-    GP_LAUNCH_LL(32);
+  if (k <= 32) {
+    with_kmax(k, [&](auto km) {
+      hipLaunchKernelGGL(loglik_lowrank_kernel<decltype(km)::value>, grid, block, 0, st, dXq, m->lo, m->hi, w.mean_part,
+                         w.vsq_part, m->kdiag, m->G, m->g0, m->scal, dout, w.mean, w.var, B, w.Bcap, (int)m->d, k,
+                         w.cur_nchunk, w.cur_nrb, (int)m->nblk, accumulate, a);
+    });
   } else {
     size_t shm = sizeof(double) * 4 * (size_t)k * (k + 1);
     if (shm > 64 * 1024)   // allowed once, up to what k <= 64 (gpemu_model_create) can ask for
@@ -612,7 +550,6 @@ int launch_loglik_lowrank(gpemu_model *m, int64_t B, const double *dXq, double *
                        w.vsq_part, m->kdiag, m->G, m->g0, m->scal, dout, w.mean, w.var, B, w.Bcap,
                        (int)m->d, k, w.cur_nchunk, w.cur_nrb, (int)m->nblk, accumulate, a);
   }
-#undef GP_LAUNCH_LL
   GP_HIP(hipGetLastError());
   path_count(GPEMU_PATH_LOGLIK_LOWRANK);
   return GPEMU_OK;

@@ -7,8 +7,8 @@
 // log-likelihood is a sum of per-observable terms; T[o][s] is the term of block o for row s, in gpemu_logpost's
 // normalisation.  PC means / variances come from gpemu_gp_predict_dev in fixed chunks of LOO_CHUNK logical rows (a chunk
 // that is not contiguous in the caller's block layout is gathered first: k_postpred.hip's rule), then
-//   loo_terms_kernel   one wave per (row, block): lowrank_block_term<KMAX> as the likelihood has it (k <= 32) or the
-//                      per-block body of walker_loglik_lowrank_lds restated (33 <= k <= 64).  No prior box: a likelihood.
+//   loo_terms_kernel   one wave per (row, block): the likelihood's own block term (loglik_dev.h), lowrank_block_term<KMAX>
+//                      (k <= 32) or lowrank_block_term_lds (33 <= k <= 64).  No prior box: a likelihood.
 //
 // PSIS of rows V[R][S] of log-likelihoods, per row: x_s = -V_s - max(-V) = min(V) - V_s (the same rounding), so the
 // ascending order statistics of x are min(V) - (the descending ones of V): the row itself is sorted (k_rows.hip's radix
@@ -24,7 +24,6 @@
 // index order, a fixed butterfly, the waves in order, the chunks in order.  No floating-point atomics: no result bit
 // depends on the grid, on the batches of rows that fit the workspace or on the run.
 #include <algorithm>
-#include <atomic>
 #include <cfloat>
 #include <cmath>
 #include <vector>
@@ -43,8 +42,7 @@ constexpr int LOO_NSUM = 5;           // partial sums of the main pass
 constexpr int LOO_STATE = 16;         // doubles of per-row state
 enum { LS_VMIN = 0, LS_VMAX, LS_XC, LS_EXC, LS_KHAT, LS_SIGMA, LS_MXW, LS_MXE, LS_LSEW, LS_A, LS_Q, LS_B, LS_MEANV, LS_E };
 
-static std::atomic<int64_t> g_loo_counts[GPEMU_LOO_PATH_COUNT];
-static void loo_path_count(int path, int64_t by = 1) { g_loo_counts[path].fetch_add(by, std::memory_order_relaxed); }
+static inline void loo_path_count(int path) { count_path(PATHS_LOO, path); }   // enum gpemu_loo_path
 
 static __device__ __forceinline__ double loo_nan() { return __longlong_as_double(0x7ff8000000000000ll); }
 
@@ -58,71 +56,6 @@ struct TermArgs {
   double *T;
   int64_t ldt;
 };
-
-// block o's constants as "block 0" of lowrank_block_term (k_loglik.hip: task_term)
-template <int KMAX>
-static __device__ __forceinline__ double loo_term_reg(const double *G, const double *g0, const double *scal, int k, double mu,
-                                                      double sd, int lane) {
-  constexpr bool PRE = KMAX <= 16;
-  double gpre[PRE ? KMAX : 1];
-  if (PRE) {
-#pragma unroll
-    for (int q = 0; q < KMAX; ++q) gpre[q] = (q < k && lane < k) ? G[q * k + lane] : 0.0;
-  }
-  const double gl_pre = (lane < k) ? g0[lane] : 0.0;
-  const double sc0_pre = scal[0], sc1_pre = scal[1];
-  return lowrank_block_term<KMAX, PRE>(0, mu, sd, gpre, gl_pre, sc0_pre, sc1_pre, G, g0, scal, k, lane);
-}
-
-// 33 <= k <= 64: the per-block body of walker_loglik_lowrank_lds (loglik_dev.h), the k x k matrix in the wave's LDS
-static __device__ __forceinline__ double loo_term_lds(const double *__restrict__ Go, const double *__restrict__ g0o,
-                                                      const double *__restrict__ scalo, int k, double mu, double sd, int lane,
-                                                      double *M, int ldm) {
-  double h = 0.0, gl = (lane < k) ? g0o[lane] : 0.0;
-  for (int q = 0; q < k; ++q) {
-    double gq = (lane < k) ? Go[q * k + lane] : 0.0;
-    h = fma(gq, __shfl(mu, q), h);
-    double sq = __shfl(sd, q);
-    if (lane < k) M[lane * ldm + q] = ((lane == q) ? 1.0 : 0.0) + sd * gq * sq;
-  }
-  h += gl;
-  double t = (lane < k) ? mu * (h + gl) : 0.0;
-  for (int off = 32; off > 0; off >>= 1) t += __shfl_xor(t, off);
-  const double quadA = t + scalo[0];
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  double logdiag = 0.0;
-  for (int j = 0; j < k; ++j) {
-    double piv = sqrt(M[j * ldm + j]);
-    __builtin_amdgcn_wave_barrier();
-    if (lane == j) {
-      M[j * ldm + j] = piv;
-      logdiag = log(piv);
-    }
-    if (lane > j && lane < k) M[lane * ldm + j] = M[lane * ldm + j] / piv;
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    if (lane > j && lane < k) {
-      double lij = M[lane * ldm + j];
-      for (int c = j + 1; c <= lane; ++c) M[lane * ldm + c] -= lij * M[c * ldm + j];
-    }
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-  }
-  double y = (lane < k) ? sd * h : 0.0;
-  for (int j = 0; j < k; ++j) {
-    double zj = __shfl(y, j) / M[j * ldm + j];
-    if (lane == j) y = zj;
-    if (lane > j && lane < k) y = fma(-M[lane * ldm + j], zj, y);
-  }
-  double ww = (lane < k) ? y * y : 0.0;
-  double ldsum = logdiag;
-  for (int off = 32; off > 0; off >>= 1) {
-    ww += __shfl_xor(ww, off);
-    ldsum += __shfl_xor(ldsum, off);
-  }
-  return -0.5 * (quadA - ww) - 0.5 * (scalo[1] + 2.0 * ldsum);
-}
 
 // task t = o nb + s of the chunk on a wave of its own, four to a workgroup; KMAX = 0: the LDS form
 template <int KMAX>
@@ -146,8 +79,10 @@ __global__ __launch_bounds__(256) void loo_terms_kernel(TermArgs a) {
   }
   const double *Go = a.G + (int64_t)o * k * k, *g0o = a.g0 + (int64_t)o * k, *sco = a.scal + 2 * o;
   double term;
-  if constexpr (KMAX == 0) term = loo_term_lds(Go, g0o, sco, k, mu, sd, lane, loo_smem + (size_t)wave * k * (k + 1), k + 1);
-  else term = loo_term_reg<(KMAX ? KMAX : 4)>(Go, g0o, sco, k, mu, sd, lane);
+  if constexpr (KMAX == 0)   // 33 <= k <= 64: the k x k matrix in the wave's LDS
+    term = lowrank_block_term_lds(Go, g0o, sco, k, mu, sd, lane, loo_smem + (size_t)wave * k * (k + 1), k + 1);
+  else                       // block o's constants as "block 0" of lowrank_block_term (k_loglik.hip: task_term)
+    term = lowrank_block_term<KMAX>(0, mu, sd, prefetch_block<KMAX>(Go, g0o, sco, k, lane), Go, g0o, sco, k, lane);
   if (!__all(fin)) term = loo_nan();
   if (lane == 0) a.T[(int64_t)o * a.ldt + a.r0 + s] = term;
 }
@@ -155,32 +90,18 @@ __global__ __launch_bounds__(256) void loo_terms_kernel(TermArgs a) {
 static int launch_loo_terms(const TermArgs &a, hipStream_t st) {
   const int k = a.k;
   const dim3 grid((unsigned)((a.nb * a.nblk + 3) / 4)), block(256);
-#define GP_LAUNCH_LOO(KM) hipLaunchKernelGGL(loo_terms_kernel<KM>, grid, block, 0, st, a)
-  if (k <= 4) GP_LAUNCH_LOO(4);
-  else if (k <= 8) GP_LAUNCH_LOO(8);
-  else if (k <= 12) GP_LAUNCH_LOO(12);
-  else if (k <= 16) GP_LAUNCH_LOO(16);
-  else if (k <= 20) GP_LAUNCH_LOO(20);
-  else if (k <= 24) GP_LAUNCH_LOO(24);
-  else if (k <= 28) GP_LAUNCH_LOO(28);
-  else if (k <= 32) GP_LAUNCH_LOO(32);
-  else {
+  if (k <= 32) {
+    with_kmax(k, [&](auto km) { hipLaunchKernelGGL(loo_terms_kernel<decltype(km)::value>, grid, block, 0, st, a); });
+  } else {
     const size_t shm = sizeof(double) * 4 * (size_t)k * (k + 1);
     if (shm > 64 * 1024) GP_TRY(allow_dynamic_lds((const void *)loo_terms_kernel<0>, (int)(sizeof(double) * 4 * 64 * 65)));
     hipLaunchKernelGGL(loo_terms_kernel<0>, grid, block, shm, st, a);
   }
-#undef GP_LAUNCH_LOO
   GP_HIP(hipGetLastError());
   return GPEMU_OK;
 }
 
 // ---- sums in a fixed tree ----------------------------------------------------------------------------------------------
-static __device__ __forceinline__ double loo_wave_sum(double s) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off, 64);
-  return s;
-}
-
 // the sum of f(i), i < n, by the whole workgroup (256 threads), in every thread: chunks of LOO_SUM in order, within a chunk
 // every lane its 16 elements in index order, the butterfly, the waves in order.  ws: 4 doubles of LDS
 template <class F>
@@ -193,7 +114,7 @@ static __device__ __forceinline__ double loo_wg_sum(int64_t n, F f, double *ws) 
       const int64_t i = c0 + (int64_t)j * 256 + tid;
       if (i < n) acc += f(i);
     }
-    acc = loo_wave_sum(acc);
+    acc = wave_sum(acc);
     if ((tid & 63) == 0) ws[tid >> 6] = acc;
     __syncthreads();
     total += ((ws[0] + ws[1]) + ws[2]) + ws[3];
@@ -381,7 +302,7 @@ static __device__ __forceinline__ double loo_wg_combine(double v, bool is_max, d
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) v = fmax(v, __shfl_xor(v, off, 64));
   } else {
-    v = loo_wave_sum(v);
+    v = wave_sum(v);
   }
   __syncthreads();
   if ((tid & 63) == 0) ws[tid >> 6] = v;
@@ -694,11 +615,7 @@ using namespace gpemu;
 
 extern "C" {
 
-int gpemu_loo_path_counts(int64_t *out, int64_t n) {
-  GP_ARG(out && n >= 0, "out, n");
-  for (int64_t i = 0; i < n && i < GPEMU_LOO_PATH_COUNT; ++i) out[i] = g_loo_counts[i].load(std::memory_order_relaxed);
-  return GPEMU_LOO_PATH_COUNT;
-}
+int gpemu_loo_path_counts(int64_t *out, int64_t n) { return read_path_counts(PATHS_LOO, out, n); }
 
 int gpemu_model_observable_blocks(const gpemu_model *m, int64_t *n_blocks) {
   GP_ARG(m && n_blocks, "null pointer");

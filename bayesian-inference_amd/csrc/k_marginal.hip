@@ -27,6 +27,7 @@
 #include "internal.h"
 #include "rows_dev.h"
 #include "sampler_internal.h"
+#include "wave_dev.h"
 
 namespace gpemu {
 
@@ -424,8 +425,7 @@ __global__ __launch_bounds__(256) void kde_sum_kernel(const double *__restrict__
   const double *p = part + (int64_t)blockIdx.x * nchunk;
   double a = 0.0;
   for (int64_t c = tid; c < nchunk; c += 256) a += p[c];
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) a += __shfl_xor(a, off, 64);
+  a = wave_sum(a);
   if ((tid & 63) == 0) ws[tid >> 6] = a;
   __syncthreads();
   if (tid == 0) {

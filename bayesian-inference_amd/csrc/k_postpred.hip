@@ -33,6 +33,7 @@
 #include "internal.h"
 #include "rows_dev.h"
 #include "sampler_internal.h"
+#include "wave_dev.h"
 
 namespace gpemu {
 
@@ -232,12 +233,6 @@ static int select_check(int64_t R, int64_t S, int64_t n_ranks, const int64_t *ra
 }
 
 // ---- posterior predictive ------------------------------------------------------------------------------------------
-static __device__ __forceinline__ double pp_wave_sum(double s) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off, 64);
-  return s;
-}
-
 // workgroup (256 samples, PP_FT features): W[(f - f0) ldw + s] = central value of feature f for sample s
 __global__ __launch_bounds__(256) void pp_project_kernel(const double *__restrict__ M, int64_t S, int k,
                                                          const double *__restrict__ comp,
@@ -282,7 +277,7 @@ __global__ __launch_bounds__(256) void pp_rowsum_kernel(const double *__restrict
       acc += centre ? (v - mu) * (v - mu) : v;
     }
   }
-  acc = pp_wave_sum(acc);
+  acc = wave_sum(acc);
   if ((tid & 63) == 0) ws[tid >> 6] = acc;
   __syncthreads();
   if (tid == 0) part[row * nchunk + c] = ((ws[0] + ws[1]) + ws[2]) + ws[3];

@@ -11,7 +11,8 @@
 //     T_o = L^-1 D^1/2 W_o,   c_o = W_o^T m + w0_o - T_o^T y_o,   Z_o = Q_o - T_o^T T_o.
 //
 // One workgroup per proposal, four waves; wave w takes the (group, block) tasks w, w + 4, ... in turn (lane = PC index,
-// as loglik_dev.h) and refactors the block's M_o in LDS, adding its c_o and Z_o to accumulators of its own.  After one
+// as loglik_dev.h) and refactors the block's M_o in LDS with the likelihood's own pieces (loglik_dev.h: lowrank_fill_lds,
+// wave_cholesky_lds), adding its c_o and Z_o to accumulators of its own.  After one
 // barrier wave 0 adds the four waves' accumulators in wave order (the same bits on every run), factors K (lane = row)
 // and finishes the stretch move of the proposal's walker (loglik_dev.h: finish_walker).  No workgroup waits for another.
 #include <algorithm>
@@ -34,38 +35,6 @@ struct SrcGroups {
   int first[SC_GROUPS_MAX + 1];       // task index of group g's block 0
 };
 
-__device__ __forceinline__ void wave_sync_lds() {
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-}
-
-__device__ __forceinline__ double wave_sum(double v) {
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
-
-// in-place Cholesky of the n x n matrix in LDS (leading dimension ldm; lane = row, n <= 64): the arithmetic of
-// walker_loglik_lowrank_lds.  Leaves L (lower triangle, diagonal included); returns log L_lane,lane on lanes < n.
-__device__ __forceinline__ double wave_cholesky_lds(double *M, int n, int ldm, int lane) {
-  double logdiag = 0.0;
-  for (int j = 0; j < n; ++j) {
-    const double piv = sqrt(M[j * ldm + j]);
-    __builtin_amdgcn_wave_barrier();
-    if (lane == j) {
-      M[j * ldm + j] = piv;
-      logdiag = log(piv);
-    }
-    if (lane > j && lane < n) M[lane * ldm + j] = M[lane * ldm + j] / piv;
-    wave_sync_lds();
-    if (lane > j && lane < n) {
-      const double lij = M[lane * ldm + j];
-      for (int c = j + 1; c <= lane; ++c) M[lane * ldm + c] -= lij * M[c * ldm + j];
-    }
-    wave_sync_lds();
-  }
-  return logdiag;
-}
-
 // c_o (lane s < S: its entry) and Z_o (added to Zacc) of observable block o of group gr for proposal b
 template <int KP>
 __device__ __forceinline__ void source_block_terms(const SrcGroup &gr, int o, int S, int64_t b, int lane, double *M,
@@ -75,13 +44,7 @@ __device__ __forceinline__ void source_block_terms(const SrcGroup &gr, int o, in
   walker_mean_sd<KP>(gr.mean_part, gr.vsq_part, gr.kdiag, nullptr, nullptr, b, gr.Bcap, k, gr.nchunk, gr.nrb, lane, mu, sd);
   const double *Go = gr.G + (int64_t)o * k * k;
   const double *Wo = gr.W + (int64_t)o * k * S;
-  double h = 0.0;
-  for (int q = 0; q < k; ++q) {
-    const double gq = (lane < k) ? Go[q * k + lane] : 0.0;
-    h = fma(gq, __shfl(mu, q), h);
-    const double sq = __shfl(sd, q);
-    if (lane < k) M[lane * ldm + q] = ((lane == q) ? 1.0 : 0.0) + sd * gq * sq;
-  }
+  double h = lowrank_fill_lds(Go, k, mu, sd, lane, M, ldm);
   h += (lane < k) ? gr.g0[(int64_t)o * k + lane] : 0.0;
   wave_sync_lds();
   (void)wave_cholesky_lds(M, k, ldm, lane);
@@ -146,11 +109,8 @@ __global__ __launch_bounds__(64 * SC_WAVES) void source_correction_kernel(const 
   if (aa.chain_per && aa.chain_data) ch = (aa.first + b) / aa.chain_per;
   // rows outside any group's box keep their -inf and get no term (every wave decides alike)
   bool inside = true;
-  for (int g = 0; g < sg.ng; ++g) {
-    bool in = true;
-    if (lane < d) in = (Xq[b * dpad_of(d) + lane] > sg.g[g].lo[lane]) && (Xq[b * dpad_of(d) + lane] < sg.g[g].hi[lane]);
-    inside = inside && __all(in);
-  }
+  for (int g = 0; g < sg.ng; ++g)
+    if (!inside_box(Xq, b, dpad_of(d), d, sg.g[g].lo, sg.g[g].hi, lane)) inside = false;
   for (int e = lane; e < S * S; e += 64) Zacc[e] = 0.0;
   double cacc = 0.0;                                         // lane s < S: entry s of this wave's sum of c_o
   wave_sync_lds();
@@ -188,11 +148,7 @@ __global__ __launch_bounds__(64 * SC_WAVES) void source_correction_kernel(const 
     }
     wave_sync_lds();
     const double logdiag = wave_cholesky_lds(K, S, S, lane);
-    double v = c;
-    for (int j = 0; j < S; ++j) {
-      const double zj = __shfl(v, j) / K[j * S + j];
-      v = (lane == j) ? zj : ((lane > j && lane < S) ? fma(-K[lane * S + j], zj, v) : v);
-    }
+    const double v = wave_forward_solve_lds(K, S, S, lane, c);
     const double vv = wave_sum((lane < S) ? v * v : 0.0);
     const double ld = wave_sum((lane < S) ? logdiag : 0.0);
     corr = 0.5 * vv - ld;

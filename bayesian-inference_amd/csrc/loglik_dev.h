@@ -1,11 +1,26 @@
-// Per-walker device functions of the low-rank likelihood shared by loglik_lowrank_kernel (k_loglik.hip) and the
-// fused sampler front kernel (k_front.hip).
+// Per-walker device functions of the low-rank likelihood: the one copy of the per-observable block term, in its register
+// form (k <= 32: lowrank_block_term) and its LDS form (k <= 64: lowrank_block_term_lds), with what its callers share
+// around it -- the likelihood kernels (k_loglik.hip), the fused sampler front kernel (k_front.hip), the source correction
+// (k_srccorr.hip), the gradient (k_grad.hip) and the per-observable terms of PSIS-LOO (k_loo.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include "internal.h"
+#include "wave_dev.h"
 
 namespace gpemu {
+
+// the strict box prior of row `row` of X (row stride `stride`), lane = parameter: whether lo < x < hi in every one of
+// the d parameters, the same answer in every lane.  A NaN fails both comparisons: outside.
+__device__ __forceinline__ bool inside_box(const double *__restrict__ X, int64_t row, int stride, int d,
+                                           const double *__restrict__ lo, const double *__restrict__ hi, int lane) {
+  bool in = true;
+  if (lane < d) {
+    const double x = X[row * stride + lane];
+    in = (x > lo[lane]) && (x < hi[lane]);
+  }
+  return __all(in);
+}
 
 // ---- per-walker evaluation --------------------------------------------------------------------
 // One wave per walker, lane = PC index p (k <= KMAX <= 64), 4 walkers per workgroup.  Row p of the
@@ -117,19 +132,54 @@ __device__ __forceinline__ double sum_first_lanes(double v) {
   return s;
 }
 
+// The register form's template argument from the runtime k (k <= 32): fn(std::integral_constant<int, KM>{}) for the
+// least KM of 4, 8, ... 32 with k <= KM.  The block term's value does not depend on KM (below), only its cost does.
+// More than 32 PCs take the LDS form: the caller's branch, not this one's.
+template <int KM = 4, class Fn>
+__host__ __device__ __forceinline__ auto with_kmax(int k, Fn &&fn) {
+  if constexpr (KM < 32) {
+    if (k > KM) return with_kmax<KM + 4>(k, fn);
+  }
+  return fn(std::integral_constant<int, KM>{});
+}
+
+// The constants of one observable block (row `lane` of G_o, entry `lane` of g0_o, q0_o, logdet A_o) requested ahead of
+// the GP partial sums, whose latency then covers theirs: call prefetch_block BEFORE walker_mean_sd.  The row is part of it
+// where the registers allow (PRE: KMAX <= 16; beyond, the prefetched row would cost 2 KMAX registers more and the block
+// loads its row like the others).
+template <int KMAX>
+struct BlockPre {
+  static constexpr bool PRE = KMAX <= 16;
+  double g[PRE ? KMAX : 1];
+  double gl, sc0, sc1;
+};
+// G, g0, scal: the block's own (already offset to block o)
+template <int KMAX>
+__device__ __forceinline__ BlockPre<KMAX> prefetch_block(const double *__restrict__ G, const double *__restrict__ g0,
+                                                         const double *__restrict__ scal, int k, int lane) {
+  BlockPre<KMAX> pre{};
+  if (BlockPre<KMAX>::PRE) {
+#pragma unroll
+    for (int q = 0; q < KMAX; ++q) pre.g[q] = (q < k && lane < k) ? G[q * k + lane] : 0.0;
+  }
+  pre.gl = (lane < k) ? g0[lane] : 0.0;
+  pre.sc0 = scal[0];
+  pre.sc1 = scal[1];
+  return pre;
+}
+
 // Low-rank log-likelihood of one walker held by one wave (lane = PC index; see k_loglik.hip for the algebra):
-// `mu`, `sd` are this lane's predictive mean and standard deviation; `gpre`, `gl_pre`, `sc0_pre`, `sc1_pre` the first
-// observable block's constants, requested by the caller ahead of the GP partial sums (PRE; without it `gpre` is not
-// read and the first block loads its row like the others: KMAX > 16, where the prefetched row would cost 2 KMAX
-// registers more).  k <= KMAX <= 32; the k x k matrix M = I + D^1/2 G D^1/2 is padded to KMAX x KMAX with the identity
+// `mu`, `sd` are this lane's predictive mean and standard deviation; `pre` the first observable block's constants
+// (prefetch_block).  k <= KMAX <= 32; the k x k matrix M = I + D^1/2 G D^1/2 is padded to KMAX x KMAX with the identity
 // so the factorisation is branch-free, row `lane` lives in registers, every cross-lane operand is a v_readlane of a
 // compile-time lane.  The padding adds exact zeros and pivots of exactly 1: the value does not depend on KMAX.
 // -inf outside the box.
 // the term of observable block o (see walker_loglik_lowrank below, which adds the blocks' terms in turn)
-template <int KMAX, bool PRE = true>
-__device__ __forceinline__ double lowrank_block_term(int o, double mu, double sd, const double *gpre, double gl_pre, double sc0_pre,
-                                                     double sc1_pre, const double *__restrict__ G, const double *__restrict__ g0,
+template <int KMAX>
+__device__ __forceinline__ double lowrank_block_term(int o, double mu, double sd, const BlockPre<KMAX> &pre,
+                                                     const double *__restrict__ G, const double *__restrict__ g0,
                                                      const double *__restrict__ scal, int k, int lane) {
+  constexpr bool PRE = BlockPre<KMAX>::PRE;
   const double *Go = G + (int64_t)o * k * k;
   // row `lane` of G_o (symmetric: read column-wise so that the wave's loads coalesce)
   double row[KMAX];
@@ -144,13 +194,13 @@ __device__ __forceinline__ double lowrank_block_term(int o, double mu, double sd
 #pragma unroll
   for (int q = 0; q < KMAX; ++q) {
     double gq;
-    if (PRE) gq = (o == 0) ? gpre[q] : ((q < k && lane < k) ? Go[q * k + lane] : 0.0);
+    if (PRE) gq = (o == 0) ? pre.g[q] : ((q < k && lane < k) ? Go[q * k + lane] : 0.0);
     else gq = (q < k && lane < k) ? Gl[((q < k) ? q : k - 1) * k] : 0.0;
     h = fma(gq, readlane_f64(mu, q), h);
     row[q] = ((lane_q == q) ? 1.0 : 0.0) + sd * gq * readlane_f64(sd, q);
   }
-  const double gl = (o == 0) ? gl_pre : ((lane < k) ? g0[(int64_t)o * k + lane] : 0.0);
-  const double sc0 = (o == 0) ? sc0_pre : scal[2 * o], sc1 = (o == 0) ? sc1_pre : scal[2 * o + 1];
+  const double gl = (o == 0) ? pre.gl : ((lane < k) ? g0[(int64_t)o * k + lane] : 0.0);
+  const double sc0 = (o == 0) ? pre.sc0 : scal[2 * o], sc1 = (o == 0) ? pre.sc1 : scal[2 * o + 1];
   h += gl;
   const double quadA = sum_first_lanes<KMAX>((lane < k) ? mu * (h + gl) : 0.0) + sc0;
   // right-looking Cholesky; y = L_M^-1 (sd o h) by forward substitution alongside.  One reciprocal
@@ -179,23 +229,96 @@ __device__ __forceinline__ double lowrank_block_term(int o, double mu, double sd
   return -0.5 * (quadA - ww) - 0.5 * (sc1 + 2.0 * ldsum);
 }
 
-template <int KMAX, bool PRE = true>
-__device__ __forceinline__ double walker_loglik_lowrank(bool inside, double mu, double sd, const double *gpre,
-                                                        double gl_pre, double sc0_pre, double sc1_pre,
+template <int KMAX>
+__device__ __forceinline__ double walker_loglik_lowrank(bool inside, double mu, double sd, const BlockPre<KMAX> &pre,
                                                         const double *__restrict__ G, const double *__restrict__ g0,
                                                         const double *__restrict__ scal, int k, int nblk, int lane) {
   double total = -INFINITY;
   if (inside) {
     total = 0.0;
-    for (int o = 0; o < nblk; ++o)
-      total += lowrank_block_term<KMAX, PRE>(o, mu, sd, gpre, gl_pre, sc0_pre, sc1_pre, G, g0, scal, k, lane);
+    for (int o = 0; o < nblk; ++o) total += lowrank_block_term<KMAX>(o, mu, sd, pre, G, g0, scal, k, lane);
   }
   return total;
 }
 
-// General k (33..64), the k x k matrix of the walker in LDS (`M`, leading dimension `ldm` >= k + 1, private to the
-// wave): the arithmetic of loglik_lowrank_lds_kernel, shared with the fused front kernel so that a sharded run
-// reproduces the single-GPU chain bit for bit.
+// ---- the LDS form: any k <= 64, the k x k matrix of the walker in LDS (`M`, leading dimension `ldm`, private to the
+// wave; lane = row).  One body for loglik_lowrank_lds_kernel, the fused front kernel (so that a sharded run reproduces
+// the single-GPU chain bit for bit), the gradient, the source correction and the LOO terms.
+
+// M = I + D^1/2 G_o D^1/2, row `lane`; returns (G_o mu)_lane.  WITH_Y: also Y[q k + lane] = sd_q G_o[q][lane] (k_grad.hip)
+template <bool WITH_Y = false>
+__device__ __forceinline__ double lowrank_fill_lds(const double *__restrict__ Go, int k, double mu, double sd, int lane,
+                                                   double *M, int ldm, double *Y = nullptr) {
+  double h = 0.0;
+  for (int q = 0; q < k; ++q) {
+    const double gq = (lane < k) ? Go[q * k + lane] : 0.0;       // G symmetric: column-wise, coalesced
+    h = fma(gq, __shfl(mu, q), h);
+    const double sq = __shfl(sd, q);
+    if (lane < k) {
+      M[lane * ldm + q] = ((lane == q) ? 1.0 : 0.0) + sd * gq * sq;
+      if (WITH_Y) Y[q * k + lane] = sq * gq;
+    }
+  }
+  return h;
+}
+
+// in-place Cholesky of the n x n matrix in LDS (n <= 64).  Leaves L (lower triangle, diagonal included); returns
+// log L_lane,lane on lanes < n, 0 on the others.
+__device__ __forceinline__ double wave_cholesky_lds(double *M, int n, int ldm, int lane) {
+  double logdiag = 0.0;
+  for (int j = 0; j < n; ++j) {
+    const double piv = sqrt(M[j * ldm + j]);
+    __builtin_amdgcn_wave_barrier();
+    if (lane == j) {
+      M[j * ldm + j] = piv;
+      logdiag = log(piv);
+    }
+    if (lane > j && lane < n) M[lane * ldm + j] = M[lane * ldm + j] / piv;
+    wave_sync_lds();
+    if (lane > j && lane < n) {
+      const double lij = M[lane * ldm + j];
+      for (int c = j + 1; c <= lane; ++c) M[lane * ldm + c] -= lij * M[c * ldm + j];
+    }
+    wave_sync_lds();
+  }
+  return logdiag;
+}
+
+// L^-1 y by forward substitution along the lanes (lane = row; L as wave_cholesky_lds leaves it); lanes >= n keep theirs
+__device__ __forceinline__ double wave_forward_solve_lds(const double *M, int n, int ldm, int lane, double y) {
+  for (int j = 0; j < n; ++j) {
+    const double zj = __shfl(y, j) / M[j * ldm + j];
+    if (lane == j) y = zj;
+    if (lane > j && lane < n) y = fma(-M[lane * ldm + j], zj, y);
+  }
+  return y;
+}
+
+// the term of one observable block (Go, g0o, scalo: the block's own constants).  Leaves L in M; h = (G_o mu + g0_o)_lane
+// and y = L^-1 D^1/2 h go back to a caller with further solves (k_grad.hip).  The caller puts a wave_sync_lds() between
+// this and the next write to M.
+template <bool WITH_Y = false>
+__device__ __forceinline__ double lowrank_block_term_lds(const double *__restrict__ Go, const double *__restrict__ g0o,
+                                                         const double *__restrict__ scalo, int k, double mu, double sd,
+                                                         int lane, double *M, int ldm, double &h, double &y,
+                                                         double *Y = nullptr) {
+  const double gl = (lane < k) ? g0o[lane] : 0.0;
+  h = lowrank_fill_lds<WITH_Y>(Go, k, mu, sd, lane, M, ldm, Y) + gl;
+  const double quadA = wave_sum((lane < k) ? mu * (h + gl) : 0.0) + scalo[0];
+  wave_sync_lds();
+  const double logdiag = wave_cholesky_lds(M, k, ldm, lane);
+  y = wave_forward_solve_lds(M, k, ldm, lane, (lane < k) ? sd * h : 0.0);
+  const double ww = wave_sum((lane < k) ? y * y : 0.0);
+  const double ldsum = wave_sum(logdiag);
+  return -0.5 * (quadA - ww) - 0.5 * (scalo[1] + 2.0 * ldsum);
+}
+__device__ __forceinline__ double lowrank_block_term_lds(const double *__restrict__ Go, const double *__restrict__ g0o,
+                                                         const double *__restrict__ scalo, int k, double mu, double sd,
+                                                         int lane, double *M, int ldm) {
+  double h, y;
+  return lowrank_block_term_lds(Go, g0o, scalo, k, mu, sd, lane, M, ldm, h, y);
+}
+
 __device__ __forceinline__ double walker_loglik_lowrank_lds(bool inside, double mu, double sd,
                                                             const double *__restrict__ G, const double *__restrict__ g0,
                                                             const double *__restrict__ scal, int k, int nblk, int lane,
@@ -204,53 +327,8 @@ __device__ __forceinline__ double walker_loglik_lowrank_lds(bool inside, double 
   if (inside) {
     total = 0.0;
     for (int o = 0; o < nblk; ++o) {
-      const double *Go = G + (int64_t)o * k * k;
-      double h = 0.0, gl = (lane < k) ? g0[(int64_t)o * k + lane] : 0.0;
-      for (int q = 0; q < k; ++q) {
-        double gq = (lane < k) ? Go[q * k + lane] : 0.0;
-        h = fma(gq, __shfl(mu, q), h);
-        double sq = __shfl(sd, q);
-        if (lane < k) M[lane * ldm + q] = ((lane == q) ? 1.0 : 0.0) + sd * gq * sq;
-      }
-      h += gl;
-      double t = (lane < k) ? mu * (h + gl) : 0.0;
-      for (int off = 32; off > 0; off >>= 1) t += __shfl_xor(t, off);
-      const double quadA = t + scal[2 * o];
-      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      double logdiag = 0.0;
-      for (int j = 0; j < k; ++j) {
-        double piv = sqrt(M[j * ldm + j]);
-        __builtin_amdgcn_wave_barrier();
-        if (lane == j) {
-          M[j * ldm + j] = piv;
-          logdiag = log(piv);
-        }
-        if (lane > j && lane < k) M[lane * ldm + j] = M[lane * ldm + j] / piv;
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        if (lane > j && lane < k) {
-          double lij = M[lane * ldm + j];
-          for (int c = j + 1; c <= lane; ++c) M[lane * ldm + c] -= lij * M[c * ldm + j];
-        }
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-      }
-      double y = (lane < k) ? sd * h : 0.0;
-      for (int j = 0; j < k; ++j) {
-        double zj = __shfl(y, j) / M[j * ldm + j];
-        if (lane == j) y = zj;
-        if (lane > j && lane < k) y = fma(-M[lane * ldm + j], zj, y);
-      }
-      double ww = (lane < k) ? y * y : 0.0;
-      double ldsum = logdiag;
-      for (int off = 32; off > 0; off >>= 1) {
-        ww += __shfl_xor(ww, off);
-        ldsum += __shfl_xor(ldsum, off);
-      }
-      total += -0.5 * (quadA - ww) - 0.5 * (scal[2 * o + 1] + 2.0 * ldsum);
-      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-      __builtin_amdgcn_wave_barrier();
+      total += lowrank_block_term_lds(G + (int64_t)o * k * k, g0 + (int64_t)o * k, scal + 2 * o, k, mu, sd, lane, M, ldm);
+      wave_sync_lds();
     }
   }
   return total;

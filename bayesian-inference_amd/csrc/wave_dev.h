@@ -1,0 +1,21 @@
+// The two wave-level primitives every kernel family shares (one wave = 64 lanes).
+#pragma once
+#include <hip/hip_runtime.h>
+
+namespace gpemu {
+
+// the sum of `v` over the wave's 64 lanes, in every lane: the xor butterfly 32, 16, ... 1 (one fixed tree: the bits
+// depend on the values alone)
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
+  return v;
+}
+
+// the wave's LDS writes so far are visible to its other lanes' reads that follow
+__device__ __forceinline__ void wave_sync_lds() {
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+}
+
+}  // namespace gpemu
