@@ -207,6 +207,8 @@ def _run_closure_batch(config, indices):
         _add_marginals(config, part, lambda c=c, **kw: sampler.marginals(chain=c, **kw),
                        label=f'closure chain {indices[c]}')
         _add_loo(config, part, lambda c=c, **kw: sampler.loo(chain=c, **kw), label=f'closure chain {indices[c]}')
+        _add_information_gain(config, part, lambda c=c, **kw: sampler.information_gain(chain=c, **kw),
+                              label=f'closure chain {indices[c]}')
         diags.append(part)
     sampler.close()
 
@@ -336,6 +338,7 @@ def run_mcmc(config, closure_index=-1):
     _add_diagnostics(config, results, sampler.get_diagnostics)
     _add_marginals(config, results, sampler.get_marginals)
     _add_loo(config, results, lambda **kw: sampler.get_loo(models=log_posterior.device_models(n_div=1.0), **kw))
+    _add_information_gain(config, results, sampler.get_information_gain)
     if closure_index >= 0:
         validation_design = io.design_array_from_h5(config.output_dir, filename='observables.h5', validation_set=True)
         results['design_point'] = validation_design[closure_index]
@@ -463,6 +466,8 @@ def _run_tempered(config, closure_index):
     _add_diagnostics(config, diag, lambda: sampler.diagnostics(temp=0), label='production chain (beta = 1)')
     _add_marginals(config, diag, lambda **kw: sampler.marginals(temp=0, **kw), label='production chain (beta = 1)')
     _add_loo(config, diag, lambda **kw: sampler.loo(temp=0, **kw), label='production chain (beta = 1)')
+    _add_information_gain(config, diag, lambda **kw: sampler.information_gain(temp=0, **kw),
+                          label='production chain (beta = 1)')
     mean_ll = sampler.mean_log_likelihood()
     log_z, dlog_z = sampler.log_evidence_estimate()
     swap_frac = sampler.tswap_acceptance_fraction
@@ -573,6 +578,7 @@ def _run_hmc(config, closure_index):
     _add_diagnostics(config, diag, sampler.diagnostics)
     _add_marginals(config, diag, sampler.marginals)
     _add_loo(config, diag, sampler.loo)
+    _add_information_gain(config, diag, sampler.information_gain)
     step_size, inverse_metric, divergences = sampler.step_size, sampler.inverse_metric, sampler.divergences
     sampler.close()
 
@@ -881,6 +887,83 @@ def loo(config, closure_index=-1, discard=0, thin=1):
     return _loo_entries(out, labels, rows)
 
 
+def information_gain_settings(mc):
+    """``(on, k, max_points)`` from the ``parameters.mcmc`` mapping: ``information_gain`` (true or false, default off: how
+    many nats the data taught about every parameter, every pair and all of them jointly), ``information_gain_k`` (the
+    neighbour the estimator uses, an integer in [1, 16], default 4) and ``information_gain_max_points`` (the most evenly
+    spaced rows of the chain it is taken over, an integer >= 2, default 65536).  DESIGN.md §4.35."""
+    on = mc.get('information_gain', False)
+    if not isinstance(on, (bool, np.bool_)):
+        raise ValueError(f"parameters.mcmc.information_gain must be true or false, got {on!r}")
+    k = mc.get('information_gain_k', 4)
+    if not isinstance(k, (int, np.integer)) or isinstance(k, (bool, np.bool_)) or not 1 <= k <= 16:
+        raise ValueError(f"parameters.mcmc.information_gain_k must be an integer in [1, 16], got {k!r}")
+    n = mc.get('information_gain_max_points', 65536)
+    if not isinstance(n, (int, np.integer)) or isinstance(n, (bool, np.bool_)) or not 2 <= n < 2 ** 31:
+        raise ValueError(f"parameters.mcmc.information_gain_max_points must be an integer in [2, 2^31), got {n!r}")
+    return bool(on), int(k), int(n)
+
+
+INFORMATION_GAIN_KEYS = ('masks', 'dims', 'nats', 'bits', 'se', 'n_used', 'copies', 'n_points', 'k', 'joint',
+                         'per_parameter', 'pairs', 'per_pair')
+
+
+def _information_gain_kwargs(config):
+    """The arguments of ``DeviceSampler.information_gain`` / ``gpemu.information.information_gain`` from the
+    configuration: the prior box of the parameterization and the ``information_gain_*`` settings.  The drop-in allows
+    copies -- an unthinned ensemble chain always holds them -- and reports their number instead."""
+    box = config.analysis_config['parameterization'][config.parameterization]
+    return dict(lower=np.asarray(box['min'], dtype=np.float64), upper=np.asarray(box['max'], dtype=np.float64),
+                k=config.information_gain_k, max_points=config.information_gain_max_points, allow_copies=True)
+
+
+def _information_gain_entries(out):
+    """the ``information_gain_*`` entries of mcmc.h5 from a result: the subsets as bit masks over the parameters"""
+    ent = {'masks': np.array([sum(1 << j for j in s) for s in out['subsets']], dtype=np.int64)}
+    for key in ('dims', 'n_used', 'copies', 'pairs'):
+        ent[key] = np.asarray(out[key], dtype=np.int64)
+    for key in ('nats', 'bits', 'se', 'per_parameter', 'per_pair'):
+        ent[key] = np.asarray(out[key], dtype=np.float64)
+    ent['n_points'], ent['k'] = np.int64(out['n_points']), np.int64(out['k'])
+    ent['joint'] = np.float64(out['joint'])
+    return {f'information_gain_{key}': ent[key] for key in INFORMATION_GAIN_KEYS}
+
+
+def _add_information_gain(config, results, compute, label='production chain'):
+    """With ``parameters.mcmc.information_gain``: the ``information_gain_*`` entries of ``compute(**kwargs)`` (a
+    sampler's ``information_gain`` on the chain where it lies) into the results that go to mcmc.h5, one log line, and a
+    warning where more than a tenth of the rows are copies (the estimate then wants a thinned chain)."""
+    if not getattr(config, 'information_gain', False):
+        return
+    try:
+        out = compute(**_information_gain_kwargs(config))
+        entries = _information_gain_entries(out)
+    except Exception as err:         # the chain is worth more than the number: it is written either way
+        logger.warning(f'parameters.mcmc.information_gain: not computed ({err!r}); mcmc.h5 is written without the '
+                       'information_gain_* entries')
+        return
+    results.update(entries)
+    top = int(np.nanargmax(out['per_parameter'])) if np.any(np.isfinite(out['per_parameter'])) else 0
+    logger.info(f"Information gain of the {label}: joint {out['joint']:.3f} nats ({out['joint'] / np.log(2.0):.3f} bits) "
+                f"over {out['n_points']} rows, k = {out['k']}; most about parameter {top} "
+                f"({out['per_parameter'][top]:.3f} nats)")
+    if np.any(np.asarray(out['copies']) > 0.1 * out['n_points']):
+        logger.warning(f"information gain: up to {int(np.max(out['copies']))} copies among {out['n_points']} rows: thin "
+                       "the chain by its autocorrelation time for a reliable estimate")
+
+
+def information_gain(config, closure_index=-1, discard=0, thin=1):
+    """The ``information_gain_*`` entries (``gpemu.information.information_gain``) of the chain stored in mcmc.h5 (of
+    closure chain ``closure_index``, if >= 0), steps ``[discard::thin]``, all walkers, with the configuration's box and
+    ``information_gain_*`` settings."""
+    cfg, chain = _stored_chain(config, closure_index, discard, thin)
+    from gpemu import information as _info
+    kw = _information_gain_kwargs(cfg)
+    lower, upper = kw.pop('lower'), kw.pop('upper')
+    return _information_gain_entries(_info.information_gain(
+        np.ascontiguousarray(chain.reshape(-1, chain.shape[-1])), lower, upper, **kw))
+
+
 def propose_design_points(config, closure_index=-1, discard=0, thin=None, n_points=8, n_reference=4096,
                           n_candidates=2048, candidates=None, seed=0, feature_weights=None, **design_kwargs):
     """``emulation.propose_design_points`` with the chain stored in mcmc.h5 (of closure chain ``closure_index``, if
@@ -1128,6 +1211,9 @@ class MCMCConfig:
         # per-observable PSIS-LOO / WAIC and the observable-influence table of the production chain (optional, default
         # off): loo_* in mcmc.h5, none without the key
         self.loo, self.loo_leave_out = loo_settings(mc)
+        # how many nats the data taught about each parameter, each pair and all of them jointly (optional, default off):
+        # information_gain_* in mcmc.h5, none without the key
+        self.information_gain, self.information_gain_k, self.information_gain_max_points = information_gain_settings(mc)
 
         # <output_dir>/<analysis>_<parameterization>[/closure/results/<index>]/{mcmc.h5, mcmc_sampler.pkl}
         self.output_dir = os.path.join(top['output_dir'], f'{analysis_name}_{parameterization}')

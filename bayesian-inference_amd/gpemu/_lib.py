@@ -209,6 +209,15 @@ _SIGNATURES = {
     "gpemu_design_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(c_i64)]),
     "gpemu_design_destroy": (C.c_int, [C.c_void_p]),
     "gpemu_design_path_counts": (C.c_int, [C.POINTER(c_i64), c_i64]),
+    "gpemu_unit_rows_dev": (C.c_int, [C.c_int, C.c_void_p, c_i64, c_i64, c_i64, C.c_int, C.c_void_p, C.c_void_p, c_i64,
+                                      C.c_void_p, C.POINTER(c_i64), C.c_void_p]),
+    "gpemu_knn_dist": (C.c_int, [C.c_int, c_i64, c_i64, C.c_int, C.c_void_p, C.c_void_p, c_i64, C.c_void_p, C.c_int,
+                                 C.c_int, c_i64, C.c_void_p, C.c_void_p]),
+    "gpemu_knn_dist_dev": (C.c_int, [C.c_int, c_i64, c_i64, C.c_int, C.c_void_p, C.c_void_p, c_i64, C.c_void_p, C.c_int,
+                                     C.c_int, c_i64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gpemu_knn_logsum_dev": (C.c_int, [C.c_int, c_i64, c_i64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p]),
+    "gpemu_knn_path_counts": (C.c_int, [C.POINTER(c_i64), c_i64]),
 }
 
 

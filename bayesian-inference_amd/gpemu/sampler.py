@@ -410,6 +410,48 @@ class DeviceSampler:
         return LO.from_terms(self.device, T, labels, (src, n_blocks, nw, stride), self.d, leave_out, shifts, r_eff,
                              workspace_bytes, baseline=(lambda: self.chain_moments(discard)) if whole else None)
 
+    def _box_or_prior(self, lower, upper):
+        """``(lower, upper)``, each defaulting to the prior box of the sampler's models."""
+        if lower is None or upper is None:
+            box = getattr(self.models[0], "prior_box", None)
+            if box is None:
+                raise ValueError("no prior box is known (likelihood_setup has not been called): pass lower and upper")
+            lower, upper = (box[0] if lower is None else lower), (box[1] if upper is None else upper)
+        return lower, upper
+
+    def information_gain(self, lower=None, upper=None, k=4, discard=0, thin=1, chain=None, max_points=65536, subsets=None,
+                         allow_copies=False, workspace_bytes=0):
+        """How many nats the data taught about every parameter, every pair and all of them jointly
+        (``gpemu.information.information_gain``): ``KL(posterior || prior)`` of the stored chain
+        ``get_chain()[discard::thin].reshape(-1, d)`` under the uniform prior on the box (default: the prior box of the
+        sampler's models), from at most ``max_points`` evenly spaced rows, read in place on the device, thinned or
+        stacked.  An ensemble chain repeats states (a rejected move keeps the walker where it was): thin it by its
+        autocorrelation time, or pass ``allow_copies``.  Stacked samplers take ``chain=<index>``."""
+        from . import information as IG
+        src, n_blocks, nw, stride, _ = self._stored_view(discard, thin, chain)
+        lower, upper = self._box_or_prior(lower, upper)
+        return IG.gain_of_view(self.device, (src, n_blocks, nw, stride), self.d, lower, upper, k=k, subsets=subsets,
+                               max_points=max_points, allow_copies=allow_copies, workspace_bytes=workspace_bytes)
+
+    def kl_divergence(self, other, lower=None, upper=None, k=4, discard=0, thin=1, chain=None, max_points=65536,
+                      subsets=None, allow_copies=False, other_chain=None, workspace_bytes=0):
+        """``D(this chain || other)`` in nats (``gpemu.information.kl_divergence``) for every subset of
+        the parameters, in the unit coordinates of the box (default: the prior box of this sampler's models).  ``other``:
+        a sampler on the same device -- its stored chain ``[discard::thin]``, chain ``other_chain`` (default ``chain``) of
+        a stacked one, read in place -- or rows ``(m, d)`` / ``(steps, walkers, d)`` as a host array or a device tensor."""
+        from . import information as IG
+        src, n_blocks, nw, stride, _ = self._stored_view(discard, thin, chain)
+        lower, upper = self._box_or_prior(lower, upper)
+        if isinstance(other, DeviceSampler):
+            if other.d != self.d or other.device != self.device:
+                raise ValueError("the two samplers differ in parameters or device")
+            oc = other_chain if other_chain is not None else (chain if other.n_chains > 1 else None)
+            osrc, ob, onw, ostride, _ = other._stored_view(discard, thin, oc)
+            other = (osrc, ob, onw, ostride)
+        return IG.divergence_of_views(self.device, (src, n_blocks, nw, stride), other, self.d, lower, upper, k=k,
+                                      subsets=subsets, max_points=max_points, allow_copies=allow_copies,
+                                      workspace_bytes=workspace_bytes)
+
     def propose_design(self, n_points, candidates=None, n_candidates=2048, n_reference=4096, discard=0, thin=None,
                        chain=None, seed=0, models=None, **kw):
         """Where to run the model next, given this posterior: ``gpemu.design.Design.select(n_points)`` (DESIGN.md
@@ -904,6 +946,17 @@ class TemperedSampler(DeviceSampler):
         """``DeviceSampler.loo`` of one rung (default: rung 0, the posterior)."""
         return DeviceSampler.loo(self, chain=int(temp), **kw)
 
+    def information_gain(self, temp=0, **kw):
+        """``DeviceSampler.information_gain`` of one rung (default: rung 0, the posterior)."""
+        return DeviceSampler.information_gain(self, chain=int(temp), **kw)
+
+    def kl_divergence(self, other, temp=0, other_temp=0, **kw):
+        """``DeviceSampler.kl_divergence`` of one rung (default: rung 0, the posterior) against ``other``: rung
+        ``other_temp`` of another tempered sampler (or of this one: how far a hotter rung is from the posterior), the
+        chain of an untempered sampler, or rows."""
+        oc = int(other_temp) if isinstance(other, TemperedSampler) else None
+        return DeviceSampler.kl_divergence(self, other, chain=int(temp), other_chain=oc, **kw)
+
     def propose_design(self, n_points, temp=0, **kw):
         """``DeviceSampler.propose_design`` of one rung (default: rung 0, the posterior)."""
         return DeviceSampler.propose_design(self, n_points, chain=int(temp), **kw)
@@ -1350,6 +1403,21 @@ class EnsembleSampler:
         if models is None:
             raise ValueError("the chain is on the host: pass the device models")
         return loo.chain_loo(models, self.get_chain(discard=discard, thin=thin, flat=True), **kw)
+
+    def get_information_gain(self, discard=0, thin=1, **kw):
+        """``gpemu.information.information_gain`` of ``get_chain(discard=discard, thin=thin, flat=True)`` (``lower``,
+        ``upper``, ``k``, ``max_points``, ``subsets``, ``allow_copies``): in place while the chain still lives on the
+        device (the box defaults to the prior box), from the host copy otherwise (``lower`` and ``upper`` are then
+        required)."""
+        discard, thin = int(discard), int(thin)
+        if self._impl is not None and getattr(self, "_device", False) and not self.__dict__.get("_frozen"):
+            return self._impl.information_gain(discard=discard + thin - 1, thin=thin, **kw)
+        from . import information
+        if kw.get("lower") is None or kw.get("upper") is None:
+            raise ValueError("the chain is on the host: pass lower and upper")
+        lower, upper = kw.pop("lower"), kw.pop("upper")
+        return information.information_gain(np.ascontiguousarray(self.get_chain(discard=discard, thin=thin, flat=True)),
+                                            lower, upper, **kw)
 
     # -- pickling (ref: mcmc.py:131-132 pickles the sampler) --------------------------------------
     def __getstate__(self):

@@ -979,6 +979,68 @@ enum gpemu_design_path {
 /* out[0 .. min(n, GPEMU_DESIGN_PATH_COUNT)) = the counters; returns GPEMU_DESIGN_PATH_COUNT (or GPEMU_ERR_ARG). */
 int gpemu_design_path_counts(int64_t *out, int64_t n);
 
+/* ---- information gain and KL divergence of chains by k-th nearest neighbours --------------------------
+ * How many nats the data taught about each parameter, each pair and all of them jointly, and how far apart two
+ * posteriors are -- the question the reference leaves open twice ("one could also plot some type of information gain
+ * metric, e.g. KL divergence"; ref: plot_qhat.py:116, plot_analyses.py:144).  Under the uniform prior on the box the
+ * gain is minus the differential entropy of u = (x - lower) / (upper - lower); the estimators (Kozachenko-Leonenko;
+ * Wang, Kulkarni, Verdu 2009; Perez-Cruz 2008) need the distance of every row to its k-th nearest neighbour.
+ *
+ * gpemu_unit_rows_dev: dU[i*d + j] = (x_j - lower[j]) * (1 / (upper[j] - lower[j])) of logical row floor(i*S / n),
+ * i < n <= S = n_blocks*block_rows < 2^31: two separately rounded operations, the bits of the same numpy expression.
+ * Logical row r is at dX + (r / block_rows)*block_stride + (r % block_rows)*d: block_stride counts ELEMENTS (a step of
+ * a chain may be padded to a length that is no multiple of d) and holds at least a block.  A row with a non-finite coordinate becomes a row of NaN -- the search passes it over -- and is
+ * counted in *n_skipped.  lower, upper, n_skipped: HOST.  Works on `stream` and waits for it.
+ *
+ * gpemu_knn_dist: queries UQ[nq*d], references UR[nr*d] (NULL: the queries themselves, nr = nq), n_subsets subsets of
+ * the d coordinates as 32-bit masks (bit j: coordinate j; HOST), 1 <= k <= 16:
+ *   r2[p*nq + i]    = the squared Euclidean distance of query i to its k-th nearest reference in the coordinates of
+ *                     subset p: acc = fma(diff, diff, acc) over the subset's coordinates in increasing order, from the
+ *                     differences (never |x|^2 + |y|^2 - 2 x.y, which cancels at neighbour distances);
+ *   zeros[p*nq + i] = the number of references at squared distance exactly 0.
+ * Zero-distance rule: a reference at squared distance exactly 0 in the subset is a copy of the query; it is counted in
+ * zeros and is NOT a neighbour.  In a self search that excludes the query itself (no index test), and it excludes the
+ * repeated states of an ensemble chain.  Fewer than k references that are no copies: r2 = +inf.  A reference with a
+ * non-finite coordinate in the subset is passed over; a query with one gets r2 = NaN, zeros = 0.
+ * One thread owns a query and keeps its k smallest distances sorted in registers; the references stream through LDS
+ * GPEMU_KNN_REF_TILE at a time; the grid is (256-query tiles, subsets, reference splits Z), and a second kernel merges
+ * the Z lists and adds the Z zero counts.  The k smallest of a set do not depend on its order: r2 and zeros are the
+ * same bits for every Z, every tile and every workspace_bytes.  splits = 0 chooses Z (so that a launch has some 2048
+ * workgroups, a split at least 64 references, Z <= 64); splits in [1, 64] forces it (for tests).  The Z partial lists
+ * ((8 k + 4) Z nq bytes per subset) go through workspace_bytes (0 = half of the free device memory) in batches of
+ * subsets; a chosen Z shrinks to what fits; if a forced Z does not fit for one subset: GPEMU_ERR_HIP.
+ * GPEMU_ERR_ARG before any launch: k outside [1, 16]; d outside [1, 16]; a mask that is 0 or has a bit >= d; nq or nr
+ * outside [1, 2^31); n_subsets outside [1, 2^20]; splits outside [0, 64]; workspace_bytes < 0; no references and
+ * nr != nq.  _dev reads dense device rows, writes the device arrays dr2 and dzeros, works on `stream`, waits for it.
+ *
+ * gpemu_knn_logsum_dev: per subset p of dr2[n_subsets*n] (and dzeros, or NULL), counts[3p ..] = n_used (rows whose
+ * distance is finite), n_short (+inf), copies (the sum of zeros); sums[2p ..] = the sum of v and of v^2 over the used
+ * rows, v = log r2.  With dnu2 (the same shape): v = log nu2 - log r2, and a row is used if both are finite, short if
+ * one is +inf.  A NaN distance passes the row over.  Blocks of 1024 rows and then the blocks, each in a fixed tree.
+ * counts (int64) and sums: HOST. */
+#define GPEMU_KNN_MAX_K 16
+#define GPEMU_KNN_REF_TILE 256
+int gpemu_unit_rows_dev(int device, const double *dX, int64_t n_blocks, int64_t block_rows, int64_t block_stride, int d,
+                        const double *lower, const double *upper, int64_t n, double *dU, int64_t *n_skipped, void *stream);
+int gpemu_knn_dist(int device, int64_t nq, int64_t nr, int d, const double *UQ, const double *UR, int64_t n_subsets,
+                   const uint32_t *masks, int k, int splits, int64_t workspace_bytes, double *r2, int32_t *zeros);
+int gpemu_knn_dist_dev(int device, int64_t nq, int64_t nr, int d, const double *dUQ, const double *dUR, int64_t n_subsets,
+                       const uint32_t *masks, int k, int splits, int64_t workspace_bytes, double *dr2, int32_t *dzeros,
+                       void *stream);
+int gpemu_knn_logsum_dev(int device, int64_t n_subsets, int64_t n, const double *dr2, const int32_t *dzeros,
+                         const double *dnu2, int64_t *counts, double *sums, void *stream);
+/* Which launches ran.  A set of its own: the other sets keep their sizes and indices. */
+enum gpemu_knn_path {
+  GPEMU_KNN_PATH_UNIT_ROWS = 0,   /* one launch of the unit-box kernel                                                 */
+  GPEMU_KNN_PATH_SEARCH,          /* one launch of the search kernel (a batch of subsets of one width)                 */
+  GPEMU_KNN_PATH_MERGE,           /* one launch of the kernel that merges the Z partial lists (Z > 1 only)             */
+  GPEMU_KNN_PATH_SUBSET_BATCH,    /* one batch of subsets through the partial-list workspace                           */
+  GPEMU_KNN_PATH_LOGSUM,          /* one gpemu_knn_logsum_dev call (the partial and the final kernel)                  */
+  GPEMU_KNN_PATH_COUNT
+};
+/* out[0 .. min(n, GPEMU_KNN_PATH_COUNT)) = the counters; returns GPEMU_KNN_PATH_COUNT (or GPEMU_ERR_ARG). */
+int gpemu_knn_path_counts(int64_t *out, int64_t n);
+
 /* ---- fit handle: test-only entry points ---------------------------------------------------------------------------
  * For the tests of the fit side only; nothing in the library's own flow calls them.
  * gpemu_fit_workspace: out[N*N] = problem z of the last evaluation (gpemu_fit_lml / _lml_batch / _factor) as the
