@@ -14,8 +14,8 @@
 #include <algorithm>
 
 #include "internal.h"
-#include "linalg_dev.h"
 #include "sampler_internal.h"
+#include "wg_dev.h"
 
 namespace gpemu {
 
@@ -97,16 +97,18 @@ __global__ __launch_bounds__(256) void acf_reduce_kernel(const double *__restric
   if (is_first && l == 0) acf0[s] = a;
 }
 
-// f[l][dd] = 1/nw sum over the block's nw walkers of acf[l][(w, dd)] / acf0[(w, dd)]; one workgroup per (l, dd)
+// f[l][dd] = 1/nw sum over the block's nw walkers of acf[l][(w, dd)] / acf0[(w, dd)]; one workgroup per (l, dd): thread
+// t adds the walkers t, t + 256, ..., then tree B (wg_dev.h)
 __global__ __launch_bounds__(256) void acf_walker_mean_kernel(const double *__restrict__ acf, const double *__restrict__ acf0,
                                                               int64_t S, int d, int nw, double *__restrict__ f) {
+  __shared__ double ws[4];
   const int l = blockIdx.x, dd = blockIdx.y;
   double a = 0.0;
   for (int w = threadIdx.x; w < nw; w += 256) {
     const int64_t s = (int64_t)w * d + dd;
     a += acf[(int64_t)l * S + s] / acf0[s];
   }
-  a = wg_sum(a);
+  a = wg_sum_b<4>(a, ws);
   if (threadIdx.x == 0) f[(int64_t)l * d + dd] = a / (double)nw;
 }
 

@@ -7,7 +7,7 @@
 // to the two GEMM operands V1' [N64 + picks][S64] and V2' [N64 + picks][M64] (k-major), which the handle keeps.
 //   V        kmat + launch_gemm, exactly as k_pcov.hip (pcov_dev.h), into the operands; the spare rows zero
 //   den0     column sums of squares of V in row order: c(s, s) (for IV_0) and den_0(c) = 1 + const - |V_c|^2 + tau
-//   wsum     IV_p = sum_s omega_s c(s, s), later IV_p -= sum_s omega_s u(s)^2: lane-strided sums, then a fixed tree
+//   wsum     IV_p = sum_s omega_s c(s, s), later IV_p -= sum_s omega_s u(s)^2: lane-strided sums, then tree A (wg_dev.h)
 //   score    per PC a 64 x 64 tile of V1'^T V2' on the matrix cores; the epilogue forms K(x_s, x_c) of each element from
 //            the raw rows (kmat_value: the numerics of pcov_kmat_kernel), subtracts, squares, weights, and adds the 64
 //            rows of the tile in a fixed order: one partial per (PC, row tile, candidate).  The S x M matrix never exists.
@@ -21,6 +21,7 @@
 #include "gemm.h"
 #include "pcov_dev.h"
 #include "rows_dev.h"
+#include "wg_dev.h"
 
 struct gpemu_design {
   gpemu_model *m = nullptr;
@@ -77,13 +78,8 @@ __global__ __launch_bounds__(256) void design_wsum_kernel(const double *__restri
     const double x = v[i];
     s = fma(omega[i], square ? x * x : x, s);
   }
-  red[t] = s;
-  __syncthreads();
-  for (int w = 128; w >= 1; w >>= 1) {
-    if (t < w) red[t] += red[t + w];
-    __syncthreads();
-  }
-  if (t == 0) iv[p] = square ? iv[p] - red[0] : red[0];
+  s = wg_sum_a<256>(s, red);
+  if (t == 0) iv[p] = square ? iv[p] - s : s;
 }
 
 // ---- the score kernel ----------------------------------------------------------------------------------------------

@@ -12,14 +12,14 @@
 // probability over the value it read), and runs k_acf.hip's kernels on Y with ld = S: per-series means (acf_sum_kernel,
 // acf_mean_kernel), centred squares (diag_ss_kernel, the same chunks), lag products (acf_lag_kernel, acf_reduce_kernel).
 // diag_chain_reduce_kernel is the fixed-order sum over the 2 nw chains of one parameter (a lane-strided sum in chain
-// order, then wg_sum's tree).  A median or quantile of the pooled unsplit segment comes from gpemu_select_dev on a dense
-// copy of the segment, which uses Y's buffer before Y is written.
+// order, then tree B of wg_dev.h).  A median or quantile of the pooled unsplit segment comes from gpemu_select_dev on a
+// dense copy of the segment, which uses Y's buffer before Y is written.
 #include <algorithm>
 
 #include "internal.h"
-#include "linalg_dev.h"
 #include "rows_dev.h"
 #include "sampler_internal.h"
+#include "wg_dev.h"
 
 namespace gpemu {
 
@@ -131,10 +131,11 @@ __global__ __launch_bounds__(256) void diag_ss_kernel(const double *__restrict__
 }
 
 // out[l d + dd] = scale * sum over the K chains k of f(in[l S + k d + dd]), f(v) = v or, with a centre, (v - centre[dd])^2:
-// the lanes add their chains in order, then wg_sum's tree; workgroup (l, dd)
+// the lanes add their chains in order, then tree B (wg_dev.h); workgroup (l, dd)
 __global__ __launch_bounds__(256) void diag_chain_reduce_kernel(const double *__restrict__ in, int64_t S, int d, int64_t K,
                                                                 const double *__restrict__ centre, double scale,
                                                                 double *__restrict__ out) {
+  __shared__ double ws[4];
   const int64_t l = blockIdx.x;
   const int dd = blockIdx.y;
   const double c = centre ? centre[dd] : 0.0;
@@ -143,15 +144,15 @@ __global__ __launch_bounds__(256) void diag_chain_reduce_kernel(const double *__
     const double v = in[l * S + k * d + dd] - c;
     a += centre ? v * v : v;
   }
-  a = wg_sum(a);
+  a = wg_sum_b<4>(a, ws);
   if (threadIdx.x == 0) out[l * d + dd] = a * scale;
 }
 
-// omin / omax[c d + dd] = min / max of imin / imax[e d + dd] over the elements e of chunk c; workgroup (dd, c)
+// omin / omax[c d + dd] = min / max of imin / imax[e d + dd] over the elements e of chunk c (tree A); workgroup (dd, c)
 __global__ __launch_bounds__(256) void diag_range_kernel(const double *__restrict__ imin, const double *__restrict__ imax,
                                                          int64_t count, int d, double *__restrict__ omin,
                                                          double *__restrict__ omax) {
-  __shared__ double lo[256], hi[256];
+  __shared__ double red[256];
   const int tid = threadIdx.x, dd = blockIdx.x;
   const int64_t per = (count + gridDim.y - 1) / gridDim.y, e0 = (int64_t)blockIdx.y * per, e1 = std::min(e0 + per, count);
   double a = INFINITY, b = -INFINITY;
@@ -159,19 +160,11 @@ __global__ __launch_bounds__(256) void diag_range_kernel(const double *__restric
     a = fmin(a, imin[e * d + dd]);
     b = fmax(b, imax[e * d + dd]);
   }
-  lo[tid] = a;
-  hi[tid] = b;
-  __syncthreads();
-  for (int off = 128; off > 0; off >>= 1) {
-    if (tid < off) {
-      lo[tid] = fmin(lo[tid], lo[tid + off]);
-      hi[tid] = fmax(hi[tid], hi[tid + off]);
-    }
-    __syncthreads();
-  }
+  a = wg_min_a<256>(a, red);
+  b = wg_max_a<256>(b, red);
   if (tid == 0) {
-    omin[(int64_t)blockIdx.y * d + dd] = lo[0];
-    omax[(int64_t)blockIdx.y * d + dd] = hi[0];
+    omin[(int64_t)blockIdx.y * d + dd] = a;
+    omax[(int64_t)blockIdx.y * d + dd] = b;
   }
 }
 

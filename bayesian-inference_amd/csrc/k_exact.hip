@@ -6,6 +6,7 @@
 //   loglik_exact_kernel   ref: log_posterior.py:87-99, 104-146   one workgroup per walker
 #include "internal.h"
 #include "linalg_dev.h"
+#include "wg_dev.h"
 
 namespace gpemu {
 
@@ -519,6 +520,7 @@ __global__ __launch_bounds__(CHOL_THREADS) void loglik_exact_kernel(
     int64_t Bcap, int d, int F,
     int k, int nchunk, int nrb, double inv_ndiv) {
   __shared__ double s_mu[64], s_var[64];
+  __shared__ double ws[CHOL_THREADS / 64];
   __shared__ int s_inside;
   const int tid = threadIdx.x, nthr = blockDim.x;
   const int64_t per = (int64_t)F * F + chol_scratch_size(F) + F;
@@ -572,8 +574,8 @@ __global__ __launch_bounds__(CHOL_THREADS) void loglik_exact_kernel(
       q = fma(dy[f], dy[f], q);
       ld += log(S[(int64_t)f * F + f]);
     }
-    q = wg_sum(q);
-    ld = wg_sum(ld);
+    q = wg_sum_b<CHOL_THREADS / 64>(q, ws);
+    ld = wg_sum_b<CHOL_THREADS / 64>(ld, ws);
     if (tid == 0) out[b] = -0.5 * q - ld;  // ref: log_posterior.py:146
   }
 }

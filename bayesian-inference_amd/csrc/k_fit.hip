@@ -23,6 +23,7 @@
 #include "gemm.h"
 #include "internal.h"
 #include "matern_dev.h"
+#include "wave_dev.h"
 
 namespace gpemu {
 
@@ -99,11 +100,6 @@ __device__ long long g_panel_stamps[128][16];     // [row of the panel][event]: 
 #define POTRF_WAVE_STAMP(i) do { } while (0)
 #define PANEL_STAMP(k) do { } while (0)
 #endif
-__device__ __forceinline__ double readlane_f64(double v, int l) {
-  const int lo = __builtin_amdgcn_readlane(__double2loint(v), l);
-  const int hi = __builtin_amdgcn_readlane(__double2hiint(v), l);
-  return __hiloint2double(hi, lo);
-}
 
 // ---- the 16-column sweep of a panel as a pipeline of three waves -----------------------------------------------
 // Until round 4 ONE wave swept a panel: lane = row (the 16 rows of the diagonal block and the rows below it), pivot by

@@ -19,6 +19,7 @@
 #include "internal.h"
 #include "rows_dev.h"
 #include "sampler_internal.h"
+#include "wg_dev.h"
 
 #include <algorithm>
 #include <cmath>
@@ -160,24 +161,13 @@ __global__ __launch_bounds__(256) void hmc_finish_kernel(HmcArgs a) {
   if (a.lpchain) a.lpchain[w] = acc ? lp1 : lp0;
 }
 
-// sum of v[0 .. n) by one workgroup of 256 in a fixed order: thread t adds the elements t, t + 256, ..., then a tree
-__device__ __forceinline__ double hmc_block_sum(const double *v, int64_t n, double *red) {
-  const int t = threadIdx.x;
-  double s = 0.0;
-  for (int64_t i = t; i < n; i += 256) s += v[i];
-  red[t] = s;
-  __syncthreads();
-  for (int off = 128; off > 0; off >>= 1) {
-    if (t < off) red[t] += red[t + off];
-    __syncthreads();
-  }
-  return red[0];
-}
-
-// one workgroup: the iteration's mean accept probability, and (adapt) the dual-averaging update
+// one workgroup: the iteration's mean accept probability (thread t adds the elements t, t + 256, ..., then tree A of
+// wg_dev.h), and (adapt) the dual-averaging update
 __global__ __launch_bounds__(256) void hmc_adapt_kernel(const double *accp, int W, double *ad, int adapt, double target) {
   __shared__ double red[256];
-  const double s = hmc_block_sum(accp, W, red);
+  double s = 0.0;
+  for (int64_t i = threadIdx.x; i < W; i += 256) s += accp[i];
+  s = wg_sum_a<256>(s, red);
   if (threadIdx.x != 0) return;
   const double mean = s / (double)W;
   ad[AD_LAST] = mean;

@@ -19,13 +19,15 @@
 // atomics: the order of every sum is fixed by S and G.
 //
 // pm_*: the pooled mean, the full covariance (divisor S) and the extents of fma(-beta, x_i, x_j) of rows in blocks, as
-// fixed-order trees over MOM_ROWS rows per workgroup like moments_partial_kernel / moments_final_kernel.
+// tree A (wg_dev.h) over MOM_ROWS rows per workgroup like moments_partial_kernel; the blocks' partials of the sums go
+// through the same final stage (launch_moments_final).
 #include <algorithm>
 #include <cmath>
 #include <vector>
 
 #include "internal.h"
 #include "rows_dev.h"
+#include "wg_dev.h"
 
 namespace gpemu {
 
@@ -198,21 +200,7 @@ __global__ __launch_bounds__(256) void kde2d_sum_kernel(const double *__restrict
   dens[i] = s * norm[p];
 }
 
-// ---- pair moments --------------------------------------------------------------------------------------------------
-// the sum over the workgroup, valid in thread 0, in a fixed tree
-static __device__ __forceinline__ double pm_wg_sum(double s, double *red) {
-  const int t = threadIdx.x;
-  red[t] = s;
-  __syncthreads();
-  for (int off = 128; off > 0; off >>= 1) {
-    if (t < off) red[t] += red[t + off];
-    __syncthreads();
-  }
-  const double out = red[0];
-  __syncthreads();
-  return out;
-}
-
+// ---- pair moments (sums, minima and maxima over the workgroup: tree A of wg_dev.h) -----------------------------------
 // mean == null: part[b][i] = the sum over the rows of block b of x_i (d entries); else part[b][e] = the sum of
 // (x_i - mean_i) (x_j - mean_j), e over the pairs i <= j in row-major order (d (d + 1) / 2 entries)
 __global__ __launch_bounds__(256) void pm_partial_kernel(RowsView v, const double *__restrict__ mean, int nent,
@@ -231,38 +219,14 @@ __global__ __launch_bounds__(256) void pm_partial_kernel(RowsView v, const doubl
         const double *row = v.row(r);
         s += mean ? (row[i] - mi) * (row[j] - mj) : row[i];
       }
-      s = pm_wg_sum(s, red);
+      s = wg_sum_a<256>(s, red);
       if (t == 0) part[(int64_t)blockIdx.x * nent + e] = s;
     }
   }
 }
 
-// out[e] = (the sum over the blocks of part[b][e]) / R; workgroup e
-__global__ __launch_bounds__(256) void pm_final_kernel(const double *__restrict__ part, int64_t nb, int nent, int64_t R,
-                                                       double *__restrict__ out) {
-  __shared__ double red[256];
-  const int e = blockIdx.x;
-  double s = 0.0;
-  for (int64_t b = threadIdx.x; b < nb; b += 256) s += part[b * nent + e];
-  s = pm_wg_sum(s, red);
-  if (threadIdx.x == 0) out[e] = s / (double)R;
-}
-
-// the minimum (which = 0) or maximum over the workgroup, valid in thread 0; NaN is passed over (fmin, fmax)
-static __device__ __forceinline__ double pm_wg_ext(double s, int which, double *red) {
-  const int t = threadIdx.x;
-  red[t] = s;
-  __syncthreads();
-  for (int off = 128; off > 0; off >>= 1) {
-    if (t < off) red[t] = which ? fmax(red[t], red[t + off]) : fmin(red[t], red[t + off]);
-    __syncthreads();
-  }
-  const double out = red[0];
-  __syncthreads();
-  return out;
-}
-
-// part[(b P + p) 2 + {0, 1}] = the minimum and maximum of shear_v over the rows of block b
+// part[(b P + p) 2 + {0, 1}] = the minimum and maximum of shear_v over the rows of block b; NaN is passed over (fmin,
+// fmax)
 __global__ __launch_bounds__(256) void pm_ext_partial_kernel(RowsView v, int P, const int *__restrict__ pairs,
                                                              const double *__restrict__ shear, double *__restrict__ part) {
   __shared__ double red[256];
@@ -278,8 +242,8 @@ __global__ __launch_bounds__(256) void pm_ext_partial_kernel(RowsView v, int P, 
       lo = fmin(lo, w);
       hi = fmax(hi, w);
     }
-    lo = pm_wg_ext(lo, 0, red);
-    hi = pm_wg_ext(hi, 1, red);
+    lo = wg_min_a<256>(lo, red);
+    hi = wg_max_a<256>(hi, red);
     if (t == 0) {
       part[((int64_t)blockIdx.x * P + p) * 2] = lo;
       part[((int64_t)blockIdx.x * P + p) * 2 + 1] = hi;
@@ -297,7 +261,7 @@ __global__ __launch_bounds__(256) void pm_ext_final_kernel(const double *__restr
     const double w = part[b * 2 * P + e];
     s = which ? fmax(s, w) : fmin(s, w);
   }
-  s = pm_wg_ext(s, which, red);
+  s = which ? wg_max_a<256>(s, red) : wg_min_a<256>(s, red);
   if (threadIdx.x == 0) ext[e] = s;
 }
 
@@ -415,9 +379,9 @@ static int pair_moments_rows(const RowsView &X, double *mean, double *cov, int64
     GP_TRY(sc.alloc(&dmean, d));
     GP_TRY(sc.alloc(&dcov, ncov));
     hipLaunchKernelGGL(pm_partial_kernel, dim3((unsigned)nb), dim3(256), 0, st, X, (const double *)nullptr, d, dpart);
-    hipLaunchKernelGGL(pm_final_kernel, dim3((unsigned)d), dim3(256), 0, st, (const double *)dpart, nb, d, R, dmean);
+    launch_moments_final(dpart, nb, d, R, dmean, st);
     hipLaunchKernelGGL(pm_partial_kernel, dim3((unsigned)nb), dim3(256), 0, st, X, (const double *)dmean, ncov, dpart);
-    hipLaunchKernelGGL(pm_final_kernel, dim3((unsigned)ncov), dim3(256), 0, st, (const double *)dpart, nb, ncov, R, dcov);
+    launch_moments_final(dpart, nb, ncov, R, dcov, st);
     GP_HIP(hipGetLastError());
     GP_TRY(sc.download(mean, dmean, d));
     GP_TRY(sc.download(tri.data(), dcov, ncov));

@@ -21,13 +21,14 @@
 // counts.  The k smallest of a set do not depend on the order of the set: the bits are the same for every Z and tile.
 //
 // knn_logsum_*: per subset the counts and the sums of log r2 (or of log nu2 - log rho2) and of its square over blocks
-// of LS_ROWS rows, each a fixed tree; then the blocks' partials in a fixed tree.  No floating-point atomics.
+// of LS_ROWS rows, each by tree A of wg_dev.h; then the blocks' partials by tree A.  No floating-point atomics.
 #include <algorithm>
 #include <cmath>
 #include <vector>
 
 #include "internal.h"
 #include "rows_dev.h"
+#include "wg_dev.h"
 
 namespace gpemu {
 
@@ -200,22 +201,7 @@ __global__ __launch_bounds__(256) void knn_merge_kernel(KnnArgs g) {
   g.zeros[(int64_t)p * g.nq + i] = zeros;
 }
 
-// ---- the sums ----------------------------------------------------------------------------------------------------------
-// the sum over the workgroup, valid in thread 0, in a fixed tree
-template <typename T>
-static __device__ __forceinline__ T ls_wg_sum(T s, T *red) {
-  const int t = threadIdx.x;
-  red[t] = s;
-  __syncthreads();
-  for (int off = 128; off > 0; off >>= 1) {
-    if (t < off) red[t] += red[t + off];
-    __syncthreads();
-  }
-  const T out = red[0];
-  __syncthreads();
-  return out;
-}
-
+// ---- the sums (tree A of wg_dev.h) ---------------------------------------------------------------------------------
 // workgroup (block of LS_ROWS rows, subset): cnt[(p nb + b) 3 + .] = used, short, copies; sum[(p nb + b) 2 + .] = the
 // sum of v and of v^2 over the used rows, v = log r2 or log nu2 - log r2.  A row is used if every distance is finite,
 // short if none is NaN and one is +inf; a NaN distance passes it over.
@@ -243,11 +229,11 @@ __global__ __launch_bounds__(256) void knn_logsum_partial_kernel(int64_t n, cons
     s += v;
     s2 = fma(v, v, s2);
   }
-  used = ls_wg_sum(used, redi);
-  shrt = ls_wg_sum(shrt, redi);
-  copies = ls_wg_sum(copies, redi);
-  s = ls_wg_sum(s, redd);
-  s2 = ls_wg_sum(s2, redd);
+  used = wg_sum_a<256>(used, redi);
+  shrt = wg_sum_a<256>(shrt, redi);
+  copies = wg_sum_a<256>(copies, redi);
+  s = wg_sum_a<256>(s, redd);
+  s2 = wg_sum_a<256>(s2, redd);
   if (t == 0) {
     long long *pc = cnt + (p * nb + b) * 3;
     pc[0] = used; pc[1] = shrt; pc[2] = copies;
@@ -270,11 +256,11 @@ __global__ __launch_bounds__(256) void knn_logsum_final_kernel(int64_t nb, const
     for (int e = 0; e < 2; ++e) s[e] += sum[(p * nb + b) * 2 + e];
   }
   for (int e = 0; e < 3; ++e) {
-    const long long v = ls_wg_sum(c[e], redi);
+    const long long v = wg_sum_a<256>(c[e], redi);
     if (threadIdx.x == 0) ocnt[p * 3 + e] = v;
   }
   for (int e = 0; e < 2; ++e) {
-    const double v = ls_wg_sum(s[e], redd);
+    const double v = wg_sum_a<256>(s[e], redd);
     if (threadIdx.x == 0) osum[p * 2 + e] = v;
   }
 }

@@ -19,6 +19,7 @@
 #include "internal.h"
 #include "linalg_dev.h"
 #include "loglik_dev.h"
+#include "wg_dev.h"
 
 namespace gpemu {
 
@@ -75,6 +76,7 @@ __global__ __launch_bounds__(CHOL_THREADS) void lik_setup_kernel(
     double *A, double *PT, double *Z /*[F][k+nch+S]*/, const double *__restrict__ comp,
     const double *__restrict__ s, const double *__restrict__ smean, const double *__restrict__ yexp,
     const double *__restrict__ src, const int *__restrict__ blk_start, GramOut go, int F, int *info, int max_nf) {
+  __shared__ double ws[CHOL_THREADS / 64];
   const int tid = threadIdx.x, nthr = blockDim.x;
   const int o = blockIdx.x, k = go.k, nch = go.nch;
   const int f0 = blk_start[o], nf = blk_start[o + 1] - f0;
@@ -99,7 +101,7 @@ __global__ __launch_bounds__(CHOL_THREADS) void lik_setup_kernel(
   }
   double ld = 0.0;
   for (int f = tid; f < nf; f += nthr) ld += log(Ao[(int64_t)f * F + f]);
-  ld = wg_sum(ld);
+  ld = wg_sum_b<CHOL_THREADS / 64>(ld, ws);
   if (tid < nch) go.scal[((int64_t)tid * go.nblk + o) * 2 + 1] = 2.0 * ld;
 }
 
@@ -140,6 +142,7 @@ __global__ __launch_bounds__(256) void lik_z_kernel(const double *__restrict__ W
 // the Gram products of GramOut for block o, logdet A_o = 2 sum log diag C: one workgroup
 __global__ __launch_bounds__(1024) void lik_gram_kernel(const double *__restrict__ Z, const double *__restrict__ Lb, int Np,
                                                         int nf, int f0, int o, GramOut go) {
+  __shared__ double ws[1024 / 64];
   const int tid = threadIdx.x, k1 = go.k + go.nch + go.S;
   const double *Zo = Z + (int64_t)f0 * k1;
   for (int idx = tid; idx < k1 * k1; idx += 1024) {
@@ -151,7 +154,7 @@ __global__ __launch_bounds__(1024) void lik_gram_kernel(const double *__restrict
   }
   double ld = 0.0;
   for (int f = tid; f < nf; f += 1024) ld += log(Lb[(int64_t)f * Np + f]);
-  ld = wg_sum(ld);
+  ld = wg_sum_b<1024 / 64>(ld, ws);
   if (tid < go.nch) go.scal[((int64_t)tid * go.nblk + o) * 2 + 1] = 2.0 * ld;
 }
 

@@ -21,7 +21,7 @@
 //                        mean and the variance of V and, on request, the normalised log-weights in the input's order (the
 //                        rank of a tail element: binary search in the sorted tail).
 // Every sum over samples runs over chunks of LOO_SUM = 4096 fixed by the logical index: a lane adds its 16 elements in
-// index order, a fixed butterfly, the waves in order, the chunks in order.  No floating-point atomics: no result bit
+// index order, then tree B of wg_dev.h, the chunks in order.  No floating-point atomics: no result bit
 // depends on the grid, on the batches of rows that fit the workspace or on the run.
 #include <algorithm>
 #include <cfloat>
@@ -32,6 +32,7 @@
 #include "loglik_dev.h"
 #include "rows_dev.h"
 #include "sampler_internal.h"
+#include "wg_dev.h"
 
 namespace gpemu {
 
@@ -101,9 +102,9 @@ static int launch_loo_terms(const TermArgs &a, hipStream_t st) {
   return GPEMU_OK;
 }
 
-// ---- sums in a fixed tree ----------------------------------------------------------------------------------------------
+// ---- sums in tree B (wg_dev.h) -------------------------------------------------------------------------------------
 // the sum of f(i), i < n, by the whole workgroup (256 threads), in every thread: chunks of LOO_SUM in order, within a chunk
-// every lane its 16 elements in index order, the butterfly, the waves in order.  ws: 4 doubles of LDS
+// every lane its 16 elements in index order, then tree B.  ws: 4 doubles of LDS
 template <class F>
 static __device__ __forceinline__ double loo_wg_sum(int64_t n, F f, double *ws) {
   const int tid = threadIdx.x;
@@ -114,11 +115,7 @@ static __device__ __forceinline__ double loo_wg_sum(int64_t n, F f, double *ws) 
       const int64_t i = c0 + (int64_t)j * 256 + tid;
       if (i < n) acc += f(i);
     }
-    acc = wave_sum(acc);
-    if ((tid & 63) == 0) ws[tid >> 6] = acc;
-    __syncthreads();
-    total += ((ws[0] + ws[1]) + ws[2]) + ws[3];
-    __syncthreads();
+    total += wg_sum_b<4>(acc, ws);
   }
   return total;
 }
@@ -295,21 +292,6 @@ static __device__ __forceinline__ double psis_lw(const PsisArgs &a, int rl, cons
   return x;
 }
 
-// the workgroup's combination of per-thread values: op = 0 sum (butterfly, waves in order), 1 max
-static __device__ __forceinline__ double loo_wg_combine(double v, bool is_max, double *ws) {
-  const int tid = threadIdx.x;
-  if (is_max) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v = fmax(v, __shfl_xor(v, off, 64));
-  } else {
-    v = wave_sum(v);
-  }
-  __syncthreads();
-  if ((tid & 63) == 0) ws[tid >> 6] = v;
-  __syncthreads();
-  return is_max ? fmax(fmax(ws[0], ws[1]), fmax(ws[2], ws[3])) : ((ws[0] + ws[1]) + ws[2]) + ws[3];
-}
-
 // workgroup (chunk c, row rl): part[.][0] = max lw, part[.][1] = max (lw + V) over the chunk
 __global__ __launch_bounds__(256) void psis_max_kernel(PsisArgs a) {
   __shared__ double ws[4];
@@ -326,8 +308,8 @@ __global__ __launch_bounds__(256) void psis_max_kernel(PsisArgs a) {
       m1 = fmax(m1, lw + v);
     }
   }
-  m0 = loo_wg_combine(m0, true, ws);
-  m1 = loo_wg_combine(m1, true, ws);
+  m0 = wg_max_b<4>(m0, ws);
+  m1 = wg_max_b<4>(m1, ws);
   if (tid == 0) {
     double *p = a.part + ((int64_t)rl * a.nchunk + c) * LOO_NSUM;
     p[0] = m0;
@@ -370,7 +352,7 @@ __global__ __launch_bounds__(256) void psis_sum_kernel(PsisArgs a) {
     }
   }
 #pragma unroll
-  for (int q = 0; q < LOO_NSUM; ++q) acc[q] = loo_wg_combine(acc[q], false, ws);
+  for (int q = 0; q < LOO_NSUM; ++q) acc[q] = wg_sum_b<4>(acc[q], ws);
   if (tid == 0) {
     double *p = a.part + ((int64_t)rl * a.nchunk + c) * LOO_NSUM;
 #pragma unroll
@@ -414,7 +396,7 @@ __global__ __launch_bounds__(256) void psis_var_kernel(PsisArgs a) {
       if (a.logw) a.logw[(a.row0 + rl) * a.S + i] = bad ? loo_nan() : psis_lw(a, rl, st, n, v) - lsew;
     }
   }
-  acc = loo_wg_combine(acc, false, ws);
+  acc = wg_sum_b<4>(acc, ws);
   if (tid == 0) a.part[((int64_t)rl * a.nchunk + c) * LOO_NSUM] = acc;
 }
 
@@ -563,7 +545,7 @@ __global__ __launch_bounds__(256) void wm_partial_kernel(WmArgs a) {
 #pragma unroll
   for (int j = 0; j <= WM_MAX_D; ++j) {
     if (j < d || j == WM_MAX_D) {
-      const double v = loo_wg_combine(acc[j], false, ws);
+      const double v = wg_sum_b<4>(acc[j], ws);
       if (tid == 0) p[j] = v;
     }
   }

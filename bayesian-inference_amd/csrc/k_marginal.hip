@@ -18,8 +18,8 @@
 // Kernel density (kde_*): workgroup (chunk of KD_CHUNK samples, tile of 256 GPT grid points, row).  A thread keeps GPT
 // grid points in registers; the samples go through LDS in stages of KD_STAGE and sample j of the chunk is added to sum
 // j mod 4 of every grid point, so the order of every sum is fixed by the sample index.  kde_sum_kernel adds a grid
-// point's chunk sums: lane-strided in chunk order, then a butterfly and the waves in order.  A term whose exponent is
-// below -746 is exactly 0 in fp64 and is not evaluated.
+// point's chunk sums: lane-strided in chunk order, then tree B of wg_dev.h.  A term whose exponent is below -746 is
+// exactly 0 in fp64 and is not evaluated.
 #include <algorithm>
 #include <cmath>
 #include <vector>
@@ -27,7 +27,7 @@
 #include "internal.h"
 #include "rows_dev.h"
 #include "sampler_internal.h"
-#include "wave_dev.h"
+#include "wg_dev.h"
 
 namespace gpemu {
 
@@ -133,13 +133,8 @@ __global__ __launch_bounds__(256) void mh_inside_kernel(const unsigned long long
   const int tid = threadIdx.x;
   unsigned long long s = 0;
   for (int b = tid; b < nb1; b += 256) s += hist1[(int64_t)blockIdx.x * nb1 + b];
-  red[tid] = s;
-  __syncthreads();
-  for (int off = 128; off > 0; off >>= 1) {
-    if (tid < off) red[tid] += red[tid + off];
-    __syncthreads();
-  }
-  if (tid == 0) n_inside[blockIdx.x] = red[0];
+  s = wg_sum_a<256>(s, red);
+  if (tid == 0) n_inside[blockIdx.x] = s;
 }
 
 struct HistSweep { int a0, a1, p0, p1; };
@@ -425,12 +420,10 @@ __global__ __launch_bounds__(256) void kde_sum_kernel(const double *__restrict__
   const double *p = part + (int64_t)blockIdx.x * nchunk;
   double a = 0.0;
   for (int64_t c = tid; c < nchunk; c += 256) a += p[c];
-  a = wave_sum(a);
-  if ((tid & 63) == 0) ws[tid >> 6] = a;
-  __syncthreads();
+  a = wg_sum_b<4>(a, ws);
   if (tid == 0) {
     const int64_t rl = blockIdx.x / G, g = blockIdx.x % G;
-    dens[(row0 + rl) * G + g] = (((ws[0] + ws[1]) + ws[2]) + ws[3]) * norm[row0 + rl];
+    dens[(row0 + rl) * G + g] = a * norm[row0 + rl];
   }
 }
 

@@ -17,6 +17,7 @@
 #include <numeric>
 
 #include "internal.h"
+#include "wave_dev.h"
 
 namespace gpemu {
 
@@ -218,7 +219,7 @@ __device__ void jacobi_solve(SolveLds<PB> &L, const double *__restrict__ src, in
       const double g = L.As[i * LDA + j];
       if (den2 > 0.0 && g != 0.0 && (aii > noise2 || ajj > noise2)) worst = fmax(worst, g * g / den2);
     }
-    for (int off = 32; off > 0; off >>= 1) worst = fmax(worst, __shfl_xor(worst, off));
+    worst = wave_max(worst);
     if ((tid & 63) == 0) atomicMax(&L.off, (unsigned long long)__double_as_longlong(sqrt(worst)));
   }
   __syncthreads();

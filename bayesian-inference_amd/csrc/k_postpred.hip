@@ -20,7 +20,7 @@
 // logical rows (a chunk that is not contiguous in the caller's block layout is gathered into a staging buffer first, so
 // the launches -- and the bits -- are those of the contiguous rows), then per block of features
 //   pp_project_kernel  mu[f][s] = (sum_p mean[s][p] comp[p][f]) scale_f + mean_f, feature-major (cv_backproject's sum);
-//   pp_rowsum_kernel   sums of fixed 4096-sample chunks (lane-strided partial sums in index order, fixed butterfly),
+//   pp_rowsum_kernel   sums of fixed 4096-sample chunks (lane-strided partial sums in index order, tree B of wg_dev.h),
 //   pp_finish_kernel   added in chunk order: the mean, then the centred second moment (two passes);
 //   selection on the rows of the workspace.
 // var_emu_f = mean_s sigma^2_f(theta_s) = (sum_p comp[p][f] vbar_p comp[p][f] + cov_unexplained[f][f]) scale_f^2 with
@@ -33,7 +33,7 @@
 #include "internal.h"
 #include "rows_dev.h"
 #include "sampler_internal.h"
-#include "wave_dev.h"
+#include "wg_dev.h"
 
 namespace gpemu {
 
@@ -260,7 +260,7 @@ __global__ __launch_bounds__(256) void pp_project_kernel(const double *__restric
 }
 
 // part[row nchunk + c] = sum over samples [c PP_SUM, (c + 1) PP_SUM) of x (centre null) or (x - centre[row])^2,
-// x = X[row rs + i es]: every lane adds its 16 elements in index order, then a fixed butterfly and the waves in order
+// x = X[row rs + i es]: every lane adds its 16 elements in index order, then tree B of wg_dev.h
 __global__ __launch_bounds__(256) void pp_rowsum_kernel(const double *__restrict__ X, int64_t rs, int64_t es, int64_t S,
                                                         const double *__restrict__ centre, double *__restrict__ part,
                                                         int64_t nchunk) {
@@ -277,10 +277,8 @@ __global__ __launch_bounds__(256) void pp_rowsum_kernel(const double *__restrict
       acc += centre ? (v - mu) * (v - mu) : v;
     }
   }
-  acc = wave_sum(acc);
-  if ((tid & 63) == 0) ws[tid >> 6] = acc;
-  __syncthreads();
-  if (tid == 0) part[row * nchunk + c] = ((ws[0] + ws[1]) + ws[2]) + ws[3];
+  acc = wg_sum_b<4>(acc, ws);
+  if (tid == 0) part[row * nchunk + c] = acc;
 }
 
 // out[row] = (sum of the row's partial sums, in chunk order) * scale

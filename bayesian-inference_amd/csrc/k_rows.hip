@@ -17,6 +17,7 @@
 // The sorted key array of a row is unique and every counter is an integer: it does not depend on the grid, on the batch
 // of rows or on the run.  The pass count is fixed, whatever the data.  The kernels are compiled once, here.
 #include "rows_dev.h"
+#include "wg_dev.h"
 
 namespace gpemu {
 
@@ -46,7 +47,7 @@ int gather_rows(const RowsView &v, int64_t r0, int64_t n, double *dst, hipStream
   return GPEMU_OK;
 }
 
-// ---- pooled mean and variance per parameter, two passes, fixed order -----------------------------------------------
+// ---- pooled mean and variance per parameter, two passes, tree A (wg_dev.h) ---------------------------------------
 // (MOM_ROWS rows of the flattened chain [R][d] per workgroup)
 
 // part[b][dd] = sum over the rows of block b of x (mean == null) or of (x - mean[dd])^2
@@ -62,39 +63,32 @@ __global__ __launch_bounds__(256) void moments_partial_kernel(const double *__re
       const double v = x[r * d + dd] - mu;
       s += mean ? v * v : v;
     }
-    red[t] = s;
-    __syncthreads();
-    for (int off = 128; off > 0; off >>= 1) {
-      if (t < off) red[t] += red[t + off];
-      __syncthreads();
-    }
-    if (t == 0) part[(int64_t)blockIdx.x * d + dd] = red[0];
-    __syncthreads();
+    s = wg_sum_a<256>(s, red);
+    if (t == 0) part[(int64_t)blockIdx.x * d + dd] = s;
   }
 }
 
-// out[dd] = (sum over the blocks of part[b][dd]) / R; grid = d workgroups
-__global__ __launch_bounds__(256) void moments_final_kernel(const double *__restrict__ part, int64_t nb, int d, int64_t R,
+// out[e] = (sum over the blocks of part[b][e]) / R; grid = nent workgroups
+__global__ __launch_bounds__(256) void moments_final_kernel(const double *__restrict__ part, int64_t nb, int nent, int64_t R,
                                                             double *__restrict__ out) {
   __shared__ double red[256];
-  const int t = threadIdx.x, dd = blockIdx.x;
+  const int t = threadIdx.x, e = blockIdx.x;
   double s = 0.0;
-  for (int64_t b = t; b < nb; b += 256) s += part[b * d + dd];
-  red[t] = s;
-  __syncthreads();
-  for (int off = 128; off > 0; off >>= 1) {
-    if (t < off) red[t] += red[t + off];
-    __syncthreads();
-  }
-  if (t == 0) out[dd] = red[0] / (double)R;
+  for (int64_t b = t; b < nb; b += 256) s += part[b * nent + e];
+  s = wg_sum_a<256>(s, red);
+  if (t == 0) out[e] = s / (double)R;
+}
+
+void launch_moments_final(const double *dpart, int64_t nb, int nent, int64_t R, double *dout, hipStream_t st) {
+  hipLaunchKernelGGL(moments_final_kernel, dim3((unsigned)nent), dim3(256), 0, st, dpart, nb, nent, R, dout);
 }
 
 int launch_moments(const double *dx, int64_t R, int d, double *dpart, double *dmom, hipStream_t st) {
   const int64_t nb = (R + MOM_ROWS - 1) / MOM_ROWS;
   hipLaunchKernelGGL(moments_partial_kernel, dim3((unsigned)nb), dim3(256), 0, st, dx, R, d, (const double *)nullptr, dpart);
-  hipLaunchKernelGGL(moments_final_kernel, dim3((unsigned)d), dim3(256), 0, st, dpart, nb, d, R, dmom);
+  launch_moments_final(dpart, nb, d, R, dmom, st);
   hipLaunchKernelGGL(moments_partial_kernel, dim3((unsigned)nb), dim3(256), 0, st, dx, R, d, (const double *)dmom, dpart);
-  hipLaunchKernelGGL(moments_final_kernel, dim3((unsigned)d), dim3(256), 0, st, dpart, nb, d, R, dmom + d);
+  launch_moments_final(dpart, nb, d, R, dmom + d, st);
   GP_HIP(hipGetLastError());
   return GPEMU_OK;
 }

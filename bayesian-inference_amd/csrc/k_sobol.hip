@@ -34,6 +34,7 @@
 #include "internal.h"
 #include "predict_dev.h"
 #include "rows_dev.h"
+#include "wg_dev.h"
 
 namespace gpemu {
 
@@ -188,20 +189,15 @@ __device__ __forceinline__ double sobol_blocked_sum(int64_t n, Fn &&f) {
 }
 
 // pivot[p] = mean of z over the m rows of A and of B in Z [2][zs][k] (slots A, B); one workgroup per PC: thread t adds
-// rows t, t + 256, .. in order, then a fixed tree over the threads
+// rows t, t + 256, .. in order, then tree A of wg_dev.h
 __global__ __launch_bounds__(256) void sobol_pivot_kernel(const double *__restrict__ Z, int64_t zs, int64_t m, int k,
                                                           double *__restrict__ pivot) {
   __shared__ double s[256];
   const int p = blockIdx.x, tid = threadIdx.x;
   double acc = 0.0;
   for (int64_t r = tid; r < m; r += 256) acc += Z[r * k + p] + Z[(zs + r) * k + p];
-  s[tid] = acc;
-  __syncthreads();
-  for (int w = 128; w >= 1; w >>= 1) {
-    if (tid < w) s[tid] += s[tid + w];
-    __syncthreads();
-  }
-  if (tid == 0) pivot[p] = s[0] / (double)(2 * m);
+  acc = wg_sum_a<256>(acc, s);
+  if (tid == 0) pivot[p] = acc / (double)(2 * m);
 }
 
 // the partial sums of one slice: [C2 k^2][M d k^2][D d k^2][sumA k][sumB k][sumD d k]

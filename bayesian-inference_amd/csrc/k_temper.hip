@@ -12,6 +12,7 @@
 // evidence (gpemu/tempering.py).
 #include "internal.h"
 #include "sampler_internal.h"
+#include "wg_dev.h"
 
 #include <algorithm>
 #include <cmath>
@@ -63,7 +64,8 @@ __global__ __launch_bounds__(256) void temper_swap_kernel(double *__restrict__ X
 }
 
 // mean_ll[t] = mean of lpchain[first .. first + n)[t Wc .. t Wc + Wc): one workgroup per rung.  Every thread adds a
-// fixed strided set of entries in a fixed order, then a fixed-shape tree in LDS: the same bits on every run.
+// fixed strided set of entries in a fixed order, then tree A of wg_dev.h over the 1024 threads: the same bits on every
+// run.
 constexpr int MEAN_LL_THREADS = 1024;
 __global__ __launch_bounds__(MEAN_LL_THREADS) void mean_ll_kernel(const double *__restrict__ lpchain, double *__restrict__ out,
                                                                   int64_t first, int64_t n, int Wc, int64_t W) {
@@ -75,13 +77,8 @@ __global__ __launch_bounds__(MEAN_LL_THREADS) void mean_ll_kernel(const double *
     const int64_t row = first + i / Wc, w = i % Wc;
     acc += lpchain[row * W + (int64_t)t * Wc + w];
   }
-  part[tid] = acc;
-  __syncthreads();
-  for (int h = MEAN_LL_THREADS / 2; h > 0; h >>= 1) {
-    if (tid < h) part[tid] += part[tid + h];
-    __syncthreads();
-  }
-  if (tid == 0) out[t] = part[0] / (double)total;
+  acc = wg_sum_a<MEAN_LL_THREADS>(acc, part);
+  if (tid == 0) out[t] = acc / (double)total;
 }
 
 int temper_validate_ladder(const double *betas, int n_temps) {

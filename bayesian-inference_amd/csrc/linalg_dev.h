@@ -160,23 +160,4 @@ __device__ inline void wg_forward_solve_vec(const double *C, int n, int ld, doub
   }
 }
 
-// workgroup sum of one double per thread (result valid in every thread)
-__device__ inline double wg_sum(double v) {
-  __shared__ double part[CHOL_THREADS / 64];
-  __shared__ double total;
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  const int wave = threadIdx.x >> 6, nwave = blockDim.x >> 6;
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) part[wave] = v;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double s = 0.0;
-    for (int w = 0; w < nwave; ++w) s += part[w];
-    total = s;
-  }
-  __syncthreads();
-  return total;
-}
-
-
 }  // namespace gpemu

@@ -117,13 +117,6 @@ __device__ __forceinline__ void finish_walker(double total, double *__restrict__
   }
 }
 
-// value of lane `l` (compile-time / wave-uniform index) as a scalar: v_readlane, no LDS round trip
-__device__ __forceinline__ double readlane_f64(double v, int l) {
-  const int lo = __builtin_amdgcn_readlane(__double2loint(v), l);
-  const int hi = __builtin_amdgcn_readlane(__double2hiint(v), l);
-  return __hiloint2double(hi, lo);
-}
-
 template <int KMAX>
 __device__ __forceinline__ double sum_first_lanes(double v) {
   double s = readlane_f64(v, 0);

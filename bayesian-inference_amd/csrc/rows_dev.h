@@ -31,9 +31,13 @@ int gather_rows(const RowsView &v, int64_t r0, int64_t n, double *dst, hipStream
 
 // ---- pooled moments ------------------------------------------------------------------------------------------------
 // dmom[0 .. d) = mean, dmom[d .. 2d) = variance (divisor R) of the R rows of dx [R][d], two passes with sums in a fixed
-// order; dpart: (R + MOM_ROWS - 1) / MOM_ROWS * d doubles of scratch; asynchronous on st
+// order (thread t its rows t, t + 256, ... of a block of MOM_ROWS, then tree A of wg_dev.h; the block partials the same
+// way); dpart: (R + MOM_ROWS - 1) / MOM_ROWS * d doubles of scratch; asynchronous on st
 constexpr int MOM_ROWS = 1024;
 int launch_moments(const double *dx, int64_t R, int d, double *dpart, double *dmom, hipStream_t st);
+// the final stage alone: dout[e] = (the sum over the nb blocks of dpart[b][e]) / R, e < nent; the caller checks the
+// launch
+void launch_moments_final(const double *dpart, int64_t nb, int nent, int64_t R, double *dout, hipStream_t st);
 // ... with its scratch, into host mean [d] and var [d]; waits for st
 int moments_to_host(const double *dx, int64_t R, int d, double *mean, double *var, hipStream_t st);
 
