@@ -167,6 +167,9 @@ LaunchSwitches read_launch_switches() {
   sw.halfstep_min_pairs = e ? atoi(e) : 64;
   e = getenv("GPEMU_LOGLIK_TASKS_MAX_ROWS");
   sw.loglik_tasks_max_rows = e ? atoll(e) : 256;
+  sw.compact = getenv("GPEMU_NO_COMPACT") == nullptr;
+  e = getenv("GPEMU_COMPACT_FORM");
+  sw.compact_form = e ? atoi(e) : -1;
   return sw;
 }
 
@@ -191,7 +194,12 @@ static bool groups_fit(gpemu_model *const *ms, int ng, int64_t B) {
 // emulators, k_halfstep.hip); (2) for several groups, one launch per stage; (3) group by group, the groups after the
 // first adding to dout.  Stacked chains take neither (1) nor (2).  Every form gives the same bits.
 int logpost_eval(gpemu_model *const *ms, int ng, int64_t B, double *dXq, double *dout, hipStream_t st,
-                 const LaunchSwitches &sw, const AcceptArgs *aa, const ProposeArgs *pa) {
+                 const LaunchSwitches &sw, const AcceptArgs *aa, const ProposeArgs *pa, const LiveCols *lv) {
+  if (lv && (ng != 1 || ms[0]->n_src != 0 || (aa && aa->chain_per != 0) || halfstep_fits(ms, 1, B, sw) ||
+             loglik_tasks_fit(ms, 1, B, aa, sw))) {
+    set_error("logpost_eval: compacted columns outside the general path of one group");   // (the caller's eligibility test)
+    return GPEMU_ERR_STATE;
+  }
   for (int g = 0; g < ng; ++g)
     if (!ms[g]->lik_ready) { set_error("gpemu_likelihood_setup has not been called"); return GPEMU_ERR_STATE; }
   // correlated sources (k_srccorr.hip): one set of sources for all groups, whose term follows the likelihood stage
@@ -237,8 +245,8 @@ int logpost_eval(gpemu_model *const *ms, int ng, int64_t B, double *dXq, double 
       GP_TRY(launch_halfstep_small(one, 1, B, dXq, st, pg));
     } else {
       path_count(GPEMU_PATH_HALFSTEP_GENERAL);
-      GP_TRY(launch_kstar(ms[g], B, dXq, st, pg));
-      GP_TRY(launch_trmm_vsq(ms[g], B, st));
+      GP_TRY(launch_kstar(ms[g], B, dXq, st, pg, lv));
+      GP_TRY(launch_trmm_vsq(ms[g], B, st, lv));
     }
     GP_TRY(loglik(one, 1, g > 0 ? 1 : 0, g + 1 == ng ? aa_lik : (aa ? &chain_only : nullptr)));
   }
@@ -343,6 +351,8 @@ static int model_fill(gpemu_model *m, const double *X_train, const double *ls, c
   GP_TRY(dev_alloc(&m->smean, F));
   GP_TRY(dev_alloc(&m->sscale, F));
   GP_TRY(dev_alloc(&m->cunexpl, F * F));
+  GP_TRY(dev_alloc(&m->live_cnt, 2));
+  GP_HIP(hipMemsetAsync(m->live_cnt, 0, sizeof(long long) * 2, st));
   GP_TRY(sc.alloc(&dL, k * N * N));
   GP_TRY(upload(m->ls, hls.data(), k * dp, st));
   {
@@ -486,8 +496,10 @@ int gpemu_model_destroy(gpemu_model *m) {
   dev_free(m->blk_start); dev_free(m->blk_of);
   for (gpemu_model::SchedEntry &en : m->sched_cache) { dev_free(en.items); dev_free(en.cnt); }
   for (gpemu_model::SchedEntry &en : m->sm_cache) { dev_free(en.items); dev_free(en.cnt); }
+  for (gpemu_model::LiveDeal &en : m->live_cache) { dev_free(en.items); dev_free(en.cnt); dev_free(en.kmap); }
   dev_free(m->lik_terms);
   dev_free(m->lik_tickets);
+  dev_free(m->live_cnt);
   free_workspace(m->ws);
   for (hipEvent_t e : m->ev_pool) (void)hipEventDestroy(e);
   if (m->stream) hipStreamDestroy(m->stream);
@@ -503,6 +515,18 @@ int gpemu_model_profile(gpemu_model *m, int enable) {
   m->profiling = enable != 0;
   m->prof_ms[0] = m->prof_ms[1] = 0.0;
   m->prof_n[0] = m->prof_n[1] = 0;
+  GP_HIP(hipMemset(m->live_cnt, 0, sizeof(long long) * 2));
+  return GPEMU_OK;
+}
+
+int gpemu_model_live_counts(gpemu_model *m, int64_t *live_proposals) {
+  GP_ARG(m && live_proposals, "null pointer");
+  GP_HIP(hipSetDevice(m->device));
+  GP_HIP(hipDeviceSynchronize());
+  long long h[2] = {0, 0};
+  GP_HIP(hipMemcpy(h, m->live_cnt, sizeof(h), hipMemcpyDeviceToHost));
+  live_proposals[0] = h[0];
+  live_proposals[1] = h[1];
   return GPEMU_OK;
 }
 

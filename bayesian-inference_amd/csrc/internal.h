@@ -101,6 +101,10 @@ struct gpemu_model {
   int sched_cap = 0;           // worker cap the current schedule was built for
   struct SchedEntry { int ncb, cap; void *items; int *cnt; int max_items, workers; };
   std::vector<SchedEntry> sched_cache;   // every schedule built so far (sched_items / sched_cnt point into one of them)
+  // the sampler's compacted half-step (k_predict.hip: live_deal): for one launch shape, the GEMM's schedule and the
+  // cross-kernel's workgroup map of EVERY number of live 64-column blocks, 0 .. 2 ncb, picked on the device
+  struct LiveDeal { int ncb, cap, form; void *items; int *cnt; int *kmap; int max_items, workers, nwg; };
+  std::vector<LiveDeal> live_cache;
   int64_t vsq_nrb = 0;         // row blocks of partial ||W k_*||^2 the triangular GEMM writes
   // schedule of the small-batch triangular GEMM (k_trmm_small.hip) for the current number of 32-column blocks
   void *sm_items = nullptr;
@@ -189,6 +193,9 @@ struct gpemu_model {
   size_t ev_next = 0;
   double prof_ms[2] = {0.0, 0.0};          // accumulated: [0] trmm_vsq, [1] kstar
   int64_t prof_n[2] = {0, 0};
+  // device, [2]: proposals inside the prior box / proposals formed by the compacted half-steps of samplers over this
+  // model (k_sampler.hip: propose_compact_kernel) since gpemu_model_profile was last called
+  long long *live_cnt = nullptr;
 
   gpemu::Workspace ws;
 };
@@ -223,6 +230,9 @@ struct AcceptArgs {
   // and scale the accept test by their inverse temperature beta[(first + b) / chain_per]; null: untempered
   const double *beta = nullptr;
   int chain_data = 1;             // with chain_per != 0: the row's chain selects the data constants (g0, q0)
+  // compacted half-step (k_sampler.hip: propose_compact_kernel): proposal b's query row, partial sums and new position
+  // are those of column slot_of[b]; a negative slot is a proposal outside the prior box, which has none.  null: column b
+  const int *slot_of = nullptr;
 };
 
 // stretch-move accept of a proposal (log-probability nlp) for a walker at oldlp, at inverse temperature beta.
@@ -250,6 +260,16 @@ struct ProposeArgs {
   // enabled == 0 and raw != nullptr: the queries come as caller rows [n][d] (gpemu_gp_predict / predict_full); the
   // kernel pads them to [..][dpad_of(d)] on the fly and stores the padded rows once (what pad_queries_kernel used to do)
   const double *raw = nullptr;
+};
+
+// The sampler's compacted half-step: the first *n_live rows of the padded query buffer are the proposals inside the
+// prior box, and the cross-kernel and the triangular GEMM serve only the ceil(*n_live / 64) column blocks that hold them
+// (the count is known on the device alone: the grids stay those of the whole batch).  form: how the live blocks are
+// dealt to the XCDs -- 0 the whole batch's schedule, 1 the whole batch's placement without the dead blocks, 2 by cost
+// (k_predict.hip: build_trmm_schedule), -1 the measured choice per count
+struct LiveCols {
+  const int *n_live = nullptr;
+  int form = -1;
 };
 
 int ensure_workspace(gpemu_model *m, int64_t B);
@@ -284,8 +304,13 @@ static inline bool kstar_same_kernel(const gpemu_model *a, const gpemu_model *b)
 
 // kernels (launchers; all asynchronous on `st`)
 // dXq_padded is read, or -- with pa->enabled -- written (rows [0, round_up(B, 128))) by the kernel
-int launch_kstar(gpemu_model *m, int64_t B, double *dXq_padded, hipStream_t st, const ProposeArgs *pa = nullptr);
-int launch_trmm_vsq(gpemu_model *m, int64_t B, hipStream_t st);
+int launch_kstar(gpemu_model *m, int64_t B, double *dXq_padded, hipStream_t st, const ProposeArgs *pa = nullptr,
+                 const LiveCols *lv = nullptr);
+int launch_trmm_vsq(gpemu_model *m, int64_t B, hipStream_t st, const LiveCols *lv = nullptr);
+// builds (once per model, shape and form) the tables the two launches above pick from with `lv` for batches of B columns:
+// the sampler calls it when it is created, so that no run allocates or copies them.  GPEMU_ERR_UNSUPPORTED: a shape the
+// tables cannot describe -- the caller evaluates every proposal instead
+int prepare_live_cols(gpemu_model *m, int64_t B, int form, hipStream_t st);
 int small_trmm_xcd_of(const gpemu_model *m, int64_t B, int p, int64_t col);
 int trmm_xcd_of(const gpemu_model *m, int64_t B, int p, int64_t col);   // XCD that reads K_*^T rows (p, col) in launch_trmm_vsq(m, B); -1: any
 int launch_trmm_vsq_small(gpemu_model *m, int64_t B, hipStream_t st);   // B <= 128; GPEMU_ERR_UNSUPPORTED if the shape does not fit
@@ -298,11 +323,13 @@ struct LaunchSwitches {
   bool loglik_tasks;              // not GPEMU_NO_LOGLIK_TASKS: observable blocks on different waves
   int halfstep_min_pairs;         // GPEMU_HALFSTEP_MIN_PAIRS, default 64
   int64_t loglik_tasks_max_rows;  // GPEMU_LOGLIK_TASKS_MAX_ROWS, default 256
+  bool compact;                   // not GPEMU_NO_COMPACT: the sampler's half-step evaluates only the proposals inside the prior box
+  int compact_form;               // GPEMU_COMPACT_FORM (measurements: LiveCols::form for every count), default -1
 };
 LaunchSwitches read_launch_switches();
 // log-posterior of B padded query rows summed over ng groups: the one place that chooses the launches (gpemu_api.hip)
 int logpost_eval(gpemu_model *const *ms, int ng, int64_t B, double *dXq, double *dout, hipStream_t st,
-                 const LaunchSwitches &sw, const AcceptArgs *aa, const ProposeArgs *pa);
+                 const LaunchSwitches &sw, const AcceptArgs *aa, const ProposeArgs *pa, const LiveCols *lv = nullptr);
 int launch_loglik_lowrank(gpemu_model *m, int64_t B, const double *dXq_padded, double *dout,
                           int accumulate, hipStream_t st, const AcceptArgs *aa);
 // several emulation groups, one launch per stage instead of one per group and stage (k_predict.hip, k_trmm_small.hip,

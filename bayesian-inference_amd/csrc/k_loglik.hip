@@ -223,14 +223,21 @@ __global__ __launch_bounds__(256) void loglik_lowrank_kernel(
     scal += ch * 2 * nblk;
   }
 
+  // compacted half-step: the proposal's column; none (negative) for a proposal outside the prior box, whose
+  // log-posterior is -inf whatever the emulators say -- the value, the NaN flag and the reject of the box test below
+  const int64_t col = aa.slot_of ? (int64_t)aa.slot_of[b] : b;
   // everything that does not depend on the GP stage is requested first: the accept operands (a dependent
   // index -> state chain) and the first observable block's constants
-  const AcceptOperands ao = load_accept_operands(Xq, b, lane, aa);
+  const AcceptOperands ao = load_accept_operands(Xq, b, lane, aa, col);
+  if (col < 0) {
+    finish_walker(-INFINITY, out, b, d, lane, accumulate, aa, ao);
+    return;
+  }
   const BlockPre<KMAX> pre = prefetch_block<KMAX>(G, g0, scal, k, lane);
-  const bool inside = inside_box(Xq, b, dpad_of(d), d, lo, hi, lane);
+  const bool inside = inside_box(Xq, col, dpad_of(d), d, lo, hi, lane);
 
   double mu, sd;
-  walker_mean_sd<(KMAX <= 16 ? 16 : 32)>(mean_part, vsq_part, kdiag, mean_out, var_out, b, Bcap, k, nchunk, nrb, lane, mu, sd);
+  walker_mean_sd<(KMAX <= 16 ? 16 : 32)>(mean_part, vsq_part, kdiag, mean_out, var_out, col, Bcap, k, nchunk, nrb, lane, mu, sd);
   const double total = walker_loglik_lowrank<KMAX>(inside, mu, sd, pre, G, g0, scal, k, nblk, lane);
   finish_walker(total, out, b, d, lane, accumulate, aa, ao);
 }
@@ -255,12 +262,17 @@ __global__ __launch_bounds__(256) void loglik_lowrank_lds_kernel(
   }
   double *M = smem + (size_t)wave * k * (k + 1);
   const int ldm = k + 1;
-  const bool inside = inside_box(Xq, b, dpad_of(d), d, lo, hi, lane);
+  const int64_t col = aa.slot_of ? (int64_t)aa.slot_of[b] : b;     // (loglik_lowrank_kernel)
+  if (col < 0) {
+    finish_walker(-INFINITY, out, b, d, lane, accumulate, aa, load_accept_operands(Xq, b, lane, aa, col));
+    return;
+  }
+  const bool inside = inside_box(Xq, col, dpad_of(d), d, lo, hi, lane);
   double mu, sd;
-  if (k <= 32) walker_mean_sd<32>(mean_part, vsq_part, kdiag, mean_out, var_out, b, Bcap, k, nchunk, nrb, lane, mu, sd);
-  else walker_mean_sd<64>(mean_part, vsq_part, kdiag, mean_out, var_out, b, Bcap, k, nchunk, nrb, lane, mu, sd);
+  if (k <= 32) walker_mean_sd<32>(mean_part, vsq_part, kdiag, mean_out, var_out, col, Bcap, k, nchunk, nrb, lane, mu, sd);
+  else walker_mean_sd<64>(mean_part, vsq_part, kdiag, mean_out, var_out, col, Bcap, k, nchunk, nrb, lane, mu, sd);
   const double total = walker_loglik_lowrank_lds(inside, mu, sd, G, g0, scal, k, nblk, lane, M, ldm);
-  finish_walker(total, out, b, d, lane, accumulate, aa, load_accept_operands(Xq, b, lane, aa));
+  finish_walker(total, out, b, d, lane, accumulate, aa, load_accept_operands(Xq, b, lane, aa, col));
 }
 
 // ---- several emulation groups in one launch ----------------------------------------------------------------------

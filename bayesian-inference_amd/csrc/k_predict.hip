@@ -39,7 +39,36 @@ struct KstarArgs {
   int k, nchunk, ncb64;                // grid = ncb64 * nchunk * k workgroups (1-D)
   int gper, ncbp;                      // gper > 0: XCD-aware placement, gper of the k ncbp (PC, 128-column block) groups
                                        // of each piece of ncbp column blocks per XCD
+  // the sampler's compacted half-step (internal.h: LiveCols): only the first ceil(*live / 64) column blocks hold queries,
+  // and workgroup i of the grid's nwg takes the unit kmap[that count][i] (kstar_pack), or none (-1)
+  const int *live, *kmap;
+  int nwg;
 };
+
+// the (PC, row chunk, 64-column block) of workgroup bidx in the grid of a whole batch
+struct KstarUnit { int p, chunk, cb; };
+__host__ __device__ static inline KstarUnit kstar_unit(int bidx, int nchunk, int ncb64, int gper, int ncbp) {
+  KstarUnit u;
+  if (gper > 0) {
+    // the GEMM runs one launch per piece of ncbp 128-column blocks (launch_trmm_vsq: at most 512 columns each), every
+    // launch dealing its k ncbp groups to the XCDs in (PC, column block) order, gper per XCD
+    const int xcd = bidx & 7, slot = bidx >> 3;
+    const int half = slot & 1, rest = slot >> 1;
+    u.chunk = rest % nchunk;
+    const int rest2 = rest / nchunk;
+    const int piece = rest2 / gper, g = xcd * gper + rest2 % gper;
+    u.p = g / ncbp;
+    u.cb = 2 * (piece * ncbp + g % ncbp) + half;
+  } else {
+    u.cb = bidx % ncb64;
+    const int rest = bidx / ncb64;
+    u.chunk = rest % nchunk;
+    u.p = rest / nchunk;
+  }
+  return u;
+}
+// a unit as an entry of KstarArgs::kmap: p < 64, chunk < 4096, cb < 256
+__host__ __device__ static inline int kstar_pack(const KstarUnit &u) { return (u.p << 20) | (u.chunk << 8) | u.cb; }
 
 // bidx: the workgroup's index within its group's grid; store_rows: this group's first workgroups keep the padded query
 // rows / stretch factors (the first group of a launch that serves several: the others form the same rows and store nothing)
@@ -60,21 +89,18 @@ __device__ __forceinline__ void kstar_body(const KstarArgs &ka, const ProposeArg
   // So each group's rows are written by the XCD that will read them: same L2, no cross-XCD traffic.
   int p, chunk, cb;
   const int nchunk = ka.nchunk;
-  if (ka.gper > 0) {
-    // the GEMM runs one launch per piece of ncbp 128-column blocks (launch_trmm_vsq: at most 512 columns each), every
-    // launch dealing its k ncbp groups to the XCDs in (PC, column block) order, gper per XCD
-    const int xcd = bidx & 7, slot = bidx >> 3;
-    const int half = slot & 1, rest = slot >> 1;
-    chunk = rest % nchunk;
-    const int rest2 = rest / nchunk;
-    const int piece = rest2 / ka.gper, g = xcd * ka.gper + rest2 % ka.gper;
-    p = g / ka.ncbp;
-    cb = 2 * (piece * ka.ncbp + g % ka.ncbp) + half;
+  if (ka.live) {
+    // compacted columns: the unit comes from the table of this launch's live block count (the same dealing as the
+    // GEMM's schedule of that count), and a workgroup beyond its XCD's list has nothing to do
+    const int c = (*ka.live + 63) >> 6;
+    const int e = ka.kmap[(int64_t)(c < 0 ? 0 : (c > ka.ncb64 ? ka.ncb64 : c)) * ka.nwg + bidx];
+    if (e < 0) return;
+    p = e >> 20;
+    chunk = (e >> 8) & 0xfff;
+    cb = e & 0xff;
   } else {
-    cb = bidx % ka.ncb64;
-    const int rest = bidx / ka.ncb64;
-    chunk = rest % nchunk;
-    p = rest / nchunk;
+    const KstarUnit u = kstar_unit(bidx, nchunk, ka.ncb64, ka.gper, ka.ncbp);
+    p = u.p; chunk = u.chunk; cb = u.cb;
   }
   const int64_t b0 = (int64_t)cb * 64;
   const int64_t b = b0 + lane;
@@ -206,7 +232,8 @@ static KstarArgs kstar_setup(gpemu_model *m, int64_t B, double *dXq, int &nwg, b
   const bool xcd_aware = Bv > 128 && ncb64 % 2 == 0 && (ncb64 / 2) % ncbp == 0 && ngroups % 8 == 0 && m->num_cu % 8 == 0;
   const int gper = xcd_aware ? ngroups / 8 : 0;
   return KstarArgs{dXq, m->Xa, m->alf, m->qsc, m->qof, m->etab, m->constv, m->Xs, m->inv_ls, w.KS, w.mean_part,
-                   m->N, m->Npad, w.Bcap, m->has_const, (int)m->d, (int)m->k, w.cur_nchunk, ncb64, gper, ncbp};
+                   m->N, m->Npad, w.Bcap, m->has_const, (int)m->d, (int)m->k, w.cur_nchunk, ncb64, gper, ncbp,
+                   nullptr, nullptr, nwg};
 }
 
 // instances: (ksteps, padded width) = (2, 8) d <= 7, (3, 8) d = 8; (3, 16) d = 9 .. 11, (4, 16) d = 12 .. 15, (5, 16) d = 16;
@@ -223,11 +250,26 @@ static KstarArgs kstar_setup(gpemu_model *m, int64_t B, double *dXq, int &nwg, b
     }                                                                                                     \
   } while (0)
 
-int launch_kstar(gpemu_model *m, int64_t B, double *dXq, hipStream_t st, const ProposeArgs *pa) {
+static int live_deal(gpemu_model *m, int ncb, int form, hipStream_t st, const gpemu_model::LiveDeal **out);
+
+int launch_kstar(gpemu_model *m, int64_t B, double *dXq, hipStream_t st, const ProposeArgs *pa, const LiveCols *lv) {
   const ProposeArgs pargs = pa ? *pa : ProposeArgs();
   int nwg = 0;
   bool small = false;
-  const KstarArgs ka = kstar_setup(m, B, dXq, nwg, small);
+  KstarArgs ka = kstar_setup(m, B, dXq, nwg, small);
+  if (lv) {
+    // compacted columns: the rows are in dXq already, and the workgroup -> unit map of the launch's live block count
+    // comes from the table the GEMM's schedules are in (live_deal)
+    const int ncb = (int)(round_up(B, TILE) / TILE);
+    const gpemu_model::LiveDeal *deal = nullptr;
+    GP_TRY(live_deal(m, ncb, lv->form, st, &deal));
+    if (small || pargs.enabled || pargs.raw || ka.ncb64 != 2 * ncb || ka.ncbp != ncb || deal->nwg != nwg) {
+      set_error("compacted columns: the cross-kernel takes them as one large-batch launch of rows it reads");
+      return GPEMU_ERR_STATE;
+    }
+    ka.live = lv->n_live;
+    ka.kmap = deal->kmap;
+  }
   const dim3 grid((unsigned)nwg), block(256);
   const int pe0 = prof_mark(m, st);
 #define GP_LAUNCH_ONE(KD, KSV, JT, DPV) hipLaunchKernelGGL((kstar_kernel<KD, KSV, JT, 2, DPV>), grid, block, 0, st, ka, pargs)
@@ -306,7 +348,10 @@ typedef __attribute__((address_space(3))) void *las_ptr;
 __global__ __launch_bounds__(512, 2) void trmm_vsq_dma_kernel(
     const double *__restrict__ Wt, const double *__restrict__ KS, double *__restrict__ out,
     const TrmmItem *__restrict__ sched, const int *__restrict__ sched_cnt, int max_items,
-    int64_t Npad, int64_t Bcap, int k, int nrb
+    int64_t Npad, int64_t Bcap, int k, int nrb,
+    // compacted columns (internal.h: LiveCols): sched / sched_cnt hold a schedule for every live block count 0 .. live_max,
+    // one after the other, and the launch takes the one of ceil(*live / 64); null: the one schedule there is
+    const int *__restrict__ live, int live_max
 #ifdef GPEMU_TRMM_STAMPS        // diagnostic build (tools/trmm_balance.py): per-worker time stamps of a launch
     , unsigned long long *__restrict__ stamps
 #endif
@@ -327,6 +372,12 @@ __global__ __launch_bounds__(512, 2) void trmm_vsq_dma_kernel(
 #ifdef GPEMU_TRMM_STAMPS
   if (stamps && tid == 0) stamps[blockIdx.x * 16] = __builtin_amdgcn_s_memrealtime();
 #endif
+  if (live) {
+    int c = (*live + 63) >> 6;
+    c = c < 0 ? 0 : (c > live_max ? live_max : c);
+    sched += (int64_t)c * gridDim.x * max_items;
+    sched_cnt += (int64_t)c * gridDim.x;
+  }
   const int nitems = sched_cnt[blockIdx.x];
   if (tid < nitems) s_items[tid] = sched[(int64_t)blockIdx.x * max_items + tid];
   __syncthreads();
@@ -504,14 +555,27 @@ __global__ __launch_bounds__(512, 2) void trmm_vsq_dma_kernel(
 
 // host side: LPT schedule of the items of one launch shape (cached per model and column-tile count)
 // keep (probes only, tools/share_probe.hip): restrict the launch to the (PC, 64-row block) pairs it accepts
+// live64 >= 0 (the sampler's compacted half-step, live_deal below): only the first live64 64-column blocks hold queries.
+// The 128-column blocks beyond them get no items, and an odd count leaves the last one half filled: all its row blocks
+// are then 64-column items of its left half.  The grid is that of the whole batch (workers), whatever is left to do;
+// form: where the items go (internal.h: LiveCols).  live64 < 0 is the whole batch, as ever.
 static void build_trmm_schedule(gpemu_model *m, int ncb, std::vector<TrmmItem> &flat, std::vector<int> &cnt,
-                                int &max_items, int &nworkers, bool (*keep)(int p, int rb) = nullptr, int split_all = 0) {
+                                int &max_items, int &nworkers, bool (*keep)(int p, int rb) = nullptr, int split_all = 0,
+                                int live64 = -1, int form = 1, int workers = 0) {
   const int nrb = (int)m->vsq_nrb, k = (int)m->k;
-  struct It { double cost; TrmmItem it; };
+  struct It { double cost; TrmmItem it; int xcd; };
   std::vector<It> items;
   // row blocks with short K are issued as two 64-column halves; with one or two column blocks (B <= 256) there
   // are too few items for 256 workers unless every row block is
-  const int split_below = (ncb <= 2 || split_all) ? nrb : nrb / 4;
+  int split_below = (ncb <= 2 || split_all) ? nrb : nrb / 4;
+  if (live64 >= 0 && workers > 0 && split_below < nrb) {
+    // few live blocks: once the longest 128-column item outweighs a worker's share of the whole launch, it alone sets
+    // the launch's time (N = 1000, 10 PCs: 72 us from 2 to 5 of 8 blocks; at 5 the halved items are no faster) -- halve every item then, as at ncb <= 2
+    double total = 0.0;
+    for (int rb = 0; rb < nrb; ++rb) total += 0.5 * k * std::min(live64, 2 * ncb) * (double)(((int64_t)rb * TM + TM + KT - 1) / KT);
+    const double top = (double)(((int64_t)(nrb - 1) * TM + TM + KT - 1) / KT);
+    if (top > 1.3 * total / workers) split_below = nrb;
+  }
   // per-item cost of the epilogue, in k-tiles.  Measured (in-kernel stamps, profiles/r03_trmm_balance.txt): workers with
   // 2 / 3 / 5 items finish at 85.3 / 87.6 / 88.5 us, but raising it to 0.4-0.9 (3 / 4 items everywhere) leaves the slowest
   // worker at 91 us: the spread is the XCDs' (means 86.6-88.2 us), not the cost model's
@@ -521,17 +585,44 @@ static void build_trmm_schedule(gpemu_model *m, int ncb, std::vector<TrmmItem> &
     for (int p = 0; p < k; ++p)
       for (int cb = 0; cb < ncb; ++cb) {
         if (keep && !keep(p, rb)) continue;
-        if (rb < split_below) {
-          items.push_back({0.5 * nt + ov, TrmmItem{p, rb, cb * TILE, 1}});
-          items.push_back({0.5 * nt + ov, TrmmItem{p, rb, cb * TILE + 64, 1}});
+        const int halves = live64 < 0 ? 2 : std::min(2, std::max(0, live64 - 2 * cb));   // live halves of this block
+        if (halves == 0) continue;
+        if (rb < split_below || halves == 1) {
+          items.push_back({0.5 * nt + ov, TrmmItem{p, rb, cb * TILE, 1}, 0});
+          if (halves == 2) items.push_back({0.5 * nt + ov, TrmmItem{p, rb, cb * TILE + 64, 1}, 0});
         } else {
-          items.push_back({nt + ov, TrmmItem{p, rb, cb * TILE, 0}});
+          items.push_back({nt + ov, TrmmItem{p, rb, cb * TILE, 0}, 0});
         }
       }
   }
-  std::stable_sort(items.begin(), items.end(), [](const It &a, const It &b) { return a.cost > b.cost; });
   const int ncu = m->num_cu;
-  nworkers = ncu < (int)items.size() ? ncu : (int)items.size();
+  nworkers = workers > 0 ? workers : (ncu < (int)items.size() ? ncu : (int)items.size());
+  const int nxcd = 8, ngroups = k * ncb;
+  const bool by_xcd = !keep && nworkers == ncu && nworkers % nxcd == 0;
+  const bool by_cost = by_xcd && live64 >= 0 && form == 2;
+  if (by_cost) {
+    // Fewer live blocks than the batch has: the groups that are left no longer divide evenly over the XCDs, and a half
+    // filled block costs half.  The items in (PC, column block, row block) order are cut at eighths of the total cost:
+    // an XCD still works on neighbouring groups, and a group that straddles a cut has its row blocks divided between
+    // two neighbouring XCDs (the cross-kernel's workgroups follow the same order: live_deal)
+    std::vector<int> ord(items.size());
+    for (size_t i = 0; i < ord.size(); ++i) ord[i] = (int)i;
+    std::stable_sort(ord.begin(), ord.end(), [&](int a, int b) {
+      const TrmmItem &x = items[a].it, &y = items[b].it;
+      if (x.p != y.p) return x.p < y.p;
+      if (x.col0 / TILE != y.col0 / TILE) return x.col0 / TILE < y.col0 / TILE;
+      if (x.rb != y.rb) return x.rb < y.rb;
+      return x.col0 < y.col0;
+    });
+    double total = 0.0, run = 0.0;
+    for (const It &x : items) total += x.cost;
+    for (int i : ord) {
+      const int xcd = (int)((run + 0.5 * items[i].cost) * nxcd / total);
+      items[i].xcd = xcd < 0 ? 0 : (xcd > nxcd - 1 ? nxcd - 1 : xcd);
+      run += items[i].cost;
+    }
+  }
+  std::stable_sort(items.begin(), items.end(), [](const It &a, const It &b) { return a.cost > b.cost; });
   std::vector<std::vector<TrmmItem>> per(nworkers);
   std::vector<double> load(nworkers, 0.0);
   // XCD-aware placement.  Workgroups are dispatched round-robin over the 8 XCDs (worker w runs on XCD w % 8),
@@ -540,12 +631,11 @@ static void build_trmm_schedule(gpemu_model *m, int ncb, std::vector<TrmmItem> &
   // dealt to the XCDs in (PC, column block) order -- an XCD then works on at most two or three PCs, and the
   // column-block items of one (PC, row block), equally long, start together and stream the same W rows through
   // that L2 -- and LPT runs within each XCD's workers.  Otherwise: plain LPT over all workers.
-  const int nxcd = 8, ngroups = k * ncb;
-  if (!keep && nworkers == ncu && nworkers % nxcd == 0 && ngroups % nxcd == 0) {
+  if (by_cost || (by_xcd && ngroups % nxcd == 0)) {
     const int gper = ngroups / nxcd;
     for (const It &x : items) {
       const int g = x.it.p * ncb + x.it.col0 / TILE;
-      const int xcd = g / gper;
+      const int xcd = by_cost ? x.xcd : g / gper;
       int best = xcd;
       for (int w = xcd; w < nworkers; w += nxcd)
         if (load[w] < load[best]) best = w;
@@ -571,11 +661,109 @@ static void build_trmm_schedule(gpemu_model *m, int ncb, std::vector<TrmmItem> &
   }
 }
 
-static int launch_trmm_vsq_one(gpemu_model *m, int64_t B, hipStream_t st, bool piece);
+// How the live blocks of a count are dealt where nothing else is asked for (LiveCols::form < 0): measured per count at
+// N = 1000, 10 PCs, 512 columns (tools/time_compact.py, profiles/compact_forms.txt)
+static int live_default_form(int live64, int ncb64) {
+  (void)live64; (void)ncb64;
+  return 2;
+}
 
-int launch_trmm_vsq(gpemu_model *m, int64_t B, hipStream_t st) {
+// The compacted half-step's tables for batches of ncb 128-column blocks: for every live count c = 0 .. 2 ncb the GEMM's
+// schedule (row c of items / cnt, all with the workers and the item stride of the widest) and the cross-kernel's
+// workgroup -> unit map (row c of kmap).  Row 2 ncb is the whole batch's own schedule and map, item for item.  Built
+// once per (model, shape, form) by the first launch that needs it, like the whole batch's schedule.
+static int live_deal(gpemu_model *m, int ncb, int form, hipStream_t st, const gpemu_model::LiveDeal **out) {
+  const int cap = m->num_cu;
+  for (const auto &e : m->live_cache)
+    if (e.ncb == ncb && e.cap == cap && e.form == form) { *out = &e; return GPEMU_OK; }
+  const int k = (int)m->k, ncb64 = 2 * ncb, nchunk = (int)(m->Npad / KSTAR_ROWS_BIG), nwg = ncb64 * nchunk * k;
+  if (k > 64 || nchunk > 4096 || ncb64 > 255) {
+    set_error("compacted half-step: %d PCs x %d row chunks x %d column blocks do not fit the cross-kernel's map", k, nchunk, ncb64);
+    return GPEMU_ERR_UNSUPPORTED;
+  }
+  std::vector<std::vector<TrmmItem>> flats(ncb64 + 1);
+  std::vector<std::vector<int>> cnts(ncb64 + 1);
+  std::vector<int> mx(ncb64 + 1, 1), forms(ncb64 + 1, 0);
+  int workers = 0;
+  build_trmm_schedule(m, ncb, flats[ncb64], cnts[ncb64], mx[ncb64], workers);
+  if (mx[ncb64] > TRMM_MAX_ITEMS) {
+    set_error("triangular GEMM schedule needs %d items per worker (limit %d): batch too large for one launch", mx[ncb64],
+              TRMM_MAX_ITEMS);
+    return GPEMU_ERR_UNSUPPORTED;
+  }
+  const int ngroups = k * ncb;
+  const bool by_xcd = workers == cap && cap % 8 == 0;
+  // the whole batch's map (kstar_setup, one piece)
+  const int gper = (ngroups % 8 == 0 && cap % 8 == 0) ? ngroups / 8 : 0;
+  int stride = mx[ncb64];
+  for (int c = 0; c < ncb64; ++c) {
+    int f = form >= 0 ? form : live_default_form(c, ncb64);
+    const int units = k * c * nchunk;                       // the cross-kernel's workgroups with work
+    if (f == 2 && (!by_xcd || (units + 7) / 8 * 8 > nwg)) f = 1;
+    if (f != 0) {
+      int nw = 0;
+      build_trmm_schedule(m, ncb, flats[c], cnts[c], mx[c], nw, nullptr, 0, c, f, workers);
+      if (mx[c] > TRMM_MAX_ITEMS) f = 0;
+    }
+    if (f == 0) { flats[c] = flats[ncb64]; cnts[c] = cnts[ncb64]; mx[c] = mx[ncb64]; }
+    forms[c] = f;
+    stride = std::max(stride, mx[c]);
+  }
+  std::vector<TrmmItem> items((size_t)(ncb64 + 1) * workers * stride, TrmmItem{0, 0, 0, 0});
+  std::vector<int> cnt((size_t)(ncb64 + 1) * workers, 0), kmap((size_t)(ncb64 + 1) * nwg, -1);
+  for (int c = 0; c <= ncb64; ++c) {
+    for (int w = 0; w < workers; ++w) {
+      cnt[(size_t)c * workers + w] = cnts[c][w];
+      for (int i = 0; i < cnts[c][w]; ++i)
+        items[((size_t)c * workers + w) * stride + i] = flats[c][(size_t)w * mx[c] + i];
+    }
+    int *row = kmap.data() + (size_t)c * nwg;
+    if (forms[c] == 2) {
+      // the units in (PC, 128-column block, row chunk, half) order, an eighth of them to each XCD (workgroup i runs on
+      // XCD i % 8), in that order: the GEMM's cuts, to within the group that straddles one
+      std::vector<int> list;
+      for (int p = 0; p < k; ++p)
+        for (int cb = 0; cb < ncb; ++cb)
+          for (int ch = 0; ch < nchunk; ++ch)
+            for (int h = 0; h < 2; ++h)
+              if (2 * cb + h < c) list.push_back(kstar_pack(KstarUnit{p, ch, 2 * cb + h}));
+      const int n = (int)list.size(), per = (n + 7) / 8;
+      for (int i = 0; i < n; ++i) row[(i % per) * 8 + i / per] = list[i];
+    } else {
+      for (int i = 0; i < nwg; ++i) {
+        const KstarUnit u = kstar_unit(i, nchunk, ncb64, gper, ncb);
+        if (u.cb < c) row[i] = kstar_pack(u);
+      }
+    }
+  }
+  DevScope sc(st);   // owns the new entry until it is complete
+  TrmmItem *ditems = nullptr;
+  int *dcnt = nullptr, *dkmap = nullptr;
+  GP_TRY(sc.alloc(&ditems, (int64_t)items.size()));
+  GP_TRY(sc.alloc(&dcnt, (int64_t)cnt.size()));
+  GP_TRY(sc.alloc(&dkmap, (int64_t)kmap.size()));
+  GP_HIP(hipMemcpy(ditems, items.data(), sizeof(TrmmItem) * items.size(), hipMemcpyHostToDevice));
+  GP_HIP(hipMemcpy(dcnt, cnt.data(), sizeof(int) * cnt.size(), hipMemcpyHostToDevice));
+  GP_HIP(hipMemcpy(dkmap, kmap.data(), sizeof(int) * kmap.size(), hipMemcpyHostToDevice));
+  m->live_cache.push_back({ncb, cap, form, sc.release(ditems), sc.release(dcnt), sc.release(dkmap), stride, workers, nwg});
+  *out = &m->live_cache.back();
+  return GPEMU_OK;
+}
+
+int prepare_live_cols(gpemu_model *m, int64_t B, int form, hipStream_t st) {
+  const gpemu_model::LiveDeal *deal = nullptr;
+  return live_deal(m, (int)(round_up(B, TILE) / TILE), form, st, &deal);
+}
+
+static int launch_trmm_vsq_one(gpemu_model *m, int64_t B, hipStream_t st, bool piece, const LiveCols *lv = nullptr);
+
+int launch_trmm_vsq(gpemu_model *m, int64_t B, hipStream_t st, const LiveCols *lv) {
   Workspace &w = m->ws;
   const int64_t per = trmm_piece_cols(m, B);
+  if (lv && (per < round_up(B, TILE) || (m->variant_B > 0 ? m->variant_B : B) <= 128)) {
+    set_error("compacted columns: the triangular GEMM takes them as one large-batch launch");   // (the sampler's eligibility test)
+    return GPEMU_ERR_STATE;
+  }
   if (per < round_up(B, TILE)) {     // one launch per piece; the column partials of a piece land where a single launch would put them
     path_count(GPEMU_PATH_TRMM_DMA_PIECES);
     double *const KS0 = w.KS, *const V0 = w.vsq_part;
@@ -589,11 +777,11 @@ int launch_trmm_vsq(gpemu_model *m, int64_t B, hipStream_t st) {
     w.vsq_part = V0;
     return rc;
   }
-  return launch_trmm_vsq_one(m, B, st, false);
+  return launch_trmm_vsq_one(m, B, st, false, lv);
 }
 
 // one launch of the triangular GEMM for B columns (a whole batch, or one piece of it)
-static int launch_trmm_vsq_one(gpemu_model *m, int64_t B, hipStream_t st, bool piece) {
+static int launch_trmm_vsq_one(gpemu_model *m, int64_t B, hipStream_t st, bool piece, const LiveCols *lv) {
   Workspace &w = m->ws;
   constexpr int64_t smallb_max = 128;
   const int64_t Bv = m->variant_B > 0 ? m->variant_B : B;   // a chain stacked with others is evaluated as it would be alone
@@ -643,6 +831,17 @@ static int launch_trmm_vsq_one(gpemu_model *m, int64_t B, hipStream_t st, bool p
   // build_trmm_schedule's XCD-aware placement: every CU a worker, whole groups per XCD
   const bool xcd = m->sched_workers == cap && cap % 8 == 0 && ((int)m->k * ncb) % 8 == 0;
   path_count(xcd ? GPEMU_PATH_TRMM_DMA_XCD : GPEMU_PATH_TRMM_DMA_LPT);
+  // compacted columns: the schedules of every live block count, the launch's own picked on the device; the grid, the
+  // path counters and the event pair are the whole batch's
+  const TrmmItem *items = (const TrmmItem *)m->sched_items;
+  const int *cnts = m->sched_cnt, *live = nullptr;
+  int max_items = m->sched_max_items, workers = m->sched_workers;
+  if (lv) {
+    const gpemu_model::LiveDeal *deal = nullptr;
+    GP_TRY(live_deal(m, ncb, lv->form, st, &deal));
+    items = (const TrmmItem *)deal->items; cnts = deal->cnt; max_items = deal->max_items; workers = deal->workers;
+    live = lv->n_live;
+  }
   const int pe0 = prof_mark(m, st);
 #ifdef GPEMU_TRMM_STAMPS
   // diagnostic build only (make STAMPS=1; tools/trmm_balance.py): per-worker time stamps of launch 600, dumped to the
@@ -654,9 +853,9 @@ static int launch_trmm_vsq_one(gpemu_model *m, int64_t B, hipStream_t st, bool p
     GP_TRY(dev_alloc(&dstamps, 16 * 1024));
     GP_HIP(hipMemset(dstamps, 0, sizeof(unsigned long long) * 16 * 1024));
   }
-  hipLaunchKernelGGL(trmm_vsq_dma_kernel, dim3((unsigned)m->sched_workers), dim3(512), 0, st, m->Wt,
-                     w.KS, w.vsq_part, (const TrmmItem *)m->sched_items, m->sched_cnt, m->sched_max_items,
-                     m->Npad, w.Bcap, (int)m->k, nrb, dstamps);
+  hipLaunchKernelGGL(trmm_vsq_dma_kernel, dim3((unsigned)workers), dim3(512), 0, st, m->Wt,
+                     w.KS, w.vsq_part, items, cnts, max_items,
+                     m->Npad, w.Bcap, (int)m->k, nrb, live, 2 * ncb, dstamps);
   GP_HIP(hipGetLastError());
   prof_pair(m, 0, pe0, prof_mark(m, st));
   if (stamp_path && ++stamp_calls == 600) {
@@ -677,9 +876,9 @@ static int launch_trmm_vsq_one(gpemu_model *m, int64_t B, hipStream_t st, bool p
     }
   }
 #else
-  hipLaunchKernelGGL(trmm_vsq_dma_kernel, dim3((unsigned)m->sched_workers), dim3(512), 0, st, m->Wt,
-                     w.KS, w.vsq_part, (const TrmmItem *)m->sched_items, m->sched_cnt, m->sched_max_items,
-                     m->Npad, w.Bcap, (int)m->k, nrb);
+  hipLaunchKernelGGL(trmm_vsq_dma_kernel, dim3((unsigned)workers), dim3(512), 0, st, m->Wt,
+                     w.KS, w.vsq_part, items, cnts, max_items,
+                     m->Npad, w.Bcap, (int)m->k, nrb, live, 2 * ncb);
   GP_HIP(hipGetLastError());
   prof_pair(m, 0, pe0, prof_mark(m, st));
 #endif

@@ -199,6 +199,72 @@ __global__ void accept_kernel(double *__restrict__ X, double *__restrict__ logp,
   if (lpchain) lpchain[w] = acc ? nlp : oldlp;
 }
 
+// The compacted half-step's first launch: forms the n proposals of a chunk (the arithmetic of the cross-kernel's fused
+// proposal, predict_dev.h / k_predict.hip: kstar_body), tests each against the strict prior box (loglik_dev.h:
+// inside_box) and writes those inside, in their order, as rows 0 .. n_live - 1 of the padded query buffer, followed by
+// zero rows up to the next multiple of 128.  A proposal outside the box is rejected whatever the emulators say (ref:
+// log_posterior.py:63-64), so the cross-kernel and the triangular GEMM that follow serve the live rows only.  One
+// workgroup; the ranks are a stable prefix sum (ballots within a wave, the waves' counts through LDS).
+template <int DP>
+__global__ __launch_bounds__(1024) void propose_compact_kernel(ProposeArgs pa, const double *__restrict__ lo,
+                                                               const double *__restrict__ hi, double *__restrict__ Xq,
+                                                               int *__restrict__ slot_of, int *__restrict__ n_live,
+                                                               long long *__restrict__ live_cnt,
+                                                               long long *__restrict__ model_cnt) {
+  __shared__ int wcnt[16];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  int base = 0;
+  for (int c0 = 0; c0 < pa.n; c0 += 1024) {
+    const int i = c0 + tid;
+    bool in = false;
+    double q[DP];
+#pragma unroll
+    for (int c = 0; c < DP; ++c) q[c] = 0.0;
+    if (i < pa.n) {
+      const int w = pa.idx_s[i], j = pa.partner[i];
+      const double z = pa.zz[i];
+      in = true;
+#pragma unroll
+      for (int c = 0; c < DP; ++c) {
+        if (c < pa.d) {
+          const double cj = pa.X[(int64_t)j * DP + c], sw = pa.X[(int64_t)w * DP + c];
+          q[c] = cj - (cj - sw) * z;                 // emcee moves/stretch.py get_proposal
+          in = in && (q[c] > lo[c]) && (q[c] < hi[c]);
+        }
+      }
+      pa.factors[i] = (pa.d - 1.0) * log(z);
+    }
+    const unsigned long long bal = __ballot(in);
+    if (lane == 0) wcnt[wave] = __popcll(bal);
+    __syncthreads();
+    int off = base, tot = 0;
+    for (int v = 0; v < 16; ++v) {
+      if (v < wave) off += wcnt[v];
+      tot += wcnt[v];
+    }
+    if (i < pa.n) {
+      const int slot = in ? off + __popcll(bal & ((1ull << lane) - 1ull)) : -1;
+      slot_of[i] = slot;
+      if (in) {
+#pragma unroll
+        for (int c = 0; c < DP; ++c) Xq[(int64_t)slot * DP + c] = q[c];
+      }
+    }
+    base += tot;
+    __syncthreads();
+  }
+  const int pad_end = (base + 127) / 128 * 128;
+  for (int e = base * DP + tid; e < pad_end * DP; e += 1024) Xq[e] = 0.0;
+  if (tid == 0) {
+    *n_live = base;
+    live_cnt[0] += base;
+    live_cnt[1] += pa.n;
+    // (gpemu_model_profile_read's entry, since profiling was last switched: samplers on other streams add here too)
+    atomicAdd((unsigned long long *)model_cnt, (unsigned long long)base);
+    atomicAdd((unsigned long long *)model_cnt + 1, (unsigned long long)pa.n);
+  }
+}
+
 template <int DP>
 __global__ void pad_rows_kernel(const double *__restrict__ src, double *__restrict__ dst, int n, int d) {
   int idx = blockIdx.x * blockDim.x + threadIdx.x;
@@ -314,7 +380,7 @@ static int half_step_fused(gpemu_sampler *s, int h, int store_chain, hipStream_t
   const int64_t chunk_max = (per_chain <= 128) ? 1024 : 2048;
   for (int64_t lo = 0; lo < n; lo += chunk_max) {
     const int64_t nb = std::min<int64_t>(chunk_max, n - lo);
-    const ProposeArgs pa = propose_args(s, h, lo, nb);
+    ProposeArgs pa = propose_args(s, h, lo, nb);
     AcceptArgs aa;
     aa.enabled = 1;
     aa.X = s->X; aa.logp = s->logp;
@@ -331,7 +397,31 @@ static int half_step_fused(gpemu_sampler *s, int h, int store_chain, hipStream_t
       aa.lpchain = s->lpchain + s->chain_len * s->W;
     }
     for (gpemu_model *m : s->groups) m->variant_B = per_chain;
-    const int rc = logpost_eval(s->groups.data(), (int)s->groups.size(), nb, s->q, s->newlp + lo, st, sw, &aa, &pa);
+    // Compacted form (the switch, one untempered chain, one group without correlated sources, the large-batch GEMM, the
+    // likelihood of one wave per proposal): the proposals are formed and tested against the prior box first, and the
+    // launches below evaluate those inside it only.  The same bits as the form that evaluates all of them.
+    // The tables are the ones built when the sampler was created (a cache hit); a shape they cannot describe, or a form
+    // asked for since, is settled here, before anything is launched: the chunk then takes the uncompacted form.
+    LiveCols lv;
+    bool compact = sw.compact && s->nchains == 1 && !s->tempered && s->groups.size() == 1 && s->groups[0]->n_src == 0 &&
+                   per_chain > 128 && nb > 128 && !loglik_tasks_fit(s->groups.data(), 1, nb, &aa, sw);
+    if (compact) {
+      const int rc = prepare_live_cols(s->groups[0], nb, sw.compact_form, st);
+      if (rc == GPEMU_ERR_UNSUPPORTED) compact = false;
+      else if (rc != GPEMU_OK) { for (gpemu_model *m : s->groups) m->variant_B = 0; return rc; }
+    }
+    if (compact) {
+      const gpemu_model *m0 = s->groups[0];
+      hipLaunchKernelGGL(s->dp == DPAD ? propose_compact_kernel<DPAD> : propose_compact_kernel<DPAD_WIDE>, dim3(1), dim3(1024),
+                         0, st, pa, m0->lo, m0->hi, s->q, s->slot_of, s->n_live, s->live_cnt, m0->live_cnt);
+      GP_HIP(hipGetLastError());
+      pa = ProposeArgs();                  // the cross-kernel reads the rows
+      aa.slot_of = s->slot_of;
+      lv.n_live = s->n_live;
+      lv.form = sw.compact_form;
+    }
+    const int rc = logpost_eval(s->groups.data(), (int)s->groups.size(), nb, s->q, s->newlp + lo, st, sw, &aa, &pa,
+                                compact ? &lv : nullptr);
     for (gpemu_model *m : s->groups) m->variant_B = 0;
     if (rc != GPEMU_OK) return rc;
   }
@@ -385,6 +475,9 @@ static int sampler_fill(gpemu_sampler *s, const uint64_t *seeds) {
   GP_TRY(dev_alloc(&s->naccept, W));
   GP_TRY(dev_alloc(&s->flags, 2));
   GP_TRY(dev_alloc(&s->seeds, n_chains));
+  GP_TRY(dev_alloc(&s->slot_of, s->qcap));
+  GP_TRY(dev_alloc(&s->n_live, 1));
+  GP_TRY(dev_alloc(&s->live_cnt, 2));
   GP_HIP(hipMemcpy(s->seeds, seeds, sizeof(unsigned long long) * n_chains, hipMemcpyHostToDevice));
   s->X = s->Xbuf; s->logp = s->lpbuf; s->cur = 0;
 
@@ -393,6 +486,9 @@ static int sampler_fill(gpemu_sampler *s, const uint64_t *seeds) {
   GP_HIP(hipMemsetAsync(s->lpbuf, 0, sizeof(double) * 2 * W, s->stream));
   GP_HIP(hipMemsetAsync(s->naccept, 0, sizeof(long long) * W, s->stream));
   GP_HIP(hipMemsetAsync(s->flags, 0, sizeof(int) * 2, s->stream));
+  GP_HIP(hipMemsetAsync(s->slot_of, 0, sizeof(int) * s->qcap, s->stream));
+  GP_HIP(hipMemsetAsync(s->n_live, 0, sizeof(int), s->stream));
+  GP_HIP(hipMemsetAsync(s->live_cnt, 0, sizeof(long long) * 2, s->stream));
   GP_HIP(hipMemsetAsync(s->Xbuf, 0, sizeof(double) * 2 * W * dp, s->stream));
   GP_HIP(hipStreamSynchronize(s->stream));
   return GPEMU_OK;
@@ -433,7 +529,18 @@ int gpemu_sampler_create_chains(gpemu_sampler **out, gpemu_model *const *groups,
   s->ns[0] = (Wc + 1) / 2 * n_chains; s->ns[1] = Wc / 2 * n_chains;     // proposals of a half, chain after chain
   s->qcap = round_up(s->ns[0], TILE) + TILE;
   s->stream = groups[0]->stream;
-  const int rc = sampler_fill(s, seeds);
+  int rc = sampler_fill(s, seeds);
+  // the compacted half-step's tables for every chunk shape of this sampler (half_step_fused), built here and not in
+  // a run; a shape they cannot describe runs uncompacted
+  if (rc == GPEMU_OK && n_chains == 1 && n_groups == 1 && groups[0]->n_src == 0 && getenv("GPEMU_NO_COMPACT") == nullptr) {
+    const LaunchSwitches sw = read_launch_switches();
+    for (int h = 0; h < 2 && rc == GPEMU_OK; ++h)
+      for (int64_t lo = 0; lo < s->ns[h] && rc == GPEMU_OK; lo += 2048) {
+        const int64_t nb = std::min<int64_t>(2048, s->ns[h] - lo);
+        if (s->ns[h] > 128 && nb > 128) rc = prepare_live_cols(groups[0], nb, sw.compact_form, s->stream);
+        if (rc == GPEMU_ERR_UNSUPPORTED) rc = GPEMU_OK;
+      }
+  }
   if (rc != GPEMU_OK) {
     gpemu_sampler_destroy(s);
     return rc;
@@ -453,6 +560,7 @@ int gpemu_sampler_destroy(gpemu_sampler *s) {
   dev_free(s->zz); dev_free(s->logu); dev_free(s->rint); dev_free(s->q);
   dev_free(s->factors); dev_free(s->newlp); dev_free(s->naccept); dev_free(s->flags);
   dev_free(s->chain); dev_free(s->lpchain);
+  dev_free(s->slot_of); dev_free(s->n_live); dev_free(s->live_cnt);
   dev_free(s->snapX); dev_free(s->snaplp); dev_free(s->snapacc); dev_free(s->snapswap);
   dev_free(s->acf_part); dev_free(s->acf_acf); dev_free(s->acf_mean); dev_free(s->acf_acf0);
   dev_free(s->betas); dev_free(s->nswap_acc); dev_free(s->nswap_try); dev_free(s->mean_ll);
@@ -702,6 +810,17 @@ int gpemu_sampler_get_chain_walkers(gpemu_sampler *s, int64_t first, int64_t n, 
     GP_HIP(hipMemcpy2DAsync(logp_out, sizeof(double) * nw, s->lpchain + first * W + w0, sizeof(double) * W,
                             sizeof(double) * nw, (size_t)n, hipMemcpyDeviceToHost, s->stream));
   GP_HIP(hipStreamSynchronize(s->stream));
+  return GPEMU_OK;
+}
+
+int gpemu_sampler_live_counts(gpemu_sampler *s, int64_t *live_proposals) {
+  GP_ARG(s && live_proposals, "null pointer");
+  GP_HIP(hipSetDevice(s->device));
+  long long h[2] = {0, 0};
+  GP_HIP(hipMemcpyAsync(h, s->live_cnt, sizeof(h), hipMemcpyDeviceToHost, s->stream));
+  GP_HIP(hipStreamSynchronize(s->stream));
+  live_proposals[0] = h[0];
+  live_proposals[1] = h[1];
   return GPEMU_OK;
 }
 

@@ -75,8 +75,10 @@ struct AcceptOperands {
   int w = 0;
   double oldlp = 0.0, factor = 0.0, logu = 0.0, xold = 0.0, xnew = 0.0;
 };
+// col: the column that holds proposal b's query row (b itself but for the sampler's compacted half-step,
+// AcceptArgs::slot_of; a proposal without a column is never accepted, so that its xnew is not read)
 __device__ __forceinline__ AcceptOperands load_accept_operands(const double *__restrict__ Xq, int64_t b, int lane,
-                                                               const AcceptArgs &aa) {
+                                                               const AcceptArgs &aa, int64_t col) {
   AcceptOperands ao;
   if (!aa.enabled) return ao;
   ao.w = aa.idx_s[b];
@@ -85,9 +87,13 @@ __device__ __forceinline__ AcceptOperands load_accept_operands(const double *__r
   ao.logu = aa.logu[b];
   if (lane < aa.dp) {
     ao.xold = aa.X[(int64_t)ao.w * aa.dp + lane];
-    ao.xnew = Xq[b * aa.dp + lane];
+    if (col >= 0) ao.xnew = Xq[col * aa.dp + lane];
   }
   return ao;
+}
+__device__ __forceinline__ AcceptOperands load_accept_operands(const double *__restrict__ Xq, int64_t b, int lane,
+                                                               const AcceptArgs &aa) {
+  return load_accept_operands(Xq, b, lane, aa, b);
 }
 
 __device__ __forceinline__ void finish_walker(double total, double *__restrict__ out, int64_t b, int d, int lane,

@@ -98,6 +98,11 @@ struct gpemu_sampler {
   double *newlp = nullptr;     // [qcap]
   long long *naccept = nullptr;  // [W]
   int *flags = nullptr;        // [1] count of NaN log-probabilities seen
+  // compacted half-step (k_sampler.hip: propose_compact_kernel): the proposals inside the prior box, in their order, are
+  // rows 0 .. *n_live - 1 of q, and only they are evaluated
+  int *slot_of = nullptr;      // [qcap] row of proposal i of the chunk in flight, -1 outside the box
+  int *n_live = nullptr;       // [1]    rows of q that hold proposals
+  long long *live_cnt = nullptr;   // [2] proposals inside the box / proposals, over every compacted chunk so far
   double *chain = nullptr;     // [chain_cap][W][d]
   double *lpchain = nullptr;   // [chain_cap][W]
   int64_t chain_cap = 0, chain_len = 0;

@@ -149,7 +149,7 @@ int main(int argc, char **argv) {
       upload_sched(flat.data(), sizeof(TrmmItem) * flat.size(), cnt, &ditems, &dcnt);
       t[variant] = time_us([&] {
         hipLaunchKernelGGL(trmm_vsq_dma_kernel, dim3((unsigned)nworkers), dim3(512), 0, sA, m.Wt, w.KS, w.vsq_part,
-                           (const TrmmItem *)ditems, dcnt, max_items, Npad, Bcap, (int)k, (int)m.vsq_nrb);
+                           (const TrmmItem *)ditems, dcnt, max_items, Npad, Bcap, (int)k, (int)m.vsq_nrb, nullptr, 0);
       }, sA, 200, 300);
       for (int c : cnt) nit[variant] += c;
       nwk[variant] = nworkers; mx[variant] = max_items;

@@ -79,11 +79,15 @@ class DeviceModel:
         check(_lib.lib().gpemu_model_profile(self._h, int(bool(enable))))
 
     def profile_read(self):
-        """{'trmm_vsq': (ms_total, launches), 'kstar': (ms_total, launches)}"""
+        """{'trmm_vsq': (ms_total, launches), 'kstar': (ms_total, launches), 'live': (proposals inside the prior box,
+        proposals) of the samplers' compacted half-steps since ``profile`` was called (``DeviceSampler.live_fraction``)}"""
         ms = np.zeros(2)
         n = np.zeros(2, dtype=np.int64)
+        live = np.zeros(2, dtype=np.int64)
         check(_lib.lib().gpemu_model_profile_read(self._h, ptr(ms), ptr(n)))
-        return {"trmm_vsq": (float(ms[0]), int(n[0])), "kstar": (float(ms[1]), int(n[1]))}
+        check(_lib.lib().gpemu_model_live_counts(self._h, ptr(live)))
+        return {"trmm_vsq": (float(ms[0]), int(n[0])), "kstar": (float(ms[1]), int(n[1])),
+                "live": (int(live[0]), int(live[1]))}
 
     # -- host-buffer API -----------------------------------------------------------------------
     def _X(self, X):

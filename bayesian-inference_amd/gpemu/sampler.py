@@ -209,6 +209,23 @@ class DeviceSampler:
         check(_lib.lib().gpemu_sampler_get_counts(self._h, ptr(nacc), C.byref(it), C.byref(cl)))
         return nacc, int(it.value), int(cl.value)
 
+    @property
+    def live_counts(self):
+        """``(live, proposals)``: of the ``proposals`` stretch proposals the compacted half-step has formed since the
+        sampler was created, the ``live`` ones lay inside the prior box and were evaluated.  ``(0, 0)`` where the
+        half-step does not compact (stacked or tempered chains, several groups, correlated sources, halves of at most
+        128 proposals, ``GPEMU_NO_COMPACT=1``)."""
+        out = np.zeros(2, dtype=np.int64)
+        check(_lib.lib().gpemu_sampler_live_counts(self._h, ptr(out)))
+        return int(out[0]), int(out[1])
+
+    @property
+    def live_fraction(self):
+        """Share of the compacted half-steps' proposals that lay inside the prior box (``live_counts``); ``None`` where
+        nothing was compacted."""
+        live, n = self.live_counts
+        return live / n if n else None
+
     def get_chain(self, first=0, n=None):
         _, _, cl = self.counts()
         n = cl - first if n is None else n

@@ -330,6 +330,12 @@ int gpemu_sampler_get_chain_walkers(gpemu_sampler *s, int64_t first, int64_t n, 
                                     double *chain_out, double *logp_out);
 int gpemu_sampler_get_counts(gpemu_sampler *s, int64_t *naccepted /*[W]*/, int64_t *iterations,
                              int64_t *chain_len);
+/* The compacted half-step (one untempered chain, one group without correlated sources, halves of more than 128
+ * proposals; GPEMU_NO_COMPACT=1 turns it off) evaluates only the proposals inside the prior box: live_proposals[0] of
+ * the live_proposals[1] proposals it has formed since the sampler was created.  Both 0: nothing went that way. */
+int gpemu_sampler_live_counts(gpemu_sampler *s, int64_t *live_proposals /*[2]*/);
+/* the same over every sampler of this model, since gpemu_model_profile was last called (either way) */
+int gpemu_model_live_counts(gpemu_model *m, int64_t *live_proposals /*[2]*/);
 /* Walker-averaged normalised autocorrelation function of the stored chain rows [first, first + n_steps), walkers
  * [w0, w0 + nw) (a chain of a stacked sampler), lags [lag0, lag0 + n_lags): f_out[n_lags][d],
  *     f[l][dd] = 1/nw sum_w acf_(w,dd)[l] / acf_(w,dd)[0],  acf[l] = sum_t (x[t] - mean)(x[t + l] - mean),
