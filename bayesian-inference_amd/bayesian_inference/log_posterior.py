@@ -218,6 +218,49 @@ def observable_labels():
     return labels
 
 
+def measurement_candidates(scale=1.0, observables=None):
+    """The candidate measurements of ``gpemu.experiment`` that repeat the observables of this analysis
+    independently with ``scale`` times their present uncertainties: one dict per observable label
+    (``observable_labels()``: the blocks ``loo`` uses), or per entry of ``observables`` -- a label, or a list of labels
+    measured together.  ``features`` index the groups' features concatenated in the order of ``device_models()``;
+    ``y_err`` is ``scale * y_err`` of the data, or, where the data has a covariance, ``cov`` is ``scale^2`` times its
+    block (blocks of different observables are independent).  Fully correlated sources are not part of a repeat's own
+    uncertainty and are left out."""
+    scale = float(scale)
+    if not (np.isfinite(scale) and scale > 0.0):
+        raise ValueError(f"scale must be finite and > 0, got {scale!r}")
+    labels = observable_labels()
+    y_err = np.asarray(experimental_results['y_err'], dtype=np.float64)
+    cov = data_covariance()[0]
+    blocks, off = [], 0          # per block: (features in the concatenated order, columns in the merged order)
+    for _, _, cols, starts in _group_layouts():
+        cols = np.asarray(cols)
+        for o in range(len(starts) - 1):
+            a, b = int(starts[o]), int(starts[o + 1])
+            blocks.append((off + np.arange(a, b, dtype=np.int64), cols[a:b]))
+        off += len(cols)
+    if observables is None:
+        classes = [[name] for name in labels]
+    else:
+        classes = [[c] if isinstance(c, str) else list(c) for c in observables]
+        if len(classes) == 0 or any(len(c) == 0 for c in classes):
+            raise ValueError("observables must be a non-empty list of labels or non-empty lists of labels")
+    out = []
+    for names in classes:
+        for name in names:
+            if labels.count(name) != 1:
+                raise ValueError(f"observables names {name!r}; the observables are {labels}")
+        feats = np.concatenate([blocks[labels.index(name)][0] for name in names])
+        cols = np.concatenate([blocks[labels.index(name)][1] for name in names])
+        cand = {'features': feats, 'label': '+'.join(names)}
+        if cov is None:
+            cand['y_err'] = scale * y_err[cols]
+        else:
+            cand['cov'] = (scale * scale) * cov[np.ix_(cols, cols)]
+        out.append(cand)
+    return out
+
+
 def log_likelihood_pointwise(X):
     """``(labels, T)``: ``T (n_obs, n_samples)``, the log-likelihood term of every observable for each row of X -- the
     terms whose sum over the observables is ``log_posterior`` of a single row inside the box (n_div =

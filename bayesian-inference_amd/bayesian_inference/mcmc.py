@@ -209,6 +209,8 @@ def _run_closure_batch(config, indices):
         _add_loo(config, part, lambda c=c, **kw: sampler.loo(chain=c, **kw), label=f'closure chain {indices[c]}')
         _add_information_gain(config, part, lambda c=c, **kw: sampler.information_gain(chain=c, **kw),
                               label=f'closure chain {indices[c]}')
+        _add_expected_information_gain(config, part, lambda c=c, **kw: sampler.expected_information_gain(chain=c, **kw),
+                                       label=f'closure chain {indices[c]}')
         diags.append(part)
     sampler.close()
 
@@ -339,6 +341,8 @@ def run_mcmc(config, closure_index=-1):
     _add_marginals(config, results, sampler.get_marginals)
     _add_loo(config, results, lambda **kw: sampler.get_loo(models=log_posterior.device_models(n_div=1.0), **kw))
     _add_information_gain(config, results, sampler.get_information_gain)
+    _add_expected_information_gain(config, results, lambda **kw: sampler.get_expected_information_gain(
+        models=log_posterior.device_models(n_div=1.0), **kw))
     if closure_index >= 0:
         validation_design = io.design_array_from_h5(config.output_dir, filename='observables.h5', validation_set=True)
         results['design_point'] = validation_design[closure_index]
@@ -468,6 +472,8 @@ def _run_tempered(config, closure_index):
     _add_loo(config, diag, lambda **kw: sampler.loo(temp=0, **kw), label='production chain (beta = 1)')
     _add_information_gain(config, diag, lambda **kw: sampler.information_gain(temp=0, **kw),
                           label='production chain (beta = 1)')
+    _add_expected_information_gain(config, diag, lambda **kw: sampler.expected_information_gain(temp=0, **kw),
+                                   label='production chain (beta = 1)')
     mean_ll = sampler.mean_log_likelihood()
     log_z, dlog_z = sampler.log_evidence_estimate()
     swap_frac = sampler.tswap_acceptance_fraction
@@ -579,6 +585,7 @@ def _run_hmc(config, closure_index):
     _add_marginals(config, diag, sampler.marginals)
     _add_loo(config, diag, sampler.loo)
     _add_information_gain(config, diag, sampler.information_gain)
+    _add_expected_information_gain(config, diag, sampler.expected_information_gain)
     step_size, inverse_metric, divergences = sampler.step_size, sampler.inverse_metric, sampler.divergences
     sampler.close()
 
@@ -964,6 +971,96 @@ def information_gain(config, closure_index=-1, discard=0, thin=1):
         np.ascontiguousarray(chain.reshape(-1, chain.shape[-1])), lower, upper, **kw))
 
 
+def expected_information_gain_settings(mc):
+    """``(on, scale, n_outer, n_inner)`` from the ``parameters.mcmc`` mapping: ``expected_information_gain`` (true or
+    false, default off: the expected information gain of an independent repeat of every observable's measurement),
+    ``eig_scale`` (the repeat's uncertainties as a multiple of the present ones, a number > 0, default 1.0),
+    ``eig_n_outer`` (simulated outcomes, an integer in [1, 2^31), default 4096) and ``eig_n_inner`` (the most evenly
+    spaced rows of the chain in the inner sample, an integer in [2, 2^31), default 16384).  DESIGN.md §4.38."""
+    on = mc.get('expected_information_gain', False)
+    if not isinstance(on, (bool, np.bool_)):
+        raise ValueError(f"parameters.mcmc.expected_information_gain must be true or false, got {on!r}")
+    scale = mc.get('eig_scale', 1.0)
+    if isinstance(scale, (bool, np.bool_)) or not isinstance(scale, (int, float, np.integer, np.floating)) \
+            or not (np.isfinite(scale) and scale > 0):
+        raise ValueError(f"parameters.mcmc.eig_scale must be a finite number > 0, got {scale!r}")
+    n_outer = mc.get('eig_n_outer', 4096)
+    if not isinstance(n_outer, (int, np.integer)) or isinstance(n_outer, (bool, np.bool_)) or not 1 <= n_outer < 2 ** 31:
+        raise ValueError(f"parameters.mcmc.eig_n_outer must be an integer in [1, 2^31), got {n_outer!r}")
+    n_inner = mc.get('eig_n_inner', 16384)
+    if not isinstance(n_inner, (int, np.integer)) or isinstance(n_inner, (bool, np.bool_)) or not 2 <= n_inner < 2 ** 31:
+        raise ValueError(f"parameters.mcmc.eig_n_inner must be an integer in [2, 2^31), got {n_inner!r}")
+    return bool(on), float(scale), int(n_outer), int(n_inner)
+
+
+EIG_KEYS = ('labels', 'nats', 'se', 'ess_mean', 'saturated')
+
+
+def _eig_kwargs(config, scale=None, observables=None):
+    """The arguments of ``DeviceSampler.expected_information_gain`` /
+    ``gpemu.experiment.chain_expected_information_gain`` from the configuration and the pool's state: the candidates
+    (``log_posterior.measurement_candidates``) and the ``eig_*`` settings."""
+    scale = config.eig_scale if scale is None else scale
+    return dict(candidates=log_posterior.measurement_candidates(scale=scale, observables=observables),
+                n_outer=config.eig_n_outer, n_inner=config.eig_n_inner)
+
+
+def _eig_entries(out):
+    """the ``eig_*`` entries of mcmc.h5 from a ranking, in the order of the candidates"""
+    return {'eig_labels': np.array(out['labels']), 'eig_nats': np.asarray(out['eig_nats'], dtype=np.float64),
+            'eig_se': np.asarray(out['se'], dtype=np.float64), 'eig_ess_mean': np.asarray(out['ess_mean'], dtype=np.float64),
+            'eig_saturated': np.asarray(out['saturated'], dtype=np.int64)}
+
+
+def _add_expected_information_gain(config, results, compute, label='production chain'):
+    """With ``parameters.mcmc.expected_information_gain``: the ``eig_*`` entries of ``compute(**kwargs)`` (a sampler's
+    ``expected_information_gain`` on the chain where it lies) into the results that go to mcmc.h5, one log line, and a
+    warning where an estimate is at its cap."""
+    if not getattr(config, 'expected_information_gain', False):
+        return
+    try:
+        out = compute(**_eig_kwargs(config))
+        entries = _eig_entries(out)
+    except Exception as err:         # the chain is worth more than the table: it is written either way
+        logger.warning(f'parameters.mcmc.expected_information_gain: not computed ({err!r}); mcmc.h5 is written without '
+                       'the eig_* entries')
+        return
+    results.update(entries)
+    best = out['table'][0]
+    logger.info(f"Expected information gain of a repeat at {config.eig_scale:g} x the present uncertainties, {label}: most "
+                f"from {best['label']!r} ({best['eig_nats']:.3f} +- {best['se']:.3f} nats) among {len(out['labels'])} "
+                f"observables; {best['n_outer']} outcomes against {best['n_inner']} rows")
+    if np.any(out['saturated']):
+        bad = [str(n) for n, w in zip(out['labels'], out['saturated']) if w]
+        logger.warning(f"expected information gain at its cap (log n_inner - 3, or fewer than 16 effective rows) for {bad}: "
+                       "lower bounds at best; raise parameters.mcmc.eig_n_inner")
+
+
+def expected_information_gain(config, closure_index=-1, discard=0, thin=1, scale=None, observables=None):
+    """The ``eig_*`` entries (``gpemu.experiment``) of the chain stored in mcmc.h5 (of closure chain
+    ``closure_index``, if >= 0), steps ``[discard::thin]``, all walkers: for every observable label (or every entry of
+    ``observables``: a label, or a list of labels measured together) the expected information gain of an independent
+    repeat of that measurement with ``scale`` (default: ``parameters.mcmc.eig_scale``) times its present
+    uncertainties, a dense covariance block where the data has one, the emulators' mean covariance added."""
+    cfg, chain = _stored_chain(config, closure_index, discard, thin)
+    box = cfg.analysis_config['parameterization'][cfg.parameterization]
+    emu_cfg = emulation.EmulationConfig.from_config_file(
+        analysis_name=cfg.analysis_name, parameterization=cfg.parameterization,
+        analysis_config=cfg.analysis_config, config_file=cfg.config_file)
+    emu_results = emu_cfg.read_all_emulator_groups()
+    truncation_cov = emulation.compute_emulator_cov_unexplained(emu_cfg, emu_results)
+    data = _data_IO().data_array_from_h5(cfg.output_dir, 'observables.h5', pseudodata_index=-1,
+                                         observable_filter=emu_cfg.observable_filter)
+    log_posterior.initialize_pool_variables(box['min'], box['max'], emu_cfg, emu_results,
+                                            _with_data_covariance(cfg, data), truncation_cov)
+    from gpemu import experiment as _exp
+    from gpemu.information import selected_rows
+    kw = _eig_kwargs(cfg, scale=scale, observables=observables)
+    rows = np.ascontiguousarray(chain.reshape(-1, chain.shape[-1]))
+    rows = np.ascontiguousarray(rows[selected_rows(rows.shape[0], kw.pop('n_inner'))])
+    return _eig_entries(_exp.chain_expected_information_gain(log_posterior.device_models(n_div=1.0), rows, **kw))
+
+
 def propose_design_points(config, closure_index=-1, discard=0, thin=None, n_points=8, n_reference=4096,
                           n_candidates=2048, candidates=None, seed=0, feature_weights=None, **design_kwargs):
     """``emulation.propose_design_points`` with the chain stored in mcmc.h5 (of closure chain ``closure_index``, if
@@ -1214,6 +1311,10 @@ class MCMCConfig:
         # how many nats the data taught about each parameter, each pair and all of them jointly (optional, default off):
         # information_gain_* in mcmc.h5, none without the key
         self.information_gain, self.information_gain_k, self.information_gain_max_points = information_gain_settings(mc)
+        # which measurement would constrain the parameters most: the expected information gain of an independent repeat
+        # of every observable (optional, default off): eig_* in mcmc.h5, none without the key
+        self.expected_information_gain, self.eig_scale, self.eig_n_outer, self.eig_n_inner = \
+            expected_information_gain_settings(mc)
 
         # <output_dir>/<analysis>_<parameterization>[/closure/results/<index>]/{mcmc.h5, mcmc_sampler.pkl}
         self.output_dir = os.path.join(top['output_dir'], f'{analysis_name}_{parameterization}')

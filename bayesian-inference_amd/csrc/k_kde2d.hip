@@ -225,6 +225,16 @@ __global__ __launch_bounds__(256) void pm_partial_kernel(RowsView v, const doubl
   }
 }
 
+// dmean[d] = the pooled mean of the rows of v -- the first pass of pair_moments_rows, for other files (rows_dev.h);
+// dpart: (rows + MOM_ROWS - 1) / MOM_ROWS * d doubles of scratch; asynchronous on st
+int launch_pooled_mean(const RowsView &v, double *dpart, double *dmean, hipStream_t st) {
+  const int64_t R = v.rows(), nb = (R + MOM_ROWS - 1) / MOM_ROWS;
+  hipLaunchKernelGGL(pm_partial_kernel, dim3((unsigned)nb), dim3(256), 0, st, v, (const double *)nullptr, v.d, dpart);
+  launch_moments_final(dpart, nb, v.d, R, dmean, st);
+  GP_HIP(hipGetLastError());
+  return GPEMU_OK;
+}
+
 // part[(b P + p) 2 + {0, 1}] = the minimum and maximum of shear_v over the rows of block b; NaN is passed over (fmin,
 // fmax)
 __global__ __launch_bounds__(256) void pm_ext_partial_kernel(RowsView v, int P, const int *__restrict__ pairs,

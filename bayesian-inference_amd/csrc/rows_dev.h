@@ -41,6 +41,10 @@ void launch_moments_final(const double *dpart, int64_t nb, int nent, int64_t R, 
 // ... with its scratch, into host mean [d] and var [d]; waits for st
 int moments_to_host(const double *dx, int64_t R, int d, double *mean, double *var, hipStream_t st);
 
+// the pooled mean alone of a view of rows of any width (k_kde2d.hip: pm_partial_kernel, then the final stage above);
+// dpart: (rows + MOM_ROWS - 1) / MOM_ROWS * d doubles of scratch; asynchronous on st
+int launch_pooled_mean(const RowsView &v, double *dpart, double *dmean, hipStream_t st);
+
 // ---- workspace budget ----------------------------------------------------------------------------------------------
 // *budget = workspace_bytes, or half of the free memory of the current device where that is 0
 int workspace_budget(int64_t workspace_bytes, int64_t *budget);

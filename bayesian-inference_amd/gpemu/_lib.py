@@ -220,6 +220,12 @@ _SIGNATURES = {
     "gpemu_knn_logsum_dev": (C.c_int, [C.c_int, c_i64, c_i64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p]),
     "gpemu_knn_path_counts": (C.c_int, [C.POINTER(c_i64), c_i64]),
+    "gpemu_pair_lse": (C.c_int, [C.c_int, c_i64, c_i64, c_i64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, c_i64,
+                                 C.c_void_p, C.c_void_p]),
+    "gpemu_pair_lse_dev": (C.c_int, [C.c_int, c_i64, c_i64, c_i64, C.c_void_p, c_i64, C.c_void_p, c_i64, C.c_void_p,
+                                     C.c_void_p, c_i64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gpemu_pairlse_centre_dev": (C.c_int, [C.c_int, c_i64, c_i64, C.c_void_p, c_i64, C.c_void_p, C.c_void_p]),
+    "gpemu_pairlse_path_counts": (C.c_int, [C.POINTER(c_i64), c_i64]),
 }
 
 

@@ -162,6 +162,21 @@ class DeviceModel:
                                             ptr(cv), ptr(cov)))
         return cv, cov
 
+    def expected_information_gain(self, X, features, y_err=None, cov=None, emulator_cov="mean", n_outer=4096, seed=0,
+                                  exclude_self=False, batch=4096, workspace_bytes=0):
+        """The expected information gain (``gpemu.experiment``) of measuring the observables ``features``
+        (indices into this model's F features) with uncertainty ``y_err`` or ``cov``, given samples ``X (S, d)`` of the
+        parameters: the result dict of ``gpemu.experiment.expected_information_gain`` with ``means`` this emulator's
+        central values at X (``predict_full(n_div=1)``, in batches).  ``emulator_cov='mean'`` adds the average over the
+        rows of the emulator's feature-space covariance (truncation term included) to the measurement's covariance, which
+        stays constant as the estimator requires; ``'none'`` uses the measurement's alone.  A likelihood covariance that
+        depends on theta -- the emulator's own, row by row -- is out of scope."""
+        from . import experiment
+        cand = dict(features=features, y_err=y_err, cov=cov)
+        return experiment.chain_expected_information_gain([self], self._finite(self._X(X)), [cand], n_outer=n_outer,
+                                                          seed=seed, emulator_cov=emulator_cov, exclude_self=exclude_self,
+                                                          batch=batch, workspace_bytes=workspace_bytes)["results"][0]
+
     @staticmethod
     def check_folds(fold, N):
         """The fold labels as an int32 vector [N] and their number; ValueError unless every label is in

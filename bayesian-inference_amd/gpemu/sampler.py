@@ -450,6 +450,28 @@ class DeviceSampler:
         return IG.gain_of_view(self.device, (src, n_blocks, nw, stride), self.d, lower, upper, k=k, subsets=subsets,
                                max_points=max_points, allow_copies=allow_copies, workspace_bytes=workspace_bytes)
 
+    def expected_information_gain(self, candidates, discard=0, thin=1, chain=None, n_inner=16384, n_outer=4096, seed=0,
+                                  emulator_cov="mean", exclude_self=False, models=None, workspace_bytes=0):
+        """Which measurement would constrain the parameters most, given this posterior
+        (``gpemu.experiment.chain_expected_information_gain``): the expected information gain of every
+        candidate (dicts with ``features``, ``y_err`` or ``cov`` and an optional ``label``), compared on common random
+        numbers and sorted.  The inner sample is at most ``n_inner`` evenly spaced rows of the stored chain
+        ``get_chain()[discard::thin].reshape(-1, d)``, gathered where the chain lies; the candidates' features index the
+        features of ``models`` (default: the sampler's groups) concatenated in their order, the order
+        ``emulation.predict`` returns.  Stacked samplers take ``chain=<index>``."""
+        from . import experiment as EX, information as IG
+        models = self.models if models is None else list(models)
+        for m in models:
+            if m.d != self.d or m.device != self.device:
+                raise ValueError("model and sampler differ in parameters or device")
+        src, n_blocks, nw, stride, _ = self._stored_view(discard, thin, chain)
+        rows, skipped = IG.unit_rows_dev(self.device, src, n_blocks, nw, stride, self.d, None, None, int(n_inner))
+        if skipped:
+            raise ValueError(f"{skipped} selected rows of the chain have a non-finite coordinate")
+        return EX.chain_expected_information_gain(models, rows.cpu().numpy(), candidates, n_outer=n_outer, seed=seed,
+                                                  emulator_cov=emulator_cov, exclude_self=exclude_self,
+                                                  workspace_bytes=workspace_bytes)
+
     def kl_divergence(self, other, lower=None, upper=None, k=4, discard=0, thin=1, chain=None, max_points=65536,
                       subsets=None, allow_copies=False, other_chain=None, workspace_bytes=0):
         """``D(this chain || other)`` in nats (``gpemu.information.kl_divergence``) for every subset of
@@ -967,6 +989,10 @@ class TemperedSampler(DeviceSampler):
         """``DeviceSampler.information_gain`` of one rung (default: rung 0, the posterior)."""
         return DeviceSampler.information_gain(self, chain=int(temp), **kw)
 
+    def expected_information_gain(self, candidates, temp=0, **kw):
+        """``DeviceSampler.expected_information_gain`` of one rung (default: rung 0, the posterior)."""
+        return DeviceSampler.expected_information_gain(self, candidates, chain=int(temp), **kw)
+
     def kl_divergence(self, other, temp=0, other_temp=0, **kw):
         """``DeviceSampler.kl_divergence`` of one rung (default: rung 0, the posterior) against ``other``: rung
         ``other_temp`` of another tempered sampler (or of this one: how far a hotter rung is from the posterior), the
@@ -1435,6 +1461,21 @@ class EnsembleSampler:
         lower, upper = kw.pop("lower"), kw.pop("upper")
         return information.information_gain(np.ascontiguousarray(self.get_chain(discard=discard, thin=thin, flat=True)),
                                             lower, upper, **kw)
+
+    def get_expected_information_gain(self, candidates, discard=0, thin=1, models=None, **kw):
+        """``DeviceSampler.expected_information_gain`` of ``get_chain(discard=discard, thin=thin)`` (``n_inner``,
+        ``n_outer``, ``seed``, ``emulator_cov``, ``exclude_self``): the rows gathered in place while the chain still lives
+        on the device, taken from the host copy otherwise (``models`` are then required)."""
+        discard, thin = int(discard), int(thin)
+        if self._impl is not None and getattr(self, "_device", False) and not self.__dict__.get("_frozen"):
+            return self._impl.expected_information_gain(candidates, models=models, discard=discard + thin - 1, thin=thin,
+                                                        **kw)
+        from . import experiment, information
+        if models is None:
+            raise ValueError("the chain is on the host: pass the device models")
+        x = self.get_chain(discard=discard, thin=thin, flat=True)
+        rows = information.selected_rows(x.shape[0], kw.pop("n_inner", 16384))
+        return experiment.chain_expected_information_gain(models, np.ascontiguousarray(x[rows]), candidates, **kw)
 
     # -- pickling (ref: mcmc.py:131-132 pickles the sampler) --------------------------------------
     def __getstate__(self):

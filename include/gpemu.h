@@ -1047,6 +1047,55 @@ enum gpemu_knn_path {
 /* out[0 .. min(n, GPEMU_KNN_PATH_COUNT)) = the counters; returns GPEMU_KNN_PATH_COUNT (or GPEMU_ERR_ARG). */
 int gpemu_knn_path_counts(int64_t *out, int64_t n);
 
+/* ---- row-wise log-sum-exp of pairwise Gaussian log-weights: expected information gain -----------------
+ * Which MEASUREMENT would constrain the parameters most?  With a Gaussian likelihood of constant covariance, whitened
+ * by its Cholesky factor, the nested Monte Carlo estimator of the expected information gain (Ryan 2003; Huan and
+ * Marzouk 2013) needs log (1/S) sum_j exp(-|y_i - z_j|^2 / 2) for n simulated outcomes y_i against S whitened
+ * predictions z_j: n x S x F multiply-adds and n x S exponentials, whose n x S matrix never exists.
+ *
+ * gpemu_pair_lse: rows Y[n*F] and Z[S*F]; a_ij = -|y_i - z_j|^2 / 2; per row i
+ *   lse[i] = m_i + log s1_i,  m_i = max_j a_ij,  s1_i = sum_j exp(a_ij - m_i);
+ *   ess[i] = s1_i^2 / s2_i,   s2_i = sum_j exp(2 (a_ij - m_i)): the effective number of columns that carry row i
+ *            (ess may be NULL).
+ * self (int64 [n], or NULL): pair (i, self[i]) is left out of row i's sums; -1 leaves nothing out.  A row whose every
+ * pair is left out has lse = -inf, ess = 0; no NaN is formed.
+ * The rows are centred first: centre[F] is subtracted from Y and Z alike (one rounded operation per element; distances
+ * are unchanged), and a_ij = y.z - |y_i|^2 / 2 - |z_j|^2 / 2 of the centred rows, y.z on the fp64 matrix cores
+ * (v_mfma_f64_16x16x4_f64, a chain of 4 ceil(F / 4) terms), the half norms one fma chain per row.  The error of a_ij
+ * is absolute, of order u (F + c) (|y_i|^2 + |z_j|^2) / 2 in the centred rows.  centre = NULL: the column means of Z,
+ * by the pooled-moments kernel (gpemu_pairlse_centre_dev gives the same numbers).
+ * A workgroup owns GPEMU_PAIRLSE_TILE_ROWS rows of Y and one chunk of GPEMU_PAIRLSE_CHUNK columns of Z and keeps an
+ * online (m, s1, s2) per row; a second kernel merges the chunks in chunk order.  No floating-point atomics; the chunks
+ * depend on S alone: lse and ess are the same bits for every workspace_bytes and every run.
+ * workspace_bytes bounds the memory of the row blocks in flight, GPEMU_PAIRLSE_BLOCK_BYTES(S, F) each (0 = half of the
+ * free device memory); the blocks go through it in batches; less than one block: GPEMU_ERR_HIP.  The centred copy of Z
+ * (8 S (F + 17) bytes at most) is allocated besides.
+ * GPEMU_ERR_ARG before any launch: n or S outside [1, 2^31); F outside [1, 65536]; a self[i] outside [-1, S); a leading
+ * dimension below F; workspace_bytes < 0; a null Y, Z or lse.
+ * _dev: every array is DEVICE memory (dself, dcentre, dess may be NULL); row i of Y starts at dY + i*ldy, of Z at
+ * dZ + i*ldz; works on `stream` and waits for it (dself is copied to the host and checked first). */
+#define GPEMU_PAIRLSE_CHUNK 2048
+#define GPEMU_PAIRLSE_TILE_ROWS 64
+#define GPEMU_PAIRLSE_BLOCK_BYTES(S, F) \
+  (8LL * GPEMU_PAIRLSE_TILE_ROWS * ((((F) + 15) / 16 * 16 + 1) + 3 * (((S) + GPEMU_PAIRLSE_CHUNK - 1) / GPEMU_PAIRLSE_CHUNK)))
+int gpemu_pair_lse(int device, int64_t n, int64_t S, int64_t F, const double *Y, const double *Z, const int64_t *self,
+                   const double *centre, int64_t workspace_bytes, double *lse, double *ess);
+int gpemu_pair_lse_dev(int device, int64_t n, int64_t S, int64_t F, const double *dY, int64_t ldy, const double *dZ,
+                       int64_t ldz, const int64_t *dself, const double *dcentre, int64_t workspace_bytes, double *dlse,
+                       double *dess, void *stream);
+/* dcentre[F] (DEVICE) = the column means of the device rows dZ: what the calls above subtract where centre is NULL. */
+int gpemu_pairlse_centre_dev(int device, int64_t S, int64_t F, const double *dZ, int64_t ldz, double *dcentre, void *stream);
+/* Which launches ran.  A set of its own: the other sets keep their sizes and indices. */
+enum gpemu_pairlse_path {
+  GPEMU_PAIRLSE_PATH_CENTRE = 0,   /* one launch of the centring pre-pass (Z once, Y once per batch of row blocks)      */
+  GPEMU_PAIRLSE_PATH_PARTIAL,      /* one launch of the partial kernel                                                  */
+  GPEMU_PAIRLSE_PATH_MERGE,        /* one launch of the kernel that merges the chunks' triples                          */
+  GPEMU_PAIRLSE_PATH_ROW_BATCH,    /* one batch of row blocks through the workspace                                     */
+  GPEMU_PAIRLSE_PATH_COUNT
+};
+/* out[0 .. min(n, GPEMU_PAIRLSE_PATH_COUNT)) = the counters; returns GPEMU_PAIRLSE_PATH_COUNT (or GPEMU_ERR_ARG). */
+int gpemu_pairlse_path_counts(int64_t *out, int64_t n);
+
 /* ---- fit handle: test-only entry points ---------------------------------------------------------------------------
  * For the tests of the fit side only; nothing in the library's own flow calls them.
  * gpemu_fit_workspace: out[N*N] = problem z of the last evaluation (gpemu_fit_lml / _lml_batch / _factor) as the
