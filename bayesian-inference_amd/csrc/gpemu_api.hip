@@ -211,6 +211,30 @@ int logpost_eval(gpemu_model *const *ms, int ng, int64_t B, double *dXq, double 
       set_error("groups set up with different numbers of correlated sources (%d and %d)", S, ms[g]->n_src);
       return GPEMU_ERR_STATE;
     }
+  // Stacked chains: a row's chain selects its data vector in a group whose CURRENT setup carries one per chain; a group
+  // set up with one vector serves every chain with it (by_chain_of).  A setup with fewer vectors than the rows have chains
+  // -- changed under a live sampler -- is refused before anything is launched: g0 / scal / w0 end at its last vector.
+  const bool by_chain = aa && aa->chain_per != 0 && aa->chain_data != 0;
+  if (by_chain) {
+    const int64_t last = (aa->first + B - 1) / aa->chain_per;
+    for (int g = 0; g < ng; ++g) {
+      if (ms[g]->lik_chains != 1 && ms[g]->lik_chains <= last) {
+        set_error("group %d is set up with %d data vectors, the sampler's rows reach chain %lld: the likelihood setup "
+                  "changed under a stacked sampler", g, ms[g]->lik_chains, (long long)last);
+        return GPEMU_ERR_STATE;
+      }
+      if (S > 0 && ms[g]->lik_chains != ms[0]->lik_chains) {
+        set_error("groups with correlated sources set up with different numbers of data vectors (%d and %d)",
+                  ms[0]->lik_chains, ms[g]->lik_chains);
+        return GPEMU_ERR_STATE;
+      }
+    }
+  }
+  auto by_chain_of = [&](const gpemu_model *m, const AcceptArgs *a) {
+    AcceptArgs out = *a;
+    if (by_chain && m->lik_chains == 1) out.chain_data = 0;
+    return out;
+  };
   for (int g = 0; g < ng; ++g) GP_TRY(ensure_workspace(ms[g], B));
   // the likelihood stage: observable blocks on different waves where that applies, else one launch for the groups
   auto loglik = [&](gpemu_model *const *gs, int n, int accumulate, const AcceptArgs *a) {
@@ -222,7 +246,12 @@ int logpost_eval(gpemu_model *const *ms, int ng, int64_t B, double *dXq, double 
   if (aa) { chain_only.chain_per = aa->chain_per; chain_only.first = aa->first; chain_only.chain_data = aa->chain_data; }
   // with sources the likelihood stage leaves the accept to the sources' launch
   const AcceptArgs *aa_lik = (S > 0 && aa) ? &chain_only : aa;
-  auto finish = [&]() { return S > 0 ? launch_source_correction(ms, ng, B, dXq, dout, st, aa) : GPEMU_OK; };
+  auto finish = [&]() {
+    if (S == 0) return (int)GPEMU_OK;
+    if (!by_chain) return launch_source_correction(ms, ng, B, dXq, dout, st, aa);
+    const AcceptArgs a0 = by_chain_of(ms[0], aa);
+    return launch_source_correction(ms, ng, B, dXq, dout, st, &a0);
+  };
   const bool one_chain = !(aa && aa->chain_per != 0);
   if (one_chain && halfstep_fits(ms, ng, B, sw)) {
     GP_TRY(launch_halfstep_small(ms, ng, B, dXq, st, pa));
@@ -250,7 +279,10 @@ int logpost_eval(gpemu_model *const *ms, int ng, int64_t B, double *dXq, double 
       GP_TRY(launch_kstar(ms[g], B, dXq, st, pg, lv));
       GP_TRY(launch_trmm_vsq(ms[g], B, st, lv));
     }
-    GP_TRY(loglik(one, 1, g > 0 ? 1 : 0, g + 1 == ng ? aa_lik : (aa ? &chain_only : nullptr)));
+    const AcceptArgs *ag = g + 1 == ng ? aa_lik : (aa ? &chain_only : nullptr);
+    AcceptArgs own;
+    if (by_chain) { own = by_chain_of(ms[g], ag); ag = &own; }
+    GP_TRY(loglik(one, 1, g > 0 ? 1 : 0, ag));
   }
   return finish();
 }

@@ -370,6 +370,27 @@ static ProposeArgs propose_args(gpemu_sampler *s, int h, int64_t lo, int64_t n) 
   return pa;
 }
 
+// The groups' CURRENT likelihood setups against a stacked sampler's chains, asked before a call that evaluates launches or
+// copies anything: a group carries one data vector (it serves every chain) or at least one per chain (chain c reads
+// vector c), and groups with correlated sources carry the same number.  Tempered rungs share vector 0: nothing to ask.
+static int setup_serves_chains(const gpemu_sampler *s) {
+  if (s->nchains == 1 || s->tempered) return GPEMU_OK;
+  for (size_t g = 0; g < s->groups.size(); ++g) {
+    const gpemu_model *m = s->groups[g];
+    if (m->lik_chains != 1 && m->lik_chains < s->nchains) {
+      set_error("group %d is set up with %d data vectors, the sampler has %d chains: the likelihood setup changed under "
+                "a stacked sampler", (int)g, m->lik_chains, s->nchains);
+      return GPEMU_ERR_STATE;
+    }
+    if (m->n_src > 0 && m->lik_chains != s->groups[0]->lik_chains) {
+      set_error("groups with correlated sources set up with different numbers of data vectors (%d and %d)",
+                s->groups[0]->lik_chains, m->lik_chains);
+      return GPEMU_ERR_STATE;
+    }
+  }
+  return GPEMU_OK;
+}
+
 // propose + log-posterior + (fused) accept / record of one half on this device.  Large halves (several chains
 // stacked, or more than 4096 walkers) go through in chunks of proposals: a proposal only reads walkers of the
 // complementary set, which no chunk of this half modifies.  The kernel variants (row-chunk sizes of the partial sums)
@@ -571,6 +592,7 @@ int gpemu_sampler_destroy(gpemu_sampler *s) {
 
 int gpemu_sampler_set_state(gpemu_sampler *s, const double *X0, const double *logp0) {
   GP_ARG(s && X0, "null pointer");
+  if (!s->hmc && !logp0) GP_TRY(setup_serves_chains(s));   // (the walkers are evaluated below)
   GP_HIP(hipSetDevice(s->device));
   hipStream_t st = s->stream;
   const LaunchSwitches sw = read_launch_switches();
@@ -722,6 +744,7 @@ int gpemu_sampler_run(gpemu_sampler *s, int64_t steps, int store_chain) {
   GP_ARG(s && steps >= 0, "sampler / steps");
   GP_HIP(hipSetDevice(s->device));
   if (s->hmc) return hmc_run(s, steps, store_chain);
+  GP_TRY(setup_serves_chains(s));
   hipStream_t st = s->stream;
   const LaunchSwitches sw = read_launch_switches();
   // On one GPU the three-launch half-step below is the faster form (0.2275 vs 0.2516 ms per step at C3,
@@ -744,6 +767,7 @@ int gpemu_sampler_step_host_rng(gpemu_sampler *s, const int32_t *inds, const dou
     set_error("gpemu_sampler_step_host_rng: a tempered sampler draws its randomness on the device (gpemu_sampler_run)");
     return GPEMU_ERR_UNSUPPORTED;
   }
+  GP_TRY(setup_serves_chains(s));
   GP_HIP(hipSetDevice(s->device));
   hipStream_t st = s->stream;
   const LaunchSwitches sw = read_launch_switches();

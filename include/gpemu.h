@@ -75,6 +75,12 @@ int gpemu_device_memory(int device, int64_t *free_bytes, int64_t *total_bytes);
  * The factor is inverted on the device once (W = L^-1) so that prediction is a triangular GEMM.
  * 1 <= d <= 16 (GPEMU_ERR_ARG beyond): d <= 8 runs on 8-wide padded rows, 9 .. 16 on 16-wide ones, whose samplers
  * take the general path (no fused sharded half-step, no small-emulator launch: the sharded run falls back).
+ *
+ * One model serves a whole analysis.  Calls on it may come in any order and from any handle built on it (samplers of
+ * every kind, design handles), one after the other -- not concurrently: the handles share the model's workspace, its
+ * caches and its stream.  What came before does not matter: a call on a used model returns, bit for bit, what the same
+ * call returns on a model created for it alone (tests/test_gpu_handle_reuse.py), and it uses the likelihood setup
+ * current at the call.
  */
 int gpemu_model_create(gpemu_model **out, int device, int64_t N, int64_t d, int64_t F, int64_t k,
                        int kernel_kind, double nu, int has_const, int has_noise,
@@ -133,7 +139,15 @@ int gpemu_model_cross_validate(gpemu_model *m, int64_t n_folds, const int32_t *f
  * features (already gathered into the group's column order).  n_div as above (1 for MCMC).
  * block_start[n_blocks+1]: first feature of every observable of the group (ascending, 0 .. F).
  * The reference's merge keeps only within-observable covariance blocks (ref: emulation.py:370-388),
- * so the likelihood factorises over these blocks.  n_blocks <= 0 or NULL = one block (whole group). */
+ * so the likelihood factorises over these blocks.  n_blocks <= 0 or NULL = one block (whole group).
+ * A setup may be replaced at any time between calls.  Every call uses the setup current at the call: a sampler created
+ * before a new setup and run after it evaluates the new one (its stored log-probabilities are the old setup's until
+ * gpemu_sampler_set_state re-evaluates them).  A stacked sampler reads data vector c for chain c where the current setup
+ * carries at least one per chain and the one vector for every chain where it carries one.  A setup with fewer vectors
+ * than the sampler has chains (but more than one), or groups with correlated sources (n_src > 0) that carry different
+ * numbers of vectors, make gpemu_sampler_set_state (where it evaluates), gpemu_sampler_run and
+ * gpemu_sampler_step_host_rng of that sampler return GPEMU_ERR_STATE before they copy or launch anything: the sampler
+ * is left as it was. */
 int gpemu_likelihood_setup(gpemu_model *m, const double *y_exp, const double *y_err,
                            const double *lo, const double *hi, double n_div, int64_t n_blocks,
                            const int64_t *block_start);
@@ -156,7 +170,8 @@ int gpemu_likelihood_setup_chains(gpemu_model *m, int n_chains, const double *y_
  * sampler over all groups), each group set up with its own columns of the same sources.  With cov = NULL and
  * n_src = 0 this is gpemu_likelihood_setup_chains, bit for bit.  GPEMU_LOGPOST_EXACT reads cov; with n_src > 0 it
  * returns GPEMU_ERR_UNSUPPORTED.  The fused sharded run and the peer transport decline sampler groups with n_src > 0
- * (gpemu_sampler_run_sharded takes the collective transport). */
+ * (gpemu_sampler_run_sharded takes the collective transport).  A stacked sampler over groups with n_src > 0 needs the
+ * same number of data vectors in every group (GPEMU_ERR_STATE from its calls otherwise: gpemu_likelihood_setup). */
 #define GPEMU_MAX_SOURCES 16
 int gpemu_likelihood_setup_cov(gpemu_model *m, int n_chains, const double *y_exp, const double *y_err,
                                const double *cov, int64_t n_src, const double *sources, const double *lo,
