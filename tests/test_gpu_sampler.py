@@ -3,6 +3,7 @@ import numpy as np
 import pytest
 
 import golden_util as GU
+from chain_compare import compare_chains as _compare_chains
 from oracle import gp_oracle as O
 from oracle import sampler_oracle as SO
 
@@ -19,15 +20,6 @@ def _setup(name="g1_rbf_noise"):
         X = np.atleast_2d(X)
         return np.array([O.log_posterior(x, {"g": model}, g["lo"], g["hi"], g["y_exp"], g["y_err"])[0] for x in X])
     return g, model, dm, oracle_lp
-
-
-def _compare_chains(chain, lps, ochain, olps):
-    """Identical accept decisions -> identical positions; a decision can only differ when
-    lnpdiff - log u is within rounding of 0, which does not happen on these seeds."""
-    np.testing.assert_allclose(chain, ochain, rtol=1e-12, atol=1e-12)
-    fin = np.isfinite(olps)
-    assert np.array_equal(fin, np.isfinite(lps))
-    np.testing.assert_allclose(lps[fin], olps[fin], rtol=1e-8)
 
 
 @pytest.mark.parametrize("W,steps", [(12, 12), (24, 12), (33, 12), (130, 8), (1025, 4), (8192, 2)])
