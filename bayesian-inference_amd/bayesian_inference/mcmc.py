@@ -13,6 +13,7 @@ from __future__ import annotations
 import logging
 import os
 import pickle
+import re
 from pathlib import Path
 
 import numpy as np
@@ -207,6 +208,7 @@ def _run_closure_batch(config, indices):
         _add_marginals(config, part, lambda c=c, **kw: sampler.marginals(chain=c, **kw),
                        label=f'closure chain {indices[c]}')
         _add_loo(config, part, lambda c=c, **kw: sampler.loo(chain=c, **kw), label=f'closure chain {indices[c]}')
+        _add_reweight(config, part, lambda c=c, **kw: sampler.reweight(chain=c, **kw), label=f'closure chain {indices[c]}')
         _add_information_gain(config, part, lambda c=c, **kw: sampler.information_gain(chain=c, **kw),
                               label=f'closure chain {indices[c]}')
         _add_expected_information_gain(config, part, lambda c=c, **kw: sampler.expected_information_gain(chain=c, **kw),
@@ -340,6 +342,8 @@ def run_mcmc(config, closure_index=-1):
     _add_diagnostics(config, results, sampler.get_diagnostics)
     _add_marginals(config, results, sampler.get_marginals)
     _add_loo(config, results, lambda **kw: sampler.get_loo(models=log_posterior.device_models(n_div=1.0), **kw))
+    _add_reweight(config, results,
+                  lambda **kw: sampler.get_reweighted(models=log_posterior.device_models(n_div=1.0), **kw))
     _add_information_gain(config, results, sampler.get_information_gain)
     _add_expected_information_gain(config, results, lambda **kw: sampler.get_expected_information_gain(
         models=log_posterior.device_models(n_div=1.0), **kw))
@@ -470,6 +474,7 @@ def _run_tempered(config, closure_index):
     _add_diagnostics(config, diag, lambda: sampler.diagnostics(temp=0), label='production chain (beta = 1)')
     _add_marginals(config, diag, lambda **kw: sampler.marginals(temp=0, **kw), label='production chain (beta = 1)')
     _add_loo(config, diag, lambda **kw: sampler.loo(temp=0, **kw), label='production chain (beta = 1)')
+    _add_reweight(config, diag, lambda **kw: sampler.reweight(temp=0, **kw), label='production chain (beta = 1)')
     _add_information_gain(config, diag, lambda **kw: sampler.information_gain(temp=0, **kw),
                           label='production chain (beta = 1)')
     _add_expected_information_gain(config, diag, lambda **kw: sampler.expected_information_gain(temp=0, **kw),
@@ -584,6 +589,7 @@ def _run_hmc(config, closure_index):
     _add_diagnostics(config, diag, sampler.diagnostics)
     _add_marginals(config, diag, sampler.marginals)
     _add_loo(config, diag, sampler.loo)
+    _add_reweight(config, diag, sampler.reweight)
     _add_information_gain(config, diag, sampler.information_gain)
     _add_expected_information_gain(config, diag, sampler.expected_information_gain)
     step_size, inverse_metric, divergences = sampler.step_size, sampler.inverse_metric, sampler.divergences
@@ -892,6 +898,138 @@ def loo(config, closure_index=-1, discard=0, thin=1):
     out = _loo.chain_loo(log_posterior.device_models(n_div=1.0), np.ascontiguousarray(chain.reshape(-1, chain.shape[-1])),
                          leave_out=rows)
     return _loo_entries(out, labels, rows)
+
+
+def reweight_settings(mc):
+    """The scenarios of ``parameters.mcmc.reweight`` (default: none): ``None`` without the key, else a list of ``(name,
+    priors)``.  The key takes either ``{reference_prior: true}`` -- one scenario ``reference_prior``: log-uniform for
+    every parameter whose name contains ``c_`` (ref: plot_qhat.py:313-316), ``priors`` ``None`` here -- or a list of
+    named scenarios ``{name: <word>, priors: {<parameter name>: {kind: flat | log_uniform | normal | log_normal, a: ..,
+    b: ..}}}`` (``a``, ``b`` for ``normal`` and ``log_normal``); parameters not named stay flat.  DESIGN.md §4.39."""
+    spec = mc.get('reweight')
+    if spec is None or spec is False:
+        return None
+    if isinstance(spec, dict):
+        on = spec.get('reference_prior')
+        if set(spec) != {'reference_prior'} or not isinstance(on, (bool, np.bool_)):
+            raise ValueError(f"parameters.mcmc.reweight must be {{reference_prior: true}} or a list of named scenarios, "
+                             f"got {spec!r}")
+        return [('reference_prior', None)] if on else None
+    if not isinstance(spec, (list, tuple)) or len(spec) == 0:
+        raise ValueError(f"parameters.mcmc.reweight must be {{reference_prior: true}} or a non-empty list of named "
+                         f"scenarios, got {spec!r}")
+    out = []
+    for sc in spec:
+        ok = isinstance(sc, dict) and set(sc) == {'name', 'priors'} and isinstance(sc['name'], str) and \
+            re.fullmatch(r'[A-Za-z0-9_]+', sc['name']) and isinstance(sc['priors'], dict) and len(sc['priors']) > 0
+        if not ok:
+            raise ValueError("every scenario of parameters.mcmc.reweight needs a name (letters, digits, _) and priors, a "
+                             f"mapping from parameter names, got {sc!r}")
+        priors = {}
+        for par, e in sc['priors'].items():
+            if not isinstance(e, dict) or not set(e) <= {'kind', 'a', 'b'} or e.get('kind') not in REWEIGHT_KINDS:
+                raise ValueError(f"scenario {sc['name']!r}: the prior of {par!r} needs a kind among {REWEIGHT_KINDS} and, "
+                                 f"for normal and log_normal, a and b; got {e!r}")
+            if e['kind'] in ('normal', 'log_normal'):
+                a, b = e.get('a'), e.get('b')
+                num = all(isinstance(v, (int, float)) and not isinstance(v, bool) and np.isfinite(v) for v in (a, b))
+                if not num or not b > 0:
+                    raise ValueError(f"scenario {sc['name']!r}: {par!r} needs a finite a and a finite b > 0, got {e!r}")
+            priors[str(par)] = dict(e)
+        if sc['name'] in [n for n, _ in out]:
+            raise ValueError(f"parameters.mcmc.reweight names scenario {sc['name']!r} twice")
+        out.append((sc['name'], priors))
+    return out
+
+
+REWEIGHT_KINDS = ('flat', 'log_uniform', 'normal', 'log_normal')
+REWEIGHT_KEYS = ('pareto_k', 'k_threshold', 'ess_w', 'reliable', 'log_mean_ratio', 'log_evidence_ratio', 'mean', 'sd',
+                 'shift', 'quantiles', 'hist_1d', 'hist_2d', 'hist_1d_q', 'hist_2d_q', 'Q')
+REWEIGHT_SHARED_KEYS = ('probabilities', 'edges_1d', 'edges_2d', 'pairs')
+
+
+def _reweight_kwargs(config, scenarios=None):
+    """``(names, priors, lower, upper)`` for ``DeviceSampler.reweight`` / ``gpemu.reweight.chain_reweight``: the
+    scenarios of the configuration (or ``scenarios``, in ``reweight_settings``' form) by parameter index."""
+    from gpemu import reweight as _rw
+    box = config.analysis_config['parameterization'][config.parameterization]
+    par = [str(n) for n in box['names']]
+    scenarios = config.reweight if scenarios is None else scenarios
+    if not scenarios:
+        raise ValueError('no reweighting scenario')
+    names, priors = [], []
+    for name, spec in scenarios:
+        if spec is None:
+            priors.append(_rw.reference_prior(par))
+        else:
+            row = {}
+            for pname, e in spec.items():
+                if par.count(pname) != 1:
+                    raise ValueError(f"parameters.mcmc.reweight names {pname!r}; the parameters are {par}")
+                row[par.index(pname)] = e
+            priors.append(row)
+        names.append(name)
+    return names, priors, np.asarray(box['min'], dtype=np.float64), np.asarray(box['max'], dtype=np.float64)
+
+
+def _reweight_entries(out, names):
+    """the ``reweight_*`` entries of mcmc.h5 from the scenarios' dicts: ``reweight_names``, the shared
+    ``reweight_probabilities``, ``reweight_edges_1d``, ``reweight_edges_2d``, ``reweight_pairs`` and, per scenario,
+    ``reweight_<name>_<key>`` for the ``REWEIGHT_KEYS`` (``log_evidence_ratio``: NaN where there is none)"""
+    entries = {'reweight_names': np.array(names)}
+    for key in REWEIGHT_SHARED_KEYS:
+        entries[f'reweight_{key}'] = np.asarray(out[0][key])
+    for name, res in zip(names, out):
+        for key in REWEIGHT_KEYS:
+            v = res[key]
+            if key == 'log_evidence_ratio' and v is None:
+                v = np.nan
+            if key == 'Q':
+                v = np.uint64(v)
+            entries[f'reweight_{name}_{key}'] = np.asarray(v)
+    return entries
+
+
+def _add_reweight(config, results, compute, label='production chain'):
+    """With ``parameters.mcmc.reweight``: the ``reweight_*`` entries of ``compute(priors=..., lower=..., upper=...)`` (a
+    sampler's ``reweight`` on the chain where it lies) into the results that go to mcmc.h5, one log line per scenario,
+    and a warning where a Pareto k-hat exceeds its threshold: that scenario needs its own run."""
+    if not getattr(config, 'reweight', None):
+        return
+    try:
+        names, priors, lower, upper = _reweight_kwargs(config)
+        out = compute(priors=priors, lower=lower, upper=upper)
+        entries = _reweight_entries(out, names)
+    except Exception as err:         # the chain is worth more than the table: it is written either way
+        logger.warning(f'parameters.mcmc.reweight: not computed ({err!r}); mcmc.h5 is written without the reweight_* '
+                       'entries')
+        return
+    results.update(entries)
+    for name, res in zip(names, out):
+        logger.info(f"Reweighting of the {label} to {name!r}: Pareto k-hat {res['pareto_k']:.3f}, effective sample size "
+                    f"{res['ess_w']:.1f}, largest shift {np.max(np.abs(res['shift'])):.3f} sd")
+        if not res['reliable']:
+            logger.warning(f"Pareto k-hat {res['pareto_k']:.3f} above {res['k_threshold']:.2f} for scenario {name!r}: the "
+                           "reweighted posterior is not reliable, this scenario needs its own run")
+
+
+def reweight(config, closure_index=-1, discard=0, thin=1, priors=None, reference_prior=False, **summary_kw):
+    """The ``reweight_*`` entries (``gpemu.reweight.summary``) of the chain stored in mcmc.h5 (of closure chain
+    ``closure_index``, if >= 0), steps ``[discard::thin]``, all walkers, inside the configuration's box.  The scenarios
+    are those of ``parameters.mcmc.reweight`` unless ``priors`` (that key's list form) or ``reference_prior=True`` gives
+    others.  ``summary_kw``: ``probabilities``, ``bins_1d``, ``bins_2d``, ``smooth``."""
+    cfg, chain = _stored_chain(config, closure_index, discard, thin)
+    scenarios = None
+    if reference_prior:
+        scenarios = reweight_settings({'reweight': {'reference_prior': True}})
+    elif priors is not None:
+        scenarios = reweight_settings({'reweight': priors})
+    from gpemu import reweight as _rw
+    names, pri, lower, upper = _reweight_kwargs(cfg, scenarios)
+    x = np.ascontiguousarray(chain.reshape(-1, chain.shape[-1]))
+    L = _rw.log_ratio(x, priors=pri, lower=lower, upper=upper)
+    log_norm = _rw.log_prior_norm(*_rw.check_priors(pri, x.shape[1], lower, upper), lower, upper)
+    return _reweight_entries(_rw.summary(x, L, lower, upper, log_norm=log_norm, **summary_kw), names)
 
 
 def information_gain_settings(mc):
@@ -1308,6 +1446,9 @@ class MCMCConfig:
         # per-observable PSIS-LOO / WAIC and the observable-influence table of the production chain (optional, default
         # off): loo_* in mcmc.h5, none without the key
         self.loo, self.loo_leave_out = loo_settings(mc)
+        # the posterior under other priors, from the production chain (optional, default none): reweight_* in mcmc.h5,
+        # none without the key
+        self.reweight = reweight_settings(mc)
         # how many nats the data taught about each parameter, each pair and all of them jointly (optional, default off):
         # information_gain_* in mcmc.h5, none without the key
         self.information_gain, self.information_gain_k, self.information_gain_max_points = information_gain_settings(mc)

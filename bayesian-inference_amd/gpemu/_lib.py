@@ -226,6 +226,22 @@ _SIGNATURES = {
                                      C.c_void_p, c_i64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gpemu_pairlse_centre_dev": (C.c_int, [C.c_int, c_i64, c_i64, C.c_void_p, c_i64, C.c_void_p, C.c_void_p]),
     "gpemu_pairlse_path_counts": (C.c_int, [C.POINTER(c_i64), c_i64]),
+    "gpemu_logprior": (C.c_int, [C.c_int, c_i64, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 5),
+    "gpemu_logprior_dev": (C.c_int, [C.c_int, C.c_void_p, c_i64, c_i64, c_i64, C.c_int, C.c_int] + [C.c_void_p] * 5
+                           + [c_i64, C.c_void_p]),
+    "gpemu_logmeanexp_dev": (C.c_int, [C.c_int, c_i64, c_i64, C.c_void_p, c_i64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gpemu_weights_fixed_dev": (C.c_int, [C.c_int, c_i64, c_i64, C.c_void_p, c_i64, C.c_void_p, c_i64, C.c_void_p,
+                                          C.c_void_p]),
+    "gpemu_weighted_select": (C.c_int, [C.c_int, c_i64, c_i64, C.c_void_p, c_i64, C.c_void_p, c_i64, C.c_void_p,
+                                        C.c_void_p]),
+    "gpemu_weighted_select_dev": (C.c_int, [C.c_int, c_i64, c_i64, C.c_void_p, c_i64, c_i64, c_i64, C.c_void_p, c_i64,
+                                            c_i64, C.c_void_p, C.c_void_p, c_i64, C.c_void_p]),
+    "gpemu_weighted_hist": (C.c_int, [C.c_int, c_i64, C.c_int, C.c_void_p, c_i64, C.c_void_p, C.c_int, C.c_void_p,
+                                      C.c_int, C.c_void_p, c_i64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gpemu_weighted_hist_dev": (C.c_int, [C.c_int, C.c_void_p, c_i64, c_i64, c_i64, C.c_int, c_i64, C.c_void_p, c_i64,
+                                          C.c_int, C.c_void_p, C.c_int, C.c_void_p, c_i64, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p]),
+    "gpemu_reweight_path_counts": (C.c_int, [C.POINTER(c_i64), c_i64]),
 }
 
 

@@ -427,6 +427,43 @@ class DeviceSampler:
         return LO.from_terms(self.device, T, labels, (src, n_blocks, nw, stride), self.d, leave_out, shifts, r_eff,
                              workspace_bytes, baseline=(lambda: self.chain_moments(discard)) if whole else None)
 
+    def reweight(self, priors=None, models_new=None, discard=0, thin=1, chain=None, lower=None, upper=None,
+                 **summary_kw):
+        """The posterior under another prior or under other data, from the stored chain ``get_chain()[discard::thin]``
+        read in place on the device (``gpemu.reweight.summary``): a list with one dict per scenario.
+        ``priors``: a list of prior scenarios (``gpemu.reweight.check_priors``) inside the box, which defaults to the
+        prior box of the sampler's models; ``models_new``: the sampler's emulators with another ``likelihood_setup`` (a
+        data scenario: one row, or added to every prior scenario).  ``summary_kw``: ``probabilities``, ``bins_1d``,
+        ``bins_2d``, ``smooth``, ``r_eff``.  The log-ratios, moments and histograms read the view as it lies, thinned or
+        stacked; the quantiles read one parameter as one stride, so a thinned chain or one chain of a stacked sampler is
+        first copied to a dense device buffer, as ``marginals`` does.  Stacked samplers take ``chain=<index>``."""
+        import torch
+        from . import reweight as RW
+        if priors is None and models_new is None:
+            raise ValueError("pass priors, models_new or both")
+        src, n_blocks, nw, stride, S = self._stored_view(discard, thin, chain)
+        lower, upper = self._box_or_prior(lower, upper)
+        d = self.d
+        view = (self.device, src, n_blocks, nw, stride, S)
+        L, log_norm = None, None
+        if priors is not None:
+            tables = RW.check_priors(priors, d, lower, upper)
+            L = RW.log_prior_dev(self.device, src, n_blocks, nw, stride, d, tables, np.asarray(lower, dtype=np.float64))
+            if models_new is None:
+                log_norm = RW.log_prior_norm(*tables, lower, upper)
+        if models_new is not None:
+            D = RW.data_log_ratio_dev(self.models, models_new, view, self._data_chain(chain))
+            L = D if L is None else L + D
+        dense = None
+        if stride != nw:
+            dense = torch.empty((S, d), dtype=torch.float64, device=torch.device("cuda", self.device))
+            check(_lib.lib().gpemu_marginal_dense_dev(self.device, C.c_void_p(src), n_blocks, nw, stride, d,
+                                                      C.c_void_p(dense.data_ptr()), _lib.current_stream(self.device)))
+        whole = thin == 1 and nw == self.W      # else a thinned or stacked view: the same reduction, uniform weights
+        return RW.summary_view(view, d, L, lower, upper, log_norm=log_norm,
+                               baseline=(lambda: self.chain_moments(discard)) if whole else None,
+                               column_src=None if dense is None else dense.data_ptr(), **summary_kw)
+
     def _box_or_prior(self, lower, upper):
         """``(lower, upper)``, each defaulting to the prior box of the sampler's models."""
         if lower is None or upper is None:
@@ -985,6 +1022,10 @@ class TemperedSampler(DeviceSampler):
         """``DeviceSampler.loo`` of one rung (default: rung 0, the posterior)."""
         return DeviceSampler.loo(self, chain=int(temp), **kw)
 
+    def reweight(self, temp=0, **kw):
+        """``DeviceSampler.reweight`` of one rung (default: rung 0, the posterior)."""
+        return DeviceSampler.reweight(self, chain=int(temp), **kw)
+
     def information_gain(self, temp=0, **kw):
         """``DeviceSampler.information_gain`` of one rung (default: rung 0, the posterior)."""
         return DeviceSampler.information_gain(self, chain=int(temp), **kw)
@@ -1446,6 +1487,19 @@ class EnsembleSampler:
         if models is None:
             raise ValueError("the chain is on the host: pass the device models")
         return loo.chain_loo(models, self.get_chain(discard=discard, thin=thin, flat=True), **kw)
+
+    def get_reweighted(self, discard=0, thin=1, models=None, **kw):
+        """``DeviceSampler.reweight`` of ``get_chain(discard=discard, thin=thin)`` (``priors``, ``models_new``, ``lower``,
+        ``upper``, ``probabilities``, ``bins_1d``, ``bins_2d``, ``smooth``, ``r_eff``): in place while the chain still lives
+        on the device, from the host copy otherwise (``models`` are then required: the device models with the likelihood
+        set up)."""
+        discard, thin = int(discard), int(thin)
+        if self._impl is not None and getattr(self, "_device", False) and not self.__dict__.get("_frozen"):
+            return self._impl.reweight(discard=discard + thin - 1, thin=thin, **kw)
+        from . import reweight
+        if models is None:
+            raise ValueError("the chain is on the host: pass the device models")
+        return reweight.chain_reweight(models, self.get_chain(discard=discard, thin=thin, flat=True), **kw)
 
     def get_information_gain(self, discard=0, thin=1, **kw):
         """``gpemu.information.information_gain`` of ``get_chain(discard=discard, thin=thin, flat=True)`` (``lower``,

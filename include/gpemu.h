@@ -1111,6 +1111,85 @@ enum gpemu_pairlse_path {
 /* out[0 .. min(n, GPEMU_PAIRLSE_PATH_COUNT)) = the counters; returns GPEMU_PAIRLSE_PATH_COUNT (or GPEMU_ERR_ARG). */
 int gpemu_pairlse_path_counts(int64_t *out, int64_t n);
 
+/* ---- importance reweighting of a chain and weighted summaries -----------------------------------------
+ * The posterior under another prior or under other data, from the chain that exists: the log-posterior takes constant
+ * priors inside a box (ref: log_posterior.py:97) while the reference's own prior sampler draws c_1, c_2, c_3 with a
+ * uniform LOGARITHM (ref: plot_qhat.py:298-326).  The stored samples are importance-reweighted to the new target;
+ * gpemu_psis_dev smooths the ratios and its Pareto k-hat says when a rerun is needed instead.
+ *
+ * gpemu_logprior: L[r*ldl + s] = sum_{i < d} f_ri(x_si), the log of the new prior over the flat one without its
+ * constants, added in index order with one rounding per addition, for R scenarios with HOST tables kind[R*d] (int),
+ * a[R*d], b[R*d]:
+ *   kind 0 flat          f = 0
+ *   kind 1 log-uniform   f = -log x                               (needs lower[i] > 0)
+ *   kind 2 normal        f = -(x - a)^2 / (2 b^2)
+ *   kind 3 log-normal    f = -log x - (log x - a)^2 / (2 b^2)     (needs lower[i] > 0)
+ * lower[d] (HOST) is the box's lower bounds; the box itself is not applied.  GPEMU_ERR_ARG before any launch: d outside
+ * [1, 16], R outside [1, 64], an unknown kind, kind 1 / 3 with lower[i] <= 0, kind 2 / 3 with a non-finite a or b or
+ * b <= 0, ldl below the number of rows.  One lane per sample, the tables in LDS.  The host form takes X[S*d] and writes
+ * L[R*S]; _dev reads the rows in the block layout of gpemu_marginal_hist_dev in place and writes the device array dL.
+ *
+ * gpemu_logmeanexp_dev: per row of dL[R][ldl], dlme[r] = logsumexp_s(L_rs) - log S (NULL: not wanted) and
+ * dlw[r*S + s] = L_rs - logsumexp(L_r) (NULL: not wanted; dense), both DEVICE arrays.  The sum runs over chunks of 4096
+ * fixed by the index -- a lane adds its 16 terms exp(L - max) in index order, then the wave tree, the chunks in order --
+ * so the bits do not depend on the grid or on the run.  A row with a NaN or +inf gives NaN, a row of -inf gives -inf.
+ *
+ * gpemu_weights_fixed_dev: dq[r*ldq + s] = (uint64) rint(exp(dlw[r*ldw + s]) * 2^52) and dQ[r] = sum_s dq[r][s], an
+ * exact integer sum (a NaN weight counts 0).  For normalised weights and S < 2^31, Q < 2^53: every partial sum of a row
+ * is an exact integer and exact in a double, so no sum below depends on its order.
+ *
+ * gpemu_weighted_select: out[(w*R_v + v)*n_targets + i] = the smallest element x of value row v with
+ * sum_{x_s <= x} q[w][s] >= targets[w*n_targets + i] -- the inverted weighted ECDF, an element of the input (a zero may
+ * come back with either sign).  targets[R_w*n_targets] is a HOST array, in any order, every one in [1, 2^53]; a target
+ * above the row's total weight returns NaN, and so does every target of a value row that holds a NaN.  The radix select
+ * of gpemu_select with histograms of weight sums: eight passes of 8 bits, 64-bit LDS integer atomics, non-zero bins
+ * flushed with 64-bit global integer atomics, a sample's weight loaded only when its key matches a live prefix; targets
+ * in groups of 16.  The (w, v) pairs go through the state (33 288 bytes each) in batches of at most 512 that fit
+ * workspace_bytes (0 = half of the free device memory; not one pair: GPEMU_ERR_HIP).  R_v, R_w >= 1, R_v*R_w < 2^31,
+ * 1 <= S < 2^31, 1 <= n_targets < 2^24, else GPEMU_ERR_ARG before any launch.  _dev addresses the values as
+ * gpemu_select_dev does (element j of row v at dV[v*row_stride + j*elem_stride]); dq[R_w][ldq] and dout are device arrays.
+ *
+ * gpemu_weighted_hist: gpemu_marginal_hist's histograms -- the same edges, binning rule and limits -- with q[w][s] added
+ * where it adds 1: hist1[R_w*d*nb1], hist2[R_w*n_pairs*nb2*nb2] (NULL allowed for d = 1), w_inside1[R_w*d] = the weight
+ * counted in hist1[w][j].  LDS holds 64-bit bins: group_bins per sweep (0: 18432 = 144 KiB; else max(nb1, nb2) <=
+ * group_bins <= 18432); a pair whose nb2^2 bins do not fit is swept in bands of floor(group_bins / nb2) bins of its
+ * first index.  One weight row per workgroup (grid.y).  1 <= R_w <= 65535.
+ * Every _dev form works on `stream` (NULL = the null stream) and waits for it before it returns. */
+int gpemu_logprior(int device, int64_t S, int d, const double *X, int R, const int *kind, const double *a,
+                   const double *b, const double *lower, double *L);
+int gpemu_logprior_dev(int device, const double *dX, int64_t n_blocks, int64_t block_rows, int64_t block_stride_rows,
+                       int d, int R, const int *kind, const double *a, const double *b, const double *lower, double *dL,
+                       int64_t ldl, void *stream);
+int gpemu_logmeanexp_dev(int device, int64_t R, int64_t S, const double *dL, int64_t ldl, double *dlme, double *dlw,
+                         void *stream);
+int gpemu_weights_fixed_dev(int device, int64_t R, int64_t S, const double *dlw, int64_t ldw, uint64_t *dq, int64_t ldq,
+                            uint64_t *dQ, void *stream);
+int gpemu_weighted_select(int device, int64_t R_v, int64_t S, const double *V, int64_t R_w, const uint64_t *q,
+                          int64_t n_targets, const uint64_t *targets, double *out);
+int gpemu_weighted_select_dev(int device, int64_t R_v, int64_t S, const double *dV, int64_t row_stride,
+                              int64_t elem_stride, int64_t R_w, const uint64_t *dq, int64_t ldq, int64_t n_targets,
+                              const uint64_t *targets, double *dout, int64_t workspace_bytes, void *stream);
+int gpemu_weighted_hist(int device, int64_t S, int d, const double *X, int64_t R_w, const uint64_t *q, int nb1,
+                        const double *edges1, int nb2, const double *edges2, int64_t group_bins, uint64_t *hist1,
+                        uint64_t *hist2, uint64_t *w_inside1);
+int gpemu_weighted_hist_dev(int device, const double *dX, int64_t n_blocks, int64_t block_rows,
+                            int64_t block_stride_rows, int d, int64_t R_w, const uint64_t *dq, int64_t ldq, int nb1,
+                            const double *edges1, int nb2, const double *edges2, int64_t group_bins, uint64_t *dhist1,
+                            uint64_t *dhist2, uint64_t *dw_inside1, void *stream);
+/* Which launches of these ran.  A set of its own: the other sets keep their sizes and indices. */
+enum gpemu_reweight_path {
+  GPEMU_REWEIGHT_PATH_LOGPRIOR = 0,      /* one launch of the log-prior kernel                                          */
+  GPEMU_REWEIGHT_PATH_QUANTISE,          /* one launch of the fixed-point weights kernel                                */
+  GPEMU_REWEIGHT_PATH_LOGSUMEXP,         /* one log-sum-exp of a matrix of rows (maximum, sum and their finish kernels) */
+  GPEMU_REWEIGHT_PATH_WSEL_HIST_PASS,    /* one pass of the weighted select's histogram kernel, for one batch of pairs  */
+  GPEMU_REWEIGHT_PATH_WSEL_SCAN,         /* one launch of the scan that walks the cumulative weight                     */
+  GPEMU_REWEIGHT_PATH_WHIST_SWEEP,       /* one sweep of the weighted histogram kernel over the rows                    */
+  GPEMU_REWEIGHT_PATH_WHIST_PAIR_GROUP,  /* ... that carried a group of pairs (or a band of one)                        */
+  GPEMU_REWEIGHT_PATH_COUNT
+};
+/* out[0 .. min(n, GPEMU_REWEIGHT_PATH_COUNT)) = the counters; returns GPEMU_REWEIGHT_PATH_COUNT (or GPEMU_ERR_ARG). */
+int gpemu_reweight_path_counts(int64_t *out, int64_t n);
+
 /* ---- fit handle: test-only entry points ---------------------------------------------------------------------------
  * For the tests of the fit side only; nothing in the library's own flow calls them.
  * gpemu_fit_workspace: out[N*N] = problem z of the last evaluation (gpemu_fit_lml / _lml_batch / _factor) as the
