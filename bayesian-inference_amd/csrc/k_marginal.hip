@@ -1,15 +1,19 @@
 // Marginal posteriors of a stored chain (gpemu_marginal_hist*, gpemu_hpd*, gpemu_kde1d*): the data of a
 // corner plot from every sample, where the chain lies.
 //
-// Histograms (mh_*): one sweep of mh_hist_kernel over the rows fills, per workgroup, private 16-bit counters in LDS --
-// two to a 32-bit word, advanced by LDS integer atomics of 1 or 1 << 16; a workgroup takes at most MH_MAX_ROWS < 2^16
-// rows, so a counter cannot carry into its neighbour -- for the 1-D histograms of parameters [a0, a1) and the 2-D
-// histograms of pairs [p0, p1).  A thread owns a row: its d doubles are loaded once, every bin index is found once
-// (guessed from the affine map of the box, then walked to the bin whose edges hold the value: numpy's rule, on the
-// edges themselves) and shared by all pairs of the sweep.  Non-zero counters go to the 64-bit outputs with global
-// integer atomics.  The host plans the sweeps: floor(cap / nb2^2) pairs each, the 1-D counters beside the last group
-// where they fit, else in sweeps of their own.  Every counter is an integer: nothing depends on the grid, on the plan
-// or on the run.
+// Histograms (hist_*; also what gpemu_weighted_hist* of k_reweight.hip runs, through hist_rows of rows_dev.h; DESIGN
+// 4.40): one sweep of hist_sweep_kernel over the rows fills, per workgroup, private bins in LDS for the 1-D histograms of
+// parameters [a0, a1) and the 2-D histograms of pairs [p0, p1).  A thread owns a row: its d doubles are loaded once,
+// every bin index is found once (guessed from the affine map of the box, then walked to the bin whose edges hold the
+// value: numpy's rule, on the edges themselves) and shared by all pairs of the sweep.  Non-zero bins go to the 64-bit
+// outputs with global integer atomics.  The kernel is written once; a bin policy gives the two forms:
+//   Bins16  counted: 16-bit counters, two to a 32-bit word, advanced by LDS integer atomics of 1 or 1 << 16; a workgroup
+//           takes at most HS_MAX_ROWS16 < 2^16 rows, so a counter cannot carry into its neighbour.  73728 to a sweep;
+//   Bins64  weighted: 64-bit bins that take the row's integer weight q[w][s] (a row of weight 0 is skipped); 18432 to a
+//           sweep, grid.y = the weight row.
+// The host plans the sweeps: floor(cap / nb2^2) pairs each, or, where the nb2^2 bins of a pair do not fit, one pair in
+// bands of its first index; the 1-D bins beside the last sweep of pairs where they fit, else in sweeps of their own.
+// Every bin is an integer: nothing depends on the grid, on the plan or on the run.
 //
 // Highest-density intervals (hpd_*): the rows are sorted by k_rows.hip's radix sort in batches; hpd_window_kernel takes,
 // for every (row, level, chunk of HW_PER windows), the lexicographic minimum of (s[S - n + i] - s[i], i), and
@@ -31,10 +35,8 @@
 
 namespace gpemu {
 
-constexpr int MH_THREADS = 1024;
-constexpr int64_t MH_CAP = 73728;        // 16-bit counters of a sweep: 144 KiB of LDS
-constexpr int64_t MH_MAX_ROWS = 65280;   // rows per workgroup, < 2^16: a 16-bit counter cannot overflow
-constexpr int MH_MAX_D = 16;
+constexpr int HS_THREADS = 1024;
+constexpr int64_t HS_MAX_ROWS16 = 65280; // rows per workgroup of a counted sweep, < 2^16: a 16-bit counter cannot overflow
 constexpr int HW_PER = 4096;             // windows per workgroup of the window search
 constexpr int KD_CHUNK = 8192;           // samples per partial sum
 constexpr int KD_STAGE = 1024;           // samples staged in LDS at a time
@@ -45,18 +47,23 @@ static inline void marginal_path_count(int path) { count_path(PATHS_MARGINAL, pa
 
 // ---- histograms ----------------------------------------------------------------------------------------------------
 struct HistArgs {
-  const double *X;
-  int64_t S, block_rows, block_stride_rows, rows_per_wg;
+  RowsView X;
+  int64_t S, rows_per_wg;
+  const u64 *q;                    // [R_w][ldq]; not read by the counted form
+  int64_t ldq;
   const double *e1, *e2;           // [d][nb1 + 1], [d][nb2 + 1]
-  int d, nb1, nb2;
+  int nb1, nb2;
   int a0, a1, p0, p1;              // this sweep: 1-D histograms of parameters [a0, a1), pairs [p0, p1)
   int i0, j0;                      // pair p0 = (i0, j0)
-  unsigned long long *hist1, *hist2;
+  int band0, band;                 // ... of the pairs, the bins [band0, band0 + band) of the first index: all nb2 of them,
+                                   // or a band of ONE pair -- either way one contiguous piece of hist2
+  u64 *hist1, *hist2;              // [R_w][d][nb1], [R_w][np][nb2][nb2]
+  int64_t n1_all, n2_all;          // d nb1, np nb2^2
 };
 
 // the bin b with e[b] <= x < e[b + 1], the last one closed on the right; -1 outside [e[0], e[nb]] and for NaN.
 // tab = {e[0], e[nb], nb / (e[nb] - e[0])}
-static __device__ __forceinline__ int mh_bin(double x, const double *__restrict__ e, int nb, const double *tab) {
+static __device__ __forceinline__ int hist_bin(double x, const double *__restrict__ e, int nb, const double *tab) {
   const double e0 = tab[0], eN = tab[1];
   if (!(x >= e0 && x <= eN)) return -1;
   double t = (x - e0) * tab[2];
@@ -67,16 +74,45 @@ static __device__ __forceinline__ int mh_bin(double x, const double *__restrict_
   return b;
 }
 
-static __device__ __forceinline__ void mh_count(unsigned *lds, int c) { atomicAdd(&lds[c >> 1], 1u << ((c & 1) << 4)); }
+// The bins of a workgroup in LDS.  Counted: 16-bit counters, two to a word, that take 1 per row.
+struct Bins16 {
+  typedef unsigned word;
+  static constexpr bool weighted = false;
+  static __device__ __forceinline__ int words(int n) { return (n + 1) >> 1; }
+  static __device__ __forceinline__ void add(word *lds, int c, u64) { atomicAdd(&lds[c >> 1], 1u << ((c & 1) << 4)); }
+  template <class F>   // f(bin, value) for the non-zero bins below n of word w
+  static __device__ __forceinline__ void flush(word v, int w, int n, F f) {
+    if (!v) return;
+#pragma unroll
+    for (int half = 0; half < 2; ++half) {
+      const int c = 2 * w + half;
+      const unsigned cnt = (v >> (16 * half)) & 0xffffu;
+      if (cnt && c < n) f(c, (u64)cnt);
+    }
+  }
+};
+// Weighted: 64-bit bins that take the row's weight.
+struct Bins64 {
+  typedef u64 word;
+  static constexpr bool weighted = true;
+  static __device__ __forceinline__ int words(int n) { return n; }
+  static __device__ __forceinline__ void add(word *lds, int c, u64 wt) { atomicAdd(&lds[c], wt); }
+  template <class F>
+  static __device__ __forceinline__ void flush(word v, int w, int, F f) {
+    if (v) f(w, v);
+  }
+};
 
-template <int DP>
-__global__ __launch_bounds__(MH_THREADS) void mh_hist_kernel(HistArgs a) {
-  extern __shared__ unsigned mh_lds[];           // the 16-bit counters, two per word: 1-D section, then the pairs
-  __shared__ double tab[2][MH_MAX_D][3];
+// workgroup (rows [x rows_per_wg, (x + 1) rows_per_wg), weight row y)
+template <int DP, class Bins>
+__global__ __launch_bounds__(HS_THREADS) void hist_sweep_kernel(HistArgs a) {
+  extern __shared__ __align__(8) unsigned char hs_lds[];   // the bins: 1-D section, then the pairs (their bands)
+  __shared__ double tab[2][ROWS_MAX_D][3];
+  typename Bins::word *lds = (typename Bins::word *)hs_lds;
   const int tid = threadIdx.x;
-  const int d = a.d, nb1 = a.nb1, nb2 = a.nb2, nb2sq = nb2 * nb2;
-  const int n1 = (a.a1 - a.a0) * nb1, ncnt = n1 + (a.p1 - a.p0) * nb2sq, nwords = (ncnt + 1) >> 1;
-  for (int w = tid; w < nwords; w += MH_THREADS) mh_lds[w] = 0;
+  const int d = a.X.d, nb1 = a.nb1, nb2 = a.nb2, psz = a.band * nb2;
+  const int n1 = (a.a1 - a.a0) * nb1, nbins = n1 + (a.p1 - a.p0) * psz, nwords = Bins::words(nbins);
+  for (int w = tid; w < nwords; w += HS_THREADS) lds[w] = 0;
   if (tid < 2 * d) {
     const int which = tid / d, k = tid % d, nb = which ? nb2 : nb1;
     const double *e = (which ? a.e2 : a.e1) + (int64_t)k * (nb + 1);
@@ -85,26 +121,46 @@ __global__ __launch_bounds__(MH_THREADS) void mh_hist_kernel(HistArgs a) {
     tab[which][k][2] = (double)nb / (e[nb] - e[0]);
   }
   __syncthreads();
+  const u64 *qrow = a.q + (int64_t)blockIdx.y * a.ldq;
   const int64_t r0 = (int64_t)blockIdx.x * a.rows_per_wg, r1 = (r0 + a.rows_per_wg < a.S) ? r0 + a.rows_per_wg : a.S;
-  for (int64_t r = r0 + tid; r < r1; r += MH_THREADS) {
-    const double *row = a.X + ((r / a.block_rows) * a.block_stride_rows + r % a.block_rows) * d;
-    int b2[DP];
+  for (int64_t r = r0 + tid; r < r1; r += HS_THREADS) {
+    u64 wt = 1;
+    if (Bins::weighted) {
+      wt = qrow[r];
+      if (wt == 0) continue;
+    }
+    const double *row = a.X.row(r);
+    u64 pk[DP / 4];   // the 2-D bins + 1 (0: outside), 16 bits each: k is uniform, a select per word keeps them in registers
+#pragma unroll
+    for (int w = 0; w < DP / 4; ++w) pk[w] = 0;
 #pragma unroll 1
-    for (int k = 0; k < d; ++k) {   // (k is the same for every lane: b2 stays in registers)
+    for (int k = 0; k < d; ++k) {
       const double xv = row[k];
       if (k >= a.a0 && k < a.a1) {
-        const int b = mh_bin(xv, a.e1 + (int64_t)k * (nb1 + 1), nb1, tab[0][k]);
-        if (b >= 0) mh_count(mh_lds, (k - a.a0) * nb1 + b);
+        const int b = hist_bin(xv, a.e1 + (int64_t)k * (nb1 + 1), nb1, tab[0][k]);
+        if (b >= 0) Bins::add(lds, (k - a.a0) * nb1 + b, wt);
       }
-      if (a.p1 > a.p0) b2[k] = mh_bin(xv, a.e2 + (int64_t)k * (nb2 + 1), nb2, tab[1][k]);
+      if (a.p1 > a.p0) {
+        const u64 b = (u64)(hist_bin(xv, a.e2 + (int64_t)k * (nb2 + 1), nb2, tab[1][k]) + 1) << ((k & 3) * 16);
+#pragma unroll
+        for (int w = 0; w < DP / 4; ++w) pk[w] |= (w == (k >> 2)) ? b : 0;
+      }
     }
     if (a.p1 > a.p0) {
       int i = a.i0, j = a.j0, off = n1;   // pair p0 = (i0, j0), then row-major: the index is the same for every lane
 #pragma unroll 1
       for (int p = a.p0; p < a.p1; ++p) {
-        const int bi = b2[i], bj = b2[j];
-        if (bi >= 0 && bj >= 0) mh_count(mh_lds, off + bi * nb2 + bj);
-        off += nb2sq;
+        u64 wi = 0, wj = 0;
+#pragma unroll
+        for (int w = 0; w < DP / 4; ++w) {
+          wi = (w == (i >> 2)) ? pk[w] : wi;
+          wj = (w == (j >> 2)) ? pk[w] : wj;
+        }
+        int bi = (int)((wi >> ((i & 3) * 16)) & 0xffff) - 1;
+        const int bj = (int)((wj >> ((j & 3) * 16)) & 0xffff) - 1;
+        bi -= a.band0;
+        if (bi >= 0 && bi < a.band && bj >= 0) Bins::add(lds, off + bi * nb2 + bj, wt);
+        off += psz;
         if (++j == d) {
           ++i;
           j = i + 1;
@@ -113,49 +169,50 @@ __global__ __launch_bounds__(MH_THREADS) void mh_hist_kernel(HistArgs a) {
     }
   }
   __syncthreads();
-  unsigned long long *g1 = a.hist1 + (int64_t)a.a0 * nb1, *g2 = a.hist2 + (int64_t)a.p0 * nb2sq;
-  for (int w = tid; w < nwords; w += MH_THREADS) {
-    const unsigned v = mh_lds[w];
-    if (!v) continue;
-#pragma unroll
-    for (int half = 0; half < 2; ++half) {
-      const int c = 2 * w + half;
-      const unsigned cnt = (v >> (16 * half)) & 0xffffu;
-      if (cnt && c < ncnt) atomicAdd(c < n1 ? &g1[c] : &g2[c - n1], (unsigned long long)cnt);
-    }
-  }
+  u64 *g1 = a.hist1 + (int64_t)blockIdx.y * a.n1_all + (int64_t)a.a0 * nb1;
+  u64 *g2 = a.hist2 + (int64_t)blockIdx.y * a.n2_all + ((int64_t)a.p0 * nb2 + a.band0) * nb2;
+  for (int w = tid; w < nwords; w += HS_THREADS)
+    Bins::flush(lds[w], w, nbins, [&](int c, u64 v) { atomicAdd(c < n1 ? &g1[c] : &g2[c - n1], v); });
 }
 
-// n_inside[j] = the sum of hist1[j][.]; workgroup j
-__global__ __launch_bounds__(256) void mh_inside_kernel(const unsigned long long *__restrict__ hist1, int nb1,
-                                                        unsigned long long *__restrict__ n_inside) {
-  __shared__ unsigned long long red[256];
+// inside[w d + j] = the sum of hist1[w][j][.]; workgroup w d + j
+__global__ __launch_bounds__(256) void hist_inside_kernel(const u64 *__restrict__ hist1, int nb1, u64 *__restrict__ inside) {
+  __shared__ u64 red[256];
   const int tid = threadIdx.x;
-  unsigned long long s = 0;
+  u64 s = 0;
   for (int b = tid; b < nb1; b += 256) s += hist1[(int64_t)blockIdx.x * nb1 + b];
   s = wg_sum_a<256>(s, red);
-  if (tid == 0) n_inside[blockIdx.x] = s;
+  if (tid == 0) inside[blockIdx.x] = s;
 }
 
-struct HistSweep { int a0, a1, p0, p1; };
+struct HistSweep { int a0, a1, p0, p1, band0, band; };
 
-// the sweeps of one call (the file's header); cap: 16-bit counters per sweep
+// the sweeps of one call; cap: bins per sweep.  nb2^2 <= cap: floor(cap / nb2^2) whole pairs per sweep; nb2^2 > cap: one
+// pair per sweep, in bands of floor(cap / nb2) bins of its first index.  The 1-D bins beside the last sweep of pairs where
+// they fit, else in sweeps of their own
 static std::vector<HistSweep> hist_plan(int d, int nb1, int nb2, int64_t cap) {
   std::vector<HistSweep> plan;
   const int np = d * (d - 1) / 2;
-  const int64_t sq = (int64_t)nb2 * nb2, ppg = cap / sq, dpg = cap / nb1;
-  for (int p0 = 0; p0 < np; p0 += (int)ppg) plan.push_back({0, 0, p0, (int)std::min<int64_t>(np, p0 + ppg)});
+  const int64_t sq = (int64_t)nb2 * nb2, dpg = cap / nb1;
+  if (sq <= cap) {
+    const int64_t ppg = cap / sq;
+    for (int p0 = 0; p0 < np; p0 += (int)ppg) plan.push_back({0, 0, p0, (int)std::min<int64_t>(np, p0 + ppg), 0, nb2});
+  } else {
+    const int band = (int)(cap / nb2);
+    for (int p = 0; p < np; ++p)
+      for (int b0 = 0; b0 < nb2; b0 += band) plan.push_back({0, 0, p, p + 1, b0, std::min(band, nb2 - b0)});
+  }
   int a = 0;
-  if (!plan.empty()) {   // beside the last group of pairs, as many parameters as fit
+  if (!plan.empty()) {   // beside the last sweep of pairs, as many parameters as fit
     HistSweep &last = plan.back();
-    a = (int)std::min<int64_t>(d, (cap - (last.p1 - last.p0) * sq) / nb1);
+    a = (int)std::min<int64_t>(d, (cap - (int64_t)(last.p1 - last.p0) * last.band * nb2) / nb1);
     last.a1 = a;
   }
-  for (; a < d; a += (int)dpg) plan.push_back({a, (int)std::min<int64_t>(d, a + dpg), 0, 0});
+  for (; a < d; a += (int)dpg) plan.push_back({a, (int)std::min<int64_t>(d, a + dpg), 0, 0, 0, nb2});
   return plan;
 }
 
-static int edges_check(const double *e, int d, int nb) {
+int edges_check(const double *e, int d, int nb) {
   for (int k = 0; k < d; ++k)
     for (int b = 0; b <= nb; ++b) {
       const double v = e[(int64_t)k * (nb + 1) + b];
@@ -165,71 +222,69 @@ static int edges_check(const double *e, int d, int nb) {
   return GPEMU_OK;
 }
 
-// the rows of the _dev calls as a view, within the marginals' own limits
-static int marginal_view(const double *dX, int64_t n_blocks, int64_t block_rows, int64_t block_stride_rows, int d,
-                         RowsView *v) {
-  GP_ARG(d >= 1 && d <= MH_MAX_D, "d must be in [1, 16]");
-  *v = RowsView{dX, n_blocks, block_rows, block_stride_rows * d, d};
-  GP_TRY(rows_check(*v));
-  GP_ARG(n_blocks <= ((1ll << 31) - 1) / block_rows, "S = n_blocks * block_rows must be below 2^31");
-  return GPEMU_OK;
-}
-
-static int hist_check(int d, int nb1, const double *edges1, int nb2, const double *edges2, int64_t group_counters,
-                      const void *hist1, const void *hist2, const void *n_inside1) {
-  GP_ARG(d >= 1 && d <= MH_MAX_D, "d must be in [1, 16]");
-  GP_ARG(nb1 >= 1 && nb1 <= 4096, "nb1 must be in [1, 4096]");
-  GP_ARG(nb2 >= 1 && nb2 <= 256, "nb2 must be in [1, 256]");
-  GP_ARG(edges1 && edges2 && hist1 && n_inside1 && (hist2 || d == 1), "null pointer");
-  GP_ARG(group_counters == 0 || (group_counters >= std::max<int64_t>(nb1, (int64_t)nb2 * nb2) && group_counters <= MH_CAP),
-         "group_counters must be 0 or in [max(nb1, nb2^2), 73728]");
-  GP_TRY(edges_check(edges1, d, nb1));
-  GP_TRY(edges_check(edges2, d, nb2));
-  return GPEMU_OK;
-}
-
-// the sweeps over device rows; asynchronous on st but for the edges' upload, which the scope outlives: waits for st
-static int hist_rows(const double *dX, int64_t n_blocks, int64_t block_rows, int64_t block_stride_rows, int d, int nb1,
-                     const double *edges1, int nb2, const double *edges2, int64_t group_counters, int64_t *dhist1,
-                     int64_t *dhist2, int64_t *dn_inside1, hipStream_t st) {
-  const int64_t S = n_blocks * block_rows, np = d * (d - 1) / 2;
-  const std::vector<HistSweep> plan = hist_plan(d, nb1, nb2, group_counters ? group_counters : MH_CAP);
+int hist_rows(const RowsView &X, int64_t R_w, const u64 *dq, int64_t ldq, int nb1, const double *edges1, int nb2,
+              const double *edges2, int64_t cap, u64 *dhist1, u64 *dhist2, u64 *dinside1, void (*on_sweep)(bool pairs),
+              hipStream_t st) {
+  const int d = X.d;
+  const int64_t S = X.rows(), np = d * (d - 1) / 2;
+  const std::vector<HistSweep> plan = hist_plan(d, nb1, nb2, cap);
   DevScope sc(st);
   double *de1 = nullptr, *de2 = nullptr;
   GP_TRY(sc.alloc(&de1, (int64_t)d * (nb1 + 1)));
   GP_TRY(sc.alloc(&de2, (int64_t)d * (nb2 + 1)));
   GP_TRY(upload(de1, edges1, (int64_t)d * (nb1 + 1), st));
   GP_TRY(upload(de2, edges2, (int64_t)d * (nb2 + 1), st));
-  GP_HIP(hipMemsetAsync(dhist1, 0, sizeof(int64_t) * (size_t)d * nb1, st));
-  if (np > 0) GP_HIP(hipMemsetAsync(dhist2, 0, sizeof(int64_t) * (size_t)np * nb2 * nb2, st));
   HistArgs a;
-  a.X = dX; a.S = S; a.block_rows = block_rows; a.block_stride_rows = block_stride_rows;
-  a.rows_per_wg = std::min<int64_t>(MH_MAX_ROWS, std::max<int64_t>(4096, round_up((S + 1023) / 1024, 256)));
-  a.e1 = de1; a.e2 = de2; a.d = d; a.nb1 = nb1; a.nb2 = nb2;
-  a.hist1 = (unsigned long long *)dhist1; a.hist2 = (unsigned long long *)dhist2;
-  const unsigned nwg = (unsigned)((S + a.rows_per_wg - 1) / a.rows_per_wg);
-  const void *fn = d <= 8 ? (const void *)mh_hist_kernel<8> : (const void *)mh_hist_kernel<16>;
-  GP_TRY(allow_dynamic_lds(fn, (int)(2 * MH_CAP + 16)));
+  a.X = X; a.S = S; a.q = dq; a.ldq = ldq;
+  a.rows_per_wg = std::max<int64_t>(4096, round_up((S + 1023) / 1024, 256));
+  if (!dq) a.rows_per_wg = std::min(a.rows_per_wg, HS_MAX_ROWS16);
+  a.e1 = de1; a.e2 = de2; a.nb1 = nb1; a.nb2 = nb2;
+  a.hist1 = dhist1; a.hist2 = dhist2;
+  a.n1_all = (int64_t)d * nb1; a.n2_all = np * nb2 * nb2;
+  GP_HIP(hipMemsetAsync(dhist1, 0, sizeof(u64) * (size_t)(R_w * a.n1_all), st));
+  if (np > 0) GP_HIP(hipMemsetAsync(dhist2, 0, sizeof(u64) * (size_t)(R_w * a.n2_all), st));
+  const dim3 grid((unsigned)((S + a.rows_per_wg - 1) / a.rows_per_wg), (unsigned)R_w);
+  void (*const fn)(HistArgs) = dq ? (d <= 8 ? hist_sweep_kernel<8, Bins64> : hist_sweep_kernel<16, Bins64>)
+                                  : (d <= 8 ? hist_sweep_kernel<8, Bins16> : hist_sweep_kernel<16, Bins16>);
+  GP_TRY(allow_dynamic_lds((const void *)fn, (int)(dq ? 8 * HIST_CAP64 : 2 * HIST_CAP16 + 16)));
   for (const HistSweep &sw : plan) {
-    a.a0 = sw.a0; a.a1 = sw.a1; a.p0 = sw.p0; a.p1 = sw.p1;
+    a.a0 = sw.a0; a.a1 = sw.a1; a.p0 = sw.p0; a.p1 = sw.p1; a.band0 = sw.band0; a.band = sw.band;
     int i0 = 0, rem = sw.p0;   // row i of the pair list holds d - 1 - i pairs
     while (i0 < d - 1 && rem >= d - 1 - i0) rem -= d - 1 - i0++;
     a.i0 = i0; a.j0 = i0 + 1 + rem;
-    const int64_t ncnt = (int64_t)(sw.a1 - sw.a0) * nb1 + (int64_t)(sw.p1 - sw.p0) * nb2 * nb2;
-    const size_t lds = (size_t)round_up(2 * ncnt + 2, 16);
-    marginal_path_count(GPEMU_MARGINAL_PATH_HIST_SWEEP);
-    if (sw.p1 > sw.p0) marginal_path_count(GPEMU_MARGINAL_PATH_PAIR_GROUP);
-    if (d <= 8)
-      hipLaunchKernelGGL(mh_hist_kernel<8>, dim3(nwg), dim3(MH_THREADS), lds, st, a);
-    else
-      hipLaunchKernelGGL(mh_hist_kernel<16>, dim3(nwg), dim3(MH_THREADS), lds, st, a);
+    const int64_t nbins = (int64_t)(sw.a1 - sw.a0) * nb1 + (int64_t)(sw.p1 - sw.p0) * sw.band * nb2;
+    const size_t lds = dq ? (size_t)(8 * std::max<int64_t>(nbins, 1)) : (size_t)round_up(2 * nbins + 2, 16);
+    on_sweep(sw.p1 > sw.p0);
+    hipLaunchKernelGGL(fn, grid, dim3(HS_THREADS), lds, st, a);
     GP_HIP(hipGetLastError());
   }
-  hipLaunchKernelGGL(mh_inside_kernel, dim3((unsigned)d), dim3(256), 0, st, (const unsigned long long *)dhist1, nb1,
-                     (unsigned long long *)dn_inside1);
+  hipLaunchKernelGGL(hist_inside_kernel, dim3((unsigned)(R_w * d)), dim3(256), 0, st, (const u64 *)dhist1, nb1, dinside1);
   GP_HIP(hipGetLastError());
-  GP_HIP(hipStreamSynchronize(st));
+  GP_HIP(hipStreamSynchronize(st));   // the edges are read by the copies above
   return GPEMU_OK;
+}
+
+static int hist_check(int d, int nb1, const double *edges1, int nb2, const double *edges2, int64_t group_counters,
+                      const void *hist1, const void *hist2, const void *n_inside1) {
+  GP_ARG(d >= 1 && d <= ROWS_MAX_D, "d must be in [1, 16]");
+  GP_ARG(nb1 >= 1 && nb1 <= 4096, "nb1 must be in [1, 4096]");
+  GP_ARG(nb2 >= 1 && nb2 <= 256, "nb2 must be in [1, 256]");
+  GP_ARG(edges1 && edges2 && hist1 && n_inside1 && (hist2 || d == 1), "null pointer");
+  GP_ARG(group_counters == 0 || (group_counters >= std::max<int64_t>(nb1, (int64_t)nb2 * nb2) && group_counters <= HIST_CAP16),
+         "group_counters must be 0 or in [max(nb1, nb2^2), 73728]");
+  GP_TRY(edges_check(edges1, d, nb1));
+  GP_TRY(edges_check(edges2, d, nb2));
+  return GPEMU_OK;
+}
+
+// the counted sweep over device rows; waits for st
+static int count_rows(const RowsView &X, int nb1, const double *edges1, int nb2, const double *edges2,
+                      int64_t group_counters, int64_t *dhist1, int64_t *dhist2, int64_t *dn_inside1, hipStream_t st) {
+  return hist_rows(X, 1, nullptr, 0, nb1, edges1, nb2, edges2, group_counters ? group_counters : HIST_CAP16, (u64 *)dhist1,
+                   (u64 *)dhist2, (u64 *)dn_inside1, [](bool pairs) {
+                     marginal_path_count(GPEMU_MARGINAL_PATH_HIST_SWEEP);
+                     if (pairs) marginal_path_count(GPEMU_MARGINAL_PATH_PAIR_GROUP);
+                   }, st);
 }
 
 // ---- highest-density intervals ---------------------------------------------------------------------------------------
@@ -302,7 +357,7 @@ __global__ __launch_bounds__(256) void hpd_finish_kernel(const u64 *__restrict__
   if (threadIdx.x == 0) {
     const u64 *k = sorted + rl * S;
     const double smin = sel_value(k[0]), smax = sel_value(k[S - 1]);
-    double lo = __longlong_as_double(0x7ff8000000000000ll), hi = lo;
+    double lo = sel_nan(), hi = lo;
     // (a chunk's sentinel index survives only where every width is a NaN: a row with an infinite end)
     if (!nan[rl] && !isinf(smin) && !isinf(smax) && bi >= 0 && bi < n) {
       lo = sel_value(k[bi]);
@@ -493,11 +548,10 @@ int gpemu_marginal_hist_dev(int device, const double *dX, int64_t n_blocks, int6
                             int64_t *dn_inside1, void *stream) {
   GP_ARG(dX, "null pointer");
   RowsView X;
-  GP_TRY(marginal_view(dX, n_blocks, block_rows, block_stride_rows, d, &X));
+  GP_TRY(rows_view(dX, n_blocks, block_rows, block_stride_rows, d, &X));
   GP_TRY(hist_check(d, nb1, edges1, nb2, edges2, group_counters, dhist1, dhist2, dn_inside1));
   GP_TRY(device_ready(device));
-  return hist_rows(dX, n_blocks, block_rows, block_stride_rows, d, nb1, edges1, nb2, edges2, group_counters, dhist1, dhist2,
-                   dn_inside1, (hipStream_t)stream);
+  return count_rows(X, nb1, edges1, nb2, edges2, group_counters, dhist1, dhist2, dn_inside1, (hipStream_t)stream);
 }
 
 int gpemu_marginal_hist(int device, int64_t S, int d, const double *X, int nb1, const double *edges1, int nb2,
@@ -517,7 +571,7 @@ int gpemu_marginal_hist(int device, int64_t S, int d, const double *X, int nb1, 
   GP_TRY(sc.alloc(&dh2, n2));
   GP_TRY(sc.alloc(&dni, d));
   GP_TRY(upload(dX, X, S * d, st));
-  GP_TRY(hist_rows(dX, 1, S, S, d, nb1, edges1, nb2, edges2, group_counters, dh1, dh2, dni, st));
+  GP_TRY(count_rows(RowsView{dX, 1, S, S * d, d}, nb1, edges1, nb2, edges2, group_counters, dh1, dh2, dni, st));
   GP_TRY(sc.download(hist1, dh1, (int64_t)d * nb1));
   if (n2 > 0) GP_TRY(sc.download(hist2, dh2, n2));
   GP_TRY(sc.download(n_inside1, dni, d));
@@ -567,7 +621,7 @@ int gpemu_marginal_dense_dev(int device, const double *dX, int64_t n_blocks, int
                              int64_t block_stride_rows, int d, double *ddense, void *stream) {
   GP_ARG(dX && ddense, "null pointer");
   RowsView X;
-  GP_TRY(marginal_view(dX, n_blocks, block_rows, block_stride_rows, d, &X));
+  GP_TRY(rows_view(dX, n_blocks, block_rows, block_stride_rows, d, &X));
   GP_TRY(device_ready(device));
   hipStream_t st = (hipStream_t)stream;
   GP_TRY(gather_rows(X, 0, X.rows(), ddense, st));
@@ -578,7 +632,7 @@ int gpemu_marginal_dense_dev(int device, const double *dX, int64_t n_blocks, int
 int gpemu_marginal_moments_dev(int device, const double *dX, int64_t S, int d, double *mean, double *var, void *stream) {
   GP_ARG(dX && mean && var, "null pointer");
   GP_ARG(S > 0 && S < (1ll << 31), "S must be in [1, 2^31)");
-  GP_ARG(d >= 1 && d <= MH_MAX_D, "d must be in [1, 16]");
+  GP_ARG(d >= 1 && d <= ROWS_MAX_D, "d must be in [1, 16]");
   GP_TRY(device_ready(device));
   return moments_to_host(dX, S, d, mean, var, (hipStream_t)stream);
 }

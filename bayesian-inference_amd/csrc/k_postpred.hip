@@ -1,20 +1,10 @@
 // Exact order statistics of many rows at once (gpemu_select*) and the posterior-predictive reduction built on them
 // (gpemu_posterior_predictive*).
 //
-// Selection: radix select on the order-preserving 64-bit key of a double (negative: all bits flipped, else the sign bit
-// set), most significant byte first, SEL_PASSES = 8 passes of 8 bits.  Per pass
-//   sel_hist_kernel   every workgroup counts a fixed slice of one row into LDS histograms (LDS atomics, the lanes of a
-//                     wave that agree with its first lane added as one count) and adds its non-zero bins to the row's
-//                     global histogram (64-bit integer atomics: counters, no floating-point sum anywhere);
-//   sel_scan_kernel   per row, every rank walks its histogram to the digit that holds it, extends its prefix by that
-//                     digit and keeps the rank within the bin.
-// All ranks of a row share the passes: ranks are sorted on the host, so ranks with one prefix are neighbours and share a
-// "slot" (one histogram); an element is counted in the slot whose prefix it matches, if any.  After the last pass the
-// prefix IS the key of the wanted element -- an element of the input, not an approximation.  The pass count is fixed:
-// a row of equal values, or of values that differ in the last bits only, takes the same eight passes.  The counts are
-// integers, so the result does not depend on the grid, on the slices or on the order in which workgroups arrive.
-// A row with a NaN returns NaN for every rank (np.quantile); -0 and +0 are distinct keys next to each other, so either
-// may be returned for a zero.  More than SEL_MAXR ranks go in groups of SEL_MAXR, rows in batches of SEL_ROWS.
+// Selection: the radix select of k_select.hip (select_rows of rows_dev.h) without weights: rank r is the
+// target r + 1 under unit weights.  An element of the input, not an approximation; a row with a NaN returns NaN for every
+// rank (np.quantile); -0 and +0 are distinct keys next to each other, so either may be returned for a zero.  Rows go in
+// batches of SEL_ROWS.
 //
 // Posterior predictive: PC means / variances of all S rows through gpemu_gp_predict_dev in fixed chunks of PP_CHUNK
 // logical rows (a chunk that is not contiguous in the caller's block layout is gathered into a staging buffer first, so
@@ -28,7 +18,7 @@
 // Every sum over samples runs over chunks fixed by the logical sample index: the bits do not depend on the workspace,
 // on the feature blocks or on the run.
 #include <algorithm>
-#include <numeric>
+#include <vector>
 
 #include "internal.h"
 #include "rows_dev.h"
@@ -37,191 +27,20 @@
 
 namespace gpemu {
 
-constexpr int SEL_PASSES = 8;        // 8 bits each
-constexpr int SEL_BINS = 256;
-constexpr int SEL_MAXR = 16;         // ranks (and slots) per group
-constexpr int SEL_ROWS = 512;        // rows per batch: 16 MiB of global histograms
-constexpr int64_t SEL_SLICE = 4096;  // least elements per workgroup
-constexpr int64_t SEL_MAX_WG = 8192; // workgroups per launch, about
 constexpr int64_t PP_CHUNK = 2048;   // logical rows per predict pass (one pass of gpemu_gp_predict_dev)
 constexpr int64_t PP_SUM = 4096;     // samples per partial sum
 constexpr int PP_FT = 32;            // features per projection workgroup
 constexpr int64_t PP_FIXED = GPEMU_POSTPRED_FIXED_BYTES;
 
-// (sel_key / sel_value: sampler_internal.h)
-
-struct SelState {
-  u64 *prefix = nullptr;    // [SEL_ROWS][SEL_MAXR] key bits found so far, per rank
-  u64 *krem = nullptr;      // [SEL_ROWS][SEL_MAXR] rank within the elements that match the prefix
-  u64 *slotpre = nullptr;   // [SEL_ROWS][SEL_MAXR] prefix of each slot
-  int *slot = nullptr;      // [SEL_ROWS][SEL_MAXR] slot of each rank
-  int *nslot = nullptr;     // [SEL_ROWS]
-  int *nan = nullptr;       // [SEL_ROWS] the row holds a NaN
-  u64 *hist = nullptr;      // [SEL_ROWS][SEL_MAXR][SEL_BINS], zero between passes
-};
-
-__global__ __launch_bounds__(256) void sel_init_kernel(SelState s, int rows, int nr, const u64 *__restrict__ ranks) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= rows * SEL_MAXR) return;
-  const int r = i % SEL_MAXR;
-  s.prefix[i] = 0;
-  s.slotpre[i] = 0;
-  s.krem[i] = r < nr ? ranks[r] : 0;
-  s.slot[i] = 0;
-  if (r == 0) {
-    s.nslot[i / SEL_MAXR] = 1;
-    s.nan[i / SEL_MAXR] = 0;
-  }
-}
-
-// workgroup (row rl, slice c) of the batch: elements [c slice, (c + 1) slice) of the row
-__global__ __launch_bounds__(256) void sel_hist_kernel(SelState s, const double *__restrict__ V, int64_t row_stride,
-                                                       int64_t elem_stride, int64_t S, int64_t row0, int nblk,
-                                                       int64_t slice, int pass) {
-  __shared__ unsigned h[SEL_MAXR * SEL_BINS];
-  __shared__ u64 spre[SEL_MAXR];
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int64_t rl = blockIdx.x / nblk, c = blockIdx.x % nblk;
-  const int ns = s.nslot[rl];
-  for (int t = tid; t < ns * SEL_BINS; t += 256) h[t] = 0;
-  if (tid < SEL_MAXR) spre[tid] = s.slotpre[rl * SEL_MAXR + tid];
-  __syncthreads();
-  const int shift = 56 - 8 * pass;
-  const double *row = V + (row0 + rl) * row_stride;
-  const int64_t base = c * slice, end = (base + slice < S) ? base + slice : S;
-  bool seen_nan = false;
-  for (int64_t off = base; off < end; off += 256) {   // the trip count is the same for every lane
-    const int64_t i = off + tid;
-    int bin = -1;
-    if (i < end) {
-      const double v = row[i * elem_stride];
-      const u64 key = sel_key(v);
-      if (pass == 0) {
-        bin = (int)(key >> 56);
-        seen_nan |= (v != v);
-      } else {
-        const u64 hi = key >> (shift + 8);
-        for (int j = 0; j < ns; ++j)
-          if ((spre[j] >> (shift + 8)) == hi) bin = j * SEL_BINS + (int)((key >> shift) & 255);
-      }
-    }
-    // the lanes that agree with the wave's first lane count once: the leading bytes of real data are nearly constant
-    const int lead = __builtin_amdgcn_readfirstlane(bin);
-    const u64 same = __ballot(bin == lead);
-    if (lead >= 0 && lane == 0) atomicAdd(&h[lead], (unsigned)__popcll(same));
-    if (bin >= 0 && bin != lead) atomicAdd(&h[bin], 1u);
-  }
-  __syncthreads();
-  u64 *g = s.hist + rl * (SEL_MAXR * SEL_BINS);
-  for (int t = tid; t < ns * SEL_BINS; t += 256)
-    if (h[t]) atomicAdd(&g[t], (u64)h[t]);
-  if (seen_nan) s.nan[rl] = 1;
-}
-
-// one workgroup per row: extend every rank's prefix by the digit of this pass, regroup the slots, clear the histograms
-__global__ __launch_bounds__(256) void sel_scan_kernel(SelState s, int nr, int pass) {
-  __shared__ u64 sh[SEL_MAXR * SEL_BINS];
-  __shared__ u64 pre[SEL_MAXR];
-  const int tid = threadIdx.x;
-  const int64_t rl = blockIdx.x;
-  const int ns = s.nslot[rl];
-  u64 *g = s.hist + rl * (SEL_MAXR * SEL_BINS);
-  for (int t = tid; t < ns * SEL_BINS; t += 256) {
-    sh[t] = g[t];
-    g[t] = 0;
-  }
-  __syncthreads();
-  const int shift = 56 - 8 * pass;
-  if (tid < nr) {
-    const int64_t i = rl * SEL_MAXR + tid;
-    const u64 *hs = sh + s.slot[i] * SEL_BINS;
-    const u64 k = s.krem[i];
-    u64 below = 0;
-    int digit = SEL_BINS - 1;
-    for (int b = 0; b < SEL_BINS; ++b) {
-      const u64 cnt = hs[b];
-      if (k < below + cnt) { digit = b; break; }
-      below += cnt;
-    }
-    const u64 p = s.prefix[i] | ((u64)digit << shift);
-    s.prefix[i] = p;
-    s.krem[i] = k - below;
-    pre[tid] = p;
-  }
-  __syncthreads();
-  if (tid == 0) {   // sorted ranks: prefixes ascend, equal ones are neighbours
-    int n = 0;
-    for (int r = 0; r < nr; ++r) {
-      if (r == 0 || pre[r] != pre[r - 1]) s.slotpre[rl * SEL_MAXR + n++] = pre[r];
-      s.slot[rl * SEL_MAXR + r] = n - 1;
-    }
-    s.nslot[rl] = n;
-  }
-}
-
-__global__ __launch_bounds__(256) void sel_out_kernel(SelState s, int rows, int nr, const int *__restrict__ perm,
-                                                      int64_t row0, int64_t out_stride, double *__restrict__ out) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= rows * nr) return;
-  const int rl = i / nr, r = i % nr;
-  const double v = s.nan[rl] ? __longlong_as_double(0x7ff8000000000000ll) : sel_value(s.prefix[rl * SEL_MAXR + r]);
-  out[(row0 + rl) * out_stride + perm[r]] = v;
-}
-
-// out[r * out_stride + i] = order statistic ranks[i] of row r (elements dV[r row_stride + j elem_stride], j < S), all
-// on st; synchronises st before it returns (the scratch goes with the call).  The caller has validated the ranks.
-static int select_rows(const double *dV, int64_t R, int64_t S, int64_t row_stride, int64_t elem_stride, int64_t n_ranks,
-                       const int64_t *ranks, double *dout, int64_t out_stride, hipStream_t st) {
-  std::vector<int> order((size_t)n_ranks);
-  std::iota(order.begin(), order.end(), 0);
-  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return ranks[a] < ranks[b]; });
-  std::vector<u64> sorted((size_t)n_ranks);
-  for (int64_t i = 0; i < n_ranks; ++i) sorted[(size_t)i] = (u64)ranks[order[(size_t)i]];
-
-  const int rows_cap = (int)std::min<int64_t>(R, SEL_ROWS);
-  DevScope sc(st);
-  SelState s;
-  u64 *dranks = nullptr;
-  int *dperm = nullptr;
-  GP_TRY(sc.alloc(&s.prefix, (int64_t)rows_cap * SEL_MAXR));
-  GP_TRY(sc.alloc(&s.krem, (int64_t)rows_cap * SEL_MAXR));
-  GP_TRY(sc.alloc(&s.slotpre, (int64_t)rows_cap * SEL_MAXR));
-  GP_TRY(sc.alloc(&s.slot, (int64_t)rows_cap * SEL_MAXR));
-  GP_TRY(sc.alloc(&s.nslot, rows_cap));
-  GP_TRY(sc.alloc(&s.nan, rows_cap));
-  GP_TRY(sc.alloc(&s.hist, (int64_t)rows_cap * SEL_MAXR * SEL_BINS));
-  GP_TRY(sc.alloc(&dranks, n_ranks));
-  GP_TRY(sc.alloc(&dperm, n_ranks));
-  GP_TRY(upload(dranks, sorted.data(), n_ranks, st));
-  GP_TRY(upload(dperm, order.data(), n_ranks, st));
-  GP_HIP(hipMemsetAsync(s.hist, 0, sizeof(u64) * (size_t)rows_cap * SEL_MAXR * SEL_BINS, st));
-
-  for (int64_t row0 = 0; row0 < R; row0 += SEL_ROWS) {
-    const int rows = (int)std::min<int64_t>(SEL_ROWS, R - row0);
-    // slices: at least SEL_SLICE elements, about SEL_MAX_WG workgroups per launch; whole multiples of the workgroup
-    int64_t nblk = std::max<int64_t>(1, std::min((S + SEL_SLICE - 1) / SEL_SLICE, SEL_MAX_WG / rows));
-    const int64_t slice = round_up((S + nblk - 1) / nblk, 256);
-    nblk = (S + slice - 1) / slice;
-    for (int64_t g0 = 0; g0 < n_ranks; g0 += SEL_MAXR) {
-      const int nr = (int)std::min<int64_t>(SEL_MAXR, n_ranks - g0);
-      hipLaunchKernelGGL(sel_init_kernel, dim3((unsigned)((rows * SEL_MAXR + 255) / 256)), dim3(256), 0, st, s, rows, nr,
-                         dranks + g0);
-      GP_HIP(hipGetLastError());
-      for (int pass = 0; pass < SEL_PASSES; ++pass) {
-        postpred_path_count(GPEMU_POSTPRED_PATH_SELECT_PASS);
-        hipLaunchKernelGGL(sel_hist_kernel, dim3((unsigned)(rows * nblk)), dim3(256), 0, st, s, dV, row_stride,
-                           elem_stride, S, row0, (int)nblk, slice, pass);
-        GP_HIP(hipGetLastError());
-        hipLaunchKernelGGL(sel_scan_kernel, dim3((unsigned)rows), dim3(256), 0, st, s, nr, pass);
-        GP_HIP(hipGetLastError());
-      }
-      hipLaunchKernelGGL(sel_out_kernel, dim3((unsigned)((rows * nr + 255) / 256)), dim3(256), 0, st, s, rows, nr,
-                         dperm + g0, row0, out_stride, dout);
-      GP_HIP(hipGetLastError());
-    }
-  }
-  GP_HIP(hipStreamSynchronize(st));   // `sorted` and `order` are read by the copies above
-  return GPEMU_OK;
+// out[r n_ranks + i] = order statistic ranks[i] of row r (elements dV[r row_stride + j elem_stride], j < S): the radix
+// select of k_select.hip without weights, target rank + 1, all on st; synchronises st before it returns.  The caller has
+// validated the ranks.
+static int select_ranks(const double *dV, int64_t R, int64_t S, int64_t row_stride, int64_t elem_stride, int64_t n_ranks,
+                        const int64_t *ranks, double *dout, hipStream_t st) {
+  std::vector<u64> targets((size_t)n_ranks);
+  for (int64_t i = 0; i < n_ranks; ++i) targets[(size_t)i] = (u64)ranks[i] + 1;
+  return select_rows(dV, R, S, row_stride, elem_stride, 1, nullptr, 0, n_ranks, targets.data(), dout,
+                     std::min<int64_t>(R, SEL_ROWS), [] { postpred_path_count(GPEMU_POSTPRED_PATH_SELECT_PASS); }, st);
 }
 
 static int select_check(int64_t R, int64_t S, int64_t n_ranks, const int64_t *ranks) {
@@ -336,14 +155,14 @@ int gpemu_select_dev(int device, int64_t R, int64_t S, const double *dV, int64_t
   GP_TRY(select_check(R, S, n_ranks, ranks));
   GP_ARG(row_stride > 0 && elem_stride > 0, "strides must be positive");
   GP_TRY(device_ready(device));
-  return select_rows(dV, R, S, row_stride, elem_stride, n_ranks, ranks, dout, n_ranks, (hipStream_t)stream);
+  return select_ranks(dV, R, S, row_stride, elem_stride, n_ranks, ranks, dout, (hipStream_t)stream);
 }
 
 int gpemu_select(int device, int64_t R, int64_t S, const double *V, int64_t n_ranks, const int64_t *ranks, double *out) {
   GP_ARG(V && out, "null pointer");
   GP_TRY(select_check(R, S, n_ranks, ranks));
   return with_host_rows(device, R, S, V, n_ranks, out, [&](const double *dV, double *dout, hipStream_t st) {
-    return select_rows(dV, R, S, S, 1, n_ranks, ranks, dout, n_ranks, st);
+    return select_ranks(dV, R, S, S, 1, n_ranks, ranks, dout, st);
   });
 }
 
@@ -423,7 +242,7 @@ int gpemu_posterior_predictive_dev(gpemu_model *m, const double *dX, int64_t n_b
       GP_HIP(hipGetLastError());
       if (dmean || dvar_param) GP_TRY(launch_rowmean(W, S, 1, fb, S, nullptr, part, mu + f0, st));
       if (dvar_param) GP_TRY(launch_rowmean(W, S, 1, fb, S, mu + f0, part, dvar_param + f0, st));
-      if (n_ranks > 0) GP_TRY(select_rows(W, fb, S, S, 1, n_ranks, ranks, dorder + f0 * n_ranks, n_ranks, st));
+      if (n_ranks > 0) GP_TRY(select_ranks(W, fb, S, S, 1, n_ranks, ranks, dorder + f0 * n_ranks, st));
     }
     if (dmean) GP_HIP(hipMemcpyAsync(dmean, mu, sizeof(double) * (size_t)F, hipMemcpyDeviceToDevice, st));
   }

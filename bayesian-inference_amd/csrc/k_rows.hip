@@ -1,5 +1,6 @@
 // The plumbing the summaries of a stored chain share (rows_dev.h): the gather of a view of rows in blocks,
-// the pooled moments, the workspace budget and the key-only radix sort of rows.  The summaries' own kernels are not here.
+// the pooled moments, the workspace budget and the key-only radix sort of rows.  The radix select is k_select.hip, the
+// histogram sweep k_marginal.hip; the summaries' own kernels are not here.
 //
 // The sort: the key-only LSD radix sort of rows of doubles that the exact ranks (k_diag.hip) and the highest-density intervals
 // (k_marginal.hip) share: order-preserving 64-bit keys (sel_key; -0 canonicalised to +0 first), RK_PASSES = 8 stable
@@ -26,6 +27,14 @@ int rows_check(const RowsView &v) {
   GP_ARG(v.n_blocks > 0 && v.block_rows > 0, "n_blocks and block_rows must be positive");
   GP_ARG(v.d >= 1, "d must be positive");
   GP_ARG(v.n_blocks == 1 || v.block_stride / v.d >= v.block_rows, "the stride between blocks must hold a block");
+  return GPEMU_OK;
+}
+
+int rows_view(const double *dX, int64_t n_blocks, int64_t block_rows, int64_t block_stride_rows, int d, RowsView *v) {
+  GP_ARG(d >= 1 && d <= ROWS_MAX_D, "d must be in [1, 16]");
+  *v = RowsView{dX, n_blocks, block_rows, block_stride_rows * d, d};
+  GP_TRY(rows_check(*v));
+  GP_ARG(n_blocks <= ((1ll << 31) - 1) / block_rows, "S = n_blocks * block_rows must be below 2^31");
   return GPEMU_OK;
 }
 

@@ -1,7 +1,8 @@
-// What the summaries of a stored chain share (k_rows.hip): the view of a chain as blocks of rows with its
-// check and its gather, the pooled moments, the workspace budget, the key-only radix sort of rows with its scratch, and
-// the host form of a function of device rows.  The summaries' own kernels -- selection, histograms, window search,
-// density, split, rank lookup -- stay in their files.
+// What the summaries of a stored chain share.  k_rows.hip: the view of a chain as blocks of rows
+// with its checks and its gather, the pooled moments, the workspace budget, the key-only radix sort of rows with its
+// scratch; here, the host form of a function of device rows.  k_select.hip: the radix select, counted and weighted.
+// k_marginal.hip: the histogram sweep, counted and weighted.  The summaries' own kernels -- window search, density,
+// split, rank lookup, log-ratios -- stay in their files.
 #pragma once
 #include <algorithm>
 
@@ -26,6 +27,10 @@ struct RowsView {
 };
 // GPEMU_ERR_ARG unless the blocks are non-empty and do not overlap; the callers add their own limits
 int rows_check(const RowsView &v);
+// the rows of a summary's _dev call (a stride in ROWS) as a view, within the summaries' limits: d <= ROWS_MAX_D, fewer
+// than 2^31 rows
+constexpr int ROWS_MAX_D = 16;
+int rows_view(const double *dX, int64_t n_blocks, int64_t block_rows, int64_t block_stride_rows, int d, RowsView *v);
 // dst[n][d] = logical rows [r0, r0 + n) of v; asynchronous on st
 int gather_rows(const RowsView &v, int64_t r0, int64_t n, double *dst, hipStream_t st);
 
@@ -77,6 +82,33 @@ struct SortScratch {
 // for a row that holds a NaN.  on_pass() is called once per pass (path counters).  Asynchronous on st
 int sort_rows(const double *dV, int64_t row_stride, int64_t elem_stride, int64_t S, int64_t row0, int64_t rows,
               const SortScratch &s, void (*on_pass)(), hipStream_t st);
+
+// ---- radix select of rows of doubles, by count or by weight (k_select.hip) ------------------------------
+constexpr int SEL_BINS = 256;      // 8 bits a pass
+constexpr int SEL_MAXT = 16;       // targets (and slots) per group
+constexpr int SEL_ROWS = 512;      // (weight row, value row) pairs per batch, at most: 16 MiB of global histograms
+constexpr int64_t SEL_ROW_BYTES = 8ll * SEL_MAXT * SEL_BINS + 3 * 8 * SEL_MAXT + 2 * 4 * SEL_MAXT + 8;   // state of one pair
+// dout[(w R_v + v) nt_all + i] = the smallest element x of value row v (elements dV[v row_stride + s elem_stride], s < S)
+// with sum_{x_s <= x} q[w][s] >= targets[w nt_all + i], NaN where the row holds a NaN or no element answers.  dq null:
+// every weight is 1 (R_w = 1), so target t is the order statistic of rank t - 1.  targets: on the host, each >= 1.  The
+// pairs go through the state in batches of rows_cap <= SEL_ROWS, the caller's choice (SEL_ROW_BYTES each); on_pass() is
+// called once per pass of a batch and a group of targets (path counters).  Waits for st
+int select_rows(const double *dV, int64_t R_v, int64_t S, int64_t row_stride, int64_t elem_stride, int64_t R_w,
+                const u64 *dq, int64_t ldq, int64_t nt_all, const u64 *targets, double *dout, int64_t rows_cap,
+                void (*on_pass)(), hipStream_t st);
+
+// ---- histogram sweep over a view of rows, by count or by weight (k_marginal.hip) ------------------------
+constexpr int64_t HIST_CAP16 = 73728;   // 16-bit counters of a counted sweep: 144 KiB of LDS
+constexpr int64_t HIST_CAP64 = 18432;   // 64-bit bins of a weighted sweep: 144 KiB of LDS
+// GPEMU_ERR_ARG unless the d rows of nb + 1 edges are finite and strictly increasing
+int edges_check(const double *e, int d, int nb);
+// dhist1[w][d][nb1], dhist2[w][np][nb2][nb2] = the sums of q[w][s] (dq null: of 1, R_w = 1) over the rows s of X in each
+// bin of the host edges; dinside1[w][j] = the sum of dhist1[w][j][.].  cap: bins of one sweep, at most HIST_CAP64
+// (HIST_CAP16 without weights), at least max(nb1, nb2) (max(nb1, nb2^2)).  on_sweep(pairs) is called once per sweep,
+// pairs: it holds 2-D bins (path counters).  Waits for st
+int hist_rows(const RowsView &X, int64_t R_w, const u64 *dq, int64_t ldq, int nb1, const double *edges1, int nb2,
+              const double *edges2, int64_t cap, u64 *dhist1, u64 *dhist2, u64 *dinside1, void (*on_sweep)(bool pairs),
+              hipStream_t st);
 
 // ---- the host form of a function of device rows --------------------------------------------------------------------
 // device_ready, V [R][S] to the device, fn(dV, dout, stream) on rows of strides (S, 1), dout [R][out_per_row] back, wait

@@ -1,6 +1,7 @@
 // Sampler state shared by k_sampler.hip (stretch move, phase API, RCCL run), k_front.hip (fused run), k_temper.hip
 // (parallel tempering), k_hmc.hip (Hamiltonian Monte Carlo), k_acf.hip (autocorrelation) and the summaries of the stored
-// chain: k_postpred.hip, k_diag.hip, k_marginal.hip and what they share, k_rows.hip (rows_dev.h).
+// chain: k_postpred.hip, k_diag.hip, k_marginal.hip, k_reweight.hip and what they share, k_rows.hip and k_select.hip
+// (rows_dev.h).
 #pragma once
 #include <vector>
 
@@ -150,7 +151,7 @@ struct gpemu_sampler {
 
 namespace gpemu {
 // order-preserving 64-bit key of a double (negative: all bits flipped, else the sign bit set) and its inverse: the
-// radix select (k_postpred.hip) and the radix sort (k_rows.hip)
+// radix select (k_select.hip) and the radix sort (k_rows.hip)
 typedef unsigned long long u64;
 static __device__ __forceinline__ u64 sel_key(double v) {
   const u64 u = (u64)__double_as_longlong(v);
@@ -160,6 +161,8 @@ static __device__ __forceinline__ double sel_value(u64 key) {
   const u64 u = (key >> 63) ? (key ^ 0x8000000000000000ull) : ~key;
   return __longlong_as_double((long long)u);
 }
+// what a summary returns where no element answers: the quiet NaN
+static __device__ __forceinline__ double sel_nan() { return __longlong_as_double(0x7ff8000000000000ll); }
 // k_acf.hip: per-series sums, means and lag products of a block of series (the kernels' own comments), which
 // k_diag.hip runs on the transformed split chains
 __global__ __launch_bounds__(256) void acf_sum_kernel(const double *__restrict__ chain, int64_t n_t, int64_t S, int64_t ld, int64_t tchunk,

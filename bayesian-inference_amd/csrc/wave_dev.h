@@ -12,6 +12,13 @@ __device__ __forceinline__ double wave_sum(double v) {
   return v;
 }
 
+// the same butterfly on 64-bit integers: the sum of `v` over the wave's 64 lanes, in every lane
+__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
+  return v;
+}
+
 // the maximum of `v` over the wave's 64 lanes, in every lane: the same butterfly with fmax (NaN is passed over)
 __device__ __forceinline__ double wave_max(double v) {
 #pragma unroll
