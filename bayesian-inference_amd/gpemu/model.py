@@ -3,6 +3,7 @@ from __future__ import annotations
 
 import ctypes as C
 import math
+import sys
 
 import numpy as np
 
@@ -239,16 +240,17 @@ class DeviceModel:
         return plan.result(mean, vp, ve, order)
 
     def posterior_predictive_dev(self, dX_ptr, n_blocks, block_rows, block_stride_rows, ranks, dmean_ptr, dvar_param_ptr,
-                                 dvar_emu_ptr, dorder_ptr, workspace_bytes=0, stream=0):
+                                 dvar_emu_ptr, dorder_ptr, workspace_bytes=0, stream=None):
         """The device-pointer entry: row r of the S = n_blocks * block_rows rows is read at ``dX + ((r // block_rows) *
         block_stride_rows + r % block_rows) * d``; ``ranks`` is a host int64 array (may be empty), the outputs device
-        pointers (0: not wanted).  Waits for the stream before it returns."""
+        pointers (0: not wanted).  ``stream``: see ``_stream`` (None: torch's current stream).  Waits for the stream
+        before it returns."""
         ranks = np.ascontiguousarray(ranks, dtype=np.int64).reshape(-1)
         vp = lambda a: C.c_void_p(a) if a else None
         check(_lib.lib().gpemu_posterior_predictive_dev(
             self._h, C.c_void_p(dX_ptr), int(n_blocks), int(block_rows), int(block_stride_rows), int(ranks.size),
             ptr(ranks) if ranks.size else None, int(workspace_bytes), vp(dmean_ptr), vp(dvar_param_ptr), vp(dvar_emu_ptr),
-            vp(dorder_ptr), C.c_void_p(stream)))
+            vp(dorder_ptr), C.c_void_p(self._stream(stream)[0])))
 
     # -- global sensitivity (DESIGN.md §4.28) ----------------------------------------------------------------
     def design(self, reference, candidates, **kw):
@@ -281,11 +283,12 @@ class DeviceModel:
         A, B = self._base_pair(A, B)
         return self._sobol_moments(_lib.lib().gpemu_sobol_moments, A.shape[0], ptr(A), ptr(B), n_batches, workspace_bytes)
 
-    def sobol_moments_dev(self, dA_ptr, dB_ptr, n, n_batches=16, workspace_bytes=0, stream=0):
+    def sobol_moments_dev(self, dA_ptr, dB_ptr, n, n_batches=16, workspace_bytes=0, stream=None):
         """``sobol_moments`` of base matrices resident on the device (``dA``, ``dB``: n x d doubles); the moments come
-        back to the host.  Works on ``stream`` (0: the model's) and waits for it.  Rows are not checked."""
+        back to the host.  Works on ``stream`` (``_stream``: None is torch's current stream, 0 the model's own) and waits for
+        it.  Rows are not checked."""
         return self._sobol_moments(_lib.lib().gpemu_sobol_moments_dev, int(n), C.c_void_p(dA_ptr), C.c_void_p(dB_ptr),
-                                   n_batches, workspace_bytes, C.c_void_p(stream))
+                                   n_batches, workspace_bytes, C.c_void_p(self._stream(stream)[0]))
 
     def _sobol_moments(self, fn, n, A, B, n_batches, workspace_bytes, *tail):
         T, d, k = int(n_batches), self.d, self.k
@@ -403,12 +406,12 @@ class DeviceModel:
             T -= 0.5 * math.log(2.0 * math.pi) * self._block_features()[:, None]
         return T
 
-    def loglik_pointwise_dev(self, dX_ptr, n_blocks, block_rows, block_stride_rows, dT_ptr, ldt, chain=0, stream=0):
+    def loglik_pointwise_dev(self, dX_ptr, n_blocks, block_rows, block_stride_rows, dT_ptr, ldt, chain=0, stream=None):
         """The device-pointer entry: rows in the block layout of ``posterior_predictive_dev``, ``T`` block-major with
         ``ldt >= n_blocks * block_rows`` doubles per observable.  Waits for the stream before it returns."""
         check(_lib.lib().gpemu_loglik_pointwise_dev(self._h, int(chain), C.c_void_p(dX_ptr), int(n_blocks), int(block_rows),
                                                     int(block_stride_rows), C.c_void_p(dT_ptr), int(ldt),
-                                                    C.c_void_p(stream)))
+                                                    C.c_void_p(self._stream(stream)[0])))
 
     # -- derivatives with respect to the parameters (DESIGN.md §4.24) -------------------------------------
     def gp_predict_grad(self, X):
@@ -434,28 +437,67 @@ class DeviceModel:
         check(_lib.lib().gpemu_logpost_grad(self._h, B, ptr(X), ptr(lp), ptr(grad), int(mode)))
         return lp, grad
 
-    def logpost_grad_dev(self, dX_ptr, B, dlp_ptr, dgrad_ptr, mode=LOWRANK, stream=0):
+    def logpost_grad_dev(self, dX_ptr, B, dlp_ptr, dgrad_ptr, mode=LOWRANK, stream=None):
+        """``logpost_grad`` on device pointers.  ``stream`` as in ``logpost_dev`` (see ``_stream``)."""
+        st, settle = self._stream(stream)
         check(_lib.lib().gpemu_logpost_grad_dev(self._h, int(B), C.c_void_p(dX_ptr), C.c_void_p(dlp_ptr),
-                                                C.c_void_p(dgrad_ptr), int(mode), C.c_void_p(stream)))
+                                                C.c_void_p(dgrad_ptr), int(mode), C.c_void_p(st)))
+        settle()
 
-    # -- device-pointer API (torch tensors on this device; stream = torch's current stream) ----
-    def logpost_dev(self, dX_ptr, B, dout_ptr, mode=LOWRANK, stream=0):
+    # -- device-pointer API (torch tensors on this device) ----------------------------------------------
+    def _stream(self, stream):
+        """``(handle, settle)`` of a ``_dev`` call.  ``stream`` is a stream handle as an integer -- 0: the model's own
+        stream, which is a non-blocking one: not ordered with any torch stream, torch's default stream included; the
+        caller synchronises before the call and ``sync()`` after it -- or None: torch's current stream on this device.
+        Torch's default stream is the null stream, whose handle 0 the model-bound entries read as "the model's own
+        stream": it is then waited for on the host before the call, and ``settle()`` waits for the model's stream after
+        it, so that the call reads what the caller's torch work wrote and torch work that follows reads its results.  On
+        any other torch stream the call is enqueued there and nothing waits.  Without torch in the process None is 0."""
+        nothing = lambda: None
+        if stream is not None:
+            return int(stream), nothing
+        torch = sys.modules.get("torch")
+        if torch is None or not torch.cuda.is_initialized():
+            return 0, nothing
+        s = torch.cuda.current_stream(torch.device("cuda", self.device))
+        if s.cuda_stream:
+            return int(s.cuda_stream), nothing
+        s.synchronize()
+        return 0, self.sync
+
+    def logpost_dev(self, dX_ptr, B, dout_ptr, mode=LOWRANK, stream=None):
+        """``logpost`` on device pointers.  ``stream`` (see ``_stream``): None is torch's current stream -- on a side
+        stream the call is enqueued there and does not wait; on torch's default stream it blocks the host, before and
+        after.  A loop that must stay asynchronous there passes ``stream=0`` (the model's own stream) and orders it
+        itself with ``sync()``."""
+        st, settle = self._stream(stream)
         check(_lib.lib().gpemu_logpost_dev(self._h, int(B), C.c_void_p(dX_ptr), C.c_void_p(dout_ptr),
-                                           int(mode), C.c_void_p(stream)))
+                                           int(mode), C.c_void_p(st)))
+        settle()
 
-    def gp_predict_dev(self, dX_ptr, B, dmean_ptr, dvar_ptr, stream=0):
+    def gp_predict_dev(self, dX_ptr, B, dmean_ptr, dvar_ptr, stream=None):
+        """``gp_predict`` on device pointers.  ``stream`` as in ``logpost_dev`` (see ``_stream``)."""
+        st, settle = self._stream(stream)
         check(_lib.lib().gpemu_gp_predict_dev(self._h, int(B), C.c_void_p(dX_ptr), C.c_void_p(dmean_ptr),
-                                              C.c_void_p(dvar_ptr), C.c_void_p(stream)))
+                                              C.c_void_p(dvar_ptr), C.c_void_p(st)))
+        settle()
 
-    def gp_predict_cov_dev(self, dX1_ptr, M1, dX2_ptr, M2, dmean_ptr, dcov_ptr, workspace_bytes=0, stream=0):
+    def gp_predict_cov_dev(self, dX1_ptr, M1, dX2_ptr, M2, dmean_ptr, dcov_ptr, workspace_bytes=0, stream=None):
+        """``gp_predict_cov`` on device pointers (0: no X2 / no mean).  ``stream``: see ``_stream``; the entry waits for
+        its stream before it returns."""
+        st, settle = self._stream(stream)
         check(_lib.lib().gpemu_gp_predict_cov_dev(self._h, int(M1), C.c_void_p(dX1_ptr), int(M2),
                                                   C.c_void_p(dX2_ptr) if dX2_ptr else None, int(workspace_bytes),
                                                   C.c_void_p(dmean_ptr) if dmean_ptr else None, C.c_void_p(dcov_ptr),
-                                                  C.c_void_p(stream)))
+                                                  C.c_void_p(st)))
+        settle()
 
-    def predict_full_dev(self, dX_ptr, B, n_div, dcv_ptr, dcov_ptr, stream=0):
+    def predict_full_dev(self, dX_ptr, B, n_div, dcv_ptr, dcov_ptr, stream=None):
+        """``predict_full`` on device pointers.  ``stream`` as in ``logpost_dev`` (see ``_stream``)."""
+        st, settle = self._stream(stream)
         check(_lib.lib().gpemu_predict_full_dev(self._h, int(B), C.c_void_p(dX_ptr), float(n_div),
-                                                C.c_void_p(dcv_ptr), C.c_void_p(dcov_ptr), C.c_void_p(stream)))
+                                                C.c_void_p(dcv_ptr), C.c_void_p(dcov_ptr), C.c_void_p(st)))
+        settle()
 
 
 def logpost_groups(models, X, mode=LOWRANK):

@@ -308,8 +308,7 @@ def data_log_ratio_dev(models_old, models_new, view, chain=0):
         T = torch.empty((sum(nobs), S), dtype=torch.float64, device=torch.device("cuda", int(device)))
         o0 = 0
         for m, nb in zip(models, nobs):
-            m.loglik_pointwise_dev(src, n_blocks, nw, stride, T[o0].data_ptr(), S, chain=chain,
-                                   stream=_lib.current_stream(device).value or 0)
+            m.loglik_pointwise_dev(src, n_blocks, nw, stride, T[o0].data_ptr(), S, chain=chain)
             o0 += nb
         sums.append(LO.group_rows_dev(device, T.data_ptr(), int(T.shape[0]), S, S, [list(range(int(T.shape[0])))]))
     return sums[0] - sums[1]

@@ -419,8 +419,7 @@ class DeviceSampler:
         for g, (m, nb) in enumerate(zip(models, nobs)):
             if m.d != self.d or m.device != self.device:
                 raise ValueError("model and sampler differ in parameters or device")
-            m.loglik_pointwise_dev(src, n_blocks, nw, stride, T[o0].data_ptr(), S, chain=self._data_chain(chain),
-                                   stream=_lib.current_stream(self.device).value or 0)
+            m.loglik_pointwise_dev(src, n_blocks, nw, stride, T[o0].data_ptr(), S, chain=self._data_chain(chain))
             labels += [f"g{g}o{o}" for o in range(nb)]
             o0 += nb
         whole = thin == 1 and nw == self.W      # else a thinned or stacked view: the same reduction, uniform weights

@@ -9,9 +9,18 @@
  *
  * Conventions
  *   - extern "C", plain pointers and sizes.  All real arrays are row-major float64, indices int64.
- *   - Buffers are caller-allocated.  Functions named *_dev take DEVICE pointers and a hipStream_t
- *     (passed as void*; NULL = the handle's own stream) and do not synchronise; the others take
- *     HOST pointers, copy, run and synchronise before returning.
+ *   - Buffers are caller-allocated.  Functions named *_dev take DEVICE pointers and a hipStream_t (passed as void*), on
+ *     which all their work is enqueued; the others take HOST pointers, copy, run and synchronise before returning.
+ *     What NULL means and whether a *_dev call waits for its stream before it returns depends on the family:
+ *       - gpemu_gp_predict_dev, gpemu_predict_full_dev, gpemu_logpost_dev, gpemu_gp_predict_grad_dev and
+ *         gpemu_logpost_grad_dev: NULL = the model's own stream; they do not synchronise (a first call, or one that
+ *         has to regrow the model's workspace, allocates and frees, which may wait for the device);
+ *       - every other *_dev entry waits for its stream before it returns, because its scratch goes with the call or its
+ *         results are host arrays; its section says what NULL means: the model's stream for the entries bound to a
+ *         model, the null stream for the device-wide families.
+ *     A model's own stream is a non-blocking stream: it is NOT ordered with the null stream or with any other stream.
+ *     Work the caller enqueued elsewhere must have finished before a call on the model's stream reads it, and
+ *     gpemu_model_sync comes before anything else reads the results.
  *   - Every function returns int: 0 = ok, <0 = argument / runtime error, >0 = numerical failure
  *     (e.g. index+1 of a non-positive Cholesky pivot).  gpemu_last_error() gives the thread-local
  *     message of the last failure.
@@ -106,7 +115,8 @@ int gpemu_gp_predict_dev(gpemu_model *m, int64_t B, const double *dX, double *dm
 
 /* skl _gpr.py:367-469 predict(X, return_cov=True), per PC: cov_out[p*M1*M2 + a*M2 + b] = kernel_(x1_a, x2_b)
  * - V1_a . V2_b.  X2 == NULL: the symmetric form on X1 (noise on the diagonal, exactly symmetric output).
- * mean_out[M1*k] may be NULL.  workspace_bytes = 0: sized from free device memory. */
+ * mean_out[M1*k] may be NULL.  workspace_bytes = 0: sized from free device memory.  The _dev form works on `stream`
+ * (NULL = the model's) and waits for it before it returns: its workspace goes with the call. */
 int gpemu_gp_predict_cov(gpemu_model *m, int64_t M1, const double *X1, int64_t M2, const double *X2,
                          int64_t workspace_bytes, double *mean_out, double *cov_out);
 int gpemu_gp_predict_cov_dev(gpemu_model *m, int64_t M1, const double *dX1, int64_t M2, const double *dX2,
@@ -323,7 +333,9 @@ int gpemu_sampler_get_swap_counts(gpemu_sampler *s, int64_t *accepted, int64_t *
  * (a fixed-order device reduction: the same bits on every call) -- the thermodynamic-integration input */
 int gpemu_sampler_mean_loglik(gpemu_sampler *s, int64_t first, int64_t n, double *out /*[n_temps]*/);
 int gpemu_sampler_destroy(gpemu_sampler *s);
-int gpemu_sampler_set_stream(gpemu_sampler *s, void *stream); /* NULL = the first group's stream */
+/* The stream of every later call on the sampler; NULL = the first group's stream.  Waits for the stream in use so far.
+ * The caller's stream must outlive its use; gpemu_sampler_run waits for it before it returns. */
+int gpemu_sampler_set_stream(gpemu_sampler *s, void *stream);
 /* X0[W*d]; logp0[W] or NULL to evaluate it (ref: mcmc.py:88, emcee State(initial_state)) */
 int gpemu_sampler_set_state(gpemu_sampler *s, const double *X0, const double *logp0);
 int gpemu_sampler_get_state(gpemu_sampler *s, double *X, double *logp);
@@ -383,7 +395,7 @@ int gpemu_comm_create(gpemu_comm **out, int device, int rank, int world, const c
                       const char *librccl_path);
 int gpemu_comm_destroy(gpemu_comm *c);
 int gpemu_comm_dims(const gpemu_comm *c, int *rank, int *world);
-/* all-gather of `count` doubles per rank, DEVICE pointers, enqueued on `stream` */
+/* all-gather of `count` doubles per rank, DEVICE pointers, enqueued on `stream` (NULL = the null stream); does not wait */
 int gpemu_comm_all_gather(gpemu_comm *c, const double *dsend, double *drecv, int64_t count, void *stream);
 /* `steps` stretch-move steps with each half's proposals split over the communicator's ranks (contiguous
  * blocks of ceil(n/world)); one 8-byte-per-proposal all-gather per half-step, no host round trip inside
@@ -525,7 +537,7 @@ int gpemu_src_path_counts(int64_t *out, int64_t n);
  * on the grid, on the scratch or on the run.  R, S, n_ranks >= 1 and every rank in [0, S), else GPEMU_ERR_ARG.
  * The _dev form reads element j of row r at dV[r*row_stride + j*elem_stride] (strides in doubles, > 0: a parameter of
  * the device chain [steps][W][d] is the "row" j with row_stride 1, elem_stride d); ranks[] is a HOST array, dout
- * [R*n_ranks] a device array; stream NULL = the null stream.  It waits for the stream before it returns (its scratch
+ * [R*n_ranks] a device array; works on `stream` (NULL = the null stream) and waits for it before it returns (its scratch
  * goes with the call). */
 int gpemu_select(int device, int64_t R, int64_t S, const double *V, int64_t n_ranks, const int64_t *ranks, double *out);
 int gpemu_select_dev(int device, int64_t R, int64_t S, const double *dV, int64_t row_stride, int64_t elem_stride,
@@ -645,6 +657,8 @@ int gpemu_rank_dev(int device, int64_t R, int64_t S, const double *dV, int64_t r
  * Memory: one buffer of n*nw*d doubles (the transformed series Y, or the dense segment while a median or quantile is
  * selected), the select's and the sort's scratch for a batch of parameters (gpemu_rank_dev's bound with S = 2*N*nw,
  * within workspace_bytes; 0 = half of the free memory) and the lag-block scratch of gpemu_sampler_acf.
+ * _create_dev works on `stream` (NULL = the null stream) and waits for it; the handle's later calls run on that stream
+ * and wait for it, so it must outlive the handle.
  *
  * gpemu_diag_transform writes Y[N][2*nw*d], series (h*nw + w)*d + dd, for one of the kinds below and returns the split
  * chains' moments, sums in a fixed order (two passes, then a tree): grand_mean[d] = the mean of the 2*nw chain means,
@@ -839,7 +853,8 @@ int gpemu_marginal_path_counts(int64_t *out, int64_t n);
  * before any launch: P < 1; G outside [1, 512]; d outside [1, 16]; S < 1 or S >= 2^31; a pair index outside [0, d) or
  * i = j; a bandwidth that is not finite and > 0; a grid value or shear that is not finite; workspace_bytes < 0.
  * gpemu_kde2d takes host samples X[S*d] and host out[P*G*G]; _dev reads the rows in the block layout of
- * gpemu_marginal_hist_dev in place, writes the device array dout[P*G*G], works on `stream` and waits for it.
+ * gpemu_marginal_hist_dev in place, writes the device array dout[P*G*G], works on `stream` (NULL = the null stream) and
+ * waits for it; so does gpemu_pair_moments_dev.
  *
  * gpemu_pair_moments_dev: what the default plan needs of device rows in the same layout.  mean[d] and cov[d*d] (the
  * full covariance, divisor S; both NULL: skipped) by two passes with sums in a fixed order; for n_pairs > 0 pairs with
@@ -905,7 +920,8 @@ int gpemu_kde2d_path_counts(int64_t *out, int64_t n);
  * dlogw[r*ldw + s]: dmean[r*d + j] = sum_s w x_sj / sum_s w, dvar[r*d + j] = sum_s w (x_sj - mean)^2 / sum_s w, w =
  * exp(logw): the leave-one-observable-out posterior moments.  Two passes, the same fixed tree.
  * gpemu_loo_group_rows_dev: dout[g*ldo + s] = the sum of rows rows[group_start[g] .. group_start[g+1]) of dT[R][ldt] at s,
- * added in the given order (group_start, rows: HOST): a class of observables left out together. */
+ * added in the given order (group_start, rows: HOST): a class of observables left out together.
+ * Both work on `stream` (NULL = the null stream) and wait for it, as gpemu_psis_dev does. */
 #define GPEMU_PSIS_ELPD_LOO 0
 #define GPEMU_PSIS_LPPD 1
 #define GPEMU_PSIS_P_LOO 2
@@ -1011,7 +1027,7 @@ int gpemu_design_path_counts(int64_t *out, int64_t n);
  * i < n <= S = n_blocks*block_rows < 2^31: two separately rounded operations, the bits of the same numpy expression.
  * Logical row r is at dX + (r / block_rows)*block_stride + (r % block_rows)*d: block_stride counts ELEMENTS (a step of
  * a chain may be padded to a length that is no multiple of d) and holds at least a block.  A row with a non-finite coordinate becomes a row of NaN -- the search passes it over -- and is
- * counted in *n_skipped.  lower, upper, n_skipped: HOST.  Works on `stream` and waits for it.
+ * counted in *n_skipped.  lower, upper, n_skipped: HOST.  Works on `stream` (NULL = the null stream) and waits for it.
  *
  * gpemu_knn_dist: queries UQ[nq*d], references UR[nr*d] (NULL: the queries themselves, nr = nq), n_subsets subsets of
  * the d coordinates as 32-bit masks (bit j: coordinate j; HOST), 1 <= k <= 16:
@@ -1032,13 +1048,14 @@ int gpemu_design_path_counts(int64_t *out, int64_t n);
  * subsets; a chosen Z shrinks to what fits; if a forced Z does not fit for one subset: GPEMU_ERR_HIP.
  * GPEMU_ERR_ARG before any launch: k outside [1, 16]; d outside [1, 16]; a mask that is 0 or has a bit >= d; nq or nr
  * outside [1, 2^31); n_subsets outside [1, 2^20]; splits outside [0, 64]; workspace_bytes < 0; no references and
- * nr != nq.  _dev reads dense device rows, writes the device arrays dr2 and dzeros, works on `stream`, waits for it.
+ * nr != nq.  _dev reads dense device rows, writes the device arrays dr2 and dzeros, works on `stream` (NULL = the null
+ * stream) and waits for it.
  *
  * gpemu_knn_logsum_dev: per subset p of dr2[n_subsets*n] (and dzeros, or NULL), counts[3p ..] = n_used (rows whose
  * distance is finite), n_short (+inf), copies (the sum of zeros); sums[2p ..] = the sum of v and of v^2 over the used
  * rows, v = log r2.  With dnu2 (the same shape): v = log nu2 - log r2, and a row is used if both are finite, short if
  * one is +inf.  A NaN distance passes the row over.  Blocks of 1024 rows and then the blocks, each in a fixed tree.
- * counts (int64) and sums: HOST. */
+ * counts (int64) and sums: HOST.  Works on `stream` (NULL = the null stream) and waits for it. */
 #define GPEMU_KNN_MAX_K 16
 #define GPEMU_KNN_REF_TILE 256
 int gpemu_unit_rows_dev(int device, const double *dX, int64_t n_blocks, int64_t block_rows, int64_t block_stride, int d,
@@ -1088,7 +1105,8 @@ int gpemu_knn_path_counts(int64_t *out, int64_t n);
  * GPEMU_ERR_ARG before any launch: n or S outside [1, 2^31); F outside [1, 65536]; a self[i] outside [-1, S); a leading
  * dimension below F; workspace_bytes < 0; a null Y, Z or lse.
  * _dev: every array is DEVICE memory (dself, dcentre, dess may be NULL); row i of Y starts at dY + i*ldy, of Z at
- * dZ + i*ldz; works on `stream` and waits for it (dself is copied to the host and checked first). */
+ * dZ + i*ldz; works on `stream` (NULL = the null stream) and waits for it (dself is copied to the host and checked
+ * first); so does gpemu_pairlse_centre_dev. */
 #define GPEMU_PAIRLSE_CHUNK 2048
 #define GPEMU_PAIRLSE_TILE_ROWS 64
 #define GPEMU_PAIRLSE_BLOCK_BYTES(S, F) \

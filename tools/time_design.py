@@ -49,7 +49,7 @@ def timed(fn):
 
 
 def unfused():
-    dm.gp_predict_cov_dev(dR.data_ptr(), S, dC.data_ptr(), M, 0, cov.data_ptr())
+    dm.gp_predict_cov_dev(dR.data_ptr(), S, dC.data_ptr(), M, 0, cov.data_ptr(), stream=0)
     num = (cov * cov).sum(dim=1) / S
     torch.cuda.synchronize()
     return num

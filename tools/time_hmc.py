@@ -98,7 +98,7 @@ def time_gradient(shape):
 
     def call():
         for m in dms:
-            m.logpost_grad_dev(X.data_ptr(), W, lp.data_ptr(), gr.data_ptr())
+            m.logpost_grad_dev(X.data_ptr(), W, lp.data_ptr(), gr.data_ptr(), stream=0)
     ms = median_ms(call, dms[0].sync, 10)
     for m in dms:
         m.close()

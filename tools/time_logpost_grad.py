@@ -69,9 +69,9 @@ def run(value_only, do_map):
             torch.cuda.synchronize()
             reps = 40 if B <= 64 else 10
             rec = {"shape": "C3", "blocks": nb, "B": B, "d": d,
-                   "value_ms": median_ms(lambda: dm.logpost_dev(X.data_ptr(), B, lp.data_ptr()), dm.sync, reps)}
+                   "value_ms": median_ms(lambda: dm.logpost_dev(X.data_ptr(), B, lp.data_ptr(), stream=0), dm.sync, reps)}
             if not value_only:
-                rec["value_grad_ms"] = median_ms(lambda: dm.logpost_grad_dev(X.data_ptr(), B, lp.data_ptr(), gr.data_ptr()),
+                rec["value_grad_ms"] = median_ms(lambda: dm.logpost_grad_dev(X.data_ptr(), B, lp.data_ptr(), gr.data_ptr(), stream=0),
                                                  dm.sync, reps)
             out.append(rec)
             print(json.dumps(rec), flush=True)

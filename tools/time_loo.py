@@ -142,7 +142,7 @@ def main():
             v = torch.empty((S, dm.k), dtype=torch.float64, device="cuda:0")
             for r0 in range(0, S, CHUNK):
                 nb = min(CHUNK, S - r0)
-                dm.gp_predict_dev(X[r0:r0 + nb].data_ptr(), nb, m[r0:r0 + nb].data_ptr(), v[r0:r0 + nb].data_ptr())
+                dm.gp_predict_dev(X[r0:r0 + nb].data_ptr(), nb, m[r0:r0 + nb].data_ptr(), v[r0:r0 + nb].data_ptr(), stream=0)
             dm.sync()
             hm, hv = m.cpu().numpy(), v.cpu().numpy()
             t1 = time.perf_counter()

@@ -41,7 +41,7 @@ def baseline(dm, wl, X, host_features):
     v = torch.empty((S, k), dtype=torch.float64, device=X.device)
     for r0 in range(0, S, CHUNK):
         nb = min(CHUNK, S - r0)
-        dm.gp_predict_dev(X[r0:r0 + nb].data_ptr(), nb, m[r0:r0 + nb].data_ptr(), v[r0:r0 + nb].data_ptr())
+        dm.gp_predict_dev(X[r0:r0 + nb].data_ptr(), nb, m[r0:r0 + nb].data_ptr(), v[r0:r0 + nb].data_ptr(), stream=0)
     dm.sync()
     t_predict = time.perf_counter() - t0
     t_dev = t_host = 0.0
@@ -80,7 +80,7 @@ def new_path(dm, X):
     c0 = postpred_path_counts()
     t0 = time.perf_counter()
     dm.posterior_predictive_dev(X.data_ptr(), 1, S, S, plan.ranks, bufs[0].data_ptr(), bufs[1].data_ptr(),
-                                bufs[2].data_ptr(), order.data_ptr())
+                                bufs[2].data_ptr(), order.data_ptr(), stream=0)
     h = bufs.cpu().numpy()
     out = plan.result(h[0], h[1], h[2], order.cpu().numpy())
     dt = time.perf_counter() - t0

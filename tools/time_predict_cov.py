@@ -27,12 +27,12 @@ for M in Ms:
     X = torch.tensor(synthetic.make_walkers(M, seed=5), dtype=torch.float64, device="cuda:0")
     cov = torch.empty((k, M, M), dtype=torch.float64, device="cuda:0")
     torch.cuda.synchronize()
-    dm.gp_predict_cov_dev(X.data_ptr(), M, 0, 0, 0, cov.data_ptr())   # warm-up (and the workspace's first allocation)
+    dm.gp_predict_cov_dev(X.data_ptr(), M, 0, 0, 0, cov.data_ptr(), stream=0)   # warm-up (and the workspace's first allocation)
     dm.sync()
     reps = 20 if M <= 2048 else 8
     t0 = time.perf_counter()
     for _ in range(reps):
-        dm.gp_predict_cov_dev(X.data_ptr(), M, 0, 0, 0, cov.data_ptr())
+        dm.gp_predict_cov_dev(X.data_ptr(), M, 0, 0, 0, cov.data_ptr(), stream=0)
     dm.sync()
     ms = (time.perf_counter() - t0) / reps * 1e3
     flop = k * (N * N * M + N * M * M)

@@ -24,11 +24,11 @@ for B in [int(a) for a in (sys.argv[1:] or ["64", "128"])]:
     X = torch.from_numpy(synthetic.make_walkers(B, seed=1)).to(dev)
     out = torch.empty(B, dtype=torch.float64, device=dev)
     for _ in range(300):                                   # clock ramp
-        dm.logpost_dev(X.data_ptr(), B, out.data_ptr())
+        dm.logpost_dev(X.data_ptr(), B, out.data_ptr(), stream=0)
     dm.sync()
     dm.profile(True)
     for _ in range(300):
-        dm.logpost_dev(X.data_ptr(), B, out.data_ptr())
+        dm.logpost_dev(X.data_ptr(), B, out.data_ptr(), stream=0)
     dm.sync()
     pr = dm.profile_read()
     dm.profile(False)
