@@ -1,5 +1,6 @@
 // Host-side ownership of device memory (included at the end of internal.h).  Every hipMalloc and hipFree of the library
-// is in this header, but for the one uncached allocation of k_pca.hip, which a DevScope adopts.  Three owners:
+// is in this header, and every one of them feeds the ledger (devledger.h), which also decides the tests' one-shot
+// refusal before the allocator is called.  Three owners:
 //   - a temporary that does not outlive the call: DevScope;
 //   - a buffer a handle keeps and regrows on demand: dev_reserve;
 //   - a fixed field of a handle: dev_alloc into the struct, dev_free in the handle's *_destroy.
@@ -8,17 +9,28 @@
 #pragma once
 #include <initializer_list>
 
+#include "devledger.h"
+
 namespace gpemu {
+
+// the ledger's one-shot refusal, asked before any HIP call of an allocation
+static inline int dev_alloc_refused(size_t bytes) {
+  if (!dev_ledger().refuse_now()) return GPEMU_OK;
+  set_error("device allocation of %zu bytes refused (gpemu_devmem_refuse_nth)", bytes);
+  return GPEMU_ERR_HIP;
+}
 
 // every allocation of the library: one error text (the bytes asked for, HIP's reason)
 static inline int dev_alloc_bytes(void **p, size_t bytes) {
   *p = nullptr;
+  GP_TRY(dev_alloc_refused(bytes));
   const hipError_t e = hipMalloc(p, bytes);
   if (e != hipSuccess) {
     *p = nullptr;
     set_error("device allocation of %zu bytes failed: %s", bytes, hipGetErrorString(e));
     return GPEMU_ERR_HIP;
   }
+  dev_ledger().note(*p, bytes);
   return GPEMU_OK;
 }
 
@@ -33,17 +45,69 @@ static int dev_alloc(T **p, int64_t n) { return dev_alloc_bytes((void **)p, dev_
 template <typename T>
 static int dev_alloc_uncached(T **p, int64_t n, bool *uncached) {
   *p = nullptr;
+  *uncached = false;
+  GP_TRY(dev_alloc_refused(dev_bytes<T>(n)));   // one allocation, whichever branch serves it
   *uncached = hipExtMallocWithFlags((void **)p, dev_bytes<T>(n), hipDeviceMallocUncached) == hipSuccess;
-  if (*uncached) return GPEMU_OK;
+  if (*uncached) {
+    dev_ledger().note((void *)*p, dev_bytes<T>(n));
+    return GPEMU_OK;
+  }
   (void)hipGetLastError();
-  return dev_alloc(p, n);
+  *p = nullptr;
+  const hipError_t e = hipMalloc((void **)p, dev_bytes<T>(n));
+  if (e != hipSuccess) {
+    *p = nullptr;
+    set_error("device allocation of %zu bytes failed: %s", dev_bytes<T>(n), hipGetErrorString(e));
+    return GPEMU_ERR_HIP;
+  }
+  dev_ledger().note((void *)*p, dev_bytes<T>(n));
+  return GPEMU_OK;
 }
 
 // frees a handle's field and nulls it.  The caller has synchronised whatever may still use it.
 template <typename T>
 static void dev_free(T *&p) {
-  (void)hipFree((void *)p);
+  if (p) {
+    dev_ledger().forget((const void *)p);
+    (void)hipFree((void *)p);
+  }
   p = nullptr;
+}
+
+// the streams and events a handle owns: created and destroyed here, so that the ledger counts them
+static inline hipError_t stream_create(hipStream_t *st, unsigned flags) {
+  const hipError_t e = hipStreamCreateWithFlags(st, flags);
+  if (e == hipSuccess) dev_ledger().stream_made();
+  return e;
+}
+static inline hipError_t stream_create(hipStream_t *st, unsigned flags, int priority) {
+  const hipError_t e = hipStreamCreateWithPriority(st, flags, priority);
+  if (e == hipSuccess) dev_ledger().stream_made();
+  return e;
+}
+static inline hipError_t stream_create_cu_mask(hipStream_t *st, uint32_t words, const uint32_t *mask) {
+  const hipError_t e = hipExtStreamCreateWithCUMask(st, words, mask);
+  if (e == hipSuccess) dev_ledger().stream_made();
+  return e;
+}
+static inline void stream_destroy(hipStream_t &st) {
+  if (st) {
+    (void)hipStreamDestroy(st);
+    dev_ledger().stream_gone();
+  }
+  st = nullptr;
+}
+static inline hipError_t event_create(hipEvent_t *ev, unsigned flags = hipEventDefault) {
+  const hipError_t e = hipEventCreateWithFlags(ev, flags);
+  if (e == hipSuccess) dev_ledger().event_made();
+  return e;
+}
+static inline void event_destroy(hipEvent_t &ev) {
+  if (ev) {
+    (void)hipEventDestroy(ev);
+    dev_ledger().event_gone();
+  }
+  ev = nullptr;
 }
 
 // asynchronous copy of n elements from host memory, which the caller keeps alive until `st` is synchronised
@@ -64,7 +128,10 @@ class DevScope {
   ~DevScope() {
     if (held_.empty()) return;
     (void)hipStreamSynchronize(st_);
-    for (void *q : held_) (void)hipFree(q);
+    for (void *q : held_) {
+      dev_ledger().forget(q);
+      (void)hipFree(q);
+    }
   }
   template <typename T>
   int alloc(T **p, int64_t n) {
@@ -72,11 +139,13 @@ class DevScope {
     held_.push_back((void *)*p);
     return GPEMU_OK;
   }
-  // takes over a pointer allocated some other way (null: nothing to own)
-  void adopt(void *p) {
-    if (p) held_.push_back(p);
+  template <typename T>
+  int alloc_uncached(T **p, int64_t n, bool *uncached) {
+    GP_TRY(dev_alloc_uncached(p, n, uncached));
+    held_.push_back((void *)*p);
+    return GPEMU_OK;
   }
-  // gives p up to a longer-lived owner
+  // gives p up to a longer-lived owner (the block stays live in the ledger)
   template <typename T>
   T *release(T *p) {
     for (size_t i = 0; i < held_.size(); ++i)

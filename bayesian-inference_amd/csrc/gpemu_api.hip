@@ -45,6 +45,12 @@ int read_path_counts(PathFamily family, int64_t *out, int64_t n) {
   return size;
 }
 
+// the one ledger of device resources (devledger.h), fed by devmem.h from every translation unit
+DevLedger &dev_ledger() {
+  static DevLedger ledger;
+  return ledger;
+}
+
 void set_error(const char *fmt, ...) {
   va_list ap;
   va_start(ap, fmt);
@@ -133,7 +139,7 @@ int prof_mark(gpemu_model *m, hipStream_t st) {
   }
   if (m->ev_next >= m->ev_pool.size()) {
     hipEvent_t e;
-    if (hipEventCreate(&e) != hipSuccess) return -1;
+    if (event_create(&e) != hipSuccess) return -1;
     m->ev_pool.push_back(e);
   }
   int idx = (int)m->ev_next++;
@@ -195,6 +201,29 @@ static bool groups_fit(gpemu_model *const *ms, int ng, int64_t B) {
 // `pa` builds them there.  In order of preference: (1) cross-kernel and GEMM of every group in one launch (small
 // emulators, k_halfstep.hip); (2) for several groups, one launch per stage; (3) group by group, the groups after the
 // first adding to dout.  Stacked chains take neither (1) nor (2).  Every form gives the same bits.
+// what the groups' setups must agree on before anything is evaluated; the host-array entries ask it before they stage
+// their rows, so that a call that is declined has allocated nothing
+static int logpost_groups_ready(gpemu_model *const *ms, int ng) {
+  for (int g = 0; g < ng; ++g)
+    if (!ms[g]->lik_ready) { set_error("gpemu_likelihood_setup has not been called"); return GPEMU_ERR_STATE; }
+  for (int g = 1; g < ng; ++g)
+    if (ms[g]->n_src != ms[0]->n_src) {
+      set_error("groups set up with different numbers of correlated sources (%d and %d)", ms[0]->n_src, ms[g]->n_src);
+      return GPEMU_ERR_STATE;
+    }
+  return GPEMU_OK;
+}
+// ... and a single model's mode
+static int logpost_mode_ready(const gpemu_model *m, int mode) {
+  GP_ARG(mode == GPEMU_LOGPOST_LOWRANK || mode == GPEMU_LOGPOST_EXACT, "mode");
+  if (!m->lik_ready) { set_error("gpemu_likelihood_setup has not been called"); return GPEMU_ERR_STATE; }
+  if (mode == GPEMU_LOGPOST_EXACT && m->n_src > 0) {
+    set_error("GPEMU_LOGPOST_EXACT does not support correlated sources (n_src = %d): use GPEMU_LOGPOST_LOWRANK", m->n_src);
+    return GPEMU_ERR_UNSUPPORTED;
+  }
+  return GPEMU_OK;
+}
+
 int logpost_eval(gpemu_model *const *ms, int ng, int64_t B, double *dXq, double *dout, hipStream_t st,
                  const LaunchSwitches &sw, const AcceptArgs *aa, const ProposeArgs *pa, const LiveCols *lv) {
   if (lv && (ng != 1 || ms[0]->n_src != 0 || (aa && aa->chain_per != 0) || halfstep_fits(ms, 1, B, sw) ||
@@ -202,15 +231,9 @@ int logpost_eval(gpemu_model *const *ms, int ng, int64_t B, double *dXq, double 
     set_error("logpost_eval: compacted columns outside the general path of one group");   // (the caller's eligibility test)
     return GPEMU_ERR_STATE;
   }
-  for (int g = 0; g < ng; ++g)
-    if (!ms[g]->lik_ready) { set_error("gpemu_likelihood_setup has not been called"); return GPEMU_ERR_STATE; }
+  GP_TRY(logpost_groups_ready(ms, ng));
   // correlated sources (k_srccorr.hip): one set of sources for all groups, whose term follows the likelihood stage
   const int S = ms[0]->n_src;
-  for (int g = 1; g < ng; ++g)
-    if (ms[g]->n_src != S) {
-      set_error("groups set up with different numbers of correlated sources (%d and %d)", S, ms[g]->n_src);
-      return GPEMU_ERR_STATE;
-    }
   // Stacked chains: a row's chain selects its data vector in a group whose CURRENT setup carries one per chain; a group
   // set up with one vector serves every chain with it (by_chain_of).  A setup with fewer vectors than the rows have chains
   // -- changed under a live sampler -- is refused before anything is launched: g0 / scal / w0 end at its last vector.
@@ -301,6 +324,21 @@ int gpemu_wide_path_counts(int64_t *out, int64_t n) { return read_path_counts(PA
 int gpemu_src_path_counts(int64_t *out, int64_t n) { return read_path_counts(PATHS_SRC, out, n); }
 int gpemu_grad_path_counts(int64_t *out, int64_t n) { return read_path_counts(PATHS_GRAD, out, n); }
 
+int gpemu_devmem_stats(int64_t *out, int64_t n) {
+  GP_ARG(out && n >= 0, "out, n");
+  const DevLedger::Stats s = dev_ledger().stats();
+  const int64_t v[GPEMU_DEVMEM_STAT_COUNT] = {s.live_blocks, s.live_bytes, s.allocs, s.frees, s.live_streams, s.live_events};
+  for (int64_t i = 0; i < n && i < GPEMU_DEVMEM_STAT_COUNT; ++i) out[i] = v[i];
+  return GPEMU_DEVMEM_STAT_COUNT;
+}
+
+int gpemu_devmem_refuse_nth(int64_t nth, int64_t *still_armed) {
+  GP_ARG(nth >= 0, "nth >= 0");
+  const bool was = dev_ledger().arm(nth);
+  if (still_armed) *still_armed = was ? 1 : 0;
+  return GPEMU_OK;
+}
+
 int gpemu_device_count(void) {
   int n = 0;
   if (hipGetDeviceCount(&n) != hipSuccess) return 0;
@@ -340,7 +378,7 @@ static int model_fill(gpemu_model *m, const double *X_train, const double *ls, c
   const int64_t N = m->N, d = m->d, F = m->F, k = m->k, Np = m->Npad;
   const int has_const = m->has_const, has_noise = m->has_noise;
   const double nu = m->nu;
-  if (hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking) != hipSuccess) {
+  if (stream_create(&m->stream, hipStreamNonBlocking) != hipSuccess) {
     set_error("hipStreamCreate failed");
     return GPEMU_ERR_HIP;
   }
@@ -535,8 +573,8 @@ int gpemu_model_destroy(gpemu_model *m) {
   dev_free(m->lik_tickets);
   dev_free(m->live_cnt);
   free_workspace(m->ws);
-  for (hipEvent_t e : m->ev_pool) (void)hipEventDestroy(e);
-  if (m->stream) hipStreamDestroy(m->stream);
+  for (hipEvent_t &e : m->ev_pool) event_destroy(e);
+  stream_destroy(m->stream);
   delete m;
   return GPEMU_OK;
 }
@@ -856,17 +894,22 @@ int gpemu_likelihood_setup_cov(gpemu_model *m, int n_chains, const double *y_exp
     m->lik_cache.clear();
     m->G = m->g0 = m->scal = m->W = m->Q = m->w0 = nullptr;
   }
+  // from here on the fields of the setup change one by one: until the last of them is in place the handle has no
+  // likelihood, so that a failure half way (an allocation, a matrix that is not positive definite) leaves a handle that
+  // says so and takes the next setup from scratch, not one whose launches read a freed or null field
+  m->lik_ready = false;
+  m->lik_host.clear();
   if (m->lik_cache.size() >= 64) {           // bounded: drop the oldest entry
     GP_HIP(hipStreamSynchronize(st));
     free_lik_entry(m->lik_cache.front());
     m->lik_cache.erase(m->lik_cache.begin());
   }
   GP_HIP(hipStreamSynchronize(st));
-  if (!m->yerr) {
-    GP_TRY(dev_alloc(&m->yerr, F));
-    GP_TRY(dev_alloc(&m->lo, m->dp)); GP_TRY(dev_alloc(&m->hi, m->dp));
-    GP_TRY(dev_alloc(&m->blk_of, F));
-  }
+  // (each on its own: an earlier setup may have ended between two of them)
+  if (!m->yerr) GP_TRY(dev_alloc(&m->yerr, F));
+  if (!m->lo) GP_TRY(dev_alloc(&m->lo, m->dp));
+  if (!m->hi) GP_TRY(dev_alloc(&m->hi, m->dp));
+  if (!m->blk_of) GP_TRY(dev_alloc(&m->blk_of, F));
   dev_free(m->yexp);
   GP_TRY(dev_alloc(&m->yexp, NC * F));
   m->lik_chains = n_chains;
@@ -893,8 +936,6 @@ int gpemu_likelihood_setup_cov(gpemu_model *m, int n_chains, const double *y_exp
   m->nblk = nblk;
   GP_HIP(hipMemcpyAsync(m->blk_start, hstart.data(), sizeof(int) * (nblk + 1), hipMemcpyHostToDevice, st));
   GP_HIP(hipMemcpyAsync(m->blk_of, hof.data(), sizeof(int) * F, hipMemcpyHostToDevice, st));
-  m->lik_ready = false;
-  m->lik_host.clear();
   m->n_div = n_div;
   double hlo[DPAD_WIDE], hhi[DPAD_WIDE];
   for (int i = 0; i < m->dp; ++i) { hlo[i] = i < m->d ? lo[i] : -INFINITY; hhi[i] = i < m->d ? hi[i] : INFINITY; }
@@ -936,12 +977,7 @@ int gpemu_logpost_dev(gpemu_model *m, int64_t B, const double *dX, double *dout,
   GP_ARG(B >= 0, "B must not be negative");
   if (B == 0) return GPEMU_OK;   /* empty batch -> empty result (ref: log_posterior.py:59,68) */
   GP_ARG(dX && dout, "null pointer");
-  GP_ARG(mode == GPEMU_LOGPOST_LOWRANK || mode == GPEMU_LOGPOST_EXACT, "mode");
-  if (!m->lik_ready) { set_error("gpemu_likelihood_setup has not been called"); return GPEMU_ERR_STATE; }
-  if (mode == GPEMU_LOGPOST_EXACT && m->n_src > 0) {
-    set_error("GPEMU_LOGPOST_EXACT does not support correlated sources (n_src = %d): use GPEMU_LOGPOST_LOWRANK", m->n_src);
-    return GPEMU_ERR_UNSUPPORTED;
-  }
+  GP_TRY(logpost_mode_ready(m, mode));
   GP_HIP(hipSetDevice(m->device));
   hipStream_t st = stream ? (hipStream_t)stream : m->stream;
   const LaunchSwitches sw = read_launch_switches();
@@ -965,6 +1001,7 @@ int gpemu_logpost(gpemu_model *m, int64_t B, const double *X, double *out, int m
   GP_ARG(B >= 0, "B must not be negative");
   if (B == 0) return GPEMU_OK;
   GP_ARG(X && out, "null pointer");
+  GP_TRY(logpost_mode_ready(m, mode));
   GP_HIP(hipSetDevice(m->device));
   hipStream_t st = m->stream;
   DevScope sc(st);
@@ -1000,8 +1037,7 @@ int gpemu_logpost_groups(gpemu_model *const *models, int n_groups, int64_t B, co
     }
     return GPEMU_OK;
   }
-  for (int g = 0; g < n_groups; ++g)
-    if (!models[g]->lik_ready) { set_error("gpemu_likelihood_setup has not been called"); return GPEMU_ERR_STATE; }
+  GP_TRY(logpost_groups_ready(models, n_groups));
   GP_HIP(hipSetDevice(m0->device));
   hipStream_t st = m0->stream;
   const LaunchSwitches sw = read_launch_switches();

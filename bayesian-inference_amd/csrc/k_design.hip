@@ -338,6 +338,23 @@ static int design_check(const gpemu_model *m, const DesignSpec &q) {
   return GPEMU_OK;
 }
 
+// the workspace the handle may use, or GPEMU_ERR_ARG where the operands and one tile of partials do not fit in it.  The
+// create calls ask before they allocate anything: a handle that is refused costs no allocation
+static int design_budget(const gpemu_model *m, const DesignSpec &q, int64_t *budget) {
+  const int64_t S = q.S, M = q.M, k = m->k, d = m->d, N = m->N;
+  const int64_t Sp = round_up(S, PC_NB), Mp = round_up(M, PC_NB), N64 = round_up(N, PC_NB);
+  const int64_t Kcap = N64 + round_up(q.max_picks, 16), colsmax = std::max(Sp, Mp), nrt = Sp / PC_NB;
+  GP_TRY(workspace_budget(q.workspace_bytes, budget));
+  const int64_t fixed = design_operand_bytes(k, Kcap, Sp, Mp) + (Sp + Mp) * d * 8;
+  const int64_t tile = std::max(k * nrt * PC_NB * 8, N64 * colsmax * 8);   // one tile of partials; the create call's KT
+  if (*budget < fixed + tile) {
+    set_error("bad argument: design: %lld bytes are needed for the operands and one tile of partials, %lld are %s",
+              (long long)(fixed + tile), (long long)*budget, workspace_budget_name(q.workspace_bytes));
+    return GPEMU_ERR_ARG;
+  }
+  return GPEMU_OK;
+}
+
 // the handle from checked arguments and device rows; the model's device is current
 static int design_build(gpemu_design **out, gpemu_model *m, const DesignSpec &q, const RowsView &ref, const double *dXcand) {
   hipStream_t st = m->stream;
@@ -345,14 +362,8 @@ static int design_build(gpemu_design **out, gpemu_model *m, const DesignSpec &q,
   const int64_t Sp = round_up(S, PC_NB), Mp = round_up(M, PC_NB), N64 = round_up(N, PC_NB);
   const int64_t Kcap = N64 + round_up(q.max_picks, 16), colsmax = std::max(Sp, Mp), nrt = Sp / PC_NB;
   int64_t budget = 0;
-  GP_TRY(workspace_budget(q.workspace_bytes, &budget));
+  GP_TRY(design_budget(m, q, &budget));
   const int64_t fixed = design_operand_bytes(k, Kcap, Sp, Mp) + (Sp + Mp) * d * 8;
-  const int64_t tile = std::max(k * nrt * PC_NB * 8, N64 * colsmax * 8);   // one tile of partials; the create call's KT
-  if (budget < fixed + tile) {
-    set_error("bad argument: design: %lld bytes are needed for the operands and one tile of partials, %lld are %s",
-              (long long)(fixed + tile), (long long)budget, workspace_budget_name(q.workspace_bytes));
-    return GPEMU_ERR_ARG;
-  }
   gpemu_design *h = new gpemu_design();
   h->m = m; h->S = S; h->M = M; h->Sp = Sp; h->Mp = Mp; h->N64 = N64; h->Kcap = Kcap; h->k = k;
   h->max_picks = q.max_picks;
@@ -467,6 +478,8 @@ int gpemu_design_create(gpemu_design **out, gpemu_model *m, int64_t S, const dou
   for (int64_t i = 0; i < S * m->d; ++i) GP_ARG(std::isfinite(Xref[i]), "Xref contains NaN or infinity");
   for (int64_t i = 0; i < M * m->d; ++i) GP_ARG(std::isfinite(Xcand[i]), "Xcand contains NaN or infinity");
   GP_HIP(hipSetDevice(m->device));
+  int64_t budget = 0;
+  GP_TRY(design_budget(m, q, &budget));   // (asked again by design_build: the copies below count against the free memory)
   hipStream_t st = m->stream;
   DevScope sc(st);
   double *dR = nullptr, *dC = nullptr;

@@ -1401,7 +1401,7 @@ static int fit_fill(gpemu_fit *f, const double *X) {
   // stream of lower priority, so that a waiting step of the chain is dispatched first
   int prio_least = 0, prio_greatest = 0;
   (void)hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest);
-  GP_HIP(hipStreamCreateWithPriority(&f->stream, hipStreamNonBlocking, prio_greatest));
+  GP_HIP(stream_create(&f->stream, hipStreamNonBlocking, prio_greatest));
   // The side stream may not use the first GPEMU_CHOL_RESERVE (default 4) CUs of every XCD: its GEMM workgroups take a
   // quarter of a CU's LDS each and are replaced one by one as they finish, so without a reserve the 75 KiB diagonal-block
   // kernel of the serial chain finds no CU with room until the whole side grid has drained (measured: 18 -> 100 us).
@@ -1413,12 +1413,12 @@ static int fit_fill(gpemu_fit *f, const double *X) {
   if (reserve > 0 && ncu % 8 == 0 && 8 * reserve < ncu) {
     std::vector<uint32_t> mask((size_t)(ncu + 31) / 32, 0u);
     for (int i = 8 * reserve; i < ncu; ++i) mask[i / 32] |= 1u << (i % 32);
-    GP_HIP(hipExtStreamCreateWithCUMask(&f->overlap.side, (uint32_t)mask.size(), mask.data()));
+    GP_HIP(stream_create_cu_mask(&f->overlap.side, (uint32_t)mask.size(), mask.data()));
   } else {
-    GP_HIP(hipStreamCreateWithPriority(&f->overlap.side, hipStreamNonBlocking, prio_least));
+    GP_HIP(stream_create(&f->overlap.side, hipStreamNonBlocking, prio_least));
   }
-  GP_HIP(hipEventCreateWithFlags(&f->overlap.panel_done, hipEventDisableTiming));
-  GP_HIP(hipEventCreateWithFlags(&f->overlap.rest_done, hipEventDisableTiming));
+  GP_HIP(event_create(&f->overlap.panel_done, hipEventDisableTiming));
+  GP_HIP(event_create(&f->overlap.rest_done, hipEventDisableTiming));
   const int dp = f->dp;
   GP_TRY(dev_alloc(&f->X, Np * dp));
   GP_TRY(fit_reserve(f, 1));
@@ -1461,14 +1461,14 @@ int gpemu_fit_destroy(gpemu_fit *f) {
   if (f->counted) g_live_fit_handles.fetch_sub(1);
   (void)hipSetDevice(f->device);
   if (f->stream) (void)hipStreamSynchronize(f->stream);
-  if (f->overlap.side) { (void)hipStreamSynchronize(f->overlap.side); (void)hipStreamDestroy(f->overlap.side); }
-  if (f->overlap.panel_done) (void)hipEventDestroy(f->overlap.panel_done);
-  if (f->overlap.rest_done) (void)hipEventDestroy(f->overlap.rest_done);
+  if (f->overlap.side) { (void)hipStreamSynchronize(f->overlap.side); stream_destroy(f->overlap.side); }
+  event_destroy(f->overlap.panel_done);
+  event_destroy(f->overlap.rest_done);
   dev_free(f->X);
   fit_buffers(f, [](double **p, int64_t) { dev_free(*p); });
   dev_free(f->info);
   dev_free(f->overlap.flags);
-  if (f->stream) (void)hipStreamDestroy(f->stream);
+  stream_destroy(f->stream);
   delete f;
   return GPEMU_OK;
 }

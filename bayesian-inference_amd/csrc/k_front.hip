@@ -489,10 +489,12 @@ static int64_t front_capacity(const gpemu_sampler *s, bool small) {
 // fabric and the store has to invalidate the reader's stale copy first (measured on the single-GPU step: 19.6 -> 13.6 us
 // for the cross-kernel when its rows are written where they are read).  Workgroup wg0 + gl runs on XCD (wg0 + gl) % 8 and
 // handles column block gl % ncolblk; its (row chunk, PC) is dealt so that the PC's rows are written on the XCD whose
-// workers read them (trmm_xcd_of); tasks without a preference fill the remaining slots.  Any bijection is correct.
-static const int *front_perm_for(gpemu_sampler *s, int g, int64_t cnt, int wg0, int ncolblk, int nchunk) {
+// workers read them (trmm_xcd_of); tasks without a preference fill the remaining slots.  Any bijection is correct, and
+// *out is null where no task has a preference (index order); a table that cannot be allocated is an error like any other.
+static int front_perm_for(gpemu_sampler *s, int g, int64_t cnt, int wg0, int ncolblk, int nchunk, const int **out) {
+  *out = nullptr;
   for (const gpemu_sampler::FrontPerm &e : s->front_perms)
-    if (e.cnt == cnt && e.group == g && e.wg0 == wg0) return e.dperm;
+    if (e.cnt == cnt && e.group == g && e.wg0 == wg0) { *out = e.dperm; return GPEMU_OK; }
   const gpemu_model *m = s->groups[g];
   const int k = (int)m->k, nrest = nchunk * k;
   std::vector<int> perm((size_t)nrest * ncolblk, -1);
@@ -517,16 +519,13 @@ static const int *front_perm_for(gpemu_sampler *s, int g, int64_t cnt, int wg0, 
   int *d = nullptr;
   if (any_pref) {
     DevScope sc(s->stream);
-    if (sc.alloc(&d, (int64_t)perm.size()) == GPEMU_OK &&
-        hipMemcpy(d, perm.data(), sizeof(int) * perm.size(), hipMemcpyHostToDevice) == hipSuccess) {
-      sc.release(d);                                        // kept in front_perms
-    } else {
-      (void)hipGetLastError();
-      d = nullptr;                                          // no table: index order (correct, only slower)
-    }
+    GP_TRY(sc.alloc(&d, (int64_t)perm.size()));
+    GP_HIP(hipMemcpy(d, perm.data(), sizeof(int) * perm.size(), hipMemcpyHostToDevice));
+    sc.release(d);                                          // kept in front_perms
   }
   s->front_perms.push_back({cnt, g, wg0, d});
-  return d;
+  *out = d;
+  return GPEMU_OK;
 }
 
 // workgroups a front launch needs for `cnt` proposals of this rank
@@ -606,7 +605,8 @@ static int launch_front(gpemu_sampler *s, const Pending &pv, bool have_next, int
     fg.kind = kstar_kind(m);
     fg.nchunk = (int)(m->Npad / rows_per_wg);
     fg.wg0 = wg;
-    fg.perm = have_next ? front_perm_for(s, g, cnt, wg, fa.ncolblk, fg.nchunk) : nullptr;
+    fg.perm = nullptr;
+    if (have_next) GP_TRY(front_perm_for(s, g, cnt, wg, fa.ncolblk, fg.nchunk, &fg.perm));
     if (have_next) wg += fa.ncolblk * fg.nchunk * fg.k;
     if (pv.have) {
       fg.mean_part_prev = pv.parity ? w.mean_part2 : w.mean_part;

@@ -272,11 +272,11 @@ int hmc_run(gpemu_sampler *s, int64_t steps, int store_chain) {
 
 // lp and the gradient of the current positions, through the gradient path (the lp every later accept compares with
 // comes from that path as well)
-int hmc_refresh_state(gpemu_sampler *s, hipStream_t st) {
+int hmc_refresh_state(gpemu_sampler *s, const double *X, double *logp, hipStream_t st) {
   HmcState *h = s->hmc;
-  GP_HIP(hipMemcpy2DAsync(h->xq, sizeof(double) * s->d, s->X, sizeof(double) * s->dp, sizeof(double) * s->d, (size_t)s->W,
+  GP_HIP(hipMemcpy2DAsync(h->xq, sizeof(double) * s->d, X, sizeof(double) * s->dp, sizeof(double) * s->d, (size_t)s->W,
                           hipMemcpyDeviceToDevice, st));
-  GP_TRY(logpost_grad_eval(s->groups.data(), (int)s->groups.size(), s->W, h->xq, s->logp, h->g, st));
+  GP_TRY(logpost_grad_eval(s->groups.data(), (int)s->groups.size(), s->W, h->xq, logp, h->g, st));
   return GPEMU_OK;
 }
 
@@ -287,14 +287,18 @@ int hmc_reset(gpemu_sampler *s) {
   return GPEMU_OK;
 }
 
+int hmc_snapshot_reserve(gpemu_sampler *s) {
+  HmcState *h = s->hmc;
+  const int64_t W = s->W, d = s->d;
+  if (!h->snapg) GP_TRY(dev_alloc(&h->snapg, W * d));
+  if (!h->snapdiv) GP_TRY(dev_alloc(&h->snapdiv, W));
+  if (!h->snapad) GP_TRY(dev_alloc(&h->snapad, AD_COUNT + HMC_MAX_D));
+  return GPEMU_OK;
+}
+
 int hmc_snapshot(gpemu_sampler *s) {
   HmcState *h = s->hmc;
   const int64_t W = s->W, d = s->d;
-  if (!h->snapg) {
-    GP_TRY(dev_alloc(&h->snapg, W * d));
-    GP_TRY(dev_alloc(&h->snapdiv, W));
-    GP_TRY(dev_alloc(&h->snapad, AD_COUNT + HMC_MAX_D));
-  }
   GP_HIP(hipMemcpyAsync(h->snapg, h->g, sizeof(double) * W * d, hipMemcpyDeviceToDevice, s->stream));
   GP_HIP(hipMemcpyAsync(h->snapdiv, h->ndiv, sizeof(long long) * W, hipMemcpyDeviceToDevice, s->stream));
   GP_HIP(hipMemcpyAsync(h->snapad, h->ad, sizeof(double) * AD_COUNT, hipMemcpyDeviceToDevice, s->stream));

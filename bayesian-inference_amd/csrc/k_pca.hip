@@ -611,8 +611,12 @@ extern "C" int gpemu_pca_fit(int device, int64_t N, int64_t F, const double *Y, 
     DevScope sc(nullptr);   // a one-off decomposition: the null stream
     GP_TRY(sc.alloc(&dY, N * F)); GP_TRY(sc.alloc(&dYs, N * F)); GP_TRY(sc.alloc(&dmean, F)); GP_TRY(sc.alloc(&dvar, F));
     GP_TRY(sc.alloc(&dscale, F)); GP_TRY(sc.alloc(&dpm, F)); GP_TRY(sc.alloc(&dW, (int64_t)ncols * ldw));
-    GP_HIP(hipExtMallocWithFlags((void **)&dpart, sizeof(double) * (size_t)npairs * nsplit * PP * PP, hipDeviceMallocUncached));
-    sc.adopt(dpart);
+    bool part_uncached = false;   // other workgroups poll dpart: plain device memory will not do
+    GP_TRY(sc.alloc_uncached(&dpart, (int64_t)npairs * nsplit * PP * PP, &part_uncached));
+    if (!part_uncached) {
+      set_error("pca_fit: the runtime has no uncached device memory for the rotation partials");
+      return GPEMU_ERR_HIP;
+    }
     GP_TRY(sc.alloc(&dJ, (int64_t)npairs * PP * PP)); GP_TRY(sc.alloc(&dss, F));
     GP_TRY(sc.alloc(&dflags, npairs));
     GP_TRY(sc.alloc(&dtickets, npairs));

@@ -153,10 +153,9 @@ int predict_cov(gpemu_model *m, int64_t M1, const double *dX1, int64_t M2, const
     return sc.alloc(&Cc, (int64_t)pc * M1p * mc);
   }();
   if (rc != GPEMU_OK) {
-    if (automatic) {   // the free memory went elsewhere between the query and the allocation
-      const std::string why = gpemu_last_error();
-      set_error("bad argument: predict_cov: the device is too full for the workspace (%s)", why.c_str());
-      return GPEMU_ERR_ARG;
+    if (automatic) {   // the free memory went elsewhere between the query and the allocation: the allocation's own
+      const std::string why = gpemu_last_error();   // code (no argument of the caller's is at fault), with the reason
+      set_error("predict_cov: the device is too full for the workspace (%s)", why.c_str());
     }
     return rc;
   }

@@ -601,12 +601,16 @@ int gpemu_sampler_set_state(gpemu_sampler *s, const double *X0, const double *lo
   double *tmp = nullptr;
   GP_TRY(sc.alloc(&tmp, W * d));
   GP_TRY(upload(tmp, X0, W * d, st));
+  // the new state is built in the idle halves of Xbuf / lpbuf and becomes current once all of it exists: a call that
+  // fails on the way (an evaluation that cannot get its workspace) leaves the positions and log-probabilities it found
+  const int next = s->cur ^ 1;
+  double *Xn = s->Xbuf + (size_t)next * W * s->dp, *lpn = s->lpbuf + (size_t)next * W;
   hipLaunchKernelGGL(s->dp == DPAD ? pad_rows_kernel<DPAD> : pad_rows_kernel<DPAD_WIDE>,
-                     dim3((unsigned)((W * s->dp + 255) / 256)), dim3(256), 0, st, tmp, s->X, (int)W, (int)d);
+                     dim3((unsigned)((W * s->dp + 255) / 256)), dim3(256), 0, st, tmp, Xn, (int)W, (int)d);
   if (s->hmc) {
-    GP_TRY(hmc_refresh_state(s, st));      // logp0 is not read: lp and the gradient come from the gradient path
+    GP_TRY(hmc_refresh_state(s, Xn, lpn, st));   // logp0 is not read: lp and the gradient come from the gradient path
   } else if (logp0) {
-    GP_TRY(upload(s->logp, logp0, W, st));
+    GP_TRY(upload(lpn, logp0, W, st));
   } else {
     // evaluate all walkers; X has exactly W rows, so go through a padded scratch copy in chunks
     // chunks never straddle a chain: every chunk is a whole number of chains or a piece of one
@@ -616,7 +620,7 @@ int gpemu_sampler_set_state(gpemu_sampler *s, const double *X0, const double *lo
     for (int64_t off = 0; off < W;) {
       int64_t nb = std::min<int64_t>(step, W - off);
       if (Wc > cap) nb = std::min<int64_t>(nb, Wc - off % Wc);
-      GP_HIP(hipMemcpyAsync(s->q, s->X + off * s->dp, sizeof(double) * nb * s->dp, hipMemcpyDeviceToDevice, st));
+      GP_HIP(hipMemcpyAsync(s->q, Xn + off * s->dp, sizeof(double) * nb * s->dp, hipMemcpyDeviceToDevice, st));
       AcceptArgs ca;                       // not an accept: only tells the likelihood which chain a row belongs to
       ca.chain_per = s->nchains > 1 ? (int)Wc : 0;
       ca.chain_data = s->tempered ? 0 : 1;     // the rungs of a tempered sampler share data vector 0
@@ -626,11 +630,12 @@ int gpemu_sampler_set_state(gpemu_sampler *s, const double *X0, const double *lo
       const int rc = logpost_eval(s->groups.data(), (int)s->groups.size(), nb, s->q, s->newlp, st, sw, &ca, nullptr);
       for (gpemu_model *m : s->groups) m->variant_B = 0;
       GP_TRY(rc);
-      GP_HIP(hipMemcpyAsync(s->logp + off, s->newlp, sizeof(double) * nb, hipMemcpyDeviceToDevice, st));
+      GP_HIP(hipMemcpyAsync(lpn + off, s->newlp, sizeof(double) * nb, hipMemcpyDeviceToDevice, st));
       off += nb;
     }
   }
   GP_HIP(hipStreamSynchronize(st));
+  s->cur = next; s->X = Xn; s->logp = lpn;
   return GPEMU_OK;
 }
 
@@ -679,17 +684,19 @@ int gpemu_sampler_snapshot(gpemu_sampler *s) {
   GP_ARG(s, "sampler");
   GP_HIP(hipSetDevice(s->device));
   const int64_t W = s->W;
-  if (!s->snapX) {
-    GP_TRY(dev_alloc(&s->snapX, W * s->dp));
-    GP_TRY(dev_alloc(&s->snaplp, W));
-    GP_TRY(dev_alloc(&s->snapacc, W));
-  }
+  // the copies below overwrite an earlier snapshot piece by piece: it is valid again once all of them are issued.
+  // Each buffer is asked for on its own: an earlier call may have ended between two of them.
+  s->snap_valid = false;
+  if (!s->snapX) GP_TRY(dev_alloc(&s->snapX, W * s->dp));
+  if (!s->snaplp) GP_TRY(dev_alloc(&s->snaplp, W));
+  if (!s->snapacc) GP_TRY(dev_alloc(&s->snapacc, W));
+  if (s->tempered && !s->snapswap) GP_TRY(dev_alloc(&s->snapswap, 2 * (s->nchains - 1) * (W / s->nchains)));
+  if (s->hmc) GP_TRY(hmc_snapshot_reserve(s));
   GP_HIP(hipMemcpyAsync(s->snapX, s->X, sizeof(double) * W * s->dp, hipMemcpyDeviceToDevice, s->stream));
   GP_HIP(hipMemcpyAsync(s->snaplp, s->logp, sizeof(double) * W, hipMemcpyDeviceToDevice, s->stream));
   GP_HIP(hipMemcpyAsync(s->snapacc, s->naccept, sizeof(long long) * W, hipMemcpyDeviceToDevice, s->stream));
   if (s->tempered) {          // the swap counters belong to the state as well
     const size_t npair = (size_t)(s->nchains - 1) * (size_t)(W / s->nchains);
-    if (!s->snapswap) GP_TRY(dev_alloc(&s->snapswap, (int64_t)(2 * npair)));
     GP_HIP(hipMemcpyAsync(s->snapswap, s->nswap_acc, sizeof(long long) * npair, hipMemcpyDeviceToDevice, s->stream));
     GP_HIP(hipMemcpyAsync(s->snapswap + npair, s->nswap_try, sizeof(long long) * npair, hipMemcpyDeviceToDevice,
                           s->stream));

@@ -299,6 +299,7 @@ static int small_schedule_ready(gpemu_model *m, int64_t B, hipStream_t st, int w
         dev_free(m->sm_cache.front().items);
         dev_free(m->sm_cache.front().cnt);
         m->sm_cache.erase(m->sm_cache.begin());
+        m->sm_ncb = -1;   // (the current schedule may have been that entry: nothing is current until the new one exists)
       }
       DevScope sc(st);   // owns the new entry until it is complete
       SmallItem *ditems = nullptr;

@@ -184,8 +184,10 @@ int temper_swap(gpemu_sampler *s, int store_chain, hipStream_t st);   // the swa
 int temper_validate_ladder(const double *betas, int n_temps);
 // k_hmc.hip: the parts of the sampler calls that an HMC sampler (s->hmc) takes
 int hmc_run(gpemu_sampler *s, int64_t steps, int store_chain);
-int hmc_refresh_state(gpemu_sampler *s, hipStream_t st);      // lp and gradient of the positions just set
+// lp (into logp) and the gradient of the padded positions X [W][dp] that gpemu_sampler_set_state is about to make current
+int hmc_refresh_state(gpemu_sampler *s, const double *X, double *logp, hipStream_t st);
 int hmc_reset(gpemu_sampler *s);
+int hmc_snapshot_reserve(gpemu_sampler *s);   // the snapshot's buffers, before anything of it is written
 int hmc_snapshot(gpemu_sampler *s);
 int hmc_restore(gpemu_sampler *s);
 void hmc_release(gpemu_sampler *s);

@@ -18,6 +18,10 @@ void set_error(const char *fmt, ...) {
   va_end(ap);
   fputc('\n', stderr);
 }
+DevLedger &dev_ledger() {   // the probe's own ledger (devledger.h): the library's is in gpemu_api.hip
+  static DevLedger ledger;
+  return ledger;
+}
 void count_path(PathFamily, int) {}   // the probe keeps no path counters
 }  // namespace gpemu
 

@@ -28,6 +28,10 @@ void set_error(const char *fmt, ...) {
   va_end(ap);
   fputc('\n', stderr);
 }
+DevLedger &dev_ledger() {   // the probe's own ledger (devledger.h): the library's is in gpemu_api.hip
+  static DevLedger ledger;
+  return ledger;
+}
 void count_path(PathFamily, int) {}   // the probe keeps no path counters
 int prof_mark(gpemu_model *, hipStream_t) { return -1; }
 void prof_pair(gpemu_model *, int, int, int) {}

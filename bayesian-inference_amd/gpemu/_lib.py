@@ -7,6 +7,7 @@ fallback.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import math
 import os
@@ -242,6 +243,8 @@ _SIGNATURES = {
                                           C.c_int, C.c_void_p, C.c_int, C.c_void_p, c_i64, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_void_p]),
     "gpemu_reweight_path_counts": (C.c_int, [C.POINTER(c_i64), c_i64]),
+    "gpemu_devmem_stats": (C.c_int, [C.POINTER(c_i64), c_i64]),
+    "gpemu_devmem_refuse_nth": (C.c_int, [c_i64, C.POINTER(c_i64)]),
 }
 
 
@@ -347,6 +350,43 @@ def device_free_bytes(device=None):
         return int(free.value)
     except Exception:
         return None
+
+
+# ---- for the tests only (include/gpemu.h: gpemu_devmem_stats, gpemu_devmem_refuse_nth) ----
+DEVMEM_STATS = ("live_blocks", "live_bytes", "allocs", "frees", "live_streams", "live_events")   # enum gpemu_devmem_stat
+
+
+def devmem_stats():
+    """The ledger of the library's device resources as a dict keyed by DEVMEM_STATS."""
+    out = (c_i64 * 16)()
+    n = lib().gpemu_devmem_stats(out, 16)
+    if n != len(DEVMEM_STATS):
+        raise GpemuError(n, f"gpemu_devmem_stats returned {n}, this binding knows {len(DEVMEM_STATS)} counters")
+    return {name: int(out[i]) for i, name in enumerate(DEVMEM_STATS)}
+
+
+def devmem_refuse_nth(nth):
+    """Arms the one-shot refusal of the nth device allocation from now (0: disarms); returns whether an earlier arming
+    had not fired yet."""
+    was = c_i64(0)
+    check(lib().gpemu_devmem_refuse_nth(int(nth), C.byref(was)))
+    return bool(was.value)
+
+
+class _Refusal:
+    fired = None      # after the block: whether the refusal fired inside it
+
+
+@contextlib.contextmanager
+def devmem_refusing(nth):
+    """``with devmem_refusing(j) as r:`` -- the j-th device allocation inside the block fails with GpemuError
+    ("... refused ..."); disarmed on the way out whatever happens, and ``r.fired`` then tells whether it fired."""
+    r = _Refusal()
+    devmem_refuse_nth(nth)
+    try:
+        yield r
+    finally:
+        r.fired = not devmem_refuse_nth(0)
 
 
 def as_f64(a, shape=None):

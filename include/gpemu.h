@@ -1223,6 +1223,28 @@ int gpemu_reweight_path_counts(int64_t *out, int64_t n);
 int gpemu_fit_workspace(gpemu_fit *f, int which, int64_t z, double *out);
 int gpemu_fit_poison(gpemu_fit *f);
 
+/* ---- device memory: test-only entry points --------------------------------------------------------------------------
+ * For the tests of the library's resource handling only; nothing in the library's own flow calls them.  One ledger per
+ * process counts every device allocation and free the library makes, and the streams and events its handles create.
+ * It does not count the IPC handles and mapped buffers of the peer transport, nor what RCCL allocates for itself.
+ * gpemu_devmem_stats: out[0 .. min(n, GPEMU_DEVMEM_STAT_COUNT)) = the counters below; returns GPEMU_DEVMEM_STAT_COUNT
+ * (or GPEMU_ERR_ARG).  ALLOCS - FREES = LIVE_BLOCKS at every reading.
+ * gpemu_devmem_refuse_nth: nth >= 1 makes the nth device allocation from now (of any host thread) fail, once, with
+ * GPEMU_ERR_HIP and an error text that holds "refused" and the bytes asked for; it is decided on the host before the
+ * allocator is called, allocates nothing and touches no device state, and disarms itself when it fires.  nth = 0
+ * disarms.  *still_armed (may be null) = 1 if an earlier arming had not fired yet, else 0.  nth < 0: GPEMU_ERR_ARG. */
+enum gpemu_devmem_stat {
+  GPEMU_DEVMEM_LIVE_BLOCKS = 0,   /* device allocations that exist now                                 */
+  GPEMU_DEVMEM_LIVE_BYTES,        /* ... and the bytes asked for them                                  */
+  GPEMU_DEVMEM_ALLOCS,            /* allocations made since the library was loaded                     */
+  GPEMU_DEVMEM_FREES,             /* frees of a live block since then (a free of null counts nothing)  */
+  GPEMU_DEVMEM_LIVE_STREAMS,      /* streams the library's handles own now                             */
+  GPEMU_DEVMEM_LIVE_EVENTS,       /* events the library's handles own now                              */
+  GPEMU_DEVMEM_STAT_COUNT
+};
+int gpemu_devmem_stats(int64_t *out, int64_t n);
+int gpemu_devmem_refuse_nth(int64_t nth, int64_t *still_armed);
+
 /* Philox4x32-10 block function (host copy of the device generator; for tests) */
 int gpemu_philox4x32(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
                      uint32_t *out4);
