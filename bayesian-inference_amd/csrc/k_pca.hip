@@ -10,9 +10,11 @@
 // The SVD is a one-sided Jacobi (Hestenes) iteration on the columns of the smaller dimension:
 // pairs of columns are rotated until mutually orthogonal; a round-robin tournament gives n/2
 // independent pairs per launch (one workgroup per pair).  Jacobi is chosen over a Gram-matrix
-// eigen-decomposition because it does not square the condition number: small singular values (the
-// truncated components that make up the "unexplained" covariance) keep full relative accuracy.
+// eigen-decomposition because it does not square the condition number: the error of a singular value is
+// absolute at the scale sigma_1 u (the block apply mixes columns through a J that carries rounding, and the scaler
+// has equilibrated the columns already), not sigma_1^2 u / sigma_i as a Gram eigen-decomposition would give.
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <numeric>
 
@@ -23,6 +25,22 @@ namespace gpemu {
 
 typedef double d4 __attribute__((ext_vector_type(4)));
 typedef double d2 __attribute__((ext_vector_type(2)));
+
+// The Gram partials pass from the workgroups that form them to the one that solves, inside one launch.  They live in
+// plain device memory and every access to them is a relaxed atomic of agent scope, which goes past the caches that are
+// not coherent between workgroups: the hand-over then needs no L2 write-back / invalidate, only the order store ->
+// ticket -> load.  (They used to live in an allocation of uncached device memory.  Once such an allocation had been
+// freed, the first decomposition of another shape in the process factored a matrix that differed from the input in a
+// few 64-row runs -- 1026 x 1025 followed by 1025 x 1100: ||Xc - S C|| = 2e-2 ||Xc|| -- and not when the partials of
+// the earlier call were simply never freed.  The library's PCA no longer allocates uncached memory.)
+__device__ __forceinline__ void part_store(double *p, double v) {
+  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ d2 part_load2(const double *p) {
+  double *q = const_cast<double *>(p);
+  return d2{__hip_atomic_load(q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT),
+            __hip_atomic_load(q + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)};
+}
 
 // Column f, rows r0 .. r0 + UN - 1 of a row-major matrix into registers: the loads of a batch are independent, so they
 // are all in flight together, while the sums that use them run strictly in row order (as numpy reduces axis 0).
@@ -181,18 +199,18 @@ __device__ void jacobi_solve(SolveLds<PB> &L, const double *__restrict__ src, in
   if (tid == 0) L.off = 0ull;
   if (tid < S::MAXSW) L.any[tid] = 0;
   {
-    // all loads of a thread in flight at once (uncached memory: ~2 us a round trip), the sums in split order
+    // all loads of a thread in flight at once (they go to memory: ~2 us a round trip), the sums in split order
     constexpr int NE = PP * PP / 512;           // d2 elements per thread
     d2 v[NE];
 #pragma unroll
-    for (int u = 0; u < NE; ++u) v[u] = reinterpret_cast<const d2 *>(src)[tid + 256 * u];
+    for (int u = 0; u < NE; ++u) v[u] = part_load2(src + 2 * (tid + 256 * u));
     for (int sp0 = 1; sp0 < nsplit; sp0 += 4) {
       d2 w[4][NE];
 #pragma unroll
       for (int q = 0; q < 4; ++q)
 #pragma unroll
         for (int u = 0; u < NE; ++u)
-          w[q][u] = (sp0 + q < nsplit) ? reinterpret_cast<const d2 *>(src + (int64_t)(sp0 + q) * (PP * PP))[tid + 256 * u] : d2{0.0, 0.0};
+          w[q][u] = (sp0 + q < nsplit) ? part_load2(src + (int64_t)(sp0 + q) * (PP * PP) + 2 * (tid + 256 * u)) : d2{0.0, 0.0};
 #pragma unroll
       for (int q = 0; q < 4; ++q)
 #pragma unroll
@@ -504,10 +522,11 @@ __global__ __launch_bounds__(256) void pca_gram_solve_kernel(const double *__res
     __syncthreads();
   }
   double *dst = part + ((int64_t)blockIdx.x * nsplit + blockIdx.y) * (PP * PP);
-  for (int idx = tid; idx < PP * PP / 2; idx += 256) reinterpret_cast<d2 *>(dst)[idx] = reinterpret_cast<const d2 *>(S)[idx];
-  // The last workgroup of the pair to get here solves.  `part` is uncached device memory: a store that has been
-  // acknowledged (vmcnt) is in memory and a load fetches from memory, so the hand-over needs no L2 write-back /
-  // invalidate (an agent-scope fence pair costs ~10 us here), only the order store -> ticket -> load.
+  for (int idx = tid; idx < PP * PP; idx += 256) part_store(dst + idx, S[idx]);
+  // The last workgroup of the pair to get here solves.  The partials are stored and loaded past the caches (part_store,
+  // part_load2): a store that has been acknowledged (vmcnt) is in memory and a load fetches from memory, so the
+  // hand-over needs no L2 write-back / invalidate (an agent-scope fence pair costs ~10 us here), only the order
+  // store -> ticket -> load.
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
   if (tid == 0) {
@@ -573,9 +592,21 @@ __global__ void pca_identity_rows_kernel(double *W, int64_t ldw, int mpad, int n
   if (j < n) W[(int64_t)j * ldw + mpad + j] = 1.0;
 }
 
+// the sweep limit of gpemu_pca_fit, and the test hook that lowers it for one call (gpemu_pca_sweep_limit_next)
+constexpr int PCA_MAX_SWEEPS = 60;
+constexpr int PCA_SECOND_INNER_FROM = 18;   // the sweep from which PB = 16 makes two inner sweeps per encounter
+static std::atomic<int64_t> g_pca_sweep_limit_next{0};
+
 }  // namespace gpemu
 
 using namespace gpemu;
+
+extern "C" int gpemu_pca_sweep_limit_next(int64_t limit, int64_t *still_armed) {
+  GP_ARG(limit >= 0 && limit <= PCA_MAX_SWEEPS, "limit must be in [0, 60]");
+  const int64_t was = g_pca_sweep_limit_next.exchange(limit, std::memory_order_relaxed);
+  if (still_armed) *still_armed = was > 0 ? 1 : 0;
+  return GPEMU_OK;
+}
 
 extern "C" int gpemu_pca_fit(int device, int64_t N, int64_t F, const double *Y, int64_t n_components,
                              double *scaler_mean, double *scaler_scale, double *scaler_var, double *pca_mean,
@@ -587,6 +618,15 @@ extern "C" int gpemu_pca_fit(int device, int64_t N, int64_t F, const double *Y, 
   const int64_t nmin = std::min(N, F);
   const int64_t nc = (n_components <= 0) ? nmin : n_components;
   GP_ARG(nc <= nmin, "n_components must be <= min(N, F)");
+  // sklearn's check_array refuses NaN and infinity (PCA.fit raises); here a NaN would drop out of every fmax of the
+  // convergence test and the iteration would "converge" at once on NaN columns
+  for (int64_t i = 0; i < N * F; ++i)
+    if (!std::isfinite(Y[i])) {
+      set_error("pca_fit: Y[%lld, %lld] is not finite", (long long)(i / F), (long long)(i % F));
+      return GPEMU_ERR_ARG;
+    }
+  const int64_t hooked = g_pca_sweep_limit_next.exchange(0, std::memory_order_relaxed);
+  const int max_sweeps = hooked > 0 ? (int)hooked : PCA_MAX_SWEEPS;
   GP_TRY(device_ready(device));
   const bool tw = N < F;                          // work on the transpose when there are fewer rows
   const int m = (int)(tw ? F : N), n = (int)(tw ? N : F);
@@ -611,12 +651,7 @@ extern "C" int gpemu_pca_fit(int device, int64_t N, int64_t F, const double *Y, 
     DevScope sc(nullptr);   // a one-off decomposition: the null stream
     GP_TRY(sc.alloc(&dY, N * F)); GP_TRY(sc.alloc(&dYs, N * F)); GP_TRY(sc.alloc(&dmean, F)); GP_TRY(sc.alloc(&dvar, F));
     GP_TRY(sc.alloc(&dscale, F)); GP_TRY(sc.alloc(&dpm, F)); GP_TRY(sc.alloc(&dW, (int64_t)ncols * ldw));
-    bool part_uncached = false;   // other workgroups poll dpart: plain device memory will not do
-    GP_TRY(sc.alloc_uncached(&dpart, (int64_t)npairs * nsplit * PP * PP, &part_uncached));
-    if (!part_uncached) {
-      set_error("pca_fit: the runtime has no uncached device memory for the rotation partials");
-      return GPEMU_ERR_HIP;
-    }
+    GP_TRY(sc.alloc(&dpart, (int64_t)npairs * nsplit * PP * PP));   // read and written past the caches: part_store
     GP_TRY(sc.alloc(&dJ, (int64_t)npairs * PP * PP)); GP_TRY(sc.alloc(&dss, F));
     GP_TRY(sc.alloc(&dflags, npairs));
     GP_TRY(sc.alloc(&dtickets, npairs));
@@ -648,10 +683,15 @@ extern "C" int gpemu_pca_fit(int device, int64_t N, int64_t F, const double *Y, 
       const double lim = noise_c * std::sqrt((double)m) * 2.220446049250313e-16;
       noise2 = lim * lim * fro2;
     }
-    for (sweeps = 0; sweeps < 60; ++sweeps) {
+    double off = 0.0;
+    for (sweeps = 0; sweeps < max_sweeps; ++sweeps) {
       GP_HIP(hipMemsetAsync(doff, 0, sizeof(unsigned long long), nullptr));
+      // A spectrum graded over many decades converges linearly for a long time with one inner sweep per encounter (37
+      // sweeps at 130 x 70 graded down to 1e-12): from sweep 18 on -- later than any flat-tailed input needs -- the
+      // PB = 16 instance makes two, as the PB = 32 instance always does.
+      const int inner_now = (PB == 16 && sweeps >= PCA_SECOND_INNER_FROM) ? 2 : inner;
       for (int r = 0; r < nb - 1; ++r) {
-        if (PB == 16) jacobi_round<16>(dW, ldw, mpad, nstrips, nb, r, nsplit, inner, tol, noise2, dpart, dtickets, dJ, dflags, doff, apply_y);
+        if (PB == 16) jacobi_round<16>(dW, ldw, mpad, nstrips, nb, r, nsplit, inner_now, tol, noise2, dpart, dtickets, dJ, dflags, doff, apply_y);
         else jacobi_round<32>(dW, ldw, mpad, nstrips, nb, r, nsplit, inner, tol, noise2, dpart, dtickets, dJ, dflags, doff, apply_y);
       }
       unsigned long long bits = 0, dbg[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -663,12 +703,16 @@ extern "C" int gpemu_pca_fit(int device, int64_t N, int64_t F, const double *Y, 
       if (trace && dbg[6])
         fprintf(stderr, "pca_fit:   pair 0: %llu rounds, gram + ticket %.2f us, solve (load, test, rotations, store) %.2f us\n", dbg[6],
                 (double)dbg[4] / dbg[6] * 0.01, (double)dbg[5] / dbg[6] * 0.01);
-      double off;
       std::memcpy(&off, &bits, sizeof(off));
       if (trace) fprintf(stderr, "pca_fit: sweep %d  largest cosine %.3e  (tol %.3e)\n", sweeps, off, tol);
       if (off <= tol) { ++sweeps; break; }
     }
     GP_HIP(hipGetLastError());
+    if (off > tol) {   // the window never closed: what the columns hold is not a decomposition
+      if (n_sweeps) *n_sweeps = sweeps;
+      set_error("pca_fit: not converged after %d sweeps: largest cosine %.3e above the tolerance %.3e", sweeps, off, tol);
+      return GPEMU_PCA_NOT_CONVERGED;
+    }
     hW.resize((size_t)ncols * ldw);
     GP_HIP(hipMemcpy(hW.data(), dW, sizeof(double) * hW.size(), hipMemcpyDeviceToHost));
     GP_HIP(hipMemcpy(scaler_mean, dmean, sizeof(double) * F, hipMemcpyDeviceToHost));

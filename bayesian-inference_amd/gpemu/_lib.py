@@ -245,6 +245,7 @@ _SIGNATURES = {
     "gpemu_reweight_path_counts": (C.c_int, [C.POINTER(c_i64), c_i64]),
     "gpemu_devmem_stats": (C.c_int, [C.POINTER(c_i64), c_i64]),
     "gpemu_devmem_refuse_nth": (C.c_int, [c_i64, C.POINTER(c_i64)]),
+    "gpemu_pca_sweep_limit_next": (C.c_int, [c_i64, C.POINTER(c_i64)]),
 }
 
 
@@ -387,6 +388,14 @@ def devmem_refusing(nth):
         yield r
     finally:
         r.fired = not devmem_refuse_nth(0)
+
+
+def pca_sweep_limit_next(limit):
+    """For the tests only (include/gpemu.h: gpemu_pca_sweep_limit_next): the next pca_fit stops after ``limit`` sweeps
+    (0: disarms); returns whether an earlier arming had not been used yet."""
+    was = c_i64(0)
+    check(lib().gpemu_pca_sweep_limit_next(int(limit), C.byref(was)))
+    return bool(was.value)
 
 
 def as_f64(a, shape=None):

@@ -133,20 +133,29 @@ def cholesky(A, device=None):
 
 def pca_fit(Y, n_components=None, device=None):
     """StandardScaler + full PCA on the device.  Returns a dict with scaler_mean/scale/var, pca_mean,
-    components (nc,F), explained_variance(_ratio) (nc,), Y_pca (N,nc), flip_argmax (nc,), n_sweeps."""
+    components (nc,F), explained_variance(_ratio) (nc,), Y_pca (N,nc), flip_argmax (nc,), n_sweeps.
+    A NaN or an infinity in ``Y`` raises ValueError before any library call (as sklearn's PCA.fit does); an iteration
+    that does not converge within the library's sweep limit raises LinAlgError."""
+    Y = as_f64(Y)
+    if Y.ndim != 2:
+        raise ValueError(f"Y must be a matrix (N, F), got shape {Y.shape}")
+    if not np.all(np.isfinite(Y)):
+        raise ValueError("Y contains NaN or infinity")
     _lib.require_device()
     device = _lib.resolve_device(device)
-    Y = as_f64(Y)
     N, F = Y.shape
     nc = min(N, F) if n_components is None else int(n_components)
     out = dict(scaler_mean=np.empty(F), scaler_scale=np.empty(F), scaler_var=np.empty(F), pca_mean=np.empty(F),
                components=np.empty((nc, F)), explained_variance=np.empty(nc), explained_variance_ratio=np.empty(nc),
                Y_pca=np.empty((N, nc)), flip_argmax=np.empty(nc, dtype=np.int64))
     ns = np.zeros(1, dtype=np.int64)
-    check(_lib.lib().gpemu_pca_fit(int(device), N, F, ptr(Y), nc, ptr(out["scaler_mean"]), ptr(out["scaler_scale"]),
-                                   ptr(out["scaler_var"]), ptr(out["pca_mean"]), ptr(out["components"]),
-                                   ptr(out["explained_variance"]), ptr(out["explained_variance_ratio"]),
-                                   ptr(out["Y_pca"]), ptr(out["flip_argmax"]), ptr(ns)))
+    rc = _lib.lib().gpemu_pca_fit(int(device), N, F, ptr(Y), nc, ptr(out["scaler_mean"]), ptr(out["scaler_scale"]),
+                                  ptr(out["scaler_var"]), ptr(out["pca_mean"]), ptr(out["components"]),
+                                  ptr(out["explained_variance"]), ptr(out["explained_variance_ratio"]),
+                                  ptr(out["Y_pca"]), ptr(out["flip_argmax"]), ptr(ns))
+    if rc > 0:
+        raise LinAlgError(_lib.lib().gpemu_last_error().decode())
+    check(rc)
     out["n_sweeps"] = int(ns[0])
     return out
 

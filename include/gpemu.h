@@ -282,7 +282,14 @@ int gpemu_cholesky(int device, int64_t N, double *A_inout);
  * (index of the max-|.| entry of each component row: the svd_flip sign decision), n_sweeps.
  * Environment GPEMU_SVD_FLIP=u (read per call): the u-based decision of the scikit-learn the reference pins (ref:
  * pdm.lock:1998-1999 -> 1.3.0: per column of U; flip_argmax then holds the deciding ROW of U); default v: the rule of
- * scikit-learn >= 1.5 the goldens were made with.  Physical-space outputs do not depend on it. */
+ * scikit-learn >= 1.5 the goldens were made with.  Physical-space outputs do not depend on it.
+ * Y must be finite: a NaN or an infinity anywhere in it is GPEMU_ERR_ARG (the error text names the element), decided
+ * on the host before anything is copied or launched, as sklearn's PCA.fit raises.
+ * The iteration stops after the first sweep in which no cosine between two columns exceeded 4 sqrt(m) eps
+ * (m = max(N, F), eps = 2^-52).  If 60 sweeps do not get there the call returns GPEMU_PCA_NOT_CONVERGED (> 0, like the
+ * info of gpemu_cholesky), the error text names the largest cosine of the last sweep and the tolerance, n_sweeps holds
+ * the sweeps made and no other output is written. */
+#define GPEMU_PCA_NOT_CONVERGED 1
 int gpemu_pca_fit(int device, int64_t N, int64_t F, const double *Y, int64_t n_components,
                   double *scaler_mean, double *scaler_scale, double *scaler_var, double *pca_mean,
                   double *components, double *explained_variance, double *explained_variance_ratio,
@@ -1244,6 +1251,15 @@ enum gpemu_devmem_stat {
 };
 int gpemu_devmem_stats(int64_t *out, int64_t n);
 int gpemu_devmem_refuse_nth(int64_t nth, int64_t *still_armed);
+
+/* ---- PCA: test-only entry point --------------------------------------------------------------------------------------
+ * For the test of gpemu_pca_fit's non-convergence report only; nothing in the library's own flow calls it.
+ * gpemu_pca_sweep_limit_next: 1 <= limit <= 60 makes the next gpemu_pca_fit (of any host thread) that passes its
+ * argument checks stop after `limit` sweeps instead of 60, once: that call disarms it whether it converges or not, and
+ * the calls after it run as in a fresh process.  limit = 0 disarms.  *still_armed (may be null) = 1 if an earlier
+ * arming had not been used yet, else 0.  limit outside [0, 60]: GPEMU_ERR_ARG.  It is decided on the host, allocates
+ * nothing and touches no device state. */
+int gpemu_pca_sweep_limit_next(int64_t limit, int64_t *still_armed);
 
 /* Philox4x32-10 block function (host copy of the device generator; for tests) */
 int gpemu_philox4x32(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
