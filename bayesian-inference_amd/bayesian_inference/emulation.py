@@ -517,13 +517,18 @@ def posterior_predictive(parameters, emulation_config: "EmulationConfig",
                          emulation_group_results: dict[str, dict[str, Any]] | None = None,
                          emulator_cov_unexplained: dict | None = None,
                          probabilities=POSTERIOR_PREDICTIVE_PROBABILITIES,
-                         merge_predictions_over_groups: bool = True) -> dict[str, Any]:
+                         merge_predictions_over_groups: bool = True, weights=None) -> dict[str, Any]:
     """What the calibrated model predicts for every observable bin, from ALL rows of ``parameters`` (S, d) --
     typically the flattened chain -- instead of the few hundred draws the reference's plots push through ``predict``
     (ref: plot_mcmc.py:343-371): ``mean``, ``variance_parameters`` (spread of the central value over the rows),
     ``variance_emulator`` (mean emulator variance of one sample, the diagonal of ``predict``'s ``cov`` with one row per
     call), ``variance`` (their sum), ``quantiles`` (nq, F) and ``probabilities``, in the observable order of
-    ``predict``.  Reduced on the device per group (``DeviceModel.posterior_predictive``)."""
+    ``predict``.  Reduced on the device per group (``DeviceModel.posterior_predictive``).
+
+    ``weights``: fixed-point importance weights ``q`` (R_w, S) of a reweighted chain (``gpemu.reweight.fixed_weights``)
+    -- the bands under another prior or other data without a rerun (``DeviceModel.posterior_predictive_weighted``,
+    DESIGN.md §4.43).  The result is then a list with one such dict per weight row, ``total_weight`` added; the
+    quantiles are the inverted weighted ECDF, elements of the sample."""
     parameters = np.array(parameters, ndmin=2, dtype=np.float64)
     emulation_group_results = emulation_group_results or {}
     emulator_cov_unexplained = emulator_cov_unexplained or {}
@@ -534,10 +539,21 @@ def posterior_predictive(parameters, emulation_config: "EmulationConfig",
             group_result = read_emulators(group_config)
         cov_un = emulator_cov_unexplained[group_name] if emulator_cov_unexplained else None
         dm = device_model_for(group_result, group_config.n_pc, cov_un)
-        per_group[group_name] = dm.posterior_predictive(parameters, probabilities=probabilities)
+        if weights is None:
+            per_group[group_name] = dm.posterior_predictive(parameters, probabilities=probabilities)
+        else:
+            per_group[group_name] = dm.posterior_predictive_weighted(parameters, weights, probabilities=probabilities)
     if not merge_predictions_over_groups:
         return per_group
-    return merge_posterior_predictive(emulation_config.sort_observables_in_matrix, per_group)
+    if weights is None:
+        return merge_posterior_predictive(emulation_config.sort_observables_in_matrix, per_group)
+    merged = []
+    for w in range(len(next(iter(per_group.values())))):
+        rows = {name: g[w] for name, g in per_group.items()}
+        out = merge_posterior_predictive(emulation_config.sort_observables_in_matrix, rows)
+        out['total_weight'] = next(iter(rows.values()))['total_weight']
+        merged.append(out)
+    return merged
 
 
 _GS_MATRICES = ('first_order', 'total', 'first_order_se', 'total_se')

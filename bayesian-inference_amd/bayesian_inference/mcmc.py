@@ -208,7 +208,8 @@ def _run_closure_batch(config, indices):
         _add_marginals(config, part, lambda c=c, **kw: sampler.marginals(chain=c, **kw),
                        label=f'closure chain {indices[c]}')
         _add_loo(config, part, lambda c=c, **kw: sampler.loo(chain=c, **kw), label=f'closure chain {indices[c]}')
-        _add_reweight(config, part, lambda c=c, **kw: sampler.reweight(chain=c, **kw), label=f'closure chain {indices[c]}')
+        _add_reweight(config, part, lambda c=c, **kw: sampler.reweight(chain=c, **kw), label=f'closure chain {indices[c]}',
+                      emu_cfg=emu_cfg)
         _add_information_gain(config, part, lambda c=c, **kw: sampler.information_gain(chain=c, **kw),
                               label=f'closure chain {indices[c]}')
         _add_expected_information_gain(config, part, lambda c=c, **kw: sampler.expected_information_gain(chain=c, **kw),
@@ -343,7 +344,8 @@ def run_mcmc(config, closure_index=-1):
     _add_marginals(config, results, sampler.get_marginals)
     _add_loo(config, results, lambda **kw: sampler.get_loo(models=log_posterior.device_models(n_div=1.0), **kw))
     _add_reweight(config, results,
-                  lambda **kw: sampler.get_reweighted(models=log_posterior.device_models(n_div=1.0), **kw))
+                  lambda **kw: sampler.get_reweighted(models=log_posterior.device_models(n_div=1.0), **kw),
+                  emu_cfg=emu_cfg)
     _add_information_gain(config, results, sampler.get_information_gain)
     _add_expected_information_gain(config, results, lambda **kw: sampler.get_expected_information_gain(
         models=log_posterior.device_models(n_div=1.0), **kw))
@@ -474,7 +476,8 @@ def _run_tempered(config, closure_index):
     _add_diagnostics(config, diag, lambda: sampler.diagnostics(temp=0), label='production chain (beta = 1)')
     _add_marginals(config, diag, lambda **kw: sampler.marginals(temp=0, **kw), label='production chain (beta = 1)')
     _add_loo(config, diag, lambda **kw: sampler.loo(temp=0, **kw), label='production chain (beta = 1)')
-    _add_reweight(config, diag, lambda **kw: sampler.reweight(temp=0, **kw), label='production chain (beta = 1)')
+    _add_reweight(config, diag, lambda **kw: sampler.reweight(temp=0, **kw), label='production chain (beta = 1)',
+                  emu_cfg=emu_cfg)
     _add_information_gain(config, diag, lambda **kw: sampler.information_gain(temp=0, **kw),
                           label='production chain (beta = 1)')
     _add_expected_information_gain(config, diag, lambda **kw: sampler.expected_information_gain(temp=0, **kw),
@@ -589,7 +592,7 @@ def _run_hmc(config, closure_index):
     _add_diagnostics(config, diag, sampler.diagnostics)
     _add_marginals(config, diag, sampler.marginals)
     _add_loo(config, diag, sampler.loo)
-    _add_reweight(config, diag, sampler.reweight)
+    _add_reweight(config, diag, sampler.reweight, emu_cfg=emu_cfg)
     _add_information_gain(config, diag, sampler.information_gain)
     _add_expected_information_gain(config, diag, sampler.expected_information_gain)
     step_size, inverse_metric, divergences = sampler.step_size, sampler.inverse_metric, sampler.divergences
@@ -942,6 +945,39 @@ def reweight_settings(mc):
     return out
 
 
+def reweight_summaries_settings(mc):
+    """``parameters.mcmc.reweight_summaries`` (default: none): ``None`` without the key, else ``{'hpd': [levels] or None,
+    'kde': bool, 'posterior_predictive': bool}`` -- the weighted highest-density intervals, 1-D kernel densities and
+    posterior-predictive bands of every scenario of ``parameters.mcmc.reweight``.  The key takes a
+    mapping with any of ``hpd`` (a non-empty list of confidence levels in (0, 1)), ``kde`` and ``posterior_predictive``
+    (true or false); unknown sub-keys, and the key without ``parameters.mcmc.reweight``, are a ValueError."""
+    spec = mc.get('reweight_summaries')
+    if spec is None:
+        return None
+    if not isinstance(spec, dict) or not set(spec) <= set(REWEIGHT_SUMMARIES):
+        raise ValueError(f"parameters.mcmc.reweight_summaries takes a mapping with {REWEIGHT_SUMMARIES}, got {spec!r}")
+    if reweight_settings(mc) is None:
+        raise ValueError("parameters.mcmc.reweight_summaries needs parameters.mcmc.reweight: there is no scenario to "
+                         "summarise")
+    out = {'hpd': None, 'kde': False, 'posterior_predictive': False}
+    for key in ('kde', 'posterior_predictive'):
+        v = spec.get(key, False)
+        if not isinstance(v, (bool, np.bool_)):
+            raise ValueError(f"parameters.mcmc.reweight_summaries.{key} must be true or false, got {v!r}")
+        out[key] = bool(v)
+    hpd = spec.get('hpd')
+    if hpd is not None:
+        ok = isinstance(hpd, (list, tuple)) and len(hpd) > 0 and all(
+            isinstance(c, (int, float)) and not isinstance(c, bool) and 0.0 < float(c) < 1.0 for c in hpd)
+        if not ok:
+            raise ValueError("parameters.mcmc.reweight_summaries.hpd must be a non-empty list of confidence levels in "
+                             f"(0, 1), got {hpd!r}")
+        out['hpd'] = [float(c) for c in hpd]
+    return out
+
+
+REWEIGHT_SUMMARIES = ('hpd', 'kde', 'posterior_predictive')
+REWEIGHT_PP_KEYS = ('mean', 'variance_parameters', 'variance_emulator', 'quantiles')
 REWEIGHT_KINDS = ('flat', 'log_uniform', 'normal', 'log_normal')
 REWEIGHT_KEYS = ('pareto_k', 'k_threshold', 'ess_w', 'reliable', 'log_mean_ratio', 'log_evidence_ratio', 'mean', 'sd',
                  'shift', 'quantiles', 'hist_1d', 'hist_2d', 'hist_1d_q', 'hist_2d_q', 'Q')
@@ -972,6 +1008,48 @@ def _reweight_kwargs(config, scenarios=None):
     return names, priors, np.asarray(box['min'], dtype=np.float64), np.asarray(box['max'], dtype=np.float64)
 
 
+def _reweight_summary_kwargs(config):
+    """the options of ``parameters.mcmc.reweight_summaries`` as keywords of a sampler's ``reweight``"""
+    summ = getattr(config, 'reweight_summaries', None) or {}
+    kw = {}
+    if summ.get('hpd') is not None:
+        kw['hpd'] = list(summ['hpd'])
+    if summ.get('kde'):
+        kw['kde'] = True
+    if summ.get('posterior_predictive'):
+        kw['posterior_predictive'] = True
+    return kw
+
+
+def _pp_merger(emu_cfg):
+    """the bands of the groups' models (in the groups' order) into the merged observable order of ``predict``"""
+    def merge(per_model):
+        return emulation.merge_posterior_predictive(emu_cfg.sort_observables_in_matrix,
+                                                    dict(zip(emu_cfg.emulation_groups_config, per_model)))
+    return merge
+
+
+def _reweight_summary_entries(out, names, merge_pp=None):
+    """the entries of ``parameters.mcmc.reweight_summaries``: ``reweight_hpd_confidence`` and, per scenario,
+    ``reweight_<name>_hpd``, ``reweight_<name>_kde_{grid,density,bandwidth}``,
+    ``reweight_<name>_pp_{mean,variance_parameters,variance_emulator,quantiles}`` -- those the scenarios' dicts hold"""
+    entries = {}
+    if 'hpd' in out[0]:
+        entries['reweight_hpd_confidence'] = np.asarray(out[0]['hpd_confidence'])
+    for name, res in zip(names, out):
+        if 'hpd' in res:
+            entries[f'reweight_{name}_hpd'] = np.asarray(res['hpd'])
+        for key in ('grid', 'density', 'bandwidth'):
+            if f'kde_{key}' in res:
+                entries[f'reweight_{name}_kde_{key}'] = np.asarray(res[f'kde_{key}'])
+        pp = res.get('posterior_predictive')
+        if pp is not None:
+            pp = merge_pp(pp) if isinstance(pp, list) else pp
+            for key in REWEIGHT_PP_KEYS:
+                entries[f'reweight_{name}_pp_{key}'] = np.asarray(pp[key])
+    return entries
+
+
 def _reweight_entries(out, names):
     """the ``reweight_*`` entries of mcmc.h5 from the scenarios' dicts: ``reweight_names``, the shared
     ``reweight_probabilities``, ``reweight_edges_1d``, ``reweight_edges_2d``, ``reweight_pairs`` and, per scenario,
@@ -990,16 +1068,29 @@ def _reweight_entries(out, names):
     return entries
 
 
-def _add_reweight(config, results, compute, label='production chain'):
+def _add_reweight(config, results, compute, label='production chain', emu_cfg=None):
     """With ``parameters.mcmc.reweight``: the ``reweight_*`` entries of ``compute(priors=..., lower=..., upper=...)`` (a
     sampler's ``reweight`` on the chain where it lies) into the results that go to mcmc.h5, one log line per scenario,
-    and a warning where a Pareto k-hat exceeds its threshold: that scenario needs its own run."""
+    and a warning where a Pareto k-hat exceeds its threshold: that scenario needs its own run.  With
+    ``parameters.mcmc.reweight_summaries`` the same call carries its options and their entries are added (``emu_cfg``:
+    the emulation configuration, for the merged observable order of the bands); where they fail, that is logged and the
+    ``reweight_*`` entries are those of a run without the key."""
     if not getattr(config, 'reweight', None):
         return
     try:
         names, priors, lower, upper = _reweight_kwargs(config)
-        out = compute(priors=priors, lower=lower, upper=upper)
-        entries = _reweight_entries(out, names)
+        more, extra_entries = _reweight_summary_kwargs(config), {}
+        if more:
+            try:
+                out = compute(priors=priors, lower=lower, upper=upper, **more)
+                extra_entries = _reweight_summary_entries(out, names, None if emu_cfg is None else _pp_merger(emu_cfg))
+            except Exception as err:
+                logger.warning(f'parameters.mcmc.reweight_summaries: not computed ({err!r}); mcmc.h5 is written without '
+                               'its entries')
+                more = {}
+        if not more:
+            out = compute(priors=priors, lower=lower, upper=upper)
+        entries = dict(_reweight_entries(out, names), **extra_entries)
     except Exception as err:         # the chain is worth more than the table: it is written either way
         logger.warning(f'parameters.mcmc.reweight: not computed ({err!r}); mcmc.h5 is written without the reweight_* '
                        'entries')
@@ -1013,12 +1104,22 @@ def _add_reweight(config, results, compute, label='production chain'):
                            "reweighted posterior is not reliable, this scenario needs its own run")
 
 
-def reweight(config, closure_index=-1, discard=0, thin=1, priors=None, reference_prior=False, **summary_kw):
+def reweight(config, closure_index=-1, discard=0, thin=1, priors=None, reference_prior=False, hpd=None, kde=None,
+             posterior_predictive=None, **summary_kw):
     """The ``reweight_*`` entries (``gpemu.reweight.summary``) of the chain stored in mcmc.h5 (of closure chain
     ``closure_index``, if >= 0), steps ``[discard::thin]``, all walkers, inside the configuration's box.  The scenarios
     are those of ``parameters.mcmc.reweight`` unless ``priors`` (that key's list form) or ``reference_prior=True`` gives
-    others.  ``summary_kw``: ``probabilities``, ``bins_1d``, ``bins_2d``, ``smooth``."""
+    others.  ``hpd``, ``kde``, ``posterior_predictive``: the options of ``parameters.mcmc.reweight_summaries`` (default:
+    that key's) and their entries; the bands come from ``emulation.posterior_predictive(weights=...)``.
+    ``summary_kw``: ``probabilities``, ``bins_1d``, ``bins_2d``, ``smooth``."""
     cfg, chain = _stored_chain(config, closure_index, discard, thin)
+    more = _reweight_summary_kwargs(cfg)
+    for key, v in (('hpd', hpd), ('kde', kde), ('posterior_predictive', posterior_predictive)):
+        if v is not None:
+            more[key] = v
+    want_pp = bool(more.pop('posterior_predictive', False))
+    if not more.get('kde', True):
+        more.pop('kde')
     scenarios = None
     if reference_prior:
         scenarios = reweight_settings({'reweight': {'reference_prior': True}})
@@ -1029,7 +1130,21 @@ def reweight(config, closure_index=-1, discard=0, thin=1, priors=None, reference
     x = np.ascontiguousarray(chain.reshape(-1, chain.shape[-1]))
     L = _rw.log_ratio(x, priors=pri, lower=lower, upper=upper)
     log_norm = _rw.log_prior_norm(*_rw.check_priors(pri, x.shape[1], lower, upper), lower, upper)
-    return _reweight_entries(_rw.summary(x, L, lower, upper, log_norm=log_norm, **summary_kw), names)
+    extra = None
+    if want_pp:
+        emu_cfg = emulation.EmulationConfig.from_config_file(
+            analysis_name=cfg.analysis_name, parameterization=cfg.parameterization,
+            analysis_config=cfg.analysis_config, config_file=cfg.config_file)
+        emu_results = emu_cfg.read_all_emulator_groups()
+        truncation_cov = emulation.compute_emulator_cov_unexplained(emu_cfg, emu_results)
+        probs = summary_kw.get('probabilities', emulation.POSTERIOR_PREDICTIVE_PROBABILITIES)
+
+        def extra(q, Q):
+            merged = emulation.posterior_predictive(x, emu_cfg, emulation_group_results=emu_results,
+                                                    emulator_cov_unexplained=truncation_cov, probabilities=probs, weights=q)
+            return [{'posterior_predictive': m} for m in merged]
+    out = _rw.summary(x, L, lower, upper, log_norm=log_norm, extra=extra, **more, **summary_kw)
+    return dict(_reweight_entries(out, names), **_reweight_summary_entries(out, names))
 
 
 def information_gain_settings(mc):
@@ -1449,6 +1564,7 @@ class MCMCConfig:
         # the posterior under other priors, from the production chain (optional, default none): reweight_* in mcmc.h5,
         # none without the key
         self.reweight = reweight_settings(mc)
+        self.reweight_summaries = reweight_summaries_settings(mc)
         # how many nats the data taught about each parameter, each pair and all of them jointly (optional, default off):
         # information_gain_* in mcmc.h5, none without the key
         self.information_gain, self.information_gain_k, self.information_gain_max_points = information_gain_settings(mc)

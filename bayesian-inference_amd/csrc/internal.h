@@ -53,15 +53,16 @@ static inline int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * 
 // a path outside its family's enum is not counted
 enum PathFamily { PATHS_LOGPOST, PATHS_FIT, PATHS_WIDE, PATHS_SRC, PATHS_GRAD, PATHS_POSTPRED, PATHS_HMC, PATHS_DIAG,
                   PATHS_SOBOL, PATHS_MARGINAL, PATHS_DESIGN, PATHS_KDE2D, PATHS_LOO, PATHS_KNN, PATHS_PAIRLSE,
-                  PATHS_REWEIGHT, PATH_FAMILIES };
+                  PATHS_REWEIGHT, PATHS_WSUMMARY, PATH_FAMILIES };
 void count_path(PathFamily family, int path);
-int read_path_counts(PathFamily family, int64_t *out, int64_t n);     // what the sixteen public gpemu_*_path_counts return
+int read_path_counts(PathFamily family, int64_t *out, int64_t n);     // what the seventeen public gpemu_*_path_counts return
 static inline void path_count(int path) { count_path(PATHS_LOGPOST, path); }    // enum gpemu_path
 static inline void fit_path_count(int path) { count_path(PATHS_FIT, path); }    // enum gpemu_fit_path
 static inline void wide_path_count(int path) { count_path(PATHS_WIDE, path); }  // enum gpemu_wide_path: d > 8 only
 static inline void src_path_count(int path) { count_path(PATHS_SRC, path); }    // enum gpemu_src_path
 static inline void grad_path_count(int path) { count_path(PATHS_GRAD, path); }  // enum gpemu_grad_path
 static inline void postpred_path_count(int path) { count_path(PATHS_POSTPRED, path); }  // enum gpemu_postpred_path
+static inline void wsummary_path_count(int path) { count_path(PATHS_WSUMMARY, path); }  // enum gpemu_wsummary_path
 
 constexpr int DPAD = 8;        // parameter dimensions padded to 8 (reference uses d = 6 or 7) ...
 constexpr int DPAD_WIDE = 16;  // ... or, for 9 <= d <= 16, to 16 (separate instantiations: d <= 8 keeps the code of DPAD)

@@ -24,6 +24,11 @@
 // j mod 4 of every grid point, so the order of every sum is fixed by the sample index.  kde_sum_kernel adds a grid
 // point's chunk sums: lane-strided in chunk order, then tree B of wg_dev.h.  A term whose exponent is below -746 is
 // exactly 0 in fp64 and is not evaluated.
+//
+// Under the fixed-point weights of a reweighted chain (gpemu_weighted_hpd*, gpemu_weighted_kde1d*): the
+// intervals by value (whpd_*: the same sort, the weights placed at the first sorted position of their key with integer
+// atomics, a three-launch 64-bit prefix sum, a bisection per run start, the same lexicographic reduction) and the
+// density with (double)q exp(.) as its term (kde_partial_kernel's KdeFixed instance; the unweighted one is KdeUnit).
 #include <algorithm>
 #include <cmath>
 #include <vector>
@@ -417,20 +422,282 @@ static int hpd_rows(const double *dV, int64_t R, int64_t S, int64_t row_stride, 
   return GPEMU_OK;
 }
 
+// ---- weighted highest-density intervals (gpemu_weighted_hpd*) --------------------------------------------
+// For sorted keys k[0 .. S) of a value row and the weights of a weight row placed at the first position of their key, C
+// their inclusive prefix sum: the interval of target mass t that starts at run start i (k[i] != k[i - 1]) ends at the
+// first j >= i with C[j] - C[i - 1] >= t, and the answer is the lexicographic minimum of (k[j] - k[i], i).
+constexpr int WH_SCAN = 2048;   // positions per workgroup of the prefix sum: 8 to a thread
+
+// the first position of `key` in the sorted row k[0 .. S); every key looked up is in the row
+static __device__ __forceinline__ int64_t whpd_first(const u64 *__restrict__ k, int64_t S, u64 key) {
+  int64_t lo = 0, hi = S - 1;
+  while (lo < hi) {
+    const int64_t mid = lo + ((hi - lo) >> 1);
+    if (k[mid] < key) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+
+// the first j in [i, S) with C[j] >= need, or -1 where C[S - 1] < need
+static __device__ __forceinline__ int64_t whpd_end(const u64 *__restrict__ C, int64_t S, int64_t i, u64 need) {
+  if (C[S - 1] < need) return -1;
+  int64_t lo = i, hi = S - 1;
+  while (lo < hi) {
+    const int64_t mid = lo + ((hi - lo) >> 1);
+    if (C[mid] < need) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+
+// C[rl S + first position of sample s's key] += q[s], C zeroed before; workgroup (256 samples, rl).  Integer atomics:
+// exact in any order
+__global__ __launch_bounds__(256) void whpd_place_kernel(const double *V, int64_t row_stride, int64_t elem_stride, int64_t S,
+                                                         int64_t row0, int64_t nblk, const u64 *__restrict__ sorted,
+                                                         const u64 *__restrict__ q, u64 *__restrict__ C) {
+  const int64_t rl = blockIdx.x / nblk, s = (blockIdx.x % nblk) * 256 + threadIdx.x;
+  if (s >= S) return;
+  const u64 wt = q[s];
+  if (wt == 0) return;
+  const u64 key = rk_key(V[(row0 + rl) * row_stride + s * elem_stride]);
+  atomicAdd(&C[rl * S + whpd_first(sorted + rl * S, S, key)], wt);
+}
+
+// cs[rl nsc + c] = the sum of chunk c of WH_SCAN positions of C; workgroup (c, rl)
+__global__ __launch_bounds__(256) void whpd_chunksum_kernel(const u64 *__restrict__ C, int64_t S, int64_t nsc,
+                                                            u64 *__restrict__ cs) {
+  __shared__ u64 red[256];
+  const int64_t c = blockIdx.x % nsc, rl = blockIdx.x / nsc;
+  u64 a = 0;
+  for (int j = 0; j < WH_SCAN / 256; ++j) {
+    const int64_t i = c * WH_SCAN + (int64_t)threadIdx.x * (WH_SCAN / 256) + j;
+    if (i < S) a += C[rl * S + i];
+  }
+  a = wg_sum_a<256>(a, red);
+  if (threadIdx.x == 0) cs[blockIdx.x] = a;
+}
+
+// cs[rl nsc + .] becomes its exclusive prefix sum; one workgroup per row: thread t owns a contiguous piece
+__global__ __launch_bounds__(256) void whpd_chunkscan_kernel(u64 *__restrict__ cs, int64_t nsc) {
+  __shared__ u64 piece[256];
+  const int tid = threadIdx.x;
+  u64 *p = cs + (int64_t)blockIdx.x * nsc;
+  const int64_t per = (nsc + 255) / 256, c0 = (int64_t)tid * per, c1 = (c0 + per < nsc) ? c0 + per : nsc;
+  u64 a = 0;
+  for (int64_t c = c0; c < c1; ++c) a += p[c];
+  piece[tid] = a;
+  __syncthreads();
+  if (tid == 0) {
+    u64 run = 0;
+    for (int t = 0; t < 256; ++t) {
+      const u64 v = piece[t];
+      piece[t] = run;
+      run += v;
+    }
+  }
+  __syncthreads();
+  u64 run = piece[tid];
+  for (int64_t c = c0; c < c1; ++c) {
+    const u64 v = p[c];
+    p[c] = run;
+    run += v;
+  }
+}
+
+// C becomes its inclusive prefix sum along the row, chunk c starting from cs[rl nsc + c]; workgroup (c, rl)
+__global__ __launch_bounds__(256) void whpd_apply_kernel(u64 *__restrict__ C, int64_t S, int64_t nsc,
+                                                         const u64 *__restrict__ cs) {
+  __shared__ u64 tsum[256];
+  constexpr int PER = WH_SCAN / 256;
+  const int tid = threadIdx.x;
+  const int64_t c = blockIdx.x % nsc, rl = blockIdx.x / nsc, i0 = c * WH_SCAN + (int64_t)tid * PER;
+  u64 v[PER], a = 0;
+#pragma unroll
+  for (int j = 0; j < PER; ++j) {
+    v[j] = (i0 + j < S) ? C[rl * S + i0 + j] : 0;
+    a += v[j];
+  }
+  tsum[tid] = a;
+  __syncthreads();
+  for (int off = 1; off < 256; off <<= 1) {   // inclusive scan of the threads' sums
+    const u64 add = tid >= off ? tsum[tid - off] : 0;
+    __syncthreads();
+    tsum[tid] += add;
+    __syncthreads();
+  }
+  u64 run = cs[blockIdx.x] + tsum[tid] - a;
+#pragma unroll
+  for (int j = 0; j < PER; ++j) {
+    run += v[j];
+    if (i0 + j < S) C[rl * S + i0 + j] = run;
+  }
+}
+
+// pw / pi[(rl L + l) nchunk + c] = the minimum of (k[j(i)] - k[i], i) over the run starts i of chunk c that have an end
+__global__ __launch_bounds__(256) void whpd_window_kernel(const u64 *__restrict__ sorted, const u64 *__restrict__ C,
+                                                          int64_t S, int n_levels, const u64 *__restrict__ targets,
+                                                          int64_t nchunk, double *__restrict__ pw,
+                                                          long long *__restrict__ pi) {
+  __shared__ double sw[256];
+  __shared__ long long si[256];
+  const int64_t c = blockIdx.x % nchunk, rl_l = blockIdx.x / nchunk, rl = rl_l / n_levels;
+  const u64 t = targets[rl_l % n_levels];
+  const u64 *k = sorted + rl * S, *cw = C + rl * S;
+  double bw = INFINITY;
+  long long bi = 0x7fffffffffffffffll;
+  for (int j = 0; j < HW_PER / 256; ++j) {
+    const int64_t i = c * HW_PER + (int64_t)j * 256 + threadIdx.x;
+    if (i < S && (i == 0 || k[i] != k[i - 1])) {
+      const int64_t e = whpd_end(cw, S, i, (i ? cw[i - 1] : (u64)0) + t);
+      if (e >= 0) {
+        const double w = sel_value(k[e]) - sel_value(k[i]);
+        if (hpd_before(w, i, bw, bi)) { bw = w; bi = i; }
+      }
+    }
+  }
+  hpd_wg_min(bw, bi, sw, si);
+  if (threadIdx.x == 0) {
+    pw[blockIdx.x] = bw;
+    pi[blockIdx.x] = bi;
+  }
+}
+
+// out[((pair0 + rl) L + l) 2 + {0, 1}] = the two ends; workgroup (rl, l)
+__global__ __launch_bounds__(256) void whpd_finish_kernel(const u64 *__restrict__ sorted, const u64 *__restrict__ C,
+                                                          int64_t S, int n_levels, const u64 *__restrict__ targets,
+                                                          int64_t nchunk, const double *__restrict__ pw,
+                                                          const long long *__restrict__ pi, const int *__restrict__ nan,
+                                                          int64_t pair0, double *__restrict__ out) {
+  __shared__ double sw[256];
+  __shared__ long long si[256];
+  const int64_t rl = blockIdx.x / n_levels;
+  double bw = INFINITY;
+  long long bi = 0x7fffffffffffffffll;
+  for (int64_t c = threadIdx.x; c < nchunk; c += 256) {
+    const double w = pw[(int64_t)blockIdx.x * nchunk + c];
+    const long long i = pi[(int64_t)blockIdx.x * nchunk + c];
+    if (hpd_before(w, i, bw, bi)) { bw = w; bi = i; }
+  }
+  hpd_wg_min(bw, bi, sw, si);
+  if (threadIdx.x == 0) {
+    const u64 *k = sorted + rl * S, *cw = C + rl * S;
+    const double smin = sel_value(k[0]), smax = sel_value(k[S - 1]);
+    double lo = sel_nan(), hi = lo;
+    // (the sentinel index survives where no run start has an end -- t exceeds Q -- and where every width is a NaN)
+    if (!nan[rl] && !isinf(smin) && !isinf(smax) && bi >= 0 && bi < S) {
+      const int64_t e = whpd_end(cw, S, bi, (bi ? cw[bi - 1] : (u64)0) + targets[blockIdx.x % n_levels]);
+      if (e >= 0) {
+        lo = sel_value(k[bi]);
+        hi = sel_value(k[e]);
+      }
+    }
+    double *o = out + ((pair0 + rl) * n_levels + blockIdx.x % n_levels) * 2;
+    o[0] = lo;
+    o[1] = hi;
+  }
+}
+
+static int whpd_check(int64_t R_v, int64_t S, int64_t R_w, int64_t n_levels, const u64 *targets) {
+  GP_ARG(R_v > 0, "R_v must be positive");
+  GP_ARG(R_w >= 1 && R_w <= WS_MAX_RW, "R_w must be in [1, 64]");
+  GP_ARG(S > 0 && S < (1ll << 31), "S must be in [1, 2^31)");
+  GP_ARG(R_v <= ((1ll << 31) - 1) / R_w, "R_v * R_w must be below 2^31");
+  GP_ARG(n_levels > 0 && n_levels <= 4096 && targets, "n_levels must be in [1, 4096]");
+  for (int64_t i = 0; i < R_w * n_levels; ++i)
+    GP_ARG(targets[i] >= 1 && targets[i] <= (1ull << 53), "every target must be in [1, 2^53]");
+  return GPEMU_OK;
+}
+
+// bytes of workspace of one (weight row, value row) pair of a batch: the sort's, the cumulative weights, the chunk sums of
+// the prefix sum, the windows' (pw, pi)
+static inline int64_t whpd_pair_bytes(int64_t S, int64_t n_levels) {
+  return rank_row_bytes(S) + 8 * S + 8 * ((S + WH_SCAN - 1) / WH_SCAN) + 16 * n_levels * ((S + HW_PER - 1) / HW_PER);
+}
+
+// the intervals of R_v value rows under R_w weight rows: the value rows in batches that fit workspace_bytes, sorted once
+// for all weight rows; waits for st
+static int whpd_rows(const double *dV, int64_t R_v, int64_t S, int64_t row_stride, int64_t elem_stride, int64_t R_w,
+                     const u64 *dq, int64_t ldq, int64_t n_levels, const u64 *targets, double *dout,
+                     int64_t workspace_bytes, hipStream_t st) {
+  int64_t budget = 0;
+  GP_TRY(workspace_budget(workspace_bytes, &budget));
+  const int64_t nchunk = (S + HW_PER - 1) / HW_PER, nsc = (S + WH_SCAN - 1) / WH_SCAN, nblk = (S + 255) / 256;
+  const int64_t per_pair = whpd_pair_bytes(S, n_levels);
+  const int64_t rows_cap = sort_rows_cap(R_v, S, budget, per_pair, n_levels * nchunk);
+  if (rows_cap < 1) {
+    set_error("weighted_hpd: out of memory: one (weight row, value row) pair of %lld elements and %lld levels needs %lld "
+              "bytes of sort, prefix-sum and window buffers; %lld bytes %s", (long long)S, (long long)n_levels,
+              (long long)per_pair, (long long)budget, workspace_budget_name(workspace_bytes));
+    return GPEMU_ERR_HIP;
+  }
+  DevScope sc(st);
+  SortScratch sort;
+  u64 *dt = nullptr, *C = nullptr, *cs = nullptr;
+  double *pw = nullptr;
+  long long *pi = nullptr;
+  GP_TRY(sort.alloc(sc, rows_cap, S));
+  GP_TRY(sc.alloc(&dt, R_w * n_levels));
+  GP_TRY(sc.alloc(&C, rows_cap * S));
+  GP_TRY(sc.alloc(&cs, rows_cap * nsc));
+  GP_TRY(sc.alloc(&pw, rows_cap * n_levels * nchunk));
+  GP_TRY(sc.alloc(&pi, rows_cap * n_levels * nchunk));
+  GP_TRY(upload(dt, targets, R_w * n_levels, st));
+  for (int64_t row0 = 0; row0 < R_v; row0 += rows_cap) {
+    const int64_t rows = std::min(rows_cap, R_v - row0);
+    wsummary_path_count(GPEMU_WSUMMARY_PATH_HPD_SORT_BATCH);
+    GP_TRY(sort_rows(dV, row_stride, elem_stride, S, row0, rows, sort, [] {}, st));
+    for (int64_t w = 0; w < R_w; ++w) {
+      GP_HIP(hipMemsetAsync(C, 0, sizeof(u64) * (size_t)(rows * S), st));
+      wsummary_path_count(GPEMU_WSUMMARY_PATH_HPD_PLACE);
+      hipLaunchKernelGGL(whpd_place_kernel, dim3((unsigned)(rows * nblk)), dim3(256), 0, st, dV, row_stride, elem_stride, S,
+                         row0, nblk, (const u64 *)sort.ka, dq + w * ldq, C);
+      GP_HIP(hipGetLastError());
+      wsummary_path_count(GPEMU_WSUMMARY_PATH_HPD_SCAN);
+      hipLaunchKernelGGL(whpd_chunksum_kernel, dim3((unsigned)(rows * nsc)), dim3(256), 0, st, (const u64 *)C, S, nsc, cs);
+      hipLaunchKernelGGL(whpd_chunkscan_kernel, dim3((unsigned)rows), dim3(256), 0, st, cs, nsc);
+      hipLaunchKernelGGL(whpd_apply_kernel, dim3((unsigned)(rows * nsc)), dim3(256), 0, st, C, S, nsc, (const u64 *)cs);
+      GP_HIP(hipGetLastError());
+      wsummary_path_count(GPEMU_WSUMMARY_PATH_HPD_WINDOW);
+      hipLaunchKernelGGL(whpd_window_kernel, dim3((unsigned)(rows * n_levels * nchunk)), dim3(256), 0, st,
+                         (const u64 *)sort.ka, (const u64 *)C, S, (int)n_levels, (const u64 *)(dt + w * n_levels), nchunk,
+                         pw, pi);
+      GP_HIP(hipGetLastError());
+      hipLaunchKernelGGL(whpd_finish_kernel, dim3((unsigned)(rows * n_levels)), dim3(256), 0, st, (const u64 *)sort.ka,
+                         (const u64 *)C, S, (int)n_levels, (const u64 *)(dt + w * n_levels), nchunk, (const double *)pw,
+                         (const long long *)pi, (const int *)sort.nan, w * R_v + row0, dout);
+      GP_HIP(hipGetLastError());
+    }
+  }
+  GP_HIP(hipStreamSynchronize(st));   // the targets are read by the copy above
+  return GPEMU_OK;
+}
+
 // ---- kernel density ------------------------------------------------------------------------------------------------
 // part[((rl G) + g) nchunk + c] = sum over the samples j of chunk c of exp(-((grid[r][g] - x_rj) inv_h[r])^2 / 2);
-// workgroup (c, tile, rl)
-template <int GPT>
+// workgroup (c, tile, rl).  Wt: the weights of the samples
+struct KdeUnit {   // none: every sample counts 1 (gpemu_kde1d)
+  static constexpr bool weighted = false;
+};
+struct KdeFixed {  // fixed-point weights (gpemu_weighted_kde1d): row r is the pair (w, v) = (r / R_v, r % R_v) of
+  static constexpr bool weighted = true;   // weight row w and value row v, and the term of sample j is (double)q_wj exp(.)
+  const u64 *q;                            // [R_w][ldq]
+  int64_t ldq, R_v;
+};
+template <int GPT, class Wt>
 __global__ __launch_bounds__(256) void kde_partial_kernel(const double *__restrict__ V, int64_t row_stride,
                                                           int64_t elem_stride, int64_t S, int64_t row0,
                                                           const double *__restrict__ grid,
                                                           const double *__restrict__ inv_h, int64_t G, int64_t nchunk,
-                                                          double *__restrict__ part) {
-  __shared__ double xs[KD_STAGE];
+                                                          double *__restrict__ part, Wt wt) {
+  __shared__ double xs[Wt::weighted ? 2 * KD_STAGE : KD_STAGE];   // the samples, then their weights
   const int tid = threadIdx.x;
   const int64_t c = blockIdx.x, rl = blockIdx.z, r = row0 + rl;
   const double ih = inv_h[r];
   const double *x = V + r * row_stride;
+  const u64 *qrow = nullptr;
+  if constexpr (Wt::weighted) {
+    x = V + (r % wt.R_v) * row_stride;
+    qrow = wt.q + (r / wt.R_v) * wt.ldq;
+  }
   double g[GPT], acc[GPT][4];
 #pragma unroll
   for (int k = 0; k < GPT; ++k) {
@@ -443,18 +710,33 @@ __global__ __launch_bounds__(256) void kde_partial_kernel(const double *__restri
   for (int64_t s0 = j0; s0 < j1; s0 += KD_STAGE) {
     const int n = (int)((j1 - s0 < KD_STAGE) ? j1 - s0 : KD_STAGE);
     __syncthreads();
-    for (int t = tid; t < n; t += 256) xs[t] = x[(s0 + t) * elem_stride];
+    for (int t = tid; t < n; t += 256) {
+      xs[t] = x[(s0 + t) * elem_stride];
+      if constexpr (Wt::weighted) xs[KD_STAGE + t] = (double)qrow[s0 + t];   // exact: q < 2^53
+    }
     __syncthreads();
     for (int t = 0; t < n; t += 4) {
 #pragma unroll
       for (int q = 0; q < 4; ++q)
         if (t + q < n) {
           const double xv = xs[t + q];
+          if constexpr (Wt::weighted) {
+            const double qd = xs[KD_STAGE + t + q];
+            if (qd != 0.0) {   // a sample of weight 0 contributes nothing
 #pragma unroll
-          for (int k = 0; k < GPT; ++k) {
-            const double u = (g[k] - xv) * ih;
-            const double e = -0.5 * (u * u);
-            if (e > -746.0) acc[k][q] += exp(e);   // below: exactly 0 in fp64
+              for (int k = 0; k < GPT; ++k) {
+                const double u = (g[k] - xv) * ih;
+                const double e = -0.5 * (u * u);
+                if (e > -746.0) acc[k][q] = fma(qd, exp(e), acc[k][q]);
+              }
+            }
+          } else {
+#pragma unroll
+            for (int k = 0; k < GPT; ++k) {
+              const double u = (g[k] - xv) * ih;
+              const double e = -0.5 * (u * u);
+              if (e > -746.0) acc[k][q] += exp(e);   // below: exactly 0 in fp64
+            }
           }
         }
     }
@@ -491,8 +773,10 @@ static int kde_check(int64_t R, int64_t S, int64_t G, const double *grid, const 
   return GPEMU_OK;
 }
 
+// the densities of R rows (Wt = KdeFixed: of R pairs); total[r]: what row r's sum is divided by, S or Q_w
+template <class Wt>
 static int kde_rows(const double *dV, int64_t R, int64_t S, int64_t row_stride, int64_t elem_stride, int64_t G,
-                    const double *grid, const double *h, double *ddens, hipStream_t st) {
+                    const double *grid, const double *h, const double *total, double *ddens, Wt wt, hipStream_t st) {
   const int64_t nchunk = (S + KD_CHUNK - 1) / KD_CHUNK;
   const int gpt = G <= 256 ? 1 : (G <= 512 ? 2 : KD_MAX_GPT);
   const int64_t ntile = (G + 256 * gpt - 1) / (256 * gpt);
@@ -503,7 +787,7 @@ static int kde_rows(const double *dV, int64_t R, int64_t S, int64_t row_stride, 
   std::vector<double> ih((size_t)R), norm((size_t)R);
   for (int64_t r = 0; r < R; ++r) {
     ih[(size_t)r] = 1.0 / h[r];
-    norm[(size_t)r] = 1.0 / ((double)S * h[r] * std::sqrt(2.0 * M_PI));
+    norm[(size_t)r] = 1.0 / (total[r] * h[r] * std::sqrt(2.0 * M_PI));
   }
   DevScope sc(st);
   double *dgrid = nullptr, *dih = nullptr, *dnorm = nullptr, *part = nullptr;
@@ -516,22 +800,51 @@ static int kde_rows(const double *dV, int64_t R, int64_t S, int64_t row_stride, 
   GP_TRY(upload(dnorm, norm.data(), R, st));
   for (int64_t row0 = 0; row0 < R; row0 += rows_cap) {
     const int64_t rows = std::min(rows_cap, R - row0);
-    marginal_path_count(GPEMU_MARGINAL_PATH_KDE);
+    if (Wt::weighted)
+      wsummary_path_count(GPEMU_WSUMMARY_PATH_KDE);
+    else
+      marginal_path_count(GPEMU_MARGINAL_PATH_KDE);
     const dim3 gr((unsigned)nchunk, (unsigned)ntile, (unsigned)rows);
     if (gpt == 1)
-      hipLaunchKernelGGL(kde_partial_kernel<1>, gr, dim3(256), 0, st, dV, row_stride, elem_stride, S, row0, dgrid, dih, G,
-                         nchunk, part);
+      hipLaunchKernelGGL((kde_partial_kernel<1, Wt>), gr, dim3(256), 0, st, dV, row_stride, elem_stride, S, row0, dgrid, dih,
+                         G, nchunk, part, wt);
     else if (gpt == 2)
-      hipLaunchKernelGGL(kde_partial_kernel<2>, gr, dim3(256), 0, st, dV, row_stride, elem_stride, S, row0, dgrid, dih, G,
-                         nchunk, part);
+      hipLaunchKernelGGL((kde_partial_kernel<2, Wt>), gr, dim3(256), 0, st, dV, row_stride, elem_stride, S, row0, dgrid, dih,
+                         G, nchunk, part, wt);
     else
-      hipLaunchKernelGGL(kde_partial_kernel<KD_MAX_GPT>, gr, dim3(256), 0, st, dV, row_stride, elem_stride, S, row0, dgrid,
-                         dih, G, nchunk, part);
+      hipLaunchKernelGGL((kde_partial_kernel<KD_MAX_GPT, Wt>), gr, dim3(256), 0, st, dV, row_stride, elem_stride, S, row0,
+                         dgrid, dih, G, nchunk, part, wt);
     hipLaunchKernelGGL(kde_sum_kernel, dim3((unsigned)(rows * G)), dim3(256), 0, st, part, nchunk, G, row0, dnorm, ddens);
     GP_HIP(hipGetLastError());
   }
   GP_HIP(hipStreamSynchronize(st));   // ih and norm are read by the copies above
   return GPEMU_OK;
+}
+
+static int wkde_check(int64_t R_v, int64_t S, int64_t R_w, int64_t G, const double *grid, const double *h) {
+  GP_ARG(R_v > 0, "R_v must be positive");
+  GP_ARG(R_w >= 1 && R_w <= WS_MAX_RW, "R_w must be in [1, 64]");
+  GP_ARG(S < (1ll << 31), "S must be in [1, 2^31)");
+  GP_ARG(R_v <= ((1ll << 31) - 1) / R_w, "R_v * R_w must be below 2^31");
+  return kde_check(R_w * R_v, S, G, grid, h);
+}
+
+// the densities of the R_w R_v pairs under the weights dq: Q_w read back first, then kde_rows over the pairs; waits for st
+static int wkde_rows(const double *dV, int64_t R_v, int64_t S, int64_t row_stride, int64_t elem_stride, int64_t R_w,
+                     const u64 *dq, int64_t ldq, int64_t G, const double *grid, const double *h, double *ddens,
+                     hipStream_t st) {
+  std::vector<u64> Q((size_t)R_w);
+  {
+    DevScope sc(st);
+    u64 *dQ = nullptr;
+    GP_TRY(sc.alloc(&dQ, R_w));
+    GP_TRY(weight_totals(dq, ldq, R_w, S, dQ, st));
+    GP_TRY(sc.download(Q.data(), dQ, R_w));
+    GP_HIP(hipStreamSynchronize(st));
+  }
+  std::vector<double> total((size_t)(R_w * R_v));
+  for (int64_t r = 0; r < R_w * R_v; ++r) total[(size_t)r] = (double)Q[(size_t)(r / R_v)];
+  return kde_rows(dV, R_w * R_v, S, row_stride, elem_stride, G, grid, h, total.data(), ddens, KdeFixed{dq, ldq, R_v}, st);
 }
 
 }  // namespace gpemu
@@ -604,7 +917,8 @@ int gpemu_kde1d_dev(int device, int64_t R, int64_t S, const double *dV, int64_t 
   GP_TRY(kde_check(R, S, G, grid, h));
   GP_ARG(row_stride > 0 && elem_stride > 0, "strides must be positive");
   GP_TRY(device_ready(device));
-  return kde_rows(dV, R, S, row_stride, elem_stride, G, grid, h, ddens, (hipStream_t)stream);
+  const std::vector<double> total((size_t)R, (double)S);
+  return kde_rows(dV, R, S, row_stride, elem_stride, G, grid, h, total.data(), ddens, KdeUnit{}, (hipStream_t)stream);
 }
 
 int gpemu_kde1d(int device, int64_t R, int64_t S, const double *V, int64_t G, const double *grid, const double *h,
@@ -612,9 +926,76 @@ int gpemu_kde1d(int device, int64_t R, int64_t S, const double *V, int64_t G, co
   GP_ARG(V && dens, "null pointer");
   GP_TRY(kde_check(R, S, G, grid, h));
   GP_ARG(R <= INT64_MAX / 8 / S, "R * S overflows");
+  const std::vector<double> total((size_t)R, (double)S);
   return with_host_rows(device, R, S, V, G, dens, [&](const double *dV, double *dd, hipStream_t st) {
-    return kde_rows(dV, R, S, S, 1, G, grid, h, dd, st);
+    return kde_rows(dV, R, S, S, 1, G, grid, h, total.data(), dd, KdeUnit{}, st);
   });
+}
+
+int gpemu_weighted_hpd_dev(int device, int64_t R_v, int64_t S, const double *dV, int64_t row_stride, int64_t elem_stride,
+                           int64_t R_w, const uint64_t *dq, int64_t ldq, int64_t n_levels, const uint64_t *targets,
+                           double *dout, const gpemu_call_ctx *ctx) {
+  GP_ARG(dV && dq && dout, "null pointer");
+  GP_TRY(whpd_check(R_v, S, R_w, n_levels, (const u64 *)targets));
+  GP_ARG(row_stride > 0 && elem_stride > 0, "strides must be positive");
+  GP_ARG(ldq >= S, "ldq must be at least S");
+  GP_ARG(ctx_workspace(ctx) >= 0, "workspace_bytes must be >= 0");
+  GP_TRY(device_ready(device));
+  return whpd_rows(dV, R_v, S, row_stride, elem_stride, R_w, (const u64 *)dq, ldq, n_levels, (const u64 *)targets, dout,
+                   ctx_workspace(ctx), ctx_stream(ctx));
+}
+
+int gpemu_weighted_hpd(int device, int64_t R_v, int64_t S, const double *V, int64_t R_w, const uint64_t *q,
+                       int64_t n_levels, const uint64_t *targets, double *out) {
+  GP_ARG(V && q && out, "null pointer");
+  GP_TRY(whpd_check(R_v, S, R_w, n_levels, (const u64 *)targets));
+  GP_ARG(R_v <= INT64_MAX / 8 / S, "R_v * S overflows");
+  GP_TRY(device_ready(device));
+  hipStream_t st = nullptr;
+  DevScope sc(st);
+  double *dV = nullptr, *dout = nullptr;
+  u64 *dq = nullptr;
+  GP_TRY(sc.alloc(&dV, R_v * S));
+  GP_TRY(sc.alloc(&dq, R_w * S));
+  GP_TRY(sc.alloc(&dout, R_w * R_v * n_levels * 2));
+  GP_TRY(upload(dV, V, R_v * S, st));
+  GP_TRY(upload(dq, (const u64 *)q, R_w * S, st));
+  GP_TRY(whpd_rows(dV, R_v, S, S, 1, R_w, dq, S, n_levels, (const u64 *)targets, dout, 0, st));
+  GP_TRY(sc.download(out, dout, R_w * R_v * n_levels * 2));
+  GP_HIP(hipStreamSynchronize(st));
+  return GPEMU_OK;
+}
+
+int gpemu_weighted_kde1d_dev(int device, int64_t R_v, int64_t S, const double *dV, int64_t row_stride,
+                             int64_t elem_stride, int64_t R_w, const uint64_t *dq, int64_t ldq, int64_t G,
+                             const double *grid, const double *h, double *ddens, const gpemu_call_ctx *ctx) {
+  GP_ARG(dV && dq && ddens, "null pointer");
+  GP_TRY(wkde_check(R_v, S, R_w, G, grid, h));
+  GP_ARG(row_stride > 0 && elem_stride > 0, "strides must be positive");
+  GP_ARG(ldq >= S, "ldq must be at least S");
+  GP_TRY(device_ready(device));
+  return wkde_rows(dV, R_v, S, row_stride, elem_stride, R_w, (const u64 *)dq, ldq, G, grid, h, ddens, ctx_stream(ctx));
+}
+
+int gpemu_weighted_kde1d(int device, int64_t R_v, int64_t S, const double *V, int64_t R_w, const uint64_t *q, int64_t G,
+                         const double *grid, const double *h, double *dens) {
+  GP_ARG(V && q && dens, "null pointer");
+  GP_TRY(wkde_check(R_v, S, R_w, G, grid, h));
+  GP_ARG(R_v <= INT64_MAX / 8 / S, "R_v * S overflows");
+  GP_TRY(device_ready(device));
+  hipStream_t st = nullptr;
+  DevScope sc(st);
+  double *dV = nullptr, *dd = nullptr;
+  u64 *dq = nullptr;
+  GP_TRY(sc.alloc(&dV, R_v * S));
+  GP_TRY(sc.alloc(&dq, R_w * S));
+  GP_TRY(sc.alloc(&dd, R_w * R_v * G));
+  GP_TRY(upload(dV, V, R_v * S, st));
+  GP_TRY(upload(dq, (const u64 *)q, R_w * S, st));
+  GP_TRY(wkde_rows(dV, R_v, S, S, 1, R_w, dq, S, G, grid, h, dd, st));
+  GP_TRY(sc.download(dens, dd, R_w * R_v * G));
+  GP_HIP(hipStreamSynchronize(st));
+  return GPEMU_OK;
 }
 
 int gpemu_marginal_dense_dev(int device, const double *dX, int64_t n_blocks, int64_t block_rows,

@@ -17,6 +17,9 @@
 // vbar_p = mean_s var_p(theta_s): the mean is linear and every term is non-negative, so the F x S variances never exist.
 // Every sum over samples runs over chunks fixed by the logical sample index: the bits do not depend on the workspace,
 // on the feature blocks or on the run.
+//
+// gpemu_posterior_predictive_weighted*  is the same reduction (pp_reduce) under rows of fixed-point weights:
+// the sums by weighted_rowmean of k_wsummary.hip, in the same tree, the quantiles by the weighted select.
 #include <algorithm>
 #include <vector>
 
@@ -166,23 +169,25 @@ int gpemu_select(int device, int64_t R, int64_t S, const double *V, int64_t n_ra
   });
 }
 
-int gpemu_posterior_predictive_dev(gpemu_model *m, const double *dX, int64_t n_blocks, int64_t block_rows,
-                                   int64_t block_stride_rows, int64_t n_ranks, const int64_t *ranks,
-                                   int64_t workspace_bytes, double *dmean, double *dvar_param, double *dvar_emu,
-                                   double *dorder, void *stream) {
-  GP_ARG(m && dX, "null pointer");
-  const RowsView X{dX, n_blocks, block_rows, block_stride_rows * m->d, (int)m->d};
-  GP_TRY(rows_check(X));
-  GP_ARG(n_blocks <= INT64_MAX / block_rows, "n_blocks * block_rows overflows");
-  GP_ARG(workspace_bytes >= 0, "workspace_bytes must be >= 0");
-  GP_ARG(n_ranks >= 0, "n_ranks must be >= 0");
-  const int64_t S = n_blocks * block_rows, F = m->F, k = m->k, d = m->d;
-  if (n_ranks > 0) {
-    GP_ARG(dorder, "order_stats is null with n_ranks > 0");
-    GP_TRY(select_check(F, S, n_ranks, ranks));
-  }
-  GP_HIP(hipSetDevice(m->device));
-  hipStream_t st = stream ? (hipStream_t)stream : m->stream;
+}  // extern "C"
+
+// the fixed-point weights of gpemu_posterior_predictive_weighted*: R_w rows, n_sel targets each
+struct PpWeights {
+  int64_t R_w;
+  const u64 *dq;       // [R_w][ldq], device
+  int64_t ldq;
+  const u64 *targets;  // [R_w][n_sel], host
+};
+
+// The reduction of both families over validated rows, on st (waited for).  wt null: the sample counts 1 and n_sel ranks
+// select; the outputs are [F] (dsel [F][n_sel]).  Else every sum runs under each weight row (weighted_rowmean of
+// rows_dev.h, the same tree), n_sel targets per weight row select, and the outputs are [R_w][F] (dsel [R_w][F][n_sel])
+static int pp_reduce(gpemu_model *m, const RowsView &X, int64_t n_sel, const int64_t *ranks, const PpWeights *wt,
+                     int64_t workspace_bytes, double *dmean, double *dvar_param, double *dvar_emu, double *dsel,
+                     hipStream_t st) {
+  const double *dX = X.base;
+  const int64_t block_rows = X.block_rows, S = X.rows(), F = m->F, k = m->k, d = m->d, n_ranks = n_sel;
+  const int64_t R_w = wt ? wt->R_w : 1;
 
   // the plan: the PC arrays stay resident, the features go through the workspace in blocks
   int64_t budget = 0;
@@ -209,9 +214,14 @@ int gpemu_posterior_predictive_dev(gpemu_model *m, const double *dX, int64_t n_b
   GP_TRY(sc.alloc(&Mpc, S * k));
   GP_TRY(sc.alloc(&Vpc, S * k));
   if (!X.dense()) GP_TRY(sc.alloc(&stage, PP_CHUNK * d));
-  GP_TRY(sc.alloc(&part, std::max(Fb, k) * nchunk));
-  GP_TRY(sc.alloc(&vbar, k));
-  GP_TRY(sc.alloc(&mu, F));
+  u64 *dQ = nullptr;
+  GP_TRY(sc.alloc(&part, R_w * std::max(Fb, k) * nchunk));
+  GP_TRY(sc.alloc(&vbar, R_w * k));
+  GP_TRY(sc.alloc(&mu, R_w * F));
+  if (wt) {
+    GP_TRY(sc.alloc(&dQ, R_w));
+    GP_TRY(weight_totals(wt->dq, wt->ldq, R_w, S, dQ, st));
+  }
   if (want_ws) GP_TRY(sc.alloc(&W, Fb * S));
 
   for (int64_t r0 = 0; r0 < S; r0 += PP_CHUNK) {
@@ -227,25 +237,131 @@ int gpemu_posterior_predictive_dev(gpemu_model *m, const double *dX, int64_t n_b
   }
 
   if (dvar_emu) {
-    GP_TRY(launch_rowmean(Vpc, 1, k, k, S, nullptr, part, vbar, st));
-    hipLaunchKernelGGL(pp_varemu_kernel, dim3((unsigned)((F + 255) / 256)), dim3(256), 0, st, vbar, m->comp, m->sscale,
-                       m->cunexpl, (int)k, F, dvar_emu);
+    if (wt)
+      GP_TRY(weighted_rowmean(Vpc, 1, k, k, S, R_w, wt->dq, wt->ldq, dQ, nullptr, 0, part, k, vbar, k, st));
+    else
+      GP_TRY(launch_rowmean(Vpc, 1, k, k, S, nullptr, part, vbar, st));
+    for (int64_t w = 0; w < R_w; ++w)
+      hipLaunchKernelGGL(pp_varemu_kernel, dim3((unsigned)((F + 255) / 256)), dim3(256), 0, st, vbar + w * k, m->comp,
+                         m->sscale, m->cunexpl, (int)k, F, dvar_emu + w * F);
     GP_HIP(hipGetLastError());
   }
   if (want_ws) {
-    postpred_path_count(Fb >= F ? GPEMU_POSTPRED_PATH_WHOLE : GPEMU_POSTPRED_PATH_FEATURE_BLOCKED);
+    if (wt)
+      wsummary_path_count(Fb >= F ? GPEMU_WSUMMARY_PATH_BANDS_WHOLE : GPEMU_WSUMMARY_PATH_BANDS_FEATURE_BLOCKED);
+    else
+      postpred_path_count(Fb >= F ? GPEMU_POSTPRED_PATH_WHOLE : GPEMU_POSTPRED_PATH_FEATURE_BLOCKED);
     for (int64_t f0 = 0; f0 < F; f0 += Fb) {
       const int64_t fb = std::min(Fb, F - f0);
-      postpred_path_count(GPEMU_POSTPRED_PATH_FEATURE_BLOCK);
+      if (!wt) postpred_path_count(GPEMU_POSTPRED_PATH_FEATURE_BLOCK);
       hipLaunchKernelGGL(pp_project_kernel, dim3((unsigned)((S + 255) / 256), (unsigned)((fb + PP_FT - 1) / PP_FT)),
                          dim3(256), 0, st, Mpc, S, (int)k, m->comp, m->smean, m->sscale, F, f0, fb, W, S);
       GP_HIP(hipGetLastError());
-      if (dmean || dvar_param) GP_TRY(launch_rowmean(W, S, 1, fb, S, nullptr, part, mu + f0, st));
-      if (dvar_param) GP_TRY(launch_rowmean(W, S, 1, fb, S, mu + f0, part, dvar_param + f0, st));
-      if (n_ranks > 0) GP_TRY(select_ranks(W, fb, S, S, 1, n_ranks, ranks, dorder + f0 * n_ranks, st));
+      if (!wt) {
+        if (dmean || dvar_param) GP_TRY(launch_rowmean(W, S, 1, fb, S, nullptr, part, mu + f0, st));
+        if (dvar_param) GP_TRY(launch_rowmean(W, S, 1, fb, S, mu + f0, part, dvar_param + f0, st));
+        if (n_ranks > 0) GP_TRY(select_ranks(W, fb, S, S, 1, n_ranks, ranks, dsel + f0 * n_ranks, st));
+        continue;
+      }
+      if (dmean || dvar_param)
+        GP_TRY(weighted_rowmean(W, S, 1, fb, S, R_w, wt->dq, wt->ldq, dQ, nullptr, 0, part, Fb, mu + f0, F, st));
+      if (dvar_param)
+        GP_TRY(weighted_rowmean(W, S, 1, fb, S, R_w, wt->dq, wt->ldq, dQ, mu + f0, F, part, Fb, dvar_param + f0, F, st));
+      for (int64_t w = 0; n_sel > 0 && w < R_w; ++w)   // a weight row at a time: its rows of dsel are contiguous
+        GP_TRY(select_rows(W, fb, S, S, 1, 1, wt->dq + w * wt->ldq, wt->ldq, n_sel, wt->targets + w * n_sel,
+                           dsel + (w * F + f0) * n_sel, std::min<int64_t>(fb, SEL_ROWS),
+                           [] { wsummary_path_count(GPEMU_WSUMMARY_PATH_SELECT_PASS); }, st));
     }
-    if (dmean) GP_HIP(hipMemcpyAsync(dmean, mu, sizeof(double) * (size_t)F, hipMemcpyDeviceToDevice, st));
+    if (dmean) GP_HIP(hipMemcpyAsync(dmean, mu, sizeof(double) * (size_t)(R_w * F), hipMemcpyDeviceToDevice, st));
   }
+  GP_HIP(hipStreamSynchronize(st));
+  return GPEMU_OK;
+}
+
+// the rows of a posterior-predictive _dev call as a view, with the checks the two families share
+static int pp_view(gpemu_model *m, const double *dX, int64_t n_blocks, int64_t block_rows, int64_t block_stride_rows,
+                   int64_t workspace_bytes, RowsView *X) {
+  GP_ARG(m && dX, "null pointer");
+  *X = RowsView{dX, n_blocks, block_rows, block_stride_rows * m->d, (int)m->d};
+  GP_TRY(rows_check(*X));
+  GP_ARG(n_blocks <= INT64_MAX / block_rows, "n_blocks * block_rows overflows");
+  GP_ARG(workspace_bytes >= 0, "workspace_bytes must be >= 0");
+  return GPEMU_OK;
+}
+
+static int ppw_check(int64_t S, int64_t R_w, int64_t n_targets, const uint64_t *targets, const void *quantiles) {
+  GP_ARG(S > 0 && S < (1ll << 31), "S must be in [1, 2^31)");
+  GP_ARG(R_w >= 1 && R_w <= WS_MAX_RW, "R_w must be in [1, 64]");
+  GP_ARG(n_targets >= 0 && n_targets < (1ll << 24), "n_targets must be in [0, 2^24)");
+  if (n_targets > 0) {
+    GP_ARG(targets && quantiles, "targets or quantiles is null with n_targets > 0");
+    for (int64_t i = 0; i < R_w * n_targets; ++i)
+      GP_ARG(targets[i] >= 1 && targets[i] <= (1ull << 53), "every target must be in [1, 2^53]");
+  }
+  return GPEMU_OK;
+}
+
+extern "C" {
+
+int gpemu_posterior_predictive_dev(gpemu_model *m, const double *dX, int64_t n_blocks, int64_t block_rows,
+                                   int64_t block_stride_rows, int64_t n_ranks, const int64_t *ranks,
+                                   int64_t workspace_bytes, double *dmean, double *dvar_param, double *dvar_emu,
+                                   double *dorder, void *stream) {
+  RowsView X;
+  GP_TRY(pp_view(m, dX, n_blocks, block_rows, block_stride_rows, workspace_bytes, &X));
+  GP_ARG(n_ranks >= 0, "n_ranks must be >= 0");
+  if (n_ranks > 0) {
+    GP_ARG(dorder, "order_stats is null with n_ranks > 0");
+    GP_TRY(select_check(m->F, X.rows(), n_ranks, ranks));
+  }
+  GP_HIP(hipSetDevice(m->device));
+  return pp_reduce(m, X, n_ranks, ranks, nullptr, workspace_bytes, dmean, dvar_param, dvar_emu, dorder,
+                   stream ? (hipStream_t)stream : m->stream);
+}
+
+int gpemu_posterior_predictive_weighted_dev(gpemu_model *m, const double *dX, int64_t n_blocks, int64_t block_rows,
+                                            int64_t block_stride_rows, int64_t R_w, const uint64_t *dq, int64_t ldq,
+                                            int64_t n_targets, const uint64_t *targets, double *dmean,
+                                            double *dvar_param, double *dvar_emu, double *dquantiles,
+                                            const gpemu_call_ctx *ctx) {
+  RowsView X;
+  GP_TRY(pp_view(m, dX, n_blocks, block_rows, block_stride_rows, ctx_workspace(ctx), &X));
+  GP_ARG(dq, "null pointer");
+  GP_TRY(ppw_check(X.rows(), R_w, n_targets, targets, dquantiles));
+  GP_ARG(ldq >= X.rows(), "ldq must be at least the number of rows");
+  GP_HIP(hipSetDevice(m->device));
+  const PpWeights wt{R_w, (const u64 *)dq, ldq, (const u64 *)targets};
+  return pp_reduce(m, X, n_targets, nullptr, &wt, ctx_workspace(ctx), dmean, dvar_param, dvar_emu, dquantiles,
+                   ctx_stream(ctx) ? ctx_stream(ctx) : m->stream);
+}
+
+int gpemu_posterior_predictive_weighted(gpemu_model *m, int64_t S, const double *X, int64_t R_w, const uint64_t *q,
+                                        int64_t n_targets, const uint64_t *targets, int64_t workspace_bytes,
+                                        double *mean, double *var_param, double *var_emu, double *quantiles) {
+  GP_ARG(m && X && q, "null pointer");
+  GP_TRY(ppw_check(S, R_w, n_targets, targets, quantiles));
+  GP_ARG(workspace_bytes >= 0, "workspace_bytes must be >= 0");
+  for (int64_t i = 0; i < S * m->d; ++i) GP_ARG(std::isfinite(X[i]), "X contains NaN or infinity");
+  GP_HIP(hipSetDevice(m->device));
+  hipStream_t st = m->stream;
+  const int64_t F = m->F;
+  DevScope sc(st);
+  double *dX = nullptr, *dm = nullptr, *dvp = nullptr, *dve = nullptr, *dqt = nullptr;
+  u64 *dq = nullptr;
+  GP_TRY(sc.alloc(&dX, S * m->d));
+  GP_TRY(sc.alloc(&dq, R_w * S));
+  if (mean) GP_TRY(sc.alloc(&dm, R_w * F));
+  if (var_param) GP_TRY(sc.alloc(&dvp, R_w * F));
+  if (var_emu) GP_TRY(sc.alloc(&dve, R_w * F));
+  if (n_targets > 0) GP_TRY(sc.alloc(&dqt, R_w * F * n_targets));
+  GP_TRY(upload(dX, X, S * m->d, st));
+  GP_TRY(upload(dq, (const u64 *)q, R_w * S, st));
+  const gpemu_call_ctx ctx{st, workspace_bytes};
+  GP_TRY(gpemu_posterior_predictive_weighted_dev(m, dX, 1, S, S, R_w, (const uint64_t *)dq, S, n_targets, targets, dm, dvp, dve, dqt, &ctx));
+  if (mean) GP_TRY(sc.download(mean, dm, R_w * F));
+  if (var_param) GP_TRY(sc.download(var_param, dvp, R_w * F));
+  if (var_emu) GP_TRY(sc.download(var_emu, dve, R_w * F));
+  if (n_targets > 0) GP_TRY(sc.download(quantiles, dqt, R_w * F * n_targets));
   GP_HIP(hipStreamSynchronize(st));
   return GPEMU_OK;
 }

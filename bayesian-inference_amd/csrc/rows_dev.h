@@ -1,7 +1,8 @@
 // What the summaries of a stored chain share.  k_rows.hip: the view of a chain as blocks of rows
 // with its checks and its gather, the pooled moments, the workspace budget, the key-only radix sort of rows with its
 // scratch; here, the host form of a function of device rows.  k_select.hip: the radix select, counted and weighted.
-// k_marginal.hip: the histogram sweep, counted and weighted.  The summaries' own kernels -- window search, density,
+// k_marginal.hip: the histogram sweep, counted and weighted.  k_wsummary.hip: the weighted row sums, and
+// here what a gpemu_call_ctx says.  The summaries' own kernels -- window search, density,
 // split, rank lookup, log-ratios -- stay in their files.
 #pragma once
 #include <algorithm>
@@ -109,6 +110,21 @@ int edges_check(const double *e, int d, int nb);
 int hist_rows(const RowsView &X, int64_t R_w, const u64 *dq, int64_t ldq, int nb1, const double *edges1, int nb2,
               const double *edges2, int64_t cap, u64 *dhist1, u64 *dhist2, u64 *dinside1, void (*on_sweep)(bool pairs),
               hipStream_t st);
+
+// ---- weighted row reductions under fixed-point weights (k_wsummary.hip) ---------------------------------
+constexpr int64_t WS_SUM = 4096;   // samples per partial sum: the chunks of k_postpred.hip's tree
+constexpr int WS_MAX_RW = 64;      // weight rows per call of the weighted summaries
+// what a gpemu_call_ctx says: null is stream NULL, workspace_bytes 0
+static inline hipStream_t ctx_stream(const gpemu_call_ctx *ctx) { return ctx ? (hipStream_t)ctx->stream : nullptr; }
+static inline int64_t ctx_workspace(const gpemu_call_ctx *ctx) { return ctx ? ctx->workspace_bytes : 0; }
+// dQ[w] = the integer sum of dq[w][0 .. S); asynchronous on st
+int weight_totals(const u64 *dq, int64_t ldq, int64_t R_w, int64_t S, u64 *dQ, hipStream_t st);
+// out[w ldo + r] = sum_s q_ws x_rs / Q_w (centre null) or sum_s q_ws (x_rs - centre[w ldc + r])^2 / Q_w for the R rows
+// x_rs = X[r rs + s es], in the tree fixed by the sample index.  part: R_w ldp ceil(S / WS_SUM) doubles of scratch,
+// ldp >= R.  Asynchronous on st
+int weighted_rowmean(const double *X, int64_t rs, int64_t es, int64_t R, int64_t S, int64_t R_w, const u64 *dq,
+                     int64_t ldq, const u64 *dQ, const double *centre, int64_t ldc, double *part, int64_t ldp,
+                     double *out, int64_t ldo, hipStream_t st);
 
 // ---- the host form of a function of device rows --------------------------------------------------------------------
 // device_ready, V [R][S] to the device, fn(dV, dout, stream) on rows of strides (S, 1), dout [R][out_per_row] back, wait

@@ -243,6 +243,20 @@ _SIGNATURES = {
                                           C.c_int, C.c_void_p, C.c_int, C.c_void_p, c_i64, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_void_p]),
     "gpemu_reweight_path_counts": (C.c_int, [C.POINTER(c_i64), c_i64]),
+    # the _dev forms end in a `const gpemu_call_ctx *` (CallCtx below; None: stream NULL, workspace 0)
+    "gpemu_posterior_predictive_weighted": (C.c_int, [C.c_void_p, c_i64, C.c_void_p, c_i64, C.c_void_p, c_i64, C.c_void_p,
+                                                      c_i64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gpemu_posterior_predictive_weighted_dev": (C.c_int, [C.c_void_p, C.c_void_p, c_i64, c_i64, c_i64, c_i64, C.c_void_p,
+                                                          c_i64, c_i64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                          C.c_void_p, C.c_void_p]),
+    "gpemu_weighted_hpd": (C.c_int, [C.c_int, c_i64, c_i64, C.c_void_p, c_i64, C.c_void_p, c_i64, C.c_void_p, C.c_void_p]),
+    "gpemu_weighted_hpd_dev": (C.c_int, [C.c_int, c_i64, c_i64, C.c_void_p, c_i64, c_i64, c_i64, C.c_void_p, c_i64, c_i64,
+                                         C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gpemu_weighted_kde1d": (C.c_int, [C.c_int, c_i64, c_i64, C.c_void_p, c_i64, C.c_void_p, c_i64, C.c_void_p,
+                                       C.c_void_p, C.c_void_p]),
+    "gpemu_weighted_kde1d_dev": (C.c_int, [C.c_int, c_i64, c_i64, C.c_void_p, c_i64, c_i64, c_i64, C.c_void_p, c_i64, c_i64,
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gpemu_wsummary_path_counts": (C.c_int, [C.POINTER(c_i64), c_i64]),
     "gpemu_devmem_stats": (C.c_int, [C.POINTER(c_i64), c_i64]),
     "gpemu_devmem_refuse_nth": (C.c_int, [c_i64, C.POINTER(c_i64)]),
     "gpemu_pca_sweep_limit_next": (C.c_int, [c_i64, C.POINTER(c_i64)]),
@@ -420,3 +434,15 @@ def current_stream(device):
     import torch
     dev = device if isinstance(device, torch.device) else torch.device("cuda", int(device))
     return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+
+class CallCtx(C.Structure):
+    """``gpemu_call_ctx`` of include/gpemu.h: the stream and the workspace limit of a ``_dev`` call, together."""
+    _fields_ = [("stream", C.c_void_p), ("workspace_bytes", C.c_int64)]
+
+
+def call_ctx(device, workspace_bytes=0, stream=None):
+    """The ``gpemu_call_ctx`` of a call on ``stream`` (None: torch's current stream on ``device``); pass it with
+    ``ctypes.byref`` and keep it alive over the call."""
+    st = current_stream(device) if stream is None else C.c_void_p(int(stream) or None)
+    return CallCtx(st.value, int(workspace_bytes))

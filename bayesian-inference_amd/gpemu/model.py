@@ -252,6 +252,46 @@ class DeviceModel:
             ptr(ranks) if ranks.size else None, int(workspace_bytes), vp(dmean_ptr), vp(dvar_param_ptr), vp(dvar_emu_ptr),
             vp(dorder_ptr), C.c_void_p(self._stream(stream)[0])))
 
+    def posterior_predictive_weighted(self, X, q, probabilities=(0.05, 0.5, 0.95), workspace_bytes=0):
+        """``posterior_predictive`` of the rows of ``X`` (S, d) under every row of the fixed-point weights ``q`` (R_w, S)
+        (``gpemu.reweight.fixed_weights``): a list with one dict per weight row, the keys of
+        ``posterior_predictive`` plus ``total_weight`` (the integer ``Q = sum_s q_s``).  ``mean``, the two variances and
+        ``variance`` are the weighted ones; ``quantiles`` (nq, F) are the inverted weighted ECDF of the central value at
+        ``max(1, ceil(p Q))``, elements of the sample as ``gpemu.reweight.weighted_quantile``'s (not interpolated).  The
+        result, bit for bit, does not depend on ``workspace_bytes``."""
+        from . import reweight as RW
+        X = self._finite(self._X(X))
+        S = int(X.shape[0])
+        q = np.ascontiguousarray(np.atleast_2d(np.asarray(q)), dtype=np.uint64)
+        if q.ndim != 2 or q.shape[1] != S or not 1 <= q.shape[0] <= RW.MAX_SCENARIOS:
+            raise ValueError(f"q must be (R_w, {S}) with R_w in [1, {RW.MAX_SCENARIOS}]")
+        R_w, Q = int(q.shape[0]), RW._totals(q)
+        if np.any(Q == 0):
+            raise ValueError("a weight row is all zero")
+        p = np.zeros(0) if probabilities is None else np.asarray(probabilities, dtype=np.float64).reshape(-1).copy()
+        tgt = RW.targets(p, Q) if p.size else np.zeros((R_w, 0), dtype=np.uint64)
+        mean, vp, ve = (np.empty((R_w, self.F)) for _ in range(3))
+        quant = np.empty((R_w, self.F, max(p.size, 1)))
+        check(_lib.lib().gpemu_posterior_predictive_weighted(
+            self._h, S, ptr(X), R_w, ptr(q), int(p.size), ptr(tgt) if p.size else None, int(workspace_bytes), ptr(mean),
+            ptr(vp), ptr(ve), ptr(quant) if p.size else None))
+        return weighted_postpred_result(mean, vp, ve, quant, p, Q)
+
+    def posterior_predictive_weighted_dev(self, dX_ptr, n_blocks, block_rows, block_stride_rows, q, targets, dmean_ptr,
+                                          dvar_param_ptr, dvar_emu_ptr, dquantiles_ptr, workspace_bytes=0, stream=None):
+        """The device-pointer entry: the rows as ``posterior_predictive_dev`` reads them, ``q`` an int64 device tensor
+        (R_w, S) of the fixed-point weights, ``targets`` a host uint64 array (R_w, n_targets) (may be empty), the outputs
+        device pointers to (R_w, F) and (R_w, F, n_targets) (0: not wanted).  ``stream``: see ``_stream`` (None: torch's
+        current stream), passed with ``workspace_bytes`` in a ``gpemu_call_ctx``.  Waits for the stream."""
+        targets = np.ascontiguousarray(targets, dtype=np.uint64)
+        R_w, nt = int(q.shape[0]), (int(targets.shape[1]) if targets.size else 0)
+        vp = lambda a: C.c_void_p(a) if a else None
+        ctx = _lib.CallCtx(self._stream(stream)[0], int(workspace_bytes))
+        check(_lib.lib().gpemu_posterior_predictive_weighted_dev(
+            self._h, C.c_void_p(dX_ptr), int(n_blocks), int(block_rows), int(block_stride_rows), R_w,
+            C.c_void_p(q.data_ptr()), int(q.shape[1]), nt, ptr(targets) if nt else None, vp(dmean_ptr), vp(dvar_param_ptr),
+            vp(dvar_emu_ptr), vp(dquantiles_ptr), C.byref(ctx)))
+
     # -- global sensitivity (DESIGN.md §4.28) ----------------------------------------------------------------
     def design(self, reference, candidates, **kw):
         """``gpemu.design.Design`` of this one group: the sequential-design criterion (integrated variance reduction;
@@ -554,6 +594,19 @@ class QuantilePlan:
         return {"mean": mean, "variance_parameters": var_param, "variance_emulator": var_emu,
                 "variance": var_param + var_emu, "quantiles": self.quantiles(order),
                 "probabilities": self.probabilities}
+
+
+def weighted_postpred_result(mean, var_param, var_emu, quantiles, probabilities, Q):
+    """One dict per weight row from ``gpemu_posterior_predictive_weighted``'s outputs ``(R_w, F)`` and
+    ``(R_w, F, nq)``: ``posterior_predictive``'s keys plus ``total_weight``."""
+    p = np.asarray(probabilities, dtype=np.float64).reshape(-1)
+    out = []
+    for w in range(mean.shape[0]):
+        qs = np.ascontiguousarray(quantiles[w, :, :p.size].T) if p.size else np.zeros((0, mean.shape[1]))
+        out.append({"mean": mean[w], "variance_parameters": var_param[w], "variance_emulator": var_emu[w],
+                    "variance": var_param[w] + var_emu[w], "quantiles": qs, "probabilities": p.copy(),
+                    "total_weight": int(Q[w])})
+    return out
 
 
 POSTPRED_FIXED_BYTES = 32 << 20    # GPEMU_POSTPRED_FIXED_BYTES

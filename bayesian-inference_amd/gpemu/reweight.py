@@ -12,7 +12,9 @@ when the answer cannot be trusted, and every chain summary has a weighted form:
 * ``weights``: normalised log-weights (PSIS, or raw with ``smooth=False``), ``pareto_k``, ``ess_w``, ``log_mean_ratio``;
 * ``fixed_weights``: the weights as integers ``q = rint(w 2^52)``, so that every weighted sum is exact;
 * ``weighted_quantile``, ``weighted_histograms``: the inverted weighted ECDF and ``np.histogram(weights=q)``, exact;
-* ``summary``: one dict per scenario.
+* ``weighted_hpd``, ``weighted_kde_1d``: the highest-density intervals by value under the weights,
+  exact, and the Gaussian kernel density with ``scipy.stats.gaussian_kde(x, weights=w)``'s bandwidth;
+* ``summary``: one dict per scenario (``hpd=``, ``kde=`` add the two above).
 
 Samples are ``(S, d)``: numpy arrays go through the host entries, contiguous float64 device tensors are read in place.
 There is no CPU implementation."""
@@ -32,6 +34,9 @@ KINDS = {"flat": 0, "log_uniform": 1, "normal": 2, "log_normal": 3}
 MAX_D, MAX_SCENARIOS = 16, 64
 MAX_BINS_1D, MAX_BINS_2D = 4096, 256
 ONE = 1 << 52   # the fixed-point unit of the weights
+# enum gpemu_wsummary_path
+WSUMMARY_PATHS = ("BANDS_WHOLE", "BANDS_FEATURE_BLOCKED", "ROW_REDUCE", "SELECT_PASS", "HPD_SORT_BATCH", "HPD_PLACE",
+                  "HPD_SCAN", "HPD_WINDOW", "KDE")
 
 
 def path_counts():
@@ -41,6 +46,15 @@ def path_counts():
     if n < 0:
         check(n)
     return {k: int(out[i]) for i, k in enumerate(PATHS)}
+
+
+def wsummary_path_counts():
+    """The library's counters of the weighted bands, intervals and densities since the process started, by name."""
+    out = (C.c_int64 * len(WSUMMARY_PATHS))()
+    n = _lib.lib().gpemu_wsummary_path_counts(out, len(WSUMMARY_PATHS))
+    if n < 0:
+        check(n)
+    return {k: int(out[i]) for i, k in enumerate(WSUMMARY_PATHS)}
 
 
 # -- host-side rules --------------------------------------------------------------------------------------------------
@@ -135,6 +149,18 @@ def targets(p, Q):
         for i, pi in enumerate(p):
             out[r, i] = max(1, math.ceil(Fraction(float(pi)) * Qr))
     return out
+
+
+def weighted_bandwidth(var_w, n_eff):
+    """``scipy.stats.gaussian_kde(x, weights=w)``'s default bandwidth for 1-D data: ``n_eff ** (-1 / 5)`` times the square
+    root of the unbiased weighted variance ``var_w / (1 - sum w^2)``, with ``var_w = sum_s w_s (x_s - mean_w)^2`` for
+    normalised weights and ``n_eff = 1 / sum w^2`` (``ess_w``).  Broadcasts; ``n_eff <= 1`` (one sample carries all the
+    weight) gives NaN."""
+    var_w, n_eff = np.asarray(var_w, dtype=np.float64), np.asarray(n_eff, dtype=np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        unbiased = var_w / (1.0 - 1.0 / n_eff)
+        h = np.power(n_eff, -1.0 / 5.0) * np.sqrt(unbiased)
+    return np.where(n_eff > 1.0, h, np.nan)
 
 
 def _log_diff_ndtr(zl, zu):
@@ -284,6 +310,38 @@ def weighted_hist_dev(device, base, n_blocks, block_rows, block_stride_rows, d, 
                                              _lib.current_stream(device)))
     u = lambda t: t.cpu().numpy().view(np.uint64)
     return u(h1), u(h2[:, :npairs].contiguous()), u(wi)
+
+
+def weighted_hpd_dev(device, base, R_v, S, row_stride, elem_stride, q, tgt, workspace_bytes=0):
+    """The highest-density intervals of target masses ``tgt (R_w, n_levels)`` uint64 of the ``R_v`` device rows (addressed
+    as ``weighted_quantile_dev``'s) under the int64 device tensor ``q (R_w, S)``: numpy ``(R_w, R_v, n_levels, 2)``."""
+    import torch
+    tgt = np.ascontiguousarray(tgt, dtype=np.uint64)
+    R_w, nl = int(q.shape[0]), int(tgt.shape[1])
+    if tgt.shape[0] != R_w or int(q.shape[1]) != int(S):
+        raise ValueError("the targets and the weights must have one row per weight row, the weights S columns")
+    out = torch.empty((R_w, int(R_v), nl, 2), dtype=torch.float64, device=q.device)
+    ctx = _lib.call_ctx(device, workspace_bytes)
+    check(_lib.lib().gpemu_weighted_hpd_dev(int(device), int(R_v), int(S), C.c_void_p(base), int(row_stride),
+                                            int(elem_stride), R_w, C.c_void_p(q.data_ptr()), int(S), nl, ptr(tgt),
+                                            C.c_void_p(out.data_ptr()), C.byref(ctx)))
+    return out.cpu().numpy()
+
+
+def weighted_kde_dev(device, base, R_v, S, row_stride, elem_stride, q, grid, h):
+    """The weighted densities of the ``R_v`` device rows under ``q (R_w, S)`` on ``grid (R_w, R_v, G)`` with bandwidths
+    ``h (R_w, R_v)``: numpy ``(R_w, R_v, G)``."""
+    import torch
+    grid, h = np.ascontiguousarray(grid, dtype=np.float64), np.ascontiguousarray(h, dtype=np.float64)
+    R_w, G = int(q.shape[0]), int(grid.shape[-1])
+    if grid.shape != (R_w, int(R_v), G) or h.shape != (R_w, int(R_v)) or int(q.shape[1]) != int(S):
+        raise ValueError("grid must be (R_w, R_v, G), h (R_w, R_v) and the weights (R_w, S)")
+    out = torch.empty((R_w, int(R_v), G), dtype=torch.float64, device=q.device)
+    ctx = _lib.call_ctx(device)
+    check(_lib.lib().gpemu_weighted_kde1d_dev(int(device), int(R_v), int(S), C.c_void_p(base), int(row_stride),
+                                              int(elem_stride), R_w, C.c_void_p(q.data_ptr()), int(S), G, ptr(grid), ptr(h),
+                                              C.c_void_p(out.data_ptr()), C.byref(ctx)))
+    return out.cpu().numpy()
 
 
 # -- public functions -------------------------------------------------------------------------------------------------
@@ -442,6 +500,132 @@ def weighted_histograms(samples, lower, upper, q, bins_1d=100, bins_2d=50, devic
     return {"edges_1d": e1, "edges_2d": e2, "pairs": M.pair_indices(d), "hist_1d_q": h1, "hist_2d_q": h2, "w_inside": wi}
 
 
+def weighted_hpd(values, confidence, q, Q=None, device=None, workspace_bytes=0):
+    """The highest-density intervals by value of every column of ``values (S, d)`` under every row of the fixed-point
+    weights ``q (R_w, S)``: ``(R_w, n_levels, d, 2)``.  For confidence ``c`` the target mass is ``t = max(1, ceil(c Q))``
+    (``targets``); over every sample value ``a``, with ``b(a)`` the smallest sample value ``>= a`` whose closed interval
+    holds weight ``>= t``, the ``(a, b(a))`` of the smallest width ``b - a``, equal widths to the smaller ``a``.  Both
+    ends are elements of the input.  NaN for a column with a NaN or an infinite extreme."""
+    x, on_device = _samples(values)
+    S, d = int(x.shape[0]), int(x.shape[1])
+    tgt = targets(confidence, _totals(q) if Q is None else Q)
+    if on_device:
+        dq = _q_tensor(q, x.device.index or 0)
+        out = weighted_hpd_dev(x.device.index or 0, x.data_ptr(), d, S, 1, d, dq, tgt, workspace_bytes)
+    else:
+        _lib.require_device()
+        qh = np.ascontiguousarray(np.atleast_2d(q), dtype=np.uint64)
+        if qh.shape[1] != S or tgt.shape[0] != qh.shape[0]:
+            raise ValueError(f"the weights must be (R_w, {S})")
+        out = np.empty((qh.shape[0], d, tgt.shape[1], 2))
+        check(_lib.lib().gpemu_weighted_hpd(int(_lib.resolve_device(device)), d, S, ptr(np.ascontiguousarray(x.T)),
+                                            int(qh.shape[0]), ptr(qh), int(tgt.shape[1]), ptr(tgt), ptr(out)))
+    return np.ascontiguousarray(out.transpose(0, 2, 1, 3))
+
+
+def _kde_plan(var_w, n_eff, xmin, xmax, R_w, d, grid, bandwidth, n_grid, cut):
+    """Bandwidths ``(R_w, d)`` and grids ``(R_w, d, G)`` of the weighted densities: as given (a number, ``(d,)`` or
+    ``(R_w, d)``; ``(G,)``, ``(d, G)`` or ``(R_w, d, G)``), else ``weighted_bandwidth`` and seaborn's support."""
+    from . import marginals as M
+    if bandwidth is None:
+        h = weighted_bandwidth(var_w, np.asarray(n_eff, dtype=np.float64).reshape(-1, 1))
+    else:
+        h = np.broadcast_to(np.asarray(bandwidth, dtype=np.float64), (R_w, d)).copy()
+    if not np.all(np.isfinite(h) & (h > 0.0)):
+        raise ValueError(f"every bandwidth must be finite and > 0, got {h} (the default needs an effective sample size "
+                         "above 1 and a positive weighted variance)")
+    if grid is None:
+        if int(n_grid) < 1:
+            raise ValueError("n_grid must be >= 1")
+        if not (np.all(np.isfinite(xmin)) and np.all(np.isfinite(xmax))):
+            raise ValueError("the default grid needs finite samples")
+        g = np.stack([M.default_grid(xmin, xmax, h[w], n_grid, cut) for w in range(R_w)])
+    else:
+        g = np.asarray(grid, dtype=np.float64)
+        if g.ndim < 1 or g.ndim > 3 or g.shape[-1] < 1:
+            raise ValueError(f"grid must be (G,), ({d}, G) or ({R_w}, {d}, G)")
+        g = np.broadcast_to(g, (R_w, d, g.shape[-1])).copy()
+    return np.ascontiguousarray(h), np.ascontiguousarray(g)
+
+
+def weighted_kde_1d(values, q, log_weights=None, grid=None, bandwidth=None, n_grid=200, cut=3.0, Q=None, device=None):
+    """The Gaussian kernel density of every column of ``values (S, d)`` under every row of the fixed-point weights
+    ``q (R_w, S)``, ``1 / (Q h sqrt(2 pi)) sum_s q_s exp(-(grid - x_s)^2 / (2 h^2))`` as a direct sum: a dict of ``grid
+    (R_w, d, G)``, ``density (R_w, d, G)`` and ``bandwidth (R_w, d)``.  ``bandwidth``: default ``weighted_bandwidth``,
+    ``scipy.stats.gaussian_kde(x, weights=w)``'s rule, from the weighted variance of ``gpemu.loo.weighted_moments_dev``
+    under ``log_weights (R_w, S)`` (the normalised log-weights ``q`` was made from; default ``log(q / Q)``) and ``n_eff =
+    1 / sum w^2``; ``grid``: default ``linspace(min - cut h, max + cut h, n_grid)`` over all samples."""
+    import torch
+    from . import loo as LO
+    x, on_device = _samples(values)
+    S, d = int(x.shape[0]), int(x.shape[1])
+    Q = _totals(q) if Q is None else np.atleast_1d(Q)
+    if np.any(np.asarray(Q) == 0):
+        raise ValueError("a weight row is all zero")
+    dev = (x.device.index or 0) if on_device else int(_lib.resolve_device(device))
+    if not on_device:
+        _lib.require_device()
+    R_w = len(Q)
+    var_w = n_eff = xmin = xmax = None
+    if bandwidth is None:
+        dx = x if on_device else _to_device(x, dev)
+        if log_weights is None:
+            dq = _q_tensor(q, dev).to(torch.float64)
+            lw = torch.log(dq) - torch.log(torch.from_numpy(np.asarray(Q).astype(np.float64)).to(dq.device))[:, None]
+        else:
+            lw, lw_dev = _rows(log_weights)
+            lw = lw if lw_dev else _to_device(np.ascontiguousarray(lw, dtype=np.float64), dev)
+        _, var_w = LO.weighted_moments_dev(dev, dx.data_ptr(), 1, S, S, d, lw)
+        n_eff = np.exp(-(logmeanexp_dev(lw * 2.0) + math.log(S)))
+    if grid is None:
+        xmin = x.amin(dim=0).cpu().numpy() if on_device else x.min(axis=0)
+        xmax = x.amax(dim=0).cpu().numpy() if on_device else x.max(axis=0)
+    h, g = _kde_plan(var_w, n_eff, xmin, xmax, R_w, d, grid, bandwidth, n_grid, cut)
+    if on_device:
+        dens = weighted_kde_dev(dev, x.data_ptr(), d, S, 1, d, _q_tensor(q, dev), g, h)
+    else:
+        qh = np.ascontiguousarray(np.atleast_2d(q), dtype=np.uint64)
+        if qh.shape != (R_w, S):
+            raise ValueError(f"the weights must be (R_w, {S})")
+        dens = np.empty(g.shape)
+        check(_lib.lib().gpemu_weighted_kde1d(dev, d, S, ptr(np.ascontiguousarray(x.T)), R_w, ptr(qh), int(g.shape[-1]),
+                                              ptr(g), ptr(h), ptr(dens)))
+    return {"grid": g, "density": dens, "bandwidth": h}
+
+
+def bands_of_view(models, view, q, Q, probabilities=(0.05, 0.5, 0.95), workspace_bytes=0):
+    """The weighted posterior-predictive bands of device rows ``view = (device, address, n_blocks, block_rows,
+    block_stride_rows, S)`` under the int64 device tensor ``q (R_w, S)`` with totals ``Q``: a list over the weight rows of
+    ``{"posterior_predictive": [one dict per model]}`` (``DeviceModel.posterior_predictive_weighted``'s dicts)."""
+    import torch
+    from .model import weighted_postpred_result
+    device, src, n_blocks, nw, stride, S = view
+    p = np.zeros(0) if probabilities is None else np.asarray(probabilities, dtype=np.float64).reshape(-1)
+    R_w = int(q.shape[0])
+    tgt = targets(p, Q) if p.size else np.zeros((R_w, 0), dtype=np.uint64)
+    per_model = []
+    for m in models:
+        mean, vp, ve = (torch.empty((R_w, m.F), dtype=torch.float64, device=q.device) for _ in range(3))
+        qt = torch.empty((R_w, m.F, max(p.size, 1)), dtype=torch.float64, device=q.device)
+        m.posterior_predictive_weighted_dev(src, n_blocks, nw, stride, q, tgt, mean.data_ptr(), vp.data_ptr(),
+                                            ve.data_ptr(), qt.data_ptr() if p.size else 0, workspace_bytes)
+        per_model.append(weighted_postpred_result(mean.cpu().numpy(), vp.cpu().numpy(), ve.cpu().numpy(),
+                                                  qt.cpu().numpy(), p, Q))
+    return [{"posterior_predictive": [pm[w] for pm in per_model]} for w in range(R_w)]
+
+
+def add_hpd_kde(out, hpd_conf, hpd, kde):
+    """``summary``'s optional entries into its list of dicts: ``hpd_confidence``, ``hpd (n_levels, d, 2)`` where ``hpd``
+    ``(R_w, n_levels, d, 2)`` is given; ``kde_grid``, ``kde_density`` ``(d, G)``, ``kde_bandwidth (d,)`` where ``kde`` is."""
+    for r, res in enumerate(out):
+        if hpd is not None:
+            res["hpd_confidence"] = np.atleast_1d(np.asarray(hpd_conf, dtype=np.float64)).copy()
+            res["hpd"] = hpd[r]
+        if kde is not None:
+            res["kde_grid"], res["kde_density"], res["kde_bandwidth"] = kde["grid"][r], kde["density"][r], kde["bandwidth"][r]
+    return out
+
+
 def assemble(stats, S, Q, mean, var, mean0, var0, quantiles, hist, probabilities, log_norm=None, log_volume=None):
     """One dict per scenario from the pieces: see ``summary``."""
     from . import loo as LO
@@ -464,11 +648,13 @@ def assemble(stats, S, Q, mean, var, mean0, var0, quantiles, hist, probabilities
 
 
 def summary_view(view, d, log_ratio_dev, lower, upper, probabilities=(0.05, 0.5, 0.95), bins_1d=100, bins_2d=50,
-                 smooth=True, r_eff=None, log_norm=None, baseline=None, column_src=None, workspace_bytes=0):
+                 smooth=True, r_eff=None, log_norm=None, baseline=None, column_src=None, workspace_bytes=0, hpd=None,
+                 kde=False, n_grid=200, extra=None):
     """``summary`` of device rows ``view = (device, address, n_blocks, block_rows, block_stride_rows, S)`` under the
     device tensor ``log_ratio_dev (R, S)``.  ``column_src``: the address of a dense copy ``[S][d]`` where one parameter
     of the view is not a single stride (a thinned chain, one chain of a stacked sampler); ``baseline()``: the unweighted
-    ``(mean, var)`` where the caller has them, else the same reduction under uniform weights."""
+    ``(mean, var)`` where the caller has them, else the same reduction under uniform weights.  ``hpd`` (confidence
+    levels), ``kde``: see ``summary``; ``extra(q, Q)``: further entries per scenario, a list of dicts to merge in."""
     import torch
     from . import loo as LO
     from . import marginals as M
@@ -496,20 +682,36 @@ def summary_view(view, d, log_ratio_dev, lower, upper, probabilities=(0.05, 0.5,
     quant = weighted_quantile_dev(device, cols, d, S, 1, d, q, tgt, workspace_bytes).transpose(0, 2, 1)
     h1, h2, wi = weighted_hist_dev(device, src, n_blocks, nw, stride, d, q, e1, e2)
     hist = {"edges_1d": e1, "edges_2d": e2, "pairs": M.pair_indices(d), "hist_1d_q": h1, "hist_2d_q": h2, "w_inside": wi}
-    return assemble(st, S, Q, mean, var, np.asarray(mean0), np.asarray(var0), np.ascontiguousarray(quant), hist,
-                    probabilities, log_norm, float(np.sum(np.log(hi - lo))))
+    out = assemble(st, S, Q, mean, var, np.asarray(mean0), np.asarray(var0), np.ascontiguousarray(quant), hist,
+                   probabilities, log_norm, float(np.sum(np.log(hi - lo))))
+    iv = dens = None
+    if hpd is not None:
+        iv = weighted_hpd_dev(device, cols, d, S, 1, d, q, targets(hpd, Q), workspace_bytes).transpose(0, 2, 1, 3)
+        iv = np.ascontiguousarray(iv)
+    if kde:
+        ends = M._hpd_dev(device, cols, S, d, [1])[0]         # n_out = 1, window 0: (smallest, largest)
+        h, g = _kde_plan(var, st["ess_w"], ends[:, 0], ends[:, 1], len(Q), d, None, None, n_grid, 3.0)
+        dens = {"grid": g, "density": weighted_kde_dev(device, cols, d, S, 1, d, q, g, h), "bandwidth": h}
+    add_hpd_kde(out, hpd, iv, dens)
+    if extra is not None:
+        for res, more in zip(out, extra(q, Q)):
+            res.update(more)
+    return out
 
 
 def summary(samples, log_ratio, lower, upper, probabilities=(0.05, 0.5, 0.95), bins_1d=100, bins_2d=50, smooth=True,
-            r_eff=None, log_norm=None, device=None):
+            r_eff=None, log_norm=None, device=None, hpd=None, kde=False, n_grid=200, extra=None):
     """The reweighted posterior of ``samples (S, d)`` under every row of ``log_ratio (R, S)``: a list with one dict per
     scenario -- ``pareto_k``, ``k_threshold`` (``gpemu.loo.k_threshold``), ``ess_w``, ``reliable = pareto_k <=
     k_threshold``, ``log_mean_ratio``, ``log_evidence_ratio`` (with ``log_norm`` from ``log_prior_norm``: the log Bayes
     factor between the normalised priors; else ``None``), ``mean``, ``sd`` ``(d,)`` under the weights, ``shift = (mean -
     mean_old) / sd_old``, ``quantiles (nq, d)``, the histograms of ``gpemu.marginals.histograms``' edges as exact integers
     ``hist_1d_q``, ``hist_2d_q`` and as densities ``hist_1d``, ``hist_2d`` ``= hist_q / Q``, ``Q``, ``edges_1d``,
-    ``edges_2d``, ``pairs``.  numpy samples go through the host entries, a float64 device tensor is read in place; the
-    results are the same bits."""
+    ``edges_2d``, ``pairs``.  ``hpd``: confidence levels, adds ``hpd_confidence`` and ``hpd (n_levels, d, 2)``
+    (``weighted_hpd``); ``kde=True`` adds ``kde_grid``, ``kde_density`` ``(d, n_grid)`` and ``kde_bandwidth (d,)``
+    (``weighted_kde_1d`` with its defaults, the weighted variance and ``ess_w`` of this summary); ``extra(q, Q)``:
+    further entries per scenario, a list of dicts to merge in (``q`` as the samples are: numpy or device).  numpy samples go
+    through the host entries, a float64 device tensor is read in place; the results are the same bits."""
     import torch
     from . import loo as LO
     x, on_device = _samples(samples)
@@ -521,7 +723,7 @@ def summary(samples, log_ratio, lower, upper, probabilities=(0.05, 0.5, 0.95), b
         dev = x.device.index or 0
         dL = L if l_dev else _to_device(np.ascontiguousarray(L, dtype=np.float64), dev)
         return summary_view((dev, x.data_ptr(), 1, S, S, S), d, dL, lower, upper, probabilities, bins_1d, bins_2d, smooth,
-                            r_eff, log_norm)
+                            r_eff, log_norm, hpd=hpd, kde=kde, n_grid=n_grid, extra=extra)
     _lib.require_device()
     dev = int(_lib.resolve_device(device))
     lo, hi = _box(lower, upper, d)
@@ -536,12 +738,25 @@ def summary(samples, log_ratio, lower, upper, probabilities=(0.05, 0.5, 0.95), b
                                      torch.zeros((1, S), dtype=torch.float64, device=dx.device))
     quant = weighted_quantile(x, probabilities, q, Q, device=dev)
     hist = weighted_histograms(x, lo, hi, q, bins_1d, bins_2d, device=dev)
-    return assemble(st, S, Q, mean, var, m0[0], v0[0], quant, hist, probabilities, log_norm,
-                    float(np.sum(np.log(hi - lo))))
+    out = assemble(st, S, Q, mean, var, m0[0], v0[0], quant, hist, probabilities, log_norm,
+                   float(np.sum(np.log(hi - lo))))
+    iv = dens = None
+    if hpd is not None:
+        iv = weighted_hpd(x, hpd, q, Q, device=dev)
+    if kde:
+        h, g = _kde_plan(var, st["ess_w"], x.min(axis=0), x.max(axis=0), len(Q), d, None, None, n_grid, 3.0)
+        dens = weighted_kde_1d(x, q, grid=g, bandwidth=h, Q=Q, device=dev)
+    add_hpd_kde(out, hpd, iv, dens)
+    if extra is not None:
+        for res, more in zip(out, extra(q, Q)):
+            res.update(more)
+    return out
 
 
-def chain_reweight(models, X, priors=None, models_new=None, lower=None, upper=None, chain=0, **summary_kw):
-    """``DeviceSampler.reweight`` for a chain on the host: ``X (S, d)``, the flattened rows, of a sampler over ``models``."""
+def chain_reweight(models, X, priors=None, models_new=None, lower=None, upper=None, chain=0, posterior_predictive=False,
+                   **summary_kw):
+    """``DeviceSampler.reweight`` for a chain on the host: ``X (S, d)``, the flattened rows, of a sampler over ``models``
+    (whose bands ``posterior_predictive`` adds)."""
     models = list(models) if isinstance(models, (list, tuple)) else [models]
     X = np.ascontiguousarray(X, dtype=np.float64)
     if X.ndim != 2 or X.shape[0] < 1 or X.shape[1] != models[0].d:
@@ -556,4 +771,11 @@ def chain_reweight(models, X, priors=None, models_new=None, lower=None, upper=No
     log_norm = None
     if priors is not None and models_new is None:
         log_norm = log_prior_norm(*check_priors(priors, X.shape[1], lower, upper), lower, upper)
-    return summary(X, L, lower, upper, log_norm=log_norm, device=models[0].device, **summary_kw)
+    extra = None
+    if posterior_predictive:
+        probs = summary_kw.get("probabilities", (0.05, 0.5, 0.95))
+
+        def extra(q, Q):
+            per_model = [m.posterior_predictive_weighted(X, q, probs) for m in models]
+            return [{"posterior_predictive": [pm[w] for pm in per_model]} for w in range(len(Q))]
+    return summary(X, L, lower, upper, log_norm=log_norm, device=models[0].device, extra=extra, **summary_kw)

@@ -427,13 +427,17 @@ class DeviceSampler:
                              workspace_bytes, baseline=(lambda: self.chain_moments(discard)) if whole else None)
 
     def reweight(self, priors=None, models_new=None, discard=0, thin=1, chain=None, lower=None, upper=None,
-                 **summary_kw):
+                 posterior_predictive=False, models=None, **summary_kw):
         """The posterior under another prior or under other data, from the stored chain ``get_chain()[discard::thin]``
         read in place on the device (``gpemu.reweight.summary``): a list with one dict per scenario.
         ``priors``: a list of prior scenarios (``gpemu.reweight.check_priors``) inside the box, which defaults to the
         prior box of the sampler's models; ``models_new``: the sampler's emulators with another ``likelihood_setup`` (a
         data scenario: one row, or added to every prior scenario).  ``summary_kw``: ``probabilities``, ``bins_1d``,
-        ``bins_2d``, ``smooth``, ``r_eff``.  The log-ratios, moments and histograms read the view as it lies, thinned or
+        ``bins_2d``, ``smooth``, ``r_eff``, and ``hpd`` (confidence levels), ``kde`` for the weighted highest-density
+        intervals and 1-D densities.  With ``posterior_predictive`` every scenario's dict gains
+        ``posterior_predictive``: a list with one dict per model of ``models`` (default: the sampler's groups), the
+        weighted bands of ``DeviceModel.posterior_predictive_weighted`` on the same view under the scenario's weights,
+        at ``probabilities``.  The log-ratios, moments and histograms read the view as it lies, thinned or
         stacked; the quantiles read one parameter as one stride, so a thinned chain or one chain of a stacked sampler is
         first copied to a dense device buffer, as ``marginals`` does.  Stacked samplers take ``chain=<index>``."""
         import torch
@@ -459,9 +463,17 @@ class DeviceSampler:
             check(_lib.lib().gpemu_marginal_dense_dev(self.device, C.c_void_p(src), n_blocks, nw, stride, d,
                                                       C.c_void_p(dense.data_ptr()), _lib.current_stream(self.device)))
         whole = thin == 1 and nw == self.W      # else a thinned or stacked view: the same reduction, uniform weights
+        extra = None
+        if posterior_predictive:
+            pp_models = self.models if models is None else list(models)
+            for m in pp_models:
+                if m.d != self.d or m.device != self.device:
+                    raise ValueError("model and sampler differ in parameters or device")
+            probs = summary_kw.get("probabilities", (0.05, 0.5, 0.95))
+            extra = lambda q, Q: RW.bands_of_view(pp_models, view, q, Q, probs, summary_kw.get("workspace_bytes", 0))
         return RW.summary_view(view, d, L, lower, upper, log_norm=log_norm,
                                baseline=(lambda: self.chain_moments(discard)) if whole else None,
-                               column_src=None if dense is None else dense.data_ptr(), **summary_kw)
+                               column_src=None if dense is None else dense.data_ptr(), extra=extra, **summary_kw)
 
     def _box_or_prior(self, lower, upper):
         """``(lower, upper)``, each defaulting to the prior box of the sampler's models."""
@@ -1489,11 +1501,14 @@ class EnsembleSampler:
 
     def get_reweighted(self, discard=0, thin=1, models=None, **kw):
         """``DeviceSampler.reweight`` of ``get_chain(discard=discard, thin=thin)`` (``priors``, ``models_new``, ``lower``,
-        ``upper``, ``probabilities``, ``bins_1d``, ``bins_2d``, ``smooth``, ``r_eff``): in place while the chain still lives
-        on the device, from the host copy otherwise (``models`` are then required: the device models with the likelihood
-        set up)."""
+        ``upper``, ``probabilities``, ``bins_1d``, ``bins_2d``, ``smooth``, ``r_eff``, ``hpd``, ``kde``,
+        ``posterior_predictive``): in place while the chain still lives on the device, from the host copy otherwise
+        (``models`` are then required: the device models with the likelihood set up).  With ``posterior_predictive`` the
+        bands are those of ``models`` (default: the sampler's groups)."""
         discard, thin = int(discard), int(thin)
         if self._impl is not None and getattr(self, "_device", False) and not self.__dict__.get("_frozen"):
+            if kw.get("posterior_predictive") and models is not None:
+                kw = dict(kw, models=models)
             return self._impl.reweight(discard=discard + thin - 1, thin=thin, **kw)
         from . import reweight
         if models is None:

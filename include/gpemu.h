@@ -21,6 +21,9 @@
  *     A model's own stream is a non-blocking stream: it is NOT ordered with the null stream or with any other stream.
  *     Work the caller enqueued elsewhere must have finished before a call on the model's stream reads it, and
  *     gpemu_model_sync comes before anything else reads the results.
+ *     The *_dev entries of the weighted chain summaries take their stream and their workspace limit
+ *     together, in a gpemu_call_ctx; their section says what a NULL stream means, and each of them waits for its stream
+ *     before it returns.
  *   - Every function returns int: 0 = ok, <0 = argument / runtime error, >0 = numerical failure
  *     (e.g. index+1 of a non-positive Cholesky pivot).  gpemu_last_error() gives the thread-local
  *     message of the last failure.
@@ -1214,6 +1217,89 @@ enum gpemu_reweight_path {
 };
 /* out[0 .. min(n, GPEMU_REWEIGHT_PATH_COUNT)) = the counters; returns GPEMU_REWEIGHT_PATH_COUNT (or GPEMU_ERR_ARG). */
 int gpemu_reweight_path_counts(int64_t *out, int64_t n);
+
+/* ---- weighted bands, highest-density intervals and densities of a reweighted chain ---------------------
+ * What a user takes from a chain next, under the fixed-point weights q[R_w][S] (uint64, Q_w = sum_s q_ws < 2^53) of
+ * gpemu_weights_fixed_dev: a double holds every q and every partial sum of q exactly.  Integer sums use integer
+ * atomics; every floating-point sum runs in a tree fixed by the logical sample index: no bit depends on the order of an
+ * atomic, on the grid, on the workspace or on the run.  1 <= R_w <= 64 and 1 <= S < 2^31 everywhere below, every target
+ * in [1, 2^53]; an argument error returns GPEMU_ERR_ARG before any launch or allocation.
+ *
+ * The _dev forms take, instead of a stream and a workspace limit of their own, */
+typedef struct { void *stream; int64_t workspace_bytes; } gpemu_call_ctx;
+/* ctx == NULL means stream NULL and workspace_bytes 0 (sized from the free device memory).  gpemu_weighted_hpd_dev and
+ * gpemu_weighted_kde1d_dev work on ctx->stream (NULL = the null stream) and each waits for it before returning;
+ * gpemu_posterior_predictive_weighted_dev works on ctx->stream (NULL = the model's) and waits for it before returning.
+ *
+ * gpemu_posterior_predictive_weighted: gpemu_posterior_predictive's reduction under every weight row w, with mu_f and
+ * sigma^2_f as defined there:
+ *   mean[w*F + f]      = sum_s q_ws mu_fs / Q_w
+ *   var_param[w*F + f] = sum_s q_ws (mu_fs - mean[w][f])^2 / Q_w                                   (two passes)
+ *   var_emu[w*F + f]   = (sum_p comp[p][f] vbar_wp comp[p][f] + cov_unexplained[f][f]) scale_f^2,
+ *                        vbar_wp = sum_s q_ws var_p(theta_s) / Q_w
+ *   quantiles[(w*F + f)*n_targets + i] = gpemu_weighted_select's answer to targets[w*n_targets + i] on feature f's row
+ * each NULL where not wanted (n_targets = 0: no quantiles).  The predict stages, the projection, the workspace rule and
+ * the whole / feature-blocked paths are gpemu_posterior_predictive's.  The weighted row reduction reads, per workgroup,
+ * 4 rows of central values and 4 weight rows once for their 16 sums over a chunk of 4096 samples: a lane adds its 16
+ * terms fma((double)q, x, .) in index order (a term of weight 0 is left out), then the wave butterfly, the waves in
+ * order, the chunks in order, and the sum is divided by (double)Q_w.  With q_s = 2^e the mean and var_emu are
+ * gpemu_posterior_predictive's bits.  Q_w = 0 gives NaN.  targets[] is a HOST array; the host form takes X[S*d] and
+ * q[R_w*S]; _dev reads the rows in the block layout of gpemu_posterior_predictive_dev in place, dq[R_w][ldq], and
+ * writes device arrays.
+ *
+ * gpemu_weighted_hpd: for value row v, weight row w and target mass t = targets[w*n_levels + l], over every sample value
+ * a of the row, with b(a) the smallest sample value >= a with sum_{a <= x_s <= b} q_ws >= t, the (a, b(a)) of the
+ * smallest double-rounded width b - a, equal widths to the smaller a:
+ *   out[((w*R_v + v)*n_levels + l)*2 + {0, 1}] = a, b
+ * both elements of the input (a zero comes back as +0).  NaN where t exceeds Q_w, where the row holds a NaN, and where
+ * its smallest or largest element is infinite, as in gpemu_hpd.  Under equal weights q_s = c and t = c (S - n_out + 1)
+ * it returns gpemu_hpd's two ends for n_out.  Per batch of value rows: gpemu_hpd's key sort once, then per weight row the
+ * weights placed by value (a binary search for the first sorted position of the sample's key, a 64-bit integer atomic
+ * there), an inclusive 64-bit prefix sum in three launches (chunk sums, their scan, apply), and the window search: every
+ * run start i finds the first j with C[j] - C[i-1] >= t by bisection, and (width, i) is reduced lexicographically as in
+ * gpemu_hpd.  A (w, v) pair of a batch holds 24*S + 1032*ceil(S/2048) + 16*n_levels*ceil(S/4096) + 4 bytes of workspace
+ * (sorted keys twice, digit histograms, cumulative weights, chunk sums, window minima); the pairs of a weight row go
+ * through it in batches that fit workspace_bytes (0 = half of the free device memory); not one pair: GPEMU_ERR_HIP with
+ * the sizes in the error text.  1 <= n_levels <= 4096.  _dev addresses the values as gpemu_select_dev does.
+ *
+ * gpemu_weighted_kde1d: dens[(w*R_v + v)*G + g] = 1 / (Q_w h sqrt(2 pi)) sum_s q_ws exp(-(grid - x_vs)^2 / (2 h^2)) with
+ * the HOST arrays grid[R_w*R_v*G] and h[R_w*R_v], one grid and bandwidth per (w, v) pair.  gpemu_kde1d's tiling and
+ * order of summation with fma((double)q, exp(.), .) where it adds exp(.): with q_s = 2^e its bits.  A sample with q = 0
+ * contributes nothing.  Q_w = 0 gives NaN; a non-finite or non-positive h and a non-finite grid point: GPEMU_ERR_ARG.
+ * The pairs go in batches of about 256 MiB of chunk sums, as gpemu_kde1d's rows do. */
+int gpemu_posterior_predictive_weighted(gpemu_model *m, int64_t S, const double *X, int64_t R_w, const uint64_t *q,
+                                        int64_t n_targets, const uint64_t *targets, int64_t workspace_bytes,
+                                        double *mean, double *var_param, double *var_emu, double *quantiles);
+int gpemu_posterior_predictive_weighted_dev(gpemu_model *m, const double *dX, int64_t n_blocks, int64_t block_rows,
+                                            int64_t block_stride_rows, int64_t R_w, const uint64_t *dq, int64_t ldq,
+                                            int64_t n_targets, const uint64_t *targets, double *dmean,
+                                            double *dvar_param, double *dvar_emu, double *dquantiles,
+                                            const gpemu_call_ctx *ctx);
+int gpemu_weighted_hpd(int device, int64_t R_v, int64_t S, const double *V, int64_t R_w, const uint64_t *q,
+                       int64_t n_levels, const uint64_t *targets, double *out);
+int gpemu_weighted_hpd_dev(int device, int64_t R_v, int64_t S, const double *dV, int64_t row_stride, int64_t elem_stride,
+                           int64_t R_w, const uint64_t *dq, int64_t ldq, int64_t n_levels, const uint64_t *targets,
+                           double *dout, const gpemu_call_ctx *ctx);
+int gpemu_weighted_kde1d(int device, int64_t R_v, int64_t S, const double *V, int64_t R_w, const uint64_t *q, int64_t G,
+                         const double *grid, const double *h, double *dens);
+int gpemu_weighted_kde1d_dev(int device, int64_t R_v, int64_t S, const double *dV, int64_t row_stride,
+                             int64_t elem_stride, int64_t R_w, const uint64_t *dq, int64_t ldq, int64_t G,
+                             const double *grid, const double *h, double *ddens, const gpemu_call_ctx *ctx);
+/* Which launches of these ran.  A set of its own: the other sets keep their sizes and indices. */
+enum gpemu_wsummary_path {
+  GPEMU_WSUMMARY_PATH_BANDS_WHOLE = 0,        /* a weighted reduction whose features all fit the workspace at once    */
+  GPEMU_WSUMMARY_PATH_BANDS_FEATURE_BLOCKED,  /* ... that went through the workspace in blocks of features            */
+  GPEMU_WSUMMARY_PATH_ROW_REDUCE,             /* one launch of the weighted row reduction                             */
+  GPEMU_WSUMMARY_PATH_SELECT_PASS,            /* one histogram + scan pass of the weighted select on the workspace    */
+  GPEMU_WSUMMARY_PATH_HPD_SORT_BATCH,         /* the key sort of one batch of value rows                              */
+  GPEMU_WSUMMARY_PATH_HPD_PLACE,              /* one launch that places a weight row's weights by value               */
+  GPEMU_WSUMMARY_PATH_HPD_SCAN,               /* one prefix sum of the placed weights (three launches)                */
+  GPEMU_WSUMMARY_PATH_HPD_WINDOW,             /* one window search with its finish                                    */
+  GPEMU_WSUMMARY_PATH_KDE,                    /* one batch of pairs of the weighted density (partial sums + their sum) */
+  GPEMU_WSUMMARY_PATH_COUNT
+};
+/* out[0 .. min(n, GPEMU_WSUMMARY_PATH_COUNT)) = the counters; returns GPEMU_WSUMMARY_PATH_COUNT (or GPEMU_ERR_ARG). */
+int gpemu_wsummary_path_counts(int64_t *out, int64_t n);
 
 /* ---- fit handle: test-only entry points ---------------------------------------------------------------------------
  * For the tests of the fit side only; nothing in the library's own flow calls them.
