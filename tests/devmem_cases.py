@@ -222,14 +222,32 @@ def _weighted_hist():
     return R.flatten(RW.weighted_histograms(_x(), LO1, HI1, _q(), 8, 4))
 
 
+def _q2():
+    """two weight rows: the loops over the weight rows of the weighted intervals and densities run twice"""
+    return _g("q2").integers(2 ** 39, 2 ** 40, (2, S1)).astype(np.uint64)
+
+
+def _weighted_hpd():
+    from gpemu import reweight as RW
+    return (RW.weighted_hpd(_x(), (0.5, 0.9), _q2()),)
+
+
+def _weighted_kde1d():
+    from gpemu import reweight as RW
+    return R.flatten(RW.weighted_kde_1d(_x(), _q2(), n_grid=16))
+
+
+# Every host one-shot of include/gpemu.h -- first parameter `int device`, no stream, no ctx -- has an entry here under its
+# name: tests/test_devmem_tables_host.py holds the table to the header.
 HOST_ONE_SHOTS = {
     "gpemu_pca_fit": _pca_fit, "gpemu_truncation_cov": _truncation_cov, "gpemu_kernel_matrix": _kernel_matrix,
     "gpemu_cholesky": _cholesky, "gpemu_select": _select, "gpemu_rank": _rank, "gpemu_hpd": _hpd, "gpemu_kde1d": _kde1d,
     "gpemu_kde2d": _kde2d, "gpemu_marginal_hist": _marginal_hist, "gpemu_psis": _psis, "gpemu_knn_dist": _knn_dist,
     "gpemu_pair_lse": _pair_lse, "gpemu_logprior": _logprior, "gpemu_weighted_select": _weighted_select,
-    "gpemu_weighted_hist": _weighted_hist,
+    "gpemu_weighted_hist": _weighted_hist, "gpemu_weighted_hpd": _weighted_hpd, "gpemu_weighted_kde1d": _weighted_kde1d,
 }
-WALK_ONE_SHOTS = ("gpemu_pca_fit", "gpemu_kde2d")      # (gp_predict_cov, the third, is an operation of reuse_cases)
+# (gp_predict_cov, the fourth, is an operation of reuse_cases)
+WALK_ONE_SHOTS = ("gpemu_pca_fit", "gpemu_kde2d", "gpemu_weighted_hpd")
 
 DEVICE_WIDE_ROWS = [r for r in SC.ROWS if r.family == SC.DEVICE_WIDE and not r.omitted]
 
@@ -305,6 +323,11 @@ def _chain0(ds):
     return {"chain": 0} if ds.n_chains > 1 else {}
 
 
+def _normal_prior(P):
+    """one scenario: a normal prior on the first parameter, centred in the box, a quarter of its width wide"""
+    return [{0: ("normal", float(P.lo[0] + P.hi[0]) / 2, float(P.hi[0] - P.lo[0]) / 4)}]
+
+
 CHAIN_METHODS = {
     "posterior_predictive": lambda ds, P: ds.posterior_predictive(**_chain0(ds)),
     "parameter_quantiles": lambda ds, P: ds.parameter_quantiles([0.05, 0.5, 0.95], **_chain0(ds)),
@@ -312,10 +335,11 @@ CHAIN_METHODS = {
     "marginals": lambda ds, P: ds.marginals(bins_1d=8, bins_2d=4, n_grid=16, kde2d=True, n_grid_2d=16),
     "marginals_thinned": lambda ds, P: ds.marginals(bins_1d=8, bins_2d=4, n_grid=16, thin=2),
     "loo": lambda ds, P: ds.loo(),
-    "reweight": lambda ds, P: ds.reweight(priors=[{0: ("normal", float(P.lo[0] + P.hi[0]) / 2, float(P.hi[0] - P.lo[0]) / 4)}],
-                                          bins_1d=8, bins_2d=4),
-    "reweight_thinned": lambda ds, P: ds.reweight(priors=[{0: ("normal", float(P.lo[0] + P.hi[0]) / 2,
-                                                                float(P.hi[0] - P.lo[0]) / 4)}], bins_1d=8, bins_2d=4, thin=2),
+    "reweight": lambda ds, P: ds.reweight(priors=_normal_prior(P), bins_1d=8, bins_2d=4),
+    "reweight_thinned": lambda ds, P: ds.reweight(priors=_normal_prior(P), bins_1d=8, bins_2d=4, thin=2),
+    # the weighted intervals, densities and bands of DESIGN.md §4.43 on the scenario's weights
+    "reweight_summaries": lambda ds, P: ds.reweight(priors=_normal_prior(P), bins_1d=8, bins_2d=4, hpd=(0.9,), kde=True,
+                                                    n_grid=16, posterior_predictive=True),
     "information_gain": lambda ds, P: ds.information_gain(allow_copies=True),
     "kl_divergence": lambda ds, P: ds.kl_divergence(R.rows(P, "devmem_kl", 200), allow_copies=True),
     "expected_information_gain": lambda ds, P: ds.expected_information_gain(_candidates(P), n_inner=256, n_outer=64),
@@ -376,6 +400,11 @@ WARM_MODEL_DEV = {
     # k_postpred.hip: Mpc, Vpc, the staging rows of a view that is not dense, part, vbar, mu, W (7), and the 10 of the
     # select it runs (gpemu_select_dev, a device-wide row of its own)
     "gpemu_posterior_predictive_dev": 17,
+    # k_postpred.hip pp_reduce under weights: Mpc, Vpc, the staging rows of a view that is not dense, part, vbar, mu, the
+    # weight totals dQ, W (8); the weighted select runs once per weight row on the rows of W, each time with the 10 of
+    # k_select.hip select_rows (prefix, trem, slotpre, slot, over, nslot, nan, hist, the targets, their permutation):
+    # 8 + 2 * 10 for the row's two weight rows.  (weight_totals and weighted_rowmean of k_wsummary.hip allocate nothing.)
+    "gpemu_posterior_predictive_weighted_dev": 28,
     # k_sobol.hip gpemu_sobol_moments_dev: Z, part, dpivot, dout, dstart, dfirst
     "gpemu_sobol_moments_dev": 6,
     # k_loo.hip gpemu_loglik_pointwise_dev: Mpc, Vpc and the staging rows of a view that is not dense
@@ -400,6 +429,9 @@ WARM_HOST = dict(
     logpost_grad=3,                   # rows, lp, gradient
     loglik_pointwise=4,               # rows, terms; the device entry's Mpc, Vpc
     posterior_predictive=21,          # rows and the four results; the device entry's 6 (a dense view) + the select's 10
+    # rows, weights and the four results (6); the device entry's 7 (a dense view: no staging rows) + the weighted
+    # select's 10 for each of the two weight rows
+    posterior_predictive_weighted=33,
     mean_pick_freeze=3,               # A, B, Z
     sobol_moments=8,                  # A, B; the device entry's 6
     cross_validate=14,                # folds, offsets, y, mean, var, the two observable-space results; cross_validate's 7

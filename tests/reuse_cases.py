@@ -42,7 +42,7 @@ CASES = {
     "chains": dataclasses.replace(_GENERAL, name="chains"),
 }
 CASE_IDS = list(CASES)
-MIN_COMPARED = 15                                    # operations of every case that must really compare
+MIN_COMPARED = 16                                  # operations of every case that must really compare
 
 
 @dataclass
@@ -234,6 +234,19 @@ def _posterior_predictive(dm, P):
     return flatten(dm.posterior_predictive(rows(P, "postpred", 300)))
 
 
+def postpred_weights(P, S, R_w=2):
+    """R_w rows of integer weights in [2^39, 2^40): a row of S <= 512 of them adds up to less than 2^49, far below the
+    2^53 that include/gpemu.h asks of a row's total"""
+    return _rng(P, "postpred_w_q").integers(2 ** 39, 2 ** 40, (R_w, S)).astype(np.uint64)
+
+
+def _posterior_predictive_weighted(dm, P):
+    """The weighted bands under two weight rows, one dict per row (total_weight among its arrays).  The problems here have
+    6 and 8 features, which always fit the workspace at once: only the whole-features path runs.  The feature-blocked one
+    stays with the 40-feature model of tests/test_gpu_wsummary.py."""
+    return flatten(dm.posterior_predictive_weighted(rows(P, "postpred_w", 300), postpred_weights(P, 300)))
+
+
 def _mean_pick_freeze(dm, P):
     return (dm.mean_pick_freeze(rows(P, "sobolA", 64), rows(P, "sobolB", 64)),)
 
@@ -405,6 +418,7 @@ OPS = [Op(f"logpost_{B}", _logpost(B)) for B in LOGPOST_B] + [
     Op("logpost_grad", _logpost_grad),
     Op("loglik_pointwise", _loglik_pointwise),
     Op("posterior_predictive", _posterior_predictive),
+    Op("posterior_predictive_weighted", _posterior_predictive_weighted),
     Op("mean_pick_freeze", _mean_pick_freeze),
     Op("sobol_moments", _sobol_moments),
     Op("cross_validate", _cross_validate),

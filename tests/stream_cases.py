@@ -1,5 +1,6 @@
-"""Streams (tests only): the table of every entry point of include/gpemu.h that takes a ``void *stream``, and the gate
-that makes a launch on the wrong stream show, whatever the timing (tests/test_gpu_streams.py, tests/test_streams_host.py).
+"""Streams (tests only): the table of every entry point of include/gpemu.h that takes a ``void *stream`` or carries one
+in a ``const gpemu_call_ctx *``, and the gate that makes a launch on the wrong stream show, whatever the timing
+(tests/test_gpu_streams.py, tests/test_streams_host.py).
 
 A row names the entry, its family, the header's own words on what NULL means for it and on whether it waits, and a
 closure ``run(st, T, out, P, dm) -> tuple`` that calls it at a small fixed shape: ``st`` the ``void *`` to pass, ``T``
@@ -25,6 +26,8 @@ GATE_MS, 70 ms, is ten times that, and no more than 200 ms.
 from __future__ import annotations
 
 import ctypes as C
+import os
+import re
 import time
 from dataclasses import dataclass
 
@@ -52,6 +55,34 @@ NULL_NONE = "NULL: none"
 NULL_FIRST_GROUP = "NULL = the first group's stream"
 NOWAIT = "do not synchronise"
 WAITS = "waits for it"
+
+
+# ---- include/gpemu.h as the CPU gates read it (tests/test_streams_host.py, tests/test_devmem_tables_host.py) -------------
+HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "gpemu.h")
+STREAM_PARAM = r"\bvoid\s*\*\s*stream\b"
+CTX_PARAM = r"\bconst\s+gpemu_call_ctx\s*\*"
+
+
+def header_text():
+    with open(HEADER) as f:
+        return f.read()
+
+
+def all_prototypes(text):
+    """{name: (offset, parameter list)} of every function prototype of the header"""
+    code = re.sub(r"/\*.*?\*/", lambda m: " " * len(m.group(0)), text, flags=re.S)      # comments blanked, offsets kept
+    return {m.group(1): (m.start(), m.group(2))
+            for m in re.finditer(r"\b(?:int|void|int64_t)\s+(gpemu_\w+)\s*\(([^;{]*?)\)\s*;", code)}
+
+
+def prototypes_with(text, pattern):
+    """{name: offset} of the prototypes whose parameter list matches `pattern`"""
+    return {name: at for name, (at, params) in all_prototypes(text).items() if re.search(pattern, params)}
+
+
+def stream_prototypes(text):
+    """{name: offset} of every function prototype with a ``void *stream`` or a ``const gpemu_call_ctx *`` parameter"""
+    return prototypes_with(text, f"{STREAM_PARAM}|{CTX_PARAM}")
 
 
 @dataclass
@@ -324,6 +355,52 @@ def _weighted_hist(st, T, out, P, dm):
     return h1, h2, wi
 
 
+# the weighted chain summaries take their stream in a ``gpemu_call_ctx``; a run is built from a
+# ``ctx_of(st)`` that gives the ctx to pass by reference, or None for ``ctx == NULL`` (tests/test_gpu_wsummary_streams.py)
+RW2 = 2                                   # weight rows: the per-weight-row loops run twice
+
+
+def ctx_on(st):
+    from gpemu import _lib
+    return _lib.CallCtx(int(st) or None, 0)
+
+
+def _ctx_ref(ctx_of, st):
+    ctx = ctx_of(st)
+    return ctx, (None if ctx is None else C.byref(ctx))        # (the ctx is kept alive over the call)
+
+
+def _in_Vq2(P, seed):
+    """3 value rows and 2 rows of fixed-point weights in [2^39, 2^40): a row's total lies in [2^47, 2^48)"""
+    q = _rng(seed, "wq").integers(2 ** 39, 2 ** 40, (RW2, S_WIDE)).astype(np.int64)
+    return {"V": np.ascontiguousarray(_unit_rows(seed, "wV").T), "q": q}
+
+
+_W_TARGETS = np.ascontiguousarray(np.tile(np.array([1, 2 ** 45, 2 ** 47], dtype=np.uint64), (RW2, 1)))
+_W_GRID = np.ascontiguousarray(np.tile(np.linspace(0.0, 1.1, 9), (RW2 * 3, 1)))
+_W_H = np.full(RW2 * 3, 0.05)
+
+
+def weighted_hpd_run(ctx_of):
+    def run(st, T, out, P, dm):
+        o = out((RW2, 3, 3, 2))
+        ctx, ref = _ctx_ref(ctx_of, st)
+        _ck(_L().gpemu_weighted_hpd_dev(0, 3, S_WIDE, _vp(T["V"]), S_WIDE, 1, RW2, _vp(T["q"]), S_WIDE, 3, _vp(_W_TARGETS),
+                                        _vp(o), ref))
+        return (o,)
+    return run
+
+
+def weighted_kde_run(ctx_of):
+    def run(st, T, out, P, dm):
+        o = out((RW2, 3, 9))
+        ctx, ref = _ctx_ref(ctx_of, st)
+        _ck(_L().gpemu_weighted_kde1d_dev(0, 3, S_WIDE, _vp(T["V"]), S_WIDE, 1, RW2, _vp(T["q"]), S_WIDE, 9, _vp(_W_GRID),
+                                          _vp(_W_H), _vp(o), ref))
+        return (o,)
+    return run
+
+
 def _in_chain(P, seed):
     nb, br, _ = VIEW
     return {"chain": _unit_rows(seed, "chain", nb * br).reshape(nb, br, D_WIDE)}
@@ -430,6 +507,27 @@ def _postpred(st, T, out, P, dm):
     return tuple(o)
 
 
+def in_weighted_view(P, seed):
+    """the rows of a chain view and 2 rows of fixed-point weights, one weight per row of the view"""
+    nb, br, bs = VIEW
+    q = _rng(seed, "wq_view").integers(2 ** 39, 2 ** 40, (RW2, nb * br)).astype(np.int64)
+    return dict(_in_model_view(P, seed), q=q)
+
+
+_W_VIEW_TARGETS = np.ascontiguousarray(np.tile(np.array([1, 2 ** 44, 2 ** 45], dtype=np.uint64), (RW2, 1)))
+
+
+def weighted_bands_run(ctx_of):
+    def run(st, T, out, P, dm):
+        nb, br, bs = VIEW
+        o = [out((RW2, P.F)), out((RW2, P.F)), out((RW2, P.F)), out((RW2, P.F, 3))]
+        ctx, ref = _ctx_ref(ctx_of, st)
+        _ck(_L().gpemu_posterior_predictive_weighted_dev(dm.handle, _vp(T["X"]), nb, br, bs, RW2, _vp(T["q"]), nb * br, 3,
+                                                         _vp(_W_VIEW_TARGETS), *[_vp(a) for a in o], ref))
+        return tuple(o)
+    return run
+
+
 def _in_AB(P, seed):
     return {"A": R.rows(P, "stream_A" + _tag(seed), B_SMALL), "B": R.rows(P, "stream_B" + _tag(seed), B_SMALL)}
 
@@ -502,6 +600,11 @@ _M_NOWAIT = dict(family=MODEL_BOUND, null_means=NULL_MODEL, waits=False,
 _M_WAIT = dict(family=MODEL_BOUND, null_means=NULL_MODEL, waits=True,
                doc=(("(NULL = the model's) and waits for it", "section"),))
 _WIDE = dict(family=DEVICE_WIDE, null_means=NULL_NULL, waits=True, doc=((NULL_NULL, "section"), (WAITS, "section")))
+# the entries whose stream is ctx->stream: their section names them one by one
+_CTX_WIDE = dict(family=DEVICE_WIDE, null_means=NULL_NULL, waits=True,
+                 doc=(("work on ctx->stream (NULL = the null stream) and each waits for it before returning", "section"),))
+_CTX_MODEL = dict(family=MODEL_BOUND, null_means=NULL_MODEL, waits=True,
+                  doc=(("works on ctx->stream (NULL = the model's) and waits for it before returning", "section"),))
 
 ROWS = [
     Row("gpemu_gp_predict_dev", inputs=_in_rows(B_BIG, "stream_gp"), run=_gp_predict, cases=ALL4, **_M_NOWAIT),
@@ -550,6 +653,10 @@ ROWS = [
     Row("gpemu_weights_fixed_dev", inputs=_in_lw, run=_weights_fixed, **_WIDE),
     Row("gpemu_weighted_select_dev", inputs=_in_Vq, run=_weighted_select, **_WIDE),
     Row("gpemu_weighted_hist_dev", inputs=_in_Vq, run=_weighted_hist, **_WIDE),
+    Row("gpemu_posterior_predictive_weighted_dev", inputs=in_weighted_view, run=weighted_bands_run(ctx_on),
+        cases=("general", "wide"), **_CTX_MODEL),
+    Row("gpemu_weighted_hpd_dev", inputs=_in_Vq2, run=weighted_hpd_run(ctx_on), **_CTX_WIDE),
+    Row("gpemu_weighted_kde1d_dev", inputs=_in_Vq2, run=weighted_kde_run(ctx_on), **_CTX_WIDE),
 ]
 ROW = {r.name: r for r in ROWS}
 

@@ -276,7 +276,8 @@ def test_a_documented_decline_allocates_nothing(pair):
 # the feature tests that list the library's argument refusals, and how many declined calls each makes at least
 BORROWED = [("test_gpu_design", "test_abi_argument_checks", 16), ("test_gpu_predict_cov", "test_abi_argument_checks", 4),
             ("test_gpu_cross_validation", "test_bad_folds_refused", 4), ("test_gpu_srccorr", "test_documented_errors", 5),
-            ("test_gpu_logpost_grad", "test_refusals", 10)]
+            ("test_gpu_logpost_grad", "test_refusals", 10),
+            ("test_gpu_wsummary", "test_refusals_return_err_arg_and_leave_the_ledger_alone", 12)]
 
 
 @pytest.mark.parametrize("module,test,at_least", BORROWED, ids=[f"{m}-{t}" for m, t, _ in BORROWED])

@@ -1,8 +1,9 @@
-"""Every entry point that takes a ``void *stream`` must work on the stream it is given (tests/stream_cases.py: the table
-and the gate).  The rest of the suite only ever passes torch's default stream, whose handle is NULL: the device-wide
-entries then run on the null stream, which serialises with almost everything, and the model-bound ones fall back to
-the model's own stream, with a synchronisation around every call -- a launch on the wrong stream, an input read before
-the stream has reached it or a wait for the wrong stream cannot show there.
+"""Every entry point that takes a ``void *stream``, or a ``gpemu_call_ctx`` that holds one, must work on the stream it
+is given (tests/stream_cases.py: the table and the gate).  The rest of the suite only ever passes torch's default
+stream, whose handle is NULL: the device-wide entries then run on the null stream, which serialises with almost
+everything, and the model-bound ones fall back to the model's own stream, with a synchronisation around every call -- a
+launch on the wrong stream, an input read before the stream has reached it or a wait for the wrong stream cannot show
+there.
 
 One-sided: a launch that goes to another stream than the one it was given is caught because that stream is not held
 up by the gate.  On a device whose streams share a few hardware queues (4 here), a wrong stream that happens to share

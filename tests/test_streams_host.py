@@ -1,6 +1,7 @@
-"""The table of tests/stream_cases.py against include/gpemu.h: it names every prototype that takes a ``void *stream``, and
-what it says about NULL and about waiting stands in the header's own comments -- so a new ``_dev`` entry cannot be added
-without a row, which tests/test_gpu_streams.py then runs on a stream of its own.
+"""The table of tests/stream_cases.py against include/gpemu.h: it names every prototype that takes a ``void *stream`` or
+carries its stream in a ``const gpemu_call_ctx *``, and what it says about NULL and about waiting stands in the header's
+own comments -- so a new ``_dev`` entry cannot be added without a row, which tests/test_gpu_streams.py then runs on a
+stream of its own.  A prototype named ``*_dev`` that shows neither spelling must be exempted here by name, with a reason.
 
 Limitation: a row's quotes are looked for in the whole section of its prototype (from the last ``/* ----`` banner), because
 most families state their contract once ("Every _dev form works on `stream` ...").  A new entry added to an existing
@@ -8,31 +9,18 @@ section therefore finds its neighbours' sentences there; what holds it to them i
 gate, not this file."""
 from __future__ import annotations
 
-import os
 import re
 
 import pytest
 
 import stream_cases as SC
 
-HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "gpemu.h")
-
-
-def _text():
-    with open(HEADER) as f:
-        return f.read()
+_text, _prototypes = SC.header_text, SC.stream_prototypes       # (the header's parser lives beside the table)
 
 
 def _squash(s):
     """comment leaders and line breaks out: the words alone"""
     return re.sub(r"\s+", " ", re.sub(r"(?m)^\s*\*\s?", " ", s.replace("/*", " ").replace("*/", " ")))
-
-
-def _prototypes(text):
-    """{name: offset} of every function prototype with a ``void *stream`` parameter"""
-    code = re.sub(r"/\*.*?\*/", lambda m: " " * len(m.group(0)), text, flags=re.S)      # comments blanked, offsets kept
-    return {m.group(1): m.start() for m in re.finditer(r"\b(?:int|void|int64_t)\s+(gpemu_\w+)\s*\(([^;{]*?)\)\s*;", code)
-            if re.search(r"\bvoid\s*\*\s*stream\b", m.group(2))}
 
 
 def _section(text, offset):
@@ -45,13 +33,35 @@ def _conventions(text):
     return text[:text.index("#ifndef GPEMU_H")]
 
 
+WEIGHTED_DEV = ("gpemu_posterior_predictive_weighted_dev", "gpemu_weighted_hpd_dev", "gpemu_weighted_kde1d_dev")
+# a prototype named *_dev that takes neither a stream nor a ctx: {name: why it needs no row}
+DEV_WITHOUT_A_STREAM = {}
+
+
 def test_the_table_names_every_prototype_with_a_stream():
-    protos = _prototypes(_text())
-    assert len(protos) == 35 and "gpemu_logpost_dev" in protos and "gpemu_sampler_set_stream" in protos, sorted(protos)
+    text = _text()
+    protos = _prototypes(text)
+    by_stream, by_ctx = SC.prototypes_with(text, SC.STREAM_PARAM), SC.prototypes_with(text, SC.CTX_PARAM)
+    assert len(by_stream) == 35 and len(by_ctx) == 3 and not set(by_stream) & set(by_ctx), (sorted(by_stream), sorted(by_ctx))
+    assert len(protos) == 38 and "gpemu_logpost_dev" in protos and "gpemu_sampler_set_stream" in protos, sorted(protos)
+    assert set(WEIGHTED_DEV) <= set(by_ctx), f"not found by their ctx: {sorted(set(WEIGHTED_DEV) - set(by_ctx))}"
     names = [r.name for r in SC.ROWS]
     assert len(set(names)) == len(names), "a row twice"
     assert set(names) == set(protos), (f"without a row: {sorted(set(protos) - set(names))}; "
                                        f"rows without a prototype: {sorted(set(names) - set(protos))}")
+
+
+def test_every_dev_prototype_is_found_or_exempted_by_name():
+    """a ``_dev`` entry whose stream is spelled a third way would slip past the table: it must be found by one of the two
+    spellings, or stand in DEV_WITHOUT_A_STREAM with the reason"""
+    text = _text()
+    dev = {n for n in SC.all_prototypes(text) if n.endswith("_dev")}
+    assert len(dev) == 36, sorted(dev)             # the 38 less gpemu_sampler_set_stream and gpemu_comm_all_gather
+    unseen = dev - set(_prototypes(text))
+    assert unseen == set(DEV_WITHOUT_A_STREAM), (
+        f"*_dev prototypes with neither a `void *stream` nor a `const gpemu_call_ctx *`, and no exemption: "
+        f"{sorted(unseen - set(DEV_WITHOUT_A_STREAM))}; exempted but found or gone: {sorted(set(DEV_WITHOUT_A_STREAM) - unseen)}")
+    assert all(isinstance(why, str) and why.strip() for why in DEV_WITHOUT_A_STREAM.values())
 
 
 def test_only_the_all_gather_is_left_out_of_the_sweep():
