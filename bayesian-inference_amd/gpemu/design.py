@@ -23,6 +23,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import check, ptr
+from .rows import DeviceRows          # reference rows that already lie in device memory (a stored chain in place)
 
 MAX_PICKS = 256
 MAX_ROWS = 4194240
@@ -58,17 +59,6 @@ def pc_weights(model_or_arrays, feature_weights=None):
     return ((comp * scale[None, :]) ** 2) @ fw
 
 
-class DeviceRows:
-    """Reference rows that already lie in device memory, as blocks of rows (a stored chain in place): row r is at
-    ``address + 8 d ((r // block_rows) block_stride_rows + r % block_rows)``.  ``stream``: the ``void *`` the rows were
-    written on (waited for before they are read), or None."""
-
-    def __init__(self, address, n_blocks, block_rows, block_stride_rows, stream=None):
-        self.address, self.n_blocks, self.block_rows = int(address), int(n_blocks), int(block_rows)
-        self.block_stride_rows, self.stream = int(block_stride_rows), stream
-        self.rows = self.n_blocks * self.block_rows
-
-
 def _rows(what, X, d):
     X = np.ascontiguousarray(np.array(X, ndmin=2, dtype=np.float64))
     if X.ndim != 2 or X.shape[1] != d:
@@ -100,10 +90,10 @@ class _GroupDesign:
             import torch
             dc = torch.from_numpy(candidates).to(torch.device("cuda", model.device))
             torch.cuda.current_stream(dc.device).synchronize()
-            check(L.gpemu_design_create_dev(C.byref(h), model.handle, C.c_void_p(reference.address), reference.n_blocks,
-                                            reference.block_rows, reference.block_stride_rows, ptr(weights), self.M,
-                                            C.c_void_p(dc.data_ptr()), ptr(pcw), ptr(tau), float(min_variance),
-                                            int(max_picks), int(workspace_bytes), reference.stream))
+            check(L.gpemu_design_create_dev(C.byref(h), model.handle, C.c_void_p(reference.address),
+                                            *reference.layout[1:], ptr(weights), self.M, C.c_void_p(dc.data_ptr()), ptr(pcw),
+                                            ptr(tau), float(min_variance), int(max_picks), int(workspace_bytes),
+                                            reference.stream))
             del dc      # the handle holds its own copy
         else:
             check(L.gpemu_design_create(C.byref(h), model.handle, reference.shape[0], ptr(reference), ptr(weights), self.M,
@@ -162,9 +152,8 @@ class Design:
         if d > 16 or any(m.k > 64 for m in models):
             raise ValueError("at most 16 parameters and 64 PCs per group")
         if isinstance(reference, DeviceRows):
-            if not (reference.n_blocks >= 1 and reference.block_rows >= 1 and reference.rows <= MAX_ROWS and
-                    (reference.n_blocks == 1 or reference.block_stride_rows >= reference.block_rows)):
-                raise ValueError("reference: bad block layout")
+            if reference.rows > MAX_ROWS:          # (the layout itself is DeviceRows' check)
+                raise ValueError(f"reference: between 1 and {MAX_ROWS} rows, got {reference.rows}")
             S = reference.rows
         else:
             reference = _rows("reference", reference, d)

@@ -28,6 +28,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import check, ptr
+from .rows import DeviceRows
 
 PATHS = ("UNIT_ROWS", "SEARCH", "MERGE", "SUBSET_BATCH", "LOGSUM")
 MAX_D = 16
@@ -327,11 +328,9 @@ def information_gain(x, lower, upper, k=4, subsets=None, max_points=65536, allow
     exceed 0.1 of the rows unless ``allow_copies``: thin the chain by its autocorrelation time."""
     X, on_device = _rows(x)
     if on_device:
-        dev = X.device.index or 0
-        U, skipped = unit_rows_dev(dev, X.data_ptr(), 1, int(X.shape[0]), int(X.shape[0]), int(X.shape[1]), lower, upper,
-                                   max_points)
-    else:
-        U, skipped = unit_rows(X, lower, upper, max_points)
+        return gain_of_view(DeviceRows.of_tensor(X), lower, upper, k, subsets, max_points, allow_copies, splits,
+                            workspace_bytes)
+    U, skipped = unit_rows(X, lower, upper, max_points)
     return _gain(U, skipped, k, subsets, allow_copies, splits, device, workspace_bytes)
 
 
@@ -370,34 +369,31 @@ def kl_divergence(x, y, lower=None, upper=None, k=4, subsets=None, max_points=65
     if X.shape[1] != Y.shape[1]:
         raise ValueError(f"x has {X.shape[1]} columns, y {Y.shape[1]}")
     if x_dev:
-        dev, d = X.device.index or 0, int(X.shape[1])
-        Ux, sx = unit_rows_dev(dev, X.data_ptr(), 1, int(X.shape[0]), int(X.shape[0]), d, lower, upper, max_points)
-        Uy, sy = unit_rows_dev(dev, Y.data_ptr(), 1, int(Y.shape[0]), int(Y.shape[0]), d, lower, upper, max_points)
-    else:
-        Ux, sx = unit_rows(X, lower, upper, max_points)
-        Uy, sy = unit_rows(Y, lower, upper, max_points)
+        return divergence_of_views(DeviceRows.of_tensor(X), DeviceRows.of_tensor(Y), lower, upper, k, subsets, max_points,
+                                   allow_copies, splits, workspace_bytes)
+    Ux, sx = unit_rows(X, lower, upper, max_points)
+    Uy, sy = unit_rows(Y, lower, upper, max_points)
     return _divergence(Ux, sx, Uy, sy, k, subsets, allow_copies, splits, device, workspace_bytes)
 
 
-def gain_of_view(device, view, d, lower, upper, k=4, subsets=None, max_points=65536, allow_copies=False, splits=0,
-                 workspace_bytes=0):
-    """``information_gain`` of device rows ``view = (address, n_blocks, block_rows, block_stride_rows)`` read in place."""
-    U, skipped = unit_rows_dev(device, *view, d, lower, upper, max_points)
-    return _gain(U, skipped, k, subsets, allow_copies, splits, device, workspace_bytes)
+def gain_of_view(rows, lower, upper, k=4, subsets=None, max_points=65536, allow_copies=False, splits=0, workspace_bytes=0):
+    """``information_gain`` of the ``DeviceRows`` ``rows`` read in place."""
+    U, skipped = unit_rows_dev(rows.device, *rows.layout, rows.d, lower, upper, max_points)
+    return _gain(U, skipped, k, subsets, allow_copies, splits, rows.device, workspace_bytes)
 
 
-def divergence_of_views(device, view_x, view_y, d, lower, upper, k=4, subsets=None, max_points=65536, allow_copies=False,
-                        splits=0, workspace_bytes=0):
-    """``kl_divergence`` of two sets of device rows; ``view_y`` may be a host array or a device tensor ``(m, d)``."""
-    Ux, sx = unit_rows_dev(device, *view_x, d, lower, upper, max_points)
-    if isinstance(view_y, tuple):
-        Uy, sy = unit_rows_dev(device, *view_y, d, lower, upper, max_points)
-    else:
+def divergence_of_views(rows_x, other, lower, upper, k=4, subsets=None, max_points=65536, allow_copies=False, splits=0,
+                        workspace_bytes=0):
+    """``kl_divergence`` of ``DeviceRows`` against ``other``: ``DeviceRows``, a host array or a device tensor ``(m, d)``."""
+    device, d = rows_x.device, rows_x.d
+    Ux, sx = unit_rows_dev(device, *rows_x.layout, d, lower, upper, max_points)
+    if not isinstance(other, DeviceRows):
         import torch
-        Y, on_device = _rows(view_y, "other")
+        Y, on_device = _rows(other, "other")
         if not on_device:
             Y = torch.from_numpy(Y).to(torch.device("cuda", int(device)))
         if int(Y.shape[1]) != int(d):
             raise ValueError(f"the chain has {d} parameters, other {int(Y.shape[1])} columns")
-        Uy, sy = unit_rows_dev(device, Y.data_ptr(), 1, int(Y.shape[0]), int(Y.shape[0]), d, lower, upper, max_points)
+        other = DeviceRows.of_tensor(Y)
+    Uy, sy = unit_rows_dev(device, *other.layout, d, lower, upper, max_points)
     return _divergence(Ux, sx, Uy, sy, k, subsets, allow_copies, splits, device, workspace_bytes)

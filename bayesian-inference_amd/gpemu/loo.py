@@ -24,6 +24,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import check, ptr
+from .rows import DeviceRows
 
 PATHS = ("SORT_PASS", "ROW_SMOOTHED", "ROW_RAW", "CHUNK", "ROW_BATCH")
 FIELDS = ("elpd_loo", "lppd", "p_loo", "pareto_k", "n_tail", "ess_w", "p_waic", "elpd_waic", "cutoff")
@@ -153,6 +154,29 @@ def weighted_moments_dev(device, base, n_blocks, block_rows, block_stride_rows, 
     return h[0].copy(), h[1].copy()
 
 
+def pointwise_dev(model_or_models, rows, chain=0):
+    """``pointwise`` of the ``DeviceRows`` ``rows``, read in place: a device tensor ``(n_obs, S)``."""
+    import torch
+    models = list(model_or_models) if isinstance(model_or_models, (list, tuple)) else [model_or_models]
+    nobs = [m.n_observable_blocks for m in models]
+    T = torch.empty((sum(nobs), rows.rows), dtype=torch.float64, device=torch.device("cuda", rows.device))
+    o0 = 0
+    for m, nb in zip(models, nobs):
+        m.loglik_pointwise_dev(*rows.layout, T[o0].data_ptr(), rows.rows, chain=chain)
+        o0 += nb
+    return T
+
+
+def plain_moments_dev(rows, baseline=None):
+    """The unweighted ``(mean, var)`` ``(d,)`` of ``DeviceRows``: ``baseline()``, else ``weighted_moments_dev``, uniform."""
+    if baseline is not None:
+        return baseline()
+    import torch
+    uniform = torch.zeros((1, rows.rows), dtype=torch.float64, device=torch.device("cuda", rows.device))
+    mean, var = weighted_moments_dev(rows.device, *rows.layout, rows.d, uniform)
+    return mean[0], var[0]
+
+
 # -- public functions -------------------------------------------------------------------------------------------------
 def pointwise(model_or_models, X, normalised=False, chain=0):
     """``T (n_obs, S)``: the log-likelihood term of every observable block of the model -- or of every model of a list,
@@ -242,28 +266,20 @@ def compare(summary_a, summary_b):
             "warning": bool(np.any(a["warning"]) or np.any(b["warning"]))}
 
 
-def from_terms(device, T, labels, view, d, leave_out=None, shifts=True, r_eff=None, workspace_bytes=0, baseline=None):
-    """The table of ``DeviceSampler.loo`` from the device tensor ``T (n_obs, S)`` of the terms of the rows ``view`` =
-    ``(address, n_blocks, block_rows, block_stride_rows)``: ``assemble`` of ``psis`` and, with ``shifts``, ``mean``, ``sd``
-    ``(d,)`` (``baseline()``, or the same reduction under uniform weights), ``loo_mean``, ``loo_sd`` ``(n_obs, d)`` and
-    ``shift = (loo_mean - mean) / sd``."""
-    import torch
+def from_terms(T, labels, rows, leave_out=None, shifts=True, r_eff=None, workspace_bytes=0, baseline=None):
+    """The table of ``DeviceSampler.loo`` from the device tensor ``T (n_obs, S)`` of the terms of the ``DeviceRows``
+    ``rows``: ``assemble`` of ``psis`` and, with ``shifts``, ``mean``, ``sd`` ``(d,)`` (``baseline()``, or the same
+    reduction under uniform weights), ``loo_mean``, ``loo_sd`` ``(n_obs, d)`` and ``shift = (loo_mean - mean) / sd``."""
     labels = [str(v) for v in labels]
     if leave_out is not None:
-        T, labels = _left_out(device, T, labels, leave_out)
+        T, labels = _left_out(rows.device, T, labels, leave_out)
     R, S = int(T.shape[0]), int(T.shape[1])
-    stats = psis_dev(device, T.data_ptr(), R, S, S, 1, r_eff, bool(shifts), workspace_bytes)
+    stats = psis_dev(rows.device, T.data_ptr(), R, S, S, 1, r_eff, bool(shifts), workspace_bytes)
     out = assemble(stats, S, labels)
     if shifts:
-        src, n_blocks, nw, stride = view
-        out["loo_mean"], var = weighted_moments_dev(device, src, n_blocks, nw, stride, d, stats["log_weights"])
+        out["loo_mean"], var = weighted_moments_dev(rows.device, *rows.layout, rows.d, stats["log_weights"])
         out["loo_sd"] = np.sqrt(var)
-        if baseline is not None:
-            mean, v0 = baseline()
-        else:
-            m0, v0 = weighted_moments_dev(device, src, n_blocks, nw, stride, d,
-                                          torch.zeros((1, S), dtype=torch.float64, device=T.device))
-            mean, v0 = m0[0], v0[0]
+        mean, v0 = plain_moments_dev(rows, baseline)
         out["mean"], out["sd"] = np.asarray(mean), np.sqrt(v0)
         out["shift"] = (out["loo_mean"] - out["mean"][None, :]) / out["sd"][None, :]
     return out
@@ -282,10 +298,8 @@ def chain_loo(models, X, leave_out=None, shifts=True, r_eff=None, chain=0, label
     X = np.ascontiguousarray(X, dtype=np.float64)
     if X.ndim != 2 or X.shape[0] < 1 or X.shape[1] != models[0].d:
         raise ValueError(f"X must be (S, {models[0].d})")
-    device = models[0].device
-    dev = torch.device("cuda", int(device))
+    dev = torch.device("cuda", int(models[0].device))
     T = torch.from_numpy(pointwise(models, X, chain=chain)).to(dev)
-    dX = torch.from_numpy(X).to(dev)
-    S = X.shape[0]
-    return from_terms(device, T, default_labels(models) if labels is None else labels, (dX.data_ptr(), 1, S, S), X.shape[1],
-                      leave_out, shifts, r_eff, workspace_bytes)
+    rows = DeviceRows.of_tensor(torch.from_numpy(X).to(dev))
+    return from_terms(T, default_labels(models) if labels is None else labels, rows, leave_out, shifts, r_eff,
+                      workspace_bytes)

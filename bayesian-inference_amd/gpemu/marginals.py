@@ -25,6 +25,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import check, ptr
+from .rows import DeviceRows
 
 PATHS = ("HIST_SWEEP", "PAIR_GROUP", "SORT_BATCH", "WINDOW_SEARCH", "KDE")
 PATHS_KDE2D = ("DENSITY", "PAIR_BATCH", "PARTIAL_SUM", "MOMENTS", "EXTENTS")
@@ -345,16 +346,15 @@ def _kde2d_dev(device, base, n_blocks, block_rows, block_stride_rows, d, plan, w
     return out.cpu().numpy()
 
 
-def _kde2d_view(device, base, n_blocks, block_rows, block_stride_rows, d, workspace_bytes=0, **plan_kw):
-    """``kde_2d`` of device rows in the block layout: the plan from the device moments and extents, then the panels."""
-    S = int(n_blocks) * int(block_rows)
-    view = (device, base, n_blocks, block_rows, block_stride_rows, d)
+def _kde2d_view(rows, workspace_bytes=0, **plan_kw):
+    """``kde_2d`` of ``DeviceRows`` read in place: the plan from the device moments and extents, then the panels."""
+    S, at = rows.rows, (rows.device, *rows.layout, rows.d)
 
     def cov():
-        return _pair_moments_dev(*view)[1] * (S / (S - 1.0))
-    plan = kde2d_plan(S, d, cov=cov, extents=lambda pr, beta: _pair_moments_dev(*view, pr, beta, moments=False)[2],
+        return _pair_moments_dev(*at)[1] * (S / (S - 1.0))
+    plan = kde2d_plan(S, rows.d, cov=cov, extents=lambda pr, beta: _pair_moments_dev(*at, pr, beta, moments=False)[2],
                       **plan_kw)
-    plan["density"] = _kde2d_dev(*view, plan, workspace_bytes)
+    plan["density"] = _kde2d_dev(*at, plan, workspace_bytes)
     return plan
 
 
@@ -493,7 +493,7 @@ def kde_2d(samples, pairs=None, covariance="full", bandwidth=None, shear=None, g
     kw = dict(pairs=pairs, covariance=covariance, bandwidth=bandwidth, shear=shear, grid_a=grid_a, grid_b=grid_b,
               n_grid=n_grid, cut=cut, bw_adjust=bw_adjust)
     if on_device:
-        return _kde2d_view(x.device.index or 0, x.data_ptr(), 1, S, S, d, workspace_bytes, **kw)
+        return _kde2d_view(DeviceRows.of_tensor(x), workspace_bytes, **kw)
     plan = kde2d_plan_host(x, **kw)
     _lib.require_device()
     P, G = plan["grid_a"].shape
@@ -536,3 +536,34 @@ def summary(samples, lower, upper, bins_1d=100, bins_2d=50, confidence=(0.9,), k
     dens = kde_1d(samples, n_grid=n_grid, device=device) if kde else None
     dens2 = kde_2d(samples, covariance=covariance_2d, n_grid=n_grid_2d, device=device) if kde2d else None
     return assemble(hist, conf, hpd, dens, dens2)
+
+
+def summary_view(rows, lower, upper, bins_1d=100, bins_2d=50, confidence=(0.9,), kde=True, n_grid=200, kde2d=False,
+                 n_grid_2d=100, covariance_2d="full"):
+    """``summary`` of ``DeviceRows`` where they lie (``DeviceSampler.marginals``): the histograms and the 2-D densities
+    read them in place, the sort and the 1-D density ``rows.columns()``, which is released before the 2-D densities run."""
+    device, d, S = rows.device, rows.d, rows.rows
+    if not (1 <= int(bins_1d) <= MAX_BINS_1D and 1 <= int(bins_2d) <= MAX_BINS_2D):
+        raise ValueError(f"bins_1d must be in [1, {MAX_BINS_1D}] and bins_2d in [1, {MAX_BINS_2D}]")
+    e1, e2 = bin_edges(lower, upper, bins_1d), bin_edges(lower, upper, bins_2d)
+    if e1.shape[0] != d:
+        raise ValueError(f"the box has {e1.shape[0]} parameters, the sampler {d}")
+    conf = np.atleast_1d(np.asarray(confidence, dtype=np.float64))
+    n_out = n_outside(conf, S)
+    h1, h2, ni = _hist_dev(device, *rows.layout, d, e1, e2)
+    hist = {"edges_1d": e1, "edges_2d": e2, "hist_1d": h1, "pairs": pair_indices(d), "hist_2d": h2, "n_inside": ni}
+    cols = rows.columns()
+    # one sort serves the intervals and, as the level n_out = 1 (window 0: smallest, largest), the density's support
+    ends = _hpd_dev(device, cols.address, S, d, np.append(n_out, 1) if kde else n_out)
+    dens = None
+    if kde:
+        def spread():
+            _, var = _moments_dev(device, cols.address, S, d)
+            return np.sqrt(var * (S / max(S - 1.0, 1.0))), ends[-1, :, 0], ends[-1, :, 1]
+        h, g = _kde_plan(S, d, None, None, n_grid, 3.0, spread)
+        dens = {"grid": g, "density": _kde_dev(device, cols.address, S, d, g, h), "bandwidth": h}
+    del cols        # (the dense copy, where one was made)
+    if kde2d and d < 2:
+        raise ValueError("kde2d needs at least two parameters")
+    dens2 = _kde2d_view(rows, covariance=covariance_2d, n_grid=n_grid_2d) if kde2d else None
+    return assemble(hist, conf, ends[:n_out.size], dens, dens2)

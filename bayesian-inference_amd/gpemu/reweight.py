@@ -28,6 +28,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import check, ptr
+from .rows import DeviceRows
 
 PATHS = ("LOGPRIOR", "QUANTISE", "LOGSUMEXP", "WSEL_HIST_PASS", "WSEL_SCAN", "WHIST_SWEEP", "WHIST_PAIR_GROUP")
 KINDS = {"flat": 0, "log_uniform": 1, "normal": 2, "log_normal": 3}
@@ -352,23 +353,14 @@ def _box(lower, upper, d):
     return np.ascontiguousarray(lo), np.ascontiguousarray(hi)
 
 
-def data_log_ratio_dev(models_old, models_new, view, chain=0):
-    """The data scenario's log-ratio of device rows ``view = (device, address, n_blocks, block_rows,
-    block_stride_rows, S)``: the pointwise terms of both lists of models (``loglik_pointwise_dev``), each list's rows
-    summed in row order on the device, then subtracted once -- a device tensor ``(1, S)``."""
-    import torch
+def data_log_ratio_dev(models_old, models_new, rows, chain=0):
+    """The data scenario's log-ratio of the ``DeviceRows`` ``rows``, a device tensor ``(1, S)``: the pointwise terms of
+    both lists of models (``gpemu.loo.pointwise_dev``), each summed in row order on the device, then subtracted once."""
     from . import loo as LO
-    device, src, n_blocks, nw, stride, S = view
-    sums = []
+    S, sums = rows.rows, []
     for models in (models_new, models_old):
-        models = list(models) if isinstance(models, (list, tuple)) else [models]
-        nobs = [m.n_observable_blocks for m in models]
-        T = torch.empty((sum(nobs), S), dtype=torch.float64, device=torch.device("cuda", int(device)))
-        o0 = 0
-        for m, nb in zip(models, nobs):
-            m.loglik_pointwise_dev(src, n_blocks, nw, stride, T[o0].data_ptr(), S, chain=chain)
-            o0 += nb
-        sums.append(LO.group_rows_dev(device, T.data_ptr(), int(T.shape[0]), S, S, [list(range(int(T.shape[0])))]))
+        T = LO.pointwise_dev(models, rows, chain)
+        sums.append(LO.group_rows_dev(rows.device, T.data_ptr(), int(T.shape[0]), S, S, [list(range(int(T.shape[0])))]))
     return sums[0] - sums[1]
 
 
@@ -398,9 +390,8 @@ def log_ratio(samples, priors=None, lower=None, upper=None, models_old=None, mod
                                             ptr(a), ptr(b), ptr(lo), ptr(L)))
     if models_new is not None:
         first = models_old[0] if isinstance(models_old, (list, tuple)) else models_old
-        dev = first.device
-        dx = x if on_device else _to_device(x, dev)
-        D = data_log_ratio_dev(models_old, models_new, (dev, dx.data_ptr(), 1, S, S, S), chain)
+        dx = x if on_device else _to_device(x, first.device)
+        D = data_log_ratio_dev(models_old, models_new, DeviceRows.of_tensor(dx), chain)
         if L is None:
             L = D if on_device else D.cpu().numpy()
         else:
@@ -593,13 +584,12 @@ def weighted_kde_1d(values, q, log_weights=None, grid=None, bandwidth=None, n_gr
     return {"grid": g, "density": dens, "bandwidth": h}
 
 
-def bands_of_view(models, view, q, Q, probabilities=(0.05, 0.5, 0.95), workspace_bytes=0):
-    """The weighted posterior-predictive bands of device rows ``view = (device, address, n_blocks, block_rows,
-    block_stride_rows, S)`` under the int64 device tensor ``q (R_w, S)`` with totals ``Q``: a list over the weight rows of
-    ``{"posterior_predictive": [one dict per model]}`` (``DeviceModel.posterior_predictive_weighted``'s dicts)."""
+def bands_of_view(models, rows, q, Q, probabilities=(0.05, 0.5, 0.95), workspace_bytes=0):
+    """The weighted posterior-predictive bands of the ``DeviceRows`` ``rows`` under the int64 device tensor ``q (R_w,
+    S)`` with totals ``Q``: a list over the weight rows of ``{"posterior_predictive": [one dict per model]}``
+    (``DeviceModel.posterior_predictive_weighted``'s dicts)."""
     import torch
     from .model import weighted_postpred_result
-    device, src, n_blocks, nw, stride, S = view
     p = np.zeros(0) if probabilities is None else np.asarray(probabilities, dtype=np.float64).reshape(-1)
     R_w = int(q.shape[0])
     tgt = targets(p, Q) if p.size else np.zeros((R_w, 0), dtype=np.uint64)
@@ -607,8 +597,8 @@ def bands_of_view(models, view, q, Q, probabilities=(0.05, 0.5, 0.95), workspace
     for m in models:
         mean, vp, ve = (torch.empty((R_w, m.F), dtype=torch.float64, device=q.device) for _ in range(3))
         qt = torch.empty((R_w, m.F, max(p.size, 1)), dtype=torch.float64, device=q.device)
-        m.posterior_predictive_weighted_dev(src, n_blocks, nw, stride, q, tgt, mean.data_ptr(), vp.data_ptr(),
-                                            ve.data_ptr(), qt.data_ptr() if p.size else 0, workspace_bytes)
+        m.posterior_predictive_weighted_dev(*rows.layout, q, tgt, mean.data_ptr(), vp.data_ptr(), ve.data_ptr(),
+                                            qt.data_ptr() if p.size else 0, workspace_bytes)
         per_model.append(weighted_postpred_result(mean.cpu().numpy(), vp.cpu().numpy(), ve.cpu().numpy(),
                                                   qt.cpu().numpy(), p, Q))
     return [{"posterior_predictive": [pm[w] for pm in per_model]} for w in range(R_w)]
@@ -647,18 +637,16 @@ def assemble(stats, S, Q, mean, var, mean0, var0, quantiles, hist, probabilities
     return out
 
 
-def summary_view(view, d, log_ratio_dev, lower, upper, probabilities=(0.05, 0.5, 0.95), bins_1d=100, bins_2d=50,
-                 smooth=True, r_eff=None, log_norm=None, baseline=None, column_src=None, workspace_bytes=0, hpd=None,
-                 kde=False, n_grid=200, extra=None):
-    """``summary`` of device rows ``view = (device, address, n_blocks, block_rows, block_stride_rows, S)`` under the
-    device tensor ``log_ratio_dev (R, S)``.  ``column_src``: the address of a dense copy ``[S][d]`` where one parameter
-    of the view is not a single stride (a thinned chain, one chain of a stacked sampler); ``baseline()``: the unweighted
-    ``(mean, var)`` where the caller has them, else the same reduction under uniform weights.  ``hpd`` (confidence
-    levels), ``kde``: see ``summary``; ``extra(q, Q)``: further entries per scenario, a list of dicts to merge in."""
-    import torch
+def summary_view(rows, log_ratio_dev, lower, upper, probabilities=(0.05, 0.5, 0.95), bins_1d=100, bins_2d=50,
+                 smooth=True, r_eff=None, log_norm=None, baseline=None, workspace_bytes=0, hpd=None, kde=False, n_grid=200,
+                 extra=None):
+    """``summary`` of the ``DeviceRows`` ``rows`` under the device tensor ``log_ratio_dev (R, S)``.  The moments and the
+    histograms read the rows as they lie; the quantiles, intervals and densities read ``rows.columns()``.  ``baseline()``:
+    the unweighted ``(mean, var)`` where the caller has them, else the same reduction under uniform weights.  ``hpd``
+    (confidence levels), ``kde``: see ``summary``; ``extra(q, Q)``: further entries per scenario, a list of dicts to merge in."""
     from . import loo as LO
     from . import marginals as M
-    device, src, n_blocks, nw, stride, S = view
+    device, d, S = rows.device, rows.d, rows.rows
     lo, hi = _box(lower, upper, d)
     if not (1 <= int(bins_1d) <= MAX_BINS_1D and 1 <= int(bins_2d) <= MAX_BINS_2D):
         raise ValueError(f"bins_1d must be in [1, {MAX_BINS_1D}] and bins_2d in [1, {MAX_BINS_2D}]")
@@ -668,30 +656,23 @@ def summary_view(view, d, log_ratio_dev, lower, upper, probabilities=(0.05, 0.5,
     q, Q = fixed_weights_dev(lw)
     if np.any(Q == 0):
         raise ValueError("a scenario's weights are all zero or not finite: its log-ratio holds a NaN or an infinity")
-    mean, var = LO.weighted_moments_dev(device, src, n_blocks, nw, stride, d, lw)
-    if baseline is not None:
-        mean0, var0 = baseline()
-    else:
-        m0, v0 = LO.weighted_moments_dev(device, src, n_blocks, nw, stride, d,
-                                         torch.zeros((1, S), dtype=torch.float64, device=lw.device))
-        mean0, var0 = m0[0], v0[0]
+    mean, var = LO.weighted_moments_dev(device, *rows.layout, d, lw)
+    mean0, var0 = LO.plain_moments_dev(rows, baseline)
     tgt = targets(probabilities, Q)
-    cols = src if column_src is None else column_src
-    if column_src is None and not (n_blocks == 1 or stride == nw):
-        raise ValueError("a view in strided blocks needs column_src, a dense copy of its rows")
-    quant = weighted_quantile_dev(device, cols, d, S, 1, d, q, tgt, workspace_bytes).transpose(0, 2, 1)
-    h1, h2, wi = weighted_hist_dev(device, src, n_blocks, nw, stride, d, q, e1, e2)
+    cols = rows.columns()
+    quant = weighted_quantile_dev(device, cols.address, d, S, 1, d, q, tgt, workspace_bytes).transpose(0, 2, 1)
+    h1, h2, wi = weighted_hist_dev(device, *rows.layout, d, q, e1, e2)
     hist = {"edges_1d": e1, "edges_2d": e2, "pairs": M.pair_indices(d), "hist_1d_q": h1, "hist_2d_q": h2, "w_inside": wi}
     out = assemble(st, S, Q, mean, var, np.asarray(mean0), np.asarray(var0), np.ascontiguousarray(quant), hist,
                    probabilities, log_norm, float(np.sum(np.log(hi - lo))))
     iv = dens = None
     if hpd is not None:
-        iv = weighted_hpd_dev(device, cols, d, S, 1, d, q, targets(hpd, Q), workspace_bytes).transpose(0, 2, 1, 3)
+        iv = weighted_hpd_dev(device, cols.address, d, S, 1, d, q, targets(hpd, Q), workspace_bytes).transpose(0, 2, 1, 3)
         iv = np.ascontiguousarray(iv)
     if kde:
-        ends = M._hpd_dev(device, cols, S, d, [1])[0]         # n_out = 1, window 0: (smallest, largest)
+        ends = M._hpd_dev(device, cols.address, S, d, [1])[0]         # n_out = 1, window 0: (smallest, largest)
         h, g = _kde_plan(var, st["ess_w"], ends[:, 0], ends[:, 1], len(Q), d, None, None, n_grid, 3.0)
-        dens = {"grid": g, "density": weighted_kde_dev(device, cols, d, S, 1, d, q, g, h), "bandwidth": h}
+        dens = {"grid": g, "density": weighted_kde_dev(device, cols.address, d, S, 1, d, q, g, h), "bandwidth": h}
     add_hpd_kde(out, hpd, iv, dens)
     if extra is not None:
         for res, more in zip(out, extra(q, Q)):
@@ -720,10 +701,9 @@ def summary(samples, log_ratio, lower, upper, probabilities=(0.05, 0.5, 0.95), b
     if int(L.shape[1]) != S:
         raise ValueError(f"log_ratio has {int(L.shape[1])} columns, the samples are {S}")
     if on_device:
-        dev = x.device.index or 0
-        dL = L if l_dev else _to_device(np.ascontiguousarray(L, dtype=np.float64), dev)
-        return summary_view((dev, x.data_ptr(), 1, S, S, S), d, dL, lower, upper, probabilities, bins_1d, bins_2d, smooth,
-                            r_eff, log_norm, hpd=hpd, kde=kde, n_grid=n_grid, extra=extra)
+        dL = L if l_dev else _to_device(np.ascontiguousarray(L, dtype=np.float64), x.device.index or 0)
+        return summary_view(DeviceRows.of_tensor(x), dL, lower, upper, probabilities, bins_1d, bins_2d, smooth, r_eff,
+                            log_norm, hpd=hpd, kde=kde, n_grid=n_grid, extra=extra)
     _lib.require_device()
     dev = int(_lib.resolve_device(device))
     lo, hi = _box(lower, upper, d)
@@ -757,15 +737,12 @@ def chain_reweight(models, X, priors=None, models_new=None, lower=None, upper=No
                    **summary_kw):
     """``DeviceSampler.reweight`` for a chain on the host: ``X (S, d)``, the flattened rows, of a sampler over ``models``
     (whose bands ``posterior_predictive`` adds)."""
+    from .sampler import DeviceSampler
     models = list(models) if isinstance(models, (list, tuple)) else [models]
     X = np.ascontiguousarray(X, dtype=np.float64)
     if X.ndim != 2 or X.shape[0] < 1 or X.shape[1] != models[0].d:
         raise ValueError(f"X must be (S, {models[0].d})")
-    if lower is None or upper is None:
-        box = getattr(models[0], "prior_box", None)
-        if box is None:
-            raise ValueError("no prior box is known (likelihood_setup has not been called): pass lower and upper")
-        lower, upper = (box[0] if lower is None else lower), (box[1] if upper is None else upper)
+    lower, upper = DeviceSampler._box_or_prior(models, lower, upper)
     L = log_ratio(X, priors=priors, lower=lower, upper=upper, models_old=models if models_new is not None else None,
                   models_new=models_new, chain=chain, device=models[0].device)
     log_norm = None

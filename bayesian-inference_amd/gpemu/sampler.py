@@ -20,6 +20,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import as_f64, check, ptr
+from .rows import DeviceRows
 
 
 def shard_bounds(n, world, rank):
@@ -255,10 +256,9 @@ class DeviceSampler:
         check(_lib.lib().gpemu_sampler_chain_ptr(self._h, int(first), C.byref(p), C.byref(n)))
         return int(p.value or 0), int(n.value)
 
-    def _stored_view(self, discard, thin, chain):
-        """The stored chain ``get_chain()[discard::thin]`` of ``chain`` as rows in blocks on the device: ``(address of
-        walker w0 of step discard, n_blocks, nw, block stride in rows, S = n_blocks * nw)`` -- a block is the chain's
-        walkers of one kept step."""
+    def _stored_view(self, discard, thin, chain, stream=None):
+        """The stored chain ``get_chain()[discard::thin]`` of ``chain`` as ``DeviceRows``: from walker w0 of step discard
+        on, a block is the chain's walkers of one kept step."""
         discard, thin = int(discard), int(thin)
         if thin < 1 or discard < 0:
             raise ValueError("discard must be >= 0 and thin >= 1")
@@ -266,8 +266,20 @@ class DeviceSampler:
         if discard >= self.counts()[2]:
             raise ValueError("no stored steps after discard")
         base, n = self.chain_ptr(discard)
-        n_blocks = (n + thin - 1) // thin
-        return base + 8 * w0 * self.d, n_blocks, nw, thin * self.W, n_blocks * nw
+        return DeviceRows(base + 8 * w0 * self.d, (n + thin - 1) // thin, nw, thin * self.W, stream, device=self.device, d=self.d)
+
+    def _models(self, models):
+        """``models`` (default: the sampler's groups) as a list, each on the sampler's parameters and device."""
+        models = self.models if models is None else list(models)
+        for m in models:
+            if m.d != self.d or m.device != self.device:
+                raise ValueError("model and sampler differ in parameters or device")
+        return models
+
+    def _baseline(self, discard, thin, rows):
+        """``chain_moments`` for the view of every walker of every step from ``discard`` on, else None (uniform weights)."""
+        whole = thin == 1 and rows.block_rows == self.W
+        return (lambda: self.chain_moments(discard)) if whole else None
 
     def posterior_predictive(self, models=None, discard=0, thin=1, probabilities=(0.05, 0.5, 0.95), chain=None,
                              workspace_bytes=0):
@@ -277,18 +289,15 @@ class DeviceSampler:
         the whole chain on every rank (every rank accepts identically), so each rank may call this on its own."""
         import torch
         from .model import QuantilePlan
-        models = self.models if models is None else list(models)
-        src, n_blocks, nw, stride, S = self._stored_view(discard, thin, chain)
-        plan = QuantilePlan(S, probabilities)
+        rows = self._stored_view(discard, thin, chain)
+        plan = QuantilePlan(rows.rows, probabilities)
+        models = self._models(models)
         dev = torch.device("cuda", self.device)
         out = []
         for m in models:
-            if m.d != self.d or m.device != self.device:
-                raise ValueError("model and sampler differ in parameters or device")
             bufs = torch.empty((3 + max(plan.ranks.size, 1), m.F), dtype=torch.float64, device=dev)
             order = bufs[3:].reshape(-1)          # [F][n_ranks] as the library writes it
-            m.posterior_predictive_dev(src, n_blocks, nw, stride, plan.ranks,
-                                       bufs[0].data_ptr(), bufs[1].data_ptr(), bufs[2].data_ptr(),
+            m.posterior_predictive_dev(*rows.layout, plan.ranks, bufs[0].data_ptr(), bufs[1].data_ptr(), bufs[2].data_ptr(),
                                        order.data_ptr() if plan.ranks.size else 0, workspace_bytes=workspace_bytes)
             h = bufs.cpu().numpy()
             out.append(plan.result(h[0].copy(), h[1].copy(), h[2].copy(),
@@ -301,7 +310,8 @@ class DeviceSampler:
         d of the device chain); one chain of a stacked sampler is not a single stride, so its walkers are copied out
         first and selected from that copy."""
         from . import select
-        src, n, nw, _, S = self._stored_view(discard, 1, chain)
+        rows = self._stored_view(discard, 1, chain)
+        src, n, nw, S = rows.address, rows.n_blocks, rows.block_rows, rows.rows
         if nw != self.W:
             x = np.empty((n, nw, self.d))
             lp = np.empty((n, nw))
@@ -336,7 +346,7 @@ class DeviceSampler:
         autocorrelation time (``integrated_time``) for an ensemble; the chains of an ``HMCSampler`` are independent and
         the statistics mean what they mean in Stan.  Stacked samplers take ``chain=<index>``."""
         from .diagnostics import Diag
-        _, n, nw, _, _ = self._stored_view(discard, thin, chain)
+        _, n, nw, _ = self._stored_view(discard, thin, chain).layout
         with Diag.from_sampler(self._h, int(discard), n, int(thin), self._chain_walkers(chain)[0], nw, self.d) as h:
             return h.summary()
 
@@ -347,52 +357,16 @@ class DeviceSampler:
         ``edges_1d``, ``edges_2d``, ``hist_1d``, ``pairs``, ``hist_2d``, ``n_inside``, ``confidence``, ``hpd (n_levels,
         d, 2)`` and, with ``kde``, ``kde_grid``, ``kde_density``, ``kde_bandwidth``.  The box defaults to the prior box
         of the sampler's models.  The histograms read the chain in place, thinned or stacked; the sort and the density
-        read one parameter as one stride, so a thinned chain or one chain of a stacked sampler is first copied to a
-        dense device buffer.  With ``kde2d``: the 2-D kernel densities of all pairs (``gpemu.marginals.kde_2d``; DESIGN.md
-        §4.33) on ``n_grid_2d`` points per axis, ``covariance_2d`` ``"full"`` or ``"diagonal"``, as ``kde2d_pairs``,
-        ``kde2d_shear``, ``kde2d_bandwidth``, ``kde2d_grid_a``, ``kde2d_grid_b`` and ``kde2d_density``; they read the same
-        view in place, thinned or stacked.  Stacked samplers take ``chain=<index>``."""
-        import torch
+        read one parameter as one stride, so a view of several strided blocks (a thinned chain, one chain of a stacked
+        sampler) is first copied to a dense device buffer.  With ``kde2d``: the 2-D kernel densities of all pairs
+        (``gpemu.marginals.kde_2d``) on ``n_grid_2d`` points per axis, ``covariance_2d`` ``"full"`` or
+        ``"diagonal"``, as ``kde2d_pairs``, ``kde2d_shear``, ``kde2d_bandwidth``, ``kde2d_grid_a``, ``kde2d_grid_b`` and
+        ``kde2d_density``; they read the same view in place, thinned or stacked.  Stacked samplers take ``chain=<index>``."""
         from . import marginals as M
-        src, n_blocks, nw, stride, S = self._stored_view(discard, thin, chain)
-        view = (self.device, src, n_blocks, nw, stride, self.d)
-        if lower is None or upper is None:
-            box = getattr(self.models[0], "prior_box", None)
-            if box is None:
-                raise ValueError("no prior box is known (likelihood_setup has not been called): pass lower and upper")
-            lower, upper = (box[0] if lower is None else lower), (box[1] if upper is None else upper)
-        if not (1 <= int(bins_1d) <= M.MAX_BINS_1D and 1 <= int(bins_2d) <= M.MAX_BINS_2D):
-            raise ValueError(f"bins_1d must be in [1, {M.MAX_BINS_1D}] and bins_2d in [1, {M.MAX_BINS_2D}]")
-        e1, e2 = M.bin_edges(lower, upper, bins_1d), M.bin_edges(lower, upper, bins_2d)
-        if e1.shape[0] != self.d:
-            raise ValueError(f"the box has {e1.shape[0]} parameters, the sampler {self.d}")
-        d = self.d
-        conf = np.atleast_1d(np.asarray(confidence, dtype=np.float64))
-        n_out = M.n_outside(conf, S)
-        h1, h2, ni = M._hist_dev(self.device, src, n_blocks, nw, stride, d, e1, e2)
-        hist = {"edges_1d": e1, "edges_2d": e2, "hist_1d": h1, "pairs": M.pair_indices(d), "hist_2d": h2, "n_inside": ni}
-        dense = None
-        if stride != nw:
-            dense = torch.empty((S, d), dtype=torch.float64, device=torch.device("cuda", self.device))
-            check(_lib.lib().gpemu_marginal_dense_dev(self.device, C.c_void_p(src), n_blocks, nw, stride, d,
-                                                      C.c_void_p(dense.data_ptr()), _lib.current_stream(self.device)))
-            src = dense.data_ptr()
-        # one sort serves the intervals and, as the level n_out = 1 (window 0: smallest, largest), the density's support
-        ends = M._hpd_dev(self.device, src, S, d, np.append(n_out, 1) if kde else n_out)
-        dens = None
-        if kde:
-            def spread():
-                _, var = M._moments_dev(self.device, src, S, d)
-                return np.sqrt(var * (S / max(S - 1.0, 1.0))), ends[-1, :, 0], ends[-1, :, 1]
-            h, g = M._kde_plan(S, d, None, None, n_grid, 3.0, spread)
-            dens = {"grid": g, "density": M._kde_dev(self.device, src, S, d, g, h), "bandwidth": h}
-        del dense
-        dens2 = None
-        if kde2d:
-            if d < 2:
-                raise ValueError("kde2d needs at least two parameters")
-            dens2 = M._kde2d_view(*view, covariance=covariance_2d, n_grid=n_grid_2d)
-        return M.assemble(hist, conf, ends[:n_out.size], dens, dens2)
+        rows = self._stored_view(discard, thin, chain)
+        lower, upper = self._box_or_prior(self.models, lower, upper)
+        return M.summary_view(rows, lower, upper, bins_1d, bins_2d, confidence, kde, n_grid, kde2d, n_grid_2d,
+                              covariance_2d)
 
     def _data_chain(self, chain):
         """The data vector of the models' likelihood setup that ``chain`` of this sampler was run on."""
@@ -408,23 +382,12 @@ class DeviceSampler:
         d)`` under each row's leave-one-out weights and ``shift = (loo_mean - mean) / sd`` -- how far leaving an observable
         out moves each parameter, in posterior standard deviations.  Stacked samplers take ``chain=<index>`` (scored
         against that chain's own data vector)."""
-        import torch
         from . import loo as LO
-        models = self.models if models is None else list(models)
-        src, n_blocks, nw, stride, S = self._stored_view(discard, thin, chain)
-        dev = torch.device("cuda", self.device)
-        nobs = [m.n_observable_blocks for m in models]
-        T = torch.empty((sum(nobs), S), dtype=torch.float64, device=dev)
-        labels, o0 = [], 0
-        for g, (m, nb) in enumerate(zip(models, nobs)):
-            if m.d != self.d or m.device != self.device:
-                raise ValueError("model and sampler differ in parameters or device")
-            m.loglik_pointwise_dev(src, n_blocks, nw, stride, T[o0].data_ptr(), S, chain=self._data_chain(chain))
-            labels += [f"g{g}o{o}" for o in range(nb)]
-            o0 += nb
-        whole = thin == 1 and nw == self.W      # else a thinned or stacked view: the same reduction, uniform weights
-        return LO.from_terms(self.device, T, labels, (src, n_blocks, nw, stride), self.d, leave_out, shifts, r_eff,
-                             workspace_bytes, baseline=(lambda: self.chain_moments(discard)) if whole else None)
+        rows = self._stored_view(discard, thin, chain)
+        models = self._models(models)
+        T = LO.pointwise_dev(models, rows, self._data_chain(chain))
+        return LO.from_terms(T, LO.default_labels(models), rows, leave_out, shifts, r_eff, workspace_bytes,
+                             baseline=self._baseline(discard, thin, rows))
 
     def reweight(self, priors=None, models_new=None, discard=0, thin=1, chain=None, lower=None, upper=None,
                  posterior_predictive=False, models=None, **summary_kw):
@@ -438,47 +401,35 @@ class DeviceSampler:
         ``posterior_predictive``: a list with one dict per model of ``models`` (default: the sampler's groups), the
         weighted bands of ``DeviceModel.posterior_predictive_weighted`` on the same view under the scenario's weights,
         at ``probabilities``.  The log-ratios, moments and histograms read the view as it lies, thinned or
-        stacked; the quantiles read one parameter as one stride, so a thinned chain or one chain of a stacked sampler is
-        first copied to a dense device buffer, as ``marginals`` does.  Stacked samplers take ``chain=<index>``."""
-        import torch
+        stacked; the quantiles read one parameter as one stride, so a view of several strided blocks is first copied to
+        a dense device buffer, as ``marginals`` does.  Stacked samplers take ``chain=<index>``."""
         from . import reweight as RW
         if priors is None and models_new is None:
             raise ValueError("pass priors, models_new or both")
-        src, n_blocks, nw, stride, S = self._stored_view(discard, thin, chain)
-        lower, upper = self._box_or_prior(lower, upper)
-        d = self.d
-        view = (self.device, src, n_blocks, nw, stride, S)
+        rows = self._stored_view(discard, thin, chain)
+        lower, upper = self._box_or_prior(self.models, lower, upper)
         L, log_norm = None, None
         if priors is not None:
-            tables = RW.check_priors(priors, d, lower, upper)
-            L = RW.log_prior_dev(self.device, src, n_blocks, nw, stride, d, tables, np.asarray(lower, dtype=np.float64))
+            tables = RW.check_priors(priors, self.d, lower, upper)
+            L = RW.log_prior_dev(self.device, *rows.layout, self.d, tables, np.asarray(lower, dtype=np.float64))
             if models_new is None:
                 log_norm = RW.log_prior_norm(*tables, lower, upper)
         if models_new is not None:
-            D = RW.data_log_ratio_dev(self.models, models_new, view, self._data_chain(chain))
+            D = RW.data_log_ratio_dev(self.models, models_new, rows, self._data_chain(chain))
             L = D if L is None else L + D
-        dense = None
-        if stride != nw:
-            dense = torch.empty((S, d), dtype=torch.float64, device=torch.device("cuda", self.device))
-            check(_lib.lib().gpemu_marginal_dense_dev(self.device, C.c_void_p(src), n_blocks, nw, stride, d,
-                                                      C.c_void_p(dense.data_ptr()), _lib.current_stream(self.device)))
-        whole = thin == 1 and nw == self.W      # else a thinned or stacked view: the same reduction, uniform weights
         extra = None
         if posterior_predictive:
-            pp_models = self.models if models is None else list(models)
-            for m in pp_models:
-                if m.d != self.d or m.device != self.device:
-                    raise ValueError("model and sampler differ in parameters or device")
+            pp_models = self._models(models)
             probs = summary_kw.get("probabilities", (0.05, 0.5, 0.95))
-            extra = lambda q, Q: RW.bands_of_view(pp_models, view, q, Q, probs, summary_kw.get("workspace_bytes", 0))
-        return RW.summary_view(view, d, L, lower, upper, log_norm=log_norm,
-                               baseline=(lambda: self.chain_moments(discard)) if whole else None,
-                               column_src=None if dense is None else dense.data_ptr(), extra=extra, **summary_kw)
+            extra = lambda q, Q: RW.bands_of_view(pp_models, rows, q, Q, probs, summary_kw.get("workspace_bytes", 0))
+        return RW.summary_view(rows, L, lower, upper, log_norm=log_norm, baseline=self._baseline(discard, thin, rows),
+                               extra=extra, **summary_kw)
 
-    def _box_or_prior(self, lower, upper):
-        """``(lower, upper)``, each defaulting to the prior box of the sampler's models."""
+    @staticmethod
+    def _box_or_prior(models, lower, upper):
+        """``(lower, upper)``, each defaulting to the prior box of ``models`` (``reweight.chain_reweight`` calls this too)."""
         if lower is None or upper is None:
-            box = getattr(self.models[0], "prior_box", None)
+            box = getattr(models[0], "prior_box", None)
             if box is None:
                 raise ValueError("no prior box is known (likelihood_setup has not been called): pass lower and upper")
             lower, upper = (box[0] if lower is None else lower), (box[1] if upper is None else upper)
@@ -493,10 +444,10 @@ class DeviceSampler:
         stacked.  An ensemble chain repeats states (a rejected move keeps the walker where it was): thin it by its
         autocorrelation time, or pass ``allow_copies``.  Stacked samplers take ``chain=<index>``."""
         from . import information as IG
-        src, n_blocks, nw, stride, _ = self._stored_view(discard, thin, chain)
-        lower, upper = self._box_or_prior(lower, upper)
-        return IG.gain_of_view(self.device, (src, n_blocks, nw, stride), self.d, lower, upper, k=k, subsets=subsets,
-                               max_points=max_points, allow_copies=allow_copies, workspace_bytes=workspace_bytes)
+        rows = self._stored_view(discard, thin, chain)
+        lower, upper = self._box_or_prior(self.models, lower, upper)
+        return IG.gain_of_view(rows, lower, upper, k=k, subsets=subsets, max_points=max_points,
+                               allow_copies=allow_copies, workspace_bytes=workspace_bytes)
 
     def expected_information_gain(self, candidates, discard=0, thin=1, chain=None, n_inner=16384, n_outer=4096, seed=0,
                                   emulator_cov="mean", exclude_self=False, models=None, workspace_bytes=0):
@@ -508,12 +459,9 @@ class DeviceSampler:
         features of ``models`` (default: the sampler's groups) concatenated in their order, the order
         ``emulation.predict`` returns.  Stacked samplers take ``chain=<index>``."""
         from . import experiment as EX, information as IG
-        models = self.models if models is None else list(models)
-        for m in models:
-            if m.d != self.d or m.device != self.device:
-                raise ValueError("model and sampler differ in parameters or device")
-        src, n_blocks, nw, stride, _ = self._stored_view(discard, thin, chain)
-        rows, skipped = IG.unit_rows_dev(self.device, src, n_blocks, nw, stride, self.d, None, None, int(n_inner))
+        models = self._models(models)
+        layout = self._stored_view(discard, thin, chain).layout
+        rows, skipped = IG.unit_rows_dev(self.device, *layout, self.d, None, None, int(n_inner))
         if skipped:
             raise ValueError(f"{skipped} selected rows of the chain have a non-finite coordinate")
         return EX.chain_expected_information_gain(models, rows.cpu().numpy(), candidates, n_outer=n_outer, seed=seed,
@@ -527,17 +475,15 @@ class DeviceSampler:
         a sampler on the same device -- its stored chain ``[discard::thin]``, chain ``other_chain`` (default ``chain``) of
         a stacked one, read in place -- or rows ``(m, d)`` / ``(steps, walkers, d)`` as a host array or a device tensor."""
         from . import information as IG
-        src, n_blocks, nw, stride, _ = self._stored_view(discard, thin, chain)
-        lower, upper = self._box_or_prior(lower, upper)
+        rows = self._stored_view(discard, thin, chain)
+        lower, upper = self._box_or_prior(self.models, lower, upper)
         if isinstance(other, DeviceSampler):
             if other.d != self.d or other.device != self.device:
                 raise ValueError("the two samplers differ in parameters or device")
             oc = other_chain if other_chain is not None else (chain if other.n_chains > 1 else None)
-            osrc, ob, onw, ostride, _ = other._stored_view(discard, thin, oc)
-            other = (osrc, ob, onw, ostride)
-        return IG.divergence_of_views(self.device, (src, n_blocks, nw, stride), other, self.d, lower, upper, k=k,
-                                      subsets=subsets, max_points=max_points, allow_copies=allow_copies,
-                                      workspace_bytes=workspace_bytes)
+            other = other._stored_view(discard, thin, oc)
+        return IG.divergence_of_views(rows, other, lower, upper, k=k, subsets=subsets, max_points=max_points,
+                                      allow_copies=allow_copies, workspace_bytes=workspace_bytes)
 
     def propose_design(self, n_points, candidates=None, n_candidates=2048, n_reference=4096, discard=0, thin=None,
                        chain=None, seed=0, models=None, **kw):
@@ -554,19 +500,18 @@ class DeviceSampler:
         if thin is None:
             steps = self.counts()[2] - int(discard)
             thin = max(1, -(-steps * nw // max(1, int(n_reference))))
-        src, n_blocks, nw, stride, S = self._stored_view(discard, thin, chain)
+        ref = self._stored_view(discard, thin, chain, _lib.current_stream(self.device))
         if candidates is None:
             box = getattr(models[0], "prior_box", None)
             if box is None:
                 raise ValueError("no prior box is known (likelihood_setup has not been called): pass candidates")
             rows = self.get_chain(int(discard))[0][::int(thin), w0:w0 + nw].reshape(-1, self.d)
             candidates = DS.default_candidates(box[0], box[1], rows, n_candidates, seed=seed)
-        ref = DS.DeviceRows(src, n_blocks, nw, stride, stream=_lib.current_stream(self.device))
         kw.setdefault("max_picks", max(int(n_points), 1))
         with DS.Design(models, ref, candidates, **kw) as ds:
             out = ds.select(n_points)
             out["candidates"] = ds.candidates
-        out["thin"], out["n_reference_rows"] = int(thin), S
+        out["thin"], out["n_reference_rows"] = int(thin), ref.rows
         return out
 
     def acf_block(self, lag0, n_lags, first=0, n=None, w0=0, nw=None):

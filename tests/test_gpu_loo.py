@@ -141,8 +141,9 @@ def test_view_forms_equal_the_host_form_bit_for_bit():
     s.run(140)                                  # 2240 rows: more than one predict chunk
     chain, _ = s.get_chain()
     for thin in (1, 3):
-        src, n_blocks, nw, stride, S = s._stored_view(0, thin, None)
-        got = _device_terms(dm, (src, n_blocks, nw, stride), d, S)
+        view = s._stored_view(0, thin, None)
+        S = view.rows
+        got = _device_terms(dm, view.layout, d, S)
         want = dm.loglik_pointwise(chain[::thin].reshape(-1, d))
         print(f"in place, thin {thin}: {S} rows, equal bits: {got.tobytes() == want.tobytes()}")
         assert got.tobytes() == want.tobytes()
@@ -156,8 +157,9 @@ def test_view_forms_equal_the_host_form_bit_for_bit():
         st.set_state(np.random.default_rng(5).uniform(c["lo"], c["hi"], (2 * W, d)))
         st.run(20)
         chain, _ = st.get_chain()
-        src, n_blocks, nw, stride, S = st._stored_view(0, 1, 1)
-        got = _device_terms(dm, (src, n_blocks, nw, stride), d, S, chain=1)
+        view = st._stored_view(0, 1, 1)
+        S = view.rows
+        got = _device_terms(dm, view.layout, d, S, chain=1)
         rows = chain[:, W:].reshape(-1, d)
         assert got.tobytes() == dm.loglik_pointwise(rows, chain=1).tobytes()
         assert got.tobytes() != dm.loglik_pointwise(rows, chain=0).tobytes()

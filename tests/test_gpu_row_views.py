@@ -79,6 +79,28 @@ def test_one_view_four_summaries(discard, thin, chain):
     _same_marginals(got, rows, lo, hi, (9, 4), (0.5, 0.9), 17)
 
 
+def test_a_single_block_of_a_stacked_chain_is_read_where_it_lies():
+    """The last step of chain 1: 8 rows in one block of a 16-walker ensemble.  One block is dense by ``RowsView::dense()``
+    whatever its stride, so the sort and the density read the chain itself, no dense copy.  The two summaries that accept 8
+    rows (the diagnostics need 8 steps; confidence 0.9 leaves int(0.1 * 8) = 0 rows outside and is refused)."""
+    from test_gpu_marginals import _same_marginals
+    from test_gpu_posterior_predictive import _same
+    s, dm, full, lo, hi = _stacked()
+    discard, thin, chain = STEPS - 1, 1, 1
+    view = s._stored_view(discard, thin, chain)
+    assert (view.n_blocks, view.block_rows, view.rows) == (1, WC, WC) and WC < s.W
+    assert view.dense and view.columns() is view
+    rows = np.ascontiguousarray(full[discard::thin][:, chain * WC:(chain + 1) * WC]).reshape(-1, lo.size)
+    assert rows.shape[0] == WC
+
+    got = s.posterior_predictive(discard=discard, thin=thin, chain=chain, probabilities=PROBS)
+    assert len(got) == 1
+    _same(dm.posterior_predictive(rows, probabilities=PROBS), got[0])
+
+    got = s.marginals(bins_1d=9, bins_2d=4, confidence=(0.5, 0.75), n_grid=17, discard=discard, thin=thin, chain=chain)
+    _same_marginals(got, rows, lo, hi, (9, 4), (0.5, 0.75), 17)
+
+
 def test_views_without_steps_or_outside_the_chains_are_refused():
     s = _stacked()[0]
     calls = (s.posterior_predictive, lambda **kw: s.parameter_quantiles(PROBS, **kw), s.diagnostics, s.marginals)

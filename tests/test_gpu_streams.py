@@ -129,10 +129,11 @@ def _w_pointwise(st, T, out, P, dm):
 def _w_data_log_ratio(st, T, out, P, dm):
     """reweight.data_log_ratio_dev: the model against a second handle of the same emulators with other data"""
     from gpemu import reweight
+    from gpemu.rows import DeviceRows
     nb, br, bs = SC.VIEW
     if getattr(dm, "other_data", None) is None:        # (made by the quiet run, closed by _sweep)
         dm.other_data = R.fresh(P, dict(P.setup, y_exp=P.Y[1].copy()))
-    return (reweight.data_log_ratio_dev([dm], [dm.other_data], (0, T["X"].data_ptr(), nb, br, bs, nb * br)),)
+    return (reweight.data_log_ratio_dev([dm], [dm.other_data], DeviceRows(T["X"].data_ptr(), nb, br, bs, device=0)),)
 
 
 def _w_design(st, T, out, P, dm):

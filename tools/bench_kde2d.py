@@ -49,6 +49,7 @@ def main():
     from bench_marginals import synthetic_chain, timed
     from gpemu import _lib
     from gpemu import marginals as M
+    from gpemu.rows import DeviceRows
     if _lib.device_count() <= 0 or not torch.cuda.is_available():
         raise SystemExit("bench_kde2d: no GPU visible; nothing is measured without one")
     G, W = args.n_grid, args.walkers
@@ -60,22 +61,23 @@ def main():
         for thin in args.thin:
             nb = args.steps // thin
             S, P = nb * W, d * (d - 1) // 2
-            view = (0, base, nb, W, thin * W, d)
+            rows = DeviceRows(base, nb, W, thin * W, device=0, d=d)
+            flat = (0, *rows.layout, d)                     # as the wrappers of one C prototype take them
             rec = {"steps": args.steps, "walkers": W, "d": d, "thin": thin, "samples": S, "pairs": P, "n_grid": G,
                    "covariance": args.covariance, "reps": args.reps}
             c0 = M.kde2d_path_counts()
-            res = M._kde2d_view(*view, covariance=args.covariance, n_grid=G)
+            res = M._kde2d_view(rows, covariance=args.covariance, n_grid=G)
             c1 = M.kde2d_path_counts()
             rec["launches"] = {k: c1[k] - c0[k] for k in c1}
             plan = {k: res[k] for k in ("pairs", "shear", "bandwidth", "grid_a", "grid_b")}
 
             def plan_only():
-                M._pair_moments_dev(*view)
-                M._pair_moments_dev(*view, np.concatenate([plan["pairs"][:, ::-1], plan["pairs"]]),
+                M._pair_moments_dev(*flat)
+                M._pair_moments_dev(*flat, np.concatenate([plan["pairs"][:, ::-1], plan["pairs"]]),
                                     np.concatenate([np.zeros(P), plan["shear"]]), moments=False)
             rec["plan"] = timed(plan_only, args.reps)
-            rec["density"] = timed(lambda: M._kde2d_dev(*view, plan), args.reps)
-            rec["total"] = timed(lambda: M._kde2d_view(*view, covariance=args.covariance, n_grid=G), max(1, args.reps // 2))
+            rec["density"] = timed(lambda: M._kde2d_dev(*flat, plan), args.reps)
+            rec["total"] = timed(lambda: M._kde2d_view(rows, covariance=args.covariance, n_grid=G), max(1, args.reps // 2))
             flop = 2.0 * P * gpad * gpad * S
             rec["mfma_flop"] = flop
             rec["mfma_floor_s"] = flop / (args.mfma_tflops * 1e12)
