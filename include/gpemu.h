@@ -24,6 +24,11 @@
  *     The *_dev entries of the weighted chain summaries take their stream and their workspace limit
  *     together, in a gpemu_call_ctx; their section says what a NULL stream means, and each of them waits for its stream
  *     before it returns.
+ *   - A call writes only the elements of its outputs that its section names.  It does not write padding (ld > n),
+ *     gaps of a strided view, or anything before or after.  It does not write its inputs.  Its results do not depend
+ *     on the previous contents of the outputs or on memory beside the inputs.  A declined call writes nothing.  (A
+ *     section that leaves elements of an output unwritten says which.)  Pointers need the natural alignment of their
+ *     element type, 8 bytes for double and int64, and no more.  tests/guard_cases.py holds every *_dev entry to this.
  *   - Every function returns int: 0 = ok, <0 = argument / runtime error, >0 = numerical failure
  *     (e.g. index+1 of a non-positive Cholesky pivot).  gpemu_last_error() gives the thread-local
  *     message of the last failure.
@@ -130,7 +135,11 @@ int gpemu_gp_sample(gpemu_model *m, int64_t M, const double *X, int64_t n_draws,
                     double *draws_out, double *tau_out);
 
 /* ref: emulation.py:466-548 (predict_emulation_group): central_value[B*F], cov[B*F*F];
- * n_div = the reference's n_samples divisor of the truncation covariance (emulation.py:531-532). */
+ * n_div = the reference's n_samples divisor of the truncation covariance (emulation.py:531-532).
+ * _dev: where dcov is 16-byte aligned and F is even (F <= 512, k <= 16) the covariances are written by the matrix-core
+ * writer, which stores two doubles at a time; otherwise by the row-wise writer.  The two add in another order and
+ * differ in the last place, so the bits of cov depend on dcov's alignment modulo 16 (and on nothing else
+ * about the pointer).  An 8-byte aligned dcov is not declined. */
 int gpemu_predict_full(gpemu_model *m, int64_t B, const double *X, double n_div, double *cv_out,
                        double *cov_out);
 int gpemu_predict_full_dev(gpemu_model *m, int64_t B, const double *dX, double n_div, double *dcv,

@@ -3,9 +3,10 @@ in a ``const gpemu_call_ctx *``, and the gate that makes a launch on the wrong s
 (tests/test_gpu_streams.py, tests/test_streams_host.py).
 
 A row names the entry, its family, the header's own words on what NULL means for it and on whether it waits, and a
-closure ``run(st, T, out, P, dm) -> tuple`` that calls it at a small fixed shape: ``st`` the ``void *`` to pass, ``T``
-the device inputs (torch tensors by name, as ``inputs(P, seed)`` made them), ``out(shape, dtype)`` the allocator of the
-device outputs, ``P`` / ``dm`` the problem of tests/reuse_cases.py and its model handle (None for the device-wide rows).
+closure ``run(st, T, out, P, dm) -> tuple`` that calls it at a small shape -- the module's constants, which ``shaped``
+rebinds to a ``Shape`` for the guard sweep of tests/guard_cases.py: ``st`` the ``void *`` to pass, ``T``
+the device inputs (torch tensors by name, as ``inputs(P, seed)`` made them), ``out(shape, dtype, ld)`` the allocator of
+the device outputs and ``out.host(shape, dtype)`` of the host outputs, ``P`` / ``dm`` the problem of tests/reuse_cases.py and its model handle (None for the device-wide rows).
 The closure returns device tensors (read on the stream under test) and host arrays.
 
 The gate (``gated``): the device inputs hold a decoy -- finite, in-box, valid values of another seed -- and the outputs
@@ -29,6 +30,8 @@ import ctypes as C
 import os
 import re
 import time
+from contextlib import contextmanager
+import dataclasses
 from dataclasses import dataclass
 
 import numpy as np
@@ -44,6 +47,66 @@ S_WIDE = 257                              # one past the 256-row tiles of the de
 D_WIDE = 3
 VIEW = (16, 4, 6)                         # a chain view: 16 steps x 4 walkers, steps 6 rows apart
 B_SMALL, B_BIG = 33, 130                  # at and just past the tile and half-step limits of the launch paths
+
+M2_COV = 17                               # gpemu_gp_predict_cov_dev: the columns of the rectangular call
+A16 = False                               # the guard arena: arrays 16-byte aligned (else 8-byte, not 16-byte)
+PAD = 0                                   # what an output's leading dimension exceeds its row length by (the guard sweep)
+
+
+
+@dataclass(frozen=True)
+class Shape:
+    """The sizes the closures of this table are called at.  The defaults are the module's constants above: what the
+    stream, allocation and reuse gates run.  ``shaped(sh)`` rebinds the constants for the guard sweep of
+    tests/guard_cases.py, which calls every row at the ``edge_shapes`` beside it."""
+    S: int = S_WIDE
+    D: int = D_WIDE
+    VIEW: tuple = VIEW
+    B_SMALL: int = B_SMALL
+    B_BIG: int = B_BIG
+    RW: int = 2
+    M2: int = M2_COV
+    pad: int = PAD
+    a16: bool = A16
+
+    def __str__(self):
+        d = Shape()
+        diff = [f"{k}={getattr(self, k)}" for k in self.__dataclass_fields__ if getattr(self, k) != getattr(d, k)]
+        return ",".join(diff).replace(" ", "") or "default"
+
+
+# ---- the edge shapes of the guard sweep: one below, at and one above every tile, chunk and wave size of the kernels ---
+def _S(*sizes, **kw):
+    return tuple(Shape(S=s, **kw) for s in sizes)
+
+
+# a wave (64 lanes), the 256-thread workgroups and 256-row tiles of the device-wide kernels (rows_dev.h RK_BINS /
+# SEL_BINS, k_knn.hip's 256-query tiles, GPEMU_KNN_REF_TILE), and d = 1, 3 (the default), 16 = the widest row
+S_EDGES = _S(1, 2, 63, 64, 65, 255, 256, 257)
+D_EDGES = (Shape(S=65, D=1), Shape(S=65, D=16), Shape(S=257, D=16))
+# the radix sort and select work on 2048 keys per workgroup (rows_dev.h RK_TILE; k_marginal.hip WH_SCAN, the weighted
+# HPD's prefix sum; GPEMU_PAIRLSE_CHUNK columns of Z)
+S_CHUNK_2048 = _S(2047, 2048, 2049)
+# partial sums over 4096 samples (k_loo.hip LOO_SUM, k_reweight.hip RW_SUM, rows_dev.h WS_SUM, k_select.hip SEL_SLICE,
+# k_marginal.hip HW_PER windows)
+S_CHUNK_4096 = _S(4095, 4096, 4097)
+# 8192 samples per partial sum of the densities (k_marginal.hip KD_CHUNK, k_kde2d.hip K2_CHUNK), staged 1024 at a time
+# (KD_STAGE); rows_dev.h MOM_ROWS and k_knn.hip LS_ROWS = 1024 rows per partial of the moments and the log sums
+S_CHUNK_1024 = _S(1023, 1024, 1025)
+S_CHUNK_8192 = _S(8191, 8192, 8193)
+# rows of a model: the 32-row cross-kernel form and KSTAR_SMALL_MAX = 128 (internal.h), TM = 64 rows per item
+# (sched_host.h), TILE = 128, PC_NB = 64 (pcov_dev.h), k_design.hip T = 64: tests/reuse_cases.py LOGPOST_B is the precedent
+B_EDGES = tuple(Shape(B_SMALL=b, B_BIG=b) for b in (1, 31, 32, 33, 63, 64, 65, 127, 128, 129))
+# gpemu_gp_predict_cov_dev: M2 = 1, below, at and above M1, on both sides of PC_NB = 64 (pcov_dev.h)
+PCOV_EDGES = tuple(Shape(B_SMALL=m1, B_BIG=m1, M2=m2) for m1, m2 in
+                   ((1, 1), (31, 33), (32, 32), (33, 1), (33, 32), (63, 65), (64, 64), (65, 63), (65, 1), (127, 129),
+                    (128, 128), (129, 127)))
+# views: contiguous, nb*br no multiple of 64 (a wave), today's, and one of 68 rows with gaps of 5 rows between the blocks
+VIEW_EDGES = tuple(Shape(VIEW=v) for v in ((1, 1, 1), (3, 5, 5), (16, 4, 6), (17, 4, 9)))
+WIDE_S = S_EDGES + D_EDGES
+WIDE_V = S_EDGES                          # (rows that take value rows V and no d)
+PADS = (1, 7)                             # ld = n + 1 and n + 7: the paddings of the outputs with a leading dimension
+
 
 MODEL_BOUND, DEVICE_WIDE, HANDLE_CREATING, SAMPLER_COMM = "model-bound", "device-wide", "handle-creating", "sampler/comm"
 
@@ -96,6 +159,11 @@ class Row:
     run: object = None                    # (st, T, out, P, dm) -> tuple of device tensors and host arrays
     cases: tuple = ()                     # model-bound: the problems of reuse_cases it runs on
     omitted: str = ""                     # why the GPU sweep leaves it out
+    edge_shapes: tuple = ()               # the Shapes of the guard sweep (tests/guard_cases.py), beside today's
+    out_ld: tuple = ()                    # the ld* / stride parameters of the prototype that belong to an OUTPUT
+    gaps: tuple = ()                      # the inputs that are rows of a VIEW: the rows between its blocks are not read
+    by_alignment: bool = False            # it picks a launch path by the 16-byte alignment of an output: swept at both
+    unwritten: object = None              # (k, shape) -> mask of the elements of the k-th output the header says stay
 
 
 def _vp(x):
@@ -114,9 +182,13 @@ def _L():
     return _lib.lib()
 
 
+CALLS_OK = [0]                            # the library calls of the closures that returned GPEMU_OK so far
+
+
 def _ck(code):
     from gpemu import _lib
     _lib.check(code)
+    CALLS_OK[0] += 1
 
 
 def _rng(seed, tag):
@@ -129,8 +201,8 @@ f64 = lambda v: np.ascontiguousarray(np.asarray(v, dtype=np.float64))
 
 
 # ---- device-wide rows: S_WIDE rows of D_WIDE parameters in the unit box -----------------------------------------------
-def _unit_rows(seed, tag, n=S_WIDE, d=D_WIDE, lo=0.1):
-    return _rng(seed, tag).uniform(lo, 1.0, (n, d))
+def _unit_rows(seed, tag, n=None, d=None, lo=0.1):
+    return _rng(seed, tag).uniform(lo, 1.0, (S_WIDE if n is None else n, D_WIDE if d is None else d))
 
 
 def _in_X(P, seed):
@@ -139,7 +211,7 @@ def _in_X(P, seed):
 
 def _in_V(P, seed):
     """R = 3 rows of S values (the parameters of the rows above, one parameter per row)"""
-    return {"V": np.ascontiguousarray(_unit_rows(seed, "V").T)}
+    return {"V": np.ascontiguousarray(_unit_rows(seed, "V", d=3).T)}
 
 
 def _in_view(P, seed):
@@ -147,12 +219,28 @@ def _in_view(P, seed):
     return {"X": _unit_rows(seed, "view", nb * bs)}
 
 
-EDGES1 = np.ascontiguousarray(np.tile(np.linspace(0.0, 1.0, 9), (D_WIDE, 1)))
-EDGES2 = np.ascontiguousarray(np.tile(np.linspace(0.0, 1.0, 5), (D_WIDE, 1)))
+def _edges(nb, d):
+    return np.ascontiguousarray(np.tile(np.linspace(0.0, 1.0, nb + 1), (d, 1)))
+
+
+EDGES1, EDGES2 = _edges(8, D_WIDE), _edges(4, D_WIDE)
+
+
+def _n_pairs():
+    return D_WIDE * (D_WIDE - 1) // 2
+
+
+def _fixed_weights(g, rows, n, log2_total):
+    """rows of n integer weights whose total lies in [2^log2_total, 2^(log2_total + 1)) whatever the seed and n: drawn
+    from [lo, 2 lo) with lo = 2^log2_total / 2^floor(log2 n), and halved where the total reaches the upper end"""
+    lo = 2 ** (log2_total - (int(n).bit_length() - 1))
+    q = g.integers(lo, 2 * lo, (rows, n)).astype(np.int64)
+    q[q.sum(axis=1) >= 2 ** (log2_total + 1)] >>= 1
+    return q
 
 
 def _select(st, T, out, P, dm):
-    ranks = i64(0, 128, 256)
+    ranks = i64(0, S_WIDE // 2, S_WIDE - 1)
     o = out((3, 3))
     _ck(_L().gpemu_select_dev(0, 3, S_WIDE, _vp(T["V"]), S_WIDE, 1, 3, _vp(ranks), _vp(o), _vp(st)))
     return (o,)
@@ -166,14 +254,16 @@ def _rank(st, T, out, P, dm):
 
 def _hist(st, T, out, P, dm):
     import torch
-    h1, h2, ni = out((D_WIDE, 8), torch.int64), out((3, 4, 4), torch.int64), out((D_WIDE,), torch.int64)
+    h1 = out((D_WIDE, 8), torch.int64)
+    h2 = out((_n_pairs(), 4, 4), torch.int64) if D_WIDE > 1 else None          # (NULL allowed for d = 1)
+    ni = out((D_WIDE,), torch.int64)
     _ck(_L().gpemu_marginal_hist_dev(0, _vp(T["X"]), 1, S_WIDE, S_WIDE, D_WIDE, 8, _vp(EDGES1), 4, _vp(EDGES2), 0,
                                      _vp(h1), _vp(h2), _vp(ni), _vp(st)))
-    return h1, h2, ni
+    return tuple(a for a in (h1, h2, ni) if a is not None)
 
 
 def _hpd(st, T, out, P, dm):
-    n_out = i64(26, 1)
+    n_out = i64(max(1, (S_WIDE + 5) // 10), 1)
     o = out((3, 2, 2))
     _ck(_L().gpemu_hpd_dev(0, 3, S_WIDE, _vp(T["V"]), S_WIDE, 1, 2, _vp(n_out), _vp(o), 0, _vp(st)))
     return (o,)
@@ -196,12 +286,17 @@ def _dense(st, T, out, P, dm):
 
 
 def _moments(st, T, out, P, dm):
-    mean, var = np.full(D_WIDE, np.nan), np.full(D_WIDE, np.nan)
+    mean, var = out.host((D_WIDE,)), out.host((D_WIDE,))
     _ck(_L().gpemu_marginal_moments_dev(0, _vp(T["X"]), S_WIDE, D_WIDE, _vp(mean), _vp(var), _vp(st)))
     return mean, var
 
 
-_PAIRS, _SHEAR = i64(0, 1, 2, 0), f64([0.1, -0.2])
+_SHEAR = f64([0.1, -0.2])
+
+
+def _pairs():
+    """(0, 1) and (d - 1, 0); with d = 1 there is no pair, and the entries decline"""
+    return i64(0, 1, D_WIDE - 1, 0)
 
 
 def _kde2d(st, T, out, P, dm):
@@ -210,14 +305,14 @@ def _kde2d(st, T, out, P, dm):
     ga = np.ascontiguousarray(np.tile(np.linspace(0.0, 1.0, G), (2, 1)))
     gb = np.ascontiguousarray(np.tile(np.linspace(-0.2, 1.2, G), (2, 1)))
     o = out((2, G, G))
-    _ck(_L().gpemu_kde2d_dev(0, _vp(T["X"]), 1, S_WIDE, S_WIDE, D_WIDE, 2, _vp(_PAIRS), _vp(_SHEAR), _vp(bw), G, _vp(ga),
+    _ck(_L().gpemu_kde2d_dev(0, _vp(T["X"]), 1, S_WIDE, S_WIDE, D_WIDE, 2, _vp(_pairs()), _vp(_SHEAR), _vp(bw), G, _vp(ga),
                              _vp(gb), _vp(o), 0, _vp(st)))
     return (o,)
 
 
 def _pair_moments(st, T, out, P, dm):
-    mean, cov, ext = np.full(D_WIDE, np.nan), np.full((D_WIDE, D_WIDE), np.nan), np.full((2, 2), np.nan)
-    _ck(_L().gpemu_pair_moments_dev(0, _vp(T["X"]), 1, S_WIDE, S_WIDE, D_WIDE, _vp(mean), _vp(cov), 2, _vp(_PAIRS),
+    mean, cov, ext = out.host((D_WIDE,)), out.host((D_WIDE, D_WIDE)), out.host((2, 2))
+    _ck(_L().gpemu_pair_moments_dev(0, _vp(T["X"]), 1, S_WIDE, S_WIDE, D_WIDE, _vp(mean), _vp(cov), 2, _vp(_pairs()),
                                     _vp(_SHEAR), _vp(ext), _vp(st)))
     return mean, cov, ext
 
@@ -250,24 +345,24 @@ def _weighted_moments(st, T, out, P, dm):
 
 
 def _group_rows(st, T, out, P, dm):
-    o = out((2, S_WIDE))
+    o = out((2, S_WIDE), ld=S_WIDE + PAD)
     _ck(_L().gpemu_loo_group_rows_dev(0, 3, S_WIDE, _vp(T["V"]), S_WIDE, 2, _vp(i64(0, 2, 3)), _vp(i64(0, 1, 2)), _vp(o),
-                                      S_WIDE, _vp(st)))
+                                      S_WIDE + PAD, _vp(st)))
     return (o,)
 
 
 def _unit(st, T, out, P, dm):
-    lo, hi = f64([0.0, 0.05, 0.1]), f64([1.0, 1.5, 2.0])
+    lo, hi = f64(0.05 * np.arange(D_WIDE)), f64(1.0 + 0.5 * np.arange(D_WIDE))
     o = out((S_WIDE, D_WIDE))
-    skipped = C.c_int64(-1)
+    skipped = out.host((1,), np.int64)
     _ck(_L().gpemu_unit_rows_dev(0, _vp(T["X"]), 1, S_WIDE, S_WIDE * D_WIDE, D_WIDE, _vp(lo), _vp(hi), S_WIDE, _vp(o),
-                                 C.byref(skipped), _vp(st)))
-    return o, np.array([skipped.value])
+                                 skipped.ctypes.data_as(C.POINTER(C.c_int64)), _vp(st)))
+    return o, skipped
 
 
 def _knn_dist(st, T, out, P, dm):
     import torch
-    masks = np.array([0b111, 0b001], dtype=np.uint32)
+    masks = np.array([(1 << min(D_WIDE, 3)) - 1, 0b001], dtype=np.uint32)
     r2, zeros = out((2, S_WIDE)), out((2, S_WIDE), torch.int32)
     _ck(_L().gpemu_knn_dist_dev(0, S_WIDE, S_WIDE, D_WIDE, _vp(T["X"]), None, 2, _vp(masks), 4, 0, 0, _vp(r2), _vp(zeros),
                                 _vp(st)))
@@ -280,7 +375,7 @@ def _in_r2(P, seed):
 
 
 def _knn_logsum(st, T, out, P, dm):
-    counts, sums = np.full(6, -1, dtype=np.int64), np.full(4, np.nan)
+    counts, sums = out.host((6,), np.int64), out.host((4,))
     _ck(_L().gpemu_knn_logsum_dev(0, 2, S_WIDE, _vp(T["r2"]), _vp(T["zeros"]), None, _vp(counts), _vp(sums), _vp(st)))
     return counts, sums
 
@@ -304,11 +399,11 @@ def _centre(st, T, out, P, dm):
 
 
 def _logprior(st, T, out, P, dm):
-    kind = np.array([[0, 1, 2], [3, 2, 0]], dtype=np.int32)
-    a, b, lower = np.full((2, 3), 0.5), np.full((2, 3), 0.3), np.full(3, 0.1)
-    o = out((2, S_WIDE))
+    kind = np.ascontiguousarray(np.array([[0, 1, 2], [3, 2, 0]], dtype=np.int32)[:, np.arange(D_WIDE) % 3])
+    a, b, lower = np.full((2, D_WIDE), 0.5), np.full((2, D_WIDE), 0.3), np.full(D_WIDE, 0.1)
+    o = out((2, S_WIDE), ld=S_WIDE + PAD)
     _ck(_L().gpemu_logprior_dev(0, _vp(T["X"]), 1, S_WIDE, S_WIDE, D_WIDE, 2, _vp(kind), _vp(a), _vp(b), _vp(lower), _vp(o),
-                                S_WIDE, _vp(st)))
+                                S_WIDE + PAD, _vp(st)))
     return (o,)
 
 
@@ -328,15 +423,16 @@ def _in_lw(P, seed):
 
 def _weights_fixed(st, T, out, P, dm):
     import torch
-    q, Q = out((2, S_WIDE), torch.int64), out((2,), torch.int64)
-    _ck(_L().gpemu_weights_fixed_dev(0, 2, S_WIDE, _vp(T["lw"]), S_WIDE, _vp(q), S_WIDE, _vp(Q), _vp(st)))
+    q, Q = out((2, S_WIDE), torch.int64, ld=S_WIDE + PAD), out((2,), torch.int64)
+    _ck(_L().gpemu_weights_fixed_dev(0, 2, S_WIDE, _vp(T["lw"]), S_WIDE, _vp(q), S_WIDE + PAD, _vp(Q), _vp(st)))
     return q, Q
 
 
 def _in_Vq(P, seed):
-    """values and fixed-point weights in [2^39, 2^40): a row's total lies in [2^47, 2^48) whatever the seed"""
-    q = _rng(seed, "q").integers(2 ** 39, 2 ** 40, (1, S_WIDE)).astype(np.int64)
-    return {"V": np.ascontiguousarray(_unit_rows(seed, "V").T), "X": _unit_rows(seed, "X"), "q": q}
+    """values and fixed-point weights (at S = 257 in [2^39, 2^40)): a row's total lies in [2^47, 2^48) whatever the
+    seed and S"""
+    q = _fixed_weights(_rng(seed, "q"), 1, S_WIDE, 47)
+    return {"V": np.ascontiguousarray(_unit_rows(seed, "V", d=3).T), "X": _unit_rows(seed, "X"), "q": q}
 
 
 def _weighted_select(st, T, out, P, dm):
@@ -349,10 +445,12 @@ def _weighted_select(st, T, out, P, dm):
 
 def _weighted_hist(st, T, out, P, dm):
     import torch
-    h1, h2, wi = out((1, D_WIDE, 8), torch.int64), out((1, 3, 4, 4), torch.int64), out((1, D_WIDE), torch.int64)
+    h1 = out((1, D_WIDE, 8), torch.int64)
+    h2 = out((1, _n_pairs(), 4, 4), torch.int64) if D_WIDE > 1 else None       # (NULL allowed for d = 1)
+    wi = out((1, D_WIDE), torch.int64)
     _ck(_L().gpemu_weighted_hist_dev(0, _vp(T["X"]), 1, S_WIDE, S_WIDE, D_WIDE, 1, _vp(T["q"]), S_WIDE, 8, _vp(EDGES1), 4,
                                      _vp(EDGES2), 0, _vp(h1), _vp(h2), _vp(wi), _vp(st)))
-    return h1, h2, wi
+    return tuple(a for a in (h1, h2, wi) if a is not None)
 
 
 # the weighted chain summaries take their stream in a ``gpemu_call_ctx``; a run is built from a
@@ -371,14 +469,20 @@ def _ctx_ref(ctx_of, st):
 
 
 def _in_Vq2(P, seed):
-    """3 value rows and 2 rows of fixed-point weights in [2^39, 2^40): a row's total lies in [2^47, 2^48)"""
-    q = _rng(seed, "wq").integers(2 ** 39, 2 ** 40, (RW2, S_WIDE)).astype(np.int64)
-    return {"V": np.ascontiguousarray(_unit_rows(seed, "wV").T), "q": q}
+    """3 value rows and RW2 rows of fixed-point weights (at S = 257 in [2^39, 2^40)): a row's total lies in
+    [2^47, 2^48)"""
+    q = _fixed_weights(_rng(seed, "wq"), RW2, S_WIDE, 47)
+    return {"V": np.ascontiguousarray(_unit_rows(seed, "wV", d=3).T), "q": q}
 
 
-_W_TARGETS = np.ascontiguousarray(np.tile(np.array([1, 2 ** 45, 2 ** 47], dtype=np.uint64), (RW2, 1)))
-_W_GRID = np.ascontiguousarray(np.tile(np.linspace(0.0, 1.1, 9), (RW2 * 3, 1)))
-_W_H = np.full(RW2 * 3, 0.05)
+def _w_tables(rw):
+    """per weight row: the targets of the device-wide rows, the grids and bandwidths, the targets of the view rows"""
+    return (np.ascontiguousarray(np.tile(np.array([1, 2 ** 45, 2 ** 47], dtype=np.uint64), (rw, 1))),
+            np.ascontiguousarray(np.tile(np.linspace(0.0, 1.1, 9), (rw * 3, 1))), np.full(rw * 3, 0.05),
+            np.ascontiguousarray(np.tile(np.array([1, 2 ** 44, 2 ** 45], dtype=np.uint64), (rw, 1))))
+
+
+_W_TARGETS, _W_GRID, _W_H, _W_VIEW_TARGETS = _w_tables(RW2)
 
 
 def weighted_hpd_run(ctx_of):
@@ -415,10 +519,10 @@ def _diag_create(st, T, out, P, dm):
     try:
         res = []
         for kind in (1, 2):                             # RANK_Z, FOLDED_RANK_Z
-            gm, mv, vm = (np.full(D_WIDE, np.nan) for _ in range(3))
+            gm, mv, vm = (out.host((D_WIDE,)) for _ in range(3))
             _ck(L.gpemu_diag_transform(h, kind, 0.0, _vp(gm), _vp(mv), _vp(vm)))
             res += [gm, mv, vm]
-        pooled = [np.full(D_WIDE, np.nan) for _ in range(5)]
+        pooled = [out.host((D_WIDE,)) for _ in range(5)]
         _ck(L.gpemu_diag_pooled(h, *[_vp(a) for a in pooled]))
         return tuple(res + pooled)
     finally:
@@ -431,7 +535,8 @@ def _tag(seed):
 
 
 def _in_rows(B, tag):
-    return lambda P, seed: {"X": R.rows(P, tag + _tag(seed), B)}
+    """B: the number of rows when the inputs are made (a closure over the shape in force)"""
+    return lambda P, seed: {"X": R.rows(P, tag + _tag(seed), B())}
 
 
 def _in_logpost(P, seed):
@@ -456,7 +561,7 @@ def _gp_predict(st, T, out, P, dm):
 
 
 def _gp_predict_cov(st, T, out, P, dm):
-    M1, M2 = B_SMALL, 17
+    M1, M2 = B_SMALL, M2_COV
     mean, cov, sym = out((M1, P.k)), out((P.k, M1, M2)), out((P.k, M1, M1))
     X = T["X"]
     _ck(_L().gpemu_gp_predict_cov_dev(dm.handle, M1, _vp(X), M2, _vp(X[M1:]), 0, _vp(mean), _vp(cov), _vp(st)))
@@ -500,7 +605,7 @@ def _logpost_grad(st, T, out, P, dm):
 
 def _postpred(st, T, out, P, dm):
     nb, br, bs = VIEW
-    ranks = i64(0, 31, 63)
+    ranks = i64(0, (nb * br - 1) // 2, nb * br - 1)
     o = [out((P.F,)), out((P.F,)), out((P.F,)), out((P.F, 3))]
     _ck(_L().gpemu_posterior_predictive_dev(dm.handle, _vp(T["X"]), nb, br, bs, 3, _vp(ranks), 0, *[_vp(a) for a in o],
                                             _vp(st)))
@@ -510,11 +615,8 @@ def _postpred(st, T, out, P, dm):
 def in_weighted_view(P, seed):
     """the rows of a chain view and 2 rows of fixed-point weights, one weight per row of the view"""
     nb, br, bs = VIEW
-    q = _rng(seed, "wq_view").integers(2 ** 39, 2 ** 40, (RW2, nb * br)).astype(np.int64)
+    q = _fixed_weights(_rng(seed, "wq_view"), RW2, nb * br, 45)          # (16 x 4 rows: in [2^39, 2^40))
     return dict(_in_model_view(P, seed), q=q)
-
-
-_W_VIEW_TARGETS = np.ascontiguousarray(np.tile(np.array([1, 2 ** 44, 2 ** 45], dtype=np.uint64), (RW2, 1)))
 
 
 def weighted_bands_run(ctx_of):
@@ -533,13 +635,14 @@ def _in_AB(P, seed):
 
 
 def _sobol(st, T, out, P, dm):
-    return R.flatten(dm.sobol_moments_dev(T["A"].data_ptr(), T["B"].data_ptr(), B_SMALL, n_batches=2, stream=int(st)))
+    return R.flatten(dm.sobol_moments_dev(T["A"].data_ptr(), T["B"].data_ptr(), B_SMALL, n_batches=min(2, B_SMALL),
+                                          stream=int(st)))
 
 
 def _pointwise(st, T, out, P, dm):
     nb, br, bs = VIEW
-    o = out((dm.n_observable_blocks, nb * br))
-    _ck(_L().gpemu_loglik_pointwise_dev(dm.handle, 0, _vp(T["X"]), nb, br, bs, _vp(o), nb * br, _vp(st)))
+    o = out((dm.n_observable_blocks, nb * br), ld=nb * br + PAD)
+    _ck(_L().gpemu_loglik_pointwise_dev(dm.handle, 0, _vp(T["X"]), nb, br, bs, _vp(o), nb * br + PAD, _vp(st)))
     return (o,)
 
 
@@ -557,7 +660,7 @@ def _design_create(st, T, out, P, dm):
     _ck(L.gpemu_design_create_dev(C.byref(h), dm.handle, _vp(T["ref"]), nb, br, bs, None, 70, _vp(T["cand"]), _vp(pcw),
                                   None, 1e-6, 4, 0, _vp(st)))
     try:
-        s0, s1, iv, den = np.full(70, np.nan), np.full(70, np.nan), np.full(P.k, np.nan), np.full((P.k, 70), np.nan)
+        s0, s1, iv, den = out.host((70,)), out.host((70,)), out.host((P.k,)), out.host((P.k, 70))
         _ck(L.gpemu_design_scores(h, _vp(s0), None))
         _ck(L.gpemu_design_condition(h, int(np.argmax(s0))))
         _ck(L.gpemu_design_scores(h, _vp(s1), None))
@@ -606,59 +709,120 @@ _CTX_WIDE = dict(family=DEVICE_WIDE, null_means=NULL_NULL, waits=True,
 _CTX_MODEL = dict(family=MODEL_BOUND, null_means=NULL_MODEL, waits=True,
                   doc=(("works on ctx->stream (NULL = the model's) and waits for it before returning", "section"),))
 
+# edge_shapes: the guard sweep's shapes of a row, from the sets above (where each set's tile, chunk and wave sizes are
+# cited by file and constant); out_ld, gaps: what tests/guard_cases.py pads and fills
 ROWS = [
-    Row("gpemu_gp_predict_dev", inputs=_in_rows(B_BIG, "stream_gp"), run=_gp_predict, cases=ALL4, **_M_NOWAIT),
-    Row("gpemu_gp_predict_cov_dev", inputs=_in_rows(B_SMALL + 17, "stream_pcov"), run=_gp_predict_cov, cases=ALL4,
+    Row("gpemu_gp_predict_dev", inputs=_in_rows(lambda: B_BIG, "stream_gp"), run=_gp_predict, cases=ALL4, edge_shapes=B_EDGES, **_M_NOWAIT),
+    Row("gpemu_gp_predict_cov_dev", inputs=_in_rows(lambda: B_SMALL + M2_COV, "stream_pcov"), run=_gp_predict_cov, cases=ALL4,
+        edge_shapes=PCOV_EDGES,
         **_M_WAIT),                      # (its workspace goes with the call)
-    Row("gpemu_predict_full_dev", inputs=_in_rows(B_SMALL, "stream_full"), run=_predict_full, cases=ALL4, **_M_NOWAIT),
-    Row("gpemu_logpost_dev", inputs=_in_logpost, run=_logpost, cases=ALL4, **_M_NOWAIT),
-    Row("gpemu_gp_predict_grad_dev", inputs=_in_rows(B_BIG, "stream_pgrad"), run=_gp_predict_grad, cases=GRAD_CASES,
-        **_M_NOWAIT),
-    Row("gpemu_logpost_grad_dev", inputs=_in_logpost, run=_logpost_grad, cases=GRAD_CASES, **_M_NOWAIT),
+    Row("gpemu_predict_full_dev", inputs=_in_rows(lambda: B_SMALL, "stream_full"), run=_predict_full, cases=ALL4,
+        # k_exact.hip launch_predict_full: the matrix-core writer stores pairs (16 bytes) and runs where dcov is 16-byte
+        # aligned and F even; the row-wise writer otherwise (other bits: include/gpemu.h).  PM_NB samples per group.
+        by_alignment=True, edge_shapes=B_EDGES + tuple(dataclasses.replace(sh, a16=True) for sh in B_EDGES), **_M_NOWAIT),
+    Row("gpemu_logpost_dev", inputs=_in_logpost, run=_logpost, cases=ALL4, edge_shapes=B_EDGES, **_M_NOWAIT),
+    Row("gpemu_gp_predict_grad_dev", inputs=_in_rows(lambda: B_BIG, "stream_pgrad"), run=_gp_predict_grad, cases=GRAD_CASES,
+        edge_shapes=B_EDGES, **_M_NOWAIT),
+    Row("gpemu_logpost_grad_dev", inputs=_in_logpost, run=_logpost_grad, cases=GRAD_CASES, edge_shapes=B_EDGES, **_M_NOWAIT),
     Row("gpemu_sampler_set_stream", family=SAMPLER_COMM, null_means=NULL_FIRST_GROUP, waits=True,
         doc=((NULL_FIRST_GROUP, "section"), ("gpemu_sampler_run waits for it", "section")),
-        inputs=_in_walkers, run=_sampler_run, cases=("general",)),
+        inputs=_in_walkers, run=_sampler_run, cases=("general",), edge_shapes=(Shape(),)),   # (W is the sampler's own)
     Row("gpemu_comm_all_gather", family=SAMPLER_COMM, null_means=NULL_NULL, waits=False,
         doc=(("enqueued on `stream` (NULL = the null stream); does not wait", "section"),),
         omitted="needs RCCL and more than one rank: tests/test_gpu_dropin.py runs it under torch.distributed"),
-    Row("gpemu_select_dev", inputs=_in_V, run=_select, **_WIDE),
-    Row("gpemu_posterior_predictive_dev", inputs=_in_model_view, run=_postpred, cases=ALL4, **_M_WAIT),
-    Row("gpemu_rank_dev", inputs=_in_V, run=_rank, **_WIDE),
-    Row("gpemu_diag_create_dev", inputs=_in_chain, run=_diag_create,
+    Row("gpemu_select_dev", inputs=_in_V, run=_select, edge_shapes=WIDE_V + S_CHUNK_2048 + S_CHUNK_4096, **_WIDE),
+    Row("gpemu_posterior_predictive_dev", inputs=_in_model_view, run=_postpred, cases=ALL4, gaps=("X",), edge_shapes=VIEW_EDGES,
+        **_M_WAIT),
+    Row("gpemu_rank_dev", inputs=_in_V, run=_rank, edge_shapes=WIDE_V + S_CHUNK_2048, **_WIDE),
+    Row("gpemu_diag_create_dev", inputs=_in_chain, run=_diag_create, edge_shapes=VIEW_EDGES + (Shape(VIEW=(17, 4, 9), D=1),
+                                                                                               Shape(VIEW=(17, 4, 9), D=16)),
         **dict(_WIDE, family=HANDLE_CREATING)),
-    Row("gpemu_sobol_moments_dev", inputs=_in_AB, run=_sobol, cases=ALL4, **_M_WAIT),
-    Row("gpemu_marginal_hist_dev", inputs=_in_X, run=_hist, **_WIDE),
-    Row("gpemu_hpd_dev", inputs=_in_V, run=_hpd, **_WIDE),
-    Row("gpemu_kde1d_dev", inputs=_in_V, run=_kde1d, **_WIDE),
-    Row("gpemu_marginal_dense_dev", inputs=_in_view, run=_dense, **_WIDE),
-    Row("gpemu_marginal_moments_dev", inputs=_in_X, run=_moments, **_WIDE),
-    Row("gpemu_kde2d_dev", inputs=_in_X, run=_kde2d, **_WIDE),
-    Row("gpemu_pair_moments_dev", inputs=_in_X, run=_pair_moments, **_WIDE),
+    Row("gpemu_sobol_moments_dev", inputs=_in_AB, run=_sobol, cases=ALL4, edge_shapes=B_EDGES,
+        **_M_WAIT),
+    Row("gpemu_marginal_hist_dev", inputs=_in_X, run=_hist, edge_shapes=WIDE_S, **_WIDE),
+    Row("gpemu_hpd_dev", inputs=_in_V, run=_hpd, edge_shapes=WIDE_V + S_CHUNK_2048 + S_CHUNK_4096, **_WIDE),
+    Row("gpemu_kde1d_dev", inputs=_in_V, run=_kde1d, edge_shapes=WIDE_V + S_CHUNK_1024 + S_CHUNK_8192, **_WIDE),
+    Row("gpemu_marginal_dense_dev", inputs=_in_view, run=_dense, gaps=("X",),
+        edge_shapes=VIEW_EDGES + (Shape(VIEW=(17, 4, 9), D=1), Shape(VIEW=(17, 4, 9), D=16)), **_WIDE),
+    Row("gpemu_marginal_moments_dev", inputs=_in_X, run=_moments, edge_shapes=WIDE_S + S_CHUNK_1024, **_WIDE),
+    Row("gpemu_kde2d_dev", inputs=_in_X, run=_kde2d, edge_shapes=WIDE_S + S_CHUNK_8192, **_WIDE),
+    Row("gpemu_pair_moments_dev", inputs=_in_X, run=_pair_moments, edge_shapes=WIDE_S + S_CHUNK_1024, **_WIDE),
     Row("gpemu_loglik_pointwise_dev", inputs=_in_model_view, run=_pointwise, cases=("general", "wide", "tasks10"),
+        gaps=("X",), out_ld=("ldt",), edge_shapes=VIEW_EDGES,
         **_M_WAIT),                      # (the per-observable terms decline correlated sources)
-    Row("gpemu_psis_dev", inputs=_in_loglik_rows, run=_psis, **_WIDE),
-    Row("gpemu_weighted_moments_dev", inputs=_in_X_logw, run=_weighted_moments, **_WIDE),
-    Row("gpemu_loo_group_rows_dev", inputs=_in_loglik_rows, run=_group_rows, **_WIDE),
+    Row("gpemu_psis_dev", inputs=_in_loglik_rows, run=_psis, edge_shapes=WIDE_V + S_CHUNK_2048 + S_CHUNK_4096, **_WIDE),
+    Row("gpemu_weighted_moments_dev", inputs=_in_X_logw, run=_weighted_moments, edge_shapes=WIDE_S + S_CHUNK_4096,
+        **_WIDE),
+    Row("gpemu_loo_group_rows_dev", inputs=_in_loglik_rows, run=_group_rows, out_ld=("ldo",), edge_shapes=WIDE_V,
+        **_WIDE),
     Row("gpemu_design_create_dev", family=HANDLE_CREATING, null_means=NULL_NONE, waits=True,
         doc=(("`stream` (NULL: none) is waited for before the rows are read", "section"),
              ("every call waits for it", "section")),
-        inputs=_in_design, run=_design_create, cases=ALL4),
-    Row("gpemu_unit_rows_dev", inputs=_in_X, run=_unit, **_WIDE),
-    Row("gpemu_knn_dist_dev", inputs=_in_X, run=_knn_dist, **_WIDE),
-    Row("gpemu_knn_logsum_dev", inputs=_in_r2, run=_knn_logsum, **_WIDE),
-    Row("gpemu_pair_lse_dev", inputs=_in_YZ, run=_pair_lse, **_WIDE),
-    Row("gpemu_pairlse_centre_dev", inputs=_in_YZ, run=_centre, **_WIDE),
-    Row("gpemu_logprior_dev", inputs=_in_X, run=_logprior, **_WIDE),
-    Row("gpemu_logmeanexp_dev", inputs=_in_L, run=_logmeanexp, **_WIDE),
-    Row("gpemu_weights_fixed_dev", inputs=_in_lw, run=_weights_fixed, **_WIDE),
-    Row("gpemu_weighted_select_dev", inputs=_in_Vq, run=_weighted_select, **_WIDE),
-    Row("gpemu_weighted_hist_dev", inputs=_in_Vq, run=_weighted_hist, **_WIDE),
+        inputs=_in_design, run=_design_create, cases=ALL4, gaps=("ref",), edge_shapes=VIEW_EDGES),
+    Row("gpemu_unit_rows_dev", inputs=_in_X, run=_unit, edge_shapes=WIDE_S, **_WIDE),
+    Row("gpemu_knn_dist_dev", inputs=_in_X, run=_knn_dist, edge_shapes=WIDE_S, **_WIDE),
+    Row("gpemu_knn_logsum_dev", inputs=_in_r2, run=_knn_logsum, edge_shapes=WIDE_V + S_CHUNK_1024, **_WIDE),
+    Row("gpemu_pair_lse_dev", inputs=_in_YZ, run=_pair_lse, edge_shapes=WIDE_V + S_CHUNK_2048 + B_EDGES[:8], **_WIDE),
+    Row("gpemu_pairlse_centre_dev", inputs=_in_YZ, run=_centre, edge_shapes=WIDE_V + S_CHUNK_1024, **_WIDE),
+    Row("gpemu_logprior_dev", inputs=_in_X, run=_logprior, out_ld=("ldl",), edge_shapes=WIDE_S, **_WIDE),
+    Row("gpemu_logmeanexp_dev", inputs=_in_L, run=_logmeanexp, edge_shapes=WIDE_V + S_CHUNK_4096, **_WIDE),
+    Row("gpemu_weights_fixed_dev", inputs=_in_lw, run=_weights_fixed, out_ld=("ldq",), edge_shapes=WIDE_V, **_WIDE),
+    Row("gpemu_weighted_select_dev", inputs=_in_Vq, run=_weighted_select, edge_shapes=WIDE_S + S_CHUNK_2048 + S_CHUNK_4096,
+        **_WIDE),
+    Row("gpemu_weighted_hist_dev", inputs=_in_Vq, run=_weighted_hist, edge_shapes=WIDE_S, **_WIDE),
     Row("gpemu_posterior_predictive_weighted_dev", inputs=in_weighted_view, run=weighted_bands_run(ctx_on),
-        cases=("general", "wide"), **_CTX_MODEL),
-    Row("gpemu_weighted_hpd_dev", inputs=_in_Vq2, run=weighted_hpd_run(ctx_on), **_CTX_WIDE),
-    Row("gpemu_weighted_kde1d_dev", inputs=_in_Vq2, run=weighted_kde_run(ctx_on), **_CTX_WIDE),
+        cases=("general", "wide"), gaps=("X",), edge_shapes=VIEW_EDGES, **_CTX_MODEL),
+    Row("gpemu_weighted_hpd_dev", inputs=_in_Vq2, run=weighted_hpd_run(ctx_on), edge_shapes=WIDE_V + S_CHUNK_2048 + S_CHUNK_4096,
+        **_CTX_WIDE),
+    Row("gpemu_weighted_kde1d_dev", inputs=_in_Vq2, run=weighted_kde_run(ctx_on), edge_shapes=WIDE_V + S_CHUNK_8192,
+        **_CTX_WIDE),
 ]
 ROW = {r.name: r for r in ROWS}
+
+
+# the ld* / stride parameters of the prototypes that address an INPUT (every other one belongs to an output and is named
+# in its row's ``out_ld``: tests/test_guards_host.py)
+INPUT_LD = {
+    "gpemu_select_dev": ("row_stride", "elem_stride"), "gpemu_rank_dev": ("row_stride", "elem_stride"),
+    "gpemu_hpd_dev": ("row_stride", "elem_stride"), "gpemu_kde1d_dev": ("row_stride", "elem_stride"),
+    "gpemu_psis_dev": ("row_stride", "elem_stride"), "gpemu_diag_create_dev": ("step_stride",),
+    "gpemu_posterior_predictive_dev": ("block_stride_rows",), "gpemu_marginal_hist_dev": ("block_stride_rows",),
+    "gpemu_marginal_dense_dev": ("block_stride_rows",), "gpemu_kde2d_dev": ("block_stride_rows",),
+    "gpemu_pair_moments_dev": ("block_stride_rows",), "gpemu_loglik_pointwise_dev": ("block_stride_rows",),
+    "gpemu_weighted_moments_dev": ("block_stride_rows", "ldw"), "gpemu_loo_group_rows_dev": ("ldt",),
+    "gpemu_design_create_dev": ("block_stride_rows",), "gpemu_unit_rows_dev": ("block_stride",),
+    "gpemu_pair_lse_dev": ("ldy", "ldz"), "gpemu_pairlse_centre_dev": ("ldz",),
+    "gpemu_logprior_dev": ("block_stride_rows",), "gpemu_logmeanexp_dev": ("ldl",), "gpemu_weights_fixed_dev": ("ldw",),
+    "gpemu_weighted_select_dev": ("row_stride", "elem_stride", "ldq"),
+    "gpemu_weighted_hist_dev": ("block_stride_rows", "ldq"),
+    "gpemu_posterior_predictive_weighted_dev": ("block_stride_rows", "ldq"),
+    "gpemu_weighted_hpd_dev": ("row_stride", "elem_stride", "ldq"),
+    "gpemu_weighted_kde1d_dev": ("row_stride", "elem_stride", "ldq"),
+}
+
+
+@contextmanager
+def shaped(sh):
+    """the module's shape constants, and the tables made from them, rebound to ``sh`` while the block runs"""
+    g = globals()
+    tables = _w_tables(sh.RW)
+    new = dict(S_WIDE=sh.S, D_WIDE=sh.D, VIEW=tuple(sh.VIEW), B_SMALL=sh.B_SMALL, B_BIG=sh.B_BIG, RW2=sh.RW, M2_COV=sh.M2,
+               PAD=sh.pad, A16=sh.a16, EDGES1=_edges(8, sh.D), EDGES2=_edges(4, sh.D), _W_TARGETS=tables[0], _W_GRID=tables[1],
+               _W_H=tables[2], _W_VIEW_TARGETS=tables[3])
+    old = {k: g[k] for k in new}
+    g.update(new)
+    try:
+        yield sh
+    finally:
+        g.update(old)
+
+
+def gap_mask(shape):
+    """of the rows of a view's input [nb*bs][d]: True where a row lies between the blocks (VIEW in force)"""
+    nb, br, bs = VIEW
+    m = np.zeros(shape, dtype=bool)
+    m.reshape(nb, bs, -1)[:, br:] = True
+    return m
 
 
 def sweep_params(families):
@@ -702,19 +866,31 @@ def _device(T):
 class Outs:
     """the allocator of a closure's device outputs: fresh tensors of NaN (integers: -1), or the ones made before"""
 
-    def __init__(self, pre=None):
-        self.made, self.pre = [], pre
+    def __init__(self, pre=None, odd=False):
+        """``odd``: the tensors start 8 bytes past a 16-byte boundary (torch's own are aligned to 512 bytes)"""
+        self.made, self.pre, self.odd = [], pre, odd
 
-    def __call__(self, shape, dtype=None):
+    def __call__(self, shape, dtype=None, ld=None):
+        """``ld``: the leading dimension of a matrix, at least its row length; the rows of the result lie ld apart"""
         import torch
         dtype = dtype or torch.float64
         if self.pre is not None:
             t = self.pre[len(self.made)]
             assert tuple(t.shape) == tuple(shape) and t.dtype == dtype
-        else:
+        elif self.odd:
+            assert ld is None or ld == shape[-1]
+            t = blank((int(np.prod(shape)) + 1,), dtype)[1:].view(tuple(shape))
+        elif ld is None or ld == shape[-1]:
             t = blank(shape, dtype)
+        else:
+            assert len(shape) == 2 and ld > shape[1]
+            t = blank((shape[0], ld), dtype)[:, :shape[1]]
         self.made.append(t)
         return t
+
+    def host(self, shape, dtype=np.float64):
+        """a host output: NaN (integers: -1)"""
+        return np.full(shape, np.nan if np.dtype(dtype).kind == "f" else -1, dtype=dtype)
 
 
 def blank(shape, dtype):
@@ -728,11 +904,11 @@ def _host(res):
     return tuple(np.array(r.cpu().numpy() if torch.is_tensor(r) else r, copy=True) for r in res)
 
 
-def quiet(row, P, dm, inputs, st=0):
+def quiet(row, P, dm, inputs, st=0, odd=False):
     """the call on a quiet device with the default stream argument: (results, the outputs it allocated)"""
     import torch
     T = _device(inputs)
-    o = Outs()
+    o = Outs(odd=odd)
     torch.cuda.synchronize()
     res = row.run(st, T, o, P, dm)
     torch.cuda.synchronize()
