@@ -47,6 +47,21 @@ __global__ __launch_bounds__(256) void acf_mean_kernel(const double *__restrict_
   mean[s] = a / (double)n_t;
 }
 
+// A series whose n_t values are all equal (a walker that never moved in the range) must centre to exact zeros, so that
+// its lag products are 0 and its ratio 0 / 0 = NaN at every lag.  The chunked sum of n_t copies of c, divided by n_t,
+// is c only for some c: elsewhere the centred series would be a rounding residue and the ratio an arbitrary finite
+// number.  So the mean of such a series is stored as the value itself.  A series that is not constant leaves the loop at
+// its first step that differs (after a step or two for a chain that moves) and keeps the mean it has, bit for bit.
+__global__ __launch_bounds__(256) void acf_constant_mean_kernel(const double *__restrict__ chain, int64_t n_t, int64_t S,
+                                                                int64_t ld, double *__restrict__ mean) {
+  const int64_t s = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (s >= S) return;
+  const double c = chain[s];
+  for (int64_t t = 1; t < n_t; ++t)
+    if (!(chain[t * ld + s] == c)) return;          // a NaN is never equal: its series keeps its NaN mean
+  if (c == c) mean[s] = c;
+}
+
 // part[(c * n_lags + l - lag0) * S + s] = sum over t in chunk c of y[t] y[t - l],  y = x - mean,  l in this thread's 16 lags
 __global__ __launch_bounds__(256) void acf_lag_kernel(const double *__restrict__ chain, const double *__restrict__ mean,
                                                       int64_t n_t, int64_t S, int64_t ld, int64_t tchunk, int64_t lag0,
@@ -125,6 +140,14 @@ int gpemu_sampler_acf(gpemu_sampler *s, int64_t first, int64_t n_steps, int64_t 
   GP_ARG(w0 >= 0 && nw >= 1 && w0 + nw <= s->W, "walker range");
   GP_ARG(lag0 >= 0 && n_lags >= 1 && n_lags <= 4096 && lag0 % ACF_LPT == 0, "lag block (lag0 must be a multiple of 16)");
   GP_ARG(n_lags <= n_steps, "more lags than steps");
+  // a continuation of the last estimate (same rows, same walkers) reads that estimate's means and lag-0 products: they
+  // belong to the chain as it stood then, so whatever may have moved or rewritten the chain since (chain_epoch) ends it
+  if (lag0 != 0 && s->acf_first == first && s->acf_n == n_steps && s->acf_w0 == w0 && s->acf_nw == nw &&
+      s->acf_epoch != s->chain_epoch) {
+    set_error("gpemu_sampler_acf: the chain has been run, reserved, reset or restored since the estimate's first block: "
+              "restart at lag 0");
+    return GPEMU_ERR_STATE;
+  }
   GP_HIP(hipSetDevice(s->device));
   hipStream_t st = s->stream;
   // only the series asked for -- walkers [w0, w0 + nw), e.g. one chain of a stacked closure run -- are transformed
@@ -149,7 +172,9 @@ int gpemu_sampler_acf(gpemu_sampler *s, int64_t first, int64_t n_steps, int64_t 
     GP_ARG(lag0 == 0, "the first block of an estimate must start at lag 0");
     hipLaunchKernelGGL(acf_sum_kernel, dim3(gs, 1, (unsigned)nchunk), block, 0, st, chain, n_t, S, ld, tchunk, s->acf_part);
     hipLaunchKernelGGL(acf_mean_kernel, dim3(gs), block, 0, st, s->acf_part, n_t, S, nchunk, s->acf_mean);
+    hipLaunchKernelGGL(acf_constant_mean_kernel, dim3(gs), block, 0, st, chain, n_t, S, ld, s->acf_mean);
     s->acf_first = first; s->acf_n = n_steps; s->acf_w0 = w0; s->acf_nw = nw;
+    s->acf_epoch = s->chain_epoch;
   }
   hipLaunchKernelGGL(acf_lag_kernel, dim3(gs, (unsigned)nlg, (unsigned)nchunk), block, 0, st, chain, s->acf_mean, n_t, S, ld,
                      tchunk, lag0, (int)n_lags, s->acf_part);

@@ -138,6 +138,7 @@ struct gpemu_sampler {
   double *acf_part = nullptr, *acf_acf = nullptr, *acf_mean = nullptr, *acf_acf0 = nullptr;
   size_t acf_part_bytes = 0, acf_acf_bytes = 0, acf_mean_bytes = 0;   // capacity of acf_part / acf_acf / acf_mean + acf_acf0
   int64_t acf_first = -1, acf_n = -1, acf_w0 = -1, acf_nw = -1;       // the estimate the scratch belongs to
+  uint64_t acf_epoch = 0;            // chain_epoch at that estimate's first block: a later block under another is refused
   // parallel tempering (gpemu_sampler_create_tempered, k_temper.hip): the nchains stacked chains are the rungs of a
   // temperature ladder on ONE data vector; rung t accepts with beta[t] and swaps states with rung t - 1 every
   // swap_every steps

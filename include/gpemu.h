@@ -387,7 +387,14 @@ int gpemu_model_live_counts(gpemu_model *m, int64_t *live_proposals /*[2]*/);
  *     f[l][dd] = 1/nw sum_w acf_(w,dd)[l] / acf_(w,dd)[0],  acf[l] = sum_t (x[t] - mean)(x[t + l] - mean),
  * i.e. emcee.autocorr.function_1d averaged as emcee.autocorr.integrated_time does (emcee 3.1.x, third party; call
  * site ref: mcmc.py:111-119 sampler.get_autocorr_time()).  The host asks for blocks of lags (lag0 a multiple of 16,
- * the first block at lag0 = 0) until Sokal's window closes, so the chain never has to leave HBM for it. */
+ * the first block at lag0 = 0) until Sokal's window closes, so the chain never has to leave HBM for it.
+ * A block with lag0 > 0 continues the estimate of the last lag0 = 0 block: it must name the same (first, n_steps, w0,
+ * nw), else GPEMU_ERR_ARG, and the chain must be the one that block read: after a run that stores, a reserve, a reset
+ * or a restore of the sampler (what invalidates a gpemu_diag) the continuation returns GPEMU_ERR_STATE before any
+ * launch and writes nothing; start again at lag 0.  n_lags <= min(4096, n_steps).
+ * A series whose n_steps values are all equal (a walker that never moved in the range; every series at n_steps = 1)
+ * centres to exact zeros and has acf[0] = 0: its parameter's f is NaN at every lag, the other parameters are not
+ * touched.  A series with a non-finite value makes its parameter NaN as well. */
 int gpemu_sampler_acf(gpemu_sampler *s, int64_t first, int64_t n_steps, int64_t w0, int64_t nw, int64_t lag0,
                       int64_t n_lags, double *f_out);
 /* Phases of one step for the multi-GPU driver: every rank holds the whole ensemble and draws the

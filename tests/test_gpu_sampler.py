@@ -1013,7 +1013,8 @@ def test_device_autocorrelation_time_equals_host_estimator():
         ds.integrated_time(first=0, n=200)
     np.testing.assert_allclose(err.value.tau, S.integrated_time(chain[:200], quiet=True), rtol=1e-9)
     # a chain so short that the window never closes: emcee's auto_window then answers window 0, tau = 1.  (A walker that
-    # never moved in the range makes its series 0 / 0: NaN here, rounding residue in the FFT routine -- not compared.)
+    # never moved in the range is centred to exact zeros and makes its parameter 0 / 0 = NaN here
+    # (acf_constant_mean_kernel; tests/test_gpu_acf.py plants one), rounding residue in the FFT routine -- not compared.)
     checked = 0
     for n_short in (12, 24, 40):
         moved = np.all(np.any(chain[:n_short] != chain[0], axis=0))
