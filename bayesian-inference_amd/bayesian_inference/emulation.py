@@ -575,9 +575,25 @@ def merge_global_sensitivity(sorter, group_results) -> dict[str, Any]:
     return out
 
 
+_GS_PAIR_MATRICES = ('closed_pair', 'interaction', 'total_pair', 'closed_pair_se', 'interaction_se', 'total_pair_se')
+
+
+def merge_global_sensitivity_pairs(sorter, group_results) -> dict[str, Any]:
+    """The groups' second-order results ((P, F_g) per key, the same ``pairs`` in every group) in the merged observable
+    order of ``predict``, scattered as ``merge_global_sensitivity`` scatters."""
+    first = next(iter(group_results.values()))
+    P = first['closed_pair'].shape[0]
+    rows = {name: np.vstack([g[key] for key in _GS_PAIR_MATRICES]) for name, g in group_results.items()}
+    merged = scatter_feature_rows(sorter, rows)
+    out = {key: merged[i * P:(i + 1) * P].copy() for i, key in enumerate(_GS_PAIR_MATRICES)}
+    out['pairs'] = np.array(first['pairs'], dtype=np.int64)
+    return out
+
+
 def global_sensitivity(emulation_config: "EmulationConfig", n: int = 4096, seed: int = 0, method: str = 'sobol',
                        box=None, n_batches: int = 16,
-                       emulation_group_results: dict[str, dict[str, Any]] | None = None) -> dict[str, Any]:
+                       emulation_group_results: dict[str, dict[str, Any]] | None = None,
+                       second_order: bool = False, pairs=None) -> dict[str, Any]:
     """Global, variance-based sensitivities of every observable bin over a parameter box: ``first_order`` (d, F), the
     share of the emulated observable's variance that parameter i explains alone, ``total`` (d, F), its share with all
     interactions, their batch-means standard errors ``first_order_se`` / ``total_se``, ``variance`` and ``mean`` (F,)
@@ -586,8 +602,16 @@ def global_sensitivity(emulation_config: "EmulationConfig", n: int = 4096, seed:
     difference at one point, ref: plot_qhat.py:172-258).  ``box`` = (lo, hi) defaults to the prior box of the
     parameterisation, the one ``mcmc.run_mcmc`` samples in; a sub-box restricts the analysis.  One pair of base
     matrices (``gpemu.sensitivity.base_samples``) is shared by all groups; reduced on the device per group
-    (``DeviceModel.sobol_indices``)."""
+    (``DeviceModel.sobol_indices``).
+
+    ``second_order=True`` adds, for ``pairs`` (P, 2) of parameters i < j (None: all of them), ``pairs`` and the (P, F)
+    arrays ``closed_pair`` (the share both explain together), ``interaction`` (= closed_pair - S_i - S_j, the share
+    they explain only jointly: with which parameter a large ``total - first_order`` interacts), ``total_pair`` and
+    their ``_se`` (``gpemu.sensitivity.pair_indices_from_moments``, DESIGN.md §4.45), from the same base pair;
+    ``gpemu.sensitivity.interacting_pairs`` picks the pairs worth asking for from a first-order result."""
     from gpemu import sensitivity as gs
+    if pairs is not None and not second_order:
+        raise ValueError("pairs needs second_order=True")
     par = emulation_config.analysis_config['parameterization'][emulation_config.parameterization]
     lo, hi = (par['min'], par['max']) if box is None else box
     A, B = gs.base_samples(n, lo, hi, seed=seed, method=method)
@@ -598,8 +622,13 @@ def global_sensitivity(emulation_config: "EmulationConfig", n: int = 4096, seed:
         if group_result is None:
             group_result = read_emulators(group_config)
         dm = device_model_for(group_result, group_config.n_pc)
-        per_group[group_name] = dm.sobol_indices(A, B, n_batches=n_batches)
+        if second_order:
+            per_group[group_name] = dm.sobol_indices(A, B, n_batches=n_batches, second_order=True, pairs=pairs)
+        else:
+            per_group[group_name] = dm.sobol_indices(A, B, n_batches=n_batches)
     out = merge_global_sensitivity(emulation_config.sort_observables_in_matrix, per_group)
+    if second_order:
+        out.update(merge_global_sensitivity_pairs(emulation_config.sort_observables_in_matrix, per_group))
     out['parameter_names'] = [str(name) for name in par['names']]
     return out
 

@@ -24,7 +24,7 @@ constexpr int PATH_FAMILY_SIZE[PATH_FAMILIES] = {GPEMU_PATH_COUNT, GPEMU_FIT_PAT
                                                  GPEMU_MARGINAL_PATH_COUNT, GPEMU_DESIGN_PATH_COUNT,
                                                  GPEMU_KDE2D_PATH_COUNT, GPEMU_LOO_PATH_COUNT, GPEMU_KNN_PATH_COUNT,
                                                  GPEMU_PAIRLSE_PATH_COUNT, GPEMU_REWEIGHT_PATH_COUNT,
-                                                 GPEMU_WSUMMARY_PATH_COUNT};
+                                                 GPEMU_WSUMMARY_PATH_COUNT, GPEMU_SOBOL_PAIRS_PATH_COUNT};
 constexpr int PATH_ROW = 32;
 static_assert(GPEMU_PATH_COUNT <= PATH_ROW && GPEMU_FIT_PATH_COUNT <= PATH_ROW && GPEMU_WIDE_PATH_COUNT <= PATH_ROW &&
               GPEMU_SRC_PATH_COUNT <= PATH_ROW && GPEMU_GRAD_PATH_COUNT <= PATH_ROW && GPEMU_POSTPRED_PATH_COUNT <= PATH_ROW &&
@@ -32,7 +32,7 @@ static_assert(GPEMU_PATH_COUNT <= PATH_ROW && GPEMU_FIT_PATH_COUNT <= PATH_ROW &
               GPEMU_MARGINAL_PATH_COUNT <= PATH_ROW && GPEMU_DESIGN_PATH_COUNT <= PATH_ROW &&
               GPEMU_KDE2D_PATH_COUNT <= PATH_ROW && GPEMU_LOO_PATH_COUNT <= PATH_ROW && GPEMU_KNN_PATH_COUNT <= PATH_ROW &&
               GPEMU_PAIRLSE_PATH_COUNT <= PATH_ROW && GPEMU_REWEIGHT_PATH_COUNT <= PATH_ROW &&
-              GPEMU_WSUMMARY_PATH_COUNT <= PATH_ROW,
+              GPEMU_WSUMMARY_PATH_COUNT <= PATH_ROW && GPEMU_SOBOL_PAIRS_PATH_COUNT <= PATH_ROW,
               "a family outgrew its row");
 static std::atomic<int64_t> g_path_counts[PATH_FAMILIES][PATH_ROW];
 

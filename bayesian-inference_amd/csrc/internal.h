@@ -53,9 +53,9 @@ static inline int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * 
 // a path outside its family's enum is not counted
 enum PathFamily { PATHS_LOGPOST, PATHS_FIT, PATHS_WIDE, PATHS_SRC, PATHS_GRAD, PATHS_POSTPRED, PATHS_HMC, PATHS_DIAG,
                   PATHS_SOBOL, PATHS_MARGINAL, PATHS_DESIGN, PATHS_KDE2D, PATHS_LOO, PATHS_KNN, PATHS_PAIRLSE,
-                  PATHS_REWEIGHT, PATHS_WSUMMARY, PATH_FAMILIES };
+                  PATHS_REWEIGHT, PATHS_WSUMMARY, PATHS_SOBOL_PAIRS, PATH_FAMILIES };
 void count_path(PathFamily family, int path);
-int read_path_counts(PathFamily family, int64_t *out, int64_t n);     // what the seventeen public gpemu_*_path_counts return
+int read_path_counts(PathFamily family, int64_t *out, int64_t n);     // what the eighteen public gpemu_*_path_counts return
 static inline void path_count(int path) { count_path(PATHS_LOGPOST, path); }    // enum gpemu_path
 static inline void fit_path_count(int path) { count_path(PATHS_FIT, path); }    // enum gpemu_fit_path
 static inline void wide_path_count(int path) { count_path(PATHS_WIDE, path); }  // enum gpemu_wide_path: d > 8 only

@@ -29,6 +29,20 @@
 // atomics; a partial sum covers a slice fixed by n and T, so the bits do not depend on the workspace or on the run.
 // The pivot c is the mean of z over the first min(n, SB_PIVOT) rows of A and of B, computed first (its own pass of
 // the mean kernel without the AB_i rows) and returned: the host re-centres about the true mean with a small correction.
+//
+// Second order (gpemu_sobol_moments_pairs).  The pair rows AB_ij (A_r with coordinates i < j from B_r) take
+// slots of their own behind the d + 2, filled by sobol_pair_mean_kernel: grid z = one FIRST index i, whose partners j > i
+// stay in registers (at most DP - 1 accumulators: no more than sobol_mean_kernel holds).  For fixed i the kernel walks j
+// upward with a running sum,
+//     r2_ij = ((sum_{l < i} t^A_l + t^B_i) + sum_{i < l < j} t^A_l + t^B_j) + sum_{l > j} t^A_l
+// again a sum of non-negative terms, every term through at most d - 1 additions.  A lane with a_i == b_i has a row
+// AB_ij that IS the row AB_j (with a_j == b_j: AB_i; with both: A), whose mean sobol_mean_kernel has already written to
+// its slot of the same chunk: the lane stores THAT value.  Writing the same association in both kernels does not give
+// the same bits (the compiler contracts the two kernels' sums into different fma chains: measured), a copy does,
+// whatever the compiler: B = A gives exact zeros, a shared column D_ij = D_j.  sobol_pair_matrix_kernel /
+// sobol_pair_vector_kernel are the siblings of
+// the two slice kernels for M2_ij = sum (zB - c) D_ij^T, D2_ij = sum D_ij D_ij^T and sum D_ij; sobol_combine_kernel serves
+// both.  The first-order kernels are untouched: the entry's first-order outputs are gpemu_sobol_moments' bytes.
 #include <algorithm>
 
 #include "internal.h"
@@ -156,12 +170,15 @@ __global__ __launch_bounds__(64) void sobol_mean_kernel(SobolMeanArgs g, const d
   }
 }
 
-static int launch_sobol_mean(const gpemu_model *m, SobolMeanArgs g, hipStream_t st) {
+// counted = false: a launch on behalf of gpemu_sobol_moments_pairs, which keeps counters of its own
+static int launch_sobol_mean(const gpemu_model *m, SobolMeanArgs g, hipStream_t st, bool counted = true) {
   g.N = m->N; g.Npad = m->Npad; g.d = (int)m->d; g.k = (int)m->k; g.has_const = m->has_const;
   const int kind = kstar_kind(m);
   if (kind == 4) g.mn = matern_nu_constants(m->nu);
-  sobol_path_count(m->dp == DPAD ? GPEMU_SOBOL_PATH_DP8 : GPEMU_SOBOL_PATH_DP16);
-  sobol_path_count(GPEMU_SOBOL_PATH_KIND0 + kind);
+  if (counted) {
+    sobol_path_count(m->dp == DPAD ? GPEMU_SOBOL_PATH_DP8 : GPEMU_SOBOL_PATH_DP16);
+    sobol_path_count(GPEMU_SOBOL_PATH_KIND0 + kind);
+  }
   dim3 grid((unsigned)((g.nr + 63) / 64), (unsigned)m->k), block(64);
   GP_TRY(with_base_kind(kind, [&](auto kd) {
     constexpr int K = decltype(kd)::value;
@@ -169,6 +186,134 @@ static int launch_sobol_mean(const gpemu_model *m, SobolMeanArgs g, hipStream_t 
       hipLaunchKernelGGL((sobol_mean_kernel<K, DPAD>), grid, block, 0, st, g, m->Xtr, m->ls, m->alpha, m->constv);
     else
       hipLaunchKernelGGL((sobol_mean_kernel<K, DPAD_WIDE>), grid, block, 0, st, g, m->Xtr, m->ls, m->alpha, m->constv);
+    return GPEMU_OK;
+  }));
+  GP_HIP(hipGetLastError());
+  return GPEMU_OK;
+}
+
+// ---- second order: the pair rows AB_ij ---------------------------------------------------------------------------------
+struct SobolPairMeanArgs {
+  const double *A = nullptr, *B = nullptr;   // [n][d] raw rows
+  int64_t r0 = 0, nr = 0;                    // rows [r0, r0 + nr) of A and B
+  double *Z = nullptr;                       // [n_pairs][zs][k]: the pair slots; row r at index r - r0
+  const double *Z1 = nullptr;                // [d + 2][zs][k]: the first-order slots of the same rows, already written
+  int64_t zs = 0;
+  int64_t N = 0, Npad = 0;
+  int d = 2, k = 1, has_const = 0;
+  unsigned char first[SB_MAXD] = {};         // the first index of grid plane z
+  short slot[SB_MAXD * SB_MAXD] = {};        // slot[i * SB_MAXD + j] = the pair's slot, -1: not asked for
+  MaternNu mn;
+};
+
+// grid (row tiles, PCs, first indices): one wave = 64 base rows of one PC and one first index i = g.first[blockIdx.z]; the
+// walk over l is unrolled and its three branches (l < i, l == i, l > i) are wave-uniform, so every register array keeps
+// constant indices
+template <int KIND, int DP>
+__global__ __launch_bounds__(64) void sobol_pair_mean_kernel(SobolPairMeanArgs g, const double *__restrict__ Xtr,
+                                                             const double *__restrict__ ls,
+                                                             const double *__restrict__ alpha,
+                                                             const double *__restrict__ constv) {
+  __shared__ double s_tab[32];
+  const int lane = threadIdx.x;
+  if (lane < 32) s_tab[lane] = c_exp2_32[lane];
+  __syncthreads();
+  const int p = blockIdx.y;
+  const int i = g.first[blockIdx.z];
+  const int64_t rl = (int64_t)blockIdx.x * 64 + lane;
+  const bool live = rl < g.nr;
+  const int64_t r = g.r0 + (live ? rl : 0);
+  const int d = g.d;
+  double qa[DP], qb[DP], inv[DP];
+  bool eq_i = false;
+  unsigned want = 0;                            // bit l: the pair (i, l) was asked for (wave-uniform)
+#pragma unroll
+  for (int l = 0; l < DP; ++l) {
+    qa[l] = (l < d) ? g.A[r * d + l] : 0.0;
+    qb[l] = (l < d) ? g.B[r * d + l] : 0.0;
+    inv[l] = 1.0 / ls[(int64_t)p * DP + l];     // padded dimensions: ls = 1, coordinates 0
+    if (l == i) eq_i = qa[l] == qb[l];
+    if (l > i && l < d && g.slot[i * SB_MAXD + l] >= 0) want |= 1u << l;
+  }
+  const double cst = g.has_const ? constv[p] : 0.0;
+  const double *al = alpha + (int64_t)p * g.Npad;
+  double acc[DP];
+#pragma unroll
+  for (int l = 0; l < DP; ++l) acc[l] = 0.0;
+
+  for (int64_t j0 = 0; j0 < g.N; j0 += SB_BLK) {
+    const int nj = (int)((g.N - j0 < SB_BLK) ? g.N - j0 : SB_BLK);
+    double bs[DP];
+#pragma unroll
+    for (int l = 0; l < DP; ++l) bs[l] = 0.0;
+    for (int jj = 0; jj < nj; ++jj) {
+      const int64_t j = j0 + jj;
+      const double *x = Xtr + j * DP;           // wave-uniform
+      const double a_j = al[j];
+      double ta[DP], tb[DP];
+#pragma unroll
+      for (int l = 0; l < DP; ++l) {
+        const double xl = x[l];
+        const double da = (qa[l] - xl) * inv[l];
+        const double db = (qb[l] - xl) * inv[l];
+        ta[l] = da * da;
+        tb[l] = db * db;
+      }
+      double suf[DP];                           // suf[l] = sum_{m > l} ta[m]
+      suf[DP - 1] = 0.0;
+#pragma unroll
+      for (int l = DP - 2; l >= 0; --l) suf[l] = suf[l + 1] + ta[l + 1];
+      // pre: the prefix of t^A below i; run: (pre + t^B_i) + the t^A between i and l
+      double pre = 0.0, run = 0.0;
+#pragma unroll
+      for (int l = 0; l < DP; ++l) {
+        if (l < i) {
+          pre += ta[l];
+        } else if (l == i) {
+          run = pre + tb[l];
+        } else {
+          if ((want >> l) & 1u) {
+            const double r2 = (run + tb[l]) + suf[l];
+            bs[l] = fma(a_j, sobol_base<KIND>(r2, s_tab, g.mn) + cst, bs[l]);
+          }
+          run += ta[l];
+        }
+      }
+    }
+#pragma unroll
+    for (int l = 0; l < DP; ++l) acc[l] += bs[l];
+  }
+  if (!live) return;
+  double *z = g.Z + rl * g.k + p;
+  const double *z1 = g.Z1 + rl * g.k + p;
+  const int64_t slot = g.zs * g.k;
+#pragma unroll
+  for (int l = 1; l < DP; ++l)
+    if ((want >> l) & 1u) {
+      const bool eq_l = qa[l] == qb[l];
+      double v = acc[l];
+      // the row AB_il is the row AB_l (a_i == b_i), AB_i (a_l == b_l) or A (both): that row's mean, from its slot
+      if (eq_i || eq_l) v = z1[(int64_t)(eq_i ? (eq_l ? 0 : 2 + l) : 2 + i) * slot];
+      z[(int64_t)g.slot[i * SB_MAXD + l] * slot] = v;
+    }
+}
+
+static inline void sobol_pairs_path_count(int path) { count_path(PATHS_SOBOL_PAIRS, path); }   // enum gpemu_sobol_pairs_path
+
+// g.first / g.slot / nz: filled by the caller (sobol_moments_run)
+static int launch_sobol_pair_mean(const gpemu_model *m, SobolPairMeanArgs g, int nz, hipStream_t st) {
+  g.N = m->N; g.Npad = m->Npad; g.d = (int)m->d; g.k = (int)m->k; g.has_const = m->has_const;
+  const int kind = kstar_kind(m);
+  if (kind == 4) g.mn = matern_nu_constants(m->nu);
+  sobol_pairs_path_count(m->dp == DPAD ? GPEMU_SOBOL_PAIRS_PATH_DP8 : GPEMU_SOBOL_PAIRS_PATH_DP16);
+  sobol_pairs_path_count(GPEMU_SOBOL_PAIRS_PATH_KIND0 + kind);
+  dim3 grid((unsigned)((g.nr + 63) / 64), (unsigned)m->k, (unsigned)nz), block(64);
+  GP_TRY(with_base_kind(kind, [&](auto kd) {
+    constexpr int K = decltype(kd)::value;
+    if (m->dp == DPAD)
+      hipLaunchKernelGGL((sobol_pair_mean_kernel<K, DPAD>), grid, block, 0, st, g, m->Xtr, m->ls, m->alpha, m->constv);
+    else
+      hipLaunchKernelGGL((sobol_pair_mean_kernel<K, DPAD_WIDE>), grid, block, 0, st, g, m->Xtr, m->ls, m->alpha, m->constv);
     return GPEMU_OK;
   }));
   GP_HIP(hipGetLastError());
@@ -264,6 +409,53 @@ __global__ __launch_bounds__(64) void sobol_vector_kernel(SobolSliceArgs g) {
   g.part[s * g.stride + (int64_t)(1 + 2 * d) * k * k + (int64_t)vi * k + p] = v;
 }
 
+// the pair partial sums of one slice: [M2 P k^2][D2 P k^2][sumD2 P k]
+static inline int64_t sobol_pair_part_stride(int64_t P, int64_t k) { return P * (2 * k * k + k); }
+
+struct SobolPairSliceArgs {
+  const double *Z = nullptr;        // the chunk's means [d + 2 + P][zs][k]
+  int64_t zs = 0, row0 = 0;         // the chunk's first row
+  const int64_t *start = nullptr;   // [nslices + 1] first row of every slice (device)
+  int64_t s0 = 0;                   // the first slice of this launch
+  const double *pivot = nullptr;    // [k]
+  double *part = nullptr;           // [nslices][stride]
+  int64_t stride = 0;
+  int d = 2, k = 1, np = 1;
+};
+
+// grid (slices, 2 P matrices, ceil(k^2 / 256)): y < P: M2 of pair y; P + y: D2 of pair y; the sums of sobol_matrix_kernel
+__global__ __launch_bounds__(256) void sobol_pair_matrix_kernel(SobolPairSliceArgs g) {
+  const int e = blockIdx.z * 256 + threadIdx.x;
+  const int k = g.k;
+  if (e >= k * k) return;
+  const int p = e / k, q = e % k;
+  const int64_t s = g.s0 + blockIdx.x;
+  const int64_t b = g.start[s] - g.row0, len = g.start[s + 1] - g.start[s];
+  const int mi = blockIdx.y, pi = (mi < g.np) ? mi : mi - g.np;
+  const int64_t slot = g.zs * k;
+  const double *zA = g.Z + b * k, *zB = zA + slot, *zi = zA + (int64_t)(g.d + 2 + pi) * slot;
+  double v;
+  if (mi < g.np) {
+    const double cp = g.pivot[p];
+    v = sobol_blocked_sum(len, [&](int64_t r) { return (zB[r * k + p] - cp) * (zi[r * k + q] - zA[r * k + q]); });
+  } else {
+    v = sobol_blocked_sum(len, [&](int64_t r) { return (zi[r * k + p] - zA[r * k + p]) * (zi[r * k + q] - zA[r * k + q]); });
+  }
+  g.part[s * g.stride + (int64_t)mi * k * k + e] = v;
+}
+
+// grid (slices, P): sum D_ij of pair y
+__global__ __launch_bounds__(64) void sobol_pair_vector_kernel(SobolPairSliceArgs g) {
+  const int p = threadIdx.x, k = g.k;
+  if (p >= k) return;
+  const int64_t s = g.s0 + blockIdx.x;
+  const int64_t b = g.start[s] - g.row0, len = g.start[s + 1] - g.start[s];
+  const int pi = blockIdx.y;
+  const double *zA = g.Z + b * k, *zi = zA + (int64_t)(g.d + 2 + pi) * g.zs * k;
+  const double v = sobol_blocked_sum(len, [&](int64_t r) { return zi[r * k + p] - zA[r * k + p]; });
+  g.part[s * g.stride + (int64_t)2 * g.np * k * k + (int64_t)pi * k + p] = v;
+}
+
 // out[t][e] = the sum over the slices [first[t], first[t + 1]) of part[.][e], e < stride; grid (ceil(stride / 256), T)
 __global__ __launch_bounds__(256) void sobol_combine_kernel(const double *__restrict__ part, int64_t stride,
                                                             const int64_t *__restrict__ first,
@@ -299,6 +491,160 @@ static bool sobol_all_finite(const double *x, int64_t n) {
   for (int64_t i = 0; i < n; ++i)
     if (!std::isfinite(x[i])) return false;
   return true;
+}
+
+struct SobolOut { double *pivot; int64_t *count; double *sumA, *sumB, *C2, *sumD, *M, *D; };   // host arrays
+struct SobolPairOut {                 // the second-order part of a call: the pairs and their host arrays
+  int64_t np = 0;
+  const int32_t *pairs = nullptr;     // [np][2], checked by the caller
+  double *sumD2 = nullptr, *M2 = nullptr, *D2 = nullptr;
+};
+
+// the body of gpemu_sobol_moments_dev (po == nullptr: its launches, allocations and counters exactly) and of
+// gpemu_sobol_moments_pairs (po: the pair slots behind the d + 2 of every chunk, their slice sums beside the first-order
+// ones, the counters of enum gpemu_sobol_pairs_path in place of enum gpemu_sobol_path's)
+static int sobol_moments_run(gpemu_model *m, int64_t n, const double *dA, const double *dB, int64_t T,
+                             int64_t workspace_bytes, const SobolOut &o, const SobolPairOut *po, hipStream_t st) {
+  const int64_t d = m->d, k = m->k, P = po ? po->np : 0;
+  const int64_t stride = sobol_part_stride(d, k), stride2 = sobol_pair_part_stride(P, k);
+  const int64_t row_bytes = (d + 2 + P) * k * 8;
+  const char *who = po ? "sobol_moments_pairs" : "sobol_moments";
+
+  std::vector<int64_t> start, first;
+  sobol_slices(n, T, start, first);
+  const int64_t nslices = (int64_t)start.size() - 1;
+  for (int64_t t = 0; t < T; ++t) o.count[t] = start[(size_t)first[(size_t)t + 1]] - start[(size_t)first[(size_t)t]];
+
+  int64_t budget = 0;
+  GP_TRY(workspace_budget(workspace_bytes, &budget));
+  const int64_t npiv = std::min(n, SB_PIVOT);
+  int64_t cap = std::min(budget / row_bytes, n);          // rows of means the workspace holds
+  if (cap < std::min<int64_t>(n, SB_SLICE)) {
+    set_error("%s: out of memory: one slice of %lld rows needs %lld bytes of PC means; %lld bytes %s", who,
+              (long long)std::min<int64_t>(n, SB_SLICE), (long long)(std::min<int64_t>(n, SB_SLICE) * row_bytes),
+              (long long)budget, workspace_budget_name(workspace_bytes));
+    return GPEMU_ERR_HIP;
+  }
+
+  // the pair kernel's tables: the first indices that occur (one grid plane each) and every pair's slot
+  SobolPairMeanArgs pg;
+  int nz = 0;
+  if (po) {
+    for (int e = 0; e < SB_MAXD * SB_MAXD; ++e) pg.slot[e] = -1;
+    bool seen[SB_MAXD] = {};
+    for (int64_t q = 0; q < P; ++q) {
+      const int i = po->pairs[2 * q], j = po->pairs[2 * q + 1];
+      pg.slot[i * SB_MAXD + j] = (short)q;
+      seen[i] = true;
+    }
+    for (int i = 0; i < SB_MAXD; ++i)
+      if (seen[i]) pg.first[nz++] = (unsigned char)i;
+  }
+
+  DevScope sc(st);
+  double *Z = nullptr, *part = nullptr, *dpivot = nullptr, *dout = nullptr, *part2 = nullptr, *dout2 = nullptr;
+  int64_t *dstart = nullptr, *dfirst = nullptr;
+  GP_TRY(sc.alloc(&Z, std::max(cap * (d + 2 + P), 2 * npiv) * k));
+  GP_TRY(sc.alloc(&part, nslices * stride));
+  GP_TRY(sc.alloc(&dpivot, k));
+  GP_TRY(sc.alloc(&dout, T * stride));
+  GP_TRY(sc.alloc(&dstart, nslices + 1));
+  GP_TRY(sc.alloc(&dfirst, T + 1));
+  if (po) {
+    GP_TRY(sc.alloc(&part2, nslices * stride2));
+    GP_TRY(sc.alloc(&dout2, T * stride2));
+  }
+  GP_TRY(upload(dstart, start.data(), nslices + 1, st));
+  GP_TRY(upload(dfirst, first.data(), T + 1, st));
+
+  const bool own = !po;                                    // count in enum gpemu_sobol_path
+  auto count_call = [&](int path) { own ? sobol_path_count(path) : sobol_pairs_path_count(path); };   // same order
+  static_assert((int)GPEMU_SOBOL_PAIRS_PATH_CALL == (int)GPEMU_SOBOL_PATH_CALL &&
+                (int)GPEMU_SOBOL_PAIRS_PATH_CHUNK == (int)GPEMU_SOBOL_PATH_CHUNK &&
+                (int)GPEMU_SOBOL_PAIRS_PATH_WHOLE == (int)GPEMU_SOBOL_PATH_WHOLE, "the two enums share their head");
+  count_call(GPEMU_SOBOL_PATH_CALL);
+  // the pivot: the means of the first npiv rows of A and B
+  SobolMeanArgs g;
+  g.A = dA; g.B = dB; g.r0 = 0; g.nr = npiv; g.Z = Z; g.zs = npiv; g.base_only = 1;
+  GP_TRY(launch_sobol_mean(m, g, st, own));
+  hipLaunchKernelGGL(sobol_pivot_kernel, dim3((unsigned)k), dim3(256), 0, st, Z, npiv, npiv, (int)k, dpivot);
+  GP_HIP(hipGetLastError());
+
+  int64_t nchunks = 0;
+  for (int64_t s0 = 0; s0 < nslices;) {
+    int64_t s1 = s0 + 1;                                   // whole slices while their rows fit
+    while (s1 < nslices && start[(size_t)s1 + 1] - start[(size_t)s0] <= cap) ++s1;
+    const int64_t row0 = start[(size_t)s0], nr = start[(size_t)s1] - row0;
+    count_call(GPEMU_SOBOL_PATH_CHUNK);
+    ++nchunks;
+    g = SobolMeanArgs();
+    g.A = dA; g.B = dB; g.r0 = row0; g.nr = nr; g.Z = Z; g.zs = nr;
+    GP_TRY(launch_sobol_mean(m, g, st, own));
+    SobolSliceArgs a;
+    a.Z = Z; a.zs = nr; a.row0 = row0; a.start = dstart; a.s0 = s0; a.pivot = dpivot; a.part = part; a.stride = stride;
+    a.d = (int)d; a.k = (int)k;
+    SobolPairSliceArgs a2;
+    if (po) {
+      pg.A = dA; pg.B = dB; pg.r0 = row0; pg.nr = nr; pg.Z = Z + (d + 2) * nr * k; pg.Z1 = Z; pg.zs = nr;
+      GP_TRY(launch_sobol_pair_mean(m, pg, nz, st));
+      a2.Z = Z; a2.zs = nr; a2.row0 = row0; a2.start = dstart; a2.pivot = dpivot; a2.part = part2; a2.stride = stride2;
+      a2.d = (int)d; a2.k = (int)k; a2.np = (int)P;
+    }
+    for (int64_t c0 = s0; c0 < s1; c0 += 32768) {          // grid.x
+      const int64_t nc = std::min<int64_t>(32768, s1 - c0);
+      a.s0 = c0;
+      hipLaunchKernelGGL(sobol_matrix_kernel, dim3((unsigned)nc, (unsigned)(1 + 2 * d), (unsigned)((k * k + 255) / 256)),
+                         dim3(256), 0, st, a);
+      GP_HIP(hipGetLastError());
+      hipLaunchKernelGGL(sobol_vector_kernel, dim3((unsigned)nc, (unsigned)(2 + d)), dim3(64), 0, st, a);
+      GP_HIP(hipGetLastError());
+      if (po) {
+        a2.s0 = c0;
+        hipLaunchKernelGGL(sobol_pair_matrix_kernel, dim3((unsigned)nc, (unsigned)(2 * P), (unsigned)((k * k + 255) / 256)),
+                           dim3(256), 0, st, a2);
+        GP_HIP(hipGetLastError());
+        hipLaunchKernelGGL(sobol_pair_vector_kernel, dim3((unsigned)nc, (unsigned)P), dim3(64), 0, st, a2);
+        GP_HIP(hipGetLastError());
+      }
+    }
+    s0 = s1;
+  }
+  if (nchunks == 1) count_call(GPEMU_SOBOL_PATH_WHOLE);
+  for (int64_t t0 = 0; t0 < T; t0 += 32768) {              // grid.y
+    const int64_t nt = std::min<int64_t>(32768, T - t0);
+    hipLaunchKernelGGL(sobol_combine_kernel, dim3((unsigned)((stride + 255) / 256), (unsigned)nt), dim3(256), 0, st, part,
+                       stride, dfirst + t0, dout + t0 * stride);
+    GP_HIP(hipGetLastError());
+    if (po) {
+      hipLaunchKernelGGL(sobol_combine_kernel, dim3((unsigned)((stride2 + 255) / 256), (unsigned)nt), dim3(256), 0, st,
+                         part2, stride2, dfirst + t0, dout2 + t0 * stride2);
+      GP_HIP(hipGetLastError());
+    }
+  }
+
+  std::vector<double> host((size_t)(T * stride)), host2((size_t)(T * stride2));
+  GP_TRY(sc.download(host.data(), dout, T * stride));
+  if (po) GP_TRY(sc.download(host2.data(), dout2, T * stride2));
+  GP_TRY(sc.download(o.pivot, dpivot, k));
+  GP_HIP(hipStreamSynchronize(st));
+  const int64_t kk = k * k;
+  for (int64_t t = 0; t < T; ++t) {
+    const double *h = host.data() + t * stride;
+    std::copy(h, h + kk, o.C2 + t * kk);
+    std::copy(h + kk, h + (1 + d) * kk, o.M + t * d * kk);
+    std::copy(h + (1 + d) * kk, h + (1 + 2 * d) * kk, o.D + t * d * kk);
+    const double *v = h + (1 + 2 * d) * kk;
+    std::copy(v, v + k, o.sumA + t * k);
+    std::copy(v + k, v + 2 * k, o.sumB + t * k);
+    std::copy(v + 2 * k, v + (2 + d) * k, o.sumD + t * d * k);
+    if (po) {
+      const double *h2 = host2.data() + t * stride2;
+      std::copy(h2, h2 + P * kk, po->M2 + t * P * kk);
+      std::copy(h2 + P * kk, h2 + 2 * P * kk, po->D2 + t * P * kk);
+      std::copy(h2 + 2 * P * kk, h2 + 2 * P * kk + P * k, po->sumD2 + t * P * k);
+    }
+  }
+  return GPEMU_OK;
 }
 
 }  // namespace gpemu
@@ -343,93 +689,8 @@ int gpemu_sobol_moments_dev(gpemu_model *m, int64_t n, const double *dA, const d
   GP_TRY(sobol_check_model(m));
   GP_HIP(hipSetDevice(m->device));
   hipStream_t st = stream ? (hipStream_t)stream : m->stream;
-  const int64_t d = m->d, k = m->k, T = n_batches;
-  const int64_t stride = sobol_part_stride(d, k), row_bytes = (d + 2) * k * 8;
-
-  std::vector<int64_t> start, first;
-  sobol_slices(n, T, start, first);
-  const int64_t nslices = (int64_t)start.size() - 1;
-  for (int64_t t = 0; t < T; ++t) count[t] = start[(size_t)first[(size_t)t + 1]] - start[(size_t)first[(size_t)t]];
-
-  int64_t budget = 0;
-  GP_TRY(workspace_budget(workspace_bytes, &budget));
-  const int64_t npiv = std::min(n, SB_PIVOT);
-  int64_t cap = std::min(budget / row_bytes, n);          // rows of means the workspace holds
-  if (cap < std::min<int64_t>(n, SB_SLICE)) {
-    set_error("sobol_moments: out of memory: one slice of %lld rows needs %lld bytes of PC means; %lld bytes %s",
-              (long long)std::min<int64_t>(n, SB_SLICE), (long long)(std::min<int64_t>(n, SB_SLICE) * row_bytes),
-              (long long)budget, workspace_budget_name(workspace_bytes));
-    return GPEMU_ERR_HIP;
-  }
-
-  DevScope sc(st);
-  double *Z = nullptr, *part = nullptr, *dpivot = nullptr, *dout = nullptr;
-  int64_t *dstart = nullptr, *dfirst = nullptr;
-  GP_TRY(sc.alloc(&Z, std::max(cap * (d + 2), 2 * npiv) * k));
-  GP_TRY(sc.alloc(&part, nslices * stride));
-  GP_TRY(sc.alloc(&dpivot, k));
-  GP_TRY(sc.alloc(&dout, T * stride));
-  GP_TRY(sc.alloc(&dstart, nslices + 1));
-  GP_TRY(sc.alloc(&dfirst, T + 1));
-  GP_TRY(upload(dstart, start.data(), nslices + 1, st));
-  GP_TRY(upload(dfirst, first.data(), T + 1, st));
-
-  sobol_path_count(GPEMU_SOBOL_PATH_CALL);
-  // the pivot: the means of the first npiv rows of A and B
-  SobolMeanArgs g;
-  g.A = dA; g.B = dB; g.r0 = 0; g.nr = npiv; g.Z = Z; g.zs = npiv; g.base_only = 1;
-  GP_TRY(launch_sobol_mean(m, g, st));
-  hipLaunchKernelGGL(sobol_pivot_kernel, dim3((unsigned)k), dim3(256), 0, st, Z, npiv, npiv, (int)k, dpivot);
-  GP_HIP(hipGetLastError());
-
-  int64_t nchunks = 0;
-  for (int64_t s0 = 0; s0 < nslices;) {
-    int64_t s1 = s0 + 1;                                   // whole slices while their rows fit
-    while (s1 < nslices && start[(size_t)s1 + 1] - start[(size_t)s0] <= cap) ++s1;
-    const int64_t row0 = start[(size_t)s0], nr = start[(size_t)s1] - row0;
-    sobol_path_count(GPEMU_SOBOL_PATH_CHUNK);
-    ++nchunks;
-    g = SobolMeanArgs();
-    g.A = dA; g.B = dB; g.r0 = row0; g.nr = nr; g.Z = Z; g.zs = nr;
-    GP_TRY(launch_sobol_mean(m, g, st));
-    SobolSliceArgs a;
-    a.Z = Z; a.zs = nr; a.row0 = row0; a.start = dstart; a.s0 = s0; a.pivot = dpivot; a.part = part; a.stride = stride;
-    a.d = (int)d; a.k = (int)k;
-    for (int64_t c0 = s0; c0 < s1; c0 += 32768) {          // grid.x
-      const int64_t nc = std::min<int64_t>(32768, s1 - c0);
-      a.s0 = c0;
-      hipLaunchKernelGGL(sobol_matrix_kernel, dim3((unsigned)nc, (unsigned)(1 + 2 * d), (unsigned)((k * k + 255) / 256)),
-                         dim3(256), 0, st, a);
-      GP_HIP(hipGetLastError());
-      hipLaunchKernelGGL(sobol_vector_kernel, dim3((unsigned)nc, (unsigned)(2 + d)), dim3(64), 0, st, a);
-      GP_HIP(hipGetLastError());
-    }
-    s0 = s1;
-  }
-  if (nchunks == 1) sobol_path_count(GPEMU_SOBOL_PATH_WHOLE);
-  for (int64_t t0 = 0; t0 < T; t0 += 32768) {              // grid.y
-    const int64_t nt = std::min<int64_t>(32768, T - t0);
-    hipLaunchKernelGGL(sobol_combine_kernel, dim3((unsigned)((stride + 255) / 256), (unsigned)nt), dim3(256), 0, st, part,
-                       stride, dfirst + t0, dout + t0 * stride);
-    GP_HIP(hipGetLastError());
-  }
-
-  std::vector<double> host((size_t)(T * stride));
-  GP_TRY(sc.download(host.data(), dout, T * stride));
-  GP_TRY(sc.download(pivot, dpivot, k));
-  GP_HIP(hipStreamSynchronize(st));
-  const int64_t kk = k * k;
-  for (int64_t t = 0; t < T; ++t) {
-    const double *h = host.data() + t * stride;
-    std::copy(h, h + kk, C2 + t * kk);
-    std::copy(h + kk, h + (1 + d) * kk, M + t * d * kk);
-    std::copy(h + (1 + d) * kk, h + (1 + 2 * d) * kk, D + t * d * kk);
-    const double *v = h + (1 + 2 * d) * kk;
-    std::copy(v, v + k, sumA + t * k);
-    std::copy(v + k, v + 2 * k, sumB + t * k);
-    std::copy(v + 2 * k, v + (2 + d) * k, sumD + t * d * k);
-  }
-  return GPEMU_OK;
+  SobolOut o{pivot, count, sumA, sumB, C2, sumD, M, D};
+  return sobol_moments_run(m, n, dA, dB, n_batches, workspace_bytes, o, nullptr, st);
 }
 
 int gpemu_sobol_moments(gpemu_model *m, int64_t n, const double *A, const double *B, int64_t n_batches,
@@ -450,6 +711,44 @@ int gpemu_sobol_moments(gpemu_model *m, int64_t n, const double *A, const double
   GP_TRY(upload(dA, A, n * d, st));
   GP_TRY(upload(dB, B, n * d, st));
   return gpemu_sobol_moments_dev(m, n, dA, dB, n_batches, workspace_bytes, pivot, count, sumA, sumB, C2, sumD, M, D, st);
+}
+
+int gpemu_sobol_pairs_path_counts(int64_t *out, int64_t n) { return read_path_counts(PATHS_SOBOL_PAIRS, out, n); }
+
+int gpemu_sobol_moments_pairs(gpemu_model *m, int64_t n, const double *A, const double *B, int64_t n_batches,
+                              int64_t n_pairs, const int32_t *pairs, int64_t workspace_bytes, double *pivot,
+                              int64_t *count, double *sumA, double *sumB, double *C2, double *sumD, double *M, double *D,
+                              double *sumD2, double *M2, double *D2) {
+  GP_ARG(m && A && B && pairs, "null pointer");
+  GP_ARG(pivot && count && sumA && sumB && C2 && sumD && M && D && sumD2 && M2 && D2, "null output pointer");
+  GP_ARG(n >= 1, "n must be >= 1");
+  GP_ARG(n_batches >= 1 && n_batches <= n, "n_batches must be in 1 .. n");
+  GP_ARG(workspace_bytes >= 0, "workspace_bytes must be >= 0");
+  GP_TRY(sobol_check_model(m));
+  const int64_t d = m->d;
+  GP_ARG(d >= 2, "a pair needs a model of d >= 2 parameters");
+  GP_ARG(n_pairs >= 1 && n_pairs <= d * (d - 1) / 2, "n_pairs must be in 1 .. d (d - 1) / 2");
+  bool asked[SB_MAXD * SB_MAXD] = {};
+  for (int64_t q = 0; q < n_pairs; ++q) {
+    const int64_t i = pairs[2 * q], j = pairs[2 * q + 1];
+    GP_ARG(i >= 0 && j >= 0 && i < d && j < d, "a pair's index is outside 0 .. d - 1");
+    GP_ARG(i < j, "a pair must be given as i < j");
+    GP_ARG(!asked[i * SB_MAXD + j], "a pair is repeated");
+    asked[i * SB_MAXD + j] = true;
+  }
+  GP_ARG(sobol_all_finite(A, n * d) && sobol_all_finite(B, n * d), "A or B contains NaN or infinity");
+  GP_HIP(hipSetDevice(m->device));
+  hipStream_t st = m->stream;
+  DevScope sc(st);
+  double *dA = nullptr, *dB = nullptr;
+  GP_TRY(sc.alloc(&dA, n * d));
+  GP_TRY(sc.alloc(&dB, n * d));
+  GP_TRY(upload(dA, A, n * d, st));
+  GP_TRY(upload(dB, B, n * d, st));
+  SobolOut o{pivot, count, sumA, sumB, C2, sumD, M, D};
+  SobolPairOut po;
+  po.np = n_pairs; po.pairs = pairs; po.sumD2 = sumD2; po.M2 = M2; po.D2 = D2;
+  return sobol_moments_run(m, n, dA, dB, n_batches, workspace_bytes, o, &po, st);
 }
 
 }  // extern "C"

@@ -170,6 +170,9 @@ _SIGNATURES = {
     "gpemu_sobol_moments": (C.c_int, [C.c_void_p, c_i64, C.c_void_p, C.c_void_p, c_i64, c_i64] + [C.c_void_p] * 8),
     "gpemu_sobol_moments_dev": (C.c_int, [C.c_void_p, c_i64, C.c_void_p, C.c_void_p, c_i64, c_i64] + [C.c_void_p] * 9),
     "gpemu_sobol_path_counts": (C.c_int, [C.POINTER(c_i64), c_i64]),
+    "gpemu_sobol_moments_pairs": (C.c_int, [C.c_void_p, c_i64, C.c_void_p, C.c_void_p, c_i64, c_i64, C.c_void_p, c_i64]
+                                  + [C.c_void_p] * 11),
+    "gpemu_sobol_pairs_path_counts": (C.c_int, [C.POINTER(c_i64), c_i64]),
     "gpemu_marginal_hist": (C.c_int, [C.c_int, c_i64, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, c_i64,
                                       C.c_void_p, C.c_void_p, C.c_void_p]),
     "gpemu_marginal_hist_dev": (C.c_int, [C.c_int, C.c_void_p, c_i64, c_i64, c_i64, C.c_int, C.c_int, C.c_void_p, C.c_int,

@@ -342,12 +342,45 @@ class DeviceModel:
         out["n"], out["n_batches"] = n, T
         return out
 
-    def sobol_indices(self, A, B, n_batches=16, workspace_bytes=0):
+    def sobol_moments_pairs(self, A, B, pairs=None, n_batches=16, workspace_bytes=0):
+        """``sobol_moments`` (the same bytes) and the moments of the pair rows ``AB_ij`` = A with columns i < j from B
+        (DESIGN.md §4.45): ``pairs`` (P, 2), ``sumD2`` (T, P, k), ``M2`` and ``D2`` (T, P, k, k) as include/gpemu.h
+        defines them.  ``pairs=None``: all i < j in the order of ``gpemu.marginals.pair_indices``.  The workspace holds
+        8 (d + 2 + P) k bytes per base row; the result, bit for bit, does not depend on it nor on which other pairs
+        are asked for."""
+        from . import sensitivity
+        A, B = self._base_pair(A, B)
+        n, T, d, k = A.shape[0], int(n_batches), self.d, self.k
+        pairs = sensitivity.check_pairs(pairs, d)
+        if not 1 <= T <= n:
+            raise ValueError(f"n_batches must be in 1 .. n = {n}, got {n_batches}")
+        P = pairs.shape[0]
+        p32 = np.ascontiguousarray(pairs, dtype=np.int32)
+        out = {"pivot": np.empty(k), "count": np.empty(T, dtype=np.int64), "sumA": np.empty((T, k)),
+               "sumB": np.empty((T, k)), "C2": np.empty((T, k, k)), "sumD": np.empty((T, d, k)),
+               "M": np.empty((T, d, k, k)), "D": np.empty((T, d, k, k)), "sumD2": np.empty((T, P, k)),
+               "M2": np.empty((T, P, k, k)), "D2": np.empty((T, P, k, k))}
+        check(_lib.lib().gpemu_sobol_moments_pairs(
+            self._h, n, ptr(A), ptr(B), T, P, ptr(p32), int(workspace_bytes),
+            *[ptr(out[key]) for key in ("pivot", "count", "sumA", "sumB", "C2", "sumD", "M", "D", "sumD2", "M2", "D2")]))
+        out["n"], out["n_batches"], out["pairs"] = n, T, pairs
+        return out
+
+    def sobol_indices(self, A, B, n_batches=16, workspace_bytes=0, second_order=False, pairs=None):
         """First-order and total-effect Sobol' indices of every feature over the rows of ``A`` and ``B``, with
         batch-means standard errors: ``gpemu.sensitivity.indices_from_moments`` of ``sobol_moments`` with the
-        components and the scaler the model was created with."""
+        components and the scaler the model was created with.  ``second_order=True`` adds the keys of
+        ``gpemu.sensitivity.pair_indices_from_moments`` for ``pairs`` (None: all i < j) from ``sobol_moments_pairs``;
+        the first-order keys keep their bytes."""
         from . import sensitivity
-        return sensitivity.indices_from_moments(self.sobol_moments(A, B, n_batches, workspace_bytes), *self._projection)
+        if not second_order:
+            if pairs is not None:
+                raise ValueError("pairs needs second_order=True")
+            return sensitivity.indices_from_moments(self.sobol_moments(A, B, n_batches, workspace_bytes), *self._projection)
+        mom = self.sobol_moments_pairs(A, B, pairs, n_batches, workspace_bytes)
+        out = sensitivity.indices_from_moments(mom, *self._projection)
+        out.update(sensitivity.pair_indices_from_moments(mom, *self._projection))
+        return out
 
     def likelihood_setup(self, y_exp, y_err, lo, hi, n_div=1.0, block_start=None, cov=None, sys_sources=None):
         """Data, box prior and the observable block boundaries of this group (``block_start`` =

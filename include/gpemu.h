@@ -779,6 +779,50 @@ enum gpemu_sobol_path {
 /* out[0 .. min(n, GPEMU_SOBOL_PATH_COUNT)) = the counters; returns GPEMU_SOBOL_PATH_COUNT (or GPEMU_ERR_ARG). */
 int gpemu_sobol_path_counts(int64_t *out, int64_t n);
 
+/* ---- second-order Sobol' indices: the pair rows AB_ij --------------------------------------------------
+ * Where T_if - S_if is clearly above zero, parameter i acts on bin f through interactions; these moments say with
+ * which other parameter.  For a pair i < j the row AB_ij is row A with columns i and j from B, and with the notation
+ * above (z the PC means, c the returned pivot) D_ij = z(AB_ij) - z(A).  Per batch t, about the pivot:
+ *   sumD2[T*P*k]    per pair: sum D_ij
+ *   M2[T*P*k*k]     per pair: sum (zB - c) D_ij^T    (the first-order estimator applied to the pair row)
+ *   D2[T*P*k*k]     per pair: sum D_ij D_ij^T        (Jansen's, for the total effect of the pair)
+ * in the order of `pairs` [n_pairs][2] (i < j < d, no repeats).  Re-centred on the host exactly as M_i and D_i are
+ * (gpemu.sensitivity.pair_indices_from_moments), per feature f with V_f the variance:
+ *   closed pair index   Sc_ij,f = s_f^2 c_f^T M_ij c_f / V_f          (Saltelli et al. 2010)
+ *   interaction index   S_ij,f  = Sc_ij,f - S_i,f - S_j,f
+ *   total of the pair   T_ij,f  = s_f^2 c_f^T D_ij c_f / (2 V_f)      (Jansen 1999)
+ * The first eight outputs are gpemu_sobol_moments' of the same arguments, byte for byte.  Every pair distance is a sum
+ * of non-negative terms (for a fixed i the kernel walks j upward with a running sum; nothing is formed by
+ * cancellation); a row with a_i == b_i IS the row AB_j and takes that row's mean as the first-order pass computed it,
+ * one with a_j == b_j that of AB_i, one with both that of A: B = A gives exact zeros in sumD2, M2, D2, and a column B
+ * shares with A gives the first-order row's M and D, bit for bit.  The sums run over the slices of gpemu_sobol_moments in its fixed order: the results, bit
+ * for bit, do not depend on workspace_bytes, on the run, or on which other pairs were asked for.  workspace_bytes
+ * bounds the chunk of PC means, 8*(d+2+n_pairs)*k bytes per row (0: half of the free device memory; at least one slice
+ * of min(n, 256) rows, else GPEMU_ERR_HIP).  GPEMU_ERR_ARG, before any launch or allocation, for n < 1, n_batches
+ * outside 1 .. n, n_pairs < 1, an index outside 0 .. d-1, i >= j, a repeated pair, non-finite rows, and a model of
+ * d == 1.  A, B and every output are HOST arrays; the call works on the model's stream and waits for it. */
+int gpemu_sobol_moments_pairs(gpemu_model *m, int64_t n, const double *A, const double *B, int64_t n_batches,
+                              int64_t n_pairs, const int32_t *pairs, int64_t workspace_bytes, double *pivot,
+                              int64_t *count, double *sumA, double *sumB, double *C2, double *sumD, double *M, double *D,
+                              double *sumD2, double *M2, double *D2);
+/* Which launches of gpemu_sobol_moments_pairs ran.  A set of its own: the other sets keep their sizes and indices, and
+ * the call does not move gpemu_sobol_path_counts. */
+enum gpemu_sobol_pairs_path {
+  GPEMU_SOBOL_PAIRS_PATH_CALL = 0,   /* one gpemu_sobol_moments_pairs                                                 */
+  GPEMU_SOBOL_PAIRS_PATH_CHUNK,      /* one chunk of rows through the workspace                                       */
+  GPEMU_SOBOL_PAIRS_PATH_WHOLE,      /* a call whose rows all fitted one chunk                                        */
+  GPEMU_SOBOL_PAIRS_PATH_DP8,        /* a launch of the pair-row mean kernel, 8-wide instance (d <= 8)                */
+  GPEMU_SOBOL_PAIRS_PATH_DP16,       /* ... 16-wide instance (9 <= d <= 16)                                           */
+  GPEMU_SOBOL_PAIRS_PATH_KIND0,      /* ... by base kernel: RBF / nu = inf, then Matern 0.5, 1.5, 2.5, general nu     */
+  GPEMU_SOBOL_PAIRS_PATH_KIND1,
+  GPEMU_SOBOL_PAIRS_PATH_KIND2,
+  GPEMU_SOBOL_PAIRS_PATH_KIND3,
+  GPEMU_SOBOL_PAIRS_PATH_KIND4,
+  GPEMU_SOBOL_PAIRS_PATH_COUNT
+};
+/* out[0 .. min(n, GPEMU_SOBOL_PAIRS_PATH_COUNT)) = the counters; returns GPEMU_SOBOL_PAIRS_PATH_COUNT (or GPEMU_ERR_ARG). */
+int gpemu_sobol_pairs_path_counts(int64_t *out, int64_t n);
+
 /* ---- marginal posteriors: histograms, highest-density intervals, kernel density ----------------------
  * The data of a corner plot from the WHOLE chain, where it lies: what ref: plot_mcmc.py _plot_posterior_pairplot draws
  * from a subsample (a Gaussian KDE of every parameter, every pair of parameters, the shaded highest-density interval)
